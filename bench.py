@@ -5,7 +5,7 @@ A "step" = one pass of the hot path over one minibatch: random_batch index draw 
 one full SAC gradient step (rlkit_custom.py:234-238 of the reference), with the replay buffer
 already resident in HBM when the timed region starts.
 
-    python bench.py --gpus N --steps K --warmup W
+    python bench.py --gpus N --steps K --warmup W [--dump-outputs DIR]
 
 N = 1: BASELINE.json configs[1] (Lift-Panda-OSC-POSE: obs 42 / act 7, batch 256, 1e6-slot buffer, full).
 N > 1: one independent replica per GPU (independent seed of the same workload; `--sweep` runs the
@@ -114,6 +114,31 @@ def build_replica(task, O, A, B, n_buf, seed, device):
     fill_buffer(buf, n_buf, O, A, 1234 + seed)
     buf.seed(seed)
     return trainer, buf
+
+
+DUMP_LIMIT_BYTES = 64 << 20
+
+
+def dump_outputs(dirname, first, last, trainer=None):
+    """--dump-outputs DIR: what the timed train_loop call computed, as DIR/<name>.npy -- the diagnostics it returned
+    (its first and its last step) and the trainer state its last step left on the device (every network's parameters,
+    the Adam moments, the scalars: log_alpha, ...).  float32 as computed; the scalars are float64 on the device."""
+    arrays = {"diag_first": first, "diag_last": last}
+    if trainer is not None:
+        st = trainer.state_dict()
+        for net, p in st["params"].items():
+            arrays[f"params_{net}"] = p
+        for net, (m, v) in st["opt"].items():
+            arrays[f"adam_m_{net}"], arrays[f"adam_v_{net}"] = m, v
+        arrays["scalars"] = st["scalars"]
+    arrays = {k: np.ascontiguousarray(v, np.float64 if np.asarray(v).dtype == np.float64 else np.float32)
+              for k, v in arrays.items()}
+    total = sum(a.nbytes for a in arrays.values())
+    if total > DUMP_LIMIT_BYTES:
+        raise SystemExit(f"--dump-outputs: {total} bytes exceed the {DUMP_LIMIT_BYTES}-byte limit")
+    os.makedirs(dirname, exist_ok=True)
+    for name, a in arrays.items():
+        np.save(os.path.join(dirname, name + ".npy"), a)
 
 
 def measure_peaks(device):
@@ -237,6 +262,8 @@ def td3_main(args):
     first, last = tr.train_loop(buf, args.steps, batch_size=B)
     tr._lib.sac_sync(tr._h)
     el = time.perf_counter() - t0
+    if args.dump_outputs:                          # (before the stepwise data point trains on)
+        dump_outputs(args.dump_outputs, first, last, tr)
     for _ in range(50):
         tr.train(buf.random_batch(B))
     tr._lib.sac_sync(tr._h)
@@ -429,6 +456,9 @@ def main():
                     help="with --replicas-per-gpu R: replica i owns 8/R XCDs (CU-masked streams) and keeps the fused step if it fits them")
     ap.add_argument("--replicas-per-gpu", type=int, default=0,
                     help="N=1 only: also time R concurrent independent runs on the GPU (reported beside, never as, value)")
+    ap.add_argument("--dump-outputs", type=str, default=None, metavar="DIR",
+                    help="after the timed steps, write what the timed call computed (diagnostics of its first and last "
+                         "step, the trainer state after its last step) as DIR/<name>.npy; rank 0 only")
     args = ap.parse_args()
 
     if args.agent == "TD3":
@@ -506,6 +536,8 @@ def main():
     elapsed_max = parallel.max_over_ranks(dist, elapsed)
     # the only collective of the job: per-GPU result vectors (steps/s, last losses, alpha) all-gathered
     per_gpu = parallel.gather_results(dist, [args.steps / elapsed, float(last[0]), float(last[1]), float(last[28])])
+    if args.dump_outputs and rank == 0:            # (before device_report: its profiled replay trains on)
+        dump_outputs(args.dump_outputs, first, last, None if args.dry_run else trainer)
 
     out = None
     if rank == 0:

@@ -92,3 +92,38 @@ def test_two_ranks_share_the_one_gpu_of_this_box():
     d = json.loads([l for l in p.stdout.splitlines() if l.strip().startswith("{")][0])
     assert d["n_gpus"] == 2 and len(d["per_gpu"]) == 2 and d["value"] > 0
     assert all(x[1] == x[1] for x in d["per_gpu"])          # finite losses from both ranks
+
+
+def test_dump_outputs_writes_the_timed_calls_diagnostics(tmp_path):
+    """--dump-outputs DIR: the arrays the timed call returned land as DIR/<name>.npy (here: the dry run's diagnostics)."""
+    p = run_bench("--gpus", "1", "--dry-run", "--steps", "3", "--warmup", "1", "--dump-outputs", str(tmp_path / "out"))
+    assert p.returncode == 0, p.stderr[-2000:]
+    d = json.loads(p.stdout.strip())
+    assert d["steps"] == 3 and d["ms_per_step"] > 0
+    import numpy as np
+    last = np.load(tmp_path / "out" / "diag_last.npy")
+    assert last.dtype == np.float32 and last.shape == (32,)
+    assert float(last[0]) == d["final"]["QF1 Loss"] and float(last[28]) == d["final"]["Alpha"]
+    assert sorted(os.listdir(tmp_path / "out")) == ["diag_first.npy", "diag_last.npy"]
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("agent", ["SAC", "TD3"])
+def test_dump_outputs_on_real_kernels(tmp_path, agent):
+    """The dump holds the timed call's last diagnostics (the JSON line's "final") and the trainer state its last step
+    left: every network's parameters and Adam moments, the scalars -- float32 / float64, 64 MB at most."""
+    import numpy as np
+    out = tmp_path / "out"
+    p = run_bench("--gpus", "1", "--agent", agent, "--steps", "40", "--warmup", "5", "--buffer", "20000",
+                  "--no-cpu-baseline", "--no-stepwise", "--no-peaks", "--dump-outputs", str(out), timeout=900)
+    assert p.returncode == 0, p.stderr[-3000:]
+    d = json.loads([l for l in p.stdout.splitlines() if l.strip().startswith("{")][0])
+    assert d["steps"] == 40 and d["ms_per_step"] > 0
+    arrays = {f[:-4]: np.load(out / f) for f in os.listdir(out)}
+    assert float(arrays["diag_last"][0]) == d["final"]["QF1 Loss"]
+    nets = ["policy", "qf1", "qf2", "target_qf1", "target_qf2"] + (["target_policy"] if agent == "TD3" else [])
+    assert {f"params_{n}" for n in nets} <= set(arrays)
+    assert {f"adam_{mv}_{n}" for mv in "mv" for n in ("policy", "qf1", "qf2")} <= set(arrays)
+    assert arrays["params_policy"].size == (80398 if agent == "SAC" else 78599) and arrays["params_qf1"].size == 78849
+    assert all(a.dtype in (np.float32, np.float64) and np.all(np.isfinite(a)) for a in arrays.values())
+    assert sum(a.nbytes for a in arrays.values()) <= 64 << 20
