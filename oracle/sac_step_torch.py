@@ -70,10 +70,12 @@ def init_sac_params(obs_dim: int, act_dim: int, hidden=(256, 256), seed: int = 0
 
 
 class _Net(torch.nn.Module):
-    def __init__(self, layers):
+    def __init__(self, layers, dtype=torch.float32):
         super().__init__()
-        self.ws = torch.nn.ParameterList([torch.nn.Parameter(torch.from_numpy(np.array(w))) for w, _ in layers])
-        self.bs = torch.nn.ParameterList([torch.nn.Parameter(torch.from_numpy(np.array(b))) for _, b in layers])
+        # (float32 parameters are exact in float64: a float64 net holds the same values)
+        cast = (lambda x: x) if dtype == torch.float32 else (lambda x: x.to(dtype))
+        self.ws = torch.nn.ParameterList([torch.nn.Parameter(cast(torch.from_numpy(np.array(w)))) for w, _ in layers])
+        self.bs = torch.nn.ParameterList([torch.nn.Parameter(cast(torch.from_numpy(np.array(b)))) for _, b in layers])
 
     def export(self):
         return [(w.detach().numpy().copy(), b.detach().numpy().copy()) for w, b in zip(self.ws, self.bs)]
@@ -119,10 +121,18 @@ class PolicyNet(_Net):
 
 
 def _stats(prefix, t):
-    """eval_util.create_stats_ordered_dict: Mean / Std (population) / Max / Min."""
-    a = t.detach().numpy().astype(np.float32).ravel()
+    """eval_util.create_stats_ordered_dict: Mean / Std (population) / Max / Min (in float64 for a float64 oracle)."""
+    a = t.detach().numpy()
+    a = (a if a.dtype == np.float64 else a.astype(np.float32)).ravel()
     return OrderedDict([(prefix + " Mean", float(np.mean(a))), (prefix + " Std", float(np.std(a))),
                         (prefix + " Max", float(np.max(a))), (prefix + " Min", float(np.min(a)))])
+
+
+def _as_tensor(dtype):
+    """numpy -> float32 tensor (the batch as the step sees it), then cast to `dtype` only if that is another type."""
+    if dtype == torch.float32:
+        return lambda x: torch.from_numpy(np.ascontiguousarray(x, dtype=np.float32))
+    return lambda x: torch.from_numpy(np.ascontiguousarray(x, dtype=np.float32)).to(dtype)
 
 
 class RlkitEquivalentSAC:
@@ -130,15 +140,18 @@ class RlkitEquivalentSAC:
 
     def __init__(self, nets, act_dim, discount=0.99, reward_scale=1.0, policy_lr=1e-3, qf_lr=1e-3,
                  soft_target_tau=1e-2, target_update_period=1, use_automatic_entropy_tuning=True,
-                 target_entropy=None):
-        self.policy = PolicyNet(nets["policy"])
-        self.qf1, self.qf2 = QNet(nets["qf1"]), QNet(nets["qf2"])
-        self.target_qf1, self.target_qf2 = QNet(nets["target_qf1"]), QNet(nets["target_qf2"])
+                 target_entropy=None, dtype=torch.float32):
+        """dtype: torch.float64 gives the float64 twin of the same step (the checkers' yardstick): parameters, log_alpha and
+        every input are cast up from their float32 values, the arithmetic is the same."""
+        self.dtype = dtype
+        self.policy = PolicyNet(nets["policy"], dtype)
+        self.qf1, self.qf2 = QNet(nets["qf1"], dtype), QNet(nets["qf2"], dtype)
+        self.target_qf1, self.target_qf2 = QNet(nets["target_qf1"], dtype), QNet(nets["target_qf2"], dtype)
         self.discount, self.reward_scale = float(discount), float(reward_scale)
         self.tau, self.period = float(soft_target_tau), int(target_update_period)
         self.auto_alpha = bool(use_automatic_entropy_tuning)
         self.target_entropy = float(-act_dim if target_entropy is None else target_entropy)  # [D] = -prod(act shape)
-        self.log_alpha = torch.zeros(1, requires_grad=True)
+        self.log_alpha = torch.zeros(1, requires_grad=True, dtype=dtype)
         self.alpha_opt = torch.optim.Adam([self.log_alpha], lr=policy_lr)
         self.policy_opt = torch.optim.Adam(self.policy.parameters(), lr=policy_lr)
         self.qf1_opt = torch.optim.Adam(self.qf1.parameters(), lr=qf_lr)
@@ -150,7 +163,7 @@ class RlkitEquivalentSAC:
     def step(self, obs, act, rew, term, next_obs, eps1, eps2):
         """All inputs float32 numpy: obs (B,O) act (B,A) rew (B,1) term (B,1) next_obs (B,O)
         eps1/eps2 (B,A).  Returns the diagnostics of this step (always computed)."""
-        t = lambda x: torch.from_numpy(np.ascontiguousarray(x, dtype=np.float32))
+        t = _as_tensor(self.dtype)
         obs, act, rew, term, next_obs, eps1, eps2 = map(t, (obs, act, rew.reshape(-1, 1), term.reshape(-1, 1),
                                                            next_obs, eps1, eps2))
         # 1-3: policy on s
@@ -164,7 +177,7 @@ class RlkitEquivalentSAC:
             alpha = self.log_alpha.exp()
         else:
             alpha_loss = torch.zeros(())
-            alpha = torch.ones(1)
+            alpha = torch.ones(1, dtype=self.dtype)
         # 7-8: actor loss
         q1_new, q2_new = self.qf1(obs, a_new), self.qf2(obs, a_new)
         q_new = torch.min(q1_new, q2_new)

@@ -33,7 +33,7 @@ from collections import OrderedDict
 import numpy as np
 import torch
 
-from .sac_step_torch import QNet, _Net, _stats, init_mlp_params
+from .sac_step_torch import QNet, _as_tensor, _Net, _stats, init_mlp_params
 
 
 def init_td3_params(obs_dim, act_dim, hidden=(256, 256), seed=0):
@@ -58,10 +58,12 @@ class TanhMlp(_Net):
 class RlkitEquivalentTD3:
     def __init__(self, nets, act_dim, target_policy_noise=0.2, target_policy_noise_clip=0.5, discount=0.99,
                  reward_scale=1.0, policy_learning_rate=1e-3, qf_learning_rate=1e-3,
-                 policy_and_target_update_period=2, tau=0.005):
-        self.policy, self.target_policy = TanhMlp(nets["policy"]), TanhMlp(nets["target_policy"])
-        self.qf1, self.qf2 = QNet(nets["qf1"]), QNet(nets["qf2"])
-        self.target_qf1, self.target_qf2 = QNet(nets["target_qf1"]), QNet(nets["target_qf2"])
+                 policy_and_target_update_period=2, tau=0.005, dtype=torch.float32):
+        """dtype: torch.float64 gives the float64 twin of the same step (see RlkitEquivalentSAC)."""
+        self.dtype = dtype
+        self.policy, self.target_policy = TanhMlp(nets["policy"], dtype), TanhMlp(nets["target_policy"], dtype)
+        self.qf1, self.qf2 = QNet(nets["qf1"], dtype), QNet(nets["qf2"], dtype)
+        self.target_qf1, self.target_qf2 = QNet(nets["target_qf1"], dtype), QNet(nets["target_qf2"], dtype)
         self.noise, self.clip = float(target_policy_noise), float(target_policy_noise_clip)
         self.discount, self.reward_scale = float(discount), float(reward_scale)
         self.period, self.tau = int(policy_and_target_update_period), float(tau)
@@ -74,7 +76,7 @@ class RlkitEquivalentTD3:
     def step(self, obs, act, rew, term, next_obs, eps):
         """float32 numpy inputs; eps (B,A) = the N(0,1) draw of the target-policy smoothing noise.
         Returns the statistics of this step (always computed)."""
-        t = lambda x: torch.from_numpy(np.ascontiguousarray(x, dtype=np.float32))
+        t = _as_tensor(self.dtype)
         obs, act, rew, term, next_obs, eps = map(t, (obs, act, rew.reshape(-1, 1), term.reshape(-1, 1), next_obs, eps))
         with torch.no_grad():
             a2 = self.target_policy(next_obs)

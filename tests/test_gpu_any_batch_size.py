@@ -6,7 +6,7 @@ import pytest
 
 from robosuite_benchmark_amd import EnvReplayBuffer
 from robosuite_benchmark_amd._lib import DIAG_NAMES, TD3_DIAG_NAMES
-from tests.helpers import make_pair, make_td3_pair, rel_err, synth_transitions
+from tests.helpers import check_step_f64, make_pair, make_td3_pair, rel_err, synth_transitions
 
 pytestmark = pytest.mark.gpu
 
@@ -20,9 +20,10 @@ def _batch(B, O, A, seed):
 
 @pytest.mark.parametrize("O,A,B", [(42, 7, 100), (42, 7, 1), (11, 3, 17), (46, 7, 250), (89, 14, 300), (10, 2, 530)])
 def test_sac_step_any_batch_size(O, A, B):
-    oracle, hip = make_pair(O, A, B, seed=11)
+    oracle, hip, o64 = make_pair(O, A, B, seed=11, with_f64=True)
     nb, eps = _batch(B, O, A, 21)
     want = oracle.step(nb["observations"], nb["actions"], nb["rewards"], nb["terminals"], nb["next_observations"], *eps)
+    want64 = o64.step(nb["observations"], nb["actions"], nb["rewards"], nb["terminals"], nb["next_observations"], *eps)
     diag = hip.train(nb, eps=eps)
     for i, name in enumerate(DIAG_NAMES):
         if name in want:
@@ -36,6 +37,7 @@ def test_sac_step_any_batch_size(O, A, B):
         ref = np.concatenate([np.concatenate([w.ravel(), b.ravel()]) for w, b in zip(ws, bs)])
         got = hip.debug_fetch(g, ref.size)
         assert np.max(np.abs(got - ref)) <= 5e-5 * max(1e-30, np.max(np.abs(ref))), g
+    check_step_f64(hip, oracle, o64, diag, want, want64)
 
 
 def test_td3_step_and_loops_with_an_odd_batch_size():

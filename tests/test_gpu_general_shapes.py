@@ -8,7 +8,7 @@ import pickle
 import numpy as np
 import pytest
 
-from tests.helpers import TASK_DIMS, flat_of, make_pair, rel_err, synth_transitions
+from tests.helpers import TASK_DIMS, check_step_f64, flat_of, make_pair, rel_err, synth_transitions
 from tests.test_gpu_sac_step import TOL, batch_and_noise, check_diag, scale_err
 
 pytestmark = pytest.mark.gpu
@@ -21,7 +21,7 @@ SHAPES = [((512, 512), None, "Lift", 256), ((256, 256, 256), None, "Door", 128),
 @pytest.mark.parametrize("hidden,hidden_q,task,B", SHAPES)
 def test_steps_against_the_oracle(hidden, hidden_q, task, B):
     O, A = TASK_DIMS[task]
-    oracle, hip = make_pair(O, A, B, seed=11, hidden=hidden, hidden_q=hidden_q)
+    oracle, hip, o64 = make_pair(O, A, B, seed=11, hidden=hidden, hidden_q=hidden_q, with_f64=True)
     assert hip.fused_mode() == 3
     for s_ in range(5):
         np_batch, eps = batch_and_noise(B, O, A, seed=700 + s_, term_frac=0.05)
@@ -41,6 +41,9 @@ def test_steps_against_the_oracle(hidden, hidden_q, task, B):
             ws, bs = L[key][:len(L[key]) // 2], L[key][len(L[key]) // 2:]
             ref = np.concatenate([np.concatenate([w.ravel(), b.ravel()]) for w, b in zip(ws, bs)])
             assert scale_err(hip.debug_fetch(key, ref.size), ref) < 5e-5, key
+        want64 = o64.step(np_batch["observations"], np_batch["actions"], np_batch["rewards"], np_batch["terminals"],
+                          np_batch["next_observations"], *eps)
+        check_step_f64(hip, oracle, o64, diag, want, want64)
     # parameters, Adam moments and the entropy coefficient after five steps.  Where a gradient is ~0 Adam's early steps move
     # a weight by ~lr whatever its sign: compare at a fraction of what five steps can move
     st, after = hip.state_dict(), oracle.export_nets()
@@ -184,7 +187,7 @@ def test_td3_steps_against_the_oracle(hidden, task, B):
     from tests.helpers import make_td3_pair
     from tests.test_gpu_td3 import batch_and_noise as td3_batch, check_diag as td3_check
     O, A = TASK_DIMS[task]
-    oracle, hip = make_td3_pair(O, A, B, seed=11, hidden=hidden, policy_and_target_update_period=2)
+    oracle, hip, o64 = make_td3_pair(O, A, B, seed=11, hidden=hidden, policy_and_target_update_period=2, with_f64=True)
     assert hip.fused_mode() == 3
     for s_ in range(5):
         nb, eps = td3_batch(B, O, A, seed=300 + s_)
@@ -201,6 +204,8 @@ def test_td3_steps_against_the_oracle(hidden, task, B):
             assert rel_err(hip.debug_fetch(name, B), ref.detach().numpy().ravel()) < 2e-5, name
         for g_ in ("g_qf1", "g_qf2", "g_policy"):
             assert scale_err(hip.debug_fetch(g_, L[g_].size), L[g_]) < 5e-5, g_
+        want64 = o64.step(nb["observations"], nb["actions"], nb["rewards"], nb["terminals"], nb["next_observations"], eps)
+        check_step_f64(hip, oracle, o64, diag, want, want64)
     nets, got = oracle.export_nets(), hip.state_dict()
     for name, lr in (("qf1", 5e-4), ("qf2", 5e-4), ("policy", 1e-3)):
         d = np.abs(got["params"][name] - flat_of(nets[name]))
@@ -290,13 +295,17 @@ def test_general_trainers_share_a_gpu_and_move_between_xcds():
 def test_extreme_shapes_against_the_oracle(hidden, hidden_q, O, A, B):
     """The corners of what sac_trainer_create_mlp accepts: one unit, seven layers, 4096 units, the widest observation and
     action the slots hold, odd widths around the tile and vector sizes -- two steps against the oracle."""
-    oracle, hip = make_pair(O, A, B, seed=9, hidden=hidden, hidden_q=hidden_q)
+    oracle, hip, o64 = make_pair(O, A, B, seed=9, hidden=hidden, hidden_q=hidden_q, with_f64=True)
     assert hip.fused_mode() == 3
     for s_ in range(2):
         np_batch, eps = batch_and_noise(B, O, A, seed=40 + s_, term_frac=0.1)
-        want = oracle.step(np_batch["observations"], np_batch["actions"], np_batch["rewards"], np_batch["terminals"],
-                           np_batch["next_observations"], *eps)
-        check_diag(hip.train(np_batch, eps=eps), want, tol=1e-4 if s_ else TOL)
+        args = (np_batch["observations"], np_batch["actions"], np_batch["rewards"], np_batch["terminals"],
+                np_batch["next_observations"], *eps)
+        want = oracle.step(*args)
+        diag = hip.train(np_batch, eps=eps)
+        check_diag(diag, want, tol=1e-4 if s_ else TOL)
+        if s_ == 0:
+            check_step_f64(hip, oracle, o64, diag, want, o64.step(*args))
     L = oracle.last
     for key in ("g_policy", "g_qf1", "g_qf2"):
         ws, bs = L[key][:len(L[key]) // 2], L[key][len(L[key]) // 2:]

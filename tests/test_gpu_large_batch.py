@@ -7,7 +7,7 @@ import numpy as np
 import pytest
 
 from robosuite_benchmark_amd._lib import DIAG_NAMES
-from tests.helpers import make_pair, rel_err, synth_transitions
+from tests.helpers import check_step_f64, make_pair, rel_err, synth_transitions
 
 pytestmark = pytest.mark.gpu
 
@@ -76,16 +76,18 @@ def test_chain_step_against_the_four_launch_step(O, A, B):
 
 @pytest.mark.parametrize("task,O,A,B", [("Door", 46, 7, 1024), ("TwoArmLift", 89, 14, 1024), ("Lift", 42, 7, 2048)])
 def test_chain_step_against_the_oracle(task, O, A, B):
-    oracle, hip = _with_env(dict(SAC_CHAIN=1), lambda: make_pair(O, A, B, seed=3))
+    oracle, hip, o64 = _with_env(dict(SAC_CHAIN=1), lambda: make_pair(O, A, B, seed=3, with_f64=True))
     assert hip.fused_mode() in (2, 4)
     obs, act, rew, term, nobs = synth_transitions(B, O, A, seed=11, term_frac=0.05)
     rs = np.random.RandomState(2)
     eps = (rs.normal(size=(B, A)).astype(np.float32), rs.normal(size=(B, A)).astype(np.float32))
     batch = dict(observations=obs, actions=act, rewards=rew, terminals=term.astype(np.float32), next_observations=nobs)
-    for _ in range(2):
+    for it in range(2):
         want = oracle.step(obs, act, rew, term.astype(np.float32), nobs, *eps)
         got = hip.train(batch, eps=eps)
         hip.end_epoch(0)
+        if it == 0:
+            check_step_f64(hip, oracle, o64, got, want, o64.step(obs, act, rew, term.astype(np.float32), nobs, *eps))
         for i, name in enumerate(DIAG_NAMES):
             assert abs(got[i] - want[name]) <= 1e-5 * max(1.0, abs(want[name])), (name, got[i], want[name])   # north_star: 1e-5
         L = oracle.last
