@@ -319,6 +319,27 @@ int64_t sac_debug_fetch(sac_trainer_t *t, const char *name, float *out, int64_t 
 int sac_policy_mirror(sac_trainer_t *t);
 int sac_policy_act(sac_trainer_t *t, const float *obs, int deterministic, const float *eps, float *act);
 
+/* ------------------------------------------------------------------------------------------
+ * Trainer groups: several runs of one configuration (the reference's seed sweeps, /root/reference/launch_jobs.sh)
+ * stepped together.  A group holds 1..SAC_GROUP_MAX existing SAC trainers that share obs_dim, act_dim, batch (at most
+ * 256 rows), hidden sizes (two layers of at most 256 units) and device; their hyperparameters and noise seeds may differ.
+ * sac_group_train_loop runs  for _ in range(n_steps): batch_r = buffers[r].random_batch(B); trainer_r.train(batch_r)
+ * for every member r at once: one grouped index draw and one grouped gather per chunk, four grouped launches per step
+ * (the four-launch step of every member, fused ones included).  Each member's result -- weights, Adam state, scalars,
+ * diagnostics, the generator of its buffer -- is bit for bit that of sac_train_loop(members[r], buffers[r], n_steps),
+ * and the members stay ordinary trainers: every sac_* entry point sees the trained state afterwards.  Members must
+ * outlive the group; destroying the group leaves them as they are.  Refused (error, nothing changed): TD3 or
+ * general-step members, batches above 256, members confined by sac_trainer_set_xcd[_mask], the same trainer or buffer
+ * twice, buffers of other dims, empty buffers.
+ * diag_first / diag_last (may be NULL): [n_members][SAC_DIAG_N], the first and last step of each member.
+ * ------------------------------------------------------------------------------------------ */
+enum { SAC_GROUP_MAX = 16 };
+typedef struct sac_group sac_group_t;
+int sac_group_create(sac_group_t **out, sac_trainer_t *const *members, int n_members);
+int sac_group_destroy(sac_group_t *g);
+int sac_group_train_loop(sac_group_t *g, sac_buffer_t *const *buffers, int64_t n_steps, float *diag_first,
+                         float *diag_last);
+
 #ifdef __cplusplus
 }
 #endif

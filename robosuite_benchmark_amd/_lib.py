@@ -109,6 +109,9 @@ SYMBOLS = {
     "sac_debug_fetch": (C.c_int64, [_P, C.c_char_p, _P, C.c_int64]),
     "sac_policy_mirror": (C.c_int, [_P]),
     "sac_policy_act": (C.c_int, [_P, _P, C.c_int, _P, _P]),
+    "sac_group_create": (C.c_int, [C.POINTER(_P), _P, C.c_int]),
+    "sac_group_destroy": (C.c_int, [_P]),
+    "sac_group_train_loop": (C.c_int, [_P, _P, C.c_int64, _P, _P]),
 }
 
 _lib = None

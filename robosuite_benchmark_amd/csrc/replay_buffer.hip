@@ -37,8 +37,8 @@ const char *last_error() { return g_err.c_str(); }
 // ------------------------------------------------------------------------------------------
 // Output j goes to out[(j / bt) * bp + j % bt]: batches of bt indices stored at a stride of bp >= bt (the row-block
 // padding of a batch whose size is not a multiple of 16; the pad entries keep a valid index and are never drawn).
-__global__ __launch_bounds__(256) void k_mt_randint(MtState *st, uint32_t rng, uint32_t mask, int64_t count,
-                                                    int64_t *__restrict__ out, int bt, int bp) {
+__device__ __forceinline__ void mt_randint_body(MtState *st, uint32_t rng, uint32_t mask, int64_t count,
+                                                int64_t *__restrict__ out, int bt, int bp) {
     __shared__ uint32_t mt[2][MT_N];
     __shared__ int s_cnt[2][12];
     __shared__ int s_newpos;
@@ -112,6 +112,21 @@ __global__ __launch_bounds__(256) void k_mt_randint(MtState *st, uint32_t rng, u
     for (int i = tid; i < MT_N; i += 256) st->mt[i] = mt[cur][i];
     if (tid == 0) st->pos = pos;
 }
+__global__ __launch_bounds__(256) void k_mt_randint(MtState *st, uint32_t rng, uint32_t mask, int64_t count,
+                                                    int64_t *__restrict__ out, int bt, int bp) {
+    mt_randint_body(st, rng, mask, count, out, bt, bp);
+}
+
+// Grouped draw (sac_group_train_loop): workgroup r draws n_batches x bt indices from generator r, exactly as
+// k_mt_randint would on its own.  A buffer of one row (rng == 0) consumes no draws (NumPy): its indices are all zero.
+__global__ __launch_bounds__(256) void k_mt_randint_group(const SampleMember *__restrict__ M, int64_t n_batches, int bt, int bp) {
+    const SampleMember &m = M[blockIdx.x];
+    if (m.rng == 0) {
+        for (int64_t i = threadIdx.x; i < (int64_t)bp * n_batches; i += 256) m.out[i] = 0;
+        return;
+    }
+    mt_randint_body(m.st, m.rng, m.mask, (int64_t)bt * n_batches, m.out, bt, bp);
+}
 
 // ------------------------------------------------------------------------------------------
 // k_gather: persistent 256-thread workgroups, each moving 16-row blocks of minibatch slots:
@@ -154,9 +169,9 @@ __device__ __forceinline__ void lds_barrier() { asm volatile("s_waitcnt lgkmcnt(
     } while (0)
 
 template <int NIT>      // obs 16-B chunks per thread: ceil(16 * (Ost/4) / 256)
-__global__ __launch_bounds__(256) void k_gather(ReplayView rv, const int64_t *__restrict__ idx, int B,
-                                                int64_t n_blocks_total, float *__restrict__ slots,
-                                                SlotLayout L, int write_saT) {
+__device__ __forceinline__ void gather_body(const ReplayView &rv, const int64_t *__restrict__ idx, int B,
+                                            int64_t n_blocks_total, float *__restrict__ slots,
+                                            const SlotLayout &L, int write_saT) {
     extern __shared__ __attribute__((aligned(16))) float lds[];
     const int Ost = rv.Ost, Ast = rv.Ast, O = rv.O, A = rv.A;
     float *t_obs = lds;                       // [16][Ost]
@@ -307,6 +322,21 @@ __global__ __launch_bounds__(256) void k_gather(ReplayView rv, const int64_t *__
             write_out(blk + stride, oB, nB, aB, sB, s2B);
         }
     }
+}
+template <int NIT>
+__global__ __launch_bounds__(256) void k_gather(ReplayView rv, const int64_t *__restrict__ idx, int B,
+                                                int64_t n_blocks_total, float *__restrict__ slots,
+                                                SlotLayout L, int write_saT) {
+    gather_body<NIT>(rv, idx, B, n_blocks_total, slots, L, write_saT);
+}
+
+// Grouped gather (sac_group_train_loop): member blockIdx.y gathers its own indices from its own buffer into its own
+// slots; each member keeps the x-extent and block map of a solo launch.
+template <int NIT>
+__global__ __launch_bounds__(256) void k_gather_group(const GatherMember *__restrict__ M, int B, int64_t n_blocks_total,
+                                                      SlotLayout L, int write_saT) {
+    const GatherMember &m = M[blockIdx.y];
+    gather_body<NIT>(m.rv, m.idx, B, n_blocks_total, m.slots, L, write_saT);
 }
 #undef GATHER_LOAD_IDX
 #undef GATHER_ISSUE_ROWS
@@ -534,6 +564,34 @@ int launch_gather(sac_buffer *b, const int64_t *d_idx, int batch, int64_t n_batc
 #define SAC_GATHER_LAUNCH(N)                                                                               \
     hipLaunchKernelGGL(k_gather<N>, dim3(grid), dim3(256), lds, q, b->view(), d_idx, batch, nblk, \
                        d_slots, L, write_saT)
+    if (nit <= 1) SAC_GATHER_LAUNCH(1);
+    else if (nit <= 2) SAC_GATHER_LAUNCH(2);
+    else if (nit <= 4) SAC_GATHER_LAUNCH(4);
+    else SAC_GATHER_LAUNCH(8);
+#undef SAC_GATHER_LAUNCH
+    SAC_HIP(hipGetLastError());
+    return 0;
+}
+
+int launch_sample_group(const SampleMember *d_tab, int R, int batch, int64_t n_batches, hipStream_t on) {
+    SAC_REQUIRE(R > 0 && batch > 0 && n_batches > 0, "bad grouped draw");
+    hipLaunchKernelGGL(k_mt_randint_group, dim3(R), dim3(256), 0, on, d_tab, n_batches, batch, round_up(batch, RB));
+    SAC_HIP(hipGetLastError());
+    return 0;
+}
+
+int launch_gather_group(const GatherMember *d_tab, int R, const sac_buffer *shape, int batch, int64_t n_batches,
+                        const SlotLayout &L, int write_saT, hipStream_t on) {
+    SAC_REQUIRE(batch > 0 && batch % RB == 0, "batch size %d must be a positive multiple of %d", batch, RB);
+    const int64_t nblk = (int64_t)(batch / RB) * n_batches;
+    SAC_REQUIRE(nblk < (1LL << 30), "too many rows in one gather launch");
+    const int grid = (int)(nblk < 1024 ? nblk : 1024);          // (the x-extent of a solo launch_gather)
+    const size_t lds = sizeof(float) * (size_t)(2 * RB * shape->Ost + RB * shape->Ast);
+    SAC_REQUIRE(lds <= 64 * 1024, "observation rows too wide for the gather tile (%zu B LDS)", lds);
+    const int nit = (RB * (shape->Ost >> 2) + 255) / 256;
+    SAC_REQUIRE(nit <= 8, "observation rows too wide for the gather kernel (obs_dim %d)", shape->O);
+#define SAC_GATHER_LAUNCH(N) \
+    hipLaunchKernelGGL(k_gather_group<N>, dim3(grid, R), dim3(256), lds, on, d_tab, batch, nblk, L, write_saT)
     if (nit <= 1) SAC_GATHER_LAUNCH(1);
     else if (nit <= 2) SAC_GATHER_LAUNCH(2);
     else if (nit <= 4) SAC_GATHER_LAUNCH(4);

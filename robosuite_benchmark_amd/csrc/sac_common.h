@@ -180,6 +180,18 @@ struct sac_buffer {
     ReplayView view() const { return ReplayView{obs, act, rew, term, nobs, O, A, Ost, Ast, capacity}; }
 };
 
+// grouped draw / gather (sac_group_train_loop): one entry per member buffer, in device memory
+struct SampleMember {
+    sac::MtState *st;
+    int64_t *out;                 // the member's indices (padded layout of launch_sample)
+    uint32_t rng, mask;           // size - 1 and its bit mask (rng == 0: a one-row buffer, no draws)
+};
+struct GatherMember {
+    ReplayView rv;
+    const int64_t *idx;
+    float *slots;
+};
+
 // slot of a live device batch (sac_random_batch_device token), or -1 with the error set (internal)
 extern "C" int sac_ring_slot_of(sac_buffer *b, int64_t token);
 extern "C" int sac_make_xcd_stream(hipStream_t *out, int xcd);
@@ -194,6 +206,10 @@ int launch_sample(sac_buffer *b, int batch, int64_t n_batches, int64_t idx_offse
                   hipStream_t on = nullptr);
 int launch_gather(sac_buffer *b, const int64_t *d_idx, int batch, int64_t n_batches, float *d_slots,
                   const SlotLayout &L, int write_saT, hipStream_t on = nullptr);
+// grouped forms of the two (tables in device memory, R members of one shape): ONE launch each for all R buffers
+int launch_sample_group(const SampleMember *d_tab, int R, int batch, int64_t n_batches, hipStream_t on);
+int launch_gather_group(const GatherMember *d_tab, int R, const sac_buffer *shape, int batch, int64_t n_batches,
+                        const SlotLayout &L, int write_saT, hipStream_t on);
 // undo the stepwise interface's read-ahead (see sac_buffer::ra_ahead); to be called in front of anything that reads or
 // changes the generator's state, the buffer's rows or its size
 int readahead_rollback(sac_buffer *b);

@@ -504,6 +504,15 @@ __device__ __forceinline__ float philox_normal(unsigned long long seed, unsigned
 __device__ __forceinline__ float bellman_target(float reward_scale, float r, float term, float discount, float tq) {
     return fmaf(reward_scale, r, __fmul_rn(__fmul_rn(1.0f - term, discount), tq));
 }
+// Polyak average target (1 - tau) + online tau: the contraction the weight-gradient launch has always made (the FMA on the
+// target's term), spelled out -- the grouped launch, which reads tau from a table, picked the other one.
+__device__ __forceinline__ float polyak_mix(float t, float p, float tau) { return fmaf(t, 1.0f - tau, __fmul_rn(p, tau)); }
+__device__ __forceinline__ f32x4 polyak_mix4(f32x4 t, f32x4 p, float tau) {
+    f32x4 o;
+#pragma unroll
+    for (int i = 0; i < 4; ++i) o[i] = polyak_mix(t[i], p[i], tau);
+    return o;
+}
 __device__ __forceinline__ float actor_da(float da1, float dq1, float da2, float dq2) { return fmaf(da1, dq1, __fmul_rn(da2, dq2)); }
 // d/dz of (alpha log_pi - min Q) through a = tanh(z): da (1 - a^2) + (alpha/B) 2 a (1 - a^2) / (1 - a^2 + eps)
 __device__ __forceinline__ float actor_dz(float da, float om, float alpha_invB, float act) {
@@ -628,9 +637,9 @@ __device__ __forceinline__ void slice_epilogue(const f32x4 (&acc)[NTW], const fl
 
 // MODE M_TD3_CRITIC: the policy blocks run the TARGET policy on s' (sq == 1) and, only when `aux` is set (policy
 // steps), the online policy on s (sq == 0); the Q blocks are the same.
+// (the body of launch A: k_fwd_a below, and the grouped entry k_fwd_a_group further down, which runs it for many trainers)
 template <int NTH, bool WIDE, int SP, int MODE = M_SAC>
-__global__ __launch_bounds__(256) void k_fwd_a(Dev d, const float *__restrict__ S, SlotLayout SL, int aux) {
-    kernarg_prefetch<sizeof(Dev) + 8 + sizeof(SlotLayout) + 4>();
+__device__ __forceinline__ void fwd_a_body(const Dev &d, const float *__restrict__ S, const SlotLayout &SL, int aux) {
     constexpr int NTW = 4 / SP, SW = 64 * NTW;               // tiles per wave, slice width
     extern __shared__ __attribute__((aligned(16))) float lds[];
     const int B = d.B, O = d.O, A = d.A, NB = d.NB;
@@ -745,13 +754,17 @@ __global__ __launch_bounds__(256) void k_fwd_a(Dev d, const float *__restrict__ 
     }
     STAMP(0, 4);
 }
+template <int NTH, bool WIDE, int SP, int MODE = M_SAC>
+__global__ __launch_bounds__(256) void k_fwd_a(Dev d, const float *__restrict__ S, SlotLayout SL, int aux) {
+    kernarg_prefetch<sizeof(Dev) + 8 + sizeof(SlotLayout) + 4>();
+    fwd_a_body<NTH, WIDE, SP, MODE>(d, S, SL, aux);
+}
 
 // MODE M_TD3_CRITIC: target-net blocks only (grid 2*SP*NB); the head is the TARGET policy's tanh(mean) on s' plus the
 // clipped smoothing noise.  MODE M_TD3_ACTOR: Q1(s, policy(s)) blocks only (grid SP*NB) with the unit-gradient tail;
 // the head is tanh(mean) of the online policy on s.
 template <int NTH, bool WIDE, int SP, int MODE = M_SAC>
-__global__ __launch_bounds__(256) void k_fwd_b(Dev d, const float *__restrict__ S, SlotLayout SL, StepArg sa) {
-    kernarg_prefetch<sizeof(Dev) + 8 + sizeof(SlotLayout) + sizeof(StepArg)>();
+__device__ __forceinline__ void fwd_b_body(const Dev &d, const float *__restrict__ S, const SlotLayout &SL, const StepArg &sa) {
     constexpr int NTW = 4 / SP, SW = 64 * NTW;
     extern __shared__ __attribute__((aligned(16))) float lds[];
     const int B = d.B, O = d.O, A = d.A, NB = d.NB;
@@ -1003,6 +1016,11 @@ __global__ __launch_bounds__(256) void k_fwd_b(Dev d, const float *__restrict__ 
         splitk_reduce<1>(acc, nullptr, red, d.dapart + (((size_t)p4 * SP + part) * B + row0) * 16, 16);
     }
     STAMP(1, 7);
+}
+template <int NTH, bool WIDE, int SP, int MODE = M_SAC>
+__global__ __launch_bounds__(256) void k_fwd_b(Dev d, const float *__restrict__ S, SlotLayout SL, StepArg sa) {
+    kernarg_prefetch<sizeof(Dev) + 8 + sizeof(SlotLayout) + sizeof(StepArg)>();
+    fwd_b_body<NTH, WIDE, SP, MODE>(d, S, SL, sa);
 }
 
 // ------------------------------------------------------------------------------------------
@@ -1269,8 +1287,7 @@ __device__ __forceinline__ void policy_bwd_block(const Dev &d, const StepArg &sa
 // {6,7} idle: an XCD's L2 pulls one network's transposed weights); larger batches use every CU instead.
 // MODE M_TD3_CRITIC: critic blocks only (grid: whole groups of eight, b % 8 in {0..3} -> Q1, {4..7} -> Q2); M_TD3_ACTOR: policy blocks only.
 template <int NTH, int SP, int MODE = M_SAC>
-__global__ __launch_bounds__(256) void k_bwd(Dev d, const float *__restrict__ S, SlotLayout SL, StepArg sa, int compact) {
-    kernarg_prefetch<sizeof(Dev) + 8 + sizeof(SlotLayout) + sizeof(StepArg)>();
+__device__ __forceinline__ void bwd_body(const Dev &d, const float *__restrict__ S, const SlotLayout &SL, const StepArg &sa, int compact) {
     if constexpr (MODE == M_TD3_CRITIC) {
         const int bq = 4 * (blockIdx.x >> 3) + (blockIdx.x & 3);
         if (bq >= SP * d.NB) return;         // (grid rounded up to whole groups of four blocks per twin: see k_fwd_b)
@@ -1285,6 +1302,11 @@ __global__ __launch_bounds__(256) void k_bwd(Dev d, const float *__restrict__ S,
         if (cls < 2) critic_bwd_block<SP>(d, S, SL, sa, cls, b);
         else policy_bwd_block<NTH, SP>(d, sa, b);
     }
+}
+template <int NTH, int SP, int MODE = M_SAC>
+__global__ __launch_bounds__(256) void k_bwd(Dev d, const float *__restrict__ S, SlotLayout SL, StepArg sa, int compact) {
+    kernarg_prefetch<sizeof(Dev) + 8 + sizeof(SlotLayout) + sizeof(StepArg)>();
+    bwd_body<NTH, SP, MODE>(d, S, SL, sa, compact);
 }
 
 // ------------------------------------------------------------------------------------------
@@ -1553,7 +1575,7 @@ __device__ __forceinline__ void dw_adam_body(const Dev &d, const DwTable &T, con
             __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
             const f32x4 pf = ld4(tw + r * 16 + 4 * g);                      // this lane as (c', g') of the forward copy
             st4_sc1(J.P + pblk, pf);
-            if (polyak) st4_sc1(J.TP + pblk, tp4 * (1.0f - d.tau) + pf * d.tau);
+            if (polyak) st4_sc1(J.TP + pblk, polyak_mix4(tp4, pf, d.tau));
         }
         if (bias_lane) {
             const int n = n0 + threadIdx.x;
@@ -1561,7 +1583,7 @@ __device__ __forceinline__ void dw_adam_body(const Dev &d, const DwTable &T, con
             adam_update(pb, mbv, vbv, gb, step_size, bc2s);
             st1g(J.bias + n, pb); st1g(J.mb + n, mbv); st1g(J.vb + n, vbv);
             if (J.gb && keep_grad) st1g(J.gb + n, gb);
-            if (polyak) st1g(J.Tbias + n, tbv * (1.0f - d.tau) + pb * d.tau);
+            if (polyak) st1g(J.Tbias + n, polyak_mix(tbv, pb, d.tau));
         }
         STAMP(4 - 2 * (sa.loop_pos & 1), 2);
     } else if (aborted) {
@@ -1699,6 +1721,46 @@ __global__ __launch_bounds__(256) void k_dw_adam(Dev d, DwTable T, const float *
     dw_adam_body(d, T, S, sa, red, redb, trs, (int)blockIdx.x, aborted);
 }
 
+// ------------------------------------------------------------------------------------------
+// Grouped step (sac_group_train_loop): the four launches of R trainers of one shape as four launches.  The member is
+// blockIdx.y; inside a member the x-extent and the block -> work map are those of its solo launch (the XCD affinity
+// stays), and the bodies are the very functions the solo entries above run.  Each member's arguments come from a table
+// in device memory (uniform index: scalar loads) instead of the kernel argument segment; the per-step StepArg is a
+// [step][R] table the host writes once per chunk (bc1 / bc2s stay host-computed doubles).  No workgroup waits for
+// another one: a grouped grid may be far larger than what is resident at once.
+// ------------------------------------------------------------------------------------------
+struct GroupMember {
+    Dev d;
+    DwTable T;                     // the member's weight-gradient table (abort = null: the four-launch step)
+    SlotLayout SL;
+    const float *slots;            // the member's loop slot 0: slot j at slots + j * SL.slot_floats
+};
+
+template <int NTH, bool WIDE, int SP>
+__global__ __launch_bounds__(256) void k_fwd_a_group(const GroupMember *__restrict__ G, int slot) {
+    const GroupMember &g = G[blockIdx.y];
+    fwd_a_body<NTH, WIDE, SP>(g.d, g.slots + (size_t)slot * g.SL.slot_floats, g.SL, 0);
+}
+template <int NTH, bool WIDE, int SP>
+__global__ __launch_bounds__(256) void k_fwd_b_group(const GroupMember *__restrict__ G, const StepArg *__restrict__ SA, int slot) {
+    const GroupMember &g = G[blockIdx.y];
+    fwd_b_body<NTH, WIDE, SP>(g.d, g.slots + (size_t)slot * g.SL.slot_floats, g.SL, SA[blockIdx.y]);
+}
+template <int NTH, int SP>
+__global__ __launch_bounds__(256) void k_bwd_group(const GroupMember *__restrict__ G, const StepArg *__restrict__ SA, int slot,
+                                                   int compact) {
+    const GroupMember &g = G[blockIdx.y];
+    bwd_body<NTH, SP>(g.d, g.slots + (size_t)slot * g.SL.slot_floats, g.SL, SA[blockIdx.y], compact);
+}
+__global__ __launch_bounds__(256) void k_dw_adam_group(const GroupMember *__restrict__ G, const StepArg *__restrict__ SA, int slot) {
+    __shared__ __attribute__((aligned(16))) float red[4 * 4 * 64 * 4];
+    __shared__ __attribute__((aligned(16))) float redb[4 * 16 * 2];
+    __shared__ __attribute__((aligned(16))) float trs[4 * 256];
+    const GroupMember &g = G[blockIdx.y];
+    if ((int)blockIdx.x > g.T.njobs) return;
+    dw_adam_body(g.d, g.T, g.slots + (size_t)slot * g.SL.slot_floats, SA[blockIdx.y], red, redb, trs, (int)blockIdx.x, 0u);
+}
+
 #include "sac_bwd8.h"
 #include "sac_fused.h"
 #include "sac_chain.h"
@@ -1743,6 +1805,7 @@ struct sac_trainer {
     float last_ms[4] = {0, 0, 0, 0};
     bool loop_primed = false;
     bool gate_exempt = false;                         // fused on CUs of its own (sac_trainer_set_xcd_mask): not serialised with other trainers
+    unsigned xcd_mask = 0xffu;                        // XCDs its launches may use (sac_trainer_set_xcd_mask; 0xff: the whole chip)
     bool timing_pending = false;                      // the last loop's event intervals have not been read yet (read lazily)
     hipEvent_t ev_tm[3] = {nullptr, nullptr, nullptr};  // around the draw and the gather of the loop's timed chunk
     std::vector<float> h_policy;                      // host mirror for acting
@@ -3135,6 +3198,7 @@ int sac_trainer_set_xcd_mask(sac_trainer_t *t, unsigned xcd_mask) {
     t->stream = ns;
     sac::stream_register(ns);
     t->pend_n = 0;
+    t->xcd_mask = xcd_mask & 0xffu;
     int cus = 0;
     SAC_HIP(hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, t->device));
     const int mine = (cus / 8) * __builtin_popcount(xcd_mask & 0xffu);
@@ -3292,6 +3356,307 @@ int sac_policy_act(sac_trainer_t *t, const float *obs, int deterministic, const 
             ls = fminf(fmaxf(ls, LOG_SIG_MIN), LOG_SIG_MAX);
             act[a] = tanhf(m + expf(ls) * eps[a]);
         }
+    }
+    return 0;
+}
+
+// ==========================================================================================
+// Trainer groups: R SAC trainers of one shape stepped together, four grouped launches per step (see GroupMember).
+// The loop is sac_train_loop's for every member at once -- same index stream per buffer, same steps, same results bit
+// for bit -- without its latency devices (no speculative next chunk, no stepwise read-ahead): chunks of LOOP_CH steps
+// alternate between the two halves of each buffer's loop slots; the draws and gathers of a chunk run on the group's
+// second stream under the steps of the previous one (unless the device's fused-launch gate is live -- another fused
+// trainer or group on the device, fused members included: then every grouped launch, draws and gathers too, is
+// serialised behind the gate's last launch, at a cost of ~0.3 ms per 256-step chunk).
+// ==========================================================================================
+struct sac_group {
+    int R = 0, device = 0;
+    sac_trainer *m[SAC_GROUP_MAX] = {};
+    hipStream_t s = nullptr, s2 = nullptr;           // steps / draws + gathers
+    hipEvent_t ev_ready[2] = {}, ev_done[2] = {}, ev_copied[2] = {}, ev_end = nullptr;
+    hipEvent_t ev_in[2 * SAC_GROUP_MAX] = {};         // the members' and the buffers' streams in front of a call
+    char *d_tab = nullptr, *h_tab = nullptr;          // device tables and their pinned host images
+    GroupMember *d_mem = nullptr, *h_mem = nullptr;   // [R]
+    SampleMember *d_smp = nullptr, *h_smp = nullptr;  // [2 halves][R]
+    GatherMember *d_gat = nullptr, *h_gat = nullptr;  // [2 halves][R]
+    StepArg *d_sa = nullptr, *h_sa = nullptr;         // [2 halves][LOOP_CH steps][R]
+    void (*fa)(const GroupMember *, int) = nullptr;
+    void (*fb)(const GroupMember *, const StepArg *, int) = nullptr;
+    void (*bw)(const GroupMember *, const StepArg *, int, int) = nullptr;
+};
+
+static void group_free(sac_group *g) {
+    if (g->s) (void)hipStreamSynchronize(g->s);
+    if (g->s2) (void)hipStreamSynchronize(g->s2);
+    for (auto &e : g->ev_ready) if (e) (void)hipEventDestroy(e);
+    for (auto &e : g->ev_done) if (e) (void)hipEventDestroy(e);
+    for (auto &e : g->ev_copied) if (e) (void)hipEventDestroy(e);
+    for (auto &e : g->ev_in) if (e) (void)hipEventDestroy(e);
+    if (g->ev_end) (void)hipEventDestroy(g->ev_end);
+    if (g->d_tab) (void)hipFree(g->d_tab);
+    if (g->h_tab) (void)hipHostFree(g->h_tab);
+    if (g->s) (void)hipStreamDestroy(g->s);
+    if (g->s2) (void)hipStreamDestroy(g->s2);
+    delete g;
+}
+
+// what a member must be (checked at creation and again in front of every call: a member may have been confined since)
+static int group_member_ok(const sac_trainer *t, int i) {
+    SAC_REQUIRE(t->algo == 0, "trainer group member %d is a TD3 trainer: groups hold SAC trainers only", i);
+    SAC_REQUIRE(!t->gen, "trainer group member %d runs the general step (hidden sizes beyond two layers of at most 256 units): "
+                "groups take the shapes of the fused kernels only", i);
+    SAC_REQUIRE(t->Bt <= 256, "trainer group member %d has batch %d: groups take batches of at most 256 rows", i, t->Bt);
+    SAC_REQUIRE(t->xcd_mask == 0xffu, "trainer group member %d is confined to XCDs (sac_trainer_set_xcd[_mask]): a group spans "
+                "the whole chip", i);
+    SAC_REQUIRE(t->SP == 4 && !t->chain && !t->bwd8, "trainer group member %d runs column split %d: groups take the "
+                "default split 4 only", i, t->SP);
+    return 0;
+}
+
+int sac_group_create(sac_group_t **out, sac_trainer_t *const *members, int n_members) {
+    SAC_REQUIRE(out && members, "null argument to sac_group_create");
+    *out = nullptr;
+    SAC_REQUIRE(n_members >= 1 && n_members <= SAC_GROUP_MAX, "a trainer group holds 1..%d members (got %d)", SAC_GROUP_MAX,
+                n_members);
+    const sac_trainer *t0 = members[0];
+    for (int i = 0; i < n_members; ++i) {
+        const sac_trainer *t = members[i];
+        SAC_REQUIRE(t != nullptr, "trainer group member %d is null", i);
+        for (int j = 0; j < i; ++j)
+            SAC_REQUIRE(members[j] != t, "trainer group members %d and %d are the same trainer", j, i);
+        if (group_member_ok(t, i)) return -1;
+        SAC_REQUIRE(t->O == t0->O && t->A == t0->A, "trainer group member %d has dims (%d,%d), member 0 (%d,%d)", i, t->O, t->A,
+                    t0->O, t0->A);
+        SAC_REQUIRE(t->Bt == t0->Bt, "trainer group member %d has batch %d, member 0 %d", i, t->Bt, t0->Bt);
+        SAC_REQUIRE(t->HP[0] == t0->HP[0] && t->HP[1] == t0->HP[1] && t->HQ[0] == t0->HQ[0] && t->HQ[1] == t0->HQ[1],
+                    "trainer group member %d has hidden sizes policy [%d,%d] qf [%d,%d], member 0 policy [%d,%d] qf [%d,%d]", i,
+                    t->HP[0], t->HP[1], t->HQ[0], t->HQ[1], t0->HP[0], t0->HP[1], t0->HQ[0], t0->HQ[1]);
+        SAC_REQUIRE(t->device == t0->device, "trainer group member %d lives on device %d, member 0 on %d", i, t->device, t0->device);
+        SAC_REQUIRE(t->fwd_a == t0->fwd_a && t->dw.njobs == t0->dw.njobs, "trainer group member %d runs another kernel variant "
+                    "than member 0", i);
+    }
+    SAC_HIP(hipSetDevice(t0->device));
+    sac_group *g = new sac_group();
+    g->R = n_members;
+    g->device = t0->device;
+    for (int i = 0; i < n_members; ++i) g->m[i] = members[i];
+    // the grouped instance of the variant the members' own four-launch step runs
+#define SAC_GROUP_PICK(NTH, W)                                                                             \
+    if (t0->fwd_a == &k_fwd_a<NTH, W, 4>) {                                                                \
+        g->fa = &k_fwd_a_group<NTH, W, 4>; g->fb = &k_fwd_b_group<NTH, W, 4>; g->bw = &k_bwd_group<NTH, 4>; \
+    }
+    SAC_GROUP_PICK(1, false) else SAC_GROUP_PICK(1, true) else SAC_GROUP_PICK(2, false) else SAC_GROUP_PICK(2, true)
+#undef SAC_GROUP_PICK
+    auto fail = [&](int rc) { group_free(g); return rc; };
+    if (!g->fa) { sac::set_error("internal: no grouped instance of the members' step kernels"); return fail(-1); }
+    auto set_lds = [](const void *fn, size_t bytes) {
+        return bytes > 64 * 1024 ? hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)bytes) : hipSuccess;
+    };
+    if (set_lds(reinterpret_cast<const void *>(g->fa), t0->lds_fa) != hipSuccess ||
+        set_lds(reinterpret_cast<const void *>(g->fb), t0->lds_fb) != hipSuccess ||
+        set_lds(reinterpret_cast<const void *>(g->bw), t0->lds_bw) != hipSuccess) {
+        sac::set_error("hipFuncSetAttribute failed for the grouped step kernels");
+        return fail(-1);
+    }
+    const int R = n_members;
+    const size_t b_mem = sizeof(GroupMember) * R, b_smp = sizeof(SampleMember) * 2 * R, b_gat = sizeof(GatherMember) * 2 * R;
+    const size_t b_sa = sizeof(StepArg) * 2 * LOOP_CH * R;
+    const size_t o_smp = (b_mem + 255) & ~(size_t)255, o_gat = o_smp + ((b_smp + 255) & ~(size_t)255);
+    const size_t o_sa = o_gat + ((b_gat + 255) & ~(size_t)255), total = o_sa + b_sa;
+    if (hipMalloc(reinterpret_cast<void **>(&g->d_tab), total) != hipSuccess ||
+        hipHostMalloc(reinterpret_cast<void **>(&g->h_tab), total, hipHostMallocDefault) != hipSuccess ||
+        hipStreamCreateWithFlags(&g->s, hipStreamNonBlocking) != hipSuccess ||
+        hipStreamCreateWithFlags(&g->s2, hipStreamNonBlocking) != hipSuccess) {
+        sac::set_error("out of device or pinned host memory for a trainer group");
+        return fail(-1);
+    }
+    for (int k = 0; k < 2; ++k)
+        if (hipEventCreateWithFlags(&g->ev_ready[k], hipEventDisableTiming) != hipSuccess ||
+            hipEventCreateWithFlags(&g->ev_done[k], hipEventDisableTiming) != hipSuccess ||
+            hipEventCreateWithFlags(&g->ev_copied[k], hipEventDisableTiming) != hipSuccess) {
+            sac::set_error("hipEventCreate failed");
+            return fail(-1);
+        }
+    for (auto &e : g->ev_in)
+        if (hipEventCreateWithFlags(&e, hipEventDisableTiming) != hipSuccess) { sac::set_error("hipEventCreate failed"); return fail(-1); }
+    if (hipEventCreateWithFlags(&g->ev_end, hipEventDisableTiming) != hipSuccess) { sac::set_error("hipEventCreate failed"); return fail(-1); }
+    g->d_mem = reinterpret_cast<GroupMember *>(g->d_tab); g->h_mem = reinterpret_cast<GroupMember *>(g->h_tab);
+    g->d_smp = reinterpret_cast<SampleMember *>(g->d_tab + o_smp); g->h_smp = reinterpret_cast<SampleMember *>(g->h_tab + o_smp);
+    g->d_gat = reinterpret_cast<GatherMember *>(g->d_tab + o_gat); g->h_gat = reinterpret_cast<GatherMember *>(g->h_tab + o_gat);
+    g->d_sa = reinterpret_cast<StepArg *>(g->d_tab + o_sa); g->h_sa = reinterpret_cast<StepArg *>(g->h_tab + o_sa);
+    {   // a tenant of the device's fused-launch gate: no fused trainer's launch may overlap the group's grids
+        FusedGate &G = g_gate[g->device & 63];
+        std::lock_guard<std::mutex> lk(G.mu);
+        if (!G.ev && hipEventCreateWithFlags(&G.ev, hipEventDisableTiming) != hipSuccess) {
+            sac::set_error("hipEventCreate failed");
+            return fail(-1);
+        }
+        G.live += 1;
+    }
+    *out = g;
+    return 0;
+}
+
+int sac_group_destroy(sac_group_t *g) {
+    if (!g) return 0;
+    (void)hipSetDevice(g->device);
+    if (g->s) (void)hipStreamSynchronize(g->s);
+    {
+        FusedGate &G = g_gate[g->device & 63];
+        std::lock_guard<std::mutex> lk(G.mu);
+        G.live -= 1;
+        if (G.last == g->s || G.last == g->s2) G.last = nullptr;
+    }
+    group_free(g);
+    return 0;
+}
+
+int sac_group_train_loop(sac_group_t *g, sac_buffer_t *const *bufs, int64_t n_steps, float *diag_first, float *diag_last) {
+    SAC_REQUIRE(g && bufs && n_steps > 0 && n_steps < (1 << 30), "bad arguments to sac_group_train_loop");
+    const int R = g->R;
+    const sac_trainer *t0 = g->m[0];
+    // every refusal comes before anything changes
+    for (int r = 0; r < R; ++r) {
+        if (group_member_ok(g->m[r], r)) return -1;
+        const sac_buffer *b = bufs[r];
+        SAC_REQUIRE(b != nullptr, "trainer group buffer %d is null", r);
+        for (int q = 0; q < r; ++q) SAC_REQUIRE(bufs[q] != b, "trainer group buffers %d and %d are the same buffer", q, r);
+        SAC_REQUIRE(b->device == g->device, "trainer group buffer %d lives on device %d, the group on %d", r, b->device, g->device);
+        SAC_REQUIRE(b->O == t0->O && b->A == t0->A, "trainer group buffer %d has dims (%d,%d), the trainers (%d,%d)", r, b->O,
+                    b->A, t0->O, t0->A);
+        SAC_REQUIRE(b->size > 0, "trainer group buffer %d is empty: random_batch on an empty replay buffer", r);
+        SAC_REQUIRE(b->size - 1 <= 0xffffffffLL, "replay buffers above 2^32 slots are not supported");
+    }
+    SAC_HIP(hipSetDevice(g->device));
+    const int Bt = t0->Bt, B = t0->B;
+    // what sac_train_loop does first, for every member and every buffer
+    for (int r = 0; r < R; ++r) {
+        sac_trainer *t = g->m[r];
+        if (t->fused && t->pend_n > 0) {          // device-batch steps nobody has verified yet: settle them first
+            if (wait_trainer_stream(t)) return -1;
+            if (recover_device_steps(t) < 0) return -1;
+        }
+        sac_buffer *b = bufs[r];
+        if (host_rng_sync_in(b)) return -1;
+        if (b->ra_ahead > 0) { if (readahead_rollback(b)) return -1; }
+        else b->ra_streak = 0;
+        if (loop_spec_drop(b)) return -1;
+        b->loop_streak = 0;
+        if (ensure_slots(b, Bt, LOOP_RING)) return -1;
+        if (ensure_idx(b, LOOP_RING * B)) return -1;
+        t->dev.eps1 = t->dev.eps2 = nullptr;
+    }
+    // Buffers bound to the SAME host generator (sac_rng_bind_host: by default every EnvReplayBuffer samples np.random)
+    // continue it one after another, as R sac_train_loop calls in member order would: buffer r starts where the previous
+    // buffer of that generator ends (its n_steps batches drawn from its own size), and the host words end at the last
+    // one's end state (host_rng_advance below runs in member order).
+    for (int r = 1; r < R; ++r) {
+        sac_buffer *b = bufs[r];
+        if (!b->host_key) continue;
+        int q = r - 1;
+        while (q >= 0 && bufs[q]->host_key != b->host_key) --q;
+        if (q < 0) continue;
+        MtState st = bufs[q]->host_seen;
+        host_rng_skip(bufs[q], st, Bt, n_steps);
+        if (host_rng_adopt(b, st)) return -1;
+    }
+    hipStream_t s = g->s, s2 = g->s2;
+    // both group streams behind everything already queued on the members' and the buffers' streams
+    for (int r = 0; r < R; ++r) {
+        SAC_HIP(hipEventRecord(g->ev_in[2 * r], g->m[r]->stream));
+        SAC_HIP(hipEventRecord(g->ev_in[2 * r + 1], bufs[r]->stream));
+        for (int k = 0; k < 2; ++k) {
+            SAC_HIP(hipStreamWaitEvent(s, g->ev_in[2 * r + k], 0));
+            SAC_HIP(hipStreamWaitEvent(s2, g->ev_in[2 * r + k], 0));
+        }
+    }
+    // the member tables of this call (the StepArg table follows chunk by chunk)
+    for (int r = 0; r < R; ++r) {
+        const sac_trainer *t = g->m[r];
+        sac_buffer *b = bufs[r];
+        GroupMember &M = g->h_mem[r];
+        M.d = t->dev;
+        M.T = t->dw;
+        M.T.abort = nullptr;                          // (the four-launch step: no fused launch can give up in front of it)
+        M.SL = b->slot;
+        M.slots = b->d_slots;
+        uint32_t rng = (uint32_t)(b->size - 1), mask = rng;
+        mask |= mask >> 1; mask |= mask >> 2; mask |= mask >> 4; mask |= mask >> 8; mask |= mask >> 16;
+        for (int h = 0; h < 2; ++h) {
+            g->h_smp[h * R + r] = SampleMember{b->d_rng, b->d_idx + (int64_t)h * LOOP_CH * B, rng, mask};
+            g->h_gat[h * R + r] = GatherMember{b->view(), b->d_idx + (int64_t)h * LOOP_CH * B,
+                                               b->d_slots + (size_t)h * LOOP_CH * b->slot.slot_floats};
+        }
+    }
+    SAC_HIP(hipMemcpyAsync(g->d_mem, g->h_mem, sizeof(GroupMember) * R, hipMemcpyHostToDevice, s2));
+    SAC_HIP(hipMemcpyAsync(g->d_smp, g->h_smp, sizeof(SampleMember) * 2 * R, hipMemcpyHostToDevice, s2));
+    SAC_HIP(hipMemcpyAsync(g->d_gat, g->h_gat, sizeof(GatherMember) * 2 * R, hipMemcpyHostToDevice, s2));
+    const int SPv = 4, NB = t0->NB;
+    const int compact = (3 * SPv * NB <= 192) ? 1 : 0;       // as launch_step
+    const int grid_ab = 4 * SPv * NB, grid_c = compact ? 4 * SPv * NB : 3 * SPv * NB, grid_d = t0->dw.njobs + 1;
+    FusedGate &G = g_gate[g->device & 63];
+    int64_t done = 0;
+    for (int c = 0; done < n_steps; ++c) {
+        const int64_t m = (n_steps - done < LOOP_CH) ? n_steps - done : LOOP_CH;
+        const int h = c & 1;
+        // the chunk's draws and gathers into half h of every buffer's loop slots, once the steps of chunk c - 2 are done there
+        if (c >= 2) SAC_HIP(hipStreamWaitEvent(s2, g->ev_done[h], 0));
+        {   // (tenants of the gate too: at R = 16 the grouped gather is 16 x 1024 workgroups that must not overlap a k_abc)
+            std::lock_guard<std::mutex> lk(G.mu);
+            const bool gate = G.live > 1;
+            if (gate && G.last && G.last != s2) SAC_HIP(hipStreamWaitEvent(s2, G.ev, 0));
+            if (launch_sample_group(g->d_smp + h * R, R, Bt, m, s2)) return -1;
+            if (launch_gather_group(g->d_gat + h * R, R, bufs[0], B, m, bufs[0]->slot, 1, s2)) return -1;
+            if (gate) { SAC_HIP(hipEventRecord(G.ev, s2)); G.last = s2; }
+        }
+        SAC_HIP(hipEventRecord(g->ev_ready[h], s2));
+        // the chunk's step arguments, computed like launch_step's (the host half is free once its last copy has run)
+        if (c >= 2 && wait_event(g->ev_copied[h])) return -1;
+        StepArg *hs = g->h_sa + (size_t)h * LOOP_CH * R;
+        for (int64_t j = 0; j < m; ++j)
+            for (int r = 0; r < R; ++r) {
+                const sac_trainer *t = g->m[r];
+                const long long k = (long long)(done + j);
+                const double tt = (double)(t->adam_t + k + 1);
+                StepArg sa{t->n_train_steps_total + k, t->adam_t + k + 1, (int)k, 0, 1.0 - std::pow(0.9, tt),
+                           std::sqrt(1.0 - std::pow(0.999, tt))};
+                sa.pad2 = (done + j == n_steps - 1) ? 2u : 0u;
+                hs[j * R + r] = sa;
+            }
+        StepArg *ds = g->d_sa + (size_t)h * LOOP_CH * R;
+        SAC_HIP(hipMemcpyAsync(ds, hs, sizeof(StepArg) * m * R, hipMemcpyHostToDevice, s));
+        SAC_HIP(hipEventRecord(g->ev_copied[h], s));
+        SAC_HIP(hipStreamWaitEvent(s, g->ev_ready[h], 0));
+        {
+            std::lock_guard<std::mutex> lk(G.mu);
+            const bool gate = G.live > 1;
+            if (gate && G.last && G.last != s) SAC_HIP(hipStreamWaitEvent(s, G.ev, 0));
+            for (int64_t j = 0; j < m; ++j) {
+                const int slot = (int)(h * LOOP_CH + j);
+                const StepArg *sa = ds + j * R;
+                hipLaunchKernelGGL(g->fa, dim3(grid_ab, R), dim3(256), t0->lds_fa, s, g->d_mem, slot);
+                hipLaunchKernelGGL(g->fb, dim3(grid_ab, R), dim3(256), t0->lds_fb, s, g->d_mem, sa, slot);
+                hipLaunchKernelGGL(g->bw, dim3(grid_c, R), dim3(256), t0->lds_bw, s, g->d_mem, sa, slot, compact);
+                hipLaunchKernelGGL(k_dw_adam_group, dim3(grid_d, R), dim3(256), 0, s, g->d_mem, sa, slot);
+            }
+            SAC_HIP(hipGetLastError());
+            if (gate) { SAC_HIP(hipEventRecord(G.ev, s)); G.last = s; }
+        }
+        SAC_HIP(hipEventRecord(g->ev_done[h], s));
+        done += m;
+    }
+    // the host mirrors of the generators follow behind the launches
+    for (int r = 0; r < R; ++r) host_rng_advance(bufs[r], Bt, n_steps);
+    SAC_HIP(hipEventRecord(g->ev_end, s));
+    if (wait_event(g->ev_end)) return -1;
+    SAC_HIP(hipStreamSynchronize(s2));
+    for (int r = 0; r < R; ++r) {
+        sac_trainer *t = g->m[r];
+        t->n_train_steps_total += n_steps;
+        t->adam_t += n_steps;
+        t->mirror_valid = false;
+        if (diag_first) memcpy(diag_first + (size_t)r * SAC_DIAG_N, t->h_diag, sizeof(float) * SAC_DIAG_N);
+        if (diag_last) memcpy(diag_last + (size_t)r * SAC_DIAG_N, t->h_diag + SAC_DIAG_N, sizeof(float) * SAC_DIAG_N);
     }
     return 0;
 }

@@ -20,6 +20,7 @@ from .checkpoint import checkpoint_exists, load_checkpoint, save_checkpoint
 from .networks import (FlattenMlp, GaussianStrategy, MakeDeterministic, PolicyWrappedWithExplorationStrategy,
                        TanhGaussianPolicy, TanhMlpPolicy)
 from .replay_buffer import EnvReplayBuffer
+from .group import SACTrainerGroup
 from .sac import SACTrainer
 from .td3 import TD3Trainer
 from .variant import env_dims, validate
@@ -123,6 +124,18 @@ def _rs_unpack(rs, d):
     rs.set_state(("MT19937", np.asarray(d["key"], np.uint32), d["pos"], d["has_gauss"], d["cached"]))
 
 
+def _progress_row(buf, trainer, expl, evalc, ak):
+    """The epoch's progress.csv columns in the reference's order, up to the time/* block."""
+    row = OrderedDict()
+    row.update(("replay_buffer/" + k, v) for k, v in buf.get_diagnostics().items())
+    row.update(("trainer/" + k, v) for k, v in trainer.get_diagnostics().items())
+    row.update(("exploration/" + k, v) for k, v in expl.get_diagnostics().items())
+    row.update(path_information(expl.epoch_paths, "exploration/"))
+    row.update(("evaluation/" + k, v) for k, v in evalc.get_diagnostics().items())
+    row.update(path_information(evalc.epoch_paths, "evaluation/", ak["expl_max_path_length"]))
+    return row
+
+
 def experiment(variant, log_dir=None, seed=1, obs_dim=None, action_dim=None, num_epochs=None, device=0,
                fused_loop=True, quiet=False, checkpoint_dir=None, resume=False):
     """variant.json -> training run.  Returns the list of progress rows (also written to
@@ -191,13 +204,7 @@ def experiment(variant, log_dir=None, seed=1, obs_dim=None, action_dim=None, num
             for _ in range(n_train):
                 trainer.train(buf.random_batch(ak["batch_size"]))
         t4 = time.time()
-        row = OrderedDict()
-        row.update(("replay_buffer/" + k, v) for k, v in buf.get_diagnostics().items())
-        row.update(("trainer/" + k, v) for k, v in trainer.get_diagnostics().items())
-        row.update(("exploration/" + k, v) for k, v in expl.get_diagnostics().items())
-        row.update(path_information(expl.epoch_paths, "exploration/"))
-        row.update(("evaluation/" + k, v) for k, v in evalc.get_diagnostics().items())
-        row.update(path_information(evalc.epoch_paths, "evaluation/", ak["expl_max_path_length"]))
+        row = _progress_row(buf, trainer, expl, evalc, ak)
         trainer.end_epoch(epoch); buf.end_epoch(epoch); expl.end_epoch(epoch); evalc.end_epoch(epoch)
         t5 = time.time()
         if checkpoint_dir:
@@ -234,3 +241,90 @@ def experiment(variant, log_dir=None, seed=1, obs_dim=None, action_dim=None, num
     if fh:
         fh.close()
     return rows
+
+
+def experiment_group(variant, seeds, log_dir=None, num_epochs=None, obs_dim=None, action_dim=None, device=0,
+                     quiet=False, resume=False):
+    """One configuration, several seeds, one process: each seed is the run ``experiment(variant, seed=s)`` would make --
+    its own synthetic environments, collectors, weights and replay buffer -- and every epoch's training block is ONE
+    SACTrainerGroup.train_loop over all seeds (grouped launches; each run's result is bit for bit its solo one).
+    Weights come from a private RandomState(s) in the order experiment() draws them from np.random, and the buffer
+    samples a private stream continued from that generator (np.random is neither read nor written).  Returns
+    {seed: progress rows}; with log_dir, each seed's rows also go to <log_dir>/s<seed>/progress.csv.  Checkpointing a
+    group and resuming it are not supported (each trainer stays individually saveable)."""
+    if resume:
+        raise RuntimeError("experiment_group does not resume: group checkpoints are not supported")
+    validate(variant)
+    if variant.get("algorithm", "SAC") != "SAC":
+        raise RuntimeError("experiment_group trains SAC variants only (trainer groups hold SAC trainers)")
+    seeds = [int(s) for s in seeds]
+    if not seeds or len(set(seeds)) != len(seeds):
+        raise RuntimeError(f"experiment_group needs distinct seeds (got {seeds})")
+    O, A = env_dims(variant["expl_environment_kwargs"], obs_dim, action_dim)
+    ak, tk = variant["algorithm_kwargs"], variant["trainer_kwargs"]
+    runs = []
+    for seed in seeds:
+        rs = np.random.RandomState(seed)                      # experiment(): np.random.seed(seed), then the weights
+        expl_env = SyntheticEnv(O, A, variant["expl_environment_kwargs"].get("horizon", 500), seed)
+        eval_env = SyntheticEnv(O, A, variant["eval_environment_kwargs"].get("horizon", 500), seed + 1)
+        qf1, qf2, tqf1, tqf2 = (FlattenMlp(input_size=O + A, output_size=1, rs=rs, **variant["qf_kwargs"]) for _ in range(4))
+        policy = TanhGaussianPolicy(obs_dim=O, action_dim=A, rs=rs, noise=np.random.RandomState(seed),
+                                    **variant["policy_kwargs"])
+        trainer = SACTrainer(env=eval_env, policy=policy, qf1=qf1, qf2=qf2, target_qf1=tqf1, target_qf2=tqf2,
+                             batch_size=ak["batch_size"], noise_seed=seed, device=device, **tk)
+        buf = EnvReplayBuffer(variant["replay_buffer_size"], obs_dim=O, action_dim=A, device=device)
+        buf.seed_from_numpy(rs)                               # (the stream np.random would continue with)
+        expl, evalc = PathCollector(expl_env, policy), PathCollector(eval_env, MakeDeterministic(policy))
+        if ak.get("min_num_steps_before_training", 0) > 0:
+            buf.add_paths(expl.collect_new_paths(ak["expl_max_path_length"], ak["min_num_steps_before_training"], False))
+            expl.end_epoch(-1)
+        runs.append(dict(seed=seed, trainer=trainer, buf=buf, expl=expl, evalc=evalc, rows=[], fh=None, writer=None))
+    group = SACTrainerGroup([r["trainer"] for r in runs])
+    t_start = time.time()
+    try:
+        for epoch in range(num_epochs if num_epochs is not None else ak["num_epochs"]):
+            times = []
+            for r in runs:
+                t0 = time.time()
+                r["evalc"].collect_new_paths(ak["eval_max_path_length"], ak["num_eval_steps_per_epoch"], True)
+                t1 = time.time()
+                new_paths = r["expl"].collect_new_paths(ak["expl_max_path_length"], ak["num_expl_steps_per_train_loop"], False)
+                t2 = time.time()
+                r["buf"].add_paths(new_paths)
+                times.append((t0, t1, t2, time.time()))
+            n_train = ak["num_trains_per_train_loop"]
+            t3 = time.time()
+            group.train_loop([r["buf"] for r in runs], n_train, batch_size=ak["batch_size"])
+            t4 = time.time()
+            for r, (a0, a1, a2, a3) in zip(runs, times):
+                row = _progress_row(r["buf"], r["trainer"], r["expl"], r["evalc"], ak)
+                for x in (r["trainer"], r["buf"], r["expl"], r["evalc"]):
+                    x.end_epoch(epoch)
+                t5 = time.time()
+                row["time/data storing (s)"] = a3 - a2
+                row["time/evaluation sampling (s)"] = a1 - a0
+                row["time/exploration sampling (s)"] = a2 - a1
+                row["time/logging (s)"] = t5 - t4
+                row["time/saving (s)"] = 0.0
+                row["time/training (s)"] = t4 - t3            # (the group's block: every seed's steps at once)
+                row["time/epoch (s)"] = t5 - a0
+                row["time/total (s)"] = t5 - t_start
+                row["Epoch"] = epoch
+                r["rows"].append(row)
+                if log_dir is not None:
+                    if r["writer"] is None:
+                        d = os.path.join(log_dir, f"s{r['seed']}")
+                        os.makedirs(d, exist_ok=True)
+                        r["fh"] = open(os.path.join(d, "progress.csv"), "w", newline="")
+                        r["writer"] = csv.DictWriter(r["fh"], fieldnames=list(row.keys()))
+                        r["writer"].writeheader()
+                    r["writer"].writerow(row)
+                    r["fh"].flush()
+            if not quiet:
+                print(f"epoch {epoch}: {len(runs)} seeds, training {t4 - t3:.3f}s "
+                      f"({len(runs) * n_train / max(t4 - t3, 1e-9):.0f} steps/s together)", flush=True)
+    finally:
+        for r in runs:
+            if r["fh"]:
+                r["fh"].close()
+    return {r["seed"]: r["rows"] for r in runs}

@@ -1,0 +1,113 @@
+"""SACTrainerGroup: several SAC runs of one configuration trained together (sac_group_* of include/sac_hip.h).
+
+The reference's real workload is many independent runs -- seeds x configurations, one job each
+(/root/reference/launch_jobs.sh).  One run at batch 256 cannot fill an MI355X; a group steps R runs of the same shape
+with grouped launches (each launch R times wider) while every member stays an ordinary SACTrainer: its own weights,
+optimizer state, hyperparameters, noise seed and replay buffer, and a result bit for bit that of training alone."""
+from __future__ import annotations
+
+import ctypes as C
+
+import numpy as np
+
+from . import _lib
+from .sac import SACTrainer
+from .td3 import TD3Trainer
+
+MAX_MEMBERS = 16
+
+
+class SACTrainerGroup:
+    def __init__(self, trainers):
+        trainers = list(trainers)
+        if not 1 <= len(trainers) <= MAX_MEMBERS:
+            raise RuntimeError(f"a trainer group holds 1..{MAX_MEMBERS} trainers (got {len(trainers)})")
+        # host metadata first: nothing is created for a group that cannot exist
+        for i, t in enumerate(trainers):
+            if isinstance(t, TD3Trainer) or not isinstance(t, SACTrainer):
+                raise RuntimeError(f"trainer group member {i} is a {type(t).__name__}: groups hold SAC trainers only")
+        if len({id(t) for t in trainers}) != len(trainers):
+            raise RuntimeError("a trainer appears twice in the group")
+        t0 = trainers[0]
+        for i, t in enumerate(trainers[1:], 1):
+            if (t.obs_dim, t.act_dim) != (t0.obs_dim, t0.act_dim):
+                raise RuntimeError(f"trainer group member {i} has dims ({t.obs_dim},{t.act_dim}), member 0 "
+                                   f"({t0.obs_dim},{t0.act_dim})")
+            for net in ("policy", "qf1"):
+                if t._hidden(net) != t0._hidden(net):
+                    raise RuntimeError(f"trainer group member {i} has {net} hidden sizes {t._hidden(net)}, member 0 "
+                                       f"{t0._hidden(net)}")
+            if t.device != t0.device:
+                raise RuntimeError(f"trainer group member {i} lives on device {t.device}, member 0 on {t0.device}")
+            if t._batch is not None and t0._batch is not None and t._batch != t0._batch:
+                raise RuntimeError(f"trainer group member {i} has batch {t._batch}, member 0 {t0._batch}")
+        self.trainers = trainers
+        self._lib = _lib.load()
+        self._g, self._handles = None, None
+
+    def __len__(self):
+        return len(self.trainers)
+
+    def _group(self):
+        """The C group over the members' current handles (a member re-creates its handle for another batch size or after
+        unpickling: the group follows)."""
+        hs = tuple(t._h.value for t in self.trainers)
+        if self._g is None or hs != self._handles:
+            self._destroy()
+            arr = (C.c_void_p * len(hs))(*hs)
+            g = C.c_void_p()
+            _lib.check(self._lib.sac_group_create(C.byref(g), arr, len(hs)), "sac_group_create")
+            self._g, self._handles = g, hs
+        return self._g
+
+    def _destroy(self):
+        g, self._g = getattr(self, "_g", None), None
+        if g:
+            self._lib.sac_group_destroy(g)
+
+    def __del__(self):
+        self._destroy()
+
+    def train_loop(self, replay_buffers, n_steps, batch_size=None):
+        """n_steps x {batch_r = replay_buffers[r].random_batch(B); trainers[r].train(batch_r)} for every member r.
+        Returns the first and last step's diagnostics, arrays of shape (R, SAC_DIAG_N)."""
+        buffers = list(replay_buffers)
+        R = len(self.trainers)
+        if len(buffers) != R:
+            raise RuntimeError(f"{R} trainers but {len(buffers)} replay buffers")
+        B = int(batch_size or self.trainers[0]._batch or 0)
+        if B <= 0:
+            raise RuntimeError("the batch size is unknown: pass batch_size or create the trainers with one")
+        # what can be refused from host metadata is refused before any member's handle is (re)created
+        if B > 256:
+            raise RuntimeError(f"batch {B}: trainer groups take batches of at most 256 rows")
+        for i, t in enumerate(self.trainers):
+            for net in ("policy", "qf1"):
+                hs = t._hidden(net)
+                if len(hs) != 2 or max(hs) > 256:
+                    raise RuntimeError(f"trainer group member {i} runs the general step ({net} hidden sizes {hs}): groups "
+                                       "take two hidden layers of at most 256 units")
+        for r, b in enumerate(buffers):
+            if b is None or b._h is None:
+                raise RuntimeError(f"trainer group buffer {r} has no device storage")
+            if any(b is c for c in buffers[:r]):
+                raise RuntimeError(f"trainer group buffer {r} is the same buffer as an earlier one")
+            if (b._observation_dim, b._action_dim) != (self.trainers[0].obs_dim, self.trainers[0].act_dim):
+                raise RuntimeError(f"trainer group buffer {r} has dims ({b._observation_dim},{b._action_dim}), the trainers "
+                                   f"({self.trainers[0].obs_dim},{self.trainers[0].act_dim})")
+            if b.num_steps_can_sample() <= 0:
+                raise RuntimeError(f"trainer group buffer {r} is empty: random_batch on an empty replay buffer")
+        for t in self.trainers:
+            if t._h is None or t._batch != B:
+                t._create(B)
+        g = self._group()
+        bufs = (C.c_void_p * R)(*[b._h.value for b in buffers])
+        first = np.empty((R, _lib.SAC_DIAG_N), np.float32)
+        last = np.empty((R, _lib.SAC_DIAG_N), np.float32)
+        _lib.check(self._lib.sac_group_train_loop(g, bufs, int(n_steps), _lib.ptr(first), _lib.ptr(last)),
+                   "sac_group_train_loop")
+        for r, t in enumerate(self.trainers):
+            t._num_train_steps += int(n_steps)
+            t._host_policy_stale = True
+            t._record(first[r])
+        return first, last

@@ -1,0 +1,71 @@
+"""Aggregate grad-steps/s of trainer groups (sac_group_train_loop): R SAC runs of Lift (obs 42, act 7) at batch 256 and
+128, each with its own 1e6-slot replay buffer, stepped together with grouped launches.  One JSON line per (batch, R).
+
+    python scripts/bench_group.py [--steps 2000] [--warmup 200] [--batches 256 128] [--replicas 1 2 4 8 16]"""
+from __future__ import annotations
+
+import argparse
+import json
+import os
+import sys
+import time
+
+import numpy as np
+
+sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
+
+from robosuite_benchmark_amd import (EnvReplayBuffer, FlattenMlp, SACTrainer, SACTrainerGroup,  # noqa: E402
+                                     TanhGaussianPolicy, _lib)
+
+
+def make_trainer(O, A, B, seed):
+    rs = np.random.RandomState(seed)
+    qs = [FlattenMlp([256, 256], 1, O + A, rs=rs) for _ in range(4)]
+    pol = TanhGaussianPolicy([256, 256], O, A, rs=rs, noise=np.random.RandomState(seed))
+    return SACTrainer(policy=pol, qf1=qs[0], qf2=qs[1], target_qf1=qs[2], target_qf2=qs[3], discount=0.99,
+                      reward_scale=1.0, policy_lr=3e-4, qf_lr=3e-4, soft_target_tau=0.005, target_update_period=1,
+                      use_automatic_entropy_tuning=True, batch_size=B, noise_seed=seed)
+
+
+def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--steps", type=int, default=2000)
+    ap.add_argument("--warmup", type=int, default=200)
+    ap.add_argument("--buffer", type=int, default=1_000_000)
+    ap.add_argument("--batches", type=int, nargs="+", default=[256, 128])
+    ap.add_argument("--replicas", type=int, nargs="+", default=[1, 2, 4, 8, 16])
+    ap.add_argument("--obs", type=int, default=42)
+    ap.add_argument("--act", type=int, default=7)
+    args = ap.parse_args()
+    if _lib.device_count() == 0:
+        raise SystemExit("bench_group.py needs a GPU")
+    O, A, N = args.obs, args.act, args.buffer
+    rs = np.random.RandomState(1)
+    rows = (rs.normal(0, 0.5, (N, O)).astype(np.float32), rs.uniform(-1, 1, (N, A)).astype(np.float32),
+            rs.uniform(0, 1, (N, 1)).astype(np.float32), rs.normal(0, 0.5, (N, O)).astype(np.float32),
+            np.zeros((N, 1), np.uint8))
+    bufs = []
+    for r in range(max(args.replicas)):
+        b = EnvReplayBuffer(N, obs_dim=O, action_dim=A)
+        b.add_block(rows[0], rows[1], rows[2], rows[3], rows[4])
+        b.seed(100 + r)
+        bufs.append(b)
+    for B in args.batches:
+        for R in args.replicas:
+            trainers = [make_trainer(O, A, B, 10 + r) for r in range(R)]
+            group = SACTrainerGroup(trainers)
+            group.train_loop(bufs[:R], args.warmup, batch_size=B)
+            t0 = time.perf_counter()
+            _, last = group.train_loop(bufs[:R], args.steps, batch_size=B)
+            dt = time.perf_counter() - t0
+            print(json.dumps(dict(metric="group_grad_steps_per_s", batch=B, replicas=R, obs_dim=O, act_dim=A,
+                                  buffer=N, steps=args.steps, seconds=round(dt, 4),
+                                  aggregate_steps_per_s=round(R * args.steps / dt, 1),
+                                  per_run_steps_per_s=round(args.steps / dt, 1),
+                                  fused_members=int(sum(t.is_fused() for t in trainers)),
+                                  finite=bool(np.all(np.isfinite(last))))), flush=True)
+            del group, trainers
+
+
+if __name__ == "__main__":
+    main()

@@ -1,6 +1,8 @@
 #!/usr/bin/env python3
 """Counterpart of the reference's scripts/train.py for the MI355X path:
     python scripts/train.py --variant <variant.json> --seed S --log_dir DIR [--epochs N]
+    python scripts/train.py --variant <variant.json> --seeds S1 S2 ... --log_dir DIR [--epochs N]
+(--seeds: one process trains every seed, the training blocks as one trainer group; DIR/s<seed>/progress.csv each)
 Runs the variant unchanged (batch size, lrs, tau, period, buffer size ... from the JSON) on the
 HIP library with a synthetic environment of the task's dimensions (robosuite is not installed)."""
 import argparse
@@ -8,7 +10,7 @@ import os
 import sys
 
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
-from robosuite_benchmark_amd.driver import experiment  # noqa: E402
+from robosuite_benchmark_amd.driver import experiment, experiment_group  # noqa: E402
 from robosuite_benchmark_amd.variant import default_variant, load_variant  # noqa: E402
 
 if __name__ == "__main__":
@@ -23,7 +25,16 @@ if __name__ == "__main__":
     ap.add_argument("--resume", type=str, default=None,
                     help="an existing run directory (…_0000--s-0): continue it from its checkpoint/ after the last saved epoch")
     ap.add_argument("--no_checkpoint", action="store_true", help="do not save <run_dir>/checkpoint after every epoch")
+    ap.add_argument("--seeds", type=int, nargs="+", default=None,
+                    help="train these seeds of the one configuration together (trainer groups; SAC, no checkpoints)")
     args = ap.parse_args()
+    if args.seeds:
+        if args.resume:
+            raise SystemExit("--seeds does not resume (group checkpoints are not supported)")
+        variant = load_variant(args.variant) if args.variant else default_variant(env=args.env, seed=args.seeds[0],
+                                                                                  batch_size=args.batch_size, agent=args.agent)
+        experiment_group(variant, args.seeds, log_dir=args.log_dir, num_epochs=args.epochs)
+        sys.exit(0)
     variant = load_variant(args.variant) if args.variant else default_variant(env=args.env, seed=args.seed,
                                                                               batch_size=args.batch_size, agent=args.agent)
     run_dir = None
