@@ -336,6 +336,15 @@ int sac_policy_act(sac_trainer_t *t, const float *obs, int deterministic, const 
 enum { SAC_GROUP_MAX = 16 };
 typedef struct sac_group sac_group_t;
 int sac_group_create(sac_group_t **out, sac_trainer_t *const *members, int n_members);
+/* The TD3 form: 1..SAC_GROUP_MAX trainers of td3_trainer_create, under the same conditions (SAC members, and so mixed
+ * groups, are refused here as TD3 members are by sac_group_create).  Their policy_and_target_update_period, step counts
+ * and every other hyperparameter may differ: each member keeps its own delayed-update plan -- critic step every step,
+ * policy step and target update on every policy_and_target_update_period-th step number, the policy statistics on the
+ * call's first step too -- and its result is bit for bit sac_train_loop's.
+ * sac_group_train_loop and sac_group_destroy serve both kinds.  For a TD3 group, diag_first holds each member's first
+ * step (its Policy Loss / Policy Action from the actor pass that step always runs) and diag_last the most recent value of
+ * every entry at the end of the call (the policy entries: of the member's last actor pass), as sac_train_loop's do. */
+int td3_group_create(sac_group_t **out, sac_trainer_t *const *members, int n_members);
 int sac_group_destroy(sac_group_t *g);
 int sac_group_train_loop(sac_group_t *g, sac_buffer_t *const *buffers, int64_t n_steps, float *diag_first,
                          float *diag_last);

@@ -1731,34 +1731,79 @@ __global__ __launch_bounds__(256) void k_dw_adam(Dev d, DwTable T, const float *
 // ------------------------------------------------------------------------------------------
 struct GroupMember {
     Dev d;
-    DwTable T;                     // the member's weight-gradient table (abort = null: the four-launch step)
+    DwTable T;                     // the member's weight-gradient table (abort = null: the four-launch step); TD3: dw_q
     SlotLayout SL;
     const float *slots;            // the member's loop slot 0: slot j at slots + j * SL.slot_floats
+    DwTable T_tp, T_pi, T_none;    // TD3 only: dw_q_tp, dw_pi, dw_none (launch_step_td3's other tables)
 };
+// A TD3 member's step (the [step][R] table of a TD3 group): launch_step_td3's two StepArgs and its plan.  Members may be
+// in different phases of the delayed update, so the actor launches of a step run for every member that needs them and
+// the others leave at block entry (a uniform branch on these flags).
+struct Td3GroupStep {
+    StepArg sq, sp;                // critic pass (kind 1, adam_t + 1) / actor pass (kind 2, adam_t_pi + 1)
+    int actor, pstep;              // the actor pass runs (policy step, or the statistics of a call's first step) / policy step
+    int pad_[2];
+};
+template <int MODE> struct GroupStepOf { using type = Td3GroupStep; };
+template <> struct GroupStepOf<M_SAC> { using type = StepArg; };
+template <int MODE> using GroupStep = typename GroupStepOf<MODE>::type;
 
-template <int NTH, bool WIDE, int SP>
-__global__ __launch_bounds__(256) void k_fwd_a_group(const GroupMember *__restrict__ G, int slot) {
+// MODE M_SAC: the SAC step.  M_TD3_CRITIC: the critic pass (launch A runs the online policy only where `actor` is set).
+// M_TD3_ACTOR: the actor pass (k_fwd_b: members with `actor`; k_bwd: members with `pstep`).
+template <int NTH, bool WIDE, int SP, int MODE = M_SAC>
+__global__ __launch_bounds__(256) void k_fwd_a_group(const GroupMember *__restrict__ G, const GroupStep<MODE> *__restrict__ SA,
+                                                     int slot) {
     const GroupMember &g = G[blockIdx.y];
-    fwd_a_body<NTH, WIDE, SP>(g.d, g.slots + (size_t)slot * g.SL.slot_floats, g.SL, 0);
+    int aux = 0;
+    if constexpr (MODE != M_SAC) aux = SA[blockIdx.y].actor;
+    fwd_a_body<NTH, WIDE, SP, MODE>(g.d, g.slots + (size_t)slot * g.SL.slot_floats, g.SL, aux);
 }
-template <int NTH, bool WIDE, int SP>
-__global__ __launch_bounds__(256) void k_fwd_b_group(const GroupMember *__restrict__ G, const StepArg *__restrict__ SA, int slot) {
+template <int NTH, bool WIDE, int SP, int MODE = M_SAC>
+__global__ __launch_bounds__(256) void k_fwd_b_group(const GroupMember *__restrict__ G, const GroupStep<MODE> *__restrict__ SA,
+                                                     int slot) {
     const GroupMember &g = G[blockIdx.y];
-    fwd_b_body<NTH, WIDE, SP>(g.d, g.slots + (size_t)slot * g.SL.slot_floats, g.SL, SA[blockIdx.y]);
+    const float *S = g.slots + (size_t)slot * g.SL.slot_floats;
+    if constexpr (MODE == M_SAC) fwd_b_body<NTH, WIDE, SP>(g.d, S, g.SL, SA[blockIdx.y]);
+    else if constexpr (MODE == M_TD3_CRITIC) fwd_b_body<NTH, WIDE, SP, MODE>(g.d, S, g.SL, SA[blockIdx.y].sq);
+    else {
+        if (!SA[blockIdx.y].actor) return;
+        fwd_b_body<NTH, WIDE, SP, MODE>(g.d, S, g.SL, SA[blockIdx.y].sp);
+    }
 }
-template <int NTH, int SP>
-__global__ __launch_bounds__(256) void k_bwd_group(const GroupMember *__restrict__ G, const StepArg *__restrict__ SA, int slot,
-                                                   int compact) {
+template <int NTH, int SP, int MODE = M_SAC>
+__global__ __launch_bounds__(256) void k_bwd_group(const GroupMember *__restrict__ G, const GroupStep<MODE> *__restrict__ SA,
+                                                   int slot, int compact) {
     const GroupMember &g = G[blockIdx.y];
-    bwd_body<NTH, SP>(g.d, g.slots + (size_t)slot * g.SL.slot_floats, g.SL, SA[blockIdx.y], compact);
+    const float *S = g.slots + (size_t)slot * g.SL.slot_floats;
+    if constexpr (MODE == M_SAC) bwd_body<NTH, SP>(g.d, S, g.SL, SA[blockIdx.y], compact);
+    else if constexpr (MODE == M_TD3_CRITIC) bwd_body<NTH, SP, MODE>(g.d, S, g.SL, SA[blockIdx.y].sq, compact);
+    else {
+        if (!SA[blockIdx.y].pstep) return;
+        bwd_body<NTH, SP, MODE>(g.d, S, g.SL, SA[blockIdx.y].sp, compact);
+    }
 }
-__global__ __launch_bounds__(256) void k_dw_adam_group(const GroupMember *__restrict__ G, const StepArg *__restrict__ SA, int slot) {
+// each member's table of this step: SAC its one table; TD3 critic pass dw_q / dw_q_tp (policy steps: with the critics'
+// Polyak targets), actor pass dw_pi (policy steps) / dw_none (statistics only) / nothing
+template <int MODE = M_SAC>
+__global__ __launch_bounds__(256) void k_dw_adam_group(const GroupMember *__restrict__ G, const GroupStep<MODE> *__restrict__ SA,
+                                                       int slot) {
     __shared__ __attribute__((aligned(16))) float red[4 * 4 * 64 * 4];
     __shared__ __attribute__((aligned(16))) float redb[4 * 16 * 2];
     __shared__ __attribute__((aligned(16))) float trs[4 * 256];
     const GroupMember &g = G[blockIdx.y];
-    if ((int)blockIdx.x > g.T.njobs) return;
-    dw_adam_body(g.d, g.T, g.slots + (size_t)slot * g.SL.slot_floats, SA[blockIdx.y], red, redb, trs, (int)blockIdx.x, 0u);
+    const DwTable *T = &g.T;
+    const StepArg *sa;
+    if constexpr (MODE == M_SAC) sa = &SA[blockIdx.y];
+    else if constexpr (MODE == M_TD3_CRITIC) {
+        if (SA[blockIdx.y].pstep) T = &g.T_tp;
+        sa = &SA[blockIdx.y].sq;
+    } else {
+        if (!SA[blockIdx.y].actor) return;
+        T = SA[blockIdx.y].pstep ? &g.T_pi : &g.T_none;
+        sa = &SA[blockIdx.y].sp;
+    }
+    if ((int)blockIdx.x > T->njobs) return;
+    dw_adam_body(g.d, *T, g.slots + (size_t)slot * g.SL.slot_floats, *sa, red, redb, trs, (int)blockIdx.x, 0u);
 }
 
 #include "sac_bwd8.h"
@@ -3361,7 +3406,8 @@ int sac_policy_act(sac_trainer_t *t, const float *obs, int deterministic, const 
 }
 
 // ==========================================================================================
-// Trainer groups: R SAC trainers of one shape stepped together, four grouped launches per step (see GroupMember).
+// Trainer groups: R SAC trainers of one shape stepped together, four grouped launches per step (see GroupMember) -- or R
+// TD3 trainers (td3_group_create), launch_step_td3's four to seven launches per step, each one grouped.
 // The loop is sac_train_loop's for every member at once -- same index stream per buffer, same steps, same results bit
 // for bit -- without its latency devices (no speculative next chunk, no stepwise read-ahead): chunks of LOOP_CH steps
 // alternate between the two halves of each buffer's loop slots; the draws and gathers of a chunk run on the group's
@@ -3370,7 +3416,7 @@ int sac_policy_act(sac_trainer_t *t, const float *obs, int deterministic, const 
 // serialised behind the gate's last launch, at a cost of ~0.3 ms per 256-step chunk).
 // ==========================================================================================
 struct sac_group {
-    int R = 0, device = 0;
+    int R = 0, device = 0, algo = 0;                  // algo: 0 SAC, 1 TD3 (every member's)
     sac_trainer *m[SAC_GROUP_MAX] = {};
     hipStream_t s = nullptr, s2 = nullptr;           // steps / draws + gathers
     hipEvent_t ev_ready[2] = {}, ev_done[2] = {}, ev_copied[2] = {}, ev_end = nullptr;
@@ -3379,10 +3425,15 @@ struct sac_group {
     GroupMember *d_mem = nullptr, *h_mem = nullptr;   // [R]
     SampleMember *d_smp = nullptr, *h_smp = nullptr;  // [2 halves][R]
     GatherMember *d_gat = nullptr, *h_gat = nullptr;  // [2 halves][R]
-    StepArg *d_sa = nullptr, *h_sa = nullptr;         // [2 halves][LOOP_CH steps][R]
-    void (*fa)(const GroupMember *, int) = nullptr;
+    StepArg *d_sa = nullptr, *h_sa = nullptr;         // SAC: [2 halves][LOOP_CH steps][R]
+    Td3GroupStep *d_ts = nullptr, *h_ts = nullptr;    // TD3: [2 halves][LOOP_CH steps][R]
+    void (*fa)(const GroupMember *, const StepArg *, int) = nullptr;
     void (*fb)(const GroupMember *, const StepArg *, int) = nullptr;
     void (*bw)(const GroupMember *, const StepArg *, int, int) = nullptr;
+    // TD3: critic pass (launches A, B, C) and actor pass (B, C)
+    void (*fa3)(const GroupMember *, const Td3GroupStep *, int) = nullptr;
+    void (*fb3)(const GroupMember *, const Td3GroupStep *, int) = nullptr, (*fb3a)(const GroupMember *, const Td3GroupStep *, int) = nullptr;
+    void (*bw3)(const GroupMember *, const Td3GroupStep *, int, int) = nullptr, (*bw3a)(const GroupMember *, const Td3GroupStep *, int, int) = nullptr;
 };
 
 static void group_free(sac_group *g) {
@@ -3401,8 +3452,9 @@ static void group_free(sac_group *g) {
 }
 
 // what a member must be (checked at creation and again in front of every call: a member may have been confined since)
-static int group_member_ok(const sac_trainer *t, int i) {
-    SAC_REQUIRE(t->algo == 0, "trainer group member %d is a TD3 trainer: groups hold SAC trainers only", i);
+static int group_member_ok(const sac_trainer *t, int i, int algo) {
+    if (algo == 0) SAC_REQUIRE(t->algo == 0, "trainer group member %d is a TD3 trainer: groups hold SAC trainers only", i);
+    else SAC_REQUIRE(t->algo == 1, "trainer group member %d is a SAC trainer: TD3 groups hold TD3 trainers only", i);
     SAC_REQUIRE(!t->gen, "trainer group member %d runs the general step (hidden sizes beyond two layers of at most 256 units): "
                 "groups take the shapes of the fused kernels only", i);
     SAC_REQUIRE(t->Bt <= 256, "trainer group member %d has batch %d: groups take batches of at most 256 rows", i, t->Bt);
@@ -3413,8 +3465,8 @@ static int group_member_ok(const sac_trainer *t, int i) {
     return 0;
 }
 
-int sac_group_create(sac_group_t **out, sac_trainer_t *const *members, int n_members) {
-    SAC_REQUIRE(out && members, "null argument to sac_group_create");
+static int group_create(sac_group_t **out, sac_trainer_t *const *members, int n_members, int algo) {
+    SAC_REQUIRE(out && members, "null argument to %s", algo ? "td3_group_create" : "sac_group_create");
     *out = nullptr;
     SAC_REQUIRE(n_members >= 1 && n_members <= SAC_GROUP_MAX, "a trainer group holds 1..%d members (got %d)", SAC_GROUP_MAX,
                 n_members);
@@ -3424,7 +3476,7 @@ int sac_group_create(sac_group_t **out, sac_trainer_t *const *members, int n_mem
         SAC_REQUIRE(t != nullptr, "trainer group member %d is null", i);
         for (int j = 0; j < i; ++j)
             SAC_REQUIRE(members[j] != t, "trainer group members %d and %d are the same trainer", j, i);
-        if (group_member_ok(t, i)) return -1;
+        if (group_member_ok(t, i, algo)) return -1;
         SAC_REQUIRE(t->O == t0->O && t->A == t0->A, "trainer group member %d has dims (%d,%d), member 0 (%d,%d)", i, t->O, t->A,
                     t0->O, t0->A);
         SAC_REQUIRE(t->Bt == t0->Bt, "trainer group member %d has batch %d, member 0 %d", i, t->Bt, t0->Bt);
@@ -3439,28 +3491,42 @@ int sac_group_create(sac_group_t **out, sac_trainer_t *const *members, int n_mem
     sac_group *g = new sac_group();
     g->R = n_members;
     g->device = t0->device;
+    g->algo = algo;
     for (int i = 0; i < n_members; ++i) g->m[i] = members[i];
     // the grouped instance of the variant the members' own four-launch step runs
 #define SAC_GROUP_PICK(NTH, W)                                                                             \
     if (t0->fwd_a == &k_fwd_a<NTH, W, 4>) {                                                                \
         g->fa = &k_fwd_a_group<NTH, W, 4>; g->fb = &k_fwd_b_group<NTH, W, 4>; g->bw = &k_bwd_group<NTH, 4>; \
     }
-    SAC_GROUP_PICK(1, false) else SAC_GROUP_PICK(1, true) else SAC_GROUP_PICK(2, false) else SAC_GROUP_PICK(2, true)
+#define TD3_GROUP_PICK(W)                                                                                  \
+    if (t0->fwd_a == &k_fwd_a<1, W, 4, M_TD3_CRITIC>) {                                                    \
+        g->fa3 = &k_fwd_a_group<1, W, 4, M_TD3_CRITIC>;                                                    \
+        g->fb3 = &k_fwd_b_group<1, W, 4, M_TD3_CRITIC>; g->fb3a = &k_fwd_b_group<1, W, 4, M_TD3_ACTOR>;      \
+        g->bw3 = &k_bwd_group<1, 4, M_TD3_CRITIC>; g->bw3a = &k_bwd_group<1, 4, M_TD3_ACTOR>;                \
+    }
+    if (algo == 0) {
+        SAC_GROUP_PICK(1, false) else SAC_GROUP_PICK(1, true) else SAC_GROUP_PICK(2, false) else SAC_GROUP_PICK(2, true)
+    } else {
+        TD3_GROUP_PICK(false) else TD3_GROUP_PICK(true)
+    }
 #undef SAC_GROUP_PICK
+#undef TD3_GROUP_PICK
     auto fail = [&](int rc) { group_free(g); return rc; };
-    if (!g->fa) { sac::set_error("internal: no grouped instance of the members' step kernels"); return fail(-1); }
+    if (!g->fa && !g->fa3) { sac::set_error("internal: no grouped instance of the members' step kernels"); return fail(-1); }
     auto set_lds = [](const void *fn, size_t bytes) {
-        return bytes > 64 * 1024 ? hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)bytes) : hipSuccess;
+        return (!fn || bytes <= 64 * 1024) ? hipSuccess : hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)bytes);
     };
-    if (set_lds(reinterpret_cast<const void *>(g->fa), t0->lds_fa) != hipSuccess ||
-        set_lds(reinterpret_cast<const void *>(g->fb), t0->lds_fb) != hipSuccess ||
-        set_lds(reinterpret_cast<const void *>(g->bw), t0->lds_bw) != hipSuccess) {
+    auto fn = [](auto f) { return reinterpret_cast<const void *>(f); };
+    if (set_lds(fn(g->fa), t0->lds_fa) != hipSuccess || set_lds(fn(g->fb), t0->lds_fb) != hipSuccess ||
+        set_lds(fn(g->bw), t0->lds_bw) != hipSuccess || set_lds(fn(g->fa3), t0->lds_fa) != hipSuccess ||
+        set_lds(fn(g->fb3), t0->lds_fb) != hipSuccess || set_lds(fn(g->fb3a), t0->lds_fb) != hipSuccess ||
+        set_lds(fn(g->bw3), t0->lds_bw) != hipSuccess || set_lds(fn(g->bw3a), t0->lds_bw) != hipSuccess) {
         sac::set_error("hipFuncSetAttribute failed for the grouped step kernels");
         return fail(-1);
     }
     const int R = n_members;
     const size_t b_mem = sizeof(GroupMember) * R, b_smp = sizeof(SampleMember) * 2 * R, b_gat = sizeof(GatherMember) * 2 * R;
-    const size_t b_sa = sizeof(StepArg) * 2 * LOOP_CH * R;
+    const size_t b_sa = (algo ? sizeof(Td3GroupStep) : sizeof(StepArg)) * 2 * LOOP_CH * R;
     const size_t o_smp = (b_mem + 255) & ~(size_t)255, o_gat = o_smp + ((b_smp + 255) & ~(size_t)255);
     const size_t o_sa = o_gat + ((b_gat + 255) & ~(size_t)255), total = o_sa + b_sa;
     if (hipMalloc(reinterpret_cast<void **>(&g->d_tab), total) != hipSuccess ||
@@ -3483,7 +3549,8 @@ int sac_group_create(sac_group_t **out, sac_trainer_t *const *members, int n_mem
     g->d_mem = reinterpret_cast<GroupMember *>(g->d_tab); g->h_mem = reinterpret_cast<GroupMember *>(g->h_tab);
     g->d_smp = reinterpret_cast<SampleMember *>(g->d_tab + o_smp); g->h_smp = reinterpret_cast<SampleMember *>(g->h_tab + o_smp);
     g->d_gat = reinterpret_cast<GatherMember *>(g->d_tab + o_gat); g->h_gat = reinterpret_cast<GatherMember *>(g->h_tab + o_gat);
-    g->d_sa = reinterpret_cast<StepArg *>(g->d_tab + o_sa); g->h_sa = reinterpret_cast<StepArg *>(g->h_tab + o_sa);
+    if (algo == 0) { g->d_sa = reinterpret_cast<StepArg *>(g->d_tab + o_sa); g->h_sa = reinterpret_cast<StepArg *>(g->h_tab + o_sa); }
+    else { g->d_ts = reinterpret_cast<Td3GroupStep *>(g->d_tab + o_sa); g->h_ts = reinterpret_cast<Td3GroupStep *>(g->h_tab + o_sa); }
     {   // a tenant of the device's fused-launch gate: no fused trainer's launch may overlap the group's grids
         FusedGate &G = g_gate[g->device & 63];
         std::lock_guard<std::mutex> lk(G.mu);
@@ -3495,6 +3562,14 @@ int sac_group_create(sac_group_t **out, sac_trainer_t *const *members, int n_mem
     }
     *out = g;
     return 0;
+}
+
+int sac_group_create(sac_group_t **out, sac_trainer_t *const *members, int n_members) {
+    return group_create(out, members, n_members, 0);
+}
+
+int td3_group_create(sac_group_t **out, sac_trainer_t *const *members, int n_members) {
+    return group_create(out, members, n_members, 1);
 }
 
 int sac_group_destroy(sac_group_t *g) {
@@ -3517,7 +3592,7 @@ int sac_group_train_loop(sac_group_t *g, sac_buffer_t *const *bufs, int64_t n_st
     const sac_trainer *t0 = g->m[0];
     // every refusal comes before anything changes
     for (int r = 0; r < R; ++r) {
-        if (group_member_ok(g->m[r], r)) return -1;
+        if (group_member_ok(g->m[r], r, g->algo)) return -1;
         const sac_buffer *b = bufs[r];
         SAC_REQUIRE(b != nullptr, "trainer group buffer %d is null", r);
         for (int q = 0; q < r; ++q) SAC_REQUIRE(bufs[q] != b, "trainer group buffers %d and %d are the same buffer", q, r);
@@ -3580,6 +3655,11 @@ int sac_group_train_loop(sac_group_t *g, sac_buffer_t *const *bufs, int64_t n_st
         M.T.abort = nullptr;                          // (the four-launch step: no fused launch can give up in front of it)
         M.SL = b->slot;
         M.slots = b->d_slots;
+        if (g->algo == 1) {
+            M.T = t->dw_q; M.T.abort = nullptr;
+            M.T_tp = t->dw_q_tp; M.T_pi = t->dw_pi; M.T_none = t->dw_none;
+            M.T_tp.abort = M.T_pi.abort = M.T_none.abort = nullptr;
+        }
         uint32_t rng = (uint32_t)(b->size - 1), mask = rng;
         mask |= mask >> 1; mask |= mask >> 2; mask |= mask >> 4; mask |= mask >> 8; mask |= mask >> 16;
         for (int h = 0; h < 2; ++h) {
@@ -3594,6 +3674,11 @@ int sac_group_train_loop(sac_group_t *g, sac_buffer_t *const *bufs, int64_t n_st
     const int SPv = 4, NB = t0->NB;
     const int compact = (3 * SPv * NB <= 192) ? 1 : 0;       // as launch_step
     const int grid_ab = 4 * SPv * NB, grid_c = compact ? 4 * SPv * NB : 3 * SPv * NB, grid_d = t0->dw.njobs + 1;
+    // TD3 (as launch_step_td3): critic pass A, B, C, D; actor pass B, C, D
+    const int grid_q = 8 * ((SPv * NB + 3) / 4), grid_pi = SPv * NB;
+    const int grid_dq = (t0->dw_q.njobs > t0->dw_q_tp.njobs ? t0->dw_q.njobs : t0->dw_q_tp.njobs) + 1, grid_dpi = t0->dw_pi.njobs + 1;
+    long long pi_steps[SAC_GROUP_MAX] = {};           // TD3: policy steps of each member so far in this call
+    unsigned char plan[LOOP_CH];                      // TD3: per step of a chunk, bit 0: some member runs the actor pass, bit 1: some policy step
     FusedGate &G = g_gate[g->device & 63];
     int64_t done = 0;
     for (int c = 0; done < n_steps; ++c) {
@@ -3612,19 +3697,47 @@ int sac_group_train_loop(sac_group_t *g, sac_buffer_t *const *bufs, int64_t n_st
         SAC_HIP(hipEventRecord(g->ev_ready[h], s2));
         // the chunk's step arguments, computed like launch_step's (the host half is free once its last copy has run)
         if (c >= 2 && wait_event(g->ev_copied[h])) return -1;
-        StepArg *hs = g->h_sa + (size_t)h * LOOP_CH * R;
-        for (int64_t j = 0; j < m; ++j)
-            for (int r = 0; r < R; ++r) {
-                const sac_trainer *t = g->m[r];
-                const long long k = (long long)(done + j);
-                const double tt = (double)(t->adam_t + k + 1);
-                StepArg sa{t->n_train_steps_total + k, t->adam_t + k + 1, (int)k, 0, 1.0 - std::pow(0.9, tt),
-                           std::sqrt(1.0 - std::pow(0.999, tt))};
-                sa.pad2 = (done + j == n_steps - 1) ? 2u : 0u;
-                hs[j * R + r] = sa;
+        const void *dsrc = nullptr, *hsrc = nullptr;
+        size_t bytes = 0;
+        if (g->algo == 0) {
+            StepArg *hs = g->h_sa + (size_t)h * LOOP_CH * R;
+            for (int64_t j = 0; j < m; ++j)
+                for (int r = 0; r < R; ++r) {
+                    const sac_trainer *t = g->m[r];
+                    const long long k = (long long)(done + j);
+                    const double tt = (double)(t->adam_t + k + 1);
+                    StepArg sa{t->n_train_steps_total + k, t->adam_t + k + 1, (int)k, 0, 1.0 - std::pow(0.9, tt),
+                               std::sqrt(1.0 - std::pow(0.999, tt))};
+                    sa.pad2 = (done + j == n_steps - 1) ? 2u : 0u;
+                    hs[j * R + r] = sa;
+                }
+            hsrc = hs; dsrc = g->d_sa + (size_t)h * LOOP_CH * R; bytes = sizeof(StepArg) * m * R;
+        } else {
+            // launch_step_td3's decision per member and step: a policy step every td3_period-th step number, the actor pass
+            // also on the call's first step (its Policy Loss / Policy Action statistics, no update)
+            Td3GroupStep *hs = g->h_ts + (size_t)h * LOOP_CH * R;
+            for (int64_t j = 0; j < m; ++j) {
+                plan[j] = 0;
+                for (int r = 0; r < R; ++r) {
+                    const sac_trainer *t = g->m[r];
+                    const long long k = (long long)(done + j), step = t->n_train_steps_total + k;
+                    const bool pstep = (step % t->td3_period) == 0, actor = pstep || k == 0;
+                    const double tq = (double)(t->adam_t + k + 1), tp = (double)(t->adam_t_pi + pi_steps[r] + 1);
+                    Td3GroupStep &ts = hs[j * R + r];
+                    ts.sq = StepArg{step, t->adam_t + k + 1, (int)k, 1, 1.0 - std::pow(0.9, tq), std::sqrt(1.0 - std::pow(0.999, tq))};
+                    ts.sp = StepArg{step, t->adam_t_pi + pi_steps[r] + 1, (int)k, 2, 1.0 - std::pow(0.9, tp),
+                                    std::sqrt(1.0 - std::pow(0.999, tp))};
+                    ts.sq.pad2 = ts.sp.pad2 = (done + j == n_steps - 1) ? 2u : 0u;
+                    ts.actor = actor ? 1 : 0;
+                    ts.pstep = pstep ? 1 : 0;
+                    ts.pad_[0] = ts.pad_[1] = 0;
+                    plan[j] |= (actor ? 1 : 0) | (pstep ? 2 : 0);
+                    pi_steps[r] += pstep ? 1 : 0;
+                }
             }
-        StepArg *ds = g->d_sa + (size_t)h * LOOP_CH * R;
-        SAC_HIP(hipMemcpyAsync(ds, hs, sizeof(StepArg) * m * R, hipMemcpyHostToDevice, s));
+            hsrc = hs; dsrc = g->d_ts + (size_t)h * LOOP_CH * R; bytes = sizeof(Td3GroupStep) * m * R;
+        }
+        SAC_HIP(hipMemcpyAsync(const_cast<void *>(dsrc), hsrc, bytes, hipMemcpyHostToDevice, s));
         SAC_HIP(hipEventRecord(g->ev_copied[h], s));
         SAC_HIP(hipStreamWaitEvent(s, g->ev_ready[h], 0));
         {
@@ -3633,11 +3746,25 @@ int sac_group_train_loop(sac_group_t *g, sac_buffer_t *const *bufs, int64_t n_st
             if (gate && G.last && G.last != s) SAC_HIP(hipStreamWaitEvent(s, G.ev, 0));
             for (int64_t j = 0; j < m; ++j) {
                 const int slot = (int)(h * LOOP_CH + j);
-                const StepArg *sa = ds + j * R;
-                hipLaunchKernelGGL(g->fa, dim3(grid_ab, R), dim3(256), t0->lds_fa, s, g->d_mem, slot);
-                hipLaunchKernelGGL(g->fb, dim3(grid_ab, R), dim3(256), t0->lds_fb, s, g->d_mem, sa, slot);
-                hipLaunchKernelGGL(g->bw, dim3(grid_c, R), dim3(256), t0->lds_bw, s, g->d_mem, sa, slot, compact);
-                hipLaunchKernelGGL(k_dw_adam_group, dim3(grid_d, R), dim3(256), 0, s, g->d_mem, sa, slot);
+                if (g->algo == 0) {
+                    const StepArg *sa = g->d_sa + (size_t)h * LOOP_CH * R + j * R;
+                    hipLaunchKernelGGL(g->fa, dim3(grid_ab, R), dim3(256), t0->lds_fa, s, g->d_mem, sa, slot);
+                    hipLaunchKernelGGL(g->fb, dim3(grid_ab, R), dim3(256), t0->lds_fb, s, g->d_mem, sa, slot);
+                    hipLaunchKernelGGL(g->bw, dim3(grid_c, R), dim3(256), t0->lds_bw, s, g->d_mem, sa, slot, compact);
+                    hipLaunchKernelGGL(k_dw_adam_group<M_SAC>, dim3(grid_d, R), dim3(256), 0, s, g->d_mem, sa, slot);
+                } else {
+                    const Td3GroupStep *ts = g->d_ts + (size_t)h * LOOP_CH * R + j * R;
+                    hipLaunchKernelGGL(g->fa3, dim3(grid_ab, R), dim3(256), t0->lds_fa, s, g->d_mem, ts, slot);
+                    hipLaunchKernelGGL(g->fb3, dim3(grid_q, R), dim3(256), t0->lds_fb, s, g->d_mem, ts, slot);
+                    hipLaunchKernelGGL(g->bw3, dim3(grid_q, R), dim3(256), t0->lds_bw, s, g->d_mem, ts, slot, 0);
+                    hipLaunchKernelGGL(k_dw_adam_group<M_TD3_CRITIC>, dim3(grid_dq, R), dim3(256), 0, s, g->d_mem, ts, slot);
+                    if (plan[j] & 1) {
+                        hipLaunchKernelGGL(g->fb3a, dim3(grid_pi, R), dim3(256), t0->lds_fb, s, g->d_mem, ts, slot);
+                        if (plan[j] & 2) hipLaunchKernelGGL(g->bw3a, dim3(grid_pi, R), dim3(256), t0->lds_bw, s, g->d_mem, ts, slot, 0);
+                        hipLaunchKernelGGL(k_dw_adam_group<M_TD3_ACTOR>, dim3((plan[j] & 2) ? grid_dpi : 1, R), dim3(256), 0, s,
+                                           g->d_mem, ts, slot);
+                    }
+                }
             }
             SAC_HIP(hipGetLastError());
             if (gate) { SAC_HIP(hipEventRecord(G.ev, s)); G.last = s; }
@@ -3654,6 +3781,7 @@ int sac_group_train_loop(sac_group_t *g, sac_buffer_t *const *bufs, int64_t n_st
         sac_trainer *t = g->m[r];
         t->n_train_steps_total += n_steps;
         t->adam_t += n_steps;
+        t->adam_t_pi += pi_steps[r];                  // (TD3; zero for SAC)
         t->mirror_valid = false;
         if (diag_first) memcpy(diag_first + (size_t)r * SAC_DIAG_N, t->h_diag, sizeof(float) * SAC_DIAG_N);
         if (diag_last) memcpy(diag_last + (size_t)r * SAC_DIAG_N, t->h_diag + SAC_DIAG_N, sizeof(float) * SAC_DIAG_N);

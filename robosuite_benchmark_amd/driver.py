@@ -20,7 +20,7 @@ from .checkpoint import checkpoint_exists, load_checkpoint, save_checkpoint
 from .networks import (FlattenMlp, GaussianStrategy, MakeDeterministic, PolicyWrappedWithExplorationStrategy,
                        TanhGaussianPolicy, TanhMlpPolicy)
 from .replay_buffer import EnvReplayBuffer
-from .group import SACTrainerGroup
+from .group import SACTrainerGroup, TD3TrainerGroup
 from .sac import SACTrainer
 from .td3 import TD3Trainer
 from .variant import env_dims, validate
@@ -247,7 +247,8 @@ def experiment_group(variant, seeds, log_dir=None, num_epochs=None, obs_dim=None
                      quiet=False, resume=False):
     """One configuration, several seeds, one process: each seed is the run ``experiment(variant, seed=s)`` would make --
     its own synthetic environments, collectors, weights and replay buffer -- and every epoch's training block is ONE
-    SACTrainerGroup.train_loop over all seeds (grouped launches; each run's result is bit for bit its solo one).
+    SACTrainerGroup.train_loop (TD3 variants: TD3TrainerGroup) over all seeds (grouped launches; each run's result is
+    bit for bit its solo one).
     Weights come from a private RandomState(s) in the order experiment() draws them from np.random, and the buffer
     samples a private stream continued from that generator (np.random is neither read nor written).  Returns
     {seed: progress rows}; with log_dir, each seed's rows also go to <log_dir>/s<seed>/progress.csv.  Checkpointing a
@@ -255,8 +256,7 @@ def experiment_group(variant, seeds, log_dir=None, num_epochs=None, obs_dim=None
     if resume:
         raise RuntimeError("experiment_group does not resume: group checkpoints are not supported")
     validate(variant)
-    if variant.get("algorithm", "SAC") != "SAC":
-        raise RuntimeError("experiment_group trains SAC variants only (trainer groups hold SAC trainers)")
+    td3 = variant.get("algorithm", "SAC") == "TD3"
     seeds = [int(s) for s in seeds]
     if not seeds or len(set(seeds)) != len(seeds):
         raise RuntimeError(f"experiment_group needs distinct seeds (got {seeds})")
@@ -268,18 +268,30 @@ def experiment_group(variant, seeds, log_dir=None, num_epochs=None, obs_dim=None
         expl_env = SyntheticEnv(O, A, variant["expl_environment_kwargs"].get("horizon", 500), seed)
         eval_env = SyntheticEnv(O, A, variant["eval_environment_kwargs"].get("horizon", 500), seed + 1)
         qf1, qf2, tqf1, tqf2 = (FlattenMlp(input_size=O + A, output_size=1, rs=rs, **variant["qf_kwargs"]) for _ in range(4))
-        policy = TanhGaussianPolicy(obs_dim=O, action_dim=A, rs=rs, noise=np.random.RandomState(seed),
-                                    **variant["policy_kwargs"])
-        trainer = SACTrainer(env=eval_env, policy=policy, qf1=qf1, qf2=qf2, target_qf1=tqf1, target_qf2=tqf2,
-                             batch_size=ak["batch_size"], noise_seed=seed, device=device, **tk)
+        if td3:                                               # as experiment()'s TD3 branch
+            policy = TanhMlpPolicy(input_size=O, output_size=A, rs=rs, **variant["policy_kwargs"])
+            target_policy = TanhMlpPolicy(input_size=O, output_size=A, rs=rs, **variant["policy_kwargs"])
+            eval_policy = policy
+            expl_policy = PolicyWrappedWithExplorationStrategy(
+                exploration_strategy=GaussianStrategy(max_sigma=0.1, min_sigma=0.1, seed=seed), policy=policy)
+            trainer = TD3Trainer(policy=policy, qf1=qf1, qf2=qf2, target_qf1=tqf1, target_qf2=tqf2,
+                                 target_policy=target_policy, batch_size=ak["batch_size"], noise_seed=seed, device=device,
+                                 **tk)
+            policy._noise = expl_policy.es._rs
+        else:
+            policy = TanhGaussianPolicy(obs_dim=O, action_dim=A, rs=rs, noise=np.random.RandomState(seed),
+                                        **variant["policy_kwargs"])
+            eval_policy, expl_policy = MakeDeterministic(policy), policy
+            trainer = SACTrainer(env=eval_env, policy=policy, qf1=qf1, qf2=qf2, target_qf1=tqf1, target_qf2=tqf2,
+                                 batch_size=ak["batch_size"], noise_seed=seed, device=device, **tk)
         buf = EnvReplayBuffer(variant["replay_buffer_size"], obs_dim=O, action_dim=A, device=device)
         buf.seed_from_numpy(rs)                               # (the stream np.random would continue with)
-        expl, evalc = PathCollector(expl_env, policy), PathCollector(eval_env, MakeDeterministic(policy))
+        expl, evalc = PathCollector(expl_env, expl_policy), PathCollector(eval_env, eval_policy)
         if ak.get("min_num_steps_before_training", 0) > 0:
             buf.add_paths(expl.collect_new_paths(ak["expl_max_path_length"], ak["min_num_steps_before_training"], False))
             expl.end_epoch(-1)
         runs.append(dict(seed=seed, trainer=trainer, buf=buf, expl=expl, evalc=evalc, rows=[], fh=None, writer=None))
-    group = SACTrainerGroup([r["trainer"] for r in runs])
+    group = (TD3TrainerGroup if td3 else SACTrainerGroup)([r["trainer"] for r in runs])
     t_start = time.time()
     try:
         for epoch in range(num_epochs if num_epochs is not None else ak["num_epochs"]):

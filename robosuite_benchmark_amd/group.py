@@ -1,9 +1,10 @@
-"""SACTrainerGroup: several SAC runs of one configuration trained together (sac_group_* of include/sac_hip.h).
+"""SACTrainerGroup / TD3TrainerGroup: several SAC or TD3 runs of one configuration trained together (sac_group_*,
+td3_group_create of include/sac_hip.h).
 
 The reference's real workload is many independent runs -- seeds x configurations, one job each
 (/root/reference/launch_jobs.sh).  One run at batch 256 cannot fill an MI355X; a group steps R runs of the same shape
-with grouped launches (each launch R times wider) while every member stays an ordinary SACTrainer: its own weights,
-optimizer state, hyperparameters, noise seed and replay buffer, and a result bit for bit that of training alone."""
+with grouped launches (each launch R times wider) while every member stays an ordinary SACTrainer (TD3Trainer): its own
+weights, optimizer state, hyperparameters, noise seed and replay buffer, and a result bit for bit that of training alone."""
 from __future__ import annotations
 
 import ctypes as C
@@ -17,15 +18,22 @@ from .td3 import TD3Trainer
 MAX_MEMBERS = 16
 
 
-class SACTrainerGroup:
+class _TrainerGroup:
+    _CREATE = None              # the C entry point that makes the group (sac_group_create / td3_group_create)
+    _ONLY = None                # why a member of another kind is refused
+
+    @staticmethod
+    def _member_ok(t):
+        raise NotImplementedError
+
     def __init__(self, trainers):
         trainers = list(trainers)
         if not 1 <= len(trainers) <= MAX_MEMBERS:
             raise RuntimeError(f"a trainer group holds 1..{MAX_MEMBERS} trainers (got {len(trainers)})")
         # host metadata first: nothing is created for a group that cannot exist
         for i, t in enumerate(trainers):
-            if isinstance(t, TD3Trainer) or not isinstance(t, SACTrainer):
-                raise RuntimeError(f"trainer group member {i} is a {type(t).__name__}: groups hold SAC trainers only")
+            if not self._member_ok(t):
+                raise RuntimeError(f"trainer group member {i} is a {type(t).__name__}: {self._ONLY}")
         if len({id(t) for t in trainers}) != len(trainers):
             raise RuntimeError("a trainer appears twice in the group")
         t0 = trainers[0]
@@ -56,7 +64,7 @@ class SACTrainerGroup:
             self._destroy()
             arr = (C.c_void_p * len(hs))(*hs)
             g = C.c_void_p()
-            _lib.check(self._lib.sac_group_create(C.byref(g), arr, len(hs)), "sac_group_create")
+            _lib.check(getattr(self._lib, self._CREATE)(C.byref(g), arr, len(hs)), self._CREATE)
             self._g, self._handles = g, hs
         return self._g
 
@@ -111,3 +119,23 @@ class SACTrainerGroup:
             t._host_policy_stale = True
             t._record(first[r])
         return first, last
+
+
+class SACTrainerGroup(_TrainerGroup):
+    _CREATE = "sac_group_create"
+    _ONLY = "groups hold SAC trainers only"
+
+    @staticmethod
+    def _member_ok(t):
+        return isinstance(t, SACTrainer) and not isinstance(t, TD3Trainer)
+
+
+class TD3TrainerGroup(_TrainerGroup):
+    """R TD3 runs of one shape; each member keeps its own delayed-update phase (policy_and_target_update_period and the
+    step count may differ), and train_loop advances each as TD3Trainer.train_loop does."""
+    _CREATE = "td3_group_create"
+    _ONLY = "TD3 groups hold TD3 trainers only"
+
+    @staticmethod
+    def _member_ok(t):
+        return isinstance(t, TD3Trainer)

@@ -1,7 +1,9 @@
-"""Aggregate grad-steps/s of trainer groups (sac_group_train_loop): R SAC runs of Lift (obs 42, act 7) at batch 256 and
-128, each with its own 1e6-slot replay buffer, stepped together with grouped launches.  One JSON line per (batch, R).
+"""Aggregate grad-steps/s of trainer groups (sac_group_train_loop): R SAC (or TD3) runs of Lift (obs 42, act 7) at batch
+256 and 128, each with its own 1e6-slot replay buffer, stepped together with grouped launches.  One JSON line per
+(batch, R).
 
-    python scripts/bench_group.py [--steps 2000] [--warmup 200] [--batches 256 128] [--replicas 1 2 4 8 16]"""
+    python scripts/bench_group.py [--agent SAC|TD3] [--steps 2000] [--warmup 200] [--batches 256 128]
+                                  [--replicas 1 2 4 8 16]"""
 from __future__ import annotations
 
 import argparse
@@ -15,7 +17,7 @@ import numpy as np
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 
 from robosuite_benchmark_amd import (EnvReplayBuffer, FlattenMlp, SACTrainer, SACTrainerGroup,  # noqa: E402
-                                     TanhGaussianPolicy, _lib)
+                                     TanhGaussianPolicy, TanhMlpPolicy, TD3Trainer, TD3TrainerGroup, _lib)
 
 
 def make_trainer(O, A, B, seed):
@@ -27,8 +29,19 @@ def make_trainer(O, A, B, seed):
                       use_automatic_entropy_tuning=True, batch_size=B, noise_seed=seed)
 
 
+def make_td3_trainer(O, A, B, seed):
+    """TD3 with the default variant's trainer_kwargs (bench.py --agent TD3's: policy_and_target_update_period 2)."""
+    rs = np.random.RandomState(seed)
+    qs = [FlattenMlp([256, 256], 1, O + A, rs=rs) for _ in range(4)]
+    pols = [TanhMlpPolicy([256, 256], A, O, rs=rs) for _ in range(2)]
+    return TD3Trainer(policy=pols[0], qf1=qs[0], qf2=qs[1], target_qf1=qs[2], target_qf2=qs[3], target_policy=pols[1],
+                      target_policy_noise=0.2, discount=0.99, reward_scale=1.0, policy_learning_rate=1e-3,
+                      qf_learning_rate=5e-4, policy_and_target_update_period=2, tau=0.005, batch_size=B, noise_seed=seed)
+
+
 def main():
     ap = argparse.ArgumentParser()
+    ap.add_argument("--agent", type=str, default="SAC", choices=["SAC", "TD3"])
     ap.add_argument("--steps", type=int, default=2000)
     ap.add_argument("--warmup", type=int, default=200)
     ap.add_argument("--buffer", type=int, default=1_000_000)
@@ -52,8 +65,9 @@ def main():
         bufs.append(b)
     for B in args.batches:
         for R in args.replicas:
-            trainers = [make_trainer(O, A, B, 10 + r) for r in range(R)]
-            group = SACTrainerGroup(trainers)
+            make, Group = (make_td3_trainer, TD3TrainerGroup) if args.agent == "TD3" else (make_trainer, SACTrainerGroup)
+            trainers = [make(O, A, B, 10 + r) for r in range(R)]
+            group = Group(trainers)
             group.train_loop(bufs[:R], args.warmup, batch_size=B)
             t0 = time.perf_counter()
             _, last = group.train_loop(bufs[:R], args.steps, batch_size=B)

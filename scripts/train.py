@@ -2,7 +2,8 @@
 """Counterpart of the reference's scripts/train.py for the MI355X path:
     python scripts/train.py --variant <variant.json> --seed S --log_dir DIR [--epochs N]
     python scripts/train.py --variant <variant.json> --seeds S1 S2 ... --log_dir DIR [--epochs N]
-(--seeds: one process trains every seed, the training blocks as one trainer group; DIR/s<seed>/progress.csv each)
+(--seeds: one process trains every seed, the training blocks as one trainer group, SAC or TD3 (--agent);
+ DIR/s<seed>/progress.csv each)
 Runs the variant unchanged (batch size, lrs, tau, period, buffer size ... from the JSON) on the
 HIP library with a synthetic environment of the task's dimensions (robosuite is not installed)."""
 import argparse
@@ -26,7 +27,8 @@ if __name__ == "__main__":
                     help="an existing run directory (…_0000--s-0): continue it from its checkpoint/ after the last saved epoch")
     ap.add_argument("--no_checkpoint", action="store_true", help="do not save <run_dir>/checkpoint after every epoch")
     ap.add_argument("--seeds", type=int, nargs="+", default=None,
-                    help="train these seeds of the one configuration together (trainer groups; SAC, no checkpoints)")
+                    help="train these seeds of the one configuration together (trainer groups; SAC or TD3, no "
+                         "checkpoints)")
     args = ap.parse_args()
     if args.seeds:
         if args.resume:
