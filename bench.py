@@ -5,7 +5,12 @@ A "step" = one pass of the hot path over one minibatch: random_batch index draw 
 one full SAC gradient step (rlkit_custom.py:234-238 of the reference), with the replay buffer
 already resident in HBM when the timed region starts.
 
-    python bench.py --gpus N --steps K --warmup W [--dump-outputs DIR]
+    python bench.py --gpus N --steps K --warmup W [--dump-outputs DIR] [--full]
+
+A plain run sets up (replay buffer, trainer and, on one GPU, the measured peaks, which also bring the clocks up), warms
+up, times the K steps, writes --dump-outputs and prints the JSON line.  `--full` then measures everything else: per-kernel
+durations and roofline figures, the gather at 1 and 1000 steps per launch, the per-call fixed cost, the CPU baseline, the
+stepwise interface, ingest, the general step's shapes, concurrent replicas.
 
 N = 1: BASELINE.json configs[1] (Lift-Panda-OSC-POSE: obs 42 / act 7, batch 256, 1e6-slot buffer, full).
 N > 1: one independent replica per GPU (independent seed of the same workload; `--sweep` runs the
@@ -264,14 +269,6 @@ def td3_main(args):
     el = time.perf_counter() - t0
     if args.dump_outputs:                          # (before the stepwise data point trains on)
         dump_outputs(args.dump_outputs, first, last, tr)
-    for _ in range(50):
-        tr.train(buf.random_batch(B))
-    tr._lib.sac_sync(tr._h)
-    t1 = time.perf_counter()
-    for _ in range(args.steps):
-        tr.train(buf.random_batch(B))
-    tr._lib.sac_sync(tr._h)
-    el2 = time.perf_counter() - t1
     P, Q = O * H + H * H + H * A, (O + A) * H + H * H + H
     # algorithmic FLOPs per step: critic pass every step, actor pass every 2nd (SURVEY.md 8d formulas adapted)
     critic = 2 * B * (P + 4 * Q) + 2 * 2 * B * (Q + H * H + H)
@@ -287,9 +284,18 @@ def td3_main(args):
                roofline=dict(bound="mfma", unit="TFLOP/s", peak=PEAK_FP32_MFMA_TFLOPS, gflop_per_step=round(gflop, 4),
                              achieved=round(gflop * args.steps / el / 1e3, 3),
                              frac=round(gflop * args.steps / el / 1e3 / PEAK_FP32_MFMA_TFLOPS, 5), traffic=None),
-               stepwise_interface=dict(value=round(args.steps / el2, 2), unit="grad-steps/s"),
-               final={"QF1 Loss": float(last[0]), "Policy Loss": float(last[2])},
-               cpu_baseline=None if args.no_cpu_baseline else cpu_baseline_td3(O, A, B))
+               final={"QF1 Loss": float(last[0]), "Policy Loss": float(last[2])})
+    if args.full:
+        for _ in range(50):
+            tr.train(buf.random_batch(B))
+        tr._lib.sac_sync(tr._h)
+        t1 = time.perf_counter()
+        for _ in range(args.steps):
+            tr.train(buf.random_batch(B))
+        tr._lib.sac_sync(tr._h)
+        el2 = time.perf_counter() - t1
+        out["stepwise_interface"] = dict(value=round(args.steps / el2, 2), unit="grad-steps/s")
+        out["cpu_baseline"] = None if args.no_cpu_baseline else cpu_baseline_td3(O, A, B)
     print(json.dumps(out), flush=True)
 
 
@@ -432,9 +438,12 @@ def main():
     ap.add_argument("--sweep", action="store_true", help="N>1: 8-task sweep (BASELINE configs[4]) instead of seeds")
     ap.add_argument("--task", type=str, default=None,
                     help="N=1 only: another task of the sweep table (e.g. Door, TwoArmHandoff); default Lift")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--no-stepwise", action="store_true", help="skip the extra stepwise-interface data point")
-    ap.add_argument("--no-peaks", action="store_true", help="skip the measured-peak microbenchmarks (spec peaks only)")
+    ap.add_argument("--full", action="store_true",
+                    help="after the timed steps, also measure everything beside the headline (per-kernel and roofline figures, "
+                         "CPU baseline, stepwise interface, ingest, general step, concurrent replicas)")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="--full: skip the CPU baseline")
+    ap.add_argument("--no-stepwise", action="store_true", help="--full: skip the extra stepwise-interface data point")
+    ap.add_argument("--no-peaks", action="store_true", help="skip the measured-peak microbenchmarks before the warm-up (spec peaks only)")
     ap.add_argument("--backend", type=str, default="nccl", help="collective backend for N>1 (nccl == RCCL; gloo for rehearsals)")
     ap.add_argument("--single-device", action="store_true",
                     help="rehearsal on a one-GPU box: every rank computes on device 0 (use with --backend gloo)")
@@ -447,19 +456,22 @@ def main():
     ap.add_argument("--force-dist", action="store_true",
                     help="N=1: still initialise the process group (world size 1) so that the N>1 branch -- RCCL set-up, "
                          "barriers, max-over-ranks, the result all-gather -- runs on a one-GPU box")
-    ap.add_argument("--profile-steps", type=int, default=500)
+    ap.add_argument("--profile-steps", type=int, default=500, help="--full: steps of the per-kernel profiled replay")
     ap.add_argument("--agent", type=str, default="SAC", choices=["SAC", "TD3"],
                     help="TD3: the SURVEY 8f row on the same workload shape (N=1, its own JSON line); default SAC = the headline metric")
-    ap.add_argument("--xcd-replicas", action="store_true", help="with --replicas-per-gpu: confine replica i to XCD i % 8")
+    ap.add_argument("--xcd-replicas", action="store_true", help="with --replicas-per-gpu: confine replica i to XCD i %% 8")
     ap.add_argument("--fused-replicas", action="store_true", help="with --replicas-per-gpu: the replicas keep the fused step")
     ap.add_argument("--split-replicas", action="store_true",
                     help="with --replicas-per-gpu R: replica i owns 8/R XCDs (CU-masked streams) and keeps the fused step if it fits them")
     ap.add_argument("--replicas-per-gpu", type=int, default=0,
-                    help="N=1 only: also time R concurrent independent runs on the GPU (reported beside, never as, value)")
+                    help="N=1 and --full only: also time R concurrent independent runs on the GPU (reported beside, never as, "
+                         "value)")
     ap.add_argument("--dump-outputs", type=str, default=None, metavar="DIR",
                     help="after the timed steps, write what the timed call computed (diagnostics of its first and last "
                          "step, the trainer state after its last step) as DIR/<name>.npy; rank 0 only")
     args = ap.parse_args()
+    if args.replicas_per_gpu > 1 and not args.full:
+        ap.error("--replicas-per-gpu is a --full data point")
 
     if args.agent == "TD3":
         if args.gpus != 1:
@@ -498,7 +510,9 @@ def main():
         import torch
         trainer, buf = build_replica(task, O, A, B, args.buffer, seed=seed, device=local_rank)
         if world == 1 and not args.no_peaks:
-            peaks = measure_peaks(local_rank)                          # (before the timed region: also ramps the clocks)
+            # (every run, not only --full: it also ramps the clocks, and the headline has always been timed right after it
+            #  -- eight alternating 20-step runs each on one MI355X: median 33.3 k steps/s with it, 32.5 k without)
+            peaks = measure_peaks(local_rank)
 
         def sync():
             torch.cuda.synchronize()
@@ -571,7 +585,10 @@ def main():
             out["data"] = "none (--dry-run: ranks sleep instead of training; plumbing test only, not a measurement)"
             out["dry_run"] = True
         else:
-            out.update(device_report(args, trainer, buf, task, O, A, B, world, value, elapsed_max, peaks, local_rank))
+            out["device_ms"] = {k: round(v, 3) for k, v in trainer.loop_timing_ms().items()}
+            out["peaks_measured"] = peaks
+            if args.full:
+                out.update(device_report(args, trainer, buf, task, O, A, B, world, value, out["device_ms"], peaks, local_rank))
     barrier()
     if dist is not None:
         dist.destroy_process_group()
@@ -579,9 +596,10 @@ def main():
         print(json.dumps(out), flush=True)
 
 
-def device_report(args, trainer, buf, task, O, A, B, world, value, elapsed_max, peaks, device):
-    """Everything of the JSON line that comes from the device after the timed region (rank 0)."""
-    out = {"device_ms": {k: round(v, 3) for k, v in trainer.loop_timing_ms().items()}}
+def device_report(args, trainer, buf, task, O, A, B, world, value, device_ms, peaks, device):
+    """--full: everything of the JSON line that comes from the device after the timed region beside the timed loop's own
+    device times (rank 0)."""
+    out = {}
     # ---- per-kernel durations: instrumented replay of the same loop (HIP events on the
     #      launching streams) ------------------------------------------------------------------
     nprof = min(args.profile_steps, args.steps, 4096)
@@ -607,7 +625,7 @@ def device_report(args, trainer, buf, task, O, A, B, world, value, elapsed_max, 
     # back: (timed step - sum of the intervals) / launches per step.  `achieved` uses that longer duration.
     # The step time is the DEVICE time of the timed loop (events on the trainer's stream), so the per-call fixed
     # cost of a short loop does not leak into a kernel's duration.
-    step_ms = out["device_ms"]["steps"] / args.steps
+    step_ms = device_ms["steps"] / args.steps
     boundary_ms = max(0.0, (step_ms - sum(prof[k] for k in fl)) / len(fl))
     dom_ms = prof[dom] + boundary_ms
     achieved = fl[dom] / (dom_ms * 1e-3) / 1e12
@@ -643,7 +661,6 @@ def device_report(args, trainer, buf, task, O, A, B, world, value, elapsed_max, 
                                   in_loop=dict(steps_per_launch=nprof, achieved=kern["k_gather"]["gbs"],
                                                frac=round(kern["k_gather"]["gbs"] / PEAK_HBM_GBS, 5)),
                                   traffic=pmc_traffic("k_gather", workload_tag(task, B))[0])
-    out["peaks_measured"] = peaks
     out["kernels"] = kern
     # ---- fixed cost of one sac_train_loop call: t(n) = fixed + n * per_step from two loop lengths -------
     if world == 1:

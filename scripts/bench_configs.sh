@@ -5,7 +5,7 @@ out=gpurun_out/configs_$tag.jsonl
 : > $out
 for cfg in "Door 1024" "Lift 512" "TwoArmLift 256" "Wipe 256" "Lift 128" "Lift 2048" "Lift 4096"; do
   set -- $cfg
-  python bench.py --task $1 --batch $2 --no-cpu-baseline --steps 1000 --warmup 100 >> $out 2>> gpurun_out/configs_$tag.err || exit 1
+  python bench.py --task $1 --batch $2 --no-cpu-baseline --full --steps 1000 --warmup 100 >> $out 2>> "${out%.jsonl}.err" || exit 1
 done
 python - <<PY
 import json

@@ -1,6 +1,6 @@
 # three default-length runs (2000 steps) without the extras: value, per-kernel execution and boundary
 for i in 1 2 3; do
-  timeout -k 10 200 python bench.py --no-cpu-baseline --no-stepwise 2>/dev/null | python3 -c "
+  timeout -k 10 200 python bench.py --no-cpu-baseline --no-stepwise --full 2>/dev/null | python3 -c "
 import json,sys
 d=json.loads(sys.stdin.read())
 r=d['roofline']

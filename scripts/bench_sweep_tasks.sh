@@ -4,7 +4,7 @@
 out=gpurun_out/sweep_tasks.jsonl
 : > $out
 for t in Lift Door Stack Wipe PickPlaceCan NutAssemblyRound TwoArmPegInHole TwoArmHandoff; do
-  timeout -k 10 200 python bench.py --task $t --no-cpu-baseline --no-stepwise --no-peaks --steps 1000 --warmup 100 >> $out 2>/dev/null || exit 1
+  timeout -k 10 200 python bench.py --task $t --no-cpu-baseline --no-stepwise --no-peaks --full --steps 1000 --warmup 100 >> $out 2>/dev/null || exit 1
 done
 python3 - <<PY
 import json

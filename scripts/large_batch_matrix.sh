@@ -8,7 +8,7 @@ mkdir -p "$(dirname "$out")"
 run() {   # label, task, batch, env...
   label=$1; task=$2; batch=$3; shift 3
   line=$(env "$@" python bench.py --task "$task" --batch "$batch" --steps 600 --warmup 60 --buffer 200000 --no-cpu-baseline \
-         --no-stepwise --no-peaks --profile-steps 300 2>/dev/null | tail -1)
+         --no-stepwise --no-peaks --profile-steps 300 --full 2>/dev/null | tail -1)
   python - "$label" "$task" "$batch" "$line" >> "$out" <<'PY'
 import json, sys
 label, task, batch, line = sys.argv[1:5]

@@ -11,7 +11,7 @@ mkdir -p $out
 cd /tmp && export TMPDIR=/tmp && cd - > /dev/null
 wl=$(python3 -c "print('${task}'.lower() + '_b${batch}')")
 # (the fused loop only: --no-stepwise keeps the stepwise data point, whose steps interleave with per-batch gathers, out of the averages)
-rocprofv3 --kernel-trace --stats --output-format csv -d $out/trace -- python3 bench.py --task $task --batch $batch --no-cpu-baseline --no-stepwise --no-peaks > $out/bench_under_rocprof.json 2> $out/trace.log
+rocprofv3 --kernel-trace --stats --output-format csv -d $out/trace -- python3 bench.py --task $task --batch $batch --no-cpu-baseline --no-stepwise --no-peaks --full > $out/bench_under_rocprof.json 2> $out/trace.log
 for pass in "fetch FETCH_SIZE" "write WRITE_SIZE" "mfma SQ_VALU_MFMA_BUSY_CYCLES SQ_BUSY_CYCLES SQ_WAVE_CYCLES SQ_INSTS_VALU_MFMA_MOPS_F32"; do
   set -- $pass
   name=$1; shift
@@ -21,5 +21,5 @@ done
 python3 scripts/make_pmc_traffic.py $out/pmc_fetch.json $out/pmc_write.json $out/pmc_mfma.json $wl > $out/pmc_traffic.json
 cp $(find $out/trace -name "*kernel_stats.csv" | head -1) $out/kernel_stats.csv
 rm -rf $out/trace $out/fetch $out/write $out/mfma
-python3 bench.py --task $task --batch $batch > $out/bench_default.json 2> $out/bench_default.err
+python3 bench.py --task $task --batch $batch --full > $out/bench_default.json 2> $out/bench_default.err
 tail -c 400 $out/bench_default.json

@@ -87,11 +87,35 @@ def test_torchrun_style_environment_is_still_honoured():
 def test_two_ranks_share_the_one_gpu_of_this_box():
     """The N = 2 path end to end on real kernels: two self-launched ranks, both on device 0, gloo for the collective."""
     p = run_bench("--gpus", "2", "--backend", "gloo", "--single-device", "--steps", "60", "--warmup", "10", "--buffer",
-                  "50000", timeout=900)
+                  "50000", "--full", timeout=900)
     assert p.returncode == 0, p.stderr[-3000:]
     d = json.loads([l for l in p.stdout.splitlines() if l.strip().startswith("{")][0])
     assert d["n_gpus"] == 2 and len(d["per_gpu"]) == 2 and d["value"] > 0
+    assert "roofline" in d and "roofline_gather" in d
     assert all(x[1] == x[1] for x in d["per_gpu"])          # finite losses from both ranks
+
+
+def test_concurrent_replicas_are_a_full_run_data_point():
+    p = run_bench("--gpus", "1", "--dry-run", "--steps", "3", "--warmup", "1", "--replicas-per-gpu", "2")
+    assert p.returncode != 0 and "--full" in p.stderr
+    assert not [l for l in p.stdout.splitlines() if l.strip().startswith("{")]
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("agent", ["SAC", "TD3"])
+def test_a_plain_run_reports_the_timed_steps_alone(agent):
+    """Without --full the run sets up, warms up, times its steps and prints the line: no profiled replay, CPU baseline or
+    other extra data point."""
+    p = run_bench("--gpus", "1", "--agent", agent, "--steps", "40", "--warmup", "5", "--buffer", "20000", timeout=900)
+    assert p.returncode == 0, p.stderr[-3000:]
+    d = json.loads([l for l in p.stdout.splitlines() if l.strip().startswith("{")][0])
+    assert d["steps"] == 40 and d["warmup"] == 5 and d["value"] > 0 and d["ms_per_step"] > 0
+    assert d["unit"] == "grad-steps/s" and d["higher_is_better"] is True and d["dtype"] == "f32"
+    extras = {"kernels", "roofline_gather", "fixed_call_us", "short_loop", "cpu_baseline",
+              "stepwise_interface", "ingest", "general_step", "concurrent_replicas"}
+    if agent == "SAC":              # (the TD3 line's roofline is computed from its timed steps alone)
+        extras.add("roofline")
+    assert not extras & set(d), sorted(extras & set(d))
 
 
 def test_dump_outputs_writes_the_timed_calls_diagnostics(tmp_path):

@@ -64,8 +64,10 @@ def test_world_size_one_nccl_group_runs_the_result_collectives_on_device_tensors
 def test_bench_nccl_branch_runs_with_force_dist():
     r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "1", "--force-dist", "--backend", "nccl",
                         "--steps", "20", "--warmup", "5", "--buffer", "100000", "--no-cpu-baseline", "--no-stepwise",
-                        "--no-peaks", "--profile-steps", "20"], env=_env(), capture_output=True, text=True, timeout=900)
+                        "--no-peaks", "--profile-steps", "20", "--full"], env=_env(), capture_output=True, text=True,
+                       timeout=900)
     assert r.returncode == 0, r.stdout[-2000:] + r.stderr[-4000:]
     line = json.loads([l for l in r.stdout.splitlines() if l.startswith("{")][-1])
     assert line["n_gpus"] == 1 and line["value"] > 0 and len(line["per_gpu"]) == 1
+    assert "roofline" in line and "kernels" in line
     assert "shared memory" in line["ranks_barrier"] or "nccl" in line["ranks_barrier"]
