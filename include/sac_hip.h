@@ -345,6 +345,16 @@ int sac_group_create(sac_group_t **out, sac_trainer_t *const *members, int n_mem
  * step (its Policy Loss / Policy Action from the actor pass that step always runs) and diag_last the most recent value of
  * every entry at the end of the call (the policy entries: of the member's last actor pass), as sac_train_loop's do. */
 int td3_group_create(sac_group_t **out, sac_trainer_t *const *members, int n_members);
+/* Mixed groups: runs of DIFFERENT tasks (a sweep of tasks x seeds) on one device.  1..SAC_GROUP_MAX trainers of one
+ * algorithm (sac_group_create_mixed: SAC, td3_group_create_mixed: TD3) whose obs_dim, act_dim (at most 16) and batch
+ * (1..256 rows) may differ per member; hidden sizes and the device must still agree, and every other refusal of
+ * sac_group_create holds.  Members of one kernel variant (head tiles from act_dim, first-layer width from obs_dim)
+ * share one grouped launch per step kernel; the variants follow one another on the group's stream.  Buffer r must have
+ * member r's dims, and member r draws n_steps batches of its own batch size from it; buffers bound to one host generator
+ * continue it in member order with each member's batch.  Each member's result is bit for bit that of
+ * sac_train_loop(members[r], buffers[r], n_steps).  sac_group_train_loop and sac_group_destroy serve mixed groups too. */
+int sac_group_create_mixed(sac_group_t **out, sac_trainer_t *const *members, int n_members);
+int td3_group_create_mixed(sac_group_t **out, sac_trainer_t *const *members, int n_members);
 int sac_group_destroy(sac_group_t *g);
 int sac_group_train_loop(sac_group_t *g, sac_buffer_t *const *buffers, int64_t n_steps, float *diag_first,
                          float *diag_last);

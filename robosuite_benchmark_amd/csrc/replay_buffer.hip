@@ -117,10 +117,12 @@ __global__ __launch_bounds__(256) void k_mt_randint(MtState *st, uint32_t rng, u
     mt_randint_body(st, rng, mask, count, out, bt, bp);
 }
 
-// Grouped draw (sac_group_train_loop): workgroup r draws n_batches x bt indices from generator r, exactly as
-// k_mt_randint would on its own.  A buffer of one row (rng == 0) consumes no draws (NumPy): its indices are all zero.
-__global__ __launch_bounds__(256) void k_mt_randint_group(const SampleMember *__restrict__ M, int64_t n_batches, int bt, int bp) {
+// Grouped draw (sac_group_train_loop): workgroup r draws n_batches x bt indices (its member's own batch) from generator r,
+// exactly as k_mt_randint would on its own.  A buffer of one row (rng == 0) consumes no draws (NumPy): its indices are
+// all zero.
+__global__ __launch_bounds__(256) void k_mt_randint_group(const SampleMember *__restrict__ M, int64_t n_batches) {
     const SampleMember &m = M[blockIdx.x];
+    const int bt = m.bt, bp = m.bp;
     if (m.rng == 0) {
         for (int64_t i = threadIdx.x; i < (int64_t)bp * n_batches; i += 256) m.out[i] = 0;
         return;
@@ -331,12 +333,15 @@ __global__ __launch_bounds__(256) void k_gather(ReplayView rv, const int64_t *__
 }
 
 // Grouped gather (sac_group_train_loop): member blockIdx.y gathers its own indices from its own buffer into its own
-// slots; each member keeps the x-extent and block map of a solo launch.
+// slots, in its own slot layout and batch.  The blocks stride by the launch's x-extent (the largest solo extent of the
+// members it covers); a member with fewer 16-row blocks than that leaves its surplus workgroups at entry.
 template <int NIT>
-__global__ __launch_bounds__(256) void k_gather_group(const GatherMember *__restrict__ M, int B, int64_t n_blocks_total,
-                                                      SlotLayout L, int write_saT) {
+__global__ __launch_bounds__(256) void k_gather_group(const GatherMember *__restrict__ M, int64_t n_batches, int write_saT) {
     const GatherMember &m = M[blockIdx.y];
-    gather_body<NIT>(m.rv, m.idx, B, n_blocks_total, m.slots, L, write_saT);
+    const int64_t nblk = (int64_t)(m.B / RB) * n_batches;
+    if ((int64_t)blockIdx.x >= nblk) return;
+    const SlotLayout L = m.L;
+    gather_body<NIT>(m.rv, m.idx, m.B, nblk, m.slots, L, write_saT);
 }
 #undef GATHER_LOAD_IDX
 #undef GATHER_ISSUE_ROWS
@@ -573,25 +578,21 @@ int launch_gather(sac_buffer *b, const int64_t *d_idx, int batch, int64_t n_batc
     return 0;
 }
 
-int launch_sample_group(const SampleMember *d_tab, int R, int batch, int64_t n_batches, hipStream_t on) {
-    SAC_REQUIRE(R > 0 && batch > 0 && n_batches > 0, "bad grouped draw");
-    hipLaunchKernelGGL(k_mt_randint_group, dim3(R), dim3(256), 0, on, d_tab, n_batches, batch, round_up(batch, RB));
+int launch_sample_group(const SampleMember *d_tab, int R, int64_t n_batches, hipStream_t on) {
+    SAC_REQUIRE(R > 0 && n_batches > 0, "bad grouped draw");
+    hipLaunchKernelGGL(k_mt_randint_group, dim3(R), dim3(256), 0, on, d_tab, n_batches);
     SAC_HIP(hipGetLastError());
     return 0;
 }
 
-int launch_gather_group(const GatherMember *d_tab, int R, const sac_buffer *shape, int batch, int64_t n_batches,
-                        const SlotLayout &L, int write_saT, hipStream_t on) {
-    SAC_REQUIRE(batch > 0 && batch % RB == 0, "batch size %d must be a positive multiple of %d", batch, RB);
-    const int64_t nblk = (int64_t)(batch / RB) * n_batches;
-    SAC_REQUIRE(nblk < (1LL << 30), "too many rows in one gather launch");
-    const int grid = (int)(nblk < 1024 ? nblk : 1024);          // (the x-extent of a solo launch_gather)
-    const size_t lds = sizeof(float) * (size_t)(2 * RB * shape->Ost + RB * shape->Ast);
+int gather_nit(const sac_buffer *b) { return (RB * (b->Ost >> 2) + 255) / 256; }
+
+int launch_gather_group(const GatherMember *d_tab, int R, int nit, int64_t n_batches, int grid, size_t lds, int write_saT,
+                        hipStream_t on) {
+    SAC_REQUIRE(R > 0 && grid > 0 && grid <= 1024 && n_batches > 0 && 16 * n_batches < (1LL << 30), "bad grouped gather");
     SAC_REQUIRE(lds <= 64 * 1024, "observation rows too wide for the gather tile (%zu B LDS)", lds);
-    const int nit = (RB * (shape->Ost >> 2) + 255) / 256;
-    SAC_REQUIRE(nit <= 8, "observation rows too wide for the gather kernel (obs_dim %d)", shape->O);
-#define SAC_GATHER_LAUNCH(N) \
-    hipLaunchKernelGGL(k_gather_group<N>, dim3(grid, R), dim3(256), lds, on, d_tab, batch, nblk, L, write_saT)
+    SAC_REQUIRE(nit >= 1 && nit <= 8, "observation rows too wide for the gather kernel");
+#define SAC_GATHER_LAUNCH(N) hipLaunchKernelGGL(k_gather_group<N>, dim3(grid, R), dim3(256), lds, on, d_tab, n_batches, write_saT)
     if (nit <= 1) SAC_GATHER_LAUNCH(1);
     else if (nit <= 2) SAC_GATHER_LAUNCH(2);
     else if (nit <= 4) SAC_GATHER_LAUNCH(4);

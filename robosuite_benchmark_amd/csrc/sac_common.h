@@ -185,11 +185,14 @@ struct SampleMember {
     sac::MtState *st;
     int64_t *out;                 // the member's indices (padded layout of launch_sample)
     uint32_t rng, mask;           // size - 1 and its bit mask (rng == 0: a one-row buffer, no draws)
+    int bt, bp;                   // the member's batch and its padded row count (a multiple of 16)
 };
 struct GatherMember {
     ReplayView rv;
     const int64_t *idx;
     float *slots;
+    sac::SlotLayout L;            // the member's slot layout (its own batch and dims)
+    int B;                        // padded batch (L.B): B / 16 row-blocks per batch
 };
 
 // slot of a live device batch (sac_random_batch_device token), or -1 with the error set (internal)
@@ -206,10 +209,13 @@ int launch_sample(sac_buffer *b, int batch, int64_t n_batches, int64_t idx_offse
                   hipStream_t on = nullptr);
 int launch_gather(sac_buffer *b, const int64_t *d_idx, int batch, int64_t n_batches, float *d_slots,
                   const SlotLayout &L, int write_saT, hipStream_t on = nullptr);
-// grouped forms of the two (tables in device memory, R members of one shape): ONE launch each for all R buffers
-int launch_sample_group(const SampleMember *d_tab, int R, int batch, int64_t n_batches, hipStream_t on);
-int launch_gather_group(const GatherMember *d_tab, int R, const sac_buffer *shape, int batch, int64_t n_batches,
-                        const SlotLayout &L, int write_saT, hipStream_t on);
+// grouped forms of the two (tables in device memory, each entry with its own batch and layout): one draw launch for all
+// R buffers; one gather launch per gather_nit class (x-extent `grid`: the largest min(B / 16 x n_batches, 1024) of the
+// class, dynamic LDS `lds`: its largest tile)
+int launch_sample_group(const SampleMember *d_tab, int R, int64_t n_batches, hipStream_t on);
+int gather_nit(const sac_buffer *b);                 // obs 16-B chunks per gather thread (k_gather's NIT before rounding)
+int launch_gather_group(const GatherMember *d_tab, int R, int nit, int64_t n_batches, int grid, size_t lds, int write_saT,
+                        hipStream_t on);
 // undo the stepwise interface's read-ahead (see sac_buffer::ra_ahead); to be called in front of anything that reads or
 // changes the generator's state, the buffer's rows or its size
 int readahead_rollback(sac_buffer *b);

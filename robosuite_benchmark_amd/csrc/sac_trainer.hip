@@ -1728,6 +1728,10 @@ __global__ __launch_bounds__(256) void k_dw_adam(Dev d, DwTable T, const float *
 // in device memory (uniform index: scalar loads) instead of the kernel argument segment; the per-step StepArg is a
 // [step][R] table the host writes once per chunk (bc1 / bc2s stay host-computed doubles).  No workgroup waits for
 // another one: a grouped grid may be far larger than what is resident at once.
+// A mixed group (sac_group_create_mixed) holds members of different shapes: one launch per variant class spans the
+// class's largest x-extent, and a block past its own member's extent (xa / xb / xc / xpi; k_dw_adam_group: its table's
+// njobs + 1) leaves at entry, before any LDS use or barrier -- a uniform exit per block.  Below it, the member keeps its
+// solo block -> work map: the bodies read d.NB, never gridDim.
 // ------------------------------------------------------------------------------------------
 struct GroupMember {
     Dev d;
@@ -1735,6 +1739,7 @@ struct GroupMember {
     SlotLayout SL;
     const float *slots;            // the member's loop slot 0: slot j at slots + j * SL.slot_floats
     DwTable T_tp, T_pi, T_none;    // TD3 only: dw_q_tp, dw_pi, dw_none (launch_step_td3's other tables)
+    int xa, xb, xc, xpi;           // the member's solo x-extents: launch A, B, C; TD3 actor pass B / C
 };
 // A TD3 member's step (the [step][R] table of a TD3 group): launch_step_td3's two StepArgs and its plan.  Members may be
 // in different phases of the delayed update, so the actor launches of a step run for every member that needs them and
@@ -1754,6 +1759,7 @@ template <int NTH, bool WIDE, int SP, int MODE = M_SAC>
 __global__ __launch_bounds__(256) void k_fwd_a_group(const GroupMember *__restrict__ G, const GroupStep<MODE> *__restrict__ SA,
                                                      int slot) {
     const GroupMember &g = G[blockIdx.y];
+    if ((int)blockIdx.x >= g.xa) return;
     int aux = 0;
     if constexpr (MODE != M_SAC) aux = SA[blockIdx.y].actor;
     fwd_a_body<NTH, WIDE, SP, MODE>(g.d, g.slots + (size_t)slot * g.SL.slot_floats, g.SL, aux);
@@ -1762,6 +1768,7 @@ template <int NTH, bool WIDE, int SP, int MODE = M_SAC>
 __global__ __launch_bounds__(256) void k_fwd_b_group(const GroupMember *__restrict__ G, const GroupStep<MODE> *__restrict__ SA,
                                                      int slot) {
     const GroupMember &g = G[blockIdx.y];
+    if ((int)blockIdx.x >= (MODE == M_TD3_ACTOR ? g.xpi : g.xb)) return;
     const float *S = g.slots + (size_t)slot * g.SL.slot_floats;
     if constexpr (MODE == M_SAC) fwd_b_body<NTH, WIDE, SP>(g.d, S, g.SL, SA[blockIdx.y]);
     else if constexpr (MODE == M_TD3_CRITIC) fwd_b_body<NTH, WIDE, SP, MODE>(g.d, S, g.SL, SA[blockIdx.y].sq);
@@ -1774,6 +1781,7 @@ template <int NTH, int SP, int MODE = M_SAC>
 __global__ __launch_bounds__(256) void k_bwd_group(const GroupMember *__restrict__ G, const GroupStep<MODE> *__restrict__ SA,
                                                    int slot, int compact) {
     const GroupMember &g = G[blockIdx.y];
+    if ((int)blockIdx.x >= (MODE == M_TD3_ACTOR ? g.xpi : g.xc)) return;
     const float *S = g.slots + (size_t)slot * g.SL.slot_floats;
     if constexpr (MODE == M_SAC) bwd_body<NTH, SP>(g.d, S, g.SL, SA[blockIdx.y], compact);
     else if constexpr (MODE == M_TD3_CRITIC) bwd_body<NTH, SP, MODE>(g.d, S, g.SL, SA[blockIdx.y].sq, compact);
@@ -3407,7 +3415,10 @@ int sac_policy_act(sac_trainer_t *t, const float *obs, int deterministic, const 
 
 // ==========================================================================================
 // Trainer groups: R SAC trainers of one shape stepped together, four grouped launches per step (see GroupMember) -- or R
-// TD3 trainers (td3_group_create), launch_step_td3's four to seven launches per step, each one grouped.
+// TD3 trainers (td3_group_create), launch_step_td3's four to seven launches per step, each one grouped.  A mixed group
+// (sac_group_create_mixed / td3_group_create_mixed) takes members of different dims and batches: each launch A, B, C is
+// issued once per variant class (GroupClass), the weight-gradient launch once for all; draws take each member's batch,
+// gathers go one launch per NIT class.
 // The loop is sac_train_loop's for every member at once -- same index stream per buffer, same steps, same results bit
 // for bit -- without its latency devices (no speculative next chunk, no stepwise read-ahead): chunks of LOOP_CH steps
 // alternate between the two halves of each buffer's loop slots; the draws and gathers of a chunk run on the group's
@@ -3415,18 +3426,13 @@ int sac_policy_act(sac_trainer_t *t, const float *obs, int deterministic, const 
 // trainer or group on the device, fused members included: then every grouped launch, draws and gathers too, is
 // serialised behind the gate's last launch, at a cost of ~0.3 ms per 256-step chunk).
 // ==========================================================================================
-struct sac_group {
-    int R = 0, device = 0, algo = 0;                  // algo: 0 SAC, 1 TD3 (every member's)
-    sac_trainer *m[SAC_GROUP_MAX] = {};
-    hipStream_t s = nullptr, s2 = nullptr;           // steps / draws + gathers
-    hipEvent_t ev_ready[2] = {}, ev_done[2] = {}, ev_copied[2] = {}, ev_end = nullptr;
-    hipEvent_t ev_in[2 * SAC_GROUP_MAX] = {};         // the members' and the buffers' streams in front of a call
-    char *d_tab = nullptr, *h_tab = nullptr;          // device tables and their pinned host images
-    GroupMember *d_mem = nullptr, *h_mem = nullptr;   // [R]
-    SampleMember *d_smp = nullptr, *h_smp = nullptr;  // [2 halves][R]
-    GatherMember *d_gat = nullptr, *h_gat = nullptr;  // [2 halves][R]
-    StepArg *d_sa = nullptr, *h_sa = nullptr;         // SAC: [2 halves][LOOP_CH steps][R]
-    Td3GroupStep *d_ts = nullptr, *h_ts = nullptr;    // TD3: [2 halves][LOOP_CH steps][R]
+// One variant class of a group: the members whose step runs the same instances of the grouped kernels (the class is a
+// contiguous range of the device tables), the largest x-extent and dynamic LDS among them.  A group of one shape is one
+// class; a mixed group (sac_group_create_mixed) has up to four, one grouped launch each per step kernel.
+struct GroupClass {
+    int lo = 0, n = 0;                                // device table entries lo .. lo + n - 1
+    int xa = 0, xb = 0, xc = 0, xpi = 0;              // the largest member extent (GroupMember::xa ..)
+    size_t lds_fa = 0, lds_fb = 0, lds_bw = 0;        // the largest member LDS
     void (*fa)(const GroupMember *, const StepArg *, int) = nullptr;
     void (*fb)(const GroupMember *, const StepArg *, int) = nullptr;
     void (*bw)(const GroupMember *, const StepArg *, int, int) = nullptr;
@@ -3434,6 +3440,25 @@ struct sac_group {
     void (*fa3)(const GroupMember *, const Td3GroupStep *, int) = nullptr;
     void (*fb3)(const GroupMember *, const Td3GroupStep *, int) = nullptr, (*fb3a)(const GroupMember *, const Td3GroupStep *, int) = nullptr;
     void (*bw3)(const GroupMember *, const Td3GroupStep *, int, int) = nullptr, (*bw3a)(const GroupMember *, const Td3GroupStep *, int, int) = nullptr;
+};
+
+struct sac_group {
+    int R = 0, device = 0, algo = 0;                  // algo: 0 SAC, 1 TD3 (every member's)
+    bool mixed = false;                               // sac_group_create_mixed / td3_group_create_mixed
+    sac_trainer *m[SAC_GROUP_MAX] = {};
+    int ord[SAC_GROUP_MAX] = {};                      // device table entry k (member and step tables) is member ord[k]
+    int ncls = 0;
+    GroupClass cls[4];
+    int grid_d = 0, grid_dq = 0, grid_dpi = 0;        // k_dw_adam_group: the largest njobs + 1 (SAC; TD3 critic / policy)
+    hipStream_t s = nullptr, s2 = nullptr;           // steps / draws + gathers
+    hipEvent_t ev_ready[2] = {}, ev_done[2] = {}, ev_copied[2] = {}, ev_end = nullptr;
+    hipEvent_t ev_in[2 * SAC_GROUP_MAX] = {};         // the members' and the buffers' streams in front of a call
+    char *d_tab = nullptr, *h_tab = nullptr;          // device tables and their pinned host images
+    GroupMember *d_mem = nullptr, *h_mem = nullptr;   // [R] (device order)
+    SampleMember *d_smp = nullptr, *h_smp = nullptr;  // [2 halves][R] (member order)
+    GatherMember *d_gat = nullptr, *h_gat = nullptr;  // [2 halves][R] (sorted by gather class, per call)
+    StepArg *d_sa = nullptr, *h_sa = nullptr;         // SAC: [2 halves][LOOP_CH steps][R] (device order)
+    Td3GroupStep *d_ts = nullptr, *h_ts = nullptr;    // TD3: [2 halves][LOOP_CH steps][R] (device order)
 };
 
 static void group_free(sac_group *g) {
@@ -3465,8 +3490,18 @@ static int group_member_ok(const sac_trainer *t, int i, int algo) {
     return 0;
 }
 
-static int group_create(sac_group_t **out, sac_trainer_t *const *members, int n_members, int algo) {
-    SAC_REQUIRE(out && members, "null argument to %s", algo ? "td3_group_create" : "sac_group_create");
+// a member's solo x-extents (launch_step / launch_step_td3 at split 4; k_bwd is compact for every batch <= 256)
+static void member_extents(const sac_trainer *t, int algo, int &xa, int &xb, int &xc, int &xpi) {
+    const int SPv = 4, NB = t->NB;
+    xa = 4 * SPv * NB;
+    if (algo == 0) { xb = xc = 4 * SPv * NB; xpi = 0; }
+    else { xb = xc = 8 * ((SPv * NB + 3) / 4); xpi = SPv * NB; }
+}
+
+static int group_create(sac_group_t **out, sac_trainer_t *const *members, int n_members, int algo, bool mixed) {
+    const char *fname = mixed ? (algo ? "td3_group_create_mixed" : "sac_group_create_mixed")
+                              : (algo ? "td3_group_create" : "sac_group_create");
+    SAC_REQUIRE(out && members, "null argument to %s", fname);
     *out = nullptr;
     SAC_REQUIRE(n_members >= 1 && n_members <= SAC_GROUP_MAX, "a trainer group holds 1..%d members (got %d)", SAC_GROUP_MAX,
                 n_members);
@@ -3477,52 +3512,93 @@ static int group_create(sac_group_t **out, sac_trainer_t *const *members, int n_
         for (int j = 0; j < i; ++j)
             SAC_REQUIRE(members[j] != t, "trainer group members %d and %d are the same trainer", j, i);
         if (group_member_ok(t, i, algo)) return -1;
-        SAC_REQUIRE(t->O == t0->O && t->A == t0->A, "trainer group member %d has dims (%d,%d), member 0 (%d,%d)", i, t->O, t->A,
-                    t0->O, t0->A);
-        SAC_REQUIRE(t->Bt == t0->Bt, "trainer group member %d has batch %d, member 0 %d", i, t->Bt, t0->Bt);
+        if (!mixed) {
+            SAC_REQUIRE(t->O == t0->O && t->A == t0->A, "trainer group member %d has dims (%d,%d), member 0 (%d,%d)", i, t->O,
+                        t->A, t0->O, t0->A);
+            SAC_REQUIRE(t->Bt == t0->Bt, "trainer group member %d has batch %d, member 0 %d", i, t->Bt, t0->Bt);
+        }
         SAC_REQUIRE(t->HP[0] == t0->HP[0] && t->HP[1] == t0->HP[1] && t->HQ[0] == t0->HQ[0] && t->HQ[1] == t0->HQ[1],
                     "trainer group member %d has hidden sizes policy [%d,%d] qf [%d,%d], member 0 policy [%d,%d] qf [%d,%d]", i,
                     t->HP[0], t->HP[1], t->HQ[0], t->HQ[1], t0->HP[0], t0->HP[1], t0->HQ[0], t0->HQ[1]);
         SAC_REQUIRE(t->device == t0->device, "trainer group member %d lives on device %d, member 0 on %d", i, t->device, t0->device);
-        SAC_REQUIRE(t->fwd_a == t0->fwd_a && t->dw.njobs == t0->dw.njobs, "trainer group member %d runs another kernel variant "
-                    "than member 0", i);
+        if (!mixed)
+            SAC_REQUIRE(t->fwd_a == t0->fwd_a && t->dw.njobs == t0->dw.njobs, "trainer group member %d runs another kernel "
+                        "variant than member 0", i);
+        SAC_REQUIRE(t->A <= 16 && 3 * 4 * t->NB <= 192, "trainer group member %d: act_dim %d / batch %d outside the grouped "
+                    "kernels", i, t->A, t->Bt);
     }
     SAC_HIP(hipSetDevice(t0->device));
     sac_group *g = new sac_group();
     g->R = n_members;
     g->device = t0->device;
     g->algo = algo;
+    g->mixed = mixed;
     for (int i = 0; i < n_members; ++i) g->m[i] = members[i];
-    // the grouped instance of the variant the members' own four-launch step runs
+    auto fail = [&](int rc) { group_free(g); return rc; };
+    // the variant classes (the instance of launch A a member's own four-launch step runs), in order of first appearance;
+    // the device tables hold them one after another, each in member order
+    const void *key[4] = {};
+    for (int i = 0; i < n_members; ++i) {
+        const void *k = reinterpret_cast<const void *>(members[i]->fwd_a);
+        int c = 0;
+        while (c < g->ncls && key[c] != k) ++c;
+        if (c == g->ncls) {
+            if (g->ncls == 4) { sac::set_error("internal: more than four kernel variants in a trainer group"); return fail(-1); }
+            key[g->ncls++] = k;
+        }
+    }
+    int pos = 0;
+    for (int c = 0; c < g->ncls; ++c) {
+        GroupClass &K = g->cls[c];
+        K.lo = pos;
+        for (int i = 0; i < n_members; ++i) {
+            const sac_trainer *t = members[i];
+            if (reinterpret_cast<const void *>(t->fwd_a) != key[c]) continue;
+            g->ord[pos++] = i;
+            int xa, xb, xc, xpi;
+            member_extents(t, algo, xa, xb, xc, xpi);
+            K.xa = std::max(K.xa, xa); K.xb = std::max(K.xb, xb); K.xc = std::max(K.xc, xc); K.xpi = std::max(K.xpi, xpi);
+            K.lds_fa = std::max(K.lds_fa, t->lds_fa); K.lds_fb = std::max(K.lds_fb, t->lds_fb);
+            K.lds_bw = std::max(K.lds_bw, t->lds_bw);
+        }
+        K.n = pos - K.lo;
+        const sac_trainer *tc = members[g->ord[K.lo]];
+        // the grouped instance of the variant the class's own four-launch step runs
 #define SAC_GROUP_PICK(NTH, W)                                                                             \
-    if (t0->fwd_a == &k_fwd_a<NTH, W, 4>) {                                                                \
-        g->fa = &k_fwd_a_group<NTH, W, 4>; g->fb = &k_fwd_b_group<NTH, W, 4>; g->bw = &k_bwd_group<NTH, 4>; \
-    }
+        if (tc->fwd_a == &k_fwd_a<NTH, W, 4>) {                                                            \
+            K.fa = &k_fwd_a_group<NTH, W, 4>; K.fb = &k_fwd_b_group<NTH, W, 4>; K.bw = &k_bwd_group<NTH, 4>; \
+        }
 #define TD3_GROUP_PICK(W)                                                                                  \
-    if (t0->fwd_a == &k_fwd_a<1, W, 4, M_TD3_CRITIC>) {                                                    \
-        g->fa3 = &k_fwd_a_group<1, W, 4, M_TD3_CRITIC>;                                                    \
-        g->fb3 = &k_fwd_b_group<1, W, 4, M_TD3_CRITIC>; g->fb3a = &k_fwd_b_group<1, W, 4, M_TD3_ACTOR>;      \
-        g->bw3 = &k_bwd_group<1, 4, M_TD3_CRITIC>; g->bw3a = &k_bwd_group<1, 4, M_TD3_ACTOR>;                \
-    }
-    if (algo == 0) {
-        SAC_GROUP_PICK(1, false) else SAC_GROUP_PICK(1, true) else SAC_GROUP_PICK(2, false) else SAC_GROUP_PICK(2, true)
-    } else {
-        TD3_GROUP_PICK(false) else TD3_GROUP_PICK(true)
-    }
+        if (tc->fwd_a == &k_fwd_a<1, W, 4, M_TD3_CRITIC>) {                                                \
+            K.fa3 = &k_fwd_a_group<1, W, 4, M_TD3_CRITIC>;                                                 \
+            K.fb3 = &k_fwd_b_group<1, W, 4, M_TD3_CRITIC>; K.fb3a = &k_fwd_b_group<1, W, 4, M_TD3_ACTOR>;   \
+            K.bw3 = &k_bwd_group<1, 4, M_TD3_CRITIC>; K.bw3a = &k_bwd_group<1, 4, M_TD3_ACTOR>;             \
+        }
+        if (algo == 0) {
+            SAC_GROUP_PICK(1, false) else SAC_GROUP_PICK(1, true) else SAC_GROUP_PICK(2, false) else SAC_GROUP_PICK(2, true)
+        } else {
+            TD3_GROUP_PICK(false) else TD3_GROUP_PICK(true)
+        }
 #undef SAC_GROUP_PICK
 #undef TD3_GROUP_PICK
-    auto fail = [&](int rc) { group_free(g); return rc; };
-    if (!g->fa && !g->fa3) { sac::set_error("internal: no grouped instance of the members' step kernels"); return fail(-1); }
-    auto set_lds = [](const void *fn, size_t bytes) {
-        return (!fn || bytes <= 64 * 1024) ? hipSuccess : hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)bytes);
-    };
-    auto fn = [](auto f) { return reinterpret_cast<const void *>(f); };
-    if (set_lds(fn(g->fa), t0->lds_fa) != hipSuccess || set_lds(fn(g->fb), t0->lds_fb) != hipSuccess ||
-        set_lds(fn(g->bw), t0->lds_bw) != hipSuccess || set_lds(fn(g->fa3), t0->lds_fa) != hipSuccess ||
-        set_lds(fn(g->fb3), t0->lds_fb) != hipSuccess || set_lds(fn(g->fb3a), t0->lds_fb) != hipSuccess ||
-        set_lds(fn(g->bw3), t0->lds_bw) != hipSuccess || set_lds(fn(g->bw3a), t0->lds_bw) != hipSuccess) {
-        sac::set_error("hipFuncSetAttribute failed for the grouped step kernels");
-        return fail(-1);
+        if (!K.fa && !K.fa3) { sac::set_error("internal: no grouped instance of the members' step kernels"); return fail(-1); }
+        auto set_lds = [](const void *fn, size_t bytes) {
+            return (!fn || bytes <= 64 * 1024) ? hipSuccess : hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)bytes);
+        };
+        auto fn = [](auto f) { return reinterpret_cast<const void *>(f); };
+        if (set_lds(fn(K.fa), K.lds_fa) != hipSuccess || set_lds(fn(K.fb), K.lds_fb) != hipSuccess ||
+            set_lds(fn(K.bw), K.lds_bw) != hipSuccess || set_lds(fn(K.fa3), K.lds_fa) != hipSuccess ||
+            set_lds(fn(K.fb3), K.lds_fb) != hipSuccess || set_lds(fn(K.fb3a), K.lds_fb) != hipSuccess ||
+            set_lds(fn(K.bw3), K.lds_bw) != hipSuccess || set_lds(fn(K.bw3a), K.lds_bw) != hipSuccess) {
+            sac::set_error("hipFuncSetAttribute failed for the grouped step kernels");
+            return fail(-1);
+        }
+    }
+    for (int i = 0; i < n_members; ++i) {
+        const sac_trainer *t = members[i];
+        g->grid_d = std::max(g->grid_d, t->dw.njobs + 1);
+        g->grid_dq = std::max(g->grid_dq, std::max(t->dw_q.njobs, t->dw_q_tp.njobs) + 1);
+        g->grid_dpi = std::max(g->grid_dpi, t->dw_pi.njobs + 1);
     }
     const int R = n_members;
     const size_t b_mem = sizeof(GroupMember) * R, b_smp = sizeof(SampleMember) * 2 * R, b_gat = sizeof(GatherMember) * 2 * R;
@@ -3565,11 +3641,19 @@ static int group_create(sac_group_t **out, sac_trainer_t *const *members, int n_
 }
 
 int sac_group_create(sac_group_t **out, sac_trainer_t *const *members, int n_members) {
-    return group_create(out, members, n_members, 0);
+    return group_create(out, members, n_members, 0, false);
 }
 
 int td3_group_create(sac_group_t **out, sac_trainer_t *const *members, int n_members) {
-    return group_create(out, members, n_members, 1);
+    return group_create(out, members, n_members, 1, false);
+}
+
+int sac_group_create_mixed(sac_group_t **out, sac_trainer_t *const *members, int n_members) {
+    return group_create(out, members, n_members, 0, true);
+}
+
+int td3_group_create_mixed(sac_group_t **out, sac_trainer_t *const *members, int n_members) {
+    return group_create(out, members, n_members, 1, true);
 }
 
 int sac_group_destroy(sac_group_t *g) {
@@ -3597,14 +3681,19 @@ int sac_group_train_loop(sac_group_t *g, sac_buffer_t *const *bufs, int64_t n_st
         SAC_REQUIRE(b != nullptr, "trainer group buffer %d is null", r);
         for (int q = 0; q < r; ++q) SAC_REQUIRE(bufs[q] != b, "trainer group buffers %d and %d are the same buffer", q, r);
         SAC_REQUIRE(b->device == g->device, "trainer group buffer %d lives on device %d, the group on %d", r, b->device, g->device);
-        SAC_REQUIRE(b->O == t0->O && b->A == t0->A, "trainer group buffer %d has dims (%d,%d), the trainers (%d,%d)", r, b->O,
-                    b->A, t0->O, t0->A);
+        if (g->mixed) {
+            const sac_trainer *t = g->m[r];
+            SAC_REQUIRE(b->O == t->O && b->A == t->A, "trainer group buffer %d has dims (%d,%d), its member (%d,%d)", r, b->O,
+                        b->A, t->O, t->A);
+        } else {
+            SAC_REQUIRE(b->O == t0->O && b->A == t0->A, "trainer group buffer %d has dims (%d,%d), the trainers (%d,%d)", r, b->O,
+                        b->A, t0->O, t0->A);
+        }
         SAC_REQUIRE(b->size > 0, "trainer group buffer %d is empty: random_batch on an empty replay buffer", r);
         SAC_REQUIRE(b->size - 1 <= 0xffffffffLL, "replay buffers above 2^32 slots are not supported");
     }
     SAC_HIP(hipSetDevice(g->device));
-    const int Bt = t0->Bt, B = t0->B;
-    // what sac_train_loop does first, for every member and every buffer
+    // what sac_train_loop does first, for every member and every buffer (each with its member's own batch)
     for (int r = 0; r < R; ++r) {
         sac_trainer *t = g->m[r];
         if (t->fused && t->pend_n > 0) {          // device-batch steps nobody has verified yet: settle them first
@@ -3617,14 +3706,14 @@ int sac_group_train_loop(sac_group_t *g, sac_buffer_t *const *bufs, int64_t n_st
         else b->ra_streak = 0;
         if (loop_spec_drop(b)) return -1;
         b->loop_streak = 0;
-        if (ensure_slots(b, Bt, LOOP_RING)) return -1;
-        if (ensure_idx(b, LOOP_RING * B)) return -1;
+        if (ensure_slots(b, t->Bt, LOOP_RING)) return -1;
+        if (ensure_idx(b, LOOP_RING * t->B)) return -1;
         t->dev.eps1 = t->dev.eps2 = nullptr;
     }
     // Buffers bound to the SAME host generator (sac_rng_bind_host: by default every EnvReplayBuffer samples np.random)
     // continue it one after another, as R sac_train_loop calls in member order would: buffer r starts where the previous
-    // buffer of that generator ends (its n_steps batches drawn from its own size), and the host words end at the last
-    // one's end state (host_rng_advance below runs in member order).
+    // buffer of that generator ends (its n_steps batches of ITS member's batch size, drawn from its own size), and the
+    // host words end at the last one's end state (host_rng_advance below runs in member order).
     for (int r = 1; r < R; ++r) {
         sac_buffer *b = bufs[r];
         if (!b->host_key) continue;
@@ -3632,7 +3721,7 @@ int sac_group_train_loop(sac_group_t *g, sac_buffer_t *const *bufs, int64_t n_st
         while (q >= 0 && bufs[q]->host_key != b->host_key) --q;
         if (q < 0) continue;
         MtState st = bufs[q]->host_seen;
-        host_rng_skip(bufs[q], st, Bt, n_steps);
+        host_rng_skip(bufs[q], st, g->m[q]->Bt, n_steps);
         if (host_rng_adopt(b, st)) return -1;
     }
     hipStream_t s = g->s, s2 = g->s2;
@@ -3645,11 +3734,12 @@ int sac_group_train_loop(sac_group_t *g, sac_buffer_t *const *bufs, int64_t n_st
             SAC_HIP(hipStreamWaitEvent(s2, g->ev_in[2 * r + k], 0));
         }
     }
-    // the member tables of this call (the StepArg table follows chunk by chunk)
-    for (int r = 0; r < R; ++r) {
+    // the member tables of this call, in device order (the StepArg table follows chunk by chunk)
+    for (int k = 0; k < R; ++k) {
+        const int r = g->ord[k];
         const sac_trainer *t = g->m[r];
         sac_buffer *b = bufs[r];
-        GroupMember &M = g->h_mem[r];
+        GroupMember &M = g->h_mem[k];
         M.d = t->dev;
         M.T = t->dw;
         M.T.abort = nullptr;                          // (the four-launch step: no fused launch can give up in front of it)
@@ -3660,23 +3750,47 @@ int sac_group_train_loop(sac_group_t *g, sac_buffer_t *const *bufs, int64_t n_st
             M.T_tp = t->dw_q_tp; M.T_pi = t->dw_pi; M.T_none = t->dw_none;
             M.T_tp.abort = M.T_pi.abort = M.T_none.abort = nullptr;
         }
+        member_extents(t, g->algo, M.xa, M.xb, M.xc, M.xpi);
+    }
+    // the draw table in member order (one launch); the gather table sorted by gather class (one launch per class: the
+    // obs chunks per thread, NIT = 1 / 2 / 4 / 8), each class in member order
+    int gord[SAC_GROUP_MAX], gnit[4] = {}, glo[5] = {}, ngc = 0;
+    size_t glds[4] = {};
+    for (int nit : {1, 2, 4, 8}) {
+        const int lo = glo[ngc];
+        int n = lo;
+        size_t lds = 0;
+        for (int r = 0; r < R; ++r) {
+            const int v = gather_nit(bufs[r]), cl = v <= 1 ? 1 : v <= 2 ? 2 : v <= 4 ? 4 : 8;
+            SAC_REQUIRE(v <= 8, "observation rows too wide for the gather kernel (obs_dim %d)", bufs[r]->O);
+            if (cl != nit) continue;
+            gord[n++] = r;
+            lds = std::max(lds, sizeof(float) * (size_t)(2 * RB * bufs[r]->Ost + RB * bufs[r]->Ast));
+        }
+        if (n == lo) continue;
+        gnit[ngc] = nit; glds[ngc] = lds;
+        glo[++ngc] = n;
+    }
+    for (int r = 0; r < R; ++r) {
+        const sac_trainer *t = g->m[r];
+        sac_buffer *b = bufs[r];
         uint32_t rng = (uint32_t)(b->size - 1), mask = rng;
         mask |= mask >> 1; mask |= mask >> 2; mask |= mask >> 4; mask |= mask >> 8; mask |= mask >> 16;
-        for (int h = 0; h < 2; ++h) {
-            g->h_smp[h * R + r] = SampleMember{b->d_rng, b->d_idx + (int64_t)h * LOOP_CH * B, rng, mask};
-            g->h_gat[h * R + r] = GatherMember{b->view(), b->d_idx + (int64_t)h * LOOP_CH * B,
-                                               b->d_slots + (size_t)h * LOOP_CH * b->slot.slot_floats};
-        }
+        for (int h = 0; h < 2; ++h)
+            g->h_smp[h * R + r] = SampleMember{b->d_rng, b->d_idx + (int64_t)h * LOOP_CH * t->B, rng, mask, t->Bt, t->B};
+    }
+    for (int p = 0; p < R; ++p) {
+        const int r = gord[p];
+        const sac_trainer *t = g->m[r];
+        sac_buffer *b = bufs[r];
+        for (int h = 0; h < 2; ++h)
+            g->h_gat[h * R + p] = GatherMember{b->view(), b->d_idx + (int64_t)h * LOOP_CH * t->B,
+                                               b->d_slots + (size_t)h * LOOP_CH * b->slot.slot_floats, b->slot, t->B};
     }
     SAC_HIP(hipMemcpyAsync(g->d_mem, g->h_mem, sizeof(GroupMember) * R, hipMemcpyHostToDevice, s2));
     SAC_HIP(hipMemcpyAsync(g->d_smp, g->h_smp, sizeof(SampleMember) * 2 * R, hipMemcpyHostToDevice, s2));
     SAC_HIP(hipMemcpyAsync(g->d_gat, g->h_gat, sizeof(GatherMember) * 2 * R, hipMemcpyHostToDevice, s2));
-    const int SPv = 4, NB = t0->NB;
-    const int compact = (3 * SPv * NB <= 192) ? 1 : 0;       // as launch_step
-    const int grid_ab = 4 * SPv * NB, grid_c = compact ? 4 * SPv * NB : 3 * SPv * NB, grid_d = t0->dw.njobs + 1;
-    // TD3 (as launch_step_td3): critic pass A, B, C, D; actor pass B, C, D
-    const int grid_q = 8 * ((SPv * NB + 3) / 4), grid_pi = SPv * NB;
-    const int grid_dq = (t0->dw_q.njobs > t0->dw_q_tp.njobs ? t0->dw_q.njobs : t0->dw_q_tp.njobs) + 1, grid_dpi = t0->dw_pi.njobs + 1;
+    const int compact = 1;                            // (3 * 4 * NB <= 192 for every member: checked at creation)
     long long pi_steps[SAC_GROUP_MAX] = {};           // TD3: policy steps of each member so far in this call
     unsigned char plan[LOOP_CH];                      // TD3: per step of a chunk, bit 0: some member runs the actor pass, bit 1: some policy step
     FusedGate &G = g_gate[g->device & 63];
@@ -3690,8 +3804,15 @@ int sac_group_train_loop(sac_group_t *g, sac_buffer_t *const *bufs, int64_t n_st
             std::lock_guard<std::mutex> lk(G.mu);
             const bool gate = G.live > 1;
             if (gate && G.last && G.last != s2) SAC_HIP(hipStreamWaitEvent(s2, G.ev, 0));
-            if (launch_sample_group(g->d_smp + h * R, R, Bt, m, s2)) return -1;
-            if (launch_gather_group(g->d_gat + h * R, R, bufs[0], B, m, bufs[0]->slot, 1, s2)) return -1;
+            if (launch_sample_group(g->d_smp + h * R, R, m, s2)) return -1;
+            for (int q = 0; q < ngc; ++q) {
+                int grid = 0;
+                for (int p = glo[q]; p < glo[q + 1]; ++p) {
+                    const int64_t nb = (int64_t)(g->m[gord[p]]->B / RB) * m;
+                    grid = std::max(grid, (int)(nb < 1024 ? nb : 1024));     // (the x-extent of a solo launch_gather)
+                }
+                if (launch_gather_group(g->d_gat + h * R + glo[q], glo[q + 1] - glo[q], gnit[q], m, grid, glds[q], 1, s2)) return -1;
+            }
             if (gate) { SAC_HIP(hipEventRecord(G.ev, s2)); G.last = s2; }
         }
         SAC_HIP(hipEventRecord(g->ev_ready[h], s2));
@@ -3702,14 +3823,14 @@ int sac_group_train_loop(sac_group_t *g, sac_buffer_t *const *bufs, int64_t n_st
         if (g->algo == 0) {
             StepArg *hs = g->h_sa + (size_t)h * LOOP_CH * R;
             for (int64_t j = 0; j < m; ++j)
-                for (int r = 0; r < R; ++r) {
-                    const sac_trainer *t = g->m[r];
-                    const long long k = (long long)(done + j);
-                    const double tt = (double)(t->adam_t + k + 1);
-                    StepArg sa{t->n_train_steps_total + k, t->adam_t + k + 1, (int)k, 0, 1.0 - std::pow(0.9, tt),
+                for (int k = 0; k < R; ++k) {
+                    const sac_trainer *t = g->m[g->ord[k]];
+                    const long long i = (long long)(done + j);
+                    const double tt = (double)(t->adam_t + i + 1);
+                    StepArg sa{t->n_train_steps_total + i, t->adam_t + i + 1, (int)i, 0, 1.0 - std::pow(0.9, tt),
                                std::sqrt(1.0 - std::pow(0.999, tt))};
                     sa.pad2 = (done + j == n_steps - 1) ? 2u : 0u;
-                    hs[j * R + r] = sa;
+                    hs[j * R + k] = sa;
                 }
             hsrc = hs; dsrc = g->d_sa + (size_t)h * LOOP_CH * R; bytes = sizeof(StepArg) * m * R;
         } else {
@@ -3718,14 +3839,15 @@ int sac_group_train_loop(sac_group_t *g, sac_buffer_t *const *bufs, int64_t n_st
             Td3GroupStep *hs = g->h_ts + (size_t)h * LOOP_CH * R;
             for (int64_t j = 0; j < m; ++j) {
                 plan[j] = 0;
-                for (int r = 0; r < R; ++r) {
+                for (int k = 0; k < R; ++k) {
+                    const int r = g->ord[k];
                     const sac_trainer *t = g->m[r];
-                    const long long k = (long long)(done + j), step = t->n_train_steps_total + k;
-                    const bool pstep = (step % t->td3_period) == 0, actor = pstep || k == 0;
-                    const double tq = (double)(t->adam_t + k + 1), tp = (double)(t->adam_t_pi + pi_steps[r] + 1);
-                    Td3GroupStep &ts = hs[j * R + r];
-                    ts.sq = StepArg{step, t->adam_t + k + 1, (int)k, 1, 1.0 - std::pow(0.9, tq), std::sqrt(1.0 - std::pow(0.999, tq))};
-                    ts.sp = StepArg{step, t->adam_t_pi + pi_steps[r] + 1, (int)k, 2, 1.0 - std::pow(0.9, tp),
+                    const long long i = (long long)(done + j), step = t->n_train_steps_total + i;
+                    const bool pstep = (step % t->td3_period) == 0, actor = pstep || i == 0;
+                    const double tq = (double)(t->adam_t + i + 1), tp = (double)(t->adam_t_pi + pi_steps[r] + 1);
+                    Td3GroupStep &ts = hs[j * R + k];
+                    ts.sq = StepArg{step, t->adam_t + i + 1, (int)i, 1, 1.0 - std::pow(0.9, tq), std::sqrt(1.0 - std::pow(0.999, tq))};
+                    ts.sp = StepArg{step, t->adam_t_pi + pi_steps[r] + 1, (int)i, 2, 1.0 - std::pow(0.9, tp),
                                     std::sqrt(1.0 - std::pow(0.999, tp))};
                     ts.sq.pad2 = ts.sp.pad2 = (done + j == n_steps - 1) ? 2u : 0u;
                     ts.actor = actor ? 1 : 0;
@@ -3744,24 +3866,53 @@ int sac_group_train_loop(sac_group_t *g, sac_buffer_t *const *bufs, int64_t n_st
             std::lock_guard<std::mutex> lk(G.mu);
             const bool gate = G.live > 1;
             if (gate && G.last && G.last != s) SAC_HIP(hipStreamWaitEvent(s, G.ev, 0));
+            // per step kernel, one grouped launch per variant class (its range of the tables, gridDim.y = its size), then
+            // one weight-gradient launch over all members
             for (int64_t j = 0; j < m; ++j) {
                 const int slot = (int)(h * LOOP_CH + j);
                 if (g->algo == 0) {
                     const StepArg *sa = g->d_sa + (size_t)h * LOOP_CH * R + j * R;
-                    hipLaunchKernelGGL(g->fa, dim3(grid_ab, R), dim3(256), t0->lds_fa, s, g->d_mem, sa, slot);
-                    hipLaunchKernelGGL(g->fb, dim3(grid_ab, R), dim3(256), t0->lds_fb, s, g->d_mem, sa, slot);
-                    hipLaunchKernelGGL(g->bw, dim3(grid_c, R), dim3(256), t0->lds_bw, s, g->d_mem, sa, slot, compact);
-                    hipLaunchKernelGGL(k_dw_adam_group<M_SAC>, dim3(grid_d, R), dim3(256), 0, s, g->d_mem, sa, slot);
+                    for (int q = 0; q < g->ncls; ++q) {
+                        const GroupClass &K = g->cls[q];
+                        hipLaunchKernelGGL(K.fa, dim3(K.xa, K.n), dim3(256), K.lds_fa, s, g->d_mem + K.lo, sa + K.lo, slot);
+                    }
+                    for (int q = 0; q < g->ncls; ++q) {
+                        const GroupClass &K = g->cls[q];
+                        hipLaunchKernelGGL(K.fb, dim3(K.xb, K.n), dim3(256), K.lds_fb, s, g->d_mem + K.lo, sa + K.lo, slot);
+                    }
+                    for (int q = 0; q < g->ncls; ++q) {
+                        const GroupClass &K = g->cls[q];
+                        hipLaunchKernelGGL(K.bw, dim3(K.xc, K.n), dim3(256), K.lds_bw, s, g->d_mem + K.lo, sa + K.lo, slot,
+                                           compact);
+                    }
+                    hipLaunchKernelGGL(k_dw_adam_group<M_SAC>, dim3(g->grid_d, R), dim3(256), 0, s, g->d_mem, sa, slot);
                 } else {
                     const Td3GroupStep *ts = g->d_ts + (size_t)h * LOOP_CH * R + j * R;
-                    hipLaunchKernelGGL(g->fa3, dim3(grid_ab, R), dim3(256), t0->lds_fa, s, g->d_mem, ts, slot);
-                    hipLaunchKernelGGL(g->fb3, dim3(grid_q, R), dim3(256), t0->lds_fb, s, g->d_mem, ts, slot);
-                    hipLaunchKernelGGL(g->bw3, dim3(grid_q, R), dim3(256), t0->lds_bw, s, g->d_mem, ts, slot, 0);
-                    hipLaunchKernelGGL(k_dw_adam_group<M_TD3_CRITIC>, dim3(grid_dq, R), dim3(256), 0, s, g->d_mem, ts, slot);
+                    for (int q = 0; q < g->ncls; ++q) {
+                        const GroupClass &K = g->cls[q];
+                        hipLaunchKernelGGL(K.fa3, dim3(K.xa, K.n), dim3(256), K.lds_fa, s, g->d_mem + K.lo, ts + K.lo, slot);
+                    }
+                    for (int q = 0; q < g->ncls; ++q) {
+                        const GroupClass &K = g->cls[q];
+                        hipLaunchKernelGGL(K.fb3, dim3(K.xb, K.n), dim3(256), K.lds_fb, s, g->d_mem + K.lo, ts + K.lo, slot);
+                    }
+                    for (int q = 0; q < g->ncls; ++q) {
+                        const GroupClass &K = g->cls[q];
+                        hipLaunchKernelGGL(K.bw3, dim3(K.xc, K.n), dim3(256), K.lds_bw, s, g->d_mem + K.lo, ts + K.lo, slot, 0);
+                    }
+                    hipLaunchKernelGGL(k_dw_adam_group<M_TD3_CRITIC>, dim3(g->grid_dq, R), dim3(256), 0, s, g->d_mem, ts, slot);
                     if (plan[j] & 1) {
-                        hipLaunchKernelGGL(g->fb3a, dim3(grid_pi, R), dim3(256), t0->lds_fb, s, g->d_mem, ts, slot);
-                        if (plan[j] & 2) hipLaunchKernelGGL(g->bw3a, dim3(grid_pi, R), dim3(256), t0->lds_bw, s, g->d_mem, ts, slot, 0);
-                        hipLaunchKernelGGL(k_dw_adam_group<M_TD3_ACTOR>, dim3((plan[j] & 2) ? grid_dpi : 1, R), dim3(256), 0, s,
+                        for (int q = 0; q < g->ncls; ++q) {
+                            const GroupClass &K = g->cls[q];
+                            hipLaunchKernelGGL(K.fb3a, dim3(K.xpi, K.n), dim3(256), K.lds_fb, s, g->d_mem + K.lo, ts + K.lo, slot);
+                        }
+                        if (plan[j] & 2)
+                            for (int q = 0; q < g->ncls; ++q) {
+                                const GroupClass &K = g->cls[q];
+                                hipLaunchKernelGGL(K.bw3a, dim3(K.xpi, K.n), dim3(256), K.lds_bw, s, g->d_mem + K.lo, ts + K.lo,
+                                                   slot, 0);
+                            }
+                        hipLaunchKernelGGL(k_dw_adam_group<M_TD3_ACTOR>, dim3((plan[j] & 2) ? g->grid_dpi : 1, R), dim3(256), 0, s,
                                            g->d_mem, ts, slot);
                     }
                 }
@@ -3772,8 +3923,8 @@ int sac_group_train_loop(sac_group_t *g, sac_buffer_t *const *bufs, int64_t n_st
         SAC_HIP(hipEventRecord(g->ev_done[h], s));
         done += m;
     }
-    // the host mirrors of the generators follow behind the launches
-    for (int r = 0; r < R; ++r) host_rng_advance(bufs[r], Bt, n_steps);
+    // the host mirrors of the generators follow behind the launches (each buffer by its member's batch)
+    for (int r = 0; r < R; ++r) host_rng_advance(bufs[r], g->m[r]->Bt, n_steps);
     SAC_HIP(hipEventRecord(g->ev_end, s));
     if (wait_event(g->ev_end)) return -1;
     SAC_HIP(hipStreamSynchronize(s2));

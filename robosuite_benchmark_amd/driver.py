@@ -20,7 +20,7 @@ from .checkpoint import checkpoint_exists, load_checkpoint, save_checkpoint
 from .networks import (FlattenMlp, GaussianStrategy, MakeDeterministic, PolicyWrappedWithExplorationStrategy,
                        TanhGaussianPolicy, TanhMlpPolicy)
 from .replay_buffer import EnvReplayBuffer
-from .group import SACTrainerGroup, TD3TrainerGroup
+from .group import MixedSACTrainerGroup, MixedTD3TrainerGroup, SACTrainerGroup, TD3TrainerGroup
 from .sac import SACTrainer
 from .td3 import TD3Trainer
 from .variant import env_dims, validate
@@ -243,6 +243,93 @@ def experiment(variant, log_dir=None, seed=1, obs_dim=None, action_dim=None, num
     return rows
 
 
+def _group_run(variant, seed, O, A, device):
+    """One run of a grouped experiment, set up as experiment(variant, seed=seed) sets it up: its own synthetic
+    environments, collectors, weights (from a private RandomState(seed), in the order experiment() draws them from
+    np.random) and replay buffer (sampling a private stream continued from that generator), prefilled."""
+    td3 = variant.get("algorithm", "SAC") == "TD3"
+    ak, tk = variant["algorithm_kwargs"], variant["trainer_kwargs"]
+    rs = np.random.RandomState(seed)                          # experiment(): np.random.seed(seed), then the weights
+    expl_env = SyntheticEnv(O, A, variant["expl_environment_kwargs"].get("horizon", 500), seed)
+    eval_env = SyntheticEnv(O, A, variant["eval_environment_kwargs"].get("horizon", 500), seed + 1)
+    qf1, qf2, tqf1, tqf2 = (FlattenMlp(input_size=O + A, output_size=1, rs=rs, **variant["qf_kwargs"]) for _ in range(4))
+    if td3:                                                   # as experiment()'s TD3 branch
+        policy = TanhMlpPolicy(input_size=O, output_size=A, rs=rs, **variant["policy_kwargs"])
+        target_policy = TanhMlpPolicy(input_size=O, output_size=A, rs=rs, **variant["policy_kwargs"])
+        eval_policy = policy
+        expl_policy = PolicyWrappedWithExplorationStrategy(
+            exploration_strategy=GaussianStrategy(max_sigma=0.1, min_sigma=0.1, seed=seed), policy=policy)
+        trainer = TD3Trainer(policy=policy, qf1=qf1, qf2=qf2, target_qf1=tqf1, target_qf2=tqf2,
+                             target_policy=target_policy, batch_size=ak["batch_size"], noise_seed=seed, device=device,
+                             **tk)
+        policy._noise = expl_policy.es._rs
+    else:
+        policy = TanhGaussianPolicy(obs_dim=O, action_dim=A, rs=rs, noise=np.random.RandomState(seed),
+                                    **variant["policy_kwargs"])
+        eval_policy, expl_policy = MakeDeterministic(policy), policy
+        trainer = SACTrainer(env=eval_env, policy=policy, qf1=qf1, qf2=qf2, target_qf1=tqf1, target_qf2=tqf2,
+                             batch_size=ak["batch_size"], noise_seed=seed, device=device, **tk)
+    buf = EnvReplayBuffer(variant["replay_buffer_size"], obs_dim=O, action_dim=A, device=device)
+    buf.seed_from_numpy(rs)                                   # (the stream np.random would continue with)
+    expl, evalc = PathCollector(expl_env, expl_policy), PathCollector(eval_env, eval_policy)
+    if ak.get("min_num_steps_before_training", 0) > 0:
+        buf.add_paths(expl.collect_new_paths(ak["expl_max_path_length"], ak["min_num_steps_before_training"], False))
+        expl.end_epoch(-1)
+    return dict(seed=seed, ak=ak, trainer=trainer, buf=buf, expl=expl, evalc=evalc, rows=[], fh=None, writer=None)
+
+
+def _group_epochs(runs, train_block, n_epochs, n_train, log_dir, quiet, what):
+    """The epoch loop of a grouped experiment: each run collects its paths, then train_block() trains every run at once,
+    then each run writes its row (to <log_dir>/<run["sub"]>/progress.csv with log_dir)."""
+    t_start = time.time()
+    try:
+        for epoch in range(n_epochs):
+            times = []
+            for r in runs:
+                ak = r["ak"]
+                t0 = time.time()
+                r["evalc"].collect_new_paths(ak["eval_max_path_length"], ak["num_eval_steps_per_epoch"], True)
+                t1 = time.time()
+                new_paths = r["expl"].collect_new_paths(ak["expl_max_path_length"], ak["num_expl_steps_per_train_loop"], False)
+                t2 = time.time()
+                r["buf"].add_paths(new_paths)
+                times.append((t0, t1, t2, time.time()))
+            t3 = time.time()
+            train_block()
+            t4 = time.time()
+            for r, (a0, a1, a2, a3) in zip(runs, times):
+                row = _progress_row(r["buf"], r["trainer"], r["expl"], r["evalc"], r["ak"])
+                for x in (r["trainer"], r["buf"], r["expl"], r["evalc"]):
+                    x.end_epoch(epoch)
+                t5 = time.time()
+                row["time/data storing (s)"] = a3 - a2
+                row["time/evaluation sampling (s)"] = a1 - a0
+                row["time/exploration sampling (s)"] = a2 - a1
+                row["time/logging (s)"] = t5 - t4
+                row["time/saving (s)"] = 0.0
+                row["time/training (s)"] = t4 - t3            # (the group's block: every run's steps at once)
+                row["time/epoch (s)"] = t5 - a0
+                row["time/total (s)"] = t5 - t_start
+                row["Epoch"] = epoch
+                r["rows"].append(row)
+                if log_dir is not None:
+                    if r["writer"] is None:
+                        d = os.path.join(log_dir, r["sub"])
+                        os.makedirs(d, exist_ok=True)
+                        r["fh"] = open(os.path.join(d, "progress.csv"), "w", newline="")
+                        r["writer"] = csv.DictWriter(r["fh"], fieldnames=list(row.keys()))
+                        r["writer"].writeheader()
+                    r["writer"].writerow(row)
+                    r["fh"].flush()
+            if not quiet:
+                print(f"epoch {epoch}: {len(runs)} {what}, training {t4 - t3:.3f}s "
+                      f"({len(runs) * n_train / max(t4 - t3, 1e-9):.0f} steps/s together)", flush=True)
+    finally:
+        for r in runs:
+            if r["fh"]:
+                r["fh"].close()
+
+
 def experiment_group(variant, seeds, log_dir=None, num_epochs=None, obs_dim=None, action_dim=None, device=0,
                      quiet=False, resume=False):
     """One configuration, several seeds, one process: each seed is the run ``experiment(variant, seed=s)`` would make --
@@ -261,82 +348,75 @@ def experiment_group(variant, seeds, log_dir=None, num_epochs=None, obs_dim=None
     if not seeds or len(set(seeds)) != len(seeds):
         raise RuntimeError(f"experiment_group needs distinct seeds (got {seeds})")
     O, A = env_dims(variant["expl_environment_kwargs"], obs_dim, action_dim)
-    ak, tk = variant["algorithm_kwargs"], variant["trainer_kwargs"]
+    ak = variant["algorithm_kwargs"]
     runs = []
     for seed in seeds:
-        rs = np.random.RandomState(seed)                      # experiment(): np.random.seed(seed), then the weights
-        expl_env = SyntheticEnv(O, A, variant["expl_environment_kwargs"].get("horizon", 500), seed)
-        eval_env = SyntheticEnv(O, A, variant["eval_environment_kwargs"].get("horizon", 500), seed + 1)
-        qf1, qf2, tqf1, tqf2 = (FlattenMlp(input_size=O + A, output_size=1, rs=rs, **variant["qf_kwargs"]) for _ in range(4))
-        if td3:                                               # as experiment()'s TD3 branch
-            policy = TanhMlpPolicy(input_size=O, output_size=A, rs=rs, **variant["policy_kwargs"])
-            target_policy = TanhMlpPolicy(input_size=O, output_size=A, rs=rs, **variant["policy_kwargs"])
-            eval_policy = policy
-            expl_policy = PolicyWrappedWithExplorationStrategy(
-                exploration_strategy=GaussianStrategy(max_sigma=0.1, min_sigma=0.1, seed=seed), policy=policy)
-            trainer = TD3Trainer(policy=policy, qf1=qf1, qf2=qf2, target_qf1=tqf1, target_qf2=tqf2,
-                                 target_policy=target_policy, batch_size=ak["batch_size"], noise_seed=seed, device=device,
-                                 **tk)
-            policy._noise = expl_policy.es._rs
-        else:
-            policy = TanhGaussianPolicy(obs_dim=O, action_dim=A, rs=rs, noise=np.random.RandomState(seed),
-                                        **variant["policy_kwargs"])
-            eval_policy, expl_policy = MakeDeterministic(policy), policy
-            trainer = SACTrainer(env=eval_env, policy=policy, qf1=qf1, qf2=qf2, target_qf1=tqf1, target_qf2=tqf2,
-                                 batch_size=ak["batch_size"], noise_seed=seed, device=device, **tk)
-        buf = EnvReplayBuffer(variant["replay_buffer_size"], obs_dim=O, action_dim=A, device=device)
-        buf.seed_from_numpy(rs)                               # (the stream np.random would continue with)
-        expl, evalc = PathCollector(expl_env, expl_policy), PathCollector(eval_env, eval_policy)
-        if ak.get("min_num_steps_before_training", 0) > 0:
-            buf.add_paths(expl.collect_new_paths(ak["expl_max_path_length"], ak["min_num_steps_before_training"], False))
-            expl.end_epoch(-1)
-        runs.append(dict(seed=seed, trainer=trainer, buf=buf, expl=expl, evalc=evalc, rows=[], fh=None, writer=None))
+        runs.append(_group_run(variant, seed, O, A, device))
+        runs[-1]["sub"] = f"s{seed}"
     group = (TD3TrainerGroup if td3 else SACTrainerGroup)([r["trainer"] for r in runs])
-    t_start = time.time()
-    try:
-        for epoch in range(num_epochs if num_epochs is not None else ak["num_epochs"]):
-            times = []
-            for r in runs:
-                t0 = time.time()
-                r["evalc"].collect_new_paths(ak["eval_max_path_length"], ak["num_eval_steps_per_epoch"], True)
-                t1 = time.time()
-                new_paths = r["expl"].collect_new_paths(ak["expl_max_path_length"], ak["num_expl_steps_per_train_loop"], False)
-                t2 = time.time()
-                r["buf"].add_paths(new_paths)
-                times.append((t0, t1, t2, time.time()))
-            n_train = ak["num_trains_per_train_loop"]
-            t3 = time.time()
-            group.train_loop([r["buf"] for r in runs], n_train, batch_size=ak["batch_size"])
-            t4 = time.time()
-            for r, (a0, a1, a2, a3) in zip(runs, times):
-                row = _progress_row(r["buf"], r["trainer"], r["expl"], r["evalc"], ak)
-                for x in (r["trainer"], r["buf"], r["expl"], r["evalc"]):
-                    x.end_epoch(epoch)
-                t5 = time.time()
-                row["time/data storing (s)"] = a3 - a2
-                row["time/evaluation sampling (s)"] = a1 - a0
-                row["time/exploration sampling (s)"] = a2 - a1
-                row["time/logging (s)"] = t5 - t4
-                row["time/saving (s)"] = 0.0
-                row["time/training (s)"] = t4 - t3            # (the group's block: every seed's steps at once)
-                row["time/epoch (s)"] = t5 - a0
-                row["time/total (s)"] = t5 - t_start
-                row["Epoch"] = epoch
-                r["rows"].append(row)
-                if log_dir is not None:
-                    if r["writer"] is None:
-                        d = os.path.join(log_dir, f"s{r['seed']}")
-                        os.makedirs(d, exist_ok=True)
-                        r["fh"] = open(os.path.join(d, "progress.csv"), "w", newline="")
-                        r["writer"] = csv.DictWriter(r["fh"], fieldnames=list(row.keys()))
-                        r["writer"].writeheader()
-                    r["writer"].writerow(row)
-                    r["fh"].flush()
-            if not quiet:
-                print(f"epoch {epoch}: {len(runs)} seeds, training {t4 - t3:.3f}s "
-                      f"({len(runs) * n_train / max(t4 - t3, 1e-9):.0f} steps/s together)", flush=True)
-    finally:
-        for r in runs:
-            if r["fh"]:
-                r["fh"].close()
+    n_train = ak["num_trains_per_train_loop"]
+    _group_epochs(runs, lambda: group.train_loop([r["buf"] for r in runs], n_train, batch_size=ak["batch_size"]),
+                  num_epochs if num_epochs is not None else ak["num_epochs"], n_train, log_dir, quiet, "seeds")
     return {r["seed"]: r["rows"] for r in runs}
+
+
+def task_label(variant):
+    """The task of a variant as a directory name: <env_name>-<robots>, e.g. Lift-Panda, TwoArmLift-PandaPanda."""
+    env = variant["expl_environment_kwargs"]
+    robots = env["robots"]
+    robots = [robots] if isinstance(robots, str) else list(robots)
+    return f"{env['env_name']}-{''.join(robots)}"
+
+
+def experiment_sweep(runs, log_dir=None, num_epochs=None, device=0, quiet=False, resume=False):
+    """Several tasks x seeds, one process, one device: every entry of ``runs`` -- (variant, seed), or (variant, seed,
+    obs_dim, action_dim) for a task without pinned dims -- is the run ``experiment(variant, seed=seed)`` would make, and
+    every epoch's training block is ONE MixedSACTrainerGroup.train_loop (TD3 variants: MixedTD3TrainerGroup) over all
+    runs, each on its own batch size (bit for bit its solo result).
+    The runs must share the algorithm, the hidden sizes and the epoch plan (num_trains_per_train_loop, and num_epochs
+    unless it is given here); dims and batch sizes may differ.  Returns the runs' progress rows, a list in the order of
+    ``runs``; with log_dir, each run's rows also go to <log_dir>/<task>-s<seed>/progress.csv.  Resuming is not
+    supported, as for experiment_group."""
+    if resume:
+        raise RuntimeError("experiment_sweep does not resume: group checkpoints are not supported")
+    specs = []
+    for spec in runs:
+        spec = tuple(spec)
+        if len(spec) not in (2, 4):
+            raise RuntimeError(f"a sweep run is (variant, seed) or (variant, seed, obs_dim, action_dim), got {len(spec)} items")
+        v, seed = spec[0], int(spec[1])
+        validate(v)
+        O, A = env_dims(v["expl_environment_kwargs"], *(spec[2:] if len(spec) == 4 else (None, None)))
+        specs.append((v, seed, O, A))
+    if not specs:
+        raise RuntimeError("experiment_sweep needs at least one run")
+    v0 = specs[0][0]
+    algo0, ak0 = v0.get("algorithm", "SAC"), v0["algorithm_kwargs"]
+    labels = set()
+    for i, (v, seed, _, _) in enumerate(specs):
+        ak = v["algorithm_kwargs"]
+        if v.get("algorithm", "SAC") != algo0:
+            raise RuntimeError(f"sweep run {i} is {v.get('algorithm', 'SAC')}, run 0 {algo0}: a sweep runs one algorithm")
+        for kw in ("policy_kwargs", "qf_kwargs"):
+            if list(v[kw]["hidden_sizes"]) != list(v0[kw]["hidden_sizes"]):
+                raise RuntimeError(f"sweep run {i} has {kw} hidden sizes {v[kw]['hidden_sizes']}, run 0 "
+                                   f"{v0[kw]['hidden_sizes']}")
+        plan = ("num_trains_per_train_loop",) + (("num_epochs",) if num_epochs is None else ())
+        for k in plan:
+            if ak[k] != ak0[k]:
+                raise RuntimeError(f"sweep run {i} has {k} {ak[k]}, run 0 {ak0[k]}: a sweep runs one epoch plan")
+        label = f"{task_label(v)}-s{seed}"
+        if label in labels:
+            raise RuntimeError(f"sweep run {i} repeats {label}")
+        labels.add(label)
+    group_runs = []
+    for v, seed, O, A in specs:
+        group_runs.append(_group_run(v, seed, O, A, device))
+        group_runs[-1]["sub"] = f"{task_label(v)}-s{seed}"
+    td3 = algo0 == "TD3"
+    group = (MixedTD3TrainerGroup if td3 else MixedSACTrainerGroup)([r["trainer"] for r in group_runs])
+    n_train = ak0["num_trains_per_train_loop"]
+    batches = [r["ak"]["batch_size"] for r in group_runs]
+    _group_epochs(group_runs, lambda: group.train_loop([r["buf"] for r in group_runs], n_train, batch_sizes=batches),
+                  num_epochs if num_epochs is not None else ak0["num_epochs"], n_train, log_dir, quiet, "runs")
+    return [r["rows"] for r in group_runs]

@@ -1,5 +1,6 @@
 """SACTrainerGroup / TD3TrainerGroup: several SAC or TD3 runs of one configuration trained together (sac_group_*,
-td3_group_create of include/sac_hip.h).
+td3_group_create of include/sac_hip.h); MixedSACTrainerGroup / MixedTD3TrainerGroup: runs of different tasks
+(sac_group_create_mixed, td3_group_create_mixed).
 
 The reference's real workload is many independent runs -- seeds x configurations, one job each
 (/root/reference/launch_jobs.sh).  One run at batch 256 cannot fill an MI355X; a group steps R runs of the same shape
@@ -18,12 +19,18 @@ from .td3 import TD3Trainer
 MAX_MEMBERS = 16
 
 
-class _TrainerGroup:
-    _CREATE = None              # the C entry point that makes the group (sac_group_create / td3_group_create)
+class _GroupBase:
+    """What every kind of trainer group shares: the member checks that hold for all of them, the C group over the
+    members' handles, and the call of sac_group_train_loop."""
+    _CREATE = None              # the C entry point that makes the group (sac_group_create / td3_group_create / ..._mixed)
     _ONLY = None                # why a member of another kind is refused
 
     @staticmethod
     def _member_ok(t):
+        raise NotImplementedError
+
+    def _check_member(self, i, t, t0):
+        """Refuse member i (i >= 1) against member 0 from host metadata."""
         raise NotImplementedError
 
     def __init__(self, trainers):
@@ -38,20 +45,22 @@ class _TrainerGroup:
             raise RuntimeError("a trainer appears twice in the group")
         t0 = trainers[0]
         for i, t in enumerate(trainers[1:], 1):
-            if (t.obs_dim, t.act_dim) != (t0.obs_dim, t0.act_dim):
-                raise RuntimeError(f"trainer group member {i} has dims ({t.obs_dim},{t.act_dim}), member 0 "
-                                   f"({t0.obs_dim},{t0.act_dim})")
-            for net in ("policy", "qf1"):
-                if t._hidden(net) != t0._hidden(net):
-                    raise RuntimeError(f"trainer group member {i} has {net} hidden sizes {t._hidden(net)}, member 0 "
-                                       f"{t0._hidden(net)}")
-            if t.device != t0.device:
-                raise RuntimeError(f"trainer group member {i} lives on device {t.device}, member 0 on {t0.device}")
-            if t._batch is not None and t0._batch is not None and t._batch != t0._batch:
-                raise RuntimeError(f"trainer group member {i} has batch {t._batch}, member 0 {t0._batch}")
+            self._check_member(i, t, t0)
         self.trainers = trainers
         self._lib = _lib.load()
         self._g, self._handles = None, None
+
+    @staticmethod
+    def _check_hidden(i, t, t0):
+        for net in ("policy", "qf1"):
+            if t._hidden(net) != t0._hidden(net):
+                raise RuntimeError(f"trainer group member {i} has {net} hidden sizes {t._hidden(net)}, member 0 "
+                                   f"{t0._hidden(net)}")
+
+    @staticmethod
+    def _check_device(i, t, t0):
+        if t.device != t0.device:
+            raise RuntimeError(f"trainer group member {i} lives on device {t.device}, member 0 on {t0.device}")
 
     def __len__(self):
         return len(self.trainers)
@@ -76,36 +85,30 @@ class _TrainerGroup:
     def __del__(self):
         self._destroy()
 
-    def train_loop(self, replay_buffers, n_steps, batch_size=None):
-        """n_steps x {batch_r = replay_buffers[r].random_batch(B); trainers[r].train(batch_r)} for every member r.
-        Returns the first and last step's diagnostics, arrays of shape (R, SAC_DIAG_N)."""
-        buffers = list(replay_buffers)
-        R = len(self.trainers)
-        if len(buffers) != R:
-            raise RuntimeError(f"{R} trainers but {len(buffers)} replay buffers")
-        B = int(batch_size or self.trainers[0]._batch or 0)
-        if B <= 0:
-            raise RuntimeError("the batch size is unknown: pass batch_size or create the trainers with one")
-        # what can be refused from host metadata is refused before any member's handle is (re)created
-        if B > 256:
-            raise RuntimeError(f"batch {B}: trainer groups take batches of at most 256 rows")
+    def _check_general(self):
         for i, t in enumerate(self.trainers):
             for net in ("policy", "qf1"):
                 hs = t._hidden(net)
                 if len(hs) != 2 or max(hs) > 256:
                     raise RuntimeError(f"trainer group member {i} runs the general step ({net} hidden sizes {hs}): groups "
                                        "take two hidden layers of at most 256 units")
-        for r, b in enumerate(buffers):
-            if b is None or b._h is None:
-                raise RuntimeError(f"trainer group buffer {r} has no device storage")
-            if any(b is c for c in buffers[:r]):
-                raise RuntimeError(f"trainer group buffer {r} is the same buffer as an earlier one")
-            if (b._observation_dim, b._action_dim) != (self.trainers[0].obs_dim, self.trainers[0].act_dim):
-                raise RuntimeError(f"trainer group buffer {r} has dims ({b._observation_dim},{b._action_dim}), the trainers "
-                                   f"({self.trainers[0].obs_dim},{self.trainers[0].act_dim})")
-            if b.num_steps_can_sample() <= 0:
-                raise RuntimeError(f"trainer group buffer {r} is empty: random_batch on an empty replay buffer")
-        for t in self.trainers:
+
+    @staticmethod
+    def _check_buffer(r, b, buffers, dims, whose):
+        if b is None or b._h is None:
+            raise RuntimeError(f"trainer group buffer {r} has no device storage")
+        if any(b is c for c in buffers[:r]):
+            raise RuntimeError(f"trainer group buffer {r} is the same buffer as an earlier one")
+        if (b._observation_dim, b._action_dim) != dims:
+            raise RuntimeError(f"trainer group buffer {r} has dims ({b._observation_dim},{b._action_dim}), {whose} "
+                               f"({dims[0]},{dims[1]})")
+        if b.num_steps_can_sample() <= 0:
+            raise RuntimeError(f"trainer group buffer {r} is empty: random_batch on an empty replay buffer")
+
+    def _run(self, buffers, batches, n_steps):
+        """Every member on its batch size, then one sac_group_train_loop call."""
+        R = len(self.trainers)
+        for t, B in zip(self.trainers, batches):
             if t._h is None or t._batch != B:
                 t._create(B)
         g = self._group()
@@ -119,6 +122,75 @@ class _TrainerGroup:
             t._host_policy_stale = True
             t._record(first[r])
         return first, last
+
+
+class _TrainerGroup(_GroupBase):
+    """Members of one shape: the same dims and batch."""
+
+    def _check_member(self, i, t, t0):
+        if (t.obs_dim, t.act_dim) != (t0.obs_dim, t0.act_dim):
+            raise RuntimeError(f"trainer group member {i} has dims ({t.obs_dim},{t.act_dim}), member 0 "
+                               f"({t0.obs_dim},{t0.act_dim})")
+        self._check_hidden(i, t, t0)
+        self._check_device(i, t, t0)
+        if t._batch is not None and t0._batch is not None and t._batch != t0._batch:
+            raise RuntimeError(f"trainer group member {i} has batch {t._batch}, member 0 {t0._batch}")
+
+    def train_loop(self, replay_buffers, n_steps, batch_size=None):
+        """n_steps x {batch_r = replay_buffers[r].random_batch(B); trainers[r].train(batch_r)} for every member r.
+        Returns the first and last step's diagnostics, arrays of shape (R, SAC_DIAG_N)."""
+        buffers = list(replay_buffers)
+        R = len(self.trainers)
+        if len(buffers) != R:
+            raise RuntimeError(f"{R} trainers but {len(buffers)} replay buffers")
+        B = int(batch_size or self.trainers[0]._batch or 0)
+        if B <= 0:
+            raise RuntimeError("the batch size is unknown: pass batch_size or create the trainers with one")
+        # what can be refused from host metadata is refused before any member's handle is (re)created
+        if B > 256:
+            raise RuntimeError(f"batch {B}: trainer groups take batches of at most 256 rows")
+        self._check_general()
+        dims = (self.trainers[0].obs_dim, self.trainers[0].act_dim)
+        for r, b in enumerate(buffers):
+            self._check_buffer(r, b, buffers, dims, "the trainers")
+        return self._run(buffers, [B] * R, n_steps)
+
+
+class _MixedTrainerGroup(_GroupBase):
+    """Members of different tasks: obs_dim, act_dim and batch may differ per member (hidden sizes, algorithm and device
+    may not).  Each member trains on its own buffer with its own batch size, bit for bit as its solo train_loop."""
+
+    def _check_member(self, i, t, t0):
+        self._check_hidden(i, t, t0)
+        self._check_device(i, t, t0)
+
+    def train_loop(self, replay_buffers, n_steps, batch_sizes=None):
+        """n_steps x {batch_r = replay_buffers[r].random_batch(B_r); trainers[r].train(batch_r)} for every member r,
+        with B_r = batch_sizes[r] (default: the trainer's own batch size).  Returns the first and last step's
+        diagnostics, arrays of shape (R, SAC_DIAG_N)."""
+        buffers = list(replay_buffers)
+        R = len(self.trainers)
+        if len(buffers) != R:
+            raise RuntimeError(f"{R} trainers but {len(buffers)} replay buffers")
+        if batch_sizes is None:
+            batch_sizes = [None] * R
+        batch_sizes = list(batch_sizes)
+        if len(batch_sizes) != R:
+            raise RuntimeError(f"{R} trainers but {len(batch_sizes)} batch sizes")
+        batches = []
+        for r, (t, B) in enumerate(zip(self.trainers, batch_sizes)):
+            B = int(B or t._batch or 0)
+            if B <= 0:
+                raise RuntimeError(f"trainer group member {r} has no batch size: pass batch_sizes or create the trainers "
+                                   "with one")
+            if B > 256:
+                raise RuntimeError(f"trainer group member {r} has batch {B}: trainer groups take batches of at most 256 rows")
+            batches.append(B)
+        self._check_general()
+        for r, b in enumerate(buffers):
+            t = self.trainers[r]
+            self._check_buffer(r, b, buffers, (t.obs_dim, t.act_dim), "its member")
+        return self._run(buffers, batches, n_steps)
 
 
 class SACTrainerGroup(_TrainerGroup):
@@ -139,3 +211,18 @@ class TD3TrainerGroup(_TrainerGroup):
     @staticmethod
     def _member_ok(t):
         return isinstance(t, TD3Trainer)
+
+
+class MixedSACTrainerGroup(_MixedTrainerGroup):
+    """R SAC runs of different tasks (observation size, action size and batch per member) on one device: the members of
+    one kernel variant share each grouped launch, the variants follow one another."""
+    _CREATE = "sac_group_create_mixed"
+    _ONLY = "groups hold SAC trainers only"
+    _member_ok = staticmethod(SACTrainerGroup._member_ok)
+
+
+class MixedTD3TrainerGroup(_MixedTrainerGroup):
+    """R TD3 runs of different tasks; each keeps its own delayed-update phase as in TD3TrainerGroup."""
+    _CREATE = "td3_group_create_mixed"
+    _ONLY = "TD3 groups hold TD3 trainers only"
+    _member_ok = staticmethod(TD3TrainerGroup._member_ok)

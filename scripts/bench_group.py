@@ -3,7 +3,13 @@
 (batch, R).
 
     python scripts/bench_group.py [--agent SAC|TD3] [--steps 2000] [--warmup 200] [--batches 256 128]
-                                  [--replicas 1 2 4 8 16]"""
+                                  [--replicas 1 2 4 8 16]
+
+--tasks sweep: the eight tasks of parallel.SWEEP (SAC), --seeds-per-task k runs of each, as ONE mixed trainer group
+(MixedSACTrainerGroup) against the same runs trained one after another with solo train_loop.  One JSON line per
+(batch, seeds per task): both aggregate rates, every task's solo rate and the step launches per step.
+
+    python scripts/bench_group.py --tasks sweep [--batches 256 128] [--seeds-per-task 1 2] [--buffer 1000000]"""
 from __future__ import annotations
 
 import argparse
@@ -16,8 +22,9 @@ import numpy as np
 
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 
-from robosuite_benchmark_amd import (EnvReplayBuffer, FlattenMlp, SACTrainer, SACTrainerGroup,  # noqa: E402
-                                     TanhGaussianPolicy, TanhMlpPolicy, TD3Trainer, TD3TrainerGroup, _lib)
+from robosuite_benchmark_amd import (EnvReplayBuffer, FlattenMlp, MixedSACTrainerGroup, SACTrainer,  # noqa: E402
+                                     SACTrainerGroup, TanhGaussianPolicy, TanhMlpPolicy, TD3Trainer, TD3TrainerGroup, _lib)
+from robosuite_benchmark_amd.parallel import SWEEP  # noqa: E402
 
 
 def make_trainer(O, A, B, seed):
@@ -39,8 +46,57 @@ def make_td3_trainer(O, A, B, seed):
                       qf_learning_rate=5e-4, policy_and_target_update_period=2, tau=0.005, batch_size=B, noise_seed=seed)
 
 
+def variant_class(O, A):
+    """The kernel variant a SAC trainer's step runs: head tiles (2A outputs in 16-wide tiles) and a first layer wider than
+    eight 16-column chunks (the Q input [obs | pad | act | pad] of round_up(O, 16) + 16 columns)."""
+    return (-(-2 * A // 16), -(-O // 16) * 16 + 16 >= 129)
+
+
+def bench_sweep(args):
+    N = args.buffer
+    gen = np.random.default_rng(1)
+    for k in args.seeds_per_task:
+        runs = [(task, O, A, s) for task, O, A in SWEEP for s in range(k)]
+        bufs = []
+        for i, (task, O, A, s) in enumerate(runs):
+            b = EnvReplayBuffer(N, obs_dim=O, action_dim=A)
+            b.add_block(gen.standard_normal((N, O), dtype=np.float32) * 0.5,
+                        gen.uniform(-1, 1, (N, A)).astype(np.float32), gen.uniform(0, 1, (N, 1)).astype(np.float32),
+                        gen.standard_normal((N, O), dtype=np.float32) * 0.5, np.zeros((N, 1), np.uint8))
+            b.seed(100 + i)
+            bufs.append(b)
+        for B in args.batches:
+            trainers = [make_trainer(O, A, B, 10 + i) for i, (task, O, A, s) in enumerate(runs)]
+            group = MixedSACTrainerGroup(trainers)
+            group.train_loop(bufs, args.warmup)
+            t0 = time.perf_counter()
+            _, last = group.train_loop(bufs, args.steps)
+            dt_group = time.perf_counter() - t0
+            solo, dt_seq = {}, 0.0
+            for (task, O, A, s), t, b in zip(runs, trainers, bufs):
+                t.train_loop(b, args.warmup, batch_size=B)
+                t0 = time.perf_counter()
+                t.train_loop(b, args.steps, batch_size=B)
+                dt = time.perf_counter() - t0
+                dt_seq += dt
+                solo.setdefault(task, []).append(round(args.steps / dt, 1))
+            n_cls = len({variant_class(O, A) for _, O, A, _ in runs})
+            print(json.dumps(dict(metric="mixed_group_sweep_grad_steps_per_s", batch=B, seeds_per_task=k, runs=len(runs),
+                                  buffer=N, steps=args.steps, group_seconds=round(dt_group, 4),
+                                  group_aggregate_steps_per_s=round(len(runs) * args.steps / dt_group, 1),
+                                  sequential_seconds=round(dt_seq, 4),
+                                  sequential_aggregate_steps_per_s=round(len(runs) * args.steps / dt_seq, 1),
+                                  gain=round(dt_seq / dt_group, 3), solo_steps_per_s=solo, variant_classes=n_cls,
+                                  step_launches_per_step=3 * n_cls + 1,
+                                  finite=bool(np.all(np.isfinite(last))))), flush=True)
+            del group, trainers
+        del bufs
+
+
 def main():
     ap = argparse.ArgumentParser()
+    ap.add_argument("--tasks", type=str, default="lift", choices=["lift", "sweep"])
+    ap.add_argument("--seeds-per-task", type=int, nargs="+", default=[1, 2])
     ap.add_argument("--agent", type=str, default="SAC", choices=["SAC", "TD3"])
     ap.add_argument("--steps", type=int, default=2000)
     ap.add_argument("--warmup", type=int, default=200)
@@ -52,6 +108,8 @@ def main():
     args = ap.parse_args()
     if _lib.device_count() == 0:
         raise SystemExit("bench_group.py needs a GPU")
+    if args.tasks == "sweep":
+        return bench_sweep(args)
     O, A, N = args.obs, args.act, args.buffer
     rs = np.random.RandomState(1)
     rows = (rs.normal(0, 0.5, (N, O)).astype(np.float32), rs.uniform(-1, 1, (N, A)).astype(np.float32),

@@ -2,8 +2,10 @@
 """Counterpart of the reference's scripts/train.py for the MI355X path:
     python scripts/train.py --variant <variant.json> --seed S --log_dir DIR [--epochs N]
     python scripts/train.py --variant <variant.json> --seeds S1 S2 ... --log_dir DIR [--epochs N]
+    python scripts/train.py --variants A.json B.json ... --seeds S1 S2 ... --log_dir DIR [--epochs N]
 (--seeds: one process trains every seed, the training blocks as one trainer group, SAC or TD3 (--agent);
- DIR/s<seed>/progress.csv each)
+ DIR/s<seed>/progress.csv each.  --variants: every (variant, seed) pair -- tasks of different dims and batch sizes --
+ as one mixed trainer group; DIR/<task>-s<seed>/progress.csv each)
 Runs the variant unchanged (batch size, lrs, tau, period, buffer size ... from the JSON) on the
 HIP library with a synthetic environment of the task's dimensions (robosuite is not installed)."""
 import argparse
@@ -11,7 +13,7 @@ import os
 import sys
 
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
-from robosuite_benchmark_amd.driver import experiment, experiment_group  # noqa: E402
+from robosuite_benchmark_amd.driver import experiment, experiment_group, experiment_sweep  # noqa: E402
 from robosuite_benchmark_amd.variant import default_variant, load_variant  # noqa: E402
 
 if __name__ == "__main__":
@@ -29,7 +31,17 @@ if __name__ == "__main__":
     ap.add_argument("--seeds", type=int, nargs="+", default=None,
                     help="train these seeds of the one configuration together (trainer groups; SAC or TD3, no "
                          "checkpoints)")
+    ap.add_argument("--variants", type=str, nargs="+", default=None,
+                    help="variant files of different tasks: every (variant, seed of --seeds or --seed) pair trains "
+                         "together as one mixed trainer group (no checkpoints)")
     args = ap.parse_args()
+    if args.variants:
+        if args.resume:
+            raise SystemExit("--variants does not resume (group checkpoints are not supported)")
+        seeds = args.seeds or [args.seed]
+        experiment_sweep([(load_variant(v), s) for v in args.variants for s in seeds], log_dir=args.log_dir,
+                         num_epochs=args.epochs)
+        sys.exit(0)
     if args.seeds:
         if args.resume:
             raise SystemExit("--seeds does not resume (group checkpoints are not supported)")
