@@ -63,6 +63,11 @@ int sac_buffer_ingest_wait(sac_buffer_t *buf);
 int64_t sac_buffer_size(const sac_buffer_t *buf);      /* 'replay_buffer/size' */
 int64_t sac_buffer_top(const sac_buffer_t *buf);
 int64_t sac_buffer_capacity(const sac_buffer_t *buf);
+/* Rows stored since the buffer was created: every row sac_buffer_add / sac_buffer_add_f64 hands to the ring (the
+ * pinned async ingest), the head an oversized add skips included, so top == rows_written mod capacity as long as nobody
+ * moves the cursor.  Never decreases; sac_buffer_set_cursor leaves it alone.  Incremental checkpoints compare it (and
+ * top) with their values at the last save to find the rows written since. */
+int64_t sac_buffer_rows_written(const sac_buffer_t *buf);
 
 /* Checkpointing (SURVEY.md 8b "Snapshot contract": the reference saves no buffer -- rlkit's
  * get_snapshot() for it is {}, /root/reference/util/rlkit_custom.py:80 -- so a resumed run starts from an

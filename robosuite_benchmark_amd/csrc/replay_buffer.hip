@@ -665,6 +665,7 @@ static int add_impl(sac_buffer *b, int64_t n, const Src *obs, const Src *act, co
         const int64_t skip = n - b->capacity;
         b->top = (b->top + skip) % b->capacity;
         b->size = b->capacity;
+        b->rows_written += skip;
         i = skip;
     }
     while (i < n) {
@@ -673,6 +674,7 @@ static int add_impl(sac_buffer *b, int64_t n, const Src *obs, const Src *act, co
         if (add_segment<Src>(b, b->top, m, obs + i * O, act + i * A, rew + i, nobs + i * O, term + i)) return -1;
         b->top = (b->top + m) % b->capacity;
         b->size = (b->size + m < b->capacity) ? b->size + m : b->capacity;
+        b->rows_written += m;
         i += m;
     }
     return 0;
@@ -784,6 +786,7 @@ int sac_buffer_set_xcd(sac_buffer_t *b, int xcd) {
 int64_t sac_buffer_size(const sac_buffer_t *b) { return b ? b->size : -1; }
 int64_t sac_buffer_top(const sac_buffer_t *b) { return b ? b->top : -1; }
 int64_t sac_buffer_capacity(const sac_buffer_t *b) { return b ? b->capacity : -1; }
+int64_t sac_buffer_rows_written(const sac_buffer_t *b) { return b ? b->rows_written : -1; }
 
 int sac_buffer_add(sac_buffer_t *b, int64_t n, const float *obs, const float *act, const float *rew,
                    const float *next_obs, const uint8_t *term) {

@@ -100,6 +100,7 @@ struct sac_buffer {
     int device = 0;
     hipStream_t stream = nullptr;
     int64_t capacity = 0, size = 0, top = 0;
+    int64_t rows_written = 0;     // rows stored since creation (every add, the skipped head of an oversized one too)
     int O = 0, A = 0, Ost = 0, Ast = 0;
     float *obs = nullptr, *act = nullptr, *rew = nullptr, *term = nullptr, *nobs = nullptr;
     sac::MtState *d_rng = nullptr;

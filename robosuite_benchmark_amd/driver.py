@@ -17,6 +17,8 @@ from collections import OrderedDict
 import numpy as np
 
 from .checkpoint import checkpoint_exists, load_checkpoint, save_checkpoint
+from .group_checkpoint import DEFAULT_CHUNK_ROWS, GroupCheckpoint, member_identity
+from .group_checkpoint import checkpoint_exists as _checkpoint_exists
 from .networks import (FlattenMlp, GaussianStrategy, MakeDeterministic, PolicyWrappedWithExplorationStrategy,
                        TanhGaussianPolicy, TanhMlpPolicy)
 from .replay_buffer import EnvReplayBuffer
@@ -243,10 +245,11 @@ def experiment(variant, log_dir=None, seed=1, obs_dim=None, action_dim=None, num
     return rows
 
 
-def _group_run(variant, seed, O, A, device):
+def _group_run(variant, seed, O, A, device, prefill=True):
     """One run of a grouped experiment, set up as experiment(variant, seed=seed) sets it up: its own synthetic
     environments, collectors, weights (from a private RandomState(seed), in the order experiment() draws them from
-    np.random) and replay buffer (sampling a private stream continued from that generator), prefilled."""
+    np.random) and replay buffer (sampling a private stream continued from that generator), prefilled unless the run is
+    about to be restored from a checkpoint."""
     td3 = variant.get("algorithm", "SAC") == "TD3"
     ak, tk = variant["algorithm_kwargs"], variant["trainer_kwargs"]
     rs = np.random.RandomState(seed)                          # experiment(): np.random.seed(seed), then the weights
@@ -272,18 +275,54 @@ def _group_run(variant, seed, O, A, device):
     buf = EnvReplayBuffer(variant["replay_buffer_size"], obs_dim=O, action_dim=A, device=device)
     buf.seed_from_numpy(rs)                                   # (the stream np.random would continue with)
     expl, evalc = PathCollector(expl_env, expl_policy), PathCollector(eval_env, eval_policy)
-    if ak.get("min_num_steps_before_training", 0) > 0:
+    if prefill and ak.get("min_num_steps_before_training", 0) > 0:
         buf.add_paths(expl.collect_new_paths(ak["expl_max_path_length"], ak["min_num_steps_before_training"], False))
         expl.end_epoch(-1)
-    return dict(seed=seed, ak=ak, trainer=trainer, buf=buf, expl=expl, evalc=evalc, rows=[], fh=None, writer=None)
+    host_rngs = dict(policy_noise=policy._noise, expl_env=expl_env._rs, eval_env=eval_env._rs)
+    return dict(seed=seed, ak=ak, trainer=trainer, buf=buf, expl=expl, evalc=evalc, rows=[], fh=None, writer=None,
+                variant=variant, host_rngs=host_rngs)
 
 
-def _group_epochs(runs, train_block, n_epochs, n_train, log_dir, quiet, what):
+def _group_checkpoint(runs, checkpoint_dir, restore, chunk_rows):
+    """The group checkpoint of a grouped experiment (None without checkpoint_dir) and the first epoch to run.  With
+    restore (resume=True and a checkpoint in checkpoint_dir), every run is restored from it -- trainer, buffer, host generators and
+    collector totals -- and continues after the saved epoch; the live group must be the saved one (same members in the
+    same order), which the loader checks before it touches any state."""
+    if not checkpoint_dir:
+        return None, 0
+    ck = GroupCheckpoint(checkpoint_dir, chunk_rows)
+    for r in runs:
+        r["identity"] = member_identity(r["sub"], r["seed"], r["variant"], r["trainer"])
+    if not restore:
+        return ck, 0
+    extras = ck.load([r["trainer"] for r in runs], [r["buf"] for r in runs], [r["identity"] for r in runs])
+    first_epoch = int(extras[0]["epoch"]) + 1
+    for r, extra in zip(runs, extras):
+        for k, rs in r["host_rngs"].items():
+            _rs_unpack(rs, extra[k])
+        r["expl"].num_steps_total, r["expl"].num_paths_total = extra["expl_totals"]
+        r["evalc"].num_steps_total, r["evalc"].num_paths_total = extra["eval_totals"]
+        r["trainer"].end_epoch(first_epoch - 1)
+    return ck, first_epoch
+
+
+def _group_save(ck, runs, epoch):
+    extras = []
+    for r in runs:
+        extra = dict(epoch=epoch, seed=r["seed"], expl_totals=[r["expl"].num_steps_total, r["expl"].num_paths_total],
+                     eval_totals=[r["evalc"].num_steps_total, r["evalc"].num_paths_total])
+        extra.update({k: _rs_pack(rs) for k, rs in r["host_rngs"].items()})
+        extras.append(extra)
+    ck.save([r["trainer"] for r in runs], [r["buf"] for r in runs], [r["identity"] for r in runs], extras)
+
+
+def _group_epochs(runs, train_block, n_epochs, n_train, log_dir, quiet, what, ck=None, first_epoch=0):
     """The epoch loop of a grouped experiment: each run collects its paths, then train_block() trains every run at once,
-    then each run writes its row (to <log_dir>/<run["sub"]>/progress.csv with log_dir)."""
+    then every run ends its epoch, the group is saved (with a GroupCheckpoint `ck`), and each run writes its row (to
+    <log_dir>/<run["sub"]>/progress.csv with log_dir; appended to after a resume)."""
     t_start = time.time()
     try:
-        for epoch in range(n_epochs):
+        for epoch in range(first_epoch, n_epochs):
             times = []
             for r in runs:
                 ak = r["ak"]
@@ -297,28 +336,38 @@ def _group_epochs(runs, train_block, n_epochs, n_train, log_dir, quiet, what):
             t3 = time.time()
             train_block()
             t4 = time.time()
-            for r, (a0, a1, a2, a3) in zip(runs, times):
+            ended = []
+            for r in runs:
                 row = _progress_row(r["buf"], r["trainer"], r["expl"], r["evalc"], r["ak"])
                 for x in (r["trainer"], r["buf"], r["expl"], r["evalc"]):
                     x.end_epoch(epoch)
-                t5 = time.time()
+                ended.append((row, time.time()))
+            t6 = time.time()
+            if ck is not None:                                # one generation for the whole group
+                _group_save(ck, runs, epoch)
+            t7 = time.time()
+            for r, (a0, a1, a2, a3), (row, t5) in zip(runs, times, ended):
+                t_end = t7 if ck is not None else t5
                 row["time/data storing (s)"] = a3 - a2
                 row["time/evaluation sampling (s)"] = a1 - a0
                 row["time/exploration sampling (s)"] = a2 - a1
                 row["time/logging (s)"] = t5 - t4
-                row["time/saving (s)"] = 0.0
+                row["time/saving (s)"] = t7 - t6 if ck is not None else 0.0
                 row["time/training (s)"] = t4 - t3            # (the group's block: every run's steps at once)
-                row["time/epoch (s)"] = t5 - a0
-                row["time/total (s)"] = t5 - t_start
+                row["time/epoch (s)"] = t_end - a0
+                row["time/total (s)"] = t_end - t_start
                 row["Epoch"] = epoch
                 r["rows"].append(row)
                 if log_dir is not None:
                     if r["writer"] is None:
                         d = os.path.join(log_dir, r["sub"])
                         os.makedirs(d, exist_ok=True)
-                        r["fh"] = open(os.path.join(d, "progress.csv"), "w", newline="")
+                        path = os.path.join(d, "progress.csv")
+                        appending = first_epoch > 0 and os.path.exists(path)
+                        r["fh"] = open(path, "a" if appending else "w", newline="")
                         r["writer"] = csv.DictWriter(r["fh"], fieldnames=list(row.keys()))
-                        r["writer"].writeheader()
+                        if not appending:
+                            r["writer"].writeheader()
                     r["writer"].writerow(row)
                     r["fh"].flush()
             if not quiet:
@@ -331,17 +380,21 @@ def _group_epochs(runs, train_block, n_epochs, n_train, log_dir, quiet, what):
 
 
 def experiment_group(variant, seeds, log_dir=None, num_epochs=None, obs_dim=None, action_dim=None, device=0,
-                     quiet=False, resume=False):
+                     quiet=False, checkpoint_dir=None, resume=False, chunk_rows=DEFAULT_CHUNK_ROWS):
     """One configuration, several seeds, one process: each seed is the run ``experiment(variant, seed=s)`` would make --
     its own synthetic environments, collectors, weights and replay buffer -- and every epoch's training block is ONE
     SACTrainerGroup.train_loop (TD3 variants: TD3TrainerGroup) over all seeds (grouped launches; each run's result is
     bit for bit its solo one).
     Weights come from a private RandomState(s) in the order experiment() draws them from np.random, and the buffer
     samples a private stream continued from that generator (np.random is neither read nor written).  Returns
-    {seed: progress rows}; with log_dir, each seed's rows also go to <log_dir>/s<seed>/progress.csv.  Checkpointing a
-    group and resuming it are not supported (each trainer stays individually saveable)."""
-    if resume:
-        raise RuntimeError("experiment_group does not resume: group checkpoints are not supported")
+    {seed: progress rows}; with log_dir, each seed's rows also go to <log_dir>/s<seed>/progress.csv.
+    checkpoint_dir: after every epoch the whole group is saved there as one generation (group_checkpoint.py: each
+    buffer in chunks of `chunk_rows` rows, only the chunks changed since the last save rewritten; `time/saving (s)`).
+    resume=True continues the group saved in checkpoint_dir after its last saved epoch, bit for bit, appending to each
+    seed's progress.csv; the seeds must be the saved ones in the saved order.  Without a checkpoint there it starts
+    afresh."""
+    if resume and not checkpoint_dir:
+        raise RuntimeError("experiment_group(resume=True) needs the checkpoint_dir to resume from")
     validate(variant)
     td3 = variant.get("algorithm", "SAC") == "TD3"
     seeds = [int(s) for s in seeds]
@@ -350,13 +403,16 @@ def experiment_group(variant, seeds, log_dir=None, num_epochs=None, obs_dim=None
     O, A = env_dims(variant["expl_environment_kwargs"], obs_dim, action_dim)
     ak = variant["algorithm_kwargs"]
     runs = []
+    restoring = bool(resume) and _checkpoint_exists(checkpoint_dir)
     for seed in seeds:
-        runs.append(_group_run(variant, seed, O, A, device))
+        runs.append(_group_run(variant, seed, O, A, device, prefill=not restoring))
         runs[-1]["sub"] = f"s{seed}"
+    ck, first_epoch = _group_checkpoint(runs, checkpoint_dir, restoring, chunk_rows)
     group = (TD3TrainerGroup if td3 else SACTrainerGroup)([r["trainer"] for r in runs])
     n_train = ak["num_trains_per_train_loop"]
     _group_epochs(runs, lambda: group.train_loop([r["buf"] for r in runs], n_train, batch_size=ak["batch_size"]),
-                  num_epochs if num_epochs is not None else ak["num_epochs"], n_train, log_dir, quiet, "seeds")
+                  num_epochs if num_epochs is not None else ak["num_epochs"], n_train, log_dir, quiet, "seeds", ck,
+                  first_epoch)
     return {r["seed"]: r["rows"] for r in runs}
 
 
@@ -368,17 +424,19 @@ def task_label(variant):
     return f"{env['env_name']}-{''.join(robots)}"
 
 
-def experiment_sweep(runs, log_dir=None, num_epochs=None, device=0, quiet=False, resume=False):
+def experiment_sweep(runs, log_dir=None, num_epochs=None, device=0, quiet=False, checkpoint_dir=None, resume=False,
+                     chunk_rows=DEFAULT_CHUNK_ROWS):
     """Several tasks x seeds, one process, one device: every entry of ``runs`` -- (variant, seed), or (variant, seed,
     obs_dim, action_dim) for a task without pinned dims -- is the run ``experiment(variant, seed=seed)`` would make, and
     every epoch's training block is ONE MixedSACTrainerGroup.train_loop (TD3 variants: MixedTD3TrainerGroup) over all
     runs, each on its own batch size (bit for bit its solo result).
     The runs must share the algorithm, the hidden sizes and the epoch plan (num_trains_per_train_loop, and num_epochs
     unless it is given here); dims and batch sizes may differ.  Returns the runs' progress rows, a list in the order of
-    ``runs``; with log_dir, each run's rows also go to <log_dir>/<task>-s<seed>/progress.csv.  Resuming is not
-    supported, as for experiment_group."""
-    if resume:
-        raise RuntimeError("experiment_sweep does not resume: group checkpoints are not supported")
+    ``runs``; with log_dir, each run's rows also go to <log_dir>/<task>-s<seed>/progress.csv.  checkpoint_dir, resume
+    and chunk_rows as for experiment_group: one generation for every run of the sweep, and a resume needs the saved
+    runs in the saved order."""
+    if resume and not checkpoint_dir:
+        raise RuntimeError("experiment_sweep(resume=True) needs the checkpoint_dir to resume from")
     specs = []
     for spec in runs:
         spec = tuple(spec)
@@ -410,13 +468,16 @@ def experiment_sweep(runs, log_dir=None, num_epochs=None, device=0, quiet=False,
             raise RuntimeError(f"sweep run {i} repeats {label}")
         labels.add(label)
     group_runs = []
+    restoring = bool(resume) and _checkpoint_exists(checkpoint_dir)
     for v, seed, O, A in specs:
-        group_runs.append(_group_run(v, seed, O, A, device))
+        group_runs.append(_group_run(v, seed, O, A, device, prefill=not restoring))
         group_runs[-1]["sub"] = f"{task_label(v)}-s{seed}"
+    ck, first_epoch = _group_checkpoint(group_runs, checkpoint_dir, restoring, chunk_rows)
     td3 = algo0 == "TD3"
     group = (MixedTD3TrainerGroup if td3 else MixedSACTrainerGroup)([r["trainer"] for r in group_runs])
     n_train = ak0["num_trains_per_train_loop"]
     batches = [r["ak"]["batch_size"] for r in group_runs]
     _group_epochs(group_runs, lambda: group.train_loop([r["buf"] for r in group_runs], n_train, batch_sizes=batches),
-                  num_epochs if num_epochs is not None else ak0["num_epochs"], n_train, log_dir, quiet, "runs")
+                  num_epochs if num_epochs is not None else ak0["num_epochs"], n_train, log_dir, quiet, "runs", ck,
+                  first_epoch)
     return [r["rows"] for r in group_runs]

@@ -222,6 +222,14 @@ class EnvReplayBuffer:
     def num_steps_can_sample(self):
         return int(self._lib.sac_buffer_size(self._h))
 
+    def top(self):
+        """The ring cursor: the storage row the next insert goes to."""
+        return int(self._lib.sac_buffer_top(self._h))
+
+    def rows_written(self):
+        """Rows stored since the buffer was created (every add_block row; never decreases, set_cursor leaves it)."""
+        return int(self._lib.sac_buffer_rows_written(self._h))
+
     # ---- checkpointing (the reference saves no buffer: rlkit get_snapshot() is {}) -----------------
     def read_rows(self, start, n):
         """Storage rows [start, start+n) as (obs, act, rew, next_obs, term) in the add_block layout."""
@@ -255,6 +263,15 @@ class EnvReplayBuffer:
         _lib.check(self._lib.sac_buffer_set_cursor(self._h, int(st["top"]), size), "sac_buffer_set_cursor")
         key = np.ascontiguousarray(st["rng_key"], dtype=np.uint32)
         _lib.check(self._lib.sac_rng_set_state(self._h, _lib.ptr(key), int(st["rng_pos"])), "sac_rng_set_state")
+
+    def set_cursor(self, top, size):
+        """Ring cursor and fill level (a restore re-inserts the saved rows from row 0, then sets them)."""
+        _lib.check(self._lib.sac_buffer_set_cursor(self._h, int(top), int(size)), "sac_buffer_set_cursor")
+
+    def set_rng_state(self, key, pos):
+        """The generator state rng_state() returned."""
+        key = np.ascontiguousarray(key, dtype=np.uint32)
+        _lib.check(self._lib.sac_rng_set_state(self._h, _lib.ptr(key), int(pos)), "sac_rng_set_state")
 
     def random_batch(self, batch_size, return_indices=False, lazy=None):
         """rlkit's random_batch.  By default (lazy) the batch is drawn and gathered on the device and STAYS there:

@@ -1,11 +1,12 @@
 #!/usr/bin/env python3
 """Counterpart of the reference's scripts/train.py for the MI355X path:
     python scripts/train.py --variant <variant.json> --seed S --log_dir DIR [--epochs N]
-    python scripts/train.py --variant <variant.json> --seeds S1 S2 ... --log_dir DIR [--epochs N]
-    python scripts/train.py --variants A.json B.json ... --seeds S1 S2 ... --log_dir DIR [--epochs N]
+    python scripts/train.py --variant <variant.json> --seeds S1 S2 ... --log_dir DIR [--epochs N] [--checkpoint]
+    python scripts/train.py --variants A.json B.json ... --seeds S1 S2 ... --log_dir DIR [--epochs N] [--checkpoint]
 (--seeds: one process trains every seed, the training blocks as one trainer group, SAC or TD3 (--agent);
  DIR/s<seed>/progress.csv each.  --variants: every (variant, seed) pair -- tasks of different dims and batch sizes --
- as one mixed trainer group; DIR/<task>-s<seed>/progress.csv each)
+ as one mixed trainer group; DIR/<task>-s<seed>/progress.csv each.  --checkpoint saves the whole group to
+ DIR/checkpoint after every epoch; the same command line with --resume DIR instead of --log_dir DIR continues it)
 Runs the variant unchanged (batch size, lrs, tau, period, buffer size ... from the JSON) on the
 HIP library with a synthetic environment of the task's dimensions (robosuite is not installed)."""
 import argparse
@@ -14,6 +15,7 @@ import sys
 
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 from robosuite_benchmark_amd.driver import experiment, experiment_group, experiment_sweep  # noqa: E402
+from robosuite_benchmark_amd.group_checkpoint import GroupMismatchError  # noqa: E402
 from robosuite_benchmark_amd.variant import default_variant, load_variant  # noqa: E402
 
 if __name__ == "__main__":
@@ -26,28 +28,35 @@ if __name__ == "__main__":
     ap.add_argument("--batch_size", type=int, default=256)
     ap.add_argument("--agent", type=str, default="SAC", choices=["SAC", "TD3"])
     ap.add_argument("--resume", type=str, default=None,
-                    help="an existing run directory (…_0000--s-0): continue it from its checkpoint/ after the last saved epoch")
+                    help="an existing run directory (…_0000--s-0): continue it from its checkpoint/ after the last saved "
+                         "epoch; with --seeds / --variants: the group's --log_dir, given the same seeds and variants in "
+                         "the same order")
     ap.add_argument("--no_checkpoint", action="store_true", help="do not save <run_dir>/checkpoint after every epoch")
     ap.add_argument("--seeds", type=int, nargs="+", default=None,
-                    help="train these seeds of the one configuration together (trainer groups; SAC or TD3, no "
-                         "checkpoints)")
+                    help="train these seeds of the one configuration together (trainer groups; SAC or TD3)")
     ap.add_argument("--variants", type=str, nargs="+", default=None,
                     help="variant files of different tasks: every (variant, seed of --seeds or --seed) pair trains "
-                         "together as one mixed trainer group (no checkpoints)")
+                         "together as one mixed trainer group")
+    ap.add_argument("--checkpoint", action="store_true",
+                    help="with --seeds / --variants and --log_dir DIR: save the whole group to DIR/checkpoint after "
+                         "every epoch (only the replay-buffer chunks changed since the last save are written)")
     args = ap.parse_args()
-    if args.variants:
-        if args.resume:
-            raise SystemExit("--variants does not resume (group checkpoints are not supported)")
-        seeds = args.seeds or [args.seed]
-        experiment_sweep([(load_variant(v), s) for v in args.variants for s in seeds], log_dir=args.log_dir,
-                         num_epochs=args.epochs)
-        sys.exit(0)
-    if args.seeds:
-        if args.resume:
-            raise SystemExit("--seeds does not resume (group checkpoints are not supported)")
-        variant = load_variant(args.variant) if args.variant else default_variant(env=args.env, seed=args.seeds[0],
-                                                                                  batch_size=args.batch_size, agent=args.agent)
-        experiment_group(variant, args.seeds, log_dir=args.log_dir, num_epochs=args.epochs)
+    if args.variants or args.seeds:
+        log_dir = args.resume or args.log_dir
+        if args.checkpoint and not log_dir:
+            raise SystemExit("--checkpoint needs --log_dir (the group is saved to <log_dir>/checkpoint)")
+        group_kw = dict(log_dir=log_dir, num_epochs=args.epochs, resume=bool(args.resume),
+                        checkpoint_dir=os.path.join(log_dir, "checkpoint") if (args.checkpoint or args.resume) else None)
+        try:
+            if args.variants:
+                seeds = args.seeds or [args.seed]
+                experiment_sweep([(load_variant(v), s) for v in args.variants for s in seeds], **group_kw)
+            else:
+                variant = load_variant(args.variant) if args.variant else default_variant(
+                    env=args.env, seed=args.seeds[0], batch_size=args.batch_size, agent=args.agent)
+                experiment_group(variant, args.seeds, **group_kw)
+        except GroupMismatchError as e:
+            raise SystemExit(f"--resume {args.resume}: {e}")
         sys.exit(0)
     variant = load_variant(args.variant) if args.variant else default_variant(env=args.env, seed=args.seed,
                                                                               batch_size=args.batch_size, agent=args.agent)
