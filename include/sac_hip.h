@@ -360,6 +360,21 @@ int td3_group_create(sac_group_t **out, sac_trainer_t *const *members, int n_mem
  * sac_train_loop(members[r], buffers[r], n_steps).  sac_group_train_loop and sac_group_destroy serve mixed groups too. */
 int sac_group_create_mixed(sac_group_t **out, sac_trainer_t *const *members, int n_members);
 int td3_group_create_mixed(sac_group_t **out, sac_trainer_t *const *members, int n_members);
+/* MLP groups: runs of the GENERAL step (sac_trainer_create_mlp / td3_trainer_create_mlp: hidden sizes other than two
+ * layers of at most 256 units -- a network-width or network-depth sweep) on one device.  1..SAC_GROUP_MAX trainers of one
+ * algorithm (sac_group_create_mlp: SAC, td3_group_create_mlp: TD3) that share the device and the hidden sizes (the
+ * policy's list and the Q nets' list); obs_dim, act_dim and batch may differ per member, as may every hyperparameter and
+ * noise seed, and TD3 members keep their own delayed-update plan as in td3_group_create.  Each stage of the general
+ * step's launch list is one grouped launch (the elementwise stages: one per action bound, up to 8 / up to 16 actions);
+ * every member keeps its own tiles, split reductions and summation orders, so its result -- weights, Adam state,
+ * scalars, diagnostics, the generator of its buffer -- is bit for bit that of sac_train_loop(members[r], buffers[r],
+ * n_steps), and the members stay ordinary trainers.  Refused (error, nothing changed): members with the shapes of the
+ * fused kernels (their solo step is not the general step), members of the other algorithm, different hidden sizes or
+ * devices, members confined by sac_trainer_set_xcd[_mask], the same trainer or buffer twice, buffers of other dims than
+ * their member, empty buffers, more than SAC_GROUP_MAX members.  The other group kinds keep refusing general-step
+ * members.  sac_group_train_loop and sac_group_destroy serve MLP groups too. */
+int sac_group_create_mlp(sac_group_t **out, sac_trainer_t *const *members, int n_members);
+int td3_group_create_mlp(sac_group_t **out, sac_trainer_t *const *members, int n_members);
 int sac_group_destroy(sac_group_t *g);
 int sac_group_train_loop(sac_group_t *g, sac_buffer_t *const *buffers, int64_t n_steps, float *diag_first,
                          float *diag_last);

@@ -226,10 +226,12 @@ struct GOperand {
 // A_RC / B_RC (compile time: the jobs of a launch share them): the operand is contiguous along the reduction -- forward
 // (true, true), backward through a layer (true, false), weight gradient (false, false).  Only the thread -> element map
 // and the LDS layout depend on it; the addresses always use the job's strides.
+// (the tile body of k_g_gemm, and of k_g_gemm_group further down, which runs it for every member of an MLP group: bx is the
+//  block's index in its own stage's grid)
 template <bool A_RC, bool B_RC>
-__global__ __launch_bounds__(64 * GW) void k_g_gemm(GemmStage T) {
+__device__ __forceinline__ void g_gemm_body(const GemmStage &T, int bx) {
     __shared__ __attribute__((aligned(16))) float As[GT * GLD], Bs[GT * GLD];
-    const int splitk = T.splitk, tile_lin = (int)blockIdx.x / splitk, ks = (int)blockIdx.x - tile_lin * splitk;
+    const int splitk = T.splitk, tile_lin = bx / splitk, ks = bx - tile_lin * splitk;
     int li = 0;
 #pragma unroll
     for (int q = 1; q < GMAXJ; ++q) li = (tile_lin >= T.tile0[q]) ? q : li;
@@ -422,6 +424,11 @@ __global__ __launch_bounds__(64 * GW) void k_g_gemm(GemmStage T) {
     GSTAMP(7);
 }
 
+template <bool A_RC, bool B_RC>
+__global__ __launch_bounds__(64 * GW) void k_g_gemm(GemmStage T) {
+    g_gemm_body<A_RC, B_RC>(T, (int)blockIdx.x);
+}
+
 // ------------------------------------------------------------------------------------------
 // elementwise kernels
 // ------------------------------------------------------------------------------------------
@@ -496,14 +503,14 @@ __device__ __forceinline__ void small_layer_rows(const float *X, int K, const fl
 }
 
 template <int MA>       // MA: 8 for up to eight actions, else 16
-__global__ __launch_bounds__(256) void k_g_head(GDev d, const float *__restrict__ S, SlotLayout SL, StepArg sa) {
+__device__ __forceinline__ void g_head_body(GDev d, const float *__restrict__ S, SlotLayout SL, StepArg sa, unsigned bx, unsigned nx) {
     const int n = d.n, O = d.O, A = d.A, ldq = d.ldq;
     __shared__ float part[GRW][16][33];
     __shared__ float xs[GRW][GCK];
     __shared__ float ws[32][GCK + 1];
     {
         const int w = 2 * O + A, tot = n * w;               // (32-bit: checked at creation)
-        for (int e = (int)(blockIdx.x * 256 + threadIdx.x); e < tot; e += (int)(gridDim.x * 256)) {
+        for (int e = (int)(bx * 256 + threadIdx.x); e < tot; e += (int)(nx * 256)) {
             const int b = e / w, k = e - b * w;
             if (k < O) {
                 const float v = S[SL.off_obs + (long long)b * O + k];
@@ -516,7 +523,7 @@ __global__ __launch_bounds__(256) void k_g_head(GDev d, const float *__restrict_
             }
         }
     }
-    const int r0 = blockIdx.x * GRW, a = threadIdx.x & 15;
+    const int r0 = bx * GRW, a = threadIdx.x & 15;
     small_layer_rows<2 * MA>(d.PHl, d.KPl, d.Wh, A, true, r0, 2 * n, part, xs, ws);
     const int rr = threadIdx.x >> 4, r = r0 + rr;
     if (rr < GRW && r < 2 * n) {
@@ -558,7 +565,7 @@ __global__ __launch_bounds__(256) void k_g_head(GDev d, const float *__restrict_
     asm volatile("s_waitcnt vmcnt(0) lgkmcnt(0)\n\ts_barrier" ::: "memory");      // (log pi left through sc1 stores: see k_g_gemm's split tail)
     if (threadIdx.x == 0) {
         const unsigned old = __hip_atomic_fetch_add(d.done, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-        am_last = (old == gridDim.x - 1) ? 1u : 0u;
+        am_last = (old == nx - 1) ? 1u : 0u;
         if (am_last) __hip_atomic_store(d.done, 0u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);     // for the next step
     }
     __syncthreads();
@@ -585,14 +592,18 @@ __global__ __launch_bounds__(256) void k_g_head(GDev d, const float *__restrict_
     c->alpha_loss = -((la * mean_lp) + 0.0f);
     c->log_alpha = nla; c->a_m = m; c->a_v = v; c->alpha = expf(nla);
 }
+template <int MA>
+__global__ __launch_bounds__(256) void k_g_head(GDev d, const float *__restrict__ S, SlotLayout SL, StepArg sa) {
+    g_head_body<MA>(d, S, SL, sa, blockIdx.x, gridDim.x);
+}
 
 // One workgroup per batch row b.  The Q nets' LAST layers (one output each: a dot product over the last hidden layer -- Q1, Q2
 // on (s, a) and (s, a_new), the targets on (s', a')), then the min over the twin nets (actor loss, target), the Bellman target
 // and dL/dq of the passes that carry a gradient -- critic rows 2 (q - y) / n, actor rows -1/n to the smaller of Q1, Q2(s, a_new)
 // (torch.min: a tie splits it) -- and the backward pass through those last layers: dL/dh = dq w where h > 0.  Three launches
 // (a matrix product with ONE output column, this kernel, a matrix product with a reduction of length one) as one.
-__global__ __launch_bounds__(256) void k_g_loss(GDev d, const float *__restrict__ S, SlotLayout SL) {
-    const int b = blockIdx.x, n = d.n, K = d.KQl;
+__device__ __forceinline__ void g_loss_body(GDev d, const float *__restrict__ S, SlotLayout SL, unsigned bx) {
+    const int b = bx, n = d.n, K = d.KQl;
     __shared__ float red[4][8];
     __shared__ float s_dq[4];
     const float *h[6] = {d.QHl[0] + (long long)b * K, d.QHl[0] + (long long)(n + b) * K, d.QHl[1] + (long long)b * K,
@@ -644,14 +655,17 @@ __global__ __launch_bounds__(256) void k_g_loss(GDev d, const float *__restrict_
         for (int q = 0; q < 4; ++q) o[q][k] = (h[q][k] > 0.f) ? s_dq[q] * w[q][k] : 0.f;
     }
 }
+__global__ __launch_bounds__(256) void k_g_loss(GDev d, const float *__restrict__ S, SlotLayout SL) {
+    g_loss_body(d, S, SL, blockIdx.x);
+}
 
 // One workgroup per GRW batch rows: the actor-loss gradient w.r.t. a_new through the FIRST layers of Q1 and Q2 (the action columns
 // of W1: a dot product over the first hidden layer per action), d/d(mean, log_std) of mean(alpha log_pi - min Q) through
 // a = tanh(mean + std eps), and the backward pass through the policy's head layer (2A terms per hidden unit, masked).  Three
 // launches (a matrix product with A output columns, the elementwise kernel, a matrix product with a reduction of length 2A) as one.
 template <int MA>       // MA: 8 for up to eight actions, else 16
-__global__ __launch_bounds__(256) void k_g_polgrad(GDev d) {
-    const int b0 = blockIdx.x * GRW, n = d.n, A = d.A, H0 = d.HQ0, ldq = d.ldq, t = threadIdx.x;
+__device__ __forceinline__ void g_polgrad_body(GDev d, unsigned bx) {
+    const int b0 = bx * GRW, n = d.n, A = d.A, H0 = d.HQ0, ldq = d.ldq, t = threadIdx.x;
     __shared__ float part[GRW][16][33];
     __shared__ float dhd[GRW][32];
     __shared__ float gs[GRW][2][GCK];          // dL/d(first hidden) of Q1 | Q2, the actor rows of this workgroup, one chunk
@@ -787,6 +801,10 @@ __global__ __launch_bounds__(256) void k_g_polgrad(GDev d) {
             if (b0 + q < n) d.dPZl[(long long)(b0 + q) * K + k] = (hc[q] > 0.f) ? sacc[q] : 0.f;
     }
 }
+template <int MA>
+__global__ __launch_bounds__(256) void k_g_polgrad(GDev d) {
+    g_polgrad_body<MA>(d, blockIdx.x);
+}
 
 __device__ void diag_block(const GDev &d, const StepArg &sa);
 __device__ void td3_diag_block(const GDev &d, const StepArg &sa);
@@ -872,14 +890,14 @@ __device__ void diag_block(const GDev &d, const StepArg &sa) {
 // critic pass: the Q nets' input rows [(s, a) ; (s', a~)], a~ = tanh(target policy(s')) + clamp(N(0,1) sigma, +-clip)
 // (the sum is NOT clipped to the action range)
 template <int MA>
-__global__ __launch_bounds__(256) void k_g_td3_head(GDev d, const float *__restrict__ S, SlotLayout SL, StepArg sa) {
+__device__ __forceinline__ void g_td3_head_body(GDev d, const float *__restrict__ S, SlotLayout SL, StepArg sa, unsigned bx, unsigned nx) {
     const int n = d.n, O = d.O, A = d.A, ldq = d.ldq;
     __shared__ float part[GRW][16][33];
     __shared__ float xs[GRW][GCK];
     __shared__ float ws[32][GCK + 1];
     {
         const int w = 2 * O + A, tot = n * w;
-        for (int e = (int)(blockIdx.x * 256 + threadIdx.x); e < tot; e += (int)(gridDim.x * 256)) {
+        for (int e = (int)(bx * 256 + threadIdx.x); e < tot; e += (int)(nx * 256)) {
             const int b = e / w, k = e - b * w;
             if (k < O) d.XQ[(long long)b * ldq + k] = S[SL.off_obs + (long long)b * O + k];
             else if (k < 2 * O) d.XQ[(long long)(n + b) * ldq + (k - O)] = S[SL.off_nobs + (long long)b * O + (k - O)];
@@ -887,7 +905,7 @@ __global__ __launch_bounds__(256) void k_g_td3_head(GDev d, const float *__restr
         }
     }
     // the target policy's head layer (A outputs) on the GRW rows of this workgroup, then thread = (row, action)
-    const int r0 = blockIdx.x * GRW, a = threadIdx.x & 15, rr = threadIdx.x >> 4, b = r0 + rr;
+    const int r0 = bx * GRW, a = threadIdx.x & 15, rr = threadIdx.x >> 4, b = r0 + rr;
     small_layer_rows<MA>(d.PHTl, d.KPl, d.WhT, A, false, r0, n, part, xs, ws);
     if (rr < GRW && b < n && a < A) {
         float mean = part[rr][0][a];
@@ -902,12 +920,16 @@ __global__ __launch_bounds__(256) void k_g_td3_head(GDev d, const float *__restr
         d.XQ[(long long)(n + b) * ldq + O + a] = act;
     }
 }
+template <int MA>
+__global__ __launch_bounds__(256) void k_g_td3_head(GDev d, const float *__restrict__ S, SlotLayout SL, StepArg sa) {
+    g_td3_head_body<MA>(d, S, SL, sa, blockIdx.x, gridDim.x);
+}
 
 // One workgroup per batch row b: the LAST layers of Q1, Q2 on (s, a) and of their targets on (s', a~) (one output each), then
 // y = reward_scale r + (1 - d) discount min(T1, T2)(s', a~), dL/dq_i = 2 (q_i - y) / n, and the backward pass through
 // those last layers (k_g_loss's structure).
-__global__ __launch_bounds__(256) void k_g_td3_loss(GDev d, const float *__restrict__ S, SlotLayout SL) {
-    const int b = blockIdx.x, n = d.n, K = d.KQl;
+__device__ __forceinline__ void g_td3_loss_body(GDev d, const float *__restrict__ S, SlotLayout SL, unsigned bx) {
+    const int b = bx, n = d.n, K = d.KQl;
     __shared__ float red[4][4];
     __shared__ float s_dq[2];
     const float *h[4] = {d.QHl[0] + (long long)b * K, d.QHl[1] + (long long)b * K, d.THl[0] + (long long)b * K, d.THl[1] + (long long)b * K};
@@ -952,20 +974,23 @@ __global__ __launch_bounds__(256) void k_g_td3_loss(GDev d, const float *__restr
         for (int q = 0; q < 2; ++q) o[q][k] = (h[q][k] > 0.f) ? s_dq[q] * w[q][k] : 0.f;
     }
 }
+__global__ __launch_bounds__(256) void k_g_td3_loss(GDev d, const float *__restrict__ S, SlotLayout SL) {
+    g_td3_loss_body(d, S, SL, blockIdx.x);
+}
 
 // actor pass: the online policy's head layer (A outputs) and Q1's input rows [obs | tanh(policy(s))]; the loss -mean Q1 has the
 // gradient -1/n on every row
 template <int MA>
-__global__ __launch_bounds__(256) void k_g_td3_ahead(GDev d, const float *__restrict__ S, SlotLayout SL) {
+__device__ __forceinline__ void g_td3_ahead_body(GDev d, const float *__restrict__ S, SlotLayout SL, unsigned bx, unsigned nx) {
     const int n = d.n, O = d.O, A = d.A, ldq = d.ldq;
     __shared__ float part[GRW][16][33];
     __shared__ float xs[GRW][GCK];
     __shared__ float ws[32][GCK + 1];
-    for (int e = (int)(blockIdx.x * 256 + threadIdx.x); e < n * O; e += (int)(gridDim.x * 256)) {
+    for (int e = (int)(bx * 256 + threadIdx.x); e < n * O; e += (int)(nx * 256)) {
         const int b = e / O, k = e - b * O;
         d.XA[(long long)b * ldq + k] = S[SL.off_obs + (long long)b * O + k];
     }
-    const int r0 = blockIdx.x * GRW, a = threadIdx.x & 15, rr = threadIdx.x >> 4, b = r0 + rr;
+    const int r0 = bx * GRW, a = threadIdx.x & 15, rr = threadIdx.x >> 4, b = r0 + rr;
     small_layer_rows<MA>(d.PHl, d.KPl, d.Wh, A, false, r0, n, part, xs, ws);
     if (rr < GRW && b < n && a < A) {
         float mean = part[rr][0][a];
@@ -979,11 +1004,15 @@ __global__ __launch_bounds__(256) void k_g_td3_ahead(GDev d, const float *__rest
         if (a == 0) d.DQA[b] = -1.0f / (float)n;
     }
 }
+template <int MA>
+__global__ __launch_bounds__(256) void k_g_td3_ahead(GDev d, const float *__restrict__ S, SlotLayout SL) {
+    g_td3_ahead_body<MA>(d, S, SL, blockIdx.x, gridDim.x);
+}
 
 // actor pass: Q1's last layer on (s, pi(s)) (one output per row: Q1(s, pi(s)), the actor loss's statistic) and the backward pass
 // through it for the loss -mean Q1: dL/dh = -1/n w where h > 0.  One workgroup per batch row.
-__global__ __launch_bounds__(256) void k_g_td3_qa(GDev d, int backward) {
-    const int b = blockIdx.x, n = d.n, K = d.KQl;
+__device__ __forceinline__ void g_td3_qa_body(GDev d, int backward, unsigned bx) {
+    const int b = bx, n = d.n, K = d.KQl;
     __shared__ float red[4];
     const float *h = d.AHl + (long long)b * K, *w = d.Wl[0];
     float acc = 0.f;
@@ -999,12 +1028,15 @@ __global__ __launch_bounds__(256) void k_g_td3_qa(GDev d, int backward) {
     float *o = d.dAZl + (long long)b * K;
     for (int k = threadIdx.x; k < K; k += 256) o[k] = (h[k] > 0.f) ? g * w[k] : 0.f;
 }
+__global__ __launch_bounds__(256) void k_g_td3_qa(GDev d, int backward) {
+    g_td3_qa_body(d, backward, blockIdx.x);
+}
 
 // actor pass, one workgroup per GRW batch rows: dL/da through the action columns of Q1's first layer, dL/d(pre-tanh) = dL/da (1 - a^2),
 // and the backward pass through the policy's head layer (k_g_polgrad's structure with one critic and A head rows)
 template <int MA>
-__global__ __launch_bounds__(256) void k_g_td3_polgrad(GDev d) {
-    const int b0 = blockIdx.x * GRW, n = d.n, A = d.A, H0 = d.HQ0, ldq = d.ldq, t = threadIdx.x;
+__device__ __forceinline__ void g_td3_polgrad_body(GDev d, unsigned bx) {
+    const int b0 = bx * GRW, n = d.n, A = d.A, H0 = d.HQ0, ldq = d.ldq, t = threadIdx.x;
     __shared__ float part[GRW][16][33];
     __shared__ float dhd[GRW][16];
     __shared__ float gs[GRW][GCK];
@@ -1110,6 +1142,10 @@ __global__ __launch_bounds__(256) void k_g_td3_polgrad(GDev d) {
             if (b0 + q < n) d.dPZl[(long long)(b0 + q) * K + k] = (hc[q] > 0.f) ? sacc[q] : 0.f;
     }
 }
+template <int MA>
+__global__ __launch_bounds__(256) void k_g_td3_polgrad(GDev d) {
+    g_td3_polgrad_body<MA>(d, blockIdx.x);
+}
 
 // TD3's statistics in the slots of the SAC vector (sac_hip.h): sa.pad bit 0 = the critic part (every step), bit 1 = the policy
 // part (policy / statistics steps).  The device copy keeps the most recent value of every entry; a launch whose caller
@@ -1176,6 +1212,94 @@ __device__ void td3_diag_block(const GDev &d, const StepArg &sa) {
         __syncthreads();
         if (threadIdx.x < SAC_DIAG_N) d.diag_last[threadIdx.x] = ld_sc1(d.diag_dev + threadIdx.x);
     }
+}
+
+// ------------------------------------------------------------------------------------------
+// MLP groups (sac_group_create_mlp / td3_group_create_mlp): the general step of R trainers with one set of hidden sizes,
+// one grouped launch per stage of its launch list.  Obs / action dims and batch may differ per member, so every member
+// keeps its own job table, tile order and split factor; the bodies above run unchanged on the member's own block index.
+// ------------------------------------------------------------------------------------------
+// a member's arguments (device table, written per call): its elementwise kernels' GDev and its loop slots
+struct GenMember {
+    GDev d;
+    SlotLayout SL;
+    const float *slots;            // the member's loop slot 0: slot j at slots + j * SL.slot_floats
+};
+// a member's step (the [step][R] table, written once per chunk): SAC uses sa and polyak; TD3 sa = the critic pass
+// (kind 1, its Polyak average on policy steps: polyak = pstep), sp = the actor pass (kind 2)
+struct GenGroupStep {
+    StepArg sa, sp;
+    int actor, pstep, polyak, pad_;
+};
+// which members a grouped launch serves: every member on its sa / members with `actor` on their sp / members with `pstep`
+enum { GSEL_ALL = 0, GSEL_ACTOR = 1, GSEL_PSTEP = 2 };
+// kernel argument of k_g_gemm_group: the blocks of device member k are start[k] .. start[k + 1] - 1 (entries past the
+// group's last member hold 1 << 30)
+struct GemmGroupMap {
+    int start[SAC_GROUP_MAX + 1];
+    int sel, pad_;
+};
+
+__device__ __forceinline__ bool gsel_skip(const GenGroupStep &st, int sel) {
+    return (sel == GSEL_ACTOR && !st.actor) || (sel == GSEL_PSTEP && !st.pstep);
+}
+
+// Stage k of every member in one grid: block -> member through the launch's prefix table (uniform: a member's blocks are
+// contiguous), then block -> (job, tile, split part) through the member's own stage header H[member] (its tile0[],
+// splitk, scratch, tile counters: written once at group creation) -- the same map and the same fixed-order split tail as
+// the member's solo launch.  The step's scalars come from the member's [step][R] entry.
+template <bool A_RC, bool B_RC>
+__global__ __launch_bounds__(64 * GW) void k_g_gemm_group(const GemmStage *__restrict__ H, const GenMember *__restrict__ G,
+                                                          const GenGroupStep *__restrict__ SA, int slot, GemmGroupMap P) {
+    const int bx = (int)blockIdx.x;
+    int m = 0;
+#pragma unroll
+    for (int q = 1; q < SAC_GROUP_MAX; ++q) m = (bx >= P.start[q]) ? q : m;
+    const GenGroupStep &st = SA[m];
+    if (gsel_skip(st, P.sel)) return;
+    union { GemmStage T; unsigned long long w[sizeof(GemmStage) / 8]; } uh;
+    {
+        const __attribute__((address_space(4))) unsigned long long *src =
+            (const __attribute__((address_space(4))) unsigned long long *)(uintptr_t)(H + m);
+#pragma unroll
+        for (int q = 0; q < (int)(sizeof(GemmStage) / 8); ++q) uh.w[q] = src[q];
+    }
+    const StepArg &sa = P.sel == GSEL_ALL ? st.sa : st.sp;
+    uh.T.S = G[m].slots + (size_t)slot * G[m].SL.slot_floats;
+    uh.T.bc1 = sa.bc1; uh.T.bc2s = sa.bc2s;
+    uh.T.polyak = P.sel == GSEL_ALL ? st.polyak : 1;
+    uh.T.keep_grad = (sa.pad2 & 2u) ? 1 : 0;
+    g_gemm_body<A_RC, B_RC>(uh.T, bx - P.start[m]);
+}
+
+// the elementwise kernels of the stage list (KIND: GK_*), blockIdx.y = the device member inside the launch's class range.
+// A block past its member's own x-extent (the solo launch's grid, from the member's batch) leaves at entry, before any LDS
+// use or barrier; so do the blocks of a member the launch does not serve this step (sel).
+enum { GK_HEAD = 1, GK_LOSS, GK_POLGRAD, GK_DIAG, GK_TD3_HEAD, GK_TD3_LOSS, GK_TD3_AHEAD, GK_TD3_QA, GK_TD3_POLGRAD };
+template <int KIND, int MA>
+__global__ __launch_bounds__(256) void k_g_small_group(const GenMember *__restrict__ G, const GenGroupStep *__restrict__ SA,
+                                                       int slot, int sel) {
+    const GenMember &g = G[blockIdx.y];
+    const GenGroupStep &st = SA[blockIdx.y];
+    if (gsel_skip(st, sel)) return;
+    const int n = g.d.n, bx = (int)blockIdx.x;
+    constexpr bool rows2 = KIND == GK_HEAD, rows1 = KIND == GK_LOSS || KIND == GK_TD3_LOSS || KIND == GK_TD3_QA;
+    const int nx = KIND == GK_DIAG ? 1 : rows1 ? n : rows2 ? (2 * n + GRW - 1) / GRW : (n + GRW - 1) / GRW;
+    if (bx >= nx) return;
+    const float *S = g.slots + (size_t)slot * g.SL.slot_floats;
+    const StepArg &sa = sel == GSEL_ALL ? st.sa : st.sp;
+    if constexpr (KIND == GK_HEAD) g_head_body<MA>(g.d, S, g.SL, sa, bx, nx);
+    else if constexpr (KIND == GK_LOSS) g_loss_body(g.d, S, g.SL, bx);
+    else if constexpr (KIND == GK_POLGRAD) g_polgrad_body<MA>(g.d, bx);
+    else if constexpr (KIND == GK_DIAG) {
+        if (g.d.algo == 1) td3_diag_block(g.d, sa);
+        else diag_block(g.d, sa);
+    }
+    else if constexpr (KIND == GK_TD3_HEAD) g_td3_head_body<MA>(g.d, S, g.SL, sa, bx, nx);
+    else if constexpr (KIND == GK_TD3_LOSS) g_td3_loss_body(g.d, S, g.SL, bx);
+    else if constexpr (KIND == GK_TD3_AHEAD) g_td3_ahead_body<MA>(g.d, S, g.SL, bx, nx);
+    else if constexpr (KIND == GK_TD3_QA) g_td3_qa_body(g.d, st.pstep, bx);
+    else g_td3_polgrad_body<MA>(g.d, bx);
 }
 
 }  // namespace gen

@@ -3440,11 +3440,27 @@ struct GroupClass {
     void (*fa3)(const GroupMember *, const Td3GroupStep *, int) = nullptr;
     void (*fb3)(const GroupMember *, const Td3GroupStep *, int) = nullptr, (*fb3a)(const GroupMember *, const Td3GroupStep *, int) = nullptr;
     void (*bw3)(const GroupMember *, const Td3GroupStep *, int, int) = nullptr, (*bw3a)(const GroupMember *, const Td3GroupStep *, int, int) = nullptr;
+    int ma = 0;                                       // MLP groups: the action bound of the class's elementwise kernels (8 / 16)
+};
+
+// One grouped launch of an MLP group's step (sac_group_create_mlp): stage `kind` (GS_*) of the members' general-step
+// launch list.  GS_GEMM: the members' stage headers are hdr[stage R .. stage R + R - 1] of the header table; `map` is the
+// block -> member prefix table, `grid` the sum of the members' own grids.  The elementwise kernels go once per variant
+// class (fn[c] on the class's largest x-extent gx[c]) -- or, the kernels without an action bound, once for all (fn[0], gx[0]).
+typedef void (*GenSmallFn)(const gen::GenMember *, const gen::GenGroupStep *, int, int);
+struct GroupGenStage {
+    int kind = 0, mode = 0, sel = 0, list = 0;        // GS_* and its mode; gen::GSEL_*; TD3: 0 the critic pass, 1 the actor pass
+    int hdr = 0, grid = 0;
+    gen::GemmGroupMap map{};
+    bool per_class = false;
+    GenSmallFn fn[4] = {};
+    int gx[4] = {};
 };
 
 struct sac_group {
     int R = 0, device = 0, algo = 0;                  // algo: 0 SAC, 1 TD3 (every member's)
     bool mixed = false;                               // sac_group_create_mixed / td3_group_create_mixed
+    bool mlp = false;                                 // sac_group_create_mlp / td3_group_create_mlp (general-step members)
     sac_trainer *m[SAC_GROUP_MAX] = {};
     int ord[SAC_GROUP_MAX] = {};                      // device table entry k (member and step tables) is member ord[k]
     int ncls = 0;
@@ -3459,6 +3475,12 @@ struct sac_group {
     GatherMember *d_gat = nullptr, *h_gat = nullptr;  // [2 halves][R] (sorted by gather class, per call)
     StepArg *d_sa = nullptr, *h_sa = nullptr;         // SAC: [2 halves][LOOP_CH steps][R] (device order)
     Td3GroupStep *d_ts = nullptr, *h_ts = nullptr;    // TD3: [2 halves][LOOP_CH steps][R] (device order)
+    // MLP groups: the grouped stage list, the members' GEMM stage headers [GEMM stage][R] (written at creation), the member
+    // table [R] and the step table [2 halves][LOOP_CH steps][R] (device order)
+    std::vector<GroupGenStage> gst;
+    gen::GemmStage *d_hdr = nullptr;
+    gen::GenMember *d_gm = nullptr, *h_gm = nullptr;
+    gen::GenGroupStep *d_gs = nullptr, *h_gs = nullptr;
 };
 
 static void group_free(sac_group *g) {
@@ -3470,6 +3492,7 @@ static void group_free(sac_group *g) {
     for (auto &e : g->ev_in) if (e) (void)hipEventDestroy(e);
     if (g->ev_end) (void)hipEventDestroy(g->ev_end);
     if (g->d_tab) (void)hipFree(g->d_tab);
+    if (g->d_hdr) (void)hipFree(g->d_hdr);
     if (g->h_tab) (void)hipHostFree(g->h_tab);
     if (g->s) (void)hipStreamDestroy(g->s);
     if (g->s2) (void)hipStreamDestroy(g->s2);
@@ -3477,9 +3500,16 @@ static void group_free(sac_group *g) {
 }
 
 // what a member must be (checked at creation and again in front of every call: a member may have been confined since)
-static int group_member_ok(const sac_trainer *t, int i, int algo) {
+static int group_member_ok(const sac_trainer *t, int i, int algo, bool mlp = false) {
     if (algo == 0) SAC_REQUIRE(t->algo == 0, "trainer group member %d is a TD3 trainer: groups hold SAC trainers only", i);
     else SAC_REQUIRE(t->algo == 1, "trainer group member %d is a SAC trainer: TD3 groups hold TD3 trainers only", i);
+    if (mlp) {
+        SAC_REQUIRE(t->gen, "trainer group member %d has the shapes of the fused kernels (two hidden layers of at most 256 "
+                    "units): MLP groups take general-step members only", i);
+        SAC_REQUIRE(t->xcd_mask == 0xffu, "trainer group member %d is confined to XCDs (sac_trainer_set_xcd[_mask]): a group "
+                    "spans the whole chip", i);
+        return 0;
+    }
     SAC_REQUIRE(!t->gen, "trainer group member %d runs the general step (hidden sizes beyond two layers of at most 256 units): "
                 "groups take the shapes of the fused kernels only", i);
     SAC_REQUIRE(t->Bt <= 256, "trainer group member %d has batch %d: groups take batches of at most 256 rows", i, t->Bt);
@@ -3496,6 +3526,49 @@ static void member_extents(const sac_trainer *t, int algo, int &xa, int &xb, int
     xa = 4 * SPv * NB;
     if (algo == 0) { xb = xc = 4 * SPv * NB; xpi = 0; }
     else { xb = xc = 8 * ((SPv * NB + 3) / 4); xpi = SPv * NB; }
+}
+
+// a group's tables (device, with their pinned host images: members b_mem | draws | gathers | steps b_sa), its two streams,
+// its events, and its tenancy of the device's fused-launch gate
+static int group_tables(sac_group *g, size_t b_mem, size_t b_sa) {
+    const int R = g->R;
+    const size_t b_smp = sizeof(SampleMember) * 2 * R, b_gat = sizeof(GatherMember) * 2 * R;
+    const size_t o_smp = (b_mem + 255) & ~(size_t)255, o_gat = o_smp + ((b_smp + 255) & ~(size_t)255);
+    const size_t o_sa = o_gat + ((b_gat + 255) & ~(size_t)255), total = o_sa + b_sa;
+    if (hipMalloc(reinterpret_cast<void **>(&g->d_tab), total) != hipSuccess ||
+        hipHostMalloc(reinterpret_cast<void **>(&g->h_tab), total, hipHostMallocDefault) != hipSuccess ||
+        hipStreamCreateWithFlags(&g->s, hipStreamNonBlocking) != hipSuccess ||
+        hipStreamCreateWithFlags(&g->s2, hipStreamNonBlocking) != hipSuccess) {
+        sac::set_error("out of device or pinned host memory for a trainer group");
+        return -1;
+    }
+    for (int k = 0; k < 2; ++k)
+        if (hipEventCreateWithFlags(&g->ev_ready[k], hipEventDisableTiming) != hipSuccess ||
+            hipEventCreateWithFlags(&g->ev_done[k], hipEventDisableTiming) != hipSuccess ||
+            hipEventCreateWithFlags(&g->ev_copied[k], hipEventDisableTiming) != hipSuccess) {
+            sac::set_error("hipEventCreate failed");
+            return -1;
+        }
+    for (auto &e : g->ev_in)
+        if (hipEventCreateWithFlags(&e, hipEventDisableTiming) != hipSuccess) { sac::set_error("hipEventCreate failed"); return -1; }
+    if (hipEventCreateWithFlags(&g->ev_end, hipEventDisableTiming) != hipSuccess) { sac::set_error("hipEventCreate failed"); return -1; }
+    if (g->mlp) { g->d_gm = reinterpret_cast<gen::GenMember *>(g->d_tab); g->h_gm = reinterpret_cast<gen::GenMember *>(g->h_tab); }
+    else { g->d_mem = reinterpret_cast<GroupMember *>(g->d_tab); g->h_mem = reinterpret_cast<GroupMember *>(g->h_tab); }
+    g->d_smp = reinterpret_cast<SampleMember *>(g->d_tab + o_smp); g->h_smp = reinterpret_cast<SampleMember *>(g->h_tab + o_smp);
+    g->d_gat = reinterpret_cast<GatherMember *>(g->d_tab + o_gat); g->h_gat = reinterpret_cast<GatherMember *>(g->h_tab + o_gat);
+    if (g->mlp) { g->d_gs = reinterpret_cast<gen::GenGroupStep *>(g->d_tab + o_sa); g->h_gs = reinterpret_cast<gen::GenGroupStep *>(g->h_tab + o_sa); }
+    else if (g->algo == 0) { g->d_sa = reinterpret_cast<StepArg *>(g->d_tab + o_sa); g->h_sa = reinterpret_cast<StepArg *>(g->h_tab + o_sa); }
+    else { g->d_ts = reinterpret_cast<Td3GroupStep *>(g->d_tab + o_sa); g->h_ts = reinterpret_cast<Td3GroupStep *>(g->h_tab + o_sa); }
+    {   // a tenant of the device's fused-launch gate: no fused trainer's launch may overlap the group's grids
+        FusedGate &G = g_gate[g->device & 63];
+        std::lock_guard<std::mutex> lk(G.mu);
+        if (!G.ev && hipEventCreateWithFlags(&G.ev, hipEventDisableTiming) != hipSuccess) {
+            sac::set_error("hipEventCreate failed");
+            return -1;
+        }
+        G.live += 1;
+    }
+    return 0;
 }
 
 static int group_create(sac_group_t **out, sac_trainer_t *const *members, int n_members, int algo, bool mixed) {
@@ -3601,41 +3674,140 @@ static int group_create(sac_group_t **out, sac_trainer_t *const *members, int n_
         g->grid_dpi = std::max(g->grid_dpi, t->dw_pi.njobs + 1);
     }
     const int R = n_members;
-    const size_t b_mem = sizeof(GroupMember) * R, b_smp = sizeof(SampleMember) * 2 * R, b_gat = sizeof(GatherMember) * 2 * R;
-    const size_t b_sa = (algo ? sizeof(Td3GroupStep) : sizeof(StepArg)) * 2 * LOOP_CH * R;
-    const size_t o_smp = (b_mem + 255) & ~(size_t)255, o_gat = o_smp + ((b_smp + 255) & ~(size_t)255);
-    const size_t o_sa = o_gat + ((b_gat + 255) & ~(size_t)255), total = o_sa + b_sa;
-    if (hipMalloc(reinterpret_cast<void **>(&g->d_tab), total) != hipSuccess ||
-        hipHostMalloc(reinterpret_cast<void **>(&g->h_tab), total, hipHostMallocDefault) != hipSuccess ||
-        hipStreamCreateWithFlags(&g->s, hipStreamNonBlocking) != hipSuccess ||
-        hipStreamCreateWithFlags(&g->s2, hipStreamNonBlocking) != hipSuccess) {
-        sac::set_error("out of device or pinned host memory for a trainer group");
+    if (group_tables(g, sizeof(GroupMember) * R, (algo ? sizeof(Td3GroupStep) : sizeof(StepArg)) * 2 * LOOP_CH * R)) return fail(-1);
+    *out = g;
+    return 0;
+}
+
+// the grouped instance of an elementwise stage of the general step (ma: the class's action bound; 0: a kernel without one)
+static GenSmallFn gen_small_fn(int kind, int ma) {
+#define GEN_SMALL(K) (ma == 16 ? &gen::k_g_small_group<gen::K, 16> : &gen::k_g_small_group<gen::K, 8>)
+    switch (kind) {
+    case GS_HEAD: return GEN_SMALL(GK_HEAD);
+    case GS_POLGRAD: return GEN_SMALL(GK_POLGRAD);
+    case GS_TD3_HEAD: return GEN_SMALL(GK_TD3_HEAD);
+    case GS_TD3_AHEAD: return GEN_SMALL(GK_TD3_AHEAD);
+    case GS_TD3_POLGRAD: return GEN_SMALL(GK_TD3_POLGRAD);
+    case GS_LOSS: return &gen::k_g_small_group<gen::GK_LOSS, 0>;
+    case GS_DIAG: return &gen::k_g_small_group<gen::GK_DIAG, 0>;
+    case GS_TD3_LOSS: return &gen::k_g_small_group<gen::GK_TD3_LOSS, 0>;
+    case GS_TD3_QA: return &gen::k_g_small_group<gen::GK_TD3_QA, 0>;
+    }
+#undef GEN_SMALL
+    return nullptr;
+}
+
+// an elementwise stage's x-extent for a member of batch n (gen_run_list's grid)
+static int gen_small_extent(int kind, int n) {
+    switch (kind) {
+    case GS_HEAD: return (2 * n + gen::GRW - 1) / gen::GRW;
+    case GS_LOSS: case GS_TD3_LOSS: case GS_TD3_QA: return n;
+    case GS_DIAG: return 1;
+    default: return (n + gen::GRW - 1) / gen::GRW;
+    }
+}
+
+// MLP groups: members of the general step with one set of hidden sizes
+static int group_create_mlp(sac_group_t **out, sac_trainer_t *const *members, int n_members, int algo) {
+    const char *fname = algo ? "td3_group_create_mlp" : "sac_group_create_mlp";
+    SAC_REQUIRE(out && members, "null argument to %s", fname);
+    *out = nullptr;
+    SAC_REQUIRE(n_members >= 1 && n_members <= SAC_GROUP_MAX, "a trainer group holds 1..%d members (got %d)", SAC_GROUP_MAX,
+                n_members);
+    const sac_trainer *t0 = members[0];
+    for (int i = 0; i < n_members; ++i) {
+        const sac_trainer *t = members[i];
+        SAC_REQUIRE(t != nullptr, "trainer group member %d is null", i);
+        for (int j = 0; j < i; ++j)
+            SAC_REQUIRE(members[j] != t, "trainer group members %d and %d are the same trainer", j, i);
+        if (group_member_ok(t, i, algo, true)) return -1;
+        const sac_general *a = t->gen, *b = t0->gen;
+        bool same = a->Lp == b->Lp && a->Lq == b->Lq;
+        for (int l = 0; same && l < a->Lp; ++l) same = a->hp[l] == b->hp[l];
+        for (int l = 0; same && l < a->Lq; ++l) same = a->hq[l] == b->hq[l];
+        SAC_REQUIRE(same, "trainer group member %d has other hidden sizes than member 0 (an MLP group shares them)", i);
+        SAC_REQUIRE(t->device == t0->device, "trainer group member %d lives on device %d, member 0 on %d", i, t->device, t0->device);
+    }
+    // the members' launch lists (SAC: the step; TD3: the critic pass, then the actor pass, whose statistics-only form is
+    // its head up to the Q1 last layer): one sequence of stage kinds for all of them -- same algorithm, same hidden sizes
+    auto lists_of = [algo](const sac_trainer *t) {
+        std::vector<const std::vector<GenStage> *> L;
+        if (algo == 0) L.push_back(&t->gen->stages);
+        else { L.push_back(&t->gen->td3_critic); L.push_back(&t->gen->td3_actor); }
+        return L;
+    };
+    for (int i = 1; i < n_members; ++i) {
+        const auto L = lists_of(members[i]), L0 = lists_of(t0);
+        for (size_t q = 0; q < L.size(); ++q) {
+            bool same = L[q]->size() == L0[q]->size();
+            for (size_t k = 0; same && k < L[q]->size(); ++k) same = (*L[q])[k].kind == (*L0[q])[k].kind && (*L[q])[k].mode == (*L0[q])[k].mode;
+            SAC_REQUIRE(same, "internal: trainer group member %d has another launch list than member 0", i);
+        }
+    }
+    SAC_HIP(hipSetDevice(t0->device));
+    sac_group *g = new sac_group();
+    g->R = n_members;
+    g->device = t0->device;
+    g->algo = algo;
+    g->mlp = true;
+    for (int i = 0; i < n_members; ++i) g->m[i] = members[i];
+    auto fail = [&](int rc) { group_free(g); return rc; };
+    const int R = n_members;
+    // variant classes: the elementwise kernels' action bound (up to 8 actions, up to 16), each class in member order
+    int pos = 0;
+    for (int ma : {8, 16}) {
+        GroupClass &K = g->cls[g->ncls];
+        K.lo = pos; K.ma = ma;
+        for (int i = 0; i < n_members; ++i)
+            if ((members[i]->A <= 8) == (ma == 8)) g->ord[pos++] = i;
+        K.n = pos - K.lo;
+        if (K.n > 0) g->ncls += 1;
+    }
+    // the grouped stage list and the GEMM stages' headers, [GEMM stage][device member]
+    std::vector<gen::GemmStage> hdr;
+    const auto L0 = lists_of(t0);
+    for (size_t li = 0; li < L0.size(); ++li) {
+        bool past_qa = false;
+        for (size_t k = 0; k < L0[li]->size(); ++k) {
+            const GenStage &s0 = (*L0[li])[k];
+            GroupGenStage st;
+            st.kind = s0.kind; st.mode = s0.mode; st.list = (int)li;
+            // TD3's actor pass: every member with `actor` up to Q1's last layer (whose backward half follows pstep), the
+            // policy's backward pass and update for members on a policy step, the statistics behind them for all of `actor`
+            st.sel = li == 0 ? gen::GSEL_ALL : ((past_qa && s0.kind != GS_DIAG) ? gen::GSEL_PSTEP : gen::GSEL_ACTOR);
+            if (s0.kind == GS_TD3_QA) past_qa = true;
+            if (s0.kind == GS_GEMM) {
+                st.hdr = (int)(hdr.size() / R);
+                int at = 0;
+                for (int q = 0; q <= SAC_GROUP_MAX; ++q) st.map.start[q] = 1 << 30;
+                for (int d = 0; d < R; ++d) {
+                    const sac_trainer *t = members[g->ord[d]];
+                    gen::GemmStage gs = (*lists_of(t)[li])[k].gs;
+                    gs.tau = t->gen->dev.tau;              // (gen_run_list sets it per launch; the rest per step, in the kernel)
+                    hdr.push_back(gs);
+                    st.map.start[d] = at;
+                    at += gs.ntiles * gs.splitk;
+                }
+                st.map.sel = st.sel;
+                st.grid = at;
+            } else {
+                st.per_class = s0.kind == GS_HEAD || s0.kind == GS_POLGRAD || s0.kind == GS_TD3_HEAD || s0.kind == GS_TD3_AHEAD ||
+                               s0.kind == GS_TD3_POLGRAD;
+                for (int c = 0; c < (st.per_class ? g->ncls : 1); ++c) {
+                    const int lo = st.per_class ? g->cls[c].lo : 0, hi = st.per_class ? lo + g->cls[c].n : R;
+                    st.fn[c] = gen_small_fn(s0.kind, st.per_class ? g->cls[c].ma : 0);
+                    for (int d = lo; d < hi; ++d) st.gx[c] = std::max(st.gx[c], gen_small_extent(s0.kind, members[g->ord[d]]->Bt));
+                }
+            }
+            g->gst.push_back(st);
+        }
+    }
+    if (hipMalloc(reinterpret_cast<void **>(&g->d_hdr), sizeof(gen::GemmStage) * hdr.size()) != hipSuccess ||
+        hipMemcpy(g->d_hdr, hdr.data(), sizeof(gen::GemmStage) * hdr.size(), hipMemcpyHostToDevice) != hipSuccess) {
+        sac::set_error("out of device memory for a trainer group");
         return fail(-1);
     }
-    for (int k = 0; k < 2; ++k)
-        if (hipEventCreateWithFlags(&g->ev_ready[k], hipEventDisableTiming) != hipSuccess ||
-            hipEventCreateWithFlags(&g->ev_done[k], hipEventDisableTiming) != hipSuccess ||
-            hipEventCreateWithFlags(&g->ev_copied[k], hipEventDisableTiming) != hipSuccess) {
-            sac::set_error("hipEventCreate failed");
-            return fail(-1);
-        }
-    for (auto &e : g->ev_in)
-        if (hipEventCreateWithFlags(&e, hipEventDisableTiming) != hipSuccess) { sac::set_error("hipEventCreate failed"); return fail(-1); }
-    if (hipEventCreateWithFlags(&g->ev_end, hipEventDisableTiming) != hipSuccess) { sac::set_error("hipEventCreate failed"); return fail(-1); }
-    g->d_mem = reinterpret_cast<GroupMember *>(g->d_tab); g->h_mem = reinterpret_cast<GroupMember *>(g->h_tab);
-    g->d_smp = reinterpret_cast<SampleMember *>(g->d_tab + o_smp); g->h_smp = reinterpret_cast<SampleMember *>(g->h_tab + o_smp);
-    g->d_gat = reinterpret_cast<GatherMember *>(g->d_tab + o_gat); g->h_gat = reinterpret_cast<GatherMember *>(g->h_tab + o_gat);
-    if (algo == 0) { g->d_sa = reinterpret_cast<StepArg *>(g->d_tab + o_sa); g->h_sa = reinterpret_cast<StepArg *>(g->h_tab + o_sa); }
-    else { g->d_ts = reinterpret_cast<Td3GroupStep *>(g->d_tab + o_sa); g->h_ts = reinterpret_cast<Td3GroupStep *>(g->h_tab + o_sa); }
-    {   // a tenant of the device's fused-launch gate: no fused trainer's launch may overlap the group's grids
-        FusedGate &G = g_gate[g->device & 63];
-        std::lock_guard<std::mutex> lk(G.mu);
-        if (!G.ev && hipEventCreateWithFlags(&G.ev, hipEventDisableTiming) != hipSuccess) {
-            sac::set_error("hipEventCreate failed");
-            return fail(-1);
-        }
-        G.live += 1;
-    }
+    if (group_tables(g, sizeof(gen::GenMember) * R, sizeof(gen::GenGroupStep) * 2 * LOOP_CH * R)) return fail(-1);
     *out = g;
     return 0;
 }
@@ -3654,6 +3826,14 @@ int sac_group_create_mixed(sac_group_t **out, sac_trainer_t *const *members, int
 
 int td3_group_create_mixed(sac_group_t **out, sac_trainer_t *const *members, int n_members) {
     return group_create(out, members, n_members, 1, true);
+}
+
+int sac_group_create_mlp(sac_group_t **out, sac_trainer_t *const *members, int n_members) {
+    return group_create_mlp(out, members, n_members, 0);
+}
+
+int td3_group_create_mlp(sac_group_t **out, sac_trainer_t *const *members, int n_members) {
+    return group_create_mlp(out, members, n_members, 1);
 }
 
 int sac_group_destroy(sac_group_t *g) {
@@ -3676,12 +3856,12 @@ int sac_group_train_loop(sac_group_t *g, sac_buffer_t *const *bufs, int64_t n_st
     const sac_trainer *t0 = g->m[0];
     // every refusal comes before anything changes
     for (int r = 0; r < R; ++r) {
-        if (group_member_ok(g->m[r], r, g->algo)) return -1;
+        if (group_member_ok(g->m[r], r, g->algo, g->mlp)) return -1;
         const sac_buffer *b = bufs[r];
         SAC_REQUIRE(b != nullptr, "trainer group buffer %d is null", r);
         for (int q = 0; q < r; ++q) SAC_REQUIRE(bufs[q] != b, "trainer group buffers %d and %d are the same buffer", q, r);
         SAC_REQUIRE(b->device == g->device, "trainer group buffer %d lives on device %d, the group on %d", r, b->device, g->device);
-        if (g->mixed) {
+        if (g->mixed || g->mlp) {
             const sac_trainer *t = g->m[r];
             SAC_REQUIRE(b->O == t->O && b->A == t->A, "trainer group buffer %d has dims (%d,%d), its member (%d,%d)", r, b->O,
                         b->A, t->O, t->A);
@@ -3735,7 +3915,19 @@ int sac_group_train_loop(sac_group_t *g, sac_buffer_t *const *bufs, int64_t n_st
         }
     }
     // the member tables of this call, in device order (the StepArg table follows chunk by chunk)
-    for (int k = 0; k < R; ++k) {
+    for (int k = 0; k < R && g->mlp; ++k) {
+        const int r = g->ord[k];
+        const sac_trainer *t = g->m[r];
+        sac_buffer *b = bufs[r];
+        SAC_REQUIRE(b->slot.off_obs == t->ext_layout.off_obs && b->slot.off_nobs == t->ext_layout.off_nobs && b->slot.Bt == t->gen->n,
+                    "internal: minibatch slot layout differs from the one the general step was built for");
+        gen::GenMember &M = g->h_gm[k];
+        M.d = t->gen->dev;
+        M.d.eps1 = M.d.eps2 = nullptr;                // (loop steps draw their noise on the device)
+        M.SL = b->slot;
+        M.slots = b->d_slots;
+    }
+    for (int k = 0; k < R && !g->mlp; ++k) {
         const int r = g->ord[k];
         const sac_trainer *t = g->m[r];
         sac_buffer *b = bufs[r];
@@ -3787,7 +3979,8 @@ int sac_group_train_loop(sac_group_t *g, sac_buffer_t *const *bufs, int64_t n_st
             g->h_gat[h * R + p] = GatherMember{b->view(), b->d_idx + (int64_t)h * LOOP_CH * t->B,
                                                b->d_slots + (size_t)h * LOOP_CH * b->slot.slot_floats, b->slot, t->B};
     }
-    SAC_HIP(hipMemcpyAsync(g->d_mem, g->h_mem, sizeof(GroupMember) * R, hipMemcpyHostToDevice, s2));
+    if (g->mlp) SAC_HIP(hipMemcpyAsync(g->d_gm, g->h_gm, sizeof(gen::GenMember) * R, hipMemcpyHostToDevice, s2));
+    else SAC_HIP(hipMemcpyAsync(g->d_mem, g->h_mem, sizeof(GroupMember) * R, hipMemcpyHostToDevice, s2));
     SAC_HIP(hipMemcpyAsync(g->d_smp, g->h_smp, sizeof(SampleMember) * 2 * R, hipMemcpyHostToDevice, s2));
     SAC_HIP(hipMemcpyAsync(g->d_gat, g->h_gat, sizeof(GatherMember) * 2 * R, hipMemcpyHostToDevice, s2));
     const int compact = 1;                            // (3 * 4 * NB <= 192 for every member: checked at creation)
@@ -3820,7 +4013,36 @@ int sac_group_train_loop(sac_group_t *g, sac_buffer_t *const *bufs, int64_t n_st
         if (c >= 2 && wait_event(g->ev_copied[h])) return -1;
         const void *dsrc = nullptr, *hsrc = nullptr;
         size_t bytes = 0;
-        if (g->algo == 0) {
+        if (g->mlp) {
+            // gen_launch_step's arguments per member and step (TD3: launch_step_td3's plan, as for the other TD3 groups)
+            gen::GenGroupStep *hs = g->h_gs + (size_t)h * LOOP_CH * R;
+            for (int64_t j = 0; j < m; ++j) {
+                plan[j] = 0;
+                for (int k = 0; k < R; ++k) {
+                    const int r = g->ord[k];
+                    const sac_trainer *t = g->m[r];
+                    const long long i = (long long)(done + j), step = t->n_train_steps_total + i;
+                    const double tq = (double)(t->adam_t + i + 1), tp = (double)(t->adam_t_pi + pi_steps[r] + 1);
+                    gen::GenGroupStep &gs = hs[j * R + k];
+                    memset(&gs, 0, sizeof(gs));
+                    gs.sa = StepArg{step, t->adam_t + i + 1, (int)i, g->algo, 1.0 - std::pow(0.9, tq), std::sqrt(1.0 - std::pow(0.999, tq))};
+                    gs.sa.pad2 = (done + j == n_steps - 1) ? 2u : 0u;
+                    if (g->algo == 0) {
+                        gs.polyak = (step % t->gen->dev.period) == 0 ? 1 : 0;
+                    } else {
+                        const bool pstep = (step % t->td3_period) == 0, actor = pstep || i == 0;
+                        gs.sp = StepArg{step, t->adam_t_pi + pi_steps[r] + 1, (int)i, 2, 1.0 - std::pow(0.9, tp),
+                                        std::sqrt(1.0 - std::pow(0.999, tp))};
+                        gs.sp.pad2 = gs.sa.pad2;
+                        gs.actor = actor ? 1 : 0;
+                        gs.pstep = gs.polyak = pstep ? 1 : 0;
+                        plan[j] |= (actor ? 1 : 0) | (pstep ? 2 : 0);
+                        pi_steps[r] += pstep ? 1 : 0;
+                    }
+                }
+            }
+            hsrc = hs; dsrc = g->d_gs + (size_t)h * LOOP_CH * R; bytes = sizeof(gen::GenGroupStep) * m * R;
+        } else if (g->algo == 0) {
             StepArg *hs = g->h_sa + (size_t)h * LOOP_CH * R;
             for (int64_t j = 0; j < m; ++j)
                 for (int k = 0; k < R; ++k) {
@@ -3870,7 +4092,29 @@ int sac_group_train_loop(sac_group_t *g, sac_buffer_t *const *bufs, int64_t n_st
             // one weight-gradient launch over all members
             for (int64_t j = 0; j < m; ++j) {
                 const int slot = (int)(h * LOOP_CH + j);
-                if (g->algo == 0) {
+                if (g->mlp) {
+                    const gen::GenGroupStep *gs = g->d_gs + (size_t)h * LOOP_CH * R + j * R;
+                    const long long i = (long long)(done + j);
+                    for (const GroupGenStage &st : g->gst) {
+                        if (st.list == 1 && !(plan[j] & 1)) continue;               // TD3: no member runs the actor pass
+                        if (st.sel == gen::GSEL_PSTEP && !(plan[j] & 2)) continue;  // no member is on a policy step
+                        // (SAC: the diagnostics on the steps somebody reads them -- the call's first and last)
+                        if (st.kind == GS_DIAG && g->algo == 0 && i != 0 && i != n_steps - 1) continue;
+                        if (st.kind == GS_GEMM) {
+                            const gen::GemmStage *H = g->d_hdr + (size_t)st.hdr * R;
+                            if (st.mode == 0) hipLaunchKernelGGL((gen::k_g_gemm_group<true, true>), dim3(st.grid), dim3(64 * gen::GW), 0, s, H, g->d_gm, gs, slot, st.map);
+                            else if (st.mode == 1) hipLaunchKernelGGL((gen::k_g_gemm_group<true, false>), dim3(st.grid), dim3(64 * gen::GW), 0, s, H, g->d_gm, gs, slot, st.map);
+                            else hipLaunchKernelGGL((gen::k_g_gemm_group<false, false>), dim3(st.grid), dim3(64 * gen::GW), 0, s, H, g->d_gm, gs, slot, st.map);
+                        } else if (st.per_class) {
+                            for (int q = 0; q < g->ncls; ++q) {
+                                const GroupClass &K = g->cls[q];
+                                hipLaunchKernelGGL(st.fn[q], dim3(st.gx[q], K.n), dim3(256), 0, s, g->d_gm + K.lo, gs + K.lo, slot, st.sel);
+                            }
+                        } else {
+                            hipLaunchKernelGGL(st.fn[0], dim3(st.gx[0], R), dim3(256), 0, s, g->d_gm, gs, slot, st.sel);
+                        }
+                    }
+                } else if (g->algo == 0) {
                     const StepArg *sa = g->d_sa + (size_t)h * LOOP_CH * R + j * R;
                     for (int q = 0; q < g->ncls; ++q) {
                         const GroupClass &K = g->cls[q];

@@ -22,7 +22,8 @@ from .group_checkpoint import checkpoint_exists as _checkpoint_exists
 from .networks import (FlattenMlp, GaussianStrategy, MakeDeterministic, PolicyWrappedWithExplorationStrategy,
                        TanhGaussianPolicy, TanhMlpPolicy)
 from .replay_buffer import EnvReplayBuffer
-from .group import MixedSACTrainerGroup, MixedTD3TrainerGroup, SACTrainerGroup, TD3TrainerGroup
+from .group import (MixedSACTrainerGroup, MixedTD3TrainerGroup, MlpSACTrainerGroup, MlpTD3TrainerGroup, SACTrainerGroup,
+                    TD3TrainerGroup, runs_general_step)
 from .sac import SACTrainer
 from .td3 import TD3Trainer
 from .variant import env_dims, validate
@@ -383,8 +384,9 @@ def experiment_group(variant, seeds, log_dir=None, num_epochs=None, obs_dim=None
                      quiet=False, checkpoint_dir=None, resume=False, chunk_rows=DEFAULT_CHUNK_ROWS):
     """One configuration, several seeds, one process: each seed is the run ``experiment(variant, seed=s)`` would make --
     its own synthetic environments, collectors, weights and replay buffer -- and every epoch's training block is ONE
-    SACTrainerGroup.train_loop (TD3 variants: TD3TrainerGroup) over all seeds (grouped launches; each run's result is
-    bit for bit its solo one).
+    SACTrainerGroup.train_loop (TD3 variants: TD3TrainerGroup; hidden sizes other than two layers of at most 256 units:
+    MlpSACTrainerGroup / MlpTD3TrainerGroup) over all seeds (grouped launches; each run's result is bit for bit its solo
+    one).
     Weights come from a private RandomState(s) in the order experiment() draws them from np.random, and the buffer
     samples a private stream continued from that generator (np.random is neither read nor written).  Returns
     {seed: progress rows}; with log_dir, each seed's rows also go to <log_dir>/s<seed>/progress.csv.
@@ -408,9 +410,15 @@ def experiment_group(variant, seeds, log_dir=None, num_epochs=None, obs_dim=None
         runs.append(_group_run(variant, seed, O, A, device, prefill=not restoring))
         runs[-1]["sub"] = f"s{seed}"
     ck, first_epoch = _group_checkpoint(runs, checkpoint_dir, restoring, chunk_rows)
-    group = (TD3TrainerGroup if td3 else SACTrainerGroup)([r["trainer"] for r in runs])
     n_train = ak["num_trains_per_train_loop"]
-    _group_epochs(runs, lambda: group.train_loop([r["buf"] for r in runs], n_train, batch_size=ak["batch_size"]),
+    if runs_general_step(runs[0]["trainer"]):                 # (hidden sizes of the general step: an MLP group)
+        group = (MlpTD3TrainerGroup if td3 else MlpSACTrainerGroup)([r["trainer"] for r in runs])
+        batches = [ak["batch_size"]] * len(runs)
+        train_block = lambda: group.train_loop([r["buf"] for r in runs], n_train, batch_sizes=batches)  # noqa: E731
+    else:
+        group = (TD3TrainerGroup if td3 else SACTrainerGroup)([r["trainer"] for r in runs])
+        train_block = lambda: group.train_loop([r["buf"] for r in runs], n_train, batch_size=ak["batch_size"])  # noqa: E731
+    _group_epochs(runs, train_block,
                   num_epochs if num_epochs is not None else ak["num_epochs"], n_train, log_dir, quiet, "seeds", ck,
                   first_epoch)
     return {r["seed"]: r["rows"] for r in runs}
@@ -428,8 +436,9 @@ def experiment_sweep(runs, log_dir=None, num_epochs=None, device=0, quiet=False,
                      chunk_rows=DEFAULT_CHUNK_ROWS):
     """Several tasks x seeds, one process, one device: every entry of ``runs`` -- (variant, seed), or (variant, seed,
     obs_dim, action_dim) for a task without pinned dims -- is the run ``experiment(variant, seed=seed)`` would make, and
-    every epoch's training block is ONE MixedSACTrainerGroup.train_loop (TD3 variants: MixedTD3TrainerGroup) over all
-    runs, each on its own batch size (bit for bit its solo result).
+    every epoch's training block is ONE MixedSACTrainerGroup.train_loop (TD3 variants: MixedTD3TrainerGroup; hidden sizes
+    of the general step: MlpSACTrainerGroup / MlpTD3TrainerGroup) over all runs, each on its own batch size (bit for bit
+    its solo result).
     The runs must share the algorithm, the hidden sizes and the epoch plan (num_trains_per_train_loop, and num_epochs
     unless it is given here); dims and batch sizes may differ.  Returns the runs' progress rows, a list in the order of
     ``runs``; with log_dir, each run's rows also go to <log_dir>/<task>-s<seed>/progress.csv.  checkpoint_dir, resume
@@ -474,7 +483,10 @@ def experiment_sweep(runs, log_dir=None, num_epochs=None, device=0, quiet=False,
         group_runs[-1]["sub"] = f"{task_label(v)}-s{seed}"
     ck, first_epoch = _group_checkpoint(group_runs, checkpoint_dir, restoring, chunk_rows)
     td3 = algo0 == "TD3"
-    group = (MixedTD3TrainerGroup if td3 else MixedSACTrainerGroup)([r["trainer"] for r in group_runs])
+    if runs_general_step(group_runs[0]["trainer"]):           # (hidden sizes of the general step: an MLP group)
+        group = (MlpTD3TrainerGroup if td3 else MlpSACTrainerGroup)([r["trainer"] for r in group_runs])
+    else:
+        group = (MixedTD3TrainerGroup if td3 else MixedSACTrainerGroup)([r["trainer"] for r in group_runs])
     n_train = ak0["num_trains_per_train_loop"]
     batches = [r["ak"]["batch_size"] for r in group_runs]
     _group_epochs(group_runs, lambda: group.train_loop([r["buf"] for r in group_runs], n_train, batch_sizes=batches),

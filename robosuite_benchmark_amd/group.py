@@ -1,6 +1,7 @@
 """SACTrainerGroup / TD3TrainerGroup: several SAC or TD3 runs of one configuration trained together (sac_group_*,
 td3_group_create of include/sac_hip.h); MixedSACTrainerGroup / MixedTD3TrainerGroup: runs of different tasks
-(sac_group_create_mixed, td3_group_create_mixed).
+(sac_group_create_mixed, td3_group_create_mixed); MlpSACTrainerGroup / MlpTD3TrainerGroup: runs of the general step --
+hidden sizes other than two layers of at most 256 units (sac_group_create_mlp, td3_group_create_mlp).
 
 The reference's real workload is many independent runs -- seeds x configurations, one job each
 (/root/reference/launch_jobs.sh).  One run at batch 256 cannot fill an MI355X; a group steps R runs of the same shape
@@ -19,6 +20,12 @@ from .td3 import TD3Trainer
 MAX_MEMBERS = 16
 
 
+def runs_general_step(t):
+    """Does trainer t run the general step (hidden sizes other than two layers of at most 256 units)?  Such runs group in
+    MlpSACTrainerGroup / MlpTD3TrainerGroup, the others in the remaining kinds."""
+    return any(len(hs) != 2 or max(hs) > 256 for hs in (t._hidden("policy"), t._hidden("qf1")))
+
+
 class _GroupBase:
     """What every kind of trainer group shares: the member checks that hold for all of them, the C group over the
     members' handles, and the call of sac_group_train_loop."""
@@ -33,6 +40,9 @@ class _GroupBase:
         """Refuse member i (i >= 1) against member 0 from host metadata."""
         raise NotImplementedError
 
+    def _check_step(self, i, t):
+        """Refuse member i for the step its hidden sizes select (the fused kernels' groups check it at train_loop)."""
+
     def __init__(self, trainers):
         trainers = list(trainers)
         if not 1 <= len(trainers) <= MAX_MEMBERS:
@@ -41,6 +51,7 @@ class _GroupBase:
         for i, t in enumerate(trainers):
             if not self._member_ok(t):
                 raise RuntimeError(f"trainer group member {i} is a {type(t).__name__}: {self._ONLY}")
+            self._check_step(i, t)
         if len({id(t) for t in trainers}) != len(trainers):
             raise RuntimeError("a trainer appears twice in the group")
         t0 = trainers[0]
@@ -159,6 +170,7 @@ class _TrainerGroup(_GroupBase):
 class _MixedTrainerGroup(_GroupBase):
     """Members of different tasks: obs_dim, act_dim and batch may differ per member (hidden sizes, algorithm and device
     may not).  Each member trains on its own buffer with its own batch size, bit for bit as its solo train_loop."""
+    _MAX_BATCH = 256            # (the fused kernels' grouped instances; the general step has no such bound)
 
     def _check_member(self, i, t, t0):
         self._check_hidden(i, t, t0)
@@ -183,7 +195,7 @@ class _MixedTrainerGroup(_GroupBase):
             if B <= 0:
                 raise RuntimeError(f"trainer group member {r} has no batch size: pass batch_sizes or create the trainers "
                                    "with one")
-            if B > 256:
+            if self._MAX_BATCH and B > self._MAX_BATCH:
                 raise RuntimeError(f"trainer group member {r} has batch {B}: trainer groups take batches of at most 256 rows")
             batches.append(B)
         self._check_general()
@@ -224,5 +236,36 @@ class MixedSACTrainerGroup(_MixedTrainerGroup):
 class MixedTD3TrainerGroup(_MixedTrainerGroup):
     """R TD3 runs of different tasks; each keeps its own delayed-update phase as in TD3TrainerGroup."""
     _CREATE = "td3_group_create_mixed"
+    _ONLY = "TD3 groups hold TD3 trainers only"
+    _member_ok = staticmethod(TD3TrainerGroup._member_ok)
+
+
+class _MlpTrainerGroup(_MixedTrainerGroup):
+    """Members of the general step (a network-width or network-depth sweep): the hidden sizes, algorithm and device are
+    shared; obs_dim, act_dim and batch may differ per member, as in mixed groups.  Members with the shapes of the fused
+    kernels are refused: their solo step is not the general step."""
+    _MAX_BATCH = None
+
+    def _check_step(self, i, t):
+        if not runs_general_step(t):
+            raise RuntimeError(f"trainer group member {i} has the shapes of the fused kernels (policy hidden sizes "
+                               f"{t._hidden('policy')}, qf hidden sizes {t._hidden('qf1')}): MLP groups take general-step "
+                               "members only")
+
+    def _check_general(self):
+        pass                    # (checked at construction, by _check_step)
+
+
+class MlpSACTrainerGroup(_MlpTrainerGroup):
+    """R SAC runs of the general step with one set of hidden sizes (e.g. the seeds of a [512, 512] variant, or several
+    tasks at [256, 256, 256]); each stage of the step is one grouped launch over all members."""
+    _CREATE = "sac_group_create_mlp"
+    _ONLY = "groups hold SAC trainers only"
+    _member_ok = staticmethod(SACTrainerGroup._member_ok)
+
+
+class MlpTD3TrainerGroup(_MlpTrainerGroup):
+    """R TD3 runs of the general step; each keeps its own delayed-update phase as in TD3TrainerGroup."""
+    _CREATE = "td3_group_create_mlp"
     _ONLY = "TD3 groups hold TD3 trainers only"
     _member_ok = staticmethod(TD3TrainerGroup._member_ok)

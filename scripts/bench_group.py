@@ -9,7 +9,14 @@
 (MixedSACTrainerGroup) against the same runs trained one after another with solo train_loop.  One JSON line per
 (batch, seeds per task): both aggregate rates, every task's solo rate and the step launches per step.
 
-    python scripts/bench_group.py --tasks sweep [--batches 256 128] [--seeds-per-task 1 2] [--buffer 1000000]"""
+    python scripts/bench_group.py --tasks sweep [--batches 256 128] [--seeds-per-task 1 2] [--buffer 1000000]
+
+--hidden H1 H2 ...: every run's policy and Q nets get these hidden sizes; other than two layers of at most 256 units
+they run the general step, and the runs form ONE MLP group (MlpSACTrainerGroup / MlpTD3TrainerGroup), measured against
+the same runs trained one after another with solo train_loop (the two alternate per (batch, R)).  One JSON line per
+(batch, R) with both aggregate rates.
+
+    python scripts/bench_group.py --hidden 512 512 [--agent SAC|TD3] [--batches 256 128] [--replicas 1 2 4 8 16]"""
 from __future__ import annotations
 
 import argparse
@@ -22,25 +29,27 @@ import numpy as np
 
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 
-from robosuite_benchmark_amd import (EnvReplayBuffer, FlattenMlp, MixedSACTrainerGroup, SACTrainer,  # noqa: E402
-                                     SACTrainerGroup, TanhGaussianPolicy, TanhMlpPolicy, TD3Trainer, TD3TrainerGroup, _lib)
+from robosuite_benchmark_amd import (EnvReplayBuffer, FlattenMlp, MixedSACTrainerGroup, MlpSACTrainerGroup,  # noqa: E402
+                                     MlpTD3TrainerGroup, SACTrainer, SACTrainerGroup, TanhGaussianPolicy, TanhMlpPolicy,
+                                     TD3Trainer, TD3TrainerGroup, _lib)
+from robosuite_benchmark_amd.group import runs_general_step  # noqa: E402
 from robosuite_benchmark_amd.parallel import SWEEP  # noqa: E402
 
 
-def make_trainer(O, A, B, seed):
+def make_trainer(O, A, B, seed, hidden=(256, 256)):
     rs = np.random.RandomState(seed)
-    qs = [FlattenMlp([256, 256], 1, O + A, rs=rs) for _ in range(4)]
-    pol = TanhGaussianPolicy([256, 256], O, A, rs=rs, noise=np.random.RandomState(seed))
+    qs = [FlattenMlp(list(hidden), 1, O + A, rs=rs) for _ in range(4)]
+    pol = TanhGaussianPolicy(list(hidden), O, A, rs=rs, noise=np.random.RandomState(seed))
     return SACTrainer(policy=pol, qf1=qs[0], qf2=qs[1], target_qf1=qs[2], target_qf2=qs[3], discount=0.99,
                       reward_scale=1.0, policy_lr=3e-4, qf_lr=3e-4, soft_target_tau=0.005, target_update_period=1,
                       use_automatic_entropy_tuning=True, batch_size=B, noise_seed=seed)
 
 
-def make_td3_trainer(O, A, B, seed):
+def make_td3_trainer(O, A, B, seed, hidden=(256, 256)):
     """TD3 with the default variant's trainer_kwargs (bench.py --agent TD3's: policy_and_target_update_period 2)."""
     rs = np.random.RandomState(seed)
-    qs = [FlattenMlp([256, 256], 1, O + A, rs=rs) for _ in range(4)]
-    pols = [TanhMlpPolicy([256, 256], A, O, rs=rs) for _ in range(2)]
+    qs = [FlattenMlp(list(hidden), 1, O + A, rs=rs) for _ in range(4)]
+    pols = [TanhMlpPolicy(list(hidden), A, O, rs=rs) for _ in range(2)]
     return TD3Trainer(policy=pols[0], qf1=qs[0], qf2=qs[1], target_qf1=qs[2], target_qf2=qs[3], target_policy=pols[1],
                       target_policy_noise=0.2, discount=0.99, reward_scale=1.0, policy_learning_rate=1e-3,
                       qf_learning_rate=5e-4, policy_and_target_update_period=2, tau=0.005, batch_size=B, noise_seed=seed)
@@ -93,6 +102,46 @@ def bench_sweep(args):
         del bufs
 
 
+def bench_hidden(args, bufs):
+    """--hidden: R runs of these hidden sizes as one group (an MLP group for the general step) against the same runs
+    trained one after another with solo train_loop."""
+    O, A, hidden = args.obs, args.act, tuple(args.hidden)
+    td3 = args.agent == "TD3"
+    make = make_td3_trainer if td3 else make_trainer
+    for B in args.batches:
+        for R in args.replicas:
+            trainers = [make(O, A, B, 10 + r, hidden) for r in range(R)]
+            general = runs_general_step(trainers[0])
+            if general:
+                group = (MlpTD3TrainerGroup if td3 else MlpSACTrainerGroup)(trainers)
+                run = lambda n: group.train_loop(bufs[:R], n, batch_sizes=[B] * R)  # noqa: E731
+            else:
+                group = (TD3TrainerGroup if td3 else SACTrainerGroup)(trainers)
+                run = lambda n: group.train_loop(bufs[:R], n, batch_size=B)  # noqa: E731
+            run(args.warmup)
+            t0 = time.perf_counter()
+            _, last = run(args.steps)
+            dt_group = time.perf_counter() - t0
+            dt_seq, solo = 0.0, []
+            for t, b in zip(trainers, bufs[:R]):
+                t.train_loop(b, args.warmup, batch_size=B)
+                t0 = time.perf_counter()
+                t.train_loop(b, args.steps, batch_size=B)
+                dt = time.perf_counter() - t0
+                dt_seq += dt
+                solo.append(round(args.steps / dt, 1))
+            print(json.dumps(dict(metric="mlp_group_grad_steps_per_s" if general else "group_grad_steps_per_s",
+                                  agent=args.agent, hidden=list(hidden), batch=B, replicas=R, obs_dim=O, act_dim=A,
+                                  buffer=args.buffer, steps=args.steps,
+                                  group_seconds=round(dt_group, 4),
+                                  group_aggregate_steps_per_s=round(R * args.steps / dt_group, 1),
+                                  sequential_seconds=round(dt_seq, 4),
+                                  sequential_aggregate_steps_per_s=round(R * args.steps / dt_seq, 1),
+                                  gain=round(dt_seq / dt_group, 3), solo_steps_per_s=solo,
+                                  finite=bool(np.all(np.isfinite(last))))), flush=True)
+            del group, trainers
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--tasks", type=str, default="lift", choices=["lift", "sweep"])
@@ -105,6 +154,7 @@ def main():
     ap.add_argument("--replicas", type=int, nargs="+", default=[1, 2, 4, 8, 16])
     ap.add_argument("--obs", type=int, default=42)
     ap.add_argument("--act", type=int, default=7)
+    ap.add_argument("--hidden", type=int, nargs="+", default=None)
     args = ap.parse_args()
     if _lib.device_count() == 0:
         raise SystemExit("bench_group.py needs a GPU")
@@ -121,6 +171,8 @@ def main():
         b.add_block(rows[0], rows[1], rows[2], rows[3], rows[4])
         b.seed(100 + r)
         bufs.append(b)
+    if args.hidden:
+        return bench_hidden(args, bufs)
     for B in args.batches:
         for R in args.replicas:
             make, Group = (make_td3_trainer, TD3TrainerGroup) if args.agent == "TD3" else (make_trainer, SACTrainerGroup)
