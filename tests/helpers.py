@@ -244,3 +244,240 @@ def check_step_f64(hip, o32, o64, diag, want32, want64, path=None, skip_rows=())
     check_grads_f64(hip, o32, o64, path, nets=("qf1", "qf2") + (("policy",) if not td3 or o32.last["policy_step"] else ()))
     check_rows_f64(hip, o32, o64, path, skip=skip_rows)
     check_diag_f64(diag, TD3_DIAG_NAMES if td3 else DIAG_NAMES, want32, want64, o64, path)
+
+
+# ---- what a step writes back: Adam, Polyak and the entropy coefficient against a float64 restatement -------------------
+def _adam_f32(p, m, v, g, lr, t):
+    """torch.optim.Adam (fp32 tensors, double bias corrections) restated in NumPy float32."""
+    f = np.float32
+    m = m + f(1.0 - 0.9) * (g - m)                                  # exp_avg.lerp_(grad, 1 - beta1)
+    v = v * f(0.999) + f(1.0 - 0.999) * g * g                       # mul_(beta2).addcmul_(grad, grad, 1 - beta2)
+    bc1, bc2s = 1.0 - 0.9 ** t, np.sqrt(1.0 - 0.999 ** t)
+    denom = np.sqrt(v) / f(bc2s) + f(1e-8)
+    p = p + (f(-(lr / bc1)) * m) / denom                            # addcdiv_(exp_avg, denom, value=-step_size)
+    return p.astype(f), m.astype(f), v.astype(f)
+
+
+U32 = 2.0 ** -24                     # unit roundoff of float32: |fl(x) - x| <= U32 |x| (normal range)
+ADAM_BETAS, ADAM_EPS = (0.9, 0.999), 1e-8
+
+
+def _f(x):
+    """A double scalar as torch applies it to float32 tensors: rounded to float32 once."""
+    return float(np.float32(x))
+
+
+def adam_scalars(lr, t):
+    """The float32 scalars of torch Adam at optimizer step t (1-based): 1 - beta1, beta2, 1 - beta2, lr / bc1, sqrt(bc2),
+    eps.  torch forms bias corrections and step size in double and each reaches the tensor ops as one float32."""
+    b1, b2 = ADAM_BETAS
+    bc1, bc2s = 1.0 - b1 ** t, (1.0 - b2 ** t) ** 0.5
+    return _f(1.0 - b1), _f(b2), _f(1.0 - b2), _f(lr / bc1), _f(bc2s), _f(ADAM_EPS)
+
+
+def adam_moments_ref(m0, v0, g, t):
+    """exp_avg.lerp_(g, 1 - beta1) and exp_avg_sq.mul_(beta2).addcmul_(g, g, 1 - beta2) in float64."""
+    c1, b2, c2 = adam_scalars(0.0, t)[:3]
+    m0, v0, g = (np.asarray(x, np.float64) for x in (m0, v0, g))
+    return m0 + c1 * (g - m0), v0 * b2 + c2 * g * g
+
+
+def adam_param_ref(p0, m, v, lr, t):
+    """param.addcdiv_(m, sqrt(v) / sqrt(bc2) + eps, value=-lr / bc1) in float64, from the moments AFTER the step.
+    Returns the new parameter and the update it added."""
+    _, _, _, ss, bc2s, eps = adam_scalars(lr, t)
+    m, v = np.asarray(m, np.float64), np.asarray(v, np.float64)
+    d = (-ss * m) / (np.sqrt(v) / bc2s + eps)
+    return np.asarray(p0, np.float64) + d, d
+
+
+def adam_ref(p0, m0, v0, g, lr, t):
+    """One step of torch.optim.Adam (betas 0.9 / 0.999, eps 1e-8, no weight decay) at optimizer step t, in float64 from
+    float32 inputs with torch's float32 scalars: (p, m, v)."""
+    m, v = adam_moments_ref(m0, v0, g, t)
+    return adam_param_ref(p0, m, v, lr, t)[0], m, v
+
+
+def polyak_ref(t_old, p_new, tau):
+    """rlkit soft_update_from_to: target * (1 - tau) + param * tau, float64 with the two float32 scalars."""
+    return np.asarray(t_old, np.float64) * _f(1.0 - tau) + np.asarray(p_new, np.float64) * _f(tau)
+
+
+def alpha_grad_ref(log_pi, target_entropy):
+    """d/d log_alpha of -(log_alpha * (log_pi + H)).mean() = -mean(log_pi + H), float64 over the B rows."""
+    return -float(np.mean(np.asarray(log_pi, np.float64) + float(np.float32(target_entropy))))
+
+
+def alpha_ref(log_alpha, a_m, a_v, log_pi, target_entropy, lr, t):
+    """One Adam step of log_alpha (torch Adam on a 0-dim float32 tensor) on the gradient of mean(log_pi + H):
+    (log_alpha, exp_avg, exp_avg_sq, gradient)."""
+    gr = alpha_grad_ref(log_pi, target_entropy)
+    p, m, v = adam_ref(log_alpha, a_m, a_v, gr, lr, t)
+    return float(p), float(m), float(v), gr
+
+
+def ulp32(x):
+    """The float32 ulp at |x| (the spacing above the float32 nearest to |x|; 2^-149 at 0)."""
+    return np.spacing(np.abs(np.asarray(x, np.float64)).astype(np.float32)).astype(np.float64)
+
+
+def ulp_distance(got, ref):
+    return np.abs(np.asarray(got, np.float64) - np.asarray(ref, np.float64)) / ulp32(ref)
+
+
+OPT_ULPS = {}               # path -> {quantity: largest |K - R| / ulp(R) seen, "<quantity> of bound": largest |K - R| / bound}
+
+
+def _within(what, got, ref, bound, path, quantity):
+    """Assert |K - R| <= bound per element; record the largest ulp distance of (path, quantity)."""
+    K, R = np.asarray(got, np.float64), np.asarray(ref, np.float64)
+    assert K.shape == R.shape, (what, K.shape, R.shape)
+    bound = np.broadcast_to(np.asarray(bound, np.float64), R.shape).ravel()
+    K, R = K.ravel(), R.ravel()
+    ul = ulp_distance(K, R)
+    if ul.size:
+        rec = OPT_ULPS.setdefault(path, {})
+        rec[quantity] = max(rec.get(quantity, 0.0), float(np.max(ul)))
+        use = np.abs(K - R) / np.maximum(bound, 1e-300)
+        rec[quantity + " of bound"] = max(rec.get(quantity + " of bound", 0.0), float(np.max(use)))
+    bad = ~(np.abs(K - R) <= bound)                     # (NaN counts as bad)
+    if np.any(bad):
+        i = int(np.argmax(np.where(bad, ul, -1.0)))
+        raise AssertionError(f"{path}: {what}: {int(bad.sum())} of {R.size} elements beyond the bound; worst at [{i}]: "
+                             f"kernel {K[i]:.9g}, reference {R[i]:.9g} ({ul[i]:.3g} ulp, bound {bound[i] / ulp32(R[i]):.3g} ulp)")
+
+
+def _bit_equal(what, got, want, path):
+    a, b = np.asarray(got, np.float32).ravel(), np.asarray(want, np.float32).ravel()
+    same = a.view(np.uint32) == b.view(np.uint32)
+    assert np.all(same), f"{path}: {what} must be bit-unchanged: {int((~same).sum())} of {a.size} elements differ"
+
+
+def optimizer_cfg(hip):
+    """What check_optimizer_step needs of a SACTrainer / TD3Trainer, from its host attributes only."""
+    td3 = hasattr(hip, "target_policy")
+    O, A = hip.obs_dim, hip.act_dim
+    hp = [int(h) for h in hip.policy.hidden_sizes]
+    hq = [int(h) for h in hip.qf1.hidden_sizes]
+
+    def mlp(k, hs, heads):
+        dims = [k] + hs
+        return [(dims[i + 1], dims[i]) for i in range(len(hs))] + [(n, hs[-1]) for n in heads]
+
+    pol = mlp(O, hp, [A] if td3 else [A, A])
+    q = mlp(O + A, hq, [1])
+    nets = {"policy": (pol, layer_names(len(pol), NET_HEADS["td3_policy" if td3 else "sac_policy"])),
+            "qf1": (q, layer_names(len(q), NET_HEADS["q"])), "qf2": (q, layer_names(len(q), NET_HEADS["q"]))}
+    if td3:
+        return dict(td3=True, nets=nets, B=hip._batch, lr={"policy": hip.policy_learning_rate, "qf1": hip.qf_learning_rate,
+                    "qf2": hip.qf_learning_rate}, tau=hip.tau, period=hip.policy_and_target_update_period,
+                    targets={"target_qf1": "qf1", "target_qf2": "qf2", "target_policy": "policy"})
+    return dict(td3=False, nets=nets, B=hip._batch, lr={"policy": hip.policy_lr, "qf1": hip.qf_lr, "qf2": hip.qf_lr},
+                tau=hip.soft_target_tau, period=hip.target_update_period, targets={"target_qf1": "qf1", "target_qf2": "qf2"},
+                auto_alpha=hip.use_automatic_entropy_tuning, target_entropy=hip.target_entropy, alpha_lr=hip.policy_lr)
+
+
+def check_optimizer_step(hip, before, after, cfg, path):
+    """What one stepwise train(batch, eps=...) wrote back -- parameters, Adam moments, Polyak targets, log_alpha and its
+    Adam state, counters -- per named tensor, each quantity from the kernel's OWN inputs to its stage (so errors do not
+    compound): `before` / `after` are state_dict()s around the step, `hip` the trainer (debug_fetch "g_*", "log_pi").
+
+    Bounds, u = 2^-24 the float32 unit roundoff, ulp(R) >= u |R| at the float64 reference R:
+      m = m0 + c1 (g - m0): fl(g - m0), fl(c1 .), fl(m0 + .) (a fused multiply-add drops one) -- at most 1/2 ulp(R) for the
+        last rounding and u |c1 (g - m0)| for the two inside, where (g - m0) may cancel against m0.  Bound: 2 ulp(R) +
+        2 u |c1 (g - m0)|.
+      v = v0 b2 + c2 g g: every term >= 0, so four roundings stay inside 2 u |R| <= 2 ulp(R).  Bound: 2 ulp(R).
+      p = p0 + d, d = (-s m) / (sqrt(v) / bc2s + eps) from the kernel's own m and v: the float32 step size s (one rounding
+        of lr / bc1 in double; the kernel's float lr may move it one more), the product, the square root (1 ulp where it is
+        not correctly rounded), the scaling, eps and the quotient put at most ~4.5 u |d| into d, and the sum rounds once.
+        Bound: 1 ulp(R) + 6 u |d|.
+      target = t (1 - tau) + p tau from `before`'s target and the kernel's own new p: the scalar 1 - tau (one more
+        rounding where it is formed in float32), two products and the sum.  Bound: 1 ulp(R) + 2 u (|t (1 - tau)| + |p tau|).
+      log_alpha: gr = -mean(log_pi + H) summed in float32 over B rows -- at most (B + 4) u (mean|log_pi| + |H|) =: E from
+        the float64 value (recursive summation of B terms, the division, adding H).  a_m: the m bound + c1 E; a_v: 2 ulp(R)
+        + c2 E (2 |gr| + E); log_alpha from the kernel's own a_m, a_v: the p bound; Alpha = exp(log_alpha) to 2 ulp.
+    Exact: where g == 0 and m0 == v0 == 0, p stays bit-unchanged and m, v stay 0; with lr == 0, p stays bit-unchanged.
+    A target off its period, the TD3 policy and its moments off a policy step stay bit-unchanged; without automatic
+    entropy tuning so do log_alpha, a_m and a_v, and Alpha is 1."""
+    td3 = cfg["td3"]
+    sb, sa = np.asarray(before["scalars"], np.float64), np.asarray(after["scalars"], np.float64)
+    n0, t0 = int(sb[4]), int(sb[3])
+    step = f"step {n0}"
+    assert sa[4] == n0 + 1 and sa[3] == t0 + 1, (path, step, "counters", sb, sa)
+    avg = n0 % cfg["period"] == 0                        # rlkit: soft update where _n_train_steps_total % period == 0
+    t_of = {"qf1": t0 + 1, "qf2": t0 + 1, "policy": t0 + 1}
+    trained = ["qf1", "qf2", "policy"]
+    if td3:
+        tp0 = int(sb[0])                                 # TD3: scalars[0] counts the (delayed) policy's optimizer steps
+        assert sa[0] == tp0 + (1 if avg else 0), (path, step, "adam_t_pi", sb, sa)
+        t_of["policy"] = tp0 + 1
+        if not avg:
+            trained = ["qf1", "qf2"]
+            _bit_equal(f"{step} policy (no policy step)", after["params"]["policy"], before["params"]["policy"], path)
+            for i, q in enumerate(("m", "v")):
+                _bit_equal(f"{step} policy {q} (no policy step)", after["opt"]["policy"][i], before["opt"]["policy"][i],
+                           path)
+    for net in trained:
+        shapes, names = cfg["nets"][net]
+        lr, t = cfg["lr"][net], t_of[net]
+        c1 = adam_scalars(lr, t)[0]
+        n = sum(a * b + a for a, b in shapes)
+        T = lambda x: named_tensors(np.asarray(x), shapes, names, net)     # noqa: E731
+        P0, M0, V0 = T(before["params"][net]), T(before["opt"][net][0]), T(before["opt"][net][1])
+        P1, M1, V1 = T(after["params"][net]), T(after["opt"][net][0]), T(after["opt"][net][1])
+        G = T(hip.debug_fetch("g_" + net, n))
+        for k in P0:
+            g, m0, v0 = (x[k].astype(np.float64) for x in (G, M0, V0))
+            mr, vr = adam_moments_ref(m0, v0, g, t)
+            _within(f"{step} exp_avg of {k} (t = {t})", M1[k], mr, 2 * ulp32(mr) + 2 * U32 * np.abs(c1 * (g - m0)), path,
+                    "m")
+            _within(f"{step} exp_avg_sq of {k} (t = {t})", V1[k], vr, 2 * ulp32(vr), path, "v")
+            pr, d = adam_param_ref(P0[k], M1[k], V1[k], lr, t)
+            _within(f"{step} {k} (t = {t})", P1[k], pr, ulp32(pr) + 6 * U32 * np.abs(d), path, "p")
+            z = (g == 0) & (m0 == 0) & (v0 == 0)
+            if np.any(z):                                # (a moment of -0 may come back +0: m0 + c1 (0 - m0))
+                _bit_equal(f"{step} {k} where g == m0 == v0 == 0", P1[k][z], P0[k][z], path)
+                assert np.all(M1[k][z] == 0) and np.all(V1[k][z] == 0), f"{path}: {step} {k}: moments must stay 0 where g == m0 == v0 == 0"
+
+            if lr == 0:
+                _bit_equal(f"{step} {k} at lr 0", P1[k], P0[k], path)
+    for tgt, src in cfg["targets"].items():
+        if src not in trained:
+            _bit_equal(f"{step} {tgt} (no policy step)", after["params"][tgt], before["params"][tgt], path)
+            continue
+        if not avg:
+            _bit_equal(f"{step} {tgt} (off its period {cfg['period']})", after["params"][tgt], before["params"][tgt], path)
+            continue
+        shapes, names = cfg["nets"][src]
+        T = lambda x: named_tensors(np.asarray(x), shapes, names, tgt)     # noqa: E731
+        T0, T1, P1 = T(before["params"][tgt]), T(after["params"][tgt]), T(after["params"][src])
+        tau = cfg["tau"]
+        for k in T0:
+            r = polyak_ref(T0[k], P1[k], tau)
+            t64, p64 = T0[k].astype(np.float64), P1[k].astype(np.float64)
+            b = ulp32(r) + 2 * U32 * (np.abs(t64 * _f(1 - tau)) + np.abs(p64 * _f(tau)))
+            _within(f"{step} {k} (Polyak, tau {tau})", T1[k], r, b, path, "target")
+    if td3:
+        return
+    la0, am0, av0 = (float(np.float32(x)) for x in sb[:3])
+    la1, am1, av1, alpha = (float(np.float32(x)) for x in sa[(0, 1, 2, 5),])
+    if not cfg["auto_alpha"]:
+        _bit_equal(f"{step} log_alpha, a_m, a_v (fixed alpha)", [la1, am1, av1], [la0, am0, av0], path)
+        assert alpha == 1.0, (path, step, "Alpha with fixed alpha", alpha)
+        return
+    t = t0 + 1
+    lp = hip.debug_fetch("log_pi", cfg["B"])
+    H = float(np.float32(cfg["target_entropy"]))
+    E = (cfg["B"] + 4) * U32 * (float(np.mean(np.abs(lp.astype(np.float64)))) + abs(H))
+    c1, _, c2 = adam_scalars(0.0, t)[:3]
+    gr = alpha_grad_ref(lp, H)
+    mr, vr = adam_moments_ref(am0, av0, gr, t)
+    _within(f"{step} log_alpha exp_avg (t = {t})", am1, mr, 2 * ulp32(mr) + 2 * U32 * abs(c1 * (gr - am0)) + c1 * E, path,
+            "a_m")
+    _within(f"{step} log_alpha exp_avg_sq (t = {t})", av1, vr, 2 * ulp32(vr) + c2 * E * (2 * abs(gr) + E), path, "a_v")
+    pr, d = adam_param_ref(la0, am1, av1, cfg["alpha_lr"], t)
+    _within(f"{step} log_alpha (t = {t})", la1, pr, ulp32(pr) + 6 * U32 * np.abs(d), path, "log_alpha")
+    ea = np.float32(np.exp(la1))
+    assert ulp_distance(alpha, ea) <= 2, (path, step, "Alpha != exp(log_alpha)", alpha, float(ea))
+    rec = OPT_ULPS.setdefault(path, {})
+    rec["alpha"] = max(rec.get("alpha", 0.0), float(ulp_distance(alpha, ea)))

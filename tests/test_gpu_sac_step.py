@@ -10,8 +10,8 @@ import numpy as np
 import pytest
 
 from robosuite_benchmark_amd._lib import DIAG_NAMES
-from tests.helpers import (TASK_DIMS, _net_info, check_f64, check_step_f64, flat_of, make_pair, named_tensors, oracle_flat_grad,
-                           rel_err, synth_transitions)
+from tests.helpers import (TASK_DIMS, _adam_f32, _net_info, check_f64, check_step_f64, flat_of, make_pair, named_tensors,
+                           oracle_flat_grad, rel_err, synth_transitions)
 
 pytestmark = pytest.mark.gpu
 TOL = 1e-5
@@ -108,17 +108,6 @@ def _flat_state(torch_opt, net, key):
     """torch.optim.Adam state of one oracle net as a flat nn.Linear vector (W, b per layer)."""
     return np.concatenate([np.concatenate([torch_opt.state[w][key].numpy().ravel(), torch_opt.state[b][key].numpy().ravel()])
                            for w, b in zip(net.ws, net.bs)])
-
-
-def _adam_f32(p, m, v, g, lr, t):
-    """torch.optim.Adam (fp32 tensors, double bias corrections) restated in NumPy float32."""
-    f = np.float32
-    m = m + f(1.0 - 0.9) * (g - m)                                  # exp_avg.lerp_(grad, 1 - beta1)
-    v = v * f(0.999) + f(1.0 - 0.999) * g * g                       # mul_(beta2).addcmul_(grad, grad, 1 - beta2)
-    bc1, bc2s = 1.0 - 0.9 ** t, np.sqrt(1.0 - 0.999 ** t)
-    denom = np.sqrt(v) / f(bc2s) + f(1e-8)
-    p = p + (f(-(lr / bc1)) * m) / denom                            # addcdiv_(exp_avg, denom, value=-step_size)
-    return p.astype(f), m.astype(f), v.astype(f)
 
 
 @pytest.mark.parametrize("task,B", [("Lift", 256), ("TwoArmHandoff", 64)])
