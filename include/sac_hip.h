@@ -375,6 +375,21 @@ int td3_group_create_mixed(sac_group_t **out, sac_trainer_t *const *members, int
  * members.  sac_group_train_loop and sac_group_destroy serve MLP groups too. */
 int sac_group_create_mlp(sac_group_t **out, sac_trainer_t *const *members, int n_members);
 int td3_group_create_mlp(sac_group_t **out, sac_trainer_t *const *members, int n_members);
+/* Arch groups: general-step runs of DIFFERENT hidden sizes (a network-width or network-depth sweep) on one device.
+ * 1..SAC_GROUP_MAX trainers of one algorithm (sac_group_create_arch: SAC, td3_group_create_arch: TD3); each member's
+ * policy and Q hidden lists may be any the general step takes (1..7 layers of 1..4096 units), and may differ from each
+ * other; dims, batch, hyperparameters, noise seeds and TD3 update periods may differ as in MLP groups.  The group walks
+ * a merged schedule: every member's launch list has the same elementwise stages in the same order, and between two of
+ * them runs of GEMM stages by mode (forward, backward, weight gradients); each such run becomes as many grouped GEMM
+ * launches as the longest member's, member m taking part in the first count_m of them.  Every member runs its own
+ * stages in its own order with its own tiles, split factors and job order, so its result is bit for bit that of
+ * sac_train_loop(members[r], buffers[r], n_steps).  Refused (error, nothing changed) as by sac_group_create_mlp, except
+ * that hidden sizes may differ.  sac_group_train_loop and sac_group_destroy serve arch groups too. */
+int sac_group_create_arch(sac_group_t **out, sac_trainer_t *const *members, int n_members);
+int td3_group_create_arch(sac_group_t **out, sac_trainer_t *const *members, int n_members);
+/* The grouped stages of one full step of group g, any kind (MLP and arch groups: SAC the step's grouped stages, TD3 the
+ * critic pass's plus the actor pass's; the fused kinds: 4 for SAC, 7 for TD3), or -2 for NULL (an argument error). */
+int sac_group_stage_count(const sac_group_t *g);
 int sac_group_destroy(sac_group_t *g);
 int sac_group_train_loop(sac_group_t *g, sac_buffer_t *const *buffers, int64_t n_steps, float *diag_first,
                          float *diag_last);

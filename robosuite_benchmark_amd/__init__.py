@@ -10,9 +10,9 @@ from .networks import (FlattenMlp, GaussianStrategy, MakeDeterministic,  # noqa:
 from .replay_buffer import DeviceBatch, EnvReplayBuffer  # noqa: F401
 from .sac import SACTrainer  # noqa: F401
 from .td3 import TD3Trainer  # noqa: F401
-from .group import (MixedSACTrainerGroup, MixedTD3TrainerGroup, MlpSACTrainerGroup, MlpTD3TrainerGroup,  # noqa: F401
-                    SACTrainerGroup, TD3TrainerGroup)
+from .group import (ArchSACTrainerGroup, ArchTD3TrainerGroup, MixedSACTrainerGroup, MixedTD3TrainerGroup,  # noqa: F401
+                    MlpSACTrainerGroup, MlpTD3TrainerGroup, SACTrainerGroup, TD3TrainerGroup)
 
 __all__ = ["EnvReplayBuffer", "DeviceBatch", "FlattenMlp", "TanhGaussianPolicy", "MakeDeterministic", "SACTrainer",
-           "SACTrainerGroup", "MixedSACTrainerGroup", "MlpSACTrainerGroup", "MlpTD3TrainerGroup", "TD3Trainer", "MixedTD3TrainerGroup", "TD3TrainerGroup", "TanhMlpPolicy", "GaussianStrategy",
+           "SACTrainerGroup", "MixedSACTrainerGroup", "MlpSACTrainerGroup", "MlpTD3TrainerGroup", "ArchSACTrainerGroup", "ArchTD3TrainerGroup", "TD3Trainer", "MixedTD3TrainerGroup", "TD3TrainerGroup", "TanhMlpPolicy", "GaussianStrategy",
            "PolicyWrappedWithExplorationStrategy"]

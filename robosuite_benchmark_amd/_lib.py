@@ -116,6 +116,9 @@ SYMBOLS = {
     "td3_group_create_mixed": (C.c_int, [C.POINTER(_P), _P, C.c_int]),
     "sac_group_create_mlp": (C.c_int, [C.POINTER(_P), _P, C.c_int]),
     "td3_group_create_mlp": (C.c_int, [C.POINTER(_P), _P, C.c_int]),
+    "sac_group_create_arch": (C.c_int, [C.POINTER(_P), _P, C.c_int]),
+    "td3_group_create_arch": (C.c_int, [C.POINTER(_P), _P, C.c_int]),
+    "sac_group_stage_count": (C.c_int, [_P]),
     "sac_group_destroy": (C.c_int, [_P]),
     "sac_group_train_loop": (C.c_int, [_P, _P, C.c_int64, _P, _P]),
 }

@@ -1234,7 +1234,8 @@ struct GenGroupStep {
 // which members a grouped launch serves: every member on its sa / members with `actor` on their sp / members with `pstep`
 enum { GSEL_ALL = 0, GSEL_ACTOR = 1, GSEL_PSTEP = 2 };
 // kernel argument of k_g_gemm_group: the blocks of device member k are start[k] .. start[k + 1] - 1 (entries past the
-// group's last member hold 1 << 30)
+// group's last member hold 1 << 30).  A member without a stage in the launch (an arch group's merged schedule) has
+// start[k] == start[k + 1]: zero blocks.
 struct GemmGroupMap {
     int start[SAC_GROUP_MAX + 1];
     int sel, pad_;
@@ -1253,6 +1254,8 @@ __global__ __launch_bounds__(64 * GW) void k_g_gemm_group(const GemmStage *__res
                                                           const GenGroupStep *__restrict__ SA, int slot, GemmGroupMap P) {
     const int bx = (int)blockIdx.x;
     int m = 0;
+    // (the last member whose start is <= bx: where members of zero blocks share a start, the tie resolves to the later
+    //  member, the one that owns the block -- a zero-block member's header is never read)
 #pragma unroll
     for (int q = 1; q < SAC_GROUP_MAX; ++q) m = (bx >= P.start[q]) ? q : m;
     const GenGroupStep &st = SA[m];

@@ -28,6 +28,7 @@
 #include "sac_common.h"
 
 #include <algorithm>
+#include <array>
 #include <cmath>
 #include <cstdlib>
 #include <chrono>
@@ -3707,9 +3708,41 @@ static int gen_small_extent(int kind, int n) {
     }
 }
 
-// MLP groups: members of the general step with one set of hidden sizes
-static int group_create_mlp(sac_group_t **out, sac_trainer_t *const *members, int n_members, int algo) {
-    const char *fname = algo ? "td3_group_create_mlp" : "sac_group_create_mlp";
+// A member's launch list as a skeleton: its plain (elementwise) stages in order, and in front of each of them -- and
+// behind the last -- its GEMM stages as three equal-mode sub-runs in the fixed order forward (0), backward (1), weight
+// gradients (2), each in list order; a sub-run may be empty (e.g. no backward launch of the policy at Lp = 1).  false:
+// the list does not have that form (a GEMM stage of a lower mode behind a higher one in the same gap).
+struct GenSkeleton {
+    std::vector<int> plain;                                    // list indices of the plain stages
+    std::vector<std::array<std::vector<int>, 3>> runs;        // runs[p][mode]: list indices in front of plain stage p
+};
+static bool gen_skeleton(const std::vector<GenStage> &L, GenSkeleton &S) {
+    S.plain.clear();
+    S.runs.assign(1, {});
+    int last = 0;
+    for (size_t k = 0; k < L.size(); ++k) {
+        if (L[k].kind != GS_GEMM) {
+            S.plain.push_back((int)k);
+            S.runs.emplace_back();
+            last = 0;
+            continue;
+        }
+        if (L[k].mode < last || L[k].mode > 2) return false;
+        last = L[k].mode;
+        S.runs.back()[L[k].mode].push_back((int)k);
+    }
+    return true;
+}
+
+// MLP groups (members of the general step with one set of hidden sizes) and arch groups (arch: any hidden sizes of the
+// general step).  Both walk the merged schedule of the members' launch lists: the plain stages in order, every member in
+// each; at each GEMM sub-run the largest count over the members of grouped launches, member m in the first count_m of
+// them and with zero blocks in the rest.  Each member thus runs its own stages in its own order, each with its own
+// header (jobs, tiles, split factor, scratch, counters): what its solo launch list runs.  Members of one set of hidden
+// sizes have one list shape, and the merged schedule is their list.
+static int group_create_mlp(sac_group_t **out, sac_trainer_t *const *members, int n_members, int algo, bool arch) {
+    const char *fname = arch ? (algo ? "td3_group_create_arch" : "sac_group_create_arch")
+                             : (algo ? "td3_group_create_mlp" : "sac_group_create_mlp");
     SAC_REQUIRE(out && members, "null argument to %s", fname);
     *out = nullptr;
     SAC_REQUIRE(n_members >= 1 && n_members <= SAC_GROUP_MAX, "a trainer group holds 1..%d members (got %d)", SAC_GROUP_MAX,
@@ -3721,27 +3754,38 @@ static int group_create_mlp(sac_group_t **out, sac_trainer_t *const *members, in
         for (int j = 0; j < i; ++j)
             SAC_REQUIRE(members[j] != t, "trainer group members %d and %d are the same trainer", j, i);
         if (group_member_ok(t, i, algo, true)) return -1;
-        const sac_general *a = t->gen, *b = t0->gen;
-        bool same = a->Lp == b->Lp && a->Lq == b->Lq;
-        for (int l = 0; same && l < a->Lp; ++l) same = a->hp[l] == b->hp[l];
-        for (int l = 0; same && l < a->Lq; ++l) same = a->hq[l] == b->hq[l];
-        SAC_REQUIRE(same, "trainer group member %d has other hidden sizes than member 0 (an MLP group shares them)", i);
+        if (!arch) {
+            const sac_general *a = t->gen, *b = t0->gen;
+            bool same = a->Lp == b->Lp && a->Lq == b->Lq;
+            for (int l = 0; same && l < a->Lp; ++l) same = a->hp[l] == b->hp[l];
+            for (int l = 0; same && l < a->Lq; ++l) same = a->hq[l] == b->hq[l];
+            SAC_REQUIRE(same, "trainer group member %d has other hidden sizes than member 0 (an MLP group shares them)", i);
+        }
         SAC_REQUIRE(t->device == t0->device, "trainer group member %d lives on device %d, member 0 on %d", i, t->device, t0->device);
     }
     // the members' launch lists (SAC: the step; TD3: the critic pass, then the actor pass, whose statistics-only form is
-    // its head up to the Q1 last layer): one sequence of stage kinds for all of them -- same algorithm, same hidden sizes
+    // its head up to the Q1 last layer), each as its skeleton: one sequence of plain stages for all of them (same
+    // algorithm), checked, not assumed
     auto lists_of = [algo](const sac_trainer *t) {
         std::vector<const std::vector<GenStage> *> L;
         if (algo == 0) L.push_back(&t->gen->stages);
         else { L.push_back(&t->gen->td3_critic); L.push_back(&t->gen->td3_actor); }
         return L;
     };
-    for (int i = 1; i < n_members; ++i) {
-        const auto L = lists_of(members[i]), L0 = lists_of(t0);
-        for (size_t q = 0; q < L.size(); ++q) {
-            bool same = L[q]->size() == L0[q]->size();
-            for (size_t k = 0; same && k < L[q]->size(); ++k) same = (*L[q])[k].kind == (*L0[q])[k].kind && (*L[q])[k].mode == (*L0[q])[k].mode;
-            SAC_REQUIRE(same, "internal: trainer group member %d has another launch list than member 0", i);
+    const size_t nlists = lists_of(t0).size();
+    std::vector<std::vector<GenSkeleton>> sk(nlists, std::vector<GenSkeleton>((size_t)n_members));   // [list][member]
+    for (int i = 0; i < n_members; ++i) {
+        const auto L = lists_of(members[i]);
+        for (size_t q = 0; q < nlists; ++q) {
+            SAC_REQUIRE(gen_skeleton(*L[q], sk[q][(size_t)i]), "internal: trainer group member %d has a launch list whose "
+                        "GEMM stages are out of mode order", i);
+            const GenSkeleton &a = sk[q][(size_t)i], &b = sk[q][0];
+            bool same = a.plain.size() == b.plain.size();
+            for (size_t k = 0; same && k < a.plain.size(); ++k) {
+                const GenStage &x = (*L[q])[(size_t)a.plain[k]], &y = (*lists_of(t0)[q])[(size_t)b.plain[k]];
+                same = x.kind == y.kind && x.mode == y.mode;
+            }
+            SAC_REQUIRE(same, "internal: trainer group member %d has another sequence of elementwise stages than member 0", i);
         }
     }
     SAC_HIP(hipSetDevice(t0->device));
@@ -3763,41 +3807,59 @@ static int group_create_mlp(sac_group_t **out, sac_trainer_t *const *members, in
         K.n = pos - K.lo;
         if (K.n > 0) g->ncls += 1;
     }
-    // the grouped stage list and the GEMM stages' headers, [GEMM stage][device member]
+    // the merged schedule and the GEMM stages' headers, [grouped GEMM stage][device member]; a member without a stage in
+    // a grouped GEMM launch gets an inert header (no tiles, never read: it owns no block of that launch)
     std::vector<gen::GemmStage> hdr;
-    const auto L0 = lists_of(t0);
-    for (size_t li = 0; li < L0.size(); ++li) {
+    gen::GemmStage inert;
+    memset(&inert, 0, sizeof(inert));
+    inert.splitk = 1;
+    for (size_t li = 0; li < nlists; ++li) {
+        const std::vector<GenStage> &L0 = *lists_of(t0)[li];
+        const GenSkeleton &S0 = sk[li][0];
         bool past_qa = false;
-        for (size_t k = 0; k < L0[li]->size(); ++k) {
-            const GenStage &s0 = (*L0[li])[k];
+        // TD3's actor pass: every member with `actor` up to Q1's last layer (whose backward half follows pstep), the
+        // policy's backward pass and update for members on a policy step, the statistics behind them for all of `actor`
+        auto sel_of = [&](int kind) {
+            return li == 0 ? gen::GSEL_ALL : ((past_qa && kind != GS_DIAG) ? gen::GSEL_PSTEP : gen::GSEL_ACTOR);
+        };
+        for (size_t p = 0; p < S0.runs.size(); ++p) {
+            for (int mode = 0; mode < 3; ++mode) {
+                size_t cnt = 0;
+                for (int d = 0; d < R; ++d) cnt = std::max(cnt, sk[li][(size_t)g->ord[d]].runs[p][(size_t)mode].size());
+                for (size_t c = 0; c < cnt; ++c) {
+                    GroupGenStage st;
+                    st.kind = GS_GEMM; st.mode = mode; st.list = (int)li; st.sel = sel_of(GS_GEMM);
+                    st.hdr = (int)(hdr.size() / R);
+                    int at = 0;
+                    for (int q = 0; q <= SAC_GROUP_MAX; ++q) st.map.start[q] = 1 << 30;
+                    for (int d = 0; d < R; ++d) {
+                        const sac_trainer *t = members[g->ord[d]];
+                        const std::vector<int> &run = sk[li][(size_t)g->ord[d]].runs[p][(size_t)mode];
+                        gen::GemmStage gs = inert;
+                        if (c < run.size()) {
+                            gs = (*lists_of(t)[li])[(size_t)run[c]].gs;
+                            gs.tau = t->gen->dev.tau;      // (gen_run_list sets it per launch; the rest per step, in the kernel)
+                        }
+                        hdr.push_back(gs);
+                        st.map.start[d] = at;
+                        at += gs.ntiles * gs.splitk;
+                    }
+                    st.map.sel = st.sel;
+                    st.grid = at;
+                    g->gst.push_back(st);
+                }
+            }
+            if (p == S0.plain.size()) break;
+            const GenStage &s0 = L0[(size_t)S0.plain[p]];
             GroupGenStage st;
-            st.kind = s0.kind; st.mode = s0.mode; st.list = (int)li;
-            // TD3's actor pass: every member with `actor` up to Q1's last layer (whose backward half follows pstep), the
-            // policy's backward pass and update for members on a policy step, the statistics behind them for all of `actor`
-            st.sel = li == 0 ? gen::GSEL_ALL : ((past_qa && s0.kind != GS_DIAG) ? gen::GSEL_PSTEP : gen::GSEL_ACTOR);
+            st.kind = s0.kind; st.mode = s0.mode; st.list = (int)li; st.sel = sel_of(s0.kind);
             if (s0.kind == GS_TD3_QA) past_qa = true;
-            if (s0.kind == GS_GEMM) {
-                st.hdr = (int)(hdr.size() / R);
-                int at = 0;
-                for (int q = 0; q <= SAC_GROUP_MAX; ++q) st.map.start[q] = 1 << 30;
-                for (int d = 0; d < R; ++d) {
-                    const sac_trainer *t = members[g->ord[d]];
-                    gen::GemmStage gs = (*lists_of(t)[li])[k].gs;
-                    gs.tau = t->gen->dev.tau;              // (gen_run_list sets it per launch; the rest per step, in the kernel)
-                    hdr.push_back(gs);
-                    st.map.start[d] = at;
-                    at += gs.ntiles * gs.splitk;
-                }
-                st.map.sel = st.sel;
-                st.grid = at;
-            } else {
-                st.per_class = s0.kind == GS_HEAD || s0.kind == GS_POLGRAD || s0.kind == GS_TD3_HEAD || s0.kind == GS_TD3_AHEAD ||
-                               s0.kind == GS_TD3_POLGRAD;
-                for (int c = 0; c < (st.per_class ? g->ncls : 1); ++c) {
-                    const int lo = st.per_class ? g->cls[c].lo : 0, hi = st.per_class ? lo + g->cls[c].n : R;
-                    st.fn[c] = gen_small_fn(s0.kind, st.per_class ? g->cls[c].ma : 0);
-                    for (int d = lo; d < hi; ++d) st.gx[c] = std::max(st.gx[c], gen_small_extent(s0.kind, members[g->ord[d]]->Bt));
-                }
+            st.per_class = s0.kind == GS_HEAD || s0.kind == GS_POLGRAD || s0.kind == GS_TD3_HEAD || s0.kind == GS_TD3_AHEAD ||
+                           s0.kind == GS_TD3_POLGRAD;
+            for (int c = 0; c < (st.per_class ? g->ncls : 1); ++c) {
+                const int lo = st.per_class ? g->cls[c].lo : 0, hi = st.per_class ? lo + g->cls[c].n : R;
+                st.fn[c] = gen_small_fn(s0.kind, st.per_class ? g->cls[c].ma : 0);
+                for (int d = lo; d < hi; ++d) st.gx[c] = std::max(st.gx[c], gen_small_extent(s0.kind, members[g->ord[d]]->Bt));
             }
             g->gst.push_back(st);
         }
@@ -3829,11 +3891,25 @@ int td3_group_create_mixed(sac_group_t **out, sac_trainer_t *const *members, int
 }
 
 int sac_group_create_mlp(sac_group_t **out, sac_trainer_t *const *members, int n_members) {
-    return group_create_mlp(out, members, n_members, 0);
+    return group_create_mlp(out, members, n_members, 0, false);
 }
 
 int td3_group_create_mlp(sac_group_t **out, sac_trainer_t *const *members, int n_members) {
-    return group_create_mlp(out, members, n_members, 1);
+    return group_create_mlp(out, members, n_members, 1, false);
+}
+
+int sac_group_create_arch(sac_group_t **out, sac_trainer_t *const *members, int n_members) {
+    return group_create_mlp(out, members, n_members, 0, true);
+}
+
+int td3_group_create_arch(sac_group_t **out, sac_trainer_t *const *members, int n_members) {
+    return group_create_mlp(out, members, n_members, 1, true);
+}
+
+int sac_group_stage_count(const sac_group_t *g) {
+    SAC_REQUIRE(g, "null argument to sac_group_stage_count");
+    if (g->mlp) return (int)g->gst.size();
+    return g->algo == 0 ? 4 : 7;                      // (the four-launch step; TD3: A, B, C, dW of the critic pass, B, C, dW of the actor pass)
 }
 
 int sac_group_destroy(sac_group_t *g) {

@@ -22,8 +22,8 @@ from .group_checkpoint import checkpoint_exists as _checkpoint_exists
 from .networks import (FlattenMlp, GaussianStrategy, MakeDeterministic, PolicyWrappedWithExplorationStrategy,
                        TanhGaussianPolicy, TanhMlpPolicy)
 from .replay_buffer import EnvReplayBuffer
-from .group import (MixedSACTrainerGroup, MixedTD3TrainerGroup, MlpSACTrainerGroup, MlpTD3TrainerGroup, SACTrainerGroup,
-                    TD3TrainerGroup, runs_general_step)
+from .group import (ArchSACTrainerGroup, ArchTD3TrainerGroup, MixedSACTrainerGroup, MixedTD3TrainerGroup,
+                    MlpSACTrainerGroup, MlpTD3TrainerGroup, SACTrainerGroup, TD3TrainerGroup, runs_general_step)
 from .sac import SACTrainer
 from .td3 import TD3Trainer
 from .variant import env_dims, validate
@@ -432,8 +432,21 @@ def task_label(variant):
     return f"{env['env_name']}-{''.join(robots)}"
 
 
+def hidden_label(variant):
+    """The hidden sizes of a variant as a name part: h512x512, or p<policy>-q<qf> when the two differ
+    (p256x256-q512x512x512)."""
+    hp, hq = ("x".join(str(int(h)) for h in variant[kw]["hidden_sizes"]) for kw in ("policy_kwargs", "qf_kwargs"))
+    return f"h{hp}" if hp == hq else f"p{hp}-q{hq}"
+
+
+def sweep_label(variant, seed, hidden_sweep=False):
+    """A sweep run's name (its log directory): <task>-s<seed>, or <task>-<hidden sizes>-s<seed> in a hidden-size sweep
+    (Lift-Panda-h512x512-s1)."""
+    return f"{task_label(variant)}-{hidden_label(variant)}-s{seed}" if hidden_sweep else f"{task_label(variant)}-s{seed}"
+
+
 def experiment_sweep(runs, log_dir=None, num_epochs=None, device=0, quiet=False, checkpoint_dir=None, resume=False,
-                     chunk_rows=DEFAULT_CHUNK_ROWS):
+                     chunk_rows=DEFAULT_CHUNK_ROWS, hidden_sweep=False):
     """Several tasks x seeds, one process, one device: every entry of ``runs`` -- (variant, seed), or (variant, seed,
     obs_dim, action_dim) for a task without pinned dims -- is the run ``experiment(variant, seed=seed)`` would make, and
     every epoch's training block is ONE MixedSACTrainerGroup.train_loop (TD3 variants: MixedTD3TrainerGroup; hidden sizes
@@ -443,7 +456,10 @@ def experiment_sweep(runs, log_dir=None, num_epochs=None, device=0, quiet=False,
     unless it is given here); dims and batch sizes may differ.  Returns the runs' progress rows, a list in the order of
     ``runs``; with log_dir, each run's rows also go to <log_dir>/<task>-s<seed>/progress.csv.  checkpoint_dir, resume
     and chunk_rows as for experiment_group: one generation for every run of the sweep, and a resume needs the saved
-    runs in the saved order."""
+    runs in the saved order.
+    hidden_sweep=True: the runs may also differ in their policy / Q hidden sizes (a network-size sweep), the training
+    block is ONE ArchSACTrainerGroup.train_loop (TD3: ArchTD3TrainerGroup), and each run's name carries its hidden
+    sizes: <task>-h<sizes>-s<seed>, or <task>-p<policy sizes>-q<Q sizes>-s<seed> (sweep_label)."""
     if resume and not checkpoint_dir:
         raise RuntimeError("experiment_sweep(resume=True) needs the checkpoint_dir to resume from")
     specs = []
@@ -464,7 +480,7 @@ def experiment_sweep(runs, log_dir=None, num_epochs=None, device=0, quiet=False,
         ak = v["algorithm_kwargs"]
         if v.get("algorithm", "SAC") != algo0:
             raise RuntimeError(f"sweep run {i} is {v.get('algorithm', 'SAC')}, run 0 {algo0}: a sweep runs one algorithm")
-        for kw in ("policy_kwargs", "qf_kwargs"):
+        for kw in ("policy_kwargs", "qf_kwargs") if not hidden_sweep else ():
             if list(v[kw]["hidden_sizes"]) != list(v0[kw]["hidden_sizes"]):
                 raise RuntimeError(f"sweep run {i} has {kw} hidden sizes {v[kw]['hidden_sizes']}, run 0 "
                                    f"{v0[kw]['hidden_sizes']}")
@@ -472,7 +488,7 @@ def experiment_sweep(runs, log_dir=None, num_epochs=None, device=0, quiet=False,
         for k in plan:
             if ak[k] != ak0[k]:
                 raise RuntimeError(f"sweep run {i} has {k} {ak[k]}, run 0 {ak0[k]}: a sweep runs one epoch plan")
-        label = f"{task_label(v)}-s{seed}"
+        label = sweep_label(v, seed, hidden_sweep)
         if label in labels:
             raise RuntimeError(f"sweep run {i} repeats {label}")
         labels.add(label)
@@ -480,10 +496,12 @@ def experiment_sweep(runs, log_dir=None, num_epochs=None, device=0, quiet=False,
     restoring = bool(resume) and _checkpoint_exists(checkpoint_dir)
     for v, seed, O, A in specs:
         group_runs.append(_group_run(v, seed, O, A, device, prefill=not restoring))
-        group_runs[-1]["sub"] = f"{task_label(v)}-s{seed}"
+        group_runs[-1]["sub"] = sweep_label(v, seed, hidden_sweep)
     ck, first_epoch = _group_checkpoint(group_runs, checkpoint_dir, restoring, chunk_rows)
     td3 = algo0 == "TD3"
-    if runs_general_step(group_runs[0]["trainer"]):           # (hidden sizes of the general step: an MLP group)
+    if hidden_sweep:                                          # (any hidden sizes: an arch group)
+        group = (ArchTD3TrainerGroup if td3 else ArchSACTrainerGroup)([r["trainer"] for r in group_runs])
+    elif runs_general_step(group_runs[0]["trainer"]):         # (hidden sizes of the general step: an MLP group)
         group = (MlpTD3TrainerGroup if td3 else MlpSACTrainerGroup)([r["trainer"] for r in group_runs])
     else:
         group = (MixedTD3TrainerGroup if td3 else MixedSACTrainerGroup)([r["trainer"] for r in group_runs])

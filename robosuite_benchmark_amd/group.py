@@ -1,7 +1,9 @@
 """SACTrainerGroup / TD3TrainerGroup: several SAC or TD3 runs of one configuration trained together (sac_group_*,
 td3_group_create of include/sac_hip.h); MixedSACTrainerGroup / MixedTD3TrainerGroup: runs of different tasks
 (sac_group_create_mixed, td3_group_create_mixed); MlpSACTrainerGroup / MlpTD3TrainerGroup: runs of the general step --
-hidden sizes other than two layers of at most 256 units (sac_group_create_mlp, td3_group_create_mlp).
+hidden sizes other than two layers of at most 256 units (sac_group_create_mlp, td3_group_create_mlp);
+ArchSACTrainerGroup / ArchTD3TrainerGroup: runs of any hidden sizes, a network-size sweep (sac_group_create_arch,
+td3_group_create_arch, and mixed groups for the fused shapes).
 
 The reference's real workload is many independent runs -- seeds x configurations, one job each
 (/root/reference/launch_jobs.sh).  One run at batch 256 cannot fill an MI355X; a group steps R runs of the same shape
@@ -10,6 +12,7 @@ weights, optimizer state, hyperparameters, noise seed and replay buffer, and a r
 from __future__ import annotations
 
 import ctypes as C
+import re
 
 import numpy as np
 
@@ -87,6 +90,13 @@ class _GroupBase:
             _lib.check(getattr(self._lib, self._CREATE)(C.byref(g), arr, len(hs)), self._CREATE)
             self._g, self._handles = g, hs
         return self._g
+
+    def stage_count(self):
+        """sac_group_stage_count: the grouped stages of one full step (the members need their handles: after a
+        train_loop, or trainers created with a batch size)."""
+        if any(t._h is None for t in self.trainers):
+            raise RuntimeError("stage_count needs every member's handle: run train_loop first")
+        return _lib.check(self._lib.sac_group_stage_count(self._group()), "sac_group_stage_count")
 
     def _destroy(self):
         g, self._g = getattr(self, "_g", None), None
@@ -181,6 +191,10 @@ class _MixedTrainerGroup(_GroupBase):
         with B_r = batch_sizes[r] (default: the trainer's own batch size).  Returns the first and last step's
         diagnostics, arrays of shape (R, SAC_DIAG_N)."""
         buffers = list(replay_buffers)
+        return self._run(buffers, self._prepare(buffers, batch_sizes), n_steps)
+
+    def _prepare(self, buffers, batch_sizes):
+        """Every refusal train_loop can make from host metadata; returns the members' batch sizes."""
         R = len(self.trainers)
         if len(buffers) != R:
             raise RuntimeError(f"{R} trainers but {len(buffers)} replay buffers")
@@ -202,7 +216,7 @@ class _MixedTrainerGroup(_GroupBase):
         for r, b in enumerate(buffers):
             t = self.trainers[r]
             self._check_buffer(r, b, buffers, (t.obs_dim, t.act_dim), "its member")
-        return self._run(buffers, batches, n_steps)
+        return batches
 
 
 class SACTrainerGroup(_TrainerGroup):
@@ -241,9 +255,10 @@ class MixedTD3TrainerGroup(_MixedTrainerGroup):
 
 
 class _MlpTrainerGroup(_MixedTrainerGroup):
-    """Members of the general step (a network-width or network-depth sweep): the hidden sizes, algorithm and device are
-    shared; obs_dim, act_dim and batch may differ per member, as in mixed groups.  Members with the shapes of the fused
-    kernels are refused: their solo step is not the general step."""
+    """Members of the general step with one set of hidden sizes (the seeds and tasks of one architecture; a sweep over
+    architectures is an ArchSACTrainerGroup / ArchTD3TrainerGroup): the hidden sizes, algorithm and device are shared;
+    obs_dim, act_dim and batch may differ per member, as in mixed groups.  Members with the shapes of the fused kernels
+    are refused: their solo step is not the general step."""
     _MAX_BATCH = None
 
     def _check_step(self, i, t):
@@ -267,5 +282,134 @@ class MlpSACTrainerGroup(_MlpTrainerGroup):
 class MlpTD3TrainerGroup(_MlpTrainerGroup):
     """R TD3 runs of the general step; each keeps its own delayed-update phase as in TD3TrainerGroup."""
     _CREATE = "td3_group_create_mlp"
+    _ONLY = "TD3 groups hold TD3 trainers only"
+    _member_ok = staticmethod(TD3TrainerGroup._member_ok)
+
+
+class _ArchGeneral(_MlpTrainerGroup):
+    """The general-step members of an arch group: one C arch group, hidden sizes free per member."""
+
+    def _check_member(self, i, t, t0):
+        self._check_device(i, t, t0)
+
+
+class _ArchGeneralSAC(_ArchGeneral):
+    _CREATE = "sac_group_create_arch"
+    _ONLY = "groups hold SAC trainers only"
+    _member_ok = staticmethod(SACTrainerGroup._member_ok)
+
+
+class _ArchGeneralTD3(_ArchGeneral):
+    _CREATE = "td3_group_create_arch"
+    _ONLY = "TD3 groups hold TD3 trainers only"
+    _member_ok = staticmethod(TD3TrainerGroup._member_ok)
+
+
+_MEMBER_REF = re.compile(r"\b(member|buffer) (\d+)\b")
+
+
+class _ArchTrainerGroup:
+    """Members of ANY hidden sizes (a network-size sweep; the paper default [256, 256] included), one algorithm, one
+    device.  The general-step members form one C arch group (sac_group_create_arch / td3_group_create_arch: the merged
+    schedule of their launch lists, one grouped launch per merged stage); the members with the shapes of the fused
+    kernels form one mixed group per distinct (policy, Q) hidden-size pair, which keeps that kind's own rules (batches of
+    at most 256 rows ...).  train_loop runs the subgroups one after another, in `run_order`: the fused subgroups in order
+    of first appearance, then the general one, each in member order.  Every member's result is bit for bit that of its
+    solo train_loop; buffers that sample one host generator (EnvReplayBuffer's default: np.random) continue it as solo
+    train_loop calls in `run_order` would."""
+    _MIXED = None               # the fused subgroups' kind
+    _GENERAL = None             # the general subgroup's kind
+    _ONLY = None
+
+    @staticmethod
+    def _member_ok(t):
+        raise NotImplementedError
+
+    def __init__(self, trainers):
+        trainers = list(trainers)
+        if not 1 <= len(trainers) <= MAX_MEMBERS:
+            raise RuntimeError(f"a trainer group holds 1..{MAX_MEMBERS} trainers (got {len(trainers)})")
+        for i, t in enumerate(trainers):
+            if not self._member_ok(t):
+                raise RuntimeError(f"trainer group member {i} is a {type(t).__name__}: {self._ONLY}")
+        if len({id(t) for t in trainers}) != len(trainers):
+            raise RuntimeError("a trainer appears twice in the group")
+        for i, t in enumerate(trainers[1:], 1):
+            _GroupBase._check_device(i, t, trainers[0])
+        fused, general = {}, []
+        for i, t in enumerate(trainers):
+            if runs_general_step(t):
+                general.append(i)
+            else:
+                fused.setdefault((tuple(t._hidden("policy")), tuple(t._hidden("qf1"))), []).append(i)
+        # (member indices per subgroup, the subgroup): the fused ones in order of first appearance, the general one last
+        self._subs = [(idx, self._MIXED([trainers[i] for i in idx])) for idx in fused.values()]
+        if general:
+            self._subs.append((general, self._GENERAL([trainers[i] for i in general])))
+        self.trainers = trainers
+        self.run_order = [i for idx, _ in self._subs for i in idx]
+
+    def __len__(self):
+        return len(self.trainers)
+
+    @property
+    def subgroups(self):
+        """The subgroups in run order, each with the indices of its members in the whole group."""
+        return [(list(idx), sub) for idx, sub in self._subs]
+
+    @staticmethod
+    def _renumber(e, idx):
+        """A subgroup's refusal, its member and buffer numbers mapped to the whole group's."""
+        def sub(m):
+            k = int(m.group(2))
+            return f"{m.group(1)} {idx[k]}" if k < len(idx) else m.group(0)
+        return RuntimeError(_MEMBER_REF.sub(sub, str(e)))
+
+    def train_loop(self, replay_buffers, n_steps, batch_sizes=None):
+        """n_steps x {batch_r = replay_buffers[r].random_batch(B_r); trainers[r].train(batch_r)} for every member r, with
+        B_r = batch_sizes[r] (default: the trainer's own batch size), one subgroup after another in `run_order`.
+        Every refusal from host metadata comes before any subgroup runs.  Returns the first and last step's
+        diagnostics, arrays of shape (R, SAC_DIAG_N) in member order."""
+        buffers = list(replay_buffers)
+        R = len(self.trainers)
+        if len(buffers) != R:
+            raise RuntimeError(f"{R} trainers but {len(buffers)} replay buffers")
+        batch_sizes = [None] * R if batch_sizes is None else list(batch_sizes)
+        if len(batch_sizes) != R:
+            raise RuntimeError(f"{R} trainers but {len(batch_sizes)} batch sizes")
+        for r, b in enumerate(buffers):
+            if b is not None and any(b is c for c in buffers[:r]):
+                raise RuntimeError(f"trainer group buffer {r} is the same buffer as an earlier one")
+        plans = []
+        for idx, sub in self._subs:
+            bufs = [buffers[i] for i in idx]
+            try:
+                plans.append((idx, sub, bufs, sub._prepare(bufs, [batch_sizes[i] for i in idx])))
+            except RuntimeError as e:
+                raise self._renumber(e, idx) from None
+        first = np.empty((R, _lib.SAC_DIAG_N), np.float32)
+        last = np.empty((R, _lib.SAC_DIAG_N), np.float32)
+        for idx, sub, bufs, batches in plans:
+            try:
+                f, l = sub._run(bufs, batches, n_steps)
+            except RuntimeError as e:
+                raise self._renumber(e, idx) from None
+            first[idx], last[idx] = f, l
+        return first, last
+
+
+class ArchSACTrainerGroup(_ArchTrainerGroup):
+    """R SAC runs of any hidden sizes (e.g. [256, 256], [512, 512], [256, 256, 256] and [1024] of one or several tasks)
+    on one device; see _ArchTrainerGroup."""
+    _MIXED = MixedSACTrainerGroup
+    _GENERAL = _ArchGeneralSAC
+    _ONLY = "groups hold SAC trainers only"
+    _member_ok = staticmethod(SACTrainerGroup._member_ok)
+
+
+class ArchTD3TrainerGroup(_ArchTrainerGroup):
+    """R TD3 runs of any hidden sizes; each keeps its own delayed-update phase as in TD3TrainerGroup."""
+    _MIXED = MixedTD3TrainerGroup
+    _GENERAL = _ArchGeneralTD3
     _ONLY = "TD3 groups hold TD3 trainers only"
     _member_ok = staticmethod(TD3TrainerGroup._member_ok)

@@ -117,3 +117,29 @@ def validate(variant):
         if k not in variant:
             raise KeyError(f"variant is missing {k!r}")
     return variant
+
+
+def parse_hidden_sizes(text):
+    """'256,256' -> [256, 256] (scripts/train.py --hidden_sizes: one entry per network size)."""
+    try:
+        hs = [int(x) for x in str(text).split(",") if x.strip()]
+    except ValueError:
+        raise ValueError(f"hidden sizes {text!r}: expected comma-separated layer widths such as 256,256") from None
+    if not hs or any(h < 1 for h in hs):
+        raise ValueError(f"hidden sizes {text!r}: expected comma-separated layer widths such as 256,256")
+    return hs
+
+
+def expand_hidden_sizes(variants, hidden_sizes):
+    """One copy of every variant per entry of hidden_sizes (lists of layer widths, or '256,256' strings), policy and Q
+    nets alike: variant-major, [v0 h0, v0 h1, ..., v1 h0, ...].  Each copy is a deep copy; the originals are left as they
+    are."""
+    sizes = [parse_hidden_sizes(h) if isinstance(h, str) else [int(x) for x in h] for h in hidden_sizes]
+    out = []
+    for v in variants:
+        for hs in sizes:
+            c = json.loads(json.dumps(v))
+            c["policy_kwargs"]["hidden_sizes"] = list(hs)
+            c["qf_kwargs"]["hidden_sizes"] = list(hs)
+            out.append(c)
+    return out

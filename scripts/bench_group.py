@@ -16,7 +16,15 @@ they run the general step, and the runs form ONE MLP group (MlpSACTrainerGroup /
 the same runs trained one after another with solo train_loop (the two alternate per (batch, R)).  One JSON line per
 (batch, R) with both aggregate rates.
 
-    python scripts/bench_group.py --hidden 512 512 [--agent SAC|TD3] [--batches 256 128] [--replicas 1 2 4 8 16]"""
+    python scripts/bench_group.py --hidden 512 512 [--agent SAC|TD3] [--batches 256 128] [--replicas 1 2 4 8 16]
+
+--hidden-sweep H1 H2 ...: a network-size sweep, --seeds-per-arch k runs of every entry (comma-separated widths, e.g.
+256,256 512,512 256,256,256 1024; policy and Q nets alike) in three layouts: ONE arch group (ArchSACTrainerGroup /
+ArchTD3TrainerGroup), one group per architecture (an MLP group for the general step, a mixed group for the fused
+shapes) run one after another, and solo train_loop runs one after another.  The layouts alternate --rounds times; one
+JSON line per batch with each layout's best aggregate rate and every round's.
+
+    python scripts/bench_group.py --hidden-sweep 256,256 512,512 256,256,256 1024 [--seeds-per-arch 2] [--rounds 2]"""
 from __future__ import annotations
 
 import argparse
@@ -29,11 +37,12 @@ import numpy as np
 
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 
-from robosuite_benchmark_amd import (EnvReplayBuffer, FlattenMlp, MixedSACTrainerGroup, MlpSACTrainerGroup,  # noqa: E402
-                                     MlpTD3TrainerGroup, SACTrainer, SACTrainerGroup, TanhGaussianPolicy, TanhMlpPolicy,
+from robosuite_benchmark_amd import (ArchSACTrainerGroup, ArchTD3TrainerGroup, EnvReplayBuffer, FlattenMlp,  # noqa: E402
+                                     MixedSACTrainerGroup, MixedTD3TrainerGroup, MlpSACTrainerGroup, MlpTD3TrainerGroup, SACTrainer, SACTrainerGroup, TanhGaussianPolicy, TanhMlpPolicy,
                                      TD3Trainer, TD3TrainerGroup, _lib)
 from robosuite_benchmark_amd.group import runs_general_step  # noqa: E402
 from robosuite_benchmark_amd.parallel import SWEEP  # noqa: E402
+from robosuite_benchmark_amd.variant import parse_hidden_sizes  # noqa: E402
 
 
 def make_trainer(O, A, B, seed, hidden=(256, 256)):
@@ -142,6 +151,62 @@ def bench_hidden(args, bufs):
             del group, trainers
 
 
+def bench_hidden_sweep(args, bufs):
+    """--hidden-sweep: k runs of every architecture as one arch group, as one group per architecture one after another,
+    and as solo train_loop runs one after another (the three alternate, --rounds times)."""
+    O, A = args.obs, args.act
+    td3 = args.agent == "TD3"
+    make = make_td3_trainer if td3 else make_trainer
+    archs = [tuple(parse_hidden_sizes(h)) for h in args.hidden_sweep]
+    k = args.seeds_per_arch
+    runs = [(h, s) for h in archs for s in range(k)]
+    R = len(runs)
+    if R > 16 or R > len(bufs):
+        raise SystemExit(f"{R} runs: an arch group holds at most 16")
+    for B in args.batches:
+        trainers = [make(O, A, B, 10 + i, h) for i, (h, _) in enumerate(runs)]
+        arch = (ArchTD3TrainerGroup if td3 else ArchSACTrainerGroup)(trainers)
+        per_arch = []                                       # (member indices, group) per architecture
+        for h in archs:
+            idx = [i for i, (hh, _) in enumerate(runs) if hh == h]
+            ts = [trainers[i] for i in idx]
+            kind = ((MlpTD3TrainerGroup if td3 else MlpSACTrainerGroup) if runs_general_step(ts[0])
+                    else (MixedTD3TrainerGroup if td3 else MixedSACTrainerGroup))
+            per_arch.append((idx, kind(ts)))
+        layouts = {
+            "arch_group": lambda n: arch.train_loop(bufs[:R], n, batch_sizes=[B] * R),
+            "per_arch_groups": lambda n: [g.train_loop([bufs[i] for i in idx], n, batch_sizes=[B] * len(idx))
+                                          for idx, g in per_arch],
+            "solo": lambda n: [t.train_loop(b, n, batch_size=B) for t, b in zip(trainers, bufs[:R])],
+        }
+        for run in layouts.values():
+            run(args.warmup)
+        rates = {name: [] for name in layouts}
+        for _ in range(args.rounds):
+            for name, run in layouts.items():
+                t0 = time.perf_counter()
+                out = run(args.steps)
+                rates[name].append(round(R * args.steps / (time.perf_counter() - t0), 1))
+                if name == "arch_group":
+                    last = out[1]
+        best = {name: max(v) for name, v in rates.items()}
+        general = [sub for idx, sub in arch.subgroups if runs_general_step(trainers[idx[0]])]
+        stages = general[0].stage_count() if general else None
+        print(json.dumps(dict(metric="arch_group_grad_steps_per_s", agent=args.agent,
+                              hidden_sweep=[list(h) for h in archs], seeds_per_arch=k, runs=R, batch=B, obs_dim=O,
+                              act_dim=A, buffer=args.buffer, steps=args.steps, rounds=args.rounds,
+                              arch_group_aggregate_steps_per_s=best["arch_group"],
+                              per_arch_groups_aggregate_steps_per_s=best["per_arch_groups"],
+                              solo_aggregate_steps_per_s=best["solo"],
+                              gain_vs_per_arch_groups=round(best["arch_group"] / best["per_arch_groups"], 3),
+                              gain_vs_solo=round(best["arch_group"] / best["solo"], 3),
+                              per_round=rates, arch_group_general_stages=stages,
+                              per_arch_general_stages=[g.stage_count() for idx, g in per_arch
+                                                       if runs_general_step(trainers[idx[0]])],
+                              finite=bool(np.all(np.isfinite(last))))), flush=True)
+        del arch, per_arch, trainers
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--tasks", type=str, default="lift", choices=["lift", "sweep"])
@@ -155,6 +220,9 @@ def main():
     ap.add_argument("--obs", type=int, default=42)
     ap.add_argument("--act", type=int, default=7)
     ap.add_argument("--hidden", type=int, nargs="+", default=None)
+    ap.add_argument("--hidden-sweep", type=str, nargs="+", default=None)
+    ap.add_argument("--seeds-per-arch", type=int, default=2)
+    ap.add_argument("--rounds", type=int, default=2)
     args = ap.parse_args()
     if _lib.device_count() == 0:
         raise SystemExit("bench_group.py needs a GPU")
@@ -166,11 +234,14 @@ def main():
             rs.uniform(0, 1, (N, 1)).astype(np.float32), rs.normal(0, 0.5, (N, O)).astype(np.float32),
             np.zeros((N, 1), np.uint8))
     bufs = []
-    for r in range(max(args.replicas)):
+    n_bufs = len(args.hidden_sweep) * args.seeds_per_arch if args.hidden_sweep else max(args.replicas)
+    for r in range(n_bufs):
         b = EnvReplayBuffer(N, obs_dim=O, action_dim=A)
         b.add_block(rows[0], rows[1], rows[2], rows[3], rows[4])
         b.seed(100 + r)
         bufs.append(b)
+    if args.hidden_sweep:
+        return bench_hidden_sweep(args, bufs)
     if args.hidden:
         return bench_hidden(args, bufs)
     for B in args.batches:

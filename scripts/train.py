@@ -3,10 +3,14 @@
     python scripts/train.py --variant <variant.json> --seed S --log_dir DIR [--epochs N]
     python scripts/train.py --variant <variant.json> --seeds S1 S2 ... --log_dir DIR [--epochs N] [--checkpoint]
     python scripts/train.py --variants A.json B.json ... --seeds S1 S2 ... --log_dir DIR [--epochs N] [--checkpoint]
+    python scripts/train.py --variants A.json ... --hidden_sizes 256,256 512,512 256,256,256 --log_dir DIR [...]
 (--seeds: one process trains every seed, the training blocks as one trainer group, SAC or TD3 (--agent);
  DIR/s<seed>/progress.csv each.  --variants: every (variant, seed) pair -- tasks of different dims and batch sizes --
  as one mixed trainer group; DIR/<task>-s<seed>/progress.csv each.  --checkpoint saves the whole group to
- DIR/checkpoint after every epoch; the same command line with --resume DIR instead of --log_dir DIR continues it)
+ DIR/checkpoint after every epoch; the same command line with --resume DIR instead of --log_dir DIR continues it.
+ --hidden_sweep: the --variants may differ in their hidden sizes, one arch trainer group trains them all;
+ DIR/<task>-h<sizes>-s<seed>/progress.csv each.  --hidden_sizes H1 H2 ...: every variant once per entry, policy and Q
+ nets alike, implies --hidden_sweep)
 Runs the variant unchanged (batch size, lrs, tau, period, buffer size ... from the JSON) on the
 HIP library with a synthetic environment of the task's dimensions (robosuite is not installed)."""
 import argparse
@@ -16,7 +20,7 @@ import sys
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 from robosuite_benchmark_amd.driver import experiment, experiment_group, experiment_sweep  # noqa: E402
 from robosuite_benchmark_amd.group_checkpoint import GroupMismatchError  # noqa: E402
-from robosuite_benchmark_amd.variant import default_variant, load_variant  # noqa: E402
+from robosuite_benchmark_amd.variant import default_variant, expand_hidden_sizes, load_variant  # noqa: E402
 
 if __name__ == "__main__":
     ap = argparse.ArgumentParser()
@@ -40,7 +44,15 @@ if __name__ == "__main__":
     ap.add_argument("--checkpoint", action="store_true",
                     help="with --seeds / --variants and --log_dir DIR: save the whole group to DIR/checkpoint after "
                          "every epoch (only the replay-buffer chunks changed since the last save are written)")
+    ap.add_argument("--hidden_sweep", action="store_true",
+                    help="with --variants: the variants may differ in their hidden sizes (a network-size sweep as one "
+                         "arch trainer group); run names carry the sizes")
+    ap.add_argument("--hidden_sizes", type=str, nargs="+", default=None,
+                    help="with --variants: train every variant once per entry (comma-separated widths, e.g. 256,256 "
+                         "512,512 256,256,256), policy and Q nets alike; implies --hidden_sweep")
     args = ap.parse_args()
+    if (args.hidden_sweep or args.hidden_sizes) and not args.variants:
+        raise SystemExit("--hidden_sweep / --hidden_sizes need --variants")
     if args.variants or args.seeds:
         log_dir = args.resume or args.log_dir
         if args.checkpoint and not log_dir:
@@ -50,7 +62,11 @@ if __name__ == "__main__":
         try:
             if args.variants:
                 seeds = args.seeds or [args.seed]
-                experiment_sweep([(load_variant(v), s) for v in args.variants for s in seeds], **group_kw)
+                variants = [load_variant(v) for v in args.variants]
+                if args.hidden_sizes:
+                    variants = expand_hidden_sizes(variants, args.hidden_sizes)
+                experiment_sweep([(v, s) for v in variants for s in seeds],
+                                 hidden_sweep=bool(args.hidden_sweep or args.hidden_sizes), **group_kw)
             else:
                 variant = load_variant(args.variant) if args.variant else default_variant(
                     env=args.env, seed=args.seeds[0], batch_size=args.batch_size, agent=args.agent)
