@@ -555,20 +555,16 @@ int gen_launch_step(sac_trainer *t, const float *S, const SlotLayout &SL, int j,
     SAC_REQUIRE(SL.off_obs == t->ext_layout.off_obs && SL.off_nobs == t->ext_layout.off_nobs && SL.Bt == g->n,
                 "internal: minibatch slot layout differs from the one the general step was built for");
     g->dev.eps1 = t->dev.eps1; g->dev.eps2 = t->dev.eps2;
-    const double tt = (double)(t->adam_t + 1);
-    StepArg sa{t->n_train_steps_total, t->adam_t + 1, j, 0, 1.0 - std::pow(0.9, tt), std::sqrt(1.0 - std::pow(0.999, tt))};
-    sa.pad2 = t->publish_diag ? 2u : 0u;
+    StepArg sa = step_arg(t->n_train_steps_total, t->adam_t + 1, j, 0, t->publish_diag);
     if (t->algo == 0) {
         if (gen_run_list(t, g->stages, S, SL, sa, (t->n_train_steps_total % g->dev.period) == 0)) return -1;
     } else {
-        const bool pstep = (t->n_train_steps_total % t->td3_period) == 0, actor = pstep || want_stats;
-        const double tp = (double)(t->adam_t_pi + 1);
-        StepArg sp{t->n_train_steps_total, t->adam_t_pi + 1, j, 2, 1.0 - std::pow(0.9, tp), std::sqrt(1.0 - std::pow(0.999, tp))};
-        sp.pad2 = sa.pad2;
+        const Td3Plan P = td3_plan(t, 0, 0, want_stats);
+        const StepArg sp = step_arg(P.step, P.t_pi, j, 2, t->publish_diag);
         sa.pad = 1;
-        if (gen_run_list(t, g->td3_critic, S, SL, sa, pstep)) return -1;
-        if (actor && gen_run_list(t, pstep ? g->td3_actor : g->td3_stats, S, SL, sp, true)) return -1;
-        if (pstep) t->adam_t_pi += 1;
+        if (gen_run_list(t, g->td3_critic, S, SL, sa, P.pstep)) return -1;
+        if (P.actor && gen_run_list(t, P.pstep ? g->td3_actor : g->td3_stats, S, SL, sp, true)) return -1;
+        if (P.pstep) t->adam_t_pi += 1;
     }
     t->n_train_steps_total += 1;
     t->adam_t += 1;

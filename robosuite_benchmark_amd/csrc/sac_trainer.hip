@@ -30,6 +30,7 @@
 #include <algorithm>
 #include <array>
 #include <cmath>
+#include <cstddef>
 #include <cstdlib>
 #include <chrono>
 #include <cstring>
@@ -61,6 +62,17 @@ struct StepArg {
     double bc1, bc2s;              // 1 - beta1^t and sqrt(1 - beta2^t), computed on the host in double like torch
     unsigned seq, pad2;            // fused step: number of this launch (1, 2, ...), the hand-off counters count in units of it
 };
+
+// The one rule for a step's arguments: step number, 1-based optimizer count t of the net(s) the launches train (bc1 / bc2s
+// follow from it), position in the loop call, kind (`pad`: 0 SAC, 1 TD3 critic pass, 2 TD3 actor pass) and whether the
+// step publishes its diagnostics (`pad2` bit 1).  Every step path -- solo, general, grouped -- takes its arguments here:
+// that a group member ends bit for bit where its solo loop would rests on it.
+inline StepArg step_arg(long long step, long long adam_t, int loop_pos, int kind, bool publish) {
+    const double tt = (double)adam_t;
+    StepArg sa{step, adam_t, loop_pos, kind, 1.0 - std::pow(0.9, tt), std::sqrt(1.0 - std::pow(0.999, tt))};
+    sa.pad2 = publish ? 2u : 0u;
+    return sa;
+}
 
 struct Ctl {                       // device-resident state of the entropy coefficient (Adam on log_alpha)
     float log_alpha, a_m, a_v, alpha, alpha_loss;
@@ -1902,6 +1914,20 @@ struct sac_trainer {
     sac_general *gen = nullptr;
 };
 
+// TD3's delayed update for step i of a call, from the trainer's counters in front of the call and the policy steps of
+// the call so far (a solo step has advanced the counters itself: i = 0, none so far).  A policy step every
+// td3_period-th step number; the actor pass also where its statistics are wanted (Policy Loss / Policy Action, no
+// update).  t_q / t_pi: the 1-based optimizer counts of the critics and of the (delayed) policy for step_arg.
+struct Td3Plan {
+    long long step, t_q, t_pi;
+    bool pstep, actor;
+};
+inline Td3Plan td3_plan(const sac_trainer *t, long long i, long long pi_steps, bool want_stats) {
+    const long long step = t->n_train_steps_total + i;
+    const bool pstep = (step % t->td3_period) == 0;
+    return Td3Plan{step, t->adam_t + i + 1, t->adam_t_pi + pi_steps + 1, pstep, pstep || want_stats};
+}
+
 #include "sac_general_host.h"
 
 namespace {
@@ -2022,14 +2048,12 @@ int launch_step_td3(sac_trainer *t, const float *S, const SlotLayout &SL, int j,
     const Dev &d = t->dev;
     hipStream_t s = t->stream;
     const int NB = t->NB, SPv = t->SP;
-    const bool pstep = (t->n_train_steps_total % t->td3_period) == 0;
-    const bool actor = pstep || want_stats;
-    const double tq = (double)(t->adam_t + 1), tp = (double)(t->adam_t_pi + 1);
-    StepArg sq{t->n_train_steps_total, t->adam_t + 1, j, 1, 1.0 - std::pow(0.9, tq), std::sqrt(1.0 - std::pow(0.999, tq))};
-    StepArg sp{t->n_train_steps_total, t->adam_t_pi + 1, j, 2, 1.0 - std::pow(0.9, tp), std::sqrt(1.0 - std::pow(0.999, tp))};
+    const Td3Plan P = td3_plan(t, 0, 0, want_stats);
+    const bool pstep = P.pstep, actor = P.actor;
     // (the diagnostics -- and the flat gradient copies of sac_debug_fetch -- go out only on the steps whose caller reads
     //  them, like the SAC step's; td3_diagnostics keeps "last" the most recent value of each entry across launches)
-    sq.pad2 = sp.pad2 = t->publish_diag ? 2u : 0u;
+    StepArg sq = step_arg(P.step, P.t_q, j, 1, t->publish_diag);
+    const StepArg sp = step_arg(P.step, P.t_pi, j, 2, t->publish_diag);
     if (t->fused) {
         // the critic pass as ONE launch (k_abc<.., M_TD3_CRITIC>, sac_fused.h) + its weight-gradient launch
         if (launch_fused_abc(t, S, SL, sq, actor ? 4u : 0u)) return -1;
@@ -2066,9 +2090,7 @@ int launch_step(sac_trainer *t, const float *S, const SlotLayout &SL, int j, hip
     const Dev &d = t->dev;
     hipStream_t s = t->stream;
     const int NB = t->NB;
-    const double tt = (double)(t->adam_t + 1);
-    StepArg sa{t->n_train_steps_total, t->adam_t + 1, j, 0, 1.0 - std::pow(0.9, tt), std::sqrt(1.0 - std::pow(0.999, tt))};
-    sa.pad2 = t->publish_diag ? 2u : 0u;
+    StepArg sa = step_arg(t->n_train_steps_total, t->adam_t + 1, j, 0, t->publish_diag);
     const int SPv = t->SP;
     if (ev) SAC_HIP(hipEventRecord(ev[0], s));
     if (t->fused) {
@@ -3414,850 +3436,6 @@ int sac_policy_act(sac_trainer_t *t, const float *obs, int deterministic, const 
     return 0;
 }
 
-// ==========================================================================================
-// Trainer groups: R SAC trainers of one shape stepped together, four grouped launches per step (see GroupMember) -- or R
-// TD3 trainers (td3_group_create), launch_step_td3's four to seven launches per step, each one grouped.  A mixed group
-// (sac_group_create_mixed / td3_group_create_mixed) takes members of different dims and batches: each launch A, B, C is
-// issued once per variant class (GroupClass), the weight-gradient launch once for all; draws take each member's batch,
-// gathers go one launch per NIT class.
-// The loop is sac_train_loop's for every member at once -- same index stream per buffer, same steps, same results bit
-// for bit -- without its latency devices (no speculative next chunk, no stepwise read-ahead): chunks of LOOP_CH steps
-// alternate between the two halves of each buffer's loop slots; the draws and gathers of a chunk run on the group's
-// second stream under the steps of the previous one (unless the device's fused-launch gate is live -- another fused
-// trainer or group on the device, fused members included: then every grouped launch, draws and gathers too, is
-// serialised behind the gate's last launch, at a cost of ~0.3 ms per 256-step chunk).
-// ==========================================================================================
-// One variant class of a group: the members whose step runs the same instances of the grouped kernels (the class is a
-// contiguous range of the device tables), the largest x-extent and dynamic LDS among them.  A group of one shape is one
-// class; a mixed group (sac_group_create_mixed) has up to four, one grouped launch each per step kernel.
-struct GroupClass {
-    int lo = 0, n = 0;                                // device table entries lo .. lo + n - 1
-    int xa = 0, xb = 0, xc = 0, xpi = 0;              // the largest member extent (GroupMember::xa ..)
-    size_t lds_fa = 0, lds_fb = 0, lds_bw = 0;        // the largest member LDS
-    void (*fa)(const GroupMember *, const StepArg *, int) = nullptr;
-    void (*fb)(const GroupMember *, const StepArg *, int) = nullptr;
-    void (*bw)(const GroupMember *, const StepArg *, int, int) = nullptr;
-    // TD3: critic pass (launches A, B, C) and actor pass (B, C)
-    void (*fa3)(const GroupMember *, const Td3GroupStep *, int) = nullptr;
-    void (*fb3)(const GroupMember *, const Td3GroupStep *, int) = nullptr, (*fb3a)(const GroupMember *, const Td3GroupStep *, int) = nullptr;
-    void (*bw3)(const GroupMember *, const Td3GroupStep *, int, int) = nullptr, (*bw3a)(const GroupMember *, const Td3GroupStep *, int, int) = nullptr;
-    int ma = 0;                                       // MLP groups: the action bound of the class's elementwise kernels (8 / 16)
-};
-
-// One grouped launch of an MLP group's step (sac_group_create_mlp): stage `kind` (GS_*) of the members' general-step
-// launch list.  GS_GEMM: the members' stage headers are hdr[stage R .. stage R + R - 1] of the header table; `map` is the
-// block -> member prefix table, `grid` the sum of the members' own grids.  The elementwise kernels go once per variant
-// class (fn[c] on the class's largest x-extent gx[c]) -- or, the kernels without an action bound, once for all (fn[0], gx[0]).
-typedef void (*GenSmallFn)(const gen::GenMember *, const gen::GenGroupStep *, int, int);
-struct GroupGenStage {
-    int kind = 0, mode = 0, sel = 0, list = 0;        // GS_* and its mode; gen::GSEL_*; TD3: 0 the critic pass, 1 the actor pass
-    int hdr = 0, grid = 0;
-    gen::GemmGroupMap map{};
-    bool per_class = false;
-    GenSmallFn fn[4] = {};
-    int gx[4] = {};
-};
-
-struct sac_group {
-    int R = 0, device = 0, algo = 0;                  // algo: 0 SAC, 1 TD3 (every member's)
-    bool mixed = false;                               // sac_group_create_mixed / td3_group_create_mixed
-    bool mlp = false;                                 // sac_group_create_mlp / td3_group_create_mlp (general-step members)
-    sac_trainer *m[SAC_GROUP_MAX] = {};
-    int ord[SAC_GROUP_MAX] = {};                      // device table entry k (member and step tables) is member ord[k]
-    int ncls = 0;
-    GroupClass cls[4];
-    int grid_d = 0, grid_dq = 0, grid_dpi = 0;        // k_dw_adam_group: the largest njobs + 1 (SAC; TD3 critic / policy)
-    hipStream_t s = nullptr, s2 = nullptr;           // steps / draws + gathers
-    hipEvent_t ev_ready[2] = {}, ev_done[2] = {}, ev_copied[2] = {}, ev_end = nullptr;
-    hipEvent_t ev_in[2 * SAC_GROUP_MAX] = {};         // the members' and the buffers' streams in front of a call
-    char *d_tab = nullptr, *h_tab = nullptr;          // device tables and their pinned host images
-    GroupMember *d_mem = nullptr, *h_mem = nullptr;   // [R] (device order)
-    SampleMember *d_smp = nullptr, *h_smp = nullptr;  // [2 halves][R] (member order)
-    GatherMember *d_gat = nullptr, *h_gat = nullptr;  // [2 halves][R] (sorted by gather class, per call)
-    StepArg *d_sa = nullptr, *h_sa = nullptr;         // SAC: [2 halves][LOOP_CH steps][R] (device order)
-    Td3GroupStep *d_ts = nullptr, *h_ts = nullptr;    // TD3: [2 halves][LOOP_CH steps][R] (device order)
-    // MLP groups: the grouped stage list, the members' GEMM stage headers [GEMM stage][R] (written at creation), the member
-    // table [R] and the step table [2 halves][LOOP_CH steps][R] (device order)
-    std::vector<GroupGenStage> gst;
-    gen::GemmStage *d_hdr = nullptr;
-    gen::GenMember *d_gm = nullptr, *h_gm = nullptr;
-    gen::GenGroupStep *d_gs = nullptr, *h_gs = nullptr;
-};
-
-static void group_free(sac_group *g) {
-    if (g->s) (void)hipStreamSynchronize(g->s);
-    if (g->s2) (void)hipStreamSynchronize(g->s2);
-    for (auto &e : g->ev_ready) if (e) (void)hipEventDestroy(e);
-    for (auto &e : g->ev_done) if (e) (void)hipEventDestroy(e);
-    for (auto &e : g->ev_copied) if (e) (void)hipEventDestroy(e);
-    for (auto &e : g->ev_in) if (e) (void)hipEventDestroy(e);
-    if (g->ev_end) (void)hipEventDestroy(g->ev_end);
-    if (g->d_tab) (void)hipFree(g->d_tab);
-    if (g->d_hdr) (void)hipFree(g->d_hdr);
-    if (g->h_tab) (void)hipHostFree(g->h_tab);
-    if (g->s) (void)hipStreamDestroy(g->s);
-    if (g->s2) (void)hipStreamDestroy(g->s2);
-    delete g;
-}
-
-// what a member must be (checked at creation and again in front of every call: a member may have been confined since)
-static int group_member_ok(const sac_trainer *t, int i, int algo, bool mlp = false) {
-    if (algo == 0) SAC_REQUIRE(t->algo == 0, "trainer group member %d is a TD3 trainer: groups hold SAC trainers only", i);
-    else SAC_REQUIRE(t->algo == 1, "trainer group member %d is a SAC trainer: TD3 groups hold TD3 trainers only", i);
-    if (mlp) {
-        SAC_REQUIRE(t->gen, "trainer group member %d has the shapes of the fused kernels (two hidden layers of at most 256 "
-                    "units): MLP groups take general-step members only", i);
-        SAC_REQUIRE(t->xcd_mask == 0xffu, "trainer group member %d is confined to XCDs (sac_trainer_set_xcd[_mask]): a group "
-                    "spans the whole chip", i);
-        return 0;
-    }
-    SAC_REQUIRE(!t->gen, "trainer group member %d runs the general step (hidden sizes beyond two layers of at most 256 units): "
-                "groups take the shapes of the fused kernels only", i);
-    SAC_REQUIRE(t->Bt <= 256, "trainer group member %d has batch %d: groups take batches of at most 256 rows", i, t->Bt);
-    SAC_REQUIRE(t->xcd_mask == 0xffu, "trainer group member %d is confined to XCDs (sac_trainer_set_xcd[_mask]): a group spans "
-                "the whole chip", i);
-    SAC_REQUIRE(t->SP == 4 && !t->chain && !t->bwd8, "trainer group member %d runs column split %d: groups take the "
-                "default split 4 only", i, t->SP);
-    return 0;
-}
-
-// a member's solo x-extents (launch_step / launch_step_td3 at split 4; k_bwd is compact for every batch <= 256)
-static void member_extents(const sac_trainer *t, int algo, int &xa, int &xb, int &xc, int &xpi) {
-    const int SPv = 4, NB = t->NB;
-    xa = 4 * SPv * NB;
-    if (algo == 0) { xb = xc = 4 * SPv * NB; xpi = 0; }
-    else { xb = xc = 8 * ((SPv * NB + 3) / 4); xpi = SPv * NB; }
-}
-
-// a group's tables (device, with their pinned host images: members b_mem | draws | gathers | steps b_sa), its two streams,
-// its events, and its tenancy of the device's fused-launch gate
-static int group_tables(sac_group *g, size_t b_mem, size_t b_sa) {
-    const int R = g->R;
-    const size_t b_smp = sizeof(SampleMember) * 2 * R, b_gat = sizeof(GatherMember) * 2 * R;
-    const size_t o_smp = (b_mem + 255) & ~(size_t)255, o_gat = o_smp + ((b_smp + 255) & ~(size_t)255);
-    const size_t o_sa = o_gat + ((b_gat + 255) & ~(size_t)255), total = o_sa + b_sa;
-    if (hipMalloc(reinterpret_cast<void **>(&g->d_tab), total) != hipSuccess ||
-        hipHostMalloc(reinterpret_cast<void **>(&g->h_tab), total, hipHostMallocDefault) != hipSuccess ||
-        hipStreamCreateWithFlags(&g->s, hipStreamNonBlocking) != hipSuccess ||
-        hipStreamCreateWithFlags(&g->s2, hipStreamNonBlocking) != hipSuccess) {
-        sac::set_error("out of device or pinned host memory for a trainer group");
-        return -1;
-    }
-    for (int k = 0; k < 2; ++k)
-        if (hipEventCreateWithFlags(&g->ev_ready[k], hipEventDisableTiming) != hipSuccess ||
-            hipEventCreateWithFlags(&g->ev_done[k], hipEventDisableTiming) != hipSuccess ||
-            hipEventCreateWithFlags(&g->ev_copied[k], hipEventDisableTiming) != hipSuccess) {
-            sac::set_error("hipEventCreate failed");
-            return -1;
-        }
-    for (auto &e : g->ev_in)
-        if (hipEventCreateWithFlags(&e, hipEventDisableTiming) != hipSuccess) { sac::set_error("hipEventCreate failed"); return -1; }
-    if (hipEventCreateWithFlags(&g->ev_end, hipEventDisableTiming) != hipSuccess) { sac::set_error("hipEventCreate failed"); return -1; }
-    if (g->mlp) { g->d_gm = reinterpret_cast<gen::GenMember *>(g->d_tab); g->h_gm = reinterpret_cast<gen::GenMember *>(g->h_tab); }
-    else { g->d_mem = reinterpret_cast<GroupMember *>(g->d_tab); g->h_mem = reinterpret_cast<GroupMember *>(g->h_tab); }
-    g->d_smp = reinterpret_cast<SampleMember *>(g->d_tab + o_smp); g->h_smp = reinterpret_cast<SampleMember *>(g->h_tab + o_smp);
-    g->d_gat = reinterpret_cast<GatherMember *>(g->d_tab + o_gat); g->h_gat = reinterpret_cast<GatherMember *>(g->h_tab + o_gat);
-    if (g->mlp) { g->d_gs = reinterpret_cast<gen::GenGroupStep *>(g->d_tab + o_sa); g->h_gs = reinterpret_cast<gen::GenGroupStep *>(g->h_tab + o_sa); }
-    else if (g->algo == 0) { g->d_sa = reinterpret_cast<StepArg *>(g->d_tab + o_sa); g->h_sa = reinterpret_cast<StepArg *>(g->h_tab + o_sa); }
-    else { g->d_ts = reinterpret_cast<Td3GroupStep *>(g->d_tab + o_sa); g->h_ts = reinterpret_cast<Td3GroupStep *>(g->h_tab + o_sa); }
-    {   // a tenant of the device's fused-launch gate: no fused trainer's launch may overlap the group's grids
-        FusedGate &G = g_gate[g->device & 63];
-        std::lock_guard<std::mutex> lk(G.mu);
-        if (!G.ev && hipEventCreateWithFlags(&G.ev, hipEventDisableTiming) != hipSuccess) {
-            sac::set_error("hipEventCreate failed");
-            return -1;
-        }
-        G.live += 1;
-    }
-    return 0;
-}
-
-static int group_create(sac_group_t **out, sac_trainer_t *const *members, int n_members, int algo, bool mixed) {
-    const char *fname = mixed ? (algo ? "td3_group_create_mixed" : "sac_group_create_mixed")
-                              : (algo ? "td3_group_create" : "sac_group_create");
-    SAC_REQUIRE(out && members, "null argument to %s", fname);
-    *out = nullptr;
-    SAC_REQUIRE(n_members >= 1 && n_members <= SAC_GROUP_MAX, "a trainer group holds 1..%d members (got %d)", SAC_GROUP_MAX,
-                n_members);
-    const sac_trainer *t0 = members[0];
-    for (int i = 0; i < n_members; ++i) {
-        const sac_trainer *t = members[i];
-        SAC_REQUIRE(t != nullptr, "trainer group member %d is null", i);
-        for (int j = 0; j < i; ++j)
-            SAC_REQUIRE(members[j] != t, "trainer group members %d and %d are the same trainer", j, i);
-        if (group_member_ok(t, i, algo)) return -1;
-        if (!mixed) {
-            SAC_REQUIRE(t->O == t0->O && t->A == t0->A, "trainer group member %d has dims (%d,%d), member 0 (%d,%d)", i, t->O,
-                        t->A, t0->O, t0->A);
-            SAC_REQUIRE(t->Bt == t0->Bt, "trainer group member %d has batch %d, member 0 %d", i, t->Bt, t0->Bt);
-        }
-        SAC_REQUIRE(t->HP[0] == t0->HP[0] && t->HP[1] == t0->HP[1] && t->HQ[0] == t0->HQ[0] && t->HQ[1] == t0->HQ[1],
-                    "trainer group member %d has hidden sizes policy [%d,%d] qf [%d,%d], member 0 policy [%d,%d] qf [%d,%d]", i,
-                    t->HP[0], t->HP[1], t->HQ[0], t->HQ[1], t0->HP[0], t0->HP[1], t0->HQ[0], t0->HQ[1]);
-        SAC_REQUIRE(t->device == t0->device, "trainer group member %d lives on device %d, member 0 on %d", i, t->device, t0->device);
-        if (!mixed)
-            SAC_REQUIRE(t->fwd_a == t0->fwd_a && t->dw.njobs == t0->dw.njobs, "trainer group member %d runs another kernel "
-                        "variant than member 0", i);
-        SAC_REQUIRE(t->A <= 16 && 3 * 4 * t->NB <= 192, "trainer group member %d: act_dim %d / batch %d outside the grouped "
-                    "kernels", i, t->A, t->Bt);
-    }
-    SAC_HIP(hipSetDevice(t0->device));
-    sac_group *g = new sac_group();
-    g->R = n_members;
-    g->device = t0->device;
-    g->algo = algo;
-    g->mixed = mixed;
-    for (int i = 0; i < n_members; ++i) g->m[i] = members[i];
-    auto fail = [&](int rc) { group_free(g); return rc; };
-    // the variant classes (the instance of launch A a member's own four-launch step runs), in order of first appearance;
-    // the device tables hold them one after another, each in member order
-    const void *key[4] = {};
-    for (int i = 0; i < n_members; ++i) {
-        const void *k = reinterpret_cast<const void *>(members[i]->fwd_a);
-        int c = 0;
-        while (c < g->ncls && key[c] != k) ++c;
-        if (c == g->ncls) {
-            if (g->ncls == 4) { sac::set_error("internal: more than four kernel variants in a trainer group"); return fail(-1); }
-            key[g->ncls++] = k;
-        }
-    }
-    int pos = 0;
-    for (int c = 0; c < g->ncls; ++c) {
-        GroupClass &K = g->cls[c];
-        K.lo = pos;
-        for (int i = 0; i < n_members; ++i) {
-            const sac_trainer *t = members[i];
-            if (reinterpret_cast<const void *>(t->fwd_a) != key[c]) continue;
-            g->ord[pos++] = i;
-            int xa, xb, xc, xpi;
-            member_extents(t, algo, xa, xb, xc, xpi);
-            K.xa = std::max(K.xa, xa); K.xb = std::max(K.xb, xb); K.xc = std::max(K.xc, xc); K.xpi = std::max(K.xpi, xpi);
-            K.lds_fa = std::max(K.lds_fa, t->lds_fa); K.lds_fb = std::max(K.lds_fb, t->lds_fb);
-            K.lds_bw = std::max(K.lds_bw, t->lds_bw);
-        }
-        K.n = pos - K.lo;
-        const sac_trainer *tc = members[g->ord[K.lo]];
-        // the grouped instance of the variant the class's own four-launch step runs
-#define SAC_GROUP_PICK(NTH, W)                                                                             \
-        if (tc->fwd_a == &k_fwd_a<NTH, W, 4>) {                                                            \
-            K.fa = &k_fwd_a_group<NTH, W, 4>; K.fb = &k_fwd_b_group<NTH, W, 4>; K.bw = &k_bwd_group<NTH, 4>; \
-        }
-#define TD3_GROUP_PICK(W)                                                                                  \
-        if (tc->fwd_a == &k_fwd_a<1, W, 4, M_TD3_CRITIC>) {                                                \
-            K.fa3 = &k_fwd_a_group<1, W, 4, M_TD3_CRITIC>;                                                 \
-            K.fb3 = &k_fwd_b_group<1, W, 4, M_TD3_CRITIC>; K.fb3a = &k_fwd_b_group<1, W, 4, M_TD3_ACTOR>;   \
-            K.bw3 = &k_bwd_group<1, 4, M_TD3_CRITIC>; K.bw3a = &k_bwd_group<1, 4, M_TD3_ACTOR>;             \
-        }
-        if (algo == 0) {
-            SAC_GROUP_PICK(1, false) else SAC_GROUP_PICK(1, true) else SAC_GROUP_PICK(2, false) else SAC_GROUP_PICK(2, true)
-        } else {
-            TD3_GROUP_PICK(false) else TD3_GROUP_PICK(true)
-        }
-#undef SAC_GROUP_PICK
-#undef TD3_GROUP_PICK
-        if (!K.fa && !K.fa3) { sac::set_error("internal: no grouped instance of the members' step kernels"); return fail(-1); }
-        auto set_lds = [](const void *fn, size_t bytes) {
-            return (!fn || bytes <= 64 * 1024) ? hipSuccess : hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)bytes);
-        };
-        auto fn = [](auto f) { return reinterpret_cast<const void *>(f); };
-        if (set_lds(fn(K.fa), K.lds_fa) != hipSuccess || set_lds(fn(K.fb), K.lds_fb) != hipSuccess ||
-            set_lds(fn(K.bw), K.lds_bw) != hipSuccess || set_lds(fn(K.fa3), K.lds_fa) != hipSuccess ||
-            set_lds(fn(K.fb3), K.lds_fb) != hipSuccess || set_lds(fn(K.fb3a), K.lds_fb) != hipSuccess ||
-            set_lds(fn(K.bw3), K.lds_bw) != hipSuccess || set_lds(fn(K.bw3a), K.lds_bw) != hipSuccess) {
-            sac::set_error("hipFuncSetAttribute failed for the grouped step kernels");
-            return fail(-1);
-        }
-    }
-    for (int i = 0; i < n_members; ++i) {
-        const sac_trainer *t = members[i];
-        g->grid_d = std::max(g->grid_d, t->dw.njobs + 1);
-        g->grid_dq = std::max(g->grid_dq, std::max(t->dw_q.njobs, t->dw_q_tp.njobs) + 1);
-        g->grid_dpi = std::max(g->grid_dpi, t->dw_pi.njobs + 1);
-    }
-    const int R = n_members;
-    if (group_tables(g, sizeof(GroupMember) * R, (algo ? sizeof(Td3GroupStep) : sizeof(StepArg)) * 2 * LOOP_CH * R)) return fail(-1);
-    *out = g;
-    return 0;
-}
-
-// the grouped instance of an elementwise stage of the general step (ma: the class's action bound; 0: a kernel without one)
-static GenSmallFn gen_small_fn(int kind, int ma) {
-#define GEN_SMALL(K) (ma == 16 ? &gen::k_g_small_group<gen::K, 16> : &gen::k_g_small_group<gen::K, 8>)
-    switch (kind) {
-    case GS_HEAD: return GEN_SMALL(GK_HEAD);
-    case GS_POLGRAD: return GEN_SMALL(GK_POLGRAD);
-    case GS_TD3_HEAD: return GEN_SMALL(GK_TD3_HEAD);
-    case GS_TD3_AHEAD: return GEN_SMALL(GK_TD3_AHEAD);
-    case GS_TD3_POLGRAD: return GEN_SMALL(GK_TD3_POLGRAD);
-    case GS_LOSS: return &gen::k_g_small_group<gen::GK_LOSS, 0>;
-    case GS_DIAG: return &gen::k_g_small_group<gen::GK_DIAG, 0>;
-    case GS_TD3_LOSS: return &gen::k_g_small_group<gen::GK_TD3_LOSS, 0>;
-    case GS_TD3_QA: return &gen::k_g_small_group<gen::GK_TD3_QA, 0>;
-    }
-#undef GEN_SMALL
-    return nullptr;
-}
-
-// an elementwise stage's x-extent for a member of batch n (gen_run_list's grid)
-static int gen_small_extent(int kind, int n) {
-    switch (kind) {
-    case GS_HEAD: return (2 * n + gen::GRW - 1) / gen::GRW;
-    case GS_LOSS: case GS_TD3_LOSS: case GS_TD3_QA: return n;
-    case GS_DIAG: return 1;
-    default: return (n + gen::GRW - 1) / gen::GRW;
-    }
-}
-
-// A member's launch list as a skeleton: its plain (elementwise) stages in order, and in front of each of them -- and
-// behind the last -- its GEMM stages as three equal-mode sub-runs in the fixed order forward (0), backward (1), weight
-// gradients (2), each in list order; a sub-run may be empty (e.g. no backward launch of the policy at Lp = 1).  false:
-// the list does not have that form (a GEMM stage of a lower mode behind a higher one in the same gap).
-struct GenSkeleton {
-    std::vector<int> plain;                                    // list indices of the plain stages
-    std::vector<std::array<std::vector<int>, 3>> runs;        // runs[p][mode]: list indices in front of plain stage p
-};
-static bool gen_skeleton(const std::vector<GenStage> &L, GenSkeleton &S) {
-    S.plain.clear();
-    S.runs.assign(1, {});
-    int last = 0;
-    for (size_t k = 0; k < L.size(); ++k) {
-        if (L[k].kind != GS_GEMM) {
-            S.plain.push_back((int)k);
-            S.runs.emplace_back();
-            last = 0;
-            continue;
-        }
-        if (L[k].mode < last || L[k].mode > 2) return false;
-        last = L[k].mode;
-        S.runs.back()[L[k].mode].push_back((int)k);
-    }
-    return true;
-}
-
-// MLP groups (members of the general step with one set of hidden sizes) and arch groups (arch: any hidden sizes of the
-// general step).  Both walk the merged schedule of the members' launch lists: the plain stages in order, every member in
-// each; at each GEMM sub-run the largest count over the members of grouped launches, member m in the first count_m of
-// them and with zero blocks in the rest.  Each member thus runs its own stages in its own order, each with its own
-// header (jobs, tiles, split factor, scratch, counters): what its solo launch list runs.  Members of one set of hidden
-// sizes have one list shape, and the merged schedule is their list.
-static int group_create_mlp(sac_group_t **out, sac_trainer_t *const *members, int n_members, int algo, bool arch) {
-    const char *fname = arch ? (algo ? "td3_group_create_arch" : "sac_group_create_arch")
-                             : (algo ? "td3_group_create_mlp" : "sac_group_create_mlp");
-    SAC_REQUIRE(out && members, "null argument to %s", fname);
-    *out = nullptr;
-    SAC_REQUIRE(n_members >= 1 && n_members <= SAC_GROUP_MAX, "a trainer group holds 1..%d members (got %d)", SAC_GROUP_MAX,
-                n_members);
-    const sac_trainer *t0 = members[0];
-    for (int i = 0; i < n_members; ++i) {
-        const sac_trainer *t = members[i];
-        SAC_REQUIRE(t != nullptr, "trainer group member %d is null", i);
-        for (int j = 0; j < i; ++j)
-            SAC_REQUIRE(members[j] != t, "trainer group members %d and %d are the same trainer", j, i);
-        if (group_member_ok(t, i, algo, true)) return -1;
-        if (!arch) {
-            const sac_general *a = t->gen, *b = t0->gen;
-            bool same = a->Lp == b->Lp && a->Lq == b->Lq;
-            for (int l = 0; same && l < a->Lp; ++l) same = a->hp[l] == b->hp[l];
-            for (int l = 0; same && l < a->Lq; ++l) same = a->hq[l] == b->hq[l];
-            SAC_REQUIRE(same, "trainer group member %d has other hidden sizes than member 0 (an MLP group shares them)", i);
-        }
-        SAC_REQUIRE(t->device == t0->device, "trainer group member %d lives on device %d, member 0 on %d", i, t->device, t0->device);
-    }
-    // the members' launch lists (SAC: the step; TD3: the critic pass, then the actor pass, whose statistics-only form is
-    // its head up to the Q1 last layer), each as its skeleton: one sequence of plain stages for all of them (same
-    // algorithm), checked, not assumed
-    auto lists_of = [algo](const sac_trainer *t) {
-        std::vector<const std::vector<GenStage> *> L;
-        if (algo == 0) L.push_back(&t->gen->stages);
-        else { L.push_back(&t->gen->td3_critic); L.push_back(&t->gen->td3_actor); }
-        return L;
-    };
-    const size_t nlists = lists_of(t0).size();
-    std::vector<std::vector<GenSkeleton>> sk(nlists, std::vector<GenSkeleton>((size_t)n_members));   // [list][member]
-    for (int i = 0; i < n_members; ++i) {
-        const auto L = lists_of(members[i]);
-        for (size_t q = 0; q < nlists; ++q) {
-            SAC_REQUIRE(gen_skeleton(*L[q], sk[q][(size_t)i]), "internal: trainer group member %d has a launch list whose "
-                        "GEMM stages are out of mode order", i);
-            const GenSkeleton &a = sk[q][(size_t)i], &b = sk[q][0];
-            bool same = a.plain.size() == b.plain.size();
-            for (size_t k = 0; same && k < a.plain.size(); ++k) {
-                const GenStage &x = (*L[q])[(size_t)a.plain[k]], &y = (*lists_of(t0)[q])[(size_t)b.plain[k]];
-                same = x.kind == y.kind && x.mode == y.mode;
-            }
-            SAC_REQUIRE(same, "internal: trainer group member %d has another sequence of elementwise stages than member 0", i);
-        }
-    }
-    SAC_HIP(hipSetDevice(t0->device));
-    sac_group *g = new sac_group();
-    g->R = n_members;
-    g->device = t0->device;
-    g->algo = algo;
-    g->mlp = true;
-    for (int i = 0; i < n_members; ++i) g->m[i] = members[i];
-    auto fail = [&](int rc) { group_free(g); return rc; };
-    const int R = n_members;
-    // variant classes: the elementwise kernels' action bound (up to 8 actions, up to 16), each class in member order
-    int pos = 0;
-    for (int ma : {8, 16}) {
-        GroupClass &K = g->cls[g->ncls];
-        K.lo = pos; K.ma = ma;
-        for (int i = 0; i < n_members; ++i)
-            if ((members[i]->A <= 8) == (ma == 8)) g->ord[pos++] = i;
-        K.n = pos - K.lo;
-        if (K.n > 0) g->ncls += 1;
-    }
-    // the merged schedule and the GEMM stages' headers, [grouped GEMM stage][device member]; a member without a stage in
-    // a grouped GEMM launch gets an inert header (no tiles, never read: it owns no block of that launch)
-    std::vector<gen::GemmStage> hdr;
-    gen::GemmStage inert;
-    memset(&inert, 0, sizeof(inert));
-    inert.splitk = 1;
-    for (size_t li = 0; li < nlists; ++li) {
-        const std::vector<GenStage> &L0 = *lists_of(t0)[li];
-        const GenSkeleton &S0 = sk[li][0];
-        bool past_qa = false;
-        // TD3's actor pass: every member with `actor` up to Q1's last layer (whose backward half follows pstep), the
-        // policy's backward pass and update for members on a policy step, the statistics behind them for all of `actor`
-        auto sel_of = [&](int kind) {
-            return li == 0 ? gen::GSEL_ALL : ((past_qa && kind != GS_DIAG) ? gen::GSEL_PSTEP : gen::GSEL_ACTOR);
-        };
-        for (size_t p = 0; p < S0.runs.size(); ++p) {
-            for (int mode = 0; mode < 3; ++mode) {
-                size_t cnt = 0;
-                for (int d = 0; d < R; ++d) cnt = std::max(cnt, sk[li][(size_t)g->ord[d]].runs[p][(size_t)mode].size());
-                for (size_t c = 0; c < cnt; ++c) {
-                    GroupGenStage st;
-                    st.kind = GS_GEMM; st.mode = mode; st.list = (int)li; st.sel = sel_of(GS_GEMM);
-                    st.hdr = (int)(hdr.size() / R);
-                    int at = 0;
-                    for (int q = 0; q <= SAC_GROUP_MAX; ++q) st.map.start[q] = 1 << 30;
-                    for (int d = 0; d < R; ++d) {
-                        const sac_trainer *t = members[g->ord[d]];
-                        const std::vector<int> &run = sk[li][(size_t)g->ord[d]].runs[p][(size_t)mode];
-                        gen::GemmStage gs = inert;
-                        if (c < run.size()) {
-                            gs = (*lists_of(t)[li])[(size_t)run[c]].gs;
-                            gs.tau = t->gen->dev.tau;      // (gen_run_list sets it per launch; the rest per step, in the kernel)
-                        }
-                        hdr.push_back(gs);
-                        st.map.start[d] = at;
-                        at += gs.ntiles * gs.splitk;
-                    }
-                    st.map.sel = st.sel;
-                    st.grid = at;
-                    g->gst.push_back(st);
-                }
-            }
-            if (p == S0.plain.size()) break;
-            const GenStage &s0 = L0[(size_t)S0.plain[p]];
-            GroupGenStage st;
-            st.kind = s0.kind; st.mode = s0.mode; st.list = (int)li; st.sel = sel_of(s0.kind);
-            if (s0.kind == GS_TD3_QA) past_qa = true;
-            st.per_class = s0.kind == GS_HEAD || s0.kind == GS_POLGRAD || s0.kind == GS_TD3_HEAD || s0.kind == GS_TD3_AHEAD ||
-                           s0.kind == GS_TD3_POLGRAD;
-            for (int c = 0; c < (st.per_class ? g->ncls : 1); ++c) {
-                const int lo = st.per_class ? g->cls[c].lo : 0, hi = st.per_class ? lo + g->cls[c].n : R;
-                st.fn[c] = gen_small_fn(s0.kind, st.per_class ? g->cls[c].ma : 0);
-                for (int d = lo; d < hi; ++d) st.gx[c] = std::max(st.gx[c], gen_small_extent(s0.kind, members[g->ord[d]]->Bt));
-            }
-            g->gst.push_back(st);
-        }
-    }
-    if (hipMalloc(reinterpret_cast<void **>(&g->d_hdr), sizeof(gen::GemmStage) * hdr.size()) != hipSuccess ||
-        hipMemcpy(g->d_hdr, hdr.data(), sizeof(gen::GemmStage) * hdr.size(), hipMemcpyHostToDevice) != hipSuccess) {
-        sac::set_error("out of device memory for a trainer group");
-        return fail(-1);
-    }
-    if (group_tables(g, sizeof(gen::GenMember) * R, sizeof(gen::GenGroupStep) * 2 * LOOP_CH * R)) return fail(-1);
-    *out = g;
-    return 0;
-}
-
-int sac_group_create(sac_group_t **out, sac_trainer_t *const *members, int n_members) {
-    return group_create(out, members, n_members, 0, false);
-}
-
-int td3_group_create(sac_group_t **out, sac_trainer_t *const *members, int n_members) {
-    return group_create(out, members, n_members, 1, false);
-}
-
-int sac_group_create_mixed(sac_group_t **out, sac_trainer_t *const *members, int n_members) {
-    return group_create(out, members, n_members, 0, true);
-}
-
-int td3_group_create_mixed(sac_group_t **out, sac_trainer_t *const *members, int n_members) {
-    return group_create(out, members, n_members, 1, true);
-}
-
-int sac_group_create_mlp(sac_group_t **out, sac_trainer_t *const *members, int n_members) {
-    return group_create_mlp(out, members, n_members, 0, false);
-}
-
-int td3_group_create_mlp(sac_group_t **out, sac_trainer_t *const *members, int n_members) {
-    return group_create_mlp(out, members, n_members, 1, false);
-}
-
-int sac_group_create_arch(sac_group_t **out, sac_trainer_t *const *members, int n_members) {
-    return group_create_mlp(out, members, n_members, 0, true);
-}
-
-int td3_group_create_arch(sac_group_t **out, sac_trainer_t *const *members, int n_members) {
-    return group_create_mlp(out, members, n_members, 1, true);
-}
-
-int sac_group_stage_count(const sac_group_t *g) {
-    SAC_REQUIRE(g, "null argument to sac_group_stage_count");
-    if (g->mlp) return (int)g->gst.size();
-    return g->algo == 0 ? 4 : 7;                      // (the four-launch step; TD3: A, B, C, dW of the critic pass, B, C, dW of the actor pass)
-}
-
-int sac_group_destroy(sac_group_t *g) {
-    if (!g) return 0;
-    (void)hipSetDevice(g->device);
-    if (g->s) (void)hipStreamSynchronize(g->s);
-    {
-        FusedGate &G = g_gate[g->device & 63];
-        std::lock_guard<std::mutex> lk(G.mu);
-        G.live -= 1;
-        if (G.last == g->s || G.last == g->s2) G.last = nullptr;
-    }
-    group_free(g);
-    return 0;
-}
-
-int sac_group_train_loop(sac_group_t *g, sac_buffer_t *const *bufs, int64_t n_steps, float *diag_first, float *diag_last) {
-    SAC_REQUIRE(g && bufs && n_steps > 0 && n_steps < (1 << 30), "bad arguments to sac_group_train_loop");
-    const int R = g->R;
-    const sac_trainer *t0 = g->m[0];
-    // every refusal comes before anything changes
-    for (int r = 0; r < R; ++r) {
-        if (group_member_ok(g->m[r], r, g->algo, g->mlp)) return -1;
-        const sac_buffer *b = bufs[r];
-        SAC_REQUIRE(b != nullptr, "trainer group buffer %d is null", r);
-        for (int q = 0; q < r; ++q) SAC_REQUIRE(bufs[q] != b, "trainer group buffers %d and %d are the same buffer", q, r);
-        SAC_REQUIRE(b->device == g->device, "trainer group buffer %d lives on device %d, the group on %d", r, b->device, g->device);
-        if (g->mixed || g->mlp) {
-            const sac_trainer *t = g->m[r];
-            SAC_REQUIRE(b->O == t->O && b->A == t->A, "trainer group buffer %d has dims (%d,%d), its member (%d,%d)", r, b->O,
-                        b->A, t->O, t->A);
-        } else {
-            SAC_REQUIRE(b->O == t0->O && b->A == t0->A, "trainer group buffer %d has dims (%d,%d), the trainers (%d,%d)", r, b->O,
-                        b->A, t0->O, t0->A);
-        }
-        SAC_REQUIRE(b->size > 0, "trainer group buffer %d is empty: random_batch on an empty replay buffer", r);
-        SAC_REQUIRE(b->size - 1 <= 0xffffffffLL, "replay buffers above 2^32 slots are not supported");
-    }
-    SAC_HIP(hipSetDevice(g->device));
-    // what sac_train_loop does first, for every member and every buffer (each with its member's own batch)
-    for (int r = 0; r < R; ++r) {
-        sac_trainer *t = g->m[r];
-        if (t->fused && t->pend_n > 0) {          // device-batch steps nobody has verified yet: settle them first
-            if (wait_trainer_stream(t)) return -1;
-            if (recover_device_steps(t) < 0) return -1;
-        }
-        sac_buffer *b = bufs[r];
-        if (host_rng_sync_in(b)) return -1;
-        if (b->ra_ahead > 0) { if (readahead_rollback(b)) return -1; }
-        else b->ra_streak = 0;
-        if (loop_spec_drop(b)) return -1;
-        b->loop_streak = 0;
-        if (ensure_slots(b, t->Bt, LOOP_RING)) return -1;
-        if (ensure_idx(b, LOOP_RING * t->B)) return -1;
-        t->dev.eps1 = t->dev.eps2 = nullptr;
-    }
-    // Buffers bound to the SAME host generator (sac_rng_bind_host: by default every EnvReplayBuffer samples np.random)
-    // continue it one after another, as R sac_train_loop calls in member order would: buffer r starts where the previous
-    // buffer of that generator ends (its n_steps batches of ITS member's batch size, drawn from its own size), and the
-    // host words end at the last one's end state (host_rng_advance below runs in member order).
-    for (int r = 1; r < R; ++r) {
-        sac_buffer *b = bufs[r];
-        if (!b->host_key) continue;
-        int q = r - 1;
-        while (q >= 0 && bufs[q]->host_key != b->host_key) --q;
-        if (q < 0) continue;
-        MtState st = bufs[q]->host_seen;
-        host_rng_skip(bufs[q], st, g->m[q]->Bt, n_steps);
-        if (host_rng_adopt(b, st)) return -1;
-    }
-    hipStream_t s = g->s, s2 = g->s2;
-    // both group streams behind everything already queued on the members' and the buffers' streams
-    for (int r = 0; r < R; ++r) {
-        SAC_HIP(hipEventRecord(g->ev_in[2 * r], g->m[r]->stream));
-        SAC_HIP(hipEventRecord(g->ev_in[2 * r + 1], bufs[r]->stream));
-        for (int k = 0; k < 2; ++k) {
-            SAC_HIP(hipStreamWaitEvent(s, g->ev_in[2 * r + k], 0));
-            SAC_HIP(hipStreamWaitEvent(s2, g->ev_in[2 * r + k], 0));
-        }
-    }
-    // the member tables of this call, in device order (the StepArg table follows chunk by chunk)
-    for (int k = 0; k < R && g->mlp; ++k) {
-        const int r = g->ord[k];
-        const sac_trainer *t = g->m[r];
-        sac_buffer *b = bufs[r];
-        SAC_REQUIRE(b->slot.off_obs == t->ext_layout.off_obs && b->slot.off_nobs == t->ext_layout.off_nobs && b->slot.Bt == t->gen->n,
-                    "internal: minibatch slot layout differs from the one the general step was built for");
-        gen::GenMember &M = g->h_gm[k];
-        M.d = t->gen->dev;
-        M.d.eps1 = M.d.eps2 = nullptr;                // (loop steps draw their noise on the device)
-        M.SL = b->slot;
-        M.slots = b->d_slots;
-    }
-    for (int k = 0; k < R && !g->mlp; ++k) {
-        const int r = g->ord[k];
-        const sac_trainer *t = g->m[r];
-        sac_buffer *b = bufs[r];
-        GroupMember &M = g->h_mem[k];
-        M.d = t->dev;
-        M.T = t->dw;
-        M.T.abort = nullptr;                          // (the four-launch step: no fused launch can give up in front of it)
-        M.SL = b->slot;
-        M.slots = b->d_slots;
-        if (g->algo == 1) {
-            M.T = t->dw_q; M.T.abort = nullptr;
-            M.T_tp = t->dw_q_tp; M.T_pi = t->dw_pi; M.T_none = t->dw_none;
-            M.T_tp.abort = M.T_pi.abort = M.T_none.abort = nullptr;
-        }
-        member_extents(t, g->algo, M.xa, M.xb, M.xc, M.xpi);
-    }
-    // the draw table in member order (one launch); the gather table sorted by gather class (one launch per class: the
-    // obs chunks per thread, NIT = 1 / 2 / 4 / 8), each class in member order
-    int gord[SAC_GROUP_MAX], gnit[4] = {}, glo[5] = {}, ngc = 0;
-    size_t glds[4] = {};
-    for (int nit : {1, 2, 4, 8}) {
-        const int lo = glo[ngc];
-        int n = lo;
-        size_t lds = 0;
-        for (int r = 0; r < R; ++r) {
-            const int v = gather_nit(bufs[r]), cl = v <= 1 ? 1 : v <= 2 ? 2 : v <= 4 ? 4 : 8;
-            SAC_REQUIRE(v <= 8, "observation rows too wide for the gather kernel (obs_dim %d)", bufs[r]->O);
-            if (cl != nit) continue;
-            gord[n++] = r;
-            lds = std::max(lds, sizeof(float) * (size_t)(2 * RB * bufs[r]->Ost + RB * bufs[r]->Ast));
-        }
-        if (n == lo) continue;
-        gnit[ngc] = nit; glds[ngc] = lds;
-        glo[++ngc] = n;
-    }
-    for (int r = 0; r < R; ++r) {
-        const sac_trainer *t = g->m[r];
-        sac_buffer *b = bufs[r];
-        uint32_t rng = (uint32_t)(b->size - 1), mask = rng;
-        mask |= mask >> 1; mask |= mask >> 2; mask |= mask >> 4; mask |= mask >> 8; mask |= mask >> 16;
-        for (int h = 0; h < 2; ++h)
-            g->h_smp[h * R + r] = SampleMember{b->d_rng, b->d_idx + (int64_t)h * LOOP_CH * t->B, rng, mask, t->Bt, t->B};
-    }
-    for (int p = 0; p < R; ++p) {
-        const int r = gord[p];
-        const sac_trainer *t = g->m[r];
-        sac_buffer *b = bufs[r];
-        for (int h = 0; h < 2; ++h)
-            g->h_gat[h * R + p] = GatherMember{b->view(), b->d_idx + (int64_t)h * LOOP_CH * t->B,
-                                               b->d_slots + (size_t)h * LOOP_CH * b->slot.slot_floats, b->slot, t->B};
-    }
-    if (g->mlp) SAC_HIP(hipMemcpyAsync(g->d_gm, g->h_gm, sizeof(gen::GenMember) * R, hipMemcpyHostToDevice, s2));
-    else SAC_HIP(hipMemcpyAsync(g->d_mem, g->h_mem, sizeof(GroupMember) * R, hipMemcpyHostToDevice, s2));
-    SAC_HIP(hipMemcpyAsync(g->d_smp, g->h_smp, sizeof(SampleMember) * 2 * R, hipMemcpyHostToDevice, s2));
-    SAC_HIP(hipMemcpyAsync(g->d_gat, g->h_gat, sizeof(GatherMember) * 2 * R, hipMemcpyHostToDevice, s2));
-    const int compact = 1;                            // (3 * 4 * NB <= 192 for every member: checked at creation)
-    long long pi_steps[SAC_GROUP_MAX] = {};           // TD3: policy steps of each member so far in this call
-    unsigned char plan[LOOP_CH];                      // TD3: per step of a chunk, bit 0: some member runs the actor pass, bit 1: some policy step
-    FusedGate &G = g_gate[g->device & 63];
-    int64_t done = 0;
-    for (int c = 0; done < n_steps; ++c) {
-        const int64_t m = (n_steps - done < LOOP_CH) ? n_steps - done : LOOP_CH;
-        const int h = c & 1;
-        // the chunk's draws and gathers into half h of every buffer's loop slots, once the steps of chunk c - 2 are done there
-        if (c >= 2) SAC_HIP(hipStreamWaitEvent(s2, g->ev_done[h], 0));
-        {   // (tenants of the gate too: at R = 16 the grouped gather is 16 x 1024 workgroups that must not overlap a k_abc)
-            std::lock_guard<std::mutex> lk(G.mu);
-            const bool gate = G.live > 1;
-            if (gate && G.last && G.last != s2) SAC_HIP(hipStreamWaitEvent(s2, G.ev, 0));
-            if (launch_sample_group(g->d_smp + h * R, R, m, s2)) return -1;
-            for (int q = 0; q < ngc; ++q) {
-                int grid = 0;
-                for (int p = glo[q]; p < glo[q + 1]; ++p) {
-                    const int64_t nb = (int64_t)(g->m[gord[p]]->B / RB) * m;
-                    grid = std::max(grid, (int)(nb < 1024 ? nb : 1024));     // (the x-extent of a solo launch_gather)
-                }
-                if (launch_gather_group(g->d_gat + h * R + glo[q], glo[q + 1] - glo[q], gnit[q], m, grid, glds[q], 1, s2)) return -1;
-            }
-            if (gate) { SAC_HIP(hipEventRecord(G.ev, s2)); G.last = s2; }
-        }
-        SAC_HIP(hipEventRecord(g->ev_ready[h], s2));
-        // the chunk's step arguments, computed like launch_step's (the host half is free once its last copy has run)
-        if (c >= 2 && wait_event(g->ev_copied[h])) return -1;
-        const void *dsrc = nullptr, *hsrc = nullptr;
-        size_t bytes = 0;
-        if (g->mlp) {
-            // gen_launch_step's arguments per member and step (TD3: launch_step_td3's plan, as for the other TD3 groups)
-            gen::GenGroupStep *hs = g->h_gs + (size_t)h * LOOP_CH * R;
-            for (int64_t j = 0; j < m; ++j) {
-                plan[j] = 0;
-                for (int k = 0; k < R; ++k) {
-                    const int r = g->ord[k];
-                    const sac_trainer *t = g->m[r];
-                    const long long i = (long long)(done + j), step = t->n_train_steps_total + i;
-                    const double tq = (double)(t->adam_t + i + 1), tp = (double)(t->adam_t_pi + pi_steps[r] + 1);
-                    gen::GenGroupStep &gs = hs[j * R + k];
-                    memset(&gs, 0, sizeof(gs));
-                    gs.sa = StepArg{step, t->adam_t + i + 1, (int)i, g->algo, 1.0 - std::pow(0.9, tq), std::sqrt(1.0 - std::pow(0.999, tq))};
-                    gs.sa.pad2 = (done + j == n_steps - 1) ? 2u : 0u;
-                    if (g->algo == 0) {
-                        gs.polyak = (step % t->gen->dev.period) == 0 ? 1 : 0;
-                    } else {
-                        const bool pstep = (step % t->td3_period) == 0, actor = pstep || i == 0;
-                        gs.sp = StepArg{step, t->adam_t_pi + pi_steps[r] + 1, (int)i, 2, 1.0 - std::pow(0.9, tp),
-                                        std::sqrt(1.0 - std::pow(0.999, tp))};
-                        gs.sp.pad2 = gs.sa.pad2;
-                        gs.actor = actor ? 1 : 0;
-                        gs.pstep = gs.polyak = pstep ? 1 : 0;
-                        plan[j] |= (actor ? 1 : 0) | (pstep ? 2 : 0);
-                        pi_steps[r] += pstep ? 1 : 0;
-                    }
-                }
-            }
-            hsrc = hs; dsrc = g->d_gs + (size_t)h * LOOP_CH * R; bytes = sizeof(gen::GenGroupStep) * m * R;
-        } else if (g->algo == 0) {
-            StepArg *hs = g->h_sa + (size_t)h * LOOP_CH * R;
-            for (int64_t j = 0; j < m; ++j)
-                for (int k = 0; k < R; ++k) {
-                    const sac_trainer *t = g->m[g->ord[k]];
-                    const long long i = (long long)(done + j);
-                    const double tt = (double)(t->adam_t + i + 1);
-                    StepArg sa{t->n_train_steps_total + i, t->adam_t + i + 1, (int)i, 0, 1.0 - std::pow(0.9, tt),
-                               std::sqrt(1.0 - std::pow(0.999, tt))};
-                    sa.pad2 = (done + j == n_steps - 1) ? 2u : 0u;
-                    hs[j * R + k] = sa;
-                }
-            hsrc = hs; dsrc = g->d_sa + (size_t)h * LOOP_CH * R; bytes = sizeof(StepArg) * m * R;
-        } else {
-            // launch_step_td3's decision per member and step: a policy step every td3_period-th step number, the actor pass
-            // also on the call's first step (its Policy Loss / Policy Action statistics, no update)
-            Td3GroupStep *hs = g->h_ts + (size_t)h * LOOP_CH * R;
-            for (int64_t j = 0; j < m; ++j) {
-                plan[j] = 0;
-                for (int k = 0; k < R; ++k) {
-                    const int r = g->ord[k];
-                    const sac_trainer *t = g->m[r];
-                    const long long i = (long long)(done + j), step = t->n_train_steps_total + i;
-                    const bool pstep = (step % t->td3_period) == 0, actor = pstep || i == 0;
-                    const double tq = (double)(t->adam_t + i + 1), tp = (double)(t->adam_t_pi + pi_steps[r] + 1);
-                    Td3GroupStep &ts = hs[j * R + k];
-                    ts.sq = StepArg{step, t->adam_t + i + 1, (int)i, 1, 1.0 - std::pow(0.9, tq), std::sqrt(1.0 - std::pow(0.999, tq))};
-                    ts.sp = StepArg{step, t->adam_t_pi + pi_steps[r] + 1, (int)i, 2, 1.0 - std::pow(0.9, tp),
-                                    std::sqrt(1.0 - std::pow(0.999, tp))};
-                    ts.sq.pad2 = ts.sp.pad2 = (done + j == n_steps - 1) ? 2u : 0u;
-                    ts.actor = actor ? 1 : 0;
-                    ts.pstep = pstep ? 1 : 0;
-                    ts.pad_[0] = ts.pad_[1] = 0;
-                    plan[j] |= (actor ? 1 : 0) | (pstep ? 2 : 0);
-                    pi_steps[r] += pstep ? 1 : 0;
-                }
-            }
-            hsrc = hs; dsrc = g->d_ts + (size_t)h * LOOP_CH * R; bytes = sizeof(Td3GroupStep) * m * R;
-        }
-        SAC_HIP(hipMemcpyAsync(const_cast<void *>(dsrc), hsrc, bytes, hipMemcpyHostToDevice, s));
-        SAC_HIP(hipEventRecord(g->ev_copied[h], s));
-        SAC_HIP(hipStreamWaitEvent(s, g->ev_ready[h], 0));
-        {
-            std::lock_guard<std::mutex> lk(G.mu);
-            const bool gate = G.live > 1;
-            if (gate && G.last && G.last != s) SAC_HIP(hipStreamWaitEvent(s, G.ev, 0));
-            // per step kernel, one grouped launch per variant class (its range of the tables, gridDim.y = its size), then
-            // one weight-gradient launch over all members
-            for (int64_t j = 0; j < m; ++j) {
-                const int slot = (int)(h * LOOP_CH + j);
-                if (g->mlp) {
-                    const gen::GenGroupStep *gs = g->d_gs + (size_t)h * LOOP_CH * R + j * R;
-                    const long long i = (long long)(done + j);
-                    for (const GroupGenStage &st : g->gst) {
-                        if (st.list == 1 && !(plan[j] & 1)) continue;               // TD3: no member runs the actor pass
-                        if (st.sel == gen::GSEL_PSTEP && !(plan[j] & 2)) continue;  // no member is on a policy step
-                        // (SAC: the diagnostics on the steps somebody reads them -- the call's first and last)
-                        if (st.kind == GS_DIAG && g->algo == 0 && i != 0 && i != n_steps - 1) continue;
-                        if (st.kind == GS_GEMM) {
-                            const gen::GemmStage *H = g->d_hdr + (size_t)st.hdr * R;
-                            if (st.mode == 0) hipLaunchKernelGGL((gen::k_g_gemm_group<true, true>), dim3(st.grid), dim3(64 * gen::GW), 0, s, H, g->d_gm, gs, slot, st.map);
-                            else if (st.mode == 1) hipLaunchKernelGGL((gen::k_g_gemm_group<true, false>), dim3(st.grid), dim3(64 * gen::GW), 0, s, H, g->d_gm, gs, slot, st.map);
-                            else hipLaunchKernelGGL((gen::k_g_gemm_group<false, false>), dim3(st.grid), dim3(64 * gen::GW), 0, s, H, g->d_gm, gs, slot, st.map);
-                        } else if (st.per_class) {
-                            for (int q = 0; q < g->ncls; ++q) {
-                                const GroupClass &K = g->cls[q];
-                                hipLaunchKernelGGL(st.fn[q], dim3(st.gx[q], K.n), dim3(256), 0, s, g->d_gm + K.lo, gs + K.lo, slot, st.sel);
-                            }
-                        } else {
-                            hipLaunchKernelGGL(st.fn[0], dim3(st.gx[0], R), dim3(256), 0, s, g->d_gm, gs, slot, st.sel);
-                        }
-                    }
-                } else if (g->algo == 0) {
-                    const StepArg *sa = g->d_sa + (size_t)h * LOOP_CH * R + j * R;
-                    for (int q = 0; q < g->ncls; ++q) {
-                        const GroupClass &K = g->cls[q];
-                        hipLaunchKernelGGL(K.fa, dim3(K.xa, K.n), dim3(256), K.lds_fa, s, g->d_mem + K.lo, sa + K.lo, slot);
-                    }
-                    for (int q = 0; q < g->ncls; ++q) {
-                        const GroupClass &K = g->cls[q];
-                        hipLaunchKernelGGL(K.fb, dim3(K.xb, K.n), dim3(256), K.lds_fb, s, g->d_mem + K.lo, sa + K.lo, slot);
-                    }
-                    for (int q = 0; q < g->ncls; ++q) {
-                        const GroupClass &K = g->cls[q];
-                        hipLaunchKernelGGL(K.bw, dim3(K.xc, K.n), dim3(256), K.lds_bw, s, g->d_mem + K.lo, sa + K.lo, slot,
-                                           compact);
-                    }
-                    hipLaunchKernelGGL(k_dw_adam_group<M_SAC>, dim3(g->grid_d, R), dim3(256), 0, s, g->d_mem, sa, slot);
-                } else {
-                    const Td3GroupStep *ts = g->d_ts + (size_t)h * LOOP_CH * R + j * R;
-                    for (int q = 0; q < g->ncls; ++q) {
-                        const GroupClass &K = g->cls[q];
-                        hipLaunchKernelGGL(K.fa3, dim3(K.xa, K.n), dim3(256), K.lds_fa, s, g->d_mem + K.lo, ts + K.lo, slot);
-                    }
-                    for (int q = 0; q < g->ncls; ++q) {
-                        const GroupClass &K = g->cls[q];
-                        hipLaunchKernelGGL(K.fb3, dim3(K.xb, K.n), dim3(256), K.lds_fb, s, g->d_mem + K.lo, ts + K.lo, slot);
-                    }
-                    for (int q = 0; q < g->ncls; ++q) {
-                        const GroupClass &K = g->cls[q];
-                        hipLaunchKernelGGL(K.bw3, dim3(K.xc, K.n), dim3(256), K.lds_bw, s, g->d_mem + K.lo, ts + K.lo, slot, 0);
-                    }
-                    hipLaunchKernelGGL(k_dw_adam_group<M_TD3_CRITIC>, dim3(g->grid_dq, R), dim3(256), 0, s, g->d_mem, ts, slot);
-                    if (plan[j] & 1) {
-                        for (int q = 0; q < g->ncls; ++q) {
-                            const GroupClass &K = g->cls[q];
-                            hipLaunchKernelGGL(K.fb3a, dim3(K.xpi, K.n), dim3(256), K.lds_fb, s, g->d_mem + K.lo, ts + K.lo, slot);
-                        }
-                        if (plan[j] & 2)
-                            for (int q = 0; q < g->ncls; ++q) {
-                                const GroupClass &K = g->cls[q];
-                                hipLaunchKernelGGL(K.bw3a, dim3(K.xpi, K.n), dim3(256), K.lds_bw, s, g->d_mem + K.lo, ts + K.lo,
-                                                   slot, 0);
-                            }
-                        hipLaunchKernelGGL(k_dw_adam_group<M_TD3_ACTOR>, dim3((plan[j] & 2) ? g->grid_dpi : 1, R), dim3(256), 0, s,
-                                           g->d_mem, ts, slot);
-                    }
-                }
-            }
-            SAC_HIP(hipGetLastError());
-            if (gate) { SAC_HIP(hipEventRecord(G.ev, s)); G.last = s; }
-        }
-        SAC_HIP(hipEventRecord(g->ev_done[h], s));
-        done += m;
-    }
-    // the host mirrors of the generators follow behind the launches (each buffer by its member's batch)
-    for (int r = 0; r < R; ++r) host_rng_advance(bufs[r], g->m[r]->Bt, n_steps);
-    SAC_HIP(hipEventRecord(g->ev_end, s));
-    if (wait_event(g->ev_end)) return -1;
-    SAC_HIP(hipStreamSynchronize(s2));
-    for (int r = 0; r < R; ++r) {
-        sac_trainer *t = g->m[r];
-        t->n_train_steps_total += n_steps;
-        t->adam_t += n_steps;
-        t->adam_t_pi += pi_steps[r];                  // (TD3; zero for SAC)
-        t->mirror_valid = false;
-        if (diag_first) memcpy(diag_first + (size_t)r * SAC_DIAG_N, t->h_diag, sizeof(float) * SAC_DIAG_N);
-        if (diag_last) memcpy(diag_last + (size_t)r * SAC_DIAG_N, t->h_diag + SAC_DIAG_N, sizeof(float) * SAC_DIAG_N);
-    }
-    return 0;
-}
+#include "sac_group_host.h"
 
 }  // extern "C"

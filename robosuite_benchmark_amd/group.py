@@ -23,16 +23,19 @@ from .td3 import TD3Trainer
 MAX_MEMBERS = 16
 
 
+def _general_shape(hs):
+    return len(hs) != 2 or max(hs) > 256
+
+
 def runs_general_step(t):
     """Does trainer t run the general step (hidden sizes other than two layers of at most 256 units)?  Such runs group in
     MlpSACTrainerGroup / MlpTD3TrainerGroup, the others in the remaining kinds."""
-    return any(len(hs) != 2 or max(hs) > 256 for hs in (t._hidden("policy"), t._hidden("qf1")))
+    return _general_shape(t._hidden("policy")) or _general_shape(t._hidden("qf1"))
 
 
-class _GroupBase:
-    """What every kind of trainer group shares: the member checks that hold for all of them, the C group over the
-    members' handles, and the call of sac_group_train_loop."""
-    _CREATE = None              # the C entry point that makes the group (sac_group_create / td3_group_create / ..._mixed)
+class _Members:
+    """The member checks that hold for every kind of trainer group (host metadata: nothing is created for a group that
+    cannot exist).  The algorithm comes from _SACMembers / _TD3Members."""
     _ONLY = None                # why a member of another kind is refused
 
     @staticmethod
@@ -46,21 +49,49 @@ class _GroupBase:
     def _check_step(self, i, t):
         """Refuse member i for the step its hidden sizes select (the fused kernels' groups check it at train_loop)."""
 
-    def __init__(self, trainers):
+    def _checked_members(self, trainers):
         trainers = list(trainers)
         if not 1 <= len(trainers) <= MAX_MEMBERS:
             raise RuntimeError(f"a trainer group holds 1..{MAX_MEMBERS} trainers (got {len(trainers)})")
-        # host metadata first: nothing is created for a group that cannot exist
         for i, t in enumerate(trainers):
             if not self._member_ok(t):
                 raise RuntimeError(f"trainer group member {i} is a {type(t).__name__}: {self._ONLY}")
             self._check_step(i, t)
         if len({id(t) for t in trainers}) != len(trainers):
             raise RuntimeError("a trainer appears twice in the group")
-        t0 = trainers[0]
         for i, t in enumerate(trainers[1:], 1):
-            self._check_member(i, t, t0)
-        self.trainers = trainers
+            self._check_member(i, t, trainers[0])
+        return trainers
+
+    @staticmethod
+    def _check_device(i, t, t0):
+        if t.device != t0.device:
+            raise RuntimeError(f"trainer group member {i} lives on device {t.device}, member 0 on {t0.device}")
+
+
+class _SACMembers:
+    _ONLY = "groups hold SAC trainers only"
+
+    @staticmethod
+    def _member_ok(t):
+        return isinstance(t, SACTrainer) and not isinstance(t, TD3Trainer)
+
+
+class _TD3Members:
+    _ONLY = "TD3 groups hold TD3 trainers only"
+
+    @staticmethod
+    def _member_ok(t):
+        return isinstance(t, TD3Trainer)
+
+
+class _GroupBase(_Members):
+    """What every kind of trainer group with a C group shares: the C group over the members' handles and the call of
+    sac_group_train_loop."""
+    _CREATE = None              # the C entry point that makes the group (sac_group_create / td3_group_create / ..._mixed)
+
+    def __init__(self, trainers):
+        self.trainers = self._checked_members(trainers)
         self._lib = _lib.load()
         self._g, self._handles = None, None
 
@@ -70,11 +101,6 @@ class _GroupBase:
             if t._hidden(net) != t0._hidden(net):
                 raise RuntimeError(f"trainer group member {i} has {net} hidden sizes {t._hidden(net)}, member 0 "
                                    f"{t0._hidden(net)}")
-
-    @staticmethod
-    def _check_device(i, t, t0):
-        if t.device != t0.device:
-            raise RuntimeError(f"trainer group member {i} lives on device {t.device}, member 0 on {t0.device}")
 
     def __len__(self):
         return len(self.trainers)
@@ -108,11 +134,10 @@ class _GroupBase:
 
     def _check_general(self):
         for i, t in enumerate(self.trainers):
-            for net in ("policy", "qf1"):
-                hs = t._hidden(net)
-                if len(hs) != 2 or max(hs) > 256:
-                    raise RuntimeError(f"trainer group member {i} runs the general step ({net} hidden sizes {hs}): groups "
-                                       "take two hidden layers of at most 256 units")
+            if runs_general_step(t):
+                net = "policy" if _general_shape(t._hidden("policy")) else "qf1"
+                raise RuntimeError(f"trainer group member {i} runs the general step ({net} hidden sizes "
+                                   f"{t._hidden(net)}): groups take two hidden layers of at most 256 units")
 
     @staticmethod
     def _check_buffer(r, b, buffers, dims, whose):
@@ -219,39 +244,25 @@ class _MixedTrainerGroup(_GroupBase):
         return batches
 
 
-class SACTrainerGroup(_TrainerGroup):
+class SACTrainerGroup(_SACMembers, _TrainerGroup):
     _CREATE = "sac_group_create"
-    _ONLY = "groups hold SAC trainers only"
-
-    @staticmethod
-    def _member_ok(t):
-        return isinstance(t, SACTrainer) and not isinstance(t, TD3Trainer)
 
 
-class TD3TrainerGroup(_TrainerGroup):
+class TD3TrainerGroup(_TD3Members, _TrainerGroup):
     """R TD3 runs of one shape; each member keeps its own delayed-update phase (policy_and_target_update_period and the
     step count may differ), and train_loop advances each as TD3Trainer.train_loop does."""
     _CREATE = "td3_group_create"
-    _ONLY = "TD3 groups hold TD3 trainers only"
-
-    @staticmethod
-    def _member_ok(t):
-        return isinstance(t, TD3Trainer)
 
 
-class MixedSACTrainerGroup(_MixedTrainerGroup):
+class MixedSACTrainerGroup(_SACMembers, _MixedTrainerGroup):
     """R SAC runs of different tasks (observation size, action size and batch per member) on one device: the members of
     one kernel variant share each grouped launch, the variants follow one another."""
     _CREATE = "sac_group_create_mixed"
-    _ONLY = "groups hold SAC trainers only"
-    _member_ok = staticmethod(SACTrainerGroup._member_ok)
 
 
-class MixedTD3TrainerGroup(_MixedTrainerGroup):
+class MixedTD3TrainerGroup(_TD3Members, _MixedTrainerGroup):
     """R TD3 runs of different tasks; each keeps its own delayed-update phase as in TD3TrainerGroup."""
     _CREATE = "td3_group_create_mixed"
-    _ONLY = "TD3 groups hold TD3 trainers only"
-    _member_ok = staticmethod(TD3TrainerGroup._member_ok)
 
 
 class _MlpTrainerGroup(_MixedTrainerGroup):
@@ -271,19 +282,15 @@ class _MlpTrainerGroup(_MixedTrainerGroup):
         pass                    # (checked at construction, by _check_step)
 
 
-class MlpSACTrainerGroup(_MlpTrainerGroup):
+class MlpSACTrainerGroup(_SACMembers, _MlpTrainerGroup):
     """R SAC runs of the general step with one set of hidden sizes (e.g. the seeds of a [512, 512] variant, or several
     tasks at [256, 256, 256]); each stage of the step is one grouped launch over all members."""
     _CREATE = "sac_group_create_mlp"
-    _ONLY = "groups hold SAC trainers only"
-    _member_ok = staticmethod(SACTrainerGroup._member_ok)
 
 
-class MlpTD3TrainerGroup(_MlpTrainerGroup):
+class MlpTD3TrainerGroup(_TD3Members, _MlpTrainerGroup):
     """R TD3 runs of the general step; each keeps its own delayed-update phase as in TD3TrainerGroup."""
     _CREATE = "td3_group_create_mlp"
-    _ONLY = "TD3 groups hold TD3 trainers only"
-    _member_ok = staticmethod(TD3TrainerGroup._member_ok)
 
 
 class _ArchGeneral(_MlpTrainerGroup):
@@ -293,22 +300,18 @@ class _ArchGeneral(_MlpTrainerGroup):
         self._check_device(i, t, t0)
 
 
-class _ArchGeneralSAC(_ArchGeneral):
+class _ArchGeneralSAC(_SACMembers, _ArchGeneral):
     _CREATE = "sac_group_create_arch"
-    _ONLY = "groups hold SAC trainers only"
-    _member_ok = staticmethod(SACTrainerGroup._member_ok)
 
 
-class _ArchGeneralTD3(_ArchGeneral):
+class _ArchGeneralTD3(_TD3Members, _ArchGeneral):
     _CREATE = "td3_group_create_arch"
-    _ONLY = "TD3 groups hold TD3 trainers only"
-    _member_ok = staticmethod(TD3TrainerGroup._member_ok)
 
 
 _MEMBER_REF = re.compile(r"\b(member|buffer) (\d+)\b")
 
 
-class _ArchTrainerGroup:
+class _ArchTrainerGroup(_Members):
     """Members of ANY hidden sizes (a network-size sweep; the paper default [256, 256] included), one algorithm, one
     device.  The general-step members form one C arch group (sac_group_create_arch / td3_group_create_arch: the merged
     schedule of their launch lists, one grouped launch per merged stage); the members with the shapes of the fused
@@ -319,23 +322,10 @@ class _ArchTrainerGroup:
     train_loop calls in `run_order` would."""
     _MIXED = None               # the fused subgroups' kind
     _GENERAL = None             # the general subgroup's kind
-    _ONLY = None
-
-    @staticmethod
-    def _member_ok(t):
-        raise NotImplementedError
+    _check_member = staticmethod(_Members._check_device)     # (hidden sizes are free)
 
     def __init__(self, trainers):
-        trainers = list(trainers)
-        if not 1 <= len(trainers) <= MAX_MEMBERS:
-            raise RuntimeError(f"a trainer group holds 1..{MAX_MEMBERS} trainers (got {len(trainers)})")
-        for i, t in enumerate(trainers):
-            if not self._member_ok(t):
-                raise RuntimeError(f"trainer group member {i} is a {type(t).__name__}: {self._ONLY}")
-        if len({id(t) for t in trainers}) != len(trainers):
-            raise RuntimeError("a trainer appears twice in the group")
-        for i, t in enumerate(trainers[1:], 1):
-            _GroupBase._check_device(i, t, trainers[0])
+        trainers = self._checked_members(trainers)
         fused, general = {}, []
         for i, t in enumerate(trainers):
             if runs_general_step(t):
@@ -398,18 +388,14 @@ class _ArchTrainerGroup:
         return first, last
 
 
-class ArchSACTrainerGroup(_ArchTrainerGroup):
+class ArchSACTrainerGroup(_SACMembers, _ArchTrainerGroup):
     """R SAC runs of any hidden sizes (e.g. [256, 256], [512, 512], [256, 256, 256] and [1024] of one or several tasks)
     on one device; see _ArchTrainerGroup."""
     _MIXED = MixedSACTrainerGroup
     _GENERAL = _ArchGeneralSAC
-    _ONLY = "groups hold SAC trainers only"
-    _member_ok = staticmethod(SACTrainerGroup._member_ok)
 
 
-class ArchTD3TrainerGroup(_ArchTrainerGroup):
+class ArchTD3TrainerGroup(_TD3Members, _ArchTrainerGroup):
     """R TD3 runs of any hidden sizes; each keeps its own delayed-update phase as in TD3TrainerGroup."""
     _MIXED = MixedTD3TrainerGroup
     _GENERAL = _ArchGeneralTD3
-    _ONLY = "TD3 groups hold TD3 trainers only"
-    _member_ok = staticmethod(TD3TrainerGroup._member_ok)
