@@ -323,6 +323,27 @@ int64_t sac_debug_fetch(sac_trainer_t *t, const char *name, float *out, int64_t 
  * eps (A floats) may be NULL when deterministic. */
 int sac_policy_mirror(sac_trainer_t *t);
 int sac_policy_act(sac_trainer_t *t, const float *obs, int deterministic, const float *eps, float *act);
+/* policy.get_actions(obs) on the DEVICE from the live weights: n rows in one launch (k_act, csrc/sac_act.h).  The kernel
+ * reads the policy where the step kernels keep it -- no mirror, no parameter copy -- and sees the weights as of the last
+ * completed step of any step path (sac_step, sac_step_device, sac_train_loop, sac_group_train_loop) or sac_set_params:
+ * the call first drains the trainer as sac_sync does, a fused step that gave up included.  n is 1..1024; SAC stochastic:
+ * tanh(mean + exp(clamp(log_std, -20, 2)) * eps), deterministic: tanh(mean); TD3: tanh(last_fc) always (eps unused).  A
+ * row's action depends on that row's observation, its eps and the weights only -- not on its place, on n or on the rest
+ * of the launch -- so row r of any call is bit for bit the one-row call.  The call returns with the actions in `act`;
+ * the host mirror of sac_policy_act is left alone, and nothing the step reads is written.
+ * For trainers with the fused kernels' shapes (two hidden layers of at most 256 units: every shipped variant).
+ * General-step trainers (sac_trainer_create_mlp with other shapes) are refused: they act through sac_policy_act. */
+int sac_policy_act_device(sac_trainer_t *t, int64_t n, const float *obs /* (n,O) host */, int deterministic,
+                          const float *eps /* (n,A) host; NULL when deterministic or TD3 */, float *act /* (n,A) host */);
+/* the same for 1..SAC_GROUP_MAX (16) trainers of one device in ONE launch; n_rows[i] == 0: member i sits out (its
+ * arrays are not touched).  It takes trainers, not a group, so it serves every group kind; SAC and TD3 members, dims,
+ * row counts and deterministic flags may be mixed.  Each member's actions are bit for bit its own
+ * sac_policy_act_device's.  Refused (<0, sac_last_error, nothing changed): null or duplicate trainers, n_rows outside
+ * 0..1024 or all zero, a stochastic SAC member without eps, trainers on different devices, general-step trainers,
+ * members confined by sac_trainer_set_xcd[_mask]. */
+int sac_policy_act_many(sac_trainer_t *const *trainers, int n_trainers, const int32_t *n_rows,
+                        const float *const *obs, const int32_t *deterministic, const float *const *eps,
+                        float *const *act);
 
 /* ------------------------------------------------------------------------------------------
  * Trainer groups: several runs of one configuration (the reference's seed sweeps, /root/reference/launch_jobs.sh)

@@ -13,6 +13,7 @@ HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.path.join(HERE, "libsac_hip.so")
 
 SAC_DIAG_N = 32
+ACT_MAX_ROWS = 1024              # rows per member of one sac_policy_act_device / sac_policy_act_many call
 DIAG_NAMES = [
     "QF1 Loss", "QF2 Loss", "Policy Loss", "Actor Loss",
     "Q1 Predictions Mean", "Q1 Predictions Std", "Q1 Predictions Max", "Q1 Predictions Min",
@@ -110,6 +111,8 @@ SYMBOLS = {
     "sac_debug_fetch": (C.c_int64, [_P, C.c_char_p, _P, C.c_int64]),
     "sac_policy_mirror": (C.c_int, [_P]),
     "sac_policy_act": (C.c_int, [_P, _P, C.c_int, _P, _P]),
+    "sac_policy_act_device": (C.c_int, [_P, C.c_int64, _P, C.c_int, _P, _P]),
+    "sac_policy_act_many": (C.c_int, [_P, C.c_int, _P, _P, _P, _P, _P]),
     "sac_group_create": (C.c_int, [C.POINTER(_P), _P, C.c_int]),
     "td3_group_create": (C.c_int, [C.POINTER(_P), _P, C.c_int]),
     "sac_group_create_mixed": (C.c_int, [C.POINTER(_P), _P, C.c_int]),

@@ -1876,6 +1876,9 @@ struct sac_trainer {
     hipEvent_t ev_tm[3] = {nullptr, nullptr, nullptr};  // around the draw and the gather of the loop's timed chunk
     std::vector<float> h_policy;                      // host mirror for acting
     bool mirror_valid = false;
+    // device acting (sac_act.h): observations, eps, actions and the member table of a call, in mapped pinned host memory
+    struct ActStage { char *h = nullptr, *d = nullptr; size_t bytes = 0; } act_stage;
+    bool act_lds_raised = false;                      // k_act may use more than 48 KB of LDS (wide observations)
     size_t lds_bw = 0;
     // fused step (k_abc, sac_fused.h): launches A + B + C as one launch with in-launch hand-offs
     bool fused = false;
@@ -2240,6 +2243,8 @@ int stage_batches(sac_trainer *t, sac_buffer *b, int64_t n_steps) {
 }
 
 }  // namespace
+
+#include "sac_act.h"
 
 extern "C" {
 
@@ -2705,6 +2710,7 @@ int sac_trainer_destroy(sac_trainer_t *t) {
     gen_destroy(t->gen);
     if (t->h_stage) (void)hipHostFree(t->h_stage);
     if (t->h_diag) (void)hipHostFree(t->h_diag);
+    if (t->act_stage.h) (void)hipHostFree(t->act_stage.h);
     for (auto &e : t->ev) if (e) (void)hipEventDestroy(e);
     for (auto &e : t->ev_tm) if (e) (void)hipEventDestroy(e);
     for (auto &e : t->ev_ready) if (e) (void)hipEventDestroy(e);

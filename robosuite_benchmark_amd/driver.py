@@ -20,10 +20,11 @@ from .checkpoint import checkpoint_exists, load_checkpoint, save_checkpoint
 from .group_checkpoint import DEFAULT_CHUNK_ROWS, GroupCheckpoint, member_identity
 from .group_checkpoint import checkpoint_exists as _checkpoint_exists
 from .networks import (FlattenMlp, GaussianStrategy, MakeDeterministic, PolicyWrappedWithExplorationStrategy,
-                       TanhGaussianPolicy, TanhMlpPolicy)
+                       TanhGaussianPolicy, TanhMlpPolicy, check_acting)
 from .replay_buffer import EnvReplayBuffer
 from .group import (ArchSACTrainerGroup, ArchTD3TrainerGroup, MixedSACTrainerGroup, MixedTD3TrainerGroup,
-                    MlpSACTrainerGroup, MlpTD3TrainerGroup, SACTrainerGroup, TD3TrainerGroup, runs_general_step)
+                    MlpSACTrainerGroup, MlpTD3TrainerGroup, SACTrainerGroup, TD3TrainerGroup, act_many,
+                    runs_general_step)
 from .sac import SACTrainer
 from .td3 import TD3Trainer
 from .variant import env_dims, validate
@@ -99,6 +100,116 @@ class PathCollector:
         return OrderedDict([("num steps total", self.num_steps_total), ("num paths total", self.num_paths_total)])
 
 
+def _acting_parts(policy):
+    """A collector's policy as (holder, deterministic, exploration wrapper or None): MakeDeterministic(holder), a
+    PolicyWrappedWithExplorationStrategy around a holder, or the holder itself."""
+    if isinstance(policy, MakeDeterministic):
+        return policy.stochastic_policy, True, None
+    if isinstance(policy, PolicyWrappedWithExplorationStrategy):
+        return policy.policy, False, policy
+    return policy, False, None
+
+
+def holder_actions(holders, obs_list, deterministic_list, act_many=act_many):
+    """One action row per holder: what holders[i].get_action(obs_list[i]) (MakeDeterministic: deterministic_list[i])
+    returns, for all of them at once.  Every stochastic TanhGaussianPolicy draws its (1, A) exploration noise on the host
+    from its own _noise stream, exactly as get_action does; the holders whose trainer has a handle then act through ONE
+    act_many call (group.act_many: the fused kernels' shapes in one launch, the general step on the host), holders
+    without one through their own NumPy forward."""
+    eps, bound = [], []
+    for h, det in zip(holders, deterministic_list):
+        stochastic = isinstance(h, TanhGaussianPolicy) and not det
+        eps.append(h._noise.standard_normal((1, h.action_dim)).astype(np.float32) if stochastic else None)
+        tr = h._trainer
+        bound.append(tr is not None and getattr(tr, "_h", None) is not None and tr.policy is h)
+    acts = [None] * len(holders)
+    ids = [i for i, b in enumerate(bound) if b]
+    if ids:
+        got = act_many([holders[i]._trainer for i in ids], [np.asarray(obs_list[i])[None] for i in ids],
+                       [deterministic_list[i] for i in ids], [eps[i] for i in ids])
+        for i, a in zip(ids, got):
+            acts[i] = a[0, :]
+    for i, h in enumerate(holders):
+        if bound[i]:
+            continue
+        obs = np.asarray(obs_list[i], np.float32)[None]
+        if isinstance(h, TanhGaussianPolicy):
+            mean, log_std = h._trunk(obs)
+            acts[i] = (np.tanh(mean) if eps[i] is None else np.tanh(mean + np.exp(log_std) * eps[i]))[0, :]
+        else:
+            acts[i] = h.get_actions(obs)[0, :]
+    return acts
+
+
+class GroupPathCollector:
+    """PathCollector.collect_new_paths for many runs in LOCKSTEP: on every tick the current observation of every member
+    that still has steps to take goes through ONE act_many call, then each of those members steps its env.
+
+    collectors: the runs' PathCollectors (env, policy, counters, epoch_paths), which this object fills exactly as their
+    own collect_new_paths would: per member the same rollouts -- env.reset / policy.reset at the start of a path, the
+    last path clipped to the remaining step budget and dropped under discard_incomplete_paths -- the same paths, and the
+    same num_steps_total / num_paths_total.  Members finish at different ticks.  Each member's envs, noise streams and
+    weights are its own, so a member's paths do not depend on who else is collected with it."""
+
+    def __init__(self, collectors, act_many=act_many):
+        self.collectors, self._act_many = list(collectors), act_many
+
+    def collect_new_paths(self, plans):
+        """plans[i] = (max_path_length, num_steps, discard_incomplete_paths) of member i.  Returns [paths of member i]."""
+        if len(plans) != len(self.collectors):
+            raise RuntimeError("GroupPathCollector.collect_new_paths takes one plan per collector")
+        parts = [_acting_parts(c.policy) for c in self.collectors]
+        S = [dict(c=c, mpl_max=int(p[0]), budget=int(p[1]), discard=bool(p[2]), paths=[], collected=0, live=True)
+             for c, p in zip(self.collectors, plans)]
+
+        def begin(m):                                         # the head of PathCollector's while loop + rollout's
+            if m["collected"] >= m["budget"]:
+                m["live"] = False
+                return
+            m["mpl"] = min(m["mpl_max"], m["budget"] - m["collected"])
+            m["o"] = m["c"].env.reset()
+            m["c"].policy.reset()
+            m["rec"] = ([], [], [], [], [])
+
+        def finish(m):                                        # the tail of rollout + of the while loop's body
+            obs_l, act_l, rew_l, nobs_l, term_l = m["rec"]
+            n = len(obs_l)
+            path = dict(observations=np.array(obs_l), actions=np.array(act_l), rewards=np.array(rew_l).reshape(n, 1),
+                        next_observations=np.array(nobs_l), terminals=np.array(term_l).reshape(n, 1),
+                        agent_infos=[{}] * n, env_infos=[{}] * n)
+            if n != m["mpl_max"] and not path["terminals"][-1] and m["discard"]:
+                m["live"] = False
+                return
+            m["collected"] += n
+            m["paths"].append(path)
+            begin(m)
+
+        for m in S:
+            begin(m)
+        while True:
+            ids = [i for i, m in enumerate(S) if m["live"]]
+            if not ids:
+                break
+            acts = holder_actions([parts[i][0] for i in ids], [S[i]["o"] for i in ids], [parts[i][1] for i in ids],
+                                  self._act_many)
+            for i, a in zip(ids, acts):
+                m, wrapper = S[i], parts[i][2]
+                if wrapper is not None:                       # PolicyWrappedWithExplorationStrategy.get_action
+                    a = wrapper.es.get_action_from_raw_action(a, wrapper.t)
+                no, r, d, _ = m["c"].env.step(a)
+                for lst, x in zip(m["rec"], (m["o"], a, r, no, d)):
+                    lst.append(x)
+                m["o"] = no
+                if d or len(m["rec"][0]) == m["mpl"]:
+                    finish(m)
+        for m in S:
+            c = m["c"]
+            c.num_paths_total += len(m["paths"])
+            c.num_steps_total += m["collected"]
+            c.epoch_paths.extend(m["paths"])
+        return [m["paths"] for m in S]
+
+
 def _stats(name, x):
     x = np.asarray(x, dtype=np.float64).ravel()
     return OrderedDict([(name + " Mean", float(np.mean(x))), (name + " Std", float(np.std(x))),
@@ -140,14 +251,19 @@ def _progress_row(buf, trainer, expl, evalc, ak):
 
 
 def experiment(variant, log_dir=None, seed=1, obs_dim=None, action_dim=None, num_epochs=None, device=0,
-               fused_loop=True, quiet=False, checkpoint_dir=None, resume=False):
+               fused_loop=True, quiet=False, checkpoint_dir=None, resume=False, acting="host"):
     """variant.json -> training run.  Returns the list of progress rows (also written to
     <log_dir>/progress.csv when log_dir is given).
 
     checkpoint_dir: after every epoch the full run state (networks, Adam moments, entropy coefficient, step
     counters, replay buffer, sampling stream, host generators) is saved there (`time/saving (s)`); with
     resume=True a run picks up after the last saved epoch and continues bit for bit -- the reference's own
-    snapshots (rlkit_custom.py:68-82) hold the networks only and cannot resume."""
+    snapshots (rlkit_custom.py:68-82) hold the networks only and cannot resume.
+
+    acting: "host" (the default: sac_policy_act, one observation per call from the mirrored weights) or "device"
+    (sac_policy_act_device: the collectors' get_action calls run k_act on the live weights).  A run of the general step
+    acts on the host either way (device acting serves the fused kernels' shapes)."""
+    check_acting(acting)
     validate(variant)
     np.random.seed(seed)                                          # scripts/train.py:112 (args.seed, not variant seed)
     O, A = env_dims(variant["expl_environment_kwargs"], obs_dim, action_dim)
@@ -173,6 +289,8 @@ def experiment(variant, log_dir=None, seed=1, obs_dim=None, action_dim=None, num
         eval_policy, expl_policy = MakeDeterministic(policy), policy
         trainer = SACTrainer(env=eval_env, policy=policy, qf1=qf1, qf2=qf2, target_qf1=tqf1, target_qf2=tqf2,
                              batch_size=ak["batch_size"], noise_seed=seed, device=device, **tk)
+    if acting == "device" and not runs_general_step(trainer):
+        policy.acting = "device"
     buf = EnvReplayBuffer(variant["replay_buffer_size"], obs_dim=O, action_dim=A, device=device)
     expl, evalc = PathCollector(expl_env, expl_policy), PathCollector(eval_env, eval_policy)
     rows, t_start = [], time.time()
@@ -246,11 +364,12 @@ def experiment(variant, log_dir=None, seed=1, obs_dim=None, action_dim=None, num
     return rows
 
 
-def _group_run(variant, seed, O, A, device, prefill=True):
+def _group_run(variant, seed, O, A, device, prefill=True, acting="host"):
     """One run of a grouped experiment, set up as experiment(variant, seed=seed) sets it up: its own synthetic
     environments, collectors, weights (from a private RandomState(seed), in the order experiment() draws them from
     np.random) and replay buffer (sampling a private stream continued from that generator), prefilled unless the run is
-    about to be restored from a checkpoint."""
+    about to be restored from a checkpoint.  acting as for experiment() (the prefill is this run's alone: its get_action
+    calls)."""
     td3 = variant.get("algorithm", "SAC") == "TD3"
     ak, tk = variant["algorithm_kwargs"], variant["trainer_kwargs"]
     rs = np.random.RandomState(seed)                          # experiment(): np.random.seed(seed), then the weights
@@ -273,6 +392,8 @@ def _group_run(variant, seed, O, A, device, prefill=True):
         eval_policy, expl_policy = MakeDeterministic(policy), policy
         trainer = SACTrainer(env=eval_env, policy=policy, qf1=qf1, qf2=qf2, target_qf1=tqf1, target_qf2=tqf2,
                              batch_size=ak["batch_size"], noise_seed=seed, device=device, **tk)
+    if acting == "device" and not runs_general_step(trainer):
+        policy.acting = "device"
     buf = EnvReplayBuffer(variant["replay_buffer_size"], obs_dim=O, action_dim=A, device=device)
     buf.seed_from_numpy(rs)                                   # (the stream np.random would continue with)
     expl, evalc = PathCollector(expl_env, expl_policy), PathCollector(eval_env, eval_policy)
@@ -317,15 +438,32 @@ def _group_save(ck, runs, epoch):
     ck.save([r["trainer"] for r in runs], [r["buf"] for r in runs], [r["identity"] for r in runs], extras)
 
 
-def _group_epochs(runs, train_block, n_epochs, n_train, log_dir, quiet, what, ck=None, first_epoch=0):
+def _group_epochs(runs, train_block, n_epochs, n_train, log_dir, quiet, what, ck=None, first_epoch=0, acting="host"):
     """The epoch loop of a grouped experiment: each run collects its paths, then train_block() trains every run at once,
     then every run ends its epoch, the group is saved (with a GroupCheckpoint `ck`), and each run writes its row (to
-    <log_dir>/<run["sub"]>/progress.csv with log_dir; appended to after a resume)."""
+    <log_dir>/<run["sub"]>/progress.csv with log_dir; appended to after a resume).
+    acting="device": the runs collect in lockstep (GroupPathCollector) -- the evaluation phase of all runs, then the
+    exploration phase of all runs, every tick's actions from one act_many call; each run's time/*sampling (s) columns
+    then hold the shared phase time."""
     t_start = time.time()
+    lock_eval = GroupPathCollector([r["evalc"] for r in runs]) if acting == "device" else None
+    lock_expl = GroupPathCollector([r["expl"] for r in runs]) if acting == "device" else None
     try:
         for epoch in range(first_epoch, n_epochs):
-            times = []
-            for r in runs:
+            times = []                                        # per run: (start, evaluation s, exploration s, storing s)
+            if acting == "device":
+                t0 = time.time()
+                lock_eval.collect_new_paths([(r["ak"]["eval_max_path_length"], r["ak"]["num_eval_steps_per_epoch"], True)
+                                             for r in runs])
+                t1 = time.time()
+                new = lock_expl.collect_new_paths([(r["ak"]["expl_max_path_length"],
+                                                    r["ak"]["num_expl_steps_per_train_loop"], False) for r in runs])
+                t2 = time.time()
+                for r, new_paths in zip(runs, new):
+                    s0 = time.time()
+                    r["buf"].add_paths(new_paths)
+                    times.append((t0, t1 - t0, t2 - t1, time.time() - s0))
+            for r in runs if acting != "device" else ():
                 ak = r["ak"]
                 t0 = time.time()
                 r["evalc"].collect_new_paths(ak["eval_max_path_length"], ak["num_eval_steps_per_epoch"], True)
@@ -333,7 +471,7 @@ def _group_epochs(runs, train_block, n_epochs, n_train, log_dir, quiet, what, ck
                 new_paths = r["expl"].collect_new_paths(ak["expl_max_path_length"], ak["num_expl_steps_per_train_loop"], False)
                 t2 = time.time()
                 r["buf"].add_paths(new_paths)
-                times.append((t0, t1, t2, time.time()))
+                times.append((t0, t1 - t0, t2 - t1, time.time() - t2))
             t3 = time.time()
             train_block()
             t4 = time.time()
@@ -347,11 +485,11 @@ def _group_epochs(runs, train_block, n_epochs, n_train, log_dir, quiet, what, ck
             if ck is not None:                                # one generation for the whole group
                 _group_save(ck, runs, epoch)
             t7 = time.time()
-            for r, (a0, a1, a2, a3), (row, t5) in zip(runs, times, ended):
+            for r, (a0, eval_s, expl_s, store_s), (row, t5) in zip(runs, times, ended):
                 t_end = t7 if ck is not None else t5
-                row["time/data storing (s)"] = a3 - a2
-                row["time/evaluation sampling (s)"] = a1 - a0
-                row["time/exploration sampling (s)"] = a2 - a1
+                row["time/data storing (s)"] = store_s
+                row["time/evaluation sampling (s)"] = eval_s
+                row["time/exploration sampling (s)"] = expl_s
                 row["time/logging (s)"] = t5 - t4
                 row["time/saving (s)"] = t7 - t6 if ck is not None else 0.0
                 row["time/training (s)"] = t4 - t3            # (the group's block: every run's steps at once)
@@ -381,7 +519,7 @@ def _group_epochs(runs, train_block, n_epochs, n_train, log_dir, quiet, what, ck
 
 
 def experiment_group(variant, seeds, log_dir=None, num_epochs=None, obs_dim=None, action_dim=None, device=0,
-                     quiet=False, checkpoint_dir=None, resume=False, chunk_rows=DEFAULT_CHUNK_ROWS):
+                     quiet=False, checkpoint_dir=None, resume=False, chunk_rows=DEFAULT_CHUNK_ROWS, acting="host"):
     """One configuration, several seeds, one process: each seed is the run ``experiment(variant, seed=s)`` would make --
     its own synthetic environments, collectors, weights and replay buffer -- and every epoch's training block is ONE
     SACTrainerGroup.train_loop (TD3 variants: TD3TrainerGroup; hidden sizes other than two layers of at most 256 units:
@@ -394,7 +532,11 @@ def experiment_group(variant, seeds, log_dir=None, num_epochs=None, obs_dim=None
     buffer in chunks of `chunk_rows` rows, only the chunks changed since the last save rewritten; `time/saving (s)`).
     resume=True continues the group saved in checkpoint_dir after its last saved epoch, bit for bit, appending to each
     seed's progress.csv; the seeds must be the saved ones in the saved order.  Without a checkpoint there it starts
-    afresh."""
+    afresh.
+    acting: "host" (the default: every run collects its own paths, one sac_policy_act call per step) or "device": the
+    runs collect in lockstep (GroupPathCollector), every tick's actions of all runs from ONE sac_policy_act_many launch
+    on the live weights; each run's rows are those of experiment(variant, seed=s, acting="device")."""
+    check_acting(acting)
     if resume and not checkpoint_dir:
         raise RuntimeError("experiment_group(resume=True) needs the checkpoint_dir to resume from")
     validate(variant)
@@ -407,7 +549,7 @@ def experiment_group(variant, seeds, log_dir=None, num_epochs=None, obs_dim=None
     runs = []
     restoring = bool(resume) and _checkpoint_exists(checkpoint_dir)
     for seed in seeds:
-        runs.append(_group_run(variant, seed, O, A, device, prefill=not restoring))
+        runs.append(_group_run(variant, seed, O, A, device, prefill=not restoring, acting=acting))
         runs[-1]["sub"] = f"s{seed}"
     ck, first_epoch = _group_checkpoint(runs, checkpoint_dir, restoring, chunk_rows)
     n_train = ak["num_trains_per_train_loop"]
@@ -420,7 +562,7 @@ def experiment_group(variant, seeds, log_dir=None, num_epochs=None, obs_dim=None
         train_block = lambda: group.train_loop([r["buf"] for r in runs], n_train, batch_size=ak["batch_size"])  # noqa: E731
     _group_epochs(runs, train_block,
                   num_epochs if num_epochs is not None else ak["num_epochs"], n_train, log_dir, quiet, "seeds", ck,
-                  first_epoch)
+                  first_epoch, acting)
     return {r["seed"]: r["rows"] for r in runs}
 
 
@@ -446,7 +588,7 @@ def sweep_label(variant, seed, hidden_sweep=False):
 
 
 def experiment_sweep(runs, log_dir=None, num_epochs=None, device=0, quiet=False, checkpoint_dir=None, resume=False,
-                     chunk_rows=DEFAULT_CHUNK_ROWS, hidden_sweep=False):
+                     chunk_rows=DEFAULT_CHUNK_ROWS, hidden_sweep=False, acting="host"):
     """Several tasks x seeds, one process, one device: every entry of ``runs`` -- (variant, seed), or (variant, seed,
     obs_dim, action_dim) for a task without pinned dims -- is the run ``experiment(variant, seed=seed)`` would make, and
     every epoch's training block is ONE MixedSACTrainerGroup.train_loop (TD3 variants: MixedTD3TrainerGroup; hidden sizes
@@ -459,7 +601,10 @@ def experiment_sweep(runs, log_dir=None, num_epochs=None, device=0, quiet=False,
     runs in the saved order.
     hidden_sweep=True: the runs may also differ in their policy / Q hidden sizes (a network-size sweep), the training
     block is ONE ArchSACTrainerGroup.train_loop (TD3: ArchTD3TrainerGroup), and each run's name carries its hidden
-    sizes: <task>-h<sizes>-s<seed>, or <task>-p<policy sizes>-q<Q sizes>-s<seed> (sweep_label)."""
+    sizes: <task>-h<sizes>-s<seed>, or <task>-p<policy sizes>-q<Q sizes>-s<seed> (sweep_label).
+    acting as for experiment_group; in a hidden sweep the runs of the general step act on the host inside the same
+    lockstep ticks (act_many), so each run's rows stay those of its solo experiment(..., acting="device")."""
+    check_acting(acting)
     if resume and not checkpoint_dir:
         raise RuntimeError("experiment_sweep(resume=True) needs the checkpoint_dir to resume from")
     specs = []
@@ -495,7 +640,7 @@ def experiment_sweep(runs, log_dir=None, num_epochs=None, device=0, quiet=False,
     group_runs = []
     restoring = bool(resume) and _checkpoint_exists(checkpoint_dir)
     for v, seed, O, A in specs:
-        group_runs.append(_group_run(v, seed, O, A, device, prefill=not restoring))
+        group_runs.append(_group_run(v, seed, O, A, device, prefill=not restoring, acting=acting))
         group_runs[-1]["sub"] = sweep_label(v, seed, hidden_sweep)
     ck, first_epoch = _group_checkpoint(group_runs, checkpoint_dir, restoring, chunk_rows)
     td3 = algo0 == "TD3"
@@ -509,5 +654,5 @@ def experiment_sweep(runs, log_dir=None, num_epochs=None, device=0, quiet=False,
     batches = [r["ak"]["batch_size"] for r in group_runs]
     _group_epochs(group_runs, lambda: group.train_loop([r["buf"] for r in group_runs], n_train, batch_sizes=batches),
                   num_epochs if num_epochs is not None else ak0["num_epochs"], n_train, log_dir, quiet, "runs", ck,
-                  first_epoch)
+                  first_epoch, acting)
     return [r["rows"] for r in group_runs]

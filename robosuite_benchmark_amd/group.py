@@ -33,6 +33,47 @@ def runs_general_step(t):
     return _general_shape(t._hidden("policy")) or _general_shape(t._hidden("qf1"))
 
 
+def act_many(trainers, obs_list, deterministic_list, eps_list):
+    """policy.get_actions for many runs at once: actions[i] = trainers[i]'s policy on obs_list[i] ((n_i, O_i); None or no
+    rows: the member sits out and gets an empty array), deterministic_list[i] as MakeDeterministic, eps_list[i] the
+    (n_i, A_i) N(0,1) draws of a stochastic SAC member (None otherwise).  The members with the fused kernels' shapes act
+    in ONE launch per 16 of them (sac_policy_act_many: SAC and TD3, dims and row counts mixed; up to 1024 rows each);
+    members of the general step act on the host through their own policy_act.  A member's actions never depend on its
+    neighbours: they are bit for bit those of its own policy_act_device (policy_act for the general step)."""
+    trainers = list(trainers)
+    R = len(trainers)
+    if not (len(obs_list) == len(deterministic_list) == len(eps_list) == R):
+        raise RuntimeError("act_many takes one observation array, deterministic flag and eps per trainer")
+    if len({id(t) for t in trainers}) != R:
+        raise RuntimeError("a trainer appears twice in act_many")
+    obs = [None if o is None else _lib.f32(np.atleast_2d(o)) for o in obs_list]
+    eps = [None if e is None else _lib.f32(np.atleast_2d(e)) for e in eps_list]
+    out = [np.empty((0 if o is None else o.shape[0], t.act_dim), np.float32) for t, o in zip(trainers, obs)]
+    dev = []
+    for i, t in enumerate(trainers):
+        if out[i].shape[0] == 0:
+            continue
+        if obs[i].shape[1] != t.obs_dim or (eps[i] is not None and eps[i].shape != out[i].shape):
+            raise RuntimeError(f"act_many member {i}: observations {obs[i].shape} / eps "
+                               f"{None if eps[i] is None else eps[i].shape} do not fit dims ({t.obs_dim}, {t.act_dim})")
+        if out[i].shape[0] > _lib.ACT_MAX_ROWS:
+            raise RuntimeError(f"act_many member {i}: {out[i].shape[0]} rows (at most {_lib.ACT_MAX_ROWS} per call)")
+        if runs_general_step(t):
+            out[i] = t.policy_act(obs[i], deterministic_list[i], eps[i])
+        else:
+            dev.append(i)
+    lib = _lib.load()
+    for c in range(0, len(dev), MAX_MEMBERS):
+        ids = dev[c:c + MAX_MEMBERS]
+        n = len(ids)
+        vp = lambda arrs: (C.c_void_p * n)(*[None if a is None else a.ctypes.data for a in arrs])  # noqa: E731
+        _lib.check(lib.sac_policy_act_many((C.c_void_p * n)(*[trainers[i]._h.value for i in ids]), n,
+                                           (C.c_int32 * n)(*[out[i].shape[0] for i in ids]), vp([obs[i] for i in ids]),
+                                           (C.c_int32 * n)(*[int(bool(deterministic_list[i])) for i in ids]),
+                                           vp([eps[i] for i in ids]), vp([out[i] for i in ids])), "sac_policy_act_many")
+    return out
+
+
 class _Members:
     """The member checks that hold for every kind of trainer group (host metadata: nothing is created for a group that
     cannot exist).  The algorithm comes from _SACMembers / _TD3Members."""

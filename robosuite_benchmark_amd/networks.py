@@ -56,7 +56,27 @@ def process_seed():
     return (zlib.crc32(np.ascontiguousarray(st[1], np.uint32).tobytes()) << 10) ^ int(st[2])
 
 
+ACTING = ("host", "device")
+
+
+def check_acting(acting):
+    """'host': the acting path of sac_policy_act (the default); 'device': sac_policy_act_device / sac_policy_act_many."""
+    if acting not in ACTING:
+        raise ValueError(f"acting must be one of {ACTING}, got {acting!r}")
+    return acting
+
+
 class _Mlp:
+    # where a policy bound to a trainer acts (TanhGaussianPolicy, TanhMlpPolicy): "host" -- sac_policy_act, one
+    # observation row per call from the mirrored weights -- or "device" -- sac_policy_act_device, every row of a call in
+    # one launch from the live weights.  The exploration noise is drawn on the host from the same stream either way.
+    acting = "host"
+
+    def _act(self, tr, obs, deterministic, eps):
+        if check_acting(self.acting) == "device":
+            return tr.policy_act_device(obs, deterministic, eps)
+        return tr.policy_act(obs, deterministic, eps)
+
     def __init__(self, hidden_sizes, output_sizes, input_size, init_w, rs=None, b_init_value=0.1):
         # b_init_value: rlkit Mlp's constant hidden bias -- 0.1 at the commit the reference pins (b7f97b2,
         # /root/reference/README.md:28; later rlkit: 0).  Unpinned: rlkit is not vendored and no shipped artefact
@@ -180,7 +200,7 @@ class TanhGaussianPolicy(_Mlp):
         if tr is not None and getattr(tr, "_h", None) is not None and tr.policy is self:
             # the library's acting entry (sac_policy_act: host forward from the policy mirrored D2H once per
             # training block) -- ONE implementation of the acting path once a trainer owns the weights
-            return tr.policy_act(obs, deterministic, eps)
+            return self._act(tr, obs, deterministic, eps)
         mean, log_std = self._trunk(obs)           # holder without a trainer (no device state yet)
         if deterministic:
             return np.tanh(mean)
@@ -234,7 +254,7 @@ class TanhMlpPolicy(_Mlp):
         obs = np.ascontiguousarray(np.atleast_2d(obs_np), dtype=np.float32)
         tr = self._trainer
         if tr is not None and getattr(tr, "_h", None) is not None and tr.policy is self:
-            return tr.policy_act(obs, True, None)  # sac_policy_act (TD3 handles: tanh(last_fc))
+            return self._act(tr, obs, True, None)  # sac_policy_act[_device] (TD3 handles: tanh(last_fc))
         h = obs
         names = list(self.layers)
         for n in names[:-1]:

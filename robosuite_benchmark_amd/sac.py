@@ -263,6 +263,21 @@ class SACTrainer:
                                                 out[i].ctypes.data_as(C.c_void_p)), "sac_policy_act")
         return out
 
+    def policy_act_device(self, obs, deterministic, eps):
+        """policy.get_actions on the DEVICE from the live weights (sac_policy_act_device): all rows of `obs` in one launch
+        per 1024 rows, no mirror of the policy on the host.  Trainers of the general step are refused by the library: they
+        act through policy_act."""
+        obs = _lib.f32(obs)
+        n, A = obs.shape[0], self.act_dim
+        out = np.empty((n, A), np.float32)
+        e = None if eps is None else _lib.f32(eps)
+        for i in range(0, n, _lib.ACT_MAX_ROWS):
+            j = min(n, i + _lib.ACT_MAX_ROWS)
+            _lib.check(self._lib.sac_policy_act_device(self._h, j - i, _lib.ptr(obs[i:j]), int(bool(deterministic)),
+                                                       None if e is None else _lib.ptr(e[i:j]), _lib.ptr(out[i:j])),
+                       "sac_policy_act_device")
+        return out
+
     def refresh_host_policy(self):
         """Mirror the trained policy D2H once per training block (acting stays on the host)."""
         if self._h is not None and self._host_policy_stale:

@@ -1,0 +1,137 @@
+"""Acting: the host path (sac_policy_act, one observation per call) against the device path (k_act through
+sac_policy_act_device / sac_policy_act_many), and what the lockstep collection of a 16-seed group epoch gains from it.
+One JSON line per measurement, appended to --out (default: stdout only).
+
+    python scripts/bench_acting.py [--windows 3] [--window-s 1.0] [--seeds 16] [--rounds 2] [--out FILE]
+    python scripts/bench_acting.py --profile-pass       # a short run of the device calls alone, for a kernel trace
+
+Every timed call returns with its actions on the host (the calls end synchronised), so a host clock around a window of
+calls measures them; a window lasts at least --window-s seconds after a warm-up, and each figure is the median over
+--windows windows with the smallest and the largest next to it.  (d) runs experiment_group with --seeds seeds of the
+default Lift variant for one epoch at its default step counts, acting="host" and acting="device" alternating --rounds
+times, and reports each mode's evaluation + exploration seconds of that epoch."""
+from __future__ import annotations
+
+import argparse
+import copy
+import json
+import os
+import sys
+import time
+
+import numpy as np
+
+sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
+
+from robosuite_benchmark_amd import FlattenMlp, SACTrainer, TanhGaussianPolicy  # noqa: E402
+from robosuite_benchmark_amd.group import act_many  # noqa: E402
+
+O, A = 42, 7                                        # Lift
+
+
+def make_trainer(seed, B=256):
+    rs = np.random.RandomState(seed)
+    qs = [FlattenMlp([256, 256], 1, O + A, rs=rs) for _ in range(4)]
+    pol = TanhGaussianPolicy([256, 256], O, A, rs=rs, noise=np.random.RandomState(seed))
+    return SACTrainer(policy=pol, qf1=qs[0], qf2=qs[1], target_qf1=qs[2], target_qf2=qs[3], batch_size=B, noise_seed=seed)
+
+
+def windows(fn, n_windows, window_s, warm_s=0.2):
+    """us per call of fn(): median, min, max over n_windows windows of at least window_s seconds each."""
+    t_end = time.perf_counter() + warm_s
+    while time.perf_counter() < t_end:
+        fn()
+    per = []
+    for _ in range(n_windows):
+        n, t0 = 0, time.perf_counter()
+        while True:
+            for _ in range(20):
+                fn()
+            n += 20
+            dt = time.perf_counter() - t0
+            if dt >= window_s:
+                break
+        per.append(1e6 * dt / n)
+    return dict(us_median=float(np.median(per)), us_min=float(min(per)), us_max=float(max(per)), windows=n_windows)
+
+
+def emit(rec, out):
+    line = json.dumps(rec)
+    print(line, flush=True)
+    if out:
+        with open(out, "a") as fh:
+            fh.write(line + "\n")
+
+
+def call_benches(args):
+    rs = np.random.RandomState(0)
+    t = make_trainer(1)
+    obs1, eps1 = rs.normal(0, 0.5, (1, O)).astype(np.float32), rs.normal(size=(1, A)).astype(np.float32)
+    emit(dict(what="a: sac_policy_act, host, per row", **windows(lambda: t.policy_act(obs1, False, eps1),
+                                                                args.windows, args.window_s)), args.out)
+    for n in (1, 16, 256, 1000):
+        obs, eps = rs.normal(0, 0.5, (n, O)).astype(np.float32), rs.normal(size=(n, A)).astype(np.float32)
+        emit(dict(what="b: sac_policy_act_device, per call", n=n,
+                  **windows(lambda: t.policy_act_device(obs, False, eps), args.windows, args.window_s)), args.out)
+    ts = [make_trainer(10 + i) for i in range(16)]
+    obs_l, eps_l = [obs1.copy() for _ in ts], [eps1.copy() for _ in ts]
+    det = [False] * 16
+    emit(dict(what="c: sac_policy_act_many, 16 Lift members x 1 row, per call (group.act_many)",
+              **windows(lambda: act_many(ts, obs_l, det, eps_l), args.windows, args.window_s)), args.out)
+
+
+def epoch_bench(args):
+    from robosuite_benchmark_amd.driver import experiment_group
+    from robosuite_benchmark_amd.variant import default_variant
+    v = default_variant(env="Lift", seed=1, batch_size=256)
+    v["replay_buffer_size"] = 100000                  # (one epoch never fills it; 16 full-size buffers only cost set-up time)
+    seeds = list(range(1, args.seeds + 1))
+    res = {"host": [], "device": []}
+    for rnd in range(args.rounds):
+        for mode in ("host", "device"):
+            rows = experiment_group(copy.deepcopy(v), seeds, num_epochs=1, quiet=True, acting=mode)
+            ev = [rows[s][0]["time/evaluation sampling (s)"] for s in seeds]
+            ex = [rows[s][0]["time/exploration sampling (s)"] for s in seeds]
+            # host: the runs collect one after another (the sum over runs); device: one shared phase (any run's column)
+            sampling = sum(ev) + sum(ex) if mode == "host" else ev[0] + ex[0]
+            res[mode].append(dict(sampling_s=sampling, training_s=rows[seeds[0]][0]["time/training (s)"]))
+    ak = v["algorithm_kwargs"]
+    emit(dict(what="d: evaluation + exploration seconds of one experiment_group epoch", seeds=args.seeds,
+              eval_steps=ak["num_eval_steps_per_epoch"], expl_steps=ak["num_expl_steps_per_train_loop"],
+              trains=ak["num_trains_per_train_loop"], rounds=args.rounds,
+              host_sampling_s=[r["sampling_s"] for r in res["host"]], device_sampling_s=[r["sampling_s"] for r in res["device"]],
+              host_training_s=[r["training_s"] for r in res["host"]], device_training_s=[r["training_s"] for r in res["device"]],
+              host_over_device=float(np.median([r["sampling_s"] for r in res["host"]])
+                                     / np.median([r["sampling_s"] for r in res["device"]]))), args.out)
+
+
+def profile_pass():
+    rs = np.random.RandomState(0)
+    ts = [make_trainer(10 + i) for i in range(16)]
+    for n in (1, 16, 256, 1000):
+        obs, eps = rs.normal(0, 0.5, (n, O)).astype(np.float32), rs.normal(size=(n, A)).astype(np.float32)
+        for _ in range(200):
+            ts[0].policy_act_device(obs, False, eps)
+    obs_l = [rs.normal(0, 0.5, (1, O)).astype(np.float32) for _ in ts]
+    eps_l = [rs.normal(size=(1, A)).astype(np.float32) for _ in ts]
+    for _ in range(200):
+        act_many(ts, obs_l, [False] * 16, eps_l)
+    print("profile pass: 4 x 200 solo calls (n = 1, 16, 256, 1000), 200 grouped calls of 16 x 1 row", flush=True)
+
+
+if __name__ == "__main__":
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--windows", type=int, default=3)
+    ap.add_argument("--window-s", type=float, default=1.0)
+    ap.add_argument("--seeds", type=int, default=16)
+    ap.add_argument("--rounds", type=int, default=2)
+    ap.add_argument("--out", type=str, default=None)
+    ap.add_argument("--skip-epoch", action="store_true", help="only the per-call measurements (a) to (c)")
+    ap.add_argument("--profile-pass", action="store_true")
+    args = ap.parse_args()
+    if args.profile_pass:
+        profile_pass()
+        sys.exit(0)
+    call_benches(args)
+    if not args.skip_epoch:
+        epoch_bench(args)

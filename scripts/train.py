@@ -10,7 +10,8 @@
  DIR/checkpoint after every epoch; the same command line with --resume DIR instead of --log_dir DIR continues it.
  --hidden_sweep: the --variants may differ in their hidden sizes, one arch trainer group trains them all;
  DIR/<task>-h<sizes>-s<seed>/progress.csv each.  --hidden_sizes H1 H2 ...: every variant once per entry, policy and Q
- nets alike, implies --hidden_sweep)
+ nets alike, implies --hidden_sweep.  --acting device: the policies act through the device kernel instead of the
+ host forward; grouped runs then collect their paths in lockstep)
 Runs the variant unchanged (batch size, lrs, tau, period, buffer size ... from the JSON) on the
 HIP library with a synthetic environment of the task's dimensions (robosuite is not installed)."""
 import argparse
@@ -50,6 +51,10 @@ if __name__ == "__main__":
     ap.add_argument("--hidden_sizes", type=str, nargs="+", default=None,
                     help="with --variants: train every variant once per entry (comma-separated widths, e.g. 256,256 "
                          "512,512 256,256,256), policy and Q nets alike; implies --hidden_sweep")
+    ap.add_argument("--acting", type=str, default="host", choices=["host", "device"],
+                    help="where the collectors' policies act: host (sac_policy_act, one observation per call) or device "
+                         "(the policy forward as a HIP kernel on the live weights; with --seeds / --variants the runs "
+                         "collect in lockstep, all their actions of a tick from one launch)")
     args = ap.parse_args()
     if (args.hidden_sweep or args.hidden_sizes) and not args.variants:
         raise SystemExit("--hidden_sweep / --hidden_sizes need --variants")
@@ -57,7 +62,7 @@ if __name__ == "__main__":
         log_dir = args.resume or args.log_dir
         if args.checkpoint and not log_dir:
             raise SystemExit("--checkpoint needs --log_dir (the group is saved to <log_dir>/checkpoint)")
-        group_kw = dict(log_dir=log_dir, num_epochs=args.epochs, resume=bool(args.resume),
+        group_kw = dict(log_dir=log_dir, num_epochs=args.epochs, resume=bool(args.resume), acting=args.acting,
                         checkpoint_dir=os.path.join(log_dir, "checkpoint") if (args.checkpoint or args.resume) else None)
         try:
             if args.variants:
@@ -94,4 +99,4 @@ if __name__ == "__main__":
         json.dump(variant, open(os.path.join(run_dir, "variant.json"), "w"), indent=2, sort_keys=True)
     ckpt = os.path.join(run_dir, "checkpoint") if (run_dir and not args.no_checkpoint) else None
     experiment(variant, log_dir=run_dir, seed=args.seed, num_epochs=args.epochs, checkpoint_dir=ckpt,
-               resume=bool(args.resume))
+               resume=bool(args.resume), acting=args.acting)
