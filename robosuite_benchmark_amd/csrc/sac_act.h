@@ -41,6 +41,27 @@ struct ActMember {
     int stochastic, pad;           // 1: SAC with exploration noise
 };
 
+// The hidden layers' bias + ReLU of k_act.  It stands in for the step kernels' hidden_epilogue, whose ReLU is
+// fmaxf(x, 0): that gives 0 for NaN and would turn a non-finite observation row into a finite action, where torch's relu
+// and the host forward keep the NaN.  Here x < 0 ? 0 : x; every finite value comes out as from fmaxf, up to the sign of
+// a zero, which no sum downstream can see.  With hidden sizes below 256 an Inf observation becomes NaN already in the
+// zero-weight pad units (0 * inf) and from there in every unit of the next layer; torch has no pad units but reaches NaN
+// in its second layer too, through inf - inf over units of both signs, so the actions agree (NaN) all the same.
+template <int NT>
+__device__ __forceinline__ void act_hidden_epilogue(const f32x4 (&acc)[NT], int n_base, int n_stride, const float (&bv)[NT],
+                                                    float *Xn, int KL) {
+    const int lane = threadIdx.x & 63, c = lane & 15, g = lane >> 4;
+#pragma unroll
+    for (int t = 0; t < NT; ++t) {
+        const int n = n_base + t * n_stride + c;
+#pragma unroll
+        for (int i = 0; i < 4; ++i) {
+            const float v = acc[t][i] + bv[t];
+            Xn[lds_off(4 * g + i, n, KL)] = v < 0.f ? 0.f : v;
+        }
+    }
+}
+
 __global__ __launch_bounds__(256) void k_act(const ActMember *__restrict__ tab, int n_members) {
     extern __shared__ __attribute__((aligned(16))) float lds[];
     // this workgroup's member: the last one whose first workgroup is not behind this one (wave-uniform, scalar loads)
@@ -74,11 +95,10 @@ __global__ __launch_bounds__(256) void k_act(const ActMember *__restrict__ tab, 
         }
     }
     lds_barrier();
-    f32x4 keep[4];
     {
         f32x4 acc[4] = {};
         gemm_ring(r0, X0, KL0, KP >> 4, acc);
-        hidden_epilogue<4>(acc, 64 * wave, 16, bv0, X1, H, keep);
+        act_hidden_epilogue<4>(acc, 64 * wave, 16, bv0, X1, H);
     }
     WRing<4> r1;
     r1.init(P + sload(&M->offW[1]), H, 64 * wave, 16);
@@ -87,7 +107,7 @@ __global__ __launch_bounds__(256) void k_act(const ActMember *__restrict__ tab, 
     {
         f32x4 acc[4] = {};
         gemm_ring(r1, X1, H, H >> 4, acc);
-        hidden_epilogue<4>(acc, 64 * wave, 16, bv1, X2, H, keep);
+        act_hidden_epilogue<4>(acc, 64 * wave, 16, bv1, X2, H);
     }
     lds_barrier();
     if (16 * wave < NH) {                // head rows 16 wave .. 16 wave + 15 (wave-uniform)

@@ -3419,7 +3419,7 @@ int sac_policy_act(sac_trainer_t *t, const float *obs, int deterministic, const 
         for (int n = 0; n < hs[l]; ++n) {
             float s = b[n];
             for (int k = 0; k < dprev; ++k) s += W[(size_t)n * dprev + k] * hin[(size_t)k];
-            hout[(size_t)n] = s > 0.f ? s : 0.f;
+            hout[(size_t)n] = s < 0.f ? 0.f : s;         // (a NaN stays a NaN, as in torch's relu)
         }
         hin.swap(hout);
         p = b + hs[l];

@@ -117,6 +117,8 @@ class SACTrainer:
     def _set_params(self, name, flat):
         flat = _lib.f32(flat)
         _lib.check(self._lib.sac_set_params(self._h, self.NETS[name], _lib.ptr(flat), flat.size), "sac_set_params")
+        if name == "policy":
+            self._host_policy_stale = True           # (the holder's arrays are refreshed at their next use)
 
     def _get_params(self, name):
         n = int(self._lib.sac_param_count(self._h, self.NETS[name]))

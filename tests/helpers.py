@@ -1,4 +1,5 @@
 """Shared helpers for the parity tests (test infrastructure; may import oracle/)."""
+import os
 from collections import OrderedDict
 
 import numpy as np
@@ -481,3 +482,107 @@ def check_optimizer_step(hip, before, after, cfg, path):
     assert ulp_distance(alpha, ea) <= 2, (path, step, "Alpha != exp(log_alpha)", alpha, float(ea))
     rec = OPT_ULPS.setdefault(path, {})
     rec["alpha"] = max(rec.get("alpha", 0.0), float(ulp_distance(alpha, ea)))
+
+
+# ---- trainers and buffers several GPU test files share -------------------------------------------------------------------
+def pair_of_hip(O, A, B, seed, noise_seed, **env):
+    """(fused, four-launch) trainers with identical parameters."""
+    old = {k: os.environ.get(k) for k in ("SAC_FUSED", "SAC_FUSED_TEST_STALL")}
+    try:
+        os.environ.pop("SAC_FUSED", None)
+        for k, v in env.items():
+            os.environ[k] = str(v)
+        _, fused = make_pair(O, A, B, seed=seed, noise_seed=noise_seed)
+        os.environ.pop("SAC_FUSED_TEST_STALL", None)
+        os.environ["SAC_FUSED"] = "0"
+        _, plain = make_pair(O, A, B, seed=seed, noise_seed=noise_seed)
+    finally:
+        for k, v in old.items():
+            if v is None:
+                os.environ.pop(k, None)
+            else:
+                os.environ[k] = v
+    return fused, plain
+
+
+def plain_buffer(n, O, A, seed):
+    from robosuite_benchmark_amd import EnvReplayBuffer
+    obs, act, rew, term, nobs = synth_transitions(n, O, A, seed=seed, term_frac=0.05)
+    buf = EnvReplayBuffer(n, obs_dim=O, action_dim=A)
+    buf.add_block(obs, act, rew, nobs, term)
+    return buf
+
+
+def filled_buffer(n, O, A, seed):
+    from robosuite_benchmark_amd import EnvReplayBuffer
+    obs, act, rew, term, nobs = synth_transitions(n, O, A, seed=seed, term_frac=0.1)
+    buf = EnvReplayBuffer(n, obs_dim=O, action_dim=A)
+    buf.add_block(obs, act, rew, nobs, term)
+    buf.seed(seed)
+    return buf
+
+
+# ---- acting: the policy's forward against oracle.sac_step_torch.PolicyNet ----------------------------------------------
+def act_reference(layers, td3, obs, deterministic, eps, dtype):
+    """policy.get_actions of the oracle: tanh(mean) or tanh(mean + exp(clamp(log_std)) * eps) on `layers` (the oracle's
+    layer list; TD3: the TanhMlpPolicy's, tanh(last_fc)) in `dtype`."""
+    from oracle.sac_step_torch import PolicyNet
+    if td3:                                         # TanhMlpPolicy = PolicyNet's mean head (its log_std head is unused)
+        layers, deterministic = list(layers) + [layers[-1]], True
+    net = PolicyNet(layers, dtype=dtype)
+    with torch.no_grad():
+        mean, log_std = net.trunk(torch.from_numpy(obs).to(dtype))
+        z = mean if deterministic else mean + torch.exp(log_std) * torch.from_numpy(eps).to(dtype)
+        return torch.tanh(z).numpy()
+
+
+ACT_ATOL, ACT_F64_FACTOR = 2e-5, 8.0        # the constants of test_gpu_device_acting.check_against_oracle
+ACT_ERRORS = {}             # tag -> [largest |K - f64|, the fp32 oracle's |P - f64| of that call, the call], for reporting
+
+
+def check_act(trainer, got, layers, obs, det, eps, where, tag=None):
+    """One acting call of either implementation (k_act or the host forward) against PolicyNet on `layers`:
+    max|K - R| <= max(2e-5, 8 max|P - R|) with R the float64 and P the fp32 oracle, and atol 2e-5 against P.  The
+    second holds only where the fp32 oracle is well conditioned, 8 max|P - R| <= 2e-5: that is asserted first, so the
+    fp32 check never drops out silently (tests/test_acting_edges_host.py asserts it for every case of the edge matrix;
+    at init and on trained weights P is closer still).  Returns the float64 bound of this call."""
+    td3 = "target_policy" in trainer.NETS
+    w32, w64 = act_reference(layers, td3, obs, det, eps, torch.float32), act_reference(layers, td3, obs, det, eps, torch.float64)
+    e_k32, e_k64 = float(np.max(np.abs(got - w32))), float(np.max(np.abs(got.astype(np.float64) - w64)))
+    e_32 = float(np.max(np.abs(w32.astype(np.float64) - w64)))
+    print(f"{where}: |K - fp32 oracle| {e_k32:.3g}  |K - f64| {e_k64:.3g}  |fp32 oracle - f64| {e_32:.3g}")
+    if tag is not None and not e_k64 < ACT_ERRORS.get(tag, [-1.0])[0]:
+        ACT_ERRORS[tag] = [e_k64, e_32, str(where)]
+    bound = max(ACT_ATOL, ACT_F64_FACTOR * e_32)
+    assert ACT_F64_FACTOR * e_32 <= ACT_ATOL, (where, "the fp32 oracle is not well conditioned here", e_32)
+    assert got.shape == w64.shape and np.all(np.isfinite(got)), (where, got.shape)
+    assert e_k64 <= bound, (where, e_k64, e_32)
+    assert np.allclose(got, w32, atol=ACT_ATOL), (where, e_k32)
+    return bound
+
+
+def is_td3(t):
+    return "target_policy" in t.NETS
+
+
+def draws(rs, n, O, A):
+    return rs.normal(0, 0.4, (n, O)).astype(np.float32), rs.normal(size=(n, A)).astype(np.float32)
+
+
+def act_c(t, obs, deterministic, eps):
+    """sac_policy_act_device through the C ABI."""
+    from robosuite_benchmark_amd import _lib
+    out = np.full((obs.shape[0], t.act_dim), 7.0, np.float32)
+    _lib.check(_lib.load().sac_policy_act_device(t._h, obs.shape[0], _lib.ptr(obs), int(deterministic), _lib.ptr(eps),
+                                                 _lib.ptr(out)), "sac_policy_act_device")
+    return out
+
+
+ACT_NETS = ("policy", "qf1", "qf2", "target_qf1", "target_qf2")
+
+
+def full_state(t, buf):
+    st = t.state_dict()
+    k, p = buf.rng_state()
+    return ([st["params"][n] for n in ACT_NETS] + [x for n in ("policy", "qf1", "qf2") for x in st["opt"][n]]
+            + [st["scalars"], np.asarray(k), np.asarray([p])])

@@ -14,24 +14,19 @@ import numpy as np
 import pytest
 import torch
 
-from oracle.sac_step_torch import PolicyNet
-from robosuite_benchmark_amd import (EnvReplayBuffer, MixedSACTrainerGroup, SACTrainerGroup, _lib)
+from robosuite_benchmark_amd import MixedSACTrainerGroup, SACTrainerGroup, _lib
 from robosuite_benchmark_amd.group import act_many
-from tests.helpers import layers_from_flat, make_pair, make_pair_from_flat, make_td3_pair, synth_transitions
+from tests.helpers import (act_c, act_reference, draws, filled_buffer, full_state, is_td3, layers_from_flat, make_pair,
+                           make_pair_from_flat, make_td3_pair)
 
 pytestmark = pytest.mark.gpu
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 ROWS = (1, 5, 16, 17, 64, 1000)
-NETS = ("policy", "qf1", "qf2", "target_qf1", "target_qf2")
 
 
 def trained_flats():
     z = np.load(os.path.join(ROOT, "tests", "golden", "trained_weights_lift_seed129.npz"))
     return {k: z[k] for k in z.files}
-
-
-def is_td3(t):
-    return "target_policy" in t.NETS
 
 
 def policy_layers(t):
@@ -42,14 +37,7 @@ def policy_layers(t):
 
 
 def reference(t, obs, deterministic, eps, dtype):
-    layers = policy_layers(t)
-    if is_td3(t):                                   # TanhMlpPolicy = PolicyNet's mean head (its log_std head is unused)
-        layers, deterministic = layers + [layers[-1]], True
-    net = PolicyNet(layers, dtype=dtype)
-    with torch.no_grad():
-        mean, log_std = net.trunk(torch.from_numpy(obs).to(dtype))
-        z = mean if deterministic else mean + torch.exp(log_std) * torch.from_numpy(eps).to(dtype)
-        return torch.tanh(z).numpy()
+    return act_reference(policy_layers(t), is_td3(t), obs, deterministic, eps, dtype)
 
 
 def check_against_oracle(t, got, obs, deterministic, eps, where):
@@ -59,18 +47,6 @@ def check_against_oracle(t, got, obs, deterministic, eps, where):
     print(f"{where}: |device - fp32 oracle| {e_k32:.3g}  |device - f64| {e_k64:.3g}  |fp32 oracle - f64| {e_32:.3g}")
     assert np.allclose(got, w32, atol=2e-5), (where, e_k32)
     assert e_k64 <= max(2e-5, 8.0 * e_32), (where, e_k64, e_32)
-
-
-def draws(rs, n, O, A):
-    return rs.normal(0, 0.4, (n, O)).astype(np.float32), rs.normal(size=(n, A)).astype(np.float32)
-
-
-def act_c(t, obs, deterministic, eps):
-    """sac_policy_act_device through the C ABI."""
-    out = np.full((obs.shape[0], t.act_dim), 7.0, np.float32)
-    _lib.check(_lib.load().sac_policy_act_device(t._h, obs.shape[0], _lib.ptr(obs), int(deterministic), _lib.ptr(eps),
-                                                 _lib.ptr(out)), "sac_policy_act_device")
-    return out
 
 
 def sweep_rows(t, seed, where):
@@ -161,14 +137,6 @@ def test_grouped_equals_solo_bitwise(R):
 
 
 # ---- 4. live weights --------------------------------------------------------------------------------------------------
-def filled_buffer(n, O, A, seed):
-    obs, act, rew, term, nobs = synth_transitions(n, O, A, seed=seed, term_frac=0.1)
-    buf = EnvReplayBuffer(n, obs_dim=O, action_dim=A)
-    buf.add_block(obs, act, rew, nobs, term)
-    buf.seed(seed)
-    return buf
-
-
 def test_acting_follows_the_live_weights():
     O, A, B = 42, 7, 64
     rs = np.random.RandomState(6)
@@ -213,13 +181,6 @@ def test_acting_follows_the_live_weights():
 
 
 # ---- 5. acting disturbs nothing ---------------------------------------------------------------------------------------
-def full_state(t, buf):
-    st = t.state_dict()
-    k, p = buf.rng_state()
-    return ([st["params"][n] for n in NETS] + [x for n in ("policy", "qf1", "qf2") for x in st["opt"][n]]
-            + [st["scalars"], np.asarray(k), np.asarray([p])])
-
-
 def test_acting_disturbs_nothing():
     O, A, B = 42, 7, 64
     (_, a), (_, b) = make_pair(O, A, B, seed=12, noise_seed=5), make_pair(O, A, B, seed=12, noise_seed=5)

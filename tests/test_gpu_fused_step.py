@@ -7,37 +7,9 @@ import numpy as np
 import pytest
 
 from robosuite_benchmark_amd._lib import DIAG_NAMES
-from tests.helpers import make_pair, synth_transitions
+from tests.helpers import make_pair, plain_buffer as _buffer, pair_of_hip as _pair_of_hip, synth_transitions
 
 pytestmark = pytest.mark.gpu
-
-
-def _pair_of_hip(O, A, B, seed, noise_seed, **env):
-    """(fused, four-launch) trainers with identical parameters."""
-    old = {k: os.environ.get(k) for k in ("SAC_FUSED", "SAC_FUSED_TEST_STALL")}
-    try:
-        os.environ.pop("SAC_FUSED", None)
-        for k, v in env.items():
-            os.environ[k] = str(v)
-        _, fused = make_pair(O, A, B, seed=seed, noise_seed=noise_seed)
-        os.environ.pop("SAC_FUSED_TEST_STALL", None)
-        os.environ["SAC_FUSED"] = "0"
-        _, plain = make_pair(O, A, B, seed=seed, noise_seed=noise_seed)
-    finally:
-        for k, v in old.items():
-            if v is None:
-                os.environ.pop(k, None)
-            else:
-                os.environ[k] = v
-    return fused, plain
-
-
-def _buffer(n, O, A, seed):
-    from robosuite_benchmark_amd import EnvReplayBuffer
-    obs, act, rew, term, nobs = synth_transitions(n, O, A, seed=seed, term_frac=0.05)
-    buf = EnvReplayBuffer(n, obs_dim=O, action_dim=A)
-    buf.add_block(obs, act, rew, nobs, term)
-    return buf
 
 
 def _same(sa, sb):
