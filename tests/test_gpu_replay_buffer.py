@@ -143,8 +143,6 @@ def test_device_batched_gather_matches_per_call_batches():
     dev.seed(59)
     rs = np.random.RandomState(59)
     dev.sample_gather_device(256, 37)
-    for s in (0, 1, 17, 36):
-        pass
     want_idx = np.stack([rs.randint(0, 20_000, 256) for _ in range(37)])
     for s in (0, 1, 17, 36):
         got, gidx = dev.read_slot(s, 256)
