@@ -415,6 +415,31 @@ int sac_group_destroy(sac_group_t *g);
 int sac_group_train_loop(sac_group_t *g, sac_buffer_t *const *buffers, int64_t n_steps, float *diag_first,
                          float *diag_last);
 
+/* ------------------------------------------------------------------------------------------
+ * Acting sessions: sac_policy_act_many for a FIXED list of trainers without the per-call marshalling (csrc/sac_actor.h).
+ * A session owns one mapped pinned slab that holds every member's observations, eps and actions at fixed addresses --
+ * the caller writes and reads them in place, a call copies nothing -- and a member table in device memory that is
+ * written once, at creation.  sac_actor_act rewrites a 256-byte control block (rows, first workgroup, stochastic flag
+ * per member), launches k_act_session once and waits for one event.  Each member's actions are bit for bit those of
+ * sac_policy_act_device on the observations cast to float32 with the same eps; every refusal returns <0, sets
+ * sac_last_error and changes nothing.  Several sessions over the same trainers coexist (they share the weights only).
+ * ------------------------------------------------------------------------------------------ */
+typedef struct sac_actor sac_actor_t;
+/* 1..SAC_GROUP_MAX trainers of one device with the fused kernels' shapes (SAC and TD3, dims mixed); max_rows[i] in
+ * 1..1024.  Refused: null or duplicate trainers, more than SAC_GROUP_MAX, trainers on different devices, general-step
+ * trainers, max_rows outside 1..1024. */
+int sac_actor_create(sac_actor_t **out, sac_trainer_t *const *trainers, int n_trainers, const int32_t *max_rows);
+int sac_actor_destroy(sac_actor_t *a);          /* members are left as they are; they must outlive the session */
+/* member i's arrays inside the session's mapped pinned slab, fixed for the session's life and 256-byte aligned:
+ * obs (max_rows, O) FLOAT64 row-major (rounded to fp32 by the kernel as numpy's astype(float32) does),
+ * eps (max_rows, A) float32, act (max_rows, A) float32.  Any of the three out pointers may be NULL. */
+int sac_actor_arrays(sac_actor_t *a, int member, double **obs, float **eps, float **act);
+/* act on rows [0, n_rows[i]) of every member's obs (and eps, for a stochastic SAC member); 0 = sits out (its arrays are
+ * not touched); rows of act at and beyond n_rows[i] are not written.  The members with rows are drained first as by
+ * sac_sync, so the actions come from the weights as of the last completed step of any step path.  Refused: n_rows[i]
+ * outside 0..max_rows[i], all n_rows zero, a member confined by sac_trainer_set_xcd[_mask]. */
+int sac_actor_act(sac_actor_t *a, const int32_t *n_rows, const int32_t *deterministic);
+
 #ifdef __cplusplus
 }
 #endif

@@ -11,8 +11,8 @@ from .replay_buffer import DeviceBatch, EnvReplayBuffer  # noqa: F401
 from .sac import SACTrainer  # noqa: F401
 from .td3 import TD3Trainer  # noqa: F401
 from .group import (ArchSACTrainerGroup, ArchTD3TrainerGroup, MixedSACTrainerGroup, MixedTD3TrainerGroup,  # noqa: F401
-                    MlpSACTrainerGroup, MlpTD3TrainerGroup, SACTrainerGroup, TD3TrainerGroup)
+                    MlpSACTrainerGroup, MlpTD3TrainerGroup, SACTrainerGroup, TD3TrainerGroup, GroupActor)
 
 __all__ = ["EnvReplayBuffer", "DeviceBatch", "FlattenMlp", "TanhGaussianPolicy", "MakeDeterministic", "SACTrainer",
            "SACTrainerGroup", "MixedSACTrainerGroup", "MlpSACTrainerGroup", "MlpTD3TrainerGroup", "ArchSACTrainerGroup", "ArchTD3TrainerGroup", "TD3Trainer", "MixedTD3TrainerGroup", "TD3TrainerGroup", "TanhMlpPolicy", "GaussianStrategy",
-           "PolicyWrappedWithExplorationStrategy"]
+           "PolicyWrappedWithExplorationStrategy", "GroupActor"]

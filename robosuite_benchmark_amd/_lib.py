@@ -124,6 +124,10 @@ SYMBOLS = {
     "sac_group_stage_count": (C.c_int, [_P]),
     "sac_group_destroy": (C.c_int, [_P]),
     "sac_group_train_loop": (C.c_int, [_P, _P, C.c_int64, _P, _P]),
+    "sac_actor_create": (C.c_int, [C.POINTER(_P), _P, C.c_int, _P]),
+    "sac_actor_destroy": (C.c_int, [_P]),
+    "sac_actor_arrays": (C.c_int, [_P, C.c_int, C.POINTER(_P), C.POINTER(_P), C.POINTER(_P)]),
+    "sac_actor_act": (C.c_int, [_P, _P, _P]),
 }
 
 _lib = None

@@ -2245,6 +2245,7 @@ int stage_batches(sac_trainer *t, sac_buffer *b, int64_t n_steps) {
 }  // namespace
 
 #include "sac_act.h"
+#include "sac_actor.h"
 
 extern "C" {
 

@@ -22,7 +22,7 @@ from .group_checkpoint import checkpoint_exists as _checkpoint_exists
 from .networks import (FlattenMlp, GaussianStrategy, MakeDeterministic, PolicyWrappedWithExplorationStrategy,
                        TanhGaussianPolicy, TanhMlpPolicy, check_acting)
 from .replay_buffer import EnvReplayBuffer
-from .group import (ArchSACTrainerGroup, ArchTD3TrainerGroup, MixedSACTrainerGroup, MixedTD3TrainerGroup,
+from .group import (ArchSACTrainerGroup, ArchTD3TrainerGroup, GroupActor, MixedSACTrainerGroup, MixedTD3TrainerGroup,
                     MlpSACTrainerGroup, MlpTD3TrainerGroup, SACTrainerGroup, TD3TrainerGroup, act_many,
                     runs_general_step)
 from .sac import SACTrainer
@@ -110,6 +110,21 @@ def _acting_parts(policy):
     return policy, False, None
 
 
+def _numpy_action(h, obs, eps):
+    """One action row of a holder without a trainer handle, from its own NumPy forward (eps: its (1, A) draw or None)."""
+    obs = np.asarray(obs, np.float32)[None]
+    if isinstance(h, TanhGaussianPolicy):
+        mean, log_std = h._trunk(obs)
+        return (np.tanh(mean) if eps is None else np.tanh(mean + np.exp(log_std) * eps))[0, :]
+    return h.get_actions(obs)[0, :]
+
+
+def _bound(h):
+    """Does holder h act through its trainer's handle (the device, or the trainer's own policy_act)?"""
+    tr = h._trainer
+    return tr is not None and getattr(tr, "_h", None) is not None and tr.policy is h
+
+
 def holder_actions(holders, obs_list, deterministic_list, act_many=act_many):
     """One action row per holder: what holders[i].get_action(obs_list[i]) (MakeDeterministic: deterministic_list[i])
     returns, for all of them at once.  Every stochastic TanhGaussianPolicy draws its (1, A) exploration noise on the host
@@ -120,8 +135,7 @@ def holder_actions(holders, obs_list, deterministic_list, act_many=act_many):
     for h, det in zip(holders, deterministic_list):
         stochastic = isinstance(h, TanhGaussianPolicy) and not det
         eps.append(h._noise.standard_normal((1, h.action_dim)).astype(np.float32) if stochastic else None)
-        tr = h._trainer
-        bound.append(tr is not None and getattr(tr, "_h", None) is not None and tr.policy is h)
+        bound.append(_bound(h))
     acts = [None] * len(holders)
     ids = [i for i, b in enumerate(bound) if b]
     if ids:
@@ -130,14 +144,8 @@ def holder_actions(holders, obs_list, deterministic_list, act_many=act_many):
         for i, a in zip(ids, got):
             acts[i] = a[0, :]
     for i, h in enumerate(holders):
-        if bound[i]:
-            continue
-        obs = np.asarray(obs_list[i], np.float32)[None]
-        if isinstance(h, TanhGaussianPolicy):
-            mean, log_std = h._trunk(obs)
-            acts[i] = (np.tanh(mean) if eps[i] is None else np.tanh(mean + np.exp(log_std) * eps[i]))[0, :]
-        else:
-            acts[i] = h.get_actions(obs)[0, :]
+        if not bound[i]:
+            acts[i] = _numpy_action(h, obs_list[i], eps[i])
     return acts
 
 
@@ -149,10 +157,55 @@ class GroupPathCollector:
     own collect_new_paths would: per member the same rollouts -- env.reset / policy.reset at the start of a path, the
     last path clipped to the remaining step budget and dropped under discard_incomplete_paths -- the same paths, and the
     same num_steps_total / num_paths_total.  Members finish at different ticks.  Each member's envs, noise streams and
-    weights are its own, so a member's paths do not depend on who else is collected with it."""
+    weights are its own, so a member's paths do not depend on who else is collected with it.
 
-    def __init__(self, collectors, act_many=act_many):
+    sessions=True: the members whose holder is bound to a trainer handle act through a GroupActor (group.py: acting
+    sessions, persistent staging) that is built at the first collect_new_paths and kept: per tick each live member's
+    observation goes into the session's obs row, each stochastic TanhGaussianPolicy's draw -- the same draw from the same
+    stream in the same order as holder_actions' -- into its eps row, one act() call follows and the action rows are
+    copied out.  Paths, counters and generator states are those of the default.  `actor` is the GroupActor factory
+    (trainers, max_rows=1), injectable as act_many is; close() destroys the sessions."""
+
+    def __init__(self, collectors, act_many=act_many, sessions=False, actor=GroupActor):
         self.collectors, self._act_many = list(collectors), act_many
+        self._sessions, self._actor_factory, self._actor, self._actor_key = bool(sessions), actor, None, None
+
+    def close(self):
+        actor, self._actor, self._actor_key = self._actor, None, None
+        if actor is not None:
+            actor.close()
+
+    def _session_tick(self, parts):
+        """The sessions' stand-in for holder_actions: tick(ids, observations) -> one action row per live member."""
+        holders = [p[0] for p in parts]
+        slot = {i: k for k, i in enumerate(i for i, h in enumerate(holders) if _bound(h))}
+        key = tuple(id(holders[i]._trainer) for i in slot)
+        if self._actor is None or key != self._actor_key:
+            self.close()
+            if slot:
+                self._actor = self._actor_factory([holders[i]._trainer for i in slot], max_rows=1)
+            self._actor_key = key
+        actor = self._actor
+        det = [bool(parts[i][1]) for i in slot]
+        stochastic = [isinstance(h, TanhGaussianPolicy) and not p[1] for h, p in zip(holders, parts)]
+
+        def tick(ids, obs_list):
+            n_rows, eps = [0] * len(slot), {}
+            for i, o in zip(ids, obs_list):
+                if stochastic[i]:
+                    eps[i] = holders[i]._noise.standard_normal((1, holders[i].action_dim))
+                if i in slot:
+                    k = slot[i]
+                    actor.obs[k][0] = o
+                    if stochastic[i]:
+                        actor.eps[k][0] = eps[i][0]
+                    n_rows[k] = 1
+            if any(n_rows):
+                actor.act(n_rows, det)
+            return [actor.act[slot[i]][0].copy() if i in slot else
+                    _numpy_action(holders[i], o, eps[i].astype(np.float32) if i in eps else None)
+                    for i, o in zip(ids, obs_list)]
+        return tick
 
     def collect_new_paths(self, plans):
         """plans[i] = (max_path_length, num_steps, discard_incomplete_paths) of member i.  Returns [paths of member i]."""
@@ -186,12 +239,16 @@ class GroupPathCollector:
 
         for m in S:
             begin(m)
+        tick = self._session_tick(parts) if self._sessions else None
         while True:
             ids = [i for i, m in enumerate(S) if m["live"]]
             if not ids:
                 break
-            acts = holder_actions([parts[i][0] for i in ids], [S[i]["o"] for i in ids], [parts[i][1] for i in ids],
-                                  self._act_many)
+            if tick is not None:
+                acts = tick(ids, [S[i]["o"] for i in ids])
+            else:
+                acts = holder_actions([parts[i][0] for i in ids], [S[i]["o"] for i in ids], [parts[i][1] for i in ids],
+                                      self._act_many)
             for i, a in zip(ids, acts):
                 m, wrapper = S[i], parts[i][2]
                 if wrapper is not None:                       # PolicyWrappedWithExplorationStrategy.get_action
@@ -438,16 +495,18 @@ def _group_save(ck, runs, epoch):
     ck.save([r["trainer"] for r in runs], [r["buf"] for r in runs], [r["identity"] for r in runs], extras)
 
 
-def _group_epochs(runs, train_block, n_epochs, n_train, log_dir, quiet, what, ck=None, first_epoch=0, acting="host"):
+def _group_epochs(runs, train_block, n_epochs, n_train, log_dir, quiet, what, ck=None, first_epoch=0, acting="host",
+                  sessions=True):
     """The epoch loop of a grouped experiment: each run collects its paths, then train_block() trains every run at once,
     then every run ends its epoch, the group is saved (with a GroupCheckpoint `ck`), and each run writes its row (to
     <log_dir>/<run["sub"]>/progress.csv with log_dir; appended to after a resume).
     acting="device": the runs collect in lockstep (GroupPathCollector) -- the evaluation phase of all runs, then the
-    exploration phase of all runs, every tick's actions from one act_many call; each run's time/*sampling (s) columns
+    exploration phase of all runs, every tick's actions from one act_many call (sessions=True: from one acting-session
+    call, GroupActor, one session for each phase's collectors; the rows are the same); each run's time/*sampling (s) columns
     then hold the shared phase time."""
     t_start = time.time()
-    lock_eval = GroupPathCollector([r["evalc"] for r in runs]) if acting == "device" else None
-    lock_expl = GroupPathCollector([r["expl"] for r in runs]) if acting == "device" else None
+    lock_eval = GroupPathCollector([r["evalc"] for r in runs], sessions=sessions) if acting == "device" else None
+    lock_expl = GroupPathCollector([r["expl"] for r in runs], sessions=sessions) if acting == "device" else None
     try:
         for epoch in range(first_epoch, n_epochs):
             times = []                                        # per run: (start, evaluation s, exploration s, storing s)
@@ -513,13 +572,16 @@ def _group_epochs(runs, train_block, n_epochs, n_train, log_dir, quiet, what, ck
                 print(f"epoch {epoch}: {len(runs)} {what}, training {t4 - t3:.3f}s "
                       f"({len(runs) * n_train / max(t4 - t3, 1e-9):.0f} steps/s together)", flush=True)
     finally:
+        for lock in (lock_eval, lock_expl):
+            if lock is not None:
+                lock.close()
         for r in runs:
             if r["fh"]:
                 r["fh"].close()
 
 
 def experiment_group(variant, seeds, log_dir=None, num_epochs=None, obs_dim=None, action_dim=None, device=0,
-                     quiet=False, checkpoint_dir=None, resume=False, chunk_rows=DEFAULT_CHUNK_ROWS, acting="host"):
+                     quiet=False, checkpoint_dir=None, resume=False, chunk_rows=DEFAULT_CHUNK_ROWS, acting="host", sessions=True):
     """One configuration, several seeds, one process: each seed is the run ``experiment(variant, seed=s)`` would make --
     its own synthetic environments, collectors, weights and replay buffer -- and every epoch's training block is ONE
     SACTrainerGroup.train_loop (TD3 variants: TD3TrainerGroup; hidden sizes other than two layers of at most 256 units:
@@ -534,8 +596,10 @@ def experiment_group(variant, seeds, log_dir=None, num_epochs=None, obs_dim=None
     seed's progress.csv; the seeds must be the saved ones in the saved order.  Without a checkpoint there it starts
     afresh.
     acting: "host" (the default: every run collects its own paths, one sac_policy_act call per step) or "device": the
-    runs collect in lockstep (GroupPathCollector), every tick's actions of all runs from ONE sac_policy_act_many launch
-    on the live weights; each run's rows are those of experiment(variant, seed=s, acting="device")."""
+    runs collect in lockstep (GroupPathCollector), every tick's actions of all runs from ONE launch on the live weights
+    (sessions=True, the default: one acting-session call, group.GroupActor; False: one sac_policy_act_many call, the
+    slower path kept for measuring against -- same rows); each run's rows are those of
+    experiment(variant, seed=s, acting="device")."""
     check_acting(acting)
     if resume and not checkpoint_dir:
         raise RuntimeError("experiment_group(resume=True) needs the checkpoint_dir to resume from")
@@ -562,7 +626,7 @@ def experiment_group(variant, seeds, log_dir=None, num_epochs=None, obs_dim=None
         train_block = lambda: group.train_loop([r["buf"] for r in runs], n_train, batch_size=ak["batch_size"])  # noqa: E731
     _group_epochs(runs, train_block,
                   num_epochs if num_epochs is not None else ak["num_epochs"], n_train, log_dir, quiet, "seeds", ck,
-                  first_epoch, acting)
+                  first_epoch, acting, sessions)
     return {r["seed"]: r["rows"] for r in runs}
 
 
@@ -588,7 +652,7 @@ def sweep_label(variant, seed, hidden_sweep=False):
 
 
 def experiment_sweep(runs, log_dir=None, num_epochs=None, device=0, quiet=False, checkpoint_dir=None, resume=False,
-                     chunk_rows=DEFAULT_CHUNK_ROWS, hidden_sweep=False, acting="host"):
+                     chunk_rows=DEFAULT_CHUNK_ROWS, hidden_sweep=False, acting="host", sessions=True):
     """Several tasks x seeds, one process, one device: every entry of ``runs`` -- (variant, seed), or (variant, seed,
     obs_dim, action_dim) for a task without pinned dims -- is the run ``experiment(variant, seed=seed)`` would make, and
     every epoch's training block is ONE MixedSACTrainerGroup.train_loop (TD3 variants: MixedTD3TrainerGroup; hidden sizes
@@ -654,5 +718,5 @@ def experiment_sweep(runs, log_dir=None, num_epochs=None, device=0, quiet=False,
     batches = [r["ak"]["batch_size"] for r in group_runs]
     _group_epochs(group_runs, lambda: group.train_loop([r["buf"] for r in group_runs], n_train, batch_sizes=batches),
                   num_epochs if num_epochs is not None else ak0["num_epochs"], n_train, log_dir, quiet, "runs", ck,
-                  first_epoch, acting)
+                  first_epoch, acting, sessions)
     return [r["rows"] for r in group_runs]

@@ -74,6 +74,153 @@ def act_many(trainers, obs_list, deterministic_list, eps_list):
     return out
 
 
+class _ActorSession:
+    """One sac_actor session (at most 16 device members): its handle, the members' handles it was opened on, and the
+    per-call argument arrays, made once."""
+
+    def __init__(self, lib, ids, trainers, max_rows):
+        n = len(ids)
+        self.lib, self.ids, self.a = lib, ids, C.c_void_p()
+        self.handles = [trainers[i]._h.value for i in ids]
+        self.gens = [trainers[i]._handle_gen for i in ids]      # (an address can come back; the count cannot)
+        self.n_rows, self.det = (C.c_int32 * n)(), (C.c_int32 * n)()
+        _lib.check(lib.sac_actor_create(C.byref(self.a), (C.c_void_p * n)(*self.handles), n,
+                                        (C.c_int32 * n)(*[max_rows[i] for i in ids])), "sac_actor_create")
+
+    def arrays(self, k, rows, O, A):
+        o, e, a = C.c_void_p(), C.c_void_p(), C.c_void_p()
+        _lib.check(self.lib.sac_actor_arrays(self.a, k, C.byref(o), C.byref(e), C.byref(a)), "sac_actor_arrays")
+        view = lambda p, ct, cols: np.ctypeslib.as_array((ct * (rows * cols)).from_address(p.value)).reshape(rows, cols)  # noqa: E731
+        return view(o, C.c_double, O), view(e, C.c_float, A), view(a, C.c_float, A)
+
+    def destroy(self):
+        a, self.a = self.a, None
+        if a:
+            self.lib.sac_actor_destroy(a)
+
+
+class _ActRows(list):
+    """GroupActor.act: the members' action views, act[i] -- and the tick itself, act(n_rows, deterministic)."""
+
+    def __init__(self, tick, rows):
+        super().__init__(rows)
+        self._tick = tick
+
+    def __call__(self, n_rows, deterministic):
+        return self._tick(n_rows, deterministic)
+
+    def __reduce__(self):
+        raise TypeError("the action views of a GroupActor are never pickled")
+
+
+class GroupActor:
+    """policy.get_actions for a FIXED list of runs, tick after tick, without marshalling: act_many as a session.
+
+    obs[i] (max_rows_i, O_i) float64, eps[i] (max_rows_i, A_i) float32 and act[i] (max_rows_i, A_i) float32 are NumPy
+    views of the staging the kernel reads and writes (sac_actor_arrays: a mapped pinned slab; nothing is copied).  A tick
+    is: write rows [0, n_i) of obs[i] (and of eps[i], for a stochastic SAC member), call act(n_rows, deterministic), read
+    rows [0, n_i) of act[i] -- and copy them before the next tick overwrites them.  n_i == 0: member i sits out and its
+    arrays are left alone.  Observations are rounded to float32 as astype(np.float32) rounds them; each member's actions
+    are bit for bit those of its own policy_act_device on obs.astype(np.float32) with the same eps.
+
+    Like act_many it opens one session per 16 members with the fused kernels' shapes; members of the general step act on
+    the host through their own policy_act inside the same act() call, with ordinary arrays behind the same attributes.
+    A session is bound to its members' handles: when a trainer has replaced its handle (a first step at another batch
+    size; seen by the trainer's count of handles made, since an address can come back), act() reopens the sessions,
+    carries the staged rows over and REPLACES the views, so read obs[i] / eps[i] / act[i] from the attributes on each
+    tick.  close() (and the finaliser) destroys the sessions.  The object holds device state only and is never pickled."""
+
+    def __init__(self, trainers, max_rows=1):
+        self.trainers = list(trainers)
+        R = len(self.trainers)
+        if R == 0 or len({id(t) for t in self.trainers}) != R:
+            raise RuntimeError("GroupActor takes one or more trainers, each once")
+        self.max_rows = [int(max_rows)] * R if np.isscalar(max_rows) else [int(m) for m in max_rows]
+        if len(self.max_rows) != R or not all(1 <= m <= _lib.ACT_MAX_ROWS for m in self.max_rows):
+            raise RuntimeError(f"GroupActor: max_rows is 1..{_lib.ACT_MAX_ROWS}, one value or one per trainer")
+        for i, t in enumerate(self.trainers):
+            if getattr(t, "_h", None) is None:
+                raise RuntimeError(f"GroupActor member {i} has no device handle yet (create it with batch_size=, or train once)")
+        self._lib = _lib.load()
+        self._td3 = [isinstance(t, TD3Trainer) for t in self.trainers]
+        self._host = [i for i, t in enumerate(self.trainers) if runs_general_step(t)]
+        self._dev = [i for i in range(R) if i not in set(self._host)]
+        self.obs, self.eps, self.act = [None] * R, [None] * R, _ActRows(self._act, [None] * R)
+        for i in self._host:
+            t, m = self.trainers[i], self.max_rows[i]
+            self.obs[i], self.eps[i] = np.zeros((m, t.obs_dim), np.float64), np.zeros((m, t.act_dim), np.float32)
+            self.act[i] = np.zeros((m, t.act_dim), np.float32)
+        self._sessions, self._closed = [], False
+        self._open()
+
+    def _open(self):
+        for c in range(0, len(self._dev), MAX_MEMBERS):
+            s = _ActorSession(self._lib, self._dev[c:c + MAX_MEMBERS], self.trainers, self.max_rows)
+            self._sessions.append(s)
+            for k, i in enumerate(s.ids):
+                t = self.trainers[i]
+                self.obs[i], self.eps[i], self.act[i] = s.arrays(k, self.max_rows[i], t.obs_dim, t.act_dim)
+
+    def _reopen(self):
+        """A member's handle was replaced: new sessions on the handles of now, the staged rows carried over."""
+        for i in self._dev:
+            if self.trainers[i]._h is None:
+                raise RuntimeError(f"GroupActor member {i} has lost its device handle")
+        kept = {i: (self.obs[i].copy(), self.eps[i].copy(), self.act[i].copy()) for i in self._dev}
+        self._destroy()
+        self._open()
+        for i, (o, e, a) in kept.items():
+            self.obs[i][...], self.eps[i][...], self.act[i][...] = o, e, a
+
+    def _act(self, n_rows, deterministic):
+        """act(n_rows, deterministic), one tick: actions of rows [0, n_rows[i]) of every member into act[i].
+        deterministic: one flag or one per member (MakeDeterministic; TD3 members are deterministic whatever it says)."""
+        if self._closed:
+            raise RuntimeError("this GroupActor is closed")
+        R = len(self.trainers)
+        det = [bool(deterministic)] * R if np.isscalar(deterministic) else [bool(d) for d in deterministic]
+        n_rows = [int(n) for n in n_rows]
+        if len(n_rows) != R or len(det) != R:
+            raise RuntimeError("GroupActor.act takes one row count (and one deterministic flag, or one for all) per trainer")
+        for i, n in enumerate(n_rows):                        # every refusal first: nothing has acted when one raises
+            if not 0 <= n <= self.max_rows[i]:
+                raise RuntimeError(f"GroupActor member {i}: {n} rows (0..{self.max_rows[i]} in this session, 0 = sits out)")
+        if not any(n_rows):
+            raise RuntimeError("no trainer has rows to act on")
+        if any(self.trainers[i]._h is None or self.trainers[i]._handle_gen != g
+               for s in self._sessions for i, g in zip(s.ids, s.gens)):
+            self._reopen()
+        for s in self._sessions:
+            rows = [n_rows[i] for i in s.ids]
+            if not any(rows):
+                continue
+            s.n_rows[:], s.det[:] = rows, [det[i] for i in s.ids]
+            _lib.check(self._lib.sac_actor_act(s.a, s.n_rows, s.det), "sac_actor_act")
+        for i in self._host:
+            n = n_rows[i]
+            if n:
+                stochastic = not det[i] and not self._td3[i]
+                self.act[i][:n] = self.trainers[i].policy_act(self.obs[i][:n], det[i], self.eps[i][:n] if stochastic else None)
+
+    def _destroy(self):
+        sessions, self._sessions = getattr(self, "_sessions", []), []
+        for s in sessions:
+            s.destroy()
+
+    def close(self):
+        """Destroy the sessions: the views must not be used afterwards, and act() raises."""
+        self._closed = True
+        self.obs, self.eps = [], []
+        del self.act[:]
+        self._destroy()
+
+    def __del__(self):
+        self._destroy()
+
+    def __reduce__(self):
+        raise TypeError("a GroupActor holds device staging and is never pickled: build a new one on the restored trainers")
+
+
 class _Members:
     """The member checks that hold for every kind of trainer group (host metadata: nothing is created for a group that
     cannot exist).  The algorithm comes from _SACMembers / _TD3Members."""

@@ -42,6 +42,7 @@ class SACTrainer:
         self._num_train_steps = 0
         self._lib = _lib.load()
         self._h, self._batch = None, None
+        self._handle_gen = 0                     # handles made so far (an acting session is bound to ONE of them)
         self._host_policy_stale = False
         self._saved_state = None
         for name in self.NETS:                   # (a holder finds its trainer: acting path, pickling)
@@ -83,6 +84,7 @@ class SACTrainer:
         self._saved_state = None
         self._destroy()
         self._h, self._batch = h, batch
+        self._handle_gen = getattr(self, "_handle_gen", 0) + 1
         if state is None:
             for name in self.NETS:
                 self._set_params(name, getattr(self, name).flat())

@@ -4,10 +4,15 @@ One JSON line per measurement, appended to --out (default: stdout only).
 
     python scripts/bench_acting.py [--windows 3] [--window-s 1.0] [--seeds 16] [--rounds 2] [--out FILE]
     python scripts/bench_acting.py --profile-pass       # a short run of the device calls alone, for a kernel trace
+    python scripts/bench_acting.py --sessions [--out FILE]      # acting sessions (GroupActor) beside the calls above
+    python scripts/bench_acting.py --profile-pass-sessions      # k_act and k_act_session side by side, for a kernel trace
 
 Every timed call returns with its actions on the host (the calls end synchronised), so a host clock around a window of
 calls measures them; a window lasts at least --window-s seconds after a warm-up, and each figure is the median over
---windows windows with the smallest and the largest next to it.  (d) runs experiment_group with --seeds seeds of the
+--windows windows with the smallest and the largest next to it.  --sessions measures, in ONE process, (c) again, (c')
+the same tick through a GroupActor -- 16 observations and 16 eps rows written into the views, 16 action rows copied out
+-- (c'') the bare sac_actor_act call, (b) and (b') a one-member session at n = 1, 16, 256, 1000, and (d') the sampling
+phases of the group epoch with sessions=True and sessions=False alternating.  (d) runs experiment_group with --seeds seeds of the
 default Lift variant for one epoch at its default step counts, acting="host" and acting="device" alternating --rounds
 times, and reports each mode's evaluation + exploration seconds of that epoch."""
 from __future__ import annotations
@@ -105,6 +110,100 @@ def epoch_bench(args):
                                      / np.median([r["sampling_s"] for r in res["device"]]))), args.out)
 
 
+def session_benches(args):
+    from robosuite_benchmark_amd import GroupActor, _lib
+    rs = np.random.RandomState(0)
+    ts = [make_trainer(10 + i) for i in range(16)]
+    obs64 = [rs.normal(0, 0.5, O) for _ in ts]                        # what an env hands out: float64 rows
+    draws = [rs.normal(size=(1, A)) for _ in ts]
+    obs_l, eps_l = [o.astype(np.float32)[None] for o in obs64], [e.astype(np.float32) for e in draws]
+    det, ones = [False] * 16, [1] * 16
+    emit(dict(what="c: sac_policy_act_many, 16 Lift members x 1 row, per call (group.act_many)",
+              **windows(lambda: act_many(ts, obs_l, det, eps_l), args.windows, args.window_s)), args.out)
+    g = GroupActor(ts, max_rows=1)
+
+    def tick():
+        for k in range(16):
+            g.obs[k][0] = obs64[k]
+            g.eps[k][0] = draws[k][0]
+        g.act(ones, det)
+        return [g.act[k][0].copy() for k in range(16)]
+    emit(dict(what="c': GroupActor tick, 16 Lift members x 1 row: 16 obs + 16 eps rows in, act, 16 action rows out",
+              **windows(tick, args.windows, args.window_s)), args.out)
+    sess = g._sessions[0]
+    sess.n_rows[:], sess.det[:] = ones, [0] * 16
+    lib = _lib.load()
+    emit(dict(what="c'': sac_actor_act alone, 16 Lift members x 1 row",
+              **windows(lambda: lib.sac_actor_act(sess.a, sess.n_rows, sess.det), args.windows, args.window_s)), args.out)
+    g.close()
+    t = ts[0]
+    g1 = GroupActor([t], max_rows=1000)
+    for n in (1, 16, 256, 1000):
+        o64, e = rs.normal(0, 0.5, (n, O)), rs.normal(size=(n, A)).astype(np.float32)
+        o32 = o64.astype(np.float32)
+        emit(dict(what="b: sac_policy_act_device, per call", n=n,
+                  **windows(lambda: t.policy_act_device(o32, False, e), args.windows, args.window_s)), args.out)
+
+        def tick1():
+            g1.obs[0][:n] = o64
+            g1.eps[0][:n] = e
+            g1.act([n], False)
+            return g1.act[0][:n].copy()
+        emit(dict(what="b': one-member GroupActor tick (rows in, act, rows out)", n=n,
+                  **windows(tick1, args.windows, args.window_s)), args.out)
+    g1.close()
+
+
+def session_epoch_bench(args):
+    import robosuite_benchmark_amd.driver as drv
+    from robosuite_benchmark_amd.variant import default_variant
+    v = default_variant(env="Lift", seed=1, batch_size=256)
+    v["replay_buffer_size"] = 100000
+    seeds = list(range(1, args.seeds + 1))
+    res = {True: [], False: []}
+    for rnd in range(args.rounds):
+        for flag in (True, False):
+            rows = drv.experiment_group(copy.deepcopy(v), seeds, num_epochs=1, quiet=True, acting="device", sessions=flag)
+            r0 = rows[seeds[0]][0]
+            res[flag].append(dict(sampling_s=r0["time/evaluation sampling (s)"] + r0["time/exploration sampling (s)"],
+                                  training_s=r0["time/training (s)"]))
+    ak = v["algorithm_kwargs"]
+    on, off = [r["sampling_s"] for r in res[True]], [r["sampling_s"] for r in res[False]]
+    emit(dict(what="d': evaluation + exploration seconds of one experiment_group epoch, acting=device, sessions on / off",
+              seeds=args.seeds, eval_steps=ak["num_eval_steps_per_epoch"], expl_steps=ak["num_expl_steps_per_train_loop"],
+              rounds=args.rounds, sessions_sampling_s=on, act_many_sampling_s=off,
+              sessions_training_s=[r["training_s"] for r in res[True]], act_many_training_s=[r["training_s"] for r in res[False]],
+              act_many_over_sessions=float(np.median(off) / np.median(on))), args.out)
+
+
+def profile_pass_sessions():
+    """k_act and k_act_session on the same inputs, 200 launches each: 16 members x 1 row, and one member x 1000 rows."""
+    from robosuite_benchmark_amd import GroupActor
+    rs = np.random.RandomState(0)
+    ts = [make_trainer(10 + i) for i in range(16)]
+    obs_l = [rs.normal(0, 0.5, (1, O)).astype(np.float32) for _ in ts]
+    eps_l = [rs.normal(size=(1, A)).astype(np.float32) for _ in ts]
+    g = GroupActor(ts, max_rows=1)
+    for k in range(16):
+        g.obs[k][...], g.eps[k][...] = obs_l[k], eps_l[k]
+    obs, eps = rs.normal(0, 0.5, (1000, O)).astype(np.float32), rs.normal(size=(1000, A)).astype(np.float32)
+    g1 = GroupActor([ts[0]], max_rows=1000)
+    g1.obs[0][...], g1.eps[0][...] = obs, eps
+    for _ in range(4):                                                # interleaved blocks of 50: neither kernel runs "later"
+        for _ in range(50):
+            act_many(ts, obs_l, [False] * 16, eps_l)
+        for _ in range(50):
+            g.act([1] * 16, False)
+        for _ in range(50):
+            ts[0].policy_act_device(obs, False, eps)
+        for _ in range(50):
+            g1.act([1000], False)
+    g.close()
+    g1.close()
+    print("profile pass: 200 launches each of k_act and k_act_session at 16 x 1 row (16 workgroups) and 1 x 1000 rows (63)",
+          flush=True)
+
+
 def profile_pass():
     rs = np.random.RandomState(0)
     ts = [make_trainer(10 + i) for i in range(16)]
@@ -128,7 +227,17 @@ if __name__ == "__main__":
     ap.add_argument("--out", type=str, default=None)
     ap.add_argument("--skip-epoch", action="store_true", help="only the per-call measurements (a) to (c)")
     ap.add_argument("--profile-pass", action="store_true")
+    ap.add_argument("--sessions", action="store_true", help="the acting-session rows (c), (c'), (c''), (b), (b') and (d')")
+    ap.add_argument("--profile-pass-sessions", action="store_true")
     args = ap.parse_args()
+    if args.profile_pass_sessions:
+        profile_pass_sessions()
+        sys.exit(0)
+    if args.sessions:
+        session_benches(args)
+        if not args.skip_epoch:
+            session_epoch_bench(args)
+        sys.exit(0)
     if args.profile_pass:
         profile_pass()
         sys.exit(0)

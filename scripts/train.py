@@ -54,7 +54,7 @@ if __name__ == "__main__":
     ap.add_argument("--acting", type=str, default="host", choices=["host", "device"],
                     help="where the collectors' policies act: host (sac_policy_act, one observation per call) or device "
                          "(the policy forward as a HIP kernel on the live weights; with --seeds / --variants the runs "
-                         "collect in lockstep, all their actions of a tick from one launch)")
+                         "collect in lockstep, all their actions of a tick from one launch of an acting session)")
     args = ap.parse_args()
     if (args.hidden_sweep or args.hidden_sizes) and not args.variants:
         raise SystemExit("--hidden_sweep / --hidden_sizes need --variants")
