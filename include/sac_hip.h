@@ -344,6 +344,21 @@ int sac_policy_act_device(sac_trainer_t *t, int64_t n, const float *obs /* (n,O)
 int sac_policy_act_many(sac_trainer_t *const *trainers, int n_trainers, const int32_t *n_rows,
                         const float *const *obs, const int32_t *deterministic, const float *const *eps,
                         float *const *act);
+/* The same two entries for GENERAL-STEP trainers (sac_trainer_create_mlp / td3_trainer_create_mlp with hidden sizes
+ * beyond two layers of at most 256 units: depth 1..7, widths 1..4096): k_act_layer (csrc/sac_act_general.h), one launch
+ * per layer depth on the live weights of the general step -- no mirror, no repacking, no second copy of the weights --
+ * and one wait at the end.  The contract is that of sac_policy_act_device / sac_policy_act_many: 1..16 trainers of one
+ * device, SAC and TD3 mixed, 0..1024 rows each (0 = sits out, at least one with rows), eps only for stochastic SAC,
+ * every member with rows drained as by sac_sync first, each member's actions bit for bit its own
+ * sac_policy_act_general's and row r of any call bit for bit the one-row call.  The host mirror of sac_policy_act is
+ * left alone; the kernel writes the trainers' own activation scratch and `act`, nothing the step reads.  Refused (<0,
+ * sac_last_error, nothing changed): what sac_policy_act_many refuses, and trainers with the fused kernels' shapes
+ * (sac_policy_act_device is their entry).  The three entries above keep refusing general-step trainers. */
+int sac_policy_act_general(sac_trainer_t *t, int64_t n, const float *obs /* (n,O) host */, int deterministic,
+                           const float *eps /* (n,A) host; NULL when deterministic or TD3 */, float *act /* (n,A) host */);
+int sac_policy_act_general_many(sac_trainer_t *const *trainers, int n_trainers, const int32_t *n_rows,
+                                const float *const *obs, const int32_t *deterministic, const float *const *eps,
+                                float *const *act);
 
 /* ------------------------------------------------------------------------------------------
  * Trainer groups: several runs of one configuration (the reference's seed sweeps, /root/reference/launch_jobs.sh)

@@ -22,8 +22,9 @@
 // and the member table live in ONE mapped pinned staging buffer (allocated on first use, grown as needed) which the
 // kernel reads and writes over the link: a call is one launch and one wait, without a copy call of its own.
 //
-// General-step trainers (hidden sizes beyond the fused kernels') are out of scope here: they act on the host
-// (sac_policy_act).
+// General-step trainers (hidden sizes beyond the fused kernels') are out of scope here: these entries refuse them, and
+// they act on the host (sac_policy_act) or through the entries of their own, sac_policy_act_general[_many]
+// (k_act_layer, sac_act_general.h).
 #pragma once
 
 namespace sac {

@@ -1879,6 +1879,8 @@ struct sac_trainer {
     // device acting (sac_act.h): observations, eps, actions and the member table of a call, in mapped pinned host memory
     struct ActStage { char *h = nullptr, *d = nullptr; size_t bytes = 0; } act_stage;
     bool act_lds_raised = false;                      // k_act may use more than 48 KB of LDS (wide observations)
+    // general-step device acting (sac_act_general.h): the activations between two layer launches ping-pong between these
+    float *act_gen[2] = {nullptr, nullptr}; size_t act_gen_floats = 0;
     size_t lds_bw = 0;
     // fused step (k_abc, sac_fused.h): launches A + B + C as one launch with in-launch hand-offs
     bool fused = false;
@@ -2245,6 +2247,7 @@ int stage_batches(sac_trainer *t, sac_buffer *b, int64_t n_steps) {
 }  // namespace
 
 #include "sac_act.h"
+#include "sac_act_general.h"
 #include "sac_actor.h"
 
 extern "C" {
@@ -2712,6 +2715,7 @@ int sac_trainer_destroy(sac_trainer_t *t) {
     if (t->h_stage) (void)hipHostFree(t->h_stage);
     if (t->h_diag) (void)hipHostFree(t->h_diag);
     if (t->act_stage.h) (void)hipHostFree(t->act_stage.h);
+    for (float *p : t->act_gen) if (p) (void)hipFree(p);
     for (auto &e : t->ev) if (e) (void)hipEventDestroy(e);
     for (auto &e : t->ev_tm) if (e) (void)hipEventDestroy(e);
     for (auto &e : t->ev_ready) if (e) (void)hipEventDestroy(e);

@@ -125,12 +125,13 @@ def _bound(h):
     return tr is not None and getattr(tr, "_h", None) is not None and tr.policy is h
 
 
-def holder_actions(holders, obs_list, deterministic_list, act_many=act_many):
+def holder_actions(holders, obs_list, deterministic_list, act_many=act_many, general="host"):
     """One action row per holder: what holders[i].get_action(obs_list[i]) (MakeDeterministic: deterministic_list[i])
     returns, for all of them at once.  Every stochastic TanhGaussianPolicy draws its (1, A) exploration noise on the host
     from its own _noise stream, exactly as get_action does; the holders whose trainer has a handle then act through ONE
     act_many call (group.act_many: the fused kernels' shapes in one launch, the general step on the host), holders
-    without one through their own NumPy forward."""
+    without one through their own NumPy forward.  general="device": act_many(..., general="device"), the holders of
+    the general step on the device as well."""
     eps, bound = [], []
     for h, det in zip(holders, deterministic_list):
         stochastic = isinstance(h, TanhGaussianPolicy) and not det
@@ -140,7 +141,8 @@ def holder_actions(holders, obs_list, deterministic_list, act_many=act_many):
     ids = [i for i, b in enumerate(bound) if b]
     if ids:
         got = act_many([holders[i]._trainer for i in ids], [np.asarray(obs_list[i])[None] for i in ids],
-                       [deterministic_list[i] for i in ids], [eps[i] for i in ids])
+                       [deterministic_list[i] for i in ids], [eps[i] for i in ids],
+                       **({} if general == "host" else dict(general=general)))
         for i, a in zip(ids, got):
             acts[i] = a[0, :]
     for i, h in enumerate(holders):
@@ -164,10 +166,15 @@ class GroupPathCollector:
     observation goes into the session's obs row, each stochastic TanhGaussianPolicy's draw -- the same draw from the same
     stream in the same order as holder_actions' -- into its eps row, one act() call follows and the action rows are
     copied out.  Paths, counters and generator states are those of the default.  `actor` is the GroupActor factory
-    (trainers, max_rows=1), injectable as act_many is; close() destroys the sessions."""
+    (trainers, max_rows=1), injectable as act_many is; close() destroys the sessions.
 
-    def __init__(self, collectors, act_many=act_many, sessions=False, actor=GroupActor):
+    general="device" (acting="device_all" of the drivers): act_many and the GroupActor factory are called with
+    general="device", so that the members of the general step act on the device too; everything else, the draws from
+    the host generators included, is as under the default "host"."""
+
+    def __init__(self, collectors, act_many=act_many, sessions=False, actor=GroupActor, general="host"):
         self.collectors, self._act_many = list(collectors), act_many
+        self._general = dict(general=general) if general != "host" else {}
         self._sessions, self._actor_factory, self._actor, self._actor_key = bool(sessions), actor, None, None
 
     def close(self):
@@ -183,7 +190,7 @@ class GroupPathCollector:
         if self._actor is None or key != self._actor_key:
             self.close()
             if slot:
-                self._actor = self._actor_factory([holders[i]._trainer for i in slot], max_rows=1)
+                self._actor = self._actor_factory([holders[i]._trainer for i in slot], max_rows=1, **self._general)
             self._actor_key = key
         actor = self._actor
         det = [bool(parts[i][1]) for i in slot]
@@ -248,7 +255,7 @@ class GroupPathCollector:
                 acts = tick(ids, [S[i]["o"] for i in ids])
             else:
                 acts = holder_actions([parts[i][0] for i in ids], [S[i]["o"] for i in ids], [parts[i][1] for i in ids],
-                                      self._act_many)
+                                      self._act_many, **self._general)
             for i, a in zip(ids, acts):
                 m, wrapper = S[i], parts[i][2]
                 if wrapper is not None:                       # PolicyWrappedWithExplorationStrategy.get_action
@@ -319,7 +326,10 @@ def experiment(variant, log_dir=None, seed=1, obs_dim=None, action_dim=None, num
 
     acting: "host" (the default: sac_policy_act, one observation per call from the mirrored weights) or "device"
     (sac_policy_act_device: the collectors' get_action calls run k_act on the live weights).  A run of the general step
-    acts on the host either way (device acting serves the fused kernels' shapes)."""
+    acts on the host either way ("device" serves the fused kernels' shapes, and its results are pinned).
+    "device_all" is "device", and a run of the general step acts on the device too (sac_policy_act_general: one
+    k_act_layer launch per layer on the live weights).  The exploration noise comes from the same host stream, in the
+    same amounts, whichever value is given."""
     check_acting(acting)
     validate(variant)
     np.random.seed(seed)                                          # scripts/train.py:112 (args.seed, not variant seed)
@@ -346,8 +356,10 @@ def experiment(variant, log_dir=None, seed=1, obs_dim=None, action_dim=None, num
         eval_policy, expl_policy = MakeDeterministic(policy), policy
         trainer = SACTrainer(env=eval_env, policy=policy, qf1=qf1, qf2=qf2, target_qf1=tqf1, target_qf2=tqf2,
                              batch_size=ak["batch_size"], noise_seed=seed, device=device, **tk)
-    if acting == "device" and not runs_general_step(trainer):
+    if acting != "host" and not runs_general_step(trainer):
         policy.acting = "device"
+    elif acting == "device_all":
+        policy.acting = "device_all"
     buf = EnvReplayBuffer(variant["replay_buffer_size"], obs_dim=O, action_dim=A, device=device)
     expl, evalc = PathCollector(expl_env, expl_policy), PathCollector(eval_env, eval_policy)
     rows, t_start = [], time.time()
@@ -449,8 +461,10 @@ def _group_run(variant, seed, O, A, device, prefill=True, acting="host"):
         eval_policy, expl_policy = MakeDeterministic(policy), policy
         trainer = SACTrainer(env=eval_env, policy=policy, qf1=qf1, qf2=qf2, target_qf1=tqf1, target_qf2=tqf2,
                              batch_size=ak["batch_size"], noise_seed=seed, device=device, **tk)
-    if acting == "device" and not runs_general_step(trainer):
+    if acting != "host" and not runs_general_step(trainer):
         policy.acting = "device"
+    elif acting == "device_all":
+        policy.acting = "device_all"
     buf = EnvReplayBuffer(variant["replay_buffer_size"], obs_dim=O, action_dim=A, device=device)
     buf.seed_from_numpy(rs)                                   # (the stream np.random would continue with)
     expl, evalc = PathCollector(expl_env, expl_policy), PathCollector(eval_env, eval_policy)
@@ -503,14 +517,17 @@ def _group_epochs(runs, train_block, n_epochs, n_train, log_dir, quiet, what, ck
     acting="device": the runs collect in lockstep (GroupPathCollector) -- the evaluation phase of all runs, then the
     exploration phase of all runs, every tick's actions from one act_many call (sessions=True: from one acting-session
     call, GroupActor, one session for each phase's collectors; the rows are the same); each run's time/*sampling (s) columns
-    then hold the shared phase time."""
+    then hold the shared phase time.  acting="device_all": the same, and the lockstep collectors send the runs of the
+    general step to the device as well (general="device")."""
     t_start = time.time()
-    lock_eval = GroupPathCollector([r["evalc"] for r in runs], sessions=sessions) if acting == "device" else None
-    lock_expl = GroupPathCollector([r["expl"] for r in runs], sessions=sessions) if acting == "device" else None
+    lockstep = acting != "host"
+    lock_kw = dict(sessions=sessions, general="device" if acting == "device_all" else "host")
+    lock_eval = GroupPathCollector([r["evalc"] for r in runs], **lock_kw) if lockstep else None
+    lock_expl = GroupPathCollector([r["expl"] for r in runs], **lock_kw) if lockstep else None
     try:
         for epoch in range(first_epoch, n_epochs):
             times = []                                        # per run: (start, evaluation s, exploration s, storing s)
-            if acting == "device":
+            if lockstep:
                 t0 = time.time()
                 lock_eval.collect_new_paths([(r["ak"]["eval_max_path_length"], r["ak"]["num_eval_steps_per_epoch"], True)
                                              for r in runs])
@@ -522,7 +539,7 @@ def _group_epochs(runs, train_block, n_epochs, n_train, log_dir, quiet, what, ck
                     s0 = time.time()
                     r["buf"].add_paths(new_paths)
                     times.append((t0, t1 - t0, t2 - t1, time.time() - s0))
-            for r in runs if acting != "device" else ():
+            for r in runs if not lockstep else ():
                 ak = r["ak"]
                 t0 = time.time()
                 r["evalc"].collect_new_paths(ak["eval_max_path_length"], ak["num_eval_steps_per_epoch"], True)
@@ -599,7 +616,8 @@ def experiment_group(variant, seeds, log_dir=None, num_epochs=None, obs_dim=None
     runs collect in lockstep (GroupPathCollector), every tick's actions of all runs from ONE launch on the live weights
     (sessions=True, the default: one acting-session call, group.GroupActor; False: one sac_policy_act_many call, the
     slower path kept for measuring against -- same rows); each run's rows are those of
-    experiment(variant, seed=s, acting="device")."""
+    experiment(variant, seed=s, acting="device").  "device_all": the same, with the runs of the general step acting on the
+    device too (one sac_policy_act_general_many call per tick and 16 of them); rows as experiment(..., acting="device_all")."""
     check_acting(acting)
     if resume and not checkpoint_dir:
         raise RuntimeError("experiment_group(resume=True) needs the checkpoint_dir to resume from")
@@ -667,7 +685,9 @@ def experiment_sweep(runs, log_dir=None, num_epochs=None, device=0, quiet=False,
     block is ONE ArchSACTrainerGroup.train_loop (TD3: ArchTD3TrainerGroup), and each run's name carries its hidden
     sizes: <task>-h<sizes>-s<seed>, or <task>-p<policy sizes>-q<Q sizes>-s<seed> (sweep_label).
     acting as for experiment_group; in a hidden sweep the runs of the general step act on the host inside the same
-    lockstep ticks (act_many), so each run's rows stay those of its solo experiment(..., acting="device")."""
+    lockstep ticks (act_many), so each run's rows stay those of its solo experiment(..., acting="device").  Under
+    "device_all" those runs act on the device inside the same ticks, and each run's rows are those of its solo
+    experiment(..., acting="device_all")."""
     check_acting(acting)
     if resume and not checkpoint_dir:
         raise RuntimeError("experiment_sweep(resume=True) needs the checkpoint_dir to resume from")

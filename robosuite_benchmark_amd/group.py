@@ -33,13 +33,39 @@ def runs_general_step(t):
     return _general_shape(t._hidden("policy")) or _general_shape(t._hidden("qf1"))
 
 
-def act_many(trainers, obs_list, deterministic_list, eps_list):
+GENERAL = ("host", "device")
+
+
+def _check_general(general):
+    if general not in GENERAL:
+        raise RuntimeError(f"general must be one of {GENERAL}, got {general!r}")
+    return general
+
+
+def _act_general_many(lib, trainers, ids, n_rows, obs, det, eps, out):
+    """ONE sac_policy_act_general_many call per 16 of the general-step members `ids`: obs / eps / out hold a float32 array
+    (or None) per trainer, n_rows and det one value per trainer."""
+    for c in range(0, len(ids), MAX_MEMBERS):
+        part = ids[c:c + MAX_MEMBERS]
+        n = len(part)
+        vp = lambda arrs: (C.c_void_p * n)(*[None if a is None else a.ctypes.data for a in arrs])  # noqa: E731
+        _lib.check(lib.sac_policy_act_general_many((C.c_void_p * n)(*[trainers[i]._h.value for i in part]), n,
+                                                   (C.c_int32 * n)(*[n_rows[i] for i in part]), vp([obs[i] for i in part]),
+                                                   (C.c_int32 * n)(*[int(bool(det[i])) for i in part]),
+                                                   vp([eps[i] for i in part]), vp([out[i] for i in part])),
+                   "sac_policy_act_general_many")
+
+
+def act_many(trainers, obs_list, deterministic_list, eps_list, general="host"):
     """policy.get_actions for many runs at once: actions[i] = trainers[i]'s policy on obs_list[i] ((n_i, O_i); None or no
     rows: the member sits out and gets an empty array), deterministic_list[i] as MakeDeterministic, eps_list[i] the
     (n_i, A_i) N(0,1) draws of a stochastic SAC member (None otherwise).  The members with the fused kernels' shapes act
     in ONE launch per 16 of them (sac_policy_act_many: SAC and TD3, dims and row counts mixed; up to 1024 rows each);
     members of the general step act on the host through their own policy_act.  A member's actions never depend on its
-    neighbours: they are bit for bit those of its own policy_act_device (policy_act for the general step)."""
+    neighbours: they are bit for bit those of its own policy_act_device (policy_act for the general step).
+    general="device": the members of the general step act on the device as well, in ONE sac_policy_act_general_many call
+    per 16 of them; their actions are bit for bit those of their own policy_act_general."""
+    _check_general(general)
     trainers = list(trainers)
     R = len(trainers)
     if not (len(obs_list) == len(deterministic_list) == len(eps_list) == R):
@@ -49,7 +75,7 @@ def act_many(trainers, obs_list, deterministic_list, eps_list):
     obs = [None if o is None else _lib.f32(np.atleast_2d(o)) for o in obs_list]
     eps = [None if e is None else _lib.f32(np.atleast_2d(e)) for e in eps_list]
     out = [np.empty((0 if o is None else o.shape[0], t.act_dim), np.float32) for t, o in zip(trainers, obs)]
-    dev = []
+    dev, gen = [], []
     for i, t in enumerate(trainers):
         if out[i].shape[0] == 0:
             continue
@@ -58,11 +84,14 @@ def act_many(trainers, obs_list, deterministic_list, eps_list):
                                f"{None if eps[i] is None else eps[i].shape} do not fit dims ({t.obs_dim}, {t.act_dim})")
         if out[i].shape[0] > _lib.ACT_MAX_ROWS:
             raise RuntimeError(f"act_many member {i}: {out[i].shape[0]} rows (at most {_lib.ACT_MAX_ROWS} per call)")
-        if runs_general_step(t):
-            out[i] = t.policy_act(obs[i], deterministic_list[i], eps[i])
-        else:
+        if not runs_general_step(t):
             dev.append(i)
+        elif general == "device":
+            gen.append(i)
+        else:
+            out[i] = t.policy_act(obs[i], deterministic_list[i], eps[i])
     lib = _lib.load()
+    _act_general_many(lib, trainers, gen, [o.shape[0] for o in out], obs, deterministic_list, eps, out)
     for c in range(0, len(dev), MAX_MEMBERS):
         ids = dev[c:c + MAX_MEMBERS]
         n = len(ids)
@@ -128,9 +157,14 @@ class GroupActor:
     A session is bound to its members' handles: when a trainer has replaced its handle (a first step at another batch
     size; seen by the trainer's count of handles made, since an address can come back), act() reopens the sessions,
     carries the staged rows over and REPLACES the views, so read obs[i] / eps[i] / act[i] from the attributes on each
-    tick.  close() (and the finaliser) destroys the sessions.  The object holds device state only and is never pickled."""
+    tick.  close() (and the finaliser) destroys the sessions.  The object holds device state only and is never pickled.
 
-    def __init__(self, trainers, max_rows=1):
+    general="device": the members of the general step act on the device too -- all of them that have rows in ONE
+    sac_policy_act_general_many call per 16, on obs.astype(np.float32), the value the sessions' conversion produces --
+    and their actions are bit for bit those of their own policy_act_general on those rows."""
+
+    def __init__(self, trainers, max_rows=1, general="host"):
+        self.general = _check_general(general)
         self.trainers = list(trainers)
         R = len(self.trainers)
         if R == 0 or len({id(t) for t in self.trainers}) != R:
@@ -196,6 +230,15 @@ class GroupActor:
                 continue
             s.n_rows[:], s.det[:] = rows, [det[i] for i in s.ids]
             _lib.check(self._lib.sac_actor_act(s.a, s.n_rows, s.det), "sac_actor_act")
+        if self.general == "device":
+            ids = [i for i in self._host if n_rows[i]]
+            obs, eps, out = [None] * R, [None] * R, [None] * R
+            for i in ids:
+                obs[i] = np.ascontiguousarray(self.obs[i][:n_rows[i]].astype(np.float32))
+                eps[i] = None if det[i] or self._td3[i] else self.eps[i][:n_rows[i]]
+                out[i] = self.act[i][:n_rows[i]]
+            _act_general_many(self._lib, self.trainers, ids, n_rows, obs, det, eps, out)
+            return
         for i in self._host:
             n = n_rows[i]
             if n:

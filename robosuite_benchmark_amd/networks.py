@@ -56,11 +56,13 @@ def process_seed():
     return (zlib.crc32(np.ascontiguousarray(st[1], np.uint32).tobytes()) << 10) ^ int(st[2])
 
 
-ACTING = ("host", "device")
+ACTING = ("host", "device", "device_all")
 
 
 def check_acting(acting):
-    """'host': the acting path of sac_policy_act (the default); 'device': sac_policy_act_device / sac_policy_act_many."""
+    """'host': the acting path of sac_policy_act (the default); 'device': sac_policy_act_device / sac_policy_act_many for
+    the fused kernels' shapes (runs of the general step keep acting on the host); 'device_all': 'device', and the runs
+    of the general step act on the device too (sac_policy_act_general / sac_policy_act_general_many)."""
     if acting not in ACTING:
         raise ValueError(f"acting must be one of {ACTING}, got {acting!r}")
     return acting
@@ -69,11 +71,16 @@ def check_acting(acting):
 class _Mlp:
     # where a policy bound to a trainer acts (TanhGaussianPolicy, TanhMlpPolicy): "host" -- sac_policy_act, one
     # observation row per call from the mirrored weights -- or "device" -- sac_policy_act_device, every row of a call in
-    # one launch from the live weights.  The exploration noise is drawn on the host from the same stream either way.
+    # one launch from the live weights -- or "device_all" -- sac_policy_act_device for a trainer with the fused kernels'
+    # shapes, sac_policy_act_general (one launch per layer) for a trainer of the general step, which "device" refuses.
+    # The exploration noise is drawn on the host from the same stream whichever it is.
     acting = "host"
 
     def _act(self, tr, obs, deterministic, eps):
-        if check_acting(self.acting) == "device":
+        acting = check_acting(self.acting)
+        if acting == "device_all" and tr._lib.sac_trainer_step_kind(tr._h) == 3:       # (3: the general step)
+            return tr.policy_act_general(obs, deterministic, eps)
+        if acting != "host":
             return tr.policy_act_device(obs, deterministic, eps)
         return tr.policy_act(obs, deterministic, eps)
 

@@ -282,6 +282,21 @@ class SACTrainer:
                        "sac_policy_act_device")
         return out
 
+    def policy_act_general(self, obs, deterministic, eps):
+        """policy.get_actions on the DEVICE for a trainer of the general step (sac_policy_act_general: k_act_layer, one
+        launch per layer on the live weights): all rows of `obs` in one call per 1024 rows, no mirror of the policy on the
+        host.  Trainers with the fused kernels' shapes are refused by the library: policy_act_device is their entry."""
+        obs = _lib.f32(obs)
+        n, A = obs.shape[0], self.act_dim
+        out = np.empty((n, A), np.float32)
+        e = None if eps is None else _lib.f32(eps)
+        for i in range(0, n, _lib.ACT_MAX_ROWS):
+            j = min(n, i + _lib.ACT_MAX_ROWS)
+            _lib.check(self._lib.sac_policy_act_general(self._h, j - i, _lib.ptr(obs[i:j]), int(bool(deterministic)),
+                                                        None if e is None else _lib.ptr(e[i:j]), _lib.ptr(out[i:j])),
+                       "sac_policy_act_general")
+        return out
+
     def refresh_host_policy(self):
         """Mirror the trained policy D2H once per training block (acting stays on the host)."""
         if self._h is not None and self._host_policy_stale:

@@ -6,6 +6,8 @@ One JSON line per measurement, appended to --out (default: stdout only).
     python scripts/bench_acting.py --profile-pass       # a short run of the device calls alone, for a kernel trace
     python scripts/bench_acting.py --sessions [--out FILE]      # acting sessions (GroupActor) beside the calls above
     python scripts/bench_acting.py --profile-pass-sessions      # k_act and k_act_session side by side, for a kernel trace
+    python scripts/bench_acting.py --general [--out FILE]       # general-step acting: host forward against k_act_layer
+    python scripts/bench_acting.py --profile-pass-general       # a short run of the general-step device calls, for a kernel trace
 
 Every timed call returns with its actions on the host (the calls end synchronised), so a host clock around a window of
 calls measures them; a window lasts at least --window-s seconds after a warm-up, and each figure is the median over
@@ -34,10 +36,10 @@ from robosuite_benchmark_amd.group import act_many  # noqa: E402
 O, A = 42, 7                                        # Lift
 
 
-def make_trainer(seed, B=256):
+def make_trainer(seed, B=256, hidden=(256, 256)):
     rs = np.random.RandomState(seed)
-    qs = [FlattenMlp([256, 256], 1, O + A, rs=rs) for _ in range(4)]
-    pol = TanhGaussianPolicy([256, 256], O, A, rs=rs, noise=np.random.RandomState(seed))
+    qs = [FlattenMlp(list(hidden), 1, O + A, rs=rs) for _ in range(4)]
+    pol = TanhGaussianPolicy(list(hidden), O, A, rs=rs, noise=np.random.RandomState(seed))
     return SACTrainer(policy=pol, qf1=qs[0], qf2=qs[1], target_qf1=qs[2], target_qf2=qs[3], batch_size=B, noise_seed=seed)
 
 
@@ -218,6 +220,93 @@ def profile_pass():
     print("profile pass: 4 x 200 solo calls (n = 1, 16, 256, 1000), 200 grouped calls of 16 x 1 row", flush=True)
 
 
+GENERAL_SHAPES = ((512, 512), (256, 256, 256), (1024, 1024))
+
+
+def general_benches(args):
+    """(a) the host forward, one row; (b) policy_act_general at n = 1, 16, 256, 1000; (c) a 16-member GroupActor tick with
+    the general-step members on the host and on the device."""
+    from robosuite_benchmark_amd import GroupActor
+    rs = np.random.RandomState(0)
+    obs1, eps1 = rs.normal(0, 0.5, (1, O)).astype(np.float32), rs.normal(size=(1, A)).astype(np.float32)
+    for hidden in GENERAL_SHAPES:
+        t = make_trainer(1, hidden=hidden)
+        emit(dict(what="a: sac_policy_act, host, per row", hidden=list(hidden),
+                  **windows(lambda: t.policy_act(obs1, False, eps1), args.windows, args.window_s)), args.out)
+        for n in (1, 16, 256, 1000):
+            obs, eps = rs.normal(0, 0.5, (n, O)).astype(np.float32), rs.normal(size=(n, A)).astype(np.float32)
+            emit(dict(what="b: sac_policy_act_general, per call", hidden=list(hidden), n=n,
+                      **windows(lambda: t.policy_act_general(obs, False, eps), args.windows, args.window_s)), args.out)
+        del t
+    ts = [make_trainer(10 + i, hidden=(512, 512)) for i in range(16)]
+    obs64, draws = [rs.normal(0, 0.5, O) for _ in ts], [rs.normal(size=(1, A)) for _ in ts]
+    det, ones = [False] * 16, [1] * 16
+    for general in ("host", "device"):
+        g = GroupActor(ts, max_rows=1, general=general)
+
+        def tick():
+            for k in range(16):
+                g.obs[k][0] = obs64[k]
+                g.eps[k][0] = draws[k][0]
+            g.act(ones, det)
+            return [g.act[k][0].copy() for k in range(16)]
+        emit(dict(what=f"c: GroupActor(general={general!r}) tick, 16 members [512,512] x 1 row: rows in, act, rows out",
+                  **windows(tick, args.windows, args.window_s)), args.out)
+        g.close()
+
+
+def general_epoch_bench(args):
+    """(d) the evaluation + exploration phases of one experiment_sweep(hidden_sweep=True) epoch over a width sweep,
+    acting="device" (the wide members act on the host inside the lockstep ticks) against "device_all", alternating."""
+    from robosuite_benchmark_amd.driver import experiment_sweep
+    from robosuite_benchmark_amd.variant import default_variant
+    widths = [(256, 256), (512, 512), (1024, 1024), (256, 256, 256)]
+    runs = []
+    for i in range(args.seeds):
+        v = default_variant(env="Lift", seed=1 + i, batch_size=256)
+        v["replay_buffer_size"] = 100000
+        v["policy_kwargs"]["hidden_sizes"] = list(widths[i % len(widths)])
+        v["qf_kwargs"]["hidden_sizes"] = list(widths[i % len(widths)])
+        if args.epoch_trains:
+            v["algorithm_kwargs"]["num_trains_per_train_loop"] = args.epoch_trains
+        runs.append((v, 1 + i))
+    res = {"device": [], "device_all": []}
+    for rnd in range(args.rounds):
+        for mode in ("device", "device_all"):
+            rows = experiment_sweep(copy.deepcopy(runs), num_epochs=1, quiet=True, hidden_sweep=True, acting=mode)
+            r0 = rows[0][0]
+            res[mode].append(dict(sampling_s=r0["time/evaluation sampling (s)"] + r0["time/exploration sampling (s)"],
+                                  training_s=r0["time/training (s)"]))
+    ak = runs[0][0]["algorithm_kwargs"]
+    dev, dall = [r["sampling_s"] for r in res["device"]], [r["sampling_s"] for r in res["device_all"]]
+    emit(dict(what="d: evaluation + exploration seconds of one experiment_sweep(hidden_sweep=True) epoch, acting=device / device_all",
+              members=args.seeds, hidden=[list(widths[i % len(widths)]) for i in range(args.seeds)],
+              eval_steps=ak["num_eval_steps_per_epoch"], expl_steps=ak["num_expl_steps_per_train_loop"],
+              trains=ak["num_trains_per_train_loop"], rounds=args.rounds, device_sampling_s=dev, device_all_sampling_s=dall,
+              device_training_s=[r["training_s"] for r in res["device"]],
+              device_all_training_s=[r["training_s"] for r in res["device_all"]],
+              device_over_device_all=float(np.median(dev) / np.median(dall))), args.out)
+
+
+def profile_pass_general():
+    """k_act_layer alone: 200 calls per shape and row count, then 200 grouped calls of 16 x 1 row."""
+    rs = np.random.RandomState(0)
+    for hidden in GENERAL_SHAPES:
+        t = make_trainer(1, hidden=hidden)
+        for n in (1, 1000):
+            obs, eps = rs.normal(0, 0.5, (n, O)).astype(np.float32), rs.normal(size=(n, A)).astype(np.float32)
+            for _ in range(200):
+                t.policy_act_general(obs, False, eps)
+        del t
+    ts = [make_trainer(10 + i, hidden=(512, 512)) for i in range(16)]
+    obs_l = [rs.normal(0, 0.5, (1, O)).astype(np.float32) for _ in ts]
+    eps_l = [rs.normal(size=(1, A)).astype(np.float32) for _ in ts]
+    for _ in range(200):
+        act_many(ts, obs_l, [False] * 16, eps_l, general="device")
+    print("profile pass: 200 solo calls per shape in", [list(h) for h in GENERAL_SHAPES], "at n = 1 and 1000 (one launch per "
+          "layer), 200 grouped calls of 16 x [512,512] x 1 row", flush=True)
+
+
 if __name__ == "__main__":
     ap = argparse.ArgumentParser()
     ap.add_argument("--windows", type=int, default=3)
@@ -229,7 +318,21 @@ if __name__ == "__main__":
     ap.add_argument("--profile-pass", action="store_true")
     ap.add_argument("--sessions", action="store_true", help="the acting-session rows (c), (c'), (c''), (b), (b') and (d')")
     ap.add_argument("--profile-pass-sessions", action="store_true")
+    ap.add_argument("--general", action="store_true",
+                    help="general-step acting: rows (a) to (d) for [512,512], [256,256,256] and [1024,1024] policies")
+    ap.add_argument("--profile-pass-general", action="store_true")
+    ap.add_argument("--epoch-trains", type=int, default=0,
+                    help="with --general: gradient steps of the measured epoch (0: the variant's; the sampling phases "
+                         "that row (d) reports do not depend on it)")
     args = ap.parse_args()
+    if args.profile_pass_general:
+        profile_pass_general()
+        sys.exit(0)
+    if args.general:
+        general_benches(args)
+        if not args.skip_epoch:
+            general_epoch_bench(args)
+        sys.exit(0)
     if args.profile_pass_sessions:
         profile_pass_sessions()
         sys.exit(0)

@@ -11,7 +11,8 @@
  --hidden_sweep: the --variants may differ in their hidden sizes, one arch trainer group trains them all;
  DIR/<task>-h<sizes>-s<seed>/progress.csv each.  --hidden_sizes H1 H2 ...: every variant once per entry, policy and Q
  nets alike, implies --hidden_sweep.  --acting device: the policies act through the device kernel instead of the
- host forward; grouped runs then collect their paths in lockstep)
+ host forward; grouped runs then collect their paths in lockstep.  --acting device_all: the same, and runs of any
+ hidden sizes act on the device)
 Runs the variant unchanged (batch size, lrs, tau, period, buffer size ... from the JSON) on the
 HIP library with a synthetic environment of the task's dimensions (robosuite is not installed)."""
 import argparse
@@ -51,10 +52,12 @@ if __name__ == "__main__":
     ap.add_argument("--hidden_sizes", type=str, nargs="+", default=None,
                     help="with --variants: train every variant once per entry (comma-separated widths, e.g. 256,256 "
                          "512,512 256,256,256), policy and Q nets alike; implies --hidden_sweep")
-    ap.add_argument("--acting", type=str, default="host", choices=["host", "device"],
+    ap.add_argument("--acting", type=str, default="host", choices=["host", "device", "device_all"],
                     help="where the collectors' policies act: host (sac_policy_act, one observation per call) or device "
                          "(the policy forward as a HIP kernel on the live weights; with --seeds / --variants the runs "
-                         "collect in lockstep, all their actions of a tick from one launch of an acting session)")
+                         "collect in lockstep, all their actions of a tick from one launch of an acting session; runs "
+                         "whose hidden sizes are beyond two layers of at most 256 units still act on the host) or "
+                         "device_all (device, and those runs act on the device too, one launch per layer)")
     args = ap.parse_args()
     if (args.hidden_sweep or args.hidden_sizes) and not args.variants:
         raise SystemExit("--hidden_sweep / --hidden_sizes need --variants")
