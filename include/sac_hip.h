@@ -455,6 +455,32 @@ int sac_actor_arrays(sac_actor_t *a, int member, double **obs, float **eps, floa
  * outside 0..max_rows[i], all n_rows zero, a member confined by sac_trainer_set_xcd[_mask]. */
 int sac_actor_act(sac_actor_t *a, const int32_t *n_rows, const int32_t *deterministic);
 
+/* ------------------------------------------------------------------------------------------
+ * Acting sessions for GENERAL-STEP trainers: sac_policy_act_general_many for a FIXED list of trainers without the
+ * per-call marshalling (csrc/sac_actor_general.h).  A session owns one mapped pinned slab laid out as sac_actor's (a
+ * control block, then per member obs float64, eps and act float32 at fixed 256-byte-aligned addresses), a job table in
+ * device memory -- member i's layer l: weights, input, output, shapes -- written once at creation, and two activation
+ * buffers per member of its own (not the trainers': sessions over the same trainers and sac_policy_act_general share
+ * the weights only).  sac_gactor_act rewrites the control block (rows and stochastic flag per member, first workgroup
+ * per layer depth and member), launches k_act_layer_session once per layer depth and waits for one event; it copies
+ * nothing, allocates nothing and rebuilds no table.  Each member's actions are bit for bit those of
+ * sac_policy_act_general on the observations cast to float32 with the same eps; every refusal returns <0, sets
+ * sac_last_error and changes nothing.
+ * ------------------------------------------------------------------------------------------ */
+typedef struct sac_gactor sac_gactor_t;
+/* 1..SAC_GROUP_MAX general-step trainers of one device (SAC and TD3, dims, depths and widths mixed); max_rows[i] in
+ * 1..1024.  Refused (*out is NULL): null or duplicate trainers, more than SAC_GROUP_MAX, trainers on different devices,
+ * trainers with the fused kernels' shapes (sac_actor_create is their entry), max_rows outside 1..1024. */
+int sac_gactor_create(sac_gactor_t **out, sac_trainer_t *const *trainers, int n_trainers, const int32_t *max_rows);
+int sac_gactor_destroy(sac_gactor_t *a);        /* members are left as they are; they must outlive the session */
+/* member i's arrays inside the slab, as sac_actor_arrays: obs (max_rows, O) FLOAT64 (rounded to fp32 by the kernel as
+ * numpy's astype(float32) does), eps (max_rows, A) float32, act (max_rows, A) float32.  Out pointers may be NULL. */
+int sac_gactor_arrays(sac_gactor_t *a, int member, double **obs, float **eps, float **act);
+/* as sac_actor_act: rows [0, n_rows[i]) of every member, 0 = sits out, rows of act at and beyond n_rows[i] are not
+ * written, members with rows are drained first as by sac_sync.  Refused: n_rows[i] outside 0..max_rows[i], all n_rows
+ * zero, a member confined by sac_trainer_set_xcd[_mask]. */
+int sac_gactor_act(sac_gactor_t *a, const int32_t *n_rows, const int32_t *deterministic);
+
 #ifdef __cplusplus
 }
 #endif

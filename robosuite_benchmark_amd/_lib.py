@@ -130,6 +130,10 @@ SYMBOLS = {
     "sac_actor_destroy": (C.c_int, [_P]),
     "sac_actor_arrays": (C.c_int, [_P, C.c_int, C.POINTER(_P), C.POINTER(_P), C.POINTER(_P)]),
     "sac_actor_act": (C.c_int, [_P, _P, _P]),
+    "sac_gactor_create": (C.c_int, [C.POINTER(_P), _P, C.c_int, _P]),
+    "sac_gactor_destroy": (C.c_int, [_P]),
+    "sac_gactor_arrays": (C.c_int, [_P, C.c_int, C.POINTER(_P), C.POINTER(_P), C.POINTER(_P)]),
+    "sac_gactor_act": (C.c_int, [_P, _P, _P]),
 }
 
 _lib = None

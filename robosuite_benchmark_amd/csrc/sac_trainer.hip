@@ -2249,6 +2249,7 @@ int stage_batches(sac_trainer *t, sac_buffer *b, int64_t n_steps) {
 #include "sac_act.h"
 #include "sac_act_general.h"
 #include "sac_actor.h"
+#include "sac_actor_general.h"
 
 extern "C" {
 

@@ -170,11 +170,15 @@ class GroupPathCollector:
 
     general="device" (acting="device_all" of the drivers): act_many and the GroupActor factory are called with
     general="device", so that the members of the general step act on the device too; everything else, the draws from
-    the host generators included, is as under the default "host"."""
+    the host generators included, is as under the default "host".  general_sessions (True / False; None: GroupActor's
+    default) goes to the GroupActor factory with it: acting sessions for the members of the general step too."""
 
-    def __init__(self, collectors, act_many=act_many, sessions=False, actor=GroupActor, general="host"):
+    def __init__(self, collectors, act_many=act_many, sessions=False, actor=GroupActor, general="host", general_sessions=None):
         self.collectors, self._act_many = list(collectors), act_many
         self._general = dict(general=general) if general != "host" else {}
+        self._actor_kw = dict(self._general)
+        if general == "device" and general_sessions is not None:
+            self._actor_kw["general_sessions"] = bool(general_sessions)
         self._sessions, self._actor_factory, self._actor, self._actor_key = bool(sessions), actor, None, None
 
     def close(self):
@@ -190,7 +194,7 @@ class GroupPathCollector:
         if self._actor is None or key != self._actor_key:
             self.close()
             if slot:
-                self._actor = self._actor_factory([holders[i]._trainer for i in slot], max_rows=1, **self._general)
+                self._actor = self._actor_factory([holders[i]._trainer for i in slot], max_rows=1, **self._actor_kw)
             self._actor_key = key
         actor = self._actor
         det = [bool(parts[i][1]) for i in slot]
@@ -510,7 +514,7 @@ def _group_save(ck, runs, epoch):
 
 
 def _group_epochs(runs, train_block, n_epochs, n_train, log_dir, quiet, what, ck=None, first_epoch=0, acting="host",
-                  sessions=True):
+                  sessions=True, general_sessions=None):
     """The epoch loop of a grouped experiment: each run collects its paths, then train_block() trains every run at once,
     then every run ends its epoch, the group is saved (with a GroupCheckpoint `ck`), and each run writes its row (to
     <log_dir>/<run["sub"]>/progress.csv with log_dir; appended to after a resume).
@@ -518,10 +522,11 @@ def _group_epochs(runs, train_block, n_epochs, n_train, log_dir, quiet, what, ck
     exploration phase of all runs, every tick's actions from one act_many call (sessions=True: from one acting-session
     call, GroupActor, one session for each phase's collectors; the rows are the same); each run's time/*sampling (s) columns
     then hold the shared phase time.  acting="device_all": the same, and the lockstep collectors send the runs of the
-    general step to the device as well (general="device")."""
+    general step to the device as well (general="device"; with sessions=True, general_sessions says whether they get
+    acting sessions of their own, None: GroupActor's default -- the rows are the same either way)."""
     t_start = time.time()
     lockstep = acting != "host"
-    lock_kw = dict(sessions=sessions, general="device" if acting == "device_all" else "host")
+    lock_kw = dict(sessions=sessions, general="device" if acting == "device_all" else "host", general_sessions=general_sessions)
     lock_eval = GroupPathCollector([r["evalc"] for r in runs], **lock_kw) if lockstep else None
     lock_expl = GroupPathCollector([r["expl"] for r in runs], **lock_kw) if lockstep else None
     try:
@@ -598,7 +603,8 @@ def _group_epochs(runs, train_block, n_epochs, n_train, log_dir, quiet, what, ck
 
 
 def experiment_group(variant, seeds, log_dir=None, num_epochs=None, obs_dim=None, action_dim=None, device=0,
-                     quiet=False, checkpoint_dir=None, resume=False, chunk_rows=DEFAULT_CHUNK_ROWS, acting="host", sessions=True):
+                     quiet=False, checkpoint_dir=None, resume=False, chunk_rows=DEFAULT_CHUNK_ROWS, acting="host", sessions=True,
+                     general_sessions=None):
     """One configuration, several seeds, one process: each seed is the run ``experiment(variant, seed=s)`` would make --
     its own synthetic environments, collectors, weights and replay buffer -- and every epoch's training block is ONE
     SACTrainerGroup.train_loop (TD3 variants: TD3TrainerGroup; hidden sizes other than two layers of at most 256 units:
@@ -617,7 +623,8 @@ def experiment_group(variant, seeds, log_dir=None, num_epochs=None, obs_dim=None
     (sessions=True, the default: one acting-session call, group.GroupActor; False: one sac_policy_act_many call, the
     slower path kept for measuring against -- same rows); each run's rows are those of
     experiment(variant, seed=s, acting="device").  "device_all": the same, with the runs of the general step acting on the
-    device too (one sac_policy_act_general_many call per tick and 16 of them); rows as experiment(..., acting="device_all")."""
+    device too (one sac_policy_act_general_many call per tick and 16 of them; with sessions and general_sessions=True one
+    sac_gactor_act call, None: GroupActor's default); rows as experiment(..., acting="device_all")."""
     check_acting(acting)
     if resume and not checkpoint_dir:
         raise RuntimeError("experiment_group(resume=True) needs the checkpoint_dir to resume from")
@@ -644,7 +651,7 @@ def experiment_group(variant, seeds, log_dir=None, num_epochs=None, obs_dim=None
         train_block = lambda: group.train_loop([r["buf"] for r in runs], n_train, batch_size=ak["batch_size"])  # noqa: E731
     _group_epochs(runs, train_block,
                   num_epochs if num_epochs is not None else ak["num_epochs"], n_train, log_dir, quiet, "seeds", ck,
-                  first_epoch, acting, sessions)
+                  first_epoch, acting, sessions, general_sessions)
     return {r["seed"]: r["rows"] for r in runs}
 
 
@@ -670,7 +677,7 @@ def sweep_label(variant, seed, hidden_sweep=False):
 
 
 def experiment_sweep(runs, log_dir=None, num_epochs=None, device=0, quiet=False, checkpoint_dir=None, resume=False,
-                     chunk_rows=DEFAULT_CHUNK_ROWS, hidden_sweep=False, acting="host", sessions=True):
+                     chunk_rows=DEFAULT_CHUNK_ROWS, hidden_sweep=False, acting="host", sessions=True, general_sessions=None):
     """Several tasks x seeds, one process, one device: every entry of ``runs`` -- (variant, seed), or (variant, seed,
     obs_dim, action_dim) for a task without pinned dims -- is the run ``experiment(variant, seed=seed)`` would make, and
     every epoch's training block is ONE MixedSACTrainerGroup.train_loop (TD3 variants: MixedTD3TrainerGroup; hidden sizes
@@ -738,5 +745,5 @@ def experiment_sweep(runs, log_dir=None, num_epochs=None, device=0, quiet=False,
     batches = [r["ak"]["batch_size"] for r in group_runs]
     _group_epochs(group_runs, lambda: group.train_loop([r["buf"] for r in group_runs], n_train, batch_sizes=batches),
                   num_epochs if num_epochs is not None else ak0["num_epochs"], n_train, log_dir, quiet, "runs", ck,
-                  first_epoch, acting, sessions)
+                  first_epoch, acting, sessions, general_sessions)
     return [r["rows"] for r in group_runs]

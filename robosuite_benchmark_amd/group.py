@@ -34,6 +34,8 @@ def runs_general_step(t):
 
 
 GENERAL = ("host", "device")
+GENERAL_SESSIONS = True         # GroupActor(general="device")'s default for general_sessions: switched on by the
+                                # measurement of DESIGN.md, section 6d (the actions are the same bits either way)
 
 
 def _check_general(general):
@@ -104,28 +106,35 @@ def act_many(trainers, obs_list, deterministic_list, eps_list, general="host"):
 
 
 class _ActorSession:
-    """One sac_actor session (at most 16 device members): its handle, the members' handles it was opened on, and the
-    per-call argument arrays, made once."""
+    """One acting session (at most 16 members): its handle, the members' handles it was opened on, and the per-call
+    argument arrays, made once.  entry: "sac_actor" (the fused kernels' shapes) or "sac_gactor" (the general step) --
+    the two families of include/sac_hip.h have the same four signatures."""
 
-    def __init__(self, lib, ids, trainers, max_rows):
+    def __init__(self, lib, ids, trainers, max_rows, entry="sac_actor"):
         n = len(ids)
-        self.lib, self.ids, self.a = lib, ids, C.c_void_p()
+        self.lib, self.ids, self.a, self.entry = lib, ids, C.c_void_p(), entry
         self.handles = [trainers[i]._h.value for i in ids]
         self.gens = [trainers[i]._handle_gen for i in ids]      # (an address can come back; the count cannot)
         self.n_rows, self.det = (C.c_int32 * n)(), (C.c_int32 * n)()
-        _lib.check(lib.sac_actor_create(C.byref(self.a), (C.c_void_p * n)(*self.handles), n,
-                                        (C.c_int32 * n)(*[max_rows[i] for i in ids])), "sac_actor_create")
+        self._act = getattr(lib, entry + "_act")
+        _lib.check(getattr(lib, entry + "_create")(C.byref(self.a), (C.c_void_p * n)(*self.handles), n,
+                                                   (C.c_int32 * n)(*[max_rows[i] for i in ids])), entry + "_create")
 
     def arrays(self, k, rows, O, A):
         o, e, a = C.c_void_p(), C.c_void_p(), C.c_void_p()
-        _lib.check(self.lib.sac_actor_arrays(self.a, k, C.byref(o), C.byref(e), C.byref(a)), "sac_actor_arrays")
+        _lib.check(getattr(self.lib, self.entry + "_arrays")(self.a, k, C.byref(o), C.byref(e), C.byref(a)),
+                   self.entry + "_arrays")
         view = lambda p, ct, cols: np.ctypeslib.as_array((ct * (rows * cols)).from_address(p.value)).reshape(rows, cols)  # noqa: E731
         return view(o, C.c_double, O), view(e, C.c_float, A), view(a, C.c_float, A)
+
+    def act(self):
+        """One tick on n_rows / det as they stand."""
+        _lib.check(self._act(self.a, self.n_rows, self.det), self.entry + "_act")
 
     def destroy(self):
         a, self.a = self.a, None
         if a:
-            self.lib.sac_actor_destroy(a)
+            getattr(self.lib, self.entry + "_destroy")(a)
 
 
 class _ActRows(list):
@@ -161,10 +170,18 @@ class GroupActor:
 
     general="device": the members of the general step act on the device too -- all of them that have rows in ONE
     sac_policy_act_general_many call per 16, on obs.astype(np.float32), the value the sessions' conversion produces --
-    and their actions are bit for bit those of their own policy_act_general on those rows."""
+    and their actions are bit for bit those of their own policy_act_general on those rows.
 
-    def __init__(self, trainers, max_rows=1, general="host"):
+    general="device", general_sessions=True: the members of the general step get acting sessions of their own
+    (sac_gactor_*, csrc/sac_actor_general.h), one per 16 of them: obs[i] (float64), eps[i] and act[i] are views into that
+    session's slab like the other members', their tick is one C call, and reopening, close() and the pickling refusal
+    cover them too.  This is the default (None: GENERAL_SESSIONS).  The actions are the same bits as with
+    general_sessions=False, which keeps the sac_policy_act_general_many path described above, to measure against.  With
+    general="host" the keyword changes nothing."""
+
+    def __init__(self, trainers, max_rows=1, general="host", general_sessions=None):
         self.general = _check_general(general)
+        self.general_sessions = general == "device" and bool(GENERAL_SESSIONS if general_sessions is None else general_sessions)
         self.trainers = list(trainers)
         R = len(self.trainers)
         if R == 0 or len({id(t) for t in self.trainers}) != R:
@@ -179,8 +196,9 @@ class GroupActor:
         self._td3 = [isinstance(t, TD3Trainer) for t in self.trainers]
         self._host = [i for i, t in enumerate(self.trainers) if runs_general_step(t)]
         self._dev = [i for i in range(R) if i not in set(self._host)]
+        self._gen = self._host if self.general_sessions else []      # the general-step members with sessions
         self.obs, self.eps, self.act = [None] * R, [None] * R, _ActRows(self._act, [None] * R)
-        for i in self._host:
+        for i in self._host if not self.general_sessions else ():
             t, m = self.trainers[i], self.max_rows[i]
             self.obs[i], self.eps[i] = np.zeros((m, t.obs_dim), np.float64), np.zeros((m, t.act_dim), np.float32)
             self.act[i] = np.zeros((m, t.act_dim), np.float32)
@@ -188,19 +206,21 @@ class GroupActor:
         self._open()
 
     def _open(self):
-        for c in range(0, len(self._dev), MAX_MEMBERS):
-            s = _ActorSession(self._lib, self._dev[c:c + MAX_MEMBERS], self.trainers, self.max_rows)
-            self._sessions.append(s)
-            for k, i in enumerate(s.ids):
-                t = self.trainers[i]
-                self.obs[i], self.eps[i], self.act[i] = s.arrays(k, self.max_rows[i], t.obs_dim, t.act_dim)
+        for ids, entry in ((self._dev, "sac_actor"), (self._gen, "sac_gactor")):
+            for c in range(0, len(ids), MAX_MEMBERS):
+                s = _ActorSession(self._lib, ids[c:c + MAX_MEMBERS], self.trainers, self.max_rows, entry)
+                self._sessions.append(s)
+                for k, i in enumerate(s.ids):
+                    t = self.trainers[i]
+                    self.obs[i], self.eps[i], self.act[i] = s.arrays(k, self.max_rows[i], t.obs_dim, t.act_dim)
 
     def _reopen(self):
         """A member's handle was replaced: new sessions on the handles of now, the staged rows carried over."""
-        for i in self._dev:
+        members = self._dev + self._gen
+        for i in members:
             if self.trainers[i]._h is None:
                 raise RuntimeError(f"GroupActor member {i} has lost its device handle")
-        kept = {i: (self.obs[i].copy(), self.eps[i].copy(), self.act[i].copy()) for i in self._dev}
+        kept = {i: (self.obs[i].copy(), self.eps[i].copy(), self.act[i].copy()) for i in members}
         self._destroy()
         self._open()
         for i, (o, e, a) in kept.items():
@@ -229,7 +249,9 @@ class GroupActor:
             if not any(rows):
                 continue
             s.n_rows[:], s.det[:] = rows, [det[i] for i in s.ids]
-            _lib.check(self._lib.sac_actor_act(s.a, s.n_rows, s.det), "sac_actor_act")
+            s.act()
+        if self.general_sessions:
+            return
         if self.general == "device":
             ids = [i for i in self._host if n_rows[i]]
             obs, eps, out = [None] * R, [None] * R, [None] * R

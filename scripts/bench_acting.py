@@ -8,6 +8,7 @@ One JSON line per measurement, appended to --out (default: stdout only).
     python scripts/bench_acting.py --profile-pass-sessions      # k_act and k_act_session side by side, for a kernel trace
     python scripts/bench_acting.py --general [--out FILE]       # general-step acting: host forward against k_act_layer
     python scripts/bench_acting.py --profile-pass-general       # a short run of the general-step device calls, for a kernel trace
+    python scripts/bench_acting.py --general-sessions [--out FILE]      # general-step acting sessions beside the per-tick calls
 
 Every timed call returns with its actions on the host (the calls end synchronised), so a host clock around a window of
 calls measures them; a window lasts at least --window-s seconds after a warm-up, and each figure is the median over
@@ -16,7 +17,11 @@ the same tick through a GroupActor -- 16 observations and 16 eps rows written in
 -- (c'') the bare sac_actor_act call, (b) and (b') a one-member session at n = 1, 16, 256, 1000, and (d') the sampling
 phases of the group epoch with sessions=True and sessions=False alternating.  (d) runs experiment_group with --seeds seeds of the
 default Lift variant for one epoch at its default step counts, acting="host" and acting="device" alternating --rounds
-times, and reports each mode's evaluation + exploration seconds of that epoch."""
+times, and reports each mode's evaluation + exploration seconds of that epoch.  --general-sessions measures, in ONE
+process and with the two paths' windows alternating, (g) the tick of 16 [512,512] members x 1 row through
+GroupActor(general="device", general_sessions=False), (g') the same tick with general_sessions=True, (g'') the bare
+sac_gactor_act call, one member at n = 1, 16, 1000 on both paths, and the sampling phases of a 16-seed [512,512]
+experiment_group epoch with acting="device_all", general_sessions on and off alternating."""
 from __future__ import annotations
 
 import argparse
@@ -242,7 +247,7 @@ def general_benches(args):
     obs64, draws = [rs.normal(0, 0.5, O) for _ in ts], [rs.normal(size=(1, A)) for _ in ts]
     det, ones = [False] * 16, [1] * 16
     for general in ("host", "device"):
-        g = GroupActor(ts, max_rows=1, general=general)
+        g = GroupActor(ts, max_rows=1, general=general, general_sessions=False)      # (sessions: --general-sessions)
 
         def tick():
             for k in range(16):
@@ -288,6 +293,115 @@ def general_epoch_bench(args):
               device_over_device_all=float(np.median(dev) / np.median(dall))), args.out)
 
 
+def alternating_windows(fns, n_windows, window_s, warm_s=0.2):
+    """windows() for several callables measured in turn: window w of every one, then window w + 1 of every one, so that
+    none of them runs "later" than the others.  Returns {name: the figures of windows()}."""
+    for fn in fns.values():
+        t_end = time.perf_counter() + warm_s
+        while time.perf_counter() < t_end:
+            fn()
+    per = {k: [] for k in fns}
+    for _ in range(n_windows):
+        for k, fn in fns.items():
+            n, t0 = 0, time.perf_counter()
+            while True:
+                for _ in range(20):
+                    fn()
+                n += 20
+                dt = time.perf_counter() - t0
+                if dt >= window_s:
+                    break
+            per[k].append(1e6 * dt / n)
+    return {k: dict(us_median=float(np.median(v)), us_min=float(min(v)), us_max=float(max(v)), windows=n_windows)
+            for k, v in per.items()}
+
+
+def general_session_benches(args):
+    """(g), (g'), (g'') and the one-member rows: GroupActor(general="device") with general_sessions off and on."""
+    from robosuite_benchmark_amd import GroupActor, _lib
+    rs = np.random.RandomState(0)
+    hidden = (512, 512)
+    ts = [make_trainer(10 + i, hidden=hidden) for i in range(16)]
+    obs64, draws = [rs.normal(0, 0.5, O) for _ in ts], [rs.normal(size=(1, A)) for _ in ts]
+    det, ones = [False] * 16, [1] * 16
+    gs = {flag: GroupActor(ts, max_rows=1, general="device", general_sessions=flag) for flag in (False, True)}
+
+    def tick_of(g):
+        def tick():
+            for k in range(16):
+                g.obs[k][0] = obs64[k]
+                g.eps[k][0] = draws[k][0]
+            g.act(ones, det)
+            return [g.act[k][0].copy() for k in range(16)]
+        return tick
+    sess = gs[True]._sessions[0]
+    lib = _lib.load()
+
+    def bare():
+        sess.n_rows[:], sess.det[:] = ones, [0] * 16
+        return lambda: lib.sac_gactor_act(sess.a, sess.n_rows, sess.det)
+    a, b = tick_of(gs[False])(), tick_of(gs[True])()
+    assert all(np.array_equal(x.view(np.uint32), y.view(np.uint32)) for x, y in zip(a, b)), "the two paths disagree"
+    res = alternating_windows({"g": tick_of(gs[False]), "g'": tick_of(gs[True]), "g''": bare()}, args.windows, args.window_s)
+    what = {"g": "g: GroupActor(general='device', general_sessions=False) tick, 16 members [512,512] x 1 row: rows in, act, rows out",
+            "g'": "g': the same tick with general_sessions=True",
+            "g''": "g'': sac_gactor_act alone, 16 members [512,512] x 1 row"}
+    for k, r in res.items():
+        emit(dict(what=what[k], hidden=list(hidden), **r), args.out)
+    for g in gs.values():
+        g.close()
+    t = ts[0]
+    g1 = {flag: GroupActor([t], max_rows=1000, general="device", general_sessions=flag) for flag in (False, True)}
+    for n in (1, 16, 1000):
+        o64, e = rs.normal(0, 0.5, (n, O)), rs.normal(size=(n, A)).astype(np.float32)
+
+        def tick1_of(g):
+            def tick1():
+                g.obs[0][:n] = o64
+                g.eps[0][:n] = e
+                g.act([n], False)
+                return g.act[0][:n].copy()
+            return tick1
+        res = alternating_windows({False: tick1_of(g1[False]), True: tick1_of(g1[True])}, args.windows, args.window_s)
+        for flag, r in res.items():
+            emit(dict(what=f"one-member GroupActor(general='device', general_sessions={flag}) tick (rows in, act, rows out)",
+                      hidden=list(hidden), n=n, **r), args.out)
+    for g in g1.values():
+        g.close()
+
+
+def general_session_epoch_bench(args):
+    """The evaluation + exploration phases of one 16-seed [512,512] experiment_group epoch, acting="device_all", general
+    sessions on and off alternating."""
+    import robosuite_benchmark_amd.driver as drv
+    from robosuite_benchmark_amd.variant import default_variant
+    v = default_variant(env="Lift", seed=1, batch_size=256)
+    v["replay_buffer_size"] = 100000
+    v["policy_kwargs"]["hidden_sizes"] = [512, 512]
+    v["qf_kwargs"]["hidden_sizes"] = [512, 512]
+    if args.epoch_trains:
+        v["algorithm_kwargs"]["num_trains_per_train_loop"] = args.epoch_trains
+    seeds = list(range(1, args.seeds + 1))
+    res = {True: [], False: []}
+    for rnd in range(args.rounds):
+        for flag in (True, False):
+            rows = drv.experiment_group(copy.deepcopy(v), seeds, num_epochs=1, quiet=True, acting="device_all", sessions=True,
+                                        general_sessions=flag)
+            r0 = rows[seeds[0]][0]
+            res[flag].append(dict(sampling_s=r0["time/evaluation sampling (s)"] + r0["time/exploration sampling (s)"],
+                                  training_s=r0["time/training (s)"]))
+    ak = v["algorithm_kwargs"]
+    on, off = [r["sampling_s"] for r in res[True]], [r["sampling_s"] for r in res[False]]
+    emit(dict(what="evaluation + exploration seconds of one [512,512] experiment_group epoch, acting=device_all, general "
+                   "sessions on / off", seeds=args.seeds, eval_steps=ak["num_eval_steps_per_epoch"],
+              expl_steps=ak["num_expl_steps_per_train_loop"], trains=ak["num_trains_per_train_loop"], rounds=args.rounds,
+              general_sessions_sampling_s=on, general_many_sampling_s=off,
+              general_sessions_training_s=[r["training_s"] for r in res[True]],
+              general_many_training_s=[r["training_s"] for r in res[False]],
+              sessions_below_in_every_round=bool(all(a < b for a, b in zip(on, off))),
+              general_many_over_sessions=float(np.median(off) / np.median(on))), args.out)
+
+
 def profile_pass_general():
     """k_act_layer alone: 200 calls per shape and row count, then 200 grouped calls of 16 x 1 row."""
     rs = np.random.RandomState(0)
@@ -321,12 +435,19 @@ if __name__ == "__main__":
     ap.add_argument("--general", action="store_true",
                     help="general-step acting: rows (a) to (d) for [512,512], [256,256,256] and [1024,1024] policies")
     ap.add_argument("--profile-pass-general", action="store_true")
+    ap.add_argument("--general-sessions", action="store_true",
+                    help="general-step acting sessions: rows (g), (g'), (g''), one member at n = 1, 16, 1000 and the epoch row")
     ap.add_argument("--epoch-trains", type=int, default=0,
-                    help="with --general: gradient steps of the measured epoch (0: the variant's; the sampling phases "
+                    help="with --general / --general-sessions: gradient steps of the measured epoch (0: the variant's; the sampling phases "
                          "that row (d) reports do not depend on it)")
     args = ap.parse_args()
     if args.profile_pass_general:
         profile_pass_general()
+        sys.exit(0)
+    if args.general_sessions:
+        general_session_benches(args)
+        if not args.skip_epoch:
+            general_session_epoch_bench(args)
         sys.exit(0)
     if args.general:
         general_benches(args)

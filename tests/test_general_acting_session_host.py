@@ -1,0 +1,341 @@
+"""Host side of acting sessions for general-step policies (no GPU): the four sac_gactor_* entry points in the header,
+the bindings and the built library, and group.GroupActor's bookkeeping for general_sessions= against a stand-in library
+(injected in place of _lib.load(), with the C ABI's signatures: it hands out NumPy arrays as slabs and computes a simple
+function of the staged rows, the same one for both acting paths)."""
+import ctypes as C
+import os
+import pickle
+
+import numpy as np
+import pytest
+
+from robosuite_benchmark_amd import GroupActor, _lib
+from robosuite_benchmark_amd import group as group_mod
+from robosuite_benchmark_amd.driver import GroupPathCollector, PathCollector
+from tests.test_acting_session_host import holder_of
+from tests.test_device_acting_host import member
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+ENTRIES = ("sac_gactor_create", "sac_gactor_destroy", "sac_gactor_arrays", "sac_gactor_act")
+
+
+def test_header_bindings_and_library_name_the_entry_points():
+    header = open(os.path.join(ROOT, "include", "sac_hip.h")).read()
+    lib = C.CDLL(_lib.LIB_PATH)
+    for name in ENTRIES:
+        assert f"int {name}(" in header and name in _lib.SYMBOLS
+        assert getattr(lib, name) is not None                           # (AttributeError if the library lacks it)
+        assert _lib.SYMBOLS[name] == _lib.SYMBOLS[name.replace("sac_gactor", "sac_actor")]
+    assert "typedef struct sac_gactor sac_gactor_t;" in header
+    src = open(os.path.join(ROOT, "robosuite_benchmark_amd", "csrc", "sac_trainer.hip")).read()
+    assert src.index('#include "sac_act_general.h"') < src.index('#include "sac_actor_general.h"')
+
+
+def test_sac_actor_create_still_refuses_general_step_trainers_in_its_source():
+    src = open(os.path.join(ROOT, "robosuite_benchmark_amd", "csrc", "sac_actor.h")).read()
+    assert 'SAC_REQUIRE(!t->gen, "trainer %d runs the general step' in src
+    gsrc = open(os.path.join(ROOT, "robosuite_benchmark_amd", "csrc", "sac_actor_general.h")).read()
+    assert "SAC_REQUIRE(t->gen," in gsrc and "sac_actor_create" in gsrc
+
+
+# ---- the stand-in ---------------------------------------------------------------------------------------------------------
+class Handle:
+    """c_void_p's face: .value."""
+
+    def __init__(self, value):
+        self.value = value
+
+
+class Trainer:
+    """What GroupActor asks of a trainer: a handle, the count of handles made, dims and hidden sizes."""
+    next_handle = [1000]
+
+    def __init__(self, O, A, hidden):
+        self.obs_dim, self.act_dim, self.hidden = O, A, list(hidden)
+        self._h, self._handle_gen = None, 0
+        self.new_handle()
+
+    def new_handle(self):
+        Trainer.next_handle[0] += 8
+        self._h, self._handle_gen = Handle(Trainer.next_handle[0]), self._handle_gen + 1
+        DIMS[self._h.value] = (self.obs_dim, self.act_dim)
+
+    def _hidden(self, net):
+        return self.hidden
+
+
+DIMS = {}                                                                 # handle -> (O, A)
+
+
+def actions_of(handle, obs32, det, eps):
+    """The stand-in's policy: a function of the handle, the float32 observations and (stochastic) eps."""
+    A = DIMS[handle][1]
+    base = obs32.astype(np.float32).sum(1, dtype=np.float32)[:, None] + np.float32(handle % 97) + np.arange(A, dtype=np.float32)
+    return (base if det else base + eps).astype(np.float32)
+
+
+class Lib:
+    """sac_actor_* / sac_gactor_* / sac_policy_act_general_many with the C signatures, on NumPy arrays; every call is
+    logged as (name, ...)."""
+
+    def __init__(self):
+        self.log, self.sessions, self.next_id = [], {}, 50
+
+    def _create(self, entry, ref, handles, n, max_rows):
+        self.next_id += 1
+        ref._obj.value = self.next_id
+        hs, mr = [handles[i] for i in range(n)], [max_rows[i] for i in range(n)]
+        arrs = [(np.full((m, DIMS[h][0]), np.nan), np.full((m, DIMS[h][1]), np.nan, np.float32),
+                 np.full((m, DIMS[h][1]), np.nan, np.float32)) for h, m in zip(hs, mr)]
+        self.sessions[self.next_id] = dict(entry=entry, handles=hs, max_rows=mr, arrays=arrs)
+        self.log.append((entry + "_create", self.next_id, hs, mr))
+        return 0
+
+    def _arrays(self, entry, a, k, ro, re, ra):
+        s = self.sessions[a.value]
+        assert s["entry"] == entry
+        for ref, arr in zip((ro, re, ra), s["arrays"][k]):
+            ref._obj.value = arr.ctypes.data
+        return 0
+
+    def _act(self, entry, a, n_rows, det):
+        s = self.sessions[a.value]
+        assert s["entry"] == entry
+        rows, flags = list(n_rows), [bool(d) for d in det]
+        assert len(rows) == len(s["handles"]) and any(rows)
+        self.log.append((entry + "_act", a.value, rows, flags))
+        for (o, e, act), h, n, d in zip(s["arrays"], s["handles"], rows, flags):
+            if n:
+                assert o.dtype == np.float64 and np.all(np.isfinite(o[:n]))
+                act[:n] = actions_of(h, o[:n].astype(np.float32), d, e[:n])
+        return 0
+
+    def _destroy(self, entry, a):
+        assert self.sessions.pop(a.value)["entry"] == entry
+        self.log.append((entry + "_destroy", a.value))
+        return 0
+
+    def sac_policy_act_general_many(self, handles, n, n_rows, obs, det, eps, out):
+        hs, rows = [handles[i] for i in range(n)], [n_rows[i] for i in range(n)]
+        self.log.append(("sac_policy_act_general_many", hs, rows, [bool(det[i]) for i in range(n)]))
+        for i, (h, r) in enumerate(zip(hs, rows)):
+            O, A = DIMS[h]
+            view = lambda p, cols: np.ctypeslib.as_array((C.c_float * (r * cols)).from_address(p)).reshape(r, cols)  # noqa: E731
+            view(out[i], A)[...] = actions_of(h, view(obs[i], O), bool(det[i]), None if eps[i] is None else view(eps[i], A))
+        return 0
+
+
+for _entry in ("sac_actor", "sac_gactor"):
+    for _op in ("create", "arrays", "act", "destroy"):
+        setattr(Lib, f"{_entry}_{_op}", (lambda e, o: lambda self, *a: getattr(self, "_" + o)(e, *a))(_entry, _op))
+
+
+@pytest.fixture
+def lib(monkeypatch):
+    fake = Lib()
+    monkeypatch.setattr(_lib, "load", lambda: fake)
+    return fake
+
+
+def members(n_fused, n_general):
+    ts = [Trainer(5 + i, 2 + i % 3, (256, 256)) for i in range(n_fused)]
+    ts += [Trainer(4 + i % 5, 1 + i % 4, [(512, 512), (64, 64, 64), (1024,)][i % 3]) for i in range(n_general)]
+    order = np.random.RandomState(3).permutation(len(ts))                  # the two kinds interleaved
+    return [ts[i] for i in order]
+
+
+def stage(g, rs, n_rows):
+    data = []
+    for i, t in enumerate(g.trainers):
+        o, e = rs.normal(size=(g.max_rows[i], t.obs_dim)), rs.normal(size=(g.max_rows[i], t.act_dim)).astype(np.float32)
+        g.obs[i][...], g.eps[i][...] = o, e
+        g.act[i][...] = -5.0
+        data.append((o, e))
+    return data
+
+
+def names(log):
+    return [c[0] for c in log]
+
+
+# ---- GroupActor -----------------------------------------------------------------------------------------------------------
+def test_general_members_are_partitioned_into_sessions_of_at_most_sixteen(lib):
+    ts = members(2, 19)
+    gen = [i for i, t in enumerate(ts) if group_mod.runs_general_step(t)]
+    g = GroupActor(ts, max_rows=[1 + i % 3 for i in range(21)], general="device", general_sessions=True)
+    assert g.general_sessions and len(gen) == 19
+    made = [c for c in lib.log if c[0].endswith("_create")]
+    assert names(made) == ["sac_actor_create", "sac_gactor_create", "sac_gactor_create"]
+    assert made[0][2] == [t._h.value for t in ts if not group_mod.runs_general_step(t)]
+    assert made[1][2] == [ts[i]._h.value for i in gen[:16]] and made[2][2] == [ts[i]._h.value for i in gen[16:]]
+    assert made[1][3] == [g.max_rows[i] for i in gen[:16]] and made[2][3] == [g.max_rows[i] for i in gen[16:]]
+    # every member's arrays are views of its session's slab: float64 observations, float32 eps and actions
+    slabs = [a for s in lib.sessions.values() for arrs in s["arrays"] for a in arrs]
+    for i, t in enumerate(ts):
+        assert g.obs[i].dtype == np.float64 and g.obs[i].shape == (g.max_rows[i], t.obs_dim)
+        assert g.eps[i].dtype == g.act[i].dtype == np.float32 and g.eps[i].shape == g.act[i].shape == (g.max_rows[i], t.act_dim)
+        for v in (g.obs[i], g.eps[i], g.act[i]):
+            assert not v.flags["OWNDATA"] and sum(np.shares_memory(v, a) for a in slabs) == 1
+    g.close()
+
+
+def test_a_tick_is_one_call_per_session_with_rows_and_equals_the_general_many_path(lib):
+    ts = members(2, 19)
+    gen = [i for i, t in enumerate(ts) if group_mod.runs_general_step(t)]
+    max_rows = [1 + i % 3 for i in range(21)]
+    on = GroupActor(ts, max_rows=max_rows, general="device", general_sessions=True)
+    off = GroupActor(ts, max_rows=max_rows, general="device", general_sessions=False)
+    assert not off.general_sessions
+    rs = np.random.RandomState(1)
+    plans = [(list(max_rows), [i % 2 == 0 for i in range(21)]),
+             ([m if i not in gen[16:] else 0 for i, m in enumerate(max_rows)], False),       # the second session sits out
+             ([1 if i in (gen[0], gen[17]) else 0 for i in range(21)], True)]                # ... and the fused members
+    for n_rows, det in plans:
+        state = rs.get_state()
+        stage(on, rs, n_rows)
+        rs.set_state(state)
+        data = stage(off, rs, n_rows)
+        del lib.log[:]
+        on.act(n_rows, det)
+        ticks = list(lib.log)
+        del lib.log[:]
+        off.act(n_rows, det)
+        flags = [det] * 21 if isinstance(det, bool) else det
+        want = []
+        for s in on._sessions:
+            rows = [n_rows[i] for i in s.ids]
+            if any(rows):
+                want.append((s.entry + "_act", s.a.value, rows, [flags[i] for i in s.ids]))
+        assert ticks == want and len(ticks) == sum(any(n_rows[i] for i in s.ids) for s in on._sessions)
+        # general_sessions=False: today's calls -- the fused sessions, then ONE sac_policy_act_general_many per 16 members
+        # with rows, on float32 observations
+        live = [i for i in gen if n_rows[i]]
+        many = [c for c in lib.log if c[0] == "sac_policy_act_general_many"]
+        assert not any("gactor" in c[0] for c in lib.log)
+        assert [c[1] for c in many] == [[ts[i]._h.value for i in live[c:c + 16]] for c in range(0, len(live), 16)]
+        assert [c[2] for c in many] == [[n_rows[i] for i in live[c:c + 16]] for c in range(0, len(live), 16)]
+        for i, (o, e) in enumerate(data):
+            n = n_rows[i]
+            assert np.array_equal(on.act[i], off.act[i]) and np.all(on.act[i][n:] == -5.0), i
+            if n:
+                stochastic = not flags[i]
+                assert np.array_equal(on.act[i][:n], actions_of(ts[i]._h.value, o[:n].astype(np.float32), not stochastic, e[:n]))
+    on.close()
+    off.close()
+
+
+def test_general_sessions_false_and_the_default_call_what_they_called_before(lib):
+    assert group_mod.GENERAL_SESSIONS in (False, True)
+    ts = members(1, 3)
+    logs = []
+    for kw in (dict(general="device", general_sessions=False), dict(general="host", general_sessions=True), dict(general="host")):
+        del lib.log[:]
+        g = GroupActor(ts, max_rows=2, **kw)
+        assert not g.general_sessions
+        for i, t in enumerate(ts):
+            if group_mod.runs_general_step(t):                             # ordinary arrays behind the same attributes
+                assert g.obs[i].flags["OWNDATA"] and g.obs[i].dtype == np.float64 and g.act[i].flags["OWNDATA"]
+        logs.append(names(lib.log))
+        g.close()
+    assert logs[0] == logs[1] == logs[2] == ["sac_actor_create"]
+    del lib.log[:]
+    g = GroupActor(ts, max_rows=2, general="device")                       # the default follows group.GENERAL_SESSIONS
+    assert g.general_sessions == group_mod.GENERAL_SESSIONS
+    assert ("sac_gactor_create" in names(lib.log)) == group_mod.GENERAL_SESSIONS
+    g.close()
+
+
+def test_a_replaced_handle_reopens_the_sessions_and_carries_the_staged_rows_over(lib):
+    ts = members(2, 5)
+    gen = [i for i, t in enumerate(ts) if group_mod.runs_general_step(t)]
+    g = GroupActor(ts, max_rows=3, general="device", general_sessions=True)
+    rs = np.random.RandomState(2)
+    n_rows = [3] * 7
+    data = stage(g, rs, n_rows)
+    g.act(n_rows, False)
+    before = [a.copy() for a in g.act]
+    old_views, old_ids = list(g.obs), set(lib.sessions)
+    t = ts[gen[2]]
+    old = t._h.value
+    t.new_handle()
+    del lib.log[:]
+    g.act([0 if i == gen[2] else 3 for i in range(7)], False)              # the member with the new handle sits out
+    assert names(lib.log) == ["sac_actor_destroy", "sac_gactor_destroy", "sac_actor_create", "sac_gactor_create",
+                              "sac_actor_act", "sac_gactor_act"]
+    assert not old_ids & set(lib.sessions)
+    made = [c for c in lib.log if c[0] == "sac_gactor_create"][0]
+    assert t._h.value in made[2] and old not in made[2]
+    for i, (o, e) in enumerate(data):                                      # new views (the stand-in's new slabs start as NaN)
+        assert g.obs[i] is not old_views[i]
+        assert np.array_equal(g.obs[i], o) and np.array_equal(g.eps[i], e)
+    assert np.array_equal(g.act[gen[2]], before[gen[2]])                   # (its last actions too: it sat out)
+    g.act(n_rows, False)
+    want = actions_of(t._h.value, data[gen[2]][0].astype(np.float32), False, data[gen[2]][1])
+    assert np.array_equal(g.act[gen[2]], want) and not np.array_equal(want, before[gen[2]])
+    # an address that comes back is still a new handle: the count decides
+    t._handle_gen += 1
+    del lib.log[:]
+    g.act(n_rows, False)
+    assert names(lib.log)[:2] == ["sac_actor_destroy", "sac_gactor_destroy"]
+    t._h = None
+    with pytest.raises(RuntimeError, match=f"member {gen[2]} has lost its device handle"):
+        g.act(n_rows, False)
+    g.close()
+
+
+def test_close_destroys_every_session_and_the_object_is_never_pickled(lib):
+    g = GroupActor(members(2, 19), general="device", general_sessions=True)
+    with pytest.raises(TypeError, match="never pickled"):
+        pickle.dumps(g)
+    with pytest.raises(TypeError, match="never pickled"):
+        pickle.dumps(g.act)
+    ids = set(lib.sessions)
+    del lib.log[:]
+    g.close()
+    assert sorted(names(lib.log)) == ["sac_actor_destroy", "sac_gactor_destroy", "sac_gactor_destroy"]
+    assert {c[1] for c in lib.log} == ids and not lib.sessions
+    assert g.obs == [] and g.eps == [] and len(g.act) == 0
+    with pytest.raises(RuntimeError, match="closed"):
+        g.act([1] * 21, True)
+    g.close()                                                              # (twice is harmless)
+    assert len(lib.log) == 3
+
+
+def test_python_refusals_come_before_any_session_acts(lib):
+    ts = members(1, 2)
+    g = GroupActor(ts, max_rows=2, general="device", general_sessions=True)
+    del lib.log[:]
+    for rows, text in (([3, 0, 0], "member 0: 3 rows"), ([0, 0, 0], "no trainer has rows"), ([1, 1], "one row count")):
+        with pytest.raises(RuntimeError, match=text):
+            g.act(rows, True)
+    assert lib.log == []
+    g.close()
+
+
+# ---- the collector passes the keyword on ------------------------------------------------------------------------------------
+def test_group_path_collector_hands_general_sessions_to_the_actor_factory():
+    class Bound:
+        def __init__(self, policy):
+            self.policy, self._h, self.act_dim = policy, object(), policy.action_dim
+            policy._trainer = self
+
+    seen = []
+
+    class Actor:
+        def __init__(self, trainers, max_rows=1, **kw):
+            seen.append(kw)
+            self.obs = [np.zeros((1, t.policy.obs_dim)) for t in trainers]
+            self.eps = [np.zeros((1, t.act_dim), np.float32) for t in trainers]
+            self.act = type("Rows", (list,), {"__call__": lambda s, n, d: None})(np.zeros((1, t.act_dim), np.float32) for t in trainers)
+
+        def close(self):
+            pass
+
+    for kw, want in ((dict(general="device", general_sessions=True), dict(general="device", general_sessions=True)),
+                     (dict(general="device", general_sessions=False), dict(general="device", general_sessions=False)),
+                     (dict(general="device"), dict(general="device")),
+                     (dict(general="host", general_sessions=True), {}), ({}, {})):
+        e, p = member("expl", 1, 11, 3)
+        Bound(holder_of(p))
+        GroupPathCollector([PathCollector(e, p)], sessions=True, actor=Actor, **kw).collect_new_paths([(5, 5, False)])
+        assert seen[-1] == want, kw
