@@ -448,6 +448,9 @@ static int group_build_fused(sac_group *g) {
         for (int c = 0; c < g->ncls; ++c) { st.fn[c] = ker[c][which]; st.gx[c] = gx[c]; st.lds[c] = lds[c]; }
         g->stages.push_back(st);
     };
+    // the one-group form of the weight-gradient body where every member runs it solo (batch <= 256, not SAC_DW_FORM=loop)
+    bool one = true;
+    for (int i = 0; i < R; ++i) one = one && g->m[i]->dw_one;
     auto for_all = [&](auto kernel, int gx, int need, bool idle_one) {
         GroupStage st;
         st.fn[0] = reinterpret_cast<const void *>(kernel); st.gx[0] = gx; st.need = need; st.idle_one = idle_one;
@@ -455,12 +458,12 @@ static int group_build_fused(sac_group *g) {
     };
     if (algo == 0) {                                  // launch_step: A, B, C (compact: 3 * 4 * NB <= 192 for every member), dW
         per_class(0, xa, lds_fa, 0, 0); per_class(1, xb, lds_fb, 0, 0); per_class(2, xc, lds_bw, 0, 1);
-        for_all(&k_dw_adam_group<M_SAC>, grid_d, 0, false);
+        for_all(one ? &k_dw_adam_group<M_SAC, true> : &k_dw_adam_group<M_SAC, false>, grid_d, 0, false);
     } else {                                          // launch_step_td3: the critic pass, then the actor pass
         per_class(0, xa, lds_fa, 0, 0); per_class(1, xb, lds_fb, 0, 0); per_class(2, xc, lds_bw, 0, 0);
-        for_all(&k_dw_adam_group<M_TD3_CRITIC>, grid_dq, 0, false);
+        for_all(one ? &k_dw_adam_group<M_TD3_CRITIC, true> : &k_dw_adam_group<M_TD3_CRITIC, false>, grid_dq, 0, false);
         per_class(3, xpi, lds_fb, 1, 0); per_class(4, xpi, lds_bw, 2, 0);
-        for_all(&k_dw_adam_group<M_TD3_ACTOR>, grid_dpi, 1, true);
+        for_all(one ? &k_dw_adam_group<M_TD3_ACTOR, true> : &k_dw_adam_group<M_TD3_ACTOR, false>, grid_dpi, 1, true);
     }
     for (const GroupStage &st : g->stages)
         for (int c = 0; c < 4; ++c)

@@ -208,6 +208,14 @@ __device__ __forceinline__ f32x4 ld4(const float *p) { return *reinterpret_cast<
 // DwLayer, has no address space the compiler can infer: its accesses become flat_load / flat_store).  Measured, not
 // assumed: k_dw_adam's OPERAND loads are left generic on purpose -- with global loads the same launch is 0.7 us longer
 // by rocprofv3 on the same box (7.45 against 6.7 us, scratch/ab_libs.sh), although its in-kernel stamps are not.
+// The one-group form of the weight-gradient contraction (dw_adam_body<true>) loads through generic (0) or explicitly global
+// (1) pointers.  Measured on one box (profiles/dw_one_group_*): generic, the launch is 6.34 us against
+// the loop form's 6.88; global -- four counted vmcnt waits, the first MFMA as early, the reduction 0.86 us earlier -- the
+// owner's state then lands ~1.7 us later, the launch stays 6.84 us and the step loses 0.25 us.  Generic is the default.
+#ifndef DW_ONE_GLOBAL
+#define DW_ONE_GLOBAL 0
+#endif
+__device__ __forceinline__ f32x4 ld4g(const float *p) { return *(const __attribute__((address_space(1))) f32x4 *)(uintptr_t)p; }
 __device__ __forceinline__ float ld1g(const float *p) { return *(const __attribute__((address_space(1))) float *)(uintptr_t)p; }
 // (write-through: a plain global store would sit dirty in the L2 until the end-of-kernel write-back)
 __device__ __forceinline__ void st1g(float *p, float v) {
@@ -1429,6 +1437,7 @@ __device__ __forceinline__ void td3_diagnostics(const Dev &d, const StepArg &sa,
 // owners).  (A function of its own since the one-launch experiment -- this body as a phase D of k_abc behind a grid-wide
 // counter hand-off: the hand-off took 6.5 us against ~3 us for the dispatch boundary plus start-up it replaced, DESIGN.md
 // section 7 -- and kept that way.)  red: 4096 floats, redb: 128 floats.
+template <bool ONE = false>
 __device__ __forceinline__ void dw_adam_body(const Dev &d, const DwTable &T, const float *__restrict__ S, const StepArg &sa,
                                              float *red, float *redb, float *trs, int vblock, unsigned aborted) {
     const int B = d.B;
@@ -1493,15 +1502,27 @@ __device__ __forceinline__ void dw_adam_body(const Dev &d, const DwTable &T, con
 #pragma unroll
         for (int t = 0; t < 4; ++t) toff[t] = (size_t)(t < nv ? t : nv - 1) * tile_floats;
         f32x4 a[4], b[4][4];
+        // operand loads: generic (see ld1g above) unless the one-group form is built with DW_ONE_GLOBAL
+        auto ldop = [](const float *p) {
+            if constexpr (ONE && DW_ONE_GLOBAL) return ld4g(p);
+            else return ld4(p);
+        };
 #pragma unroll
         for (int u = 0; u < 4; ++u) {
             const int cq = chunk_of(s0 + u);
-            a[u] = ld4(yp + 256 * cq);
+            a[u] = ldop(yp + 256 * cq);
 #pragma unroll
-            for (int t = 0; t < 4; ++t) b[u][t] = ld4(xp + toff[t] + 256 * cq);
+            for (int t = 0; t < 4; ++t) b[u][t] = ldop(xp + toff[t] + 256 * cq);
+            if constexpr (ONE) SB();
         }
         f32x4 p4 = {0.f, 0.f, 0.f, 0.f}, m4 = p4, v4 = p4;
-        if (own_valid) {
+        if constexpr (ONE) {
+            // unconditional (a lane outside the layer re-reads the array's first 16 B, select on the value): a branch
+            // around these loads would leave the counted waits below to the shorter of its two paths
+            const size_t os = own_valid ? ot : 0;
+            const f32x4 pl = ldop(J.PT + os), ml = ldop(J.MT + os), vl = ldop(J.VT + os);
+            p4 = own_valid ? pl : p4; m4 = own_valid ? ml : m4; v4 = own_valid ? vl : v4;
+        } else if (own_valid) {
             p4 = ld4(J.PT + ot);
             m4 = ld4(J.MT + ot);
             v4 = ld4(J.VT + ot);
@@ -1515,7 +1536,7 @@ __device__ __forceinline__ void dw_adam_body(const Dev &d, const DwTable &T, con
         const bool tile_ok = (k0 + 16 * wave) < J.ldp;                     // (wave-uniform: the last k tile of a 48-wide layer)
         const size_t pblk = frag_off(n0, k0 + 16 * wave, J.ldp) + 4 * lane;
         f32x4 tp4 = {0.f, 0.f, 0.f, 0.f};
-        if (polyak && tile_ok) tp4 = ld4(J.TP + pblk);
+        if (polyak && tile_ok) tp4 = ldop(J.TP + pblk);
         float pb = 0.f, mbv = 0.f, vbv = 0.f, tbv = 0.f;
         const bool bias_lane = (k0 == 0) && threadIdx.x < 16 && (n0 + (int)threadIdx.x) < J.N;
         if (bias_lane) {
@@ -1523,6 +1544,33 @@ __device__ __forceinline__ void dw_adam_body(const Dev &d, const DwTable &T, con
             pb = ld1g(J.bias + n); mbv = ld1g(J.mb + n); vbv = ld1g(J.vb + n);
             if (polyak) tbv = ld1g(J.Tbias + n);
         }
+        if constexpr (ONE) {
+            // One group (batch <= 256: s1 - s0 <= 4), straight line: the 16 MFMAs of chunk u wait for ITS five loads only
+            // (the chunk's fragments are made opaque together, so the compiler places one wait per chunk), never for the
+            // owner's state behind them.  What hipcc makes of it -- with generic loads: vmcnt(0) behind the first 15 operand
+            // loads, THEN chunk 3, the state, the target and the biases are requested, 48 MFMAs run under those requests,
+            // vmcnt(0), the last 16; with global loads: vmcnt(18), (13), (8), (3), everything in flight from the start.
+            // The loop form waits for every load it issued, the state included, before its first MFMA.
+            // Accumulation order as in the loop: u, i, t.
+#pragma unroll
+            for (int u = 0; u < 4; ++u) {
+                SB();
+                asm volatile("" : "+v"(a[u]), "+v"(b[u][0]), "+v"(b[u][1]), "+v"(b[u][2]), "+v"(b[u][3]));
+#ifdef SAC_STAMPS
+                if (u == 0) STAMP(4, 4);             // first MFMA
+                if (u == 3) STAMP(4, 5);             // last operands arrived
+#endif
+                const f32x4 au = (s0 + u < s1) ? a[u] : zero4;
+                bsum += (au[0] + au[1]) + (au[2] + au[3]);
+#pragma unroll
+                for (int i = 0; i < 4; ++i) {
+#pragma unroll
+                    for (int t = 0; t < 4; ++t)
+                        acc[t] = __builtin_amdgcn_mfma_f32_16x16x4f32(au[i], b[u][t][i], acc[t], 0, 0, 0);
+                }
+            }
+            SB();
+        } else {
 #ifdef SAC_STAMPS
         { float probe = a[0][0] + b[3][3][3]; asm volatile("" :: "v"(probe)); }
         STAMP(4, 4);
@@ -1548,6 +1596,7 @@ __device__ __forceinline__ void dw_adam_body(const Dev &d, const DwTable &T, con
                     for (int t = 0; t < 4; ++t) b[u][t] = ld4(xp + toff[t] + 256 * cq);
                 }
             }
+        }
         }
 #pragma unroll
         for (int t = 0; t < 4; ++t) st4(red + ((wave * 4 + t) * 64 + lane) * 4, acc[t]);
@@ -1723,7 +1772,8 @@ __device__ __forceinline__ void dw_adam_body(const Dev &d, const DwTable &T, con
     }
 }
 
-__global__ __launch_bounds__(256) void k_dw_adam(Dev d, DwTable T, const float *__restrict__ S, StepArg sa) {
+template <bool ONE>
+__device__ __forceinline__ void dw_adam_entry(const Dev &d, const DwTable &T, const float *__restrict__ S, const StepArg &sa) {
     kernarg_prefetch<sizeof(Dev) + sizeof(DwTable) + 8 + sizeof(StepArg)>();
     __shared__ __attribute__((aligned(16))) float red[4 * 4 * 64 * 4];   // 16 KB (also diag scratch)
     __shared__ __attribute__((aligned(16))) float redb[4 * 16 * 2];
@@ -1731,7 +1781,14 @@ __global__ __launch_bounds__(256) void k_dw_adam(Dev d, DwTable T, const float *
     // fused step: the forward/backward launch gave up (a hand-off wait timed out) => this launch, the step's only
     // writer of weights, Adam state, targets and the entropy coefficient, applies NOTHING
     const unsigned aborted = T.abort ? sload(T.abort) : 0u;
-    dw_adam_body(d, T, S, sa, red, redb, trs, (int)blockIdx.x, aborted);
+    dw_adam_body<ONE>(d, T, S, sa, red, redb, trs, (int)blockIdx.x, aborted);
+}
+// k_dw_adam: the loop form (any batch).  k_dw_adam_one: the one-group form, batches up to 256 rows (sac_trainer::dw_one).
+__global__ __launch_bounds__(256) void k_dw_adam(Dev d, DwTable T, const float *__restrict__ S, StepArg sa) {
+    dw_adam_entry<false>(d, T, S, sa);
+}
+__global__ __launch_bounds__(256) void k_dw_adam_one(Dev d, DwTable T, const float *__restrict__ S, StepArg sa) {
+    dw_adam_entry<true>(d, T, S, sa);
 }
 
 // ------------------------------------------------------------------------------------------
@@ -1805,7 +1862,7 @@ __global__ __launch_bounds__(256) void k_bwd_group(const GroupMember *__restrict
 }
 // each member's table of this step: SAC its one table; TD3 critic pass dw_q / dw_q_tp (policy steps: with the critics'
 // Polyak targets), actor pass dw_pi (policy steps) / dw_none (statistics only) / nothing
-template <int MODE = M_SAC>
+template <int MODE = M_SAC, bool ONE = false>
 __global__ __launch_bounds__(256) void k_dw_adam_group(const GroupMember *__restrict__ G, const GroupStep<MODE> *__restrict__ SA,
                                                        int slot) {
     __shared__ __attribute__((aligned(16))) float red[4 * 4 * 64 * 4];
@@ -1824,7 +1881,7 @@ __global__ __launch_bounds__(256) void k_dw_adam_group(const GroupMember *__rest
         sa = &SA[blockIdx.y].sp;
     }
     if ((int)blockIdx.x > T->njobs) return;
-    dw_adam_body(g.d, *T, g.slots + (size_t)slot * g.SL.slot_floats, *sa, red, redb, trs, (int)blockIdx.x, 0u);
+    dw_adam_body<ONE>(g.d, *T, g.slots + (size_t)slot * g.SL.slot_floats, *sa, red, redb, trs, (int)blockIdx.x, 0u);
 }
 
 #include "sac_bwd8.h"
@@ -1883,6 +1940,7 @@ struct sac_trainer {
     float *act_gen[2] = {nullptr, nullptr}; size_t act_gen_floats = 0;
     size_t lds_bw = 0;
     // fused step (k_abc, sac_fused.h): launches A + B + C as one launch with in-launch hand-offs
+    bool dw_one = false;                              // weight-gradient launch in its one-group form (batch <= 256; SAC_DW_FORM=loop: never)
     bool fused = false;
     unsigned fused_seq = 0;                           // launches so far: the hand-off counters count in units of it
     unsigned fused_unchecked = 0;                     // fused launches since the host last looked at the abort marker
@@ -2069,15 +2127,15 @@ int launch_step_td3(sac_trainer *t, const float *S, const SlotLayout &SL, int j,
         hipLaunchKernelGGL(t->bwd, dim3(g2), dim3(256), t->lds_bw, s, d, S, SL, sq, 0);
     }
     const DwTable &Tq = pstep ? t->dw_q_tp : t->dw_q;
-    hipLaunchKernelGGL(k_dw_adam, dim3(Tq.njobs + 1), dim3(256), 0, s, d, Tq, S, sq);
+    hipLaunchKernelGGL(t->dw_one ? k_dw_adam_one : k_dw_adam, dim3(Tq.njobs + 1), dim3(256), 0, s, d, Tq, S, sq);
     if (actor) {
         hipLaunchKernelGGL(t->fwd_b2, dim3(SPv * NB), dim3(256), t->lds_fb, s, d, S, SL, sp);
         if (pstep) {
             hipLaunchKernelGGL(t->bwd2, dim3(SPv * NB), dim3(256), t->lds_bw, s, d, S, SL, sp, 0);
-            hipLaunchKernelGGL(k_dw_adam, dim3(t->dw_pi.njobs + 1), dim3(256), 0, s, d, t->dw_pi, S, sp);
+            hipLaunchKernelGGL(t->dw_one ? k_dw_adam_one : k_dw_adam, dim3(t->dw_pi.njobs + 1), dim3(256), 0, s, d, t->dw_pi, S, sp);
             t->adam_t_pi += 1;
         } else {
-            hipLaunchKernelGGL(k_dw_adam, dim3(1), dim3(256), 0, s, d, t->dw_none, S, sp);      // statistics only
+            hipLaunchKernelGGL(t->dw_one ? k_dw_adam_one : k_dw_adam, dim3(1), dim3(256), 0, s, d, t->dw_none, S, sp);      // statistics only
         }
     }
     SAC_HIP(hipGetLastError());
@@ -2117,7 +2175,7 @@ int launch_step(sac_trainer *t, const float *S, const SlotLayout &SL, int j, hip
         if (ev) SAC_HIP(hipEventRecord(ev[3], s));
     }
     if (ev) SAC_HIP(hipEventRecord(ev[4], s));
-    hipLaunchKernelGGL(k_dw_adam, dim3(t->dw.njobs + 1), dim3(256), 0, s, d, t->dw, S, sa);
+    hipLaunchKernelGGL(t->dw_one ? k_dw_adam_one : k_dw_adam, dim3(t->dw.njobs + 1), dim3(256), 0, s, d, t->dw, S, sa);
     if (ev) { SAC_HIP(hipEventRecord(ev[5], s)); SAC_HIP(hipEventRecord(ev[6], s)); }
     SAC_HIP(hipGetLastError());
     t->n_train_steps_total += 1;
@@ -2518,6 +2576,11 @@ static int trainer_build(sac_trainer *t, const sac_config_t *cfg, const td3_conf
     // The fused step (sac_fused.h) needs: SAC, column split 4 (at most 16 row-blocks), and every one of its 16*NB
     // workgroups resident at once (one per CU: 100-160 KB of LDS each, which also bounds obs_dim to ~1000).  SAC_FUSED=0 selects the
     // four-launch step (co-tenant processes on one GPU; ablations).
+    {   // the weight-gradient launch: one group of four batch chunks per wave covers 256 rows => its straight-line form
+        // (dw_adam_body<true>); SAC_DW_FORM=loop keeps the loop form at every batch size (ablations, tests)
+        const char *e = getenv("SAC_DW_FORM");
+        t->dw_one = d.B / 16 <= 16 && !(e && strcmp(e, "loop") == 0);
+    }
     {
         int cus = 0;
         SAC_HIP(hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, t->device));

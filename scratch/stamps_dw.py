@@ -17,9 +17,14 @@ w = st[4]
 bl = [b for b in range(512) if w[b, 0] > 0]
 t0 = min(w[b, 0] for b in bl)
 ww = w[bl]
-for i, nm in ((0, "start"), (3, "table read"), (4, "operands arrived"), (1, "reduced (barrier)"), (2, "end")):
+# slot 4: the loop form stamps it once ALL operands of the group have arrived (its first MFMA waits for them); the one-group
+# form stamps it at its first MFMA (chunk 0 arrived) and slot 5 once the last chunk has arrived (block-leader wave)
+one = bool((ww[:, 5] > 0).any())
+rows = ((0, "start"), (3, "table read"), (4, "first MFMA" if one else "operands arrived = first MFMA"))
+rows += ((5, "last operands arrived"),) if one else ()
+for i, nm in rows + ((1, "reduced (barrier)"), (2, "end")):
     v = (ww[:, i] - t0) / 100.0
-    print(f"{nm:>18s}: median {np.median(v):6.2f}  p90 {np.percentile(v, 90):6.2f}  max {v.max():6.2f}")
+    print(f"{nm:>30s}: median {np.median(v):6.2f}  p90 {np.percentile(v, 90):6.2f}  max {v.max():6.2f}")
 d3 = st[3]
 b3 = [b for b in range(512) if d3[b, 0] > 0]
 if b3:
