@@ -360,6 +360,26 @@ int sac_policy_act_general_many(sac_trainer_t *const *trainers, int n_trainers, 
                                 const float *const *obs, const int32_t *deterministic, const float *const *eps,
                                 float *const *act);
 
+/* Q_net(obs, act) on the DEVICE from the live weights: n rows of any non-empty subset of the four Q networks in one
+ * launch (k_qval, csrc/sac_qval.h).  `nets` is a mask of SAC_Q_* bits (bit 1 << (SAC_NET_* - 1)); q receives one row of n
+ * values per selected net, the selected nets in ascending SAC_NET_* order.  The kernel reads the nets where the step
+ * kernels keep them -- no mirror, no parameter copy -- and sees the weights as of the last completed step of any step
+ * path or sac_set_params: the call first drains the trainer as sac_sync does, a fused step that gave up included.  n is
+ * 1..1024.  A row's value depends on that row's observation and action and the net's weights only -- not on its place,
+ * on n, on the other nets selected or on the rest of the launch -- so row r of any call is bit for bit the one-row call.
+ * Nothing the step reads is written.  SAC and TD3 handles with the fused kernels' shapes (two hidden layers of at most
+ * 256 units); general-step trainers are refused: their Q values come from sac_get_params and a forward on the host. */
+enum { SAC_Q_QF1 = 1, SAC_Q_QF2 = 2, SAC_Q_TARGET_QF1 = 4, SAC_Q_TARGET_QF2 = 8 };
+int sac_q_values(sac_trainer_t *t, int64_t n, const float *obs /* (n,O) host */, const float *act /* (n,A) host */,
+                 uint32_t nets, float *q /* (popcount(nets), n) host */);
+/* the same for 1..SAC_GROUP_MAX (16) trainers of one device in ONE launch; n_rows[i] == 0: member i sits out (its
+ * arrays and its mask are not looked at).  SAC and TD3 members, dims, row counts and masks may be mixed.  Each member's
+ * values are bit for bit its own sac_q_values'.  Refused (<0, sac_last_error, nothing changed): null or duplicate
+ * trainers, trainers on different devices, general-step trainers, members confined by sac_trainer_set_xcd[_mask],
+ * n_rows outside 0..1024 or all zero, and for a member with rows a mask that is 0 or has bits above 8, or a null array. */
+int sac_q_values_many(sac_trainer_t *const *trainers, int n_trainers, const int32_t *n_rows,
+                      const float *const *obs, const float *const *act, const uint32_t *nets, float *const *q);
+
 /* ------------------------------------------------------------------------------------------
  * Trainer groups: several runs of one configuration (the reference's seed sweeps, /root/reference/launch_jobs.sh)
  * stepped together.  A group holds 1..SAC_GROUP_MAX existing SAC trainers that share obs_dim, act_dim, batch (at most

@@ -26,6 +26,24 @@ DIAG_NAMES = [
 ]
 NET_IDS = {"policy": 0, "qf1": 1, "qf2": 2, "target_qf1": 3, "target_qf2": 4}
 TD3_NET_IDS = dict(NET_IDS, target_policy=5)
+# the Q networks sac_q_values evaluates: name -> SAC_Q_* bit (1 << (SAC_NET_* - 1))
+Q_NET_BITS = {"qf1": 1, "qf2": 2, "target_qf1": 4, "target_qf2": 8}
+
+
+def q_net_mask(nets):
+    """(mask, rows) of a selection of Q networks given by name, e.g. ("qf2", "qf1"): the SAC_Q_* mask sac_q_values takes,
+    and for each name as given its row in the library's output (the selected nets in ascending SAC_NET_* order)."""
+    names = [nets] if isinstance(nets, str) else list(nets)
+    if not names:
+        raise ValueError("q_values needs at least one Q network")
+    for name in names:
+        if name not in Q_NET_BITS:
+            raise ValueError(f"unknown Q network {name!r}: one of {tuple(Q_NET_BITS)}")
+    if len(set(names)) != len(names):
+        raise ValueError(f"a Q network is named twice in {tuple(names)}")
+    mask = sum(Q_NET_BITS[name] for name in names)
+    order = sorted(names, key=Q_NET_BITS.get)
+    return mask, [order.index(name) for name in names]
 
 
 class SacConfig(C.Structure):
@@ -115,6 +133,8 @@ SYMBOLS = {
     "sac_policy_act_many": (C.c_int, [_P, C.c_int, _P, _P, _P, _P, _P]),
     "sac_policy_act_general": (C.c_int, [_P, C.c_int64, _P, C.c_int, _P, _P]),
     "sac_policy_act_general_many": (C.c_int, [_P, C.c_int, _P, _P, _P, _P, _P]),
+    "sac_q_values": (C.c_int, [_P, C.c_int64, _P, _P, C.c_uint32, _P]),
+    "sac_q_values_many": (C.c_int, [_P, C.c_int, _P, _P, _P, _P, _P]),
     "sac_group_create": (C.c_int, [C.POINTER(_P), _P, C.c_int]),
     "td3_group_create": (C.c_int, [C.POINTER(_P), _P, C.c_int]),
     "sac_group_create_mixed": (C.c_int, [C.POINTER(_P), _P, C.c_int]),

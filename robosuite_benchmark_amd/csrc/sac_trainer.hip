@@ -1936,6 +1936,7 @@ struct sac_trainer {
     // device acting (sac_act.h): observations, eps, actions and the member table of a call, in mapped pinned host memory
     struct ActStage { char *h = nullptr, *d = nullptr; size_t bytes = 0; } act_stage;
     bool act_lds_raised = false;                      // k_act may use more than 48 KB of LDS (wide observations)
+    bool qval_lds_raised = false;                     // k_qval likewise (sac_qval.h)
     // general-step device acting (sac_act_general.h): the activations between two layer launches ping-pong between these
     float *act_gen[2] = {nullptr, nullptr}; size_t act_gen_floats = 0;
     size_t lds_bw = 0;
@@ -2305,6 +2306,7 @@ int stage_batches(sac_trainer *t, sac_buffer *b, int64_t n_steps) {
 }  // namespace
 
 #include "sac_act.h"
+#include "sac_qval.h"
 #include "sac_act_general.h"
 #include "sac_actor.h"
 #include "sac_actor_general.h"

@@ -24,7 +24,7 @@ from .networks import (FlattenMlp, GaussianStrategy, MakeDeterministic, PolicyWr
 from .replay_buffer import EnvReplayBuffer
 from .group import (ArchSACTrainerGroup, ArchTD3TrainerGroup, GroupActor, MixedSACTrainerGroup, MixedTD3TrainerGroup,
                     MlpSACTrainerGroup, MlpTD3TrainerGroup, SACTrainerGroup, TD3TrainerGroup, act_many,
-                    runs_general_step)
+                    q_values_many, runs_general_step)
 from .sac import SACTrainer
 from .td3 import TD3Trainer
 from .variant import env_dims, validate
@@ -297,6 +297,41 @@ def path_information(paths, prefix, expl_len=None):
     return d
 
 
+def q_bias_information(paths, q1, q2, discount, reward_scale):
+    """The critics against the returns actually obtained on `paths` (the overestimation bias of the TD3 and SAC papers),
+    in float64.  q1 / q2: Q1 / Q2(s_t, a_t) for every step of every path, the paths one behind the other.  For each step
+    G_t = sum_{k >= t} discount^(k - t) * reward_scale * r_k over the path AS COLLECTED: a path cut by the time limit (or
+    by the epoch's step budget) lacks its tail, so its G_t is short of the return the critics estimate by up to
+    discount^(T - t) * V(s_T), most of all near the path's end.  Columns, each Mean / Std / Max / Min (_stats):
+    evaluation/Q1 Estimates, evaluation/Q2 Estimates, evaluation/Returns To Go, evaluation/Q Bias = min(q1, q2) - G."""
+    q1, q2 = np.asarray(q1, np.float64).ravel(), np.asarray(q2, np.float64).ravel()
+    G = []
+    for p in paths:
+        r = float(reward_scale) * np.asarray(p["rewards"], np.float64).ravel()
+        g, acc = np.empty(r.size, np.float64), 0.0
+        for t in range(r.size - 1, -1, -1):
+            acc = r[t] + float(discount) * acc
+            g[t] = acc
+        G.append(g)
+    G = np.concatenate(G) if G else np.empty(0, np.float64)
+    if not (q1.size == q2.size == G.size):
+        raise ValueError(f"q_bias_information: {q1.size} / {q2.size} Q values for {G.size} steps")
+    d = OrderedDict()
+    d.update(_stats("evaluation/Q1 Estimates", q1))
+    d.update(_stats("evaluation/Q2 Estimates", q2))
+    d.update(_stats("evaluation/Returns To Go", G))
+    d.update(_stats("evaluation/Q Bias", np.minimum(q1, q2) - G))
+    return d
+
+
+def _path_steps(paths, O, A):
+    """Every (observation, action) of `paths`, the paths one behind the other: (n, O), (n, A) float32."""
+    if not paths:
+        return np.empty((0, O), np.float32), np.empty((0, A), np.float32)
+    return (np.concatenate([np.asarray(p["observations"], np.float32).reshape(-1, O) for p in paths]),
+            np.concatenate([np.asarray(p["actions"], np.float32).reshape(-1, A) for p in paths]))
+
+
 def _rs_pack(rs):
     st = rs.get_state()
     return dict(key=[int(x) for x in st[1]], pos=int(st[2]), has_gauss=int(st[3]), cached=float(st[4]))
@@ -319,7 +354,7 @@ def _progress_row(buf, trainer, expl, evalc, ak):
 
 
 def experiment(variant, log_dir=None, seed=1, obs_dim=None, action_dim=None, num_epochs=None, device=0,
-               fused_loop=True, quiet=False, checkpoint_dir=None, resume=False, acting="host"):
+               fused_loop=True, quiet=False, checkpoint_dir=None, resume=False, acting="host", q_diagnostics=False):
     """variant.json -> training run.  Returns the list of progress rows (also written to
     <log_dir>/progress.csv when log_dir is given).
 
@@ -333,7 +368,13 @@ def experiment(variant, log_dir=None, seed=1, obs_dim=None, action_dim=None, num
     acts on the host either way ("device" serves the fused kernels' shapes, and its results are pinned).
     "device_all" is "device", and a run of the general step acts on the device too (sac_policy_act_general: one
     k_act_layer launch per layer on the live weights).  The exploration noise comes from the same host stream, in the
-    same amounts, whichever value is given."""
+    same amounts, whichever value is given.
+
+    q_diagnostics=True: every epoch, right behind the evaluation paths and in front of the training block (policy and
+    critics of one moment), qf1 and qf2 are evaluated on every (observation, action) of the epoch's evaluation paths
+    (trainer.q_values: on the device from the live weights) and the row gets q_bias_information's sixteen columns
+    behind its evaluation/ block; the time counts under `time/evaluation sampling (s)`.  Off (the default), the row is
+    exactly what it was."""
     check_acting(acting)
     validate(variant)
     np.random.seed(seed)                                          # scripts/train.py:112 (args.seed, not variant seed)
@@ -385,6 +426,10 @@ def experiment(variant, log_dir=None, seed=1, obs_dim=None, action_dim=None, num
     for epoch in range(first_epoch, num_epochs if num_epochs is not None else ak["num_epochs"]):
         t0 = time.time()
         evalc.collect_new_paths(ak["eval_max_path_length"], ak["num_eval_steps_per_epoch"], True)
+        q_info = None
+        if q_diagnostics:
+            q1, q2 = trainer.q_values(*_path_steps(evalc.epoch_paths, O, A), nets=("qf1", "qf2"))
+            q_info = q_bias_information(evalc.epoch_paths, q1, q2, trainer.discount, trainer.reward_scale)
         t1 = time.time()
         new_paths = expl.collect_new_paths(ak["expl_max_path_length"], ak["num_expl_steps_per_train_loop"], False)
         t2 = time.time()
@@ -399,6 +444,8 @@ def experiment(variant, log_dir=None, seed=1, obs_dim=None, action_dim=None, num
                 trainer.train(buf.random_batch(ak["batch_size"]))
         t4 = time.time()
         row = _progress_row(buf, trainer, expl, evalc, ak)
+        if q_info is not None:
+            row.update(q_info)
         trainer.end_epoch(epoch); buf.end_epoch(epoch); expl.end_epoch(epoch); evalc.end_epoch(epoch)
         t5 = time.time()
         if checkpoint_dir:
@@ -513,8 +560,18 @@ def _group_save(ck, runs, epoch):
     ck.save([r["trainer"] for r in runs], [r["buf"] for r in runs], [r["identity"] for r in runs], extras)
 
 
+def _group_q_information(runs):
+    """q_bias_information of every run's evaluation paths of this epoch, qf1 and qf2 of all runs from ONE q_values_many
+    call (one launch per 16 runs with the fused kernels' shapes and 1024 rows)."""
+    steps = [_path_steps(r["evalc"].epoch_paths, r["trainer"].obs_dim, r["trainer"].act_dim) for r in runs]
+    qs = q_values_many([r["trainer"] for r in runs], [s[0] for s in steps], [s[1] for s in steps],
+                       [("qf1", "qf2")] * len(runs))
+    return [q_bias_information(r["evalc"].epoch_paths, q[0], q[1], r["trainer"].discount, r["trainer"].reward_scale)
+            for r, q in zip(runs, qs)]
+
+
 def _group_epochs(runs, train_block, n_epochs, n_train, log_dir, quiet, what, ck=None, first_epoch=0, acting="host",
-                  sessions=True, general_sessions=None):
+                  sessions=True, general_sessions=None, q_diagnostics=False):
     """The epoch loop of a grouped experiment: each run collects its paths, then train_block() trains every run at once,
     then every run ends its epoch, the group is saved (with a GroupCheckpoint `ck`), and each run writes its row (to
     <log_dir>/<run["sub"]>/progress.csv with log_dir; appended to after a resume).
@@ -523,7 +580,10 @@ def _group_epochs(runs, train_block, n_epochs, n_train, log_dir, quiet, what, ck
     call, GroupActor, one session for each phase's collectors; the rows are the same); each run's time/*sampling (s) columns
     then hold the shared phase time.  acting="device_all": the same, and the lockstep collectors send the runs of the
     general step to the device as well (general="device"; with sessions=True, general_sessions says whether they get
-    acting sessions of their own, None: GroupActor's default -- the rows are the same either way)."""
+    acting sessions of their own, None: GroupActor's default -- the rows are the same either way).
+    q_diagnostics=True: as experiment()'s, qf1 and qf2 of ALL runs on their evaluation paths from one q_values_many call
+    per epoch, behind the runs' evaluation paths and in front of the training block; its time is added to every run's
+    time/evaluation sampling (s)."""
     t_start = time.time()
     lockstep = acting != "host"
     lock_kw = dict(sessions=sessions, general="device" if acting == "device_all" else "host", general_sessions=general_sessions)
@@ -536,6 +596,7 @@ def _group_epochs(runs, train_block, n_epochs, n_train, log_dir, quiet, what, ck
                 t0 = time.time()
                 lock_eval.collect_new_paths([(r["ak"]["eval_max_path_length"], r["ak"]["num_eval_steps_per_epoch"], True)
                                              for r in runs])
+                q_infos = _group_q_information(runs) if q_diagnostics else None
                 t1 = time.time()
                 new = lock_expl.collect_new_paths([(r["ak"]["expl_max_path_length"],
                                                     r["ak"]["num_expl_steps_per_train_loop"], False) for r in runs])
@@ -553,12 +614,19 @@ def _group_epochs(runs, train_block, n_epochs, n_train, log_dir, quiet, what, ck
                 t2 = time.time()
                 r["buf"].add_paths(new_paths)
                 times.append((t0, t1 - t0, t2 - t1, time.time() - t2))
+            if q_diagnostics and not lockstep:                # (nobody has trained since the first run's evaluation paths)
+                s0 = time.time()
+                q_infos = _group_q_information(runs)
+                q_s = time.time() - s0
+                times = [(a0, eval_s + q_s, expl_s, store_s) for a0, eval_s, expl_s, store_s in times]
             t3 = time.time()
             train_block()
             t4 = time.time()
             ended = []
             for r in runs:
                 row = _progress_row(r["buf"], r["trainer"], r["expl"], r["evalc"], r["ak"])
+                if q_diagnostics:
+                    row.update(q_infos[len(ended)])
                 for x in (r["trainer"], r["buf"], r["expl"], r["evalc"]):
                     x.end_epoch(epoch)
                 ended.append((row, time.time()))
@@ -604,7 +672,7 @@ def _group_epochs(runs, train_block, n_epochs, n_train, log_dir, quiet, what, ck
 
 def experiment_group(variant, seeds, log_dir=None, num_epochs=None, obs_dim=None, action_dim=None, device=0,
                      quiet=False, checkpoint_dir=None, resume=False, chunk_rows=DEFAULT_CHUNK_ROWS, acting="host", sessions=True,
-                     general_sessions=None):
+                     general_sessions=None, q_diagnostics=False):
     """One configuration, several seeds, one process: each seed is the run ``experiment(variant, seed=s)`` would make --
     its own synthetic environments, collectors, weights and replay buffer -- and every epoch's training block is ONE
     SACTrainerGroup.train_loop (TD3 variants: TD3TrainerGroup; hidden sizes other than two layers of at most 256 units:
@@ -624,7 +692,9 @@ def experiment_group(variant, seeds, log_dir=None, num_epochs=None, obs_dim=None
     slower path kept for measuring against -- same rows); each run's rows are those of
     experiment(variant, seed=s, acting="device").  "device_all": the same, with the runs of the general step acting on the
     device too (one sac_policy_act_general_many call per tick and 16 of them; with sessions and general_sessions=True one
-    sac_gactor_act call, None: GroupActor's default); rows as experiment(..., acting="device_all")."""
+    sac_gactor_act call, None: GroupActor's default); rows as experiment(..., acting="device_all").
+    q_diagnostics=True: experiment()'s critic columns for every seed, all seeds' Q values from one q_values_many call per
+    epoch; each seed's rows are those of experiment(variant, seed=s, q_diagnostics=True)."""
     check_acting(acting)
     if resume and not checkpoint_dir:
         raise RuntimeError("experiment_group(resume=True) needs the checkpoint_dir to resume from")
@@ -651,7 +721,7 @@ def experiment_group(variant, seeds, log_dir=None, num_epochs=None, obs_dim=None
         train_block = lambda: group.train_loop([r["buf"] for r in runs], n_train, batch_size=ak["batch_size"])  # noqa: E731
     _group_epochs(runs, train_block,
                   num_epochs if num_epochs is not None else ak["num_epochs"], n_train, log_dir, quiet, "seeds", ck,
-                  first_epoch, acting, sessions, general_sessions)
+                  first_epoch, acting, sessions, general_sessions, q_diagnostics)
     return {r["seed"]: r["rows"] for r in runs}
 
 
@@ -677,7 +747,8 @@ def sweep_label(variant, seed, hidden_sweep=False):
 
 
 def experiment_sweep(runs, log_dir=None, num_epochs=None, device=0, quiet=False, checkpoint_dir=None, resume=False,
-                     chunk_rows=DEFAULT_CHUNK_ROWS, hidden_sweep=False, acting="host", sessions=True, general_sessions=None):
+                     chunk_rows=DEFAULT_CHUNK_ROWS, hidden_sweep=False, acting="host", sessions=True, general_sessions=None,
+                     q_diagnostics=False):
     """Several tasks x seeds, one process, one device: every entry of ``runs`` -- (variant, seed), or (variant, seed,
     obs_dim, action_dim) for a task without pinned dims -- is the run ``experiment(variant, seed=seed)`` would make, and
     every epoch's training block is ONE MixedSACTrainerGroup.train_loop (TD3 variants: MixedTD3TrainerGroup; hidden sizes
@@ -694,7 +765,8 @@ def experiment_sweep(runs, log_dir=None, num_epochs=None, device=0, quiet=False,
     acting as for experiment_group; in a hidden sweep the runs of the general step act on the host inside the same
     lockstep ticks (act_many), so each run's rows stay those of its solo experiment(..., acting="device").  Under
     "device_all" those runs act on the device inside the same ticks, and each run's rows are those of its solo
-    experiment(..., acting="device_all")."""
+    experiment(..., acting="device_all").
+    q_diagnostics as for experiment_group (the runs of the general step take q_values' host path inside the same call)."""
     check_acting(acting)
     if resume and not checkpoint_dir:
         raise RuntimeError("experiment_sweep(resume=True) needs the checkpoint_dir to resume from")
@@ -745,5 +817,5 @@ def experiment_sweep(runs, log_dir=None, num_epochs=None, device=0, quiet=False,
     batches = [r["ak"]["batch_size"] for r in group_runs]
     _group_epochs(group_runs, lambda: group.train_loop([r["buf"] for r in group_runs], n_train, batch_sizes=batches),
                   num_epochs if num_epochs is not None else ak0["num_epochs"], n_train, log_dir, quiet, "runs", ck,
-                  first_epoch, acting, sessions, general_sessions)
+                  first_epoch, acting, sessions, general_sessions, q_diagnostics)
     return [r["rows"] for r in group_runs]

@@ -105,6 +105,52 @@ def act_many(trainers, obs_list, deterministic_list, eps_list, general="host"):
     return out
 
 
+def q_values_many(trainers, obs_list, act_list, nets_list):
+    """SACTrainer.q_values for many runs at once: q[i] = trainers[i]'s critics nets_list[i] (names, as q_values takes
+    them) on obs_list[i] / act_list[i] ((n_i, O_i) / (n_i, A_i); None or no rows: the member sits out and gets an empty
+    (len(nets), 0) array).  The members with the fused kernels' shapes are served by ONE launch per 16 of them and 1024
+    rows (sac_q_values_many: SAC and TD3, dims, row counts and nets mixed); members of the general step take q_values'
+    host path inside the same call.  A member's values never depend on its neighbours: they are bit for bit those of its
+    own q_values."""
+    trainers = list(trainers)
+    R = len(trainers)
+    if not (len(obs_list) == len(act_list) == len(nets_list) == R):
+        raise RuntimeError("q_values_many takes one observation array, action array and net selection per trainer")
+    if len({id(t) for t in trainers}) != R:
+        raise RuntimeError("a trainer appears twice in q_values_many")
+    obs, act, rows, names, masks, out = [None] * R, [None] * R, [None] * R, [None] * R, [0] * R, [None] * R
+    dev = []
+    for i, t in enumerate(trainers):
+        names[i] = [nets_list[i]] if isinstance(nets_list[i], str) else list(nets_list[i])
+        masks[i], rows[i] = _lib.q_net_mask(names[i])
+        if obs_list[i] is None or np.atleast_2d(obs_list[i]).shape[0] == 0:
+            out[i] = np.empty((len(names[i]), 0), np.float32)
+            continue
+        obs[i], act[i], _, _ = t._q_inputs(obs_list[i], act_list[i], names[i])
+        if t._h is None or runs_general_step(t):
+            out[i] = t._q_values_host(obs[i], act[i], names[i])
+        else:
+            out[i] = np.empty((len(names[i]), obs[i].shape[0]), np.float32)
+            dev.append(i)
+    lib = _lib.load() if dev else None
+    for r0 in range(0, max([obs[i].shape[0] for i in dev], default=0), _lib.ACT_MAX_ROWS):
+        live = [i for i in dev if obs[i].shape[0] > r0]
+        for c in range(0, len(live), MAX_MEMBERS):
+            ids = live[c:c + MAX_MEMBERS]
+            n = len(ids)
+            n_rows = [min(obs[i].shape[0] - r0, _lib.ACT_MAX_ROWS) for i in ids]
+            o = [obs[i][r0:r0 + k] for i, k in zip(ids, n_rows)]
+            a = [act[i][r0:r0 + k] for i, k in zip(ids, n_rows)]
+            q = [np.empty((len(names[i]), k), np.float32) for i, k in zip(ids, n_rows)]
+            vp = lambda arrs: (C.c_void_p * n)(*[x.ctypes.data for x in arrs])  # noqa: E731
+            _lib.check(lib.sac_q_values_many((C.c_void_p * n)(*[trainers[i]._h.value for i in ids]), n,
+                                             (C.c_int32 * n)(*n_rows), vp(o), vp(a),
+                                             (C.c_uint32 * n)(*[masks[i] for i in ids]), vp(q)), "sac_q_values_many")
+            for i, k, part in zip(ids, n_rows, q):
+                out[i][:, r0:r0 + k] = part[rows[i]]
+    return out
+
+
 class _ActorSession:
     """One acting session (at most 16 members): its handle, the members' handles it was opened on, and the per-call
     argument arrays, made once.  entry: "sac_actor" (the fused kernels' shapes) or "sac_gactor" (the general step) --
@@ -320,6 +366,12 @@ class _Members:
     def _check_device(i, t, t0):
         if t.device != t0.device:
             raise RuntimeError(f"trainer group member {i} lives on device {t.device}, member 0 on {t0.device}")
+
+    def q_many(self, obs_list, act_list, nets_list=None):
+        """q_values_many over the group's members (nets_list None: qf1 and qf2 of every member)."""
+        if nets_list is None:
+            nets_list = [("qf1", "qf2")] * len(self.trainers)
+        return q_values_many(self.trainers, obs_list, act_list, nets_list)
 
 
 class _SACMembers:

@@ -173,6 +173,17 @@ class FlattenMlp(_Mlp):
         w, b = self.layers[names[-1]]
         return h @ w.T + b
 
+    def __call__(self, obs, act):
+        """``qf(obs, actions)`` as the reference's module: (n, 1).  A holder bound to a trainer with a live handle answers
+        from the trainer's LIVE weights (SACTrainer.q_values: on the device for the fused kernels' shapes), whichever
+        of the trainer's Q networks it is; a holder without one through forward_np, from its own arrays."""
+        tr = self._trainer
+        if tr is not None and getattr(tr, "_h", None) is not None:
+            for name in ("qf1", "qf2", "target_qf1", "target_qf2"):
+                if getattr(tr, name, None) is self:
+                    return tr.q_values(obs, act, nets=(name,)).reshape(-1, 1)
+        return self.forward_np(np.atleast_2d(obs), np.atleast_2d(act))
+
 
 class TanhGaussianPolicy(_Mlp):
     """``TanhGaussianPolicy(hidden_sizes=, obs_dim=, action_dim=)``; ``get_action(obs_np)`` returns

@@ -297,6 +297,60 @@ class SACTrainer:
                        "sac_policy_act_general")
         return out
 
+    def _q_inputs(self, obs, act, nets):
+        """q_values' arguments, checked before any library call: (obs, act, mask, rows)."""
+        mask, rows = _lib.q_net_mask(nets)
+        obs, act = _lib.f32(np.atleast_2d(obs)), _lib.f32(np.atleast_2d(act))
+        if obs.ndim != 2 or act.ndim != 2 or obs.shape[1] != self.obs_dim or act.shape[1] != self.act_dim:
+            raise ValueError(f"q_values: observations {obs.shape} / actions {act.shape} do not fit dims "
+                             f"({self.obs_dim}, {self.act_dim})")
+        if obs.shape[0] != act.shape[0] or obs.shape[0] < 1:
+            raise ValueError(f"q_values: {obs.shape[0]} observation rows and {act.shape[0]} action rows (one action per "
+                             "observation, at least one row)")
+        return obs, act, mask, rows
+
+    def _q_values_host(self, obs, act, nets):
+        """The host path of q_values: the nets' current weights (sac_sync, sac_get_params; the holders' own arrays while
+        the trainer has no handle yet) and a float32 NumPy forward."""
+        if self._h is not None:
+            _lib.check(self._lib.sac_sync(self._h), "sac_sync")
+        x = np.concatenate([obs, act], axis=1)
+        out = np.empty((len(nets), x.shape[0]), np.float32)
+        for r, name in enumerate(nets):
+            flat = self._get_params(name) if self._h is not None else _lib.f32(getattr(self, name).flat())
+            h, off = x, 0
+            sizes = self._hidden(name) + [1]
+            for l, n_out in enumerate(sizes):
+                k = h.shape[1]
+                w, b = flat[off:off + n_out * k].reshape(n_out, k), flat[off + n_out * k:off + n_out * k + n_out]
+                off += n_out * k + n_out
+                h = h @ w.T + b
+                if l + 1 < len(sizes):
+                    h = np.where(h < 0, np.float32(0), h)
+            assert off == flat.size
+            out[r] = h[:, 0]
+        return out
+
+    def q_values(self, obs, act, nets=("qf1", "qf2")):
+        """Q_net(obs, act) of this run's critics from the LIVE weights: float32 (len(nets), n), one row per name in `nets`
+        (of "qf1", "qf2", "target_qf1", "target_qf2") in the order given.  On the device (sac_q_values: k_qval, one launch
+        per 1024 rows for all the nets asked for, no parameter copy); a trainer of the general step, which the library's
+        entry refuses, takes the host path -- sac_sync, sac_get_params, a float32 NumPy forward.  Nothing the step reads
+        is written either way."""
+        obs, act, mask, rows = self._q_inputs(obs, act, nets)
+        names = [nets] if isinstance(nets, str) else list(nets)
+        if self._h is None or self.fused_mode() == 3:
+            return self._q_values_host(obs, act, names)
+        n = obs.shape[0]
+        out = np.empty((len(names), n), np.float32)
+        for i in range(0, n, _lib.ACT_MAX_ROWS):
+            j = min(n, i + _lib.ACT_MAX_ROWS)
+            part = np.empty((len(names), j - i), np.float32)
+            _lib.check(self._lib.sac_q_values(self._h, j - i, _lib.ptr(obs[i:j]), _lib.ptr(act[i:j]), mask, _lib.ptr(part)),
+                       "sac_q_values")
+            out[:, i:j] = part[rows]
+        return out
+
     def refresh_host_policy(self):
         """Mirror the trained policy D2H once per training block (acting stays on the host)."""
         if self._h is not None and self._host_policy_stale:
