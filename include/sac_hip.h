@@ -368,7 +368,8 @@ int sac_policy_act_general_many(sac_trainer_t *const *trainers, int n_trainers, 
  * 1..1024.  A row's value depends on that row's observation and action and the net's weights only -- not on its place,
  * on n, on the other nets selected or on the rest of the launch -- so row r of any call is bit for bit the one-row call.
  * Nothing the step reads is written.  SAC and TD3 handles with the fused kernels' shapes (two hidden layers of at most
- * 256 units); general-step trainers are refused: their Q values come from sac_get_params and a forward on the host. */
+ * 256 units); general-step trainers are refused: their Q values come from sac_get_params and a forward on the host, or
+ * from sac_q_values_general below. */
 enum { SAC_Q_QF1 = 1, SAC_Q_QF2 = 2, SAC_Q_TARGET_QF1 = 4, SAC_Q_TARGET_QF2 = 8 };
 int sac_q_values(sac_trainer_t *t, int64_t n, const float *obs /* (n,O) host */, const float *act /* (n,A) host */,
                  uint32_t nets, float *q /* (popcount(nets), n) host */);
@@ -379,6 +380,21 @@ int sac_q_values(sac_trainer_t *t, int64_t n, const float *obs /* (n,O) host */,
  * n_rows outside 0..1024 or all zero, and for a member with rows a mask that is 0 or has bits above 8, or a null array. */
 int sac_q_values_many(sac_trainer_t *const *trainers, int n_trainers, const int32_t *n_rows,
                       const float *const *obs, const float *const *act, const uint32_t *nets, float *const *q);
+/* The same two entries for GENERAL-STEP trainers (a policy or critics beyond two hidden layers of at most 256 units:
+ * depth 1..7, widths 1..4096; a trainer whose critics alone have the fused shape is served here too): k_qval_layer
+ * (csrc/sac_qval_general.h), one launch per layer depth on the live critic weights of the general step -- no mirror, no
+ * repacking, no parameter copy -- and one wait at the end.  The contract is that of sac_q_values / sac_q_values_many:
+ * SAC_Q_* masks, the selected nets in ascending order, q (popcount(nets), n), n 1..1024 for the solo call, 1..16
+ * trainers of one device, SAC and TD3 handles, dims, depths, widths, row counts and masks mixed, n_rows[i] == 0 = sits
+ * out (at least one with rows), every member with rows drained as by sac_sync first, each member's values bit for bit
+ * its own sac_q_values_general's and row r of any call bit for bit the one-row call.  The kernel writes the trainers' own
+ * activation scratch (shared with sac_policy_act_general: the calls never overlap) and q, nothing the step reads.
+ * Refused (<0, sac_last_error, nothing changed): what sac_q_values_many refuses, and trainers with the fused kernels'
+ * shapes (sac_q_values is their entry).  sac_q_values / sac_q_values_many keep refusing general-step trainers. */
+int sac_q_values_general(sac_trainer_t *t, int64_t n, const float *obs /* (n,O) host */, const float *act /* (n,A) host */,
+                         uint32_t nets, float *q /* (popcount(nets), n) host */);
+int sac_q_values_general_many(sac_trainer_t *const *trainers, int n_trainers, const int32_t *n_rows,
+                              const float *const *obs, const float *const *act, const uint32_t *nets, float *const *q);
 
 /* ------------------------------------------------------------------------------------------
  * Trainer groups: several runs of one configuration (the reference's seed sweeps, /root/reference/launch_jobs.sh)

@@ -26,8 +26,10 @@
 // member table live in the trainer's mapped pinned staging (act_stage_reserve, sac_act.h): a call is one launch and one
 // wait, without a copy call of its own.
 //
-// General-step trainers (hidden sizes beyond the fused kernels') are out of scope here: these entries refuse them, and
-// their Q values come from the host (sac_get_params and a forward there; SACTrainer.q_values does that by itself).
+// General-step trainers (hidden sizes beyond the fused kernels') are out of scope here: these entries refuse them.  Their
+// Q values come from the host (sac_get_params and a forward there: SACTrainer.q_values' default) or from the device
+// through sac_q_values_general[_many] (k_qval_layer, sac_qval_general.h: one launch per layer, as k_act_layer), which in
+// turn refuses the shapes served here.
 #pragma once
 
 namespace sac {

@@ -24,7 +24,7 @@ from .networks import (FlattenMlp, GaussianStrategy, MakeDeterministic, PolicyWr
 from .replay_buffer import EnvReplayBuffer
 from .group import (ArchSACTrainerGroup, ArchTD3TrainerGroup, GroupActor, MixedSACTrainerGroup, MixedTD3TrainerGroup,
                     MlpSACTrainerGroup, MlpTD3TrainerGroup, SACTrainerGroup, TD3TrainerGroup, act_many,
-                    q_values_many, runs_general_step)
+                    _check_general, q_values_many, runs_general_step)
 from .sac import SACTrainer
 from .td3 import TD3Trainer
 from .variant import env_dims, validate
@@ -354,7 +354,8 @@ def _progress_row(buf, trainer, expl, evalc, ak):
 
 
 def experiment(variant, log_dir=None, seed=1, obs_dim=None, action_dim=None, num_epochs=None, device=0,
-               fused_loop=True, quiet=False, checkpoint_dir=None, resume=False, acting="host", q_diagnostics=False):
+               fused_loop=True, quiet=False, checkpoint_dir=None, resume=False, acting="host", q_diagnostics=False,
+               q_general="host"):
     """variant.json -> training run.  Returns the list of progress rows (also written to
     <log_dir>/progress.csv when log_dir is given).
 
@@ -374,8 +375,11 @@ def experiment(variant, log_dir=None, seed=1, obs_dim=None, action_dim=None, num
     critics of one moment), qf1 and qf2 are evaluated on every (observation, action) of the epoch's evaluation paths
     (trainer.q_values: on the device from the live weights) and the row gets q_bias_information's sixteen columns
     behind its evaluation/ block; the time counts under `time/evaluation sampling (s)`.  Off (the default), the row is
-    exactly what it was."""
+    exactly what it was.  q_general ("host", the default, or "device") is q_values' `general`: where a run of the general
+    step evaluates its critics -- sac_get_params and a NumPy forward, or sac_q_values_general (one k_qval_layer launch per
+    layer on the live weights).  Without q_diagnostics, and for a run with the fused kernels' shapes, it has no effect."""
     check_acting(acting)
+    _check_general(q_general)
     validate(variant)
     np.random.seed(seed)                                          # scripts/train.py:112 (args.seed, not variant seed)
     O, A = env_dims(variant["expl_environment_kwargs"], obs_dim, action_dim)
@@ -428,7 +432,7 @@ def experiment(variant, log_dir=None, seed=1, obs_dim=None, action_dim=None, num
         evalc.collect_new_paths(ak["eval_max_path_length"], ak["num_eval_steps_per_epoch"], True)
         q_info = None
         if q_diagnostics:
-            q1, q2 = trainer.q_values(*_path_steps(evalc.epoch_paths, O, A), nets=("qf1", "qf2"))
+            q1, q2 = trainer.q_values(*_path_steps(evalc.epoch_paths, O, A), nets=("qf1", "qf2"), **_q_general_kw(q_general))
             q_info = q_bias_information(evalc.epoch_paths, q1, q2, trainer.discount, trainer.reward_scale)
         t1 = time.time()
         new_paths = expl.collect_new_paths(ak["expl_max_path_length"], ak["num_expl_steps_per_train_loop"], False)
@@ -560,18 +564,24 @@ def _group_save(ck, runs, epoch):
     ck.save([r["trainer"] for r in runs], [r["buf"] for r in runs], [r["identity"] for r in runs], extras)
 
 
-def _group_q_information(runs):
+def _q_general_kw(q_general):
+    """q_general as q_values' / q_values_many's keyword: left out at the default, so the call is what it was."""
+    return {} if q_general == "host" else {"general": q_general}
+
+
+def _group_q_information(runs, q_general="host"):
     """q_bias_information of every run's evaluation paths of this epoch, qf1 and qf2 of all runs from ONE q_values_many
-    call (one launch per 16 runs with the fused kernels' shapes and 1024 rows)."""
+    call (one launch per 16 runs with the fused kernels' shapes and 1024 rows; q_general="device": the runs of the
+    general step from one sac_q_values_general_many call per 16 of them, otherwise from the host path)."""
     steps = [_path_steps(r["evalc"].epoch_paths, r["trainer"].obs_dim, r["trainer"].act_dim) for r in runs]
     qs = q_values_many([r["trainer"] for r in runs], [s[0] for s in steps], [s[1] for s in steps],
-                       [("qf1", "qf2")] * len(runs))
+                       [("qf1", "qf2")] * len(runs), **_q_general_kw(q_general))
     return [q_bias_information(r["evalc"].epoch_paths, q[0], q[1], r["trainer"].discount, r["trainer"].reward_scale)
             for r, q in zip(runs, qs)]
 
 
 def _group_epochs(runs, train_block, n_epochs, n_train, log_dir, quiet, what, ck=None, first_epoch=0, acting="host",
-                  sessions=True, general_sessions=None, q_diagnostics=False):
+                  sessions=True, general_sessions=None, q_diagnostics=False, q_general="host"):
     """The epoch loop of a grouped experiment: each run collects its paths, then train_block() trains every run at once,
     then every run ends its epoch, the group is saved (with a GroupCheckpoint `ck`), and each run writes its row (to
     <log_dir>/<run["sub"]>/progress.csv with log_dir; appended to after a resume).
@@ -583,7 +593,7 @@ def _group_epochs(runs, train_block, n_epochs, n_train, log_dir, quiet, what, ck
     acting sessions of their own, None: GroupActor's default -- the rows are the same either way).
     q_diagnostics=True: as experiment()'s, qf1 and qf2 of ALL runs on their evaluation paths from one q_values_many call
     per epoch, behind the runs' evaluation paths and in front of the training block; its time is added to every run's
-    time/evaluation sampling (s)."""
+    time/evaluation sampling (s); q_general is q_values_many's `general` for that call."""
     t_start = time.time()
     lockstep = acting != "host"
     lock_kw = dict(sessions=sessions, general="device" if acting == "device_all" else "host", general_sessions=general_sessions)
@@ -596,7 +606,7 @@ def _group_epochs(runs, train_block, n_epochs, n_train, log_dir, quiet, what, ck
                 t0 = time.time()
                 lock_eval.collect_new_paths([(r["ak"]["eval_max_path_length"], r["ak"]["num_eval_steps_per_epoch"], True)
                                              for r in runs])
-                q_infos = _group_q_information(runs) if q_diagnostics else None
+                q_infos = _group_q_information(runs, q_general) if q_diagnostics else None
                 t1 = time.time()
                 new = lock_expl.collect_new_paths([(r["ak"]["expl_max_path_length"],
                                                     r["ak"]["num_expl_steps_per_train_loop"], False) for r in runs])
@@ -616,7 +626,7 @@ def _group_epochs(runs, train_block, n_epochs, n_train, log_dir, quiet, what, ck
                 times.append((t0, t1 - t0, t2 - t1, time.time() - t2))
             if q_diagnostics and not lockstep:                # (nobody has trained since the first run's evaluation paths)
                 s0 = time.time()
-                q_infos = _group_q_information(runs)
+                q_infos = _group_q_information(runs, q_general)
                 q_s = time.time() - s0
                 times = [(a0, eval_s + q_s, expl_s, store_s) for a0, eval_s, expl_s, store_s in times]
             t3 = time.time()
@@ -672,7 +682,7 @@ def _group_epochs(runs, train_block, n_epochs, n_train, log_dir, quiet, what, ck
 
 def experiment_group(variant, seeds, log_dir=None, num_epochs=None, obs_dim=None, action_dim=None, device=0,
                      quiet=False, checkpoint_dir=None, resume=False, chunk_rows=DEFAULT_CHUNK_ROWS, acting="host", sessions=True,
-                     general_sessions=None, q_diagnostics=False):
+                     general_sessions=None, q_diagnostics=False, q_general="host"):
     """One configuration, several seeds, one process: each seed is the run ``experiment(variant, seed=s)`` would make --
     its own synthetic environments, collectors, weights and replay buffer -- and every epoch's training block is ONE
     SACTrainerGroup.train_loop (TD3 variants: TD3TrainerGroup; hidden sizes other than two layers of at most 256 units:
@@ -694,8 +704,10 @@ def experiment_group(variant, seeds, log_dir=None, num_epochs=None, obs_dim=None
     device too (one sac_policy_act_general_many call per tick and 16 of them; with sessions and general_sessions=True one
     sac_gactor_act call, None: GroupActor's default); rows as experiment(..., acting="device_all").
     q_diagnostics=True: experiment()'s critic columns for every seed, all seeds' Q values from one q_values_many call per
-    epoch; each seed's rows are those of experiment(variant, seed=s, q_diagnostics=True)."""
+    epoch; each seed's rows are those of experiment(variant, seed=s, q_diagnostics=True).  q_general as for experiment()
+    (general-step seeds: one sac_q_values_general_many call per 16 of them with "device")."""
     check_acting(acting)
+    _check_general(q_general)
     if resume and not checkpoint_dir:
         raise RuntimeError("experiment_group(resume=True) needs the checkpoint_dir to resume from")
     validate(variant)
@@ -721,7 +733,7 @@ def experiment_group(variant, seeds, log_dir=None, num_epochs=None, obs_dim=None
         train_block = lambda: group.train_loop([r["buf"] for r in runs], n_train, batch_size=ak["batch_size"])  # noqa: E731
     _group_epochs(runs, train_block,
                   num_epochs if num_epochs is not None else ak["num_epochs"], n_train, log_dir, quiet, "seeds", ck,
-                  first_epoch, acting, sessions, general_sessions, q_diagnostics)
+                  first_epoch, acting, sessions, general_sessions, q_diagnostics, q_general)
     return {r["seed"]: r["rows"] for r in runs}
 
 
@@ -748,7 +760,7 @@ def sweep_label(variant, seed, hidden_sweep=False):
 
 def experiment_sweep(runs, log_dir=None, num_epochs=None, device=0, quiet=False, checkpoint_dir=None, resume=False,
                      chunk_rows=DEFAULT_CHUNK_ROWS, hidden_sweep=False, acting="host", sessions=True, general_sessions=None,
-                     q_diagnostics=False):
+                     q_diagnostics=False, q_general="host"):
     """Several tasks x seeds, one process, one device: every entry of ``runs`` -- (variant, seed), or (variant, seed,
     obs_dim, action_dim) for a task without pinned dims -- is the run ``experiment(variant, seed=seed)`` would make, and
     every epoch's training block is ONE MixedSACTrainerGroup.train_loop (TD3 variants: MixedTD3TrainerGroup; hidden sizes
@@ -766,8 +778,10 @@ def experiment_sweep(runs, log_dir=None, num_epochs=None, device=0, quiet=False,
     lockstep ticks (act_many), so each run's rows stay those of its solo experiment(..., acting="device").  Under
     "device_all" those runs act on the device inside the same ticks, and each run's rows are those of its solo
     experiment(..., acting="device_all").
-    q_diagnostics as for experiment_group (the runs of the general step take q_values' host path inside the same call)."""
+    q_diagnostics as for experiment_group (the runs of the general step take q_values' host path inside the same call;
+    with q_general="device" they are evaluated on the device, one sac_q_values_general_many call per 16 of them)."""
     check_acting(acting)
+    _check_general(q_general)
     if resume and not checkpoint_dir:
         raise RuntimeError("experiment_sweep(resume=True) needs the checkpoint_dir to resume from")
     specs = []
@@ -817,5 +831,5 @@ def experiment_sweep(runs, log_dir=None, num_epochs=None, device=0, quiet=False,
     batches = [r["ak"]["batch_size"] for r in group_runs]
     _group_epochs(group_runs, lambda: group.train_loop([r["buf"] for r in group_runs], n_train, batch_sizes=batches),
                   num_epochs if num_epochs is not None else ak0["num_epochs"], n_train, log_dir, quiet, "runs", ck,
-                  first_epoch, acting, sessions, general_sessions, q_diagnostics)
+                  first_epoch, acting, sessions, general_sessions, q_diagnostics, q_general)
     return [r["rows"] for r in group_runs]

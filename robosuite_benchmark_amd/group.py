@@ -105,13 +105,17 @@ def act_many(trainers, obs_list, deterministic_list, eps_list, general="host"):
     return out
 
 
-def q_values_many(trainers, obs_list, act_list, nets_list):
+def q_values_many(trainers, obs_list, act_list, nets_list, general="host"):
     """SACTrainer.q_values for many runs at once: q[i] = trainers[i]'s critics nets_list[i] (names, as q_values takes
     them) on obs_list[i] / act_list[i] ((n_i, O_i) / (n_i, A_i); None or no rows: the member sits out and gets an empty
     (len(nets), 0) array).  The members with the fused kernels' shapes are served by ONE launch per 16 of them and 1024
     rows (sac_q_values_many: SAC and TD3, dims, row counts and nets mixed); members of the general step take q_values'
     host path inside the same call.  A member's values never depend on its neighbours: they are bit for bit those of its
-    own q_values."""
+    own q_values.
+    general="device": the members of the general step are evaluated on the device as well, by ONE
+    sac_q_values_general_many call per 16 of them and 1024 rows; their values are bit for bit those of their own
+    q_values(general="device")."""
+    _check_general(general)
     trainers = list(trainers)
     R = len(trainers)
     if not (len(obs_list) == len(act_list) == len(nets_list) == R):
@@ -119,7 +123,7 @@ def q_values_many(trainers, obs_list, act_list, nets_list):
     if len({id(t) for t in trainers}) != R:
         raise RuntimeError("a trainer appears twice in q_values_many")
     obs, act, rows, names, masks, out = [None] * R, [None] * R, [None] * R, [None] * R, [0] * R, [None] * R
-    dev = []
+    dev, gen = [], []
     for i, t in enumerate(trainers):
         names[i] = [nets_list[i]] if isinstance(nets_list[i], str) else list(nets_list[i])
         masks[i], rows[i] = _lib.q_net_mask(names[i])
@@ -127,27 +131,29 @@ def q_values_many(trainers, obs_list, act_list, nets_list):
             out[i] = np.empty((len(names[i]), 0), np.float32)
             continue
         obs[i], act[i], _, _ = t._q_inputs(obs_list[i], act_list[i], names[i])
-        if t._h is None or runs_general_step(t):
+        general_step = t._h is not None and runs_general_step(t)
+        if t._h is None or (general_step and general != "device"):
             out[i] = t._q_values_host(obs[i], act[i], names[i])
         else:
             out[i] = np.empty((len(names[i]), obs[i].shape[0]), np.float32)
-            dev.append(i)
-    lib = _lib.load() if dev else None
-    for r0 in range(0, max([obs[i].shape[0] for i in dev], default=0), _lib.ACT_MAX_ROWS):
-        live = [i for i in dev if obs[i].shape[0] > r0]
-        for c in range(0, len(live), MAX_MEMBERS):
-            ids = live[c:c + MAX_MEMBERS]
-            n = len(ids)
-            n_rows = [min(obs[i].shape[0] - r0, _lib.ACT_MAX_ROWS) for i in ids]
-            o = [obs[i][r0:r0 + k] for i, k in zip(ids, n_rows)]
-            a = [act[i][r0:r0 + k] for i, k in zip(ids, n_rows)]
-            q = [np.empty((len(names[i]), k), np.float32) for i, k in zip(ids, n_rows)]
-            vp = lambda arrs: (C.c_void_p * n)(*[x.ctypes.data for x in arrs])  # noqa: E731
-            _lib.check(lib.sac_q_values_many((C.c_void_p * n)(*[trainers[i]._h.value for i in ids]), n,
-                                             (C.c_int32 * n)(*n_rows), vp(o), vp(a),
-                                             (C.c_uint32 * n)(*[masks[i] for i in ids]), vp(q)), "sac_q_values_many")
-            for i, k, part in zip(ids, n_rows, q):
-                out[i][:, r0:r0 + k] = part[rows[i]]
+            (gen if general_step else dev).append(i)
+    lib = _lib.load() if dev or gen else None
+    for members, entry in ((dev, "sac_q_values_many"), (gen, "sac_q_values_general_many")):
+        for r0 in range(0, max([obs[i].shape[0] for i in members], default=0), _lib.ACT_MAX_ROWS):
+            live = [i for i in members if obs[i].shape[0] > r0]
+            for c in range(0, len(live), MAX_MEMBERS):
+                ids = live[c:c + MAX_MEMBERS]
+                n = len(ids)
+                n_rows = [min(obs[i].shape[0] - r0, _lib.ACT_MAX_ROWS) for i in ids]
+                o = [obs[i][r0:r0 + k] for i, k in zip(ids, n_rows)]
+                a = [act[i][r0:r0 + k] for i, k in zip(ids, n_rows)]
+                q = [np.empty((len(names[i]), k), np.float32) for i, k in zip(ids, n_rows)]
+                vp = lambda arrs: (C.c_void_p * n)(*[x.ctypes.data for x in arrs])  # noqa: E731
+                _lib.check(getattr(lib, entry)((C.c_void_p * n)(*[trainers[i]._h.value for i in ids]), n,
+                                               (C.c_int32 * n)(*n_rows), vp(o), vp(a),
+                                               (C.c_uint32 * n)(*[masks[i] for i in ids]), vp(q)), entry)
+                for i, k, part in zip(ids, n_rows, q):
+                    out[i][:, r0:r0 + k] = part[rows[i]]
     return out
 
 
@@ -367,11 +373,12 @@ class _Members:
         if t.device != t0.device:
             raise RuntimeError(f"trainer group member {i} lives on device {t.device}, member 0 on {t0.device}")
 
-    def q_many(self, obs_list, act_list, nets_list=None):
-        """q_values_many over the group's members (nets_list None: qf1 and qf2 of every member)."""
+    def q_many(self, obs_list, act_list, nets_list=None, general="host"):
+        """q_values_many over the group's members (nets_list None: qf1 and qf2 of every member; general as there)."""
+        _check_general(general)
         if nets_list is None:
             nets_list = [("qf1", "qf2")] * len(self.trainers)
-        return q_values_many(self.trainers, obs_list, act_list, nets_list)
+        return q_values_many(self.trainers, obs_list, act_list, nets_list, general=general)
 
 
 class _SACMembers:

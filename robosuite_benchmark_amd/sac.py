@@ -331,23 +331,31 @@ class SACTrainer:
             out[r] = h[:, 0]
         return out
 
-    def q_values(self, obs, act, nets=("qf1", "qf2")):
+    def q_values(self, obs, act, nets=("qf1", "qf2"), general="host"):
         """Q_net(obs, act) of this run's critics from the LIVE weights: float32 (len(nets), n), one row per name in `nets`
         (of "qf1", "qf2", "target_qf1", "target_qf2") in the order given.  On the device (sac_q_values: k_qval, one launch
         per 1024 rows for all the nets asked for, no parameter copy); a trainer of the general step, which the library's
         entry refuses, takes the host path -- sac_sync, sac_get_params, a float32 NumPy forward.  Nothing the step reads
-        is written either way."""
+        is written either way.
+        general (one of group.GENERAL) decides for a trainer of the general step only: "host", the default, keeps the host
+        path; "device" evaluates on the device as well (sac_q_values_general: k_qval_layer, one launch per layer on the
+        live weights, in calls of at most 1024 rows, no parameter copy).  A trainer with the fused kernels' shapes takes
+        sac_q_values and a trainer without a handle the host path under either value."""
+        from .group import _check_general
+        _check_general(general)
         obs, act, mask, rows = self._q_inputs(obs, act, nets)
         names = [nets] if isinstance(nets, str) else list(nets)
-        if self._h is None or self.fused_mode() == 3:
+        gen = self._h is not None and self.fused_mode() == 3
+        if self._h is None or (gen and general != "device"):
             return self._q_values_host(obs, act, names)
+        entry = "sac_q_values_general" if gen else "sac_q_values"
+        fn = getattr(self._lib, entry)
         n = obs.shape[0]
         out = np.empty((len(names), n), np.float32)
         for i in range(0, n, _lib.ACT_MAX_ROWS):
             j = min(n, i + _lib.ACT_MAX_ROWS)
             part = np.empty((len(names), j - i), np.float32)
-            _lib.check(self._lib.sac_q_values(self._h, j - i, _lib.ptr(obs[i:j]), _lib.ptr(act[i:j]), mask, _lib.ptr(part)),
-                       "sac_q_values")
+            _lib.check(fn(self._h, j - i, _lib.ptr(obs[i:j]), _lib.ptr(act[i:j]), mask, _lib.ptr(part)), entry)
             out[:, i:j] = part[rows]
         return out
 

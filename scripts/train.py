@@ -13,7 +13,8 @@
  nets alike, implies --hidden_sweep.  --acting device: the policies act through the device kernel instead of the
  host forward; grouped runs then collect their paths in lockstep.  --acting device_all: the same, and runs of any
  hidden sizes act on the device.  --q_diagnostics: every epoch, Q1 and Q2 on the evaluation paths from the live
- weights against the discounted returns obtained there: sixteen evaluation/ columns more in progress.csv)
+ weights against the discounted returns obtained there: sixteen evaluation/ columns more in progress.csv.
+ --q_general device: with --q_diagnostics, runs of any hidden sizes evaluate their critics on the device too)
 Runs the variant unchanged (batch size, lrs, tau, period, buffer size ... from the JSON) on the
 HIP library with a synthetic environment of the task's dimensions (robosuite is not installed)."""
 import argparse
@@ -63,6 +64,10 @@ if __name__ == "__main__":
                     help="every epoch, evaluate qf1 and qf2 on the evaluation paths (a HIP kernel on the live weights) and "
                          "log evaluation/Q1 Estimates, Q2 Estimates, Returns To Go and Q Bias = min(Q1, Q2) - discounted "
                          "return to go; off: progress.csv is unchanged")
+    ap.add_argument("--q_general", type=str, default="host", choices=["host", "device"],
+                    help="with --q_diagnostics: where runs whose hidden sizes are beyond two layers of at most 256 units "
+                         "evaluate qf1 and qf2 -- host (a parameter copy and a NumPy forward) or device (one HIP launch per "
+                         "layer on the live weights); without --q_diagnostics it has no effect")
     args = ap.parse_args()
     if (args.hidden_sweep or args.hidden_sizes) and not args.variants:
         raise SystemExit("--hidden_sweep / --hidden_sizes need --variants")
@@ -71,7 +76,7 @@ if __name__ == "__main__":
         if args.checkpoint and not log_dir:
             raise SystemExit("--checkpoint needs --log_dir (the group is saved to <log_dir>/checkpoint)")
         group_kw = dict(log_dir=log_dir, num_epochs=args.epochs, resume=bool(args.resume), acting=args.acting,
-                        q_diagnostics=args.q_diagnostics,
+                        q_diagnostics=args.q_diagnostics, q_general=args.q_general,
                         checkpoint_dir=os.path.join(log_dir, "checkpoint") if (args.checkpoint or args.resume) else None)
         try:
             if args.variants:
@@ -108,4 +113,5 @@ if __name__ == "__main__":
         json.dump(variant, open(os.path.join(run_dir, "variant.json"), "w"), indent=2, sort_keys=True)
     ckpt = os.path.join(run_dir, "checkpoint") if (run_dir and not args.no_checkpoint) else None
     experiment(variant, log_dir=run_dir, seed=args.seed, num_epochs=args.epochs, checkpoint_dir=ckpt,
-               resume=bool(args.resume), acting=args.acting, q_diagnostics=args.q_diagnostics)
+               resume=bool(args.resume), acting=args.acting, q_diagnostics=args.q_diagnostics,
+               q_general=args.q_general)
