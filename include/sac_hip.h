@@ -396,6 +396,41 @@ int sac_q_values_general(sac_trainer_t *t, int64_t n, const float *obs /* (n,O) 
 int sac_q_values_general_many(sac_trainer_t *const *trainers, int n_trainers, const int32_t *n_rows,
                               const float *const *obs, const float *const *act, const uint32_t *nets, float *const *q);
 
+/* The SAC objectives on HELD-OUT transitions, on the DEVICE from the live weights: the forward half of the step as an
+ * evaluation (k_eval, csrc/sac_eval.h) -- n transitions (s, a, r, d, s') with their N(0,1) draws in one launch, three
+ * independent chains per 16-row block:
+ *   rows[SAC_EVAL_Q1 / Q2]                  Q1 / Q2(s, a)
+ *   rows[SAC_EVAL_Q1_NEW / Q2_NEW]          Q1 / Q2(s, a_new), a_new = tanh(mean(s) + exp(clamp(log_std(s), -20, 2)) eps)
+ *   rows[SAC_EVAL_LOG_PI]                   log pi(a_new | s)   (mu, log_std: the head's mean and clamped log_std)
+ *   rows[SAC_EVAL_TQ1 / TQ2]                target_qf1 / target_qf2(s', a_next), a_next from s' and eps_next
+ *   rows[SAC_EVAL_LOG_PI_NEXT]              log pi(a_next | s')
+ *   rows[SAC_EVAL_Y]                        reward_scale r + (1 - d) discount (min(tq1, tq2) - alpha log_pi_next), each
+ *                                           operation rounded to float32 on its own, in this order
+ * alpha is the trainer's CURRENT entropy coefficient -- sac_get_scalars' scalars[5], 1 with automatic tuning off, exp(log_alpha) for a trainer that
+ * has neither stepped nor been given scalars, whose scalars[5] still reads 0 -- read behind the drain and returned in io->alpha: the objective at the current parameters.  (The training step logs Alpha,
+ * Q Targets and its losses behind its own alpha update, one alpha step further on.)  The Q columns are bit for bit
+ * sac_q_values' on the same rows and a_new / a_next bit for bit sac_policy_act_device's; row r of any call is bit for
+ * bit the one-row call.  The call drains the trainer as sac_sync does, reads the nets where the step keeps them and
+ * writes nothing the step reads: parameters, optimizer state, scalars, the step's noise counter and the buffer
+ * generator stay untouched.  n is 1..1024.  SAC trainers with the fused kernels' shapes; general-step trainers are
+ * refused (sac_get_params and a forward on the host is their path) and so are TD3 trainers (this is the SAC objective). */
+enum { SAC_EVAL_Q1, SAC_EVAL_Q2, SAC_EVAL_Q1_NEW, SAC_EVAL_Q2_NEW, SAC_EVAL_TQ1, SAC_EVAL_TQ2,
+       SAC_EVAL_LOG_PI, SAC_EVAL_LOG_PI_NEXT, SAC_EVAL_Y, SAC_EVAL_ROWS_N };
+typedef struct {
+    const float *obs, *act, *rew, *term, *next_obs;   /* (n,O) (n,A) (n) (n) (n,O), host */
+    const float *eps, *eps_next;                      /* (n,A) N(0,1) draws, host */
+    float *rows;                                      /* (SAC_EVAL_ROWS_N, n) */
+    float *mu, *log_std, *a_new, *a_next;             /* (n,A) each; any may be NULL */
+    float alpha;                                      /* out: the entropy coefficient used */
+} sac_eval_io_t;
+int sac_evaluate(sac_trainer_t *t, int64_t n, sac_eval_io_t *io);                 /* n in 1..1024 */
+/* the same for 1..SAC_GROUP_MAX (16) trainers of one device in ONE launch, io[i] for trainer i; n_rows[i] == 0: member i
+ * sits out (its io is not looked at).  Dims, hidden sizes and row counts may be mixed; each member's columns are bit for
+ * bit its own sac_evaluate's.  Refused (<0, sac_last_error, nothing changed): null or duplicate trainers, trainers on
+ * different devices, TD3 trainers, general-step trainers, members confined by sac_trainer_set_xcd[_mask], n_rows outside
+ * 0..1024 or all zero, and for a member with rows a null input array or null rows. */
+int sac_evaluate_many(sac_trainer_t *const *trainers, int n_trainers, const int32_t *n_rows, sac_eval_io_t *io);
+
 /* ------------------------------------------------------------------------------------------
  * Trainer groups: several runs of one configuration (the reference's seed sweeps, /root/reference/launch_jobs.sh)
  * stepped together.  A group holds 1..SAC_GROUP_MAX existing SAC trainers that share obs_dim, act_dim, batch (at most

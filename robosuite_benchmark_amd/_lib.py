@@ -68,6 +68,17 @@ class Td3Config(C.Structure):
     ]
 
 
+# the per-row columns of sac_evaluate (SAC_EVAL_*: the rows of sac_eval_io_t.rows, in this order)
+EVAL_ROWS = ["q1", "q2", "q1_new", "q2_new", "tq1", "tq2", "log_pi", "log_pi_next", "y"]
+EVAL_ARRAYS = ["mu", "log_std", "a_new", "a_next"]      # its (n, A) outputs
+
+
+class SacEvalIO(C.Structure):
+    """sac_eval_io_t"""
+    _fields_ = [(k, C.c_void_p) for k in ("obs", "act", "rew", "term", "next_obs", "eps", "eps_next", "rows",
+                                          "mu", "log_std", "a_new", "a_next")] + [("alpha", C.c_float)]
+
+
 TD3_DIAG_NAMES = DIAG_NAMES[:16] + [f"Bellman Errors {i} {s}" for i in (1, 2) for s in ("Mean", "Std", "Max", "Min")] + [
     f"Policy Action {s}" for s in ("Mean", "Std", "Max", "Min")]
 
@@ -137,6 +148,8 @@ SYMBOLS = {
     "sac_q_values_many": (C.c_int, [_P, C.c_int, _P, _P, _P, _P, _P]),
     "sac_q_values_general": (C.c_int, [_P, C.c_int64, _P, _P, C.c_uint32, _P]),
     "sac_q_values_general_many": (C.c_int, [_P, C.c_int, _P, _P, _P, _P, _P]),
+    "sac_evaluate": (C.c_int, [_P, C.c_int64, _P]),
+    "sac_evaluate_many": (C.c_int, [_P, C.c_int, _P, _P]),
     "sac_group_create": (C.c_int, [C.POINTER(_P), _P, C.c_int]),
     "td3_group_create": (C.c_int, [C.POINTER(_P), _P, C.c_int]),
     "sac_group_create_mixed": (C.c_int, [C.POINTER(_P), _P, C.c_int]),

@@ -24,8 +24,8 @@ from .networks import (FlattenMlp, GaussianStrategy, MakeDeterministic, PolicyWr
 from .replay_buffer import EnvReplayBuffer
 from .group import (ArchSACTrainerGroup, ArchTD3TrainerGroup, GroupActor, MixedSACTrainerGroup, MixedTD3TrainerGroup,
                     MlpSACTrainerGroup, MlpTD3TrainerGroup, SACTrainerGroup, TD3TrainerGroup, act_many,
-                    _check_general, q_values_many, runs_general_step)
-from .sac import SACTrainer
+                    _check_general, evaluate_many, q_values_many, runs_general_step)
+from .sac import SACTrainer, eval_statistics
 from .td3 import TD3Trainer
 from .variant import env_dims, validate
 
@@ -332,6 +332,54 @@ def _path_steps(paths, O, A):
             np.concatenate([np.asarray(p["actions"], np.float32).reshape(-1, A) for p in paths]))
 
 
+VALIDATION_STREAM = 0x56414C      # "VAL": the third seed word of an epoch's validation draws
+
+
+def _validation_batch(paths, O, A):
+    """Every transition of `paths`, the paths one behind the other, as the dict SACTrainer.evaluate takes (None without
+    paths)."""
+    if not paths:
+        return None
+    cat = lambda k, w: np.concatenate([np.asarray(p[k], np.float32).reshape(-1, w) for p in paths])  # noqa: E731
+    return dict(observations=cat("observations", O), actions=cat("actions", A), rewards=cat("rewards", 1),
+                terminals=cat("terminals", 1), next_observations=cat("next_observations", O))
+
+
+def _validation_eps(seed, epoch, batch, A):
+    """(eps, eps_next) of a run's validation in `epoch`: a function of (seed, epoch) alone, so nothing needs checkpointing
+    and a resumed run logs the same rows."""
+    if batch is None:
+        return None
+    rs = np.random.RandomState([int(seed) & 0xFFFFFFFF, int(epoch), VALIDATION_STREAM])
+    n = batch["observations"].shape[0]
+    return rs.standard_normal((n, A)), rs.standard_normal((n, A))
+
+
+def _validation_columns(stats, batch):
+    """validation/<key> for every key of SACTrainer.evaluate, and validation/Num Transitions."""
+    d = OrderedDict()
+    if stats is None:                                         # (no evaluation path this epoch: the columns stay, empty)
+        z = np.zeros((1, 1))
+        stats = OrderedDict((k, float("nan")) for k in eval_statistics(np.zeros((9, 1)), z, z, 1.0, 0.0, 0.0, False))
+    d.update(("validation/" + k, v) for k, v in stats.items())
+    d["validation/Num Transitions"] = 0 if batch is None else int(batch["observations"].shape[0])
+    return d
+
+
+def _refuse_td3_validation(variant, what):
+    if variant.get("algorithm", "SAC") == "TD3":
+        raise RuntimeError(f"{what}(validation=True): validation evaluates the SAC objective (SACTrainer.evaluate); a TD3 "
+                           "variant has no such evaluation")
+
+
+def _group_validation(runs, epoch):
+    """_validation_columns of every run's evaluation paths of this epoch, all runs from ONE evaluate_many call."""
+    batches = [_validation_batch(r["evalc"].epoch_paths, r["trainer"].obs_dim, r["trainer"].act_dim) for r in runs]
+    eps = [_validation_eps(r["seed"], epoch, b, r["trainer"].act_dim) for r, b in zip(runs, batches)]
+    stats = evaluate_many([r["trainer"] for r in runs], batches, eps=eps)
+    return [_validation_columns(s, b) for s, b in zip(stats, batches)]
+
+
 def _rs_pack(rs):
     st = rs.get_state()
     return dict(key=[int(x) for x in st[1]], pos=int(st[2]), has_gauss=int(st[3]), cached=float(st[4]))
@@ -355,7 +403,7 @@ def _progress_row(buf, trainer, expl, evalc, ak):
 
 def experiment(variant, log_dir=None, seed=1, obs_dim=None, action_dim=None, num_epochs=None, device=0,
                fused_loop=True, quiet=False, checkpoint_dir=None, resume=False, acting="host", q_diagnostics=False,
-               q_general="host"):
+               q_general="host", validation=False):
     """variant.json -> training run.  Returns the list of progress rows (also written to
     <log_dir>/progress.csv when log_dir is given).
 
@@ -377,10 +425,21 @@ def experiment(variant, log_dir=None, seed=1, obs_dim=None, action_dim=None, num
     behind its evaluation/ block; the time counts under `time/evaluation sampling (s)`.  Off (the default), the row is
     exactly what it was.  q_general ("host", the default, or "device") is q_values' `general`: where a run of the general
     step evaluates its critics -- sac_get_params and a NumPy forward, or sac_q_values_general (one k_qval_layer launch per
-    layer on the live weights).  Without q_diagnostics, and for a run with the fused kernels' shapes, it has no effect."""
+    layer on the live weights).  Without q_diagnostics, and for a run with the fused kernels' shapes, it has no effect.
+
+    validation=True: every epoch, right behind the evaluation paths (and q_diagnostics) and in front of the training
+    block, the SAC objectives are evaluated on the transitions of the epoch's evaluation paths -- collected
+    deterministically, never in the replay buffer: a held-out set -- by trainer.evaluate (on the device from the live
+    weights and the current entropy coefficient; a run of the general step on the host), with the N(0,1) draws of
+    RandomState([seed, epoch, 0x56414C]): nothing to checkpoint, and a resumed run logs the same rows.  The row gains
+    validation/<key> for every key of evaluate and validation/Num Transitions, behind the q_diagnostics columns and in
+    front of time/*; the time counts under `time/evaluation sampling (s)`.  A TD3 variant is refused.  Off (the
+    default), the row, every generator and every column are exactly what they were."""
     check_acting(acting)
     _check_general(q_general)
     validate(variant)
+    if validation:
+        _refuse_td3_validation(variant, "experiment")
     np.random.seed(seed)                                          # scripts/train.py:112 (args.seed, not variant seed)
     O, A = env_dims(variant["expl_environment_kwargs"], obs_dim, action_dim)
     ak, tk = variant["algorithm_kwargs"], variant["trainer_kwargs"]
@@ -434,6 +493,11 @@ def experiment(variant, log_dir=None, seed=1, obs_dim=None, action_dim=None, num
         if q_diagnostics:
             q1, q2 = trainer.q_values(*_path_steps(evalc.epoch_paths, O, A), nets=("qf1", "qf2"), **_q_general_kw(q_general))
             q_info = q_bias_information(evalc.epoch_paths, q1, q2, trainer.discount, trainer.reward_scale)
+        v_info = None
+        if validation:
+            vb = _validation_batch(evalc.epoch_paths, O, A)
+            v_info = _validation_columns(None if vb is None else trainer.evaluate(vb, eps=_validation_eps(seed, epoch, vb, A)),
+                                         vb)
         t1 = time.time()
         new_paths = expl.collect_new_paths(ak["expl_max_path_length"], ak["num_expl_steps_per_train_loop"], False)
         t2 = time.time()
@@ -450,6 +514,8 @@ def experiment(variant, log_dir=None, seed=1, obs_dim=None, action_dim=None, num
         row = _progress_row(buf, trainer, expl, evalc, ak)
         if q_info is not None:
             row.update(q_info)
+        if v_info is not None:
+            row.update(v_info)
         trainer.end_epoch(epoch); buf.end_epoch(epoch); expl.end_epoch(epoch); evalc.end_epoch(epoch)
         t5 = time.time()
         if checkpoint_dir:
@@ -581,7 +647,7 @@ def _group_q_information(runs, q_general="host"):
 
 
 def _group_epochs(runs, train_block, n_epochs, n_train, log_dir, quiet, what, ck=None, first_epoch=0, acting="host",
-                  sessions=True, general_sessions=None, q_diagnostics=False, q_general="host"):
+                  sessions=True, general_sessions=None, q_diagnostics=False, q_general="host", validation=False):
     """The epoch loop of a grouped experiment: each run collects its paths, then train_block() trains every run at once,
     then every run ends its epoch, the group is saved (with a GroupCheckpoint `ck`), and each run writes its row (to
     <log_dir>/<run["sub"]>/progress.csv with log_dir; appended to after a resume).
@@ -593,7 +659,9 @@ def _group_epochs(runs, train_block, n_epochs, n_train, log_dir, quiet, what, ck
     acting sessions of their own, None: GroupActor's default -- the rows are the same either way).
     q_diagnostics=True: as experiment()'s, qf1 and qf2 of ALL runs on their evaluation paths from one q_values_many call
     per epoch, behind the runs' evaluation paths and in front of the training block; its time is added to every run's
-    time/evaluation sampling (s); q_general is q_values_many's `general` for that call."""
+    time/evaluation sampling (s); q_general is q_values_many's `general` for that call.
+    validation=True: as experiment()'s, ALL runs on their evaluation paths from one evaluate_many call per epoch, at the
+    same place and with the same accounting of its time."""
     t_start = time.time()
     lockstep = acting != "host"
     lock_kw = dict(sessions=sessions, general="device" if acting == "device_all" else "host", general_sessions=general_sessions)
@@ -607,6 +675,7 @@ def _group_epochs(runs, train_block, n_epochs, n_train, log_dir, quiet, what, ck
                 lock_eval.collect_new_paths([(r["ak"]["eval_max_path_length"], r["ak"]["num_eval_steps_per_epoch"], True)
                                              for r in runs])
                 q_infos = _group_q_information(runs, q_general) if q_diagnostics else None
+                v_infos = _group_validation(runs, epoch) if validation else None
                 t1 = time.time()
                 new = lock_expl.collect_new_paths([(r["ak"]["expl_max_path_length"],
                                                     r["ak"]["num_expl_steps_per_train_loop"], False) for r in runs])
@@ -629,6 +698,11 @@ def _group_epochs(runs, train_block, n_epochs, n_train, log_dir, quiet, what, ck
                 q_infos = _group_q_information(runs, q_general)
                 q_s = time.time() - s0
                 times = [(a0, eval_s + q_s, expl_s, store_s) for a0, eval_s, expl_s, store_s in times]
+            if validation and not lockstep:
+                s0 = time.time()
+                v_infos = _group_validation(runs, epoch)
+                v_s = time.time() - s0
+                times = [(a0, eval_s + v_s, expl_s, store_s) for a0, eval_s, expl_s, store_s in times]
             t3 = time.time()
             train_block()
             t4 = time.time()
@@ -637,6 +711,8 @@ def _group_epochs(runs, train_block, n_epochs, n_train, log_dir, quiet, what, ck
                 row = _progress_row(r["buf"], r["trainer"], r["expl"], r["evalc"], r["ak"])
                 if q_diagnostics:
                     row.update(q_infos[len(ended)])
+                if validation:
+                    row.update(v_infos[len(ended)])
                 for x in (r["trainer"], r["buf"], r["expl"], r["evalc"]):
                     x.end_epoch(epoch)
                 ended.append((row, time.time()))
@@ -682,7 +758,7 @@ def _group_epochs(runs, train_block, n_epochs, n_train, log_dir, quiet, what, ck
 
 def experiment_group(variant, seeds, log_dir=None, num_epochs=None, obs_dim=None, action_dim=None, device=0,
                      quiet=False, checkpoint_dir=None, resume=False, chunk_rows=DEFAULT_CHUNK_ROWS, acting="host", sessions=True,
-                     general_sessions=None, q_diagnostics=False, q_general="host"):
+                     general_sessions=None, q_diagnostics=False, q_general="host", validation=False):
     """One configuration, several seeds, one process: each seed is the run ``experiment(variant, seed=s)`` would make --
     its own synthetic environments, collectors, weights and replay buffer -- and every epoch's training block is ONE
     SACTrainerGroup.train_loop (TD3 variants: TD3TrainerGroup; hidden sizes other than two layers of at most 256 units:
@@ -705,9 +781,13 @@ def experiment_group(variant, seeds, log_dir=None, num_epochs=None, obs_dim=None
     sac_gactor_act call, None: GroupActor's default); rows as experiment(..., acting="device_all").
     q_diagnostics=True: experiment()'s critic columns for every seed, all seeds' Q values from one q_values_many call per
     epoch; each seed's rows are those of experiment(variant, seed=s, q_diagnostics=True).  q_general as for experiment()
-    (general-step seeds: one sac_q_values_general_many call per 16 of them with "device")."""
+    (general-step seeds: one sac_q_values_general_many call per 16 of them with "device").
+    validation=True: experiment()'s validation/ columns for every seed, all seeds from one evaluate_many call per epoch;
+    each seed's rows are those of experiment(variant, seed=s, validation=True).  A TD3 variant is refused."""
     check_acting(acting)
     _check_general(q_general)
+    if validation:
+        _refuse_td3_validation(variant, "experiment_group")
     if resume and not checkpoint_dir:
         raise RuntimeError("experiment_group(resume=True) needs the checkpoint_dir to resume from")
     validate(variant)
@@ -733,7 +813,7 @@ def experiment_group(variant, seeds, log_dir=None, num_epochs=None, obs_dim=None
         train_block = lambda: group.train_loop([r["buf"] for r in runs], n_train, batch_size=ak["batch_size"])  # noqa: E731
     _group_epochs(runs, train_block,
                   num_epochs if num_epochs is not None else ak["num_epochs"], n_train, log_dir, quiet, "seeds", ck,
-                  first_epoch, acting, sessions, general_sessions, q_diagnostics, q_general)
+                  first_epoch, acting, sessions, general_sessions, q_diagnostics, q_general, validation)
     return {r["seed"]: r["rows"] for r in runs}
 
 
@@ -760,7 +840,7 @@ def sweep_label(variant, seed, hidden_sweep=False):
 
 def experiment_sweep(runs, log_dir=None, num_epochs=None, device=0, quiet=False, checkpoint_dir=None, resume=False,
                      chunk_rows=DEFAULT_CHUNK_ROWS, hidden_sweep=False, acting="host", sessions=True, general_sessions=None,
-                     q_diagnostics=False, q_general="host"):
+                     q_diagnostics=False, q_general="host", validation=False):
     """Several tasks x seeds, one process, one device: every entry of ``runs`` -- (variant, seed), or (variant, seed,
     obs_dim, action_dim) for a task without pinned dims -- is the run ``experiment(variant, seed=seed)`` would make, and
     every epoch's training block is ONE MixedSACTrainerGroup.train_loop (TD3 variants: MixedTD3TrainerGroup; hidden sizes
@@ -779,9 +859,13 @@ def experiment_sweep(runs, log_dir=None, num_epochs=None, device=0, quiet=False,
     "device_all" those runs act on the device inside the same ticks, and each run's rows are those of its solo
     experiment(..., acting="device_all").
     q_diagnostics as for experiment_group (the runs of the general step take q_values' host path inside the same call;
-    with q_general="device" they are evaluated on the device, one sac_q_values_general_many call per 16 of them)."""
+    with q_general="device" they are evaluated on the device, one sac_q_values_general_many call per 16 of them).
+    validation as for experiment_group (the runs of the general step take evaluate's host path inside the same call); TD3
+    sweeps are refused."""
     check_acting(acting)
     _check_general(q_general)
+    for spec in runs if validation else ():
+        _refuse_td3_validation(tuple(spec)[0], "experiment_sweep")
     if resume and not checkpoint_dir:
         raise RuntimeError("experiment_sweep(resume=True) needs the checkpoint_dir to resume from")
     specs = []
@@ -831,5 +915,5 @@ def experiment_sweep(runs, log_dir=None, num_epochs=None, device=0, quiet=False,
     batches = [r["ak"]["batch_size"] for r in group_runs]
     _group_epochs(group_runs, lambda: group.train_loop([r["buf"] for r in group_runs], n_train, batch_sizes=batches),
                   num_epochs if num_epochs is not None else ak0["num_epochs"], n_train, log_dir, quiet, "runs", ck,
-                  first_epoch, acting, sessions, general_sessions, q_diagnostics, q_general)
+                  first_epoch, acting, sessions, general_sessions, q_diagnostics, q_general, validation)
     return [r["rows"] for r in group_runs]

@@ -157,6 +157,53 @@ def q_values_many(trainers, obs_list, act_list, nets_list, general="host"):
     return out
 
 
+def evaluate_many(trainers, batches, eps=None, rngs=None, rows=False):
+    """SACTrainer.evaluate for many runs at once: result[i] = trainers[i].evaluate(batches[i], eps[i], rngs[i]) (eps / rngs:
+    one entry per trainer or None; batches[i] None or without rows: the member sits out and gets None).  The SAC members
+    with the fused kernels' shapes are served by ONE launch per 16 of them and 1024 rows (sac_evaluate_many: dims, hidden
+    sizes and row counts mixed); the others -- the general step, trainers without a handle -- go through their own
+    evaluate inside the same call (a TD3 member raises there).  A member's columns never depend on its neighbours: they
+    are bit for bit those of its own evaluate.  Results come back in member order; rows=True as for evaluate."""
+    trainers = list(trainers)
+    R = len(trainers)
+    eps = [None] * R if eps is None else list(eps)
+    rngs = [None] * R if rngs is None else list(rngs)
+    if not (len(batches) == len(eps) == len(rngs) == R):
+        raise RuntimeError("evaluate_many takes one batch (and eps pair, and rng) per trainer")
+    if len({id(t) for t in trainers}) != R:
+        raise RuntimeError("a trainer appears twice in evaluate_many")
+    out, arrs, chunks, alphas, dev = [None] * R, [None] * R, [None] * R, [1.0] * R, []
+    for i, t in enumerate(trainers):
+        b = batches[i]
+        if b is None or np.atleast_2d(b["observations"]).shape[0] == 0:
+            continue
+        if isinstance(t, TD3Trainer) or t._h is None or runs_general_step(t) or t._evaluate_on_host:
+            out[i] = t.evaluate(b, eps=eps[i], rng=rngs[i], rows=rows)
+            continue
+        arrs[i], chunks[i] = t._eval_inputs(b, eps[i], rngs[i]), []
+        dev.append(i)
+    lib = _lib.load() if dev else None
+    for r0 in range(0, max([arrs[i][0].shape[0] for i in dev], default=0), _lib.ACT_MAX_ROWS):
+        live = [i for i in dev if arrs[i][0].shape[0] > r0]
+        for c in range(0, len(live), MAX_MEMBERS):
+            ids = live[c:c + MAX_MEMBERS]
+            n = len(ids)
+            n_rows = [min(arrs[i][0].shape[0] - r0, _lib.ACT_MAX_ROWS) for i in ids]
+            made = [trainers[i]._eval_io(arrs[i], r0, r0 + k) for i, k in zip(ids, n_rows)]
+            ios = (_lib.SacEvalIO * n)(*[m[0] for m in made])
+            _lib.check(lib.sac_evaluate_many((C.c_void_p * n)(*[trainers[i]._h.value for i in ids]), n,
+                                             (C.c_int32 * n)(*n_rows), ios), "sac_evaluate_many")
+            for k, i in enumerate(ids):
+                chunks[i].append(made[k][1])
+                alphas[i] = float(ios[k].alpha)
+    from .sac import _eval_columns
+    for i in dev:
+        cols = _eval_columns(chunks[i], alphas[i])
+        stats = trainers[i]._eval_stats(cols)
+        out[i] = (stats, cols) if rows else stats
+    return out
+
+
 class _ActorSession:
     """One acting session (at most 16 members): its handle, the members' handles it was opened on, and the per-call
     argument arrays, made once.  entry: "sac_actor" (the fused kernels' shapes) or "sac_gactor" (the general step) --
@@ -379,6 +426,10 @@ class _Members:
         if nets_list is None:
             nets_list = [("qf1", "qf2")] * len(self.trainers)
         return q_values_many(self.trainers, obs_list, act_list, nets_list, general=general)
+
+    def evaluate_many(self, batches, eps=None, rngs=None, rows=False):
+        """evaluate_many over the group's members."""
+        return evaluate_many(self.trainers, batches, eps=eps, rngs=rngs, rows=rows)
 
 
 class _SACMembers:

@@ -16,6 +16,59 @@ from ._lib import DIAG_NAMES, NET_IDS, SacConfig
 from .networks import process_seed
 
 
+def eval_target(rew, term, tq1, tq2, log_pi_next, alpha, reward_scale, discount):
+    """k_eval's y in float32 NumPy, operation for operation:
+    y = rs * r + ((1 - d) * discount) * (min(tq1, tq2) - alpha * log_pi_next), each result rounded to float32."""
+    f = np.float32
+    rew, term, tq1, tq2, lp = (np.asarray(x, f) for x in (rew, term, tq1, tq2, log_pi_next))
+    return f(reward_scale) * rew + ((f(1.0) - term) * f(discount)) * (np.fmin(tq1, tq2) - f(alpha) * lp)
+
+
+def _eval_columns(chunks, alpha):
+    """The per-row columns of evaluate from its chunks' outputs (rows (9, k), mu, log_std, a_new, a_next (k, A))."""
+    cols = OrderedDict()
+    rows = np.concatenate([c["rows"] for c in chunks], axis=1)
+    for i, name in enumerate(_lib.EVAL_ROWS):
+        cols[name] = np.ascontiguousarray(rows[i])
+    for name in _lib.EVAL_ARRAYS:
+        cols[name] = np.concatenate([c[name] for c in chunks], axis=0)
+    cols["alpha"] = float(alpha)
+    return cols
+
+
+def eval_statistics(rows, mu, log_std, alpha, log_alpha, target_entropy, auto):
+    """The statistics of SACTrainer.evaluate from its per-row columns, on the host in float64: `rows` is the
+    (SAC_EVAL_ROWS_N, n) array q1, q2, q1_new, q2_new, tq1, tq2, log_pi, log_pi_next, y (_lib.EVAL_ROWS), mu / log_std the
+    policy head's (n, A) mean and clamped log_std.  An OrderedDict with get_diagnostics()' keys in their order --
+    QF Loss = mean((q - y)^2); Policy Loss = mean(log_pi - min(q1_new, q2_new)), the reference's logged form without
+    alpha; Mean / Std (np.std) / Max / Min of q1, q2, y, log_pi, mu, log_std; Alpha; Alpha Loss =
+    -mean(log_alpha * (log_pi + target_entropy)), 0 with tuning off -- followed by TD Error 1 / TD Error 2 Mean / Std /
+    Max / Min (q - y, signed)."""
+    r = [np.asarray(x, np.float64).ravel() for x in rows]
+    q1, q2, q1n, q2n, _, _, lp, _, y = r
+
+    def stats(d, name, x):
+        x = np.asarray(x, np.float64).ravel()
+        d[name + " Mean"], d[name + " Std"] = float(np.mean(x)), float(np.std(x))
+        d[name + " Max"], d[name + " Min"] = float(np.max(x)), float(np.min(x))
+
+    d = OrderedDict()
+    d["QF1 Loss"] = float(np.mean((q1 - y) ** 2))
+    d["QF2 Loss"] = float(np.mean((q2 - y) ** 2))
+    d["Policy Loss"] = float(np.mean(lp - np.minimum(q1n, q2n)))
+    stats(d, "Q1 Predictions", q1)
+    stats(d, "Q2 Predictions", q2)
+    stats(d, "Q Targets", y)
+    stats(d, "Log Pis", lp)
+    stats(d, "Policy mu", mu)
+    stats(d, "Policy log std", log_std)
+    d["Alpha"] = float(alpha)
+    d["Alpha Loss"] = float(-np.mean(float(log_alpha) * (lp + float(target_entropy)))) if auto else 0.0
+    stats(d, "TD Error 1", q1 - y)
+    stats(d, "TD Error 2", q2 - y)
+    return d
+
+
 class SACTrainer:
     def __init__(self, env=None, policy=None, qf1=None, qf2=None, target_qf1=None, target_qf2=None,
                  discount=0.99, reward_scale=1.0, policy_lr=1e-3, qf_lr=1e-3, optimizer_class=None,
@@ -358,6 +411,156 @@ class SACTrainer:
             _lib.check(fn(self._h, j - i, _lib.ptr(obs[i:j]), _lib.ptr(act[i:j]), mask, _lib.ptr(part)), entry)
             out[:, i:j] = part[rows]
         return out
+
+    # ---- evaluation on held-out transitions --------------------------------------------------
+    _evaluate_on_host = False        # private switch: the host path for a fused-shape trainer too (scripts/bench_evaluate.py
+                                     # measures the two paths of ONE trainer against each other)
+    _eval_rng = None                 # evaluate's private noise stream, made on first use
+
+    def _eval_inputs(self, batch, eps, rng):
+        """evaluate's arguments, checked before any library call: float32 obs, act, rew, term, next_obs, eps, eps_next."""
+        obs = _lib.f32(np.atleast_2d(batch["observations"]))
+        n = obs.shape[0]
+        act, nobs = _lib.f32(np.atleast_2d(batch["actions"])), _lib.f32(np.atleast_2d(batch["next_observations"]))
+        if n < 1 or obs.shape != (n, self.obs_dim) or nobs.shape != obs.shape or act.shape != (n, self.act_dim):
+            raise ValueError(f"evaluate: observations {obs.shape} / actions {act.shape} / next_observations {nobs.shape} "
+                             f"do not fit dims ({self.obs_dim}, {self.act_dim}) (at least one row)")
+        rew, term = (_lib.f32(np.asarray(batch[k]).reshape(-1)) for k in ("rewards", "terminals"))
+        if rew.shape != (n,) or term.shape != (n,):
+            raise ValueError(f"evaluate: {rew.size} rewards and {term.size} terminals for {n} rows")
+        if eps is None:
+            if rng is None:                          # a stream private to the trainer: np.random is never touched
+                if self._eval_rng is None:
+                    self._eval_rng = np.random.RandomState(
+                        [int(self.noise_seed & 0xFFFFFFFF), int(self.noise_seed >> 32), 0x4556414C])
+                rng = self._eval_rng
+            eps = (rng.standard_normal((n, self.act_dim)), rng.standard_normal((n, self.act_dim)))
+        e1, e2 = (_lib.f32(np.atleast_2d(e)) for e in eps)
+        if e1.shape != act.shape or e2.shape != act.shape:
+            raise ValueError(f"evaluate: eps {e1.shape} / eps_next {e2.shape} for actions {act.shape}")
+        return obs, act, rew, term, nobs, e1, e2
+
+    def _eval_io(self, arrs, i, j):
+        """sac_eval_io_t over rows i..j of evaluate's inputs, and the output arrays it points to."""
+        k, A = j - i, self.act_dim
+        out = dict(rows=np.empty((len(_lib.EVAL_ROWS), k), np.float32))
+        out.update((name, np.empty((k, A), np.float32)) for name in _lib.EVAL_ARRAYS)
+        parts = [np.ascontiguousarray(a[i:j]) for a in arrs]
+        io = _lib.SacEvalIO(*[p.ctypes.data for p in parts], out["rows"].ctypes.data,
+                            *[out[name].ctypes.data for name in _lib.EVAL_ARRAYS], 0.0)
+        return io, out, parts
+
+    def _evaluate_device(self, arrs):
+        n = arrs[0].shape[0]
+        chunks, alpha = [], 1.0
+        for i in range(0, n, _lib.ACT_MAX_ROWS):
+            j = min(n, i + _lib.ACT_MAX_ROWS)
+            io, out, _keep = self._eval_io(arrs, i, j)
+            _lib.check(self._lib.sac_evaluate(self._h, j - i, C.byref(io)), "sac_evaluate")
+            chunks.append(out)
+            alpha = float(io.alpha)
+        return _eval_columns(chunks, alpha)
+
+    def _host_net(self, name):
+        """[(W, b)] of one net from the current weights: sac_get_params, or the holder's arrays without a handle."""
+        flat = self._get_params(name) if self._h is not None else _lib.f32(getattr(self, name).flat())
+        sizes = self._hidden(name) + ([self.act_dim, self.act_dim] if name == "policy" else [1])
+        k = self.obs_dim if name == "policy" else self.obs_dim + self.act_dim
+        layers, off = [], 0
+        for l, n_out in enumerate(sizes):
+            layers.append((flat[off:off + n_out * k].reshape(n_out, k), flat[off + n_out * k:off + n_out * k + n_out]))
+            off += n_out * k + n_out
+            if l < len(self._hidden(name)):
+                k = n_out
+        assert off == flat.size
+        return layers
+
+    def _evaluate_host(self, arrs):
+        """The host path of evaluate: the nets' current weights (sac_sync, sac_get_params; the holders' own arrays while
+        the trainer has no handle yet), a float32 NumPy forward and the device path's y expression."""
+        obs, act, rew, term, nobs, e1, e2 = arrs
+        alpha = 1.0
+        if self._h is not None:
+            _lib.check(self._lib.sac_sync(self._h), "sac_sync")
+            if self.use_automatic_entropy_tuning:        # (as sac_evaluate: no alpha before the first step, exp(log_alpha))
+                sc = self._scalars()
+                alpha = float(sc[5]) if sc[5] > 0 else float(np.exp(np.float32(sc[0])))
+        elif self.use_automatic_entropy_tuning and self._saved_state is not None:
+            alpha = float(np.exp(np.float32(self._saved_state["scalars"][0])))
+        nets = {name: self._host_net(name) for name in NET_IDS}
+        f = np.float32
+
+        def hidden(h, layers):
+            for w, b in layers:
+                h = h @ w.T + b
+                h = np.where(h < 0, f(0), h)
+            return h
+
+        def q(name, s, a):
+            layers = nets[name]
+            h = hidden(np.concatenate([s, a], axis=1), layers[:-1])
+            return (h @ layers[-1][0].T + layers[-1][1])[:, 0]
+
+        def pi(s, e):
+            layers = nets["policy"]
+            h = hidden(s, layers[:-2])
+            mean = h @ layers[-2][0].T + layers[-2][1]
+            ls = np.clip(h @ layers[-1][0].T + layers[-1][1], f(-20.0), f(2.0))
+            std = np.exp(ls)
+            z = mean + std * e
+            a = np.tanh(z)
+            dd = z - mean
+            nlp = -(dd * dd) / (f(2.0) * (std * std)) - np.log(std) - f(0.91893853320467274178)
+            lp = nlp - np.log(f(1.0) - a * a + f(1e-6))
+            return a, mean, ls, lp.sum(axis=1, dtype=f)
+
+        with np.errstate(all="ignore"):
+            a_new, mu, log_std, log_pi = pi(obs, e1)
+            a_next, _, _, log_pi_next = pi(nobs, e2)
+            tq1, tq2 = q("target_qf1", nobs, a_next), q("target_qf2", nobs, a_next)
+            cols = dict(q1=q("qf1", obs, act), q2=q("qf2", obs, act), q1_new=q("qf1", obs, a_new),
+                        q2_new=q("qf2", obs, a_new), tq1=tq1, tq2=tq2, log_pi=log_pi, log_pi_next=log_pi_next,
+                        y=eval_target(rew, term, tq1, tq2, log_pi_next, alpha, self.reward_scale, self.discount))
+        out = dict(rows=np.stack([_lib.f32(cols[k]) for k in _lib.EVAL_ROWS]), mu=_lib.f32(mu), log_std=_lib.f32(log_std),
+                   a_new=_lib.f32(a_new), a_next=_lib.f32(a_next))
+        return _eval_columns([out], alpha)
+
+    def _scalars(self):
+        sc = np.zeros(6, np.float64)
+        _lib.check(self._lib.sac_get_scalars(self._h, _lib.ptr(sc)), "sac_get_scalars")
+        return sc
+
+    def _eval_log_alpha(self):
+        if self._h is not None:
+            return float(self._scalars()[0])
+        return float(self._saved_state["scalars"][0]) if self._saved_state is not None else 0.0
+
+    def _eval_stats(self, cols):
+        return eval_statistics(np.stack([cols[k] for k in _lib.EVAL_ROWS]), cols["mu"], cols["log_std"], cols["alpha"],
+                               self._eval_log_alpha(), self.target_entropy, self.use_automatic_entropy_tuning)
+
+    def evaluate(self, batch, eps=None, rng=None, rows=False):
+        """The SAC objectives of this run on `batch` WITHOUT a gradient step: `batch` is the dict train() takes
+        (observations, actions, rewards, terminals, next_observations; any n >= 1), typically transitions the run has not
+        trained on -- an epoch's evaluation paths.  From the LIVE weights and the CURRENT entropy coefficient: on the
+        device (sac_evaluate: k_eval, one launch per 1024 rows, no parameter copy); a trainer of the general step, which
+        the library's entry refuses, and a trainer without a handle take the host path -- sac_sync, sac_get_params, a
+        float32 NumPy forward.  Nothing the step reads is written either way, and the trainer's own statistics
+        (get_diagnostics, the step counters) are left alone.
+        eps: (eps, eps_next), the (n, A) N(0,1) draws of a_new and a_next; None: drawn as standard_normal((n, A)) twice
+        from `rng`, or from a RandomState private to the trainer (seeded from noise_seed) when that is None too --
+        np.random is never touched.
+        Returns an OrderedDict with get_diagnostics()' keys plus TD Error 1 / TD Error 2 Mean / Std / Max / Min (q - y,
+        signed): eval_statistics of the per-row columns.  The training step logs its values behind its own alpha update;
+        these are one alpha step earlier.  rows=True: (stats, columns), columns a dict of the float32 per-row arrays q1,
+        q2, q1_new, q2_new, tq1, tq2, log_pi, log_pi_next, y (n,), mu, log_std, a_new, a_next (n, A), and alpha."""
+        arrs = self._eval_inputs(batch, eps, rng)
+        if self._h is None or self.fused_mode() == 3 or self._evaluate_on_host:
+            cols = self._evaluate_host(arrs)
+        else:
+            cols = self._evaluate_device(arrs)
+        stats = self._eval_stats(cols)
+        return (stats, cols) if rows else stats
 
     def refresh_host_policy(self):
         """Mirror the trained policy D2H once per training block (acting stays on the host)."""

@@ -14,7 +14,9 @@
  host forward; grouped runs then collect their paths in lockstep.  --acting device_all: the same, and runs of any
  hidden sizes act on the device.  --q_diagnostics: every epoch, Q1 and Q2 on the evaluation paths from the live
  weights against the discounted returns obtained there: sixteen evaluation/ columns more in progress.csv.
- --q_general device: with --q_diagnostics, runs of any hidden sizes evaluate their critics on the device too)
+ --q_general device: with --q_diagnostics, runs of any hidden sizes evaluate their critics on the device too.
+ --validation: every epoch, the SAC losses, TD errors and targets on the evaluation paths' transitions -- held-out data
+ -- from the live weights: validation/ columns in progress.csv; SAC only)
 Runs the variant unchanged (batch size, lrs, tau, period, buffer size ... from the JSON) on the
 HIP library with a synthetic environment of the task's dimensions (robosuite is not installed)."""
 import argparse
@@ -68,6 +70,10 @@ if __name__ == "__main__":
                     help="with --q_diagnostics: where runs whose hidden sizes are beyond two layers of at most 256 units "
                          "evaluate qf1 and qf2 -- host (a parameter copy and a NumPy forward) or device (one HIP launch per "
                          "layer on the live weights); without --q_diagnostics it has no effect")
+    ap.add_argument("--validation", action="store_true",
+                    help="every epoch, evaluate the SAC objectives (QF losses, TD errors, Q targets, log pi, policy loss) on "
+                         "the transitions of the evaluation paths, which never enter the replay buffer (a HIP kernel on "
+                         "the live weights), and log them as validation/<key>; SAC only; off: progress.csv is unchanged")
     args = ap.parse_args()
     if (args.hidden_sweep or args.hidden_sizes) and not args.variants:
         raise SystemExit("--hidden_sweep / --hidden_sizes need --variants")
@@ -76,7 +82,7 @@ if __name__ == "__main__":
         if args.checkpoint and not log_dir:
             raise SystemExit("--checkpoint needs --log_dir (the group is saved to <log_dir>/checkpoint)")
         group_kw = dict(log_dir=log_dir, num_epochs=args.epochs, resume=bool(args.resume), acting=args.acting,
-                        q_diagnostics=args.q_diagnostics, q_general=args.q_general,
+                        q_diagnostics=args.q_diagnostics, q_general=args.q_general, validation=args.validation,
                         checkpoint_dir=os.path.join(log_dir, "checkpoint") if (args.checkpoint or args.resume) else None)
         try:
             if args.variants:
@@ -114,4 +120,4 @@ if __name__ == "__main__":
     ckpt = os.path.join(run_dir, "checkpoint") if (run_dir and not args.no_checkpoint) else None
     experiment(variant, log_dir=run_dir, seed=args.seed, num_epochs=args.epochs, checkpoint_dir=ckpt,
                resume=bool(args.resume), acting=args.acting, q_diagnostics=args.q_diagnostics,
-               q_general=args.q_general)
+               q_general=args.q_general, validation=args.validation)
