@@ -10,13 +10,10 @@
 //           is one member's layer l.  Launch l holds layer l of every member that has one; a member's head is its last
 //           layer, whatever the launch index.
 //   grid    one workgroup (4 waves) per 16-row x 64-column output tile of one job; wave w owns columns 16 w .. 16 w + 15
-//   GEMM    fp32 MFMA 16x16x4 over K in ascending chunks of AG_KC: the chunk's 16 input rows go through LDS, the weights
-//           come straight from global memory, 16 bytes per lane along K (one lane's four consecutive k feed four
-//           successive MFMAs, as in k_g_gemm); the next chunk's loads are in flight under this chunk's MFMAs.  Loads are
-//           unconditional from clamped indices, and what lies beyond K is zeroed in the edge chunk only (k_g_gemm's
-//           comments say why).  The reduction is never split across workgroups.
-//   hidden  bias, then x < 0 ? 0 : x (act_hidden_epilogue's ReLU: a NaN stays a NaN)
-//   head    at most 32 outputs: one column tile; bias, then through LDS --
+//   GEMM    infer_layer_tile<float, false> (sac_infer.h): fp32 MFMA 16x16x4 over K in ascending chunks of AG_KC.  The
+//           reduction is never split across workgroups.
+//   hidden  infer_layer_store: bias, then x < 0 ? 0 : x (a NaN stays a NaN)
+//   head    at most 32 outputs: one column tile; infer_layer_head: bias, then through LDS --
 //           SAC: tanh(mean) | tanh(mean + exp(clamp(log_std, -20, 2)) * eps);  TD3: tanh(last_fc)
 //
 // Row independence.  An output element is one MFMA chain over k in an order fixed by K alone (chunk, then the MFMA's index
@@ -32,13 +29,6 @@
 
 namespace sac {
 
-constexpr int AG_KC = 128;                // reduction chunk
-constexpr int AG_LD = AG_KC + 4;          // LDS row stride of the staged input rows
-constexpr int AG_NQ = AG_KC / 16;         // groups of four MFMAs per chunk
-constexpr int AG_XE = RB * AG_KC / 256;   // input values of a chunk per thread
-constexpr int AG_CT = 64;                 // columns of an output tile
-enum { AG_HIDDEN = 0, AG_SAC_MEAN = 1, AG_SAC_SAMPLE = 2, AG_TD3 = 3 };
-
 struct ActLayerJob {
     const float *W, *b;            // [N][K], [N]
     const float *X, *eps;          // input rows [n][K]; head of a stochastic SAC member: the N(0,1) draws [n][A]
@@ -50,8 +40,6 @@ struct ActLayerJob {
 __global__ __launch_bounds__(256) void k_act_layer(const ActLayerJob *__restrict__ tab, int n_jobs) {
     __shared__ __attribute__((aligned(16))) float Xs[RB * AG_LD];
     __shared__ float HL[RB * ACT_HEAD_LD];
-    typedef const __attribute__((address_space(1))) f32x4 *gvec;
-    typedef __attribute__((address_space(1))) float *gout;
     // this workgroup's job: the last one whose first workgroup is not behind this one (wave-uniform, scalar loads)
     int ji = 0;
     for (int i = 1; i < n_jobs; ++i)
@@ -63,109 +51,10 @@ __global__ __launch_bounds__(256) void k_act_layer(const ActLayerJob *__restrict
     const bool vec = sload(&J->vec) != 0;
     const int tile = (int)blockIdx.x - sload(&J->wg0);
     const int row0 = RB * (tile / tiles_n), n0 = AG_CT * (tile % tiles_n);
-    const int tid = threadIdx.x, wave = tid >> 6, lane = tid & 63, c = lane & 15, g = lane >> 4;
-    const int ncol = n0 + 16 * wave + c;
-    // this lane's weight row and this thread's input elements (chunk coordinates: row xr + 2 j, k = xk), both clamped
-    const unsigned wrow = (unsigned)min(ncol, N - 1) * (unsigned)K;
-    const int xk = tid & (AG_KC - 1), xr = tid >> 7;
-    unsigned xrow[AG_XE];
-#pragma unroll
-    for (int j = 0; j < AG_XE; ++j) xrow[j] = (unsigned)min(row0 + xr + 2 * j, n - 1) * (unsigned)K;
-    const float bias = ld1g(bp + min(ncol, N - 1));
-
-    f32x4 wn[AG_NQ], wc[AG_NQ];
-    float xn[AG_XE];
-    auto fetch = [&](int kc) {
-        if (kc + AG_KC <= K) {
-            if (vec) {
-#pragma unroll
-                for (int q = 0; q < AG_NQ; ++q) wn[q] = *(gvec)(uintptr_t)(W + (wrow + (unsigned)(kc + 16 * q + 4 * g)));
-            } else {
-#pragma unroll
-                for (int q = 0; q < AG_NQ; ++q)
-#pragma unroll
-                    for (int i = 0; i < 4; ++i) wn[q][i] = ld1g(W + (wrow + (unsigned)(kc + 16 * q + 4 * g + i)));
-            }
-#pragma unroll
-            for (int j = 0; j < AG_XE; ++j) xn[j] = ld1g(X + (xrow[j] + (unsigned)(kc + xk)));
-            return;
-        }
-        // the edge chunk: reduction indices clamped (zeroed by fix); whole vectors stay inside K (K % 4 == 0)
-        if (vec) {
-#pragma unroll
-            for (int q = 0; q < AG_NQ; ++q) wn[q] = *(gvec)(uintptr_t)(W + (wrow + (unsigned)min(kc + 16 * q + 4 * g, K - 4)));
-        } else {
-#pragma unroll
-            for (int q = 0; q < AG_NQ; ++q)
-#pragma unroll
-                for (int i = 0; i < 4; ++i) wn[q][i] = ld1g(W + (wrow + (unsigned)min(kc + 16 * q + 4 * g + i, K - 1)));
-        }
-#pragma unroll
-        for (int j = 0; j < AG_XE; ++j) xn[j] = ld1g(X + (xrow[j] + (unsigned)min(kc + xk, K - 1)));
-    };
-    // behind the loads' arrival: the reduction's zero padding, on both operands
-    auto fix = [&](int kc) {
-        if (kc + AG_KC <= K) return;
-#pragma unroll
-        for (int q = 0; q < AG_NQ; ++q)
-#pragma unroll
-            for (int i = 0; i < 4; ++i) if (kc + 16 * q + 4 * g + i >= K) wc[q][i] = 0.f;
-        if (kc + xk >= K) {
-#pragma unroll
-            for (int j = 0; j < AG_XE; ++j) xn[j] = 0.f;
-        }
-    };
-
-    f32x4 acc = {};
-    const int nS = (K + AG_KC - 1) / AG_KC;
-    fetch(0);
-    for (int s = 0; s < nS; ++s) {
-        const int kc = AG_KC * s;
-        if (s > 0) __syncthreads();
-#pragma unroll
-        for (int q = 0; q < AG_NQ; ++q) wc[q] = wn[q];
-        fix(kc);
-#pragma unroll
-        for (int j = 0; j < AG_XE; ++j) Xs[(xr + 2 * j) * AG_LD + xk] = xn[j];
-        __syncthreads();
-        if (s + 1 < nS) fetch(kc + AG_KC);
-        SB();
-#pragma unroll
-        for (int q = 0; q < AG_NQ; ++q) {
-            const f32x4 a = ld4(Xs + c * AG_LD + 16 * q + 4 * g);
-#pragma unroll
-            for (int i = 0; i < 4; ++i) acc = __builtin_amdgcn_mfma_f32_16x16x4f32(a[i], wc[q][i], acc, 0, 0, 0);
-        }
-        SB();
-    }
-
-    if (kind == AG_HIDDEN) {
-        float *Y = sload(&J->Y);
-#pragma unroll
-        for (int i = 0; i < 4; ++i) {
-            const int row = row0 + 4 * g + i;
-            const float v = acc[i] + bias;
-            if (row < n && ncol < N) *(gout)(uintptr_t)(Y + ((unsigned)row * (unsigned)N + (unsigned)ncol)) = v < 0.f ? 0.f : v;
-        }
-        return;
-    }
-    // the head (one column tile, kind is uniform over the workgroup): pre-activations through LDS, one thread per action
-    if (16 * wave < ACT_HEAD_LD) {
-#pragma unroll
-        for (int i = 0; i < 4; ++i) HL[(4 * g + i) * ACT_HEAD_LD + 16 * wave + c] = acc[i] + bias;
-    }
-    __syncthreads();
-    const int A = sload(&J->A);
-    const int r = tid >> 4, a = tid & 15;
-    if (a < A && row0 + r < n) {
-        const unsigned o = (unsigned)(row0 + r) * (unsigned)A + (unsigned)a;
-        float v = HL[r * ACT_HEAD_LD + a];
-        if (kind == AG_SAC_SAMPLE) {
-            const float ls = fminf(fmaxf(HL[r * ACT_HEAD_LD + A + a], LOG_SIG_MIN), LOG_SIG_MAX);
-            v += expf(ls) * ld1g(sload(&J->eps) + o);
-        }
-        *(gout)(uintptr_t)(sload(&J->Y) + o) = tanhf(v);
-    }
+    const int ncol = n0 + 16 * (threadIdx.x >> 6) + (threadIdx.x & 15);
+    const LayerTile t = infer_layer_tile<float, false>(Xs, W, bp, X, X, N, K, K, n, vec, row0, ncol);
+    if (kind == AG_HIDDEN) infer_layer_store(t, sload(&J->Y), N, n, row0, ncol, true);
+    else infer_layer_head(t, HL, J, kind, n, row0);
 }
 
 }  // namespace sac
@@ -189,49 +78,18 @@ int act_general_reserve(sac_trainer *t, size_t floats) {
 int sac_policy_act_general_many(sac_trainer_t *const *trainers, int n_trainers, const int32_t *n_rows, const float *const *obs,
                                 const int32_t *deterministic, const float *const *eps, float *const *act) {
     SAC_REQUIRE(trainers && n_rows && obs && deterministic && act, "bad arguments to sac_policy_act_general_many");
-    SAC_REQUIRE(n_trainers >= 1 && n_trainers <= SAC_GROUP_MAX, "sac_policy_act_general_many takes 1..%d trainers (got %d)",
-                SAC_GROUP_MAX, n_trainers);
-    // every refusal comes first: nothing has changed when one of them returns
-    bool stoch[SAC_GROUP_MAX];
-    int active = 0;
-    for (int i = 0; i < n_trainers; ++i) {
-        const sac_trainer *t = trainers[i];
-        SAC_REQUIRE(t, "trainer %d is null", i);
-        for (int j = 0; j < i; ++j) SAC_REQUIRE(trainers[j] != t, "trainer %d is trainer %d again", i, j);
-        SAC_REQUIRE(t->device == trainers[0]->device, "trainer %d lives on device %d, trainer 0 on device %d", i, t->device,
-                    trainers[0]->device);
-        SAC_REQUIRE(t->gen, "trainer %d has the fused kernels' shapes (two hidden layers of at most 256 units): "
-                    "sac_policy_act_device is its device acting entry, sac_policy_act_general serves the general step", i);
-        SAC_REQUIRE(t->xcd_mask == 0xffu, "trainer %d is confined by sac_trainer_set_xcd[_mask]: device acting launches on the "
-                    "whole chip", i);
-        SAC_REQUIRE(n_rows[i] >= 0 && n_rows[i] <= ACT_MAX_ROWS, "trainer %d: %d rows (0..%d per call, 0 = sits out)", i,
-                    (int)n_rows[i], ACT_MAX_ROWS);
-        stoch[i] = t->algo == 0 && !deterministic[i];
-        if (n_rows[i] == 0) continue;
-        active += 1;
-        SAC_REQUIRE(obs[i] && act[i], "trainer %d: null observations or actions", i);
-        SAC_REQUIRE(!stoch[i] || (eps && eps[i]), "trainer %d: stochastic acting needs the N(0,1) draws (eps)", i);
-    }
-    SAC_REQUIRE(active > 0, "no trainer has rows to act on");
+    const InferEntry E = {"sac_policy_act_general_many", true, false, "device acting",
+                          "sac_policy_act_device is its device acting entry, sac_policy_act_general serves the general step", "act on"};
+    bool stoch[SAC_GROUP_MAX] = {};
+    if (int rc = act_admit(E, trainers, n_trainers, n_rows, obs, deterministic, eps, act, stoch)) return rc;
     sac_trainer *t0 = trainers[0];
-    SAC_HIP(hipSetDevice(t0->device));
-    // the weights as of the last completed step of any step path: drain every member with rows
-    for (int i = 0; i < n_trainers; ++i)
-        if (n_rows[i] > 0 && sac_sync(trainers[i])) return -1;
-
-    const size_t tab_bytes = (sizeof(ActLayerJob) * SAC_GROUP_MAX * gen::GMAXL + 255) & ~(size_t)255;
-    size_t off[SAC_GROUP_MAX][3], bytes = tab_bytes;
+    size_t off[SAC_GROUP_MAX][3], bytes = infer_align(sizeof(ActLayerJob) * SAC_GROUP_MAX * gen::GMAXL);
+    act_carve(bytes, off, trainers, n_trainers, n_rows, stoch);
     int launches = 0;
     for (int i = 0; i < n_trainers; ++i) {
-        sac_trainer *t = trainers[i];
-        const size_t n = (size_t)n_rows[i];
-        const size_t part[3] = {n * t->O, stoch[i] ? n * t->A : 0, n * t->A};
-        for (int k = 0; k < 3; ++k) { off[i][k] = bytes; bytes += (sizeof(float) * part[k] + 255) & ~(size_t)255; }
-        if (n == 0) continue;
-        const GenNet &P = t->gen->net[SAC_NET_POLICY];
-        int widest = 1;
-        for (int l = 0; l + 1 < P.nl; ++l) widest = std::max(widest, P.L[l].N);
-        if (act_general_reserve(t, n * (size_t)widest)) return -1;
+        if (n_rows[i] == 0) continue;
+        const GenNet &P = trainers[i]->gen->net[SAC_NET_POLICY];
+        if (act_general_reserve(trainers[i], (size_t)n_rows[i] * infer_widest(P))) return -1;
         launches = std::max(launches, P.nl);
     }
     if (act_stage_reserve(t0, bytes)) return -1;
@@ -247,15 +105,13 @@ int sac_policy_act_general_many(sac_trainer_t *const *trainers, int n_trainers, 
             const GenLayer &L = P.L[l];
             const bool head = l + 1 == P.nl;
             ActLayerJob &J = tab[(size_t)l * SAC_GROUP_MAX + njobs[l]++];
-            J.W = P.P + L.offW; J.b = P.P + L.offB;
+            infer_layer_job(J, P, L);
             J.X = x;
             J.eps = reinterpret_cast<const float *>(S.d + off[i][1]);
             J.Y = head ? reinterpret_cast<float *>(S.d + off[i][2]) : t->act_gen[l & 1];
-            J.N = L.N; J.K = L.K; J.n = n_rows[i]; J.wg0 = blocks[l];
+            J.n = n_rows[i]; J.wg0 = blocks[l];
             J.kind = !head ? AG_HIDDEN : (t->algo == 1 ? AG_TD3 : (stoch[i] ? AG_SAC_SAMPLE : AG_SAC_MEAN));
-            J.tiles_n = (L.N + AG_CT - 1) / AG_CT;
             J.A = t->A;
-            J.vec = (L.K % 4 == 0 && L.offW % 4 == 0) ? 1 : 0;
             blocks[l] += ((n_rows[i] + RB - 1) / RB) * J.tiles_n;
             x = J.Y;
         }

@@ -18,11 +18,10 @@
 // when member 0 sits out and so was not drained: the tick then queues behind member 0's steps in flight (the result is
 // the same; a caller that wants the short latency keeps a member with rows in front).
 //
-// k_act_session is k_act (sac_act.h) line for line behind the prologue: the same workgroup mapping (one workgroup per
-// 16-row block of one member), LDS layout, WRing / gemm_ring GEMMs, act_hidden_epilogue and head, so every action element
-// is the same chain of operations and a session's actions are bit for bit sac_policy_act_device's.  The observations
-// are float64 in the slab (what the environments produce) and rounded to fp32 as they are loaded: a plain cast, round to
-// nearest even, the value of numpy's astype(float32) and of sac_buffer_add_f64.
+// Behind its prologue k_act_session calls what k_act (sac_act.h) calls, the pieces of sac_infer.h, on the same workgroup
+// mapping and LDS layout: a session's actions are bit for bit sac_policy_act_device's.  The observations are float64 in
+// the slab (what the environments produce) and rounded to fp32 as infer_fill loads them: a plain cast, round to nearest
+// even, the value of numpy's astype(float32) and of sac_buffer_add_f64.
 //
 // Net::P and the layer offsets.  A fused-shape trainer's networks live in its arena, allocated and laid out once in
 // trainer_build; no step path (the four-launch step, the fused step and its fall-back, the chained steps, the group
@@ -31,8 +30,6 @@
 // (one pointer compare per member).  What does end a table entry is the end of the handle itself: the members must
 // outlive the session (the Python GroupActor reopens its sessions when a trainer replaces its handle).
 #pragma once
-
-#include <atomic>
 
 namespace sac {
 
@@ -77,59 +74,13 @@ __global__ __launch_bounds__(256) void k_act_session(const ActEntry *__restrict_
     float *X1 = X0 + RB * KL0;           // [16][256]
     float *X2 = X1 + RB * H;             // [16][256]
     float *HL = X2 + RB * H;             // [16][32]
-    const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63, c = lane & 15, g = lane >> 4;
-
-    // weight requests of the first layer go out in front of the observation rows
-    WRing<4> r0;
-    r0.init(P + sload(&M->offW[0]), KP, 64 * wave, 16);
-    r0.fill(KP >> 4);
-    float bv0[4], bv1[4];
-    const float *b0 = P + sload(&M->offB[0]), *b1 = P + sload(&M->offB[1]);
-#pragma unroll
-    for (int t = 0; t < 4; ++t) { bv0[t] = b0[64 * wave + 16 * t + c]; bv1[t] = b1[64 * wave + 16 * t + c]; }
-    {   // observations of the row-block, float64 -> fp32; rows beyond n and columns beyond O are zero
-        const double *obs = sload(&M->obs);
-        for (int i = threadIdx.x; i < RB * KL0; i += 256) {
-            const int r = i / KL0, k = i - r * KL0;
-            X0[lds_off(r, k, KL0)] = (row0 + r < n && k < O) ? (float)obs[(size_t)(row0 + r) * O + k] : 0.f;
-        }
-    }
-    lds_barrier();
-    {
-        f32x4 acc[4] = {};
-        gemm_ring(r0, X0, KL0, KP >> 4, acc);
-        act_hidden_epilogue<4>(acc, 64 * wave, 16, bv0, X1, H);
-    }
-    WRing<4> r1;
-    r1.init(P + sload(&M->offW[1]), H, 64 * wave, 16);
-    r1.fill(H >> 4);
-    lds_barrier();
-    {
-        f32x4 acc[4] = {};
-        gemm_ring(r1, X1, H, H >> 4, acc);
-        act_hidden_epilogue<4>(acc, 64 * wave, 16, bv1, X2, H);
-    }
-    lds_barrier();
-    if (16 * wave < NH) {                // head rows 16 wave .. 16 wave + 15 (wave-uniform)
-        WRing<1> rh;
-        rh.init(P + sload(&M->offW[2]), H, 16 * wave, 16);
-        rh.fill(H >> 4);
-        const float bh = (P + sload(&M->offB[2]))[16 * wave + c];
-        f32x4 acc[1] = {};
-        gemm_ring(rh, X2, H, H >> 4, acc);
-#pragma unroll
-        for (int i = 0; i < 4; ++i) HL[(4 * g + i) * ACT_HEAD_LD + 16 * wave + c] = acc[0][i] + bh;
-    }
-    lds_barrier();
+    // (the observations are float64 in the slab: infer_fill rounds them)
+    infer_hidden(P, M->offW, M->offB, X0, KL0, KP, X1, X2, [&] { infer_fill(X0, KL0, row0, n, sload(&M->obs), O); });
+    infer_head(P, M->offW, M->offB, NH, X2, HL);
     const int r = threadIdx.x >> 4, a = threadIdx.x & 15;
     if (a < A && row0 + r < n) {
         const size_t o = (size_t)(row0 + r) * A + a;
-        float v = HL[r * ACT_HEAD_LD + a];
-        if (stochastic) {
-            const float ls = fminf(fmaxf(HL[r * ACT_HEAD_LD + A + a], LOG_SIG_MIN), LOG_SIG_MAX);
-            v += expf(ls) * sload(&M->eps)[o];
-        }
-        sload(&M->act)[o] = tanhf(v);
+        sload(&M->act)[o] = infer_action(HL, r, a, A, stochastic != 0, [&] { return sload(&M->eps)[o]; });
     }
 }
 
@@ -174,11 +125,8 @@ int actor_build(sac_actor *a, size_t bytes, int kp_max) {
     for (int i = 0; i < a->n; ++i) actor_entry(a, i, a->tab[i]);
     SAC_HIP(hipMemcpy(a->d_tab, a->tab, sizeof(a->tab), hipMemcpyHostToDevice));
     SAC_HIP(hipEventCreateWithFlags(&a->ev, hipEventDisableTiming));
-    if (act_lds_bytes(kp_max) > 48 * 1024 && !g_session_lds_raised[a->device & 63]) {
-        SAC_HIP(hipFuncSetAttribute(reinterpret_cast<const void *>(k_act_session), hipFuncAttributeMaxDynamicSharedMemorySize,
-                                    (int)act_lds_bytes(512)));
-        g_session_lds_raised[a->device & 63] = true;
-    }
+    if (infer_raise_lds(reinterpret_cast<const void *>(k_act_session), g_session_lds_raised, a->device, act_lds_bytes(kp_max),
+                        act_lds_bytes(512))) return -1;
     return 0;
 }
 
@@ -198,32 +146,17 @@ int sac_actor_create(sac_actor_t **out, sac_trainer_t *const *trainers, int n_tr
     SAC_REQUIRE(out, "null out pointer to sac_actor_create");
     *out = nullptr;
     SAC_REQUIRE(trainers && max_rows, "bad arguments to sac_actor_create");
-    SAC_REQUIRE(n_trainers >= 1 && n_trainers <= SAC_GROUP_MAX, "sac_actor_create takes 1..%d trainers (got %d)", SAC_GROUP_MAX,
-                n_trainers);
-    for (int i = 0; i < n_trainers; ++i) {
-        const sac_trainer *t = trainers[i];
-        SAC_REQUIRE(t, "trainer %d is null", i);
-        for (int j = 0; j < i; ++j) SAC_REQUIRE(trainers[j] != t, "trainer %d is trainer %d again", i, j);
-        SAC_REQUIRE(t->device == trainers[0]->device, "trainer %d lives on device %d, trainer 0 on device %d", i, t->device,
-                    trainers[0]->device);
-        SAC_REQUIRE(!t->gen, "trainer %d runs the general step (hidden sizes beyond two layers of at most 256 units): device "
-                    "acting serves the fused kernels' shapes, sac_policy_act is the acting path for this trainer", i);
-        SAC_REQUIRE(max_rows[i] >= 1 && max_rows[i] <= ACT_MAX_ROWS, "trainer %d: max_rows %d (1..%d)", i, (int)max_rows[i],
-                    ACT_MAX_ROWS);
-    }
+    const InferEntry E = {"sac_actor_create", false, false, "device acting", "sac_policy_act is the acting path", "act on"};
+    if (int rc = infer_admit_session(E, trainers, n_trainers, max_rows)) return rc;
     sac_actor *a = new sac_actor;
     a->device = trainers[0]->device;
     a->n = n_trainers;
-    size_t bytes = (sizeof(ActCtl) + 255) & ~(size_t)255;
+    const size_t bytes = infer_slab(sizeof(ActCtl), trainers, n_trainers, max_rows, a->off);
     int kp_max = 0;
     for (int i = 0; i < n_trainers; ++i) {
-        sac_trainer *t = trainers[i];
-        a->member[i] = t;
+        a->member[i] = trainers[i];
         a->max_rows[i] = max_rows[i];
-        const size_t rows = (size_t)max_rows[i];
-        const size_t part[3] = {sizeof(double) * rows * t->O, sizeof(float) * rows * t->A, sizeof(float) * rows * t->A};
-        for (int k = 0; k < 3; ++k) { a->off[i][k] = bytes; bytes += (part[k] + 255) & ~(size_t)255; }
-        kp_max = std::max(kp_max, t->KP);
+        kp_max = std::max(kp_max, trainers[i]->KP);
     }
     if (actor_build(a, bytes, kp_max)) { actor_free(a); return -1; }
     *out = a;
@@ -238,9 +171,7 @@ int sac_actor_destroy(sac_actor_t *a) {
 int sac_actor_arrays(sac_actor_t *a, int member, double **obs, float **eps, float **act) {
     SAC_REQUIRE(a, "null acting session");
     SAC_REQUIRE(member >= 0 && member < a->n, "sac_actor_arrays: member %d of %d", member, a->n);
-    if (obs) *obs = reinterpret_cast<double *>(a->slab_h + a->off[member][0]);
-    if (eps) *eps = reinterpret_cast<float *>(a->slab_h + a->off[member][1]);
-    if (act) *act = reinterpret_cast<float *>(a->slab_h + a->off[member][2]);
+    infer_slab_arrays(a->slab_h, a->off[member], obs, eps, act);
     return 0;
 }
 

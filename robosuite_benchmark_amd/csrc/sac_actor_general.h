@@ -19,13 +19,13 @@
 // layer depth on member 0's stream and waits for one event of its own.  As with sac_actor_act the launches go on member
 // 0's stream even when member 0 sits out.
 //
-// k_act_layer_session is k_act_layer (sac_act_general.h) line for line behind the prologue: the same tile mapping, AG_KC
-// chunking, clamped loads and fix, MFMA order, hidden epilogue and head, so every action element is the same chain of
-// operations and a session's actions are bit for bit sac_policy_act_general's.  The prologue reads the launch's wg0 row,
+// Behind its prologue k_act_layer_session runs k_act_layer's tile and epilogues (sac_act_general.h; infer_layer_tile,
+// infer_layer_store, infer_layer_head of sac_infer.h): a session's actions are bit for bit sac_policy_act_general's.
+// The prologue reads the launch's wg0 row,
 // n and stochastic with three 16-dword scalar loads issued together, picks the member with scalar compares and reads
 // that member's static job from device memory.  In launch 0 (template parameter F64) the input rows are float64 in the
-// slab and are rounded to fp32 on the way into LDS: a plain cast, round to nearest even, the value of numpy's
-// astype(float32).  The fp32 instance has exactly k_act_layer's loads.
+// slab (infer_layer_tile<double, false>) and are rounded to fp32 on the way into LDS: a plain cast, round to nearest
+// even, the value of numpy's astype(float32).  The fp32 instance is k_act_layer's.
 //
 // GenNet::P and the layer offsets.  A general-step trainer's networks live in sac_general::arena, which
 // gen_build_sac / gen_build_td3 (sac_general_host.h) allocate once and carve with a bump allocator; gen_shape_net, the
@@ -36,8 +36,6 @@
 // the end of the handle itself: the members must outlive the session (the Python GroupActor reopens its sessions when a
 // trainer replaces its handle).
 #pragma once
-
-#include <type_traits>
 
 namespace sac {
 
@@ -58,14 +56,10 @@ struct GActCtl {                   // per call, at the head of the slab
                                           // layer l share theirs with the next member; behind the last: the grid size)
 };
 
-__device__ __forceinline__ double ld1gd(const double *p) { return *(const __attribute__((address_space(1))) double *)(uintptr_t)p; }
-
 template <bool F64>
 __global__ __launch_bounds__(256) void k_act_layer_session(const GActJob *__restrict__ tab, const GActCtl *__restrict__ ctl, int l) {
     __shared__ __attribute__((aligned(16))) float Xs[RB * AG_LD];
     __shared__ float HL[RB * ACT_HEAD_LD];
-    typedef const __attribute__((address_space(1))) f32x4 *gvec;
-    typedef __attribute__((address_space(1))) float *gout;
     typedef typename std::conditional<F64, double, float>::type xin_t;
     // this workgroup's member: the last one whose first workgroup is not behind this one (wave-uniform; the three arrays
     // come over the link in one go: three 16-dword scalar loads); a member without a job here is passed over
@@ -85,112 +79,10 @@ __global__ __launch_bounds__(256) void k_act_layer_session(const GActJob *__rest
     const bool vec = sload(&J->vec) != 0;
     const int tile = (int)blockIdx.x - wg0;
     const int row0 = RB * (tile / tiles_n), n0 = AG_CT * (tile % tiles_n);
-    const int tid = threadIdx.x, wave = tid >> 6, lane = tid & 63, c = lane & 15, g = lane >> 4;
-    const int ncol = n0 + 16 * wave + c;
-    // this lane's weight row and this thread's input elements (chunk coordinates: row xr + 2 j, k = xk), both clamped
-    const unsigned wrow = (unsigned)min(ncol, N - 1) * (unsigned)K;
-    const int xk = tid & (AG_KC - 1), xr = tid >> 7;
-    unsigned xrow[AG_XE];
-#pragma unroll
-    for (int j = 0; j < AG_XE; ++j) xrow[j] = (unsigned)min(row0 + xr + 2 * j, n - 1) * (unsigned)K;
-    const float bias = ld1g(bp + min(ncol, N - 1));
-    auto ldx = [&](unsigned i) -> xin_t {
-        if constexpr (F64) return ld1gd(X + i); else return ld1g(X + i);
-    };
-
-    f32x4 wn[AG_NQ], wc[AG_NQ];
-    xin_t xn[AG_XE];                   // (float64 rows stay float64 until they go into LDS: the loads stay in flight)
-    auto fetch = [&](int kc) {
-        if (kc + AG_KC <= K) {
-            if (vec) {
-#pragma unroll
-                for (int q = 0; q < AG_NQ; ++q) wn[q] = *(gvec)(uintptr_t)(W + (wrow + (unsigned)(kc + 16 * q + 4 * g)));
-            } else {
-#pragma unroll
-                for (int q = 0; q < AG_NQ; ++q)
-#pragma unroll
-                    for (int i = 0; i < 4; ++i) wn[q][i] = ld1g(W + (wrow + (unsigned)(kc + 16 * q + 4 * g + i)));
-            }
-#pragma unroll
-            for (int j = 0; j < AG_XE; ++j) xn[j] = ldx(xrow[j] + (unsigned)(kc + xk));
-            return;
-        }
-        // the edge chunk: reduction indices clamped (zeroed by fix); whole vectors stay inside K (K % 4 == 0)
-        if (vec) {
-#pragma unroll
-            for (int q = 0; q < AG_NQ; ++q) wn[q] = *(gvec)(uintptr_t)(W + (wrow + (unsigned)min(kc + 16 * q + 4 * g, K - 4)));
-        } else {
-#pragma unroll
-            for (int q = 0; q < AG_NQ; ++q)
-#pragma unroll
-                for (int i = 0; i < 4; ++i) wn[q][i] = ld1g(W + (wrow + (unsigned)min(kc + 16 * q + 4 * g + i, K - 1)));
-        }
-#pragma unroll
-        for (int j = 0; j < AG_XE; ++j) xn[j] = ldx(xrow[j] + (unsigned)min(kc + xk, K - 1));
-    };
-    // behind the loads' arrival: the reduction's zero padding, on both operands
-    auto fix = [&](int kc) {
-        if (kc + AG_KC <= K) return;
-#pragma unroll
-        for (int q = 0; q < AG_NQ; ++q)
-#pragma unroll
-            for (int i = 0; i < 4; ++i) if (kc + 16 * q + 4 * g + i >= K) wc[q][i] = 0.f;
-        if (kc + xk >= K) {
-#pragma unroll
-            for (int j = 0; j < AG_XE; ++j) xn[j] = 0;
-        }
-    };
-
-    f32x4 acc = {};
-    const int nS = (K + AG_KC - 1) / AG_KC;
-    fetch(0);
-    for (int s = 0; s < nS; ++s) {
-        const int kc = AG_KC * s;
-        if (s > 0) __syncthreads();
-#pragma unroll
-        for (int q = 0; q < AG_NQ; ++q) wc[q] = wn[q];
-        fix(kc);
-#pragma unroll
-        for (int j = 0; j < AG_XE; ++j) Xs[(xr + 2 * j) * AG_LD + xk] = (float)xn[j];
-        __syncthreads();
-        if (s + 1 < nS) fetch(kc + AG_KC);
-        SB();
-#pragma unroll
-        for (int q = 0; q < AG_NQ; ++q) {
-            const f32x4 a = ld4(Xs + c * AG_LD + 16 * q + 4 * g);
-#pragma unroll
-            for (int i = 0; i < 4; ++i) acc = __builtin_amdgcn_mfma_f32_16x16x4f32(a[i], wc[q][i], acc, 0, 0, 0);
-        }
-        SB();
-    }
-
-    if (kind == AG_HIDDEN) {
-        float *Y = sload(&J->Y);
-#pragma unroll
-        for (int i = 0; i < 4; ++i) {
-            const int row = row0 + 4 * g + i;
-            const float v = acc[i] + bias;
-            if (row < n && ncol < N) *(gout)(uintptr_t)(Y + ((unsigned)row * (unsigned)N + (unsigned)ncol)) = v < 0.f ? 0.f : v;
-        }
-        return;
-    }
-    // the head (one column tile, kind is uniform over the workgroup): pre-activations through LDS, one thread per action
-    if (16 * wave < ACT_HEAD_LD) {
-#pragma unroll
-        for (int i = 0; i < 4; ++i) HL[(4 * g + i) * ACT_HEAD_LD + 16 * wave + c] = acc[i] + bias;
-    }
-    __syncthreads();
-    const int A = sload(&J->A);
-    const int r = tid >> 4, a = tid & 15;
-    if (a < A && row0 + r < n) {
-        const unsigned o = (unsigned)(row0 + r) * (unsigned)A + (unsigned)a;
-        float v = HL[r * ACT_HEAD_LD + a];
-        if (kind == AG_SAC_SAMPLE) {
-            const float ls = fminf(fmaxf(HL[r * ACT_HEAD_LD + A + a], LOG_SIG_MIN), LOG_SIG_MAX);
-            v += expf(ls) * ld1g(sload(&J->eps) + o);
-        }
-        *(gout)(uintptr_t)(sload(&J->Y) + o) = tanhf(v);
-    }
+    const int ncol = n0 + 16 * (threadIdx.x >> 6) + (threadIdx.x & 15);
+    const LayerTile t = infer_layer_tile<xin_t, false>(Xs, W, bp, X, X, N, K, K, n, vec, row0, ncol);
+    if (kind == AG_HIDDEN) infer_layer_store(t, sload(&J->Y), N, n, row0, ncol, true);
+    else infer_layer_head(t, HL, J, kind, n, row0);
 }
 
 }  // namespace sac
@@ -210,12 +102,6 @@ struct sac_gactor {
 
 namespace {
 
-int gactor_widest(const GenNet &P) {
-    int widest = 1;
-    for (int l = 0; l + 1 < P.nl; ++l) widest = std::max(widest, P.L[l].N);
-    return widest;
-}
-
 // the session's allocations: the slab, the scratch, the device table (written here, once), the event
 int gactor_build(sac_gactor *a, size_t slab_bytes) {
     SAC_HIP(hipSetDevice(a->device));
@@ -224,7 +110,7 @@ int gactor_build(sac_gactor *a, size_t slab_bytes) {
     memset(a->slab_h, 0, slab_bytes);
     size_t buf[SAC_GROUP_MAX], floats = 0;             // floats of ONE of member i's two buffers (a multiple of 64)
     for (int i = 0; i < a->n; ++i) {
-        buf[i] = ((size_t)a->max_rows[i] * gactor_widest(a->member[i]->gen->net[SAC_NET_POLICY]) + 63) & ~(size_t)63;
+        buf[i] = ((size_t)a->max_rows[i] * infer_widest(a->member[i]->gen->net[SAC_NET_POLICY]) + 63) & ~(size_t)63;
         floats += 2 * buf[i];
     }
     SAC_HIP(hipMalloc(reinterpret_cast<void **>(&a->scratch), sizeof(float) * floats));
@@ -241,14 +127,11 @@ int gactor_build(sac_gactor *a, size_t slab_bytes) {
             const GenLayer &L = P.L[l];
             const bool head = l + 1 == P.nl;
             GActJob &J = a->tab[l][i];
-            J.W = P.P + L.offW; J.b = P.P + L.offB;
+            infer_layer_job(J, P, L);
             J.X = x;
             J.eps = reinterpret_cast<const float *>(a->slab_d + a->off[i][1]);
             J.Y = head ? reinterpret_cast<float *>(a->slab_d + a->off[i][2]) : pp[l & 1];
-            J.N = L.N; J.K = L.K;
-            J.tiles_n = (L.N + AG_CT - 1) / AG_CT;
             J.A = t->A;
-            J.vec = (L.K % 4 == 0 && L.offW % 4 == 0) ? 1 : 0;
             J.kind = !head ? AG_HIDDEN : (t->algo == 1 ? AG_TD3 : AG_SAC_MEAN);
             J.live = 1;
             x = J.Y;
@@ -277,30 +160,16 @@ int sac_gactor_create(sac_gactor_t **out, sac_trainer_t *const *trainers, int n_
     SAC_REQUIRE(out, "null out pointer to sac_gactor_create");
     *out = nullptr;
     SAC_REQUIRE(trainers && max_rows, "bad arguments to sac_gactor_create");
-    SAC_REQUIRE(n_trainers >= 1 && n_trainers <= SAC_GROUP_MAX, "sac_gactor_create takes 1..%d trainers (got %d)", SAC_GROUP_MAX,
-                n_trainers);
-    for (int i = 0; i < n_trainers; ++i) {
-        const sac_trainer *t = trainers[i];
-        SAC_REQUIRE(t, "trainer %d is null", i);
-        for (int j = 0; j < i; ++j) SAC_REQUIRE(trainers[j] != t, "trainer %d is trainer %d again", i, j);
-        SAC_REQUIRE(t->device == trainers[0]->device, "trainer %d lives on device %d, trainer 0 on device %d", i, t->device,
-                    trainers[0]->device);
-        SAC_REQUIRE(t->gen, "trainer %d has the fused kernels' shapes (two hidden layers of at most 256 units): sac_actor_create "
-                    "makes its acting sessions, sac_gactor_create serves the general step", i);
-        SAC_REQUIRE(max_rows[i] >= 1 && max_rows[i] <= ACT_MAX_ROWS, "trainer %d: max_rows %d (1..%d)", i, (int)max_rows[i],
-                    ACT_MAX_ROWS);
-    }
+    const InferEntry E = {"sac_gactor_create", true, false, "device acting",
+                          "sac_actor_create makes its acting sessions, sac_gactor_create serves the general step", "act on"};
+    if (int rc = infer_admit_session(E, trainers, n_trainers, max_rows)) return rc;
     sac_gactor *a = new sac_gactor;
     a->device = trainers[0]->device;
     a->n = n_trainers;
-    size_t bytes = (sizeof(GActCtl) + 255) & ~(size_t)255;
+    const size_t bytes = infer_slab(sizeof(GActCtl), trainers, n_trainers, max_rows, a->off);
     for (int i = 0; i < n_trainers; ++i) {
-        sac_trainer *t = trainers[i];
-        a->member[i] = t;
+        a->member[i] = trainers[i];
         a->max_rows[i] = max_rows[i];
-        const size_t rows = (size_t)max_rows[i];
-        const size_t part[3] = {sizeof(double) * rows * t->O, sizeof(float) * rows * t->A, sizeof(float) * rows * t->A};
-        for (int k = 0; k < 3; ++k) { a->off[i][k] = bytes; bytes += (part[k] + 255) & ~(size_t)255; }
     }
     if (gactor_build(a, bytes)) { gactor_free(a); return -1; }
     *out = a;
@@ -315,9 +184,7 @@ int sac_gactor_destroy(sac_gactor_t *a) {
 int sac_gactor_arrays(sac_gactor_t *a, int member, double **obs, float **eps, float **act) {
     SAC_REQUIRE(a, "null acting session");
     SAC_REQUIRE(member >= 0 && member < a->n, "sac_gactor_arrays: member %d of %d", member, a->n);
-    if (obs) *obs = reinterpret_cast<double *>(a->slab_h + a->off[member][0]);
-    if (eps) *eps = reinterpret_cast<float *>(a->slab_h + a->off[member][1]);
-    if (act) *act = reinterpret_cast<float *>(a->slab_h + a->off[member][2]);
+    infer_slab_arrays(a->slab_h, a->off[member], obs, eps, act);
     return 0;
 }
 

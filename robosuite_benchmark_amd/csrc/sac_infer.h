@@ -1,0 +1,441 @@
+// The forward pass of the device inference kernels, once (included by sac_trainer.hip in front of sac_act.h).
+//
+// Seven kernels run a network forward on live weights without training: k_act, k_act_session, k_qval, k_eval (the fused
+// kernels' shapes: one workgroup carries a 16-row block through a whole net in LDS) and k_act_layer,
+// k_act_layer_session<F64>, k_qval_layer (general shapes: one launch per layer, one workgroup per 16 x 64 output tile).
+// Each of them is a prologue that finds its member or job, calls into the pieces below, and an epilogue of its own.
+// Every bit-for-bit promise between them -- a session's actions are the device call's, k_eval's Q values are k_qval's
+// and its actions k_act's -- holds because they run THESE functions, not copies of them.  A new inference kernel
+// composes the same pieces; it does not paste a body.
+//
+//   fused shapes     infer_member, infer_fill, infer_hidden, infer_head, infer_q_out, infer_action
+//   general shapes   infer_layer_tile, infer_layer_store, infer_layer_head (infer_action again)
+//   host             infer_admit / infer_admit_session (the refusals), infer_carve / infer_slab (staging and slab layout),
+//                    infer_raise_lds, infer_widest / infer_layer_job (per-layer job tables)
+#pragma once
+
+#include <atomic>
+#include <type_traits>
+
+namespace sac {
+
+constexpr int ACT_MAX_ROWS = 1024;        // rows per member and call
+constexpr int ACT_HEAD_LD = 32;           // head pre-activations [16][32]: mean | log_std (A <= 16)
+
+// ---- fused shapes: two hidden layers of at most 256 units, padded to 256, weights in Net::P (fragment-major) ----
+
+// The hidden layers' bias + ReLU.  It stands in for the step kernels' hidden_epilogue, whose ReLU is
+// fmaxf(x, 0): that gives 0 for NaN and would turn a non-finite observation row into a finite action, where torch's relu
+// and the host forward keep the NaN.  Here x < 0 ? 0 : x; every finite value comes out as from fmaxf, up to the sign of
+// a zero, which no sum downstream can see.  With hidden sizes below 256 an Inf observation becomes NaN already in the
+// zero-weight pad units (0 * inf) and from there in every unit of the next layer; torch has no pad units but reaches NaN
+// in its second layer too, through inf - inf over units of both signs, so the actions agree (NaN) all the same.
+template <int NT>
+__device__ __forceinline__ void act_hidden_epilogue(const f32x4 (&acc)[NT], int n_base, int n_stride, const float (&bv)[NT],
+                                                    float *Xn, int KL) {
+    const int lane = threadIdx.x & 63, c = lane & 15, g = lane >> 4;
+#pragma unroll
+    for (int t = 0; t < NT; ++t) {
+        const int n = n_base + t * n_stride + c;
+#pragma unroll
+        for (int i = 0; i < 4; ++i) {
+            const float v = acc[t][i] + bv[t];
+            Xn[lds_off(4 * g + i, n, KL)] = v < 0.f ? 0.f : v;
+        }
+    }
+}
+
+// this workgroup's member of a per-member table: the last one whose first workgroup (the field wg0) is not behind this
+// workgroup (wave-uniform, scalar loads)
+template <class M>
+__device__ __forceinline__ int infer_member(const M *tab, int n_members, int M::*wg0) {
+    int mi = 0;
+    for (int i = 1; i < n_members; ++i)
+        if ((int)blockIdx.x >= sload(&(tab[i].*wg0))) mi = i;
+    return mi;
+}
+
+// the row-block's input X0 [16][KL0]: observations (float, or double rounded by a plain cast) in columns 0..O-1, with
+// A > 0 the actions in columns KP..KP+A-1; the other columns and the rows beyond n are zero
+template <class T>
+__device__ __forceinline__ void infer_fill(float *X0, int KL0, int row0, int n, const T *obs, int O,
+                                           const float *act = nullptr, int KP = 0, int A = 0) {
+    for (int i = threadIdx.x; i < RB * KL0; i += 256) {
+        const int r = i / KL0, k = i - r * KL0;
+        float v = 0.f;
+        if (row0 + r < n) {
+            if (k < O) v = (float)obs[(size_t)(row0 + r) * O + k];
+            else if (k >= KP && k < KP + A) v = act[(size_t)(row0 + r) * A + (k - KP)];
+        }
+        X0[lds_off(r, k, KL0)] = v;
+    }
+}
+
+// two hidden layers of one net on the row-block in X0: X2 = relu(W1 relu(W0 X0 + b0) + b1).  Wave w owns hidden units
+// 64 w .. 64 w + 63 of both layers.  The first layer's weight requests and both layers' biases go out in front of
+// fill(), which writes X0 (or nothing, where X0 is in place already); the first barrier stands behind it: X0 is
+// complete and a previous net's readers of X1 / X2 are through.  Ends behind a barrier.
+template <class Fill>
+__device__ __forceinline__ void infer_hidden(const float *P, const long long *offW, const long long *offB, const float *X0,
+                                             int KL0, int K0, float *X1, float *X2, Fill fill) {
+    const int wave = threadIdx.x >> 6, c = threadIdx.x & 15;
+    WRing<4> r0;
+    r0.init(P + sload(&offW[0]), K0, 64 * wave, 16);
+    r0.fill(K0 >> 4);
+    float bv0[4], bv1[4];
+    const float *b0 = P + sload(&offB[0]), *b1 = P + sload(&offB[1]);
+#pragma unroll
+    for (int t = 0; t < 4; ++t) { bv0[t] = b0[64 * wave + 16 * t + c]; bv1[t] = b1[64 * wave + 16 * t + c]; }
+    fill();
+    lds_barrier();
+    {
+        f32x4 acc[4] = {};
+        gemm_ring(r0, X0, KL0, K0 >> 4, acc);
+        act_hidden_epilogue<4>(acc, 64 * wave, 16, bv0, X1, H);
+    }
+    WRing<4> r1;
+    r1.init(P + sload(&offW[1]), H, 64 * wave, 16);
+    r1.fill(H >> 4);
+    lds_barrier();
+    {
+        f32x4 acc[4] = {};
+        gemm_ring(r1, X1, H, H >> 4, acc);
+        act_hidden_epilogue<4>(acc, 64 * wave, 16, bv1, X2, H);
+    }
+    lds_barrier();
+}
+
+// the policy head's pre-activations into HL [16][ACT_HEAD_LD]: wave w owns head rows 16 w .. 16 w + 15 of the NH padded
+// ones (wave-uniform).  Ends behind a barrier.
+__device__ __forceinline__ void infer_head(const float *P, const long long *offW, const long long *offB, int NH,
+                                           const float *X2, float *HL) {
+    const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63, c = lane & 15, g = lane >> 4;
+    if (16 * wave < NH) {
+        WRing<1> rh;
+        rh.init(P + sload(&offW[2]), H, 16 * wave, 16);
+        rh.fill(H >> 4);
+        const float bh = (P + sload(&offB[2]))[16 * wave + c];
+        f32x4 acc[1] = {};
+        gemm_ring(rh, X2, H, H >> 4, acc);
+#pragma unroll
+        for (int i = 0; i < 4; ++i) HL[(4 * g + i) * ACT_HEAD_LD + 16 * wave + c] = acc[0][i] + bh;
+    }
+    lds_barrier();
+}
+
+// the Q output unit (row 0 of the padded last layer: wave 0, one tile, column c == 0) into QL [16].  Ends behind a barrier.
+__device__ __forceinline__ void infer_q_out(const float *P, const long long *offW, const long long *offB, const float *X2,
+                                            float *QL) {
+    const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63, c = lane & 15, g = lane >> 4;
+    if (wave == 0) {
+        WRing<1> rq;
+        rq.init(P + sload(&offW[2]), H, 0, 16);
+        rq.fill(H >> 4);
+        const float bq = (P + sload(&offB[2]))[c];
+        f32x4 acc[1] = {};
+        gemm_ring(rq, X2, H, H >> 4, acc);
+        if (c == 0) {
+#pragma unroll
+            for (int i = 0; i < 4; ++i) QL[4 * g + i] = acc[0][i] + bq;
+        }
+    }
+    lds_barrier();
+}
+
+__device__ __forceinline__ float infer_log_std(float raw) { return fminf(fmaxf(raw, LOG_SIG_MIN), LOG_SIG_MAX); }
+
+// action a of row r from the head tile HL: tanh(mean), or with `stochastic` tanh(mean + exp(clamp(log_std)) * eps());
+// eps is called only then.  *pre gets the value under the tanh.
+template <class Eps>
+__device__ __forceinline__ float infer_action(const float *HL, int r, int a, int A, bool stochastic, Eps eps,
+                                              float *pre = nullptr) {
+    float v = HL[r * ACT_HEAD_LD + a];
+    if (stochastic) v += expf(infer_log_std(HL[r * ACT_HEAD_LD + A + a])) * eps();
+    if (pre) *pre = v;
+    return tanhf(v);
+}
+
+// ---- general shapes: nn.Linear layout W [N][K] then b, one launch per layer ----
+
+constexpr int AG_KC = 128;                // reduction chunk
+constexpr int AG_LD = AG_KC + 4;          // LDS row stride of the staged input rows
+constexpr int AG_NQ = AG_KC / 16;         // groups of four MFMAs per chunk
+constexpr int AG_XE = RB * AG_KC / 256;   // input values of a chunk per thread
+constexpr int AG_CT = 64;                 // columns of an output tile
+enum { AG_HIDDEN = 0, AG_SAC_MEAN = 1, AG_SAC_SAMPLE = 2, AG_TD3 = 3 };
+
+__device__ __forceinline__ double ld1gd(const double *p) { return *(const __attribute__((address_space(1))) double *)(uintptr_t)p; }
+
+struct LayerTile { f32x4 acc; float bias; };       // this lane's four rows (4 g + i) of column ncol, and that column's bias
+
+// One 16-row x 64-column tile of X W^T: rows row0 .. row0 + 15 of the n input rows, wave w's lane column
+// ncol = n0 + 16 w + c.  fp32 MFMA 16x16x4 over K in ascending chunks of AG_KC: the chunk's 16 input rows go through LDS
+// (Xs [16][AG_LD]), the weights come straight from global memory, 16 bytes per lane along K where `vec` allows it (one
+// lane's four consecutive k feed four successive MFMAs, as in k_g_gemm); the next chunk's loads are in flight under
+// this chunk's MFMAs.  Loads are unconditional from clamped indices -- rows beyond n repeat row n - 1, columns beyond N
+// column N - 1 -- and what lies beyond K is zeroed in the edge chunk only (k_g_gemm's comments say why).
+//   T       the input rows' element type: float, or double, which stays double until it goes into LDS (the loads stay
+//           in flight) and is rounded there by a plain cast
+//   SPLIT   two sources: element k of row r is X[r K1 + k] for k < K1 and X2[r (K - K1) + k - K1] otherwise, both loaded
+//           from clamped indices, then a select.  Without it K1 and X2 are unused and the loads are X's alone.
+template <class T, bool SPLIT>
+__device__ __forceinline__ LayerTile infer_layer_tile(float *Xs, const float *W, const float *bp, const T *X, const T *X2,
+                                                      int N, int K, int K1, int n, bool vec, int row0, int ncol) {
+    typedef const __attribute__((address_space(1))) f32x4 *gvec;
+    const int tid = threadIdx.x, lane = tid & 63, c = lane & 15, g = lane >> 4;
+    // this lane's weight row and this thread's input elements (chunk coordinates: row xr + 2 j, k = xk), both clamped
+    const unsigned wrow = (unsigned)min(ncol, N - 1) * (unsigned)K;
+    const int xk = tid & (AG_KC - 1), xr = tid >> 7;
+    const int K2 = K - K1, k2max = max(K2 - 1, 0);
+    unsigned xrow[AG_XE], xrow2[AG_XE];
+#pragma unroll
+    for (int j = 0; j < AG_XE; ++j) {
+        const unsigned r = (unsigned)min(row0 + xr + 2 * j, n - 1);
+        xrow[j] = r * (unsigned)(SPLIT ? K1 : K);
+        if constexpr (SPLIT) xrow2[j] = r * (unsigned)K2;
+    }
+    LayerTile t;
+    t.bias = ld1g(bp + min(ncol, N - 1));
+    auto ldx = [](const T *p) -> T {
+        if constexpr (std::is_same<T, double>::value) return ld1gd(p); else return ld1g(p);
+    };
+
+    f32x4 wn[AG_NQ], wc[AG_NQ];
+    T xn[AG_XE];
+    // the chunk's input elements (k beyond K is zeroed by fix)
+    auto fetch_x = [&](int kc, bool full) {
+        const int k = kc + xk;
+        if constexpr (SPLIT) {
+            const unsigned k1 = (unsigned)min(k, K1 - 1), k2 = (unsigned)min(max(k - K1, 0), k2max);
+#pragma unroll
+            for (int j = 0; j < AG_XE; ++j) {
+                const T a = ldx(X + (xrow[j] + k1)), b = ldx(X2 + (xrow2[j] + k2));
+                xn[j] = k < K1 ? a : b;
+            }
+        } else {
+#pragma unroll
+            for (int j = 0; j < AG_XE; ++j) xn[j] = ldx(X + (xrow[j] + (unsigned)(full ? k : min(k, K - 1))));
+        }
+    };
+    auto fetch = [&](int kc) {
+        if (kc + AG_KC <= K) {
+            if (vec) {
+#pragma unroll
+                for (int q = 0; q < AG_NQ; ++q) wn[q] = *(gvec)(uintptr_t)(W + (wrow + (unsigned)(kc + 16 * q + 4 * g)));
+            } else {
+#pragma unroll
+                for (int q = 0; q < AG_NQ; ++q)
+#pragma unroll
+                    for (int i = 0; i < 4; ++i) wn[q][i] = ld1g(W + (wrow + (unsigned)(kc + 16 * q + 4 * g + i)));
+            }
+            fetch_x(kc, true);
+            return;
+        }
+        // the edge chunk: reduction indices clamped (zeroed by fix); whole vectors stay inside K (K % 4 == 0)
+        if (vec) {
+#pragma unroll
+            for (int q = 0; q < AG_NQ; ++q) wn[q] = *(gvec)(uintptr_t)(W + (wrow + (unsigned)min(kc + 16 * q + 4 * g, K - 4)));
+        } else {
+#pragma unroll
+            for (int q = 0; q < AG_NQ; ++q)
+#pragma unroll
+                for (int i = 0; i < 4; ++i) wn[q][i] = ld1g(W + (wrow + (unsigned)min(kc + 16 * q + 4 * g + i, K - 1)));
+        }
+        fetch_x(kc, false);
+    };
+    // behind the loads' arrival: the reduction's zero padding, on both operands
+    auto fix = [&](int kc) {
+        if (kc + AG_KC <= K) return;
+#pragma unroll
+        for (int q = 0; q < AG_NQ; ++q)
+#pragma unroll
+            for (int i = 0; i < 4; ++i) if (kc + 16 * q + 4 * g + i >= K) wc[q][i] = 0.f;
+        if (kc + xk >= K) {
+#pragma unroll
+            for (int j = 0; j < AG_XE; ++j) xn[j] = 0;
+        }
+    };
+
+    t.acc = f32x4{};
+    const int nS = (K + AG_KC - 1) / AG_KC;
+    fetch(0);
+    for (int s = 0; s < nS; ++s) {
+        const int kc = AG_KC * s;
+        if (s > 0) __syncthreads();
+#pragma unroll
+        for (int q = 0; q < AG_NQ; ++q) wc[q] = wn[q];
+        fix(kc);
+#pragma unroll
+        for (int j = 0; j < AG_XE; ++j) Xs[(xr + 2 * j) * AG_LD + xk] = (float)xn[j];
+        __syncthreads();
+        if (s + 1 < nS) fetch(kc + AG_KC);
+        SB();
+#pragma unroll
+        for (int q = 0; q < AG_NQ; ++q) {
+            const f32x4 a = ld4(Xs + c * AG_LD + 16 * q + 4 * g);
+#pragma unroll
+            for (int i = 0; i < 4; ++i) t.acc = __builtin_amdgcn_mfma_f32_16x16x4f32(a[i], wc[q][i], t.acc, 0, 0, 0);
+        }
+        SB();
+    }
+    return t;
+}
+
+// the tile's values into Y [n][N]: bias, with `relu` x < 0 ? 0 : x (act_hidden_epilogue's ReLU: a NaN stays a NaN).  A
+// hidden layer's store; with N == 1 and no relu the Q column: column 0 alone passes ncol < N and lands in Y[row].
+__device__ __forceinline__ void infer_layer_store(const LayerTile &t, float *Y, int N, int n, int row0, int ncol, bool relu) {
+    typedef __attribute__((address_space(1))) float *gout;
+    const int g = (threadIdx.x & 63) >> 4;
+#pragma unroll
+    for (int i = 0; i < 4; ++i) {
+        const int row = row0 + 4 * g + i;
+        float v = t.acc[i] + t.bias;
+        if (relu) v = v < 0.f ? 0.f : v;
+        if (row < n && ncol < N) *(gout)(uintptr_t)(Y + ((unsigned)row * (unsigned)N + (unsigned)ncol)) = v;
+    }
+}
+
+// the policy head of job J (one column tile, kind is uniform over the workgroup): pre-activations through HL, then one
+// thread per action; J->A, J->eps and J->Y are read with scalar loads where they are needed
+template <class Job>
+__device__ __forceinline__ void infer_layer_head(const LayerTile &t, float *HL, const Job *J, int kind, int n, int row0) {
+    typedef __attribute__((address_space(1))) float *gout;
+    const int tid = threadIdx.x, wave = tid >> 6, lane = tid & 63, c = lane & 15, g = lane >> 4;
+    if (16 * wave < ACT_HEAD_LD) {
+#pragma unroll
+        for (int i = 0; i < 4; ++i) HL[(4 * g + i) * ACT_HEAD_LD + 16 * wave + c] = t.acc[i] + t.bias;
+    }
+    __syncthreads();
+    const int A = sload(&J->A);
+    const int r = tid >> 4, a = tid & 15;
+    if (a < A && row0 + r < n) {
+        const unsigned o = (unsigned)(row0 + r) * (unsigned)A + (unsigned)a;
+        *(gout)(uintptr_t)(sload(&J->Y) + o) =
+            infer_action(HL, r, a, A, kind == AG_SAC_SAMPLE, [&] { return ld1g(sload(&J->eps) + o); });
+    }
+}
+
+}  // namespace sac
+
+// ---- the host halves ----
+
+namespace {
+
+// What an entry's refusals say about itself.  The messages are part of the interface (the tests match them).
+struct InferEntry {
+    const char *fn;          // the entry's name
+    bool general;            // serves general-step trainers and refuses the fused kernels' shapes; false: the reverse
+    bool sac_only;           // refuses TD3 trainers
+    const char *what;        // "device acting", "device Q evaluation", "device evaluation"
+    const char *instead;     // the shape refusal's advice
+    const char *rows_to;     // no trainer has rows to ...
+};
+
+// trainer i of a list: not null, not listed twice, on trainer 0's device, of the algorithm and shapes the entry serves
+int infer_admit_trainer(const InferEntry &E, sac_trainer_t *const *trainers, int i) {
+    const sac_trainer *t = trainers[i];
+    SAC_REQUIRE(t, "trainer %d is null", i);
+    for (int j = 0; j < i; ++j) SAC_REQUIRE(trainers[j] != t, "trainer %d is trainer %d again", i, j);
+    SAC_REQUIRE(t->device == trainers[0]->device, "trainer %d lives on device %d, trainer 0 on device %d", i, t->device,
+                trainers[0]->device);
+    SAC_REQUIRE(!E.sac_only || t->algo == 0, "trainer %d is a TD3 trainer: this entry evaluates the SAC objective "
+                "(entropy-regularised targets of a tanh-Gaussian policy)", i);
+    if (E.general)
+        SAC_REQUIRE(t->gen, "trainer %d has the fused kernels' shapes (two hidden layers of at most 256 units): %s", i, E.instead);
+    else
+        SAC_REQUIRE(!t->gen, "trainer %d runs the general step (hidden sizes beyond two layers of at most 256 units): %s serves "
+                    "the fused kernels' shapes, %s for this trainer", i, E.what, E.instead);
+    return 0;
+}
+
+// The refusals of a *_many entry, all of them in front of anything that changes: per trainer the list checks above, no
+// XCD confinement, the row count, and for a trainer with rows the entry's own checks, member(i).  Then the drain: the
+// weights as of the last completed step of any step path (sac_sync re-runs what a fused step that gave up left undone),
+// for every member with rows.
+template <class Member>
+int infer_admit(const InferEntry &E, sac_trainer_t *const *trainers, int n_trainers, const int32_t *n_rows, Member member) {
+    SAC_REQUIRE(n_trainers >= 1 && n_trainers <= SAC_GROUP_MAX, "%s takes 1..%d trainers (got %d)", E.fn, SAC_GROUP_MAX,
+                n_trainers);
+    int active = 0;
+    for (int i = 0; i < n_trainers; ++i) {
+        if (int rc = infer_admit_trainer(E, trainers, i)) return rc;
+        SAC_REQUIRE(trainers[i]->xcd_mask == 0xffu, "trainer %d is confined by sac_trainer_set_xcd[_mask]: %s launches on the "
+                    "whole chip", i, E.what);
+        SAC_REQUIRE(n_rows[i] >= 0 && n_rows[i] <= ACT_MAX_ROWS, "trainer %d: %d rows (0..%d per call, 0 = sits out)", i,
+                    (int)n_rows[i], ACT_MAX_ROWS);
+        if (n_rows[i] == 0) continue;
+        active += 1;
+        if (int rc = member(i)) return rc;
+    }
+    SAC_REQUIRE(active > 0, "no trainer has rows to %s", E.rows_to);
+    SAC_HIP(hipSetDevice(trainers[0]->device));
+    for (int i = 0; i < n_trainers; ++i)
+        if (n_rows[i] > 0 && sac_sync(trainers[i])) return -1;
+    return 0;
+}
+
+// the refusals of a *_create entry
+int infer_admit_session(const InferEntry &E, sac_trainer_t *const *trainers, int n_trainers, const int32_t *max_rows) {
+    SAC_REQUIRE(n_trainers >= 1 && n_trainers <= SAC_GROUP_MAX, "%s takes 1..%d trainers (got %d)", E.fn, SAC_GROUP_MAX,
+                n_trainers);
+    for (int i = 0; i < n_trainers; ++i) {
+        if (int rc = infer_admit_trainer(E, trainers, i)) return rc;
+        SAC_REQUIRE(max_rows[i] >= 1 && max_rows[i] <= ACT_MAX_ROWS, "trainer %d: max_rows %d (1..%d)", i, (int)max_rows[i],
+                    ACT_MAX_ROWS);
+    }
+    return 0;
+}
+
+inline size_t infer_align(size_t bytes) { return (bytes + 255) & ~(size_t)255; }
+
+// carves `count` arrays of part[k] elements out of a buffer that is `bytes` long so far: each on a 256-byte boundary
+inline void infer_carve(size_t &bytes, size_t *off, const size_t *part, int count, size_t elem = sizeof(float)) {
+    for (int k = 0; k < count; ++k) { off[k] = bytes; bytes += infer_align(elem * part[k]); }
+}
+
+// the slab of an acting session: the control block, then per member obs (max_rows, O) FLOAT64, eps (max_rows, A) fp32,
+// act (max_rows, A) fp32, each 256-byte aligned.  Returns the slab's size.
+inline size_t infer_slab(size_t ctl_bytes, sac_trainer_t *const *trainers, int n_trainers, const int32_t *max_rows,
+                         size_t (*off)[3]) {
+    size_t bytes = infer_align(ctl_bytes);
+    for (int i = 0; i < n_trainers; ++i) {
+        const size_t rows = (size_t)max_rows[i];
+        const size_t part[3] = {sizeof(double) * rows * trainers[i]->O, sizeof(float) * rows * trainers[i]->A,
+                                sizeof(float) * rows * trainers[i]->A};
+        infer_carve(bytes, off[i], part, 3, 1);
+    }
+    return bytes;
+}
+
+inline void infer_slab_arrays(char *slab_h, const size_t *off, double **obs, float **eps, float **act) {
+    if (obs) *obs = reinterpret_cast<double *>(slab_h + off[0]);
+    if (eps) *eps = reinterpret_cast<float *>(slab_h + off[1]);
+    if (act) *act = reinterpret_cast<float *>(slab_h + off[2]);
+}
+
+// A kernel that needs `lds` bytes of dynamic LDS may use them: beyond 48 KB its limit is raised to `most`, once per
+// kernel and device (`raised`: the kernel's flags, one per device).
+int infer_raise_lds(const void *kernel, std::atomic<bool> (&raised)[64], int device, size_t lds, size_t most) {
+    if (lds <= 48 * 1024 || raised[device & 63]) return 0;
+    SAC_HIP(hipFuncSetAttribute(kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)most));
+    raised[device & 63] = true;
+    return 0;
+}
+
+// the widest hidden layer of a general-step net: the columns of its activation scratch
+int infer_widest(const GenNet &N) {
+    int widest = 1;
+    for (int l = 0; l + 1 < N.nl; ++l) widest = std::max(widest, N.L[l].N);
+    return widest;
+}
+
+// what every per-layer job says about layer L of net N (vec: W's rows may be fetched in 16-byte pieces)
+template <class Job>
+void infer_layer_job(Job &J, const GenNet &N, const GenLayer &L) {
+    J.W = N.P + L.offW; J.b = N.P + L.offB;
+    J.N = L.N; J.K = L.K;
+    J.tiles_n = (L.N + AG_CT - 1) / AG_CT;
+    J.vec = (L.K % 4 == 0 && L.offW % 4 == 0) ? 1 : 0;
+}
+
+}  // namespace

@@ -11,10 +11,8 @@
 //           table QvalMember (device-visible memory, read with scalar loads)
 //   LDS     the row-block's input [16][round_up(KQ, 64)]: observations in columns 0..O-1, actions in columns
 //           KP..KP+A-1, zeros elsewhere and in the rows beyond n; both hidden layers [16][256]; the output column [16]
-//   GEMMs   fp32 MFMA 16x16x4 through the step kernels' weight ring (WRing / gemm_ring): wave w owns hidden units
-//           64 w .. 64 w + 63 of both hidden layers; the last layer is row 0 of its padded [16][256] matrix: wave 0,
-//           one tile, as k_act's head
-//   ReLU    act_hidden_epilogue (x < 0 ? 0 : x): a NaN row stays NaN as in torch
+//   math    the pieces of sac_infer.h: infer_fill, infer_hidden (a NaN row stays NaN as in torch), infer_q_out (the
+//           last layer is row 0 of its padded [16][256] matrix: wave 0, one tile)
 //
 // Row independence.  A row's Q value is a function of that row's observation and action and the net's weights only:
 // every output element is one MFMA dot product over k in ascending chunks, and neither the row's place in its block,
@@ -45,11 +43,7 @@ struct QvalMember {
 
 __global__ __launch_bounds__(256) void k_qval(const QvalMember *__restrict__ tab, int n_members) {
     extern __shared__ __attribute__((aligned(16))) float lds[];
-    // this workgroup's member: the last one whose first workgroup is not behind this one (wave-uniform, scalar loads)
-    int mi = 0;
-    for (int i = 1; i < n_members; ++i)
-        if ((int)blockIdx.x >= sload(&tab[i].wg0)) mi = i;
-    const QvalMember *M = tab + mi;
+    const QvalMember *M = tab + infer_member(tab, n_members, &QvalMember::wg0);
     const int O = sload(&M->O), A = sload(&M->A), KP = sload(&M->KP), n = sload(&M->n);
     const int KQ = KP + 16, nrb = (n + RB - 1) / RB;
     const int local = (int)blockIdx.x - sload(&M->wg0);
@@ -60,57 +54,9 @@ __global__ __launch_bounds__(256) void k_qval(const QvalMember *__restrict__ tab
     float *X1 = X0 + RB * KL0;           // [16][256]
     float *X2 = X1 + RB * H;             // [16][256]
     float *QL = X2 + RB * H;             // [16]
-    const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63, c = lane & 15, g = lane >> 4;
-
-    // weight requests of the first layer go out in front of the input rows
-    WRing<4> r0;
-    r0.init(P + sload(&M->offW[0]), KQ, 64 * wave, 16);
-    r0.fill(KQ >> 4);
-    float bv0[4], bv1[4];
-    const float *b0 = P + sload(&M->offB[0]), *b1 = P + sload(&M->offB[1]);
-#pragma unroll
-    for (int t = 0; t < 4; ++t) { bv0[t] = b0[64 * wave + 16 * t + c]; bv1[t] = b1[64 * wave + 16 * t + c]; }
-    {   // [obs | 0 | act | 0] of the row-block; rows beyond n are zero
-        const float *obs = sload(&M->obs), *act = sload(&M->act);
-        for (int i = threadIdx.x; i < RB * KL0; i += 256) {
-            const int r = i / KL0, k = i - r * KL0;
-            float v = 0.f;
-            if (row0 + r < n) {
-                if (k < O) v = obs[(size_t)(row0 + r) * O + k];
-                else if (k >= KP && k < KP + A) v = act[(size_t)(row0 + r) * A + (k - KP)];
-            }
-            X0[lds_off(r, k, KL0)] = v;
-        }
-    }
-    lds_barrier();
-    {
-        f32x4 acc[4] = {};
-        gemm_ring(r0, X0, KL0, KQ >> 4, acc);
-        act_hidden_epilogue<4>(acc, 64 * wave, 16, bv0, X1, H);
-    }
-    WRing<4> r1;
-    r1.init(P + sload(&M->offW[1]), H, 64 * wave, 16);
-    r1.fill(H >> 4);
-    lds_barrier();
-    {
-        f32x4 acc[4] = {};
-        gemm_ring(r1, X1, H, H >> 4, acc);
-        act_hidden_epilogue<4>(acc, 64 * wave, 16, bv1, X2, H);
-    }
-    lds_barrier();
-    if (wave == 0) {                     // the output unit is row 0 of the padded last layer: column c == 0 of the tile
-        WRing<1> rq;
-        rq.init(P + sload(&M->offW[2]), H, 0, 16);
-        rq.fill(H >> 4);
-        const float bq = (P + sload(&M->offB[2]))[c];
-        f32x4 acc[1] = {};
-        gemm_ring(rq, X2, H, H >> 4, acc);
-        if (c == 0) {
-#pragma unroll
-            for (int i = 0; i < 4; ++i) QL[4 * g + i] = acc[0][i] + bq;
-        }
-    }
-    lds_barrier();
+    infer_hidden(P, M->offW, M->offB, X0, KL0, KQ, X1, X2,
+                 [&] { infer_fill(X0, KL0, row0, n, sload(&M->obs), O, sload(&M->act), KP, A); });
+    infer_q_out(P, M->offW, M->offB, X2, QL);
     if (threadIdx.x < RB && row0 + (int)threadIdx.x < n)
         sload(&M->q)[(size_t)sel * n + row0 + threadIdx.x] = QL[threadIdx.x];
 }
@@ -121,49 +67,42 @@ namespace {
 
 size_t qval_lds_bytes(int KQ) { return sizeof(float) * (size_t)RB * (((KQ + 63) & ~63) + 2 * H + 1); }
 
+std::atomic<bool> g_qval_lds_raised[64];
+
+// What sac_q_values_many and sac_q_values_general_many do alike in front of their tables: the refusals and the drain
+// (infer_admit)
+int qval_admit(const InferEntry &E, sac_trainer_t *const *trainers, int n_trainers, const int32_t *n_rows,
+               const float *const *obs, const float *const *act, const uint32_t *nets, float *const *q) {
+    return infer_admit(E, trainers, n_trainers, n_rows, [&](int i) {
+        SAC_REQUIRE(nets[i] != 0 && nets[i] <= 15u, "trainer %d: nets 0x%x selects no Q network or an unknown one (bits "
+                    "SAC_Q_QF1 | SAC_Q_QF2 | SAC_Q_TARGET_QF1 | SAC_Q_TARGET_QF2)", i, (unsigned)nets[i]);
+        SAC_REQUIRE(obs[i] && act[i] && q[i], "trainer %d: null observations, actions or Q values", i);
+        return 0;
+    });
+}
+
+// The staging behind the call's table (`bytes` so far): per member obs (n, O), act (n, A), q (selected nets, n).
+void qval_carve(size_t &bytes, size_t (*off)[3], sac_trainer_t *const *trainers, int n_trainers, const int32_t *n_rows,
+                const uint32_t *nets) {
+    for (int i = 0; i < n_trainers; ++i) {
+        const size_t n = (size_t)n_rows[i];
+        const size_t part[3] = {n * trainers[i]->O, n * trainers[i]->A, n ? n * __builtin_popcount(nets[i]) : 0};
+        infer_carve(bytes, off[i], part, 3);
+    }
+}
+
 }  // namespace
 
 // (declared extern "C" in include/sac_hip.h)
 int sac_q_values_many(sac_trainer_t *const *trainers, int n_trainers, const int32_t *n_rows, const float *const *obs,
                       const float *const *act, const uint32_t *nets, float *const *q) {
     SAC_REQUIRE(trainers && n_rows && obs && act && nets && q, "bad arguments to sac_q_values_many");
-    SAC_REQUIRE(n_trainers >= 1 && n_trainers <= SAC_GROUP_MAX, "sac_q_values_many takes 1..%d trainers (got %d)",
-                SAC_GROUP_MAX, n_trainers);
-    // every refusal comes first: nothing has changed when one of them returns
-    int active = 0;
-    for (int i = 0; i < n_trainers; ++i) {
-        const sac_trainer *t = trainers[i];
-        SAC_REQUIRE(t, "trainer %d is null", i);
-        for (int j = 0; j < i; ++j) SAC_REQUIRE(trainers[j] != t, "trainer %d is trainer %d again", i, j);
-        SAC_REQUIRE(t->device == trainers[0]->device, "trainer %d lives on device %d, trainer 0 on device %d", i, t->device,
-                    trainers[0]->device);
-        SAC_REQUIRE(!t->gen, "trainer %d runs the general step (hidden sizes beyond two layers of at most 256 units): device "
-                    "Q evaluation serves the fused kernels' shapes, sac_get_params and a forward on the host is the path for "
-                    "this trainer", i);
-        SAC_REQUIRE(t->xcd_mask == 0xffu, "trainer %d is confined by sac_trainer_set_xcd[_mask]: device Q evaluation launches "
-                    "on the whole chip", i);
-        SAC_REQUIRE(n_rows[i] >= 0 && n_rows[i] <= ACT_MAX_ROWS, "trainer %d: %d rows (0..%d per call, 0 = sits out)", i,
-                    (int)n_rows[i], ACT_MAX_ROWS);
-        if (n_rows[i] == 0) continue;
-        active += 1;
-        SAC_REQUIRE(nets[i] != 0 && nets[i] <= 15u, "trainer %d: nets 0x%x selects no Q network or an unknown one (bits "
-                    "SAC_Q_QF1 | SAC_Q_QF2 | SAC_Q_TARGET_QF1 | SAC_Q_TARGET_QF2)", i, (unsigned)nets[i]);
-        SAC_REQUIRE(obs[i] && act[i] && q[i], "trainer %d: null observations, actions or Q values", i);
-    }
-    SAC_REQUIRE(active > 0, "no trainer has rows to evaluate");
+    const InferEntry E = {"sac_q_values_many", false, false, "device Q evaluation",
+                          "sac_get_params and a forward on the host is the path", "evaluate"};
+    if (int rc = qval_admit(E, trainers, n_trainers, n_rows, obs, act, nets, q)) return rc;
     sac_trainer *t0 = trainers[0];
-    SAC_HIP(hipSetDevice(t0->device));
-    // the weights as of the last completed step: drain every member, re-run what a fused step that gave up left undone
-    for (int i = 0; i < n_trainers; ++i)
-        if (n_rows[i] > 0 && sac_sync(trainers[i])) return -1;
-
-    size_t off[SAC_GROUP_MAX][3], bytes = (sizeof(QvalMember) * SAC_GROUP_MAX + 255) & ~(size_t)255;
-    for (int i = 0; i < n_trainers; ++i) {
-        const sac_trainer *t = trainers[i];
-        const size_t n = (size_t)n_rows[i];
-        const size_t part[3] = {n * t->O, n * t->A, n ? n * __builtin_popcount(nets[i]) : 0};
-        for (int k = 0; k < 3; ++k) { off[i][k] = bytes; bytes += (sizeof(float) * part[k] + 255) & ~(size_t)255; }
-    }
+    size_t off[SAC_GROUP_MAX][3], bytes = infer_align(sizeof(QvalMember) * SAC_GROUP_MAX);
+    qval_carve(bytes, off, trainers, n_trainers, n_rows, nets);
     if (act_stage_reserve(t0, bytes)) return -1;
     const sac_trainer::ActStage &S = t0->act_stage;
     QvalMember *tab = reinterpret_cast<QvalMember *>(S.h);
@@ -190,11 +129,7 @@ int sac_q_values_many(sac_trainer_t *const *trainers, int n_trainers, const int3
         memcpy(S.h + off[i][1], act[i], sizeof(float) * (size_t)n_rows[i] * t->A);
     }
     const size_t lds = qval_lds_bytes(kq_max);
-    if (lds > 48 * 1024 && !t0->qval_lds_raised) {
-        SAC_HIP(hipFuncSetAttribute(reinterpret_cast<const void *>(k_qval), hipFuncAttributeMaxDynamicSharedMemorySize,
-                                    (int)qval_lds_bytes(512)));
-        t0->qval_lds_raised = true;
-    }
+    if (infer_raise_lds(reinterpret_cast<const void *>(k_qval), g_qval_lds_raised, t0->device, lds, qval_lds_bytes(512))) return -1;
     hipLaunchKernelGGL(k_qval, dim3(wgs), dim3(256), lds, t0->stream, reinterpret_cast<const QvalMember *>(S.d), m);
     SAC_HIP(hipGetLastError());
     if (wait_trainer_stream(t0)) return -1;

@@ -12,15 +12,12 @@
 //           one; a net's output layer is its last layer, whatever the launch index.  A workgroup finds its job by a
 //           bisection over wg0 (ascending): at most 6 dependent scalar loads where a scan would chain 64.
 //   grid    one workgroup (4 waves) per 16-row x 64-column output tile of one job; wave w owns columns 16 w .. 16 w + 15
-//   GEMM    fp32 MFMA 16x16x4 over K in ascending chunks of AG_KC: the chunk's 16 input rows go through LDS, the weights
-//           come straight from global memory, 16 bytes per lane along K where K % 4 == 0 and offW % 4 == 0; the next
-//           chunk's loads are in flight under this chunk's MFMAs.  Loads are unconditional from clamped indices, and what
-//           lies beyond K is zeroed in the edge chunk only.  The reduction is never split across workgroups.
-//   input   two sources and a split point K1: element k of row r is X[r K1 + k] for k < K1 and X2[r (K - K1) + k - K1]
-//           otherwise -- both loads from clamped indices, then a select.  The first layer reads cat(obs, act) this way
-//           (X = obs, X2 = act, K1 = O: the host stages the two blocks and never builds the concatenated rows; all
-//           selected nets of a member read the same two blocks); hidden layers set K1 = K and X2 = X.
-//   hidden  bias, then x < 0 ? 0 : x (act_hidden_epilogue's ReLU: a NaN stays a NaN)
+//   GEMM    infer_layer_tile<float, true> (sac_infer.h): k_act_layer's tile with two input sources.  The reduction is
+//           never split across workgroups.
+//   input   the split point K1: the first layer reads cat(obs, act) through it (X = obs, X2 = act, K1 = O: the host
+//           stages the two blocks and never builds the concatenated rows; all selected nets of a member read the same
+//           two blocks); hidden layers set K1 = K and X2 = X.
+//   hidden  infer_layer_store: bias, then x < 0 ? 0 : x (a NaN stays a NaN)
 //   output  N = 1: the same tile with the columns clamped to the one weight row -- every column of the tile computes the
 //           net's value by the same MFMA chain, column 0 of wave 0 stores it: bias, no activation, row r of selected net s
 //           to q[s n + r].  The order of summation is that of any other column: it depends on K alone.
@@ -52,8 +49,6 @@ struct QvalLayerJob {
 
 __global__ __launch_bounds__(256) void k_qval_layer(const QvalLayerJob *__restrict__ tab, int n_jobs) {
     __shared__ __attribute__((aligned(16))) float Xs[RB * AG_LD];
-    typedef const __attribute__((address_space(1))) f32x4 *gvec;
-    typedef __attribute__((address_space(1))) float *gout;
     // this workgroup's job: the last one whose first workgroup is not behind this one (wave-uniform, scalar loads)
     int lo = 0, hi = n_jobs;
     while (hi - lo > 1) {
@@ -67,103 +62,10 @@ __global__ __launch_bounds__(256) void k_qval_layer(const QvalLayerJob *__restri
     const bool vec = sload(&J->vec) != 0, relu = sload(&J->relu) != 0;
     const int tile = (int)blockIdx.x - sload(&J->wg0);
     const int row0 = RB * (tile / tiles_n), n0 = AG_CT * (tile % tiles_n);
-    const int tid = threadIdx.x, wave = tid >> 6, lane = tid & 63, c = lane & 15, g = lane >> 4;
-    const int ncol = n0 + 16 * wave + c;
-    // this lane's weight row and this thread's input elements (chunk coordinates: row xr + 2 j, k = xk), both clamped
-    const unsigned wrow = (unsigned)min(ncol, N - 1) * (unsigned)K;
-    const int xk = tid & (AG_KC - 1), xr = tid >> 7;
-    const int K2 = K - K1, k2max = max(K2 - 1, 0);
-    unsigned xrow[AG_XE], xrow2[AG_XE];
-#pragma unroll
-    for (int j = 0; j < AG_XE; ++j) {
-        const unsigned r = (unsigned)min(row0 + xr + 2 * j, n - 1);
-        xrow[j] = r * (unsigned)K1; xrow2[j] = r * (unsigned)K2;
-    }
-    const float bias = ld1g(bp + min(ncol, N - 1));
-
-    f32x4 wn[AG_NQ], wc[AG_NQ];
-    float xn[AG_XE];
-    // the chunk's input elements: both sources from clamped indices, then the select (k beyond K is zeroed by fix)
-    auto fetch_x = [&](int kc) {
-        const int k = kc + xk;
-        const unsigned k1 = (unsigned)min(k, K1 - 1), k2 = (unsigned)min(max(k - K1, 0), k2max);
-#pragma unroll
-        for (int j = 0; j < AG_XE; ++j) {
-            const float a = ld1g(X + (xrow[j] + k1)), b = ld1g(X2 + (xrow2[j] + k2));
-            xn[j] = k < K1 ? a : b;
-        }
-    };
-    auto fetch = [&](int kc) {
-        if (kc + AG_KC <= K) {
-            if (vec) {
-#pragma unroll
-                for (int q = 0; q < AG_NQ; ++q) wn[q] = *(gvec)(uintptr_t)(W + (wrow + (unsigned)(kc + 16 * q + 4 * g)));
-            } else {
-#pragma unroll
-                for (int q = 0; q < AG_NQ; ++q)
-#pragma unroll
-                    for (int i = 0; i < 4; ++i) wn[q][i] = ld1g(W + (wrow + (unsigned)(kc + 16 * q + 4 * g + i)));
-            }
-            fetch_x(kc);
-            return;
-        }
-        // the edge chunk: reduction indices clamped (zeroed by fix); whole vectors stay inside K (K % 4 == 0)
-        if (vec) {
-#pragma unroll
-            for (int q = 0; q < AG_NQ; ++q) wn[q] = *(gvec)(uintptr_t)(W + (wrow + (unsigned)min(kc + 16 * q + 4 * g, K - 4)));
-        } else {
-#pragma unroll
-            for (int q = 0; q < AG_NQ; ++q)
-#pragma unroll
-                for (int i = 0; i < 4; ++i) wn[q][i] = ld1g(W + (wrow + (unsigned)min(kc + 16 * q + 4 * g + i, K - 1)));
-        }
-        fetch_x(kc);
-    };
-    // behind the loads' arrival: the reduction's zero padding, on both operands
-    auto fix = [&](int kc) {
-        if (kc + AG_KC <= K) return;
-#pragma unroll
-        for (int q = 0; q < AG_NQ; ++q)
-#pragma unroll
-            for (int i = 0; i < 4; ++i) if (kc + 16 * q + 4 * g + i >= K) wc[q][i] = 0.f;
-        if (kc + xk >= K) {
-#pragma unroll
-            for (int j = 0; j < AG_XE; ++j) xn[j] = 0.f;
-        }
-    };
-
-    f32x4 acc = {};
-    const int nS = (K + AG_KC - 1) / AG_KC;
-    fetch(0);
-    for (int s = 0; s < nS; ++s) {
-        const int kc = AG_KC * s;
-        if (s > 0) __syncthreads();
-#pragma unroll
-        for (int q = 0; q < AG_NQ; ++q) wc[q] = wn[q];
-        fix(kc);
-#pragma unroll
-        for (int j = 0; j < AG_XE; ++j) Xs[(xr + 2 * j) * AG_LD + xk] = xn[j];
-        __syncthreads();
-        if (s + 1 < nS) fetch(kc + AG_KC);
-        SB();
-#pragma unroll
-        for (int q = 0; q < AG_NQ; ++q) {
-            const f32x4 a = ld4(Xs + c * AG_LD + 16 * q + 4 * g);
-#pragma unroll
-            for (int i = 0; i < 4; ++i) acc = __builtin_amdgcn_mfma_f32_16x16x4f32(a[i], wc[q][i], acc, 0, 0, 0);
-        }
-        SB();
-    }
-
+    const int ncol = n0 + 16 * (threadIdx.x >> 6) + (threadIdx.x & 15);
+    const LayerTile t = infer_layer_tile<float, true>(Xs, W, bp, X, X2, N, K, K1, n, vec, row0, ncol);
     // hidden layer: ReLU; output layer (N == 1, relu == 0): column 0 alone passes ncol < N and lands in q[s n + row]
-    float *Y = sload(&J->Y);
-#pragma unroll
-    for (int i = 0; i < 4; ++i) {
-        const int row = row0 + 4 * g + i;
-        float v = acc[i] + bias;
-        if (relu) v = v < 0.f ? 0.f : v;
-        if (row < n && ncol < N) *(gout)(uintptr_t)(Y + ((unsigned)row * (unsigned)N + (unsigned)ncol)) = v;
-    }
+    infer_layer_store(t, sload(&J->Y), N, n, row0, ncol, relu);
 }
 
 }  // namespace sac
@@ -172,49 +74,18 @@ __global__ __launch_bounds__(256) void k_qval_layer(const QvalLayerJob *__restri
 int sac_q_values_general_many(sac_trainer_t *const *trainers, int n_trainers, const int32_t *n_rows, const float *const *obs,
                               const float *const *act, const uint32_t *nets, float *const *q) {
     SAC_REQUIRE(trainers && n_rows && obs && act && nets && q, "bad arguments to sac_q_values_general_many");
-    SAC_REQUIRE(n_trainers >= 1 && n_trainers <= SAC_GROUP_MAX, "sac_q_values_general_many takes 1..%d trainers (got %d)",
-                SAC_GROUP_MAX, n_trainers);
-    // every refusal comes first: nothing has changed when one of them returns
-    int active = 0;
-    for (int i = 0; i < n_trainers; ++i) {
-        const sac_trainer *t = trainers[i];
-        SAC_REQUIRE(t, "trainer %d is null", i);
-        for (int j = 0; j < i; ++j) SAC_REQUIRE(trainers[j] != t, "trainer %d is trainer %d again", i, j);
-        SAC_REQUIRE(t->device == trainers[0]->device, "trainer %d lives on device %d, trainer 0 on device %d", i, t->device,
-                    trainers[0]->device);
-        SAC_REQUIRE(t->gen, "trainer %d has the fused kernels' shapes (two hidden layers of at most 256 units): sac_q_values "
-                    "is its device Q evaluation entry, sac_q_values_general serves the general step", i);
-        SAC_REQUIRE(t->xcd_mask == 0xffu, "trainer %d is confined by sac_trainer_set_xcd[_mask]: device Q evaluation launches "
-                    "on the whole chip", i);
-        SAC_REQUIRE(n_rows[i] >= 0 && n_rows[i] <= ACT_MAX_ROWS, "trainer %d: %d rows (0..%d per call, 0 = sits out)", i,
-                    (int)n_rows[i], ACT_MAX_ROWS);
-        if (n_rows[i] == 0) continue;
-        active += 1;
-        SAC_REQUIRE(nets[i] != 0 && nets[i] <= 15u, "trainer %d: nets 0x%x selects no Q network or an unknown one (bits "
-                    "SAC_Q_QF1 | SAC_Q_QF2 | SAC_Q_TARGET_QF1 | SAC_Q_TARGET_QF2)", i, (unsigned)nets[i]);
-        SAC_REQUIRE(obs[i] && act[i] && q[i], "trainer %d: null observations, actions or Q values", i);
-    }
-    SAC_REQUIRE(active > 0, "no trainer has rows to evaluate");
+    const InferEntry E = {"sac_q_values_general_many", true, false, "device Q evaluation",
+                          "sac_q_values is its device Q evaluation entry, sac_q_values_general serves the general step", "evaluate"};
+    if (int rc = qval_admit(E, trainers, n_trainers, n_rows, obs, act, nets, q)) return rc;
     sac_trainer *t0 = trainers[0];
-    SAC_HIP(hipSetDevice(t0->device));
-    // the weights as of the last completed step of any step path: drain every member with rows
-    for (int i = 0; i < n_trainers; ++i)
-        if (n_rows[i] > 0 && sac_sync(trainers[i])) return -1;
-
-    const size_t tab_bytes = (sizeof(QvalLayerJob) * QG_JOBS * gen::GMAXL + 255) & ~(size_t)255;
-    size_t off[SAC_GROUP_MAX][3], slice[SAC_GROUP_MAX] = {}, bytes = tab_bytes;
+    size_t off[SAC_GROUP_MAX][3], slice[SAC_GROUP_MAX] = {}, bytes = infer_align(sizeof(QvalLayerJob) * QG_JOBS * gen::GMAXL);
+    qval_carve(bytes, off, trainers, n_trainers, n_rows, nets);
     int launches = 0;
     for (int i = 0; i < n_trainers; ++i) {
-        sac_trainer *t = trainers[i];
-        const size_t n = (size_t)n_rows[i];
-        const size_t part[3] = {n * t->O, n * t->A, n ? n * __builtin_popcount(nets[i]) : 0};
-        for (int k = 0; k < 3; ++k) { off[i][k] = bytes; bytes += (sizeof(float) * part[k] + 255) & ~(size_t)255; }
-        if (n == 0) continue;
-        const GenNet &Q = t->gen->net[SAC_NET_QF1];                    // (the four Q nets share their layout)
-        int widest = 1;
-        for (int l = 0; l + 1 < Q.nl; ++l) widest = std::max(widest, Q.L[l].N);
-        slice[i] = n * (size_t)widest;
-        if (act_general_reserve(t, slice[i] * __builtin_popcount(nets[i]))) return -1;
+        if (n_rows[i] == 0) continue;
+        const GenNet &Q = trainers[i]->gen->net[SAC_NET_QF1];          // (the four Q nets share their layout)
+        slice[i] = (size_t)n_rows[i] * infer_widest(Q);
+        if (act_general_reserve(trainers[i], slice[i] * __builtin_popcount(nets[i]))) return -1;
         launches = std::max(launches, Q.nl);
     }
     if (act_stage_reserve(t0, bytes)) return -1;
@@ -235,15 +106,13 @@ int sac_q_values_general_many(sac_trainer_t *const *trainers, int n_trainers, co
                 const GenLayer &L = Q.L[l];
                 const bool last = l + 1 == Q.nl;
                 QvalLayerJob &J = tab[(size_t)l * QG_JOBS + njobs[l]++];
-                J.W = Q.P + L.offW; J.b = Q.P + L.offB;
+                infer_layer_job(J, Q, L);
                 J.X = x; J.X2 = x2;
                 J.Y = last ? reinterpret_cast<float *>(S.d + off[i][2]) + (size_t)s * n_rows[i]
                            : t->act_gen[l & 1] + (size_t)s * slice[i];
-                J.N = L.N; J.K = L.K; J.K1 = l == 0 ? t->O : L.K; J.n = n_rows[i];
+                J.K1 = l == 0 ? t->O : L.K; J.n = n_rows[i];
                 J.wg0 = blocks[l];
-                J.tiles_n = (L.N + AG_CT - 1) / AG_CT;
                 J.relu = last ? 0 : 1;
-                J.vec = (L.K % 4 == 0 && L.offW % 4 == 0) ? 1 : 0;
                 blocks[l] += ((n_rows[i] + RB - 1) / RB) * J.tiles_n;
                 x = x2 = J.Y;
             }

@@ -1935,9 +1935,6 @@ struct sac_trainer {
     bool mirror_valid = false;
     // device acting (sac_act.h): observations, eps, actions and the member table of a call, in mapped pinned host memory
     struct ActStage { char *h = nullptr, *d = nullptr; size_t bytes = 0; } act_stage;
-    bool act_lds_raised = false;                      // k_act may use more than 48 KB of LDS (wide observations)
-    bool qval_lds_raised = false;                     // k_qval likewise (sac_qval.h)
-    bool eval_lds_raised = false;                     // k_eval likewise (sac_eval.h)
     // general-step device acting (sac_act_general.h) and Q evaluation (sac_qval_general.h): the activations between two
     // layer launches ping-pong between these
     float *act_gen[2] = {nullptr, nullptr}; size_t act_gen_floats = 0;
@@ -2307,6 +2304,7 @@ int stage_batches(sac_trainer *t, sac_buffer *b, int64_t n_steps) {
 
 }  // namespace
 
+#include "sac_infer.h"
 #include "sac_act.h"
 #include "sac_qval.h"
 #include "sac_eval.h"

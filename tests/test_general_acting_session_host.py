@@ -32,10 +32,18 @@ def test_header_bindings_and_library_name_the_entry_points():
 
 
 def test_sac_actor_create_still_refuses_general_step_trainers_in_its_source():
-    src = open(os.path.join(ROOT, "robosuite_benchmark_amd", "csrc", "sac_actor.h")).read()
-    assert 'SAC_REQUIRE(!t->gen, "trainer %d runs the general step' in src
-    gsrc = open(os.path.join(ROOT, "robosuite_benchmark_amd", "csrc", "sac_actor_general.h")).read()
-    assert "SAC_REQUIRE(t->gen," in gsrc and "sac_actor_create" in gsrc
+    # both refusals are written once, in sac_infer.h; which of them an entry makes is its InferEntry's second field
+    csrc = os.path.join(ROOT, "robosuite_benchmark_amd", "csrc")
+    shared = open(os.path.join(csrc, "sac_infer.h")).read()
+    assert 'SAC_REQUIRE(!t->gen, "trainer %d runs the general step' in shared
+    assert 'SAC_REQUIRE(t->gen, "trainer %d has the fused kernels\' shapes' in shared
+    assert shared.count("infer_admit_trainer(E, trainers, i)") == 2          # the call check and the create check
+    src = open(os.path.join(csrc, "sac_actor.h")).read()
+    assert 'const InferEntry E = {"sac_actor_create", false,' in src
+    assert "infer_admit_session(E, trainers, n_trainers, max_rows)" in src
+    gsrc = open(os.path.join(csrc, "sac_actor_general.h")).read()
+    assert 'const InferEntry E = {"sac_gactor_create", true,' in gsrc and "sac_actor_create" in gsrc
+    assert "infer_admit_session(E, trainers, n_trainers, max_rows)" in gsrc
 
 
 # ---- the stand-in ---------------------------------------------------------------------------------------------------------
