@@ -7,6 +7,7 @@
 #include <cstdarg>
 
 #include "../../include/sac_hip.h"
+#include "sac_step_plan.h"      // RB, H, round_up and the other constants the step plan shares with the kernels
 
 namespace sac {
 
@@ -29,11 +30,9 @@ void set_error(const char *fmt, ...);
         }                                                                                     \
     } while (0)
 
-constexpr int RB = 16;            // rows of one row-block (one MFMA 16x16x4 M tile)
 constexpr int MT_N = 624;
 constexpr int MT_M = 397;
 
-static inline int round_up(int x, int m) { return (x + m - 1) / m * m; }
 static inline int64_t round_up64(int64_t x, int64_t m) { return (x + m - 1) / m * m; }
 
 // Weight matrices AND the feature-major activations ([feature][batch]: rows = features, k = batch row) live in HBM in

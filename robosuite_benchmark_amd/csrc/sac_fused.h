@@ -42,7 +42,7 @@
 
 constexpr int CNT_STRIDE = 32;                                  // unsigned per counter: one 128-B line each
 constexpr unsigned long long HANDOFF_TIMEOUT_TICKS = 5000000ull;   // s_memrealtime ticks (100 MHz): 50 ms
-constexpr int FUSED_RED = 2048;                                 // floats of split-K scratch
+// (FUSED_RED, the floats of split-K scratch: sac_step_plan.h)
 
 // one lane: wait until *cnt has reached target (wrap-safe); false = abort (ours or somebody else's)
 // (SLEEP: s_sleep units of 64 cycles between polls -- 1 for the short waits of k_abc; the long waits of k_chain8<.., BWD>, where

@@ -26,8 +26,8 @@
 #pragma once
 
 // One variant class of a group: the members whose step runs the same instances of the grouped kernels, a contiguous
-// range of the device tables.  A group of one shape is one class; a mixed group has up to four (by the instance of
-// launch A a member's own step runs), an MLP or arch group up to two (by the elementwise kernels' action bound).
+// range of the device tables.  A group of one shape is one class; a mixed group has up to four (by the (nth, wide) of
+// its members' step plans), an MLP or arch group up to two (by the elementwise kernels' action bound).
 struct GroupClass {
     int lo = 0, n = 0;                                // device table entries lo .. lo + n - 1
     int ma = 0;                                       // MLP groups: the action bound of the class's elementwise kernels (8 / 16)
@@ -114,17 +114,14 @@ static int group_member_ok(const sac_trainer *t, int i, int algo, bool mlp = fal
     SAC_REQUIRE(t->Bt <= 256, "trainer group member %d has batch %d: groups take batches of at most 256 rows", i, t->Bt);
     SAC_REQUIRE(t->xcd_mask == 0xffu, "trainer group member %d is confined to XCDs (sac_trainer_set_xcd[_mask]): a group spans "
                 "the whole chip", i);
-    SAC_REQUIRE(t->SP == 4 && !t->chain && !t->bwd8, "trainer group member %d runs column split %d: groups take the "
-                "default split 4 only", i, t->SP);
+    SAC_REQUIRE(t->plan.SP == 4 && !t->plan.chain && !t->plan.bwd8, "trainer group member %d runs column split %d: groups take the "
+                "default split 4 only", i, t->plan.SP);
     return 0;
 }
 
-// a member's solo x-extents (launch_step / launch_step_td3 at split 4; k_bwd is compact for every batch <= 256)
-static void member_extents(const sac_trainer *t, int algo, int &xa, int &xb, int &xc, int &xpi) {
-    const int SPv = 4, NB = t->NB;
-    xa = 4 * SPv * NB;
-    if (algo == 0) { xb = xc = 4 * SPv * NB; xpi = 0; }
-    else { xb = xc = 8 * ((SPv * NB + 3) / 4); xpi = SPv * NB; }
+// members of one variant class run the same instances of the step kernels (the column split is 4: group_member_ok)
+static bool same_variant(const sac_trainer *a, const sac_trainer *b) {
+    return a->plan.nth == b->plan.nth && a->plan.wide == b->plan.wide;
 }
 
 // a group's tables (device, with their pinned host images: members | draws | gathers | steps), its two streams, its
@@ -156,15 +153,8 @@ static int group_tables(sac_group *g, size_t mem_bytes, size_t step_bytes) {
     g->d_smp = reinterpret_cast<SampleMember *>(g->d_tab + o_smp); g->h_smp = reinterpret_cast<SampleMember *>(g->h_tab + o_smp);
     g->d_gat = reinterpret_cast<GatherMember *>(g->d_tab + o_gat); g->h_gat = reinterpret_cast<GatherMember *>(g->h_tab + o_gat);
     g->d_step = g->d_tab + o_sa; g->h_step = g->h_tab + o_sa;
-    {   // a tenant of the device's fused-launch gate: no fused trainer's launch may overlap the group's grids
-        FusedGate &G = g_gate[g->device & 63];
-        std::lock_guard<std::mutex> lk(G.mu);
-        if (!G.ev && hipEventCreateWithFlags(&G.ev, hipEventDisableTiming) != hipSuccess) {
-            sac::set_error("hipEventCreate failed");
-            return -1;
-        }
-        G.live += 1;
-    }
+    // a tenant of the device's fused-launch gate: no fused trainer's launch may overlap the group's grids
+    if (gate_join(g->device)) { sac::set_error("hipEventCreate failed"); return -1; }
     return 0;
 }
 
@@ -185,33 +175,11 @@ static int fused_member_shape(const sac_trainer *t, const sac_trainer *t0, int i
 // ... and these behind it
 static int fused_member_kernels(const sac_trainer *t, const sac_trainer *t0, int i, bool mixed) {
     if (!mixed)
-        SAC_REQUIRE(t->fwd_a == t0->fwd_a && t->dw.njobs == t0->dw.njobs, "trainer group member %d runs another kernel "
+        SAC_REQUIRE(same_variant(t, t0) && t->dw.njobs == t0->dw.njobs, "trainer group member %d runs another kernel "
                     "variant than member 0", i);
     SAC_REQUIRE(t->A <= 16 && 3 * 4 * t->NB <= 192, "trainer group member %d: act_dim %d / batch %d outside the grouped "
                 "kernels", i, t->A, t->Bt);
     return 0;
-}
-
-// the grouped instances of the variant a class's own four-launch step runs (tc: a member of the class): launches A, B,
-// C -- and TD3's actor pass B, C; false: none.  (The order in which kernels are first named fixes their order in the
-// code object: keep it when comparing builds byte for byte.)
-static bool fused_group_kernels(const sac_trainer *tc, int algo, const void *k[5]) {
-    auto fn = [](auto f) { return reinterpret_cast<const void *>(f); };
-#define SAC_GROUP_PICK(NTH, W)                                                                             \
-    if (algo == 0 && tc->fwd_a == &k_fwd_a<NTH, W, 4>) {                                                   \
-        k[0] = fn(&k_fwd_a_group<NTH, W, 4>); k[1] = fn(&k_fwd_b_group<NTH, W, 4>); k[2] = fn(&k_bwd_group<NTH, 4>); \
-    }
-#define TD3_GROUP_PICK(W)                                                                                  \
-    if (algo == 1 && tc->fwd_a == &k_fwd_a<1, W, 4, M_TD3_CRITIC>) {                                       \
-        k[0] = fn(&k_fwd_a_group<1, W, 4, M_TD3_CRITIC>);                                                  \
-        k[1] = fn(&k_fwd_b_group<1, W, 4, M_TD3_CRITIC>); k[3] = fn(&k_fwd_b_group<1, W, 4, M_TD3_ACTOR>);   \
-        k[2] = fn(&k_bwd_group<1, 4, M_TD3_CRITIC>); k[4] = fn(&k_bwd_group<1, 4, M_TD3_ACTOR>);             \
-    }
-    SAC_GROUP_PICK(1, false) SAC_GROUP_PICK(1, true) SAC_GROUP_PICK(2, false) SAC_GROUP_PICK(2, true)
-    TD3_GROUP_PICK(false) TD3_GROUP_PICK(true)
-#undef SAC_GROUP_PICK
-#undef TD3_GROUP_PICK
-    return k[0] != nullptr;
 }
 
 // the grouped instance of an elementwise stage of the general step (ma: the class's action bound; 0: a kernel without one)
@@ -399,37 +367,40 @@ static int group_build_mlp(sac_group *g) {
 // Same-shape and mixed groups: the variant classes and the stage list of the members' four-launch step.
 static int group_build_fused(sac_group *g) {
     const int R = g->R, algo = g->algo;
-    // the variant classes (the instance of launch A a member's own four-launch step runs), in order of first appearance;
-    // the device tables hold them one after another, each in member order
-    const void *key[4] = {};
+    // the variant classes (the (nth, wide) of a member's step plan), in order of first appearance; the device tables
+    // hold them one after another, each in member order
+    const sac_trainer *key[4] = {};
     for (int i = 0; i < R; ++i) {
-        const void *k = reinterpret_cast<const void *>(g->m[i]->fwd_a);
+        const sac_trainer *k = g->m[i];
         int c = 0;
-        while (c < g->ncls && key[c] != k) ++c;
+        while (c < g->ncls && !same_variant(key[c], k)) ++c;
         if (c == g->ncls) {
             if (g->ncls == 4) { sac::set_error("internal: more than four kernel variants in a trainer group"); return -1; }
             key[g->ncls++] = k;
         }
     }
-    // per class: its kernels, the largest member extents (member_extents) and the largest member LDS of launches A, B, C
+    // per class: its kernels (step_kernels), the largest member extents and the largest member LDS of launches A, B, C
     const void *ker[4][5] = {};
-    int xa[4] = {}, xb[4] = {}, xc[4] = {}, xpi[4] = {}, pos = 0;
-    size_t lds_fa[4] = {}, lds_fb[4] = {}, lds_bw[4] = {};
+    StepLaunch mx[4][5];                              // [class][launch a, b, c, b2, c2]
+    int pos = 0;
     for (int c = 0; c < g->ncls; ++c) {
         GroupClass &K = g->cls[c];
         K.lo = pos;
         for (int i = 0; i < R; ++i) {
             const sac_trainer *t = g->m[i];
-            if (reinterpret_cast<const void *>(t->fwd_a) != key[c]) continue;
+            if (!same_variant(t, key[c])) continue;
             g->ord[pos++] = i;
-            int a, b, cc, pi;
-            member_extents(t, algo, a, b, cc, pi);
-            xa[c] = std::max(xa[c], a); xb[c] = std::max(xb[c], b); xc[c] = std::max(xc[c], cc); xpi[c] = std::max(xpi[c], pi);
-            lds_fa[c] = std::max(lds_fa[c], t->lds_fa); lds_fb[c] = std::max(lds_fb[c], t->lds_fb);
-            lds_bw[c] = std::max(lds_bw[c], t->lds_bw);
+            const StepLaunch *const l[5] = {&t->plan.a, &t->plan.b, &t->plan.c, &t->plan.b2, &t->plan.c2};
+            for (int q = 0; q < 5; ++q) {
+                mx[c][q].grid = std::max(mx[c][q].grid, l[q]->grid);
+                mx[c][q].lds = std::max(mx[c][q].lds, l[q]->lds);
+            }
         }
         K.n = pos - K.lo;
-        if (!fused_group_kernels(g->m[g->ord[K.lo]], algo, ker[c])) {
+        const StepPlan &P0 = key[c]->plan;
+        const StepKernels sk = step_kernels(P0.nth, P0.wide, 4, algo, P0.chain8, P0.wide4);
+        for (int q = 0; q < 5; ++q) ker[c][q] = sk.group[q];
+        if (!ker[c][0]) {
             sac::set_error("internal: no grouped instance of the members' step kernels");
             return -1;
         }
@@ -442,27 +413,27 @@ static int group_build_fused(sac_group *g) {
         grid_dq = std::max(grid_dq, std::max(t->dw_q.njobs, t->dw_q_tp.njobs) + 1);
         grid_dpi = std::max(grid_dpi, t->dw_pi.njobs + 1);
     }
-    auto per_class = [&](int which, const int *gx, const size_t *lds, int need, int arg) {
+    auto per_class = [&](int which, int need, int arg) {
         GroupStage st;
         st.per_class = true; st.need = need; st.arg = arg;
-        for (int c = 0; c < g->ncls; ++c) { st.fn[c] = ker[c][which]; st.gx[c] = gx[c]; st.lds[c] = lds[c]; }
+        for (int c = 0; c < g->ncls; ++c) { st.fn[c] = ker[c][which]; st.gx[c] = mx[c][which].grid; st.lds[c] = mx[c][which].lds; }
         g->stages.push_back(st);
     };
     // the one-group form of the weight-gradient body where every member runs it solo (batch <= 256, not SAC_DW_FORM=loop)
     bool one = true;
-    for (int i = 0; i < R; ++i) one = one && g->m[i]->dw_one;
+    for (int i = 0; i < R; ++i) one = one && g->m[i]->plan.dw_one;
     auto for_all = [&](auto kernel, int gx, int need, bool idle_one) {
         GroupStage st;
         st.fn[0] = reinterpret_cast<const void *>(kernel); st.gx[0] = gx; st.need = need; st.idle_one = idle_one;
         g->stages.push_back(st);
     };
     if (algo == 0) {                                  // launch_step: A, B, C (compact: 3 * 4 * NB <= 192 for every member), dW
-        per_class(0, xa, lds_fa, 0, 0); per_class(1, xb, lds_fb, 0, 0); per_class(2, xc, lds_bw, 0, 1);
+        per_class(0, 0, 0); per_class(1, 0, 0); per_class(2, 0, 1);
         for_all(one ? &k_dw_adam_group<M_SAC, true> : &k_dw_adam_group<M_SAC, false>, grid_d, 0, false);
     } else {                                          // launch_step_td3: the critic pass, then the actor pass
-        per_class(0, xa, lds_fa, 0, 0); per_class(1, xb, lds_fb, 0, 0); per_class(2, xc, lds_bw, 0, 0);
+        per_class(0, 0, 0); per_class(1, 0, 0); per_class(2, 0, 0);
         for_all(one ? &k_dw_adam_group<M_TD3_CRITIC, true> : &k_dw_adam_group<M_TD3_CRITIC, false>, grid_dq, 0, false);
-        per_class(3, xpi, lds_fb, 1, 0); per_class(4, xpi, lds_bw, 2, 0);
+        per_class(3, 1, 0); per_class(4, 2, 0);
         for_all(one ? &k_dw_adam_group<M_TD3_ACTOR, true> : &k_dw_adam_group<M_TD3_ACTOR, false>, grid_dpi, 1, true);
     }
     for (const GroupStage &st : g->stages)
@@ -556,12 +527,7 @@ int sac_group_destroy(sac_group_t *g) {
     if (!g) return 0;
     (void)hipSetDevice(g->device);
     if (g->s) (void)hipStreamSynchronize(g->s);
-    {
-        FusedGate &G = g_gate[g->device & 63];
-        std::lock_guard<std::mutex> lk(G.mu);
-        G.live -= 1;
-        if (G.last == g->s || G.last == g->s2) G.last = nullptr;
-    }
+    gate_leave(g->device, true, g->s, g->s2);
     group_free(g);
     return 0;
 }
@@ -660,7 +626,7 @@ int sac_group_train_loop(sac_group_t *g, sac_buffer_t *const *bufs, int64_t n_st
             M.T_tp = t->dw_q_tp; M.T_pi = t->dw_pi; M.T_none = t->dw_none;
             M.T_tp.abort = M.T_pi.abort = M.T_none.abort = nullptr;
         }
-        member_extents(t, g->algo, M.xa, M.xb, M.xc, M.xpi);
+        M.xa = t->plan.a.grid; M.xb = t->plan.b.grid; M.xc = t->plan.c.grid; M.xpi = t->plan.b2.grid;
     }
     // the draw table in member order (one launch); the gather table sorted by gather class (one launch per class: the
     // obs chunks per thread, NIT = 1 / 2 / 4 / 8), each class in member order

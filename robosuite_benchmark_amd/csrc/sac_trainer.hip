@@ -41,7 +41,6 @@ namespace sac {
 
 typedef float f32x4 __attribute__((ext_vector_type(4)));
 
-constexpr int H = 256;            // hidden width (every shipped variant.json)
 constexpr float LOG_SIG_MAX = 2.0f, LOG_SIG_MIN = -20.0f, TANH_EPS = 1e-6f;
 constexpr float ADAM_B1 = 0.9f, ADAM_B2 = 0.999f, ADAM_EPS = 1e-8f;
 // torch computes 1 - beta in double and applies it as an fp32 scalar: (float)(1.0 - 0.9), (float)(1.0 - 0.999)
@@ -304,7 +303,6 @@ struct WRing {
 // `stage` != null: every weight fragment is also copied to LDS as it leaves the ring, TRANSPOSED: stage[k][row of W]
 // with row stride WLD (this wave's tile t owns columns 16 t ..), for a later contraction over the rows of W
 // (gemm_lds_rows) -- the same bytes a backward pass would otherwise fetch again from the transposed copy.
-constexpr int WLD = 64 + 4;       // 64 staged weight rows; +4: scatter writes and 16-B reads are bank-conflict free
 // ALT = false: a one-tile GEMM accumulates in ONE register like a tile of a four-tile GEMM does (bit-identical to it).
 template <bool STAGED = false, bool ALT = true, int NT, int D>
 __device__ __forceinline__ void gemm_ring(WRing<NT, D> &R, const float *X, int KL, int KS, f32x4 (&acc)[NT],
@@ -441,7 +439,6 @@ __device__ __forceinline__ void gemm_straight_pf(WRing<NT, D> &R, const float *X
         }
     }
 }
-constexpr int RD0 = 8;            // narrow first layers: up to 8 k-chunks (K <= 128) held at once
 
 // split-K epilogue: the four waves each hold a partial [16 x 16*NTT]; sum them through LDS into
 // `out` (row-major [16][ldo]) + bias.  red = 4*NTT*256 floats.
@@ -1889,6 +1886,60 @@ __global__ __launch_bounds__(256) void k_dw_adam_group(const GroupMember *__rest
 #include "sac_chain.h"
 #include "sac_general.h"
 
+// The one table from a step variant to its kernel instances.  a / b / c: launches A, B, C (SAC, or TD3's critic pass);
+// b2 / c2: TD3's actor pass; abc: the fused launch; chain: k_chain8 or k_chain; chain_bwd: k_chain8 with the backward
+// blocks inside; bwd8: launch C on eight waves (the last three: SAC only).  group[]: the grouped instances of a, b, c,
+// b2, c2 (column split 4 only).  `fused` is left to the trainer: abc or chain_bwd, as its plan says.
+using StepFnA = void (*)(Dev, const float *, SlotLayout, int);
+using StepFnB = void (*)(Dev, const float *, SlotLayout, StepArg);
+using StepFnC = void (*)(Dev, const float *, SlotLayout, StepArg, int);
+struct StepKernels {
+    StepFnA a = nullptr;
+    StepFnB b = nullptr, b2 = nullptr, abc = nullptr, chain = nullptr, chain_bwd = nullptr, fused = nullptr;
+    StepFnC c = nullptr, c2 = nullptr, bwd8 = nullptr;
+    const void *group[5] = {};
+};
+
+template <int NTH, bool W, int SP>
+void step_kernels_abc(StepKernels &k, int algo) {
+    auto fn = [](auto f) { return reinterpret_cast<const void *>(f); };
+    if (algo == 0) {
+        k.a = &k_fwd_a<NTH, W, SP>; k.b = &k_fwd_b<NTH, W, SP>; k.c = &k_bwd<NTH, SP>;
+        k.abc = &k_abc<NTH, W>;
+        if constexpr (SP == 4) {
+            k.group[0] = fn(&k_fwd_a_group<NTH, W, 4>); k.group[1] = fn(&k_fwd_b_group<NTH, W, 4>);
+            k.group[2] = fn(&k_bwd_group<NTH, 4>);
+        }
+    } else if constexpr (NTH == 1) {                  // (TD3's policy head is one tile: act_dim <= 16)
+        k.a = &k_fwd_a<1, W, SP, M_TD3_CRITIC>; k.b = &k_fwd_b<1, W, SP, M_TD3_CRITIC>; k.c = &k_bwd<1, SP, M_TD3_CRITIC>;
+        k.b2 = &k_fwd_b<1, W, SP, M_TD3_ACTOR>; k.c2 = &k_bwd<1, SP, M_TD3_ACTOR>;
+        k.abc = &k_abc<1, W, M_TD3_CRITIC>;
+        if constexpr (SP == 4) {
+            k.group[0] = fn(&k_fwd_a_group<1, W, 4, M_TD3_CRITIC>);
+            k.group[1] = fn(&k_fwd_b_group<1, W, 4, M_TD3_CRITIC>); k.group[3] = fn(&k_fwd_b_group<1, W, 4, M_TD3_ACTOR>);
+            k.group[2] = fn(&k_bwd_group<1, 4, M_TD3_CRITIC>); k.group[4] = fn(&k_bwd_group<1, 4, M_TD3_ACTOR>);
+        }
+    }
+}
+
+template <int NTH>
+StepKernels step_kernels_nth(bool wide, int sp, int algo, bool chain8, bool wide4) {
+    StepKernels k;
+    if (sp == 4) wide ? step_kernels_abc<NTH, true, 4>(k, algo) : step_kernels_abc<NTH, false, 4>(k, algo);
+    else if (sp == 2) wide ? step_kernels_abc<NTH, true, 2>(k, algo) : step_kernels_abc<NTH, false, 2>(k, algo);
+    else wide ? step_kernels_abc<NTH, true, 1>(k, algo) : step_kernels_abc<NTH, false, 1>(k, algo);
+    if (algo == 0) {
+        k.chain = chain8 ? (wide4 ? &k_chain8<NTH, true> : &k_chain8<NTH, false>) : (wide4 ? &k_chain<NTH, true> : &k_chain<NTH, false>);
+        k.chain_bwd = wide4 ? &k_chain8<NTH, true, true> : &k_chain8<NTH, false, true>;
+        k.bwd8 = &k_bwd8<NTH>;
+    }
+    return k;
+}
+
+static StepKernels step_kernels(int nth, bool wide, int sp, int algo, bool chain8, bool wide4) {
+    return nth == 1 ? step_kernels_nth<1>(wide, sp, algo, chain8, wide4) : step_kernels_nth<2>(wide, sp, algo, chain8, wide4);
+}
+
 }  // namespace sac
 
 // ==========================================================================================
@@ -1900,17 +1951,17 @@ struct sac_general;
 
 struct sac_trainer {
     sac_config_t cfg{};
-    int device = 0;
+    int device = 0, cus = 0;                          // cus: the device's CU count
     hipStream_t stream = nullptr;
-    int B = 0, Bt = 0, O = 0, A = 0, KP = 0, KQ = 0, NH = 0, NB = 0, SP = 4;   // B: batch padded to row-blocks, Bt: true batch
+    int B = 0, Bt = 0, O = 0, A = 0, KP = 0, KQ = 0, NH = 0, NB = 0;   // B: batch padded to row-blocks, Bt: true batch
+    StepPlan plan{};                                  // the step of the fused kernels' shapes: what it launches (written once at creation)
+    StepKernels k{};                                  // ... and the kernel instances behind it (c: k_bwd8 where the plan says so)
     Net net[6];                                       // 5: TD3 target policy
     int HP[2] = {256, 256}, HQ[2] = {256, 256};       // logical hidden sizes (<= 256: zero-padded to the kernels' 256)
     int algo = 0;                                     // 0 SAC, 1 TD3
     int td3_period = 2;                               // policy_and_target_update_period
     long long adam_t_pi = 0;                          // TD3: optimizer steps of the policy (delayed)
     DwTable dw_q{}, dw_q_tp{}, dw_pi{}, dw_none{};    // TD3 work tables: critics (without / with Polyak), policy, diagnostics only
-    void (*fwd_b2)(Dev, const float *, SlotLayout, StepArg) = nullptr;      // TD3 actor pass
-    void (*bwd2)(Dev, const float *, SlotLayout, StepArg, int) = nullptr;
     Dev dev{};
     DwTable dw{};
     DwLayer *d_dwl = nullptr;
@@ -1938,14 +1989,12 @@ struct sac_trainer {
     // general-step device acting (sac_act_general.h) and Q evaluation (sac_qval_general.h): the activations between two
     // layer launches ping-pong between these
     float *act_gen[2] = {nullptr, nullptr}; size_t act_gen_floats = 0;
-    size_t lds_bw = 0;
-    // fused step (k_abc, sac_fused.h): launches A + B + C as one launch with in-launch hand-offs
-    bool dw_one = false;                              // weight-gradient launch in its one-group form (batch <= 256; SAC_DW_FORM=loop: never)
+    // fused step (k_abc, sac_fused.h; k_chain8<.., BWD>, sac_chain.h): launches A + B + C as one launch with in-launch
+    // hand-offs.  Starts as plan.fused; a give-up or sac_trainer_set_xcd_mask clears it for good (trainer_drop_fused).
     bool fused = false;
     unsigned fused_seq = 0;                           // launches so far: the hand-off counters count in units of it
     unsigned fused_unchecked = 0;                     // fused launches since the host last looked at the abort marker
     bool publish_diag = true;                         // the next step's diagnostics go to the pinned host buffer (its caller reads them)
-    unsigned test_stall_at = 0;                       // SAC_FUSED_TEST_STALL=<n>: the n-th fused launch loses a producer (tests)
     // Fused steps launched by sac_step_device that the host has not yet seen applied: should one of them give up, these
     // are re-run on the four-launch step from their slots (still intact: the host never runs more than two groups of
     // sixteen steps ahead of the device on this path -- thr_ev, one event per sixteen steps).
@@ -1957,20 +2006,7 @@ struct sac_trainer {
     long long dev_steps = 0;                          // fused device-batch steps launched so far (sixteen per throttle event)
     hipEvent_t thr_ev[4] = {nullptr, nullptr, nullptr, nullptr};
     int fallbacks = 0;                                // times the fused step gave up (at most once: the fall-back is for good)
-    void (*abc)(Dev, const float *, SlotLayout, StepArg) = nullptr;
-    size_t lds_abc = 0;
-    int abc_grid = 0, abc_threads = 256;              // the fused launch's shape (k_abc: 16 NB x 256; k_chain8<.., BWD>: 4 NB x 512)
-    bool chain_bwd = false;                           // batch 1024: the fused launch is k_chain8 with the backward blocks inside
     unsigned *d_sync = nullptr; size_t sync_bytes = 0;   // counters (one per 128-B line) + abort word
-    void (*fwd_a)(Dev, const float *, SlotLayout, int) = nullptr;
-    void (*fwd_b)(Dev, const float *, SlotLayout, StepArg) = nullptr;
-    void (*bwd)(Dev, const float *, SlotLayout, StepArg, int) = nullptr;
-    size_t lds_fa = 0, lds_fb = 0;
-    // column split 1 (batch >= 1024): launches A + B as one launch without any hand-off (k_chain, sac_chain.h)
-    bool chain = false, chain8 = false;               // chain8: the eight-wave variant of k_chain (512 threads per workgroup)
-    bool bwd8 = false;                                // the backward launch at column split 1 on eight waves (k_bwd8, sac_bwd8.h)
-    void (*chaink)(Dev, const float *, SlotLayout, StepArg) = nullptr;
-    size_t lds_chain = 0;
     long long n_train_steps_total = 0, adam_t = 0;   // host-side step counters (rlkit _n_train_steps_total)
     // hidden_sizes beyond two layers of <= 256 units: the general step (sac_general.h); everything above that belongs to
     // the fused kernels stays unused
@@ -2092,17 +2128,36 @@ int ensure_stage_t(sac_trainer *t, size_t bytes) {
 struct FusedGate { std::mutex mu; hipEvent_t ev = nullptr; hipStream_t last = nullptr; int live = 0; };
 FusedGate g_gate[64];
 
+// a fused trainer or a trainer group becomes a tenant of its device's gate ...
+int gate_join(int device) {
+    FusedGate &G = g_gate[device & 63];
+    std::lock_guard<std::mutex> lk(G.mu);
+    if (!G.ev) SAC_HIP(hipEventCreateWithFlags(&G.ev, hipEventDisableTiming));
+    G.live += 1;
+    return 0;
+}
+
+// ... and leaves it (tenant = false: it held no tenancy, e.g. a trainer on CUs of its own); the gate forgets the streams
+// given, which are about to go away
+void gate_leave(int device, bool tenant = true, hipStream_t s = nullptr, hipStream_t s2 = nullptr) {
+    FusedGate &G = g_gate[device & 63];
+    std::lock_guard<std::mutex> lk(G.mu);
+    if (tenant) G.live -= 1;
+    if (G.last && (G.last == s || G.last == s2)) G.last = nullptr;
+}
+
 // the fused forward/backward launch of a step (k_abc: SAC, or the TD3 critic pass); sa gets the launch number
 int launch_fused_abc(sac_trainer *t, const float *S, const SlotLayout &SL, StepArg &sa, unsigned extra_flags) {
     hipStream_t s = t->stream;
     sa.seq = ++t->fused_seq;
-    sa.pad2 |= extra_flags | ((t->test_stall_at && sa.seq == t->test_stall_at) ? 1u : 0u);
+    sa.pad2 |= extra_flags | ((t->plan.test_stall_at && sa.seq == t->plan.test_stall_at) ? 1u : 0u);
     t->fused_unchecked += 1;
     FusedGate &G = g_gate[t->device & 63];
     std::lock_guard<std::mutex> lk(G.mu);
     const bool gate = G.live > 1 && !t->gate_exempt;
     if (gate && G.last && G.last != s) SAC_HIP(hipStreamWaitEvent(s, G.ev, 0));
-    hipLaunchKernelGGL(t->abc, dim3(t->abc_grid), dim3(t->abc_threads), t->lds_abc, s, t->dev, S, SL, sa);
+    const StepLaunch &F = t->plan.fused_launch;
+    hipLaunchKernelGGL(t->k.fused, dim3(F.grid), dim3(F.threads), F.lds, s, t->dev, S, SL, sa);
     if (gate) { SAC_HIP(hipEventRecord(G.ev, s)); G.last = s; }
     return 0;
 }
@@ -2110,7 +2165,7 @@ int launch_fused_abc(sac_trainer *t, const float *S, const SlotLayout &SL, StepA
 int launch_step_td3(sac_trainer *t, const float *S, const SlotLayout &SL, int j, bool want_stats) {
     const Dev &d = t->dev;
     hipStream_t s = t->stream;
-    const int NB = t->NB, SPv = t->SP;
+    const StepPlan &L = t->plan;
     const Td3Plan P = td3_plan(t, 0, 0, want_stats);
     const bool pstep = P.pstep, actor = P.actor;
     // (the diagnostics -- and the flat gradient copies of sac_debug_fetch -- go out only on the steps whose caller reads
@@ -2121,21 +2176,20 @@ int launch_step_td3(sac_trainer *t, const float *S, const SlotLayout &SL, int j,
         // the critic pass as ONE launch (k_abc<.., M_TD3_CRITIC>, sac_fused.h) + its weight-gradient launch
         if (launch_fused_abc(t, S, SL, sq, actor ? 4u : 0u)) return -1;
     } else {
-        hipLaunchKernelGGL(t->fwd_a, dim3(4 * SPv * NB), dim3(256), t->lds_fa, s, d, S, SL, actor ? 1 : 0);
-        const unsigned g2 = 8u * (unsigned)((SPv * NB + 3) / 4);      // two twins x groups of four blocks (k_fwd_b / k_bwd, TD3 critic map)
-        hipLaunchKernelGGL(t->fwd_b, dim3(g2), dim3(256), t->lds_fb, s, d, S, SL, sq);
-        hipLaunchKernelGGL(t->bwd, dim3(g2), dim3(256), t->lds_bw, s, d, S, SL, sq, 0);
+        hipLaunchKernelGGL(t->k.a, dim3(L.a.grid), dim3(L.a.threads), L.a.lds, s, d, S, SL, actor ? 1 : 0);
+        hipLaunchKernelGGL(t->k.b, dim3(L.b.grid), dim3(L.b.threads), L.b.lds, s, d, S, SL, sq);
+        hipLaunchKernelGGL(t->k.c, dim3(L.c.grid), dim3(L.c.threads), L.c.lds, s, d, S, SL, sq, 0);
     }
     const DwTable &Tq = pstep ? t->dw_q_tp : t->dw_q;
-    hipLaunchKernelGGL(t->dw_one ? k_dw_adam_one : k_dw_adam, dim3(Tq.njobs + 1), dim3(256), 0, s, d, Tq, S, sq);
+    hipLaunchKernelGGL(t->plan.dw_one ? k_dw_adam_one : k_dw_adam, dim3(Tq.njobs + 1), dim3(256), 0, s, d, Tq, S, sq);
     if (actor) {
-        hipLaunchKernelGGL(t->fwd_b2, dim3(SPv * NB), dim3(256), t->lds_fb, s, d, S, SL, sp);
+        hipLaunchKernelGGL(t->k.b2, dim3(L.b2.grid), dim3(L.b2.threads), L.b2.lds, s, d, S, SL, sp);
         if (pstep) {
-            hipLaunchKernelGGL(t->bwd2, dim3(SPv * NB), dim3(256), t->lds_bw, s, d, S, SL, sp, 0);
-            hipLaunchKernelGGL(t->dw_one ? k_dw_adam_one : k_dw_adam, dim3(t->dw_pi.njobs + 1), dim3(256), 0, s, d, t->dw_pi, S, sp);
+            hipLaunchKernelGGL(t->k.c2, dim3(L.c2.grid), dim3(L.c2.threads), L.c2.lds, s, d, S, SL, sp, 0);
+            hipLaunchKernelGGL(t->plan.dw_one ? k_dw_adam_one : k_dw_adam, dim3(t->dw_pi.njobs + 1), dim3(256), 0, s, d, t->dw_pi, S, sp);
             t->adam_t_pi += 1;
         } else {
-            hipLaunchKernelGGL(t->dw_one ? k_dw_adam_one : k_dw_adam, dim3(1), dim3(256), 0, s, d, t->dw_none, S, sp);      // statistics only
+            hipLaunchKernelGGL(t->plan.dw_one ? k_dw_adam_one : k_dw_adam, dim3(1), dim3(256), 0, s, d, t->dw_none, S, sp);      // statistics only
         }
     }
     SAC_HIP(hipGetLastError());
@@ -2152,30 +2206,28 @@ int launch_step(sac_trainer *t, const float *S, const SlotLayout &SL, int j, hip
     if (t->algo == 1) return launch_step_td3(t, S, SL, j, want_stats);
     const Dev &d = t->dev;
     hipStream_t s = t->stream;
-    const int NB = t->NB;
+    const StepPlan &L = t->plan;
     StepArg sa = step_arg(t->n_train_steps_total, t->adam_t + 1, j, 0, t->publish_diag);
-    const int SPv = t->SP;
     if (ev) SAC_HIP(hipEventRecord(ev[0], s));
     if (t->fused) {
         // two launches: A + B + C as k_abc (in-launch hand-offs), then the weight-gradient / Adam launch
         if (launch_fused_abc(t, S, SL, sa, 0u)) return -1;
         if (ev) { SAC_HIP(hipEventRecord(ev[1], s)); SAC_HIP(hipEventRecord(ev[2], s)); SAC_HIP(hipEventRecord(ev[3], s)); }
     } else {
-        if (t->chain) {
-            hipLaunchKernelGGL(t->chaink, dim3(4 * NB), dim3(t->chain8 ? 512 : 256), t->lds_chain, s, d, S, SL, sa);
+        if (L.chain) {
+            hipLaunchKernelGGL(t->k.chain, dim3(L.chained.grid), dim3(L.chained.threads), L.chained.lds, s, d, S, SL, sa);
             if (ev) { SAC_HIP(hipEventRecord(ev[1], s)); SAC_HIP(hipEventRecord(ev[2], s)); }
         } else {
-            hipLaunchKernelGGL(t->fwd_a, dim3(4 * SPv * NB), dim3(256), t->lds_fa, s, d, S, SL, 0);
+            hipLaunchKernelGGL(t->k.a, dim3(L.a.grid), dim3(L.a.threads), L.a.lds, s, d, S, SL, 0);
             if (ev) SAC_HIP(hipEventRecord(ev[1], s));
-            hipLaunchKernelGGL(t->fwd_b, dim3(4 * SPv * NB), dim3(256), t->lds_fb, s, d, S, SL, sa);
+            hipLaunchKernelGGL(t->k.b, dim3(L.b.grid), dim3(L.b.threads), L.b.lds, s, d, S, SL, sa);
             if (ev) SAC_HIP(hipEventRecord(ev[2], s));
         }
-        const int compact = (3 * SPv * NB <= 192) ? 1 : 0;     // see k_bwd
-        hipLaunchKernelGGL(t->bwd, dim3(compact ? 4 * SPv * NB : 3 * SPv * NB), dim3(t->bwd8 ? 512 : 256), t->lds_bw, s, d, S, SL, sa, compact);
+        hipLaunchKernelGGL(t->k.c, dim3(L.c.grid), dim3(L.c.threads), L.c.lds, s, d, S, SL, sa, L.compact);
         if (ev) SAC_HIP(hipEventRecord(ev[3], s));
     }
     if (ev) SAC_HIP(hipEventRecord(ev[4], s));
-    hipLaunchKernelGGL(t->dw_one ? k_dw_adam_one : k_dw_adam, dim3(t->dw.njobs + 1), dim3(256), 0, s, d, t->dw, S, sa);
+    hipLaunchKernelGGL(t->plan.dw_one ? k_dw_adam_one : k_dw_adam, dim3(t->dw.njobs + 1), dim3(256), 0, s, d, t->dw, S, sa);
     if (ev) { SAC_HIP(hipEventRecord(ev[5], s)); SAC_HIP(hipEventRecord(ev[6], s)); }
     SAC_HIP(hipGetLastError());
     t->n_train_steps_total += 1;
@@ -2200,6 +2252,14 @@ static int wait_trainer_stream(sac_trainer *t, hipEvent_t recorded = nullptr) {
 // every weight-gradient table of the trainer looks at (or stops looking at) the fused step's give-up word
 static void set_abort_ptrs(sac_trainer *t, const unsigned *p) {
     t->dw.abort = p; t->dw_q.abort = p; t->dw_q_tp.abort = p; t->dw_pi.abort = p; t->dw_none.abort = p;
+}
+
+// the fused step is dropped for good: the trainer goes on with the plan's a / b / c (or chained / c) launches
+static void trainer_drop_fused(sac_trainer *t) {
+    t->fused = false;
+    set_abort_ptrs(t, nullptr);
+    if (!t->gate_exempt) gate_leave(t->device);
+    t->gate_exempt = false;
 }
 
 // wait for ONE event (not for the stream behind it): a short user-space poll, then the blocking wait
@@ -2230,8 +2290,6 @@ int check_fused_abort(sac_trainer *t, unsigned *lost_out = nullptr) {
     if (lost > launched) lost = launched;
     t->n_train_steps_total -= lost;
     t->adam_t -= lost;
-    t->fused = false;
-    set_abort_ptrs(t, nullptr);
     if (t->algo == 1) {          // TD3: the policy's optimizer steps among the lost steps (every td3_period-th step number)
         for (long long k = t->n_train_steps_total; k < t->n_train_steps_total + (long long)lost; ++k)
             if (k % t->td3_period == 0) t->adam_t_pi -= 1;
@@ -2239,12 +2297,7 @@ int check_fused_abort(sac_trainer *t, unsigned *lost_out = nullptr) {
     t->h_diag[SAC_DIAG_N + 30] = t->h_diag[SAC_DIAG_N + 31] = 0.f;
     SAC_HIP(hipMemsetAsync(t->d_sync, 0, t->sync_bytes, t->stream));
     SAC_HIP(hipStreamSynchronize(t->stream));
-    if (!t->gate_exempt) {
-        FusedGate &G = g_gate[t->device & 63];
-        std::lock_guard<std::mutex> lk(G.mu);
-        G.live -= 1;
-    }
-    t->gate_exempt = false;
+    trainer_drop_fused(t);
     t->fallbacks += 1;
     if (lost_out) *lost_out = lost;
     fprintf(stderr, "[libsac_hip] warning: the fused SAC step gave up -- a hand-off between its workgroups timed out (is another "
@@ -2322,12 +2375,14 @@ int sac_trainer_create(sac_trainer_t **out, const sac_config_t *cfg) {
     return trainer_create(out, cfg, nullptr);
 }
 
-// TD3 (SURVEY.md 8f row 4; /root/reference/util/rlkit_utils.py:107-135, scripts/train.py:38-47): the same handle
-// type and the same sac_* accessors; net id 5 is the target policy.
-int td3_trainer_create(sac_trainer_t **out, const td3_config_t *c) {
-    SAC_REQUIRE(out && c, "null argument to td3_trainer_create");
+static int admit_td3(const td3_config_t *c) {
     SAC_REQUIRE(c->policy_and_target_update_period > 0, "policy_and_target_update_period must be positive");
     SAC_REQUIRE(c->target_policy_noise >= 0.f && c->target_policy_noise_clip >= 0.f, "negative target policy noise");
+    return 0;
+}
+
+// a TD3 configuration as the SAC one the trainer is built from (no entropy term, targets follow every policy step)
+static sac_config_t td3_as_sac_config(const td3_config_t *c) {
     sac_config_t s{};
     s.obs_dim = c->obs_dim; s.act_dim = c->act_dim; s.hidden = c->hidden; s.batch = c->batch;
     for (int i = 0; i < 2; ++i) { s.policy_hidden[i] = c->policy_hidden[i]; s.qf_hidden[i] = c->qf_hidden[i]; }
@@ -2335,15 +2390,15 @@ int td3_trainer_create(sac_trainer_t **out, const td3_config_t *c) {
     s.policy_lr = c->policy_learning_rate; s.qf_lr = c->qf_learning_rate;
     s.soft_target_tau = c->tau; s.target_update_period = 1; s.use_automatic_entropy_tuning = 0;
     s.target_entropy = 0.f; s.noise_seed = c->noise_seed; s.device = c->device;
-    return trainer_create(out, &s, c);
+    return s;
 }
 
-static int trainer_build(sac_trainer *t, const sac_config_t *cfg, const td3_config_t *td3);
-
-static int trainer_create(sac_trainer_t **out, const sac_config_t *cfg, const td3_config_t *td3) {
-    *out = nullptr;
+// What every create entry refuses, in the order a call with several faults is refused.  general: a trainer of the
+// general step (no bound on its hidden sizes here; its TD3 checks, td3 != null, come behind the device's).
+static int admit_trainer(const sac_config_t *cfg, const td3_config_t *td3, bool general) {
     SAC_REQUIRE(sac_device_count() > 0, "no HIP device visible: libsac_hip has no CPU fallback");
-    for (int i = 0; i < 2; ++i) {
+    if (td3) { if (int rc = admit_td3(td3)) return rc; }
+    for (int i = 0; i < 2 && !general; ++i) {
         const int hp = cfg->policy_hidden[i] ? cfg->policy_hidden[i] : cfg->hidden, hq = cfg->qf_hidden[i] ? cfg->qf_hidden[i] : cfg->hidden;
         SAC_REQUIRE(hp >= 1 && hp <= H && hq >= 1 && hq <= H,
                     "hidden sizes policy %d / qf %d unsupported: two hidden layers of 1..256 units each (wider or deeper "
@@ -2351,10 +2406,29 @@ static int trainer_create(sac_trainer_t **out, const sac_config_t *cfg, const td
     }
     SAC_REQUIRE(cfg->obs_dim > 0 && cfg->act_dim > 0 && cfg->act_dim <= 16,
                 "unsupported dims obs=%d act=%d (act_dim must be in 1..16)", cfg->obs_dim, cfg->act_dim);
-    SAC_REQUIRE(cfg->obs_dim <= 496, "obs_dim %d unsupported: the row staging of the step kernels holds cat(obs, act) rows of at "
-                "most 512 columns (obs_dim <= 496; the shipped tasks reach 379)", cfg->obs_dim);
+    SAC_REQUIRE(cfg->obs_dim <= 496, "obs_dim %d unsupported%s", cfg->obs_dim,
+                general ? " (the minibatch slots hold cat(obs, act) rows of at most 512 columns)"
+                        : ": the row staging of the step kernels holds cat(obs, act) rows of at most 512 columns (obs_dim <= 496; "
+                          "the shipped tasks reach 379)");
     SAC_REQUIRE(cfg->batch > 0, "batch size %d must be positive", cfg->batch);
     SAC_REQUIRE(cfg->target_update_period > 0, "target_update_period must be positive");
+    return 0;
+}
+
+// TD3 (SURVEY.md 8f row 4; /root/reference/util/rlkit_utils.py:107-135, scripts/train.py:38-47): the same handle
+// type and the same sac_* accessors; net id 5 is the target policy.
+int td3_trainer_create(sac_trainer_t **out, const td3_config_t *c) {
+    SAC_REQUIRE(out && c, "null argument to td3_trainer_create");
+    if (int rc = admit_td3(c)) return rc;
+    const sac_config_t s = td3_as_sac_config(c);
+    return trainer_create(out, &s, c);
+}
+
+static int trainer_build(sac_trainer *t, const sac_config_t *cfg, const td3_config_t *td3);
+
+static int trainer_create(sac_trainer_t **out, const sac_config_t *cfg, const td3_config_t *td3) {
+    *out = nullptr;
+    if (int rc = admit_trainer(cfg, nullptr, false)) return rc;
     SAC_HIP(hipSetDevice(cfg->device));
     sac_trainer *t = new sac_trainer();
     if (trainer_build(t, cfg, td3)) {        // (the error message is already set)
@@ -2368,6 +2442,7 @@ static int trainer_create(sac_trainer_t **out, const sac_config_t *cfg, const td
 // what every kind of trainer has: stream, events, the pinned diagnostics
 static int trainer_common_init(sac_trainer *t, const sac_config_t *cfg) {
     t->cfg = *cfg; t->device = cfg->device;
+    SAC_HIP(hipDeviceGetAttribute(&t->cus, hipDeviceAttributeMultiprocessorCount, t->device));
     t->Bt = cfg->batch; t->B = round_up(cfg->batch, RB); t->O = cfg->obs_dim; t->A = cfg->act_dim;
     SAC_HIP(hipStreamCreateWithFlags(&t->stream, hipStreamNonBlocking));
     sac::stream_register(t->stream);
@@ -2397,26 +2472,10 @@ static int trainer_prime_events(sac_trainer *t) {
     return 0;
 }
 
-static int trainer_build(sac_trainer *t, const sac_config_t *cfg, const td3_config_t *td3) {
-    if (trainer_common_init(t, cfg)) return -1;
-    t->algo = td3 ? 1 : 0;
-    for (int i = 0; i < 2; ++i) {
-        t->HP[i] = cfg->policy_hidden[i] ? cfg->policy_hidden[i] : cfg->hidden;
-        t->HQ[i] = cfg->qf_hidden[i] ? cfg->qf_hidden[i] : cfg->hidden;
-    }
-    if (td3) t->td3_period = td3->policy_and_target_update_period;
-    t->KP = round_up(t->O, 16); t->KQ = t->KP + 16; t->NH = round_up((td3 ? 1 : 2) * t->A, 16);
-    t->NB = t->B / 16;
-    // column split: small batches spread every 256-wide layer over 4 workgroups per row-block; once the
-    // row-blocks alone fill the 256 CUs (B >= 512) fewer, fatter workgroups win.  SP*NB stays even (XCD map).
-    t->SP = (t->NB <= 16) ? 4 : (t->NB <= 32 ? 2 : ((t->NB & 1) ? 2 : 1));
-    if (const char *e = getenv("SAC_FORCE_SP")) {       // tuning experiments only
-        const int v = atoi(e);
-        if ((v == 1 || v == 2 || v == 4) && ((v * t->NB) % 2 == 0)) t->SP = v;
-    }
+// the arena (parameters, optimizer state, workspace, counters) and the device view of it
+static int trainer_alloc(sac_trainer *t, const sac_config_t *cfg, const td3_config_t *td3) {
     hipStream_t s = t->stream;
     const int B = t->B;
-
     Arena arena;
     g_arena = &arena;
     const int shp[3][2] = {{H, t->O}, {H, H}, {(td3 ? 1 : 2) * t->A, H}};
@@ -2467,7 +2526,7 @@ static int trainer_build(sac_trainer *t, const sac_config_t *cfg, const td3_conf
     d.auto_alpha = cfg->use_automatic_entropy_tuning; d.noise_seed = cfg->noise_seed;
     d.ctl = t->d_ctl;
     for (int i = 0; i < 6; ++i) d.P[i] = (i < nnets) ? t->net[i].P : nullptr;
-    d.algo = t->algo; d.sp = t->SP;
+    d.algo = t->algo; d.sp = t->plan.SP;
     d.td3_sigma = td3 ? td3->target_policy_noise : 0.f;
     d.td3_clip = td3 ? td3->target_policy_noise_clip : 0.f;
     for (int i = 0; i < 3; ++i) d.PT[i] = t->net[i].PT;
@@ -2478,6 +2537,13 @@ static int trainer_build(sac_trainer *t, const sac_config_t *cfg, const td3_conf
     d.cnt = t->d_sync;
     d.abort_flag = t->d_sync + (size_t)CNT_STRIDE * (5 * t->NB + 1);
 
+    return 0;
+}
+
+static int trainer_dw_tables(sac_trainer *t, const sac_config_t *cfg, const td3_config_t *td3) {
+    hipStream_t s = t->stream;
+    const int B = t->B;
+    const Dev &d = t->dev;
     // weight-gradient work tables: the 256x256 layers first (longest jobs).  SAC: one table (3 nets).  TD3: the two
     // critics without / with the Polyak targets (the soft update follows the critics' step on policy steps only),
     // the policy (Polyak target = target policy), and an empty one (diagnostics block only).
@@ -2539,177 +2605,90 @@ static int trainer_build(sac_trainer *t, const sac_config_t *cfg, const td3_conf
     }
     SAC_HIP(hipMemcpyAsync(t->d_dwl, hl.data(), sizeof(DwLayer) * hl.size(), hipMemcpyHostToDevice, s));
     SAC_HIP(hipStreamSynchronize(s));      // hl is a local
+    return 0;
+}
 
-    const int KL0q = round_up(t->KQ, 64);
-    const int nth = t->NH / 16;
-    const int sw = 64 * (4 / t->SP);
-    t->lds_fa = sizeof(float) * (size_t)(RB * KL0q + RB * H + RB * sw + 4 * nth * 256);
-    t->lds_fb = sizeof(float) * (size_t)(RB * KL0q + RB * H + RB * sw + 1024 + (t->SP == 4 ? H * WLD : 0));
-    t->lds_bw = sizeof(float) * (size_t)(RB * 64 + RB * H);
-    SAC_REQUIRE(t->lds_fa <= 160 * 1024 - 512, "observation too wide for the LDS row-block budget (obs_dim=%d)", t->O);
-    int wide_min = 16 * RD0 + 1;                       // (SAC_WIDE_MIN_KQ: tuning experiments only)
-    if (const char *e = getenv("SAC_WIDE_MIN_KQ")) wide_min = atoi(e);
-    const bool wide = t->KQ >= wide_min;
-#define SAC_PICK(SPV)                                                                                      \
-    do {                                                                                                   \
-        t->fwd_a = (nth == 1) ? (wide ? &k_fwd_a<1, true, SPV> : &k_fwd_a<1, false, SPV>)                   \
-                              : (wide ? &k_fwd_a<2, true, SPV> : &k_fwd_a<2, false, SPV>);                  \
-        t->fwd_b = (nth == 1) ? (wide ? &k_fwd_b<1, true, SPV> : &k_fwd_b<1, false, SPV>)                   \
-                              : (wide ? &k_fwd_b<2, true, SPV> : &k_fwd_b<2, false, SPV>);                  \
-        t->bwd = (nth == 1) ? &k_bwd<1, SPV> : &k_bwd<2, SPV>;                                             \
-    } while (0)
-#define TD3_PICK(SPV)                                                                                      \
-    do {                                                                                                   \
-        t->fwd_a = wide ? &k_fwd_a<1, true, SPV, M_TD3_CRITIC> : &k_fwd_a<1, false, SPV, M_TD3_CRITIC>;     \
-        t->fwd_b = wide ? &k_fwd_b<1, true, SPV, M_TD3_CRITIC> : &k_fwd_b<1, false, SPV, M_TD3_CRITIC>;     \
-        t->fwd_b2 = wide ? &k_fwd_b<1, true, SPV, M_TD3_ACTOR> : &k_fwd_b<1, false, SPV, M_TD3_ACTOR>;      \
-        t->bwd = &k_bwd<1, SPV, M_TD3_CRITIC>;                                                             \
-        t->bwd2 = &k_bwd<1, SPV, M_TD3_ACTOR>;                                                             \
-    } while (0)
-    if (!td3) {
-        if (t->SP == 4) SAC_PICK(4);
-        else if (t->SP == 2) SAC_PICK(2);
-        else SAC_PICK(1);
-    } else {
-        if (t->SP == 4) TD3_PICK(4);
-        else if (t->SP == 2) TD3_PICK(2);
-        else TD3_PICK(1);
+// a launch that asks for more dynamic LDS than a kernel gets by default (a fused launch: always) has the limit raised
+static int raise_lds(const void *fn, const StepLaunch &l, bool always = false) {
+    if (always || l.lds > LDS_DEFAULT) SAC_HIP(hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)l.lds));
+    return 0;
+}
+
+// the trainer's step becomes the plan's fused launch: every weight-gradient table looks at its give-up word, and the
+// trainer is a tenant of the device's fused-launch gate
+static int trainer_make_fused(sac_trainer *t) {
+    if (raise_lds(reinterpret_cast<const void *>(t->k.fused), t->plan.fused_launch, true)) return -1;
+    set_abort_ptrs(t, t->dev.abort_flag);
+    if (gate_join(t->device)) return -1;
+    t->fused = true;
+    return 0;
+}
+
+// the plan's kernel instances, with the LDS limits its launches need
+static int trainer_bind(sac_trainer *t) {
+    const StepPlan &P = t->plan;
+    auto fn = [](auto f) { return reinterpret_cast<const void *>(f); };
+    t->k = step_kernels(P.nth, P.wide, P.SP, P.algo, P.chain8, P.wide4);
+    if (P.bwd8) t->k.c = t->k.bwd8;
+    t->k.fused = P.chain_bwd ? t->k.chain_bwd : t->k.abc;
+    if (P.fused && trainer_make_fused(t)) return -1;
+    if (P.chain && raise_lds(fn(t->k.chain), P.chained)) return -1;
+    if (raise_lds(fn(t->k.a), P.a) || raise_lds(fn(t->k.b), P.b)) return -1;
+    if (t->k.b2 && raise_lds(fn(t->k.b2), P.b2)) return -1;
+    return 0;
+}
+
+static int trainer_build(sac_trainer *t, const sac_config_t *cfg, const td3_config_t *td3) {
+    if (trainer_common_init(t, cfg)) return -1;
+    t->algo = td3 ? 1 : 0;
+    for (int i = 0; i < 2; ++i) {
+        t->HP[i] = cfg->policy_hidden[i] ? cfg->policy_hidden[i] : cfg->hidden;
+        t->HQ[i] = cfg->qf_hidden[i] ? cfg->qf_hidden[i] : cfg->hidden;
     }
-#undef SAC_PICK
-#undef TD3_PICK
-    // The fused step (sac_fused.h) needs: SAC, column split 4 (at most 16 row-blocks), and every one of its 16*NB
-    // workgroups resident at once (one per CU: 100-160 KB of LDS each, which also bounds obs_dim to ~1000).  SAC_FUSED=0 selects the
-    // four-launch step (co-tenant processes on one GPU; ablations).
-    {   // the weight-gradient launch: one group of four batch chunks per wave covers 256 rows => its straight-line form
-        // (dw_adam_body<true>); SAC_DW_FORM=loop keeps the loop form at every batch size (ablations, tests)
-        const char *e = getenv("SAC_DW_FORM");
-        t->dw_one = d.B / 16 <= 16 && !(e && strcmp(e, "loop") == 0);
-    }
-    {
-        int cus = 0;
-        SAC_HIP(hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, t->device));
-        const char *e = getenv("SAC_FUSED");
-        t->lds_abc = sizeof(float) * (size_t)(RB * KL0q + RB * H + RB * 64 + FUSED_RED + H * WLD);
-        t->fused = t->SP == 4 && t->NB <= 16 && 16 * t->NB <= cus && t->lds_abc <= 160 * 1024 - 512 && !(e && atoi(e) == 0);
-        if (const char *ts = getenv("SAC_FUSED_TEST_STALL")) t->test_stall_at = (unsigned)atoi(ts);
-        if (td3) t->abc = wide ? &k_abc<1, true, M_TD3_CRITIC> : &k_abc<1, false, M_TD3_CRITIC>;
-        else t->abc = (nth == 1) ? (wide ? &k_abc<1, true> : &k_abc<1, false>) : (wide ? &k_abc<2, true> : &k_abc<2, false>);
-        t->abc_grid = 16 * t->NB; t->abc_threads = 256;
-        if (t->fused) {
-            SAC_HIP(hipFuncSetAttribute(reinterpret_cast<const void *>(t->abc), hipFuncAttributeMaxDynamicSharedMemorySize,
-                                        (int)t->lds_abc));
-            set_abort_ptrs(t, d.abort_flag);
-            FusedGate &G = g_gate[t->device & 63];
-            std::lock_guard<std::mutex> lk(G.mu);
-            if (!G.ev) SAC_HIP(hipEventCreateWithFlags(&G.ev, hipEventDisableTiming));
-            G.live += 1;
-        }
-    }
-    {   // column split 1: the forward launches as one (sac_chain.h); SAC_CHAIN=0: the four-launch step (A/B comparisons)
-        const char *e = getenv("SAC_CHAIN");
-        t->lds_chain = sizeof(float) * (size_t)(RB * KL0q + 2 * RB * H + 4 * nth * 256 + RB * 32);
-        // Where it pays (measured, scripts/large_batch_matrix.sh; round 3's second half with the eight-wave kernel): first layers
-        // of at most eight k-chunks -- Door 46/7 batch 1024 58.1 -> 51.8 us per step, TwoArmHandoff 86/14 64.9 -> 60.9, and
-        // now batches of more than one round of workgroups too (Door batch 1536 87.7 -> 83.9, batch 2048 95.3 -> 91.7: the
-        // four-wave kernel's 350 registers lost there); Wipe's 25-chunk first layers (recomputed by both P items) still lose
-        // (83.4 against 86.6).
-        int cus = 0;
-        SAC_HIP(hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, t->device));
-        const char *e8 = getenv("SAC_CHAIN8");                // (A/B comparisons: 0 = the four-wave kernel)
-        t->chain8 = !(e8 && atoi(e8) == 0);
-        const bool pays = ((t->chain8 || 4 * t->NB <= cus) && t->KQ <= 128) || (e && atoi(e) == 1);
-        t->chain = !td3 && !t->fused && t->SP == 1 && (t->NB % 2) == 0 && t->lds_chain <= 160 * 1024 - 512 && pays && !(e && atoi(e) == 0);
-        {
-            const bool wide4 = t->KQ > 64;       // first layers of more than four k-chunks
-            t->chaink = (nth == 1) ? (wide4 ? &k_chain<1, true> : &k_chain<1, false>) : (wide4 ? &k_chain<2, true> : &k_chain<2, false>);
-            if (t->chain8)
-                t->chaink = (nth == 1) ? (wide4 ? &k_chain8<1, true> : &k_chain8<1, false>) : (wide4 ? &k_chain8<2, true> : &k_chain8<2, false>);
-        }
-        {   // column split 1, SAC: the backward launch on eight waves too (SAC_BWD8=0: the four-wave kernel, A/B comparisons)
-            const char *eb = getenv("SAC_BWD8");
-            t->bwd8 = !td3 && t->SP == 1 && !(eb && atoi(eb) == 0);
-            if (t->bwd8) t->bwd = (nth == 1) ? &k_bwd8<1> : &k_bwd8<2>;
-        }
-        {   // one round of workgroups (batch 1024): the backward blocks inside the forward launch behind in-launch hand-offs
-            // (k_chain8<.., BWD>, sac_chain.h) -- a fused step like k_abc's: same give-up protocol, same fall-back (to k_chain8 + k_bwd8)
-            // Where it pays (A/B on one box, 2 x 2000 steps): exactly one workgroup per CU and narrow first layers -- Door 46/7
-            // batch 1024 19 290 -> 19 860 steps/s (the launch 33.6 us for 22.3 + 10.6 + a boundary); TwoArmHandoff 86/14 batch 1024
-            // -3.5 %, batch 992 -3 %, batch 800 -8 % (fewer workgroups than CUs: the separate backward launch was spreading its
-            // 192 blocks over idle CUs).  SAC_CHAIN_BWD=1 / 0 forces it (any batch whose workgroups are all resident) / off.
-            const char *ecb = getenv("SAC_CHAIN_BWD");
-            const bool pays_b = 4 * t->NB == cus && t->KQ <= 64;
-            t->chain_bwd = t->chain && t->chain8 && t->bwd8 && 4 * t->NB <= cus && (ecb ? atoi(ecb) == 1 : pays_b);
-            if (t->chain_bwd) {
-                const bool wide4 = t->KQ > 64;
-                t->abc = (nth == 1) ? (wide4 ? &k_chain8<1, true, true> : &k_chain8<1, false, true>)
-                                    : (wide4 ? &k_chain8<2, true, true> : &k_chain8<2, false, true>);
-                t->lds_abc = t->lds_chain > sizeof(float) * (size_t)(RB * 64 + RB * H) ? t->lds_chain : sizeof(float) * (size_t)(RB * 64 + RB * H);
-                t->abc_grid = 4 * t->NB; t->abc_threads = 512;
-                t->fused = true;
-                if (const char *ts = getenv("SAC_FUSED_TEST_STALL")) t->test_stall_at = (unsigned)atoi(ts);
-                SAC_HIP(hipFuncSetAttribute(reinterpret_cast<const void *>(t->abc), hipFuncAttributeMaxDynamicSharedMemorySize, (int)t->lds_abc));
-                set_abort_ptrs(t, d.abort_flag);
-                FusedGate &G = g_gate[t->device & 63];
-                std::lock_guard<std::mutex> lk(G.mu);
-                if (!G.ev) SAC_HIP(hipEventCreateWithFlags(&G.ev, hipEventDisableTiming));
-                G.live += 1;
-            }
-        }
-        if (t->chain && t->lds_chain > 64 * 1024)
-            SAC_HIP(hipFuncSetAttribute(reinterpret_cast<const void *>(t->chaink), hipFuncAttributeMaxDynamicSharedMemorySize,
-                                        (int)t->lds_chain));
-    }
-    if (t->lds_fa > 64 * 1024)
-        SAC_HIP(hipFuncSetAttribute(reinterpret_cast<const void *>(t->fwd_a),
-                                    hipFuncAttributeMaxDynamicSharedMemorySize, (int)t->lds_fa));
-    if (t->lds_fb > 64 * 1024) {
-        SAC_HIP(hipFuncSetAttribute(reinterpret_cast<const void *>(t->fwd_b),
-                                    hipFuncAttributeMaxDynamicSharedMemorySize, (int)t->lds_fb));
-        if (t->fwd_b2)
-            SAC_HIP(hipFuncSetAttribute(reinterpret_cast<const void *>(t->fwd_b2),
-                                        hipFuncAttributeMaxDynamicSharedMemorySize, (int)t->lds_fb));
-    }
-    SAC_REQUIRE(t->lds_fb <= 160 * 1024 - 512, "observation too wide for the LDS row-block budget (obs_dim=%d)", t->O);
+    if (td3) t->td3_period = td3->policy_and_target_update_period;
+    t->plan = step_plan(t->O, t->A, t->Bt, t->algo, t->cus, step_env_from_environment());
+    const StepPlan &P = t->plan;
+    SAC_REQUIRE(P.ok, "observation too wide for the LDS row-block budget (obs_dim=%d)", t->O);
+    t->KP = P.KP; t->KQ = P.KQ; t->NH = P.NH; t->NB = P.NB;
+    if (trainer_alloc(t, cfg, td3) || trainer_dw_tables(t, cfg, td3) || trainer_bind(t)) return -1;
     return trainer_prime_events(t);
 }
 
 // hidden_sizes of any depth (sac_hip.h): shapes the fused kernels carry -- two hidden layers of at most 256 units per
 // family -- get them; everything else gets the general step (sac_general.h).  SAC_GENERAL=1 in the environment selects
-// the general step for every shape (cross-checks).
-int sac_trainer_create_mlp(sac_trainer_t **out, const sac_config_t *cfg, const int32_t *policy_hidden, int32_t n_policy_hidden,
-                           const int32_t *qf_hidden, int32_t n_qf_hidden) {
-    SAC_REQUIRE(out && cfg && policy_hidden && qf_hidden, "null argument to sac_trainer_create_mlp");
+// the general step for every shape (cross-checks).  Both _mlp entries: td3 null for SAC; cfg: the SAC configuration the
+// trainer is built from.
+static int trainer_create_mlp(sac_trainer_t **out, const sac_config_t *cfg, const td3_config_t *td3, const int32_t *policy_hidden,
+                              int32_t n_policy_hidden, const int32_t *qf_hidden, int32_t n_qf_hidden) {
     *out = nullptr;
     SAC_REQUIRE(n_policy_hidden >= 1 && n_policy_hidden < gen::GMAXL && n_qf_hidden >= 1 && n_qf_hidden < gen::GMAXL,
                 "%d / %d hidden layers unsupported: 1..%d per network", n_policy_hidden, n_qf_hidden, gen::GMAXL - 1);
-    bool fits = n_policy_hidden == 2 && n_qf_hidden == 2;
-    for (int i = 0; i < n_policy_hidden; ++i) {
-        SAC_REQUIRE(policy_hidden[i] >= 1 && policy_hidden[i] <= 4096, "policy hidden size %d unsupported (1..4096)", policy_hidden[i]);
-        fits = fits && policy_hidden[i] <= H;
-    }
-    for (int i = 0; i < n_qf_hidden; ++i) {
-        SAC_REQUIRE(qf_hidden[i] >= 1 && qf_hidden[i] <= 4096, "qf hidden size %d unsupported (1..4096)", qf_hidden[i]);
-        fits = fits && qf_hidden[i] <= H;
-    }
+    bool fits = n_policy_hidden == 2 && n_qf_hidden == 2;      // ... the fused kernels: two layers of at most 256 units
+    int hp[gen::GMAXL], hq[gen::GMAXL];
+    auto sizes = [&fits](const char *net, const int32_t *h, int n, int *to) {
+        for (int i = 0; i < n; ++i) {
+            SAC_REQUIRE(h[i] >= 1 && h[i] <= 4096, "%s hidden size %d unsupported (1..4096)", net, h[i]);
+            fits = fits && h[i] <= H;
+            to[i] = h[i];
+        }
+        return 0;
+    };
+    if (int rc = sizes("policy", policy_hidden, n_policy_hidden, hp)) return rc;
+    if (int rc = sizes("qf", qf_hidden, n_qf_hidden, hq)) return rc;
     const char *force = getenv("SAC_GENERAL");
     if (fits && !(force && atoi(force) == 1)) {
         sac_config_t c = *cfg;
-        for (int i = 0; i < 2; ++i) { c.policy_hidden[i] = policy_hidden[i]; c.qf_hidden[i] = qf_hidden[i]; }
-        return sac_trainer_create(out, &c);
+        for (int i = 0; i < 2; ++i) { c.policy_hidden[i] = hp[i]; c.qf_hidden[i] = hq[i]; }
+        if (td3) { if (int rc = admit_td3(td3)) return rc; }
+        return trainer_create(out, &c, td3);
     }
-    SAC_REQUIRE(sac_device_count() > 0, "no HIP device visible: libsac_hip has no CPU fallback");
-    SAC_REQUIRE(cfg->obs_dim > 0 && cfg->act_dim > 0 && cfg->act_dim <= 16,
-                "unsupported dims obs=%d act=%d (act_dim must be in 1..16)", cfg->obs_dim, cfg->act_dim);
-    SAC_REQUIRE(cfg->obs_dim <= 496, "obs_dim %d unsupported (the minibatch slots hold cat(obs, act) rows of at most 512 columns)",
-                cfg->obs_dim);
-    SAC_REQUIRE(cfg->batch > 0, "batch size %d must be positive", cfg->batch);
-    SAC_REQUIRE(cfg->target_update_period > 0, "target_update_period must be positive");
+    if (int rc = admit_trainer(cfg, td3, true)) return rc;
     SAC_HIP(hipSetDevice(cfg->device));
     sac_trainer *t = new sac_trainer();
-    int hp[gen::GMAXL], hq[gen::GMAXL];
-    for (int i = 0; i < n_policy_hidden; ++i) hp[i] = policy_hidden[i];
-    for (int i = 0; i < n_qf_hidden; ++i) hq[i] = qf_hidden[i];
-    if (trainer_common_init(t, cfg) || gen_build(t, hp, n_policy_hidden, hq, n_qf_hidden) || trainer_prime_events(t)) {
+    if (td3) { t->algo = 1; t->td3_period = td3->policy_and_target_update_period; }
+    if (trainer_common_init(t, cfg) ||
+        (td3 ? gen_build_td3(t, td3, hp, n_policy_hidden, hq, n_qf_hidden) : gen_build(t, hp, n_policy_hidden, hq, n_qf_hidden)) ||
+        trainer_prime_events(t)) {
         sac_trainer_destroy(t);
         return -1;
     }
@@ -2717,67 +2696,26 @@ int sac_trainer_create_mlp(sac_trainer_t **out, const sac_config_t *cfg, const i
     return 0;
 }
 
-// TD3 with hidden_sizes of any depth (sac_hip.h): the fused kernels' shapes through td3_trainer_create, everything else on
-// the general step (gen_build_td3)
+int sac_trainer_create_mlp(sac_trainer_t **out, const sac_config_t *cfg, const int32_t *policy_hidden, int32_t n_policy_hidden,
+                           const int32_t *qf_hidden, int32_t n_qf_hidden) {
+    SAC_REQUIRE(out && cfg && policy_hidden && qf_hidden, "null argument to sac_trainer_create_mlp");
+    return trainer_create_mlp(out, cfg, nullptr, policy_hidden, n_policy_hidden, qf_hidden, n_qf_hidden);
+}
+
+// TD3 with hidden_sizes of any depth (sac_hip.h): the fused kernels' shapes as td3_trainer_create builds them, everything
+// else on the general step (gen_build_td3)
 int td3_trainer_create_mlp(sac_trainer_t **out, const td3_config_t *c, const int32_t *policy_hidden, int32_t n_policy_hidden,
                            const int32_t *qf_hidden, int32_t n_qf_hidden) {
     SAC_REQUIRE(out && c && policy_hidden && qf_hidden, "null argument to td3_trainer_create_mlp");
-    *out = nullptr;
-    SAC_REQUIRE(n_policy_hidden >= 1 && n_policy_hidden < gen::GMAXL && n_qf_hidden >= 1 && n_qf_hidden < gen::GMAXL,
-                "%d / %d hidden layers unsupported: 1..%d per network", n_policy_hidden, n_qf_hidden, gen::GMAXL - 1);
-    bool fits = n_policy_hidden == 2 && n_qf_hidden == 2;
-    for (int i = 0; i < n_policy_hidden; ++i) {
-        SAC_REQUIRE(policy_hidden[i] >= 1 && policy_hidden[i] <= 4096, "policy hidden size %d unsupported (1..4096)", policy_hidden[i]);
-        fits = fits && policy_hidden[i] <= H;
-    }
-    for (int i = 0; i < n_qf_hidden; ++i) {
-        SAC_REQUIRE(qf_hidden[i] >= 1 && qf_hidden[i] <= 4096, "qf hidden size %d unsupported (1..4096)", qf_hidden[i]);
-        fits = fits && qf_hidden[i] <= H;
-    }
-    const char *force = getenv("SAC_GENERAL");
-    if (fits && !(force && atoi(force) == 1)) {
-        td3_config_t cc = *c;
-        for (int i = 0; i < 2; ++i) { cc.policy_hidden[i] = policy_hidden[i]; cc.qf_hidden[i] = qf_hidden[i]; }
-        return td3_trainer_create(out, &cc);
-    }
-    SAC_REQUIRE(sac_device_count() > 0, "no HIP device visible: libsac_hip has no CPU fallback");
-    SAC_REQUIRE(c->policy_and_target_update_period > 0, "policy_and_target_update_period must be positive");
-    SAC_REQUIRE(c->target_policy_noise >= 0.f && c->target_policy_noise_clip >= 0.f, "negative target policy noise");
-    SAC_REQUIRE(c->obs_dim > 0 && c->act_dim > 0 && c->act_dim <= 16, "unsupported dims obs=%d act=%d (act_dim must be in 1..16)",
-                c->obs_dim, c->act_dim);
-    SAC_REQUIRE(c->obs_dim <= 496, "obs_dim %d unsupported (the minibatch slots hold cat(obs, act) rows of at most 512 columns)", c->obs_dim);
-    SAC_REQUIRE(c->batch > 0, "batch size %d must be positive", c->batch);
-    SAC_HIP(hipSetDevice(c->device));
-    sac_config_t s{};
-    s.obs_dim = c->obs_dim; s.act_dim = c->act_dim; s.hidden = c->hidden; s.batch = c->batch;
-    s.discount = c->discount; s.reward_scale = c->reward_scale;
-    s.policy_lr = c->policy_learning_rate; s.qf_lr = c->qf_learning_rate;
-    s.soft_target_tau = c->tau; s.target_update_period = 1; s.use_automatic_entropy_tuning = 0;
-    s.target_entropy = 0.f; s.noise_seed = c->noise_seed; s.device = c->device;
-    sac_trainer *t = new sac_trainer();
-    t->algo = 1;
-    t->td3_period = c->policy_and_target_update_period;
-    int hp[gen::GMAXL], hq[gen::GMAXL];
-    for (int i = 0; i < n_policy_hidden; ++i) hp[i] = policy_hidden[i];
-    for (int i = 0; i < n_qf_hidden; ++i) hq[i] = qf_hidden[i];
-    if (trainer_common_init(t, &s) || gen_build_td3(t, c, hp, n_policy_hidden, hq, n_qf_hidden) || trainer_prime_events(t)) {
-        sac_trainer_destroy(t);
-        return -1;
-    }
-    *out = t;
-    return 0;
+    const sac_config_t s = td3_as_sac_config(c);
+    return trainer_create_mlp(out, &s, c, policy_hidden, n_policy_hidden, qf_hidden, n_qf_hidden);
 }
 
 int sac_trainer_destroy(sac_trainer_t *t) {
     if (!t) return 0;
     (void)hipSetDevice(t->device);
     if (t->stream) (void)hipStreamSynchronize(t->stream);
-    if (t->fused) {
-        FusedGate &G = g_gate[t->device & 63];
-        std::lock_guard<std::mutex> lk(G.mu);
-        if (!t->gate_exempt) G.live -= 1;
-        if (G.last == t->stream) G.last = nullptr;
-    }
+    if (t->fused) gate_leave(t->device, !t->gate_exempt, t->stream);
     (void)hipFree(t->arena);
     gen_destroy(t->gen);
     if (t->h_stage) (void)hipHostFree(t->h_stage);
@@ -3354,23 +3292,16 @@ int sac_trainer_set_xcd_mask(sac_trainer_t *t, unsigned xcd_mask) {
     sac::stream_register(ns);
     t->pend_n = 0;
     t->xcd_mask = xcd_mask & 0xffu;
-    int cus = 0;
-    SAC_HIP(hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, t->device));
-    const int mine = (cus / 8) * __builtin_popcount(xcd_mask & 0xffu);
+    const int mine = (t->cus / 8) * __builtin_popcount(xcd_mask & 0xffu);
     if (t->fused) {
-        FusedGate &G = g_gate[t->device & 63];
-        std::lock_guard<std::mutex> lk(G.mu);
-        if (!t->gate_exempt) G.live -= 1;
-        if (t->abc_grid <= mine && (xcd_mask & 0xffu) != 0xffu) {
+        const bool whole = (xcd_mask & 0xffu) == 0xffu;
+        if (!whole && t->plan.fused_launch.grid <= mine) {       // fused on CUs of its own: out of the gate
+            if (!t->gate_exempt) gate_leave(t->device);
             t->gate_exempt = true;
-        } else if ((xcd_mask & 0xffu) == 0xffu) {
+        } else if (whole) {                                       // back on the whole chip: a tenant again
+            if (t->gate_exempt && gate_join(t->device)) return -1;
             t->gate_exempt = false;
-            G.live += 1;
-        } else {
-            t->gate_exempt = false;
-            t->fused = false;
-            set_abort_ptrs(t, nullptr);
-        }
+        } else trainer_drop_fused(t);                             // its CUs cannot hold the fused launch
     }
     return 0;
 }
@@ -3381,7 +3312,7 @@ int sac_trainer_set_xcd(sac_trainer_t *t, int xcd) {
 
 // 1 while this trainer runs the fused two-launch step (k_abc + k_dw_adam), 0 for the four-launch step
 int sac_trainer_is_fused(const sac_trainer_t *t) { return (t && t->fused) ? 1 : 0; }
-int sac_trainer_step_kind(const sac_trainer_t *t) { return !t ? -1 : (t->gen ? 3 : (t->fused ? (t->chain_bwd ? 4 : 1) : (t->chain ? 2 : 0))); }
+int sac_trainer_step_kind(const sac_trainer_t *t) { return !t ? -1 : (t->gen ? 3 : (t->fused ? (t->plan.chain_bwd ? 4 : 1) : (t->plan.chain ? 2 : 0))); }
 
 int sac_last_loop_ms(sac_trainer_t *t, float *total_ms, float *sample_ms, float *gather_ms, float *steps_ms) {
     SAC_REQUIRE(t, "null trainer");
