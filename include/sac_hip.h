@@ -413,7 +413,8 @@ int sac_q_values_general_many(sac_trainer_t *const *trainers, int n_trainers, co
  * bit the one-row call.  The call drains the trainer as sac_sync does, reads the nets where the step keeps them and
  * writes nothing the step reads: parameters, optimizer state, scalars, the step's noise counter and the buffer
  * generator stay untouched.  n is 1..1024.  SAC trainers with the fused kernels' shapes; general-step trainers are
- * refused (sac_get_params and a forward on the host is their path) and so are TD3 trainers (this is the SAC objective). */
+ * refused (sac_get_params and a forward on the host is their path, or sac_evaluate_general below) and so are TD3
+ * trainers (this is the SAC objective). */
 enum { SAC_EVAL_Q1, SAC_EVAL_Q2, SAC_EVAL_Q1_NEW, SAC_EVAL_Q2_NEW, SAC_EVAL_TQ1, SAC_EVAL_TQ2,
        SAC_EVAL_LOG_PI, SAC_EVAL_LOG_PI_NEXT, SAC_EVAL_Y, SAC_EVAL_ROWS_N };
 typedef struct {
@@ -430,6 +431,22 @@ int sac_evaluate(sac_trainer_t *t, int64_t n, sac_eval_io_t *io);               
  * different devices, TD3 trainers, general-step trainers, members confined by sac_trainer_set_xcd[_mask], n_rows outside
  * 0..1024 or all zero, and for a member with rows a null input array or null rows. */
 int sac_evaluate_many(sac_trainer_t *const *trainers, int n_trainers, const int32_t *n_rows, sac_eval_io_t *io);
+/* The same two entries for GENERAL-STEP SAC trainers (a policy or critics beyond two hidden layers of at most 256 units:
+ * depth 1..7, widths 1..4096): k_eval_layer (csrc/sac_eval_general.h), one launch per layer depth on the live weights of
+ * the general step -- the policy's layers on s and s', then the critics' layers on [s | a], [s | a_new] and
+ * [s' | a_next], then y -- on the first trainer's stream with one wait at the end; no mirror, no repacking, no parameter
+ * copy.  The contract is that of sac_evaluate / sac_evaluate_many: the same sac_eval_io_t, the same nine rows, the same
+ * optional arrays, io->alpha read the same way, n 1..1024 for the solo call, 1..16 trainers of one device with dims,
+ * depths, widths and row counts mixed, n_rows[i] == 0 = sits out (at least one with rows), every member with rows
+ * drained as by sac_sync first.  The six Q columns are bit for bit sac_q_values_general's on the same rows, a_new / a_next
+ * bit for bit sac_policy_act_general's, y its float32 restatement; each member's columns are bit for bit its own
+ * sac_evaluate_general's and row r of any call bit for bit the one-row call.  The kernels write the trainers' own
+ * activation scratch (shared with sac_policy_act_general and sac_q_values_general: the calls never overlap) and the
+ * outputs, nothing the step reads.  Refused (<0, sac_last_error, nothing changed, no output written): what
+ * sac_evaluate_many refuses (general-step trainers apart), and trainers with the fused kernels' shapes (sac_evaluate is their entry).  sac_evaluate /
+ * sac_evaluate_many keep refusing general-step trainers. */
+int sac_evaluate_general(sac_trainer_t *t, int64_t n, sac_eval_io_t *io);         /* n in 1..1024 */
+int sac_evaluate_general_many(sac_trainer_t *const *trainers, int n_trainers, const int32_t *n_rows, sac_eval_io_t *io);
 
 /* ------------------------------------------------------------------------------------------
  * Trainer groups: several runs of one configuration (the reference's seed sweeps, /root/reference/launch_jobs.sh)

@@ -150,6 +150,8 @@ SYMBOLS = {
     "sac_q_values_general_many": (C.c_int, [_P, C.c_int, _P, _P, _P, _P, _P]),
     "sac_evaluate": (C.c_int, [_P, C.c_int64, _P]),
     "sac_evaluate_many": (C.c_int, [_P, C.c_int, _P, _P]),
+    "sac_evaluate_general": (C.c_int, [_P, C.c_int64, _P]),
+    "sac_evaluate_general_many": (C.c_int, [_P, C.c_int, _P, _P]),
     "sac_group_create": (C.c_int, [C.POINTER(_P), _P, C.c_int]),
     "td3_group_create": (C.c_int, [C.POINTER(_P), _P, C.c_int]),
     "sac_group_create_mixed": (C.c_int, [C.POINTER(_P), _P, C.c_int]),

@@ -34,8 +34,8 @@
 // staging (act_stage_reserve, sac_act.h) and nothing else: nothing the step kernels read, no noise counter, no
 // parameter.
 //
-// General-step trainers are refused (SACTrainer.evaluate's host path serves them), TD3 trainers too: this is the SAC
-// objective.
+// General-step trainers are refused (SACTrainer.evaluate's host path serves them, or sac_evaluate_general:
+// sac_eval_general.h), TD3 trainers too: this is the SAC objective.
 #pragma once
 
 namespace sac {
@@ -162,24 +162,9 @@ size_t eval_lds_bytes(int KQ) {
 
 std::atomic<bool> g_eval_lds_raised[64];
 
-}  // namespace
-
-static_assert((int)EVAL_ROWS_N == (int)SAC_EVAL_ROWS_N && (int)EVAL_Y == (int)SAC_EVAL_Y, "k_eval's rows are sac_hip.h's");
-
-// (declared extern "C" in include/sac_hip.h)
-int sac_evaluate_many(sac_trainer_t *const *trainers, int n_trainers, const int32_t *n_rows, sac_eval_io_t *io) {
-    SAC_REQUIRE(trainers && n_rows && io, "bad arguments to sac_evaluate_many");
-    const InferEntry IE = {"sac_evaluate_many", false, true, "device evaluation",
-                           "sac_get_params and a forward on the host is the path", "evaluate"};
-    if (int rc = infer_admit(IE, trainers, n_trainers, n_rows, [&](int i) {
-            const sac_eval_io_t &E = io[i];
-            SAC_REQUIRE(E.obs && E.act && E.rew && E.term && E.next_obs && E.eps && E.eps_next && E.rows,
-                        "trainer %d: a null input array or null rows", i);
-            return 0;
-        })) return rc;
-    sac_trainer *t0 = trainers[0];
-    // the entropy coefficient of this moment (sac_get_scalars' scalars[5]; 1 with automatic tuning off)
-    float alpha[SAC_GROUP_MAX];
+// the entropy coefficient of this moment for every member with rows (sac_get_scalars' scalars[5]; 1 with automatic
+// tuning off), behind the drain: what sac_evaluate_many and sac_evaluate_general_many both evaluate y with
+int eval_read_alpha(sac_trainer_t *const *trainers, int n_trainers, const int32_t *n_rows, float *alpha) {
     for (int i = 0; i < n_trainers; ++i) {
         sac_trainer *t = trainers[i];
         if (n_rows[i] == 0) continue;
@@ -192,6 +177,29 @@ int sac_evaluate_many(sac_trainer_t *const *trainers, int n_trainers, const int3
             alpha[i] = c.alpha > 0.f ? c.alpha : expf(c.log_alpha);
         }
     }
+    return 0;
+}
+
+// an entry's own refusal for a member with rows: every input array and `rows` are there
+int eval_admit_io(const sac_eval_io_t &E, int i) {
+    SAC_REQUIRE(E.obs && E.act && E.rew && E.term && E.next_obs && E.eps && E.eps_next && E.rows,
+                "trainer %d: a null input array or null rows", i);
+    return 0;
+}
+
+}  // namespace
+
+static_assert((int)EVAL_ROWS_N == (int)SAC_EVAL_ROWS_N && (int)EVAL_Y == (int)SAC_EVAL_Y, "k_eval's rows are sac_hip.h's");
+
+// (declared extern "C" in include/sac_hip.h)
+int sac_evaluate_many(sac_trainer_t *const *trainers, int n_trainers, const int32_t *n_rows, sac_eval_io_t *io) {
+    SAC_REQUIRE(trainers && n_rows && io, "bad arguments to sac_evaluate_many");
+    const InferEntry IE = {"sac_evaluate_many", false, true, "device evaluation",
+                           "sac_get_params and a forward on the host is the path", "evaluate"};
+    if (int rc = infer_admit(IE, trainers, n_trainers, n_rows, [&](int i) { return eval_admit_io(io[i], i); })) return rc;
+    sac_trainer *t0 = trainers[0];
+    float alpha[SAC_GROUP_MAX];
+    if (eval_read_alpha(trainers, n_trainers, n_rows, alpha)) return -1;
 
     // per member: obs act rew term nobs eps eps_next | rows mu log_std a_new a_next
     enum { NPART = 12 };

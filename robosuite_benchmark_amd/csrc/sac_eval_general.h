@@ -1,0 +1,244 @@
+// Evaluating the SAC objectives on the device for general-step trainers: nets of any depth and width (included by
+// sac_trainer.hip behind sac_eval.h, sac_act_general.h and sac_qval_general.h).
+//
+// What k_eval (sac_eval.h) computes in one launch for the fused kernels' shapes -- the thirteen arrays of sac_eval_io_t
+// for 1..1024 transitions (s, a, r, d, s') with their draws eps / eps_next, of each of 1..SAC_GROUP_MAX SAC trainers, from
+// the live weights -- is computed here layer by layer: k_act_layer's and k_qval_layer's scheme, one table-driven launch
+// per layer depth on the first member's stream and ONE wait at the end.  The nets are read where the general step keeps
+// them (sac_general::net[...].P: nn.Linear layout W [N][K] then b): nothing is repacked, mirrored or copied.
+//
+//   schedule  with LP = the deepest policy of the call (hidden layers + head) and LQ = the deepest critic:
+//               launches 0 .. LP-1        k_eval_layer<false>: policy layer l of every member that has one, TWO jobs per
+//                                         member -- the rows s with eps and the rows s' with eps_next (rows are
+//                                         independent: two jobs are the stacked 2n rows).  A member's head is its last
+//                                         layer, whatever the launch index.
+//               launches LP .. LP+LQ-1    k_eval_layer<true>: critic layer l of every member that has one, SIX jobs per
+//                                         member -- [s | a] and [s | a_new] through qf1 and qf2, [s' | a_next] through
+//                                         target_qf1 and target_qf2.  Chain Q needs no policy, but it waits for the
+//                                         critic phase: one rule for all six jobs, and no launch more.
+//               launch LP+LQ              k_eval_y: y, elementwise, from the columns the launches in front of it wrote
+//   table     a launch carries up to EG_JOBS = 6 SAC_GROUP_MAX jobs (EvalLayerJob, device-visible memory, read with scalar
+//             loads).  A workgroup finds its job by a bisection over wg0 (ascending), as in k_qval_layer.
+//   grid      one workgroup (4 waves) per 16-row x 64-column output tile of one job
+//   policy    infer_layer_tile<float, false> and infer_layer_store (sac_infer.h): k_act_layer's hidden layers
+//   head      N = 2A <= 32, one column tile, through HL: infer_layer_head_eval (sac_infer.h) -- the action is
+//             infer_action's with the draws (k_act_layer's stochastic action, bit for bit), log_pi is k_eval's expression
+//             summed by group16_sum, and for the rows s the mean and the clamped log_std (a NaN stays a NaN).  a_new and
+//             a_next ALWAYS go to the staging, where the critic launches read them, whether or not the caller asked for
+//             them.
+//   critics   infer_layer_tile<float, true> and infer_layer_store: k_qval_layer's layers.  The first layer reads its two
+//             blocks through the split point K1 = O; the output unit (N = 1) is summed like any other column and lands in
+//             its row of `rows`: the six Q columns are bit for bit sac_q_values_general's on the same rows.
+//   y         eval_y (sac_eval.h) unchanged: every operation rounded to float32 on its own, none fused
+//
+// Workgroups never talk to each other: no hand-offs, no spinning, no atomics; the order between layers is the order of
+// the launches on one stream.  Row independence as in k_act_layer / k_qval_layer: an output element is one MFMA chain
+// over k in an order fixed by K alone, rows beyond a job's n repeat row n - 1 on the way in and are never written.
+//
+// The kernels write the caller's outputs in the staging (act_stage_reserve) and the members' activation scratch: nothing
+// the step reads.  The scratch is the trainer's act_gen pair (act_general_reserve), shared with sac_policy_act_general
+// and sac_q_values_general -- each of those calls, and this one, ends with a wait on the stream, so they never overlap.
+// Each buffer holds max(2 n x the widest policy layer, 6 n x the widest critic layer) floats; the worst case is
+// 6 jobs x 1024 rows x 4096 units x 4 bytes x 2 buffers = 192 MB per trainer.  Vector stores only.
+#pragma once
+
+namespace sac {
+
+constexpr int EG_JOBS = 6 * SAC_GROUP_MAX;      // jobs of one launch
+constexpr int EG_LAUNCHES = 2 * gen::GMAXL;     // layer launches of one call, at most
+constexpr int EG_YROWS = 256;                   // rows of one k_eval_y workgroup
+enum { EG_STORE = 0, EG_HEAD = 1 };
+
+struct EvalLayerJob {
+    const float *W, *b;            // [N][K], [N]
+    const float *X, *X2;           // input rows: columns 0 .. K1-1 from X [n][K1], columns K1 .. K-1 from X2 [n][K - K1]
+    float *Y;                      // hidden layer: [n][N]; critic output (N == 1): its row of `rows`; head: the actions [n][A]
+    const float *eps;              // head: the N(0,1) draws [n][A]
+    float *lp, *mu, *ls;           // head: log_pi [n]; mean and clamped log_std [n][A], or null
+    int N, K, K1, n;
+    int wg0, tiles_n, relu, vec;   // wg0: first workgroup of this job in the launch; vec: 16-byte pieces of W's rows
+    int kind, A, pad[2];
+};
+
+struct EvalYMember {
+    const float *rew, *term;       // [n]
+    float *rows;                   // (SAC_EVAL_ROWS_N, n)
+    int n, wg0;
+    float alpha, rs, discount;
+    int pad;
+};
+
+// SPLIT false: a policy launch (hidden layers and heads); true: a critic launch
+template <bool SPLIT>
+__global__ __launch_bounds__(256) void k_eval_layer(const EvalLayerJob *__restrict__ tab, int n_jobs) {
+    __shared__ __attribute__((aligned(16))) float Xs[RB * AG_LD];
+    // this workgroup's job: the last one whose first workgroup is not behind this one (wave-uniform, scalar loads)
+    int lo = 0, hi = n_jobs;
+    while (hi - lo > 1) {
+        const int mid = (lo + hi) >> 1;
+        if ((int)blockIdx.x >= sload(&tab[mid].wg0)) lo = mid; else hi = mid;
+    }
+    const EvalLayerJob *J = tab + lo;
+    const float *W = sload(&J->W), *X = sload(&J->X), *bp = sload(&J->b);
+    const int N = sload(&J->N), K = sload(&J->K), n = sload(&J->n);
+    const int tiles_n = sload(&J->tiles_n);
+    const bool vec = sload(&J->vec) != 0;
+    const int tile = (int)blockIdx.x - sload(&J->wg0);
+    const int row0 = RB * (tile / tiles_n), n0 = AG_CT * (tile % tiles_n);
+    const int ncol = n0 + 16 * (threadIdx.x >> 6) + (threadIdx.x & 15);
+    if constexpr (SPLIT) {
+        const LayerTile t = infer_layer_tile<float, true>(Xs, W, bp, X, sload(&J->X2), N, K, sload(&J->K1), n, vec, row0, ncol);
+        // hidden layer: ReLU; output layer (N == 1, relu == 0): column 0 alone passes ncol < N and lands in its row of `rows`
+        infer_layer_store(t, sload(&J->Y), N, n, row0, ncol, sload(&J->relu) != 0);
+    } else {
+        __shared__ float HL[RB * ACT_HEAD_LD];
+        const LayerTile t = infer_layer_tile<float, false>(Xs, W, bp, X, X, N, K, K, n, vec, row0, ncol);
+        if (sload(&J->kind) == EG_STORE) infer_layer_store(t, sload(&J->Y), N, n, row0, ncol, true);
+        else infer_layer_head_eval(t, HL, J, n, row0);
+    }
+}
+
+__global__ __launch_bounds__(EG_YROWS) void k_eval_y(const EvalYMember *__restrict__ tab, int n_members) {
+    typedef __attribute__((address_space(1))) float *gout;
+    const EvalYMember *M = tab + infer_member(tab, n_members, &EvalYMember::wg0);
+    const int n = sload(&M->n);
+    const int row = ((int)blockIdx.x - sload(&M->wg0)) * EG_YROWS + (int)threadIdx.x;
+    if (row >= n) return;
+    float *rows = sload(&M->rows);
+    const float tq1 = ld1g(rows + ((unsigned)EVAL_TQ1 * (unsigned)n + (unsigned)row));
+    const float tq2 = ld1g(rows + ((unsigned)EVAL_TQ2 * (unsigned)n + (unsigned)row));
+    const float lpn = ld1g(rows + ((unsigned)EVAL_LOG_PI_NEXT * (unsigned)n + (unsigned)row));
+    const float rew = ld1g(sload(&M->rew) + row), d = ld1g(sload(&M->term) + row);
+    *(gout)(uintptr_t)(rows + ((unsigned)EVAL_Y * (unsigned)n + (unsigned)row)) =
+        eval_y(sload(&M->rs), rew, d, sload(&M->discount), tq1, tq2, sload(&M->alpha), lpn);
+}
+
+}  // namespace sac
+
+// (declared extern "C" in include/sac_hip.h)
+int sac_evaluate_general_many(sac_trainer_t *const *trainers, int n_trainers, const int32_t *n_rows, sac_eval_io_t *io) {
+    SAC_REQUIRE(trainers && n_rows && io, "bad arguments to sac_evaluate_general_many");
+    const InferEntry IE = {"sac_evaluate_general_many", true, true, "device evaluation",
+                           "sac_evaluate is its device evaluation entry, sac_evaluate_general serves the general step", "evaluate"};
+    if (int rc = infer_admit(IE, trainers, n_trainers, n_rows, [&](int i) { return eval_admit_io(io[i], i); })) return rc;
+    sac_trainer *t0 = trainers[0];
+    float alpha[SAC_GROUP_MAX];
+    if (eval_read_alpha(trainers, n_trainers, n_rows, alpha)) return -1;
+
+    // the staging: the layer tables, k_eval_y's table, then per member
+    //   obs act rew term nobs eps eps_next | rows a_new a_next (always: the critic launches read them) mu log_std
+    enum { P_OBS, P_ACT, P_REW, P_TERM, P_NOBS, P_EPS, P_EPS_NEXT, P_ROWS, P_A_NEW, P_A_NEXT, P_MU, P_LOG_STD, NPART };
+    const size_t tab_bytes = infer_align(sizeof(EvalLayerJob) * EG_JOBS * EG_LAUNCHES);
+    size_t off[SAC_GROUP_MAX][NPART], bytes = tab_bytes + infer_align(sizeof(EvalYMember) * SAC_GROUP_MAX);
+    int LP = 0, LQ = 0;
+    size_t slice_p[SAC_GROUP_MAX] = {}, slice_q[SAC_GROUP_MAX] = {};
+    for (int i = 0; i < n_trainers; ++i) {
+        sac_trainer *t = trainers[i];
+        const size_t n = (size_t)n_rows[i], nO = n * t->O, nA = n * t->A;
+        const sac_eval_io_t &E = io[i];
+        const size_t part[NPART] = {nO, nA, n, n, nO, nA, nA, n * SAC_EVAL_ROWS_N, nA, nA,
+                                    n && E.mu ? nA : 0, n && E.log_std ? nA : 0};
+        infer_carve(bytes, off[i], part, NPART);
+        if (n == 0) continue;
+        const GenNet &P = t->gen->net[SAC_NET_POLICY], &Q = t->gen->net[SAC_NET_QF1];      // (the four Q nets share their layout)
+        slice_p[i] = n * infer_widest(P); slice_q[i] = n * infer_widest(Q);
+        if (act_general_reserve(t, std::max(2 * slice_p[i], 6 * slice_q[i]))) return -1;
+        LP = std::max(LP, P.nl); LQ = std::max(LQ, Q.nl);
+    }
+    if (act_stage_reserve(t0, bytes)) return -1;
+    const sac_trainer::ActStage &S = t0->act_stage;
+    EvalLayerJob *tab = reinterpret_cast<EvalLayerJob *>(S.h);
+    EvalYMember *ytab = reinterpret_cast<EvalYMember *>(S.h + tab_bytes);
+    int njobs[EG_LAUNCHES] = {}, blocks[EG_LAUNCHES] = {}, yblocks = 0, m = 0;
+    for (int i = 0; i < n_trainers; ++i) {
+        const sac_trainer *t = trainers[i];
+        if (n_rows[i] == 0) continue;
+        const sac_eval_io_t &E = io[i];
+        const int n = n_rows[i], rbs = (n + RB - 1) / RB;
+        const size_t nO = (size_t)n * t->O, nA = (size_t)n * t->A;
+        auto dev = [&](int k) { return reinterpret_cast<float *>(S.d + off[i][k]); };
+        auto in = [&](int k, const float *src, size_t count) { memcpy(S.h + off[i][k], src, sizeof(float) * count); };
+        in(P_OBS, E.obs, nO); in(P_ACT, E.act, nA); in(P_REW, E.rew, n); in(P_TERM, E.term, n);
+        in(P_NOBS, E.next_obs, nO); in(P_EPS, E.eps, nA); in(P_EPS_NEXT, E.eps_next, nA);
+        float *rows = dev(P_ROWS);
+        auto job = [&](int launch, const GenNet &N, const GenLayer &L) -> EvalLayerJob & {
+            EvalLayerJob &J = tab[(size_t)launch * EG_JOBS + njobs[launch]++];
+            J = EvalLayerJob{};
+            infer_layer_job(J, N, L);
+            J.K1 = L.K; J.n = n; J.A = t->A; J.relu = 1; J.kind = EG_STORE;
+            J.wg0 = blocks[launch];
+            blocks[launch] += rbs * J.tiles_n;
+            return J;
+        };
+        // the policy on s (with eps) and on s' (with eps_next)
+        const GenNet &P = t->gen->net[SAC_NET_POLICY];
+        for (int s = 0; s < 2; ++s) {
+            const float *x = dev(s ? P_NOBS : P_OBS);
+            for (int l = 0; l < P.nl; ++l) {
+                EvalLayerJob &J = job(l, P, P.L[l]);
+                J.X = J.X2 = x;
+                if (l + 1 < P.nl) {
+                    J.Y = t->act_gen[l & 1] + (size_t)s * slice_p[i];
+                } else {
+                    J.kind = EG_HEAD; J.relu = 0;
+                    J.Y = dev(s ? P_A_NEXT : P_A_NEW);
+                    J.eps = dev(s ? P_EPS_NEXT : P_EPS);
+                    J.lp = rows + (size_t)(s ? EVAL_LOG_PI_NEXT : EVAL_LOG_PI) * n;
+                    J.mu = !s && E.mu ? dev(P_MU) : nullptr;
+                    J.ls = !s && E.log_std ? dev(P_LOG_STD) : nullptr;
+                }
+                x = J.Y;
+            }
+        }
+        // the critics: job s writes row s of `rows` (EVAL_Q1 .. EVAL_TQ2)
+        const int net_of[6] = {SAC_NET_QF1, SAC_NET_QF2, SAC_NET_QF1, SAC_NET_QF2, SAC_NET_TARGET_QF1, SAC_NET_TARGET_QF2};
+        const int obs_of[6] = {P_OBS, P_OBS, P_OBS, P_OBS, P_NOBS, P_NOBS};
+        const int act_of[6] = {P_ACT, P_ACT, P_A_NEW, P_A_NEW, P_A_NEXT, P_A_NEXT};
+        for (int s = 0; s < 6; ++s) {
+            const GenNet &Q = t->gen->net[net_of[s]];
+            const float *x = dev(obs_of[s]), *x2 = dev(act_of[s]);
+            for (int l = 0; l < Q.nl; ++l) {
+                const bool last = l + 1 == Q.nl;
+                EvalLayerJob &J = job(LP + l, Q, Q.L[l]);
+                J.X = x; J.X2 = x2;
+                J.K1 = l == 0 ? t->O : Q.L[l].K;
+                J.Y = last ? rows + (size_t)s * n : t->act_gen[l & 1] + (size_t)s * slice_q[i];
+                J.relu = last ? 0 : 1;
+                x = x2 = J.Y;
+            }
+        }
+        EvalYMember &M = ytab[m++];
+        M.rew = dev(P_REW); M.term = dev(P_TERM); M.rows = rows;
+        M.n = n; M.wg0 = yblocks;
+        M.alpha = alpha[i]; M.rs = t->cfg.reward_scale; M.discount = t->cfg.discount; M.pad = 0;
+        yblocks += (n + EG_YROWS - 1) / EG_YROWS;
+    }
+    const EvalLayerJob *d_tab = reinterpret_cast<const EvalLayerJob *>(S.d);
+    for (int l = 0; l < LP + LQ; ++l) {
+        if (l < LP) hipLaunchKernelGGL(k_eval_layer<false>, dim3(blocks[l]), dim3(256), 0, t0->stream, d_tab + (size_t)l * EG_JOBS, njobs[l]);
+        else hipLaunchKernelGGL(k_eval_layer<true>, dim3(blocks[l]), dim3(256), 0, t0->stream, d_tab + (size_t)l * EG_JOBS, njobs[l]);
+        SAC_HIP(hipGetLastError());
+    }
+    hipLaunchKernelGGL(k_eval_y, dim3(yblocks), dim3(EG_YROWS), 0, t0->stream,
+                       reinterpret_cast<const EvalYMember *>(S.d + tab_bytes), m);
+    SAC_HIP(hipGetLastError());
+    if (wait_trainer_stream(t0)) return -1;
+    for (int i = 0; i < n_trainers; ++i) {
+        if (n_rows[i] == 0) continue;
+        sac_eval_io_t &E = io[i];
+        const size_t n = (size_t)n_rows[i], nA = n * trainers[i]->A;
+        memcpy(E.rows, S.h + off[i][P_ROWS], sizeof(float) * n * SAC_EVAL_ROWS_N);
+        float *const dst[4] = {E.a_new, E.a_next, E.mu, E.log_std};
+        for (int k = 0; k < 4; ++k)
+            if (dst[k]) memcpy(dst[k], S.h + off[i][P_A_NEW + k], sizeof(float) * nA);
+        E.alpha = alpha[i];
+    }
+    return 0;
+}
+
+int sac_evaluate_general(sac_trainer_t *t, int64_t n, sac_eval_io_t *io) {
+    SAC_REQUIRE(t && io, "bad arguments to sac_evaluate_general");
+    SAC_REQUIRE(n >= 1 && n <= ACT_MAX_ROWS, "sac_evaluate_general: %lld rows (1..%d per call)", (long long)n, ACT_MAX_ROWS);
+    const int32_t rows = (int32_t)n;
+    return sac_evaluate_general_many(&t, 1, &rows, io);
+}

@@ -1,15 +1,16 @@
 // The forward pass of the device inference kernels, once (included by sac_trainer.hip in front of sac_act.h).
 //
-// Seven kernels run a network forward on live weights without training: k_act, k_act_session, k_qval, k_eval (the fused
+// Eight kernels run a network forward on live weights without training: k_act, k_act_session, k_qval, k_eval (the fused
 // kernels' shapes: one workgroup carries a 16-row block through a whole net in LDS) and k_act_layer,
-// k_act_layer_session<F64>, k_qval_layer (general shapes: one launch per layer, one workgroup per 16 x 64 output tile).
+// k_act_layer_session<F64>, k_qval_layer, k_eval_layer<SPLIT> (general shapes: one launch per layer, one workgroup per
+// 16 x 64 output tile).
 // Each of them is a prologue that finds its member or job, calls into the pieces below, and an epilogue of its own.
 // Every bit-for-bit promise between them -- a session's actions are the device call's, k_eval's Q values are k_qval's
 // and its actions k_act's -- holds because they run THESE functions, not copies of them.  A new inference kernel
 // composes the same pieces; it does not paste a body.
 //
 //   fused shapes     infer_member, infer_fill, infer_hidden, infer_head, infer_q_out, infer_action
-//   general shapes   infer_layer_tile, infer_layer_store, infer_layer_head (infer_action again)
+//   general shapes   infer_layer_tile, infer_layer_store, infer_layer_head / infer_layer_head_eval (infer_action again)
 //   host             infer_admit / infer_admit_session (the refusals), infer_carve / infer_slab (staging and slab layout),
 //                    infer_raise_lds, infer_widest / infer_layer_job (per-layer job tables)
 #pragma once
@@ -297,15 +298,21 @@ __device__ __forceinline__ void infer_layer_store(const LayerTile &t, float *Y, 
 
 // the policy head of job J (one column tile, kind is uniform over the workgroup): pre-activations through HL, then one
 // thread per action; J->A, J->eps and J->Y are read with scalar loads where they are needed
-template <class Job>
-__device__ __forceinline__ void infer_layer_head(const LayerTile &t, float *HL, const Job *J, int kind, int n, int row0) {
-    typedef __attribute__((address_space(1))) float *gout;
+// the head tile's pre-activations (bias added) into HL [16][ACT_HEAD_LD].  Ends behind a barrier.
+__device__ __forceinline__ void infer_layer_head_lds(const LayerTile &t, float *HL) {
     const int tid = threadIdx.x, wave = tid >> 6, lane = tid & 63, c = lane & 15, g = lane >> 4;
     if (16 * wave < ACT_HEAD_LD) {
 #pragma unroll
         for (int i = 0; i < 4; ++i) HL[(4 * g + i) * ACT_HEAD_LD + 16 * wave + c] = t.acc[i] + t.bias;
     }
     __syncthreads();
+}
+
+template <class Job>
+__device__ __forceinline__ void infer_layer_head(const LayerTile &t, float *HL, const Job *J, int kind, int n, int row0) {
+    typedef __attribute__((address_space(1))) float *gout;
+    infer_layer_head_lds(t, HL);
+    const int tid = threadIdx.x;
     const int A = sload(&J->A);
     const int r = tid >> 4, a = tid & 15;
     if (a < A && row0 + r < n) {
@@ -313,6 +320,41 @@ __device__ __forceinline__ void infer_layer_head(const LayerTile &t, float *HL, 
         *(gout)(uintptr_t)(sload(&J->Y) + o) =
             infer_action(HL, r, a, A, kind == AG_SAC_SAMPLE, [&] { return ld1g(sload(&J->eps) + o); });
     }
+}
+
+// infer_layer_head's sibling for loss evaluation: the stochastic SAC head of job J with everything the objectives need
+// from it.  The action is infer_action's (bit for bit k_act_layer's AG_SAC_SAMPLE action) and goes to J->Y always; log_pi is
+// k_eval's expression on the same head values -- Normal.log_prob of the value under the tanh, minus
+// log(1 - a^2 + TANH_EPS), summed over the actions by group16_sum -- and goes to J->lp [n]; J->mu / J->ls [n][A], where
+// not null, get the mean and the clamped log_std (a NaN stays a NaN: fmaxf would drop it).
+template <class Job>
+__device__ __forceinline__ void infer_layer_head_eval(const LayerTile &t, float *HL, const Job *J, int n, int row0) {
+    typedef __attribute__((address_space(1))) float *gout;
+    infer_layer_head_lds(t, HL);
+    const int tid = threadIdx.x;
+    const int A = sload(&J->A);
+    const int r = tid >> 4, a = tid & 15;
+    const bool live = row0 + r < n;
+    float lp = 0.f;
+    if (a < A) {
+        const unsigned o = (unsigned)(row0 + r) * (unsigned)A + (unsigned)a;
+        const float mean = HL[r * ACT_HEAD_LD + a], raw = HL[r * ACT_HEAD_LD + A + a], ls = infer_log_std(raw);
+        float v;
+        const float actv = infer_action(HL, r, a, A, true, [&] { return live ? ld1g(sload(&J->eps) + o) : 0.f; }, &v);
+        const float stdv = expf(ls);
+        const float dd = __fsub_rn(v, mean);                             // Normal.log_prob(z)
+        const float var = __fmul_rn(stdv, stdv);
+        const float nlp = -(dd * dd) / (2.0f * var) - logf(stdv) - 0.91893853320467274178f;
+        lp = nlp - logf(1.0f - actv * actv + TANH_EPS);
+        if (live) {
+            *(gout)(uintptr_t)(sload(&J->Y) + o) = actv;
+            float *pm = sload(&J->mu), *pl = sload(&J->ls);
+            if (pm) *(gout)(uintptr_t)(pm + o) = mean;
+            if (pl) *(gout)(uintptr_t)(pl + o) = raw != raw ? raw : ls;
+        }
+    }
+    const float lsum = group16_sum(lp);
+    if (a == 0 && live) *(gout)(uintptr_t)(sload(&J->lp) + (unsigned)(row0 + r)) = lsum;
 }
 
 }  // namespace sac

@@ -157,13 +157,17 @@ def q_values_many(trainers, obs_list, act_list, nets_list, general="host"):
     return out
 
 
-def evaluate_many(trainers, batches, eps=None, rngs=None, rows=False):
+def evaluate_many(trainers, batches, eps=None, rngs=None, rows=False, general="host"):
     """SACTrainer.evaluate for many runs at once: result[i] = trainers[i].evaluate(batches[i], eps[i], rngs[i]) (eps / rngs:
     one entry per trainer or None; batches[i] None or without rows: the member sits out and gets None).  The SAC members
     with the fused kernels' shapes are served by ONE launch per 16 of them and 1024 rows (sac_evaluate_many: dims, hidden
     sizes and row counts mixed); the others -- the general step, trainers without a handle -- go through their own
     evaluate inside the same call (a TD3 member raises there).  A member's columns never depend on its neighbours: they
-    are bit for bit those of its own evaluate.  Results come back in member order; rows=True as for evaluate."""
+    are bit for bit those of its own evaluate.  Results come back in member order; rows=True as for evaluate.
+    general="device": the SAC members of the general step are evaluated on the device as well, by ONE
+    sac_evaluate_general_many call per 16 of them and 1024 rows; their results are bit for bit those of their own
+    evaluate(general="device")."""
+    _check_general(general)
     trainers = list(trainers)
     R = len(trainers)
     eps = [None] * R if eps is None else list(eps)
@@ -172,32 +176,34 @@ def evaluate_many(trainers, batches, eps=None, rngs=None, rows=False):
         raise RuntimeError("evaluate_many takes one batch (and eps pair, and rng) per trainer")
     if len({id(t) for t in trainers}) != R:
         raise RuntimeError("a trainer appears twice in evaluate_many")
-    out, arrs, chunks, alphas, dev = [None] * R, [None] * R, [None] * R, [1.0] * R, []
+    out, arrs, chunks, alphas, dev, gen = [None] * R, [None] * R, [None] * R, [1.0] * R, [], []
     for i, t in enumerate(trainers):
         b = batches[i]
         if b is None or np.atleast_2d(b["observations"]).shape[0] == 0:
             continue
-        if isinstance(t, TD3Trainer) or t._h is None or runs_general_step(t) or t._evaluate_on_host:
+        general_step = runs_general_step(t)
+        if isinstance(t, TD3Trainer) or t._h is None or (general_step and general != "device") or t._evaluate_on_host:
             out[i] = t.evaluate(b, eps=eps[i], rng=rngs[i], rows=rows)
             continue
         arrs[i], chunks[i] = t._eval_inputs(b, eps[i], rngs[i]), []
-        dev.append(i)
-    lib = _lib.load() if dev else None
-    for r0 in range(0, max([arrs[i][0].shape[0] for i in dev], default=0), _lib.ACT_MAX_ROWS):
-        live = [i for i in dev if arrs[i][0].shape[0] > r0]
-        for c in range(0, len(live), MAX_MEMBERS):
-            ids = live[c:c + MAX_MEMBERS]
-            n = len(ids)
-            n_rows = [min(arrs[i][0].shape[0] - r0, _lib.ACT_MAX_ROWS) for i in ids]
-            made = [trainers[i]._eval_io(arrs[i], r0, r0 + k) for i, k in zip(ids, n_rows)]
-            ios = (_lib.SacEvalIO * n)(*[m[0] for m in made])
-            _lib.check(lib.sac_evaluate_many((C.c_void_p * n)(*[trainers[i]._h.value for i in ids]), n,
-                                             (C.c_int32 * n)(*n_rows), ios), "sac_evaluate_many")
-            for k, i in enumerate(ids):
-                chunks[i].append(made[k][1])
-                alphas[i] = float(ios[k].alpha)
+        (gen if general_step else dev).append(i)
+    lib = _lib.load() if dev or gen else None
+    for members, entry in ((dev, "sac_evaluate_many"), (gen, "sac_evaluate_general_many")):
+        for r0 in range(0, max([arrs[i][0].shape[0] for i in members], default=0), _lib.ACT_MAX_ROWS):
+            live = [i for i in members if arrs[i][0].shape[0] > r0]
+            for c in range(0, len(live), MAX_MEMBERS):
+                ids = live[c:c + MAX_MEMBERS]
+                n = len(ids)
+                n_rows = [min(arrs[i][0].shape[0] - r0, _lib.ACT_MAX_ROWS) for i in ids]
+                made = [trainers[i]._eval_io(arrs[i], r0, r0 + k) for i, k in zip(ids, n_rows)]
+                ios = (_lib.SacEvalIO * n)(*[m[0] for m in made])
+                _lib.check(getattr(lib, entry)((C.c_void_p * n)(*[trainers[i]._h.value for i in ids]), n,
+                                               (C.c_int32 * n)(*n_rows), ios), entry)
+                for k, i in enumerate(ids):
+                    chunks[i].append(made[k][1])
+                    alphas[i] = float(ios[k].alpha)
     from .sac import _eval_columns
-    for i in dev:
+    for i in dev + gen:
         cols = _eval_columns(chunks[i], alphas[i])
         stats = trainers[i]._eval_stats(cols)
         out[i] = (stats, cols) if rows else stats
@@ -427,9 +433,9 @@ class _Members:
             nets_list = [("qf1", "qf2")] * len(self.trainers)
         return q_values_many(self.trainers, obs_list, act_list, nets_list, general=general)
 
-    def evaluate_many(self, batches, eps=None, rngs=None, rows=False):
-        """evaluate_many over the group's members."""
-        return evaluate_many(self.trainers, batches, eps=eps, rngs=rngs, rows=rows)
+    def evaluate_many(self, batches, eps=None, rngs=None, rows=False, general="host"):
+        """evaluate_many over the group's members (general as there)."""
+        return evaluate_many(self.trainers, batches, eps=eps, rngs=rngs, rows=rows, general=general)
 
 
 class _SACMembers:

@@ -450,13 +450,14 @@ class SACTrainer:
                             *[out[name].ctypes.data for name in _lib.EVAL_ARRAYS], 0.0)
         return io, out, parts
 
-    def _evaluate_device(self, arrs):
+    def _evaluate_device(self, arrs, entry="sac_evaluate"):
         n = arrs[0].shape[0]
         chunks, alpha = [], 1.0
+        fn = getattr(self._lib, entry)
         for i in range(0, n, _lib.ACT_MAX_ROWS):
             j = min(n, i + _lib.ACT_MAX_ROWS)
             io, out, _keep = self._eval_io(arrs, i, j)
-            _lib.check(self._lib.sac_evaluate(self._h, j - i, C.byref(io)), "sac_evaluate")
+            _lib.check(fn(self._h, j - i, C.byref(io)), entry)
             chunks.append(out)
             alpha = float(io.alpha)
         return _eval_columns(chunks, alpha)
@@ -539,7 +540,7 @@ class SACTrainer:
         return eval_statistics(np.stack([cols[k] for k in _lib.EVAL_ROWS]), cols["mu"], cols["log_std"], cols["alpha"],
                                self._eval_log_alpha(), self.target_entropy, self.use_automatic_entropy_tuning)
 
-    def evaluate(self, batch, eps=None, rng=None, rows=False):
+    def evaluate(self, batch, eps=None, rng=None, rows=False, general="host"):
         """The SAC objectives of this run on `batch` WITHOUT a gradient step: `batch` is the dict train() takes
         (observations, actions, rewards, terminals, next_observations; any n >= 1), typically transitions the run has not
         trained on -- an epoch's evaluation paths.  From the LIVE weights and the CURRENT entropy coefficient: on the
@@ -553,12 +554,19 @@ class SACTrainer:
         Returns an OrderedDict with get_diagnostics()' keys plus TD Error 1 / TD Error 2 Mean / Std / Max / Min (q - y,
         signed): eval_statistics of the per-row columns.  The training step logs its values behind its own alpha update;
         these are one alpha step earlier.  rows=True: (stats, columns), columns a dict of the float32 per-row arrays q1,
-        q2, q1_new, q2_new, tq1, tq2, log_pi, log_pi_next, y (n,), mu, log_std, a_new, a_next (n, A), and alpha."""
+        q2, q1_new, q2_new, tq1, tq2, log_pi, log_pi_next, y (n,), mu, log_std, a_new, a_next (n, A), and alpha.
+        general (one of group.GENERAL) decides for a trainer of the general step only: "host", the default, keeps the host
+        path; "device" evaluates on the device as well (sac_evaluate_general: k_eval_layer, one launch per layer on the
+        live weights, in calls of at most 1024 rows, no parameter copy).  A trainer with the fused kernels' shapes takes
+        sac_evaluate and a trainer without a handle the host path under either value."""
+        from .group import _check_general
+        _check_general(general)
         arrs = self._eval_inputs(batch, eps, rng)
-        if self._h is None or self.fused_mode() == 3 or self._evaluate_on_host:
+        gen = self._h is not None and self.fused_mode() == 3
+        if self._h is None or (gen and general != "device") or self._evaluate_on_host:
             cols = self._evaluate_host(arrs)
         else:
-            cols = self._evaluate_device(arrs)
+            cols = self._evaluate_device(arrs, "sac_evaluate_general" if gen else "sac_evaluate")
         stats = self._eval_stats(cols)
         return (stats, cols) if rows else stats
 

@@ -16,7 +16,8 @@
  weights against the discounted returns obtained there: sixteen evaluation/ columns more in progress.csv.
  --q_general device: with --q_diagnostics, runs of any hidden sizes evaluate their critics on the device too.
  --validation: every epoch, the SAC losses, TD errors and targets on the evaluation paths' transitions -- held-out data
- -- from the live weights: validation/ columns in progress.csv; SAC only)
+ -- from the live weights: validation/ columns in progress.csv; SAC only.
+ --eval_general device: with --validation, runs of any hidden sizes evaluate these objectives on the device too.)
 Runs the variant unchanged (batch size, lrs, tau, period, buffer size ... from the JSON) on the
 HIP library with a synthetic environment of the task's dimensions (robosuite is not installed)."""
 import argparse
@@ -74,7 +75,12 @@ if __name__ == "__main__":
                     help="every epoch, evaluate the SAC objectives (QF losses, TD errors, Q targets, log pi, policy loss) on "
                          "the transitions of the evaluation paths, which never enter the replay buffer (a HIP kernel on "
                          "the live weights), and log them as validation/<key>; SAC only; off: progress.csv is unchanged")
+    ap.add_argument("--eval_general", type=str, default="host", choices=["host", "device"],
+                    help="with --validation: where runs whose hidden sizes are beyond two layers of at most 256 units "
+                         "evaluate the SAC objectives -- host (a parameter copy and a NumPy forward) or device (one HIP "
+                         "launch per layer on the live weights); without --validation it has no effect")
     args = ap.parse_args()
+    eval_kw = {} if args.eval_general == "host" else dict(eval_general=args.eval_general)
     if (args.hidden_sweep or args.hidden_sizes) and not args.variants:
         raise SystemExit("--hidden_sweep / --hidden_sizes need --variants")
     if args.variants or args.seeds:
@@ -83,7 +89,8 @@ if __name__ == "__main__":
             raise SystemExit("--checkpoint needs --log_dir (the group is saved to <log_dir>/checkpoint)")
         group_kw = dict(log_dir=log_dir, num_epochs=args.epochs, resume=bool(args.resume), acting=args.acting,
                         q_diagnostics=args.q_diagnostics, q_general=args.q_general, validation=args.validation,
-                        checkpoint_dir=os.path.join(log_dir, "checkpoint") if (args.checkpoint or args.resume) else None)
+                        checkpoint_dir=os.path.join(log_dir, "checkpoint") if (args.checkpoint or args.resume) else None,
+                        **eval_kw)
         try:
             if args.variants:
                 seeds = args.seeds or [args.seed]
@@ -120,4 +127,4 @@ if __name__ == "__main__":
     ckpt = os.path.join(run_dir, "checkpoint") if (run_dir and not args.no_checkpoint) else None
     experiment(variant, log_dir=run_dir, seed=args.seed, num_epochs=args.epochs, checkpoint_dir=ckpt,
                resume=bool(args.resume), acting=args.acting, q_diagnostics=args.q_diagnostics,
-               q_general=args.q_general, validation=args.validation)
+               q_general=args.q_general, validation=args.validation, **eval_kw)
