@@ -134,6 +134,12 @@ int sac_sample_gather_device(sac_buffer_t *buf, int batch, int64_t n_batches, fl
 /* copy slot s of the last sac_sample_gather_device back to the host (tests) */
 int sac_read_slot(sac_buffer_t *buf, int64_t slot, float *obs, float *act, float *rew, float *term,
                   float *next_obs, int64_t *idx_out);
+/* The two row images of a minibatch slot (tests): per 16-row block the rows once more as the swizzled LDS row-block
+ * [16][KLQ] the fused step starts from, KLQ = round_up(round_up(obs_dim, 16) + 16, 64); element (row, k) of a block at
+ * row * KLQ + ((((k >> 2) ^ row) << 2) | (k & 3)).  img_sa holds [obs | 0 | act at round_up(obs_dim, 16) | 0], img_n
+ * [next_obs | 0]; each receives round_up(batch, 16) * KLQ floats.  ring = 0: slot `which` of the last batched draw
+ * (sac_read_slot's slots); ring = 1: the device batch with token `which` (sac_random_batch_device). */
+int sac_read_slot_images(sac_buffer_t *buf, int ring, int64_t which, float *img_sa, float *img_n);
 
 /* ------------------------------------------------------------------------------------------
  * SAC trainer.  Replaces rlkit SACTrainer (+ TorchTrainer.train, np_to_pytorch_batch,
@@ -314,8 +320,9 @@ int sac_trainer_set_xcd_mask(sac_trainer_t *t, unsigned xcd_mask);
 int sac_measure_peaks(int device, float out[4]);
 
 /* test access to intermediates of the last step: name in {"a_new","log_pi","mu","log_std","q1","q2",
- * "q_target","q1_new","q2_new","a_next","log_pi_next","g_policy","g_qf1","g_qf2"} (g_* = flat
- * gradient in the sac_get_params layout).  Returns the element count, <0 on error. */
+ * "q_target","q1_new","q2_new","a_next","log_pi_next","g_policy","g_qf1","g_qf2","ext_img_sa","ext_img_n"} (g_* = flat
+ * gradient in the sac_get_params layout; ext_img_*: the row images sac_step staged with its last batch, see
+ * sac_read_slot_images).  Returns the element count, <0 on error. */
 int64_t sac_debug_fetch(sac_trainer_t *t, const char *name, float *out, int64_t cap);
 
 /* policy.get_action(obs) on the HOST with weights mirrored from the device (acting path,

@@ -112,6 +112,7 @@ SYMBOLS = {
     "sac_gather": (C.c_int, [_P, _P, C.c_int, _P, _P, _P, _P, _P]),
     "sac_sample_gather_device": (C.c_int, [_P, C.c_int, C.c_int64, _P]),
     "sac_read_slot": (C.c_int, [_P, C.c_int64, _P, _P, _P, _P, _P, _P]),
+    "sac_read_slot_images": (C.c_int, [_P, C.c_int, C.c_int64, _P, _P]),
     "sac_trainer_create": (C.c_int, [C.POINTER(_P), C.POINTER(SacConfig)]),
     "sac_trainer_create_mlp": (C.c_int, [C.POINTER(_P), C.POINTER(SacConfig), _P, C.c_int32, _P, C.c_int32]),
     "td3_trainer_create": (C.c_int, [C.POINTER(_P), C.POINTER(Td3Config)]),

@@ -134,7 +134,8 @@ __global__ __launch_bounds__(256) void k_mt_randint_group(const SampleMember *__
 // k_gather: persistent 256-thread workgroups, each moving 16-row blocks of minibatch slots:
 //   HBM rows (16-B aligned, padded stride) --dwordx4--> registers --> LDS tile --dwordx4--> slot.
 // The LDS tile lets the unpadded (B,O) output be written as full 16-B-per-lane coalesced stores
-// and lets the same rows be re-emitted feature-major (saT[KQ][B], fragment-major: frag_off) for the weight-gradient kernel.
+// and lets the same rows be re-emitted feature-major (saT[KQ][B], fragment-major: frag_off) for the weight-gradient kernel
+// and as the two row images (img_sa, img_n: the swizzled LDS row-block of the fused step, ready to copy -- write_images).
 // Three-stage software pipeline per workgroup (indices of block n+2, rows of block n+1, write-out
 // of block n), so a workgroup always has a row burst in flight while it stores: the gather is
 // bound by bytes in flight per CU, not by the two dependent round trips (index -> row) per block.
@@ -216,8 +217,40 @@ __device__ __forceinline__ void gather_body(const ReplayView &rv, const int64_t 
         }
     }
 
+    // The two row images of a row-block (SlotLayout::off_img_sa / off_img_n): the rows once more, as the swizzled LDS
+    // row-block [16][KLQ] a step kernel starts from, so that the kernel copies 16 bytes per thread and page instead of
+    // converting the layout in front of its first MFMA -- once here, off the step's critical path, instead of once per
+    // block of the row-block and step.  Thread (row, c) writes the 16-byte group that sits at group 16 p + c of its row:
+    // columns 4 g .. 4 g + 3 with g = 16 p + (c ^ row) (img_off); padding columns are +0.0.
+    const int irow = tid >> 4, ic = tid & 15;
+    auto write_images = [&](float *S, int row0) {
+        const int KLQ = L.KLQ, ga = L.KA >> 2, na = ac < 4 ? ac : 4;
+        float *dsa = S + L.off_img_sa + (int64_t)(row0 + irow) * KLQ + 4 * ic;
+        float *dn = S + L.off_img_n + (int64_t)(row0 + irow) * KLQ + 4 * ic;
+        for (int p = 0; p < (KLQ >> 6); ++p) {
+            const int g = 16 * p + (ic ^ irow);
+            float4 a = make_float4(0.f, 0.f, 0.f, 0.f), n = a;
+            if (g < oc) {
+                a = *reinterpret_cast<const float4 *>(t_obs + irow * Ost + 4 * g);
+                n = *reinterpret_cast<const float4 *>(t_nobs + irow * Ost + 4 * g);
+                const int left = O - 4 * g;          // (storage rows are padded to 16 bytes: those columns are no input)
+                if (left < 4) { a.w = 0.f; n.w = 0.f; }
+                if (left < 3) { a.z = 0.f; n.z = 0.f; }
+                if (left < 2) { a.y = 0.f; n.y = 0.f; }
+            } else if (g >= ga && g < ga + na) {
+                a = *reinterpret_cast<const float4 *>(t_act + irow * Ast + 4 * (g - ga));
+                const int left = A - 4 * (g - ga);
+                if (left < 4) a.w = 0.f;
+                if (left < 3) a.z = 0.f;
+                if (left < 2) a.y = 0.f;
+            }
+            *reinterpret_cast<float4 *>(dsa + 64 * p) = a;
+            *reinterpret_cast<float4 *>(dn + 64 * p) = n;
+        }
+    };
+
     // stage C: registers of one block -> LDS tile -> slot
-    auto write_out = [&](int blk, const float4 (&Do)[NIT], const float4 (&Dn)[NIT], const float4 &Da, float Ds,
+    auto write_out =[&](int blk, const float4 (&Do)[NIT], const float4 (&Dn)[NIT], const float4 &Da, float Ds,
                          float Ds2) {
         const int slot = blk / blocks_per_slot;
         const int row0 = (blk - slot * blocks_per_slot) * RB;
@@ -252,6 +285,7 @@ __device__ __forceinline__ void gather_body(const ReplayView &rv, const int64_t 
                     const int f = (tid + 256 * ps) >> 2, frow = (f < O) ? f : L.KA + (f - O);
                     *reinterpret_cast<float4 *>(S + L.off_saT + frag_off(frow, row0 + 4 * (tid & 3), B)) = v;   // fragment-major
                 }
+            write_images(S, row0);
             lds_barrier();                         // tile free for the next block
             return;
         }
@@ -300,6 +334,7 @@ __device__ __forceinline__ void gather_body(const ReplayView &rv, const int64_t 
                 *reinterpret_cast<float4 *>(T + frag_off((f < O) ? f : L.KA + (f - O), row0 + 4 * q, B)) = v;
             }
         }
+        write_images(S, row0);
         lds_barrier();                             // tile free for the next block
     };
 
@@ -1144,6 +1179,26 @@ int sac_read_slot(sac_buffer_t *b, int64_t slot, float *obs, float *act, float *
     if (idx_out)
         SAC_HIP(hipMemcpyAsync(idx_out, b->d_idx + slot * b->slot.B, sizeof(int64_t) * b->slot.Bt,
                                hipMemcpyDeviceToHost, b->stream));
+    SAC_HIP(hipStreamSynchronize(b->stream));
+    return 0;
+}
+
+int sac_read_slot_images(sac_buffer_t *b, int ring, int64_t which, float *img_sa, float *img_n) {
+    SAC_REQUIRE(b && img_sa && img_n, "bad arguments to sac_read_slot_images");
+    int64_t slot = which;
+    if (ring) {
+        slot = sac_ring_slot_of(b, which);
+        if (slot < 0) return -1;
+    } else {
+        SAC_REQUIRE(slot >= 0 && slot < b->n_slots, "slot %lld out of range", (long long)slot);
+    }
+    SAC_HIP(hipSetDevice(b->device));
+    const SlotLayout &L = ring ? b->ring_layout : b->slot;
+    SAC_REQUIRE(L.has_images(), "this slot layout carries no row images");
+    const float *S = (ring ? b->d_ring : b->d_slots) + slot * L.slot_floats;
+    const size_t bytes = sizeof(float) * (size_t)L.B * L.KLQ;
+    SAC_HIP(hipMemcpyAsync(img_sa, S + L.off_img_sa, bytes, hipMemcpyDeviceToHost, b->stream));
+    SAC_HIP(hipMemcpyAsync(img_n, S + L.off_img_n, bytes, hipMemcpyDeviceToHost, b->stream));
     SAC_HIP(hipStreamSynchronize(b->stream));
     return 0;
 }

@@ -59,8 +59,22 @@ struct SlotLayout {
     int KQ;                       // KA + 16
     int KQ64;                     // rows allocated for saT: round_up(KQ, 64) (64-wide k strips)
     int64_t off_obs, off_act, off_rew, off_term, off_nobs, off_saT;
+    // Row images: per 16-row block one ready copy [16][KLQ] of the swizzled LDS row-block a step kernel starts from --
+    // element (row, k) at float offset img_off(row, k, KLQ), which is lds_off of the step kernels, padding columns +0.0.
+    // img_sa holds [obs | 0 | act | 0] (the Q nets' input; the policy reads its first KA columns), img_n holds
+    // [next_obs | 0 | 0] (the action chunk is the head's to write).  Row-block rb of an image starts at rb * 16 * KLQ.
+    // Every writer of a slot writes them (gather kernels, external-batch staging): a layout with off_img_sa == 0 has none.
+    int KLQ;                      // image row stride: round_up(KQ, 64), the step kernels' stride of X0
+    int64_t off_img_sa, off_img_n;
     int64_t slot_floats;          // multiple of 64 floats (256 B)
+    __host__ __device__ bool has_images() const { return off_img_sa > 0; }
 };
+
+// position of element (row, k) in a swizzled row-block of stride KL (a multiple of 64): the 16-byte groups of a row are
+// permuted by its row number inside each 64-float page -- bank-conflict-free MFMA operand reads (== lds_off, sac_trainer.hip)
+static inline __host__ __device__ int img_off(int row, int k, int KL) {
+    return row * KL + ((((k >> 2) ^ (row & 15)) << 2) | (k & 3));
+}
 
 static inline SlotLayout make_slot_layout(int batch, int O, int A) {
     SlotLayout L;
@@ -76,6 +90,9 @@ static inline SlotLayout make_slot_layout(int batch, int O, int A) {
     L.off_term = off; off += round_up64(B, 64);
     L.off_nobs = off; off += round_up64((int64_t)B * O, 64);
     L.off_saT = off;  off += (int64_t)L.KQ64 * B;
+    L.KLQ = L.KQ64;
+    L.off_img_sa = off; off += (int64_t)B * L.KLQ;
+    L.off_img_n = off;  off += (int64_t)B * L.KLQ;
     L.slot_floats = round_up64(off, 64);
     return L;
 }

@@ -194,12 +194,45 @@ __device__ __forceinline__ bool split_first_layer(WRing<1, D> &rq, const float *
     return true;
 }
 
+// The swizzled LDS row-block [16][KL] from a slot's row image (SlotLayout::off_img_sa: the gather has stored the same words in
+// the same order, img_off == lds_off): thread (row = tid / 16, c = tid % 16) moves the 16 bytes at row * KL + 64 p + 4 c of
+// every 64-float page p -- at one page per row (K <= 64) that is 4 * tid.  One multiply-add of address arithmetic, no select,
+// no per-element swizzle, against RowRegs' K / 16 dword loads and ds_write_b32 per thread.  issue() / commit() as RowRegs:
+// request early, write LDS when the rows are needed.
+template <int PAGES>                          // KL <= 64 * PAGES
+struct ImgRegs {
+    f32x4 v[PAGES];
+    __device__ __forceinline__ void issue(const float *__restrict__ img, int KL) {
+        const float *p = img + (threadIdx.x >> 4) * KL + 4 * (threadIdx.x & 15);
+#pragma unroll
+        for (int j = 0; j < PAGES; ++j) {
+            v[j] = f32x4{0.f, 0.f, 0.f, 0.f};
+            if (64 * j < KL) v[j] = ld4(p + 64 * j);
+        }
+    }
+    // skip_k >= 0: the k-chunk (16 columns) at skip_k is left to another writer (the policy head's action)
+    __device__ __forceinline__ void commit(float *X, int KL, int skip_k = -1) const {
+        const int row = threadIdx.x >> 4, c = threadIdx.x & 15;
+        float *p = X + row * KL + 4 * c;
+        // (this thread's group of page p holds columns 64 p + 4 (c ^ row) ..: in the chunk iff p and two bits of c ^ row match)
+        const int sp = (skip_k >= 0 && ((c ^ row) >> 2) == ((skip_k >> 4) & 3)) ? (skip_k >> 6) : -1;
+#pragma unroll
+        for (int j = 0; j < PAGES; ++j)
+            if (64 * j < KL && j != sp) st4(p + 64 * j, v[j]);
+    }
+};
+
 // MODE M_TD3_CRITIC (round 3): the TD3 critic pass as the same launch.  Critic chain: phase A (Q_i(s, a)), no phase B, phase C
 // (critic backward, target without entropy term) behind the target partials.  Policy chain on s' (net 1): the TARGET
 // policy, head = tanh(mean) + clipped smoothing noise, T2; policy chain on s (net 0): the online policy's phase A only when
 // an actor pass follows this launch (sa.pad2 bit 2: its head partials and activations are what that pass reads), then T1.
 // No log pi anywhere, no policy backward (the actor pass keeps its own launches).
-template <int NTH, bool WIDE, int MODE = M_SAC>
+//
+// IMG: the input rows come as the slot's row images (ImgRegs) instead of being converted from the row-major rows (RowRegs) --
+// the same values into the same LDS words, so the two instances compute the same bits.  The s' chain then keeps its phase-A
+// rows for phase B (only the action chunk differs, and the head writes it), and the critic chain takes the batch action from
+// X0's action chunk instead of loading it again.  Chosen by the step plan (StepPlan::row_images).
+template <int NTH, bool WIDE, int MODE = M_SAC, bool IMG = false>
 __global__ __launch_bounds__(256) void k_abc(Dev d, const float *__restrict__ S, SlotLayout SL, StepArg sa) {
     kernarg_prefetch<sizeof(Dev) + 8 + sizeof(SlotLayout) + sizeof(StepArg)>();
     constexpr int SP = 4, SW = 64;
@@ -254,8 +287,10 @@ __global__ __launch_bounds__(256) void k_abc(Dev d, const float *__restrict__ S,
         const Layer L0 = isq ? d.LQ[0] : d.LP[0], L1 = isq ? d.LQ[1] : d.LP[1], L2 = isq ? d.LQ[2] : d.LP[2];
         const int K0 = isq ? d.KQ : d.KP;
         const float *obs = S + ((!isq && net) ? SL.off_nobs : SL.off_obs) + (size_t)row0 * O;
-        RowRegs<WIDE ? 32 : 8> rows;
-        rows.issue(K0, obs, O, O, S + SL.off_act + (size_t)row0 * A, isq ? A : 0, A, d.KP);
+        RowRegs<IMG ? 1 : (WIDE ? 32 : 8)> rows;
+        ImgRegs<IMG ? (WIDE ? 8 : 2) : 1> img;
+        if constexpr (IMG) img.issue(S + ((!isq && net) ? SL.off_img_n : SL.off_img_sa) + (size_t)row0 * KLQ, KLQ);
+        else rows.issue(K0, obs, O, O, S + SL.off_act + (size_t)row0 * A, isq ? A : 0, A, d.KP);
         WRing<4, WIDE ? 1 : RD0> r0;
         WRing<1, 8> rq;                                       // WIDE: this wave's ONE tile of this part's quarter (split_first_layer)
         constexpr int PRE0 = 2;
@@ -288,6 +323,7 @@ __global__ __launch_bounds__(256) void k_abc(Dev d, const float *__restrict__ S,
             SB();                                                                                       \
         } while (0)
         if constexpr (WIDE) ABC_LATE_REQUESTS();
+        STAMP(0, 12);                                         // the block's first requests are issued
         // The N(0,1) draw of phase B's rsample depends on nothing but (seed, step, row, action): it is computed HERE, behind
         // the block's first requests, in the ~1.3 us it waits for their data anyway (in phase B it would sit on the
         // critical path: the head partials are usually there before this chain is).
@@ -296,8 +332,10 @@ __global__ __launch_bounds__(256) void k_abc(Dev d, const float *__restrict__ S,
             const float *epp0 = side0 ? d.eps2 : d.eps1;
             if (a < A && !epp0) eps = philox_normal(d.noise_seed, (unsigned long long)sa.step_now, (unsigned)(grow * 16 + a), side0 ? 1u : 0u);
         }
-        rows.commit(X0, KLQ, K0, O, d.KP, isq ? A : 0);
+        if constexpr (IMG) img.commit(X0, KLQ);            // (whole pages: the policy chains ignore the columns behind KP)
+        else rows.commit(X0, KLQ, K0, O, d.KP, isq ? A : 0);
         lds_barrier();
+        STAMP(0, 13);                                         // the input rows are in LDS
         if constexpr (WIDE) {   // first layer: this part's quarter, then the exchange with the other three parts
             const int chain = isq ? net : 2 + net;
             if (!split_first_layer(rq, X0, KLQ, K0 >> 4, bq, d.zx + (size_t)(chain * NB + rb) * (RB * H),
@@ -390,10 +428,16 @@ __global__ __launch_bounds__(256) void k_abc(Dev d, const float *__restrict__ S,
     const float hbm = PH[d.LP[2].offB + am], hbr = (MODE == M_SAC) ? PH[d.LP[2].offB + A + am] : 0.f;
     if (a < A && epp) eps = epp[grow * A + am];            // (caller-supplied noise; the device stream's draw was made at entry)
     // (a handful of small loads that do not depend on the hand-off either: the s' rows of the target net / the batch action)
-    RowRegs<WIDE ? 32 : 8> rows2;
+    // (row images: the s' chain still holds these rows in X0 from its phase A, and the critic chain the batch action)
+    RowRegs<IMG ? 1 : (WIDE ? 32 : 8)> rows2;
+    ImgRegs<IMG ? (WIDE ? 8 : 2) : 1> img2;
     float abat = 0.f;
-    if (isq) abat = S[SL.off_act + (size_t)grow * A + ((a < A) ? a : 0)];
-    else rows2.issue(d.KQ, S + SL.off_nobs + (size_t)row0 * O, O, O, nullptr, 0, 0, 0);
+    if constexpr (IMG) {
+        if (!isq && net == 0) img2.issue(S + SL.off_img_n + (size_t)row0 * KLQ, KLQ);
+    } else {
+        if (isq) abat = S[SL.off_act + (size_t)grow * A + ((a < A) ? a : 0)];
+        else rows2.issue(d.KQ, S + SL.off_nobs + (size_t)row0 * O, O, O, nullptr, 0, 0, 0);
+    }
     if (threadIdx.x == 0)
         s_ok = (isq && (int)(peek - 4u * seq) >= 0) ? 1 : handoff_wait(cnt_head + (size_t)(side * NB + rb) * CNT_STRIDE, 4u * seq, d.abort_flag);
     if (isq) asm volatile("s_waitcnt vmcnt(0)" ::: "memory");          // phase A's stores (and two small loads): ~1 us old
@@ -452,7 +496,11 @@ __global__ __launch_bounds__(256) void k_abc(Dev d, const float *__restrict__ S,
 #pragma unroll
     for (int u = 0; u < 4; ++u) w3[u] = PQ[d.LQ[2].offW + frag_off(0, SW * part + a + 16 * u, H)];
     SB();
-    if (!isq) rows2.commit(X0, KLQ, d.KQ, O, 0, 0, d.KP, d.KP + 16);     // (the head writes the action chunk)
+    if constexpr (IMG) {
+        if (!isq && net == 0) img2.commit(X0, KLQ, d.KP);                // (the head writes the action chunk)
+    } else {
+        if (!isq) rows2.commit(X0, KLQ, d.KQ, O, 0, 0, d.KP, d.KP + 16);
+    }
     // ---- tanh-Gaussian head on this block's rows (every block of the row-block computes the same) ----
     float lp = 0.f, mean = 0.f, raw = 0.f, lstd = 0.f, stdv = 1.f, zz = 0.f, act = 0.f;
     USE_FROM_HERE(hm[0]);
@@ -477,7 +525,11 @@ __global__ __launch_bounds__(256) void k_abc(Dev d, const float *__restrict__ S,
         }
     }
     // the whole action chunk (0 beyond A); the critic chain contracts the difference to the batch action
-    X0[lds_off(row, d.KP + a, KLQ)] = (a < A) ? (isq ? act - abat : act) : 0.f;
+    {
+        float *xa = X0 + lds_off(row, d.KP + a, KLQ);
+        if constexpr (IMG) { if (isq) abat = *xa; }                      // (phase A left [obs | 0 | act | 0] here)
+        *xa = (a < A) ? (isq ? act - abat : act) : 0.f;
+    }
     const float lsum = group16_sum(lp);
     if (own_s && a == 0) red[row] = (grow < d.Bt) ? lsum : 0.f;          // (pad rows carry no weight)
     lds_barrier();

@@ -36,6 +36,7 @@ struct StepEnv {
     EnvInt chain8;                // SAC_CHAIN8=0: the four-wave k_chain (A/B comparisons)
     EnvInt bwd8;                  // SAC_BWD8=0: the four-wave backward launch at column split 1 (A/B comparisons)
     EnvInt chain_bwd;             // SAC_CHAIN_BWD=1 / 0: forces the backward blocks into the chained launch / out of it
+    EnvInt row_images;            // SAC_ROW_IMAGES=0: k_abc converts its input rows itself (RowRegs; A/B comparisons)
 };
 
 // the only getenv() calls for these names
@@ -46,7 +47,8 @@ static inline StepEnv step_env_from_environment() {
     };
     const char *form = getenv("SAC_DW_FORM");
     return StepEnv{num("SAC_FORCE_SP"), num("SAC_WIDE_MIN_KQ"), form && strcmp(form, "loop") == 0, num("SAC_FUSED"),
-                   num("SAC_FUSED_TEST_STALL"), num("SAC_CHAIN"), num("SAC_CHAIN8"), num("SAC_BWD8"), num("SAC_CHAIN_BWD")};
+                   num("SAC_FUSED_TEST_STALL"), num("SAC_CHAIN"), num("SAC_CHAIN8"), num("SAC_BWD8"), num("SAC_CHAIN_BWD"),
+                   num("SAC_ROW_IMAGES")};
 }
 
 struct StepLaunch {
@@ -65,6 +67,7 @@ struct StepPlan {
     bool bwd8 = false;                                // launch C at column split 1 on eight waves (k_bwd8)
     bool chain_bwd = false;                           // the fused launch is k_chain8 with the backward blocks inside
     bool dw_one = false;                              // the weight-gradient launch in its one-group form
+    bool row_images = false;                          // k_abc copies its input rows from the slot's ready LDS images (SlotLayout::off_img_sa)
     unsigned test_stall_at = 0;
     // The launches.  a / b / c are the four-launch step's (what a fused trainer falls back to -- with `chained` in place
     // of a + b where `chain` is set); compact: k_bwd's last argument (SAC).  b2 / c2: TD3's actor pass.
@@ -108,6 +111,10 @@ static inline StepPlan step_plan(int obs_dim, int act_dim, int batch, int algo, 
     const size_t lds_abc = sizeof(float) * (size_t)(RB * KL0q + RB * H + RB * 64 + FUSED_RED + H * WLD);
     P.fused = SP == 4 && NB <= 16 && 16 * NB <= cus && lds_abc <= LDS_CAP && !E.fused.is(0);
     P.fused_launch = StepLaunch{16 * NB, 256, lds_abc};
+    // k_abc takes its input rows as the slot's row images.  Every writer of a slot produces them (the gather kernels, the
+    // staging of an external batch: SlotLayout::has_images), so the choice is by kernel alone -- the other step kernels
+    // convert the row-major rows themselves.
+    P.row_images = P.fused && !E.row_images.is(0);
     // Column split 1: the forward launches as one (sac_chain.h).
     // Where it pays (measured, scripts/large_batch_matrix.sh; round 3's second half with the eight-wave kernel): first layers
     // of at most eight k-chunks -- Door 46/7 batch 1024 58.1 -> 51.8 us per step, TwoArmHandoff 86/14 64.9 -> 60.9, and
@@ -131,6 +138,7 @@ static inline StepPlan step_plan(int obs_dim, int act_dim, int batch, int algo, 
     P.chain_bwd = P.chain && P.chain8 && P.bwd8 && 4 * NB <= cus && (E.chain_bwd.set ? E.chain_bwd.v == 1 : pays_b);
     if (P.chain_bwd) {
         P.fused = true;
+        P.row_images = false;
         P.fused_launch = StepLaunch{4 * NB, 512, lds_chain > lds_bw ? lds_chain : lds_bw};
     }
     // the four launches (launch C of SAC: see k_bwd for `compact`; TD3's critic map: two twins x groups of four blocks)

@@ -1889,13 +1889,14 @@ __global__ __launch_bounds__(256) void k_dw_adam_group(const GroupMember *__rest
 // The one table from a step variant to its kernel instances.  a / b / c: launches A, B, C (SAC, or TD3's critic pass);
 // b2 / c2: TD3's actor pass; abc: the fused launch; chain: k_chain8 or k_chain; chain_bwd: k_chain8 with the backward
 // blocks inside; bwd8: launch C on eight waves (the last three: SAC only).  group[]: the grouped instances of a, b, c,
-// b2, c2 (column split 4 only).  `fused` is left to the trainer: abc or chain_bwd, as its plan says.
+// b2, c2 (column split 4 only).  abc_img: k_abc reading the slot's row images.  `fused` is left to the trainer: abc,
+// abc_img or chain_bwd, as its plan says.
 using StepFnA = void (*)(Dev, const float *, SlotLayout, int);
 using StepFnB = void (*)(Dev, const float *, SlotLayout, StepArg);
 using StepFnC = void (*)(Dev, const float *, SlotLayout, StepArg, int);
 struct StepKernels {
     StepFnA a = nullptr;
-    StepFnB b = nullptr, b2 = nullptr, abc = nullptr, chain = nullptr, chain_bwd = nullptr, fused = nullptr;
+    StepFnB b = nullptr, b2 = nullptr, abc = nullptr, abc_img = nullptr, chain = nullptr, chain_bwd = nullptr, fused = nullptr;
     StepFnC c = nullptr, c2 = nullptr, bwd8 = nullptr;
     const void *group[5] = {};
 };
@@ -1905,7 +1906,7 @@ void step_kernels_abc(StepKernels &k, int algo) {
     auto fn = [](auto f) { return reinterpret_cast<const void *>(f); };
     if (algo == 0) {
         k.a = &k_fwd_a<NTH, W, SP>; k.b = &k_fwd_b<NTH, W, SP>; k.c = &k_bwd<NTH, SP>;
-        k.abc = &k_abc<NTH, W>;
+        k.abc = &k_abc<NTH, W>; k.abc_img = &k_abc<NTH, W, M_SAC, true>;
         if constexpr (SP == 4) {
             k.group[0] = fn(&k_fwd_a_group<NTH, W, 4>); k.group[1] = fn(&k_fwd_b_group<NTH, W, 4>);
             k.group[2] = fn(&k_bwd_group<NTH, 4>);
@@ -1913,7 +1914,7 @@ void step_kernels_abc(StepKernels &k, int algo) {
     } else if constexpr (NTH == 1) {                  // (TD3's policy head is one tile: act_dim <= 16)
         k.a = &k_fwd_a<1, W, SP, M_TD3_CRITIC>; k.b = &k_fwd_b<1, W, SP, M_TD3_CRITIC>; k.c = &k_bwd<1, SP, M_TD3_CRITIC>;
         k.b2 = &k_fwd_b<1, W, SP, M_TD3_ACTOR>; k.c2 = &k_bwd<1, SP, M_TD3_ACTOR>;
-        k.abc = &k_abc<1, W, M_TD3_CRITIC>;
+        k.abc = &k_abc<1, W, M_TD3_CRITIC>; k.abc_img = &k_abc<1, W, M_TD3_CRITIC, true>;
         if constexpr (SP == 4) {
             k.group[0] = fn(&k_fwd_a_group<1, W, 4, M_TD3_CRITIC>);
             k.group[1] = fn(&k_fwd_b_group<1, W, 4, M_TD3_CRITIC>); k.group[3] = fn(&k_fwd_b_group<1, W, 4, M_TD3_ACTOR>);
@@ -2149,6 +2150,7 @@ void gate_leave(int device, bool tenant = true, hipStream_t s = nullptr, hipStre
 // the fused forward/backward launch of a step (k_abc: SAC, or the TD3 critic pass); sa gets the launch number
 int launch_fused_abc(sac_trainer *t, const float *S, const SlotLayout &SL, StepArg &sa, unsigned extra_flags) {
     hipStream_t s = t->stream;
+    SAC_REQUIRE(!t->plan.row_images || (SL.has_images() && SL.KLQ == round_up(t->plan.KQ, 64)), "the fused step reads row images, this slot has none");
     sa.seq = ++t->fused_seq;
     sa.pad2 |= extra_flags | ((t->plan.test_stall_at && sa.seq == t->plan.test_stall_at) ? 1u : 0u);
     t->fused_unchecked += 1;
@@ -2631,7 +2633,7 @@ static int trainer_bind(sac_trainer *t) {
     auto fn = [](auto f) { return reinterpret_cast<const void *>(f); };
     t->k = step_kernels(P.nth, P.wide, P.SP, P.algo, P.chain8, P.wide4);
     if (P.bwd8) t->k.c = t->k.bwd8;
-    t->k.fused = P.chain_bwd ? t->k.chain_bwd : t->k.abc;
+    t->k.fused = P.chain_bwd ? t->k.chain_bwd : (P.row_images ? t->k.abc_img : t->k.abc);
     if (P.fused && trainer_make_fused(t)) return -1;
     if (P.chain && raise_lds(fn(t->k.chain), P.chained)) return -1;
     if (raise_lds(fn(t->k.a), P.a) || raise_lds(fn(t->k.b), P.b)) return -1;
@@ -2849,20 +2851,28 @@ int sac_step(sac_trainer_t *t, const float *obs, const float *act, const float *
     const int B = t->B, Bt = t->Bt, O = t->O, A = t->A;     // B: slot rows (padded to row-blocks), Bt: rows given
     const SlotLayout &L = t->ext_layout;
     hipStream_t s = t->stream;
-    // np_to_pytorch_batch: host fp32 -> pinned -> HBM slot (row-major part), + feature-major saT; rows beyond the
-    // batch (row-block padding) are zero and carry no weight
-    const size_t nfl = (size_t)B * (2 * O + A + 2) + (size_t)L.KQ64 * B + (eps1 ? 2 * (size_t)B * A : 0);
+    // np_to_pytorch_batch: host fp32 -> pinned -> HBM slot (row-major part), + feature-major saT, + the two row images
+    // (SlotLayout::off_img_sa: every writer of a slot writes them); rows beyond the batch (row-block padding) are zero
+    // and carry no weight
+    const size_t nimg = 2 * (size_t)B * L.KLQ;
+    const size_t nfl = (size_t)B * (2 * O + A + 2) + (size_t)L.KQ64 * B + nimg + (eps1 ? 2 * (size_t)B * A : 0);
     if (ensure_stage_t(t, sizeof(float) * nfl)) return -1;
     float *st = (float *)t->h_stage;
     memset(st, 0, sizeof(float) * nfl);
     float *so = st, *sa = so + (size_t)B * O, *sr = sa + (size_t)B * A, *stt = sr + B, *sn = stt + B,
-          *sT = sn + (size_t)B * O, *se = sT + (size_t)L.KQ64 * B;
+          *sT = sn + (size_t)B * O, *sI = sT + (size_t)L.KQ64 * B, *se = sI + nimg;
     memcpy(so, obs, sizeof(float) * Bt * O); memcpy(sa, act, sizeof(float) * Bt * A);
     memcpy(sr, rew, sizeof(float) * Bt); memcpy(stt, term, sizeof(float) * Bt);
     memcpy(sn, next_obs, sizeof(float) * Bt * O);
     for (int b = 0; b < Bt; ++b) {
         for (int k = 0; k < O; ++k) sT[frag_off(k, b, B)] = obs[(size_t)b * O + k];
         for (int k = 0; k < A; ++k) sT[frag_off(L.KA + k, b, B)] = act[(size_t)b * A + k];
+        float *isa = sI + (size_t)(b / RB) * RB * L.KLQ, *in = isa + (size_t)B * L.KLQ;      // this row-block of img_sa, img_n
+        for (int k = 0; k < O; ++k) {
+            isa[img_off(b % RB, k, L.KLQ)] = obs[(size_t)b * O + k];
+            in[img_off(b % RB, k, L.KLQ)] = next_obs[(size_t)b * O + k];
+        }
+        for (int k = 0; k < A; ++k) isa[img_off(b % RB, L.KA + k, L.KLQ)] = act[(size_t)b * A + k];
     }
     float *E = t->ext_slot;
     SAC_HIP(hipMemcpyAsync(E + L.off_obs, so, sizeof(float) * B * O, hipMemcpyHostToDevice, s));
@@ -2871,6 +2881,7 @@ int sac_step(sac_trainer_t *t, const float *obs, const float *act, const float *
     SAC_HIP(hipMemcpyAsync(E + L.off_term, stt, sizeof(float) * B, hipMemcpyHostToDevice, s));
     SAC_HIP(hipMemcpyAsync(E + L.off_nobs, sn, sizeof(float) * B * O, hipMemcpyHostToDevice, s));
     SAC_HIP(hipMemcpyAsync(E + L.off_saT, sT, sizeof(float) * (size_t)L.KQ64 * B, hipMemcpyHostToDevice, s));
+    SAC_HIP(hipMemcpyAsync(E + L.off_img_sa, sI, sizeof(float) * nimg, hipMemcpyHostToDevice, s));      // (img_n follows img_sa)
     if (eps1) {
         memcpy(se, eps1, sizeof(float) * Bt * A); memcpy(se + (size_t)B * A, eps2, sizeof(float) * Bt * A);
         SAC_HIP(hipMemcpyAsync(t->d_eps, se, sizeof(float) * 2 * B * A, hipMemcpyHostToDevice, s));
@@ -3346,6 +3357,15 @@ int64_t sac_debug_fetch(sac_trainer_t *t, const char *name, float *out, int64_t 
         return 0;
     };
     std::vector<float> h;
+    if (nm == "ext_img_sa" || nm == "ext_img_n") {          // a row image of the external-batch slot (sac_step's staging)
+        const SlotLayout &L = t->ext_layout;
+        const int64_t n = (int64_t)L.B * L.KLQ;
+        if (!L.has_images()) { sac::set_error("the external-batch slot carries no row images"); return -2; }
+        if (cap < n) { sac::set_error("buffer too small"); return -2; }
+        if (fetch(t->ext_slot + (nm == "ext_img_sa" ? L.off_img_sa : L.off_img_n), n, h)) return -1;
+        memcpy(out, h.data(), sizeof(float) * n);
+        return n;
+    }
     if (nm == "diag_trace") {
         const int64_t n = (int64_t)DIAG_TRACE_CAP * SAC_DIAG_N < cap ? (int64_t)DIAG_TRACE_CAP * SAC_DIAG_N : cap;
         if (fetch(d.diag_trace, n, h)) return -1;

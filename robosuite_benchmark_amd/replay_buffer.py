@@ -336,6 +336,17 @@ class EnvReplayBuffer:
                                            _lib.ptr(term), _lib.ptr(nobs), _lib.ptr(idx)), "sac_read_slot")
         return dict(observations=obs, actions=act, rewards=rew, terminals=term, next_observations=nobs), idx
 
+    def read_slot_images(self, which, batch_size, ring=False):
+        """The two row images of a minibatch slot, each as [row-blocks][16 * KLQ] in device order (tests).  ring: `which` is
+        a device batch (its token, or the batch dict random_batch returned) instead of a slot of the last batched draw."""
+        O = self._observation_dim
+        klq = -(-(-(-O // 16) * 16 + 16) // 64) * 64
+        nb = -(-int(batch_size) // 16)
+        img_sa, img_n = np.empty((nb, 16 * klq), np.float32), np.empty((nb, 16 * klq), np.float32)
+        _lib.check(self._lib.sac_read_slot_images(self._h, int(bool(ring)), int(which), _lib.ptr(img_sa), _lib.ptr(img_n)),
+                   "sac_read_slot_images")
+        return img_sa, img_n
+
     def get_diagnostics(self):
         return OrderedDict([("size", self.num_steps_can_sample())])
 

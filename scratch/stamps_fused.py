@@ -30,6 +30,9 @@ for sel, name in ((lambda b: ((b & 7) ^ XOR) < 4, "critic chain"), (lambda b: ((
     print(f"{name} n={len(bl)}")
     for i in range(ns):
         print(f"   {names[i]:>14s}: median {med[i]:6.2f}  max {mx[i]:6.2f}")
+    if ww[:, 13].max() > 0:      # the prologue of phase A: stamps 12 (first requests issued) and 13 (input rows in LDS)
+        for i, nm in ((12, "requests issued"), (13, "rows committed")):
+            print(f"   {nm:>14s}: median {np.median(ww[:, i] - t0) / 100.0:6.2f}  max {(ww[:, i].max() - t0) / 100.0:6.2f}")
 w4 = st[4]
 b4 = [b for b in range(512) if w4[b, 0] > 0]
 if b4:
