@@ -454,6 +454,30 @@ int sac_evaluate_many(sac_trainer_t *const *trainers, int n_trainers, const int3
  * sac_evaluate_many keep refusing general-step trainers. */
 int sac_evaluate_general(sac_trainer_t *t, int64_t n, sac_eval_io_t *io);         /* n in 1..1024 */
 int sac_evaluate_general_many(sac_trainer_t *const *trainers, int n_trainers, const int32_t *n_rows, sac_eval_io_t *io);
+/* The STATISTICS of such an evaluation reduced on the device as well (k_eval_moments, csrc/sac_eval_moments.h): one more
+ * launch behind the evaluation's kernels and in front of the call's single wait reads the float32 columns where they
+ * lie and leaves nine moment records per member, every element formed in float64:
+ *   SAC_EVAL_M_Q1 / Q2 / Y / LOG_PI     the rows q1, q2, y, log_pi                                  (n elements)
+ *   SAC_EVAL_M_MU / LOG_STD             the head's mean and clamped log_std                         (n A elements)
+ *   SAC_EVAL_M_TD1 / TD2                (double)q1 - (double)y, (double)q2 - (double)y              (n)
+ *   SAC_EVAL_M_POLICY                   (double)log_pi - min((double)q1_new, (double)q2_new)        (n)
+ * A record: count; sum = sum of x; sumsq = sum of x^2; m2 = sum of (x - sum / count)^2 in a second pass over the same
+ * elements (np.std's form: 0 for a constant column); max and min, which keep a NaN as np.max / np.min do.  The order of
+ * every sum is a function of the record's own element count only -- never of the other members of the call, of a
+ * member's place among them or of the optional arrays asked for: a member's records are byte for byte those of its
+ * solo call.  alpha is io->alpha; log_alpha what sac_get_scalars' scalars[0] would return at this moment, from the same
+ * read.  The contract is that of sac_evaluate_many / sac_evaluate_general_many (admission, refusals, the drain, 0..1024
+ * rows, 1..16 trainers, each family refusing the other's trainers) with two differences: io[i].rows may be NULL -- then no
+ * column is copied back -- and stats[i] is filled for every member with rows.  Null stats: refused.  The columns are
+ * bit for bit those of the entries above. */
+enum { SAC_EVAL_M_Q1, SAC_EVAL_M_Q2, SAC_EVAL_M_Y, SAC_EVAL_M_LOG_PI, SAC_EVAL_M_MU, SAC_EVAL_M_LOG_STD,
+       SAC_EVAL_M_TD1, SAC_EVAL_M_TD2, SAC_EVAL_M_POLICY, SAC_EVAL_MOMENTS_N };
+typedef struct { double count, sum, m2, sumsq, max, min; } sac_eval_moment_t;
+typedef struct { sac_eval_moment_t m[SAC_EVAL_MOMENTS_N]; double alpha, log_alpha; } sac_eval_stats_t;
+int sac_evaluate_stats_many(sac_trainer_t *const *trainers, int n_trainers, const int32_t *n_rows, sac_eval_io_t *io,
+                            sac_eval_stats_t *stats);
+int sac_evaluate_general_stats_many(sac_trainer_t *const *trainers, int n_trainers, const int32_t *n_rows, sac_eval_io_t *io,
+                                    sac_eval_stats_t *stats);
 
 /* ------------------------------------------------------------------------------------------
  * Trainer groups: several runs of one configuration (the reference's seed sweeps, /root/reference/launch_jobs.sh)

@@ -79,6 +79,21 @@ class SacEvalIO(C.Structure):
                                           "mu", "log_std", "a_new", "a_next")] + [("alpha", C.c_float)]
 
 
+# the moment records of sac_evaluate_stats_many (SAC_EVAL_M_*: sac_eval_stats_t.m, in this order)
+EVAL_MOMENTS = ["q1", "q2", "y", "log_pi", "mu", "log_std", "td1", "td2", "policy"]
+EVAL_MOMENT_FIELDS = ["count", "sum", "m2", "sumsq", "max", "min"]
+
+
+class SacEvalMoment(C.Structure):
+    """sac_eval_moment_t"""
+    _fields_ = [(k, C.c_double) for k in EVAL_MOMENT_FIELDS]
+
+
+class SacEvalStats(C.Structure):
+    """sac_eval_stats_t"""
+    _fields_ = [("m", SacEvalMoment * len(EVAL_MOMENTS)), ("alpha", C.c_double), ("log_alpha", C.c_double)]
+
+
 TD3_DIAG_NAMES = DIAG_NAMES[:16] + [f"Bellman Errors {i} {s}" for i in (1, 2) for s in ("Mean", "Std", "Max", "Min")] + [
     f"Policy Action {s}" for s in ("Mean", "Std", "Max", "Min")]
 
@@ -153,6 +168,8 @@ SYMBOLS = {
     "sac_evaluate_many": (C.c_int, [_P, C.c_int, _P, _P]),
     "sac_evaluate_general": (C.c_int, [_P, C.c_int64, _P]),
     "sac_evaluate_general_many": (C.c_int, [_P, C.c_int, _P, _P]),
+    "sac_evaluate_stats_many": (C.c_int, [_P, C.c_int, _P, _P, _P]),
+    "sac_evaluate_general_stats_many": (C.c_int, [_P, C.c_int, _P, _P, _P]),
     "sac_group_create": (C.c_int, [C.POINTER(_P), _P, C.c_int]),
     "td3_group_create": (C.c_int, [C.POINTER(_P), _P, C.c_int]),
     "sac_group_create_mixed": (C.c_int, [C.POINTER(_P), _P, C.c_int]),

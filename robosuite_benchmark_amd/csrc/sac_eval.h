@@ -163,27 +163,33 @@ size_t eval_lds_bytes(int KQ) {
 std::atomic<bool> g_eval_lds_raised[64];
 
 // the entropy coefficient of this moment for every member with rows (sac_get_scalars' scalars[5]; 1 with automatic
-// tuning off), behind the drain: what sac_evaluate_many and sac_evaluate_general_many both evaluate y with
-int eval_read_alpha(sac_trainer_t *const *trainers, int n_trainers, const int32_t *n_rows, float *alpha) {
+// tuning off), behind the drain: what sac_evaluate_many and sac_evaluate_general_many both evaluate y with.  log_alpha
+// (the *_stats_many entries; null otherwise): sac_get_scalars' scalars[0] from the same copy of Ctl, which is then made
+// with tuning off too.
+int eval_read_alpha(sac_trainer_t *const *trainers, int n_trainers, const int32_t *n_rows, float *alpha,
+                    float *log_alpha = nullptr) {
     for (int i = 0; i < n_trainers; ++i) {
         sac_trainer *t = trainers[i];
         if (n_rows[i] == 0) continue;
         alpha[i] = 1.0f;
-        if (t->cfg.use_automatic_entropy_tuning) {
+        if (t->cfg.use_automatic_entropy_tuning || log_alpha) {
             Ctl c;
             SAC_HIP(hipMemcpyAsync(&c, t->d_ctl, sizeof(c), hipMemcpyDeviceToHost, t->stream));
             SAC_HIP(hipStreamSynchronize(t->stream));
             // (a trainer that has neither stepped nor been given scalars holds log_alpha and no alpha yet: exp(log_alpha))
-            alpha[i] = c.alpha > 0.f ? c.alpha : expf(c.log_alpha);
+            if (t->cfg.use_automatic_entropy_tuning) alpha[i] = c.alpha > 0.f ? c.alpha : expf(c.log_alpha);
+            if (log_alpha) log_alpha[i] = c.log_alpha;
         }
     }
     return 0;
 }
 
-// an entry's own refusal for a member with rows: every input array and `rows` are there
-int eval_admit_io(const sac_eval_io_t &E, int i) {
-    SAC_REQUIRE(E.obs && E.act && E.rew && E.term && E.next_obs && E.eps && E.eps_next && E.rows,
-                "trainer %d: a null input array or null rows", i);
+// an entry's own refusal for a member with rows: every input array is there, and `rows` unless the entry returns
+// statistics (there a null `rows` means that no column is copied back)
+int eval_admit_io(const sac_eval_io_t &E, int i, bool need_rows) {
+    const bool inputs = E.obs && E.act && E.rew && E.term && E.next_obs && E.eps && E.eps_next;
+    if (need_rows) SAC_REQUIRE(inputs && E.rows, "trainer %d: a null input array or null rows", i);
+    SAC_REQUIRE(inputs, "trainer %d: a null input array", i);
     return 0;
 }
 
@@ -191,15 +197,15 @@ int eval_admit_io(const sac_eval_io_t &E, int i) {
 
 static_assert((int)EVAL_ROWS_N == (int)SAC_EVAL_ROWS_N && (int)EVAL_Y == (int)SAC_EVAL_Y, "k_eval's rows are sac_hip.h's");
 
-// (declared extern "C" in include/sac_hip.h)
-int sac_evaluate_many(sac_trainer_t *const *trainers, int n_trainers, const int32_t *n_rows, sac_eval_io_t *io) {
-    SAC_REQUIRE(trainers && n_rows && io, "bad arguments to sac_evaluate_many");
-    const InferEntry IE = {"sac_evaluate_many", false, true, "device evaluation",
-                           "sac_get_params and a forward on the host is the path", "evaluate"};
-    if (int rc = infer_admit(IE, trainers, n_trainers, n_rows, [&](int i) { return eval_admit_io(io[i], i); })) return rc;
+// sac_evaluate_many (stats null) and sac_evaluate_stats_many: with stats, mu and log_std always have their place in the
+// staging (k_eval_moments reads them there; only the copy to the caller depends on what was asked for), k_eval_moments
+// runs behind k_eval in front of the wait, and a null io[i].rows is taken
+static int evaluate_many(const InferEntry &IE, sac_trainer_t *const *trainers, int n_trainers, const int32_t *n_rows,
+                         sac_eval_io_t *io, sac_eval_stats_t *stats) {
+    if (int rc = infer_admit(IE, trainers, n_trainers, n_rows, [&](int i) { return eval_admit_io(io[i], i, !stats); })) return rc;
     sac_trainer *t0 = trainers[0];
-    float alpha[SAC_GROUP_MAX];
-    if (eval_read_alpha(trainers, n_trainers, n_rows, alpha)) return -1;
+    float alpha[SAC_GROUP_MAX], log_alpha[SAC_GROUP_MAX];
+    if (eval_read_alpha(trainers, n_trainers, n_rows, alpha, stats ? log_alpha : nullptr)) return -1;
 
     // per member: obs act rew term nobs eps eps_next | rows mu log_std a_new a_next
     enum { NPART = 12 };
@@ -209,9 +215,12 @@ int sac_evaluate_many(sac_trainer_t *const *trainers, int n_trainers, const int3
         const size_t n = (size_t)n_rows[i], nO = n * t->O, nA = n * t->A;
         const sac_eval_io_t &E = io[i];
         const size_t part[NPART] = {nO, nA, n, n, nO, nA, nA, n * SAC_EVAL_ROWS_N,
-                                    n && E.mu ? nA : 0, n && E.log_std ? nA : 0, n && E.a_new ? nA : 0, n && E.a_next ? nA : 0};
+                                    n && (E.mu || stats) ? nA : 0, n && (E.log_std || stats) ? nA : 0,
+                                    n && E.a_new ? nA : 0, n && E.a_next ? nA : 0};
         infer_carve(bytes, off[i], part, NPART);
     }
+    MomentsStage MS;
+    if (stats) moments_carve(bytes, MS, n_trainers);
     if (act_stage_reserve(t0, bytes)) return -1;
     const sac_trainer::ActStage &S = t0->act_stage;
     EvalMember *tab = reinterpret_cast<EvalMember *>(S.h);
@@ -229,9 +238,10 @@ int sac_evaluate_many(sac_trainer_t *const *trainers, int n_trainers, const int3
         };
         M.obs = in(0, E.obs, nO); M.act = in(1, E.act, nA); M.rew = in(2, E.rew, n); M.term = in(3, E.term, n);
         M.nobs = in(4, E.next_obs, nO); M.eps = in(5, E.eps, nA); M.eps_next = in(6, E.eps_next, nA);
-        auto out = [&](int k, const float *asked) { return asked ? reinterpret_cast<float *>(S.d + off[i][k]) : nullptr; };
-        M.rows = out(7, E.rows); M.mu = out(8, E.mu); M.log_std = out(9, E.log_std);
+        auto out = [&](int k, bool asked) { return asked ? reinterpret_cast<float *>(S.d + off[i][k]) : nullptr; };
+        M.rows = out(7, true); M.mu = out(8, E.mu || stats); M.log_std = out(9, E.log_std || stats);
         M.a_new = out(10, E.a_new); M.a_next = out(11, E.a_next);
+        if (stats) moments_member(S, MS, m - 1, i, M.rows, M.mu, M.log_std, n_rows[i], t->A);
         const Net &NP = t->net[SAC_NET_POLICY], &NQ = t->net[SAC_NET_QF1];
         for (int l = 0; l < 3; ++l) {
             M.pW[l] = NP.L[l].offW; M.pB[l] = NP.L[l].offB;
@@ -247,18 +257,36 @@ int sac_evaluate_many(sac_trainer_t *const *trainers, int n_trainers, const int3
     if (infer_raise_lds(reinterpret_cast<const void *>(k_eval), g_eval_lds_raised, t0->device, lds, eval_lds_bytes(512))) return -1;
     hipLaunchKernelGGL(k_eval, dim3(wgs), dim3(256), lds, t0->stream, reinterpret_cast<const EvalMember *>(S.d), m);
     SAC_HIP(hipGetLastError());
+    if (stats && moments_launch(t0, MS, m)) return -1;
     if (wait_trainer_stream(t0)) return -1;
     for (int i = 0; i < n_trainers; ++i) {
         if (n_rows[i] == 0) continue;
         sac_eval_io_t &E = io[i];
         const size_t n = (size_t)n_rows[i], nA = n * trainers[i]->A;
-        memcpy(E.rows, S.h + off[i][7], sizeof(float) * n * SAC_EVAL_ROWS_N);
+        if (E.rows) memcpy(E.rows, S.h + off[i][7], sizeof(float) * n * SAC_EVAL_ROWS_N);
         float *const dst[4] = {E.mu, E.log_std, E.a_new, E.a_next};
         for (int k = 0; k < 4; ++k)
             if (dst[k]) memcpy(dst[k], S.h + off[i][8 + k], sizeof(float) * nA);
         E.alpha = alpha[i];
+        if (stats) moments_read(S, MS, i, alpha[i], log_alpha[i], &stats[i]);
     }
     return 0;
+}
+
+// (declared extern "C" in include/sac_hip.h)
+int sac_evaluate_many(sac_trainer_t *const *trainers, int n_trainers, const int32_t *n_rows, sac_eval_io_t *io) {
+    SAC_REQUIRE(trainers && n_rows && io, "bad arguments to sac_evaluate_many");
+    const InferEntry IE = {"sac_evaluate_many", false, true, "device evaluation",
+                           "sac_get_params and a forward on the host is the path", "evaluate"};
+    return evaluate_many(IE, trainers, n_trainers, n_rows, io, nullptr);
+}
+
+int sac_evaluate_stats_many(sac_trainer_t *const *trainers, int n_trainers, const int32_t *n_rows, sac_eval_io_t *io,
+                            sac_eval_stats_t *stats) {
+    SAC_REQUIRE(trainers && n_rows && io && stats, "bad arguments to sac_evaluate_stats_many");
+    const InferEntry IE = {"sac_evaluate_stats_many", false, true, "device evaluation",
+                           "sac_evaluate_general_stats_many is the entry", "evaluate"};
+    return evaluate_many(IE, trainers, n_trainers, n_rows, io, stats);
 }
 
 int sac_evaluate(sac_trainer_t *t, int64_t n, sac_eval_io_t *io) {

@@ -115,15 +115,15 @@ __global__ __launch_bounds__(EG_YROWS) void k_eval_y(const EvalYMember *__restri
 
 }  // namespace sac
 
-// (declared extern "C" in include/sac_hip.h)
-int sac_evaluate_general_many(sac_trainer_t *const *trainers, int n_trainers, const int32_t *n_rows, sac_eval_io_t *io) {
-    SAC_REQUIRE(trainers && n_rows && io, "bad arguments to sac_evaluate_general_many");
-    const InferEntry IE = {"sac_evaluate_general_many", true, true, "device evaluation",
-                           "sac_evaluate is its device evaluation entry, sac_evaluate_general serves the general step", "evaluate"};
-    if (int rc = infer_admit(IE, trainers, n_trainers, n_rows, [&](int i) { return eval_admit_io(io[i], i); })) return rc;
+// sac_evaluate_general_many (stats null) and sac_evaluate_general_stats_many: with stats, mu and log_std always have
+// their place in the staging, k_eval_moments (sac_eval_moments.h) runs behind k_eval_y in front of the wait, and a null
+// io[i].rows is taken -- as evaluate_many (sac_eval.h) does for the fused shapes
+static int evaluate_general_many(const InferEntry &IE, sac_trainer_t *const *trainers, int n_trainers, const int32_t *n_rows,
+                                 sac_eval_io_t *io, sac_eval_stats_t *stats) {
+    if (int rc = infer_admit(IE, trainers, n_trainers, n_rows, [&](int i) { return eval_admit_io(io[i], i, !stats); })) return rc;
     sac_trainer *t0 = trainers[0];
-    float alpha[SAC_GROUP_MAX];
-    if (eval_read_alpha(trainers, n_trainers, n_rows, alpha)) return -1;
+    float alpha[SAC_GROUP_MAX], log_alpha[SAC_GROUP_MAX];
+    if (eval_read_alpha(trainers, n_trainers, n_rows, alpha, stats ? log_alpha : nullptr)) return -1;
 
     // the staging: the layer tables, k_eval_y's table, then per member
     //   obs act rew term nobs eps eps_next | rows a_new a_next (always: the critic launches read them) mu log_std
@@ -137,7 +137,7 @@ int sac_evaluate_general_many(sac_trainer_t *const *trainers, int n_trainers, co
         const size_t n = (size_t)n_rows[i], nO = n * t->O, nA = n * t->A;
         const sac_eval_io_t &E = io[i];
         const size_t part[NPART] = {nO, nA, n, n, nO, nA, nA, n * SAC_EVAL_ROWS_N, nA, nA,
-                                    n && E.mu ? nA : 0, n && E.log_std ? nA : 0};
+                                    n && (E.mu || stats) ? nA : 0, n && (E.log_std || stats) ? nA : 0};
         infer_carve(bytes, off[i], part, NPART);
         if (n == 0) continue;
         const GenNet &P = t->gen->net[SAC_NET_POLICY], &Q = t->gen->net[SAC_NET_QF1];      // (the four Q nets share their layout)
@@ -145,6 +145,8 @@ int sac_evaluate_general_many(sac_trainer_t *const *trainers, int n_trainers, co
         if (act_general_reserve(t, std::max(2 * slice_p[i], 6 * slice_q[i]))) return -1;
         LP = std::max(LP, P.nl); LQ = std::max(LQ, Q.nl);
     }
+    MomentsStage MS;
+    if (stats) moments_carve(bytes, MS, n_trainers);
     if (act_stage_reserve(t0, bytes)) return -1;
     const sac_trainer::ActStage &S = t0->act_stage;
     EvalLayerJob *tab = reinterpret_cast<EvalLayerJob *>(S.h);
@@ -184,8 +186,8 @@ int sac_evaluate_general_many(sac_trainer_t *const *trainers, int n_trainers, co
                     J.Y = dev(s ? P_A_NEXT : P_A_NEW);
                     J.eps = dev(s ? P_EPS_NEXT : P_EPS);
                     J.lp = rows + (size_t)(s ? EVAL_LOG_PI_NEXT : EVAL_LOG_PI) * n;
-                    J.mu = !s && E.mu ? dev(P_MU) : nullptr;
-                    J.ls = !s && E.log_std ? dev(P_LOG_STD) : nullptr;
+                    J.mu = !s && (E.mu || stats) ? dev(P_MU) : nullptr;
+                    J.ls = !s && (E.log_std || stats) ? dev(P_LOG_STD) : nullptr;
                 }
                 x = J.Y;
             }
@@ -207,6 +209,7 @@ int sac_evaluate_general_many(sac_trainer_t *const *trainers, int n_trainers, co
                 x = x2 = J.Y;
             }
         }
+        if (stats) moments_member(S, MS, m, i, rows, dev(P_MU), dev(P_LOG_STD), n, t->A);
         EvalYMember &M = ytab[m++];
         M.rew = dev(P_REW); M.term = dev(P_TERM); M.rows = rows;
         M.n = n; M.wg0 = yblocks;
@@ -222,18 +225,36 @@ int sac_evaluate_general_many(sac_trainer_t *const *trainers, int n_trainers, co
     hipLaunchKernelGGL(k_eval_y, dim3(yblocks), dim3(EG_YROWS), 0, t0->stream,
                        reinterpret_cast<const EvalYMember *>(S.d + tab_bytes), m);
     SAC_HIP(hipGetLastError());
+    if (stats && moments_launch(t0, MS, m)) return -1;
     if (wait_trainer_stream(t0)) return -1;
     for (int i = 0; i < n_trainers; ++i) {
         if (n_rows[i] == 0) continue;
         sac_eval_io_t &E = io[i];
         const size_t n = (size_t)n_rows[i], nA = n * trainers[i]->A;
-        memcpy(E.rows, S.h + off[i][P_ROWS], sizeof(float) * n * SAC_EVAL_ROWS_N);
+        if (E.rows) memcpy(E.rows, S.h + off[i][P_ROWS], sizeof(float) * n * SAC_EVAL_ROWS_N);
         float *const dst[4] = {E.a_new, E.a_next, E.mu, E.log_std};
         for (int k = 0; k < 4; ++k)
             if (dst[k]) memcpy(dst[k], S.h + off[i][P_A_NEW + k], sizeof(float) * nA);
         E.alpha = alpha[i];
+        if (stats) moments_read(S, MS, i, alpha[i], log_alpha[i], &stats[i]);
     }
     return 0;
+}
+
+// (declared extern "C" in include/sac_hip.h)
+int sac_evaluate_general_many(sac_trainer_t *const *trainers, int n_trainers, const int32_t *n_rows, sac_eval_io_t *io) {
+    SAC_REQUIRE(trainers && n_rows && io, "bad arguments to sac_evaluate_general_many");
+    const InferEntry IE = {"sac_evaluate_general_many", true, true, "device evaluation",
+                           "sac_evaluate is its device evaluation entry, sac_evaluate_general serves the general step", "evaluate"};
+    return evaluate_general_many(IE, trainers, n_trainers, n_rows, io, nullptr);
+}
+
+int sac_evaluate_general_stats_many(sac_trainer_t *const *trainers, int n_trainers, const int32_t *n_rows, sac_eval_io_t *io,
+                                    sac_eval_stats_t *stats) {
+    SAC_REQUIRE(trainers && n_rows && io && stats, "bad arguments to sac_evaluate_general_stats_many");
+    const InferEntry IE = {"sac_evaluate_general_stats_many", true, true, "device evaluation",
+                           "sac_evaluate_stats_many is its entry, sac_evaluate_general_stats_many serves the general step", "evaluate"};
+    return evaluate_general_many(IE, trainers, n_trainers, n_rows, io, stats);
 }
 
 int sac_evaluate_general(sac_trainer_t *t, int64_t n, sac_eval_io_t *io) {

@@ -25,7 +25,7 @@ from .replay_buffer import EnvReplayBuffer
 from .group import (ArchSACTrainerGroup, ArchTD3TrainerGroup, GroupActor, MixedSACTrainerGroup, MixedTD3TrainerGroup,
                     MlpSACTrainerGroup, MlpTD3TrainerGroup, SACTrainerGroup, TD3TrainerGroup, act_many,
                     _check_general, evaluate_many, q_values_many, runs_general_step)
-from .sac import SACTrainer, eval_statistics
+from .sac import SACTrainer, _check_stats, eval_statistics
 from .td3 import TD3Trainer
 from .variant import env_dims, validate
 
@@ -372,12 +372,14 @@ def _refuse_td3_validation(variant, what):
                            "variant has no such evaluation")
 
 
-def _group_validation(runs, epoch, eval_general="host"):
+def _group_validation(runs, epoch, eval_general="host", eval_stats="host"):
     """_validation_columns of every run's evaluation paths of this epoch, all runs from ONE evaluate_many call
-    (eval_general="device": the runs of the general step on the device too, evaluate_many's general)."""
+    (eval_general="device": the runs of the general step on the device too, evaluate_many's general; eval_stats="device":
+    the statistics of the runs evaluated on the device reduced there too, evaluate_many's stats)."""
     batches = [_validation_batch(r["evalc"].epoch_paths, r["trainer"].obs_dim, r["trainer"].act_dim) for r in runs]
     eps = [_validation_eps(r["seed"], epoch, b, r["trainer"].act_dim) for r, b in zip(runs, batches)]
-    stats = evaluate_many([r["trainer"] for r in runs], batches, eps=eps, **_q_general_kw(eval_general))
+    stats = evaluate_many([r["trainer"] for r in runs], batches, eps=eps, **_q_general_kw(eval_general),
+                          **_eval_stats_kw(eval_stats))
     return [_validation_columns(s, b) for s, b in zip(stats, batches)]
 
 
@@ -404,7 +406,7 @@ def _progress_row(buf, trainer, expl, evalc, ak):
 
 def experiment(variant, log_dir=None, seed=1, obs_dim=None, action_dim=None, num_epochs=None, device=0,
                fused_loop=True, quiet=False, checkpoint_dir=None, resume=False, acting="host", q_diagnostics=False,
-               q_general="host", validation=False, eval_general="host"):
+               q_general="host", validation=False, eval_general="host", eval_stats="host"):
     """variant.json -> training run.  Returns the list of progress rows (also written to
     <log_dir>/progress.csv when log_dir is given).
 
@@ -438,7 +440,11 @@ def experiment(variant, log_dir=None, seed=1, obs_dim=None, action_dim=None, num
     default), the row, every generator and every column are exactly what they were.  eval_general ("host", the default,
     or "device") is evaluate's `general`: where a run of the general step evaluates its objectives -- sac_get_params and
     a NumPy forward, or sac_evaluate_general (one k_eval_layer launch per layer on the live weights).  Without validation,
-    and for a run with the fused kernels' shapes, it has no effect."""
+    and for a run with the fused kernels' shapes, it has no effect.  eval_stats ("host", the default, or "device") is
+    evaluate's `stats`: where the statistics of a run that is evaluated on the device are reduced -- eval_statistics on
+    the columns copied out, or k_eval_moments on the device (the same columns of progress.csv, equal up to the rounding
+    of a float64 sum in another order).  Without validation it has no effect."""
+    _check_stats(eval_stats)
     check_acting(acting)
     _check_general(q_general)
     _check_general(eval_general)
@@ -502,7 +508,8 @@ def experiment(variant, log_dir=None, seed=1, obs_dim=None, action_dim=None, num
         if validation:
             vb = _validation_batch(evalc.epoch_paths, O, A)
             v_info = _validation_columns(None if vb is None else trainer.evaluate(vb, eps=_validation_eps(seed, epoch, vb, A),
-                                                                                  **_q_general_kw(eval_general)), vb)
+                                                                                  **_q_general_kw(eval_general),
+                                                                                  **_eval_stats_kw(eval_stats)), vb)
         t1 = time.time()
         new_paths = expl.collect_new_paths(ak["expl_max_path_length"], ak["num_expl_steps_per_train_loop"], False)
         t2 = time.time()
@@ -641,6 +648,11 @@ def _q_general_kw(q_general):
     return {} if q_general == "host" else {"general": q_general}
 
 
+def _eval_stats_kw(eval_stats):
+    """eval_stats as the `stats` keyword of evaluate / evaluate_many: left out at the default, as _q_general_kw does."""
+    return {} if eval_stats == "host" else {"stats": eval_stats}
+
+
 def _group_q_information(runs, q_general="host"):
     """q_bias_information of every run's evaluation paths of this epoch, qf1 and qf2 of all runs from ONE q_values_many
     call (one launch per 16 runs with the fused kernels' shapes and 1024 rows; q_general="device": the runs of the
@@ -654,7 +666,7 @@ def _group_q_information(runs, q_general="host"):
 
 def _group_epochs(runs, train_block, n_epochs, n_train, log_dir, quiet, what, ck=None, first_epoch=0, acting="host",
                   sessions=True, general_sessions=None, q_diagnostics=False, q_general="host", validation=False,
-                  eval_general="host"):
+                  eval_general="host", eval_stats="host"):
     """The epoch loop of a grouped experiment: each run collects its paths, then train_block() trains every run at once,
     then every run ends its epoch, the group is saved (with a GroupCheckpoint `ck`), and each run writes its row (to
     <log_dir>/<run["sub"]>/progress.csv with log_dir; appended to after a resume).
@@ -668,7 +680,8 @@ def _group_epochs(runs, train_block, n_epochs, n_train, log_dir, quiet, what, ck
     per epoch, behind the runs' evaluation paths and in front of the training block; its time is added to every run's
     time/evaluation sampling (s); q_general is q_values_many's `general` for that call.
     validation=True: as experiment()'s, ALL runs on their evaluation paths from one evaluate_many call per epoch, at the
-    same place and with the same accounting of its time; eval_general is evaluate_many's `general` for that call."""
+    same place and with the same accounting of its time; eval_general is evaluate_many's `general` for that call and
+    eval_stats its `stats`."""
     t_start = time.time()
     lockstep = acting != "host"
     lock_kw = dict(sessions=sessions, general="device" if acting == "device_all" else "host", general_sessions=general_sessions)
@@ -682,7 +695,7 @@ def _group_epochs(runs, train_block, n_epochs, n_train, log_dir, quiet, what, ck
                 lock_eval.collect_new_paths([(r["ak"]["eval_max_path_length"], r["ak"]["num_eval_steps_per_epoch"], True)
                                              for r in runs])
                 q_infos = _group_q_information(runs, q_general) if q_diagnostics else None
-                v_infos = _group_validation(runs, epoch, eval_general) if validation else None
+                v_infos = _group_validation(runs, epoch, eval_general, eval_stats) if validation else None
                 t1 = time.time()
                 new = lock_expl.collect_new_paths([(r["ak"]["expl_max_path_length"],
                                                     r["ak"]["num_expl_steps_per_train_loop"], False) for r in runs])
@@ -707,7 +720,7 @@ def _group_epochs(runs, train_block, n_epochs, n_train, log_dir, quiet, what, ck
                 times = [(a0, eval_s + q_s, expl_s, store_s) for a0, eval_s, expl_s, store_s in times]
             if validation and not lockstep:
                 s0 = time.time()
-                v_infos = _group_validation(runs, epoch, eval_general)
+                v_infos = _group_validation(runs, epoch, eval_general, eval_stats)
                 v_s = time.time() - s0
                 times = [(a0, eval_s + v_s, expl_s, store_s) for a0, eval_s, expl_s, store_s in times]
             t3 = time.time()
@@ -766,7 +779,7 @@ def _group_epochs(runs, train_block, n_epochs, n_train, log_dir, quiet, what, ck
 def experiment_group(variant, seeds, log_dir=None, num_epochs=None, obs_dim=None, action_dim=None, device=0,
                      quiet=False, checkpoint_dir=None, resume=False, chunk_rows=DEFAULT_CHUNK_ROWS, acting="host", sessions=True,
                      general_sessions=None, q_diagnostics=False, q_general="host", validation=False,
-                     eval_general="host"):
+                     eval_general="host", eval_stats="host"):
     """One configuration, several seeds, one process: each seed is the run ``experiment(variant, seed=s)`` would make --
     its own synthetic environments, collectors, weights and replay buffer -- and every epoch's training block is ONE
     SACTrainerGroup.train_loop (TD3 variants: TD3TrainerGroup; hidden sizes other than two layers of at most 256 units:
@@ -792,7 +805,9 @@ def experiment_group(variant, seeds, log_dir=None, num_epochs=None, obs_dim=None
     (general-step seeds: one sac_q_values_general_many call per 16 of them with "device").
     validation=True: experiment()'s validation/ columns for every seed, all seeds from one evaluate_many call per epoch;
     each seed's rows are those of experiment(variant, seed=s, validation=True).  A TD3 variant is refused.
-    eval_general as for experiment() (general-step seeds: one sac_evaluate_general_many call per 16 of them with "device")."""
+    eval_general as for experiment() (general-step seeds: one sac_evaluate_general_many call per 16 of them with "device"),
+    eval_stats too (the seeds evaluated on the device: their statistics from the same call, sac_evaluate_stats_many)."""
+    _check_stats(eval_stats)
     check_acting(acting)
     _check_general(q_general)
     _check_general(eval_general)
@@ -823,7 +838,7 @@ def experiment_group(variant, seeds, log_dir=None, num_epochs=None, obs_dim=None
         train_block = lambda: group.train_loop([r["buf"] for r in runs], n_train, batch_size=ak["batch_size"])  # noqa: E731
     _group_epochs(runs, train_block,
                   num_epochs if num_epochs is not None else ak["num_epochs"], n_train, log_dir, quiet, "seeds", ck,
-                  first_epoch, acting, sessions, general_sessions, q_diagnostics, q_general, validation, eval_general)
+                  first_epoch, acting, sessions, general_sessions, q_diagnostics, q_general, validation, eval_general, eval_stats)
     return {r["seed"]: r["rows"] for r in runs}
 
 
@@ -851,7 +866,7 @@ def sweep_label(variant, seed, hidden_sweep=False):
 def experiment_sweep(runs, log_dir=None, num_epochs=None, device=0, quiet=False, checkpoint_dir=None, resume=False,
                      chunk_rows=DEFAULT_CHUNK_ROWS, hidden_sweep=False, acting="host", sessions=True, general_sessions=None,
                      q_diagnostics=False, q_general="host", validation=False,
-                     eval_general="host"):
+                     eval_general="host", eval_stats="host"):
     """Several tasks x seeds, one process, one device: every entry of ``runs`` -- (variant, seed), or (variant, seed,
     obs_dim, action_dim) for a task without pinned dims -- is the run ``experiment(variant, seed=seed)`` would make, and
     every epoch's training block is ONE MixedSACTrainerGroup.train_loop (TD3 variants: MixedTD3TrainerGroup; hidden sizes
@@ -873,7 +888,8 @@ def experiment_sweep(runs, log_dir=None, num_epochs=None, device=0, quiet=False,
     with q_general="device" they are evaluated on the device, one sac_q_values_general_many call per 16 of them).
     validation as for experiment_group (the runs of the general step take evaluate's host path inside the same call;
     with eval_general="device" they are evaluated on the device, one sac_evaluate_general_many call per 16 of them); TD3
-    sweeps are refused."""
+    sweeps are refused.  eval_stats as for experiment_group."""
+    _check_stats(eval_stats)
     check_acting(acting)
     _check_general(q_general)
     _check_general(eval_general)
@@ -928,5 +944,5 @@ def experiment_sweep(runs, log_dir=None, num_epochs=None, device=0, quiet=False,
     batches = [r["ak"]["batch_size"] for r in group_runs]
     _group_epochs(group_runs, lambda: group.train_loop([r["buf"] for r in group_runs], n_train, batch_sizes=batches),
                   num_epochs if num_epochs is not None else ak0["num_epochs"], n_train, log_dir, quiet, "runs", ck,
-                  first_epoch, acting, sessions, general_sessions, q_diagnostics, q_general, validation, eval_general)
+                  first_epoch, acting, sessions, general_sessions, q_diagnostics, q_general, validation, eval_general, eval_stats)
     return [r["rows"] for r in group_runs]

@@ -17,7 +17,7 @@ import re
 import numpy as np
 
 from . import _lib
-from .sac import SACTrainer
+from .sac import SACTrainer, _check_stats, _eval_columns, _merge_all, _stats_moments, moments_statistics
 from .td3 import TD3Trainer
 
 MAX_MEMBERS = 16
@@ -157,7 +157,7 @@ def q_values_many(trainers, obs_list, act_list, nets_list, general="host"):
     return out
 
 
-def evaluate_many(trainers, batches, eps=None, rngs=None, rows=False, general="host"):
+def evaluate_many(trainers, batches, eps=None, rngs=None, rows=False, general="host", stats="host"):
     """SACTrainer.evaluate for many runs at once: result[i] = trainers[i].evaluate(batches[i], eps[i], rngs[i]) (eps / rngs:
     one entry per trainer or None; batches[i] None or without rows: the member sits out and gets None).  The SAC members
     with the fused kernels' shapes are served by ONE launch per 16 of them and 1024 rows (sac_evaluate_many: dims, hidden
@@ -166,8 +166,15 @@ def evaluate_many(trainers, batches, eps=None, rngs=None, rows=False, general="h
     are bit for bit those of its own evaluate.  Results come back in member order; rows=True as for evaluate.
     general="device": the SAC members of the general step are evaluated on the device as well, by ONE
     sac_evaluate_general_many call per 16 of them and 1024 rows; their results are bit for bit those of their own
-    evaluate(general="device")."""
+    evaluate(general="device").
+    stats="device" (evaluate's `stats`): the members served by those two entries get their statistics reduced on the device
+    in the same call (sac_evaluate_stats_many / sac_evaluate_general_stats_many: one k_eval_moments launch in front of the
+    call's wait) -- no eval_statistics and no sac_get_scalars for them, and with rows=False no column is copied back.  A
+    member's records are byte for byte those of its own evaluate(stats="device").  The members on the host path get
+    eval_statistics under either value."""
+    _check_stats(stats)
     _check_general(general)
+    on_device = stats == "device"
     trainers = list(trainers)
     R = len(trainers)
     eps = [None] * R if eps is None else list(eps)
@@ -177,6 +184,7 @@ def evaluate_many(trainers, batches, eps=None, rngs=None, rows=False, general="h
     if len({id(t) for t in trainers}) != R:
         raise RuntimeError("a trainer appears twice in evaluate_many")
     out, arrs, chunks, alphas, dev, gen = [None] * R, [None] * R, [None] * R, [1.0] * R, [], []
+    moments, log_alphas = [None] * R, [0.0] * R
     for i, t in enumerate(trainers):
         b = batches[i]
         if b is None or np.atleast_2d(b["observations"]).shape[0] == 0:
@@ -188,25 +196,32 @@ def evaluate_many(trainers, batches, eps=None, rngs=None, rows=False, general="h
         arrs[i], chunks[i] = t._eval_inputs(b, eps[i], rngs[i]), []
         (gen if general_step else dev).append(i)
     lib = _lib.load() if dev or gen else None
-    for members, entry in ((dev, "sac_evaluate_many"), (gen, "sac_evaluate_general_many")):
+    for members, entry in ((dev, "sac_evaluate_stats_many" if on_device else "sac_evaluate_many"),
+                           (gen, "sac_evaluate_general_stats_many" if on_device else "sac_evaluate_general_many")):
         for r0 in range(0, max([arrs[i][0].shape[0] for i in members], default=0), _lib.ACT_MAX_ROWS):
             live = [i for i in members if arrs[i][0].shape[0] > r0]
             for c in range(0, len(live), MAX_MEMBERS):
                 ids = live[c:c + MAX_MEMBERS]
                 n = len(ids)
                 n_rows = [min(arrs[i][0].shape[0] - r0, _lib.ACT_MAX_ROWS) for i in ids]
-                made = [trainers[i]._eval_io(arrs[i], r0, r0 + k) for i, k in zip(ids, n_rows)]
+                made = [trainers[i]._eval_io(arrs[i], r0, r0 + k, outputs=rows or not on_device) for i, k in zip(ids, n_rows)]
                 ios = (_lib.SacEvalIO * n)(*[m[0] for m in made])
+                sts = (_lib.SacEvalStats * n)() if on_device else None
                 _lib.check(getattr(lib, entry)((C.c_void_p * n)(*[trainers[i]._h.value for i in ids]), n,
-                                               (C.c_int32 * n)(*n_rows), ios), entry)
+                                               (C.c_int32 * n)(*n_rows), ios, *([sts] if on_device else [])), entry)
                 for k, i in enumerate(ids):
                     chunks[i].append(made[k][1])
                     alphas[i] = float(ios[k].alpha)
-    from .sac import _eval_columns
+                    if on_device:
+                        moments[i], log_alphas[i] = _merge_all(moments[i], _stats_moments(sts[k])), sts[k].log_alpha
     for i in dev + gen:
-        cols = _eval_columns(chunks[i], alphas[i])
-        stats = trainers[i]._eval_stats(cols)
-        out[i] = (stats, cols) if rows else stats
+        t = trainers[i]
+        cols = _eval_columns(chunks[i], alphas[i]) if rows or not on_device else None
+        if on_device:
+            result = moments_statistics(moments[i], alphas[i], log_alphas[i], t.target_entropy, t.use_automatic_entropy_tuning)
+        else:
+            result = t._eval_stats(cols)
+        out[i] = (result, cols) if rows else result
     return out
 
 
@@ -433,9 +448,9 @@ class _Members:
             nets_list = [("qf1", "qf2")] * len(self.trainers)
         return q_values_many(self.trainers, obs_list, act_list, nets_list, general=general)
 
-    def evaluate_many(self, batches, eps=None, rngs=None, rows=False, general="host"):
-        """evaluate_many over the group's members (general as there)."""
-        return evaluate_many(self.trainers, batches, eps=eps, rngs=rngs, rows=rows, general=general)
+    def evaluate_many(self, batches, eps=None, rngs=None, rows=False, general="host", stats="host"):
+        """evaluate_many over the group's members (general and stats as there)."""
+        return evaluate_many(self.trainers, batches, eps=eps, rngs=rngs, rows=rows, general=general, stats=stats)
 
 
 class _SACMembers:

@@ -69,6 +69,84 @@ def eval_statistics(rows, mu, log_std, alpha, log_alpha, target_entropy, auto):
     return d
 
 
+STATS = ("host", "device")      # where evaluate's statistics are reduced: eval_statistics, or k_eval_moments on the device
+
+
+def _check_stats(stats):
+    if stats not in STATS:
+        raise RuntimeError(f"stats must be one of {STATS}, got {stats!r}")
+    return stats
+
+
+def eval_moments(rows, mu, log_std):
+    """k_eval_moments (csrc/sac_eval_moments.h) restated in NumPy float64 -- the reference of its tests and nothing else:
+    an OrderedDict with one record {count, sum, m2, sumsq, max, min} per name of _lib.EVAL_MOMENTS, over q1, q2, y, log_pi
+    (n elements), mu, log_std (n A), td1 = q1 - y, td2 = q2 - y and policy = log_pi - min(q1_new, q2_new) (n), every
+    element formed in float64 from the columns given.  m2 = sum((x - sum / count)^2), a second pass as np.std's; max and
+    min keep a NaN."""
+    r = [np.asarray(x, np.float64).ravel() for x in rows]
+    q1, q2, q1n, q2n, _, _, lp, _, y = r
+    flat = lambda x: np.asarray(x, np.float64).ravel()               # noqa: E731
+    xs = [q1, q2, y, lp, flat(mu), flat(log_std), q1 - y, q2 - y, lp - np.minimum(q1n, q2n)]
+    out = OrderedDict()
+    with np.errstate(all="ignore"):
+        for name, x in zip(_lib.EVAL_MOMENTS, xs):
+            s = float(np.sum(x))
+            out[name] = dict(count=float(x.size), sum=s, m2=float(np.sum((x - s / x.size) ** 2)), sumsq=float(np.sum(x * x)),
+                             max=float(np.max(x)), min=float(np.min(x)))
+    return out
+
+
+def merge_moments(a, b):
+    """The record of two disjoint sets of elements of one quantity from their records a and b (a call above 1024 rows
+    runs as several launches): count, sum and sumsq add, max and min combine (a NaN stays), and
+    m2 = m2_a + m2_b + delta^2 n_a n_b / (n_a + n_b) with delta the difference of the two means."""
+    na, nb = a["count"], b["count"]
+    n = na + nb
+    delta = b["sum"] / nb - a["sum"] / na
+    return dict(count=n, sum=a["sum"] + b["sum"], m2=a["m2"] + b["m2"] + delta * delta * (na * nb / n),
+                sumsq=a["sumsq"] + b["sumsq"], max=float(np.maximum(a["max"], b["max"])),
+                min=float(np.minimum(a["min"], b["min"])))
+
+
+def _merge_all(a, b):
+    """merge_moments per quantity; a None: b."""
+    return b if a is None else OrderedDict((k, merge_moments(a[k], b[k])) for k in a)
+
+
+def _stats_moments(st):
+    """The records of one sac_eval_stats_t as eval_moments returns them."""
+    vals = np.frombuffer(st, np.float64, len(_lib.EVAL_MOMENTS) * len(_lib.EVAL_MOMENT_FIELDS)).tolist()
+    k = len(_lib.EVAL_MOMENT_FIELDS)
+    return OrderedDict((name, dict(zip(_lib.EVAL_MOMENT_FIELDS, vals[i * k:(i + 1) * k])))
+                       for i, name in enumerate(_lib.EVAL_MOMENTS))
+
+
+def moments_statistics(moments, alpha, log_alpha, target_entropy, auto):
+    """eval_statistics' OrderedDict -- the same keys in the same order -- from the moment records of eval_moments or of
+    the device (sac_evaluate_stats_many): Mean = sum / count, Std = sqrt(m2 / count), Max and Min as stored, QF Loss =
+    td.sumsq / count, Policy Loss = policy.sum / count, Alpha Loss = -(log_alpha (log_pi.sum / count + target_entropy)),
+    0 with tuning off."""
+    def stats(d, name, m):
+        d[name + " Mean"], d[name + " Std"] = m["sum"] / m["count"], float(np.sqrt(m["m2"] / m["count"]))
+        d[name + " Max"], d[name + " Min"] = m["max"], m["min"]
+
+    M = moments
+    d = OrderedDict()
+    with np.errstate(all="ignore"):
+        d["QF1 Loss"] = M["td1"]["sumsq"] / M["td1"]["count"]
+        d["QF2 Loss"] = M["td2"]["sumsq"] / M["td2"]["count"]
+        d["Policy Loss"] = M["policy"]["sum"] / M["policy"]["count"]
+        for name, key in (("Q1 Predictions", "q1"), ("Q2 Predictions", "q2"), ("Q Targets", "y"), ("Log Pis", "log_pi"),
+                          ("Policy mu", "mu"), ("Policy log std", "log_std")):
+            stats(d, name, M[key])
+        d["Alpha"] = float(alpha)
+        d["Alpha Loss"] = -(float(log_alpha) * (M["log_pi"]["sum"] / M["log_pi"]["count"] + float(target_entropy))) if auto else 0.0
+        stats(d, "TD Error 1", M["td1"])
+        stats(d, "TD Error 2", M["td2"])
+    return d
+
+
 class SACTrainer:
     def __init__(self, env=None, policy=None, qf1=None, qf2=None, target_qf1=None, target_qf2=None,
                  discount=0.99, reward_scale=1.0, policy_lr=1e-3, qf_lr=1e-3, optimizer_class=None,
@@ -440,12 +518,15 @@ class SACTrainer:
             raise ValueError(f"evaluate: eps {e1.shape} / eps_next {e2.shape} for actions {act.shape}")
         return obs, act, rew, term, nobs, e1, e2
 
-    def _eval_io(self, arrs, i, j):
-        """sac_eval_io_t over rows i..j of evaluate's inputs, and the output arrays it points to."""
+    def _eval_io(self, arrs, i, j, outputs=True):
+        """sac_eval_io_t over rows i..j of evaluate's inputs, and the output arrays it points to.  outputs=False (the
+        *_stats_many entries alone take it): no output array is made, `rows` and the optional arrays are NULL."""
         k, A = j - i, self.act_dim
+        parts = [np.ascontiguousarray(a[i:j]) for a in arrs]
+        if not outputs:
+            return _lib.SacEvalIO(*[p.ctypes.data for p in parts], *([None] * (1 + len(_lib.EVAL_ARRAYS))), 0.0), None, parts
         out = dict(rows=np.empty((len(_lib.EVAL_ROWS), k), np.float32))
         out.update((name, np.empty((k, A), np.float32)) for name in _lib.EVAL_ARRAYS)
-        parts = [np.ascontiguousarray(a[i:j]) for a in arrs]
         io = _lib.SacEvalIO(*[p.ctypes.data for p in parts], out["rows"].ctypes.data,
                             *[out[name].ctypes.data for name in _lib.EVAL_ARRAYS], 0.0)
         return io, out, parts
@@ -461,6 +542,24 @@ class SACTrainer:
             chunks.append(out)
             alpha = float(io.alpha)
         return _eval_columns(chunks, alpha)
+
+    def _evaluate_device_stats(self, arrs, entry, rows):
+        """evaluate(stats="device") of a member of the device path: one `entry` call (sac_evaluate_stats_many or
+        sac_evaluate_general_stats_many, this trainer alone) per 1024 rows, the chunks' records merged by merge_moments.
+        No eval_statistics, no sac_get_scalars.  (statistics, columns -- None unless rows)."""
+        n = arrs[0].shape[0]
+        chunks, moments, st = [], None, _lib.SacEvalStats()
+        fn = getattr(self._lib, entry)
+        handle, one = (C.c_void_p * 1)(self._h.value), (C.c_int32 * 1)()
+        for i in range(0, n, _lib.ACT_MAX_ROWS):
+            j = min(n, i + _lib.ACT_MAX_ROWS)
+            io, out, _keep = self._eval_io(arrs, i, j, outputs=rows)
+            one[0] = j - i
+            _lib.check(fn(handle, 1, one, C.byref(io), C.byref(st)), entry)
+            chunks.append(out)
+            moments = _merge_all(moments, _stats_moments(st))
+        stats = moments_statistics(moments, st.alpha, st.log_alpha, self.target_entropy, self.use_automatic_entropy_tuning)
+        return stats, (_eval_columns(chunks, st.alpha) if rows else None)
 
     def _host_net(self, name):
         """[(W, b)] of one net from the current weights: sac_get_params, or the holder's arrays without a handle."""
@@ -540,7 +639,7 @@ class SACTrainer:
         return eval_statistics(np.stack([cols[k] for k in _lib.EVAL_ROWS]), cols["mu"], cols["log_std"], cols["alpha"],
                                self._eval_log_alpha(), self.target_entropy, self.use_automatic_entropy_tuning)
 
-    def evaluate(self, batch, eps=None, rng=None, rows=False, general="host"):
+    def evaluate(self, batch, eps=None, rng=None, rows=False, general="host", stats="host"):
         """The SAC objectives of this run on `batch` WITHOUT a gradient step: `batch` is the dict train() takes
         (observations, actions, rewards, terminals, next_observations; any n >= 1), typically transitions the run has not
         trained on -- an epoch's evaluation paths.  From the LIVE weights and the CURRENT entropy coefficient: on the
@@ -558,13 +657,25 @@ class SACTrainer:
         general (one of group.GENERAL) decides for a trainer of the general step only: "host", the default, keeps the host
         path; "device" evaluates on the device as well (sac_evaluate_general: k_eval_layer, one launch per layer on the
         live weights, in calls of at most 1024 rows, no parameter copy).  A trainer with the fused kernels' shapes takes
-        sac_evaluate and a trainer without a handle the host path under either value."""
+        sac_evaluate and a trainer without a handle the host path under either value.
+        stats (one of sac.STATS) decides where the statistics of a trainer that is evaluated on the device are reduced:
+        "host", the default, copies the columns out and runs eval_statistics; "device" reduces them on the device as well
+        (sac_evaluate_stats_many / sac_evaluate_general_stats_many: k_eval_moments behind the evaluation's kernels, in
+        front of the same wait) and builds the same keys from the moment records (moments_statistics) -- no
+        eval_statistics, no sac_get_scalars, and with rows=False no column leaves the staging.  The values agree with
+        "host" up to the rounding of a float64 sum in another order; Max, Min and Alpha are equal.  A trainer on the host
+        path gets eval_statistics under either value."""
+        _check_stats(stats)
         from .group import _check_general
         _check_general(general)
         arrs = self._eval_inputs(batch, eps, rng)
         gen = self._h is not None and self.fused_mode() == 3
         if self._h is None or (gen and general != "device") or self._evaluate_on_host:
             cols = self._evaluate_host(arrs)
+        elif stats == "device":
+            result, cols = self._evaluate_device_stats(
+                arrs, "sac_evaluate_general_stats_many" if gen else "sac_evaluate_stats_many", rows)
+            return (result, cols) if rows else result
         else:
             cols = self._evaluate_device(arrs, "sac_evaluate_general" if gen else "sac_evaluate")
         stats = self._eval_stats(cols)

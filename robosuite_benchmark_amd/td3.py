@@ -65,7 +65,7 @@ class TD3Trainer(SACTrainer):
                 if name != "Actor Loss":
                     self.eval_statistics[name] = float(diag[i])
 
-    def evaluate(self, batch, eps=None, rng=None, rows=False, general="host"):
+    def evaluate(self, batch, eps=None, rng=None, rows=False, general="host", stats="host"):
         raise NotImplementedError("TD3Trainer.evaluate: evaluate computes the SAC objective (entropy-regularised targets of "
                                   "a tanh-Gaussian policy); TD3's objective -- a deterministic policy with target "
                                   "smoothing -- is not implemented")

@@ -17,7 +17,8 @@
  --q_general device: with --q_diagnostics, runs of any hidden sizes evaluate their critics on the device too.
  --validation: every epoch, the SAC losses, TD errors and targets on the evaluation paths' transitions -- held-out data
  -- from the live weights: validation/ columns in progress.csv; SAC only.
- --eval_general device: with --validation, runs of any hidden sizes evaluate these objectives on the device too.)
+ --eval_general device: with --validation, runs of any hidden sizes evaluate these objectives on the device too.
+ --eval_stats device: with --validation, the statistics of the runs evaluated on the device are reduced there as well.)
 Runs the variant unchanged (batch size, lrs, tau, period, buffer size ... from the JSON) on the
 HIP library with a synthetic environment of the task's dimensions (robosuite is not installed)."""
 import argparse
@@ -79,8 +80,15 @@ if __name__ == "__main__":
                     help="with --validation: where runs whose hidden sizes are beyond two layers of at most 256 units "
                          "evaluate the SAC objectives -- host (a parameter copy and a NumPy forward) or device (one HIP "
                          "launch per layer on the live weights); without --validation it has no effect")
+    ap.add_argument("--eval_stats", type=str, default="host", choices=["host", "device"],
+                    help="with --validation: where the statistics (means, deviations, extremes, losses) of the runs that are "
+                         "evaluated on the device are reduced -- host (the columns are copied out and reduced in NumPy) or "
+                         "device (one more HIP launch in front of the call's wait); the same validation/ columns either "
+                         "way; without --validation it has no effect")
     args = ap.parse_args()
     eval_kw = {} if args.eval_general == "host" else dict(eval_general=args.eval_general)
+    if args.eval_stats != "host":
+        eval_kw["eval_stats"] = args.eval_stats
     if (args.hidden_sweep or args.hidden_sizes) and not args.variants:
         raise SystemExit("--hidden_sweep / --hidden_sizes need --variants")
     if args.variants or args.seeds:
