@@ -24,8 +24,9 @@ from .networks import (FlattenMlp, GaussianStrategy, MakeDeterministic, PolicyWr
 from .replay_buffer import EnvReplayBuffer
 from .group import (ArchSACTrainerGroup, ArchTD3TrainerGroup, GroupActor, MixedSACTrainerGroup, MixedTD3TrainerGroup,
                     MlpSACTrainerGroup, MlpTD3TrainerGroup, SACTrainerGroup, TD3TrainerGroup, act_many,
-                    _check_general, evaluate_many, q_values_many, runs_general_step)
-from .sac import SACTrainer, _check_stats, eval_statistics
+                    evaluate_many, q_values_many, runs_general_step)
+from .infer import check_general, check_stats
+from .sac import SACTrainer, eval_statistics
 from .td3 import TD3Trainer
 from .variant import env_dims, validate
 
@@ -142,7 +143,7 @@ def holder_actions(holders, obs_list, deterministic_list, act_many=act_many, gen
     if ids:
         got = act_many([holders[i]._trainer for i in ids], [np.asarray(obs_list[i])[None] for i in ids],
                        [deterministic_list[i] for i in ids], [eps[i] for i in ids],
-                       **({} if general == "host" else dict(general=general)))
+                       **_q_general_kw(general))
         for i, a in zip(ids, got):
             acts[i] = a[0, :]
     for i, h in enumerate(holders):
@@ -175,7 +176,7 @@ class GroupPathCollector:
 
     def __init__(self, collectors, act_many=act_many, sessions=False, actor=GroupActor, general="host", general_sessions=None):
         self.collectors, self._act_many = list(collectors), act_many
-        self._general = dict(general=general) if general != "host" else {}
+        self._general = _q_general_kw(general)
         self._actor_kw = dict(self._general)
         if general == "device" and general_sessions is not None:
             self._actor_kw["general_sessions"] = bool(general_sessions)
@@ -444,10 +445,10 @@ def experiment(variant, log_dir=None, seed=1, obs_dim=None, action_dim=None, num
     evaluate's `stats`: where the statistics of a run that is evaluated on the device are reduced -- eval_statistics on
     the columns copied out, or k_eval_moments on the device (the same columns of progress.csv, equal up to the rounding
     of a float64 sum in another order).  Without validation it has no effect."""
-    _check_stats(eval_stats)
+    check_stats(eval_stats)
     check_acting(acting)
-    _check_general(q_general)
-    _check_general(eval_general)
+    check_general(q_general)
+    check_general(eval_general)
     validate(variant)
     if validation:
         _refuse_td3_validation(variant, "experiment")
@@ -807,10 +808,10 @@ def experiment_group(variant, seeds, log_dir=None, num_epochs=None, obs_dim=None
     each seed's rows are those of experiment(variant, seed=s, validation=True).  A TD3 variant is refused.
     eval_general as for experiment() (general-step seeds: one sac_evaluate_general_many call per 16 of them with "device"),
     eval_stats too (the seeds evaluated on the device: their statistics from the same call, sac_evaluate_stats_many)."""
-    _check_stats(eval_stats)
+    check_stats(eval_stats)
     check_acting(acting)
-    _check_general(q_general)
-    _check_general(eval_general)
+    check_general(q_general)
+    check_general(eval_general)
     if validation:
         _refuse_td3_validation(variant, "experiment_group")
     if resume and not checkpoint_dir:
@@ -889,10 +890,10 @@ def experiment_sweep(runs, log_dir=None, num_epochs=None, device=0, quiet=False,
     validation as for experiment_group (the runs of the general step take evaluate's host path inside the same call;
     with eval_general="device" they are evaluated on the device, one sac_evaluate_general_many call per 16 of them); TD3
     sweeps are refused.  eval_stats as for experiment_group."""
-    _check_stats(eval_stats)
+    check_stats(eval_stats)
     check_acting(acting)
-    _check_general(q_general)
-    _check_general(eval_general)
+    check_general(q_general)
+    check_general(eval_general)
     for spec in runs if validation else ():
         _refuse_td3_validation(tuple(spec)[0], "experiment_sweep")
     if resume and not checkpoint_dir:

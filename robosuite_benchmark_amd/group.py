@@ -17,393 +17,11 @@ import re
 import numpy as np
 
 from . import _lib
-from .sac import SACTrainer, _check_stats, _eval_columns, _merge_all, _stats_moments, moments_statistics
+# (the inference names live in infer.py; they stay importable from here)
+from .infer import (GENERAL, GENERAL_SESSIONS, MAX_MEMBERS, GroupActor, act_many, check_general,  # noqa: F401
+                    evaluate_many, general_shape, q_values_many, runs_general_step)
+from .sac import SACTrainer
 from .td3 import TD3Trainer
-
-MAX_MEMBERS = 16
-
-
-def _general_shape(hs):
-    return len(hs) != 2 or max(hs) > 256
-
-
-def runs_general_step(t):
-    """Does trainer t run the general step (hidden sizes other than two layers of at most 256 units)?  Such runs group in
-    MlpSACTrainerGroup / MlpTD3TrainerGroup, the others in the remaining kinds."""
-    return _general_shape(t._hidden("policy")) or _general_shape(t._hidden("qf1"))
-
-
-GENERAL = ("host", "device")
-GENERAL_SESSIONS = True         # GroupActor(general="device")'s default for general_sessions: switched on by the
-                                # measurement of DESIGN.md, section 6d (the actions are the same bits either way)
-
-
-def _check_general(general):
-    if general not in GENERAL:
-        raise RuntimeError(f"general must be one of {GENERAL}, got {general!r}")
-    return general
-
-
-def _act_general_many(lib, trainers, ids, n_rows, obs, det, eps, out):
-    """ONE sac_policy_act_general_many call per 16 of the general-step members `ids`: obs / eps / out hold a float32 array
-    (or None) per trainer, n_rows and det one value per trainer."""
-    for c in range(0, len(ids), MAX_MEMBERS):
-        part = ids[c:c + MAX_MEMBERS]
-        n = len(part)
-        vp = lambda arrs: (C.c_void_p * n)(*[None if a is None else a.ctypes.data for a in arrs])  # noqa: E731
-        _lib.check(lib.sac_policy_act_general_many((C.c_void_p * n)(*[trainers[i]._h.value for i in part]), n,
-                                                   (C.c_int32 * n)(*[n_rows[i] for i in part]), vp([obs[i] for i in part]),
-                                                   (C.c_int32 * n)(*[int(bool(det[i])) for i in part]),
-                                                   vp([eps[i] for i in part]), vp([out[i] for i in part])),
-                   "sac_policy_act_general_many")
-
-
-def act_many(trainers, obs_list, deterministic_list, eps_list, general="host"):
-    """policy.get_actions for many runs at once: actions[i] = trainers[i]'s policy on obs_list[i] ((n_i, O_i); None or no
-    rows: the member sits out and gets an empty array), deterministic_list[i] as MakeDeterministic, eps_list[i] the
-    (n_i, A_i) N(0,1) draws of a stochastic SAC member (None otherwise).  The members with the fused kernels' shapes act
-    in ONE launch per 16 of them (sac_policy_act_many: SAC and TD3, dims and row counts mixed; up to 1024 rows each);
-    members of the general step act on the host through their own policy_act.  A member's actions never depend on its
-    neighbours: they are bit for bit those of its own policy_act_device (policy_act for the general step).
-    general="device": the members of the general step act on the device as well, in ONE sac_policy_act_general_many call
-    per 16 of them; their actions are bit for bit those of their own policy_act_general."""
-    _check_general(general)
-    trainers = list(trainers)
-    R = len(trainers)
-    if not (len(obs_list) == len(deterministic_list) == len(eps_list) == R):
-        raise RuntimeError("act_many takes one observation array, deterministic flag and eps per trainer")
-    if len({id(t) for t in trainers}) != R:
-        raise RuntimeError("a trainer appears twice in act_many")
-    obs = [None if o is None else _lib.f32(np.atleast_2d(o)) for o in obs_list]
-    eps = [None if e is None else _lib.f32(np.atleast_2d(e)) for e in eps_list]
-    out = [np.empty((0 if o is None else o.shape[0], t.act_dim), np.float32) for t, o in zip(trainers, obs)]
-    dev, gen = [], []
-    for i, t in enumerate(trainers):
-        if out[i].shape[0] == 0:
-            continue
-        if obs[i].shape[1] != t.obs_dim or (eps[i] is not None and eps[i].shape != out[i].shape):
-            raise RuntimeError(f"act_many member {i}: observations {obs[i].shape} / eps "
-                               f"{None if eps[i] is None else eps[i].shape} do not fit dims ({t.obs_dim}, {t.act_dim})")
-        if out[i].shape[0] > _lib.ACT_MAX_ROWS:
-            raise RuntimeError(f"act_many member {i}: {out[i].shape[0]} rows (at most {_lib.ACT_MAX_ROWS} per call)")
-        if not runs_general_step(t):
-            dev.append(i)
-        elif general == "device":
-            gen.append(i)
-        else:
-            out[i] = t.policy_act(obs[i], deterministic_list[i], eps[i])
-    lib = _lib.load()
-    _act_general_many(lib, trainers, gen, [o.shape[0] for o in out], obs, deterministic_list, eps, out)
-    for c in range(0, len(dev), MAX_MEMBERS):
-        ids = dev[c:c + MAX_MEMBERS]
-        n = len(ids)
-        vp = lambda arrs: (C.c_void_p * n)(*[None if a is None else a.ctypes.data for a in arrs])  # noqa: E731
-        _lib.check(lib.sac_policy_act_many((C.c_void_p * n)(*[trainers[i]._h.value for i in ids]), n,
-                                           (C.c_int32 * n)(*[out[i].shape[0] for i in ids]), vp([obs[i] for i in ids]),
-                                           (C.c_int32 * n)(*[int(bool(deterministic_list[i])) for i in ids]),
-                                           vp([eps[i] for i in ids]), vp([out[i] for i in ids])), "sac_policy_act_many")
-    return out
-
-
-def q_values_many(trainers, obs_list, act_list, nets_list, general="host"):
-    """SACTrainer.q_values for many runs at once: q[i] = trainers[i]'s critics nets_list[i] (names, as q_values takes
-    them) on obs_list[i] / act_list[i] ((n_i, O_i) / (n_i, A_i); None or no rows: the member sits out and gets an empty
-    (len(nets), 0) array).  The members with the fused kernels' shapes are served by ONE launch per 16 of them and 1024
-    rows (sac_q_values_many: SAC and TD3, dims, row counts and nets mixed); members of the general step take q_values'
-    host path inside the same call.  A member's values never depend on its neighbours: they are bit for bit those of its
-    own q_values.
-    general="device": the members of the general step are evaluated on the device as well, by ONE
-    sac_q_values_general_many call per 16 of them and 1024 rows; their values are bit for bit those of their own
-    q_values(general="device")."""
-    _check_general(general)
-    trainers = list(trainers)
-    R = len(trainers)
-    if not (len(obs_list) == len(act_list) == len(nets_list) == R):
-        raise RuntimeError("q_values_many takes one observation array, action array and net selection per trainer")
-    if len({id(t) for t in trainers}) != R:
-        raise RuntimeError("a trainer appears twice in q_values_many")
-    obs, act, rows, names, masks, out = [None] * R, [None] * R, [None] * R, [None] * R, [0] * R, [None] * R
-    dev, gen = [], []
-    for i, t in enumerate(trainers):
-        names[i] = [nets_list[i]] if isinstance(nets_list[i], str) else list(nets_list[i])
-        masks[i], rows[i] = _lib.q_net_mask(names[i])
-        if obs_list[i] is None or np.atleast_2d(obs_list[i]).shape[0] == 0:
-            out[i] = np.empty((len(names[i]), 0), np.float32)
-            continue
-        obs[i], act[i], _, _ = t._q_inputs(obs_list[i], act_list[i], names[i])
-        general_step = t._h is not None and runs_general_step(t)
-        if t._h is None or (general_step and general != "device"):
-            out[i] = t._q_values_host(obs[i], act[i], names[i])
-        else:
-            out[i] = np.empty((len(names[i]), obs[i].shape[0]), np.float32)
-            (gen if general_step else dev).append(i)
-    lib = _lib.load() if dev or gen else None
-    for members, entry in ((dev, "sac_q_values_many"), (gen, "sac_q_values_general_many")):
-        for r0 in range(0, max([obs[i].shape[0] for i in members], default=0), _lib.ACT_MAX_ROWS):
-            live = [i for i in members if obs[i].shape[0] > r0]
-            for c in range(0, len(live), MAX_MEMBERS):
-                ids = live[c:c + MAX_MEMBERS]
-                n = len(ids)
-                n_rows = [min(obs[i].shape[0] - r0, _lib.ACT_MAX_ROWS) for i in ids]
-                o = [obs[i][r0:r0 + k] for i, k in zip(ids, n_rows)]
-                a = [act[i][r0:r0 + k] for i, k in zip(ids, n_rows)]
-                q = [np.empty((len(names[i]), k), np.float32) for i, k in zip(ids, n_rows)]
-                vp = lambda arrs: (C.c_void_p * n)(*[x.ctypes.data for x in arrs])  # noqa: E731
-                _lib.check(getattr(lib, entry)((C.c_void_p * n)(*[trainers[i]._h.value for i in ids]), n,
-                                               (C.c_int32 * n)(*n_rows), vp(o), vp(a),
-                                               (C.c_uint32 * n)(*[masks[i] for i in ids]), vp(q)), entry)
-                for i, k, part in zip(ids, n_rows, q):
-                    out[i][:, r0:r0 + k] = part[rows[i]]
-    return out
-
-
-def evaluate_many(trainers, batches, eps=None, rngs=None, rows=False, general="host", stats="host"):
-    """SACTrainer.evaluate for many runs at once: result[i] = trainers[i].evaluate(batches[i], eps[i], rngs[i]) (eps / rngs:
-    one entry per trainer or None; batches[i] None or without rows: the member sits out and gets None).  The SAC members
-    with the fused kernels' shapes are served by ONE launch per 16 of them and 1024 rows (sac_evaluate_many: dims, hidden
-    sizes and row counts mixed); the others -- the general step, trainers without a handle -- go through their own
-    evaluate inside the same call (a TD3 member raises there).  A member's columns never depend on its neighbours: they
-    are bit for bit those of its own evaluate.  Results come back in member order; rows=True as for evaluate.
-    general="device": the SAC members of the general step are evaluated on the device as well, by ONE
-    sac_evaluate_general_many call per 16 of them and 1024 rows; their results are bit for bit those of their own
-    evaluate(general="device").
-    stats="device" (evaluate's `stats`): the members served by those two entries get their statistics reduced on the device
-    in the same call (sac_evaluate_stats_many / sac_evaluate_general_stats_many: one k_eval_moments launch in front of the
-    call's wait) -- no eval_statistics and no sac_get_scalars for them, and with rows=False no column is copied back.  A
-    member's records are byte for byte those of its own evaluate(stats="device").  The members on the host path get
-    eval_statistics under either value."""
-    _check_stats(stats)
-    _check_general(general)
-    on_device = stats == "device"
-    trainers = list(trainers)
-    R = len(trainers)
-    eps = [None] * R if eps is None else list(eps)
-    rngs = [None] * R if rngs is None else list(rngs)
-    if not (len(batches) == len(eps) == len(rngs) == R):
-        raise RuntimeError("evaluate_many takes one batch (and eps pair, and rng) per trainer")
-    if len({id(t) for t in trainers}) != R:
-        raise RuntimeError("a trainer appears twice in evaluate_many")
-    out, arrs, chunks, alphas, dev, gen = [None] * R, [None] * R, [None] * R, [1.0] * R, [], []
-    moments, log_alphas = [None] * R, [0.0] * R
-    for i, t in enumerate(trainers):
-        b = batches[i]
-        if b is None or np.atleast_2d(b["observations"]).shape[0] == 0:
-            continue
-        general_step = runs_general_step(t)
-        if isinstance(t, TD3Trainer) or t._h is None or (general_step and general != "device") or t._evaluate_on_host:
-            out[i] = t.evaluate(b, eps=eps[i], rng=rngs[i], rows=rows)
-            continue
-        arrs[i], chunks[i] = t._eval_inputs(b, eps[i], rngs[i]), []
-        (gen if general_step else dev).append(i)
-    lib = _lib.load() if dev or gen else None
-    for members, entry in ((dev, "sac_evaluate_stats_many" if on_device else "sac_evaluate_many"),
-                           (gen, "sac_evaluate_general_stats_many" if on_device else "sac_evaluate_general_many")):
-        for r0 in range(0, max([arrs[i][0].shape[0] for i in members], default=0), _lib.ACT_MAX_ROWS):
-            live = [i for i in members if arrs[i][0].shape[0] > r0]
-            for c in range(0, len(live), MAX_MEMBERS):
-                ids = live[c:c + MAX_MEMBERS]
-                n = len(ids)
-                n_rows = [min(arrs[i][0].shape[0] - r0, _lib.ACT_MAX_ROWS) for i in ids]
-                made = [trainers[i]._eval_io(arrs[i], r0, r0 + k, outputs=rows or not on_device) for i, k in zip(ids, n_rows)]
-                ios = (_lib.SacEvalIO * n)(*[m[0] for m in made])
-                sts = (_lib.SacEvalStats * n)() if on_device else None
-                _lib.check(getattr(lib, entry)((C.c_void_p * n)(*[trainers[i]._h.value for i in ids]), n,
-                                               (C.c_int32 * n)(*n_rows), ios, *([sts] if on_device else [])), entry)
-                for k, i in enumerate(ids):
-                    chunks[i].append(made[k][1])
-                    alphas[i] = float(ios[k].alpha)
-                    if on_device:
-                        moments[i], log_alphas[i] = _merge_all(moments[i], _stats_moments(sts[k])), sts[k].log_alpha
-    for i in dev + gen:
-        t = trainers[i]
-        cols = _eval_columns(chunks[i], alphas[i]) if rows or not on_device else None
-        if on_device:
-            result = moments_statistics(moments[i], alphas[i], log_alphas[i], t.target_entropy, t.use_automatic_entropy_tuning)
-        else:
-            result = t._eval_stats(cols)
-        out[i] = (result, cols) if rows else result
-    return out
-
-
-class _ActorSession:
-    """One acting session (at most 16 members): its handle, the members' handles it was opened on, and the per-call
-    argument arrays, made once.  entry: "sac_actor" (the fused kernels' shapes) or "sac_gactor" (the general step) --
-    the two families of include/sac_hip.h have the same four signatures."""
-
-    def __init__(self, lib, ids, trainers, max_rows, entry="sac_actor"):
-        n = len(ids)
-        self.lib, self.ids, self.a, self.entry = lib, ids, C.c_void_p(), entry
-        self.handles = [trainers[i]._h.value for i in ids]
-        self.gens = [trainers[i]._handle_gen for i in ids]      # (an address can come back; the count cannot)
-        self.n_rows, self.det = (C.c_int32 * n)(), (C.c_int32 * n)()
-        self._act = getattr(lib, entry + "_act")
-        _lib.check(getattr(lib, entry + "_create")(C.byref(self.a), (C.c_void_p * n)(*self.handles), n,
-                                                   (C.c_int32 * n)(*[max_rows[i] for i in ids])), entry + "_create")
-
-    def arrays(self, k, rows, O, A):
-        o, e, a = C.c_void_p(), C.c_void_p(), C.c_void_p()
-        _lib.check(getattr(self.lib, self.entry + "_arrays")(self.a, k, C.byref(o), C.byref(e), C.byref(a)),
-                   self.entry + "_arrays")
-        view = lambda p, ct, cols: np.ctypeslib.as_array((ct * (rows * cols)).from_address(p.value)).reshape(rows, cols)  # noqa: E731
-        return view(o, C.c_double, O), view(e, C.c_float, A), view(a, C.c_float, A)
-
-    def act(self):
-        """One tick on n_rows / det as they stand."""
-        _lib.check(self._act(self.a, self.n_rows, self.det), self.entry + "_act")
-
-    def destroy(self):
-        a, self.a = self.a, None
-        if a:
-            getattr(self.lib, self.entry + "_destroy")(a)
-
-
-class _ActRows(list):
-    """GroupActor.act: the members' action views, act[i] -- and the tick itself, act(n_rows, deterministic)."""
-
-    def __init__(self, tick, rows):
-        super().__init__(rows)
-        self._tick = tick
-
-    def __call__(self, n_rows, deterministic):
-        return self._tick(n_rows, deterministic)
-
-    def __reduce__(self):
-        raise TypeError("the action views of a GroupActor are never pickled")
-
-
-class GroupActor:
-    """policy.get_actions for a FIXED list of runs, tick after tick, without marshalling: act_many as a session.
-
-    obs[i] (max_rows_i, O_i) float64, eps[i] (max_rows_i, A_i) float32 and act[i] (max_rows_i, A_i) float32 are NumPy
-    views of the staging the kernel reads and writes (sac_actor_arrays: a mapped pinned slab; nothing is copied).  A tick
-    is: write rows [0, n_i) of obs[i] (and of eps[i], for a stochastic SAC member), call act(n_rows, deterministic), read
-    rows [0, n_i) of act[i] -- and copy them before the next tick overwrites them.  n_i == 0: member i sits out and its
-    arrays are left alone.  Observations are rounded to float32 as astype(np.float32) rounds them; each member's actions
-    are bit for bit those of its own policy_act_device on obs.astype(np.float32) with the same eps.
-
-    Like act_many it opens one session per 16 members with the fused kernels' shapes; members of the general step act on
-    the host through their own policy_act inside the same act() call, with ordinary arrays behind the same attributes.
-    A session is bound to its members' handles: when a trainer has replaced its handle (a first step at another batch
-    size; seen by the trainer's count of handles made, since an address can come back), act() reopens the sessions,
-    carries the staged rows over and REPLACES the views, so read obs[i] / eps[i] / act[i] from the attributes on each
-    tick.  close() (and the finaliser) destroys the sessions.  The object holds device state only and is never pickled.
-
-    general="device": the members of the general step act on the device too -- all of them that have rows in ONE
-    sac_policy_act_general_many call per 16, on obs.astype(np.float32), the value the sessions' conversion produces --
-    and their actions are bit for bit those of their own policy_act_general on those rows.
-
-    general="device", general_sessions=True: the members of the general step get acting sessions of their own
-    (sac_gactor_*, csrc/sac_actor_general.h), one per 16 of them: obs[i] (float64), eps[i] and act[i] are views into that
-    session's slab like the other members', their tick is one C call, and reopening, close() and the pickling refusal
-    cover them too.  This is the default (None: GENERAL_SESSIONS).  The actions are the same bits as with
-    general_sessions=False, which keeps the sac_policy_act_general_many path described above, to measure against.  With
-    general="host" the keyword changes nothing."""
-
-    def __init__(self, trainers, max_rows=1, general="host", general_sessions=None):
-        self.general = _check_general(general)
-        self.general_sessions = general == "device" and bool(GENERAL_SESSIONS if general_sessions is None else general_sessions)
-        self.trainers = list(trainers)
-        R = len(self.trainers)
-        if R == 0 or len({id(t) for t in self.trainers}) != R:
-            raise RuntimeError("GroupActor takes one or more trainers, each once")
-        self.max_rows = [int(max_rows)] * R if np.isscalar(max_rows) else [int(m) for m in max_rows]
-        if len(self.max_rows) != R or not all(1 <= m <= _lib.ACT_MAX_ROWS for m in self.max_rows):
-            raise RuntimeError(f"GroupActor: max_rows is 1..{_lib.ACT_MAX_ROWS}, one value or one per trainer")
-        for i, t in enumerate(self.trainers):
-            if getattr(t, "_h", None) is None:
-                raise RuntimeError(f"GroupActor member {i} has no device handle yet (create it with batch_size=, or train once)")
-        self._lib = _lib.load()
-        self._td3 = [isinstance(t, TD3Trainer) for t in self.trainers]
-        self._host = [i for i, t in enumerate(self.trainers) if runs_general_step(t)]
-        self._dev = [i for i in range(R) if i not in set(self._host)]
-        self._gen = self._host if self.general_sessions else []      # the general-step members with sessions
-        self.obs, self.eps, self.act = [None] * R, [None] * R, _ActRows(self._act, [None] * R)
-        for i in self._host if not self.general_sessions else ():
-            t, m = self.trainers[i], self.max_rows[i]
-            self.obs[i], self.eps[i] = np.zeros((m, t.obs_dim), np.float64), np.zeros((m, t.act_dim), np.float32)
-            self.act[i] = np.zeros((m, t.act_dim), np.float32)
-        self._sessions, self._closed = [], False
-        self._open()
-
-    def _open(self):
-        for ids, entry in ((self._dev, "sac_actor"), (self._gen, "sac_gactor")):
-            for c in range(0, len(ids), MAX_MEMBERS):
-                s = _ActorSession(self._lib, ids[c:c + MAX_MEMBERS], self.trainers, self.max_rows, entry)
-                self._sessions.append(s)
-                for k, i in enumerate(s.ids):
-                    t = self.trainers[i]
-                    self.obs[i], self.eps[i], self.act[i] = s.arrays(k, self.max_rows[i], t.obs_dim, t.act_dim)
-
-    def _reopen(self):
-        """A member's handle was replaced: new sessions on the handles of now, the staged rows carried over."""
-        members = self._dev + self._gen
-        for i in members:
-            if self.trainers[i]._h is None:
-                raise RuntimeError(f"GroupActor member {i} has lost its device handle")
-        kept = {i: (self.obs[i].copy(), self.eps[i].copy(), self.act[i].copy()) for i in members}
-        self._destroy()
-        self._open()
-        for i, (o, e, a) in kept.items():
-            self.obs[i][...], self.eps[i][...], self.act[i][...] = o, e, a
-
-    def _act(self, n_rows, deterministic):
-        """act(n_rows, deterministic), one tick: actions of rows [0, n_rows[i]) of every member into act[i].
-        deterministic: one flag or one per member (MakeDeterministic; TD3 members are deterministic whatever it says)."""
-        if self._closed:
-            raise RuntimeError("this GroupActor is closed")
-        R = len(self.trainers)
-        det = [bool(deterministic)] * R if np.isscalar(deterministic) else [bool(d) for d in deterministic]
-        n_rows = [int(n) for n in n_rows]
-        if len(n_rows) != R or len(det) != R:
-            raise RuntimeError("GroupActor.act takes one row count (and one deterministic flag, or one for all) per trainer")
-        for i, n in enumerate(n_rows):                        # every refusal first: nothing has acted when one raises
-            if not 0 <= n <= self.max_rows[i]:
-                raise RuntimeError(f"GroupActor member {i}: {n} rows (0..{self.max_rows[i]} in this session, 0 = sits out)")
-        if not any(n_rows):
-            raise RuntimeError("no trainer has rows to act on")
-        if any(self.trainers[i]._h is None or self.trainers[i]._handle_gen != g
-               for s in self._sessions for i, g in zip(s.ids, s.gens)):
-            self._reopen()
-        for s in self._sessions:
-            rows = [n_rows[i] for i in s.ids]
-            if not any(rows):
-                continue
-            s.n_rows[:], s.det[:] = rows, [det[i] for i in s.ids]
-            s.act()
-        if self.general_sessions:
-            return
-        if self.general == "device":
-            ids = [i for i in self._host if n_rows[i]]
-            obs, eps, out = [None] * R, [None] * R, [None] * R
-            for i in ids:
-                obs[i] = np.ascontiguousarray(self.obs[i][:n_rows[i]].astype(np.float32))
-                eps[i] = None if det[i] or self._td3[i] else self.eps[i][:n_rows[i]]
-                out[i] = self.act[i][:n_rows[i]]
-            _act_general_many(self._lib, self.trainers, ids, n_rows, obs, det, eps, out)
-            return
-        for i in self._host:
-            n = n_rows[i]
-            if n:
-                stochastic = not det[i] and not self._td3[i]
-                self.act[i][:n] = self.trainers[i].policy_act(self.obs[i][:n], det[i], self.eps[i][:n] if stochastic else None)
-
-    def _destroy(self):
-        sessions, self._sessions = getattr(self, "_sessions", []), []
-        for s in sessions:
-            s.destroy()
-
-    def close(self):
-        """Destroy the sessions: the views must not be used afterwards, and act() raises."""
-        self._closed = True
-        self.obs, self.eps = [], []
-        del self.act[:]
-        self._destroy()
-
-    def __del__(self):
-        self._destroy()
-
-    def __reduce__(self):
-        raise TypeError("a GroupActor holds device staging and is never pickled: build a new one on the restored trainers")
 
 
 class _Members:
@@ -443,7 +61,7 @@ class _Members:
 
     def q_many(self, obs_list, act_list, nets_list=None, general="host"):
         """q_values_many over the group's members (nets_list None: qf1 and qf2 of every member; general as there)."""
-        _check_general(general)
+        check_general(general)
         if nets_list is None:
             nets_list = [("qf1", "qf2")] * len(self.trainers)
         return q_values_many(self.trainers, obs_list, act_list, nets_list, general=general)
@@ -519,7 +137,7 @@ class _GroupBase(_Members):
     def _check_general(self):
         for i, t in enumerate(self.trainers):
             if runs_general_step(t):
-                net = "policy" if _general_shape(t._hidden("policy")) else "qf1"
+                net = "policy" if general_shape(t._hidden("policy")) else "qf1"
                 raise RuntimeError(f"trainer group member {i} runs the general step ({net} hidden sizes "
                                    f"{t._hidden(net)}): groups take two hidden layers of at most 256 units")
 

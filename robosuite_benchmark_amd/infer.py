@@ -1,0 +1,607 @@
+"""Inference above the C ABI: acting, Q values and loss evaluation for one trainer or many, on live weights.
+
+Every Python inference call -- SACTrainer.policy_act_device / policy_act_general / q_values / evaluate, act_many,
+q_values_many, evaluate_many, GroupActor and the drivers above them -- goes through three things defined here once
+(DESIGN.md, section 6g):
+  the predicate   runs_general_step: does this trainer run the general step?
+  the route       route: does one member's request run on the host, through the fused entry or the general entry?
+  the windows     windows: a request cut into calls of at most 1024 rows and 16 members, marshalled by handles / ints /
+                  pointers.
+A solo request is a group of one: the library's solo entries do nothing else.  Also here, because the routes end in
+them: the statistics of an evaluation (eval_statistics on the host, the moment records of the device)."""
+from __future__ import annotations
+
+import ctypes as C
+from collections import OrderedDict
+
+import numpy as np
+
+from . import _lib
+
+MAX_MEMBERS = 16                # members of one *_many call, of one acting session, of one trainer group
+GENERAL = ("host", "device")
+GENERAL_SESSIONS = True         # GroupActor(general="device")'s default for general_sessions: switched on by the
+                                # measurement of DESIGN.md, section 6d (the actions are the same bits either way)
+STATS = ("host", "device")      # where evaluate's statistics are reduced: eval_statistics, or k_eval_moments on the device
+
+
+def check_general(general):
+    if general not in GENERAL:
+        raise RuntimeError(f"general must be one of {GENERAL}, got {general!r}")
+    return general
+
+
+def check_stats(stats):
+    if stats not in STATS:
+        raise RuntimeError(f"stats must be one of {STATS}, got {stats!r}")
+    return stats
+
+
+# ---- the predicate ------------------------------------------------------------------------------------------------------
+def general_shape(hs):
+    return len(hs) != 2 or max(hs) > 256
+
+
+def general_step(t):
+    """The predicate behind SACTrainer.runs_general_step: a trainer with a handle runs what the library built
+    (sac_trainer_step_kind; SAC_GENERAL=1 builds the general step for the fused kernels' shapes too), a trainer without
+    one is judged by its hidden sizes -- a policy or a Q family that is not two layers of at most 256 units."""
+    if t._h is not None:
+        return int(t._lib.sac_trainer_step_kind(t._h)) == 3
+    return _general_sizes(t)
+
+
+def _general_sizes(t):
+    return general_shape(t._hidden("policy")) or general_shape(t._hidden("qf1"))
+
+
+def runs_general_step(t):
+    """Does trainer t run the general step (hidden sizes other than two layers of at most 256 units)?  Such runs group in
+    MlpSACTrainerGroup / MlpTD3TrainerGroup, the others in the remaining kinds.  A SACTrainer answers itself
+    (runs_general_step); an object without that method -- a stand-in with a handle's face and _hidden, no library behind
+    it -- is judged by its hidden sizes."""
+    own = getattr(t, "runs_general_step", None)
+    return own() if own is not None else _general_sizes(t)
+
+
+def _is_td3(t):
+    return "target_policy" in getattr(t, "NETS", ())
+
+
+# ---- the route ----------------------------------------------------------------------------------------------------------
+HOST, FUSED, GENERAL_STEP = "host", "fused", "general"
+ACT_ENTRIES = {FUSED: "sac_policy_act_many", GENERAL_STEP: "sac_policy_act_general_many"}
+SESSION_ENTRIES = {FUSED: "sac_actor", GENERAL_STEP: "sac_gactor"}
+Q_ENTRIES = {FUSED: "sac_q_values_many", GENERAL_STEP: "sac_q_values_general_many"}
+EVAL_ENTRIES = {FUSED: ("sac_evaluate_many", "sac_evaluate_stats_many"),             # (stats "host", "device")
+                GENERAL_STEP: ("sac_evaluate_general_many", "sac_evaluate_general_stats_many")}
+
+
+def route(t, general, on_host=False):
+    """Where one member's request runs: HOST (its own host forward), FUSED or GENERAL_STEP (the key of the request's
+    *_ENTRIES).  No handle: the host.  The fused kernels' shapes: the fused entry under either `general`.  The general
+    step: the host, or the general entry under general="device".  on_host (evaluation: _evaluate_on_host) sends a member
+    with a handle to the host too; a TD3 member's evaluation never gets here (its own evaluate refuses)."""
+    if t._h is None or on_host:
+        return HOST
+    if not runs_general_step(t):
+        return FUSED
+    return GENERAL_STEP if general == "device" else HOST
+
+
+# ---- the windows --------------------------------------------------------------------------------------------------------
+def windows(members, n_rows):
+    """(r0, ids, counts) per library call: rows r0 = 0, 1024, ... of the members (indices into n_rows) that still have
+    rows there, 16 members per call; counts[k] = the rows of ids[k] in this window."""
+    for r0 in range(0, max([n_rows[i] for i in members], default=0), _lib.ACT_MAX_ROWS):
+        live = [i for i in members if n_rows[i] > r0]
+        for c in range(0, len(live), MAX_MEMBERS):
+            ids = live[c:c + MAX_MEMBERS]
+            yield r0, ids, [min(n_rows[i] - r0, _lib.ACT_MAX_ROWS) for i in ids]
+
+
+def _handles(trainers, ids):
+    return (C.c_void_p * len(ids))(*[trainers[i]._h.value for i in ids])
+
+
+def _ints(values, ctype=C.c_int32):
+    return (ctype * len(values))(*values)
+
+
+def _pointers(arrays):
+    return (C.c_void_p * len(arrays))(*[None if a is None else a.ctypes.data for a in arrays])
+
+
+def _row_pointers(arrays, r0, ids, counts):
+    """The pointer array of one window: rows r0.. of arrays[i] (a C-contiguous array per trainer, or None)."""
+    return _pointers([None if arrays[i] is None else arrays[i][r0:r0 + k] for i, k in zip(ids, counts)])
+
+
+# ---- acting -------------------------------------------------------------------------------------------------------------
+def act_calls(lib, entry, trainers, members, n_rows, obs, det, eps, out):
+    """The `entry` calls (one of ACT_ENTRIES) for `members`: obs / eps / out hold a float32 array (eps: or None) per
+    trainer, n_rows and det one value per trainer; out[i] is written in place."""
+    fn = getattr(lib, entry)
+    for r0, ids, counts in windows(members, n_rows):
+        _lib.check(fn(_handles(trainers, ids), len(ids), _ints(counts), _row_pointers(obs, r0, ids, counts),
+                      _ints([int(bool(det[i])) for i in ids]), _row_pointers(eps, r0, ids, counts),
+                      _row_pointers(out, r0, ids, counts)), entry)
+
+
+def act_many(trainers, obs_list, deterministic_list, eps_list, general="host"):
+    """policy.get_actions for many runs at once: actions[i] = trainers[i]'s policy on obs_list[i] ((n_i, O_i); None or no
+    rows: the member sits out and gets an empty array), deterministic_list[i] as MakeDeterministic, eps_list[i] the
+    (n_i, A_i) N(0,1) draws of a stochastic SAC member (None otherwise).  The members with the fused kernels' shapes act
+    in ONE launch per 16 of them (sac_policy_act_many: SAC and TD3, dims and row counts mixed; up to 1024 rows each);
+    members of the general step act on the host through their own policy_act.  A member's actions never depend on its
+    neighbours: they are bit for bit those of its own policy_act_device (policy_act for the general step).
+    general="device": the members of the general step act on the device as well, in ONE sac_policy_act_general_many call
+    per 16 of them; their actions are bit for bit those of their own policy_act_general."""
+    check_general(general)
+    trainers = list(trainers)
+    R = len(trainers)
+    if not (len(obs_list) == len(deterministic_list) == len(eps_list) == R):
+        raise RuntimeError("act_many takes one observation array, deterministic flag and eps per trainer")
+    if len({id(t) for t in trainers}) != R:
+        raise RuntimeError("a trainer appears twice in act_many")
+    obs = [None if o is None else _lib.f32(np.atleast_2d(o)) for o in obs_list]
+    eps = [None if e is None else _lib.f32(np.atleast_2d(e)) for e in eps_list]
+    out = [np.empty((0 if o is None else o.shape[0], t.act_dim), np.float32) for t, o in zip(trainers, obs)]
+    served = {FUSED: [], GENERAL_STEP: []}
+    for i, t in enumerate(trainers):
+        if out[i].shape[0] == 0:
+            continue
+        if obs[i].shape[1] != t.obs_dim or (eps[i] is not None and eps[i].shape != out[i].shape):
+            raise RuntimeError(f"act_many member {i}: observations {obs[i].shape} / eps "
+                               f"{None if eps[i] is None else eps[i].shape} do not fit dims ({t.obs_dim}, {t.act_dim})")
+        if out[i].shape[0] > _lib.ACT_MAX_ROWS:
+            raise RuntimeError(f"act_many member {i}: {out[i].shape[0]} rows (at most {_lib.ACT_MAX_ROWS} per call)")
+        where = route(t, general)
+        if where == HOST:
+            out[i] = t.policy_act(obs[i], deterministic_list[i], eps[i])
+        else:
+            served[where].append(i)
+    lib, n_rows = _lib.load(), [o.shape[0] for o in out]
+    for family in (GENERAL_STEP, FUSED):
+        act_calls(lib, ACT_ENTRIES[family], trainers, served[family], n_rows, obs, deterministic_list, eps, out)
+    return out
+
+
+# ---- Q values -----------------------------------------------------------------------------------------------------------
+def q_values_of(trainers, obs, act, names, masks, rows, general):
+    """q_values / q_values_many behind their argument checks, one entry per trainer: obs / act as SACTrainer._q_inputs
+    checked them (None: the member sits out), names the nets asked for, masks / rows their _lib.q_net_mask.  The host
+    members first, in member order; then the fused family, then the general one, each in windows."""
+    R = len(trainers)
+    out, n_rows, served = [None] * R, [0] * R, {FUSED: [], GENERAL_STEP: []}
+    for i, t in enumerate(trainers):
+        if obs[i] is None:
+            out[i] = np.empty((len(names[i]), 0), np.float32)
+            continue
+        where = route(t, general)
+        if where == HOST:
+            out[i] = t._q_values_host(obs[i], act[i], names[i])
+        else:
+            out[i], n_rows[i] = np.empty((len(names[i]), obs[i].shape[0]), np.float32), obs[i].shape[0]
+            served[where].append(i)
+    lib = _lib.load() if served[FUSED] or served[GENERAL_STEP] else None
+    for family in (FUSED, GENERAL_STEP):
+        entry = Q_ENTRIES[family]
+        for r0, ids, counts in windows(served[family], n_rows):
+            q = [np.empty((len(names[i]), k), np.float32) for i, k in zip(ids, counts)]
+            _lib.check(getattr(lib, entry)(_handles(trainers, ids), len(ids), _ints(counts), _row_pointers(obs, r0, ids, counts),
+                                           _row_pointers(act, r0, ids, counts), _ints([masks[i] for i in ids], C.c_uint32),
+                                           _pointers(q)), entry)
+            for i, k, part in zip(ids, counts, q):
+                out[i][:, r0:r0 + k] = part[rows[i]]
+    return out
+
+
+def q_values_many(trainers, obs_list, act_list, nets_list, general="host"):
+    """SACTrainer.q_values for many runs at once: q[i] = trainers[i]'s critics nets_list[i] (names, as q_values takes
+    them) on obs_list[i] / act_list[i] ((n_i, O_i) / (n_i, A_i); None or no rows: the member sits out and gets an empty
+    (len(nets), 0) array).  The members with the fused kernels' shapes are served by ONE launch per 16 of them and 1024
+    rows (sac_q_values_many: SAC and TD3, dims, row counts and nets mixed); members of the general step take q_values'
+    host path inside the same call.  A member's values never depend on its neighbours: they are bit for bit those of its
+    own q_values.
+    general="device": the members of the general step are evaluated on the device as well, by ONE
+    sac_q_values_general_many call per 16 of them and 1024 rows; their values are bit for bit those of their own
+    q_values(general="device")."""
+    check_general(general)
+    trainers = list(trainers)
+    R = len(trainers)
+    if not (len(obs_list) == len(act_list) == len(nets_list) == R):
+        raise RuntimeError("q_values_many takes one observation array, action array and net selection per trainer")
+    if len({id(t) for t in trainers}) != R:
+        raise RuntimeError("a trainer appears twice in q_values_many")
+    obs, act, rows, names, masks = [None] * R, [None] * R, [None] * R, [None] * R, [0] * R
+    for i, t in enumerate(trainers):
+        names[i] = [nets_list[i]] if isinstance(nets_list[i], str) else list(nets_list[i])
+        masks[i], rows[i] = _lib.q_net_mask(names[i])
+        if obs_list[i] is not None and np.atleast_2d(obs_list[i]).shape[0] != 0:
+            obs[i], act[i], _, _ = t._q_inputs(obs_list[i], act_list[i], names[i])
+    return q_values_of(trainers, obs, act, names, masks, rows, general)
+
+
+# ---- evaluation: its statistics -----------------------------------------------------------------------------------------
+def eval_target(rew, term, tq1, tq2, log_pi_next, alpha, reward_scale, discount):
+    """k_eval's y in float32 NumPy, operation for operation:
+    y = rs * r + ((1 - d) * discount) * (min(tq1, tq2) - alpha * log_pi_next), each result rounded to float32."""
+    f = np.float32
+    rew, term, tq1, tq2, lp = (np.asarray(x, f) for x in (rew, term, tq1, tq2, log_pi_next))
+    return f(reward_scale) * rew + ((f(1.0) - term) * f(discount)) * (np.fmin(tq1, tq2) - f(alpha) * lp)
+
+
+def _eval_columns(chunks, alpha):
+    """The per-row columns of evaluate from its chunks' outputs (rows (9, k), mu, log_std, a_new, a_next (k, A))."""
+    cols = OrderedDict()
+    rows = np.concatenate([c["rows"] for c in chunks], axis=1)
+    for i, name in enumerate(_lib.EVAL_ROWS):
+        cols[name] = np.ascontiguousarray(rows[i])
+    for name in _lib.EVAL_ARRAYS:
+        cols[name] = np.concatenate([c[name] for c in chunks], axis=0)
+    cols["alpha"] = float(alpha)
+    return cols
+
+
+def eval_statistics(rows, mu, log_std, alpha, log_alpha, target_entropy, auto):
+    """The statistics of SACTrainer.evaluate from its per-row columns, on the host in float64: `rows` is the
+    (SAC_EVAL_ROWS_N, n) array q1, q2, q1_new, q2_new, tq1, tq2, log_pi, log_pi_next, y (_lib.EVAL_ROWS), mu / log_std the
+    policy head's (n, A) mean and clamped log_std.  An OrderedDict with get_diagnostics()' keys in their order --
+    QF Loss = mean((q - y)^2); Policy Loss = mean(log_pi - min(q1_new, q2_new)), the reference's logged form without
+    alpha; Mean / Std (np.std) / Max / Min of q1, q2, y, log_pi, mu, log_std; Alpha; Alpha Loss =
+    -mean(log_alpha * (log_pi + target_entropy)), 0 with tuning off -- followed by TD Error 1 / TD Error 2 Mean / Std /
+    Max / Min (q - y, signed)."""
+    r = [np.asarray(x, np.float64).ravel() for x in rows]
+    q1, q2, q1n, q2n, _, _, lp, _, y = r
+
+    def stats(d, name, x):
+        x = np.asarray(x, np.float64).ravel()
+        d[name + " Mean"], d[name + " Std"] = float(np.mean(x)), float(np.std(x))
+        d[name + " Max"], d[name + " Min"] = float(np.max(x)), float(np.min(x))
+
+    d = OrderedDict()
+    d["QF1 Loss"] = float(np.mean((q1 - y) ** 2))
+    d["QF2 Loss"] = float(np.mean((q2 - y) ** 2))
+    d["Policy Loss"] = float(np.mean(lp - np.minimum(q1n, q2n)))
+    stats(d, "Q1 Predictions", q1)
+    stats(d, "Q2 Predictions", q2)
+    stats(d, "Q Targets", y)
+    stats(d, "Log Pis", lp)
+    stats(d, "Policy mu", mu)
+    stats(d, "Policy log std", log_std)
+    d["Alpha"] = float(alpha)
+    d["Alpha Loss"] = float(-np.mean(float(log_alpha) * (lp + float(target_entropy)))) if auto else 0.0
+    stats(d, "TD Error 1", q1 - y)
+    stats(d, "TD Error 2", q2 - y)
+    return d
+
+
+def eval_moments(rows, mu, log_std):
+    """k_eval_moments (csrc/sac_eval_moments.h) restated in NumPy float64 -- the reference of its tests and nothing else:
+    an OrderedDict with one record {count, sum, m2, sumsq, max, min} per name of _lib.EVAL_MOMENTS, over q1, q2, y, log_pi
+    (n elements), mu, log_std (n A), td1 = q1 - y, td2 = q2 - y and policy = log_pi - min(q1_new, q2_new) (n), every
+    element formed in float64 from the columns given.  m2 = sum((x - sum / count)^2), a second pass as np.std's; max and
+    min keep a NaN."""
+    r = [np.asarray(x, np.float64).ravel() for x in rows]
+    q1, q2, q1n, q2n, _, _, lp, _, y = r
+    flat = lambda x: np.asarray(x, np.float64).ravel()               # noqa: E731
+    xs = [q1, q2, y, lp, flat(mu), flat(log_std), q1 - y, q2 - y, lp - np.minimum(q1n, q2n)]
+    out = OrderedDict()
+    with np.errstate(all="ignore"):
+        for name, x in zip(_lib.EVAL_MOMENTS, xs):
+            s = float(np.sum(x))
+            out[name] = dict(count=float(x.size), sum=s, m2=float(np.sum((x - s / x.size) ** 2)), sumsq=float(np.sum(x * x)),
+                             max=float(np.max(x)), min=float(np.min(x)))
+    return out
+
+
+def merge_moments(a, b):
+    """The record of two disjoint sets of elements of one quantity from their records a and b (a call above 1024 rows
+    runs as several launches): count, sum and sumsq add, max and min combine (a NaN stays), and
+    m2 = m2_a + m2_b + delta^2 n_a n_b / (n_a + n_b) with delta the difference of the two means."""
+    na, nb = a["count"], b["count"]
+    n = na + nb
+    delta = b["sum"] / nb - a["sum"] / na
+    return dict(count=n, sum=a["sum"] + b["sum"], m2=a["m2"] + b["m2"] + delta * delta * (na * nb / n),
+                sumsq=a["sumsq"] + b["sumsq"], max=float(np.maximum(a["max"], b["max"])),
+                min=float(np.minimum(a["min"], b["min"])))
+
+
+def _merge_all(a, b):
+    """merge_moments per quantity; a None: b."""
+    return b if a is None else OrderedDict((k, merge_moments(a[k], b[k])) for k in a)
+
+
+def _stats_moments(st):
+    """The records of one sac_eval_stats_t as eval_moments returns them."""
+    vals = np.frombuffer(st, np.float64, len(_lib.EVAL_MOMENTS) * len(_lib.EVAL_MOMENT_FIELDS)).tolist()
+    k = len(_lib.EVAL_MOMENT_FIELDS)
+    return OrderedDict((name, dict(zip(_lib.EVAL_MOMENT_FIELDS, vals[i * k:(i + 1) * k])))
+                       for i, name in enumerate(_lib.EVAL_MOMENTS))
+
+
+def moments_statistics(moments, alpha, log_alpha, target_entropy, auto):
+    """eval_statistics' OrderedDict -- the same keys in the same order -- from the moment records of eval_moments or of
+    the device (sac_evaluate_stats_many): Mean = sum / count, Std = sqrt(m2 / count), Max and Min as stored, QF Loss =
+    td.sumsq / count, Policy Loss = policy.sum / count, Alpha Loss = -(log_alpha (log_pi.sum / count + target_entropy)),
+    0 with tuning off."""
+    def stats(d, name, m):
+        d[name + " Mean"], d[name + " Std"] = m["sum"] / m["count"], float(np.sqrt(m["m2"] / m["count"]))
+        d[name + " Max"], d[name + " Min"] = m["max"], m["min"]
+
+    M = moments
+    d = OrderedDict()
+    with np.errstate(all="ignore"):
+        d["QF1 Loss"] = M["td1"]["sumsq"] / M["td1"]["count"]
+        d["QF2 Loss"] = M["td2"]["sumsq"] / M["td2"]["count"]
+        d["Policy Loss"] = M["policy"]["sum"] / M["policy"]["count"]
+        for name, key in (("Q1 Predictions", "q1"), ("Q2 Predictions", "q2"), ("Q Targets", "y"), ("Log Pis", "log_pi"),
+                          ("Policy mu", "mu"), ("Policy log std", "log_std")):
+            stats(d, name, M[key])
+        d["Alpha"] = float(alpha)
+        d["Alpha Loss"] = -(float(log_alpha) * (M["log_pi"]["sum"] / M["log_pi"]["count"] + float(target_entropy))) if auto else 0.0
+        stats(d, "TD Error 1", M["td1"])
+        stats(d, "TD Error 2", M["td2"])
+    return d
+
+
+# ---- evaluation ---------------------------------------------------------------------------------------------------------
+def evaluate_of(trainers, inputs, rows, general, stats):
+    """evaluate / evaluate_many behind their argument checks: inputs[i] = the member's arrays as SACTrainer._eval_inputs
+    checked them, or None for a member that sits out (its result: None).  The host members first, in member order; then
+    the fused family, then the general one, each in windows."""
+    on_device = stats == "device"
+    R = len(trainers)
+    out, n_rows, served = [None] * R, [0] * R, {FUSED: [], GENERAL_STEP: []}
+    for i, (t, arrs) in enumerate(zip(trainers, inputs)):
+        if arrs is None:
+            continue
+        where = route(t, general, t._evaluate_on_host)
+        if where == HOST:
+            cols = t._evaluate_host(arrs)
+            result = t._eval_stats(cols)
+            out[i] = (result, cols) if rows else result
+        else:
+            n_rows[i] = arrs[0].shape[0]
+            served[where].append(i)
+    members = served[FUSED] + served[GENERAL_STEP]
+    lib = _lib.load() if members else None
+    chunks, alphas, moments, log_alphas = {i: [] for i in members}, [1.0] * R, [None] * R, [0.0] * R
+    for family in (FUSED, GENERAL_STEP):
+        entry = EVAL_ENTRIES[family][on_device]
+        for r0, ids, counts in windows(served[family], n_rows):
+            made = [trainers[i]._eval_io(inputs[i], r0, r0 + k, outputs=rows or not on_device) for i, k in zip(ids, counts)]
+            ios = (_lib.SacEvalIO * len(ids))(*[m[0] for m in made])
+            sts = (_lib.SacEvalStats * len(ids))() if on_device else None
+            _lib.check(getattr(lib, entry)(_handles(trainers, ids), len(ids), _ints(counts), ios,
+                                           *([sts] if on_device else [])), entry)
+            for k, i in enumerate(ids):
+                chunks[i].append(made[k][1])
+                alphas[i] = float(ios[k].alpha)
+                if on_device:
+                    moments[i], log_alphas[i] = _merge_all(moments[i], _stats_moments(sts[k])), sts[k].log_alpha
+    for i in members:
+        t = trainers[i]
+        cols = _eval_columns(chunks[i], alphas[i]) if rows or not on_device else None
+        if on_device:
+            result = moments_statistics(moments[i], alphas[i], log_alphas[i], t.target_entropy, t.use_automatic_entropy_tuning)
+        else:
+            result = t._eval_stats(cols)
+        out[i] = (result, cols) if rows else result
+    return out
+
+
+def evaluate_many(trainers, batches, eps=None, rngs=None, rows=False, general="host", stats="host"):
+    """SACTrainer.evaluate for many runs at once: result[i] = trainers[i].evaluate(batches[i], eps[i], rngs[i]) (eps / rngs:
+    one entry per trainer or None; batches[i] None or without rows: the member sits out and gets None).  The SAC members
+    with the fused kernels' shapes are served by ONE launch per 16 of them and 1024 rows (sac_evaluate_many: dims, hidden
+    sizes and row counts mixed); the others -- the general step, trainers without a handle -- go through their own
+    evaluate inside the same call (a TD3 member raises there).  A member's columns never depend on its neighbours: they
+    are bit for bit those of its own evaluate.  Results come back in member order; rows=True as for evaluate.
+    general="device": the SAC members of the general step are evaluated on the device as well, by ONE
+    sac_evaluate_general_many call per 16 of them and 1024 rows; their results are bit for bit those of their own
+    evaluate(general="device").
+    stats="device" (evaluate's `stats`): the members served by those two entries get their statistics reduced on the device
+    in the same call (sac_evaluate_stats_many / sac_evaluate_general_stats_many: one k_eval_moments launch in front of the
+    call's wait) -- no eval_statistics and no sac_get_scalars for them, and with rows=False no column is copied back.  A
+    member's records are byte for byte those of its own evaluate(stats="device").  The members on the host path get
+    eval_statistics under either value."""
+    check_stats(stats)
+    check_general(general)
+    trainers = list(trainers)
+    R = len(trainers)
+    eps = [None] * R if eps is None else list(eps)
+    rngs = [None] * R if rngs is None else list(rngs)
+    if not (len(batches) == len(eps) == len(rngs) == R):
+        raise RuntimeError("evaluate_many takes one batch (and eps pair, and rng) per trainer")
+    if len({id(t) for t in trainers}) != R:
+        raise RuntimeError("a trainer appears twice in evaluate_many")
+    inputs = [None] * R
+    for i, (t, b) in enumerate(zip(trainers, batches)):
+        if b is None or np.atleast_2d(b["observations"]).shape[0] == 0:
+            continue
+        if _is_td3(t):
+            t.evaluate(b, eps=eps[i], rng=rngs[i], rows=rows)        # (TD3Trainer.evaluate refuses: the SAC objective)
+        inputs[i] = t._eval_inputs(b, eps[i], rngs[i])
+    return evaluate_of(trainers, inputs, rows, general, stats)
+
+
+# ---- acting sessions ----------------------------------------------------------------------------------------------------
+class _ActorSession:
+    """One acting session (at most 16 members): its handle, the members' handles it was opened on, and the per-call
+    argument arrays, made once.  entry: "sac_actor" (the fused kernels' shapes) or "sac_gactor" (the general step) --
+    the two families of include/sac_hip.h have the same four signatures."""
+
+    def __init__(self, lib, ids, trainers, max_rows, entry="sac_actor"):
+        n = len(ids)
+        self.lib, self.ids, self.a, self.entry = lib, ids, C.c_void_p(), entry
+        self.handles = [trainers[i]._h.value for i in ids]
+        self.gens = [trainers[i]._handle_gen for i in ids]      # (an address can come back; the count cannot)
+        self.n_rows, self.det = (C.c_int32 * n)(), (C.c_int32 * n)()
+        self._act = getattr(lib, entry + "_act")
+        _lib.check(getattr(lib, entry + "_create")(C.byref(self.a), _handles(trainers, ids), n,
+                                                   _ints([max_rows[i] for i in ids])), entry + "_create")
+
+    def arrays(self, k, rows, O, A):
+        o, e, a = C.c_void_p(), C.c_void_p(), C.c_void_p()
+        _lib.check(getattr(self.lib, self.entry + "_arrays")(self.a, k, C.byref(o), C.byref(e), C.byref(a)),
+                   self.entry + "_arrays")
+        view = lambda p, ct, cols: np.ctypeslib.as_array((ct * (rows * cols)).from_address(p.value)).reshape(rows, cols)  # noqa: E731
+        return view(o, C.c_double, O), view(e, C.c_float, A), view(a, C.c_float, A)
+
+    def act(self):
+        """One tick on n_rows / det as they stand."""
+        _lib.check(self._act(self.a, self.n_rows, self.det), self.entry + "_act")
+
+    def destroy(self):
+        a, self.a = self.a, None
+        if a:
+            getattr(self.lib, self.entry + "_destroy")(a)
+
+
+class _ActRows(list):
+    """GroupActor.act: the members' action views, act[i] -- and the tick itself, act(n_rows, deterministic)."""
+
+    def __init__(self, tick, rows):
+        super().__init__(rows)
+        self._tick = tick
+
+    def __call__(self, n_rows, deterministic):
+        return self._tick(n_rows, deterministic)
+
+    def __reduce__(self):
+        raise TypeError("the action views of a GroupActor are never pickled")
+
+
+class GroupActor:
+    """policy.get_actions for a FIXED list of runs, tick after tick, without marshalling: act_many as a session.
+
+    obs[i] (max_rows_i, O_i) float64, eps[i] (max_rows_i, A_i) float32 and act[i] (max_rows_i, A_i) float32 are NumPy
+    views of the staging the kernel reads and writes (sac_actor_arrays: a mapped pinned slab; nothing is copied).  A tick
+    is: write rows [0, n_i) of obs[i] (and of eps[i], for a stochastic SAC member), call act(n_rows, deterministic), read
+    rows [0, n_i) of act[i] -- and copy them before the next tick overwrites them.  n_i == 0: member i sits out and its
+    arrays are left alone.  Observations are rounded to float32 as astype(np.float32) rounds them; each member's actions
+    are bit for bit those of its own policy_act_device on obs.astype(np.float32) with the same eps.
+
+    Like act_many it opens one session per 16 members with the fused kernels' shapes; members of the general step act on
+    the host through their own policy_act inside the same act() call, with ordinary arrays behind the same attributes.
+    A session is bound to its members' handles: when a trainer has replaced its handle (a first step at another batch
+    size; seen by the trainer's count of handles made, since an address can come back), act() reopens the sessions,
+    carries the staged rows over and REPLACES the views, so read obs[i] / eps[i] / act[i] from the attributes on each
+    tick.  close() (and the finaliser) destroys the sessions.  The object holds device state only and is never pickled.
+
+    general="device": the members of the general step act on the device too -- all of them that have rows in ONE
+    sac_policy_act_general_many call per 16, on obs.astype(np.float32), the value the sessions' conversion produces --
+    and their actions are bit for bit those of their own policy_act_general on those rows.
+
+    general="device", general_sessions=True: the members of the general step get acting sessions of their own
+    (sac_gactor_*, csrc/sac_actor_general.h), one per 16 of them: obs[i] (float64), eps[i] and act[i] are views into that
+    session's slab like the other members', their tick is one C call, and reopening, close() and the pickling refusal
+    cover them too.  This is the default (None: GENERAL_SESSIONS).  The actions are the same bits as with
+    general_sessions=False, which keeps the sac_policy_act_general_many path described above, to measure against.  With
+    general="host" the keyword changes nothing."""
+
+    def __init__(self, trainers, max_rows=1, general="host", general_sessions=None):
+        self.general = check_general(general)
+        self.general_sessions = general == "device" and bool(GENERAL_SESSIONS if general_sessions is None else general_sessions)
+        self.trainers = list(trainers)
+        R = len(self.trainers)
+        if R == 0 or len({id(t) for t in self.trainers}) != R:
+            raise RuntimeError("GroupActor takes one or more trainers, each once")
+        self.max_rows = [int(max_rows)] * R if np.isscalar(max_rows) else [int(m) for m in max_rows]
+        if len(self.max_rows) != R or not all(1 <= m <= _lib.ACT_MAX_ROWS for m in self.max_rows):
+            raise RuntimeError(f"GroupActor: max_rows is 1..{_lib.ACT_MAX_ROWS}, one value or one per trainer")
+        for i, t in enumerate(self.trainers):
+            if getattr(t, "_h", None) is None:
+                raise RuntimeError(f"GroupActor member {i} has no device handle yet (create it with batch_size=, or train once)")
+        self._lib = _lib.load()
+        self._td3 = [_is_td3(t) for t in self.trainers]
+        # each member's route, fixed here: a session per 16 of a family (the general one under general_sessions), ONE
+        # general call per tick and 16 members (_calls: general="device" without sessions), or its own policy_act (_host)
+        routes = [route(t, general) for t in self.trainers]
+        general_step = [i for i in range(R) if routes[i] == GENERAL_STEP]
+        self._session_ids = {FUSED: [i for i in range(R) if routes[i] == FUSED],
+                             GENERAL_STEP: general_step if self.general_sessions else []}
+        self._calls = [] if self.general_sessions else general_step
+        self._host = [i for i in range(R) if routes[i] == HOST]
+        self.obs, self.eps, self.act = [None] * R, [None] * R, _ActRows(self._act, [None] * R)
+        for i in self._calls + self._host:
+            t, m = self.trainers[i], self.max_rows[i]
+            self.obs[i], self.eps[i] = np.zeros((m, t.obs_dim), np.float64), np.zeros((m, t.act_dim), np.float32)
+            self.act[i] = np.zeros((m, t.act_dim), np.float32)
+        self._sessions, self._closed = [], False
+        self._open()
+
+    def _open(self):
+        for family in (FUSED, GENERAL_STEP):
+            ids = self._session_ids[family]
+            for c in range(0, len(ids), MAX_MEMBERS):
+                s = _ActorSession(self._lib, ids[c:c + MAX_MEMBERS], self.trainers, self.max_rows, SESSION_ENTRIES[family])
+                self._sessions.append(s)
+                for k, i in enumerate(s.ids):
+                    t = self.trainers[i]
+                    self.obs[i], self.eps[i], self.act[i] = s.arrays(k, self.max_rows[i], t.obs_dim, t.act_dim)
+
+    def _reopen(self):
+        """A member's handle was replaced: new sessions on the handles of now, the staged rows carried over."""
+        members = self._session_ids[FUSED] + self._session_ids[GENERAL_STEP]
+        for i in members:
+            if self.trainers[i]._h is None:
+                raise RuntimeError(f"GroupActor member {i} has lost its device handle")
+        kept = {i: (self.obs[i].copy(), self.eps[i].copy(), self.act[i].copy()) for i in members}
+        self._destroy()
+        self._open()
+        for i, (o, e, a) in kept.items():
+            self.obs[i][...], self.eps[i][...], self.act[i][...] = o, e, a
+
+    def _act(self, n_rows, deterministic):
+        """act(n_rows, deterministic), one tick: actions of rows [0, n_rows[i]) of every member into act[i].
+        deterministic: one flag or one per member (MakeDeterministic; TD3 members are deterministic whatever it says)."""
+        if self._closed:
+            raise RuntimeError("this GroupActor is closed")
+        R = len(self.trainers)
+        det = [bool(deterministic)] * R if np.isscalar(deterministic) else [bool(d) for d in deterministic]
+        n_rows = [int(n) for n in n_rows]
+        if len(n_rows) != R or len(det) != R:
+            raise RuntimeError("GroupActor.act takes one row count (and one deterministic flag, or one for all) per trainer")
+        for i, n in enumerate(n_rows):                        # every refusal first: nothing has acted when one raises
+            if not 0 <= n <= self.max_rows[i]:
+                raise RuntimeError(f"GroupActor member {i}: {n} rows (0..{self.max_rows[i]} in this session, 0 = sits out)")
+        if not any(n_rows):
+            raise RuntimeError("no trainer has rows to act on")
+        if any(self.trainers[i]._h is None or self.trainers[i]._handle_gen != g
+               for s in self._sessions for i, g in zip(s.ids, s.gens)):
+            self._reopen()
+        for s in self._sessions:
+            rows = [n_rows[i] for i in s.ids]
+            if not any(rows):
+                continue
+            s.n_rows[:], s.det[:] = rows, [det[i] for i in s.ids]
+            s.act()
+        if not (self._calls or self._host):                   # (every member has a session)
+            return
+        eps = {i: None if det[i] or self._td3[i] else self.eps[i][:n_rows[i]] for i in self._calls + self._host}
+        obs = {i: np.ascontiguousarray(self.obs[i][:n_rows[i]].astype(np.float32)) for i in self._calls}
+        act_calls(self._lib, ACT_ENTRIES[GENERAL_STEP], self.trainers, self._calls, n_rows, obs, det, eps, self.act)
+        for i in self._host:
+            if n_rows[i]:
+                self.act[i][:n_rows[i]] = self.trainers[i].policy_act(self.obs[i][:n_rows[i]], det[i], eps[i])
+
+    def _destroy(self):
+        sessions, self._sessions = getattr(self, "_sessions", []), []
+        for s in sessions:
+            s.destroy()
+
+    def close(self):
+        """Destroy the sessions: the views must not be used afterwards, and act() raises."""
+        self._closed = True
+        self.obs, self.eps = [], []
+        del self.act[:]
+        self._destroy()
+
+    def __del__(self):
+        self._destroy()
+
+    def __reduce__(self):
+        raise TypeError("a GroupActor holds device staging and is never pickled: build a new one on the restored trainers")

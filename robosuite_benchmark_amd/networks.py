@@ -78,7 +78,7 @@ class _Mlp:
 
     def _act(self, tr, obs, deterministic, eps):
         acting = check_acting(self.acting)
-        if acting == "device_all" and tr._lib.sac_trainer_step_kind(tr._h) == 3:       # (3: the general step)
+        if acting == "device_all" and tr.runs_general_step():
             return tr.policy_act_general(obs, deterministic, eps)
         if acting != "host":
             return tr.policy_act_device(obs, deterministic, eps)

@@ -11,140 +11,25 @@ from collections import OrderedDict
 
 import numpy as np
 
-from . import _lib
+from . import _lib, infer
 from ._lib import DIAG_NAMES, NET_IDS, SacConfig
+from .infer import (STATS, eval_moments, eval_statistics, eval_target, merge_moments,  # noqa: F401  (their home is infer)
+                    moments_statistics)
 from .networks import process_seed
 
 
-def eval_target(rew, term, tq1, tq2, log_pi_next, alpha, reward_scale, discount):
-    """k_eval's y in float32 NumPy, operation for operation:
-    y = rs * r + ((1 - d) * discount) * (min(tq1, tq2) - alpha * log_pi_next), each result rounded to float32."""
-    f = np.float32
-    rew, term, tq1, tq2, lp = (np.asarray(x, f) for x in (rew, term, tq1, tq2, log_pi_next))
-    return f(reward_scale) * rew + ((f(1.0) - term) * f(discount)) * (np.fmin(tq1, tq2) - f(alpha) * lp)
+def _hidden_layers(h, layers):
+    """The hidden layers of the host forwards, float32: relu(h W^T + b) per (W, b)."""
+    for w, b in layers:
+        h = h @ w.T + b
+        h = np.where(h < 0, np.float32(0), h)
+    return h
 
 
-def _eval_columns(chunks, alpha):
-    """The per-row columns of evaluate from its chunks' outputs (rows (9, k), mu, log_std, a_new, a_next (k, A))."""
-    cols = OrderedDict()
-    rows = np.concatenate([c["rows"] for c in chunks], axis=1)
-    for i, name in enumerate(_lib.EVAL_ROWS):
-        cols[name] = np.ascontiguousarray(rows[i])
-    for name in _lib.EVAL_ARRAYS:
-        cols[name] = np.concatenate([c[name] for c in chunks], axis=0)
-    cols["alpha"] = float(alpha)
-    return cols
-
-
-def eval_statistics(rows, mu, log_std, alpha, log_alpha, target_entropy, auto):
-    """The statistics of SACTrainer.evaluate from its per-row columns, on the host in float64: `rows` is the
-    (SAC_EVAL_ROWS_N, n) array q1, q2, q1_new, q2_new, tq1, tq2, log_pi, log_pi_next, y (_lib.EVAL_ROWS), mu / log_std the
-    policy head's (n, A) mean and clamped log_std.  An OrderedDict with get_diagnostics()' keys in their order --
-    QF Loss = mean((q - y)^2); Policy Loss = mean(log_pi - min(q1_new, q2_new)), the reference's logged form without
-    alpha; Mean / Std (np.std) / Max / Min of q1, q2, y, log_pi, mu, log_std; Alpha; Alpha Loss =
-    -mean(log_alpha * (log_pi + target_entropy)), 0 with tuning off -- followed by TD Error 1 / TD Error 2 Mean / Std /
-    Max / Min (q - y, signed)."""
-    r = [np.asarray(x, np.float64).ravel() for x in rows]
-    q1, q2, q1n, q2n, _, _, lp, _, y = r
-
-    def stats(d, name, x):
-        x = np.asarray(x, np.float64).ravel()
-        d[name + " Mean"], d[name + " Std"] = float(np.mean(x)), float(np.std(x))
-        d[name + " Max"], d[name + " Min"] = float(np.max(x)), float(np.min(x))
-
-    d = OrderedDict()
-    d["QF1 Loss"] = float(np.mean((q1 - y) ** 2))
-    d["QF2 Loss"] = float(np.mean((q2 - y) ** 2))
-    d["Policy Loss"] = float(np.mean(lp - np.minimum(q1n, q2n)))
-    stats(d, "Q1 Predictions", q1)
-    stats(d, "Q2 Predictions", q2)
-    stats(d, "Q Targets", y)
-    stats(d, "Log Pis", lp)
-    stats(d, "Policy mu", mu)
-    stats(d, "Policy log std", log_std)
-    d["Alpha"] = float(alpha)
-    d["Alpha Loss"] = float(-np.mean(float(log_alpha) * (lp + float(target_entropy)))) if auto else 0.0
-    stats(d, "TD Error 1", q1 - y)
-    stats(d, "TD Error 2", q2 - y)
-    return d
-
-
-STATS = ("host", "device")      # where evaluate's statistics are reduced: eval_statistics, or k_eval_moments on the device
-
-
-def _check_stats(stats):
-    if stats not in STATS:
-        raise RuntimeError(f"stats must be one of {STATS}, got {stats!r}")
-    return stats
-
-
-def eval_moments(rows, mu, log_std):
-    """k_eval_moments (csrc/sac_eval_moments.h) restated in NumPy float64 -- the reference of its tests and nothing else:
-    an OrderedDict with one record {count, sum, m2, sumsq, max, min} per name of _lib.EVAL_MOMENTS, over q1, q2, y, log_pi
-    (n elements), mu, log_std (n A), td1 = q1 - y, td2 = q2 - y and policy = log_pi - min(q1_new, q2_new) (n), every
-    element formed in float64 from the columns given.  m2 = sum((x - sum / count)^2), a second pass as np.std's; max and
-    min keep a NaN."""
-    r = [np.asarray(x, np.float64).ravel() for x in rows]
-    q1, q2, q1n, q2n, _, _, lp, _, y = r
-    flat = lambda x: np.asarray(x, np.float64).ravel()               # noqa: E731
-    xs = [q1, q2, y, lp, flat(mu), flat(log_std), q1 - y, q2 - y, lp - np.minimum(q1n, q2n)]
-    out = OrderedDict()
-    with np.errstate(all="ignore"):
-        for name, x in zip(_lib.EVAL_MOMENTS, xs):
-            s = float(np.sum(x))
-            out[name] = dict(count=float(x.size), sum=s, m2=float(np.sum((x - s / x.size) ** 2)), sumsq=float(np.sum(x * x)),
-                             max=float(np.max(x)), min=float(np.min(x)))
-    return out
-
-
-def merge_moments(a, b):
-    """The record of two disjoint sets of elements of one quantity from their records a and b (a call above 1024 rows
-    runs as several launches): count, sum and sumsq add, max and min combine (a NaN stays), and
-    m2 = m2_a + m2_b + delta^2 n_a n_b / (n_a + n_b) with delta the difference of the two means."""
-    na, nb = a["count"], b["count"]
-    n = na + nb
-    delta = b["sum"] / nb - a["sum"] / na
-    return dict(count=n, sum=a["sum"] + b["sum"], m2=a["m2"] + b["m2"] + delta * delta * (na * nb / n),
-                sumsq=a["sumsq"] + b["sumsq"], max=float(np.maximum(a["max"], b["max"])),
-                min=float(np.minimum(a["min"], b["min"])))
-
-
-def _merge_all(a, b):
-    """merge_moments per quantity; a None: b."""
-    return b if a is None else OrderedDict((k, merge_moments(a[k], b[k])) for k in a)
-
-
-def _stats_moments(st):
-    """The records of one sac_eval_stats_t as eval_moments returns them."""
-    vals = np.frombuffer(st, np.float64, len(_lib.EVAL_MOMENTS) * len(_lib.EVAL_MOMENT_FIELDS)).tolist()
-    k = len(_lib.EVAL_MOMENT_FIELDS)
-    return OrderedDict((name, dict(zip(_lib.EVAL_MOMENT_FIELDS, vals[i * k:(i + 1) * k])))
-                       for i, name in enumerate(_lib.EVAL_MOMENTS))
-
-
-def moments_statistics(moments, alpha, log_alpha, target_entropy, auto):
-    """eval_statistics' OrderedDict -- the same keys in the same order -- from the moment records of eval_moments or of
-    the device (sac_evaluate_stats_many): Mean = sum / count, Std = sqrt(m2 / count), Max and Min as stored, QF Loss =
-    td.sumsq / count, Policy Loss = policy.sum / count, Alpha Loss = -(log_alpha (log_pi.sum / count + target_entropy)),
-    0 with tuning off."""
-    def stats(d, name, m):
-        d[name + " Mean"], d[name + " Std"] = m["sum"] / m["count"], float(np.sqrt(m["m2"] / m["count"]))
-        d[name + " Max"], d[name + " Min"] = m["max"], m["min"]
-
-    M = moments
-    d = OrderedDict()
-    with np.errstate(all="ignore"):
-        d["QF1 Loss"] = M["td1"]["sumsq"] / M["td1"]["count"]
-        d["QF2 Loss"] = M["td2"]["sumsq"] / M["td2"]["count"]
-        d["Policy Loss"] = M["policy"]["sum"] / M["policy"]["count"]
-        for name, key in (("Q1 Predictions", "q1"), ("Q2 Predictions", "q2"), ("Q Targets", "y"), ("Log Pis", "log_pi"),
-                          ("Policy mu", "mu"), ("Policy log std", "log_std")):
-            stats(d, name, M[key])
-        d["Alpha"] = float(alpha)
-        d["Alpha Loss"] = -(float(log_alpha) * (M["log_pi"]["sum"] / M["log_pi"]["count"] + float(target_entropy))) if auto else 0.0
-        stats(d, "TD Error 1", M["td1"])
-        stats(d, "TD Error 2", M["td2"])
-    return d
+def _q_forward(layers, x):
+    """Q(x) of one net's [(W, b)] on the rows x = [obs, act], float32 (n,)."""
+    h = _hidden_layers(x, layers[:-1])
+    return (h @ layers[-1][0].T + layers[-1][1])[:, 0]
 
 
 class SACTrainer:
@@ -367,6 +252,11 @@ class SACTrainer:
     def is_fused(self):
         return self.fused_mode() == 1
 
+    def runs_general_step(self):
+        """Does this trainer run the general step?  With a handle: what the library built; without one: hidden sizes other
+        than two layers of at most 256 units (infer.general_step)."""
+        return infer.general_step(self)
+
     def loop_timing_ms(self):
         v = [C.c_float() for _ in range(4)]
         _lib.check(self._lib.sac_last_loop_ms(self._h, *[C.byref(x) for x in v]), "sac_last_loop_ms")
@@ -402,30 +292,20 @@ class SACTrainer:
         """policy.get_actions on the DEVICE from the live weights (sac_policy_act_device): all rows of `obs` in one launch
         per 1024 rows, no mirror of the policy on the host.  Trainers of the general step are refused by the library: they
         act through policy_act."""
-        obs = _lib.f32(obs)
-        n, A = obs.shape[0], self.act_dim
-        out = np.empty((n, A), np.float32)
-        e = None if eps is None else _lib.f32(eps)
-        for i in range(0, n, _lib.ACT_MAX_ROWS):
-            j = min(n, i + _lib.ACT_MAX_ROWS)
-            _lib.check(self._lib.sac_policy_act_device(self._h, j - i, _lib.ptr(obs[i:j]), int(bool(deterministic)),
-                                                       None if e is None else _lib.ptr(e[i:j]), _lib.ptr(out[i:j])),
-                       "sac_policy_act_device")
-        return out
+        return self._act_on_device(infer.FUSED, obs, deterministic, eps)
 
     def policy_act_general(self, obs, deterministic, eps):
         """policy.get_actions on the DEVICE for a trainer of the general step (sac_policy_act_general: k_act_layer, one
         launch per layer on the live weights): all rows of `obs` in one call per 1024 rows, no mirror of the policy on the
         host.  Trainers with the fused kernels' shapes are refused by the library: policy_act_device is their entry."""
+        return self._act_on_device(infer.GENERAL_STEP, obs, deterministic, eps)
+
+    def _act_on_device(self, family, obs, deterministic, eps):
+        """policy_act_device / policy_act_general: this trainer alone through its family's entry of infer.ACT_ENTRIES."""
         obs = _lib.f32(obs)
-        n, A = obs.shape[0], self.act_dim
-        out = np.empty((n, A), np.float32)
-        e = None if eps is None else _lib.f32(eps)
-        for i in range(0, n, _lib.ACT_MAX_ROWS):
-            j = min(n, i + _lib.ACT_MAX_ROWS)
-            _lib.check(self._lib.sac_policy_act_general(self._h, j - i, _lib.ptr(obs[i:j]), int(bool(deterministic)),
-                                                        None if e is None else _lib.ptr(e[i:j]), _lib.ptr(out[i:j])),
-                       "sac_policy_act_general")
+        out = np.empty((obs.shape[0], self.act_dim), np.float32)
+        infer.act_calls(self._lib, infer.ACT_ENTRIES[family], [self], [0], [obs.shape[0]], [obs], [deterministic],
+                        [None if eps is None else _lib.f32(eps)], [out])
         return out
 
     def _q_inputs(self, obs, act, nets):
@@ -448,18 +328,7 @@ class SACTrainer:
         x = np.concatenate([obs, act], axis=1)
         out = np.empty((len(nets), x.shape[0]), np.float32)
         for r, name in enumerate(nets):
-            flat = self._get_params(name) if self._h is not None else _lib.f32(getattr(self, name).flat())
-            h, off = x, 0
-            sizes = self._hidden(name) + [1]
-            for l, n_out in enumerate(sizes):
-                k = h.shape[1]
-                w, b = flat[off:off + n_out * k].reshape(n_out, k), flat[off + n_out * k:off + n_out * k + n_out]
-                off += n_out * k + n_out
-                h = h @ w.T + b
-                if l + 1 < len(sizes):
-                    h = np.where(h < 0, np.float32(0), h)
-            assert off == flat.size
-            out[r] = h[:, 0]
+            out[r] = _q_forward(self._host_net(name), x)
         return out
 
     def q_values(self, obs, act, nets=("qf1", "qf2"), general="host"):
@@ -472,23 +341,10 @@ class SACTrainer:
         path; "device" evaluates on the device as well (sac_q_values_general: k_qval_layer, one launch per layer on the
         live weights, in calls of at most 1024 rows, no parameter copy).  A trainer with the fused kernels' shapes takes
         sac_q_values and a trainer without a handle the host path under either value."""
-        from .group import _check_general
-        _check_general(general)
+        infer.check_general(general)
         obs, act, mask, rows = self._q_inputs(obs, act, nets)
         names = [nets] if isinstance(nets, str) else list(nets)
-        gen = self._h is not None and self.fused_mode() == 3
-        if self._h is None or (gen and general != "device"):
-            return self._q_values_host(obs, act, names)
-        entry = "sac_q_values_general" if gen else "sac_q_values"
-        fn = getattr(self._lib, entry)
-        n = obs.shape[0]
-        out = np.empty((len(names), n), np.float32)
-        for i in range(0, n, _lib.ACT_MAX_ROWS):
-            j = min(n, i + _lib.ACT_MAX_ROWS)
-            part = np.empty((len(names), j - i), np.float32)
-            _lib.check(fn(self._h, j - i, _lib.ptr(obs[i:j]), _lib.ptr(act[i:j]), mask, _lib.ptr(part)), entry)
-            out[:, i:j] = part[rows]
-        return out
+        return infer.q_values_of([self], [obs], [act], [names], [mask], [rows], general)[0]
 
     # ---- evaluation on held-out transitions --------------------------------------------------
     _evaluate_on_host = False        # private switch: the host path for a fused-shape trainer too (scripts/bench_evaluate.py
@@ -531,36 +387,6 @@ class SACTrainer:
                             *[out[name].ctypes.data for name in _lib.EVAL_ARRAYS], 0.0)
         return io, out, parts
 
-    def _evaluate_device(self, arrs, entry="sac_evaluate"):
-        n = arrs[0].shape[0]
-        chunks, alpha = [], 1.0
-        fn = getattr(self._lib, entry)
-        for i in range(0, n, _lib.ACT_MAX_ROWS):
-            j = min(n, i + _lib.ACT_MAX_ROWS)
-            io, out, _keep = self._eval_io(arrs, i, j)
-            _lib.check(fn(self._h, j - i, C.byref(io)), entry)
-            chunks.append(out)
-            alpha = float(io.alpha)
-        return _eval_columns(chunks, alpha)
-
-    def _evaluate_device_stats(self, arrs, entry, rows):
-        """evaluate(stats="device") of a member of the device path: one `entry` call (sac_evaluate_stats_many or
-        sac_evaluate_general_stats_many, this trainer alone) per 1024 rows, the chunks' records merged by merge_moments.
-        No eval_statistics, no sac_get_scalars.  (statistics, columns -- None unless rows)."""
-        n = arrs[0].shape[0]
-        chunks, moments, st = [], None, _lib.SacEvalStats()
-        fn = getattr(self._lib, entry)
-        handle, one = (C.c_void_p * 1)(self._h.value), (C.c_int32 * 1)()
-        for i in range(0, n, _lib.ACT_MAX_ROWS):
-            j = min(n, i + _lib.ACT_MAX_ROWS)
-            io, out, _keep = self._eval_io(arrs, i, j, outputs=rows)
-            one[0] = j - i
-            _lib.check(fn(handle, 1, one, C.byref(io), C.byref(st)), entry)
-            chunks.append(out)
-            moments = _merge_all(moments, _stats_moments(st))
-        stats = moments_statistics(moments, st.alpha, st.log_alpha, self.target_entropy, self.use_automatic_entropy_tuning)
-        return stats, (_eval_columns(chunks, st.alpha) if rows else None)
-
     def _host_net(self, name):
         """[(W, b)] of one net from the current weights: sac_get_params, or the holder's arrays without a handle."""
         flat = self._get_params(name) if self._h is not None else _lib.f32(getattr(self, name).flat())
@@ -590,20 +416,12 @@ class SACTrainer:
         nets = {name: self._host_net(name) for name in NET_IDS}
         f = np.float32
 
-        def hidden(h, layers):
-            for w, b in layers:
-                h = h @ w.T + b
-                h = np.where(h < 0, f(0), h)
-            return h
-
         def q(name, s, a):
-            layers = nets[name]
-            h = hidden(np.concatenate([s, a], axis=1), layers[:-1])
-            return (h @ layers[-1][0].T + layers[-1][1])[:, 0]
+            return _q_forward(nets[name], np.concatenate([s, a], axis=1))
 
         def pi(s, e):
             layers = nets["policy"]
-            h = hidden(s, layers[:-2])
+            h = _hidden_layers(s, layers[:-2])
             mean = h @ layers[-2][0].T + layers[-2][1]
             ls = np.clip(h @ layers[-1][0].T + layers[-1][1], f(-20.0), f(2.0))
             std = np.exp(ls)
@@ -623,7 +441,7 @@ class SACTrainer:
                         y=eval_target(rew, term, tq1, tq2, log_pi_next, alpha, self.reward_scale, self.discount))
         out = dict(rows=np.stack([_lib.f32(cols[k]) for k in _lib.EVAL_ROWS]), mu=_lib.f32(mu), log_std=_lib.f32(log_std),
                    a_new=_lib.f32(a_new), a_next=_lib.f32(a_next))
-        return _eval_columns([out], alpha)
+        return infer._eval_columns([out], alpha)
 
     def _scalars(self):
         sc = np.zeros(6, np.float64)
@@ -665,21 +483,9 @@ class SACTrainer:
         eval_statistics, no sac_get_scalars, and with rows=False no column leaves the staging.  The values agree with
         "host" up to the rounding of a float64 sum in another order; Max, Min and Alpha are equal.  A trainer on the host
         path gets eval_statistics under either value."""
-        _check_stats(stats)
-        from .group import _check_general
-        _check_general(general)
-        arrs = self._eval_inputs(batch, eps, rng)
-        gen = self._h is not None and self.fused_mode() == 3
-        if self._h is None or (gen and general != "device") or self._evaluate_on_host:
-            cols = self._evaluate_host(arrs)
-        elif stats == "device":
-            result, cols = self._evaluate_device_stats(
-                arrs, "sac_evaluate_general_stats_many" if gen else "sac_evaluate_stats_many", rows)
-            return (result, cols) if rows else result
-        else:
-            cols = self._evaluate_device(arrs, "sac_evaluate_general" if gen else "sac_evaluate")
-        stats = self._eval_stats(cols)
-        return (stats, cols) if rows else stats
+        infer.check_stats(stats)
+        infer.check_general(general)
+        return infer.evaluate_of([self], [self._eval_inputs(batch, eps, rng)], rows, general, stats)[0]
 
     def refresh_host_policy(self):
         """Mirror the trained policy D2H once per training block (acting stays on the host)."""

@@ -1,0 +1,339 @@
+"""Host side of the Python inference layer (no GPU, no library): which entry of the C ABI each call reaches (the route
+table), how a request is cut into calls of at most 1024 rows and 16 members (the window rule), and the [256, 256]
+trainer that the library built on the general step (SAC_GENERAL=1).
+
+A recording stand-in takes the place of _lib.load() and of the trainers' own library.  It implements the solo entries
+by forwarding to the *_many ones, as the library does, and logs at the *_many level only: (entry, handles, n_rows).  Its
+outputs are a function of (handle, row index) -- the row index travels in column 0 of the observations -- so a value
+that lands in the wrong slot, chunk or window is seen."""
+import ctypes as C
+
+import numpy as np
+import pytest
+
+from robosuite_benchmark_amd import FlattenMlp, TanhGaussianPolicy, TanhMlpPolicy, TD3Trainer, _lib
+from robosuite_benchmark_amd.group import act_many, evaluate_many, q_values_many, runs_general_step
+from robosuite_benchmark_amd.sac import SACTrainer
+
+O, A = 4, 2
+NET_NAMES = {v: k for k, v in _lib.TD3_NET_IDS.items()}
+
+
+class Handle:
+    """c_void_p's face: .value."""
+
+    def __init__(self, value):
+        self.value = value
+
+
+def f32_view(address, *shape):
+    return np.ctypeslib.as_array((C.c_float * int(np.prod(shape))).from_address(address)).reshape(shape)
+
+
+def addr(p):
+    return getattr(p, "value", p)
+
+
+class Lib:
+    """The entries the inference layer calls, with the C signatures.  by_handle: handle -> (trainer, step kind)."""
+
+    def __init__(self):
+        self.log, self.by_handle = [], {}
+
+    # -- what the host paths and the predicate read (not logged) --
+    def sac_trainer_step_kind(self, h):
+        return self.by_handle[h.value][1]
+
+    def sac_sync(self, h):
+        return 0
+
+    def sac_trainer_destroy(self, h):             # (SACTrainer's finaliser)
+        return 0
+
+    def sac_param_count(self, h, net):
+        return getattr(self.by_handle[h.value][0], NET_NAMES[net]).flat().size
+
+    def sac_get_params(self, h, net, p, n):
+        f32_view(addr(p), n)[...] = getattr(self.by_handle[h.value][0], NET_NAMES[net]).flat()
+        return 0
+
+    def sac_get_scalars(self, h, p):
+        return 0
+
+    def sac_policy_act(self, h, obs, det, eps, out):
+        f32_view(addr(out), A)[...] = 0.0
+        return 0
+
+    # -- the *_many entries: logged --
+    def _note(self, entry, handles, n, n_rows):
+        hs, rows = [addr(handles[k]) for k in range(n)], [int(n_rows[k]) for k in range(n)]
+        assert 1 <= n <= 16 and all(1 <= r <= 1024 for r in rows)
+        self.log.append((entry, hs, rows))
+        return hs, rows
+
+    def _act_many(self, entry, handles, n, n_rows, obs, det, eps, out):
+        for k, (h, r) in enumerate(zip(*self._note(entry, handles, n, n_rows))):
+            f32_view(addr(out[k]), r, A)[...] = value(h, f32_view(addr(obs[k]), r, O)[:, 0])[:, None]
+        return 0
+
+    def _q_many(self, entry, handles, n, n_rows, obs, act, masks, q):
+        for k, (h, r) in enumerate(zip(*self._note(entry, handles, n, n_rows))):
+            nets = bin(int(masks[k])).count("1")
+            f32_view(addr(q[k]), nets, r)[...] = value(h, f32_view(addr(obs[k]), r, O)[:, 0])[None, :] + 10000.0 * np.arange(nets)[:, None]
+        return 0
+
+    def _evaluate_many(self, entry, handles, n, n_rows, ios, sts=None):
+        ios, sts = ([x._obj] if hasattr(x, "_obj") else x for x in (ios, sts))      # (a solo caller passes byref)
+        for k, (h, r) in enumerate(zip(*self._note(entry, handles, n, n_rows))):
+            io = ios[k]
+            v = value(h, f32_view(io.obs, r, O)[:, 0])
+            if io.rows:
+                f32_view(io.rows, len(_lib.EVAL_ROWS), r)[...] = v[None, :] + 10000.0 * np.arange(len(_lib.EVAL_ROWS))[:, None]
+                for name in _lib.EVAL_ARRAYS:
+                    f32_view(getattr(io, name), r, A)[...] = v[:, None]
+            io.alpha = 0.5
+            if sts is not None:
+                v64 = v.astype(np.float64)
+                for m in sts[k].m:
+                    m.count, m.sum, m.m2, m.sumsq, m.max, m.min = r, v64.sum(), 0.0, (v64 * v64).sum(), v64.max(), v64.min()
+                sts[k].alpha, sts[k].log_alpha = 0.5, 0.0
+        return 0
+
+    def sac_evaluate_stats_many(self, *a):
+        return self._evaluate_many("sac_evaluate_stats_many", *a)
+
+    def sac_evaluate_general_stats_many(self, *a):
+        return self._evaluate_many("sac_evaluate_general_stats_many", *a)
+
+
+def value(handle, row_index):
+    """The stand-in's answer for one row of one trainer (exact in float32)."""
+    return (np.float32(handle) + np.asarray(row_index, np.float32)).astype(np.float32)
+
+
+def _many_and_solo(many, solo, impl, solo_args):
+    setattr(Lib, many, lambda self, *a: getattr(self, impl)(many, *a))
+    setattr(Lib, solo, lambda self, h, n, *a: getattr(self, many)([h], 1, [n], *solo_args(*a)))
+
+
+for _g in ("", "_general"):
+    _many_and_solo(f"sac_policy_act{_g}_many", "sac_policy_act_general" if _g else "sac_policy_act_device", "_act_many",
+                   lambda obs, det, eps, out: ([obs], [det], [eps], [out]))
+    _many_and_solo(f"sac_q_values{_g}_many", f"sac_q_values{_g}", "_q_many", lambda obs, act, mask, q: ([obs], [act], [mask], [q]))
+    _many_and_solo(f"sac_evaluate{_g}_many", f"sac_evaluate{_g}", "_evaluate_many", lambda io: (io,))
+
+
+@pytest.fixture
+def lib(monkeypatch):
+    fake = Lib()
+    monkeypatch.setattr(_lib, "load", lambda: fake)
+    return fake
+
+
+NEXT = [1000]
+
+
+def make(lib, hidden=(8, 8), kind=1, handle=True, td3=False, on_host=False):
+    """A trainer without a device: holders, host metadata, a stand-in handle that the stand-in library answers `kind`
+    for (sac_trainer_step_kind: 1 a fused step, 3 the general step)."""
+    rs = np.random.RandomState(len(hidden))
+    t = (TD3Trainer if td3 else SACTrainer).__new__(TD3Trainer if td3 else SACTrainer)
+    t.policy = TanhMlpPolicy(list(hidden), A, O, rs=rs) if td3 else TanhGaussianPolicy(list(hidden), O, A, rs=rs)
+    t.qf1, t.qf2, t.target_qf1, t.target_qf2 = (FlattenMlp(list(hidden), 1, O + A, rs=rs) for _ in range(4))
+    t.target_policy = t.policy
+    t.obs_dim, t.act_dim, t._lib, t._h, t._saved_state = O, A, lib, None, None
+    t.use_automatic_entropy_tuning, t.target_entropy, t.reward_scale, t.discount = False, 0.0, 1.0, 0.99
+    if on_host:
+        t._evaluate_on_host = True
+    if handle:
+        NEXT[0] += 8
+        t._h = Handle(NEXT[0])
+        lib.by_handle[t._h.value] = (t, kind)
+    return t
+
+
+def request(n):
+    """n rows whose column 0 is the row index: (obs, act, batch, eps)."""
+    obs = np.zeros((n, O), np.float32)
+    obs[:, 0] = np.arange(n)
+    act = np.zeros((n, A), np.float32)
+    batch = dict(observations=obs, actions=act, rewards=np.zeros(n), terminals=np.zeros(n), next_observations=obs)
+    return obs, act, batch, (act, act)
+
+
+def entries(lib):
+    got = [c[0] for c in lib.log]
+    del lib.log[:]
+    return got
+
+
+# ---- 1. the route table -----------------------------------------------------------------------------------------------------
+KINDS = {"no handle": dict(handle=False), "fused": dict(), "general": dict(hidden=(8, 8, 8), kind=3),
+         "td3": dict(td3=True), "on host": dict(on_host=True)}
+Q, QG = "sac_q_values_many", "sac_q_values_general_many"
+E = {("fused", "host"): "sac_evaluate_many", ("fused", "device"): "sac_evaluate_stats_many",
+     ("general", "host"): "sac_evaluate_general_many", ("general", "device"): "sac_evaluate_general_stats_many"}
+# (kind, general) -> the family that serves Q values / evaluation / act_many; None: no *_many call (the host, or TD3's refusal)
+ROUTES = {
+    ("no handle", "host"): (None, None, "n/a"), ("no handle", "device"): (None, None, "n/a"),
+    ("fused", "host"): ("fused", "fused", "fused"), ("fused", "device"): ("fused", "fused", "fused"),
+    ("general", "host"): (None, None, None), ("general", "device"): ("general", "general", "general"),
+    ("td3", "host"): ("fused", "refused", "fused"), ("td3", "device"): ("fused", "refused", "fused"),
+    ("on host", "host"): ("fused", None, "fused"), ("on host", "device"): ("fused", None, "fused"),
+}
+
+
+@pytest.mark.parametrize("kind,general", list(ROUTES))
+def test_route_table(lib, kind, general):
+    q_family, eval_family, act_family = ROUTES[(kind, general)]
+    t = make(lib, **KINDS[kind])
+    obs, act, batch, eps = request(3)
+    q_entry = [] if q_family is None else [dict(fused=Q, general=QG)[q_family]]
+    t.q_values(obs, act, general=general)
+    assert entries(lib) == q_entry
+    q_values_many([t], [obs], [act], [("qf1", "qf2")], general=general)
+    assert entries(lib) == q_entry
+    for stats in ("host", "device"):
+        if eval_family == "refused":
+            for call in (lambda: t.evaluate(batch, eps=eps, general=general, stats=stats),
+                         lambda: evaluate_many([t], [batch], eps=[eps], general=general, stats=stats)):
+                with pytest.raises(NotImplementedError, match="SAC objective"):
+                    call()
+            assert entries(lib) == []
+            continue
+        eval_entry = [] if eval_family is None else [E[(eval_family, stats)]]
+        t.evaluate(batch, eps=eps, general=general, stats=stats)
+        assert entries(lib) == eval_entry, stats
+        evaluate_many([t], [batch], eps=[eps], general=general, stats=stats)
+        assert entries(lib) == eval_entry, stats
+    if act_family != "n/a":                       # (acting needs a handle: GroupActor refuses a member without one)
+        act_many([t], [obs], [True], [None], general=general)
+        assert entries(lib) == ([] if act_family is None else [dict(fused="sac_policy_act_many",
+                                                                    general="sac_policy_act_general_many")[act_family]])
+        # the solo device methods address one family each, whatever the trainer is: the library refuses the other kind
+        t.policy_act_device(obs, True, None)
+        assert entries(lib) == ["sac_policy_act_many"]
+        t.policy_act_general(obs, True, None)
+        assert entries(lib) == ["sac_policy_act_general_many"]
+
+
+# ---- 2. the window rule -----------------------------------------------------------------------------------------------------
+def window_log(entry, handles, n_rows):
+    """The rule, restated: rows 0, 1024, ... of the members that still have rows, 16 members per call."""
+    want = []
+    for r0 in range(0, max(n_rows), 1024):
+        live = [i for i, n in enumerate(n_rows) if n > r0]
+        for c in range(0, len(live), 16):
+            want.append((entry, [handles[i] for i in live[c:c + 16]], [min(n_rows[i] - r0, 1024) for i in live[c:c + 16]]))
+    return want
+
+
+FAMILIES = [("fused", "host", dict()), ("general", "device", dict(hidden=(8, 8, 8), kind=3))]
+
+
+# 35 members: 28 have rows (two chunks in the first window), 14 reach the second window, 7 the third; 42 members: 33 have
+# rows, so the first window takes three chunks
+@pytest.mark.parametrize("R,members_per_call", [(35, [16, 12, 14, 7]), (42, [16, 16, 1, 16, 8])])
+@pytest.mark.parametrize("family,general,kw", FAMILIES)
+def test_q_values_many_and_evaluate_many_windows(lib, family, general, kw, R, members_per_call):
+    ts = [make(lib, **kw) for _ in range(R)]
+    hs = [t._h.value for t in ts]
+    n_rows = [(0, 1, 1024, 1025, 2049)[i % 5] for i in range(R)]
+    reqs = [request(n) for n in n_rows]
+    nets = [("qf2", "qf1") if i % 2 else ("target_qf1",) for i in range(R)]
+    q = q_values_many(ts, [r[0] for r in reqs], [r[1] for r in reqs], nets, general=general)
+    assert [len(c[1]) for c in lib.log] == members_per_call
+    assert lib.log[0][2][:4] == [1, 1024, 1024, 1024] and lib.log[-1][2] == [1] * members_per_call[-1]
+    assert lib.log == window_log(dict(fused=Q, general=QG)[family], hs, n_rows)
+    del lib.log[:]
+    for i, n in enumerate(n_rows):
+        assert q[i].shape == (len(nets[i]), n) and q[i].dtype == np.float32
+        rows = value(hs[i], np.arange(n))
+        if i % 2:                                 # asked for as (qf2, qf1): the library's rows are in ascending net order
+            assert np.array_equal(q[i][0], rows + 10000.0) and np.array_equal(q[i][1], rows), i
+        else:
+            assert np.array_equal(q[i][0], rows), i
+    for stats in ("host", "device"):
+        got = evaluate_many(ts, [r[2] for r in reqs], eps=[r[3] for r in reqs], rows=True, general=general, stats=stats)
+        assert lib.log == window_log(E[(family, stats)], hs, n_rows), stats
+        del lib.log[:]
+        for i, n in enumerate(n_rows):
+            if n == 0:
+                assert got[i] is None
+                continue
+            result, cols = got[i]
+            rows = value(hs[i], np.arange(n))
+            assert cols["q1"].shape == (n,) and np.array_equal(cols["q1"], rows) and np.array_equal(cols["y"], rows + 80000.0), i
+            assert cols["mu"].shape == (n, A) and np.array_equal(cols["a_next"][:, 1], rows) and cols["alpha"] == 0.5, i
+            assert result["Q1 Predictions Max"] == hs[i] + n - 1 and result["Q1 Predictions Min"] == hs[i], (stats, i)
+            assert result["Policy mu Mean"] == pytest.approx(hs[i] + (n - 1) / 2, rel=1e-12), (stats, i)
+        # without the columns the device statistics come from the same calls, and nothing else
+        if stats == "device":
+            plain = evaluate_many(ts, [r[2] for r in reqs], eps=[r[3] for r in reqs], general=general, stats=stats)
+            assert lib.log == window_log(E[(family, stats)], hs, n_rows)
+            del lib.log[:]
+            assert plain == [None if g is None else g[0] for g in got]
+
+
+@pytest.mark.parametrize("family,general,kw", FAMILIES)
+def test_act_many_chunks_and_its_row_limit(lib, family, general, kw):
+    ts = [make(lib, **kw) for _ in range(35)]
+    hs = [t._h.value for t in ts]
+    n_rows = [(0, 1, 1024)[i % 3] for i in range(35)]
+    obs = [request(n)[0] if n else None for n in n_rows]
+    out = act_many(ts, obs, [True] * 35, [None] * 35, general=general)
+    entry = dict(fused="sac_policy_act_many", general="sac_policy_act_general_many")[family]
+    assert [len(c[1]) for c in lib.log] == [16, 7] and lib.log[0][2][:3] == [1, 1024, 1]
+    assert lib.log == window_log(entry, hs, n_rows)
+    for i, n in enumerate(n_rows):
+        assert out[i].shape == (n, A) and np.array_equal(out[i][:, 0], value(hs[i], np.arange(n))), i
+    del lib.log[:]
+    with pytest.raises(RuntimeError, match="member 1: 1025 rows"):
+        act_many(ts[:2], [obs[1], request(1025)[0]], [True] * 2, [None] * 2, general=general)
+    assert lib.log == []
+
+
+@pytest.mark.parametrize("n,calls", [(1, 1), (1024, 1), (1025, 2), (2049, 3)])
+@pytest.mark.parametrize("family,general,kw", FAMILIES)
+def test_solo_methods_are_windows_of_one_member(lib, family, general, kw, n, calls):
+    t = make(lib, **kw)
+    h = t._h.value
+    obs, act, batch, eps = request(n)
+    want = [([h], [min(n - r0, 1024)]) for r0 in range(0, n, 1024)]
+    assert len(want) == calls
+    rows = value(h, np.arange(n))
+    q = t.q_values(obs, act, nets=("target_qf2", "qf1"), general=general)
+    assert [c[1:] for c in lib.log] == want and {c[0] for c in lib.log} == {dict(fused=Q, general=QG)[family]}
+    assert np.array_equal(q[1], rows) and np.array_equal(q[0], rows + 10000.0)
+    del lib.log[:]
+    for stats in ("host", "device"):
+        result, cols = t.evaluate(batch, eps=eps, rows=True, general=general, stats=stats)
+        assert [c[1:] for c in lib.log] == want and {c[0] for c in lib.log} == {E[(family, stats)]}
+        assert np.array_equal(cols["q2"], rows + 10000.0) and result["Q1 Predictions Max"] == h + n - 1
+        del lib.log[:]
+    for act_fn, entry in ((t.policy_act_device, "sac_policy_act_many"), (t.policy_act_general, "sac_policy_act_general_many")):
+        a = act_fn(obs, True, None)
+        assert [c[1:] for c in lib.log] == want and {c[0] for c in lib.log} == {entry}
+        assert a.shape == (n, A) and np.array_equal(a[:, 1], rows)
+        del lib.log[:]
+
+
+# ---- 3. the [256, 256] trainer on the general step --------------------------------------------------------------------------
+@pytest.mark.parametrize("general,q_entry,eval_entry,act_entry",
+                         [("host", [], [], []),
+                          ("device", [QG], ["sac_evaluate_general_many"], ["sac_policy_act_general_many"])])
+def test_fused_shapes_that_the_library_built_on_the_general_step_are_routed_as_general(lib, general, q_entry, eval_entry, act_entry):
+    t = make(lib, hidden=(256, 256), kind=3)
+    obs, act, batch, eps = request(3)
+    t.q_values(obs, act, general=general)
+    assert entries(lib) == q_entry
+    q_values_many([t], [obs], [act], [("qf1", "qf2")], general=general)
+    assert entries(lib) == q_entry
+    t.evaluate(batch, eps=eps, general=general)
+    assert entries(lib) == eval_entry
+    evaluate_many([t], [batch], eps=[eps], general=general)
+    assert entries(lib) == eval_entry
+    act_many([t], [obs], [True], [None], general=general)
+    assert entries(lib) == act_entry
+    # one predicate: what the library built, not what the hidden sizes say
+    assert runs_general_step(t) and t.runs_general_step() and not runs_general_step(make(lib, hidden=(256, 256), handle=False))
