@@ -478,6 +478,23 @@ int sac_evaluate_stats_many(sac_trainer_t *const *trainers, int n_trainers, cons
                             sac_eval_stats_t *stats);
 int sac_evaluate_general_stats_many(sac_trainer_t *const *trainers, int n_trainers, const int32_t *n_rows, sac_eval_io_t *io,
                                     sac_eval_stats_t *stats);
+/* The same evaluations on REPLAY rows IN PLACE: the five input arrays of member i are storage rows src[i].idx[0 .. n_rows[i])
+ * of the replay buffer src[i].buf, copied on the device (k_eval_rows, csrc/sac_eval_rows.h: one launch in front of the
+ * evaluation's kernels) from the replay storage into the staging the evaluation reads (mapped pinned host memory, as
+ * for the entries above) -- no synchronised gather to the host, no host conversion and no memcpy into the staging.  io[i].obs / act / rew / term / next_obs are ignored and may be NULL; eps and eps_next still come from the
+ * host.  stats NULL: the contract of sac_evaluate_many / sac_evaluate_general_many (io[i].rows needed); with stats that of
+ * the *_stats_many entries (rows may be NULL).  The columns and the moment records are bit for bit those of the same
+ * entry on the rows sac_gather returns for the same indices.  A storage row is an index into [0, sac_buffer_size): the
+ * rows as they lie, not in insertion order.  Two members may name one buffer.  The rows are read behind every insert
+ * pending on the buffer's stream (an event, no host wait), and the buffer is only read: its generator, bound host words,
+ * read-ahead and loop speculation stay as they are.  Refused in addition (<0, sac_last_error, nothing launched, no
+ * output written), each naming the member: a null buf or idx, a buffer on another device, buffer dims other than the
+ * trainer's, an empty buffer, an index outside [0, sac_buffer_size). */
+typedef struct { sac_buffer_t *buf; const int64_t *idx; } sac_eval_src_t;   /* idx: n_rows[i] storage rows, host */
+int sac_evaluate_replay_many(sac_trainer_t *const *trainers, int n_trainers, const int32_t *n_rows,
+                             const sac_eval_src_t *src, sac_eval_io_t *io, sac_eval_stats_t *stats /* may be NULL */);
+int sac_evaluate_replay_general_many(sac_trainer_t *const *trainers, int n_trainers, const int32_t *n_rows,
+                                     const sac_eval_src_t *src, sac_eval_io_t *io, sac_eval_stats_t *stats /* may be NULL */);
 
 /* ------------------------------------------------------------------------------------------
  * Trainer groups: several runs of one configuration (the reference's seed sweeps, /root/reference/launch_jobs.sh)

@@ -89,6 +89,11 @@ class SacEvalMoment(C.Structure):
     _fields_ = [(k, C.c_double) for k in EVAL_MOMENT_FIELDS]
 
 
+class SacEvalSrc(C.Structure):
+    """sac_eval_src_t"""
+    _fields_ = [("buf", C.c_void_p), ("idx", C.c_void_p)]
+
+
 class SacEvalStats(C.Structure):
     """sac_eval_stats_t"""
     _fields_ = [("m", SacEvalMoment * len(EVAL_MOMENTS)), ("alpha", C.c_double), ("log_alpha", C.c_double)]
@@ -170,6 +175,8 @@ SYMBOLS = {
     "sac_evaluate_general_many": (C.c_int, [_P, C.c_int, _P, _P]),
     "sac_evaluate_stats_many": (C.c_int, [_P, C.c_int, _P, _P, _P]),
     "sac_evaluate_general_stats_many": (C.c_int, [_P, C.c_int, _P, _P, _P]),
+    "sac_evaluate_replay_many": (C.c_int, [_P, C.c_int, _P, _P, _P, _P]),
+    "sac_evaluate_replay_general_many": (C.c_int, [_P, C.c_int, _P, _P, _P, _P]),
     "sac_group_create": (C.c_int, [C.POINTER(_P), _P, C.c_int]),
     "td3_group_create": (C.c_int, [C.POINTER(_P), _P, C.c_int]),
     "sac_group_create_mixed": (C.c_int, [C.POINTER(_P), _P, C.c_int]),

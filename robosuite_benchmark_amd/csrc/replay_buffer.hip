@@ -765,6 +765,7 @@ int sac_buffer_destroy(sac_buffer_t *b) {
     (void)hipSetDevice(b->device);
     if (b->stream) (void)hipStreamSynchronize(b->stream);
     if (b->spec_ev) (void)hipEventDestroy(b->spec_ev);
+    if (b->eval_ev) (void)hipEventDestroy(b->eval_ev);
     for (void *p : {(void *)b->obs, (void *)b->nobs, (void *)b->act, (void *)b->rew, (void *)b->term,
                     (void *)b->d_rng, (void *)b->d_idx, (void *)b->d_slots})
         (void)hipFree(p);

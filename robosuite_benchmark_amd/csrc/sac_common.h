@@ -133,6 +133,7 @@ struct sac_buffer {
     bool ing_busy[2] = {false, false};
     uint64_t ing_next = 0;
     hipEvent_t ev[4] = {nullptr, nullptr, nullptr, nullptr};
+    hipEvent_t eval_ev = nullptr;                    // sac_evaluate_replay*_many: behind what is pending here when the call reads the rows
     // device-resident batches of the stepwise interface (sac_random_batch_device): a ring of NRING slots; batch
     // number n lives in slot n % NRING until batch n + NRING is drawn
     static constexpr int NRING = 64;                 // (a token stays valid until at least NRING - RA_MAX = 48 more batches have been drawn)

@@ -199,10 +199,14 @@ static_assert((int)EVAL_ROWS_N == (int)SAC_EVAL_ROWS_N && (int)EVAL_Y == (int)SA
 
 // sac_evaluate_many (stats null) and sac_evaluate_stats_many: with stats, mu and log_std always have their place in the
 // staging (k_eval_moments reads them there; only the copy to the caller depends on what was asked for), k_eval_moments
-// runs behind k_eval in front of the wait, and a null io[i].rows is taken
+// runs behind k_eval in front of the wait, and a null io[i].rows is taken.  sac_evaluate_replay_many (src not null): the
+// five input parts of the staging are filled on the device, by k_eval_rows (sac_eval_rows.h) in front of k_eval, from
+// src[i]'s replay storage instead of io[i]'s arrays; everything else is the same body
 static int evaluate_many(const InferEntry &IE, sac_trainer_t *const *trainers, int n_trainers, const int32_t *n_rows,
-                         sac_eval_io_t *io, sac_eval_stats_t *stats) {
-    if (int rc = infer_admit(IE, trainers, n_trainers, n_rows, [&](int i) { return eval_admit_io(io[i], i, !stats); })) return rc;
+                         sac_eval_io_t *io, sac_eval_stats_t *stats, const sac_eval_src_t *src = nullptr) {
+    if (int rc = infer_admit(IE, trainers, n_trainers, n_rows, [&](int i) {
+            return src ? eval_rows_admit(io[i], src[i], trainers[i], i, n_rows[i], !stats) : eval_admit_io(io[i], i, !stats);
+        })) return rc;
     sac_trainer *t0 = trainers[0];
     float alpha[SAC_GROUP_MAX], log_alpha[SAC_GROUP_MAX];
     if (eval_read_alpha(trainers, n_trainers, n_rows, alpha, stats ? log_alpha : nullptr)) return -1;
@@ -221,10 +225,12 @@ static int evaluate_many(const InferEntry &IE, sac_trainer_t *const *trainers, i
     }
     MomentsStage MS;
     if (stats) moments_carve(bytes, MS, n_trainers);
+    EvalRowsStage RS;
+    if (src) eval_rows_carve(bytes, RS, n_trainers, n_rows);
     if (act_stage_reserve(t0, bytes)) return -1;
     const sac_trainer::ActStage &S = t0->act_stage;
     EvalMember *tab = reinterpret_cast<EvalMember *>(S.h);
-    int wgs = 0, m = 0, kq_max = 0;
+    int wgs = 0, m = 0, kq_max = 0, row_wgs = 0;
     for (int i = 0; i < n_trainers; ++i) {
         const sac_trainer *t = trainers[i];
         if (n_rows[i] == 0) continue;
@@ -232,13 +238,16 @@ static int evaluate_many(const InferEntry &IE, sac_trainer_t *const *trainers, i
         const size_t n = (size_t)n_rows[i], nO = n * t->O, nA = n * t->A;
         EvalMember &M = tab[m++];
         for (int k = 0; k < 5; ++k) M.P[k] = t->net[SAC_NET_POLICY + k].P;
-        auto in = [&](int k, const float *src, size_t count) {
-            memcpy(S.h + off[i][k], src, sizeof(float) * count);
+        auto in = [&](int k, const float *from, size_t count) {          // (from null: k_eval_rows fills the part)
+            if (from) memcpy(S.h + off[i][k], from, sizeof(float) * count);
             return reinterpret_cast<const float *>(S.d + off[i][k]);
         };
-        M.obs = in(0, E.obs, nO); M.act = in(1, E.act, nA); M.rew = in(2, E.rew, n); M.term = in(3, E.term, n);
-        M.nobs = in(4, E.next_obs, nO); M.eps = in(5, E.eps, nA); M.eps_next = in(6, E.eps_next, nA);
         auto out = [&](int k, bool asked) { return asked ? reinterpret_cast<float *>(S.d + off[i][k]) : nullptr; };
+        M.obs = in(0, src ? nullptr : E.obs, nO); M.act = in(1, src ? nullptr : E.act, nA);
+        M.rew = in(2, src ? nullptr : E.rew, n); M.term = in(3, src ? nullptr : E.term, n);
+        M.nobs = in(4, src ? nullptr : E.next_obs, nO); M.eps = in(5, E.eps, nA); M.eps_next = in(6, E.eps_next, nA);
+        if (src) row_wgs += eval_rows_member(S, RS, m - 1, i, row_wgs, src[i], n_rows[i], out(0, true), out(1, true),
+                                             out(2, true), out(3, true), out(4, true));
         M.rows = out(7, true); M.mu = out(8, E.mu || stats); M.log_std = out(9, E.log_std || stats);
         M.a_new = out(10, E.a_new); M.a_next = out(11, E.a_next);
         if (stats) moments_member(S, MS, m - 1, i, M.rows, M.mu, M.log_std, n_rows[i], t->A);
@@ -255,6 +264,7 @@ static int evaluate_many(const InferEntry &IE, sac_trainer_t *const *trainers, i
     }
     const size_t lds = eval_lds_bytes(kq_max);
     if (infer_raise_lds(reinterpret_cast<const void *>(k_eval), g_eval_lds_raised, t0->device, lds, eval_lds_bytes(512))) return -1;
+    if (src && eval_rows_launch(t0, RS, m, row_wgs, src, n_trainers, n_rows)) return -1;
     hipLaunchKernelGGL(k_eval, dim3(wgs), dim3(256), lds, t0->stream, reinterpret_cast<const EvalMember *>(S.d), m);
     SAC_HIP(hipGetLastError());
     if (stats && moments_launch(t0, MS, m)) return -1;
@@ -287,6 +297,14 @@ int sac_evaluate_stats_many(sac_trainer_t *const *trainers, int n_trainers, cons
     const InferEntry IE = {"sac_evaluate_stats_many", false, true, "device evaluation",
                            "sac_evaluate_general_stats_many is the entry", "evaluate"};
     return evaluate_many(IE, trainers, n_trainers, n_rows, io, stats);
+}
+
+int sac_evaluate_replay_many(sac_trainer_t *const *trainers, int n_trainers, const int32_t *n_rows, const sac_eval_src_t *src,
+                             sac_eval_io_t *io, sac_eval_stats_t *stats) {
+    SAC_REQUIRE(trainers && n_rows && src && io, "bad arguments to sac_evaluate_replay_many");
+    const InferEntry IE = {"sac_evaluate_replay_many", false, true, "device evaluation",
+                           "sac_evaluate_replay_general_many is the entry", "evaluate"};
+    return evaluate_many(IE, trainers, n_trainers, n_rows, io, stats, src);
 }
 
 int sac_evaluate(sac_trainer_t *t, int64_t n, sac_eval_io_t *io) {

@@ -117,10 +117,14 @@ __global__ __launch_bounds__(EG_YROWS) void k_eval_y(const EvalYMember *__restri
 
 // sac_evaluate_general_many (stats null) and sac_evaluate_general_stats_many: with stats, mu and log_std always have
 // their place in the staging, k_eval_moments (sac_eval_moments.h) runs behind k_eval_y in front of the wait, and a null
-// io[i].rows is taken -- as evaluate_many (sac_eval.h) does for the fused shapes
+// io[i].rows is taken -- as evaluate_many (sac_eval.h) does for the fused shapes.  sac_evaluate_replay_general_many (src
+// not null): k_eval_rows (sac_eval_rows.h) fills the five input parts from src[i]'s replay storage in front of the first
+// layer launch, as there
 static int evaluate_general_many(const InferEntry &IE, sac_trainer_t *const *trainers, int n_trainers, const int32_t *n_rows,
-                                 sac_eval_io_t *io, sac_eval_stats_t *stats) {
-    if (int rc = infer_admit(IE, trainers, n_trainers, n_rows, [&](int i) { return eval_admit_io(io[i], i, !stats); })) return rc;
+                                 sac_eval_io_t *io, sac_eval_stats_t *stats, const sac_eval_src_t *src = nullptr) {
+    if (int rc = infer_admit(IE, trainers, n_trainers, n_rows, [&](int i) {
+            return src ? eval_rows_admit(io[i], src[i], trainers[i], i, n_rows[i], !stats) : eval_admit_io(io[i], i, !stats);
+        })) return rc;
     sac_trainer *t0 = trainers[0];
     float alpha[SAC_GROUP_MAX], log_alpha[SAC_GROUP_MAX];
     if (eval_read_alpha(trainers, n_trainers, n_rows, alpha, stats ? log_alpha : nullptr)) return -1;
@@ -147,11 +151,13 @@ static int evaluate_general_many(const InferEntry &IE, sac_trainer_t *const *tra
     }
     MomentsStage MS;
     if (stats) moments_carve(bytes, MS, n_trainers);
+    EvalRowsStage RS;
+    if (src) eval_rows_carve(bytes, RS, n_trainers, n_rows);
     if (act_stage_reserve(t0, bytes)) return -1;
     const sac_trainer::ActStage &S = t0->act_stage;
     EvalLayerJob *tab = reinterpret_cast<EvalLayerJob *>(S.h);
     EvalYMember *ytab = reinterpret_cast<EvalYMember *>(S.h + tab_bytes);
-    int njobs[EG_LAUNCHES] = {}, blocks[EG_LAUNCHES] = {}, yblocks = 0, m = 0;
+    int njobs[EG_LAUNCHES] = {}, blocks[EG_LAUNCHES] = {}, yblocks = 0, m = 0, row_wgs = 0;
     for (int i = 0; i < n_trainers; ++i) {
         const sac_trainer *t = trainers[i];
         if (n_rows[i] == 0) continue;
@@ -159,9 +165,13 @@ static int evaluate_general_many(const InferEntry &IE, sac_trainer_t *const *tra
         const int n = n_rows[i], rbs = (n + RB - 1) / RB;
         const size_t nO = (size_t)n * t->O, nA = (size_t)n * t->A;
         auto dev = [&](int k) { return reinterpret_cast<float *>(S.d + off[i][k]); };
-        auto in = [&](int k, const float *src, size_t count) { memcpy(S.h + off[i][k], src, sizeof(float) * count); };
-        in(P_OBS, E.obs, nO); in(P_ACT, E.act, nA); in(P_REW, E.rew, n); in(P_TERM, E.term, n);
-        in(P_NOBS, E.next_obs, nO); in(P_EPS, E.eps, nA); in(P_EPS_NEXT, E.eps_next, nA);
+        auto in = [&](int k, const float *from, size_t count) { memcpy(S.h + off[i][k], from, sizeof(float) * count); };
+        if (src) {
+            row_wgs += eval_rows_member(S, RS, m, i, row_wgs, src[i], n, dev(P_OBS), dev(P_ACT), dev(P_REW), dev(P_TERM), dev(P_NOBS));
+        } else {
+            in(P_OBS, E.obs, nO); in(P_ACT, E.act, nA); in(P_REW, E.rew, n); in(P_TERM, E.term, n); in(P_NOBS, E.next_obs, nO);
+        }
+        in(P_EPS, E.eps, nA); in(P_EPS_NEXT, E.eps_next, nA);
         float *rows = dev(P_ROWS);
         auto job = [&](int launch, const GenNet &N, const GenLayer &L) -> EvalLayerJob & {
             EvalLayerJob &J = tab[(size_t)launch * EG_JOBS + njobs[launch]++];
@@ -216,6 +226,7 @@ static int evaluate_general_many(const InferEntry &IE, sac_trainer_t *const *tra
         M.alpha = alpha[i]; M.rs = t->cfg.reward_scale; M.discount = t->cfg.discount; M.pad = 0;
         yblocks += (n + EG_YROWS - 1) / EG_YROWS;
     }
+    if (src && eval_rows_launch(t0, RS, m, row_wgs, src, n_trainers, n_rows)) return -1;
     const EvalLayerJob *d_tab = reinterpret_cast<const EvalLayerJob *>(S.d);
     for (int l = 0; l < LP + LQ; ++l) {
         if (l < LP) hipLaunchKernelGGL(k_eval_layer<false>, dim3(blocks[l]), dim3(256), 0, t0->stream, d_tab + (size_t)l * EG_JOBS, njobs[l]);
@@ -255,6 +266,14 @@ int sac_evaluate_general_stats_many(sac_trainer_t *const *trainers, int n_traine
     const InferEntry IE = {"sac_evaluate_general_stats_many", true, true, "device evaluation",
                            "sac_evaluate_stats_many is its entry, sac_evaluate_general_stats_many serves the general step", "evaluate"};
     return evaluate_general_many(IE, trainers, n_trainers, n_rows, io, stats);
+}
+
+int sac_evaluate_replay_general_many(sac_trainer_t *const *trainers, int n_trainers, const int32_t *n_rows,
+                                     const sac_eval_src_t *src, sac_eval_io_t *io, sac_eval_stats_t *stats) {
+    SAC_REQUIRE(trainers && n_rows && src && io, "bad arguments to sac_evaluate_replay_general_many");
+    const InferEntry IE = {"sac_evaluate_replay_general_many", true, true, "device evaluation",
+                           "sac_evaluate_replay_many is its entry, sac_evaluate_replay_general_many serves the general step", "evaluate"};
+    return evaluate_general_many(IE, trainers, n_trainers, n_rows, io, stats, src);
 }
 
 int sac_evaluate_general(sac_trainer_t *t, int64_t n, sac_eval_io_t *io) {

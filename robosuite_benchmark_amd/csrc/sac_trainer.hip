@@ -2363,6 +2363,7 @@ int stage_batches(sac_trainer *t, sac_buffer *b, int64_t n_steps) {
 #include "sac_act.h"
 #include "sac_qval.h"
 #include "sac_eval_moments.h"
+#include "sac_eval_rows.h"
 #include "sac_eval.h"
 #include "sac_act_general.h"
 #include "sac_qval_general.h"

@@ -24,7 +24,7 @@ from .networks import (FlattenMlp, GaussianStrategy, MakeDeterministic, PolicyWr
 from .replay_buffer import EnvReplayBuffer
 from .group import (ArchSACTrainerGroup, ArchTD3TrainerGroup, GroupActor, MixedSACTrainerGroup, MixedTD3TrainerGroup,
                     MlpSACTrainerGroup, MlpTD3TrainerGroup, SACTrainerGroup, TD3TrainerGroup, act_many,
-                    evaluate_many, q_values_many, runs_general_step)
+                    evaluate_many, evaluate_replay_many, q_values_many, runs_general_step)
 from .infer import check_general, check_stats
 from .sac import SACTrainer, eval_statistics
 from .td3 import TD3Trainer
@@ -384,6 +384,53 @@ def _group_validation(runs, epoch, eval_general="host", eval_stats="host"):
     return [_validation_columns(s, b) for s, b in zip(stats, batches)]
 
 
+REPLAY_STREAM = 0x52504C          # "RPL": the third seed word of an epoch's replay-evaluation draws
+
+
+def check_replay_eval(replay_eval):
+    if isinstance(replay_eval, bool) or not isinstance(replay_eval, (int, np.integer)) or replay_eval < 0:
+        raise RuntimeError(f"replay_eval is a row count (0: off), got {replay_eval!r}")
+    return int(replay_eval)
+
+
+def _replay_rows(replay_eval, buf):
+    """The replay rows of an epoch's evaluation: min(replay_eval, buffer size)."""
+    return min(int(replay_eval), int(buf.num_steps_can_sample()))
+
+
+def _replay_rng(seed, epoch):
+    """The generator of a run's replay evaluation in `epoch` (the indices, then eps, then eps_next): a function of
+    (seed, epoch) alone, so nothing needs checkpointing and a resumed run logs the same rows."""
+    return np.random.RandomState([int(seed) & 0xFFFFFFFF, int(epoch), REPLAY_STREAM])
+
+
+def _replay_columns(stats, n):
+    """replay/<key> for every key of SACTrainer.evaluate, and replay/Num Transitions."""
+    d = OrderedDict()
+    if stats is None:                                         # (an empty buffer this epoch: the columns stay, empty)
+        z = np.zeros((1, 1))
+        stats = OrderedDict((k, float("nan")) for k in eval_statistics(np.zeros((9, 1)), z, z, 1.0, 0.0, 0.0, False))
+    d.update(("replay/" + k, v) for k, v in stats.items())
+    d["replay/Num Transitions"] = int(n)
+    return d
+
+
+def _refuse_td3_replay_eval(variant, what):
+    if variant.get("algorithm", "SAC") == "TD3":
+        raise RuntimeError(f"{what}(replay_eval=N): the replay evaluation computes the SAC objective "
+                           "(SACTrainer.evaluate_replay); a TD3 variant has no such evaluation")
+
+
+def _group_replay_eval(runs, epoch, replay_eval, eval_general="host", eval_stats="host"):
+    """_replay_columns of every run's replay rows of this epoch, all runs from ONE evaluate_replay_many call (eval_general
+    and eval_stats as for _group_validation)."""
+    ns = [_replay_rows(replay_eval, r["buf"]) for r in runs]
+    stats = evaluate_replay_many([r["trainer"] for r in runs], [r["buf"] for r in runs], n=ns,
+                                 rngs=[_replay_rng(r["seed"], epoch) for r in runs], **_q_general_kw(eval_general),
+                                 **_eval_stats_kw(eval_stats)) if any(ns) else [None] * len(runs)
+    return [_replay_columns(s, n) for s, n in zip(stats, ns)]
+
+
 def _rs_pack(rs):
     st = rs.get_state()
     return dict(key=[int(x) for x in st[1]], pos=int(st[2]), has_gauss=int(st[3]), cached=float(st[4]))
@@ -407,7 +454,7 @@ def _progress_row(buf, trainer, expl, evalc, ak):
 
 def experiment(variant, log_dir=None, seed=1, obs_dim=None, action_dim=None, num_epochs=None, device=0,
                fused_loop=True, quiet=False, checkpoint_dir=None, resume=False, acting="host", q_diagnostics=False,
-               q_general="host", validation=False, eval_general="host", eval_stats="host"):
+               q_general="host", validation=False, eval_general="host", eval_stats="host", replay_eval=0):
     """variant.json -> training run.  Returns the list of progress rows (also written to
     <log_dir>/progress.csv when log_dir is given).
 
@@ -444,14 +491,26 @@ def experiment(variant, log_dir=None, seed=1, obs_dim=None, action_dim=None, num
     and for a run with the fused kernels' shapes, it has no effect.  eval_stats ("host", the default, or "device") is
     evaluate's `stats`: where the statistics of a run that is evaluated on the device are reduced -- eval_statistics on
     the columns copied out, or k_eval_moments on the device (the same columns of progress.csv, equal up to the rounding
-    of a float64 sum in another order).  Without validation it has no effect."""
+    of a float64 sum in another order).  Without validation and replay_eval it has no effect.
+
+    replay_eval=N > 0: every epoch, at the point where validation is taken (behind it, in front of the exploration paths
+    and the training block), the same objectives are evaluated on min(N, buffer size) rows of the REPLAY buffer in place
+    (trainer.evaluate_replay: a kernel copies the rows into the evaluation's staging, no gather to the host) -- the figure validation/QF1 Loss stands next to, at the
+    same parameters.  Indices and N(0,1) draws come from RandomState([seed, epoch, 0x52504C]): nothing to checkpoint,
+    and a resumed run logs the same rows.  The row gains replay/<key> for every key of evaluate and
+    replay/Num Transitions, behind the validation columns and in front of time/*; the time counts under
+    `time/evaluation sampling (s)`.  eval_general and eval_stats apply to it as to validation.  A TD3 variant is
+    refused.  With 0 (the default), the row, every generator and every column are exactly what they were."""
     check_stats(eval_stats)
     check_acting(acting)
     check_general(q_general)
     check_general(eval_general)
+    replay_eval = check_replay_eval(replay_eval)
     validate(variant)
     if validation:
         _refuse_td3_validation(variant, "experiment")
+    if replay_eval:
+        _refuse_td3_replay_eval(variant, "experiment")
     np.random.seed(seed)                                          # scripts/train.py:112 (args.seed, not variant seed)
     O, A = env_dims(variant["expl_environment_kwargs"], obs_dim, action_dim)
     ak, tk = variant["algorithm_kwargs"], variant["trainer_kwargs"]
@@ -511,6 +570,11 @@ def experiment(variant, log_dir=None, seed=1, obs_dim=None, action_dim=None, num
             v_info = _validation_columns(None if vb is None else trainer.evaluate(vb, eps=_validation_eps(seed, epoch, vb, A),
                                                                                   **_q_general_kw(eval_general),
                                                                                   **_eval_stats_kw(eval_stats)), vb)
+        r_info = None
+        if replay_eval:
+            rn = _replay_rows(replay_eval, buf)
+            r_info = _replay_columns(None if rn == 0 else trainer.evaluate_replay(
+                buf, n=rn, rng=_replay_rng(seed, epoch), **_q_general_kw(eval_general), **_eval_stats_kw(eval_stats)), rn)
         t1 = time.time()
         new_paths = expl.collect_new_paths(ak["expl_max_path_length"], ak["num_expl_steps_per_train_loop"], False)
         t2 = time.time()
@@ -529,6 +593,8 @@ def experiment(variant, log_dir=None, seed=1, obs_dim=None, action_dim=None, num
             row.update(q_info)
         if v_info is not None:
             row.update(v_info)
+        if r_info is not None:
+            row.update(r_info)
         trainer.end_epoch(epoch); buf.end_epoch(epoch); expl.end_epoch(epoch); evalc.end_epoch(epoch)
         t5 = time.time()
         if checkpoint_dir:
@@ -667,7 +733,7 @@ def _group_q_information(runs, q_general="host"):
 
 def _group_epochs(runs, train_block, n_epochs, n_train, log_dir, quiet, what, ck=None, first_epoch=0, acting="host",
                   sessions=True, general_sessions=None, q_diagnostics=False, q_general="host", validation=False,
-                  eval_general="host", eval_stats="host"):
+                  eval_general="host", eval_stats="host", replay_eval=0):
     """The epoch loop of a grouped experiment: each run collects its paths, then train_block() trains every run at once,
     then every run ends its epoch, the group is saved (with a GroupCheckpoint `ck`), and each run writes its row (to
     <log_dir>/<run["sub"]>/progress.csv with log_dir; appended to after a resume).
@@ -682,7 +748,12 @@ def _group_epochs(runs, train_block, n_epochs, n_train, log_dir, quiet, what, ck
     time/evaluation sampling (s); q_general is q_values_many's `general` for that call.
     validation=True: as experiment()'s, ALL runs on their evaluation paths from one evaluate_many call per epoch, at the
     same place and with the same accounting of its time; eval_general is evaluate_many's `general` for that call and
-    eval_stats its `stats`."""
+    eval_stats its `stats`.
+    replay_eval=N > 0: as experiment()'s, ALL runs on rows of their replay buffers from one evaluate_replay_many call per
+    epoch, in front of the epoch's exploration paths and the training block (each buffer as the run's own experiment()
+    sees it there); eval_general and eval_stats apply to it too.  Its time is added to every run's
+    time/evaluation sampling (s), and, where the runs collect one after the other and the call stands in front of them
+    all, to every run's time/epoch (s) as well: a row's phases stay inside its epoch."""
     t_start = time.time()
     lockstep = acting != "host"
     lock_kw = dict(sessions=sessions, general="device" if acting == "device_all" else "host", general_sessions=general_sessions)
@@ -697,6 +768,7 @@ def _group_epochs(runs, train_block, n_epochs, n_train, log_dir, quiet, what, ck
                                              for r in runs])
                 q_infos = _group_q_information(runs, q_general) if q_diagnostics else None
                 v_infos = _group_validation(runs, epoch, eval_general, eval_stats) if validation else None
+                r_infos = _group_replay_eval(runs, epoch, replay_eval, eval_general, eval_stats) if replay_eval else None
                 t1 = time.time()
                 new = lock_expl.collect_new_paths([(r["ak"]["expl_max_path_length"],
                                                     r["ak"]["num_expl_steps_per_train_loop"], False) for r in runs])
@@ -705,6 +777,11 @@ def _group_epochs(runs, train_block, n_epochs, n_train, log_dir, quiet, what, ck
                     s0 = time.time()
                     r["buf"].add_paths(new_paths)
                     times.append((t0, t1 - t0, t2 - t1, time.time() - s0))
+            r_s = 0.0
+            if replay_eval and not lockstep:                  # (in front of every run's new rows: the buffers of experiment())
+                s0 = time.time()
+                r_infos = _group_replay_eval(runs, epoch, replay_eval, eval_general, eval_stats)
+                r_s = time.time() - s0
             for r in runs if not lockstep else ():
                 ak = r["ak"]
                 t0 = time.time()
@@ -713,7 +790,9 @@ def _group_epochs(runs, train_block, n_epochs, n_train, log_dir, quiet, what, ck
                 new_paths = r["expl"].collect_new_paths(ak["expl_max_path_length"], ak["num_expl_steps_per_train_loop"], False)
                 t2 = time.time()
                 r["buf"].add_paths(new_paths)
-                times.append((t0, t1 - t0, t2 - t1, time.time() - t2))
+                # (the replay evaluation stood in front of every run's t0: each run's epoch starts that much earlier, so
+                # that its time/evaluation sampling (s) lies inside its time/epoch (s))
+                times.append((t0 - r_s, t1 - t0 + r_s, t2 - t1, time.time() - t2))
             if q_diagnostics and not lockstep:                # (nobody has trained since the first run's evaluation paths)
                 s0 = time.time()
                 q_infos = _group_q_information(runs, q_general)
@@ -734,6 +813,8 @@ def _group_epochs(runs, train_block, n_epochs, n_train, log_dir, quiet, what, ck
                     row.update(q_infos[len(ended)])
                 if validation:
                     row.update(v_infos[len(ended)])
+                if replay_eval:
+                    row.update(r_infos[len(ended)])
                 for x in (r["trainer"], r["buf"], r["expl"], r["evalc"]):
                     x.end_epoch(epoch)
                 ended.append((row, time.time()))
@@ -780,7 +861,7 @@ def _group_epochs(runs, train_block, n_epochs, n_train, log_dir, quiet, what, ck
 def experiment_group(variant, seeds, log_dir=None, num_epochs=None, obs_dim=None, action_dim=None, device=0,
                      quiet=False, checkpoint_dir=None, resume=False, chunk_rows=DEFAULT_CHUNK_ROWS, acting="host", sessions=True,
                      general_sessions=None, q_diagnostics=False, q_general="host", validation=False,
-                     eval_general="host", eval_stats="host"):
+                     eval_general="host", eval_stats="host", replay_eval=0):
     """One configuration, several seeds, one process: each seed is the run ``experiment(variant, seed=s)`` would make --
     its own synthetic environments, collectors, weights and replay buffer -- and every epoch's training block is ONE
     SACTrainerGroup.train_loop (TD3 variants: TD3TrainerGroup; hidden sizes other than two layers of at most 256 units:
@@ -807,13 +888,18 @@ def experiment_group(variant, seeds, log_dir=None, num_epochs=None, obs_dim=None
     validation=True: experiment()'s validation/ columns for every seed, all seeds from one evaluate_many call per epoch;
     each seed's rows are those of experiment(variant, seed=s, validation=True).  A TD3 variant is refused.
     eval_general as for experiment() (general-step seeds: one sac_evaluate_general_many call per 16 of them with "device"),
-    eval_stats too (the seeds evaluated on the device: their statistics from the same call, sac_evaluate_stats_many)."""
+    eval_stats too (the seeds evaluated on the device: their statistics from the same call, sac_evaluate_stats_many).
+    replay_eval=N: experiment()'s replay/ columns for every seed, all seeds from one evaluate_replay_many call per epoch;
+    each seed's columns are those of experiment(variant, seed=s, replay_eval=N).  A TD3 variant is refused."""
     check_stats(eval_stats)
     check_acting(acting)
     check_general(q_general)
     check_general(eval_general)
+    replay_eval = check_replay_eval(replay_eval)
     if validation:
         _refuse_td3_validation(variant, "experiment_group")
+    if replay_eval:
+        _refuse_td3_replay_eval(variant, "experiment_group")
     if resume and not checkpoint_dir:
         raise RuntimeError("experiment_group(resume=True) needs the checkpoint_dir to resume from")
     validate(variant)
@@ -839,7 +925,8 @@ def experiment_group(variant, seeds, log_dir=None, num_epochs=None, obs_dim=None
         train_block = lambda: group.train_loop([r["buf"] for r in runs], n_train, batch_size=ak["batch_size"])  # noqa: E731
     _group_epochs(runs, train_block,
                   num_epochs if num_epochs is not None else ak["num_epochs"], n_train, log_dir, quiet, "seeds", ck,
-                  first_epoch, acting, sessions, general_sessions, q_diagnostics, q_general, validation, eval_general, eval_stats)
+                  first_epoch, acting, sessions, general_sessions, q_diagnostics, q_general, validation, eval_general, eval_stats,
+                  replay_eval)
     return {r["seed"]: r["rows"] for r in runs}
 
 
@@ -867,7 +954,7 @@ def sweep_label(variant, seed, hidden_sweep=False):
 def experiment_sweep(runs, log_dir=None, num_epochs=None, device=0, quiet=False, checkpoint_dir=None, resume=False,
                      chunk_rows=DEFAULT_CHUNK_ROWS, hidden_sweep=False, acting="host", sessions=True, general_sessions=None,
                      q_diagnostics=False, q_general="host", validation=False,
-                     eval_general="host", eval_stats="host"):
+                     eval_general="host", eval_stats="host", replay_eval=0):
     """Several tasks x seeds, one process, one device: every entry of ``runs`` -- (variant, seed), or (variant, seed,
     obs_dim, action_dim) for a task without pinned dims -- is the run ``experiment(variant, seed=seed)`` would make, and
     every epoch's training block is ONE MixedSACTrainerGroup.train_loop (TD3 variants: MixedTD3TrainerGroup; hidden sizes
@@ -889,13 +976,17 @@ def experiment_sweep(runs, log_dir=None, num_epochs=None, device=0, quiet=False,
     with q_general="device" they are evaluated on the device, one sac_q_values_general_many call per 16 of them).
     validation as for experiment_group (the runs of the general step take evaluate's host path inside the same call;
     with eval_general="device" they are evaluated on the device, one sac_evaluate_general_many call per 16 of them); TD3
-    sweeps are refused.  eval_stats as for experiment_group."""
+    sweeps are refused.  eval_stats as for experiment_group.
+    replay_eval as for experiment_group (one evaluate_replay_many call per epoch over all runs); TD3 sweeps are refused."""
     check_stats(eval_stats)
     check_acting(acting)
     check_general(q_general)
     check_general(eval_general)
+    replay_eval = check_replay_eval(replay_eval)
     for spec in runs if validation else ():
         _refuse_td3_validation(tuple(spec)[0], "experiment_sweep")
+    for spec in runs if replay_eval else ():
+        _refuse_td3_replay_eval(tuple(spec)[0], "experiment_sweep")
     if resume and not checkpoint_dir:
         raise RuntimeError("experiment_sweep(resume=True) needs the checkpoint_dir to resume from")
     specs = []
@@ -945,5 +1036,6 @@ def experiment_sweep(runs, log_dir=None, num_epochs=None, device=0, quiet=False,
     batches = [r["ak"]["batch_size"] for r in group_runs]
     _group_epochs(group_runs, lambda: group.train_loop([r["buf"] for r in group_runs], n_train, batch_sizes=batches),
                   num_epochs if num_epochs is not None else ak0["num_epochs"], n_train, log_dir, quiet, "runs", ck,
-                  first_epoch, acting, sessions, general_sessions, q_diagnostics, q_general, validation, eval_general, eval_stats)
+                  first_epoch, acting, sessions, general_sessions, q_diagnostics, q_general, validation, eval_general, eval_stats,
+                  replay_eval)
     return [r["rows"] for r in group_runs]

@@ -19,7 +19,7 @@ import numpy as np
 from . import _lib
 # (the inference names live in infer.py; they stay importable from here)
 from .infer import (GENERAL, GENERAL_SESSIONS, MAX_MEMBERS, GroupActor, act_many, check_general,  # noqa: F401
-                    evaluate_many, general_shape, q_values_many, runs_general_step)
+                    evaluate_many, evaluate_replay_many, general_shape, q_values_many, runs_general_step)
 from .sac import SACTrainer
 from .td3 import TD3Trainer
 
@@ -69,6 +69,13 @@ class _Members:
     def evaluate_many(self, batches, eps=None, rngs=None, rows=False, general="host", stats="host"):
         """evaluate_many over the group's members (general and stats as there)."""
         return evaluate_many(self.trainers, batches, eps=eps, rngs=rngs, rows=rows, general=general, stats=stats)
+
+    def evaluate_replay_many(self, replay_buffers, n=None, indices=None, eps=None, rngs=None, rows=False, general="host",
+                             stats="host"):
+        """evaluate_replay_many over the group's members on their replay buffers -- the ones train_loop takes, one per
+        member (n, indices, general and stats as there)."""
+        return evaluate_replay_many(self.trainers, replay_buffers, n=n, indices=indices, eps=eps, rngs=rngs, rows=rows,
+                                    general=general, stats=stats)
 
 
 class _SACMembers:

@@ -75,6 +75,8 @@ SESSION_ENTRIES = {FUSED: "sac_actor", GENERAL_STEP: "sac_gactor"}
 Q_ENTRIES = {FUSED: "sac_q_values_many", GENERAL_STEP: "sac_q_values_general_many"}
 EVAL_ENTRIES = {FUSED: ("sac_evaluate_many", "sac_evaluate_stats_many"),             # (stats "host", "device")
                 GENERAL_STEP: ("sac_evaluate_general_many", "sac_evaluate_general_stats_many")}
+EVAL_REPLAY_ENTRIES = {FUSED: "sac_evaluate_replay_many",                            # (stats: an argument, NULL for "host")
+                       GENERAL_STEP: "sac_evaluate_replay_general_many"}
 
 
 def route(t, general, on_host=False):
@@ -347,35 +349,51 @@ def moments_statistics(moments, alpha, log_alpha, target_entropy, auto):
 
 
 # ---- evaluation ---------------------------------------------------------------------------------------------------------
-def evaluate_of(trainers, inputs, rows, general, stats):
+def replay_route(t, buffer, general):
+    """route for a member of evaluate_replay: a buffer without device storage (no handle) sends it to the host too."""
+    return route(t, general, t._evaluate_on_host or getattr(buffer, "_h", None) is None)
+
+
+def evaluate_of(trainers, inputs, rows, general, stats, replay=None):
     """evaluate / evaluate_many behind their argument checks: inputs[i] = the member's arrays as SACTrainer._eval_inputs
     checked them, or None for a member that sits out (its result: None).  The host members first, in member order; then
-    the fused family, then the general one, each in windows."""
+    the fused family, then the general one, each in windows.
+    replay (evaluate_replay_of): replay[i] = (buffer, indices) of a member with rows, whose inputs[i] then holds None for
+    the five arrays the device takes from the replay storage (EVAL_REPLAY_ENTRIES); a host member evaluates the gathered
+    batch."""
     on_device = stats == "device"
     R = len(trainers)
     out, n_rows, served = [None] * R, [0] * R, {FUSED: [], GENERAL_STEP: []}
     for i, (t, arrs) in enumerate(zip(trainers, inputs)):
         if arrs is None:
             continue
-        where = route(t, general, t._evaluate_on_host)
+        where = route(t, general, t._evaluate_on_host) if replay is None else replay_route(t, replay[i][0], general)
         if where == HOST:
+            if replay is not None:
+                arrs = t._eval_inputs(replay[i][0].gather(replay[i][1]), arrs[5:], None)
             cols = t._evaluate_host(arrs)
             result = t._eval_stats(cols)
             out[i] = (result, cols) if rows else result
         else:
-            n_rows[i] = arrs[0].shape[0]
+            n_rows[i] = arrs[5].shape[0]
             served[where].append(i)
     members = served[FUSED] + served[GENERAL_STEP]
     lib = _lib.load() if members else None
     chunks, alphas, moments, log_alphas = {i: [] for i in members}, [1.0] * R, [None] * R, [0.0] * R
     for family in (FUSED, GENERAL_STEP):
-        entry = EVAL_ENTRIES[family][on_device]
+        entry = EVAL_ENTRIES[family][on_device] if replay is None else EVAL_REPLAY_ENTRIES[family]
         for r0, ids, counts in windows(served[family], n_rows):
             made = [trainers[i]._eval_io(inputs[i], r0, r0 + k, outputs=rows or not on_device) for i, k in zip(ids, counts)]
             ios = (_lib.SacEvalIO * len(ids))(*[m[0] for m in made])
             sts = (_lib.SacEvalStats * len(ids))() if on_device else None
-            _lib.check(getattr(lib, entry)(_handles(trainers, ids), len(ids), _ints(counts), ios,
-                                           *([sts] if on_device else [])), entry)
+            if replay is None:
+                args = [ios] + ([sts] if on_device else [])
+            else:
+                idx = [np.ascontiguousarray(replay[i][1][r0:r0 + k]) for i, k in zip(ids, counts)]
+                srcs = (_lib.SacEvalSrc * len(ids))(*[_lib.SacEvalSrc(replay[i][0]._h.value, x.ctypes.data)
+                                                      for i, x in zip(ids, idx)])
+                args = [srcs, ios, sts]
+            _lib.check(getattr(lib, entry)(_handles(trainers, ids), len(ids), _ints(counts), *args), entry)
             for k, i in enumerate(ids):
                 chunks[i].append(made[k][1])
                 alphas[i] = float(ios[k].alpha)
@@ -425,6 +443,55 @@ def evaluate_many(trainers, batches, eps=None, rngs=None, rows=False, general="h
             t.evaluate(b, eps=eps[i], rng=rngs[i], rows=rows)        # (TD3Trainer.evaluate refuses: the SAC objective)
         inputs[i] = t._eval_inputs(b, eps[i], rngs[i])
     return evaluate_of(trainers, inputs, rows, general, stats)
+
+
+def evaluate_replay_of(trainers, buffers, requests, rows, general, stats):
+    """evaluate_replay / evaluate_replay_many behind their argument checks: requests[i] = (indices, eps, eps_next) as
+    SACTrainer._replay_request checked them, or None for a member that sits out.  With rows the column dict of a member
+    additionally holds "indices"."""
+    inputs = [None if q is None else (None,) * 5 + (q[1], q[2]) for q in requests]
+    replay = [None if q is None else (b, q[0]) for b, q in zip(buffers, requests)]
+    out = evaluate_of(trainers, inputs, rows, general, stats, replay=replay)
+    if rows:
+        for q, res in zip(requests, out):
+            if q is not None:
+                res[1]["indices"] = q[0]
+    return out
+
+
+def evaluate_replay_many(trainers, buffers, n=None, indices=None, eps=None, rngs=None, rows=False, general="host",
+                         stats="host"):
+    """SACTrainer.evaluate_replay for many runs at once: result[i] = trainers[i].evaluate_replay(buffers[i], n or
+    indices[i], eps[i], rngs[i]).  Exactly one of n and indices: n one row count for every member or one per member,
+    indices one array of storage rows per member; an entry of None / 0 / no rows: the member sits out and gets None.
+    eps / rngs: one entry per trainer or None.  Two members may share a buffer (rows are only read).  The members on
+    the device are served by ONE call per 16 of them and 1024 rows per family (sac_evaluate_replay_many /
+    sac_evaluate_replay_general_many; general and stats as for evaluate_many); the others run evaluate on their gathered
+    batch inside the same call.  A member's result is bit for bit that of its own evaluate_replay; a TD3 member raises."""
+    check_stats(stats)
+    check_general(general)
+    trainers, buffers = list(trainers), list(buffers)
+    R = len(trainers)
+    if (n is None) == (indices is None):
+        raise ValueError("evaluate_replay_many takes exactly one of n and indices")
+    counts = [None] * R if n is None else ([n] * R if np.isscalar(n) else list(n))
+    indices = [None] * R if indices is None else list(indices)
+    eps = [None] * R if eps is None else list(eps)
+    rngs = [None] * R if rngs is None else list(rngs)
+    if not (len(buffers) == len(counts) == len(indices) == len(eps) == len(rngs) == R):
+        raise RuntimeError("evaluate_replay_many takes one buffer (and row count or indices, eps pair, rng) per trainer")
+    if len({id(t) for t in trainers}) != R:
+        raise RuntimeError("a trainer appears twice in evaluate_replay_many")
+    requests = [None] * R
+    for i, (t, b) in enumerate(zip(trainers, buffers)):
+        if n is not None and not counts[i]:
+            continue
+        if n is None and (indices[i] is None or np.asarray(indices[i]).size == 0):
+            continue
+        if _is_td3(t):
+            t.evaluate_replay(b, n=counts[i], indices=indices[i])     # (TD3Trainer.evaluate_replay refuses: the SAC objective)
+        requests[i] = t._replay_request(b, counts[i], indices[i], eps[i], rngs[i])
+    return evaluate_replay_of(trainers, buffers, requests, rows, general, stats)
 
 
 # ---- acting sessions ----------------------------------------------------------------------------------------------------

@@ -32,6 +32,10 @@ def _q_forward(layers, x):
     return (h @ layers[-1][0].T + layers[-1][1])[:, 0]
 
 
+def _lib_pointers(parts):
+    return [None if p is None else p.ctypes.data for p in parts]
+
+
 class SACTrainer:
     def __init__(self, env=None, policy=None, qf1=None, qf2=None, target_qf1=None, target_qf2=None,
                  discount=0.99, reward_scale=1.0, policy_lr=1e-3, qf_lr=1e-3, optimizer_class=None,
@@ -351,6 +355,15 @@ class SACTrainer:
                                      # measures the two paths of ONE trainer against each other)
     _eval_rng = None                 # evaluate's private noise stream, made on first use
 
+    def _eval_stream(self, rng):
+        """rng, or for None the stream private to the trainer (seeded from noise_seed): np.random is never touched."""
+        if rng is None:
+            if self._eval_rng is None:
+                self._eval_rng = np.random.RandomState(
+                    [int(self.noise_seed & 0xFFFFFFFF), int(self.noise_seed >> 32), 0x4556414C])
+            rng = self._eval_rng
+        return rng
+
     def _eval_inputs(self, batch, eps, rng):
         """evaluate's arguments, checked before any library call: float32 obs, act, rew, term, next_obs, eps, eps_next."""
         obs = _lib.f32(np.atleast_2d(batch["observations"]))
@@ -363,11 +376,7 @@ class SACTrainer:
         if rew.shape != (n,) or term.shape != (n,):
             raise ValueError(f"evaluate: {rew.size} rewards and {term.size} terminals for {n} rows")
         if eps is None:
-            if rng is None:                          # a stream private to the trainer: np.random is never touched
-                if self._eval_rng is None:
-                    self._eval_rng = np.random.RandomState(
-                        [int(self.noise_seed & 0xFFFFFFFF), int(self.noise_seed >> 32), 0x4556414C])
-                rng = self._eval_rng
+            rng = self._eval_stream(rng)
             eps = (rng.standard_normal((n, self.act_dim)), rng.standard_normal((n, self.act_dim)))
         e1, e2 = (_lib.f32(np.atleast_2d(e)) for e in eps)
         if e1.shape != act.shape or e2.shape != act.shape:
@@ -378,12 +387,13 @@ class SACTrainer:
         """sac_eval_io_t over rows i..j of evaluate's inputs, and the output arrays it points to.  outputs=False (the
         *_stats_many entries alone take it): no output array is made, `rows` and the optional arrays are NULL."""
         k, A = j - i, self.act_dim
-        parts = [np.ascontiguousarray(a[i:j]) for a in arrs]
+        # (an input that is None -- evaluate_replay: the five arrays the device takes from the replay storage -- stays NULL)
+        parts = [None if a is None else np.ascontiguousarray(a[i:j]) for a in arrs]
         if not outputs:
-            return _lib.SacEvalIO(*[p.ctypes.data for p in parts], *([None] * (1 + len(_lib.EVAL_ARRAYS))), 0.0), None, parts
+            return _lib.SacEvalIO(*_lib_pointers(parts), *([None] * (1 + len(_lib.EVAL_ARRAYS))), 0.0), None, parts
         out = dict(rows=np.empty((len(_lib.EVAL_ROWS), k), np.float32))
         out.update((name, np.empty((k, A), np.float32)) for name in _lib.EVAL_ARRAYS)
-        io = _lib.SacEvalIO(*[p.ctypes.data for p in parts], out["rows"].ctypes.data,
+        io = _lib.SacEvalIO(*_lib_pointers(parts), out["rows"].ctypes.data,
                             *[out[name].ctypes.data for name in _lib.EVAL_ARRAYS], 0.0)
         return io, out, parts
 
@@ -486,6 +496,58 @@ class SACTrainer:
         infer.check_stats(stats)
         infer.check_general(general)
         return infer.evaluate_of([self], [self._eval_inputs(batch, eps, rng)], rows, general, stats)[0]
+
+    def _replay_request(self, buffer, n, indices, eps, rng):
+        """evaluate_replay's arguments, checked before any library call: (indices int64 (k,), eps, eps_next float32 (k, A)).
+        Exactly one of n and indices; with n the indices are rng.randint(0, size, n), drawn IN FRONT of the eps pair from
+        the same stream (rng None: evaluate's private one)."""
+        if (n is None) == (indices is None):
+            raise ValueError("evaluate_replay takes exactly one of n and indices")
+        size = int(buffer.num_steps_can_sample())
+        if size < 1:
+            raise RuntimeError("evaluate_replay: the replay buffer is empty")
+        if indices is None:
+            if int(n) < 1:
+                raise ValueError(f"evaluate_replay: n = {n} (at least one row)")
+            rng = self._eval_stream(rng)
+            idx = np.ascontiguousarray(rng.randint(0, size, int(n)), dtype=np.int64)
+        else:
+            idx = np.ascontiguousarray(np.asarray(indices).reshape(-1), dtype=np.int64)
+            if idx.size < 1:
+                raise ValueError("evaluate_replay: no indices (at least one row)")
+            if int(idx.min()) < 0 or int(idx.max()) >= size:
+                bad = idx[(idx < 0) | (idx >= size)][0]
+                raise RuntimeError(f"evaluate_replay: index {int(bad)} out of range [0, {size})")
+        k, A = idx.size, self.act_dim
+        if eps is None:
+            rng = self._eval_stream(rng)
+            eps = (rng.standard_normal((k, A)), rng.standard_normal((k, A)))
+        e1, e2 = (_lib.f32(np.atleast_2d(e)) for e in eps)
+        if e1.shape != (k, A) or e2.shape != (k, A):
+            raise ValueError(f"evaluate_replay: eps {e1.shape} / eps_next {e2.shape} for {k} rows of {A} actions")
+        return idx, e1, e2
+
+    def evaluate_replay(self, buffer, n=None, indices=None, eps=None, rng=None, rows=False, general="host", stats="host"):
+        """evaluate on rows of `buffer` (an EnvReplayBuffer of this run's dims) IN PLACE: the SAC objectives at the
+        current parameters on the data the run trains on -- the figure validation/QF1 Loss stands next to.  Exactly one
+        of n and indices: `indices` are STORAGE rows (0 <= index < buffer size, any count, repeats allowed), `n` draws
+        them as rng.randint(0, size, n) in front of the eps pair from the same `rng` (None: evaluate's private stream;
+        np.random is never touched).  eps, rng, rows, general and stats are evaluate's; the result is what
+        evaluate(buffer.gather(indices), eps=the same pair, ...) returns, bit for bit, and with rows=True the column dict
+        additionally holds "indices".
+        On the device sac_evaluate_replay_many / sac_evaluate_replay_general_many copy the rows with a kernel from the
+        replay storage into the evaluation's staging (k_eval_rows, one launch per 1024 rows in front of the evaluation's
+        kernels), ordered behind pending add_* copies by an event.  That staging is mapped pinned HOST memory, as for
+        evaluate: the rows still cross the link, once out by the kernel's stores and once back by the evaluation's loads.
+        What is saved is the host's part -- no synchronised D2H copy, no NumPy dict, no conversion and no memcpy into
+        the staging.  The buffer is only read: its generator, np.random, its read-ahead and loop speculation stay as they
+        are, and training continues bit for bit as if the call had not happened.  A trainer that evaluate sends to the
+        host path (no handle; the general step under general="host"), and a buffer without device storage, run
+        evaluate(buffer.gather(indices) as a batch, ...)."""
+        infer.check_stats(stats)
+        infer.check_general(general)
+        request = self._replay_request(buffer, n, indices, eps, rng)
+        return infer.evaluate_replay_of([self], [buffer], [request], rows, general, stats)[0]
 
     def refresh_host_policy(self):
         """Mirror the trained policy D2H once per training block (acting stays on the host)."""

@@ -70,6 +70,11 @@ class TD3Trainer(SACTrainer):
                                   "a tanh-Gaussian policy); TD3's objective -- a deterministic policy with target "
                                   "smoothing -- is not implemented")
 
+    def evaluate_replay(self, buffer, n=None, indices=None, eps=None, rng=None, rows=False, general="host", stats="host"):
+        raise NotImplementedError("TD3Trainer.evaluate_replay: evaluate computes the SAC objective (entropy-regularised "
+                                  "targets of a tanh-Gaussian policy); TD3's objective -- a deterministic policy with "
+                                  "target smoothing -- is not implemented")
+
     def get_snapshot(self):
         snap = super().get_snapshot()
         snap["target_policy"] = self.target_policy

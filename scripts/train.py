@@ -18,7 +18,9 @@
  --validation: every epoch, the SAC losses, TD errors and targets on the evaluation paths' transitions -- held-out data
  -- from the live weights: validation/ columns in progress.csv; SAC only.
  --eval_general device: with --validation, runs of any hidden sizes evaluate these objectives on the device too.
- --eval_stats device: with --validation, the statistics of the runs evaluated on the device are reduced there as well.)
+ --eval_stats device: with --validation, the statistics of the runs evaluated on the device are reduced there as well.
+ --replay_eval [N]: every epoch, the same objectives on N (bare: 1024) rows of the replay buffer, read in place on the
+ device: replay/ columns in progress.csv, the training-data figures next to the validation/ ones; SAC only.)
 Runs the variant unchanged (batch size, lrs, tau, period, buffer size ... from the JSON) on the
 HIP library with a synthetic environment of the task's dimensions (robosuite is not installed)."""
 import argparse
@@ -30,7 +32,8 @@ from robosuite_benchmark_amd.driver import experiment, experiment_group, experim
 from robosuite_benchmark_amd.group_checkpoint import GroupMismatchError  # noqa: E402
 from robosuite_benchmark_amd.variant import default_variant, expand_hidden_sizes, load_variant  # noqa: E402
 
-if __name__ == "__main__":
+
+def build_parser():
     ap = argparse.ArgumentParser()
     ap.add_argument("--variant", type=str, default=None)
     ap.add_argument("--seed", type=int, default=1)
@@ -85,10 +88,22 @@ if __name__ == "__main__":
                          "evaluated on the device are reduced -- host (the columns are copied out and reduced in NumPy) or "
                          "device (one more HIP launch in front of the call's wait); the same validation/ columns either "
                          "way; without --validation it has no effect")
-    args = ap.parse_args()
+    ap.add_argument("--replay_eval", type=int, nargs="?", const=1024, default=0, metavar="N",
+                    help="every epoch, evaluate the same objectives on min(N, buffer size) rows of the replay buffer in "
+                         "place (a HIP kernel copies the rows from the replay storage into the evaluation's mapped staging: no "
+                         "gather to the host, no host conversion), at the point where --validation is taken, and log them as replay/<key>: "
+                         "the training-data figure the validation/ columns stand next to; the bare flag: 1024 rows; SAC "
+                         "only; --eval_general and --eval_stats apply to it too; 0 (the default): progress.csv is unchanged")
+    return ap
+
+
+if __name__ == "__main__":
+    args = build_parser().parse_args()
     eval_kw = {} if args.eval_general == "host" else dict(eval_general=args.eval_general)
     if args.eval_stats != "host":
         eval_kw["eval_stats"] = args.eval_stats
+    if args.replay_eval:
+        eval_kw["replay_eval"] = args.replay_eval
     if (args.hidden_sweep or args.hidden_sizes) and not args.variants:
         raise SystemExit("--hidden_sweep / --hidden_sizes need --variants")
     if args.variants or args.seeds:
