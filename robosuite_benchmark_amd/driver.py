@@ -13,6 +13,7 @@ import csv
 import os
 import time
 from collections import OrderedDict
+from typing import NamedTuple
 
 import numpy as np
 
@@ -356,32 +357,20 @@ def _validation_eps(seed, epoch, batch, A):
     return rs.standard_normal((n, A)), rs.standard_normal((n, A))
 
 
-def _validation_columns(stats, batch):
-    """validation/<key> for every key of SACTrainer.evaluate, and validation/Num Transitions."""
-    d = OrderedDict()
-    if stats is None:                                         # (no evaluation path this epoch: the columns stay, empty)
+def _objective_columns(prefix, stats, n):
+    """<prefix><key> for every key of SACTrainer.evaluate, and <prefix>Num Transitions = n.  stats None (nothing to evaluate
+    this epoch: no evaluation path, an empty buffer): the columns stay, empty."""
+    if stats is None:
         z = np.zeros((1, 1))
         stats = OrderedDict((k, float("nan")) for k in eval_statistics(np.zeros((9, 1)), z, z, 1.0, 0.0, 0.0, False))
-    d.update(("validation/" + k, v) for k, v in stats.items())
-    d["validation/Num Transitions"] = 0 if batch is None else int(batch["observations"].shape[0])
+    d = OrderedDict((prefix + k, v) for k, v in stats.items())
+    d[prefix + "Num Transitions"] = int(n)
     return d
 
 
-def _refuse_td3_validation(variant, what):
-    if variant.get("algorithm", "SAC") == "TD3":
-        raise RuntimeError(f"{what}(validation=True): validation evaluates the SAC objective (SACTrainer.evaluate); a TD3 "
-                           "variant has no such evaluation")
-
-
-def _group_validation(runs, epoch, eval_general="host", eval_stats="host"):
-    """_validation_columns of every run's evaluation paths of this epoch, all runs from ONE evaluate_many call
-    (eval_general="device": the runs of the general step on the device too, evaluate_many's general; eval_stats="device":
-    the statistics of the runs evaluated on the device reduced there too, evaluate_many's stats)."""
-    batches = [_validation_batch(r["evalc"].epoch_paths, r["trainer"].obs_dim, r["trainer"].act_dim) for r in runs]
-    eps = [_validation_eps(r["seed"], epoch, b, r["trainer"].act_dim) for r, b in zip(runs, batches)]
-    stats = evaluate_many([r["trainer"] for r in runs], batches, eps=eps, **_q_general_kw(eval_general),
-                          **_eval_stats_kw(eval_stats))
-    return [_validation_columns(s, b) for s, b in zip(stats, batches)]
+def _validation_columns(stats, batch):
+    """The validation block of a row: the statistics of `batch` (None: no evaluation path this epoch)."""
+    return _objective_columns("validation/", stats, 0 if batch is None else batch["observations"].shape[0])
 
 
 REPLAY_STREAM = 0x52504C          # "RPL": the third seed word of an epoch's replay-evaluation draws
@@ -405,30 +394,8 @@ def _replay_rng(seed, epoch):
 
 
 def _replay_columns(stats, n):
-    """replay/<key> for every key of SACTrainer.evaluate, and replay/Num Transitions."""
-    d = OrderedDict()
-    if stats is None:                                         # (an empty buffer this epoch: the columns stay, empty)
-        z = np.zeros((1, 1))
-        stats = OrderedDict((k, float("nan")) for k in eval_statistics(np.zeros((9, 1)), z, z, 1.0, 0.0, 0.0, False))
-    d.update(("replay/" + k, v) for k, v in stats.items())
-    d["replay/Num Transitions"] = int(n)
-    return d
-
-
-def _refuse_td3_replay_eval(variant, what):
-    if variant.get("algorithm", "SAC") == "TD3":
-        raise RuntimeError(f"{what}(replay_eval=N): the replay evaluation computes the SAC objective "
-                           "(SACTrainer.evaluate_replay); a TD3 variant has no such evaluation")
-
-
-def _group_replay_eval(runs, epoch, replay_eval, eval_general="host", eval_stats="host"):
-    """_replay_columns of every run's replay rows of this epoch, all runs from ONE evaluate_replay_many call (eval_general
-    and eval_stats as for _group_validation)."""
-    ns = [_replay_rows(replay_eval, r["buf"]) for r in runs]
-    stats = evaluate_replay_many([r["trainer"] for r in runs], [r["buf"] for r in runs], n=ns,
-                                 rngs=[_replay_rng(r["seed"], epoch) for r in runs], **_q_general_kw(eval_general),
-                                 **_eval_stats_kw(eval_stats)) if any(ns) else [None] * len(runs)
-    return [_replay_columns(s, n) for s, n in zip(stats, ns)]
+    """The replay block of a row: the statistics of n replay rows (0: an empty buffer this epoch)."""
+    return _objective_columns("replay/", stats, n)
 
 
 def _rs_pack(rs):
@@ -440,16 +407,229 @@ def _rs_unpack(rs, d):
     rs.set_state(("MT19937", np.asarray(d["key"], np.uint32), d["pos"], d["has_gauss"], d["cached"]))
 
 
-def _progress_row(buf, trainer, expl, evalc, ak):
-    """The epoch's progress.csv columns in the reference's order, up to the time/* block."""
+def _q_general_kw(q_general):
+    """q_general (eval_general) as the `general` keyword of q_values / q_values_many (evaluate / evaluate_many): left out
+    at the default, so the call is what it was."""
+    return {} if q_general == "host" else {"general": q_general}
+
+
+def _eval_stats_kw(eval_stats):
+    """eval_stats as the `stats` keyword of evaluate / evaluate_many: left out at the default, as _q_general_kw does."""
+    return {} if eval_stats == "host" else {"stats": eval_stats}
+
+
+class EvalOptions(NamedTuple):
+    """The per-epoch evaluations of experiment(), experiment_group() and experiment_sweep(): each is taken right behind
+    the epoch's evaluation paths and in front of the training block (policy and critics of one moment), adds a block of
+    columns in front of time/* -- Q bias, validation, replay, in this order -- and counts under
+    `time/evaluation sampling (s)`.  With all of them off (the defaults) the row, every generator and every column are
+    exactly what they were.  experiment() calls the trainer's own methods; the group entries make ONE q_values_many,
+    evaluate_many and evaluate_replay_many call per epoch over all runs, and each run's columns are its solo ones.
+
+    q_diagnostics=True: qf1 and qf2 on every (observation, action) of the epoch's evaluation paths (q_values: on the
+    device from the live weights) and q_bias_information's sixteen columns behind the evaluation/ block.
+    q_general ("host" or "device") is q_values' `general`: where a run of the general step evaluates its critics --
+    sac_get_params and a NumPy forward, or sac_q_values_general (one k_qval_layer launch per layer on the live weights;
+    in a group one sac_q_values_general_many call per 16 such runs).  Without q_diagnostics, and for a run with the
+    fused kernels' shapes, it has no effect.
+
+    validation=True: the SAC objectives on the transitions of the epoch's evaluation paths -- collected
+    deterministically, never in the replay buffer: a held-out set -- by evaluate (on the device from the live weights
+    and the current entropy coefficient; a run of the general step on the host), with the N(0,1) draws of
+    RandomState([seed, epoch, 0x56414C]): nothing to checkpoint, and a resumed run logs the same rows.  The row gains
+    validation/<key> for every key of evaluate and validation/Num Transitions.  A TD3 variant is refused.
+    eval_general ("host" or "device") is evaluate's `general`: where a run of the general step evaluates its objectives
+    -- sac_get_params and a NumPy forward, or sac_evaluate_general (one k_eval_layer launch per layer on the live
+    weights; in a group one sac_evaluate_general_many call per 16 such runs).  Without validation and replay_eval, and
+    for a run with the fused kernels' shapes, it has no effect.
+    eval_stats ("host" or "device") is evaluate's `stats`: where the statistics of a run that is evaluated on the device
+    are reduced -- eval_statistics on the columns copied out, or k_eval_moments on the device (the same columns of
+    progress.csv, equal up to the rounding of a float64 sum in another order).  Without validation and replay_eval it
+    has no effect.
+
+    replay_eval=N > 0: the same objectives on min(N, buffer size) rows of the REPLAY buffer in place (evaluate_replay: a
+    kernel copies the rows into the evaluation's staging, no gather to the host), in front of the epoch's exploration
+    paths -- the figure validation/QF1 Loss stands next to, at the same parameters.  Indices and N(0,1) draws come from
+    RandomState([seed, epoch, 0x52504C]).  The row gains replay/<key> for every key of evaluate and
+    replay/Num Transitions.  eval_general and eval_stats apply to it as to validation.  A TD3 variant is refused."""
+    q_diagnostics: bool = False
+    q_general: str = "host"
+    validation: bool = False
+    eval_general: str = "host"
+    eval_stats: str = "host"
+    replay_eval: int = 0
+
+
+def _refuse_td3(variant, what, call, reason):
+    if variant.get("algorithm", "SAC") == "TD3":
+        raise RuntimeError(f"{what}({call}): {reason}; a TD3 variant has no such evaluation")
+
+
+def _options(what, specs, acting, q_diagnostics, q_general, validation, eval_general, eval_stats, replay_eval):
+    """The EvalOptions of entry `what`, after the value checks of its keywords (acting's too) and, for the variant at
+    the head of every run spec in `specs`, the TD3 refusals: all of it in front of anything that builds a run."""
+    check_stats(eval_stats)
+    check_acting(acting)
+    check_general(q_general)
+    check_general(eval_general)
+    opts = EvalOptions(q_diagnostics, q_general, validation, eval_general, eval_stats, check_replay_eval(replay_eval))
+    for spec in specs if opts.validation else ():
+        _refuse_td3(tuple(spec)[0], what, "validation=True", "validation evaluates the SAC objective (SACTrainer.evaluate)")
+    for spec in specs if opts.replay_eval else ():
+        _refuse_td3(tuple(spec)[0], what, "replay_eval=N",
+                    "the replay evaluation computes the SAC objective (SACTrainer.evaluate_replay)")
+    return opts
+
+
+EVAL_BLOCKS = ("q", "validation", "replay")                   # the optional column blocks, in the row's order
+
+
+def _epoch_evaluations(runs, epoch, opts, take=EVAL_BLOCKS, many=True):
+    """The blocks of `take` that `opts` switches on, for every run at this moment of `epoch`: ([{block: columns} per
+    run], seconds spent).  many: ONE q_values_many / evaluate_many / evaluate_replay_many call over all runs (the last
+    only when some run has rows); otherwise each trainer's own q_values / evaluate / evaluate_replay."""
+    s0 = time.time()
+    cols, trainers = [{} for _ in runs], [r["trainer"] for r in runs]
+    paths = [r["evalc"].epoch_paths for r in runs]
+    gen, stats_kw = _q_general_kw(opts.eval_general), _eval_stats_kw(opts.eval_stats)
+    if opts.q_diagnostics and "q" in take:
+        steps = [_path_steps(p, t.obs_dim, t.act_dim) for p, t in zip(paths, trainers)]
+        kw = _q_general_kw(opts.q_general)
+        qs = (q_values_many(trainers, [s[0] for s in steps], [s[1] for s in steps], [("qf1", "qf2")] * len(runs), **kw)
+              if many else [t.q_values(*s, nets=("qf1", "qf2"), **kw) for t, s in zip(trainers, steps)])
+        for c, p, t, q in zip(cols, paths, trainers, qs):
+            c["q"] = q_bias_information(p, q[0], q[1], t.discount, t.reward_scale)
+    if opts.validation and "validation" in take:
+        batches = [_validation_batch(p, t.obs_dim, t.act_dim) for p, t in zip(paths, trainers)]
+        eps = [_validation_eps(r["seed"], epoch, b, t.act_dim) for r, b, t in zip(runs, batches, trainers)]
+        got = (evaluate_many(trainers, batches, eps=eps, **gen, **stats_kw) if many else
+               [None if b is None else t.evaluate(b, eps=e, **gen, **stats_kw) for t, b, e in zip(trainers, batches, eps)])
+        for c, s, b in zip(cols, got, batches):
+            c["validation"] = _validation_columns(s, b)
+    if opts.replay_eval and "replay" in take:
+        bufs, ns = [r["buf"] for r in runs], [_replay_rows(opts.replay_eval, r["buf"]) for r in runs]
+        got = [None] * len(runs)
+        if any(ns):
+            rngs = [_replay_rng(r["seed"], epoch) for r in runs]
+            got = (evaluate_replay_many(trainers, bufs, n=ns, rngs=rngs, **gen, **stats_kw) if many else
+                   [t.evaluate_replay(b, n=n, rng=g, **gen, **stats_kw) for t, b, n, g in zip(trainers, bufs, ns, rngs)])
+        for c, s, n in zip(cols, got, ns):
+            c["replay"] = _replay_columns(s, n)
+    return cols, time.time() - s0
+
+
+def _end_epoch_row(r, blocks, epoch):
+    """Run r's progress.csv columns of `epoch` in the reference's order up to the time/* block, the blocks of
+    _epoch_evaluations behind them in EVAL_BLOCKS' order; then the run's parts end their epoch."""
+    buf, trainer, expl, evalc = r["buf"], r["trainer"], r["expl"], r["evalc"]
     row = OrderedDict()
     row.update(("replay_buffer/" + k, v) for k, v in buf.get_diagnostics().items())
     row.update(("trainer/" + k, v) for k, v in trainer.get_diagnostics().items())
     row.update(("exploration/" + k, v) for k, v in expl.get_diagnostics().items())
     row.update(path_information(expl.epoch_paths, "exploration/"))
     row.update(("evaluation/" + k, v) for k, v in evalc.get_diagnostics().items())
-    row.update(path_information(evalc.epoch_paths, "evaluation/", ak["expl_max_path_length"]))
+    row.update(path_information(evalc.epoch_paths, "evaluation/", r["ak"]["expl_max_path_length"]))
+    for name in EVAL_BLOCKS:
+        row.update(blocks.get(name, ()))
+    for x in (trainer, buf, expl, evalc):
+        x.end_epoch(epoch)
     return row
+
+
+def _stamp_times(row, epoch, storing, evaluation, exploration, logging, saving, training, epoch_s, total):
+    """The row's last nine columns, in the reference's order."""
+    row["time/data storing (s)"] = storing
+    row["time/evaluation sampling (s)"] = evaluation
+    row["time/exploration sampling (s)"] = exploration
+    row["time/logging (s)"] = logging
+    row["time/saving (s)"] = saving
+    row["time/training (s)"] = training
+    row["time/epoch (s)"] = epoch_s
+    row["time/total (s)"] = total
+    row["Epoch"] = epoch
+
+
+def _log_row(r, row, log_dir, first_epoch):
+    """Run r keeps the row and, with log_dir, writes it to <log_dir>/progress.csv: opened at the run's first row, with
+    the row's columns as the header -- or, after a resume (first_epoch > 0) onto an existing file, appended to without
+    one."""
+    r["rows"].append(row)
+    if log_dir is None:
+        return
+    if r["writer"] is None:
+        os.makedirs(log_dir, exist_ok=True)
+        path = os.path.join(log_dir, "progress.csv")
+        appending = first_epoch > 0 and os.path.exists(path)
+        r["fh"] = open(path, "a" if appending else "w", newline="")
+        r["writer"] = csv.DictWriter(r["fh"], fieldnames=list(row.keys()))
+        if not appending:
+            r["writer"].writeheader()
+    r["writer"].writerow(row)
+    r["fh"].flush()
+
+
+def _pack_extra(r, epoch):
+    """What a checkpoint keeps of run r next to its trainer and buffer: the epoch, the seed, the collectors' totals and
+    the host generators."""
+    extra = dict(epoch=epoch, seed=r["seed"], expl_totals=[r["expl"].num_steps_total, r["expl"].num_paths_total],
+                 eval_totals=[r["evalc"].num_steps_total, r["evalc"].num_paths_total])
+    extra.update({k: _rs_pack(rs) for k, rs in r["host_rngs"].items()})
+    return extra
+
+
+def _restore_extra(r, extra):
+    """_pack_extra's counterpart on a run whose trainer and buffer have been restored; returns the first epoch to run."""
+    for k, rs in r["host_rngs"].items():
+        _rs_unpack(rs, extra[k])
+    r["expl"].num_steps_total, r["expl"].num_paths_total = extra["expl_totals"]
+    r["evalc"].num_steps_total, r["evalc"].num_paths_total = extra["eval_totals"]
+    r["trainer"].end_epoch(int(extra["epoch"]))
+    return int(extra["epoch"]) + 1
+
+
+def _build_run(variant, seed, O, A, device, acting, rs):
+    """The run record of (variant, seed): seed, ak (the variant's algorithm_kwargs), trainer, buf, expl and evalc (the
+    two PathCollectors), rows, fh and writer (its progress.csv), variant, host_rngs (the host generators a checkpoint
+    keeps: policy noise and the two environments').  The synthetic environments and every noise stream come from `seed`,
+    the initial weights from the generator `rs`: qf1, qf2, target_qf1, target_qf2, then the policy or policies.  The
+    buffer is empty.  acting: see experiment()."""
+    ak, tk = variant["algorithm_kwargs"], variant["trainer_kwargs"]
+    expl_env = SyntheticEnv(O, A, variant["expl_environment_kwargs"].get("horizon", 500), seed)
+    eval_env = SyntheticEnv(O, A, variant["eval_environment_kwargs"].get("horizon", 500), seed + 1)
+    qf1, qf2, tqf1, tqf2 = (FlattenMlp(input_size=O + A, output_size=1, rs=rs, **variant["qf_kwargs"]) for _ in range(4))
+    if variant.get("algorithm", "SAC") == "TD3":                  # rlkit_utils.py:107-135
+        policy = TanhMlpPolicy(input_size=O, output_size=A, rs=rs, **variant["policy_kwargs"])
+        target_policy = TanhMlpPolicy(input_size=O, output_size=A, rs=rs, **variant["policy_kwargs"])
+        eval_policy = policy
+        expl_policy = PolicyWrappedWithExplorationStrategy(
+            exploration_strategy=GaussianStrategy(max_sigma=0.1, min_sigma=0.1, seed=seed), policy=policy)
+        trainer = TD3Trainer(policy=policy, qf1=qf1, qf2=qf2, target_qf1=tqf1, target_qf2=tqf2, target_policy=target_policy,
+                             batch_size=ak["batch_size"], noise_seed=seed, device=device, **tk)
+        policy._noise = expl_policy.es._rs                        # (the generator a checkpoint saves as policy_noise)
+    else:
+        policy = TanhGaussianPolicy(obs_dim=O, action_dim=A, rs=rs, noise=np.random.RandomState(seed),
+                                    **variant["policy_kwargs"])
+        eval_policy, expl_policy = MakeDeterministic(policy), policy
+        trainer = SACTrainer(env=eval_env, policy=policy, qf1=qf1, qf2=qf2, target_qf1=tqf1, target_qf2=tqf2,
+                             batch_size=ak["batch_size"], noise_seed=seed, device=device, **tk)
+    if acting != "host" and not runs_general_step(trainer):
+        policy.acting = "device"
+    elif acting == "device_all":
+        policy.acting = "device_all"
+    buf = EnvReplayBuffer(variant["replay_buffer_size"], obs_dim=O, action_dim=A, device=device)
+    expl, evalc = PathCollector(expl_env, expl_policy), PathCollector(eval_env, eval_policy)
+    host_rngs = dict(policy_noise=policy._noise, expl_env=expl_env._rs, eval_env=eval_env._rs)
+    return dict(seed=seed, ak=ak, trainer=trainer, buf=buf, expl=expl, evalc=evalc, rows=[], fh=None, writer=None,
+                variant=variant, host_rngs=host_rngs)
+
+
+def _prefill(r):
+    """min_num_steps_before_training exploration steps into the buffer, in front of epoch 0 (the run's own get_action
+    calls)."""
+    ak = r["ak"]
+    if ak.get("min_num_steps_before_training", 0) > 0:
+        r["buf"].add_paths(r["expl"].collect_new_paths(ak["expl_max_path_length"], ak["min_num_steps_before_training"], False))
+        r["expl"].end_epoch(-1)
 
 
 def experiment(variant, log_dir=None, seed=1, obs_dim=None, action_dim=None, num_epochs=None, device=0,
@@ -470,210 +650,70 @@ def experiment(variant, log_dir=None, seed=1, obs_dim=None, action_dim=None, num
     k_act_layer launch per layer on the live weights).  The exploration noise comes from the same host stream, in the
     same amounts, whichever value is given.
 
-    q_diagnostics=True: every epoch, right behind the evaluation paths and in front of the training block (policy and
-    critics of one moment), qf1 and qf2 are evaluated on every (observation, action) of the epoch's evaluation paths
-    (trainer.q_values: on the device from the live weights) and the row gets q_bias_information's sixteen columns
-    behind its evaluation/ block; the time counts under `time/evaluation sampling (s)`.  Off (the default), the row is
-    exactly what it was.  q_general ("host", the default, or "device") is q_values' `general`: where a run of the general
-    step evaluates its critics -- sac_get_params and a NumPy forward, or sac_q_values_general (one k_qval_layer launch per
-    layer on the live weights).  Without q_diagnostics, and for a run with the fused kernels' shapes, it has no effect.
-
-    validation=True: every epoch, right behind the evaluation paths (and q_diagnostics) and in front of the training
-    block, the SAC objectives are evaluated on the transitions of the epoch's evaluation paths -- collected
-    deterministically, never in the replay buffer: a held-out set -- by trainer.evaluate (on the device from the live
-    weights and the current entropy coefficient; a run of the general step on the host), with the N(0,1) draws of
-    RandomState([seed, epoch, 0x56414C]): nothing to checkpoint, and a resumed run logs the same rows.  The row gains
-    validation/<key> for every key of evaluate and validation/Num Transitions, behind the q_diagnostics columns and in
-    front of time/*; the time counts under `time/evaluation sampling (s)`.  A TD3 variant is refused.  Off (the
-    default), the row, every generator and every column are exactly what they were.  eval_general ("host", the default,
-    or "device") is evaluate's `general`: where a run of the general step evaluates its objectives -- sac_get_params and
-    a NumPy forward, or sac_evaluate_general (one k_eval_layer launch per layer on the live weights).  Without validation,
-    and for a run with the fused kernels' shapes, it has no effect.  eval_stats ("host", the default, or "device") is
-    evaluate's `stats`: where the statistics of a run that is evaluated on the device are reduced -- eval_statistics on
-    the columns copied out, or k_eval_moments on the device (the same columns of progress.csv, equal up to the rounding
-    of a float64 sum in another order).  Without validation and replay_eval it has no effect.
-
-    replay_eval=N > 0: every epoch, at the point where validation is taken (behind it, in front of the exploration paths
-    and the training block), the same objectives are evaluated on min(N, buffer size) rows of the REPLAY buffer in place
-    (trainer.evaluate_replay: a kernel copies the rows into the evaluation's staging, no gather to the host) -- the figure validation/QF1 Loss stands next to, at the
-    same parameters.  Indices and N(0,1) draws come from RandomState([seed, epoch, 0x52504C]): nothing to checkpoint,
-    and a resumed run logs the same rows.  The row gains replay/<key> for every key of evaluate and
-    replay/Num Transitions, behind the validation columns and in front of time/*; the time counts under
-    `time/evaluation sampling (s)`.  eval_general and eval_stats apply to it as to validation.  A TD3 variant is
-    refused.  With 0 (the default), the row, every generator and every column are exactly what they were."""
-    check_stats(eval_stats)
-    check_acting(acting)
-    check_general(q_general)
-    check_general(eval_general)
-    replay_eval = check_replay_eval(replay_eval)
+    q_diagnostics, q_general, validation, eval_general, eval_stats, replay_eval: the per-epoch evaluations, EvalOptions;
+    here from the trainer's own q_values, evaluate and evaluate_replay."""
+    opts = _options("experiment", [(variant,)], acting, q_diagnostics, q_general, validation, eval_general, eval_stats,
+                    replay_eval)
     validate(variant)
-    if validation:
-        _refuse_td3_validation(variant, "experiment")
-    if replay_eval:
-        _refuse_td3_replay_eval(variant, "experiment")
-    np.random.seed(seed)                                          # scripts/train.py:112 (args.seed, not variant seed)
-    O, A = env_dims(variant["expl_environment_kwargs"], obs_dim, action_dim)
-    ak, tk = variant["algorithm_kwargs"], variant["trainer_kwargs"]
-    expl_env = SyntheticEnv(O, A, variant["expl_environment_kwargs"].get("horizon", 500), seed)
-    eval_env = SyntheticEnv(O, A, variant["eval_environment_kwargs"].get("horizon", 500), seed + 1)
-    # This driver's runs are a function of `seed` alone: initial weights come from np.random (seeded above), every noise
+    # This driver's runs are a function of `seed` alone: initial weights come from np.random (seeded here), every noise
     # stream from `seed` -- whether or not torch happens to be loaded in the process (the reference's own scripts seed
     # torch as well, train.py:113, and the holders then follow torch's generator by themselves: networks.process_stream).
-    qf1, qf2, tqf1, tqf2 = (FlattenMlp(input_size=O + A, output_size=1, rs=np.random, **variant["qf_kwargs"]) for _ in range(4))
-    if variant.get("algorithm", "SAC") == "TD3":                  # rlkit_utils.py:107-135
-        policy = TanhMlpPolicy(input_size=O, output_size=A, rs=np.random, **variant["policy_kwargs"])
-        target_policy = TanhMlpPolicy(input_size=O, output_size=A, rs=np.random, **variant["policy_kwargs"])
-        eval_policy = policy
-        expl_policy = PolicyWrappedWithExplorationStrategy(
-            exploration_strategy=GaussianStrategy(max_sigma=0.1, min_sigma=0.1, seed=seed), policy=policy)
-        trainer = TD3Trainer(policy=policy, qf1=qf1, qf2=qf2, target_qf1=tqf1, target_qf2=tqf2, target_policy=target_policy,
-                             batch_size=ak["batch_size"], noise_seed=seed, device=device, **tk)
-        policy._noise = expl_policy.es._rs                        # (the generator a checkpoint saves as policy_noise)
-    else:
-        policy = TanhGaussianPolicy(obs_dim=O, action_dim=A, rs=np.random, noise=np.random.RandomState(seed),
-                                    **variant["policy_kwargs"])
-        eval_policy, expl_policy = MakeDeterministic(policy), policy
-        trainer = SACTrainer(env=eval_env, policy=policy, qf1=qf1, qf2=qf2, target_qf1=tqf1, target_qf2=tqf2,
-                             batch_size=ak["batch_size"], noise_seed=seed, device=device, **tk)
-    if acting != "host" and not runs_general_step(trainer):
-        policy.acting = "device"
-    elif acting == "device_all":
-        policy.acting = "device_all"
-    buf = EnvReplayBuffer(variant["replay_buffer_size"], obs_dim=O, action_dim=A, device=device)
-    expl, evalc = PathCollector(expl_env, expl_policy), PathCollector(eval_env, eval_policy)
-    rows, t_start = [], time.time()
-    writer, fh = None, None
-    first_epoch = 0
-    host_rngs = dict(policy_noise=policy._noise, expl_env=expl_env._rs, eval_env=eval_env._rs)
+    np.random.seed(seed)                                          # scripts/train.py:112 (args.seed, not variant seed)
+    O, A = env_dims(variant["expl_environment_kwargs"], obs_dim, action_dim)
+    # (no private stream for the buffer: it samples np.random itself -- bound to its state words)
+    r = _build_run(variant, seed, O, A, device, acting, np.random)
+    ak, trainer, buf, expl, evalc = r["ak"], r["trainer"], r["buf"], r["expl"], r["evalc"]
+    first_epoch, t_start = 0, time.time()
     if resume and checkpoint_dir and checkpoint_exists(checkpoint_dir):
         extra = load_checkpoint(checkpoint_dir, trainer, buf)
-        first_epoch = int(extra["epoch"]) + 1
         _rs_unpack(np.random, extra["np_random"])
-        for k, rs in host_rngs.items():
-            _rs_unpack(rs, extra[k])
-        expl.num_steps_total, expl.num_paths_total = extra["expl_totals"]
-        evalc.num_steps_total, evalc.num_paths_total = extra["eval_totals"]
-        trainer.end_epoch(first_epoch - 1)
-    elif ak.get("min_num_steps_before_training", 0) > 0:
-        buf.add_paths(expl.collect_new_paths(ak["expl_max_path_length"], ak["min_num_steps_before_training"], False))
-        expl.end_epoch(-1)
+        first_epoch = _restore_extra(r, extra)
+    else:
+        _prefill(r)
+    n_train = ak["num_trains_per_train_loop"]
     for epoch in range(first_epoch, num_epochs if num_epochs is not None else ak["num_epochs"]):
         t0 = time.time()
         evalc.collect_new_paths(ak["eval_max_path_length"], ak["num_eval_steps_per_epoch"], True)
-        q_info = None
-        if q_diagnostics:
-            q1, q2 = trainer.q_values(*_path_steps(evalc.epoch_paths, O, A), nets=("qf1", "qf2"), **_q_general_kw(q_general))
-            q_info = q_bias_information(evalc.epoch_paths, q1, q2, trainer.discount, trainer.reward_scale)
-        v_info = None
-        if validation:
-            vb = _validation_batch(evalc.epoch_paths, O, A)
-            v_info = _validation_columns(None if vb is None else trainer.evaluate(vb, eps=_validation_eps(seed, epoch, vb, A),
-                                                                                  **_q_general_kw(eval_general),
-                                                                                  **_eval_stats_kw(eval_stats)), vb)
-        r_info = None
-        if replay_eval:
-            rn = _replay_rows(replay_eval, buf)
-            r_info = _replay_columns(None if rn == 0 else trainer.evaluate_replay(
-                buf, n=rn, rng=_replay_rng(seed, epoch), **_q_general_kw(eval_general), **_eval_stats_kw(eval_stats)), rn)
+        blocks, _ = _epoch_evaluations([r], epoch, opts, many=False)
         t1 = time.time()
         new_paths = expl.collect_new_paths(ak["expl_max_path_length"], ak["num_expl_steps_per_train_loop"], False)
         t2 = time.time()
         buf.add_paths(new_paths)
         t3 = time.time()
-        # (the buffer samples np.random itself -- bound to its state words: nothing to hand over before or after the block)
-        n_train = ak["num_trains_per_train_loop"]
         if fused_loop:
             trainer.train_loop(buf, n_train, batch_size=ak["batch_size"])
         else:
             for _ in range(n_train):
                 trainer.train(buf.random_batch(ak["batch_size"]))
         t4 = time.time()
-        row = _progress_row(buf, trainer, expl, evalc, ak)
-        if q_info is not None:
-            row.update(q_info)
-        if v_info is not None:
-            row.update(v_info)
-        if r_info is not None:
-            row.update(r_info)
-        trainer.end_epoch(epoch); buf.end_epoch(epoch); expl.end_epoch(epoch); evalc.end_epoch(epoch)
+        row = _end_epoch_row(r, blocks[0], epoch)
         t5 = time.time()
         if checkpoint_dir:
-            extra = dict(epoch=epoch, seed=seed, np_random=_rs_pack(np.random),
-                         expl_totals=[expl.num_steps_total, expl.num_paths_total],
-                         eval_totals=[evalc.num_steps_total, evalc.num_paths_total])
-            extra.update({k: _rs_pack(rs) for k, rs in host_rngs.items()})
-            save_checkpoint(checkpoint_dir, trainer, buf, extra)
+            save_checkpoint(checkpoint_dir, trainer, buf, dict(_pack_extra(r, epoch), np_random=_rs_pack(np.random)))
         t6 = time.time()
-        row["time/data storing (s)"] = t3 - t2
-        row["time/evaluation sampling (s)"] = t1 - t0
-        row["time/exploration sampling (s)"] = t2 - t1
-        row["time/logging (s)"] = t5 - t4
-        row["time/saving (s)"] = t6 - t5
-        row["time/training (s)"] = t4 - t3
-        row["time/epoch (s)"] = t6 - t0
-        row["time/total (s)"] = t6 - t_start
-        row["Epoch"] = epoch
-        rows.append(row)
-        if log_dir is not None:
-            if writer is None:
-                os.makedirs(log_dir, exist_ok=True)
-                appending = first_epoch > 0 and os.path.exists(os.path.join(log_dir, "progress.csv"))
-                fh = open(os.path.join(log_dir, "progress.csv"), "a" if appending else "w", newline="")
-                writer = csv.DictWriter(fh, fieldnames=list(row.keys()))
-                if not appending:
-                    writer.writeheader()
-            writer.writerow(row)
-            fh.flush()
+        _stamp_times(row, epoch, storing=t3 - t2, evaluation=t1 - t0, exploration=t2 - t1, logging=t5 - t4,
+                     saving=t6 - t5, training=t4 - t3, epoch_s=t6 - t0, total=t6 - t_start)
+        _log_row(r, row, log_dir, first_epoch)
         if not quiet:
             print(f"epoch {epoch}: buffer {row['replay_buffer/size']}  QF1 {row['trainer/QF1 Loss']:.4f}  "
                   f"policy loss {row['trainer/Policy Loss']:.4f}  training {row['time/training (s)']:.3f}s "
                   f"({n_train / max(row['time/training (s)'], 1e-9):.0f} steps/s)", flush=True)
-    if fh:
-        fh.close()
-    return rows
+    if r["fh"]:
+        r["fh"].close()
+    return r["rows"]
 
 
 def _group_run(variant, seed, O, A, device, prefill=True, acting="host"):
-    """One run of a grouped experiment, set up as experiment(variant, seed=seed) sets it up: its own synthetic
-    environments, collectors, weights (from a private RandomState(seed), in the order experiment() draws them from
-    np.random) and replay buffer (sampling a private stream continued from that generator), prefilled unless the run is
-    about to be restored from a checkpoint.  acting as for experiment() (the prefill is this run's alone: its get_action
-    calls)."""
-    td3 = variant.get("algorithm", "SAC") == "TD3"
-    ak, tk = variant["algorithm_kwargs"], variant["trainer_kwargs"]
+    """One run of a grouped experiment, set up as experiment(variant, seed=seed) sets it up (_build_run), but for the
+    generators: the weights come from a private RandomState(seed), in the order experiment() draws them from np.random,
+    and the replay buffer samples a private stream continued from that generator.  Prefilled unless the run is about to
+    be restored from a checkpoint (the prefill is this run's alone: its get_action calls)."""
     rs = np.random.RandomState(seed)                          # experiment(): np.random.seed(seed), then the weights
-    expl_env = SyntheticEnv(O, A, variant["expl_environment_kwargs"].get("horizon", 500), seed)
-    eval_env = SyntheticEnv(O, A, variant["eval_environment_kwargs"].get("horizon", 500), seed + 1)
-    qf1, qf2, tqf1, tqf2 = (FlattenMlp(input_size=O + A, output_size=1, rs=rs, **variant["qf_kwargs"]) for _ in range(4))
-    if td3:                                                   # as experiment()'s TD3 branch
-        policy = TanhMlpPolicy(input_size=O, output_size=A, rs=rs, **variant["policy_kwargs"])
-        target_policy = TanhMlpPolicy(input_size=O, output_size=A, rs=rs, **variant["policy_kwargs"])
-        eval_policy = policy
-        expl_policy = PolicyWrappedWithExplorationStrategy(
-            exploration_strategy=GaussianStrategy(max_sigma=0.1, min_sigma=0.1, seed=seed), policy=policy)
-        trainer = TD3Trainer(policy=policy, qf1=qf1, qf2=qf2, target_qf1=tqf1, target_qf2=tqf2,
-                             target_policy=target_policy, batch_size=ak["batch_size"], noise_seed=seed, device=device,
-                             **tk)
-        policy._noise = expl_policy.es._rs
-    else:
-        policy = TanhGaussianPolicy(obs_dim=O, action_dim=A, rs=rs, noise=np.random.RandomState(seed),
-                                    **variant["policy_kwargs"])
-        eval_policy, expl_policy = MakeDeterministic(policy), policy
-        trainer = SACTrainer(env=eval_env, policy=policy, qf1=qf1, qf2=qf2, target_qf1=tqf1, target_qf2=tqf2,
-                             batch_size=ak["batch_size"], noise_seed=seed, device=device, **tk)
-    if acting != "host" and not runs_general_step(trainer):
-        policy.acting = "device"
-    elif acting == "device_all":
-        policy.acting = "device_all"
-    buf = EnvReplayBuffer(variant["replay_buffer_size"], obs_dim=O, action_dim=A, device=device)
-    buf.seed_from_numpy(rs)                                   # (the stream np.random would continue with)
-    expl, evalc = PathCollector(expl_env, expl_policy), PathCollector(eval_env, eval_policy)
-    if prefill and ak.get("min_num_steps_before_training", 0) > 0:
-        buf.add_paths(expl.collect_new_paths(ak["expl_max_path_length"], ak["min_num_steps_before_training"], False))
-        expl.end_epoch(-1)
-    host_rngs = dict(policy_noise=policy._noise, expl_env=expl_env._rs, eval_env=eval_env._rs)
-    return dict(seed=seed, ak=ak, trainer=trainer, buf=buf, expl=expl, evalc=evalc, rows=[], fh=None, writer=None,
-                variant=variant, host_rngs=host_rngs)
+    r = _build_run(variant, seed, O, A, device, acting, rs)
+    r["buf"].seed_from_numpy(rs)                              # (the stream np.random would continue with)
+    if prefill:
+        _prefill(r)
+    return r
 
 
 def _group_checkpoint(runs, checkpoint_dir, restore, chunk_rows):
@@ -689,71 +729,28 @@ def _group_checkpoint(runs, checkpoint_dir, restore, chunk_rows):
     if not restore:
         return ck, 0
     extras = ck.load([r["trainer"] for r in runs], [r["buf"] for r in runs], [r["identity"] for r in runs])
-    first_epoch = int(extras[0]["epoch"]) + 1
-    for r, extra in zip(runs, extras):
-        for k, rs in r["host_rngs"].items():
-            _rs_unpack(rs, extra[k])
-        r["expl"].num_steps_total, r["expl"].num_paths_total = extra["expl_totals"]
-        r["evalc"].num_steps_total, r["evalc"].num_paths_total = extra["eval_totals"]
-        r["trainer"].end_epoch(first_epoch - 1)
-    return ck, first_epoch
+    first_epochs = [_restore_extra(r, extra) for r, extra in zip(runs, extras)]
+    return ck, first_epochs[0]                                # (one generation: every run saved the same epoch)
 
 
-def _group_save(ck, runs, epoch):
-    extras = []
-    for r in runs:
-        extra = dict(epoch=epoch, seed=r["seed"], expl_totals=[r["expl"].num_steps_total, r["expl"].num_paths_total],
-                     eval_totals=[r["evalc"].num_steps_total, r["evalc"].num_paths_total])
-        extra.update({k: _rs_pack(rs) for k, rs in r["host_rngs"].items()})
-        extras.append(extra)
-    ck.save([r["trainer"] for r in runs], [r["buf"] for r in runs], [r["identity"] for r in runs], extras)
-
-
-def _q_general_kw(q_general):
-    """q_general (eval_general) as the `general` keyword of q_values / q_values_many (evaluate / evaluate_many): left out
-    at the default, so the call is what it was."""
-    return {} if q_general == "host" else {"general": q_general}
-
-
-def _eval_stats_kw(eval_stats):
-    """eval_stats as the `stats` keyword of evaluate / evaluate_many: left out at the default, as _q_general_kw does."""
-    return {} if eval_stats == "host" else {"stats": eval_stats}
-
-
-def _group_q_information(runs, q_general="host"):
-    """q_bias_information of every run's evaluation paths of this epoch, qf1 and qf2 of all runs from ONE q_values_many
-    call (one launch per 16 runs with the fused kernels' shapes and 1024 rows; q_general="device": the runs of the
-    general step from one sac_q_values_general_many call per 16 of them, otherwise from the host path)."""
-    steps = [_path_steps(r["evalc"].epoch_paths, r["trainer"].obs_dim, r["trainer"].act_dim) for r in runs]
-    qs = q_values_many([r["trainer"] for r in runs], [s[0] for s in steps], [s[1] for s in steps],
-                       [("qf1", "qf2")] * len(runs), **_q_general_kw(q_general))
-    return [q_bias_information(r["evalc"].epoch_paths, q[0], q[1], r["trainer"].discount, r["trainer"].reward_scale)
-            for r, q in zip(runs, qs)]
-
-
-def _group_epochs(runs, train_block, n_epochs, n_train, log_dir, quiet, what, ck=None, first_epoch=0, acting="host",
-                  sessions=True, general_sessions=None, q_diagnostics=False, q_general="host", validation=False,
-                  eval_general="host", eval_stats="host", replay_eval=0):
+def _group_epochs(*, runs, train_block, n_epochs, n_train, log_dir, quiet, what, opts, acting, sessions, general_sessions,
+                  ck, first_epoch):
     """The epoch loop of a grouped experiment: each run collects its paths, then train_block() trains every run at once,
-    then every run ends its epoch, the group is saved (with a GroupCheckpoint `ck`), and each run writes its row (to
-    <log_dir>/<run["sub"]>/progress.csv with log_dir; appended to after a resume).
-    acting="device": the runs collect in lockstep (GroupPathCollector) -- the evaluation phase of all runs, then the
-    exploration phase of all runs, every tick's actions from one act_many call (sessions=True: from one acting-session
-    call, GroupActor, one session for each phase's collectors; the rows are the same); each run's time/*sampling (s) columns
-    then hold the shared phase time.  acting="device_all": the same, and the lockstep collectors send the runs of the
-    general step to the device as well (general="device"; with sessions=True, general_sessions says whether they get
-    acting sessions of their own, None: GroupActor's default -- the rows are the same either way).
-    q_diagnostics=True: as experiment()'s, qf1 and qf2 of ALL runs on their evaluation paths from one q_values_many call
-    per epoch, behind the runs' evaluation paths and in front of the training block; its time is added to every run's
-    time/evaluation sampling (s); q_general is q_values_many's `general` for that call.
-    validation=True: as experiment()'s, ALL runs on their evaluation paths from one evaluate_many call per epoch, at the
-    same place and with the same accounting of its time; eval_general is evaluate_many's `general` for that call and
-    eval_stats its `stats`.
-    replay_eval=N > 0: as experiment()'s, ALL runs on rows of their replay buffers from one evaluate_replay_many call per
-    epoch, in front of the epoch's exploration paths and the training block (each buffer as the run's own experiment()
-    sees it there); eval_general and eval_stats apply to it too.  Its time is added to every run's
-    time/evaluation sampling (s), and, where the runs collect one after the other and the call stands in front of them
-    all, to every run's time/epoch (s) as well: a row's phases stay inside its epoch."""
+    then every run ends its epoch, the group is saved (with a GroupCheckpoint `ck`: one generation for the whole group,
+    and the epoch ends behind the save), and each run writes its row (to <log_dir>/<run["sub"]>/progress.csv with
+    log_dir; appended to after a resume).
+    acting="host": the runs collect one after the other -- evaluation paths, exploration paths, add_paths each.  The
+    replay evaluation of all runs stands in front of them all (each buffer as the run's own experiment() sees it there),
+    Q bias and validation of all runs behind them all (nobody has trained since the first run's evaluation paths).  The
+    seconds of these calls are added to every run's time/evaluation sampling (s); the replay evaluation's also to its
+    time/epoch (s), the run's start taken that much earlier: a row's phases stay inside its epoch.
+    acting="device": the runs collect in lockstep (GroupPathCollector) -- the evaluation phase of all runs, the
+    evaluations of `opts` (EvalOptions) in experiment()'s order, then the exploration phase of all runs, every tick's
+    actions from one act_many call (sessions=True: from one acting-session call, GroupActor, one session for each
+    phase's collectors; the rows are the same); each run's time/*sampling (s) columns then hold the shared phase time.
+    acting="device_all": the same, and the lockstep collectors send the runs of the general step to the device as well
+    (general="device"; with sessions=True, general_sessions says whether they get acting sessions of their own, None:
+    GroupActor's default -- the rows are the same either way)."""
     t_start = time.time()
     lockstep = acting != "host"
     lock_kw = dict(sessions=sessions, general="device" if acting == "device_all" else "host", general_sessions=general_sessions)
@@ -766,9 +763,7 @@ def _group_epochs(runs, train_block, n_epochs, n_train, log_dir, quiet, what, ck
                 t0 = time.time()
                 lock_eval.collect_new_paths([(r["ak"]["eval_max_path_length"], r["ak"]["num_eval_steps_per_epoch"], True)
                                              for r in runs])
-                q_infos = _group_q_information(runs, q_general) if q_diagnostics else None
-                v_infos = _group_validation(runs, epoch, eval_general, eval_stats) if validation else None
-                r_infos = _group_replay_eval(runs, epoch, replay_eval, eval_general, eval_stats) if replay_eval else None
+                blocks, _ = _epoch_evaluations(runs, epoch, opts)
                 t1 = time.time()
                 new = lock_expl.collect_new_paths([(r["ak"]["expl_max_path_length"],
                                                     r["ak"]["num_expl_steps_per_train_loop"], False) for r in runs])
@@ -777,75 +772,36 @@ def _group_epochs(runs, train_block, n_epochs, n_train, log_dir, quiet, what, ck
                     s0 = time.time()
                     r["buf"].add_paths(new_paths)
                     times.append((t0, t1 - t0, t2 - t1, time.time() - s0))
-            r_s = 0.0
-            if replay_eval and not lockstep:                  # (in front of every run's new rows: the buffers of experiment())
-                s0 = time.time()
-                r_infos = _group_replay_eval(runs, epoch, replay_eval, eval_general, eval_stats)
-                r_s = time.time() - s0
-            for r in runs if not lockstep else ():
-                ak = r["ak"]
-                t0 = time.time()
-                r["evalc"].collect_new_paths(ak["eval_max_path_length"], ak["num_eval_steps_per_epoch"], True)
-                t1 = time.time()
-                new_paths = r["expl"].collect_new_paths(ak["expl_max_path_length"], ak["num_expl_steps_per_train_loop"], False)
-                t2 = time.time()
-                r["buf"].add_paths(new_paths)
-                # (the replay evaluation stood in front of every run's t0: each run's epoch starts that much earlier, so
-                # that its time/evaluation sampling (s) lies inside its time/epoch (s))
-                times.append((t0 - r_s, t1 - t0 + r_s, t2 - t1, time.time() - t2))
-            if q_diagnostics and not lockstep:                # (nobody has trained since the first run's evaluation paths)
-                s0 = time.time()
-                q_infos = _group_q_information(runs, q_general)
-                q_s = time.time() - s0
-                times = [(a0, eval_s + q_s, expl_s, store_s) for a0, eval_s, expl_s, store_s in times]
-            if validation and not lockstep:
-                s0 = time.time()
-                v_infos = _group_validation(runs, epoch, eval_general, eval_stats)
-                v_s = time.time() - s0
-                times = [(a0, eval_s + v_s, expl_s, store_s) for a0, eval_s, expl_s, store_s in times]
+            else:
+                blocks, r_s = _epoch_evaluations(runs, epoch, opts, take=("replay",))
+                for r in runs:
+                    ak = r["ak"]
+                    t0 = time.time()
+                    r["evalc"].collect_new_paths(ak["eval_max_path_length"], ak["num_eval_steps_per_epoch"], True)
+                    t1 = time.time()
+                    new_paths = r["expl"].collect_new_paths(ak["expl_max_path_length"], ak["num_expl_steps_per_train_loop"], False)
+                    t2 = time.time()
+                    r["buf"].add_paths(new_paths)
+                    times.append((t0 - r_s, t1 - t0 + r_s, t2 - t1, time.time() - t2))
+                behind, b_s = _epoch_evaluations(runs, epoch, opts, take=("q", "validation"))
+                for b, more in zip(blocks, behind):
+                    b.update(more)
+                times = [(a0, eval_s + b_s, expl_s, store_s) for a0, eval_s, expl_s, store_s in times]
             t3 = time.time()
             train_block()
             t4 = time.time()
-            ended = []
-            for r in runs:
-                row = _progress_row(r["buf"], r["trainer"], r["expl"], r["evalc"], r["ak"])
-                if q_diagnostics:
-                    row.update(q_infos[len(ended)])
-                if validation:
-                    row.update(v_infos[len(ended)])
-                if replay_eval:
-                    row.update(r_infos[len(ended)])
-                for x in (r["trainer"], r["buf"], r["expl"], r["evalc"]):
-                    x.end_epoch(epoch)
-                ended.append((row, time.time()))
+            ended = [(_end_epoch_row(r, b, epoch), time.time()) for r, b in zip(runs, blocks)]
             t6 = time.time()
-            if ck is not None:                                # one generation for the whole group
-                _group_save(ck, runs, epoch)
+            if ck is not None:
+                ck.save([r["trainer"] for r in runs], [r["buf"] for r in runs], [r["identity"] for r in runs],
+                        [_pack_extra(r, epoch) for r in runs])
             t7 = time.time()
             for r, (a0, eval_s, expl_s, store_s), (row, t5) in zip(runs, times, ended):
                 t_end = t7 if ck is not None else t5
-                row["time/data storing (s)"] = store_s
-                row["time/evaluation sampling (s)"] = eval_s
-                row["time/exploration sampling (s)"] = expl_s
-                row["time/logging (s)"] = t5 - t4
-                row["time/saving (s)"] = t7 - t6 if ck is not None else 0.0
-                row["time/training (s)"] = t4 - t3            # (the group's block: every run's steps at once)
-                row["time/epoch (s)"] = t_end - a0
-                row["time/total (s)"] = t_end - t_start
-                row["Epoch"] = epoch
-                r["rows"].append(row)
-                if log_dir is not None:
-                    if r["writer"] is None:
-                        d = os.path.join(log_dir, r["sub"])
-                        os.makedirs(d, exist_ok=True)
-                        path = os.path.join(d, "progress.csv")
-                        appending = first_epoch > 0 and os.path.exists(path)
-                        r["fh"] = open(path, "a" if appending else "w", newline="")
-                        r["writer"] = csv.DictWriter(r["fh"], fieldnames=list(row.keys()))
-                        if not appending:
-                            r["writer"].writeheader()
-                    r["writer"].writerow(row)
-                    r["fh"].flush()
+                _stamp_times(row, epoch, storing=store_s, evaluation=eval_s, exploration=expl_s, logging=t5 - t4,
+                             saving=t7 - t6 if ck is not None else 0.0, training=t4 - t3,   # (the group's block)
+                             epoch_s=t_end - a0, total=t_end - t_start)
+                _log_row(r, row, None if log_dir is None else os.path.join(log_dir, r["sub"]), first_epoch)
             if not quiet:
                 print(f"epoch {epoch}: {len(runs)} {what}, training {t4 - t3:.3f}s "
                       f"({len(runs) * n_train / max(t4 - t3, 1e-9):.0f} steps/s together)", flush=True)
@@ -882,24 +838,10 @@ def experiment_group(variant, seeds, log_dir=None, num_epochs=None, obs_dim=None
     experiment(variant, seed=s, acting="device").  "device_all": the same, with the runs of the general step acting on the
     device too (one sac_policy_act_general_many call per tick and 16 of them; with sessions and general_sessions=True one
     sac_gactor_act call, None: GroupActor's default); rows as experiment(..., acting="device_all").
-    q_diagnostics=True: experiment()'s critic columns for every seed, all seeds' Q values from one q_values_many call per
-    epoch; each seed's rows are those of experiment(variant, seed=s, q_diagnostics=True).  q_general as for experiment()
-    (general-step seeds: one sac_q_values_general_many call per 16 of them with "device").
-    validation=True: experiment()'s validation/ columns for every seed, all seeds from one evaluate_many call per epoch;
-    each seed's rows are those of experiment(variant, seed=s, validation=True).  A TD3 variant is refused.
-    eval_general as for experiment() (general-step seeds: one sac_evaluate_general_many call per 16 of them with "device"),
-    eval_stats too (the seeds evaluated on the device: their statistics from the same call, sac_evaluate_stats_many).
-    replay_eval=N: experiment()'s replay/ columns for every seed, all seeds from one evaluate_replay_many call per epoch;
-    each seed's columns are those of experiment(variant, seed=s, replay_eval=N).  A TD3 variant is refused."""
-    check_stats(eval_stats)
-    check_acting(acting)
-    check_general(q_general)
-    check_general(eval_general)
-    replay_eval = check_replay_eval(replay_eval)
-    if validation:
-        _refuse_td3_validation(variant, "experiment_group")
-    if replay_eval:
-        _refuse_td3_replay_eval(variant, "experiment_group")
+    q_diagnostics, q_general, validation, eval_general, eval_stats, replay_eval: the per-epoch evaluations, EvalOptions;
+    each seed's rows are those of experiment(variant, seed=s) with the same options."""
+    opts = _options("experiment_group", [(variant,)], acting, q_diagnostics, q_general, validation, eval_general,
+                    eval_stats, replay_eval)
     if resume and not checkpoint_dir:
         raise RuntimeError("experiment_group(resume=True) needs the checkpoint_dir to resume from")
     validate(variant)
@@ -923,10 +865,9 @@ def experiment_group(variant, seeds, log_dir=None, num_epochs=None, obs_dim=None
     else:
         group = (TD3TrainerGroup if td3 else SACTrainerGroup)([r["trainer"] for r in runs])
         train_block = lambda: group.train_loop([r["buf"] for r in runs], n_train, batch_size=ak["batch_size"])  # noqa: E731
-    _group_epochs(runs, train_block,
-                  num_epochs if num_epochs is not None else ak["num_epochs"], n_train, log_dir, quiet, "seeds", ck,
-                  first_epoch, acting, sessions, general_sessions, q_diagnostics, q_general, validation, eval_general, eval_stats,
-                  replay_eval)
+    _group_epochs(runs=runs, train_block=train_block, n_epochs=num_epochs if num_epochs is not None else ak["num_epochs"],
+                  n_train=n_train, log_dir=log_dir, quiet=quiet, what="seeds", opts=opts, acting=acting, sessions=sessions,
+                  general_sessions=general_sessions, ck=ck, first_epoch=first_epoch)
     return {r["seed"]: r["rows"] for r in runs}
 
 
@@ -972,21 +913,11 @@ def experiment_sweep(runs, log_dir=None, num_epochs=None, device=0, quiet=False,
     lockstep ticks (act_many), so each run's rows stay those of its solo experiment(..., acting="device").  Under
     "device_all" those runs act on the device inside the same ticks, and each run's rows are those of its solo
     experiment(..., acting="device_all").
-    q_diagnostics as for experiment_group (the runs of the general step take q_values' host path inside the same call;
-    with q_general="device" they are evaluated on the device, one sac_q_values_general_many call per 16 of them).
-    validation as for experiment_group (the runs of the general step take evaluate's host path inside the same call;
-    with eval_general="device" they are evaluated on the device, one sac_evaluate_general_many call per 16 of them); TD3
-    sweeps are refused.  eval_stats as for experiment_group.
-    replay_eval as for experiment_group (one evaluate_replay_many call per epoch over all runs); TD3 sweeps are refused."""
-    check_stats(eval_stats)
-    check_acting(acting)
-    check_general(q_general)
-    check_general(eval_general)
-    replay_eval = check_replay_eval(replay_eval)
-    for spec in runs if validation else ():
-        _refuse_td3_validation(tuple(spec)[0], "experiment_sweep")
-    for spec in runs if replay_eval else ():
-        _refuse_td3_replay_eval(tuple(spec)[0], "experiment_sweep")
+    q_diagnostics, q_general, validation, eval_general, eval_stats, replay_eval: the per-epoch evaluations, EvalOptions,
+    as for experiment_group; in a hidden sweep the runs of the general step take the host path inside the same call, or
+    the device's under q_general / eval_general "device".  A sweep with a TD3 run refuses validation and replay_eval."""
+    opts = _options("experiment_sweep", runs, acting, q_diagnostics, q_general, validation, eval_general, eval_stats,
+                    replay_eval)
     if resume and not checkpoint_dir:
         raise RuntimeError("experiment_sweep(resume=True) needs the checkpoint_dir to resume from")
     specs = []
@@ -1034,8 +965,8 @@ def experiment_sweep(runs, log_dir=None, num_epochs=None, device=0, quiet=False,
         group = (MixedTD3TrainerGroup if td3 else MixedSACTrainerGroup)([r["trainer"] for r in group_runs])
     n_train = ak0["num_trains_per_train_loop"]
     batches = [r["ak"]["batch_size"] for r in group_runs]
-    _group_epochs(group_runs, lambda: group.train_loop([r["buf"] for r in group_runs], n_train, batch_sizes=batches),
-                  num_epochs if num_epochs is not None else ak0["num_epochs"], n_train, log_dir, quiet, "runs", ck,
-                  first_epoch, acting, sessions, general_sessions, q_diagnostics, q_general, validation, eval_general, eval_stats,
-                  replay_eval)
+    _group_epochs(runs=group_runs, n_epochs=num_epochs if num_epochs is not None else ak0["num_epochs"], n_train=n_train,
+                  train_block=lambda: group.train_loop([r["buf"] for r in group_runs], n_train, batch_sizes=batches),
+                  log_dir=log_dir, quiet=quiet, what="runs", opts=opts, acting=acting, sessions=sessions,
+                  general_sessions=general_sessions, ck=ck, first_epoch=first_epoch)
     return [r["rows"] for r in group_runs]

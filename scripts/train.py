@@ -99,21 +99,23 @@ def build_parser():
 
 if __name__ == "__main__":
     args = build_parser().parse_args()
-    eval_kw = {} if args.eval_general == "host" else dict(eval_general=args.eval_general)
+    # the option keywords of all three entries (driver.EvalOptions, and acting); the later ones are left out at their defaults
+    option_kw = dict(acting=args.acting, q_diagnostics=args.q_diagnostics, q_general=args.q_general, validation=args.validation)
+    if args.eval_general != "host":
+        option_kw["eval_general"] = args.eval_general
     if args.eval_stats != "host":
-        eval_kw["eval_stats"] = args.eval_stats
+        option_kw["eval_stats"] = args.eval_stats
     if args.replay_eval:
-        eval_kw["replay_eval"] = args.replay_eval
+        option_kw["replay_eval"] = args.replay_eval
     if (args.hidden_sweep or args.hidden_sizes) and not args.variants:
         raise SystemExit("--hidden_sweep / --hidden_sizes need --variants")
     if args.variants or args.seeds:
         log_dir = args.resume or args.log_dir
         if args.checkpoint and not log_dir:
             raise SystemExit("--checkpoint needs --log_dir (the group is saved to <log_dir>/checkpoint)")
-        group_kw = dict(log_dir=log_dir, num_epochs=args.epochs, resume=bool(args.resume), acting=args.acting,
-                        q_diagnostics=args.q_diagnostics, q_general=args.q_general, validation=args.validation,
+        group_kw = dict(log_dir=log_dir, num_epochs=args.epochs, resume=bool(args.resume),
                         checkpoint_dir=os.path.join(log_dir, "checkpoint") if (args.checkpoint or args.resume) else None,
-                        **eval_kw)
+                        **option_kw)
         try:
             if args.variants:
                 seeds = args.seeds or [args.seed]
@@ -149,5 +151,4 @@ if __name__ == "__main__":
         json.dump(variant, open(os.path.join(run_dir, "variant.json"), "w"), indent=2, sort_keys=True)
     ckpt = os.path.join(run_dir, "checkpoint") if (run_dir and not args.no_checkpoint) else None
     experiment(variant, log_dir=run_dir, seed=args.seed, num_epochs=args.epochs, checkpoint_dir=ckpt,
-               resume=bool(args.resume), acting=args.acting, q_diagnostics=args.q_diagnostics,
-               q_general=args.q_general, validation=args.validation, **eval_kw)
+               resume=bool(args.resume), **option_kw)

@@ -95,8 +95,7 @@ def test_drivers_and_train_script_take_eval_general():
         assert inspect.signature(fn).parameters["eval_general"].default == "host", fn.__name__
         with pytest.raises(RuntimeError, match="general"):       # (checked in front of everything else)
             fn(*args, eval_general="gpu")
-    assert inspect.signature(driver._group_epochs).parameters["eval_general"].default == "host"
-    assert inspect.signature(driver._group_validation).parameters["eval_general"].default == "host"
+    assert driver.EvalOptions._field_defaults["eval_general"] == "host"
     for fn in (SACTrainer.evaluate, TD3Trainer.evaluate, evaluate_many, ArchSACTrainerGroup.evaluate_many):
         assert inspect.signature(fn).parameters["general"].default == "host", fn.__qualname__
     # the keyword is left out of the calls at the default: a replacement of evaluate with the old signature still serves

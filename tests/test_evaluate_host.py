@@ -165,8 +165,9 @@ def test_bindings_header_and_drivers_name_the_feature():
     assert tuple(_lib.EVAL_ROWS) == ROW_COLUMNS and len(_lib.SacEvalIO._fields_) == 13
     assert _lib.SacEvalIO.alpha.offset == 12 * 8                     # twelve pointers, then the float
     from robosuite_benchmark_amd import driver
-    for fn in (driver.experiment, driver.experiment_group, driver.experiment_sweep, driver._group_epochs):
+    for fn in (driver.experiment, driver.experiment_group, driver.experiment_sweep):
         assert inspect.signature(fn).parameters["validation"].default is False, fn.__name__
+    assert driver.EvalOptions._field_defaults["validation"] is False
     out = subprocess.run([sys.executable, os.path.join(ROOT, "scripts", "train.py"), "--help"], capture_output=True,
                          text=True, check=True).stdout
     assert "--validation" in out

@@ -79,8 +79,9 @@ def test_defaults():
         p = inspect.signature(fn).parameters
         assert p["general"].default == "host" and p["stats"].default == "host", fn.__qualname__
         assert p["n"].default is None and p["indices"].default is None and p["rows"].default is False, fn.__qualname__
-    for fn in (driver.experiment, driver.experiment_group, driver.experiment_sweep, driver._group_epochs):
+    for fn in (driver.experiment, driver.experiment_group, driver.experiment_sweep):
         assert inspect.signature(fn).parameters["replay_eval"].default == 0, fn.__name__
+    assert driver.EvalOptions._field_defaults["replay_eval"] == 0
     for bad in (-1, 1.5, "many", True):
         for fn, args in ((driver.experiment, (None,)), (driver.experiment_group, (None, None)), (driver.experiment_sweep, (None,))):
             with pytest.raises(RuntimeError, match="replay_eval is a row count"):

@@ -127,9 +127,9 @@ def test_stats_defaults_to_host_everywhere():
     assert sac.STATS == ("host", "device")
     for fn in (SACTrainer.evaluate, TD3Trainer.evaluate, evaluate_many, ArchSACTrainerGroup.evaluate_many):
         assert inspect.signature(fn).parameters["stats"].default == "host", fn.__qualname__
-    for fn in (driver.experiment, driver.experiment_group, driver.experiment_sweep, driver._group_epochs,
-               driver._group_validation):
+    for fn in (driver.experiment, driver.experiment_group, driver.experiment_sweep):
         assert inspect.signature(fn).parameters["eval_stats"].default == "host", fn.__name__
+    assert driver.EvalOptions._field_defaults["eval_stats"] == "host"
     # the keyword is left out of the calls at the default: a replacement of evaluate with the old signature still serves
     assert driver._eval_stats_kw("host") == {} and driver._eval_stats_kw("device") == dict(stats="device")
     out = subprocess.run([sys.executable, os.path.join(ROOT, "scripts", "train.py"), "--help"], capture_output=True,

@@ -155,8 +155,9 @@ def test_bindings_and_header_name_the_entry_points():
 def test_drivers_take_q_diagnostics():
     import inspect
     from robosuite_benchmark_amd import driver
-    for fn in (driver.experiment, driver.experiment_group, driver.experiment_sweep, driver._group_epochs):
+    for fn in (driver.experiment, driver.experiment_group, driver.experiment_sweep):
         assert inspect.signature(fn).parameters["q_diagnostics"].default is False, fn.__name__
+    assert driver.EvalOptions._field_defaults["q_diagnostics"] is False
     out = subprocess.run([sys.executable, os.path.join(ROOT, "scripts", "train.py"), "--help"], capture_output=True,
                          text=True, check=True).stdout
     assert "--q_diagnostics" in out
