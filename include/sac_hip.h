@@ -235,6 +235,12 @@ int sac_trainer_destroy(sac_trainer_t *t);
 /* flat fp32 parameter vector of one net, nn.Linear layout (W (out,in) row-major, then b):
  *   Q nets : fc0.W fc0.b fc1.W fc1.b last_fc.W last_fc.b
  *   policy : fc0.W fc0.b fc1.W fc1.b last_fc.W last_fc.b last_fc_log_std.W last_fc_log_std.b */
+/* The six getters and setters below return, or overwrite, the state AS OF THE LAST COMPLETED STEP -- the one the counters
+ * in `scalars` name.  A trainer on the fused step may have up to 47 sac_step_device steps in flight that nobody has
+ * verified; each of these entries first waits for them and, if a fused launch among them gave up, re-runs the lost
+ * steps on the four-launch step (what sac_sync does), so a getter never returns parameters that lack steps the counters
+ * count, and a setter's state is never stepped on by steps launched in front of it.  Those re-runs read the buffers'
+ * slots: see sac_step_device for how long a buffer must live. */
 int64_t sac_param_count(const sac_trainer_t *t, int net);
 int sac_set_params(sac_trainer_t *t, int net, const float *flat, int64_t n);
 int sac_get_params(sac_trainer_t *t, int net, float *flat, int64_t n);
@@ -255,7 +261,12 @@ int sac_step(sac_trainer_t *t, const float *obs, const float *act, const float *
 
 /* trainer.train(batch) on a device-resident batch (token of sac_random_batch_device on `buf`): four kernel
  * launches behind the gather, no host copy, no synchronisation -- unless diag != NULL, which copies the step's
- * diagnostics out (rlkit reads them on the first step of an epoch only).  Noise: the device stream. */
+ * diagnostics out (rlkit reads them on the first step of an epoch only).  Noise: the device stream.
+ * Lifetime: with diag == NULL the trainer keeps (buf, token) on record until it has seen the step applied, and a later
+ * call that settles it (sac_sync, a step with diag, sac_train_loop, sac_get_* / sac_set_*, sac_policy_mirror /
+ * sac_policy_act, sac_trainer_set_xcd_mask) may re-run the step from buf's slot.  `buf` must therefore outlive a
+ * sac_sync -- or a sac_trainer_destroy -- of every trainer that stepped on its device batches: sac_buffer_destroy does
+ * not know of these records. */
 int sac_step_device(sac_trainer_t *t, sac_buffer_t *buf, int64_t token, float diag[SAC_DIAG_N]);
 
 /* The whole hot loop of rlkit_custom.py:234-238 on the device:
@@ -312,6 +323,8 @@ int sac_profile_loop(sac_trainer_t *t, sac_buffer_t *buf, int64_t n_steps, float
 int sac_buffer_set_xcd(sac_buffer_t *buf, int xcd);
 int sac_trainer_set_xcd(sac_trainer_t *t, int xcd);
 int sac_buffer_set_xcd_mask(sac_buffer_t *buf, unsigned xcd_mask);
+/* (sac_trainer_set_xcd[_mask] settles the trainer first, like the state getters above: unverified fused steps are looked
+ *  at, and re-run if lost, on the stream they were launched on, before that stream is replaced.) */
 int sac_trainer_set_xcd_mask(sac_trainer_t *t, unsigned xcd_mask);
 
 /* SURVEY.md 8d "Bounding roofline": the peaks the roofline fractions divide by, MEASURED on the box -- a float4
@@ -327,7 +340,8 @@ int64_t sac_debug_fetch(sac_trainer_t *t, const char *name, float *out, int64_t 
 
 /* policy.get_action(obs) on the HOST with weights mirrored from the device (acting path,
  * /root/reference/util/rlkit_custom.py:437; MakeDeterministic => tanh(mean)).
- * eps (A floats) may be NULL when deterministic. */
+ * eps (A floats) may be NULL when deterministic.  The mirror is a state read: it holds the policy as of the last completed
+ * step (see sac_get_params), and sac_policy_act takes a new one on its first call behind any step. */
 int sac_policy_mirror(sac_trainer_t *t);
 int sac_policy_act(sac_trainer_t *t, const float *obs, int deterministic, const float *eps, float *act);
 /* policy.get_actions(obs) on the DEVICE from the live weights: n rows in one launch (k_act, csrc/sac_act.h).  The kernel

@@ -131,8 +131,26 @@ def save_checkpoint(dirname, trainer, replay_buffer=None, extra=None):
     return man
 
 
+def adopt_noise_seed(trainer, noise_seed, batch_size):
+    """A loading trainer takes over the saved run's noise stream, and owns a handle afterwards: the rsample / target-noise
+    draws of step n are a function of (noise_seed, n), and a handle is keyed when it is created -- so a trainer without
+    one gets it (for `batch_size` rows) under the saved seed, and one whose handle was keyed otherwise (noise_seed=None
+    is a process-derived value) gets a new one for its own batch size.  Called behind every check of a load and in front
+    of load_state_dict.  noise_seed None (a save that recorded none): the trainer keeps its own."""
+    if noise_seed is not None:
+        noise_seed = int(noise_seed) & 0xFFFFFFFFFFFFFFFF
+        if noise_seed != trainer.noise_seed:
+            trainer.noise_seed = noise_seed
+            trainer._eval_rng = None                   # (evaluate's private stream is seeded from noise_seed on first use)
+            if trainer._h is not None:
+                trainer._create(trainer._batch)
+    if trainer._h is None:
+        trainer._create(int(batch_size))
+
+
 def load_checkpoint(dirname, trainer, replay_buffer=None):
-    """Restore trainer (and buffer) state saved by save_checkpoint; returns the manifest's `extra`."""
+    """Restore trainer (and buffer) state saved by save_checkpoint; returns the manifest's `extra`.  The trainer continues
+    on the saved run's noise stream (adopt_noise_seed); its other hyperparameters stay as it was built."""
     cdir = current_dir(dirname)
     if cdir is None:
         raise FileNotFoundError(f"{dirname}: no complete checkpoint")
@@ -164,8 +182,7 @@ def load_checkpoint(dirname, trainer, replay_buffer=None):
         bs = dict(man["buffer"])
         for k in ("observations", "actions", "rewards", "next_observations", "terminals", "rng_key"):
             bs[k] = arr("buffer." + k)
-    if trainer._h is None:
-        trainer._create(int(tm["batch_size"]))
+    adopt_noise_seed(trainer, tm.get("hparams", {}).get("noise_seed"), int(tm["batch_size"]))
     trainer.load_state_dict(st)
     trainer._num_train_steps = int(tm["num_train_steps"])
     if bs is not None:

@@ -2344,6 +2344,16 @@ int recover_device_steps(sac_trainer *t) {
     return wait_trainer_stream(t);
 }
 
+// Settle a trainer in front of an entry that reads or overwrites its state outside any step path (sac_get_* / sac_set_*,
+// the acting mirror, sac_trainer_set_xcd_mask): fused steps that nobody has verified yet are waited for, and if one of
+// them gave up the lost steps are re-run, so that the caller sees the state as of the last completed step -- the one the
+// counters already name.  A trainer with nothing unverified (and every general-step trainer) returns at once.
+int settle_trainer(sac_trainer *t) {
+    if (!t->fused || (t->pend_n == 0 && t->fused_unchecked == 0)) return 0;
+    if (wait_trainer_stream(t)) return -1;
+    return recover_device_steps(t) < 0 ? -1 : 0;
+}
+
 // sample + gather all slots of a loop on the buffer's stream, make the trainer's stream wait
 int stage_batches(sac_trainer *t, sac_buffer *b, int64_t n_steps) {
     if (readahead_rollback(b)) return -1;
@@ -2786,6 +2796,7 @@ int sac_set_params(sac_trainer_t *t, int net, const float *flat, int64_t n) {
     SAC_REQUIRE(n == sac_param_count(t, net), "net %d expects %lld parameters, got %lld", net,
                 (long long)sac_param_count(t, net), (long long)n);
     SAC_HIP(hipSetDevice(t->device));
+    if (settle_trainer(t)) return -1;
     t->mirror_valid = false;
     if (t->gen) return gen_upload(t, net, flat, t->gen->net[net].P);
     return upload_padded(t, net, flat, t->net[net].P, net < 3 ? t->net[net].PT : nullptr);
@@ -2796,6 +2807,7 @@ int sac_get_params(sac_trainer_t *t, int net, float *flat, int64_t n) {
     SAC_REQUIRE(n == sac_param_count(t, net), "net %d holds %lld parameters, buffer has %lld", net,
                 (long long)sac_param_count(t, net), (long long)n);
     SAC_HIP(hipSetDevice(t->device));
+    if (settle_trainer(t)) return -1;
     if (t->gen) return gen_download(t, net, t->gen->net[net].P, flat);
     return download_padded(t, net, t->net[net].P, flat);
 }
@@ -2804,6 +2816,7 @@ int sac_set_opt_state(sac_trainer_t *t, int net, const float *m, const float *v,
     SAC_REQUIRE(t && m && v && net >= 0 && net <= 2, "bad arguments to sac_set_opt_state (trained nets are 0..2)");
     SAC_REQUIRE(n == sac_param_count(t, net), "size mismatch in sac_set_opt_state");
     SAC_HIP(hipSetDevice(t->device));
+    if (settle_trainer(t)) return -1;
     if (t->gen) return gen_upload(t, net, m, t->gen->net[net].M) || gen_upload(t, net, v, t->gen->net[net].V) ? -1 : 0;
     if (upload_padded(t, net, m, t->net[net].M, t->net[net].MT)) return -1;
     return upload_padded(t, net, v, t->net[net].V, t->net[net].VT);
@@ -2813,6 +2826,7 @@ int sac_get_opt_state(sac_trainer_t *t, int net, float *m, float *v, int64_t n) 
     SAC_REQUIRE(t && m && v && net >= 0 && net <= 2, "bad arguments to sac_get_opt_state (trained nets are 0..2)");
     SAC_REQUIRE(n == sac_param_count(t, net), "size mismatch in sac_get_opt_state");
     SAC_HIP(hipSetDevice(t->device));
+    if (settle_trainer(t)) return -1;
     if (t->gen) return gen_download(t, net, t->gen->net[net].M, m) || gen_download(t, net, t->gen->net[net].V, v) ? -1 : 0;
     if (download_padded(t, net, t->net[net].M, m, t->net[net].MT)) return -1;
     return download_padded(t, net, t->net[net].V, v, t->net[net].VT);
@@ -2821,6 +2835,7 @@ int sac_get_opt_state(sac_trainer_t *t, int net, float *m, float *v, int64_t n) 
 int sac_set_scalars(sac_trainer_t *t, const double sc[6]) {
     SAC_REQUIRE(t && sc, "bad arguments to sac_set_scalars");
     SAC_HIP(hipSetDevice(t->device));
+    if (settle_trainer(t)) return -1;          // (lost steps are re-run in front of the new counters, not behind them)
     Ctl c;
     memset(&c, 0, sizeof(c));
     if (t->algo == 1) t->adam_t_pi = (long long)sc[0];            // TD3: sc[0] = optimizer steps of the (delayed) policy
@@ -2835,6 +2850,7 @@ int sac_set_scalars(sac_trainer_t *t, const double sc[6]) {
 int sac_get_scalars(sac_trainer_t *t, double sc[6]) {
     SAC_REQUIRE(t && sc, "bad arguments to sac_get_scalars");
     SAC_HIP(hipSetDevice(t->device));
+    if (settle_trainer(t)) return -1;
     Ctl c;
     SAC_HIP(hipMemcpyAsync(&c, t->d_ctl, sizeof(c), hipMemcpyDeviceToHost, t->stream));
     SAC_HIP(hipStreamSynchronize(t->stream));
@@ -3297,6 +3313,7 @@ extern "C" int sac_make_xcd_mask_stream(hipStream_t *out, unsigned xcd_mask);
 int sac_trainer_set_xcd_mask(sac_trainer_t *t, unsigned xcd_mask) {
     SAC_REQUIRE(t != nullptr, "null trainer");
     SAC_HIP(hipSetDevice(t->device));
+    if (settle_trainer(t)) return -1;        // (unverified fused steps: looked at, and re-run if lost, on the stream they ran on)
     SAC_HIP(hipStreamSynchronize(t->stream));
     hipStream_t ns = nullptr;
     if (sac_make_xcd_mask_stream(&ns, xcd_mask)) return -1;
@@ -3419,6 +3436,8 @@ int sac_fetch_stamps(sac_trainer_t *t, unsigned long long *out) {
 
 int sac_policy_mirror(sac_trainer_t *t) {
     SAC_REQUIRE(t, "null trainer");
+    SAC_HIP(hipSetDevice(t->device));
+    if (settle_trainer(t)) return -1;
     const int64_t n = sac_param_count(t, SAC_NET_POLICY);
     t->h_policy.resize((size_t)n);
     if (sac_get_params(t, SAC_NET_POLICY, t->h_policy.data(), n)) return -1;

@@ -27,7 +27,7 @@ from collections import OrderedDict
 
 import numpy as np
 
-from .checkpoint import _fsync_dir, _generations
+from .checkpoint import _fsync_dir, _generations, adopt_noise_seed
 
 FORMAT = "robosuite_benchmark_amd.group_checkpoint/1"
 DEFAULT_CHUNK_ROWS = 4096
@@ -326,15 +326,15 @@ class GroupCheckpoint:
         return state
 
 
-def _restore(dirname, trainer, buf, m, arrays):
+def _restore(dirname, trainer, buf, m, arrays, noise_seed=None):
     """One member from its verified state arrays and chunk files: the trainer's state, then the buffer as
-    EnvReplayBuffer.load_state_dict restores one (rows in storage order, cursor, generator)."""
+    EnvReplayBuffer.load_state_dict restores one (rows in storage order, cursor, generator).  noise_seed: the saved
+    member's, for a trainer that was not checked against the member's identity (load_group_member)."""
     nets = [k[len("params."):] for k in arrays if k.startswith("params.")]
     st = dict(params={n: arrays[f"params.{n}"] for n in nets},
               opt={n: (arrays[f"adam_m.{n}"], arrays[f"adam_v.{n}"]) for n in nets if f"adam_m.{n}" in arrays},
               scalars=arrays["trainer_scalars"])
-    if trainer._h is None:
-        trainer._create(int(m["trainer"]["batch_size"]))
+    adopt_noise_seed(trainer, noise_seed, int(m["trainer"]["batch_size"]))
     trainer.load_state_dict(st)
     trainer._num_train_steps = int(m["trainer"]["num_train_steps"])
     bm = m["buffer"]
@@ -353,7 +353,8 @@ def _restore(dirname, trainer, buf, m, arrays):
 
 def load_group_member(dirname, index, trainer, buffer):
     """Member `index` of the group checkpoint under `dirname` into an ordinary trainer and replay buffer (a run can then
-    go on solo).  Returns the member's extra (epoch, seed, host generators, collector totals)."""
+    go on solo, on the member's noise stream: checkpoint.adopt_noise_seed).  Returns the member's extra (epoch, seed, host
+    generators, collector totals)."""
     man = read_manifest(dirname)
     if not 0 <= int(index) < len(man["members"]):
         raise IndexError(f"{dirname}: the group has {len(man['members'])} members, no member {index}")
@@ -363,5 +364,5 @@ def load_group_member(dirname, index, trainer, buffer):
         raise GroupMismatchError(f"group member {index} ({ident['label']}): dims ({trainer.obs_dim},{trainer.act_dim}) "
                                  f"here, ({ident['obs_dim']},{ident['action_dim']}) in the checkpoint")
     st = GroupCheckpoint(dirname, man["chunk_rows"])._verify(man, int(index), m, buffer)
-    _restore(dirname, trainer, buffer, m, st)
+    _restore(dirname, trainer, buffer, m, st, noise_seed=ident.get("hparams", {}).get("noise_seed"))
     return m["extra"]

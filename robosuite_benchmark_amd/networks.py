@@ -121,11 +121,14 @@ class _Mlp:
 
     # The reference pickles these objects every epoch: ``logger.save_itr_params(epoch, snapshot)`` with the trainer's
     # networks and both collectors' policies in the snapshot (rlkit_custom.py:54-56,68-82).  A holder bound to a trainer
-    # first pulls its trained weights off the device and is saved WITHOUT the binding (a ctypes handle cannot be pickled):
-    # the loaded object is a self-contained host network, which is all rlkit_utils.py:173-174,241-250 need.
+    # -- whichever of its nets it is: the policy, a critic, a target -- first pulls its trained weights off the device and
+    # is saved WITHOUT the binding (a ctypes handle cannot be pickled): the loaded object is a self-contained host network,
+    # which is all rlkit_utils.py:173-174,241-250 need.  (flat(), state_dict() and as_layer_list() called directly on a
+    # bound holder do NOT pull: they read the host arrays as the last sync left them -- get_snapshot() or
+    # sync_networks_to_host() first.)
     def __getstate__(self):
         tr = self._trainer
-        if tr is not None and getattr(tr, "_h", None) is not None and tr.policy is self:
+        if tr is not None and getattr(tr, "_h", None) is not None:
             tr.sync_holder_to_host(self)
         st = dict(self.__dict__)
         st["_trainer"] = None
@@ -271,8 +274,10 @@ class TanhMlpPolicy(_Mlp):
     def get_actions(self, obs_np):
         obs = np.ascontiguousarray(np.atleast_2d(obs_np), dtype=np.float32)
         tr = self._trainer
-        if tr is not None and getattr(tr, "_h", None) is not None and tr.policy is self:
-            return self._act(tr, obs, True, None)  # sac_policy_act[_device] (TD3 handles: tanh(last_fc))
+        if tr is not None and getattr(tr, "_h", None) is not None:
+            if tr.policy is self:
+                return self._act(tr, obs, True, None)  # sac_policy_act[_device] (TD3 handles: tanh(last_fc))
+            tr.sync_holder_to_host(self)           # the target policy: its trained weights first, then the host forward
         h = obs
         names = list(self.layers)
         for n in names[:-1]:

@@ -73,6 +73,18 @@ class SACTrainer:
     # ---- handle management -----------------------------------------------------------------
     NETS = NET_IDS                           # name -> C net id (TD3Trainer adds target_policy)
 
+    # The replay buffers of device batches this trainer has stepped on WITHOUT waiting (train() returned None): the
+    # library keeps those steps on record by buffer and slot until it has seen them applied, and re-runs them from their
+    # slots should a fused step have given up -- at the next call that settles the trainer, which may be a state read long
+    # after the caller dropped its buffer (a DeviceBatch is gone as soon as train() returns).  The references keep such a
+    # buffer alive until then; every call that settles drops them (_settled).
+    _stepped_buffers = ()
+
+    def _settled(self):
+        """The library has just settled this trainer (a step that returned diagnostics, train_loop, a state read or write,
+        sac_sync): no step is on record for any buffer."""
+        self._stepped_buffers = ()
+
     def _new_handle(self, batch):
         hp, hq = self._hidden("policy"), self._hidden("qf1")
         cfg = SacConfig(self.obs_dim, self.act_dim, 256, batch, self.discount, self.reward_scale, self.policy_lr,
@@ -115,6 +127,7 @@ class SACTrainer:
         h, self._h = getattr(self, "_h", None), None
         if h:
             self._lib.sac_trainer_destroy(h)
+        self._settled()                          # (the record went with the handle)
 
     def __del__(self):
         self._destroy()
@@ -127,7 +140,7 @@ class SACTrainer:
         if self._h is not None:
             self.sync_networks_to_host()
             st["_saved_state"] = self._export_state()
-        st["_h"], st["_lib"] = None, None
+        st["_h"], st["_lib"], st["_stepped_buffers"] = None, None, ()
         return st
 
     def __setstate__(self, st):
@@ -139,6 +152,7 @@ class SACTrainer:
     def _set_params(self, name, flat):
         flat = _lib.f32(flat)
         _lib.check(self._lib.sac_set_params(self._h, self.NETS[name], _lib.ptr(flat), flat.size), "sac_set_params")
+        self._settled()
         if name == "policy":
             self._host_policy_stale = True           # (the holder's arrays are refreshed at their next use)
 
@@ -146,6 +160,7 @@ class SACTrainer:
         n = int(self._lib.sac_param_count(self._h, self.NETS[name]))
         out = np.empty(n, np.float32)
         _lib.check(self._lib.sac_get_params(self._h, self.NETS[name], _lib.ptr(out), n), "sac_get_params")
+        self._settled()
         return out
 
     def _export_state(self):
@@ -169,6 +184,7 @@ class SACTrainer:
                                                    m.size), "sac_set_opt_state")
         sc = np.ascontiguousarray(st["scalars"], np.float64)
         _lib.check(self._lib.sac_set_scalars(self._h, _lib.ptr(sc)), "sac_set_scalars")
+        self._settled()
         self._host_policy_stale = True           # the acting copy on the host is refreshed at its next use
 
     state_dict, load_state_dict = _export_state, _import_state
@@ -195,6 +211,9 @@ class SACTrainer:
             self._host_policy_stale = True
             if diag is not None:
                 self._record(diag)
+                self._settled()
+            elif not any(b is np_batch._buffer for b in self._stepped_buffers):
+                self._stepped_buffers += (np_batch._buffer,)
             return diag
         obs = _lib.f32(np_batch["observations"])
         B = obs.shape[0]
@@ -209,6 +228,7 @@ class SACTrainer:
         diag = np.empty(_lib.SAC_DIAG_N, np.float32)
         _lib.check(self._lib.sac_step(self._h, _lib.ptr(obs), _lib.ptr(act), _lib.ptr(rew), _lib.ptr(term),
                                       _lib.ptr(nobs), _lib.ptr(e1), _lib.ptr(e2), _lib.ptr(diag)), "sac_step")
+        self._settled()
         self._host_policy_stale = True
         self._record(diag)
         return diag
@@ -221,6 +241,7 @@ class SACTrainer:
         first, last = np.empty(_lib.SAC_DIAG_N, np.float32), np.empty(_lib.SAC_DIAG_N, np.float32)
         _lib.check(self._lib.sac_train_loop(self._h, replay_buffer._h, int(n_steps), _lib.ptr(first), _lib.ptr(last)),
                    "sac_train_loop")
+        self._settled()
         self._num_train_steps += int(n_steps)
         self._host_policy_stale = True
         self._record(first)
@@ -290,6 +311,8 @@ class SACTrainer:
             _lib.check(self._lib.sac_policy_act(self._h, obs[i].ctypes.data_as(C.c_void_p), int(bool(deterministic)),
                                                 None if e is None else e[i].ctypes.data_as(C.c_void_p),
                                                 out[i].ctypes.data_as(C.c_void_p)), "sac_policy_act")
+        if n:                                    # (the mirror behind a training block is a state read: it settles)
+            self._settled()
         return out
 
     def policy_act_device(self, obs, deterministic, eps):
@@ -329,6 +352,7 @@ class SACTrainer:
         the trainer has no handle yet) and a float32 NumPy forward."""
         if self._h is not None:
             _lib.check(self._lib.sac_sync(self._h), "sac_sync")
+            self._settled()
         x = np.concatenate([obs, act], axis=1)
         out = np.empty((len(nets), x.shape[0]), np.float32)
         for r, name in enumerate(nets):
@@ -418,6 +442,7 @@ class SACTrainer:
         alpha = 1.0
         if self._h is not None:
             _lib.check(self._lib.sac_sync(self._h), "sac_sync")
+            self._settled()
             if self.use_automatic_entropy_tuning:        # (as sac_evaluate: no alpha before the first step, exp(log_alpha))
                 sc = self._scalars()
                 alpha = float(sc[5]) if sc[5] > 0 else float(np.exp(np.float32(sc[0])))
@@ -456,6 +481,7 @@ class SACTrainer:
     def _scalars(self):
         sc = np.zeros(6, np.float64)
         _lib.check(self._lib.sac_get_scalars(self._h, _lib.ptr(sc)), "sac_get_scalars")
+        self._settled()
         return sc
 
     def _eval_log_alpha(self):

@@ -505,6 +505,26 @@ def pair_of_hip(O, A, B, seed, noise_seed, **env):
     return fused, plain
 
 
+def _td3_pair_of_hip(O, A, B, seed, noise_seed, **env):
+    """(fused critic pass, four-launch critic pass) TD3 trainers with identical parameters."""
+    old = {k: os.environ.get(k) for k in ("SAC_FUSED", "SAC_FUSED_TEST_STALL")}
+    try:
+        os.environ.pop("SAC_FUSED", None)
+        for k, v in env.items():
+            os.environ[k] = str(v)
+        _, fused = make_td3_pair(O, A, B, seed=seed, noise_seed=noise_seed)
+        os.environ.pop("SAC_FUSED_TEST_STALL", None)
+        os.environ["SAC_FUSED"] = "0"
+        _, plain = make_td3_pair(O, A, B, seed=seed, noise_seed=noise_seed)
+    finally:
+        for k, v in old.items():
+            if v is None:
+                os.environ.pop(k, None)
+            else:
+                os.environ[k] = v
+    return fused, plain
+
+
 def plain_buffer(n, O, A, seed):
     from robosuite_benchmark_amd import EnvReplayBuffer
     obs, act, rew, term, nobs = synth_transitions(n, O, A, seed=seed, term_frac=0.05)

@@ -163,3 +163,59 @@ def test_a_dangling_latest_pointer_is_not_no_checkpoint(tmp_path):
     with pytest.raises(FileNotFoundError, match="refusing"):
         ck.checkpoint_exists(d)
     assert ck.checkpoint_exists(str(tmp_path / "never_written")) is False
+
+
+# ---- the saved noise_seed is adopted (the handle is keyed by it when it is created) -----------------------------
+class _SeededStub(_StubTrainer):
+    """_StubTrainer that records, in order, the handles it builds and the states it loads, each with the noise_seed it
+    had at that moment."""
+
+    def __init__(self, fill, noise_seed, handle=True, batch=8):
+        super().__init__(fill)
+        self.noise_seed, self._batch, self.log = noise_seed, batch, []
+        if not handle:
+            self._h = None
+
+    def _create(self, batch):
+        self.log.append(("create", int(batch), self.noise_seed))
+        self._h, self._batch = object(), int(batch)
+
+    def load_state_dict(self, st):
+        self.log.append(("load_state_dict", self.noise_seed))
+        super().load_state_dict(st)
+
+
+SAVED_SEED = (0xFEED << 40) | 12345
+
+
+def test_load_checkpoint_adopts_the_saved_noise_seed_before_the_state_goes_in(tmp_path):
+    d = str(tmp_path / "ck")
+    ck.save_checkpoint(d, _SeededStub(1.0, SAVED_SEED, batch=8), extra=dict(epoch=3))
+    # a live handle keyed by another seed: rebuilt for the trainer's OWN batch size, then loaded
+    live = _SeededStub(9.0, 7, batch=16)
+    old = live._h
+    assert ck.load_checkpoint(d, live) == dict(epoch=3)
+    assert live.noise_seed == SAVED_SEED and live._h is not old
+    assert live.log == [("create", 16, SAVED_SEED), ("load_state_dict", SAVED_SEED)]
+    assert float(live.st["params"]["policy"][0]) == 1.0
+    # no handle yet: built for the SAVED batch size, under the saved seed
+    bare = _SeededStub(9.0, 7, handle=False, batch=None)
+    ck.load_checkpoint(d, bare)
+    assert bare.noise_seed == SAVED_SEED and bare.log == [("create", 8, SAVED_SEED), ("load_state_dict", SAVED_SEED)]
+    # the same seed and a live handle: nothing to rebuild
+    same = _SeededStub(9.0, SAVED_SEED, batch=16)
+    old = same._h
+    ck.load_checkpoint(d, same)
+    assert same._h is old and same.log == [("load_state_dict", SAVED_SEED)]
+
+
+def test_a_refused_load_leaves_seed_and_handle_alone(tmp_path):
+    d = str(tmp_path / "ck")
+    ck.save_checkpoint(d, _SeededStub(1.0, SAVED_SEED), extra=dict(epoch=0))
+    np.save(os.path.join(ck.current_dir(d), "adam_m.policy.npy"), np.full(32, 5.0, np.float32))     # fails its CRC
+    for back in (_SeededStub(9.0, 7), _SeededStub(9.0, 7, handle=False)):
+        old = back._h
+        with pytest.raises(ValueError, match="content does not match"):
+            ck.load_checkpoint(d, back)
+        assert back.noise_seed == 7 and back._h is old and back.log == []
+        assert float(back.st["params"]["policy"][0]) == 9.0

@@ -5,7 +5,7 @@ import pytest
 
 from robosuite_benchmark_amd import EnvReplayBuffer
 from robosuite_benchmark_amd._lib import TD3_DIAG_NAMES
-from tests.helpers import check_step_f64, flat_of, make_td3_pair, rel_err, synth_transitions
+from tests.helpers import _td3_pair_of_hip, check_step_f64, flat_of, make_td3_pair, rel_err, synth_transitions
 
 pytestmark = pytest.mark.gpu
 
@@ -147,27 +147,6 @@ def test_td3_variant_through_the_driver_with_checkpoint_resume(tmp_path):
 
 
 # ---- round 3: the TD3 critic pass as ONE launch (k_abc<.., M_TD3_CRITIC>, csrc/sac_fused.h) ----------------------------
-def _td3_pair_of_hip(O, A, B, seed, noise_seed, **env):
-    """(fused critic pass, four-launch critic pass) TD3 trainers with identical parameters."""
-    import os
-    old = {k: os.environ.get(k) for k in ("SAC_FUSED", "SAC_FUSED_TEST_STALL")}
-    try:
-        os.environ.pop("SAC_FUSED", None)
-        for k, v in env.items():
-            os.environ[k] = str(v)
-        _, fused = make_td3_pair(O, A, B, seed=seed, noise_seed=noise_seed)
-        os.environ.pop("SAC_FUSED_TEST_STALL", None)
-        os.environ["SAC_FUSED"] = "0"
-        _, plain = make_td3_pair(O, A, B, seed=seed, noise_seed=noise_seed)
-    finally:
-        for k, v in old.items():
-            if v is None:
-                os.environ.pop(k, None)
-            else:
-                os.environ[k] = v
-    return fused, plain
-
-
 def _filled(n, O, A, seed):
     obs, act, rew, term, nobs = synth_transitions(n, O, A, seed=seed, term_frac=0.05)
     b = EnvReplayBuffer(n, obs_dim=O, action_dim=A)

@@ -81,7 +81,12 @@ class StubTrainer:
     def __init__(self, fill, O=5, A=2, batch=8, noise_seed=0):
         self._h, self.obs_dim, self.act_dim, self._batch, self.noise_seed = object(), O, A, batch, noise_seed
         self._num_train_steps = 0
+        self.created = []                    # (batch, noise_seed) of every handle built after construction
         self.fill(fill)
+
+    def _create(self, batch):
+        self.created.append((int(batch), self.noise_seed))
+        self._h, self._batch = object(), int(batch)
 
     def fill(self, v):
         self.st = dict(params={k: np.full(32, v + i, np.float32) for i, k in enumerate(self.NETS)},
@@ -375,6 +380,8 @@ def test_load_group_member_into_a_solo_trainer(tmp_path):
     t, b = StubTrainer(0.0), StubBuffer(3000, seed=9)
     assert gc.load_group_member(d, 2, t, b) == dict(epoch=6, seed=2)
     assert_same_member(trainers[2], buffers[2], t, b)
+    # the solo trainer goes on under the member's noise seed: its handle was rebuilt with it (for its own batch size)
+    assert t.noise_seed == trainers[2].noise_seed == 102 and t.created == [(8, 102)]
     with pytest.raises(IndexError):
         gc.load_group_member(d, 3, t, b)
 
