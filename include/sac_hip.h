@@ -510,6 +510,45 @@ int sac_evaluate_replay_many(sac_trainer_t *const *trainers, int n_trainers, con
 int sac_evaluate_replay_general_many(sac_trainer_t *const *trainers, int n_trainers, const int32_t *n_rows,
                                      const sac_eval_src_t *src, sac_eval_io_t *io, sac_eval_stats_t *stats /* may be NULL */);
 
+/* PER-UNIT statistics of the hidden layers, on the device from the live weights: how much of each network is alive
+ * (dormant units, Sokar et al. 2023; dead units; the feature norm).  For n (obs, act) rows, each selected net and each of
+ * its hidden layers l of N_l true units, the post-ReLU activations h[r][u] (float32, as the inference kernels produce
+ * them) are reduced per unit into a record of SAC_UNIT_FIELDS_N arrays of N_l float64 (k_unit_moments,
+ * csrc/sac_units.h):
+ *   SAC_UNIT_SUM      sum over rows of (double)h
+ *   SAC_UNIT_SUMSQ    sum over rows of (double)h (double)h
+ *   SAC_UNIT_ACTIVE   the number of rows with h > 0 (a NaN is not active)
+ *   SAC_UNIT_MAX      the largest h; a NaN stays
+ * The order of every sum is a function of n alone (rows w, w + 4, ... for w = 0..3, then (p0 + p1) + (p2 + p3)), no
+ * atomics: a member's records are byte for byte those of its solo call, whatever else is selected or asked for.
+ * `nets`: bit k selects net SAC_NET_* == k (bit 5, the target policy: TD3 handles only).  The policy's layers see obs,
+ * the Q nets' cat(obs, act); output layers and heads are not computed.  SAC and TD3 trainers are served.
+ * sac_unit_moments[_many] serve the fused kernels' shapes (k_units, csrc/sac_units.h): ONE launch for up to 16 members,
+ * 6 nets and 1024 rows each -- one workgroup per (member, selected net, 16-row block) runs the two hidden layers exactly
+ * as k_act / k_qval do and stores rows < n and columns < the true widths (pad units of hidden sizes below 256 are not
+ * units: a (64, 32) net has records of 64 and 32 entries) -- and one k_unit_moments launch behind it.
+ * sac_unit_moments_general[_many] serve general-step trainers (csrc/sac_units_general.h): per layer depth one
+ * k_qval_layer launch over every (member, selected net) that has a hidden layer there and one k_unit_moments launch on
+ * its outputs; with `activations` the layers' outputs are written straight into the staging the caller's copy is made
+ * from.  Either way everything runs on the first member's stream with one wait at the end.  Admission, the drain
+ * (sac_sync semantics: the weights as of the last completed step), 0..1024 rows per member (0 = sits out) and 1..16
+ * trainers are those of sac_q_values_many / sac_q_values_general_many.  The entries write staging, activation scratch
+ * and the caller's outputs only: nothing the step reads, no generator.  Refused (<0, sac_last_error, nothing changed):
+ * what those entries refuse (each family the other's trainers, naming the right entry), a mask that selects no net or an
+ * unknown bit, bit 5 on a SAC handle, a Q net selected with act == NULL, null obs or moments. */
+enum { SAC_UNIT_SUM, SAC_UNIT_SUMSQ, SAC_UNIT_ACTIVE, SAC_UNIT_MAX, SAC_UNIT_FIELDS_N };
+typedef struct sac_units_io {
+    const float *obs;        /* (n, O) host */
+    const float *act;        /* (n, A) host; may be NULL when no Q net is selected */
+    uint32_t nets, reserved;
+    double *moments;         /* out: per selected net in ascending id, per hidden layer l: SAC_UNIT_FIELDS_N arrays of N_l */
+    float *activations;      /* out, may be NULL: per selected net, per hidden layer l: (n, N_l) row-major */
+} sac_units_io_t;
+int sac_unit_moments(sac_trainer_t *t, int64_t n, sac_units_io_t *io);                             /* n in 1..1024 */
+int sac_unit_moments_many(sac_trainer_t *const *trainers, int n_trainers, const int32_t *n_rows, sac_units_io_t *io);
+int sac_unit_moments_general(sac_trainer_t *t, int64_t n, sac_units_io_t *io);                     /* n in 1..1024 */
+int sac_unit_moments_general_many(sac_trainer_t *const *trainers, int n_trainers, const int32_t *n_rows, sac_units_io_t *io);
+
 /* ------------------------------------------------------------------------------------------
  * Trainer groups: several runs of one configuration (the reference's seed sweeps, /root/reference/launch_jobs.sh)
  * stepped together.  A group holds 1..SAC_GROUP_MAX existing SAC trainers that share obs_dim, act_dim, batch (at most

@@ -99,6 +99,18 @@ class SacEvalStats(C.Structure):
     _fields_ = [("m", SacEvalMoment * len(EVAL_MOMENTS)), ("alpha", C.c_double), ("log_alpha", C.c_double)]
 
 
+# the per-unit records of sac_unit_moments_* (SAC_UNIT_*: the arrays of one hidden layer's record, in this order)
+UNIT_FIELDS = ("sum", "sumsq", "active", "max")
+UNIT_NET_BITS = {name: 1 << k for name, k in TD3_NET_IDS.items()}      # name -> bit SAC_NET_* of sac_units_io_t.nets
+UNIT_Q_NETS = ("qf1", "qf2", "target_qf1", "target_qf2")               # the nets that read cat(obs, act)
+
+
+class SacUnitsIO(C.Structure):
+    """sac_units_io_t"""
+    _fields_ = [("obs", C.c_void_p), ("act", C.c_void_p), ("nets", C.c_uint32), ("reserved", C.c_uint32),
+                ("moments", C.c_void_p), ("activations", C.c_void_p)]
+
+
 TD3_DIAG_NAMES = DIAG_NAMES[:16] + [f"Bellman Errors {i} {s}" for i in (1, 2) for s in ("Mean", "Std", "Max", "Min")] + [
     f"Policy Action {s}" for s in ("Mean", "Std", "Max", "Min")]
 
@@ -177,6 +189,10 @@ SYMBOLS = {
     "sac_evaluate_general_stats_many": (C.c_int, [_P, C.c_int, _P, _P, _P]),
     "sac_evaluate_replay_many": (C.c_int, [_P, C.c_int, _P, _P, _P, _P]),
     "sac_evaluate_replay_general_many": (C.c_int, [_P, C.c_int, _P, _P, _P, _P]),
+    "sac_unit_moments": (C.c_int, [_P, C.c_int64, _P]),
+    "sac_unit_moments_many": (C.c_int, [_P, C.c_int, _P, _P]),
+    "sac_unit_moments_general": (C.c_int, [_P, C.c_int64, _P]),
+    "sac_unit_moments_general_many": (C.c_int, [_P, C.c_int, _P, _P]),
     "sac_group_create": (C.c_int, [C.POINTER(_P), _P, C.c_int]),
     "td3_group_create": (C.c_int, [C.POINTER(_P), _P, C.c_int]),
     "sac_group_create_mixed": (C.c_int, [C.POINTER(_P), _P, C.c_int]),

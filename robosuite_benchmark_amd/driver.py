@@ -25,7 +25,8 @@ from .networks import (FlattenMlp, GaussianStrategy, MakeDeterministic, PolicyWr
 from .replay_buffer import EnvReplayBuffer
 from .group import (ArchSACTrainerGroup, ArchTD3TrainerGroup, GroupActor, MixedSACTrainerGroup, MixedTD3TrainerGroup,
                     MlpSACTrainerGroup, MlpTD3TrainerGroup, SACTrainerGroup, TD3TrainerGroup, act_many,
-                    evaluate_many, evaluate_replay_many, q_values_many, runs_general_step)
+                    evaluate_many, evaluate_replay_many, q_values_many, runs_general_step, unit_moments_many,
+                    unit_statistics)
 from .infer import check_general, check_stats
 from .sac import SACTrainer, eval_statistics
 from .td3 import TD3Trainer
@@ -451,13 +452,23 @@ class EvalOptions(NamedTuple):
     kernel copies the rows into the evaluation's staging, no gather to the host), in front of the epoch's exploration
     paths -- the figure validation/QF1 Loss stands next to, at the same parameters.  Indices and N(0,1) draws come from
     RandomState([seed, epoch, 0x52504C]).  The row gains replay/<key> for every key of evaluate and
-    replay/Num Transitions.  eval_general and eval_stats apply to it as to validation.  A TD3 variant is refused."""
+    replay/Num Transitions.  eval_general and eval_stats apply to it as to validation.  A TD3 variant is refused.
+
+    unit_diagnostics=True: how much of each network is alive -- the per-unit records of policy, qf1 and qf2 on every
+    (observation, action) of the epoch's evaluation paths (unit_moments: the same steps as q_diagnostics, so no
+    generator is used and nothing needs a checkpoint) and unit_statistics' twelve columns units/<Net> Dormant Fraction /
+    Dead Fraction / Active Fraction / Feature Norm behind the replay/ block.  unit_general ("host" or "device") is
+    unit_moments' `general`: where a run of the general step reduces them -- sac_get_params and a NumPy forward, or
+    sac_unit_moments_general (in a group one sac_unit_moments_general_many call per 16 such runs); a run with the
+    fused kernels' shapes reduces them on the device either way (sac_unit_moments).  TD3 variants are served."""
     q_diagnostics: bool = False
     q_general: str = "host"
     validation: bool = False
     eval_general: str = "host"
     eval_stats: str = "host"
     replay_eval: int = 0
+    unit_diagnostics: bool = False
+    unit_general: str = "host"
 
 
 def _refuse_td3(variant, what, call, reason):
@@ -465,14 +476,17 @@ def _refuse_td3(variant, what, call, reason):
         raise RuntimeError(f"{what}({call}): {reason}; a TD3 variant has no such evaluation")
 
 
-def _options(what, specs, acting, q_diagnostics, q_general, validation, eval_general, eval_stats, replay_eval):
+def _options(what, specs, acting, q_diagnostics, q_general, validation, eval_general, eval_stats, replay_eval,
+             unit_diagnostics=False, unit_general="host"):
     """The EvalOptions of entry `what`, after the value checks of its keywords (acting's too) and, for the variant at
     the head of every run spec in `specs`, the TD3 refusals: all of it in front of anything that builds a run."""
     check_stats(eval_stats)
     check_acting(acting)
     check_general(q_general)
     check_general(eval_general)
-    opts = EvalOptions(q_diagnostics, q_general, validation, eval_general, eval_stats, check_replay_eval(replay_eval))
+    check_general(unit_general)
+    opts = EvalOptions(q_diagnostics, q_general, validation, eval_general, eval_stats, check_replay_eval(replay_eval),
+                       bool(unit_diagnostics), unit_general)
     for spec in specs if opts.validation else ():
         _refuse_td3(tuple(spec)[0], what, "validation=True", "validation evaluates the SAC objective (SACTrainer.evaluate)")
     for spec in specs if opts.replay_eval else ():
@@ -481,13 +495,24 @@ def _options(what, specs, acting, q_diagnostics, q_general, validation, eval_gen
     return opts
 
 
-EVAL_BLOCKS = ("q", "validation", "replay")                   # the optional column blocks, in the row's order
+EVAL_BLOCKS = ("q", "validation", "replay", "units")          # the optional column blocks, in the row's order
+UNIT_NETS = ("policy", "qf1", "qf2")                          # the nets of the units/ block
+
+
+def _unit_columns(moments):
+    """The units block of a row: unit_statistics of a run's records (None: no evaluation path this epoch, the columns
+    stay, empty)."""
+    if moments is None:
+        z = dict(count=1.0, sum=np.zeros(1), sumsq=np.zeros(1), active=np.zeros(1), max=np.zeros(1))
+        return OrderedDict(("units/" + k, float("nan")) for k in unit_statistics(OrderedDict((n, [z]) for n in UNIT_NETS)))
+    return OrderedDict(("units/" + k, v) for k, v in unit_statistics(moments).items())
 
 
 def _epoch_evaluations(runs, epoch, opts, take=EVAL_BLOCKS, many=True):
     """The blocks of `take` that `opts` switches on, for every run at this moment of `epoch`: ([{block: columns} per
-    run], seconds spent).  many: ONE q_values_many / evaluate_many / evaluate_replay_many call over all runs (the last
-    only when some run has rows); otherwise each trainer's own q_values / evaluate / evaluate_replay."""
+    run], seconds spent).  many: ONE q_values_many / evaluate_many / evaluate_replay_many / unit_moments_many call over
+    all runs (evaluate_replay_many only when some run has rows); otherwise each trainer's own q_values / evaluate /
+    evaluate_replay / unit_moments."""
     s0 = time.time()
     cols, trainers = [{} for _ in runs], [r["trainer"] for r in runs]
     paths = [r["evalc"].epoch_paths for r in runs]
@@ -515,6 +540,14 @@ def _epoch_evaluations(runs, epoch, opts, take=EVAL_BLOCKS, many=True):
                    [t.evaluate_replay(b, n=n, rng=g, **gen, **stats_kw) for t, b, n, g in zip(trainers, bufs, ns, rngs)])
         for c, s, n in zip(cols, got, ns):
             c["replay"] = _replay_columns(s, n)
+    if opts.unit_diagnostics and "units" in take:
+        steps = [_path_steps(p, t.obs_dim, t.act_dim) for p, t in zip(paths, trainers)]
+        kw = _q_general_kw(opts.unit_general)
+        got = (unit_moments_many(trainers, [s[0] for s in steps], [s[1] for s in steps], [UNIT_NETS] * len(runs), **kw)
+               if many else [t.unit_moments(*s, nets=UNIT_NETS, **kw) if s[0].shape[0] else None
+                             for t, s in zip(trainers, steps)])
+        for c, m in zip(cols, got):
+            c["units"] = _unit_columns(m)
     return cols, time.time() - s0
 
 
@@ -634,7 +667,8 @@ def _prefill(r):
 
 def experiment(variant, log_dir=None, seed=1, obs_dim=None, action_dim=None, num_epochs=None, device=0,
                fused_loop=True, quiet=False, checkpoint_dir=None, resume=False, acting="host", q_diagnostics=False,
-               q_general="host", validation=False, eval_general="host", eval_stats="host", replay_eval=0):
+               q_general="host", validation=False, eval_general="host", eval_stats="host", replay_eval=0,
+               unit_diagnostics=False, unit_general="host"):
     """variant.json -> training run.  Returns the list of progress rows (also written to
     <log_dir>/progress.csv when log_dir is given).
 
@@ -650,10 +684,10 @@ def experiment(variant, log_dir=None, seed=1, obs_dim=None, action_dim=None, num
     k_act_layer launch per layer on the live weights).  The exploration noise comes from the same host stream, in the
     same amounts, whichever value is given.
 
-    q_diagnostics, q_general, validation, eval_general, eval_stats, replay_eval: the per-epoch evaluations, EvalOptions;
-    here from the trainer's own q_values, evaluate and evaluate_replay."""
+    q_diagnostics, q_general, validation, eval_general, eval_stats, replay_eval, unit_diagnostics, unit_general: the
+    per-epoch evaluations, EvalOptions; here from the trainer's own q_values, evaluate, evaluate_replay and unit_moments."""
     opts = _options("experiment", [(variant,)], acting, q_diagnostics, q_general, validation, eval_general, eval_stats,
-                    replay_eval)
+                    replay_eval, unit_diagnostics, unit_general)
     validate(variant)
     # This driver's runs are a function of `seed` alone: initial weights come from np.random (seeded here), every noise
     # stream from `seed` -- whether or not torch happens to be loaded in the process (the reference's own scripts seed
@@ -741,7 +775,8 @@ def _group_epochs(*, runs, train_block, n_epochs, n_train, log_dir, quiet, what,
     log_dir; appended to after a resume).
     acting="host": the runs collect one after the other -- evaluation paths, exploration paths, add_paths each.  The
     replay evaluation of all runs stands in front of them all (each buffer as the run's own experiment() sees it there),
-    Q bias and validation of all runs behind them all (nobody has trained since the first run's evaluation paths).  The
+    Q bias, validation and the unit statistics of all runs behind them all (nobody has trained since the first run's
+    evaluation paths).  The
     seconds of these calls are added to every run's time/evaluation sampling (s); the replay evaluation's also to its
     time/epoch (s), the run's start taken that much earlier: a row's phases stay inside its epoch.
     acting="device": the runs collect in lockstep (GroupPathCollector) -- the evaluation phase of all runs, the
@@ -783,7 +818,7 @@ def _group_epochs(*, runs, train_block, n_epochs, n_train, log_dir, quiet, what,
                     t2 = time.time()
                     r["buf"].add_paths(new_paths)
                     times.append((t0 - r_s, t1 - t0 + r_s, t2 - t1, time.time() - t2))
-                behind, b_s = _epoch_evaluations(runs, epoch, opts, take=("q", "validation"))
+                behind, b_s = _epoch_evaluations(runs, epoch, opts, take=("q", "validation", "units"))
                 for b, more in zip(blocks, behind):
                     b.update(more)
                 times = [(a0, eval_s + b_s, expl_s, store_s) for a0, eval_s, expl_s, store_s in times]
@@ -817,7 +852,7 @@ def _group_epochs(*, runs, train_block, n_epochs, n_train, log_dir, quiet, what,
 def experiment_group(variant, seeds, log_dir=None, num_epochs=None, obs_dim=None, action_dim=None, device=0,
                      quiet=False, checkpoint_dir=None, resume=False, chunk_rows=DEFAULT_CHUNK_ROWS, acting="host", sessions=True,
                      general_sessions=None, q_diagnostics=False, q_general="host", validation=False,
-                     eval_general="host", eval_stats="host", replay_eval=0):
+                     eval_general="host", eval_stats="host", replay_eval=0, unit_diagnostics=False, unit_general="host"):
     """One configuration, several seeds, one process: each seed is the run ``experiment(variant, seed=s)`` would make --
     its own synthetic environments, collectors, weights and replay buffer -- and every epoch's training block is ONE
     SACTrainerGroup.train_loop (TD3 variants: TD3TrainerGroup; hidden sizes other than two layers of at most 256 units:
@@ -838,10 +873,10 @@ def experiment_group(variant, seeds, log_dir=None, num_epochs=None, obs_dim=None
     experiment(variant, seed=s, acting="device").  "device_all": the same, with the runs of the general step acting on the
     device too (one sac_policy_act_general_many call per tick and 16 of them; with sessions and general_sessions=True one
     sac_gactor_act call, None: GroupActor's default); rows as experiment(..., acting="device_all").
-    q_diagnostics, q_general, validation, eval_general, eval_stats, replay_eval: the per-epoch evaluations, EvalOptions;
-    each seed's rows are those of experiment(variant, seed=s) with the same options."""
+    q_diagnostics, q_general, validation, eval_general, eval_stats, replay_eval, unit_diagnostics, unit_general: the
+    per-epoch evaluations, EvalOptions; each seed's rows are those of experiment(variant, seed=s) with the same options."""
     opts = _options("experiment_group", [(variant,)], acting, q_diagnostics, q_general, validation, eval_general,
-                    eval_stats, replay_eval)
+                    eval_stats, replay_eval, unit_diagnostics, unit_general)
     if resume and not checkpoint_dir:
         raise RuntimeError("experiment_group(resume=True) needs the checkpoint_dir to resume from")
     validate(variant)
@@ -895,7 +930,7 @@ def sweep_label(variant, seed, hidden_sweep=False):
 def experiment_sweep(runs, log_dir=None, num_epochs=None, device=0, quiet=False, checkpoint_dir=None, resume=False,
                      chunk_rows=DEFAULT_CHUNK_ROWS, hidden_sweep=False, acting="host", sessions=True, general_sessions=None,
                      q_diagnostics=False, q_general="host", validation=False,
-                     eval_general="host", eval_stats="host", replay_eval=0):
+                     eval_general="host", eval_stats="host", replay_eval=0, unit_diagnostics=False, unit_general="host"):
     """Several tasks x seeds, one process, one device: every entry of ``runs`` -- (variant, seed), or (variant, seed,
     obs_dim, action_dim) for a task without pinned dims -- is the run ``experiment(variant, seed=seed)`` would make, and
     every epoch's training block is ONE MixedSACTrainerGroup.train_loop (TD3 variants: MixedTD3TrainerGroup; hidden sizes
@@ -913,11 +948,12 @@ def experiment_sweep(runs, log_dir=None, num_epochs=None, device=0, quiet=False,
     lockstep ticks (act_many), so each run's rows stay those of its solo experiment(..., acting="device").  Under
     "device_all" those runs act on the device inside the same ticks, and each run's rows are those of its solo
     experiment(..., acting="device_all").
-    q_diagnostics, q_general, validation, eval_general, eval_stats, replay_eval: the per-epoch evaluations, EvalOptions,
-    as for experiment_group; in a hidden sweep the runs of the general step take the host path inside the same call, or
+    q_diagnostics, q_general, validation, eval_general, eval_stats, replay_eval, unit_diagnostics, unit_general: the
+    per-epoch evaluations, EvalOptions, as for experiment_group; in a hidden sweep the runs of the general step take the
+    host path inside the same call, or
     the device's under q_general / eval_general "device".  A sweep with a TD3 run refuses validation and replay_eval."""
     opts = _options("experiment_sweep", runs, acting, q_diagnostics, q_general, validation, eval_general, eval_stats,
-                    replay_eval)
+                    replay_eval, unit_diagnostics, unit_general)
     if resume and not checkpoint_dir:
         raise RuntimeError("experiment_sweep(resume=True) needs the checkpoint_dir to resume from")
     specs = []

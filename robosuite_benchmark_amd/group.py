@@ -19,7 +19,8 @@ import numpy as np
 from . import _lib
 # (the inference names live in infer.py; they stay importable from here)
 from .infer import (GENERAL, GENERAL_SESSIONS, MAX_MEMBERS, GroupActor, act_many, check_general,  # noqa: F401
-                    evaluate_many, evaluate_replay_many, general_shape, q_values_many, runs_general_step)
+                    evaluate_many, evaluate_replay_many, general_shape, merge_unit_moments, q_values_many,
+                    runs_general_step, unit_moments_many, unit_moments_reference, unit_statistics)
 from .sac import SACTrainer
 from .td3 import TD3Trainer
 
@@ -65,6 +66,14 @@ class _Members:
         if nets_list is None:
             nets_list = [("qf1", "qf2")] * len(self.trainers)
         return q_values_many(self.trainers, obs_list, act_list, nets_list, general=general)
+
+    def unit_moments_many(self, obs_list, act_list, nets_list=None, activations=False, general="host"):
+        """unit_moments_many over the group's members (nets_list None: policy, qf1 and qf2 of every member; activations
+        and general as there)."""
+        check_general(general)
+        if nets_list is None:
+            nets_list = [("policy", "qf1", "qf2")] * len(self.trainers)
+        return unit_moments_many(self.trainers, obs_list, act_list, nets_list, activations=activations, general=general)
 
     def evaluate_many(self, batches, eps=None, rngs=None, rows=False, general="host", stats="host"):
         """evaluate_many over the group's members (general and stats as there)."""

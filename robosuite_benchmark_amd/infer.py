@@ -1,7 +1,9 @@
-"""Inference above the C ABI: acting, Q values and loss evaluation for one trainer or many, on live weights.
+"""Inference above the C ABI: acting, Q values, loss evaluation and per-unit statistics for one trainer or many, on live
+weights.
 
-Every Python inference call -- SACTrainer.policy_act_device / policy_act_general / q_values / evaluate, act_many,
-q_values_many, evaluate_many, GroupActor and the drivers above them -- goes through three things defined here once
+Every Python inference call -- SACTrainer.policy_act_device / policy_act_general / q_values / evaluate / unit_moments,
+act_many, q_values_many, evaluate_many, unit_moments_many, GroupActor and the drivers above them -- goes through three
+things defined here once
 (DESIGN.md, section 6g):
   the predicate   runs_general_step: does this trainer run the general step?
   the route       route: does one member's request run on the host, through the fused entry or the general entry?
@@ -89,6 +91,9 @@ def route(t, general, on_host=False):
     if not runs_general_step(t):
         return FUSED
     return GENERAL_STEP if general == "device" else HOST
+
+
+UNIT_ENTRIES = {FUSED: "sac_unit_moments_many", GENERAL_STEP: "sac_unit_moments_general_many"}
 
 
 # ---- the windows --------------------------------------------------------------------------------------------------------
@@ -223,6 +228,173 @@ def q_values_many(trainers, obs_list, act_list, nets_list, general="host"):
         if obs_list[i] is not None and np.atleast_2d(obs_list[i]).shape[0] != 0:
             obs[i], act[i], _, _ = t._q_inputs(obs_list[i], act_list[i], names[i])
     return q_values_of(trainers, obs, act, names, masks, rows, general)
+
+
+# ---- per-unit statistics of the hidden layers ---------------------------------------------------------------------------
+UNIT_NET_TITLES = OrderedDict([("policy", "Policy"), ("qf1", "QF1"), ("qf2", "QF2"), ("target_qf1", "Target QF1"),
+                               ("target_qf2", "Target QF2"), ("target_policy", "Target Policy")])
+UNIT_FIGURES = ("Dormant Fraction", "Dead Fraction", "Active Fraction", "Feature Norm")
+
+
+def _np_max(m, x):
+    """em_max (csrc/sac_eval_moments.h) on arrays: x where x > m or x is NaN, else m -- a NaN on either side stays."""
+    return np.where((x > m) | (x != x), x, m)
+
+
+def unit_moments_reference(h):
+    """k_unit_moments (csrc/sac_units.h) restated in NumPy float64, operation for operation -- the reference of its tests
+    and the body of the host path: the record {count, sum, sumsq, active, max} of one hidden layer's post-ReLU activations
+    h (n, N) float32, four float64 arrays of N.  Partial w of 0..3 starts at 0 (max: -inf) and takes rows w, w + 4, ...
+    ascending: sum += x, sumsq += x x, active += (h > 0), max = x if x > max or x is NaN; the four partials meet as
+    (p0 + p1) + (p2 + p3), max likewise.  A NaN element makes its unit's sum, sumsq and max NaN and is not active."""
+    h = np.asarray(h, np.float32)
+    if h.ndim != 2 or h.shape[0] < 1:
+        raise ValueError(f"unit_moments_reference takes (n, N) activations with at least one row, got {h.shape}")
+    n, N = h.shape
+    x = h.astype(np.float64)
+    part = []
+    with np.errstate(all="ignore"):
+        for w in range(4):
+            s, q, a, m = np.zeros(N), np.zeros(N), np.zeros(N), np.full(N, -np.inf)
+            for r in range(w, n, 4):
+                s = s + x[r]
+                q = q + x[r] * x[r]
+                a = a + (h[r] > 0)
+                m = _np_max(m, x[r])
+            part.append((s, q, a, m))
+        p = list(zip(*part))
+        total = [(f[0] + f[1]) + (f[2] + f[3]) for f in p[:3]]
+        mx = _np_max(_np_max(p[3][0], p[3][1]), _np_max(p[3][2], p[3][3]))
+    return dict(count=float(n), sum=total[0], sumsq=total[1], active=total[2], max=mx)
+
+
+def merge_unit_moments(a, b):
+    """The record of two disjoint sets of rows of one layer from their records a and b (a call above 1024 rows runs as
+    several windows): count, sum, sumsq and active add, max combines and keeps a NaN.  With activations ("h") the rows
+    are joined too."""
+    with np.errstate(all="ignore"):
+        out = dict(count=a["count"] + b["count"], sum=a["sum"] + b["sum"], sumsq=a["sumsq"] + b["sumsq"],
+                   active=a["active"] + b["active"], max=_np_max(a["max"], b["max"]))
+    if "h" in a and "h" in b:
+        out["h"] = np.concatenate([a["h"], b["h"]], axis=0)
+    return out
+
+
+def unit_statistics(moments, tau=0.025):
+    """The figures of a unit_moments result (OrderedDict net -> [record per hidden layer]): an OrderedDict with, per net in
+    the order given, under its title of UNIT_NET_TITLES,
+      "<Net> Dormant Fraction"   the share of the net's hidden units that are tau-dormant (Sokar et al. 2023): unit u of a
+                                 layer is dormant iff sum[u] <= tau * mean_k(sum[k]) of its layer -- the mean activation
+                                 against the layer's, without a division: an all-zero layer is all dormant
+      "<Net> Dead Fraction"      the share of hidden units with active == 0: active on no row
+      "<Net> Active Fraction"    the mean over hidden units of active / count
+      "<Net> Feature Norm"       sqrt(sum_u sumsq[u] / count) of the LAST hidden layer: the RMS norm of the features
+    NaN follows NumPy: a comparison with a NaN is False (a NaN unit is not dormant, and makes no unit of its layer
+    dormant through the layer mean), a NaN is not active, and a NaN sumsq makes the Feature Norm NaN."""
+    d = OrderedDict()
+    with np.errstate(all="ignore"):
+        for net, records in moments.items():
+            title = UNIT_NET_TITLES.get(net, net)
+            units = sum(r["sum"].size for r in records)
+            dormant = sum(int(np.count_nonzero(r["sum"] <= tau * np.mean(r["sum"]))) for r in records)
+            dead = sum(int(np.count_nonzero(r["active"] == 0)) for r in records)
+            active = sum(float(np.sum(r["active"] / r["count"])) for r in records)
+            last = records[-1]
+            d[title + " Dormant Fraction"] = dormant / units
+            d[title + " Dead Fraction"] = dead / units
+            d[title + " Active Fraction"] = active / units
+            d[title + " Feature Norm"] = float(np.sqrt(np.sum(last["sumsq"]) / last["count"]))
+    return d
+
+
+def _unit_records(widths, moments, taps, k):
+    """One net's records out of a window's outputs: `moments` the net's float64 block (per layer len(UNIT_FIELDS) arrays
+    of N), `taps` its float32 activations block ((k, N) per layer) or None."""
+    out, m0, h0 = [], 0, 0
+    for N in widths:
+        rec = dict(count=float(k))
+        for f in _lib.UNIT_FIELDS:
+            rec[f] = moments[m0:m0 + N].copy()
+            m0 += N
+        if taps is not None:
+            rec["h"] = taps[h0:h0 + k * N].reshape(k, N).copy()
+            h0 += k * N
+        out.append(rec)
+    return out
+
+
+def unit_moments_of(trainers, obs, act, names, activations, general):
+    """unit_moments / unit_moments_many behind their argument checks, one entry per trainer: obs / act as
+    SACTrainer._unit_inputs checked them (obs None: the member sits out and gets None), names the nets asked for.  The
+    host members first, in member order; then the device families of UNIT_ENTRIES, each in windows, a member's windows
+    joined by merge_unit_moments."""
+    R = len(trainers)
+    out, n_rows, served = [None] * R, [0] * R, {FUSED: [], GENERAL_STEP: []}
+    for i, t in enumerate(trainers):
+        if obs[i] is None:
+            continue
+        where = route(t, general)
+        if where == HOST:
+            out[i] = t._unit_moments_host(obs[i], act[i], names[i], activations)
+        else:
+            n_rows[i] = obs[i].shape[0]
+            served[where].append(i)
+    lib = _lib.load() if served[FUSED] or served[GENERAL_STEP] else None
+    for family in (FUSED, GENERAL_STEP):
+        if not served[family]:
+            continue
+        entry = UNIT_ENTRIES[family]
+        order = {i: sorted(names[i], key=_lib.UNIT_NET_BITS.get) for i in served[family]}
+        widths = {i: [trainers[i]._hidden(name) for name in order[i]] for i in served[family]}
+        for r0, ids, counts in windows(served[family], n_rows):
+            units = [sum(sum(w) for w in widths[i]) for i in ids]
+            mom = [np.empty(len(_lib.UNIT_FIELDS) * u, np.float64) for u in units]
+            taps = [np.empty(k * u, np.float32) if activations else None for k, u in zip(counts, units)]
+            o = [np.ascontiguousarray(obs[i][r0:r0 + k]) for i, k in zip(ids, counts)]
+            a = [None if act[i] is None else np.ascontiguousarray(act[i][r0:r0 + k]) for i, k in zip(ids, counts)]
+            ios = (_lib.SacUnitsIO * len(ids))(*[
+                _lib.SacUnitsIO(o[j].ctypes.data, None if a[j] is None else a[j].ctypes.data,
+                                sum(_lib.UNIT_NET_BITS[name] for name in names[i]), 0, mom[j].ctypes.data,
+                                None if taps[j] is None else taps[j].ctypes.data) for j, i in enumerate(ids)])
+            _lib.check(getattr(lib, entry)(_handles(trainers, ids), len(ids), _ints(counts), ios), entry)
+            for j, (i, k) in enumerate(zip(ids, counts)):
+                part, m0, h0 = {}, 0, 0
+                for name, ws in zip(order[i], widths[i]):
+                    u = sum(ws)
+                    part[name] = _unit_records(ws, mom[j][m0:m0 + len(_lib.UNIT_FIELDS) * u],
+                                               None if taps[j] is None else taps[j][h0:h0 + k * u], k)
+                    m0, h0 = m0 + len(_lib.UNIT_FIELDS) * u, h0 + k * u
+                if out[i] is None:
+                    out[i] = OrderedDict((name, part[name]) for name in names[i])
+                else:
+                    for name in names[i]:
+                        out[i][name] = [merge_unit_moments(x, y) for x, y in zip(out[i][name], part[name])]
+    return out
+
+
+def unit_moments_many(trainers, obs_list, act_list, nets_list, activations=False, general="host"):
+    """SACTrainer.unit_moments for many runs at once: result[i] = trainers[i]'s per-unit records of the nets nets_list[i]
+    (names, as unit_moments takes them) on obs_list[i] / act_list[i] ((n_i, O_i) / (n_i, A_i), act None where no Q net is
+    named; obs None or no rows: the member sits out and gets None).  Routing is unit_moments': the members with the fused
+    kernels' shapes are served by ONE k_units launch per 16 of them and 1024 rows (sac_unit_moments_many: SAC and TD3,
+    dims, hidden sizes, row counts and nets mixed), under general="device" the members of the general step by ONE
+    sac_unit_moments_general_many call per 16 of them and 1024 rows; the others take their own host path inside the same
+    call.  A member's records never depend on its neighbours: they are byte for byte those of its own unit_moments."""
+    check_general(general)
+    trainers = list(trainers)
+    R = len(trainers)
+    if not (len(obs_list) == len(act_list) == len(nets_list) == R):
+        raise RuntimeError("unit_moments_many takes one observation array, action array and net selection per trainer")
+    if len({id(t) for t in trainers}) != R:
+        raise RuntimeError("a trainer appears twice in unit_moments_many")
+    obs, act, names = [None] * R, [None] * R, [None] * R
+    for i, t in enumerate(trainers):
+        names[i] = [nets_list[i]] if isinstance(nets_list[i], str) else list(nets_list[i])
+        if obs_list[i] is not None and np.atleast_2d(obs_list[i]).shape[0] != 0:
+            obs[i], act[i] = t._unit_inputs(obs_list[i], act_list[i], names[i])
+        else:
+            t._unit_names(names[i])
+    return unit_moments_of(trainers, obs, act, names, bool(activations), general)
 
 
 # ---- evaluation: its statistics -----------------------------------------------------------------------------------------

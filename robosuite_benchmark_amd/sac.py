@@ -374,8 +374,85 @@ class SACTrainer:
         names = [nets] if isinstance(nets, str) else list(nets)
         return infer.q_values_of([self], [obs], [act], [names], [mask], [rows], general)[0]
 
+    # ---- per-unit statistics of the hidden layers ----------------------------------------------
+    def _unit_names(self, nets):
+        """unit_moments' net selection, checked: names of this trainer's nets, each once, at least one."""
+        names = [nets] if isinstance(nets, str) else list(nets)
+        if not names:
+            raise ValueError("unit_moments needs at least one network")
+        for name in names:
+            if name not in self.NETS:
+                raise ValueError(f"unknown network {name!r}: one of {tuple(self.NETS)}")
+        if len(set(names)) != len(names):
+            raise ValueError(f"a network is named twice in {tuple(names)}")
+        return names
+
+    def _unit_inputs(self, obs, act, nets):
+        """unit_moments' arguments, checked before any library call: (obs, act); act None where no Q net is named."""
+        names = self._unit_names(nets)
+        obs = _lib.f32(np.atleast_2d(obs))
+        if obs.ndim != 2 or obs.shape[1] != self.obs_dim or obs.shape[0] < 1:
+            raise ValueError(f"unit_moments: observations {obs.shape} do not fit obs_dim {self.obs_dim} (at least one row)")
+        if not any(name in _lib.UNIT_Q_NETS for name in names):
+            return obs, None
+        if act is None:
+            raise ValueError(f"unit_moments: {tuple(names)} names a Q network and the actions are None")
+        act = _lib.f32(np.atleast_2d(act))
+        if act.shape != (obs.shape[0], self.act_dim):
+            raise ValueError(f"unit_moments: actions {act.shape} for {obs.shape[0]} observation rows and act_dim {self.act_dim}")
+        return obs, act
+
+    def _host_hidden(self, name):
+        """[(W, b)] of one net's HIDDEN layers from the current weights (sac_get_params, or the holder's arrays without a
+        handle): the front of the flat vector, whatever output layer or head follows."""
+        flat = self._get_params(name) if self._h is not None else _lib.f32(getattr(self, name).flat())
+        k = self.obs_dim + (self.act_dim if name in _lib.UNIT_Q_NETS else 0)
+        layers, off = [], 0
+        for n_out in self._hidden(name):
+            layers.append((flat[off:off + n_out * k].reshape(n_out, k), flat[off + n_out * k:off + n_out * k + n_out]))
+            off, k = off + n_out * k + n_out, n_out
+        return layers
+
+    def _unit_moments_host(self, obs, act, nets, activations=False):
+        """The host path of unit_moments: the nets' current weights (sac_sync, sac_get_params; the holders' own arrays
+        while the trainer has no handle yet), the float32 NumPy forward layer by layer, infer.unit_moments_reference."""
+        if self._h is not None:
+            _lib.check(self._lib.sac_sync(self._h), "sac_sync")
+            self._settled()
+        out = OrderedDict()
+        with np.errstate(all="ignore"):
+            for name in nets:
+                h = np.concatenate([obs, act], axis=1) if name in _lib.UNIT_Q_NETS else obs
+                out[name] = []
+                for layer in self._host_hidden(name):
+                    h = _lib.f32(_hidden_layers(h, [layer]))
+                    rec = infer.unit_moments_reference(h)
+                    if activations:
+                        rec["h"] = h
+                    out[name].append(rec)
+        return out
+
+    def unit_moments(self, obs, act=None, nets=("policy", "qf1", "qf2"), activations=False, general="host"):
+        """How much of each network is alive: per-unit records of the hidden layers' post-ReLU activations on the rows
+        obs (n, O) / act (n, A; needed where a Q net is named) from the LIVE weights.  An OrderedDict net -> [record per
+        hidden layer] for the names in `nets` (of "policy", "qf1", "qf2", "target_qf1", "target_qf2"; a TD3Trainer also
+        "target_policy") in the order given; a record is a dict of count (n) and four float64 arrays of the layer's true
+        width -- sum, sumsq, active (rows with h > 0), max -- as infer.unit_moments_reference defines them, plus h (n, N)
+        float32 with activations=True.  infer.unit_statistics turns the result into dormant / dead / active fractions and
+        the feature norm.  Nothing the step reads is written, and no generator is touched.
+        Routing is q_values': a trainer with the fused kernels' shapes goes to the device under either `general`
+        (sac_unit_moments: k_units keeps the two hidden layers of k_act / k_qval, k_unit_moments reduces them; calls of at
+        most 1024 rows joined by infer.merge_unit_moments, no parameter copy).  A trainer of the general step takes the
+        host path by default -- sac_sync, sac_get_params, a float32 NumPy forward, unit_moments_reference -- and under
+        general="device" the device (sac_unit_moments_general: k_qval_layer per layer depth and k_unit_moments on its
+        outputs).  A trainer without a handle takes the host path."""
+        infer.check_general(general)
+        names = self._unit_names(nets)
+        obs, act = self._unit_inputs(obs, act, names)
+        return infer.unit_moments_of([self], [obs], [act], [names], bool(activations), general)[0]
+
     # ---- evaluation on held-out transitions --------------------------------------------------
-    _evaluate_on_host = False        # private switch: the host path for a fused-shape trainer too (scripts/bench_evaluate.py
+    _evaluate_on_host = False       # private switch: the host path for a fused-shape trainer too (scripts/bench_evaluate.py
                                      # measures the two paths of ONE trainer against each other)
     _eval_rng = None                 # evaluate's private noise stream, made on first use
 

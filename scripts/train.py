@@ -20,7 +20,10 @@
  --eval_general device: with --validation, runs of any hidden sizes evaluate these objectives on the device too.
  --eval_stats device: with --validation, the statistics of the runs evaluated on the device are reduced there as well.
  --replay_eval [N]: every epoch, the same objectives on N (bare: 1024) rows of the replay buffer, read in place on the
- device: replay/ columns in progress.csv, the training-data figures next to the validation/ ones; SAC only.)
+ device: replay/ columns in progress.csv, the training-data figures next to the validation/ ones; SAC only.
+ --unit_diagnostics: every epoch, the dormant, dead and active fractions and the feature norm of policy, qf1 and qf2 on
+ the evaluation paths, from per-unit reductions of the hidden layers: twelve units/ columns; SAC and TD3.
+ --unit_general device: with --unit_diagnostics, runs of any hidden sizes reduce them on the device.)
 Runs the variant unchanged (batch size, lrs, tau, period, buffer size ... from the JSON) on the
 HIP library with a synthetic environment of the task's dimensions (robosuite is not installed)."""
 import argparse
@@ -94,6 +97,15 @@ def build_parser():
                          "gather to the host, no host conversion), at the point where --validation is taken, and log them as replay/<key>: "
                          "the training-data figure the validation/ columns stand next to; the bare flag: 1024 rows; SAC "
                          "only; --eval_general and --eval_stats apply to it too; 0 (the default): progress.csv is unchanged")
+    ap.add_argument("--unit_diagnostics", action="store_true",
+                    help="every epoch, reduce the hidden layers' activations of policy, qf1 and qf2 on the evaluation paths "
+                         "per unit, from the live weights, and log units/<Net> Dormant Fraction, Dead Fraction, Active "
+                         "Fraction and Feature Norm: how much of each network is alive; SAC and TD3; off: progress.csv is "
+                         "unchanged")
+    ap.add_argument("--unit_general", type=str, default="host", choices=["host", "device"],
+                    help="with --unit_diagnostics: where runs whose hidden sizes are beyond two layers of at most 256 units "
+                         "reduce them -- host (a parameter copy and a NumPy forward) or device (per layer one forward "
+                         "launch and one reduction launch on the live weights); without --unit_diagnostics it has no effect")
     return ap
 
 
@@ -107,6 +119,10 @@ if __name__ == "__main__":
         option_kw["eval_stats"] = args.eval_stats
     if args.replay_eval:
         option_kw["replay_eval"] = args.replay_eval
+    if args.unit_diagnostics:
+        option_kw["unit_diagnostics"] = True
+    if args.unit_general != "host":
+        option_kw["unit_general"] = args.unit_general
     if (args.hidden_sweep or args.hidden_sizes) and not args.variants:
         raise SystemExit("--hidden_sweep / --hidden_sizes need --variants")
     if args.variants or args.seeds:
