@@ -335,7 +335,12 @@ int sac_measure_peaks(int device, float out[4]);
 /* test access to intermediates of the last step: name in {"a_new","log_pi","mu","log_std","q1","q2",
  * "q_target","q1_new","q2_new","a_next","log_pi_next","g_policy","g_qf1","g_qf2","ext_img_sa","ext_img_n"} (g_* = flat
  * gradient in the sac_get_params layout; ext_img_*: the row images sac_step staged with its last batch, see
- * sac_read_slot_images).  Returns the element count, <0 on error. */
+ * sac_read_slot_images).  And two read-only views of the trained state, which settle the trainer first like the state
+ * getters: "pt_policy" / "pt_qf1" / "pt_qf2" -- sac_get_params' vector with the weights taken from the TRANSPOSED copy
+ * the backward passes and Adam read (fused kernels' shapes only; equal to sac_get_params bit for bit by invariant) --
+ * and "pad_nonzero" -- counts of elements x with !(x == 0) at the padding positions no flat index reaches: for each
+ * trained net 0..2 the counts of P, PT, MT, VT (general step: P, M, V), then of P for each target net (all 0 by
+ * invariant).  Returns the element count, <0 on error. */
 int64_t sac_debug_fetch(sac_trainer_t *t, const char *name, float *out, int64_t cap);
 
 /* policy.get_action(obs) on the HOST with weights mirrored from the device (acting path,

@@ -488,6 +488,14 @@ int gen_download(sac_trainer *t, int net, const float *src, float *flat) {
     return 0;
 }
 
+// elements x with !(x == 0) (non-finite ones count) of a padded device array, read back as h, at the positions that no
+// flat index maps to (reach[i] == 0)
+int64_t count_unreached_nonzero(const std::vector<float> &h, const std::vector<char> &reach) {
+    int64_t c = 0;
+    for (size_t i = 0; i < h.size(); ++i) c += (!reach[i] && !(h[i] == 0.f)) ? 1 : 0;
+    return c;
+}
+
 // one launch list on minibatch slot S
 // (polyak: the weight-gradient launch of this list also soft-updates the targets of the nets it trains)
 int gen_run_list(sac_trainer *t, const std::vector<GenStage> &list, const float *S, const SlotLayout &SL, const StepArg &sa,
@@ -609,6 +617,28 @@ int64_t gen_debug_fetch(sac_trainer *t, const std::string &nm, float *out, int64
             if (gen_download(t, i, g->net[i].G, out)) return -1;
             return g->net[i].nflat;
         }
+    // Elements x with !(x == 0) of the device vectors outside GenNet::perm (the alignment gaps in front of each W and at
+    // the end).  Order: for each trained net 0..2 (policy, qf1, qf2) the counts of P, M, V; then the count of P for each
+    // target net 3, 4 (TD3: and 5).  11 floats (TD3: 12).  (The general step keeps no transposed copy: no "pt_<net>".)
+    if (nm == "pad_nonzero") {
+        const int nnets = t->algo == 1 ? 6 : 5;
+        const int64_t cnt = 3 * 3 + (nnets - 3);
+        if (cap < cnt) { sac::set_error("buffer too small"); return -2; }
+        int64_t o = 0;
+        for (int i = 0; i < nnets; ++i) {
+            const GenNet &N = g->net[i];
+            std::vector<char> reach((size_t)N.n, 0);
+            for (long long fi = 0; fi < N.nflat; ++fi) reach[(size_t)N.perm[(size_t)fi]] = 1;
+            std::vector<float> h((size_t)N.n);
+            const float *arrs[3] = {N.P, N.M, N.V};
+            for (int a = 0; a < (i < 3 ? 3 : 1); ++a) {
+                if (hipMemcpyAsync(h.data(), arrs[a], sizeof(float) * h.size(), hipMemcpyDeviceToHost, t->stream) != hipSuccess ||
+                    hipStreamSynchronize(t->stream) != hipSuccess) { sac::set_error("copy failed in sac_debug_fetch"); return -1; }
+                out[o++] = (float)count_unreached_nonzero(h, reach);
+            }
+        }
+        return cnt;
+    }
     sac::set_error("unknown debug tensor '%s'", nm.c_str());
     return -2;
 }

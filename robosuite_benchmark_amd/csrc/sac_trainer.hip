@@ -3367,10 +3367,12 @@ int sac_last_loop_ms(sac_trainer_t *t, float *total_ms, float *sample_ms, float 
 int64_t sac_debug_fetch(sac_trainer_t *t, const char *name, float *out, int64_t cap) {
     if (!t || !name || !out) { sac::set_error("bad arguments to sac_debug_fetch"); return -2; }
     if (hipSetDevice(t->device) != hipSuccess) { sac::set_error("hipSetDevice failed"); return -1; }
-    if (t->gen) return gen_debug_fetch(t, std::string(name), out, cap);
+    const std::string nm(name);
+    // the readers of trained state ("pt_<net>", "pad_nonzero") see it as of the last completed step, as sac_get_params does
+    if ((nm == "pad_nonzero" || nm.rfind("pt_", 0) == 0) && settle_trainer(t)) return -1;
+    if (t->gen) return gen_debug_fetch(t, nm, out, cap);
     const int B = t->B, A = t->A;
     const Dev &d = t->dev;
-    const std::string nm(name);
     auto fetch = [&](const float *src, int64_t n, std::vector<float> &h) -> int {
         h.resize((size_t)n);
         SAC_HIP(hipMemcpyAsync(h.data(), src, sizeof(float) * n, hipMemcpyDeviceToHost, t->stream));
@@ -3378,6 +3380,45 @@ int64_t sac_debug_fetch(sac_trainer_t *t, const char *name, float *out, int64_t 
         return 0;
     };
     std::vector<float> h;
+    // the flat nn.Linear vector of a trained net as the backward passes (and Adam) see it: weights from the transposed
+    // copy PT, biases from P.  Bit-equal to sac_get_params while the two copies agree.
+    const char *ptn[3] = {"pt_policy", "pt_qf1", "pt_qf2"};
+    for (int i = 0; i < 3; ++i)
+        if (nm == ptn[i]) {
+            const int64_t n = sac_param_count(t, i);
+            if (cap < n) { sac::set_error("buffer too small"); return -2; }
+            if (download_padded(t, i, t->net[i].P, out, t->net[i].PT)) return -1;
+            return n;
+        }
+    // Elements x with !(x == 0) (non-finite ones count) at the positions of the padded arrays that the flat map
+    // (for_each_param) does not reach: row and column padding, the action-column gap of a Q first layer, alignment gaps,
+    // the +16 rows of the transposed arrays.  Order: for each trained net 0..2 (policy, qf1, qf2) the counts of P, PT, MT,
+    // VT; then the count of P for each target net 3, 4 (TD3: and 5).  14 floats (TD3: 15).
+    if (nm == "pad_nonzero") {
+        const int nnets = t->algo == 1 ? 6 : 5;
+        const int64_t n = 4 * 3 + (nnets - 3);
+        if (cap < n) { sac::set_error("buffer too small"); return -2; }
+        int64_t o = 0;
+        for (int i = 0; i < nnets; ++i) {
+            const Net &N = t->net[i];
+            std::vector<char> fwd((size_t)N.nP, 0), tr((size_t)(i < 3 ? N.nPT : 0), 0);
+            for_each_param(t, i, [&](int64_t, int l, int nn, int k, bool is_b) {
+                const Layer &L = N.L[l];
+                if (is_b) fwd[(size_t)L.offB + nn] = 1;
+                else {
+                    fwd[(size_t)L.offW + frag_off(nn, k, L.Kp)] = 1;
+                    if (i < 3) tr[(size_t)L.offWt + frag_off(k, nn, L.Np)] = 1;
+                }
+            });
+            struct Arr { const float *p; const std::vector<char> *reach; };
+            const Arr arrs[4] = {{N.P, &fwd}, {N.PT, &tr}, {N.MT, &tr}, {N.VT, &tr}};
+            for (int a = 0; a < (i < 3 ? 4 : 1); ++a) {
+                if (fetch(arrs[a].p, (int64_t)arrs[a].reach->size(), h)) return -1;
+                out[o++] = (float)count_unreached_nonzero(h, *arrs[a].reach);
+            }
+        }
+        return n;
+    }
     if (nm == "ext_img_sa" || nm == "ext_img_n") {          // a row image of the external-batch slot (sac_step's staging)
         const SlotLayout &L = t->ext_layout;
         const int64_t n = (int64_t)L.B * L.KLQ;
