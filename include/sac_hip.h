@@ -554,6 +554,45 @@ int sac_unit_moments_many(sac_trainer_t *const *trainers, int n_trainers, const 
 int sac_unit_moments_general(sac_trainer_t *t, int64_t n, sac_units_io_t *io);                     /* n in 1..1024 */
 int sac_unit_moments_general_many(sac_trainer_t *const *trainers, int n_trainers, const int32_t *n_rows, sac_units_io_t *io);
 
+/* PER-TENSOR statistics of the state the step kernels write -- parameters, Adam moments, Polyak targets -- reduced on
+ * the device where that state lives (k_param_moments / k_param_finish, csrc/sac_params.h): weight norms, the size of
+ * Adam's moments, non-finite weights, how far a target lags its online net, without copying a parameter to the host.
+ * A tensor is one tensor of the flat nn.Linear layout of sac_get_params: fc<i>.weight, fc<i>.bias, ..., last_fc.weight,
+ * last_fc.bias and, on a SAC policy, last_fc_log_std.weight, last_fc_log_std.bias.  sac_param_tensors returns net's
+ * tensor count (at most 18) and, where sizes is not NULL, their element counts E; <0 for a bad argument.
+ * Per tensor a record of SAC_PARAM_FIELDS_N float64, formed in float64 from the float32 words with add, multiply,
+ * compare and fabs only:
+ *   SAC_PARAM_SUM, SAC_PARAM_SUMSQ          sum x, sum x x over the parameters
+ *   SAC_PARAM_ABSMAX                        the largest |x|; a NaN stays
+ *   SAC_PARAM_NONFINITE                     the number of elements that are not finite
+ *   SAC_PARAM_M_SUMSQ, SAC_PARAM_M_ABSMAX   the same over Adam's first moment (the words sac_get_opt_state returns)
+ *   SAC_PARAM_V_SUM, SAC_PARAM_V_MAX        the sum and the largest value of Adam's second moment
+ *   SAC_PARAM_GAP_SUMSQ                     sum (x - x_target)^2, the difference in float64: qf1 against target_qf1, qf2
+ *                                           against target_qf2, on TD3 handles the policy against the target policy
+ * A field that does not apply is exactly 0.0: the Adam fields of target nets or without SAC_PARAMS_OPT, the gap of a SAC
+ * policy and of target nets or without SAC_PARAMS_GAP.  The order of every sum is a function of the tensor's element
+ * count E alone -- chunks of 16384 elements, lane l of 256 adds e = l, l + 256, ... ascending from 0.0, the lanes meet by
+ * halving (128, 64, ..., 1), the chunks are joined in ascending order -- no atomics: a tensor's record is byte for byte
+ * the same grouped or solo, under any mask and any flags, and infer.param_moments_reference restates it in NumPy.
+ * Both families (the fused kernels' shapes and the general step) and both algorithms are served, mixed in one call: ONE
+ * k_param_moments launch and one k_param_finish launch on the first member's stream, one wait.  Admission and the drain
+ * are those of sac_q_values_many (1..16 trainers of one device, none confined by sac_trainer_set_xcd[_mask]; the state as
+ * of the last completed step of any step path; unverified fused steps are settled first, as by the getters).  The call
+ * writes staging and the caller's records: nothing the step reads, no generator.  Refused in addition (<0,
+ * sac_last_error, nothing written): a mask that selects no net or an unknown bit, bit 5 (the target policy) on a SAC
+ * handle, unknown flags, null moments. */
+enum { SAC_PARAM_SUM, SAC_PARAM_SUMSQ, SAC_PARAM_ABSMAX, SAC_PARAM_NONFINITE, SAC_PARAM_M_SUMSQ, SAC_PARAM_M_ABSMAX,
+       SAC_PARAM_V_SUM, SAC_PARAM_V_MAX, SAC_PARAM_GAP_SUMSQ, SAC_PARAM_FIELDS_N };
+enum { SAC_PARAMS_OPT = 1, SAC_PARAMS_GAP = 2 };
+typedef struct sac_params_io {
+    uint32_t nets;      /* bit k selects SAC_NET_* == k */
+    uint32_t flags;     /* SAC_PARAMS_OPT | SAC_PARAMS_GAP */
+    double *moments;    /* out: for the selected nets ascending, their tensors in flat order, SAC_PARAM_FIELDS_N doubles each */
+} sac_params_io_t;
+int sac_param_tensors(const sac_trainer_t *t, int net, int64_t *sizes /* may be NULL */);
+int sac_param_moments(sac_trainer_t *t, sac_params_io_t *io);
+int sac_param_moments_many(sac_trainer_t *const *trainers, int n_trainers, sac_params_io_t *io);   /* up to SAC_GROUP_MAX */
+
 /* ------------------------------------------------------------------------------------------
  * Trainer groups: several runs of one configuration (the reference's seed sweeps, /root/reference/launch_jobs.sh)
  * stepped together.  A group holds 1..SAC_GROUP_MAX existing SAC trainers that share obs_dim, act_dim, batch (at most

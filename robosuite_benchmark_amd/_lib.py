@@ -111,6 +111,17 @@ class SacUnitsIO(C.Structure):
                 ("moments", C.c_void_p), ("activations", C.c_void_p)]
 
 
+# the per-tensor records of sac_param_moments* (SAC_PARAM_*: the float64 values of one tensor's record, in this order)
+PARAM_FIELDS = ("sum", "sumsq", "absmax", "nonfinite", "m_sumsq", "m_absmax", "v_sum", "v_max", "gap_sumsq")
+PARAMS_OPT, PARAMS_GAP = 1, 2                                          # sac_params_io_t.flags
+PARAM_MAX_TENSORS = 18
+
+
+class SacParamsIO(C.Structure):
+    """sac_params_io_t"""
+    _fields_ = [("nets", C.c_uint32), ("flags", C.c_uint32), ("moments", C.c_void_p)]
+
+
 TD3_DIAG_NAMES = DIAG_NAMES[:16] + [f"Bellman Errors {i} {s}" for i in (1, 2) for s in ("Mean", "Std", "Max", "Min")] + [
     f"Policy Action {s}" for s in ("Mean", "Std", "Max", "Min")]
 
@@ -193,6 +204,9 @@ SYMBOLS = {
     "sac_unit_moments_many": (C.c_int, [_P, C.c_int, _P, _P]),
     "sac_unit_moments_general": (C.c_int, [_P, C.c_int64, _P]),
     "sac_unit_moments_general_many": (C.c_int, [_P, C.c_int, _P, _P]),
+    "sac_param_tensors": (C.c_int, [_P, C.c_int, _P]),
+    "sac_param_moments": (C.c_int, [_P, _P]),
+    "sac_param_moments_many": (C.c_int, [_P, C.c_int, _P]),
     "sac_group_create": (C.c_int, [C.POINTER(_P), _P, C.c_int]),
     "td3_group_create": (C.c_int, [C.POINTER(_P), _P, C.c_int]),
     "sac_group_create_mixed": (C.c_int, [C.POINTER(_P), _P, C.c_int]),

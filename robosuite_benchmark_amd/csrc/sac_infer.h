@@ -371,6 +371,7 @@ struct InferEntry {
     const char *what;        // "device acting", "device Q evaluation", "device evaluation"
     const char *instead;     // the shape refusal's advice
     const char *rows_to;     // no trainer has rows to ...
+    bool both = false;       // serves both families (no forward pass: sac_params.h); `general` and `instead` are unused
 };
 
 // trainer i of a list: not null, not listed twice, on trainer 0's device, of the algorithm and shapes the entry serves
@@ -382,6 +383,7 @@ int infer_admit_trainer(const InferEntry &E, sac_trainer_t *const *trainers, int
                 trainers[0]->device);
     SAC_REQUIRE(!E.sac_only || t->algo == 0, "trainer %d is a TD3 trainer: this entry evaluates the SAC objective "
                 "(entropy-regularised targets of a tanh-Gaussian policy)", i);
+    if (E.both) return 0;
     if (E.general)
         SAC_REQUIRE(t->gen, "trainer %d has the fused kernels' shapes (two hidden layers of at most 256 units): %s", i, E.instead);
     else

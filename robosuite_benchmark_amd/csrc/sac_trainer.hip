@@ -2379,6 +2379,7 @@ int stage_batches(sac_trainer *t, sac_buffer *b, int64_t n_steps) {
 #include "sac_qval_general.h"
 #include "sac_units.h"
 #include "sac_units_general.h"
+#include "sac_params.h"
 #include "sac_eval_general.h"
 #include "sac_actor.h"
 #include "sac_actor_general.h"

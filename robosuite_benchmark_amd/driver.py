@@ -25,9 +25,9 @@ from .networks import (FlattenMlp, GaussianStrategy, MakeDeterministic, PolicyWr
 from .replay_buffer import EnvReplayBuffer
 from .group import (ArchSACTrainerGroup, ArchTD3TrainerGroup, GroupActor, MixedSACTrainerGroup, MixedTD3TrainerGroup,
                     MlpSACTrainerGroup, MlpTD3TrainerGroup, SACTrainerGroup, TD3TrainerGroup, act_many,
-                    evaluate_many, evaluate_replay_many, q_values_many, runs_general_step, unit_moments_many,
-                    unit_statistics)
-from .infer import check_general, check_stats
+                    evaluate_many, evaluate_replay_many, q_values_many, runs_general_step, param_moments_many, param_statistics,
+                    unit_moments_many, unit_statistics)
+from .infer import check_general, check_stats, param_target
 from .sac import SACTrainer, eval_statistics
 from .td3 import TD3Trainer
 from .variant import env_dims, validate
@@ -460,7 +460,14 @@ class EvalOptions(NamedTuple):
     Dead Fraction / Active Fraction / Feature Norm behind the replay/ block.  unit_general ("host" or "device") is
     unit_moments' `general`: where a run of the general step reduces them -- sac_get_params and a NumPy forward, or
     sac_unit_moments_general (in a group one sac_unit_moments_general_many call per 16 such runs); a run with the
-    fused kernels' shapes reduces them on the device either way (sac_unit_moments).  TD3 variants are served."""
+    fused kernels' shapes reduces them on the device either way (sac_unit_moments).  TD3 variants are served.
+
+    param_diagnostics=True: the state the step kernels write -- every net's parameters, Adam's moments, the distance of
+    each target to its online net -- reduced per tensor on the device where it lives (param_moments: no parameter copy,
+    no generator, nothing to checkpoint), at the point of the epoch where validation is taken, and param_statistics'
+    columns params/<Net> Weight Norm / Weight Abs Max / Adam M Norm / Adam V Mean / Adam V Max / Target Gap and
+    params/Non Finite behind the units/ block.  The group entries make ONE param_moments_many call per epoch.  SAC and TD3
+    variants are served (a TD3 policy has a Target Gap too)."""
     q_diagnostics: bool = False
     q_general: str = "host"
     validation: bool = False
@@ -469,6 +476,7 @@ class EvalOptions(NamedTuple):
     replay_eval: int = 0
     unit_diagnostics: bool = False
     unit_general: str = "host"
+    param_diagnostics: bool = False
 
 
 def _refuse_td3(variant, what, call, reason):
@@ -477,7 +485,7 @@ def _refuse_td3(variant, what, call, reason):
 
 
 def _options(what, specs, acting, q_diagnostics, q_general, validation, eval_general, eval_stats, replay_eval,
-             unit_diagnostics=False, unit_general="host"):
+             unit_diagnostics=False, unit_general="host", param_diagnostics=False):
     """The EvalOptions of entry `what`, after the value checks of its keywords (acting's too) and, for the variant at
     the head of every run spec in `specs`, the TD3 refusals: all of it in front of anything that builds a run."""
     check_stats(eval_stats)
@@ -486,7 +494,7 @@ def _options(what, specs, acting, q_diagnostics, q_general, validation, eval_gen
     check_general(eval_general)
     check_general(unit_general)
     opts = EvalOptions(q_diagnostics, q_general, validation, eval_general, eval_stats, check_replay_eval(replay_eval),
-                       bool(unit_diagnostics), unit_general)
+                       bool(unit_diagnostics), unit_general, bool(param_diagnostics))
     for spec in specs if opts.validation else ():
         _refuse_td3(tuple(spec)[0], what, "validation=True", "validation evaluates the SAC objective (SACTrainer.evaluate)")
     for spec in specs if opts.replay_eval else ():
@@ -497,6 +505,7 @@ def _options(what, specs, acting, q_diagnostics, q_general, validation, eval_gen
 
 EVAL_BLOCKS = ("q", "validation", "replay", "units")          # the optional column blocks, in the row's order
 UNIT_NETS = ("policy", "qf1", "qf2")                          # the nets of the units/ block
+ALL_BLOCKS = EVAL_BLOCKS + ("params",)                        # ... and the params/ block behind them
 
 
 def _unit_columns(moments):
@@ -508,11 +517,18 @@ def _unit_columns(moments):
     return OrderedDict(("units/" + k, v) for k, v in unit_statistics(moments).items())
 
 
-def _epoch_evaluations(runs, epoch, opts, take=EVAL_BLOCKS, many=True):
+def _param_columns(t, moments):
+    """The params block of a row: param_statistics of a run's records, over every net of its trainer."""
+    sizes = {net: [int(np.prod(shape)) for _, shape in t.param_tensors(net)] for net in moments}
+    targets = tuple(net for net in moments if param_target(t, net) is not None)
+    return OrderedDict(("params/" + k, v) for k, v in param_statistics(moments, sizes, targets).items())
+
+
+def _epoch_evaluations(runs, epoch, opts, take=ALL_BLOCKS, many=True):
     """The blocks of `take` that `opts` switches on, for every run at this moment of `epoch`: ([{block: columns} per
-    run], seconds spent).  many: ONE q_values_many / evaluate_many / evaluate_replay_many / unit_moments_many call over
-    all runs (evaluate_replay_many only when some run has rows); otherwise each trainer's own q_values / evaluate /
-    evaluate_replay / unit_moments."""
+    run], seconds spent).  many: ONE q_values_many / evaluate_many / evaluate_replay_many / unit_moments_many
+    / param_moments_many call over all runs (evaluate_replay_many only when some run has rows); otherwise each trainer's
+    own q_values / evaluate / evaluate_replay / unit_moments / param_moments."""
     s0 = time.time()
     cols, trainers = [{} for _ in runs], [r["trainer"] for r in runs]
     paths = [r["evalc"].epoch_paths for r in runs]
@@ -548,12 +564,16 @@ def _epoch_evaluations(runs, epoch, opts, take=EVAL_BLOCKS, many=True):
                              for t, s in zip(trainers, steps)])
         for c, m in zip(cols, got):
             c["units"] = _unit_columns(m)
+    if opts.param_diagnostics and "params" in take:
+        got = param_moments_many(trainers) if many else [t.param_moments() for t in trainers]
+        for c, t, m in zip(cols, trainers, got):
+            c["params"] = _param_columns(t, m)
     return cols, time.time() - s0
 
 
 def _end_epoch_row(r, blocks, epoch):
     """Run r's progress.csv columns of `epoch` in the reference's order up to the time/* block, the blocks of
-    _epoch_evaluations behind them in EVAL_BLOCKS' order; then the run's parts end their epoch."""
+    _epoch_evaluations behind them in ALL_BLOCKS' order; then the run's parts end their epoch."""
     buf, trainer, expl, evalc = r["buf"], r["trainer"], r["expl"], r["evalc"]
     row = OrderedDict()
     row.update(("replay_buffer/" + k, v) for k, v in buf.get_diagnostics().items())
@@ -562,7 +582,7 @@ def _end_epoch_row(r, blocks, epoch):
     row.update(path_information(expl.epoch_paths, "exploration/"))
     row.update(("evaluation/" + k, v) for k, v in evalc.get_diagnostics().items())
     row.update(path_information(evalc.epoch_paths, "evaluation/", r["ak"]["expl_max_path_length"]))
-    for name in EVAL_BLOCKS:
+    for name in ALL_BLOCKS:
         row.update(blocks.get(name, ()))
     for x in (trainer, buf, expl, evalc):
         x.end_epoch(epoch)
@@ -668,7 +688,7 @@ def _prefill(r):
 def experiment(variant, log_dir=None, seed=1, obs_dim=None, action_dim=None, num_epochs=None, device=0,
                fused_loop=True, quiet=False, checkpoint_dir=None, resume=False, acting="host", q_diagnostics=False,
                q_general="host", validation=False, eval_general="host", eval_stats="host", replay_eval=0,
-               unit_diagnostics=False, unit_general="host"):
+               unit_diagnostics=False, unit_general="host", param_diagnostics=False):
     """variant.json -> training run.  Returns the list of progress rows (also written to
     <log_dir>/progress.csv when log_dir is given).
 
@@ -684,10 +704,11 @@ def experiment(variant, log_dir=None, seed=1, obs_dim=None, action_dim=None, num
     k_act_layer launch per layer on the live weights).  The exploration noise comes from the same host stream, in the
     same amounts, whichever value is given.
 
-    q_diagnostics, q_general, validation, eval_general, eval_stats, replay_eval, unit_diagnostics, unit_general: the
+    q_diagnostics, q_general, validation, eval_general, eval_stats, replay_eval, unit_diagnostics, unit_general,
+    param_diagnostics: the
     per-epoch evaluations, EvalOptions; here from the trainer's own q_values, evaluate, evaluate_replay and unit_moments."""
     opts = _options("experiment", [(variant,)], acting, q_diagnostics, q_general, validation, eval_general, eval_stats,
-                    replay_eval, unit_diagnostics, unit_general)
+                    replay_eval, unit_diagnostics, unit_general, param_diagnostics)
     validate(variant)
     # This driver's runs are a function of `seed` alone: initial weights come from np.random (seeded here), every noise
     # stream from `seed` -- whether or not torch happens to be loaded in the process (the reference's own scripts seed
@@ -818,7 +839,7 @@ def _group_epochs(*, runs, train_block, n_epochs, n_train, log_dir, quiet, what,
                     t2 = time.time()
                     r["buf"].add_paths(new_paths)
                     times.append((t0 - r_s, t1 - t0 + r_s, t2 - t1, time.time() - t2))
-                behind, b_s = _epoch_evaluations(runs, epoch, opts, take=("q", "validation", "units"))
+                behind, b_s = _epoch_evaluations(runs, epoch, opts, take=("q", "validation", "units", "params"))
                 for b, more in zip(blocks, behind):
                     b.update(more)
                 times = [(a0, eval_s + b_s, expl_s, store_s) for a0, eval_s, expl_s, store_s in times]
@@ -852,7 +873,8 @@ def _group_epochs(*, runs, train_block, n_epochs, n_train, log_dir, quiet, what,
 def experiment_group(variant, seeds, log_dir=None, num_epochs=None, obs_dim=None, action_dim=None, device=0,
                      quiet=False, checkpoint_dir=None, resume=False, chunk_rows=DEFAULT_CHUNK_ROWS, acting="host", sessions=True,
                      general_sessions=None, q_diagnostics=False, q_general="host", validation=False,
-                     eval_general="host", eval_stats="host", replay_eval=0, unit_diagnostics=False, unit_general="host"):
+                     eval_general="host", eval_stats="host", replay_eval=0, unit_diagnostics=False, unit_general="host",
+                     param_diagnostics=False):
     """One configuration, several seeds, one process: each seed is the run ``experiment(variant, seed=s)`` would make --
     its own synthetic environments, collectors, weights and replay buffer -- and every epoch's training block is ONE
     SACTrainerGroup.train_loop (TD3 variants: TD3TrainerGroup; hidden sizes other than two layers of at most 256 units:
@@ -873,10 +895,11 @@ def experiment_group(variant, seeds, log_dir=None, num_epochs=None, obs_dim=None
     experiment(variant, seed=s, acting="device").  "device_all": the same, with the runs of the general step acting on the
     device too (one sac_policy_act_general_many call per tick and 16 of them; with sessions and general_sessions=True one
     sac_gactor_act call, None: GroupActor's default); rows as experiment(..., acting="device_all").
-    q_diagnostics, q_general, validation, eval_general, eval_stats, replay_eval, unit_diagnostics, unit_general: the
+    q_diagnostics, q_general, validation, eval_general, eval_stats, replay_eval, unit_diagnostics, unit_general,
+    param_diagnostics: the
     per-epoch evaluations, EvalOptions; each seed's rows are those of experiment(variant, seed=s) with the same options."""
     opts = _options("experiment_group", [(variant,)], acting, q_diagnostics, q_general, validation, eval_general,
-                    eval_stats, replay_eval, unit_diagnostics, unit_general)
+                    eval_stats, replay_eval, unit_diagnostics, unit_general, param_diagnostics)
     if resume and not checkpoint_dir:
         raise RuntimeError("experiment_group(resume=True) needs the checkpoint_dir to resume from")
     validate(variant)
@@ -930,7 +953,8 @@ def sweep_label(variant, seed, hidden_sweep=False):
 def experiment_sweep(runs, log_dir=None, num_epochs=None, device=0, quiet=False, checkpoint_dir=None, resume=False,
                      chunk_rows=DEFAULT_CHUNK_ROWS, hidden_sweep=False, acting="host", sessions=True, general_sessions=None,
                      q_diagnostics=False, q_general="host", validation=False,
-                     eval_general="host", eval_stats="host", replay_eval=0, unit_diagnostics=False, unit_general="host"):
+                     eval_general="host", eval_stats="host", replay_eval=0, unit_diagnostics=False, unit_general="host",
+                     param_diagnostics=False):
     """Several tasks x seeds, one process, one device: every entry of ``runs`` -- (variant, seed), or (variant, seed,
     obs_dim, action_dim) for a task without pinned dims -- is the run ``experiment(variant, seed=seed)`` would make, and
     every epoch's training block is ONE MixedSACTrainerGroup.train_loop (TD3 variants: MixedTD3TrainerGroup; hidden sizes
@@ -948,12 +972,13 @@ def experiment_sweep(runs, log_dir=None, num_epochs=None, device=0, quiet=False,
     lockstep ticks (act_many), so each run's rows stay those of its solo experiment(..., acting="device").  Under
     "device_all" those runs act on the device inside the same ticks, and each run's rows are those of its solo
     experiment(..., acting="device_all").
-    q_diagnostics, q_general, validation, eval_general, eval_stats, replay_eval, unit_diagnostics, unit_general: the
+    q_diagnostics, q_general, validation, eval_general, eval_stats, replay_eval, unit_diagnostics, unit_general,
+    param_diagnostics: the
     per-epoch evaluations, EvalOptions, as for experiment_group; in a hidden sweep the runs of the general step take the
     host path inside the same call, or
     the device's under q_general / eval_general "device".  A sweep with a TD3 run refuses validation and replay_eval."""
     opts = _options("experiment_sweep", runs, acting, q_diagnostics, q_general, validation, eval_general, eval_stats,
-                    replay_eval, unit_diagnostics, unit_general)
+                    replay_eval, unit_diagnostics, unit_general, param_diagnostics)
     if resume and not checkpoint_dir:
         raise RuntimeError("experiment_sweep(resume=True) needs the checkpoint_dir to resume from")
     specs = []

@@ -19,8 +19,8 @@ import numpy as np
 from . import _lib
 # (the inference names live in infer.py; they stay importable from here)
 from .infer import (GENERAL, GENERAL_SESSIONS, MAX_MEMBERS, GroupActor, act_many, check_general,  # noqa: F401
-                    evaluate_many, evaluate_replay_many, general_shape, merge_unit_moments, q_values_many,
-                    runs_general_step, unit_moments_many, unit_moments_reference, unit_statistics)
+                    evaluate_many, evaluate_replay_many, general_shape, merge_unit_moments, param_moments_many,
+                    param_moments_reference, param_statistics, q_values_many, runs_general_step, unit_moments_many, unit_moments_reference, unit_statistics)
 from .sac import SACTrainer
 from .td3 import TD3Trainer
 
@@ -74,6 +74,11 @@ class _Members:
         if nets_list is None:
             nets_list = [("policy", "qf1", "qf2")] * len(self.trainers)
         return unit_moments_many(self.trainers, obs_list, act_list, nets_list, activations=activations, general=general)
+
+    def param_moments_many(self, nets_list=None, opt=True, gap=True, route="device"):
+        """param_moments_many over the group's members (nets_list None: every net of every member; opt, gap and route as
+        there): one sac_param_moments_many call per 16 members."""
+        return param_moments_many(self.trainers, nets_list, opt=opt, gap=gap, route=route)
 
     def evaluate_many(self, batches, eps=None, rngs=None, rows=False, general="host", stats="host"):
         """evaluate_many over the group's members (general and stats as there)."""

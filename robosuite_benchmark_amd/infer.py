@@ -1,5 +1,5 @@
-"""Inference above the C ABI: acting, Q values, loss evaluation and per-unit statistics for one trainer or many, on live
-weights.
+"""Inference above the C ABI: acting, Q values, loss evaluation, per-unit statistics and per-tensor parameter statistics
+for one trainer or many, on live weights.
 
 Every Python inference call -- SACTrainer.policy_act_device / policy_act_general / q_values / evaluate / unit_moments,
 act_many, q_values_many, evaluate_many, unit_moments_many, GroupActor and the drivers above them -- goes through three
@@ -395,6 +395,179 @@ def unit_moments_many(trainers, obs_list, act_list, nets_list, activations=False
         else:
             t._unit_names(names[i])
     return unit_moments_of(trainers, obs, act, names, bool(activations), general)
+
+
+# ---- per-tensor statistics of parameters, Adam moments and target gaps ---------------------------------------------------
+PARAM_CH, PARAM_LANES = 16384, 256          # k_param_moments: elements of a chunk, lanes of its workgroup
+PARAM_ROUTES = ("device", "host")
+PARAM_TRAINED = ("policy", "qf1", "qf2")    # the nets with Adam moments
+PARAM_FIGURES = ("Weight Norm", "Weight Abs Max", "Adam M Norm", "Adam V Mean", "Adam V Max")
+_FLT_MAX = float(np.finfo(np.float32).max)
+
+
+def check_route(route_):
+    if route_ not in PARAM_ROUTES:
+        raise RuntimeError(f"route must be one of {PARAM_ROUTES}, got {route_!r}")
+    return route_
+
+
+def param_target(t, net):
+    """The target net whose distance param_moments' gap measures for `net` of trainer t, or None: qf1 / qf2 against
+    their targets, on a TD3 trainer the policy against the target policy."""
+    if net in ("qf1", "qf2"):
+        return "target_" + net
+    return "target_policy" if net == "policy" and _is_td3(t) else None
+
+
+def _param_reduce(x, is_max=False, start=0.0):
+    """One field of k_param_moments over the float64 elements x (E,): per chunk of PARAM_CH elements lane l takes
+    e = l, l + 256, ... ascending from `start`, the 256 lanes meet by halving (128, 64, ..., 1), the chunks are joined in
+    ascending order, left to right; sums add, max fields use em_max.  Positions past E hold `start`, which changes
+    nothing (p + 0.0 == p for a p that started at +0.0; em_max(p, start) == p)."""
+    op = _np_max if is_max else np.add
+    E = x.size
+    nch = -(-E // PARAM_CH)
+    buf = np.full(nch * PARAM_CH, start, np.float64)
+    buf[:E] = x
+    buf = buf.reshape(nch, PARAM_CH // PARAM_LANES, PARAM_LANES)
+    p = np.full((nch, PARAM_LANES), start, np.float64)
+    for r in range(PARAM_CH // PARAM_LANES):
+        p = op(p, buf[:, r])
+    s = PARAM_LANES // 2
+    while s > 0:
+        p = op(p[:, :s], p[:, s:2 * s])
+        s //= 2
+    acc = p[0, 0]
+    for c in range(1, nch):
+        acc = op(acc, p[c, 0])
+    return float(acc)
+
+
+def param_moments_reference(x, m=None, v=None, target=None):
+    """k_param_moments / k_param_finish (csrc/sac_params.h) restated in NumPy float64, operation for operation -- the
+    reference of its tests and the body of the host route: the record of one tensor, len(_lib.PARAM_FIELDS) float64
+    values, from its float32 elements x in flat order, Adam's moments m and v (None: their fields are 0.0) and the
+    target's elements (None: the gap is 0.0).  sum x, sum x x, max |x| (a NaN stays), the count of non-finite elements,
+    sum m m, max |m|, sum v, max v (from -inf), sum (x - target)^2 with the difference in float64; the order of every sum
+    is _param_reduce's, a function of x.size alone."""
+    x = np.asarray(x, np.float32).ravel()
+    if x.size < 1:
+        raise ValueError("param_moments_reference takes a tensor of at least one element")
+    rec = np.zeros(len(_lib.PARAM_FIELDS), np.float64)
+    with np.errstate(all="ignore"):
+        xd = x.astype(np.float64)
+        ax = np.abs(xd)
+        rec[0] = _param_reduce(xd)
+        rec[1] = _param_reduce(xd * xd)
+        rec[2] = _param_reduce(ax, True)
+        rec[3] = _param_reduce(np.where(ax <= _FLT_MAX, 0.0, 1.0))
+        if m is not None:
+            md = np.asarray(m, np.float32).ravel().astype(np.float64)
+            vd = np.asarray(v, np.float32).ravel().astype(np.float64)
+            if md.size != x.size or vd.size != x.size:
+                raise ValueError("param_moments_reference: the moments do not have the tensor's size")
+            rec[4] = _param_reduce(md * md)
+            rec[5] = _param_reduce(np.abs(md), True)
+            rec[6] = _param_reduce(vd)
+            rec[7] = _param_reduce(vd, True, -np.inf)
+        if target is not None:
+            td = np.asarray(target, np.float32).ravel().astype(np.float64)
+            if td.size != x.size:
+                raise ValueError("param_moments_reference: the target does not have the tensor's size")
+            d = xd - td
+            rec[8] = _param_reduce(d * d)
+    return rec
+
+
+def param_statistics(moments, sizes, targets=("qf1", "qf2")):
+    """The logged figures of a param_moments result (OrderedDict net -> (n_tensors, 9) float64; sizes: net -> the element
+    counts of its tensors, as SACTrainer.param_tensors gives the shapes; targets: the nets whose gap was taken -- a TD3
+    trainer's include the policy).  An OrderedDict with, per TRAINED net (policy, qf1, qf2) in the order given, under its
+    title of UNIT_NET_TITLES,
+      "<Net> Weight Norm"      sqrt of the net's sumsq total
+      "<Net> Weight Abs Max"   the largest |x| of the net (a NaN stays)
+      "<Net> Adam M Norm"      sqrt of the m_sumsq total
+      "<Net> Adam V Mean"      the v_sum total over the net's element count
+      "<Net> Adam V Max"       the largest second moment
+      "<Net> Target Gap"       sqrt(gap_sumsq total) / sqrt(sumsq total), for the nets of `targets`: the distance to the
+                               target relative to the net's norm
+    and last "Non Finite": the nonfinite total over everything in `moments`, target nets included."""
+    F = {k: i for i, k in enumerate(_lib.PARAM_FIELDS)}
+    d, bad = OrderedDict(), 0.0
+    with np.errstate(all="ignore"):
+        for net, rec in moments.items():
+            rec = np.asarray(rec, np.float64).reshape(-1, len(_lib.PARAM_FIELDS))
+            bad += float(np.sum(rec[:, F["nonfinite"]]))
+            if net not in PARAM_TRAINED:
+                continue
+            title = UNIT_NET_TITLES.get(net, net)
+            sumsq = float(np.sum(rec[:, F["sumsq"]]))
+            d[title + " Weight Norm"] = float(np.sqrt(sumsq))
+            d[title + " Weight Abs Max"] = float(np.max(rec[:, F["absmax"]]))
+            d[title + " Adam M Norm"] = float(np.sqrt(np.sum(rec[:, F["m_sumsq"]])))
+            d[title + " Adam V Mean"] = float(np.sum(rec[:, F["v_sum"]]) / float(sum(int(e) for e in sizes[net])))
+            d[title + " Adam V Max"] = float(np.max(rec[:, F["v_max"]]))
+            if net in targets:
+                d[title + " Target Gap"] = float(np.sqrt(np.sum(rec[:, F["gap_sumsq"]])) / np.sqrt(sumsq))
+    d["Non Finite"] = bad
+    return d
+
+
+def param_moments_of(trainers, names, opt, gap, route_):
+    """param_moments / param_moments_many behind their argument checks: names[i] the nets asked of trainers[i] (None: the
+    member sits out and gets None).  The members without a handle, and all of them under route "host", take their own
+    host route; the others ONE sac_param_moments_many call per 16 of them, both families and both algorithms mixed."""
+    R = len(trainers)
+    out, served = [None] * R, []
+    for i, t in enumerate(trainers):
+        if names[i] is None:
+            continue
+        if t._h is None or route_ == "host":
+            out[i] = t._param_moments_host(names[i], opt, gap)
+        else:
+            served.append(i)
+    if not served:
+        return out
+    lib = _lib.load()
+    nf = len(_lib.PARAM_FIELDS)
+    flags = (_lib.PARAMS_OPT if opt else 0) | (_lib.PARAMS_GAP if gap else 0)
+    order = {i: sorted(names[i], key=_lib.UNIT_NET_BITS.get) for i in served}
+    counts = {i: [len(trainers[i].param_tensors(name)) for name in order[i]] for i in served}
+    for c in range(0, len(served), MAX_MEMBERS):
+        ids = served[c:c + MAX_MEMBERS]
+        mom = [np.empty(nf * sum(counts[i]), np.float64) for i in ids]
+        ios = (_lib.SacParamsIO * len(ids))(*[
+            _lib.SacParamsIO(sum(_lib.UNIT_NET_BITS[name] for name in names[i]), flags, mom[j].ctypes.data)
+            for j, i in enumerate(ids)])
+        _lib.check(lib.sac_param_moments_many(_handles(trainers, ids), len(ids), ios), "sac_param_moments_many")
+        for j, i in enumerate(ids):
+            part, m0 = {}, 0
+            for name, k in zip(order[i], counts[i]):
+                part[name] = mom[j][m0:m0 + nf * k].reshape(k, nf).copy()
+                m0 += nf * k
+            out[i] = OrderedDict((name, part[name]) for name in names[i])
+            trainers[i]._settled()
+    return out
+
+
+def param_moments_many(trainers, nets_list=None, opt=True, gap=True, route="device"):
+    """SACTrainer.param_moments for many runs at once: result[i] = trainers[i]'s per-tensor records of the nets
+    nets_list[i] (names; None for the list: every net of every trainer; None for a member: it sits out and gets None).
+    The members with a handle are served by ONE k_param_moments launch per 16 of them (sac_param_moments_many: SAC and
+    TD3, the fused kernels' shapes and the general step, dims and nets mixed), the others -- and all of them under
+    route="host" -- by their own host route.  A member's records never depend on its neighbours: they are byte for byte
+    those of its own param_moments."""
+    check_route(route)
+    trainers = list(trainers)
+    R = len(trainers)
+    if nets_list is None:
+        nets_list = [tuple(t.NETS) for t in trainers]
+    if len(nets_list) != R:
+        raise RuntimeError("param_moments_many takes one net selection per trainer")
+    if len({id(t) for t in trainers}) != R:
+        raise RuntimeError("a trainer appears twice in param_moments_many")
+    names = [None if n is None else t._param_names(n) for t, n in zip(trainers, nets_list)]
+    return param_moments_of(trainers, names, bool(opt), bool(gap), route)
 
 
 # ---- evaluation: its statistics -----------------------------------------------------------------------------------------

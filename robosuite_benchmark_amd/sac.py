@@ -451,6 +451,77 @@ class SACTrainer:
         obs, act = self._unit_inputs(obs, act, names)
         return infer.unit_moments_of([self], [obs], [act], [names], bool(activations), general)[0]
 
+    # ---- per-tensor statistics of parameters, Adam moments and target gaps ----------------------
+    def _param_names(self, nets):
+        """param_moments' net selection, checked: None is every net of the trainer; else names, each once, at least one."""
+        if nets is None:
+            return list(self.NETS)
+        names = [nets] if isinstance(nets, str) else list(nets)
+        if not names:
+            raise ValueError("param_moments needs at least one network")
+        for name in names:
+            if name not in self.NETS:
+                raise ValueError(f"unknown network {name!r}: one of {tuple(self.NETS)}")
+        if len(set(names)) != len(names):
+            raise ValueError(f"a network is named twice in {tuple(names)}")
+        return names
+
+    def param_tensors(self, net):
+        """[(name, shape)] of the tensors of `net` in the flat nn.Linear order of sac_get_params: fc0.weight, fc0.bias,
+        ..., last_fc.weight, last_fc.bias (a SAC policy: last_fc_log_std.weight, last_fc_log_std.bias too) -- the rows of
+        param_moments' arrays."""
+        if net not in self.NETS:
+            raise ValueError(f"unknown network {net!r}: one of {tuple(self.NETS)}")
+        out = []
+        for name, (w, b) in getattr(self, net).layers.items():
+            out += [(name + ".weight", tuple(w.shape)), (name + ".bias", tuple(b.shape))]
+        return out
+
+    def _param_moments_host(self, names, opt=True, gap=True):
+        """The host route of param_moments: the flat vectors (sac_get_params / sac_get_opt_state; without a handle the
+        holders' arrays and the saved or fresh -- zero -- Adam moments), cut into tensors, infer.param_moments_reference."""
+        def flat(name):
+            return self._get_params(name) if self._h is not None else _lib.f32(getattr(self, name).flat())
+        out = OrderedDict()
+        for name in names:
+            x, m, v, tg = flat(name), None, None, None
+            if opt and name in infer.PARAM_TRAINED:
+                if self._h is not None:
+                    m, v = np.empty(x.size, np.float32), np.empty(x.size, np.float32)
+                    _lib.check(self._lib.sac_get_opt_state(self._h, self.NETS[name], _lib.ptr(m), _lib.ptr(v), x.size),
+                               "sac_get_opt_state")
+                    self._settled()
+                elif self._saved_state is not None:
+                    m, v = (_lib.f32(a) for a in self._saved_state["opt"][name])
+                else:
+                    m, v = np.zeros(x.size, np.float32), np.zeros(x.size, np.float32)
+            tname = infer.param_target(self, name) if gap else None
+            if tname is not None:
+                tg = flat(tname)
+            rec, off = [], 0
+            for _, shape in self.param_tensors(name):
+                e = int(np.prod(shape))
+                cut = slice(off, off + e)
+                rec.append(infer.param_moments_reference(x[cut], None if m is None else m[cut], None if v is None else v[cut],
+                                                         None if tg is None else tg[cut]))
+                off += e
+            out[name] = np.stack(rec)
+        return out
+
+    def param_moments(self, nets=None, opt=True, gap=True, route="device"):
+        """The state the step kernels write, reduced per tensor where it lives: an OrderedDict net -> float64 array
+        (n_tensors, 9) for the names in `nets` (None: every net of the trainer; a TD3Trainer has "target_policy" too), rows
+        in param_tensors' order, columns _lib.PARAM_FIELDS: sum, sumsq, absmax, nonfinite over the parameters; m_sumsq,
+        m_absmax, v_sum, v_max over Adam's moments (opt; 0.0 on target nets); gap_sumsq, sum (x - x_target)^2 (gap; qf1 /
+        qf2 against their targets, a TD3 policy against the target policy, 0.0 elsewhere).  infer.param_statistics turns
+        the result into weight norms, Adam figures, target gaps and a non-finite count.
+        route="device": sac_param_moments -- ONE k_param_moments launch over every selected tensor, read in place, no
+        parameter copy; both step families.  route="host", and a trainer without a handle: sac_get_params /
+        sac_get_opt_state and infer.param_moments_reference -- the same bytes.  Nothing the step reads is written."""
+        infer.check_route(route)
+        names = self._param_names(nets)
+        return infer.param_moments_of([self], [names], bool(opt), bool(gap), route)[0]
+
     # ---- evaluation on held-out transitions --------------------------------------------------
     _evaluate_on_host = False       # private switch: the host path for a fused-shape trainer too (scripts/bench_evaluate.py
                                      # measures the two paths of ONE trainer against each other)

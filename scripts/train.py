@@ -106,6 +106,11 @@ def build_parser():
                     help="with --unit_diagnostics: where runs whose hidden sizes are beyond two layers of at most 256 units "
                          "reduce them -- host (a parameter copy and a NumPy forward) or device (per layer one forward "
                          "launch and one reduction launch on the live weights); without --unit_diagnostics it has no effect")
+    ap.add_argument("--param_diagnostics", action="store_true",
+                    help="every epoch, reduce every net's parameters, Adam moments and target distances per tensor on the "
+                         "device where they live (one HIP launch, no parameter copy) and log params/<Net> Weight Norm, "
+                         "Weight Abs Max, Adam M Norm, Adam V Mean, Adam V Max, Target Gap and params/Non Finite; SAC and "
+                         "TD3; off: progress.csv is unchanged")
     return ap
 
 
@@ -123,6 +128,8 @@ if __name__ == "__main__":
         option_kw["unit_diagnostics"] = True
     if args.unit_general != "host":
         option_kw["unit_general"] = args.unit_general
+    if args.param_diagnostics:
+        option_kw["param_diagnostics"] = True
     if (args.hidden_sweep or args.hidden_sizes) and not args.variants:
         raise SystemExit("--hidden_sweep / --hidden_sizes need --variants")
     if args.variants or args.seeds:
