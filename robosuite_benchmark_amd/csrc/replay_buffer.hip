@@ -143,6 +143,12 @@ __global__ __launch_bounds__(256) void k_mt_randint_group(const SampleMember *__
 // ------------------------------------------------------------------------------------------
 __device__ __forceinline__ void lds_barrier() { asm volatile("s_waitcnt lgkmcnt(0)\n\ts_barrier" ::: "memory"); }
 
+// a word of a pad row: itself, or +0.0 for a NaN or an Inf
+__device__ __forceinline__ float finite_or_zero(float v) { return fabsf(v) <= 3.402823466e+38f ? v : 0.f; }
+__device__ __forceinline__ float4 finite_or_zero(float4 v) {
+    return make_float4(finite_or_zero(v.x), finite_or_zero(v.y), finite_or_zero(v.z), finite_or_zero(v.w));
+}
+
 // LOAD_IDX / ISSUE_ROWS work on plain local arrays with static indices (structs passed by reference
 // into lambdas end up in scratch memory, and a scratch store of an in-flight load is a wait).
 #define GATHER_LOAD_IDX(BLK, IO, IA, IS)                                                          \
@@ -255,14 +261,22 @@ __device__ __forceinline__ void gather_body(const ReplayView &rv, const int64_t 
         const int slot = blk / blocks_per_slot;
         const int row0 = (blk - slot * blocks_per_slot) * RB;
         float *S = slots + (int64_t)slot * L.slot_floats;
+        // Rows behind the batch (the padding of the last row-block) were loaded from buffer row 0, the pad entries' valid
+        // index.  They carry no weight -- the step masks their dq -- but the weight gradient contracts g[pad] = 0 against
+        // x[pad], and 0 * x is NaN where row 0 holds a NaN or an Inf: a pad row keeps row 0's words except the non-finite
+        // ones, which become +0.0.
+        const int live = L.Bt - row0;
 #pragma unroll
         for (int i = 0; i < NIT; ++i)
             if (ro[i] >= 0) {
-                *reinterpret_cast<float4 *>(t_obs + ro[i] * Ost + 4 * qo[i]) = Do[i];
-                *reinterpret_cast<float4 *>(t_nobs + ro[i] * Ost + 4 * qo[i]) = Dn[i];
+                *reinterpret_cast<float4 *>(t_obs + ro[i] * Ost + 4 * qo[i]) = ro[i] < live ? Do[i] : finite_or_zero(Do[i]);
+                *reinterpret_cast<float4 *>(t_nobs + ro[i] * Ost + 4 * qo[i]) = ro[i] < live ? Dn[i] : finite_or_zero(Dn[i]);
             }
-        if (ra >= 0) *reinterpret_cast<float4 *>(t_act + ra * Ast + 4 * qa) = Da;
-        if (rs >= 0) S[(tid < RB ? L.off_rew : L.off_term) + row0 + rs] = (tid < RB) ? Ds : Ds2;
+        if (ra >= 0) *reinterpret_cast<float4 *>(t_act + ra * Ast + 4 * qa) = ra < live ? Da : finite_or_zero(Da);
+        if (rs >= 0) {
+            const float v = (tid < RB) ? Ds : Ds2;
+            S[(tid < RB ? L.off_rew : L.off_term) + row0 + rs] = rs < live ? v : finite_or_zero(v);
+        }
         lds_barrier();
         if constexpr (NIT == 1) {
             if (has_o) {

@@ -93,7 +93,7 @@ __device__ __forceinline__ void critic_block(const Dev &d, const float *__restri
         va = qa + b3a;                                                   // T1(s',a')
         vb = qb + b3b;                                                   // T2(s',a')
         vq = qq + b3q;                                                   // Q_i(s,a)
-        const float tq = fminf(va, vb) - alpha * in_c;
+        const float tq = min_nan(va, vb) - alpha * in_c;
         yv = bellman_target(d.reward_scale, in_r, in_t, d.discount, tq);
         dq = (row0 + (int)threadIdx.x < d.Bt) ? 2.0f * (vq - yv) * invB : 0.f;
         s_dq[threadIdx.x] = dq;
@@ -105,7 +105,7 @@ __device__ __forceinline__ void critic_block(const Dev &d, const float *__restri
         for (int qd = 0; qd < 4; ++qd) {
 #pragma unroll
             for (int i = 0; i < 4; ++i) {
-                gv2[qd][i] = (h2v[qd][i] > 0.f) ? s_dq[4 * qd + i] * wk : 0.f;
+                gv2[qd][i] = (h2v[qd][i] <= 0.f) ? 0.f : s_dq[4 * qd + i] * wk;
                 X2[lds_off(4 * qd + i, k, H)] = gv2[qd][i];
             }
         }
@@ -128,7 +128,7 @@ __device__ __forceinline__ void critic_block(const Dev &d, const float *__restri
         for (int t = 0; t < CT; ++t) {
             f32x4 gv;
 #pragma unroll
-            for (int i = 0; i < 4; ++i) gv[i] = (h1v[t][i] > 0.f) ? acc[t][i] : 0.f;
+            for (int i = 0; i < 4; ++i) gv[i] = (h1v[t][i] <= 0.f) ? 0.f : acc[t][i];
             st4(d.dQH1T + (size_t)qi * H * B + frag_off(n0 + 16 * t + c, row0 + 4 * g, B), gv);
         }
     }
@@ -184,8 +184,8 @@ __device__ __forceinline__ void policy_block(const Dev &d, const StepArg &sa, in
     float qnew1 = 0.f, qnew2 = 0.f, dz = 0.f, dls = 0.f;
     {
         const float va = qa + b3a, vb = qb + b3b;                                    // Q1, Q2(s, a_new)
-        const float sel1 = (va < vb) ? 1.0f : ((va == vb) ? 0.5f : 0.0f);
-        const float dq1 = -invB * sel1, dq2 = -invB * (1.0f - sel1);
+        const float sel1 = min_backward(va, vb), sel2 = min_backward(vb, va);
+        const float dq1 = -invB * sel1, dq2 = -invB * sel2;
         qnew1 = va; qnew2 = vb;
         if (lo && a < A && row0 + row < d.Bt) {
             const float da = actor_da(dap0, dq1, dap1, dq2);
@@ -208,7 +208,7 @@ __device__ __forceinline__ void policy_block(const Dev &d, const StepArg &sa, in
             const int n = n0 + 16 * t + c;
 #pragma unroll
             for (int i = 0; i < 4; ++i) {
-                gk2[t][i] = (h2v[t][i] > 0.f) ? acc[t][i] : 0.f;
+                gk2[t][i] = (h2v[t][i] <= 0.f) ? 0.f : acc[t][i];
                 X2[lds_off(4 * g + i, n, H)] = gk2[t][i];
             }
         }
@@ -229,7 +229,7 @@ __device__ __forceinline__ void policy_block(const Dev &d, const StepArg &sa, in
         for (int t = 0; t < CT; ++t) {
             f32x4 gv;
 #pragma unroll
-            for (int i = 0; i < 4; ++i) gv[i] = (h1v[t][i] > 0.f) ? acc[t][i] : 0.f;
+            for (int i = 0; i < 4; ++i) gv[i] = (h1v[t][i] <= 0.f) ? 0.f : acc[t][i];
             st4(d.dPH1T + frag_off(n0 + 16 * t + c, row0 + 4 * g, B), gv);
         }
     }

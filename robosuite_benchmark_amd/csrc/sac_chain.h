@@ -22,7 +22,7 @@
 //
 // Arithmetic: the policy pass, the head and the target / critic passes run the MFMA sequences of k_fwd_a / k_fwd_b at
 // column split 1 (bit-identical).  Q_i(s, a_new)'s first layer is contracted over [obs | a_new] directly -- the
-// four-launch step takes launch A's pre-activations of Q_i(s, a) and adds W1[:, action] (a_new - a), which needs the
+// four-launch step takes launch A's first-layer sums of Q_i(s, a) and adds W1[:, action] a_new to them, which needs the
 // other pass's result -- so q_new and what follows agree with the four-launch step to rounding (~1e-7 relative), not
 // bit for bit; against the oracle both sit within the same tolerances (tests/test_gpu_large_batch.py).
 #pragma once
@@ -264,7 +264,7 @@ __global__ __launch_bounds__(256) void k_chain(Dev d, const float *__restrict__ 
     if (a < A) {
         mean = HD[row * 32 + a] + PP[d.LP[2].offB + am];
         raw = HD[row * 32 + A + a] + PP[d.LP[2].offB + A + am];
-        lstd = fminf(fmaxf(raw, LOG_SIG_MIN), LOG_SIG_MAX);
+        lstd = clamp_nan(raw, LOG_SIG_MIN, LOG_SIG_MAX);
         stdv = expf(lstd);
         eps = epp ? epp[grow * A + am]
                   : philox_normal(d.noise_seed, (unsigned long long)sa.step_now, (unsigned)(grow * 16 + a), side ? 1u : 0u);
@@ -331,7 +331,7 @@ __global__ __launch_bounds__(256) void k_chain(Dev d, const float *__restrict__ 
 #pragma unroll
     for (int u = 0; u < 16; ++u) {
         const int off = lds_off(row, a + 16 * u, H);
-        XS[off] = (XS[off] > 0.f) ? w3[u] : 0.f;
+        XS[off] = (XS[off] <= 0.f) ? 0.f : w3[u];
     }
     lds_barrier();
     {   // dq/dh1 = dq/dh2 . W2, masked in place; the action rows of W1^T are requested inside it
@@ -345,7 +345,7 @@ __global__ __launch_bounds__(256) void k_chain(Dev d, const float *__restrict__ 
 #pragma unroll
             for (int i = 0; i < 4; ++i) {
                 const int off = lds_off(4 * g + i, 64 * wave + 16 * t + c, H);
-                X1[off] = (X1[off] > 0.f) ? acc[t][i] : 0.f;
+                X1[off] = (X1[off] <= 0.f) ? 0.f : acc[t][i];
             }
     }
     lds_barrier();
@@ -636,7 +636,7 @@ __global__ __launch_bounds__(512) void k_chain8(Dev d, const float *__restrict__
     if (a < A) {
         mean = HD[row * 32 + a] + PP[d.LP[2].offB + am];
         raw = HD[row * 32 + A + a] + PP[d.LP[2].offB + A + am];
-        lstd = fminf(fmaxf(raw, LOG_SIG_MIN), LOG_SIG_MAX);
+        lstd = clamp_nan(raw, LOG_SIG_MIN, LOG_SIG_MAX);
         stdv = expf(lstd);
         eps = epp ? epp[grow * A + am]
                   : philox_normal(d.noise_seed, (unsigned long long)sa.step_now, (unsigned)(grow * 16 + a), side ? 1u : 0u);
@@ -719,7 +719,7 @@ __global__ __launch_bounds__(512) void k_chain8(Dev d, const float *__restrict__
 #pragma unroll
         for (int u = 0; u < 16; ++u) {
             const int off = lds_off(row, a + 16 * u, H);
-            XS[off] = (XS[off] > 0.f) ? w3[u] : 0.f;
+            XS[off] = (XS[off] <= 0.f) ? 0.f : w3[u];
         }
     }
     lds_barrier();
@@ -733,7 +733,7 @@ __global__ __launch_bounds__(512) void k_chain8(Dev d, const float *__restrict__
 #pragma unroll
             for (int i = 0; i < 4; ++i) {
                 const int off = lds_off(4 * g + i, chain8::CF * wave + 16 * t + c, H);
-                X1[off] = (X1[off] > 0.f) ? acc[t][i] : 0.f;
+                X1[off] = (X1[off] <= 0.f) ? 0.f : acc[t][i];
             }
     }
     lds_barrier();

@@ -8,12 +8,12 @@
 // workgroups run all three phases and hand those few KB to each other through HBM inside the launch:
 //
 //   critic chain (twin i, row-block rb, column part p)      policy chain (side s, rb, p)
-//   A  Q_i(s, a): first layer (z kept in registers),         A  pi(side): first layer, 64-column slice, head partial
+//   A  Q_i(s, a): first layer (z_s kept in registers),       A  pi(side): first layer, 64-column slice, head partial
 //      64-column slice (W2 slice streamed once, staged           --> head[side][rb] published
 //      transposed in LDS), q partial
 //   -- wait head[s][rb] ---------------------------------    -- wait head[s'][rb] ---------------------------------
 //   B  tanh-Gaussian head on s; Q_i(s, a_new): first layer    B  head on s'; T_{side+1}(s', a'): first layer, slice,
-//      = z + W1[:, act] (a_new - a), slice (second, L2-warm      q partial
+//      = z_s + W1[:, act] a_new, slice (second, L2-warm          q partial
 //      pass over the same W2 slice), q partial; unit
 //      gradient dQ_i/da from the staged slice (partials)
 //   -- wait phase B of all 16 blocks of rb, and the 16 row-block sums of log pi -------------------------------------
@@ -344,18 +344,19 @@ __global__ __launch_bounds__(256) void k_abc(Dev d, const float *__restrict__ S,
             for (int t = 0; t < 4; ++t)
 #pragma unroll
                 for (int i = 0; i < 4; ++i) {
-                    keep1[t][i] = fmaxf(zkeep[t][i], 0.f);
+                    keep1[t][i] = relu_nan(zkeep[t][i]);
                     X1[lds_off(4 * g + i, 64 * wave + 16 * t + c, H)] = keep1[t][i];
                 }
         } else {   // first layer, all 256 features (recomputed by the 4 blocks of this row-block)
-            f32x4 acc[4] = {};
-            gemm_straight_pf(r0, X0, KLQ, K0 >> 4, acc, r1, H >> 4, PRE0);
-            // the critic chain keeps the PRE-activation z = W1 [s, a] + b in registers: the layer is linear in the action,
-            // so phase B gets Q_i(s, a_new)'s first layer as z + W1[:, action chunk] (a_new - a)
+            f32x4 acc[4] = {}, zs[4];
+            gemm_straight_pf(r0, X0, KLQ, K0 >> 4, acc, r1, H >> 4, PRE0, isq ? (d.KP >> 4) : -1, zs);
+            // the critic chain keeps the sums in front of the action chunk (the last one), z_s = W1[:, obs] s + b, in
+            // registers: the layer is linear in the action, so phase B gets Q_i(s, a_new)'s first layer as
+            // z_s + W1[:, action chunk] a_new -- the batch action never enters it, as in torch (k_fwd_a, narrow layers)
 #pragma unroll
             for (int t = 0; t < 4; ++t)
 #pragma unroll
-                for (int i = 0; i < 4; ++i) zkeep[t][i] = acc[t][i] + bv0[t];
+                for (int i = 0; i < 4; ++i) zkeep[t][i] = (isq ? zs[t][i] : acc[t][i]) + bv0[t];
             hidden_epilogue<4>(acc, 64 * wave, 16, bv0, X1, H, keep1);
         }
         lds_barrier();
@@ -510,7 +511,7 @@ __global__ __launch_bounds__(256) void k_abc(Dev d, const float *__restrict__ S,
         for (int p = 1; p < SP; ++p) { mean += hm[p]; raw += hr[p]; }     // fixed order
         mean += hbm; raw += hbr;
         if constexpr (MODE == M_SAC) {
-            lstd = fminf(fmaxf(raw, LOG_SIG_MIN), LOG_SIG_MAX);
+            lstd = clamp_nan(raw, LOG_SIG_MIN, LOG_SIG_MAX);
             stdv = expf(lstd);
             zz = __fadd_rn(mean, __fmul_rn(stdv, eps));                  // TanhNormal.rsample
             act = tanhf(zz);
@@ -521,14 +522,14 @@ __global__ __launch_bounds__(256) void k_abc(Dev d, const float *__restrict__ S,
         } else {
             // TD3 target smoothing (k_fwd_b<M_TD3_CRITIC>): a' + clamp(N(0,1) * sigma, +-clip); the sum is NOT re-clipped
             zz = tanhf(mean);
-            act = zz + fminf(fmaxf(eps * d.td3_sigma, -d.td3_clip), d.td3_clip);
+            act = zz + clamp_nan(eps * d.td3_sigma, -d.td3_clip, d.td3_clip);
         }
     }
     // the whole action chunk (0 beyond A); the critic chain contracts the difference to the batch action
     {
         float *xa = X0 + lds_off(row, d.KP + a, KLQ);
         if constexpr (IMG) { if (isq) abat = *xa; }                      // (phase A left [obs | 0 | act | 0] here)
-        *xa = (a < A) ? (isq ? act - abat : act) : 0.f;
+        *xa = (a < A) ? ((isq && WIDE) ? act - abat : act) : 0.f;            // (narrow: z_s + W_a a_new)
     }
     const float lsum = group16_sum(lp);
     if (own_s && a == 0) red[row] = (grow < d.Bt) ? lsum : 0.f;          // (pad rows carry no weight)
@@ -549,7 +550,7 @@ __global__ __launch_bounds__(256) void k_abc(Dev d, const float *__restrict__ S,
 #pragma unroll
             for (int t = 0; t < 4; ++t)
 #pragma unroll
-                for (int i = 0; i < 4; ++i) X1[lds_off(4 * g + i, 64 * wave + 16 * t + c, H)] = fmaxf(acc0[t][i], 0.f);
+                for (int i = 0; i < 4; ++i) X1[lds_off(4 * g + i, 64 * wave + 16 * t + c, H)] = relu_nan(acc0[t][i]);
         }
     } else {
         gemm_straight(q0, X0, KLQ, KS0, acc0, lo0);
@@ -606,7 +607,7 @@ __global__ __launch_bounds__(256) void k_abc(Dev d, const float *__restrict__ S,
 #pragma unroll
         for (int u = 0; u < 4; ++u) {                        // dq/dh2 = w3 * relu'(h2), in place (own elements)
             const int off = lds_off(row, a + 16 * u, SW);
-            XS[off] = (XS[off] > 0.f) ? w3[u] : 0.f;
+            XS[off] = (XS[off] <= 0.f) ? 0.f : w3[u];
         }
         lds_barrier();
         {   // partial dq/dh1 over ALL first-hidden features = dq/dh2[:, slice] . W2[slice, :] (staged in phase A), masked
@@ -617,7 +618,7 @@ __global__ __launch_bounds__(256) void k_abc(Dev d, const float *__restrict__ S,
 #pragma unroll
                 for (int i = 0; i < 4; ++i) {
                     const int off = lds_off(4 * g + i, 64 * wave + 16 * t + c, H);
-                    X1[off] = (X1[off] > 0.f) ? acc[t][i] : 0.f;
+                    X1[off] = (X1[off] <= 0.f) ? 0.f : acc[t][i];
                 }
             }
         }
@@ -693,7 +694,7 @@ __global__ __launch_bounds__(256) void k_abc(Dev d, const float *__restrict__ S,
             va += b3a;                                                       // T1(s',a')
             vb += b3b;                                                       // T2(s',a')
             vq += b3q;                                                       // Q_i(s,a)
-            const float tq = fminf(va, vb) - alpha * in_c;
+            const float tq = min_nan(va, vb) - alpha * in_c;
             yv = bellman_target(d.reward_scale, in_r, in_t, d.discount, tq);
             dq = (row0 + (int)threadIdx.x < d.Bt) ? 2.0f * (vq - yv) * invB : 0.f;
             s_dq[threadIdx.x] = dq;
@@ -706,7 +707,7 @@ __global__ __launch_bounds__(256) void k_abc(Dev d, const float *__restrict__ S,
         for (int qd = 0; qd < 4; ++qd) {
 #pragma unroll
             for (int i = 0; i < 4; ++i) {
-                gv2[qd][i] = (h2v[qd][i] > 0.f) ? s_dq[4 * qd + i] * wk : 0.f;
+                gv2[qd][i] = (h2v[qd][i] <= 0.f) ? 0.f : s_dq[4 * qd + i] * wk;
                 X2[lds_off(4 * qd + i, k, H)] = gv2[qd][i];
             }
         }
@@ -730,7 +731,7 @@ __global__ __launch_bounds__(256) void k_abc(Dev d, const float *__restrict__ S,
             }
             f32x4 gv;
 #pragma unroll
-            for (int i = 0; i < 4; ++i) gv[i] = (h1v[0][i] > 0.f) ? acc[0][i] : 0.f;
+            for (int i = 0; i < 4; ++i) gv[i] = (h1v[0][i] <= 0.f) ? 0.f : acc[0][i];
             st4(d.dQH1T + (size_t)net * H * B + frag_off(n0 + c, row0 + 4 * g, B), gv);
         }
         STAMP(0, 9);
@@ -787,8 +788,8 @@ __global__ __launch_bounds__(256) void k_abc(Dev d, const float *__restrict__ S,
             for (int p = 1; p < SP; ++p) { va += qa[p]; vb += qb[p]; }                   // fixed order
             va += b3a; vb += b3b;                                                        // Q1, Q2(s, a_new)
             // torch.min backward: the smaller one takes the gradient, a tie splits it
-            const float sel1 = (va < vb) ? 1.0f : ((va == vb) ? 0.5f : 0.0f);
-            const float dq1 = -invB * sel1, dq2 = -invB * (1.0f - sel1);
+            const float sel1 = min_backward(va, vb), sel2 = min_backward(vb, va);
+            const float dq1 = -invB * sel1, dq2 = -invB * sel2;
             qnew1 = va; qnew2 = vb;
             if (a < A && grow < d.Bt) {
                 float da1 = dap[0], da2 = dap[SP];
@@ -814,7 +815,7 @@ __global__ __launch_bounds__(256) void k_abc(Dev d, const float *__restrict__ S,
                 const int n = 64 * wave + 16 * t + c;
 #pragma unroll
                 for (int i = 0; i < 4; ++i) {
-                    gk2[t][i] = (h2v[t][i] > 0.f) ? acc[t][i] : 0.f;
+                    gk2[t][i] = (h2v[t][i] <= 0.f) ? 0.f : acc[t][i];
                     X2[lds_off(4 * g + i, n, H)] = gk2[t][i];
                 }
             }
@@ -839,7 +840,7 @@ __global__ __launch_bounds__(256) void k_abc(Dev d, const float *__restrict__ S,
                 const f32x4 o = ld4(hx + ((wave & 1) * 64 + lane) * 4);
                 f32x4 gv;
 #pragma unroll
-                for (int i = 0; i < 4; ++i) gv[i] = (h1v[0][i] > 0.f) ? (acc[0][i] + o[i]) : 0.f;
+                for (int i = 0; i < 4; ++i) gv[i] = (h1v[0][i] <= 0.f) ? 0.f : (acc[0][i] + o[i]);
                 st4(d.dPH1T + frag_off(nt + c, row0 + 4 * g, B), gv);
             }
         }

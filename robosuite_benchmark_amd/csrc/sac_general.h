@@ -405,8 +405,8 @@ __device__ __forceinline__ void g_gemm_body(const GemmStage &T, int bx) {
         for (int i = 0; i < 4; ++i) {
             const int m = m0 + 16 * rt + 4 * g + i;
             float v = acc[t][i] + (has_bias ? bv[t] : 0.f);
-            if (J.relu) v = fmaxf(v, 0.f);
-            if (has_mask) v = (mk[t][i] > 0.f) ? v : 0.f;
+            if (J.relu) v = relu_nan(v);
+            if (has_mask) v = (mk[t][i] <= 0.f) ? 0.f : v;
             if (m < J.M && n < J.N) *(__attribute__((address_space(1))) float *)(uintptr_t)(Cg + ((unsigned)m * ldc + (unsigned)n)) = v;
         }
     }
@@ -536,7 +536,7 @@ __device__ __forceinline__ void g_head_body(GDev d, const float *__restrict__ S,
             for (int q = 1; q < 16; ++q) { mean += part[rr][q][a]; raw += part[rr][q][16 + a]; }      // fixed order
             mean += d.bh[a]; raw += d.bh[A + a];
             d.HDw[(long long)r * 2 * A + a] = mean; d.HDw[(long long)r * 2 * A + A + a] = raw;
-            const float lstd = fminf(fmaxf(raw, LOG_SIG_MIN), LOG_SIG_MAX);
+            const float lstd = clamp_nan(raw, LOG_SIG_MIN, LOG_SIG_MAX);
             const float stdv = expf(lstd);
             const float eps = epp ? epp[(long long)b * A + a]
                                   : philox_normal(d.noise_seed, (unsigned long long)sa.step_now, (unsigned)(b * d.NI + a), side ? 1u : 0u);
@@ -637,13 +637,13 @@ __device__ __forceinline__ void g_loss_body(GDev d, const float *__restrict__ S,
         const float q1 = v[0] + p_b[0], qa = v[1] + p_b[0], q2 = v[2] + p_b[1], qb = v[3] + p_b[1];
         const float t1 = v[4] + p_b[2], t2 = v[5] + p_b[3];
         const float invB = 1.0f / (float)n;
-        const float tq = fminf(t1, t2) - p_alpha * p_lp2;
+        const float tq = min_nan(t1, t2) - p_alpha * p_lp2;
         const float y = bellman_target(d.reward_scale, p_rew, p_term, d.discount, tq);
         d.QOw[0][b] = q1; d.QOw[0][n + b] = qa; d.QOw[1][b] = q2; d.QOw[1][n + b] = qb; d.QOw[2][b] = t1; d.QOw[3][b] = t2;
         d.y[b] = y;
-        d.qn[b] = fminf(qa, qb);
-        const float sel1 = (qa < qb) ? 1.0f : ((qa == qb) ? 0.5f : 0.0f);
-        const float g0 = 2.0f * (q1 - y) * invB, g1 = 2.0f * (q2 - y) * invB, g2 = -invB * sel1, g3 = -invB * (1.0f - sel1);
+        d.qn[b] = min_nan(qa, qb);
+        const float sel1 = min_backward(qa, qb), sel2 = min_backward(qb, qa);
+        const float g0 = 2.0f * (q1 - y) * invB, g1 = 2.0f * (q2 - y) * invB, g2 = -invB * sel1, g3 = -invB * sel2;
         d.DQ[0][b] = g0; d.DQ[1][b] = g1; d.DQ[0][n + b] = g2; d.DQ[1][n + b] = g3;
         s_dq[0] = g0; s_dq[1] = g2; s_dq[2] = g1; s_dq[3] = g3;          // in the order of h[0 .. 3]
     }
@@ -652,7 +652,7 @@ __device__ __forceinline__ void g_loss_body(GDev d, const float *__restrict__ S,
                    d.dQZl[1] + (long long)(n + b) * K};
     for (int k = threadIdx.x; k < K; k += 256) {
 #pragma unroll
-        for (int q = 0; q < 4; ++q) o[q][k] = (h[q][k] > 0.f) ? s_dq[q] * w[q][k] : 0.f;
+        for (int q = 0; q < 4; ++q) o[q][k] = (h[q][k] <= 0.f) ? 0.f : s_dq[q] * w[q][k];
     }
 }
 __global__ __launch_bounds__(256) void k_g_loss(GDev d, const float *__restrict__ S, SlotLayout SL) {
@@ -798,7 +798,7 @@ __device__ __forceinline__ void g_polgrad_body(GDev d, unsigned bx) {
             }
 #pragma unroll
         for (int q = 0; q < GRW; ++q)
-            if (b0 + q < n) d.dPZl[(long long)(b0 + q) * K + k] = (hc[q] > 0.f) ? sacc[q] : 0.f;
+            if (b0 + q < n) d.dPZl[(long long)(b0 + q) * K + k] = (hc[q] <= 0.f) ? 0.f : sacc[q];
     }
 }
 template <int MA>
@@ -828,7 +828,7 @@ __device__ void diag_block(const GDev &d, const StepArg &sa) {
     const float alpha = d.ctl->alpha;
     auto stat = [&](int q0, float v) {
         acc[q0] += (double)v; acc[q0 + 1] += (double)v * (double)v;
-        acc[q0 + 2] = fmax(acc[q0 + 2], (double)v); acc[q0 + 3] = fmin(acc[q0 + 3], (double)v);
+        acc[q0 + 2] = max_nan(acc[q0 + 2], (double)v); acc[q0 + 3] = min_nan(acc[q0 + 3], (double)v);
     };
     for (int i = threadIdx.x; i < n; i += 256) {
         const float q1 = d.QO[0][i], q2 = d.QO[1][i], y = d.y[i], lp = d.logpi[i], qn = d.qn[i];
@@ -847,7 +847,7 @@ __device__ void diag_block(const GDev &d, const StepArg &sa) {
         double v = acc[q];
         for (int o = 32; o > 0; o >>= 1) {
             const double w = __shfl_xor(v, o);
-            v = kind == 2 ? fmax(v, w) : (kind == 3 ? fmin(v, w) : v + w);
+            v = kind == 2 ? max_nan(v, w) : (kind == 3 ? min_nan(v, w) : v + w);
         }
         if (lane == 0) part[wave][q] = v;
     }
@@ -858,7 +858,7 @@ __device__ void diag_block(const GDev &d, const StepArg &sa) {
         const bool stq = q < 16 || q >= 20;
         const int kind = stq ? (q & 3) : 0;
         double v = part[0][q];
-        for (int w = 1; w < 4; ++w) v = kind == 2 ? fmax(v, part[w][q]) : (kind == 3 ? fmin(v, part[w][q]) : v + part[w][q]);
+        for (int w = 1; w < 4; ++w) v = kind == 2 ? max_nan(v, part[w][q]) : (kind == 3 ? min_nan(v, part[w][q]) : v + part[w][q]);
         tot[q] = v;
     }
     float out[SAC_DIAG_N];
@@ -915,7 +915,7 @@ __device__ __forceinline__ void g_td3_head_body(GDev d, const float *__restrict_
         d.HDTw[(long long)b * A + a] = mean;
         const float eps = d.eps2 ? d.eps2[(long long)b * A + a]
                                  : philox_normal(d.noise_seed, (unsigned long long)sa.step_now, (unsigned)(b * d.NI + a), 1u);
-        const float act = tanhf(mean) + fminf(fmaxf(eps * d.td3_sigma, -d.td3_clip), d.td3_clip);
+        const float act = tanhf(mean) + clamp_nan(eps * d.td3_sigma, -d.td3_clip, d.td3_clip);
         d.a2[(long long)b * A + a] = act;
         d.XQ[(long long)(n + b) * ldq + O + a] = act;
     }
@@ -959,7 +959,7 @@ __device__ __forceinline__ void g_td3_loss_body(GDev d, const float *__restrict_
 #pragma unroll
         for (int q = 0; q < 4; ++q) v[q] = ((red[0][q] + red[1][q]) + (red[2][q] + red[3][q])) + p_b[q];      // fixed order
         const float invB = 1.0f / (float)n;
-        const float y = bellman_target(d.reward_scale, p_rew, p_term, d.discount, fminf(v[2], v[3]));
+        const float y = bellman_target(d.reward_scale, p_rew, p_term, d.discount, min_nan(v[2], v[3]));
 #pragma unroll
         for (int q = 0; q < 4; ++q) d.QOw[q][b] = v[q];
         d.y[b] = y;
@@ -971,7 +971,7 @@ __device__ __forceinline__ void g_td3_loss_body(GDev d, const float *__restrict_
     float *o[2] = {d.dQZl[0] + (long long)b * K, d.dQZl[1] + (long long)b * K};
     for (int k = threadIdx.x; k < K; k += 256) {
 #pragma unroll
-        for (int q = 0; q < 2; ++q) o[q][k] = (h[q][k] > 0.f) ? s_dq[q] * w[q][k] : 0.f;
+        for (int q = 0; q < 2; ++q) o[q][k] = (h[q][k] <= 0.f) ? 0.f : s_dq[q] * w[q][k];
     }
 }
 __global__ __launch_bounds__(256) void k_g_td3_loss(GDev d, const float *__restrict__ S, SlotLayout SL) {
@@ -1026,7 +1026,7 @@ __device__ __forceinline__ void g_td3_qa_body(GDev d, int backward, unsigned bx)
     if (!backward) return;
     const float g = -1.0f / (float)n;
     float *o = d.dAZl + (long long)b * K;
-    for (int k = threadIdx.x; k < K; k += 256) o[k] = (h[k] > 0.f) ? g * w[k] : 0.f;
+    for (int k = threadIdx.x; k < K; k += 256) o[k] = (h[k] <= 0.f) ? 0.f : g * w[k];
 }
 __global__ __launch_bounds__(256) void k_g_td3_qa(GDev d, int backward) {
     g_td3_qa_body(d, backward, blockIdx.x);
@@ -1139,7 +1139,7 @@ __device__ __forceinline__ void g_td3_polgrad_body(GDev d, unsigned bx) {
             }
 #pragma unroll
         for (int q = 0; q < GRW; ++q)
-            if (b0 + q < n) d.dPZl[(long long)(b0 + q) * K + k] = (hc[q] > 0.f) ? sacc[q] : 0.f;
+            if (b0 + q < n) d.dPZl[(long long)(b0 + q) * K + k] = (hc[q] <= 0.f) ? 0.f : sacc[q];
     }
 }
 template <int MA>
@@ -1157,7 +1157,7 @@ __device__ void td3_diag_block(const GDev &d, const StepArg &sa) {
     float mx[NS], mn[NS];
 #pragma unroll
     for (int q = 0; q < NS; ++q) { sm[q] = 0; sq[q] = 0; mx[q] = -INFINITY; mn[q] = INFINITY; }
-    auto acc1 = [&](int q, float v) { sm[q] += v; sq[q] += (double)v * v; mx[q] = fmaxf(mx[q], v); mn[q] = fminf(mn[q], v); };
+    auto acc1 = [&](int q, float v) { sm[q] += v; sq[q] += (double)v * v; mx[q] = max_nan(mx[q], v); mn[q] = min_nan(mn[q], v); };
     if (sa.pad & 1)
         for (int i = threadIdx.x; i < n; i += 256) {
             const float yv = d.y[i], q1 = d.QO[0][i], q2 = d.QO[1][i];
@@ -1172,7 +1172,7 @@ __device__ void td3_diag_block(const GDev &d, const StepArg &sa) {
 #pragma unroll
         for (int q = 0; q < NS; ++q) {
             sm[q] += __shfl_xor(sm[q], o); sq[q] += __shfl_xor(sq[q], o);
-            mx[q] = fmaxf(mx[q], __shfl_xor(mx[q], o)); mn[q] = fminf(mn[q], __shfl_xor(mn[q], o));
+            mx[q] = max_nan(mx[q], __shfl_xor(mx[q], o)); mn[q] = min_nan(mn[q], __shfl_xor(mn[q], o));
         }
         lsum += __shfl_xor(lsum, o);
     }
@@ -1193,7 +1193,7 @@ __device__ void td3_diag_block(const GDev &d, const StepArg &sa) {
         const int q = threadIdx.x;
         if ((q < 5) ? (sa.pad & 1) : (sa.pad & 2)) {
             double s = 0, s2 = 0, MX = -INFINITY, MN = INFINITY;
-            for (int w = 0; w < 4; ++w) { s += sh[w][q]; s2 += sh[w][6 + q]; MX = fmax(MX, sh[w][12 + q]); MN = fmin(MN, sh[w][18 + q]); }
+            for (int w = 0; w < 4; ++w) { s += sh[w][q]; s2 += sh[w][6 + q]; MX = max_nan(MX, sh[w][12 + q]); MN = min_nan(MN, sh[w][18 + q]); }
             const double cnt = (q < 5) ? (double)n : (double)n * A;
             const double mean = s / cnt;
             double var = s2 / cnt - mean * mean;

@@ -25,9 +25,9 @@ constexpr int ACT_HEAD_LD = 32;           // head pre-activations [16][32]: mean
 
 // ---- fused shapes: two hidden layers of at most 256 units, padded to 256, weights in Net::P (fragment-major) ----
 
-// The hidden layers' bias + ReLU.  It stands in for the step kernels' hidden_epilogue, whose ReLU is
-// fmaxf(x, 0): that gives 0 for NaN and would turn a non-finite observation row into a finite action, where torch's relu
-// and the host forward keep the NaN.  Here x < 0 ? 0 : x; every finite value comes out as from fmaxf, up to the sign of
+// The hidden layers' bias + ReLU, as the step kernels' hidden_epilogue spells it (relu_nan): x < 0 ? 0 : x, not
+// fmaxf(x, 0), which gives 0 for NaN and would turn a non-finite observation row into a finite action, where torch's relu
+// and the host forward keep the NaN.  Every finite value comes out as from fmaxf, up to the sign of
 // a zero, which no sum downstream can see.  With hidden sizes below 256 an Inf observation becomes NaN already in the
 // zero-weight pad units (0 * inf) and from there in every unit of the next layer; torch has no pad units but reaches NaN
 // in its second layer too, through inf - inf over units of both signs, so the actions agree (NaN) all the same.

@@ -14,7 +14,7 @@
 // the Polyak update in its epilogue, so gradients never round-trip through HBM.
 //
 //   A k_fwd_a       16*B/16 WGs   pi(s), pi(s') -> head partials; Q1,Q2(s,a) -> q partials (+ first-layer pre-activations z)
-//   B k_fwd_b       16*B/16 WGs   tanh-Gaussian head; Q1,Q2(s,a_new) (first layer = z + W_a (a_new - a)), T1,T2(s',a')
+//   B k_fwd_b       16*B/16 WGs   tanh-Gaussian head; Q1,Q2(s,a_new) (first layer = z_s + W_a a_new), T1,T2(s',a')
 //                                 -> q partials; the Q(s,a_new) blocks continue to the UNIT gradient dQ/da (partials)
 //   C k_bwd         12*B/16 WGs   critic dL/dh (2 nets) | policy: min-select, head gradient (reparameterised), dL/dh
 //   D k_dw_adam     ~250  WGs     dW = dY^T X over the batch (MFMA), Adam, Polyak, diagnostics
@@ -46,6 +46,18 @@ constexpr float ADAM_B1 = 0.9f, ADAM_B2 = 0.999f, ADAM_EPS = 1e-8f;
 // torch computes 1 - beta in double and applies it as an fp32 scalar: (float)(1.0 - 0.9), (float)(1.0 - 0.999)
 constexpr float ADAM_1MB1 = (float)(1.0 - 0.9), ADAM_1MB2 = (float)(1.0 - 0.999);
 constexpr int DIAG_TRACE_CAP = 4096;
+
+// The step's ReLU, minimum, clamps and running Max / Min as torch and NumPy define them on non-finite values: a NaN on
+// either side stays a NaN (fmaxf / fminf return the OTHER operand, which turns a NaN pre-activation into a dead unit, a
+// NaN log-std into -20 and drops a NaN row from a logged Max).  Every finite value comes out as from fmaxf / fminf, up to
+// the sign of a zero.  A diverged run so logs NaN where the reference does.
+__host__ __device__ __forceinline__ float relu_nan(float v) { return v < 0.f ? 0.f : v; }                  // torch.relu
+template <class T> __host__ __device__ __forceinline__ T max_nan(T a, T b) { return (b > a || b != b) ? b : a; }   // np.max
+template <class T> __host__ __device__ __forceinline__ T min_nan(T a, T b) { return (b < a || b != b) ? b : a; }   // torch.min
+__host__ __device__ __forceinline__ float clamp_nan(float v, float lo, float hi) { return v < lo ? lo : (v > hi ? hi : v); }
+// torch.minimum's backward, the share of the gradient that `a` takes: all of it where a < b, half on a tie, none where
+// a > b -- and all of it on BOTH sides where either is a NaN (torch masks by a > b, which a NaN never satisfies).
+__device__ __forceinline__ float min_backward(float a, float b) { return (a == b) ? 0.5f : ((a > b) ? 0.0f : 1.0f); }
 // kernel variants: the SAC step, the TD3 critic pass (target policy, T1/T2, critic backward) and the TD3 actor pass
 constexpr int M_SAC = 0, M_TD3_CRITIC = 1, M_TD3_ACTOR = 2;
 constexpr int RD = 4;             // ring depth (k-chunks in flight) for the runtime-K first layers
@@ -406,7 +418,8 @@ __device__ __forceinline__ void gemm_straight(WRing<NT, D> &R, const float *X, i
 // those loads would only keep the wave stalled at issue (the CU's fill path is the bottleneck) in front of this GEMM.
 template <int NT, int D, int NT1, int D1>
 __device__ __forceinline__ void gemm_straight_pf(WRing<NT, D> &R, const float *X, int KL, int KS, f32x4 (&acc)[NT],
-                                                 WRing<NT1, D1> &R1, int KS1, int pre = D) {
+                                                 WRing<NT1, D1> &R1, int KS1, int pre = D, int snap_u = -1,
+                                                 f32x4 *snap = nullptr) {
     const int lane = threadIdx.x & 63;
     const int r = lane & 15, g = lane >> 4;
     const float *xrow = X + r * KL;
@@ -419,6 +432,12 @@ __device__ __forceinline__ void gemm_straight_pf(WRing<NT, D> &R, const float *X
             SB();
             R.fill_part(KS, u + pre, u + pre + 1);
             SB();
+        }
+        // snap_u >= 0: the sums over the chunks in front of chunk snap_u are kept in `snap` (the critics' first layer
+        // without its action chunk, the last one: what Q_i(s, a_new) starts from)
+        if (u == snap_u) {
+#pragma unroll
+            for (int t = 0; t < NT; ++t) snap[t] = acc[t];
         }
         if (u < KS) {
             const f32x4 a = ld4(xrow + 4 * ((4 * u + g) ^ r));
@@ -593,7 +612,7 @@ __device__ __forceinline__ void hidden_epilogue(const f32x4 (&acc)[NT], int n_ba
         const int n = n_base + t * n_stride + c;
 #pragma unroll
         for (int i = 0; i < 4; ++i) {
-            keep[t][i] = fmaxf(acc[t][i] + bv[t], 0.f);
+            keep[t][i] = relu_nan(acc[t][i] + bv[t]);
             Xn[lds_off(4 * g + i, n, KL)] = keep[t][i];
         }
     }
@@ -642,7 +661,7 @@ __device__ __forceinline__ void slice_epilogue(const f32x4 (&acc)[NTW], const fl
         f32x4 v;
 #pragma unroll
         for (int i = 0; i < 4; ++i) {
-            v[i] = fmaxf(acc[t][i] + bv[t], 0.f);
+            v[i] = relu_nan(acc[t][i] + bv[t]);
             XS[lds_off(4 * g + i, 16 * (NTW * wave + t) + c, 64 * NTW)] = v[i];
         }
         if (outT) {
@@ -725,17 +744,20 @@ __device__ __forceinline__ void fwd_a_body(const Dev &d, const float *__restrict
     f32x4 keep1[4], zkeep[4];
     {   // first layer, all 256 features (recomputed by the SP blocks of this row-block)
         f32x4 acc[4] = {};
+        // Q blocks keep this quarter's pre-activation for launch B: the first layer is linear in the action, so
+        // Q_i(s, a_new) only needs the action chunk of the weights there instead of streaming the whole first layer again.
+        // Narrow layers keep the sums WITHOUT the action chunk (the last one), z_s = W1[:, obs] s + b, and launch B adds
+        // W1[:, action chunk] a_new: the batch action never enters Q_i(s, a_new), as in torch (a NaN action stays out of
+        // the policy's loss).  Wide layers keep z = W1 [s, a] + b, and launch B adds W1[:, action chunk] (a_new - a).
+        f32x4 zs[4];
         if constexpr (WIDE) gemm_ring(r0, X0, KL0, K0 >> 4, acc);
         else {
-            gemm_straight_pf(r0, X0, KL0, K0 >> 4, acc, r1, H >> 4, PRE0);
+            gemm_straight_pf(r0, X0, KL0, K0 >> 4, acc, r1, H >> 4, PRE0, (MODE == M_SAC && !is_pi) ? (d.KP >> 4) : -1, zs);
         }
-        // Q blocks keep this quarter's PRE-activation z = W1 [s, a] + b for launch B: the first layer is linear in
-        // the action, so Q_i(s, a_new) only needs z + W1[:, action chunk] (a_new - a) there instead of streaming
-        // the whole first layer again
 #pragma unroll
         for (int t = 0; t < 4; ++t)
 #pragma unroll
-            for (int i = 0; i < 4; ++i) zkeep[t][i] = acc[t][i] + bv0[t];
+            for (int i = 0; i < 4; ++i) zkeep[t][i] = ((WIDE || MODE != M_SAC || is_pi) ? acc[t][i] : zs[t][i]) + bv0[t];
         hidden_epilogue<4>(acc, 64 * wave, 16, bv0, X1, H, keep1);
     }
     lds_barrier();
@@ -833,9 +855,10 @@ __device__ __forceinline__ void fwd_b_body(const Dev &d, const float *__restrict
         if constexpr (MODE == M_SAC) hbr = PH[d.LP[2].offB + A + am];
         if (MODE != M_TD3_ACTOR && epp) epsin = epp[grow * A + am];
     }
-    // Q1/Q2(s, a_new) blocks: launch A left the first-layer pre-activations z of Q_i(s, a) in QU and the layer is linear
-    // in the action, so z + W1[:, action chunk] (a_new - a) needs only the action chunk of the weights and of the
-    // input; target-net blocks do the whole layer.  (Wide first layers: the ring starts AT the action chunk.)
+    // Q1/Q2(s, a_new) blocks: launch A left the first-layer sums z_s of Q_i(s, a) without the action chunk in QU and the
+    // layer is linear in the action, so z_s + W1[:, action chunk] a_new needs only the action chunk of the weights and
+    // of the input; target-net blocks do the whole layer.  (Wide first layers: QU holds z of [s, a], the input is
+    // a_new - a, and the ring starts AT the action chunk.)
     const bool act_only = (MODE == M_SAC) && (p4 < 2);
     constexpr int D0 = WIDE ? RD : RD0, Q0 = D0 / 4;         // first-layer ring, issued in four pieces
     const int KS0 = d.KQ >> 4;
@@ -886,7 +909,7 @@ __device__ __forceinline__ void fwd_b_body(const Dev &d, const float *__restrict
         for (int p = 1; p < SP; ++p) { mean += hm[p]; raw += hr[p]; }     // fixed order
         mean += hbm; raw += hbr;
         if constexpr (MODE == M_SAC) {
-            lstd = fminf(fmaxf(raw, LOG_SIG_MIN), LOG_SIG_MAX);
+            lstd = clamp_nan(raw, LOG_SIG_MIN, LOG_SIG_MAX);
             stdv = expf(lstd);
         }
         if constexpr (MODE != M_TD3_ACTOR)
@@ -904,14 +927,14 @@ __device__ __forceinline__ void fwd_b_body(const Dev &d, const float *__restrict
         } else if constexpr (MODE == M_TD3_CRITIC) {
             // TD3 target smoothing: a' + clamp(N(0,1) * sigma, +-clip); the sum is NOT clipped to the action range
             zz = tanhf(mean);
-            act = zz + fminf(fmaxf(eps * d.td3_sigma, -d.td3_clip), d.td3_clip);
+            act = zz + clamp_nan(eps * d.td3_sigma, -d.td3_clip, d.td3_clip);
         } else {
             zz = mean;                                                   // pre-tanh output of the online policy
             act = tanhf(mean);
         }
     }
     // the whole action chunk (0 beyond A); act_only blocks contract the difference to the batch action
-    XQ[lds_off(row, d.KP + a, KLQ)] = (a < A) ? (act_only ? act - abat : act) : 0.f;
+    XQ[lds_off(row, d.KP + a, KLQ)] = (a < A) ? ((act_only && WIDE) ? act - abat : act) : 0.f;   // (narrow: z_s + W_a a_new)
     SB();
     r0.fill_part(ks0, 3 * Q0, D0, lo0);
     r1.fill_part(H >> 4, act_only ? 3 * QR : 0, act_only ? RD1 : RD1 / 2);
@@ -1008,7 +1031,7 @@ __device__ __forceinline__ void fwd_b_body(const Dev &d, const float *__restrict
 #pragma unroll
     for (int u = 0; u < 4 * NTW; ++u) {                      // dq/dh2 = w3 * relu'(h2), in place (own elements)
         const int off = lds_off(row, a + 16 * u, SW);
-        XS[off] = (XS[off] > 0.f) ? w3[u] : 0.f;
+        XS[off] = (XS[off] <= 0.f) ? 0.f : w3[u];
     }
     lds_barrier();
     STAMP(1, 5);
@@ -1022,7 +1045,7 @@ __device__ __forceinline__ void fwd_b_body(const Dev &d, const float *__restrict
 #pragma unroll
             for (int i = 0; i < 4; ++i) {
                 const int off = lds_off(4 * g + i, 64 * wave + 16 * t + c, H);
-                X1[off] = (X1[off] > 0.f) ? acc[t][i] : 0.f;
+                X1[off] = (X1[off] <= 0.f) ? 0.f : acc[t][i];
             }
         }
     }
@@ -1111,7 +1134,7 @@ __device__ __forceinline__ void critic_bwd_block(const Dev &d, const float *__re
         va += b3a;                                                       // T1(s',a')
         vb += b3b;                                                       // T2(s',a')
         vq += b3q;                                                       // Q_i(s,a)
-        const float tq = fminf(va, vb) - alpha * in_c;
+        const float tq = min_nan(va, vb) - alpha * in_c;
         yv = bellman_target(d.reward_scale, in_r, in_t, d.discount, tq);
         dq = (row0 + (int)threadIdx.x < d.Bt) ? 2.0f * (vq - yv) * invB : 0.f;
         s_dq[threadIdx.x] = dq;
@@ -1123,7 +1146,7 @@ __device__ __forceinline__ void critic_bwd_block(const Dev &d, const float *__re
     for (int qd = 0; qd < 4; ++qd) {
 #pragma unroll
         for (int i = 0; i < 4; ++i) {
-            gv2[qd][i] = (h2v[qd][i] > 0.f) ? s_dq[4 * qd + i] * wk : 0.f;
+            gv2[qd][i] = (h2v[qd][i] <= 0.f) ? 0.f : s_dq[4 * qd + i] * wk;
             X2[lds_off(4 * qd + i, k, H)] = gv2[qd][i];
         }
     }
@@ -1147,7 +1170,7 @@ __device__ __forceinline__ void critic_bwd_block(const Dev &d, const float *__re
         for (int t = 0; t < NTW; ++t) {
             f32x4 gv;
 #pragma unroll
-            for (int i = 0; i < 4; ++i) gv[i] = (h1v[t][i] > 0.f) ? acc[t][i] : 0.f;
+            for (int i = 0; i < 4; ++i) gv[i] = (h1v[t][i] <= 0.f) ? 0.f : acc[t][i];
             st4(d.dQH1T + (size_t)qi * H * B + frag_off(n0 + 16 * t + c, row0 + 4 * g, B), gv);
         }
     }
@@ -1234,8 +1257,9 @@ __device__ __forceinline__ void policy_bwd_block(const Dev &d, const StepArg &sa
         for (int p = 1; p < SP; ++p) { va += qa[p]; vb += qb[p]; }                   // fixed order
         va += b3a; vb += b3b;                                                        // Q1, Q2(s, a_new)
         // torch.min backward: the smaller one takes the gradient, a tie splits it
-        const float sel1 = (MODE == M_SAC) ? ((va < vb) ? 1.0f : ((va == vb) ? 0.5f : 0.0f)) : 1.0f;   // TD3: Q1 only
-        const float dq1 = -invB * sel1, dq2 = -invB * (1.0f - sel1);
+        const float sel1 = (MODE == M_SAC) ? min_backward(va, vb) : 1.0f;                  // TD3: Q1 only
+        const float sel2 = (MODE == M_SAC) ? min_backward(vb, va) : 0.0f;
+        const float dq1 = -invB * sel1, dq2 = -invB * sel2;
         qnew1 = va; qnew2 = vb;
         if (a < A && row0 + row < d.Bt) {
             float da1 = dap[0], da2 = dap[SP];
@@ -1265,7 +1289,7 @@ __device__ __forceinline__ void policy_bwd_block(const Dev &d, const StepArg &sa
             const int n = 64 * wave + 16 * t + c;
 #pragma unroll
             for (int i = 0; i < 4; ++i) {
-                gk2[t][i] = (h2v[t][i] > 0.f) ? acc[t][i] : 0.f;
+                gk2[t][i] = (h2v[t][i] <= 0.f) ? 0.f : acc[t][i];
                 X2[lds_off(4 * g + i, n, H)] = gk2[t][i];
             }
         }
@@ -1294,7 +1318,7 @@ __device__ __forceinline__ void policy_bwd_block(const Dev &d, const StepArg &sa
         for (int t = 0; t < NTW; ++t) {
             f32x4 gv;
 #pragma unroll
-            for (int i = 0; i < 4; ++i) gv[i] = (h1v[t][i] > 0.f) ? acc[t][i] : 0.f;
+            for (int i = 0; i < 4; ++i) gv[i] = (h1v[t][i] <= 0.f) ? 0.f : acc[t][i];
             st4(d.dPH1T + frag_off(n0 + 16 * t + c, row0 + 4 * g, B), gv);
         }
     }
@@ -1359,7 +1383,7 @@ __device__ __forceinline__ void td3_diagnostics(const Dev &d, const StepArg &sa,
     float mx[NS], mn[NS];
 #pragma unroll
     for (int q = 0; q < NS; ++q) { sm[q] = 0; sq[q] = 0; mx[q] = -INFINITY; mn[q] = INFINITY; }
-    auto acc1 = [&](int q, float v) { sm[q] += v; sq[q] += (double)v * v; mx[q] = fmaxf(mx[q], v); mn[q] = fminf(mn[q], v); };
+    auto acc1 = [&](int q, float v) { sm[q] += v; sq[q] += (double)v * v; mx[q] = max_nan(mx[q], v); mn[q] = min_nan(mn[q], v); };
     if (sa.pad & 1)
         for (int i = threadIdx.x; i < B; i += 256) {
             const float yv = d.y[i], q1 = d.q[i], q2 = d.q[Bs + i];
@@ -1380,7 +1404,7 @@ __device__ __forceinline__ void td3_diagnostics(const Dev &d, const StepArg &sa,
 #pragma unroll
         for (int q = 0; q < NS; ++q) {
             sm[q] += __shfl_xor(sm[q], o); sq[q] += __shfl_xor(sq[q], o);
-            mx[q] = fmaxf(mx[q], __shfl_xor(mx[q], o)); mn[q] = fminf(mn[q], __shfl_xor(mn[q], o));
+            mx[q] = max_nan(mx[q], __shfl_xor(mx[q], o)); mn[q] = min_nan(mn[q], __shfl_xor(mn[q], o));
         }
         lsum += __shfl_xor(lsum, o);
     }
@@ -1408,7 +1432,7 @@ __device__ __forceinline__ void td3_diagnostics(const Dev &d, const StepArg &sa,
             double s = 0, s2 = 0, MX = -INFINITY, MN = INFINITY;
             for (int w = 0; w < 4; ++w) {
                 s += sh[w * 32 + q]; s2 += sh[w * 32 + 6 + q];
-                MX = fmax(MX, sh[w * 32 + 12 + q]); MN = fmin(MN, sh[w * 32 + 18 + q]);
+                MX = max_nan(MX, sh[w * 32 + 12 + q]); MN = min_nan(MN, sh[w * 32 + 18 + q]);
             }
             const double cnt = (q < 5) ? (double)B : (double)B * d.A;
             const double mean = s / cnt;
@@ -1685,7 +1709,7 @@ __device__ __forceinline__ void dw_adam_body(const Dev &d, const DwTable &T, con
             const int i = i0 + threadIdx.x;
             {
                 const float e1 = q10 - yv0, e2 = q20 - yv0;
-                const float qn = fminf(qa0, qb0);
+                const float qn = min_nan(qa0, qb0);
                 // the row's <= 16 values of mu / log_std: sums in float (seven to sixteen terms per row)
                 float s_mu = 0.f, s_mu2 = 0.f, s_ls = 0.f, s_ls2 = 0.f, mx_mu = -INFINITY, mn_mu = INFINITY, mx_ls = -INFINITY, mn_ls = INFINITY;
 #pragma unroll
@@ -1694,8 +1718,8 @@ __device__ __forceinline__ void dw_adam_body(const Dev &d, const DwTable &T, con
                     for (int u = 0; u < 4; ++u)
                         if (4 * j + u < d.A) {
                             const float m_ = mu0[j][u], l_ = ls0[j][u];
-                            s_mu += m_; s_mu2 += m_ * m_; mx_mu = fmaxf(mx_mu, m_); mn_mu = fminf(mn_mu, m_);
-                            s_ls += l_; s_ls2 += l_ * l_; mx_ls = fmaxf(mx_ls, l_); mn_ls = fminf(mn_ls, l_);
+                            s_mu += m_; s_mu2 += m_ * m_; mx_mu = max_nan(mx_mu, m_); mn_mu = min_nan(mn_mu, m_);
+                            s_ls += l_; s_ls2 += l_ * l_; mx_ls = max_nan(mx_ls, l_); mn_ls = min_nan(mn_ls, l_);
                         }
                 const float vals[16] = {q10, q20, yv0, lp0, e1 * e1, e2 * e2, lp0 - qn, alpha * lp0 - qn,
                                         s_mu, s_mu2, mx_mu, mn_mu, s_ls, s_ls2, mx_ls, mn_ls};
@@ -1708,7 +1732,7 @@ __device__ __forceinline__ void dw_adam_body(const Dev &d, const DwTable &T, con
                 const float v = panel[qd * 256 + rr];
                 r_s += (double)v;
                 r_s2 += (double)v * (double)v;              // (used for quantities 0-3 only)
-                r_mx = fmaxf(r_mx, v); r_mn = fminf(r_mn, v);
+                r_mx = max_nan(r_mx, v); r_mn = min_nan(r_mn, v);
             }
             lds_barrier();                                    // panel free for the next pass
             if (i0 + 256 < Bt) {             // batches above 256 rows: the next pass's row
@@ -1722,7 +1746,7 @@ __device__ __forceinline__ void dw_adam_body(const Dev &d, const DwTable &T, con
 #pragma unroll
         for (int o = 8; o > 0; o >>= 1) {
             r_s += __shfl_xor(r_s, o); r_s2 += __shfl_xor(r_s2, o);
-            r_mx = fmaxf(r_mx, __shfl_xor(r_mx, o)); r_mn = fminf(r_mn, __shfl_xor(r_mn, o));
+            r_mx = max_nan(r_mx, __shfl_xor(r_mx, o)); r_mn = min_nan(r_mn, __shfl_xor(r_mn, o));
         }
 #ifdef SAC_STAMPS
         { float probe = (float)r_s; asm volatile("" ::"v"(probe)); STAMP(3, 4); }
@@ -3525,7 +3549,7 @@ int sac_policy_act(sac_trainer_t *t, const float *obs, int deterministic, const 
         else {
             ls = bs[a];
             for (int k = 0; k < H2; ++k) ls += Ws[(size_t)a * H2 + k] * h2[k];
-            ls = fminf(fmaxf(ls, LOG_SIG_MIN), LOG_SIG_MAX);
+            ls = clamp_nan(ls, LOG_SIG_MIN, LOG_SIG_MAX);
             act[a] = tanhf(m + expf(ls) * eps[a]);
         }
     }
