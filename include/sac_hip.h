@@ -515,6 +515,38 @@ int sac_evaluate_replay_many(sac_trainer_t *const *trainers, int n_trainers, con
 int sac_evaluate_replay_general_many(sac_trainer_t *const *trainers, int n_trainers, const int32_t *n_rows,
                                      const sac_eval_src_t *src, sac_eval_io_t *io, sac_eval_stats_t *stats /* may be NULL */);
 
+/* The TD3 objectives on HELD-OUT transitions, on the DEVICE from the live weights: the forward half of the TD3 step as an
+ * evaluation (k_eval_td3, csrc/td3_eval.h) -- n transitions (s, a, r, d, s') with their N(0,1) smoothing draw in one
+ * launch, three independent chains per 16-row block:
+ *   rows[TD3_EVAL_Q1 / Q2]      Q1 / Q2(s, a)
+ *   rows[TD3_EVAL_Q_PI]         Q1(s, a_pi), a_pi = tanh(last_fc(s)) of the policy (the policy loss is -mean of it)
+ *   rows[TD3_EVAL_TQ1 / TQ2]    target_qf1 / target_qf2(s', a_smooth), a_target = tanh(last_fc(s')) of the TARGET policy,
+ *                               a_smooth = a_target + clamp(eps * target_policy_noise, -noise_clip, +noise_clip): the
+ *                               step's expression, the sum is not clipped again; a NaN draw stays a NaN
+ *   rows[TD3_EVAL_Y]            reward_scale r + ((1 - d) discount) min(tq1, tq2), each operation rounded to float32 on
+ *                               its own, in this order (fminf for the minimum)
+ * target_policy_noise and noise_clip are the trainer's td3_config_t values.  The Q columns are bit for bit sac_q_values'
+ * on the same rows and a_pi bit for bit sac_policy_act_device's; row r of any call is bit for bit the one-row call.  The
+ * call drains the trainer as sac_sync does, reads the six nets where the step keeps them and writes nothing the step
+ * reads: parameters, optimizer state, scalars, the step's noise counter and the buffer generator stay untouched.  n is
+ * 1..1024.  TD3 trainers with the fused kernels' shapes; SAC trainers are refused (sac_evaluate is their entry) and so
+ * are general-step TD3 trainers (sac_get_params and a forward on the host is their path). */
+enum { TD3_EVAL_Q1, TD3_EVAL_Q2, TD3_EVAL_Q_PI, TD3_EVAL_TQ1, TD3_EVAL_TQ2, TD3_EVAL_Y, TD3_EVAL_ROWS_N };
+typedef struct {
+    const float *obs, *act, *rew, *term, *next_obs;   /* (n,O) (n,A) (n) (n) (n,O), host */
+    const float *eps;                                 /* (n,A) N(0,1): the smoothing draw, host */
+    float *rows;                                      /* (TD3_EVAL_ROWS_N, n) */
+    float *a_pi, *a_target, *a_smooth;                /* (n,A) each; any may be NULL */
+} td3_eval_io_t;
+int td3_evaluate(sac_trainer_t *t, int64_t n, td3_eval_io_t *io);                 /* n in 1..1024 */
+/* the same for 1..SAC_GROUP_MAX (16) TD3 trainers of one device in ONE launch, io[i] for trainer i; n_rows[i] == 0: member
+ * i sits out (its io is not looked at).  Dims, hidden sizes and row counts may be mixed; each member's columns are bit
+ * for bit its own td3_evaluate's.  Refused (<0, sac_last_error, nothing changed, no output written): null or duplicate
+ * trainers, more than 16, trainers on different devices, SAC trainers, general-step trainers, members confined by
+ * sac_trainer_set_xcd[_mask], n_rows outside 0..1024 or all zero, and for a member with rows a null input array or null
+ * rows. */
+int td3_evaluate_many(sac_trainer_t *const *trainers, int n_trainers, const int32_t *n_rows, td3_eval_io_t *io);
+
 /* PER-UNIT statistics of the hidden layers, on the device from the live weights: how much of each network is alive
  * (dormant units, Sokar et al. 2023; dead units; the feature norm).  For n (obs, act) rows, each selected net and each of
  * its hidden layers l of N_l true units, the post-ReLU activations h[r][u] (float32, as the inference kernels produce

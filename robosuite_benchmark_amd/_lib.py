@@ -79,6 +79,17 @@ class SacEvalIO(C.Structure):
                                           "mu", "log_std", "a_new", "a_next")] + [("alpha", C.c_float)]
 
 
+# the per-row columns of td3_evaluate (TD3_EVAL_*: the rows of td3_eval_io_t.rows, in this order) and its (n, A) outputs
+TD3_EVAL_ROWS = ["q1", "q2", "q_pi", "tq1", "tq2", "y"]
+TD3_EVAL_ARRAYS = ["a_pi", "a_target", "a_smooth"]
+
+
+class Td3EvalIO(C.Structure):
+    """td3_eval_io_t"""
+    _fields_ = [(k, C.c_void_p) for k in ("obs", "act", "rew", "term", "next_obs", "eps", "rows",
+                                          "a_pi", "a_target", "a_smooth")]
+
+
 # the moment records of sac_evaluate_stats_many (SAC_EVAL_M_*: sac_eval_stats_t.m, in this order)
 EVAL_MOMENTS = ["q1", "q2", "y", "log_pi", "mu", "log_std", "td1", "td2", "policy"]
 EVAL_MOMENT_FIELDS = ["count", "sum", "m2", "sumsq", "max", "min"]
@@ -200,6 +211,8 @@ SYMBOLS = {
     "sac_evaluate_general_stats_many": (C.c_int, [_P, C.c_int, _P, _P, _P]),
     "sac_evaluate_replay_many": (C.c_int, [_P, C.c_int, _P, _P, _P, _P]),
     "sac_evaluate_replay_general_many": (C.c_int, [_P, C.c_int, _P, _P, _P, _P]),
+    "td3_evaluate": (C.c_int, [_P, C.c_int64, _P]),
+    "td3_evaluate_many": (C.c_int, [_P, C.c_int, _P, _P]),
     "sac_unit_moments": (C.c_int, [_P, C.c_int64, _P]),
     "sac_unit_moments_many": (C.c_int, [_P, C.c_int, _P, _P]),
     "sac_unit_moments_general": (C.c_int, [_P, C.c_int64, _P]),

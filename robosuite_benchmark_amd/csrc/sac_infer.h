@@ -1,7 +1,7 @@
 // The forward pass of the device inference kernels, once (included by sac_trainer.hip in front of sac_act.h).
 //
-// Eight kernels run a network forward on live weights without training: k_act, k_act_session, k_qval, k_eval (the fused
-// kernels' shapes: one workgroup carries a 16-row block through a whole net in LDS) and k_act_layer,
+// Nine kernels run a network forward on live weights without training: k_act, k_act_session, k_qval, k_eval, k_eval_td3
+// (the fused kernels' shapes: one workgroup carries a 16-row block through a whole net in LDS) and k_act_layer,
 // k_act_layer_session<F64>, k_qval_layer, k_eval_layer<SPLIT> (general shapes: one launch per layer, one workgroup per
 // 16 x 64 output tile).
 // Each of them is a prologue that finds its member or job, calls into the pieces below, and an epilogue of its own.
@@ -372,6 +372,7 @@ struct InferEntry {
     const char *instead;     // the shape refusal's advice
     const char *rows_to;     // no trainer has rows to ...
     bool both = false;       // serves both families (no forward pass: sac_params.h); `general` and `instead` are unused
+    bool td3_only = false;   // refuses SAC trainers (td3_eval.h)
 };
 
 // trainer i of a list: not null, not listed twice, on trainer 0's device, of the algorithm and shapes the entry serves
@@ -383,6 +384,8 @@ int infer_admit_trainer(const InferEntry &E, sac_trainer_t *const *trainers, int
                 trainers[0]->device);
     SAC_REQUIRE(!E.sac_only || t->algo == 0, "trainer %d is a TD3 trainer: this entry evaluates the SAC objective "
                 "(entropy-regularised targets of a tanh-Gaussian policy)", i);
+    SAC_REQUIRE(!E.td3_only || t->algo == 1, "trainer %d is a SAC trainer: this entry evaluates the TD3 objective (a "
+                "deterministic policy with target smoothing); sac_evaluate is the entry for the SAC objective", i);
     if (E.both) return 0;
     if (E.general)
         SAC_REQUIRE(t->gen, "trainer %d has the fused kernels' shapes (two hidden layers of at most 256 units): %s", i, E.instead);

@@ -26,8 +26,10 @@ from .replay_buffer import EnvReplayBuffer
 from .group import (ArchSACTrainerGroup, ArchTD3TrainerGroup, GroupActor, MixedSACTrainerGroup, MixedTD3TrainerGroup,
                     MlpSACTrainerGroup, MlpTD3TrainerGroup, SACTrainerGroup, TD3TrainerGroup, act_many,
                     evaluate_many, evaluate_replay_many, q_values_many, runs_general_step, param_moments_many, param_statistics,
+                    td3_evaluate_many,
                     unit_moments_many, unit_statistics)
 from .infer import check_general, check_stats, param_target
+from .infer import td3_eval_statistics
 from .sac import SACTrainer, eval_statistics
 from .td3 import TD3Trainer
 from .variant import env_dims, validate
@@ -358,6 +360,25 @@ def _validation_eps(seed, epoch, batch, A):
     return rs.standard_normal((n, A)), rs.standard_normal((n, A))
 
 
+def _td3_validation_eps(seed, epoch, batch, A):
+    """The smoothing draw of a TD3 run's validation in `epoch`: the first draw of _validation_eps' generator, a function
+    of (seed, epoch) alone."""
+    if batch is None:
+        return None
+    rs = np.random.RandomState([int(seed) & 0xFFFFFFFF, int(epoch), VALIDATION_STREAM])
+    return rs.standard_normal((batch["observations"].shape[0], A))
+
+
+def _td3_validation_columns(stats, batch):
+    """The validation block of a TD3 run's row: validation/<key> for every key of td3_eval_statistics and
+    validation/Num Transitions.  stats None (no evaluation path this epoch): the columns stay, empty."""
+    if stats is None:
+        stats = OrderedDict((k, float("nan")) for k in td3_eval_statistics(np.zeros((6, 1)), np.zeros((1, 1))))
+    d = OrderedDict(("validation/" + k, v) for k, v in stats.items())
+    d["validation/Num Transitions"] = 0 if batch is None else int(batch["observations"].shape[0])
+    return d
+
+
 def _objective_columns(prefix, stats, n):
     """<prefix><key> for every key of SACTrainer.evaluate, and <prefix>Num Transitions = n.  stats None (nothing to evaluate
     this epoch: no evaluation path, an empty buffer): the columns stay, empty."""
@@ -467,7 +488,15 @@ class EvalOptions(NamedTuple):
     no generator, nothing to checkpoint), at the point of the epoch where validation is taken, and param_statistics'
     columns params/<Net> Weight Norm / Weight Abs Max / Adam M Norm / Adam V Mean / Adam V Max / Target Gap and
     params/Non Finite behind the units/ block.  The group entries make ONE param_moments_many call per epoch.  SAC and TD3
-    variants are served (a TD3 policy has a Target Gap too)."""
+    variants are served (a TD3 policy has a Target Gap too).
+
+    td3_validation=True: validation for TD3 runs -- the TD3 objectives (a deterministic policy, target smoothing, no
+    entropy term) on the transitions of the epoch's evaluation paths by evaluate_td3 (on the device from the live
+    weights: td3_evaluate, k_eval_td3; a run of the general step on the host), with the smoothing draw
+    RandomState([seed, epoch, 0x56414C]).standard_normal((n, A)): nothing to checkpoint, and a resumed run logs the same
+    rows.  The row gains validation/<key> for every key of td3_eval_statistics and validation/Num Transitions where the
+    SAC validation block sits; the group entries make ONE td3_evaluate_many call per epoch.  Every run must be a TD3
+    variant: a SAC variant is refused (validation=True is its option)."""
     q_diagnostics: bool = False
     q_general: str = "host"
     validation: bool = False
@@ -477,6 +506,7 @@ class EvalOptions(NamedTuple):
     unit_diagnostics: bool = False
     unit_general: str = "host"
     param_diagnostics: bool = False
+    td3_validation: bool = False
 
 
 def _refuse_td3(variant, what, call, reason):
@@ -485,7 +515,7 @@ def _refuse_td3(variant, what, call, reason):
 
 
 def _options(what, specs, acting, q_diagnostics, q_general, validation, eval_general, eval_stats, replay_eval,
-             unit_diagnostics=False, unit_general="host", param_diagnostics=False):
+             unit_diagnostics=False, unit_general="host", param_diagnostics=False, td3_validation=False):
     """The EvalOptions of entry `what`, after the value checks of its keywords (acting's too) and, for the variant at
     the head of every run spec in `specs`, the TD3 refusals: all of it in front of anything that builds a run."""
     check_stats(eval_stats)
@@ -494,12 +524,16 @@ def _options(what, specs, acting, q_diagnostics, q_general, validation, eval_gen
     check_general(eval_general)
     check_general(unit_general)
     opts = EvalOptions(q_diagnostics, q_general, validation, eval_general, eval_stats, check_replay_eval(replay_eval),
-                       bool(unit_diagnostics), unit_general, bool(param_diagnostics))
+                       bool(unit_diagnostics), unit_general, bool(param_diagnostics), bool(td3_validation))
     for spec in specs if opts.validation else ():
         _refuse_td3(tuple(spec)[0], what, "validation=True", "validation evaluates the SAC objective (SACTrainer.evaluate)")
     for spec in specs if opts.replay_eval else ():
         _refuse_td3(tuple(spec)[0], what, "replay_eval=N",
                     "the replay evaluation computes the SAC objective (SACTrainer.evaluate_replay)")
+    for spec in specs if opts.td3_validation else ():
+        if tuple(spec)[0].get("algorithm", "SAC") != "TD3":
+            raise RuntimeError(f"{what}(td3_validation=True): td3_validation evaluates the TD3 objective "
+                               "(TD3Trainer.evaluate_td3); a SAC variant takes validation=True")
     return opts
 
 
@@ -547,6 +581,13 @@ def _epoch_evaluations(runs, epoch, opts, take=ALL_BLOCKS, many=True):
                [None if b is None else t.evaluate(b, eps=e, **gen, **stats_kw) for t, b, e in zip(trainers, batches, eps)])
         for c, s, b in zip(cols, got, batches):
             c["validation"] = _validation_columns(s, b)
+    if opts.td3_validation and "validation" in take:
+        batches = [_validation_batch(p, t.obs_dim, t.act_dim) for p, t in zip(paths, trainers)]
+        eps = [_td3_validation_eps(r["seed"], epoch, b, t.act_dim) for r, b, t in zip(runs, batches, trainers)]
+        got = (td3_evaluate_many(trainers, batches, eps=eps) if many else
+               [None if b is None else t.evaluate_td3(b, eps=e) for t, b, e in zip(trainers, batches, eps)])
+        for c, s, b in zip(cols, got, batches):
+            c["validation"] = _td3_validation_columns(s, b)
     if opts.replay_eval and "replay" in take:
         bufs, ns = [r["buf"] for r in runs], [_replay_rows(opts.replay_eval, r["buf"]) for r in runs]
         got = [None] * len(runs)
@@ -688,7 +729,7 @@ def _prefill(r):
 def experiment(variant, log_dir=None, seed=1, obs_dim=None, action_dim=None, num_epochs=None, device=0,
                fused_loop=True, quiet=False, checkpoint_dir=None, resume=False, acting="host", q_diagnostics=False,
                q_general="host", validation=False, eval_general="host", eval_stats="host", replay_eval=0,
-               unit_diagnostics=False, unit_general="host", param_diagnostics=False):
+               unit_diagnostics=False, unit_general="host", param_diagnostics=False, td3_validation=False):
     """variant.json -> training run.  Returns the list of progress rows (also written to
     <log_dir>/progress.csv when log_dir is given).
 
@@ -705,10 +746,10 @@ def experiment(variant, log_dir=None, seed=1, obs_dim=None, action_dim=None, num
     same amounts, whichever value is given.
 
     q_diagnostics, q_general, validation, eval_general, eval_stats, replay_eval, unit_diagnostics, unit_general,
-    param_diagnostics: the
+    param_diagnostics, td3_validation: the
     per-epoch evaluations, EvalOptions; here from the trainer's own q_values, evaluate, evaluate_replay and unit_moments."""
     opts = _options("experiment", [(variant,)], acting, q_diagnostics, q_general, validation, eval_general, eval_stats,
-                    replay_eval, unit_diagnostics, unit_general, param_diagnostics)
+                    replay_eval, unit_diagnostics, unit_general, param_diagnostics, td3_validation)
     validate(variant)
     # This driver's runs are a function of `seed` alone: initial weights come from np.random (seeded here), every noise
     # stream from `seed` -- whether or not torch happens to be loaded in the process (the reference's own scripts seed
@@ -874,7 +915,7 @@ def experiment_group(variant, seeds, log_dir=None, num_epochs=None, obs_dim=None
                      quiet=False, checkpoint_dir=None, resume=False, chunk_rows=DEFAULT_CHUNK_ROWS, acting="host", sessions=True,
                      general_sessions=None, q_diagnostics=False, q_general="host", validation=False,
                      eval_general="host", eval_stats="host", replay_eval=0, unit_diagnostics=False, unit_general="host",
-                     param_diagnostics=False):
+                     param_diagnostics=False, td3_validation=False):
     """One configuration, several seeds, one process: each seed is the run ``experiment(variant, seed=s)`` would make --
     its own synthetic environments, collectors, weights and replay buffer -- and every epoch's training block is ONE
     SACTrainerGroup.train_loop (TD3 variants: TD3TrainerGroup; hidden sizes other than two layers of at most 256 units:
@@ -896,10 +937,10 @@ def experiment_group(variant, seeds, log_dir=None, num_epochs=None, obs_dim=None
     device too (one sac_policy_act_general_many call per tick and 16 of them; with sessions and general_sessions=True one
     sac_gactor_act call, None: GroupActor's default); rows as experiment(..., acting="device_all").
     q_diagnostics, q_general, validation, eval_general, eval_stats, replay_eval, unit_diagnostics, unit_general,
-    param_diagnostics: the
+    param_diagnostics, td3_validation: the
     per-epoch evaluations, EvalOptions; each seed's rows are those of experiment(variant, seed=s) with the same options."""
     opts = _options("experiment_group", [(variant,)], acting, q_diagnostics, q_general, validation, eval_general,
-                    eval_stats, replay_eval, unit_diagnostics, unit_general, param_diagnostics)
+                    eval_stats, replay_eval, unit_diagnostics, unit_general, param_diagnostics, td3_validation)
     if resume and not checkpoint_dir:
         raise RuntimeError("experiment_group(resume=True) needs the checkpoint_dir to resume from")
     validate(variant)
@@ -954,7 +995,7 @@ def experiment_sweep(runs, log_dir=None, num_epochs=None, device=0, quiet=False,
                      chunk_rows=DEFAULT_CHUNK_ROWS, hidden_sweep=False, acting="host", sessions=True, general_sessions=None,
                      q_diagnostics=False, q_general="host", validation=False,
                      eval_general="host", eval_stats="host", replay_eval=0, unit_diagnostics=False, unit_general="host",
-                     param_diagnostics=False):
+                     param_diagnostics=False, td3_validation=False):
     """Several tasks x seeds, one process, one device: every entry of ``runs`` -- (variant, seed), or (variant, seed,
     obs_dim, action_dim) for a task without pinned dims -- is the run ``experiment(variant, seed=seed)`` would make, and
     every epoch's training block is ONE MixedSACTrainerGroup.train_loop (TD3 variants: MixedTD3TrainerGroup; hidden sizes
@@ -973,12 +1014,12 @@ def experiment_sweep(runs, log_dir=None, num_epochs=None, device=0, quiet=False,
     "device_all" those runs act on the device inside the same ticks, and each run's rows are those of its solo
     experiment(..., acting="device_all").
     q_diagnostics, q_general, validation, eval_general, eval_stats, replay_eval, unit_diagnostics, unit_general,
-    param_diagnostics: the
+    param_diagnostics, td3_validation: the
     per-epoch evaluations, EvalOptions, as for experiment_group; in a hidden sweep the runs of the general step take the
     host path inside the same call, or
     the device's under q_general / eval_general "device".  A sweep with a TD3 run refuses validation and replay_eval."""
     opts = _options("experiment_sweep", runs, acting, q_diagnostics, q_general, validation, eval_general, eval_stats,
-                    replay_eval, unit_diagnostics, unit_general, param_diagnostics)
+                    replay_eval, unit_diagnostics, unit_general, param_diagnostics, td3_validation)
     if resume and not checkpoint_dir:
         raise RuntimeError("experiment_sweep(resume=True) needs the checkpoint_dir to resume from")
     specs = []

@@ -85,7 +85,8 @@ def route(t, general, on_host=False):
     """Where one member's request runs: HOST (its own host forward), FUSED or GENERAL_STEP (the key of the request's
     *_ENTRIES).  No handle: the host.  The fused kernels' shapes: the fused entry under either `general`.  The general
     step: the host, or the general entry under general="device".  on_host (evaluation: _evaluate_on_host) sends a member
-    with a handle to the host too; a TD3 member's evaluation never gets here (its own evaluate refuses)."""
+    with a handle to the host too; a TD3 member's evaluate never gets here (its own evaluate refuses), its evaluate_td3
+    does, under general="host": td3_evaluate_many is the fused entry and there is no general one."""
     if t._h is None or on_host:
         return HOST
     if not runs_general_step(t):
@@ -837,6 +838,135 @@ def evaluate_replay_many(trainers, buffers, n=None, indices=None, eps=None, rngs
             t.evaluate_replay(b, n=counts[i], indices=indices[i])     # (TD3Trainer.evaluate_replay refuses: the SAC objective)
         requests[i] = t._replay_request(b, counts[i], indices[i], eps[i], rngs[i])
     return evaluate_replay_of(trainers, buffers, requests, rows, general, stats)
+
+
+# ---- evaluation of the TD3 objectives -----------------------------------------------------------------------------------
+def td3_eval_target(rew, term, tq1, tq2, reward_scale, discount):
+    """k_eval_td3's y in float32 NumPy, operation for operation:
+    y = rs * r + ((1 - d) * discount) * min(tq1, tq2), each result rounded to float32 (np.fmin, as fminf)."""
+    f = np.float32
+    rew, term, tq1, tq2 = (np.asarray(x, f) for x in (rew, term, tq1, tq2))
+    return f(reward_scale) * rew + ((f(1.0) - term) * f(discount)) * np.fmin(tq1, tq2)
+
+
+def td3_smooth(a_target, eps, sigma, clip):
+    """The smoothed target action of the TD3 step in float32 NumPy: a_target + clip(eps * sigma, -clip, clip).  The sum is
+    not clipped again; a NaN draw stays a NaN."""
+    f = np.float32
+    a_target, eps = np.asarray(a_target, f), np.asarray(eps, f)
+    return a_target + np.clip(eps * f(sigma), -f(clip), f(clip))
+
+
+def td3_eval_statistics(rows, a_pi):
+    """The statistics of TD3Trainer.evaluate_td3 from its per-row columns, on the host in float64: `rows` is the
+    (TD3_EVAL_ROWS_N, n) array q1, q2, q_pi, tq1, tq2, y (_lib.TD3_EVAL_ROWS), a_pi the policy's (n, A) actions.  An
+    OrderedDict with TD3Trainer.get_diagnostics()' keys in their order -- QF Loss = mean((q - y)^2); Policy Loss =
+    -mean(q_pi); Mean / Std (np.std) / Max / Min of q1, q2, y, the Bellman errors (q - y)^2 and a_pi -- followed by
+    TD Error 1 / TD Error 2 Mean / Std / Max / Min (q - y, signed)."""
+    q1, q2, q_pi, _, _, y = [np.asarray(x, np.float64).ravel() for x in rows]
+
+    def stats(d, name, x):
+        x = np.asarray(x, np.float64).ravel()
+        d[name + " Mean"], d[name + " Std"] = float(np.mean(x)), float(np.std(x))
+        d[name + " Max"], d[name + " Min"] = float(np.max(x)), float(np.min(x))
+
+    d = OrderedDict()
+    with np.errstate(all="ignore"):
+        b1, b2 = (q1 - y) ** 2, (q2 - y) ** 2
+        d["QF1 Loss"] = float(np.mean(b1))
+        d["QF2 Loss"] = float(np.mean(b2))
+        d["Policy Loss"] = float(-np.mean(q_pi))
+        stats(d, "Q1 Predictions", q1)
+        stats(d, "Q2 Predictions", q2)
+        stats(d, "Q Targets", y)
+        stats(d, "Bellman Errors 1", b1)
+        stats(d, "Bellman Errors 2", b2)
+        stats(d, "Policy Action", a_pi)
+        stats(d, "TD Error 1", q1 - y)
+        stats(d, "TD Error 2", q2 - y)
+    return d
+
+
+def _td3_eval_columns(chunks):
+    """The per-row columns of evaluate_td3 from its chunks' outputs (rows (6, k), a_pi, a_target, a_smooth (k, A))."""
+    cols = OrderedDict()
+    rows = np.concatenate([c["rows"] for c in chunks], axis=1)
+    for i, name in enumerate(_lib.TD3_EVAL_ROWS):
+        cols[name] = np.ascontiguousarray(rows[i])
+    for name in _lib.TD3_EVAL_ARRAYS:
+        cols[name] = np.concatenate([c[name] for c in chunks], axis=0)
+    return cols
+
+
+def _td3_eval_result(cols, rows):
+    result = td3_eval_statistics(np.stack([cols[k] for k in _lib.TD3_EVAL_ROWS]), cols["a_pi"])
+    return (result, cols) if rows else result
+
+
+def td3_evaluate_of(trainers, inputs, rows):
+    """evaluate_td3 / td3_evaluate_many behind their argument checks: inputs[i] = the member's arrays as
+    TD3Trainer._td3_eval_inputs checked them, or None for a member that sits out (its result: None).  The host members
+    first, in member order; then the members with the fused kernels' shapes in windows (td3_evaluate_many: 16 members
+    and 1024 rows per call)."""
+    R = len(trainers)
+    out, n_rows, served = [None] * R, [0] * R, []
+    for i, (t, arrs) in enumerate(zip(trainers, inputs)):
+        if arrs is None:
+            continue
+        if route(t, "host", t._evaluate_on_host) == HOST:
+            out[i] = _td3_eval_result(t._evaluate_td3_host(arrs), rows)
+        else:
+            n_rows[i] = arrs[0].shape[0]
+            served.append(i)
+    if not served:
+        return out
+    lib = _lib.load()
+    chunks = {i: [] for i in served}
+    for r0, ids, counts in windows(served, n_rows):
+        parts, outs = [], []
+        for i, k in zip(ids, counts):
+            parts.append([np.ascontiguousarray(a[r0:r0 + k]) for a in inputs[i]])
+            o = dict(rows=np.empty((len(_lib.TD3_EVAL_ROWS), k), np.float32))
+            o.update((name, np.empty((k, trainers[i].act_dim), np.float32)) for name in _lib.TD3_EVAL_ARRAYS)
+            outs.append(o)
+        ios = (_lib.Td3EvalIO * len(ids))(*[
+            _lib.Td3EvalIO(*[a.ctypes.data for a in p], o["rows"].ctypes.data,
+                           *[o[name].ctypes.data for name in _lib.TD3_EVAL_ARRAYS]) for p, o in zip(parts, outs)])
+        _lib.check(lib.td3_evaluate_many(_handles(trainers, ids), len(ids), _ints(counts), ios), "td3_evaluate_many")
+        for i, o in zip(ids, outs):
+            chunks[i].append(o)
+    for i in served:
+        trainers[i]._settled()
+        out[i] = _td3_eval_result(_td3_eval_columns(chunks[i]), rows)
+    return out
+
+
+def td3_evaluate_many(trainers, batches, eps=None, rngs=None, rows=False):
+    """TD3Trainer.evaluate_td3 for many runs at once: result[i] = trainers[i].evaluate_td3(batches[i], eps[i], rngs[i])
+    (eps / rngs: one entry per trainer or None; batches[i] None or without rows: the member sits out and gets None).  The
+    TD3 members with the fused kernels' shapes are served by ONE launch per 16 of them and 1024 rows (td3_evaluate_many:
+    dims, hidden sizes and row counts mixed); the others -- the general step, trainers without a handle -- take their
+    host path inside the same call.  A member's columns never depend on its neighbours: they are bit for bit those of
+    its own evaluate_td3.  Results come back in member order; rows=True as for evaluate_td3.  A SAC member raises
+    (evaluate_many is the call for the SAC objective)."""
+    trainers = list(trainers)
+    R = len(trainers)
+    eps = [None] * R if eps is None else list(eps)
+    rngs = [None] * R if rngs is None else list(rngs)
+    if not (len(batches) == len(eps) == len(rngs) == R):
+        raise RuntimeError("td3_evaluate_many takes one batch (and eps, and rng) per trainer")
+    if len({id(t) for t in trainers}) != R:
+        raise RuntimeError("a trainer appears twice in td3_evaluate_many")
+    for i, t in enumerate(trainers):
+        if not _is_td3(t):
+            raise RuntimeError(f"td3_evaluate_many member {i} is a SAC trainer: this call evaluates the TD3 objective (a "
+                               "deterministic policy with target smoothing); evaluate_many evaluates the SAC objective")
+    inputs = [None] * R
+    for i, (t, b) in enumerate(zip(trainers, batches)):
+        if b is None or np.atleast_2d(b["observations"]).shape[0] == 0:
+            continue
+        inputs[i] = t._td3_eval_inputs(b, eps[i], rngs[i])
+    return td3_evaluate_of(trainers, inputs, rows)
 
 
 # ---- acting sessions ----------------------------------------------------------------------------------------------------

@@ -10,9 +10,9 @@ from collections import OrderedDict
 
 import numpy as np
 
-from . import _lib
+from . import _lib, infer
 from ._lib import TD3_DIAG_NAMES, TD3_NET_IDS, Td3Config
-from .sac import SACTrainer
+from .sac import SACTrainer, _hidden_layers, _q_forward
 
 
 class TD3Trainer(SACTrainer):
@@ -74,6 +74,81 @@ class TD3Trainer(SACTrainer):
         raise NotImplementedError("TD3Trainer.evaluate_replay: evaluate computes the SAC objective (entropy-regularised "
                                   "targets of a tanh-Gaussian policy); TD3's objective -- a deterministic policy with "
                                   "target smoothing -- is not implemented")
+
+    # ---- the TD3 objectives on held-out transitions ------------------------------------------
+    def _td3_eval_inputs(self, batch, eps, rng):
+        """evaluate_td3's arguments, checked before any library call: float32 obs, act, rew, term, next_obs, eps."""
+        obs = _lib.f32(np.atleast_2d(batch["observations"]))
+        n = obs.shape[0]
+        act, nobs = _lib.f32(np.atleast_2d(batch["actions"])), _lib.f32(np.atleast_2d(batch["next_observations"]))
+        if n < 1 or obs.shape != (n, self.obs_dim) or nobs.shape != obs.shape or act.shape != (n, self.act_dim):
+            raise ValueError(f"evaluate_td3: observations {obs.shape} / actions {act.shape} / next_observations "
+                             f"{nobs.shape} do not fit dims ({self.obs_dim}, {self.act_dim}) (at least one row)")
+        rew, term = (_lib.f32(np.asarray(batch[k]).reshape(-1)) for k in ("rewards", "terminals"))
+        if rew.shape != (n,) or term.shape != (n,):
+            raise ValueError(f"evaluate_td3: {rew.size} rewards and {term.size} terminals for {n} rows")
+        if eps is None:
+            eps = self._eval_stream(rng).standard_normal((n, self.act_dim))
+        eps = _lib.f32(np.atleast_2d(eps))
+        if eps.shape != act.shape:
+            raise ValueError(f"evaluate_td3: eps {eps.shape} for actions {act.shape}")
+        return obs, act, rew, term, nobs, eps
+
+    def _host_net(self, name):
+        """[(W, b)] of one net from the current weights; the two policies are TanhMlpPolicy: one head of act_dim units."""
+        if name not in ("policy", "target_policy"):
+            return super()._host_net(name)
+        flat = self._get_params(name) if self._h is not None else _lib.f32(getattr(self, name).flat())
+        layers, off, k = [], 0, self.obs_dim
+        for n_out in self._hidden(name) + [self.act_dim]:
+            layers.append((flat[off:off + n_out * k].reshape(n_out, k), flat[off + n_out * k:off + n_out * k + n_out]))
+            off, k = off + n_out * k + n_out, n_out
+        assert off == flat.size
+        return layers
+
+    def _evaluate_td3_host(self, arrs):
+        """The host path of evaluate_td3: the nets' current weights (sac_sync, sac_get_params; the holders' own arrays
+        while the trainer has no handle yet), a float32 NumPy forward and the device path's smoothing and y expressions."""
+        obs, act, rew, term, nobs, eps = arrs
+        if self._h is not None:
+            _lib.check(self._lib.sac_sync(self._h), "sac_sync")
+            self._settled()
+        nets = {name: self._host_net(name) for name in self.NETS}
+
+        def q(name, s, a):
+            return _q_forward(nets[name], np.concatenate([s, a], axis=1))
+
+        def pi(name, s):
+            layers = nets[name]
+            return np.tanh(_hidden_layers(s, layers[:-1]) @ layers[-1][0].T + layers[-1][1])
+
+        with np.errstate(all="ignore"):
+            a_pi, a_target = pi("policy", obs), pi("target_policy", nobs)
+            a_smooth = infer.td3_smooth(a_target, eps, self.target_policy_noise, self.target_policy_noise_clip)
+            tq1, tq2 = q("target_qf1", nobs, a_smooth), q("target_qf2", nobs, a_smooth)
+            cols = dict(q1=q("qf1", obs, act), q2=q("qf2", obs, act), q_pi=q("qf1", obs, a_pi), tq1=tq1, tq2=tq2,
+                        y=infer.td3_eval_target(rew, term, tq1, tq2, self.reward_scale, self.discount))
+        out = dict(rows=np.stack([_lib.f32(cols[k]) for k in _lib.TD3_EVAL_ROWS]), a_pi=_lib.f32(a_pi),
+                   a_target=_lib.f32(a_target), a_smooth=_lib.f32(a_smooth))
+        return infer._td3_eval_columns([out])
+
+    def evaluate_td3(self, batch, eps=None, rng=None, rows=False):
+        """The TD3 objectives of this run on `batch` WITHOUT a gradient step: `batch` is the dict train() takes
+        (observations, actions, rewards, terminals, next_observations; any n >= 1), typically transitions the run has not
+        trained on -- an epoch's evaluation paths.  From the LIVE weights: on the device (td3_evaluate: k_eval_td3, one
+        launch per 1024 rows, no parameter copy); a trainer of the general step, which the library's entry refuses, and a
+        trainer without a handle take the host path -- sac_sync, sac_get_params, a float32 NumPy forward.  Nothing the
+        step reads is written either way, and the trainer's own statistics (get_diagnostics, the step counters) are left
+        alone.
+        eps: the (n, A) N(0,1) draw of the target smoothing; None: drawn as standard_normal((n, A)) from `rng`, or from a
+        RandomState private to the trainer (seeded from noise_seed) when that is None too -- np.random is never touched.
+        Returns an OrderedDict with get_diagnostics()' keys plus TD Error 1 / TD Error 2 Mean / Std / Max / Min (q - y,
+        signed): infer.td3_eval_statistics of the per-row columns.  rows=True: (stats, columns), columns a dict of the
+        float32 per-row arrays q1, q2, q_pi, tq1, tq2, y (n,) and a_pi, a_target, a_smooth (n, A):
+        q_pi = Q1(s, a_pi), a_pi the policy's action on s; a_target the TARGET policy's action on s',
+        a_smooth = a_target + clip(eps * target_policy_noise, +-target_policy_noise_clip), the targets tq1 / tq2 on
+        (s', a_smooth), y = reward_scale r + (1 - d) discount min(tq1, tq2)."""
+        return infer.td3_evaluate_of([self], [self._td3_eval_inputs(batch, eps, rng)], rows)[0]
 
     def get_snapshot(self):
         snap = super().get_snapshot()

@@ -23,7 +23,9 @@
  device: replay/ columns in progress.csv, the training-data figures next to the validation/ ones; SAC only.
  --unit_diagnostics: every epoch, the dormant, dead and active fractions and the feature norm of policy, qf1 and qf2 on
  the evaluation paths, from per-unit reductions of the hidden layers: twelve units/ columns; SAC and TD3.
- --unit_general device: with --unit_diagnostics, runs of any hidden sizes reduce them on the device.)
+ --unit_general device: with --unit_diagnostics, runs of any hidden sizes reduce them on the device.
+ --td3_validation: --validation for TD3 runs: every epoch, the TD3 losses, TD errors and targets on the evaluation
+ paths' transitions from the live weights: validation/ columns in progress.csv; TD3 only.)
 Runs the variant unchanged (batch size, lrs, tau, period, buffer size ... from the JSON) on the
 HIP library with a synthetic environment of the task's dimensions (robosuite is not installed)."""
 import argparse
@@ -111,6 +113,11 @@ def build_parser():
                          "device where they live (one HIP launch, no parameter copy) and log params/<Net> Weight Norm, "
                          "Weight Abs Max, Adam M Norm, Adam V Mean, Adam V Max, Target Gap and params/Non Finite; SAC and "
                          "TD3; off: progress.csv is unchanged")
+    ap.add_argument("--td3_validation", action="store_true",
+                    help="every epoch, evaluate the TD3 objectives (QF losses, TD errors, Q targets with target smoothing, "
+                         "policy loss) on the transitions of the evaluation paths, which never enter the replay buffer (a "
+                         "HIP kernel on the live weights), and log them as validation/<key>; TD3 only (SAC runs take "
+                         "--validation); off: progress.csv is unchanged")
     return ap
 
 
@@ -130,6 +137,8 @@ if __name__ == "__main__":
         option_kw["unit_general"] = args.unit_general
     if args.param_diagnostics:
         option_kw["param_diagnostics"] = True
+    if args.td3_validation:
+        option_kw["td3_validation"] = True
     if (args.hidden_sweep or args.hidden_sizes) and not args.variants:
         raise SystemExit("--hidden_sweep / --hidden_sizes need --variants")
     if args.variants or args.seeds:
