@@ -1,16 +1,38 @@
-// Evaluating the SAC objectives on the device: the forward half of the step on rows the run has not trained on (included
-// by sac_trainer.hip).
+// Evaluating an objective on the device: the forward half of the step on rows the run has not trained on (included by
+// sac_trainer.hip).  Here: the row-block frame and the host staging of every such evaluation, once, and the SAC
+// objective; td3_eval.h holds the TD3 objective.
 //
-// k_eval computes, for 1..1024 transitions (s, a, r, d, s') with their N(0,1) draws eps / eps_next, of each of
-// 1..SAC_GROUP_MAX SAC trainers in ONE launch and from the live weights,
+// eval_frame<Objective> computes, for 1..1024 transitions (s, a, r, d, s') of each of 1..SAC_GROUP_MAX trainers in ONE
+// launch and from the live weights, three chains per 16-row block:
+//   chain Q   [s | a] -> qf1 -> qf2                                               rows 0, 1 of `rows`: q1, q2
+//   chain P   s  -> Objective::policy -> Objective::head -> action; [s  | action] -> qf1 (-> qf2: Objective::critics)
+//   chain N   s' -> Objective::policy -> Objective::head -> action; [s' | action] -> target_qf1 -> target_qf2
+//             behind either, Objective::rows: the chain's columns of `rows`
+// An objective is a struct of static __device__ functions that supplies these four and nothing else; head is what stands
+// between infer_head and the write of the action chunk: the action that goes into the Q nets' input, the objective's own
+// (n, A) outputs, and one per-row value handed to rows.
 //
-//   chain Q   [s | a] -> qf1 -> qf2                                               q1, q2
-//   chain P   s -> policy with eps: a_new = tanh(mean + exp(clamp(log_std)) eps), log_pi, mu, clamped log_std;
-//             [s | a_new] -> qf1 -> qf2                                           q1_new, q2_new, log_pi (mu, log_std, a_new)
-//   chain N   s' -> policy with eps_next: a_next, log_pi_next; [s' | a_next] -> target_qf1 -> target_qf2
-//                                                                                 tq1, tq2, log_pi_next, y (a_next)
+//   grid    one workgroup (4 waves) per (member, chain, 16-row block): three workgroups per row-block, the workgroups of
+//           all members side by side, found through the objective's per-member table (device-visible memory, read with
+//           scalar loads; EvalCommon leads it).  Workgroups never talk to each other: no hand-offs, no spinning, no atomics.
+//   LDS     the row-block's input [16][round_up(KQ, 64)] -- the policy reads its first KP columns, the Q nets all KQ --
+//           both hidden layers [16][256], the head [16][32], the Q output columns [2][16]
+//   math    the nets where the step keeps them (Net::P, fragment-major, padded to 256; first Q layer over
+//           [obs | pad | act | pad]), through the pieces of sac_infer.h that k_act and k_qval run: infer_fill,
+//           infer_hidden, infer_head, infer_action, infer_q_out
+//
+// So the Q columns are bit for bit k_qval's values on the same rows and the actions bit for bit k_act's.  Row
+// independence as there: a row's columns are a function of that row's inputs and the member's weights only.  Rows beyond
+// a member's n are zero padding and are never written.  A kernel writes the caller's outputs in the staging
+// (act_stage_reserve, sac_act.h) and nothing else: nothing the step kernels read, no noise counter, no parameter.
+//
+// k_eval = eval_frame<SacObjective>, with the N(0,1) draws eps / eps_next:
+//   chain P   the policy with eps: a_new = tanh(mean + exp(clamp(log_std)) eps), log_pi, mu, clamped log_std; qf1, qf2
+//                                                                                 q1_new, q2_new, log_pi (mu, log_std, a_new)
+//   chain N   the same policy with eps_next: a_next, log_pi_next                  tq1, tq2, log_pi_next, y (a_next)
 //   y = rs r + ((1 - d) discount) (fminf(tq1, tq2) - alpha log_pi_next), every operation rounded to float32 on its own
 //       and none fused (eval_y), so that NumPy float32 restates it bit for bit
+//   log_pi is the step's expression (k_fwd_b's tanh-Gaussian head) on the same head values, summed by group16_sum
 //
 // alpha is the trainer's CURRENT entropy coefficient (what sac_get_scalars reports as scalars[5]; 1 with automatic tuning
 // off; exp(log_alpha) while a trainer has neither stepped nor been given scalars and its alpha still reads 0), read on
@@ -18,39 +40,26 @@
 // The training step logs its Alpha, Q Targets and losses behind its own alpha update, so they differ from
 // an evaluation of the same batch by that one alpha step.
 //
-//   grid    one workgroup (4 waves) per (member, chain, 16-row block): three workgroups per row-block, the workgroups of
-//           all members side by side, found through the per-member table EvalMember (device-visible memory, read with
-//           scalar loads).  Workgroups never talk to each other: no hand-offs, no spinning, no atomics.
-//   LDS     the row-block's input [16][round_up(KQ, 64)] -- the policy reads its first KP columns, the Q nets all KQ --
-//           both hidden layers [16][256], the head [16][32], the Q output columns [2][16]
-//   math    the nets where the step keeps them (Net::P, fragment-major, padded to 256; first Q layer over
-//           [obs | pad | act | pad]), through the pieces of sac_infer.h that k_act and k_qval run: infer_fill,
-//           infer_hidden, infer_head, infer_action, infer_q_out; log_pi is the step's expression (k_fwd_b's
-//           tanh-Gaussian head) on the same head values, summed over the actions by group16_sum
-//
-// So q1, q2, q1_new, q2_new, tq1, tq2 are bit for bit k_qval's values on the same rows and a_new / a_next bit for bit
-// k_act's.  Row independence as there: a row's columns are a function of that row's inputs and the member's weights
-// only.  Rows beyond a member's n are zero padding and are never written.  The kernel writes the caller's outputs in the
-// staging (act_stage_reserve, sac_act.h) and nothing else: nothing the step kernels read, no noise counter, no
-// parameter.
-//
 // General-step trainers are refused (SACTrainer.evaluate's host path serves them, or sac_evaluate_general:
 // sac_eval_general.h), TD3 trainers too: this is the SAC objective.
 #pragma once
 
+#include <initializer_list>
+
 namespace sac {
 
-struct EvalMember {
-    const float *P[5];                       // forward copies (Net::P): policy, qf1, qf2, target_qf1, target_qf2
-    const float *obs, *act, *rew, *term, *nobs, *eps, *eps_next;
-    float *rows;                             // (SAC_EVAL_ROWS_N, n)
-    float *mu, *log_std, *a_new, *a_next;    // (n, A) each, or null
+// the fields every objective's member table starts with
+struct EvalCommon {
+    const float *P[6];                       // forward copies (Net::P): policy, qf1, qf2, target_qf1, target_qf2, TD3's target policy
+    const float *obs, *act, *rew, *term, *nobs;
+    float *rows;                             // (the objective's columns, n)
     long long pW[3], pB[3], qW[3], qB[3];    // the layers inside the policy's P / a Q net's P
     int O, A, KP, NH;
     int n, wg0;                              // rows; first workgroup of this member in the launch
-    float alpha, rs, discount;
-    int pad;
+    float rs, discount;
 };
+
+struct EvalPolicy { const float *P; const long long *W, *B; };     // a policy's forward copy and the layers inside it
 
 // y, every operation rounded to float32 on its own so that NumPy float32 restates it bit for bit.  With this compiler
 // __fmul_rn / __fadd_rn are plain `x * y` / `x + y`, which -ffp-contract=fast fuses into FMAs like any other product
@@ -65,11 +74,11 @@ __device__ __forceinline__ float eval_y(float rs, float r, float d, float discou
     return a + b;
 }
 
-enum { EVAL_Q1, EVAL_Q2, EVAL_Q1_NEW, EVAL_Q2_NEW, EVAL_TQ1, EVAL_TQ2, EVAL_LOG_PI, EVAL_LOG_PI_NEXT, EVAL_Y, EVAL_ROWS_N };
-
-__global__ __launch_bounds__(256) void k_eval(const EvalMember *__restrict__ tab, int n_members) {
+// the row-block frame of Objective (the file comment): the body of k_eval and k_eval_td3
+template <class Objective>
+__device__ __forceinline__ void eval_frame(const typename Objective::Member *__restrict__ tab, int n_members) {
     extern __shared__ __attribute__((aligned(16))) float lds[];
-    const EvalMember *M = tab + infer_member(tab, n_members, &EvalMember::wg0);
+    const typename Objective::Member *M = tab + infer_member(tab, n_members, &EvalCommon::wg0);
     const int O = sload(&M->O), A = sload(&M->A), KP = sload(&M->KP), NH = sload(&M->NH), n = sload(&M->n);
     const int KQ = KP + 16, nrb = (n + RB - 1) / RB;
     const int local = (int)blockIdx.x - sload(&M->wg0);
@@ -92,50 +101,74 @@ __global__ __launch_bounds__(256) void k_eval(const EvalMember *__restrict__ tab
             infer_hidden(P, M->qW, M->qB, X0, KL0, KQ, X1, X2, in_place);
             infer_q_out(P, M->qW, M->qB, X2, QL + RB * q);
         }
-        if (a == 0 && grow < n) {
-            rows[(size_t)EVAL_Q1 * n + grow] = QL[r];
-            rows[(size_t)EVAL_Q2 * n + grow] = QL[RB + r];
+        if (a == 0 && grow < n) {        // q1, q2: rows 0 and 1 of every objective
+            rows[grow] = QL[r];
+            rows[(size_t)n + grow] = QL[RB + r];
         }
         return;
     }
 
     const bool next = chain == 2;        // (wave-uniform)
-    // [s or s' | 0]: the action columns are written by the head below
+    // [s or s' | 0]: the action columns are written behind the head
     infer_fill(X0, KL0, row0, n, next ? sload(&M->nobs) : sload(&M->obs), O);
-    const float *PP = sload(&M->P[0]);
-    infer_hidden(PP, M->pW, M->pB, X0, KL0, KP, X1, X2, in_place);
-    infer_head(PP, M->pW, M->pB, NH, X2, HL);
-    // tanh-Gaussian head: the action as k_act's (infer_action), log_pi as the step's
-    float lp = 0.f, actv = 0.f;
-    if (a < A) {
-        const size_t o = (size_t)grow * A + a;
-        const float mean = HL[r * ACT_HEAD_LD + a], raw = HL[r * ACT_HEAD_LD + A + a], ls = infer_log_std(raw);
-        float v;
-        actv = infer_action(HL, r, a, A, true, [&] { return grow < n ? (next ? sload(&M->eps_next) : sload(&M->eps))[o] : 0.f; }, &v);
-        const float stdv = expf(ls);
-        const float dd = __fsub_rn(v, mean);                             // Normal.log_prob(z)
-        const float var = __fmul_rn(stdv, stdv);
-        const float nlp = -(dd * dd) / (2.0f * var) - logf(stdv) - 0.91893853320467274178f;
-        lp = nlp - logf(1.0f - actv * actv + TANH_EPS);
-        if (grow < n) {
-            float *pa = next ? sload(&M->a_next) : sload(&M->a_new);
-            if (pa) pa[o] = actv;
-            if (!next) {
-                float *pm = sload(&M->mu), *pl = sload(&M->log_std);
-                if (pm) pm[o] = mean;
-                if (pl) pl[o] = raw != raw ? raw : ls;       // (fmaxf drops a NaN; torch.clamp and the host path keep it)
-            }
-        }
-    }
-    X0[lds_off(r, KP + a, KL0)] = actv;  // the whole action chunk (0 beyond A)
-    const float lsum = group16_sum(lp);
+    const EvalPolicy pi = Objective::policy(M, next);
+    infer_hidden(pi.P, pi.W, pi.B, X0, KL0, KP, X1, X2, in_place);
+    infer_head(pi.P, pi.W, pi.B, NH, X2, HL);
+    float carry;                         // the head's per-row value, for the epilogue
+    X0[lds_off(r, KP + a, KL0)] = Objective::head(M, HL, r, a, A, grow, n, next, carry);   // the whole action chunk (0 beyond A)
+    const int nq = Objective::critics(next);
 #pragma unroll 1
-    for (int q = 0; q < 2; ++q) {        // qf1, qf2 or the two target nets
+    for (int q = 0; q < nq; ++q) {       // qf1 (, qf2) or the two target nets
         const float *P = sload(&M->P[(next ? 3 : 1) + q]);
         infer_hidden(P, M->qW, M->qB, X0, KL0, KQ, X1, X2, in_place);
         infer_q_out(P, M->qW, M->qB, X2, QL + RB * q);
     }
-    if (a == 0 && grow < n) {
+    if (a == 0 && grow < n) Objective::rows(M, rows, n, grow, next, QL, r, carry);
+}
+
+struct EvalMember : EvalCommon {
+    const float *eps, *eps_next;
+    float *mu, *log_std, *a_new, *a_next;    // (n, A) each, or null
+    float alpha;
+    int pad;
+};
+
+enum { EVAL_Q1, EVAL_Q2, EVAL_Q1_NEW, EVAL_Q2_NEW, EVAL_TQ1, EVAL_TQ2, EVAL_LOG_PI, EVAL_LOG_PI_NEXT, EVAL_Y, EVAL_ROWS_N };
+
+struct SacObjective {
+    typedef EvalMember Member;
+    // both chains read the trainer's own policy, and both run two critics
+    static __device__ __forceinline__ EvalPolicy policy(const Member *M, bool) { return {sload(&M->P[0]), M->pW, M->pB}; }
+    static __device__ __forceinline__ int critics(bool) { return 2; }
+    // tanh-Gaussian head: the action as k_act's (infer_action), log_pi as the step's; *lsum: log_pi of the row
+    static __device__ __forceinline__ float head(const Member *M, const float *HL, int r, int a, int A, int grow, int n,
+                                                 bool next, float &lsum) {
+        float lp = 0.f, actv = 0.f;
+        if (a < A) {
+            const size_t o = (size_t)grow * A + a;
+            const float mean = HL[r * ACT_HEAD_LD + a], raw = HL[r * ACT_HEAD_LD + A + a], ls = infer_log_std(raw);
+            float v;
+            actv = infer_action(HL, r, a, A, true, [&] { return grow < n ? (next ? sload(&M->eps_next) : sload(&M->eps))[o] : 0.f; }, &v);
+            const float stdv = expf(ls);
+            const float dd = __fsub_rn(v, mean);                             // Normal.log_prob(z)
+            const float var = __fmul_rn(stdv, stdv);
+            const float nlp = -(dd * dd) / (2.0f * var) - logf(stdv) - 0.91893853320467274178f;
+            lp = nlp - logf(1.0f - actv * actv + TANH_EPS);
+            if (grow < n) {
+                float *pa = next ? sload(&M->a_next) : sload(&M->a_new);
+                if (pa) pa[o] = actv;
+                if (!next) {
+                    float *pm = sload(&M->mu), *pl = sload(&M->log_std);
+                    if (pm) pm[o] = mean;
+                    if (pl) pl[o] = raw != raw ? raw : ls;       // (fmaxf drops a NaN; torch.clamp and the host path keep it)
+                }
+            }
+        }
+        lsum = group16_sum(lp);
+        return actv;
+    }
+    static __device__ __forceinline__ void rows(const Member *M, float *rows, int n, int grow, bool next, const float *QL,
+                                                int r, float lsum) {
         const float qa = QL[r], qb = QL[RB + r];
         if (!next) {
             rows[(size_t)EVAL_Q1_NEW * n + grow] = qa;
@@ -150,17 +183,82 @@ __global__ __launch_bounds__(256) void k_eval(const EvalMember *__restrict__ tab
             rows[(size_t)EVAL_Y * n + grow] = eval_y(rs, rew, d, gamma, qa, qb, alpha, lsum);
         }
     }
+};
+
+__global__ __launch_bounds__(256) void k_eval(const EvalMember *__restrict__ tab, int n_members) {
+    eval_frame<SacObjective>(tab, n_members);
 }
 
 }  // namespace sac
 
 namespace {
 
-size_t eval_lds_bytes(int KQ) {
-    return sizeof(float) * (size_t)RB * (((KQ + 63) & ~63) + 2 * H + ACT_HEAD_LD + 2);
+size_t eval_lds_bytes(int KQ) { return sizeof(float) * (size_t)RB * (((KQ + 63) & ~63) + 2 * H + ACT_HEAD_LD + 2); }
+
+template <class Member> std::atomic<bool> g_eval_lds_raised[64];     // (infer_raise_lds: per kernel, that is per member table)
+
+// ---- the host staging of a grouped evaluation call (evaluate_many, td3_evaluate_many, evaluate_general_many) ----
+
+// The call's place in the first member's staging (act_stage_reserve): the kernels' tables in front (head_bytes), then
+// per member its parts -- float arrays, each on a 256-byte boundary -- in the order of the caller's size table.
+struct EvalStage {
+    size_t off[SAC_GROUP_MAX][12], floats[SAC_GROUP_MAX][12], bytes;
+    const sac_trainer::ActStage *S = nullptr;                            // behind reserve()
+    explicit EvalStage(size_t head_bytes) : bytes(infer_align(head_bytes)) {}
+    void carve(int i, const size_t *part, int count) {
+        infer_carve(bytes, off[i], part, count);
+        std::copy(part, part + count, floats[i]);
+    }
+    int reserve(sac_trainer *t0) { S = &t0->act_stage; return act_stage_reserve(t0, bytes); }
+    // part k of member i on the device (`asked` false: null); as an input, filled from `from` first (null: a kernel in
+    // front fills the part)
+    float *dev(int i, int k, bool asked = true) const { return asked ? reinterpret_cast<float *>(S->d + off[i][k]) : nullptr; }
+    const float *in(int i, int k, const float *from) const {
+        if (from) memcpy(S->h + off[i][k], from, sizeof(float) * floats[i][k]);
+        return dev(i, k);
+    }
+    // behind the wait: the parts the caller asked for (dst not null) into its arrays
+    struct Back { float *dst; int part; };
+    void back(int i, std::initializer_list<Back> table) const {
+        for (const Back &b : table)
+            if (b.dst) memcpy(b.dst, S->h + off[i][b.part], sizeof(float) * floats[i][b.part]);
+    }
+};
+
+void eval_layers(long long *W, long long *B, const Net &N) {
+    for (int l = 0; l < 3; ++l) { W[l] = N.L[l].offW; B[l] = N.L[l].offB; }
 }
 
-std::atomic<bool> g_eval_lds_raised[64];
+// EvalCommon of trainer t with n rows and its first n_nets nets, but for the parts; the member's three workgroups per
+// row-block go behind wgs, its KQ into kq_max
+void eval_member(sac::EvalCommon &M, const sac_trainer *t, int n_nets, int n, int &wgs, int &kq_max) {
+    for (int k = 0; k < 6; ++k) M.P[k] = k < n_nets ? t->net[k].P : nullptr;
+    eval_layers(M.pW, M.pB, t->net[SAC_NET_POLICY]);
+    eval_layers(M.qW, M.qB, t->net[SAC_NET_QF1]);
+    M.O = t->O; M.A = t->A; M.KP = t->KP; M.NH = t->NH;
+    M.n = n; M.wg0 = wgs;
+    M.rs = t->cfg.reward_scale; M.discount = t->cfg.discount;
+    wgs += 3 * ((n + RB - 1) / RB);
+    kq_max = std::max(kq_max, t->KQ);
+}
+
+// the frame's launch on t0's stream (wgs workgroups, the m members of the table at the staging's start), and the wait
+// behind `behind`, which may launch a reader of the frame's outputs
+template <class Member, class Behind>
+int eval_launch(void (*kernel)(const Member *, int), sac_trainer *t0, int wgs, int m, int kq_max, Behind behind) {
+    const size_t lds = eval_lds_bytes(kq_max);
+    if (infer_raise_lds(reinterpret_cast<const void *>(kernel), g_eval_lds_raised<Member>, t0->device, lds, eval_lds_bytes(512)))
+        return -1;
+    hipLaunchKernelGGL(kernel, dim3(wgs), dim3(256), lds, t0->stream, reinterpret_cast<const Member *>(t0->act_stage.d), m);
+    SAC_HIP(hipGetLastError());
+    return behind() || wait_trainer_stream(t0) ? -1 : 0;
+}
+
+// the row count of a one-trainer entry
+int eval_admit_solo(const char *fn, int64_t n) {
+    SAC_REQUIRE(n >= 1 && n <= ACT_MAX_ROWS, "%s: %lld rows (1..%d per call)", fn, (long long)n, ACT_MAX_ROWS);
+    return 0;
+}
 
 // the entropy coefficient of this moment for every member with rows (sac_get_scalars' scalars[5]; 1 with automatic
 // tuning off), behind the drain: what sac_evaluate_many and sac_evaluate_general_many both evaluate y with.  log_alpha
@@ -195,7 +293,8 @@ int eval_admit_io(const sac_eval_io_t &E, int i, bool need_rows) {
 
 }  // namespace
 
-static_assert((int)EVAL_ROWS_N == (int)SAC_EVAL_ROWS_N && (int)EVAL_Y == (int)SAC_EVAL_Y, "k_eval's rows are sac_hip.h's");
+static_assert((int)EVAL_ROWS_N == (int)SAC_EVAL_ROWS_N && (int)EVAL_Y == (int)SAC_EVAL_Y && EVAL_Q1 == 0 && EVAL_Q2 == 1,
+              "k_eval's rows are sac_hip.h's, chain Q's the first two");
 
 // sac_evaluate_many (stats null) and sac_evaluate_stats_many: with stats, mu and log_std always have their place in the
 // staging (k_eval_moments reads them there; only the copy to the caller depends on what was asked for), k_eval_moments
@@ -211,9 +310,8 @@ static int evaluate_many(const InferEntry &IE, sac_trainer_t *const *trainers, i
     float alpha[SAC_GROUP_MAX], log_alpha[SAC_GROUP_MAX];
     if (eval_read_alpha(trainers, n_trainers, n_rows, alpha, stats ? log_alpha : nullptr)) return -1;
 
-    // per member: obs act rew term nobs eps eps_next | rows mu log_std a_new a_next
-    enum { NPART = 12 };
-    size_t off[SAC_GROUP_MAX][NPART], bytes = infer_align(sizeof(EvalMember) * SAC_GROUP_MAX);
+    enum { P_OBS, P_ACT, P_REW, P_TERM, P_NOBS, P_EPS, P_EPS_NEXT, P_ROWS, P_MU, P_LOG_STD, P_A_NEW, P_A_NEXT, NPART };
+    EvalStage ST(sizeof(EvalMember) * SAC_GROUP_MAX);
     for (int i = 0; i < n_trainers; ++i) {
         const sac_trainer *t = trainers[i];
         const size_t n = (size_t)n_rows[i], nO = n * t->O, nA = n * t->A;
@@ -221,13 +319,13 @@ static int evaluate_many(const InferEntry &IE, sac_trainer_t *const *trainers, i
         const size_t part[NPART] = {nO, nA, n, n, nO, nA, nA, n * SAC_EVAL_ROWS_N,
                                     n && (E.mu || stats) ? nA : 0, n && (E.log_std || stats) ? nA : 0,
                                     n && E.a_new ? nA : 0, n && E.a_next ? nA : 0};
-        infer_carve(bytes, off[i], part, NPART);
+        ST.carve(i, part, NPART);
     }
     MomentsStage MS;
-    if (stats) moments_carve(bytes, MS, n_trainers);
+    if (stats) moments_carve(ST.bytes, MS, n_trainers);
     EvalRowsStage RS;
-    if (src) eval_rows_carve(bytes, RS, n_trainers, n_rows);
-    if (act_stage_reserve(t0, bytes)) return -1;
+    if (src) eval_rows_carve(ST.bytes, RS, n_trainers, n_rows);
+    if (ST.reserve(t0)) return -1;
     const sac_trainer::ActStage &S = t0->act_stage;
     EvalMember *tab = reinterpret_cast<EvalMember *>(S.h);
     int wgs = 0, m = 0, kq_max = 0, row_wgs = 0;
@@ -235,48 +333,26 @@ static int evaluate_many(const InferEntry &IE, sac_trainer_t *const *trainers, i
         const sac_trainer *t = trainers[i];
         if (n_rows[i] == 0) continue;
         const sac_eval_io_t &E = io[i];
-        const size_t n = (size_t)n_rows[i], nO = n * t->O, nA = n * t->A;
         EvalMember &M = tab[m++];
-        for (int k = 0; k < 5; ++k) M.P[k] = t->net[SAC_NET_POLICY + k].P;
-        auto in = [&](int k, const float *from, size_t count) {          // (from null: k_eval_rows fills the part)
-            if (from) memcpy(S.h + off[i][k], from, sizeof(float) * count);
-            return reinterpret_cast<const float *>(S.d + off[i][k]);
-        };
-        auto out = [&](int k, bool asked) { return asked ? reinterpret_cast<float *>(S.d + off[i][k]) : nullptr; };
-        M.obs = in(0, src ? nullptr : E.obs, nO); M.act = in(1, src ? nullptr : E.act, nA);
-        M.rew = in(2, src ? nullptr : E.rew, n); M.term = in(3, src ? nullptr : E.term, n);
-        M.nobs = in(4, src ? nullptr : E.next_obs, nO); M.eps = in(5, E.eps, nA); M.eps_next = in(6, E.eps_next, nA);
-        if (src) row_wgs += eval_rows_member(S, RS, m - 1, i, row_wgs, src[i], n_rows[i], out(0, true), out(1, true),
-                                             out(2, true), out(3, true), out(4, true));
-        M.rows = out(7, true); M.mu = out(8, E.mu || stats); M.log_std = out(9, E.log_std || stats);
-        M.a_new = out(10, E.a_new); M.a_next = out(11, E.a_next);
+        eval_member(M, t, 5, n_rows[i], wgs, kq_max);
+        // (src: k_eval_rows fills the five parts)
+        M.obs = ST.in(i, P_OBS, src ? nullptr : E.obs); M.act = ST.in(i, P_ACT, src ? nullptr : E.act);
+        M.rew = ST.in(i, P_REW, src ? nullptr : E.rew); M.term = ST.in(i, P_TERM, src ? nullptr : E.term);
+        M.nobs = ST.in(i, P_NOBS, src ? nullptr : E.next_obs);
+        M.eps = ST.in(i, P_EPS, E.eps); M.eps_next = ST.in(i, P_EPS_NEXT, E.eps_next);
+        if (src) row_wgs += eval_rows_member(S, RS, m - 1, i, row_wgs, src[i], n_rows[i], ST.dev(i, P_OBS), ST.dev(i, P_ACT),
+                                             ST.dev(i, P_REW), ST.dev(i, P_TERM), ST.dev(i, P_NOBS));
+        M.rows = ST.dev(i, P_ROWS); M.mu = ST.dev(i, P_MU, E.mu || stats); M.log_std = ST.dev(i, P_LOG_STD, E.log_std || stats);
+        M.a_new = ST.dev(i, P_A_NEW, E.a_new); M.a_next = ST.dev(i, P_A_NEXT, E.a_next);
         if (stats) moments_member(S, MS, m - 1, i, M.rows, M.mu, M.log_std, n_rows[i], t->A);
-        const Net &NP = t->net[SAC_NET_POLICY], &NQ = t->net[SAC_NET_QF1];
-        for (int l = 0; l < 3; ++l) {
-            M.pW[l] = NP.L[l].offW; M.pB[l] = NP.L[l].offB;
-            M.qW[l] = NQ.L[l].offW; M.qB[l] = NQ.L[l].offB;
-        }
-        M.O = t->O; M.A = t->A; M.KP = t->KP; M.NH = t->NH;
-        M.n = n_rows[i]; M.wg0 = wgs;
-        M.alpha = alpha[i]; M.rs = t->cfg.reward_scale; M.discount = t->cfg.discount; M.pad = 0;
-        wgs += 3 * ((n_rows[i] + RB - 1) / RB);
-        kq_max = std::max(kq_max, t->KQ);
+        M.alpha = alpha[i]; M.pad = 0;
     }
-    const size_t lds = eval_lds_bytes(kq_max);
-    if (infer_raise_lds(reinterpret_cast<const void *>(k_eval), g_eval_lds_raised, t0->device, lds, eval_lds_bytes(512))) return -1;
     if (src && eval_rows_launch(t0, RS, m, row_wgs, src, n_trainers, n_rows)) return -1;
-    hipLaunchKernelGGL(k_eval, dim3(wgs), dim3(256), lds, t0->stream, reinterpret_cast<const EvalMember *>(S.d), m);
-    SAC_HIP(hipGetLastError());
-    if (stats && moments_launch(t0, MS, m)) return -1;
-    if (wait_trainer_stream(t0)) return -1;
+    if (eval_launch(k_eval, t0, wgs, m, kq_max, [&] { return stats ? moments_launch(t0, MS, m) : 0; })) return -1;
     for (int i = 0; i < n_trainers; ++i) {
         if (n_rows[i] == 0) continue;
         sac_eval_io_t &E = io[i];
-        const size_t n = (size_t)n_rows[i], nA = n * trainers[i]->A;
-        if (E.rows) memcpy(E.rows, S.h + off[i][7], sizeof(float) * n * SAC_EVAL_ROWS_N);
-        float *const dst[4] = {E.mu, E.log_std, E.a_new, E.a_next};
-        for (int k = 0; k < 4; ++k)
-            if (dst[k]) memcpy(dst[k], S.h + off[i][8 + k], sizeof(float) * nA);
+        ST.back(i, {{E.rows, P_ROWS}, {E.mu, P_MU}, {E.log_std, P_LOG_STD}, {E.a_new, P_A_NEW}, {E.a_next, P_A_NEXT}});
         E.alpha = alpha[i];
         if (stats) moments_read(S, MS, i, alpha[i], log_alpha[i], &stats[i]);
     }
@@ -309,7 +385,7 @@ int sac_evaluate_replay_many(sac_trainer_t *const *trainers, int n_trainers, con
 
 int sac_evaluate(sac_trainer_t *t, int64_t n, sac_eval_io_t *io) {
     SAC_REQUIRE(t && io, "bad arguments to sac_evaluate");
-    SAC_REQUIRE(n >= 1 && n <= ACT_MAX_ROWS, "sac_evaluate: %lld rows (1..%d per call)", (long long)n, ACT_MAX_ROWS);
+    if (int rc = eval_admit_solo("sac_evaluate", n)) return rc;
     const int32_t rows = (int32_t)n;
     return sac_evaluate_many(&t, 1, &rows, io);
 }

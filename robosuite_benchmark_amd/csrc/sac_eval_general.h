@@ -133,7 +133,7 @@ static int evaluate_general_many(const InferEntry &IE, sac_trainer_t *const *tra
     //   obs act rew term nobs eps eps_next | rows a_new a_next (always: the critic launches read them) mu log_std
     enum { P_OBS, P_ACT, P_REW, P_TERM, P_NOBS, P_EPS, P_EPS_NEXT, P_ROWS, P_A_NEW, P_A_NEXT, P_MU, P_LOG_STD, NPART };
     const size_t tab_bytes = infer_align(sizeof(EvalLayerJob) * EG_JOBS * EG_LAUNCHES);
-    size_t off[SAC_GROUP_MAX][NPART], bytes = tab_bytes + infer_align(sizeof(EvalYMember) * SAC_GROUP_MAX);
+    EvalStage ST(tab_bytes + infer_align(sizeof(EvalYMember) * SAC_GROUP_MAX));
     int LP = 0, LQ = 0;
     size_t slice_p[SAC_GROUP_MAX] = {}, slice_q[SAC_GROUP_MAX] = {};
     for (int i = 0; i < n_trainers; ++i) {
@@ -142,7 +142,7 @@ static int evaluate_general_many(const InferEntry &IE, sac_trainer_t *const *tra
         const sac_eval_io_t &E = io[i];
         const size_t part[NPART] = {nO, nA, n, n, nO, nA, nA, n * SAC_EVAL_ROWS_N, nA, nA,
                                     n && (E.mu || stats) ? nA : 0, n && (E.log_std || stats) ? nA : 0};
-        infer_carve(bytes, off[i], part, NPART);
+        ST.carve(i, part, NPART);
         if (n == 0) continue;
         const GenNet &P = t->gen->net[SAC_NET_POLICY], &Q = t->gen->net[SAC_NET_QF1];      // (the four Q nets share their layout)
         slice_p[i] = n * infer_widest(P); slice_q[i] = n * infer_widest(Q);
@@ -150,10 +150,10 @@ static int evaluate_general_many(const InferEntry &IE, sac_trainer_t *const *tra
         LP = std::max(LP, P.nl); LQ = std::max(LQ, Q.nl);
     }
     MomentsStage MS;
-    if (stats) moments_carve(bytes, MS, n_trainers);
+    if (stats) moments_carve(ST.bytes, MS, n_trainers);
     EvalRowsStage RS;
-    if (src) eval_rows_carve(bytes, RS, n_trainers, n_rows);
-    if (act_stage_reserve(t0, bytes)) return -1;
+    if (src) eval_rows_carve(ST.bytes, RS, n_trainers, n_rows);
+    if (ST.reserve(t0)) return -1;
     const sac_trainer::ActStage &S = t0->act_stage;
     EvalLayerJob *tab = reinterpret_cast<EvalLayerJob *>(S.h);
     EvalYMember *ytab = reinterpret_cast<EvalYMember *>(S.h + tab_bytes);
@@ -163,15 +163,14 @@ static int evaluate_general_many(const InferEntry &IE, sac_trainer_t *const *tra
         if (n_rows[i] == 0) continue;
         const sac_eval_io_t &E = io[i];
         const int n = n_rows[i], rbs = (n + RB - 1) / RB;
-        const size_t nO = (size_t)n * t->O, nA = (size_t)n * t->A;
-        auto dev = [&](int k) { return reinterpret_cast<float *>(S.d + off[i][k]); };
-        auto in = [&](int k, const float *from, size_t count) { memcpy(S.h + off[i][k], from, sizeof(float) * count); };
+        auto dev = [&](int k) { return ST.dev(i, k); };
+        auto in = [&](int k, const float *from) { ST.in(i, k, from); };
         if (src) {
             row_wgs += eval_rows_member(S, RS, m, i, row_wgs, src[i], n, dev(P_OBS), dev(P_ACT), dev(P_REW), dev(P_TERM), dev(P_NOBS));
         } else {
-            in(P_OBS, E.obs, nO); in(P_ACT, E.act, nA); in(P_REW, E.rew, n); in(P_TERM, E.term, n); in(P_NOBS, E.next_obs, nO);
+            in(P_OBS, E.obs); in(P_ACT, E.act); in(P_REW, E.rew); in(P_TERM, E.term); in(P_NOBS, E.next_obs);
         }
-        in(P_EPS, E.eps, nA); in(P_EPS_NEXT, E.eps_next, nA);
+        in(P_EPS, E.eps); in(P_EPS_NEXT, E.eps_next);
         float *rows = dev(P_ROWS);
         auto job = [&](int launch, const GenNet &N, const GenLayer &L) -> EvalLayerJob & {
             EvalLayerJob &J = tab[(size_t)launch * EG_JOBS + njobs[launch]++];
@@ -241,11 +240,7 @@ static int evaluate_general_many(const InferEntry &IE, sac_trainer_t *const *tra
     for (int i = 0; i < n_trainers; ++i) {
         if (n_rows[i] == 0) continue;
         sac_eval_io_t &E = io[i];
-        const size_t n = (size_t)n_rows[i], nA = n * trainers[i]->A;
-        if (E.rows) memcpy(E.rows, S.h + off[i][P_ROWS], sizeof(float) * n * SAC_EVAL_ROWS_N);
-        float *const dst[4] = {E.a_new, E.a_next, E.mu, E.log_std};
-        for (int k = 0; k < 4; ++k)
-            if (dst[k]) memcpy(dst[k], S.h + off[i][P_A_NEW + k], sizeof(float) * nA);
+        ST.back(i, {{E.rows, P_ROWS}, {E.a_new, P_A_NEW}, {E.a_next, P_A_NEXT}, {E.mu, P_MU}, {E.log_std, P_LOG_STD}});
         E.alpha = alpha[i];
         if (stats) moments_read(S, MS, i, alpha[i], log_alpha[i], &stats[i]);
     }
@@ -278,7 +273,7 @@ int sac_evaluate_replay_general_many(sac_trainer_t *const *trainers, int n_train
 
 int sac_evaluate_general(sac_trainer_t *t, int64_t n, sac_eval_io_t *io) {
     SAC_REQUIRE(t && io, "bad arguments to sac_evaluate_general");
-    SAC_REQUIRE(n >= 1 && n <= ACT_MAX_ROWS, "sac_evaluate_general: %lld rows (1..%d per call)", (long long)n, ACT_MAX_ROWS);
+    if (int rc = eval_admit_solo("sac_evaluate_general", n)) return rc;
     const int32_t rows = (int32_t)n;
     return sac_evaluate_general_many(&t, 1, &rows, io);
 }

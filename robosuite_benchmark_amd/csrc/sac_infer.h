@@ -47,9 +47,9 @@ __device__ __forceinline__ void act_hidden_epilogue(const f32x4 (&acc)[NT], int 
 }
 
 // this workgroup's member of a per-member table: the last one whose first workgroup (the field wg0) is not behind this
-// workgroup (wave-uniform, scalar loads)
-template <class M>
-__device__ __forceinline__ int infer_member(const M *tab, int n_members, int M::*wg0) {
+// workgroup (wave-uniform, scalar loads); the field may be a base's (B) of the table's struct
+template <class M, class B>
+__device__ __forceinline__ int infer_member(const M *tab, int n_members, int B::*wg0) {
     int mi = 0;
     for (int i = 1; i < n_members; ++i)
         if ((int)blockIdx.x >= sload(&(tab[i].*wg0))) mi = i;

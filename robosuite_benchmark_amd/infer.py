@@ -580,16 +580,56 @@ def eval_target(rew, term, tq1, tq2, log_pi_next, alpha, reward_scale, discount)
     return f(reward_scale) * rew + ((f(1.0) - term) * f(discount)) * (np.fmin(tq1, tq2) - f(alpha) * lp)
 
 
-def _eval_columns(chunks, alpha):
-    """The per-row columns of evaluate from its chunks' outputs (rows (9, k), mu, log_std, a_new, a_next (k, A))."""
+def _eval_columns(chunks, row_names, array_names):
+    """The per-row columns of an evaluation from its chunks' outputs: rows (len(row_names), k) and one (k, A) array per
+    name of array_names -- _lib.EVAL_ROWS / EVAL_ARRAYS for evaluate, _lib.TD3_EVAL_ROWS / TD3_EVAL_ARRAYS for evaluate_td3."""
     cols = OrderedDict()
     rows = np.concatenate([c["rows"] for c in chunks], axis=1)
-    for i, name in enumerate(_lib.EVAL_ROWS):
+    for i, name in enumerate(row_names):
         cols[name] = np.ascontiguousarray(rows[i])
-    for name in _lib.EVAL_ARRAYS:
+    for name in array_names:
         cols[name] = np.concatenate([c[name] for c in chunks], axis=0)
+    return cols
+
+
+def _sac_eval_columns(chunks, alpha):
+    cols = _eval_columns(chunks, _lib.EVAL_ROWS, _lib.EVAL_ARRAYS)
     cols["alpha"] = float(alpha)
     return cols
+
+
+def _eval_io(struct, row_names, array_names, arrs, i, j, act_dim, outputs=True):
+    """(io, out, parts): `struct` (SacEvalIO, Td3EvalIO) over rows i..j of an evaluation's inputs arrs, the output arrays
+    it points to -- out["rows"] and one (j - i, act_dim) array per name of array_names -- and the input slices, to be kept
+    alive.  An input that is None (evaluate_replay: the arrays the device takes from the replay storage) stays NULL.
+    outputs=False (the *_stats_many entries alone take it): no output array is made, out is None and its fields NULL."""
+    parts = [None if a is None else np.ascontiguousarray(a[i:j]) for a in arrs]
+    ins = [None if p is None else p.ctypes.data for p in parts]
+    if not outputs:
+        return struct(*ins), None, parts
+    out = dict(rows=np.empty((len(row_names), j - i), np.float32))
+    out.update((name, np.empty((j - i, act_dim), np.float32)) for name in array_names)
+    return struct(*ins, out["rows"].ctypes.data, *[out[name].ctypes.data for name in array_names]), out, parts
+
+
+def _four_figures(d, name, x):
+    """d[name + " Mean" / " Std" (np.std) / " Max" / " Min"] of x in float64."""
+    x = np.asarray(x, np.float64).ravel()
+    d[name + " Mean"], d[name + " Std"] = float(np.mean(x)), float(np.std(x))
+    d[name + " Max"], d[name + " Min"] = float(np.max(x)), float(np.min(x))
+
+
+def _member_args(caller, takes, trainers, *per_member):
+    """The per-member arguments of the *_many evaluation calls: the trainers as a list, each of them once, and every
+    argument of per_member as a list of one entry per trainer (None: no entry for anyone)."""
+    trainers = list(trainers)
+    R = len(trainers)
+    lists = [[None] * R if x is None else list(x) for x in per_member]
+    if any(len(x) != R for x in lists):
+        raise RuntimeError(f"{caller} takes one {takes} per trainer")
+    if len({id(t) for t in trainers}) != R:
+        raise RuntimeError(f"a trainer appears twice in {caller}")
+    return [trainers] + lists
 
 
 def eval_statistics(rows, mu, log_std, alpha, log_alpha, target_entropy, auto):
@@ -602,12 +642,7 @@ def eval_statistics(rows, mu, log_std, alpha, log_alpha, target_entropy, auto):
     Max / Min (q - y, signed)."""
     r = [np.asarray(x, np.float64).ravel() for x in rows]
     q1, q2, q1n, q2n, _, _, lp, _, y = r
-
-    def stats(d, name, x):
-        x = np.asarray(x, np.float64).ravel()
-        d[name + " Mean"], d[name + " Std"] = float(np.mean(x)), float(np.std(x))
-        d[name + " Max"], d[name + " Min"] = float(np.max(x)), float(np.min(x))
-
+    stats = _four_figures
     d = OrderedDict()
     d["QF1 Loss"] = float(np.mean((q1 - y) ** 2))
     d["QF2 Loss"] = float(np.mean((q2 - y) ** 2))
@@ -747,7 +782,7 @@ def evaluate_of(trainers, inputs, rows, general, stats, replay=None):
                     moments[i], log_alphas[i] = _merge_all(moments[i], _stats_moments(sts[k])), sts[k].log_alpha
     for i in members:
         t = trainers[i]
-        cols = _eval_columns(chunks[i], alphas[i]) if rows or not on_device else None
+        cols = _sac_eval_columns(chunks[i], alphas[i]) if rows or not on_device else None
         if on_device:
             result = moments_statistics(moments[i], alphas[i], log_alphas[i], t.target_entropy, t.use_automatic_entropy_tuning)
         else:
@@ -773,15 +808,8 @@ def evaluate_many(trainers, batches, eps=None, rngs=None, rows=False, general="h
     eval_statistics under either value."""
     check_stats(stats)
     check_general(general)
-    trainers = list(trainers)
-    R = len(trainers)
-    eps = [None] * R if eps is None else list(eps)
-    rngs = [None] * R if rngs is None else list(rngs)
-    if not (len(batches) == len(eps) == len(rngs) == R):
-        raise RuntimeError("evaluate_many takes one batch (and eps pair, and rng) per trainer")
-    if len({id(t) for t in trainers}) != R:
-        raise RuntimeError("a trainer appears twice in evaluate_many")
-    inputs = [None] * R
+    trainers, batches, eps, rngs = _member_args("evaluate_many", "batch (and eps pair, and rng)", trainers, batches, eps, rngs)
+    inputs = [None] * len(trainers)
     for i, (t, b) in enumerate(zip(trainers, batches)):
         if b is None or np.atleast_2d(b["observations"]).shape[0] == 0:
             continue
@@ -816,18 +844,13 @@ def evaluate_replay_many(trainers, buffers, n=None, indices=None, eps=None, rngs
     batch inside the same call.  A member's result is bit for bit that of its own evaluate_replay; a TD3 member raises."""
     check_stats(stats)
     check_general(general)
-    trainers, buffers = list(trainers), list(buffers)
+    trainers = list(trainers)
     R = len(trainers)
     if (n is None) == (indices is None):
         raise ValueError("evaluate_replay_many takes exactly one of n and indices")
-    counts = [None] * R if n is None else ([n] * R if np.isscalar(n) else list(n))
-    indices = [None] * R if indices is None else list(indices)
-    eps = [None] * R if eps is None else list(eps)
-    rngs = [None] * R if rngs is None else list(rngs)
-    if not (len(buffers) == len(counts) == len(indices) == len(eps) == len(rngs) == R):
-        raise RuntimeError("evaluate_replay_many takes one buffer (and row count or indices, eps pair, rng) per trainer")
-    if len({id(t) for t in trainers}) != R:
-        raise RuntimeError("a trainer appears twice in evaluate_replay_many")
+    trainers, buffers, counts, indices, eps, rngs = _member_args(
+        "evaluate_replay_many", "buffer (and row count or indices, eps pair, rng)", trainers, buffers,
+        [n] * R if np.isscalar(n) else n, indices, eps, rngs)
     requests = [None] * R
     for i, (t, b) in enumerate(zip(trainers, buffers)):
         if n is not None and not counts[i]:
@@ -864,12 +887,7 @@ def td3_eval_statistics(rows, a_pi):
     -mean(q_pi); Mean / Std (np.std) / Max / Min of q1, q2, y, the Bellman errors (q - y)^2 and a_pi -- followed by
     TD Error 1 / TD Error 2 Mean / Std / Max / Min (q - y, signed)."""
     q1, q2, q_pi, _, _, y = [np.asarray(x, np.float64).ravel() for x in rows]
-
-    def stats(d, name, x):
-        x = np.asarray(x, np.float64).ravel()
-        d[name + " Mean"], d[name + " Std"] = float(np.mean(x)), float(np.std(x))
-        d[name + " Max"], d[name + " Min"] = float(np.max(x)), float(np.min(x))
-
+    stats = _four_figures
     d = OrderedDict()
     with np.errstate(all="ignore"):
         b1, b2 = (q1 - y) ** 2, (q2 - y) ** 2
@@ -885,17 +903,6 @@ def td3_eval_statistics(rows, a_pi):
         stats(d, "TD Error 1", q1 - y)
         stats(d, "TD Error 2", q2 - y)
     return d
-
-
-def _td3_eval_columns(chunks):
-    """The per-row columns of evaluate_td3 from its chunks' outputs (rows (6, k), a_pi, a_target, a_smooth (k, A))."""
-    cols = OrderedDict()
-    rows = np.concatenate([c["rows"] for c in chunks], axis=1)
-    for i, name in enumerate(_lib.TD3_EVAL_ROWS):
-        cols[name] = np.ascontiguousarray(rows[i])
-    for name in _lib.TD3_EVAL_ARRAYS:
-        cols[name] = np.concatenate([c[name] for c in chunks], axis=0)
-    return cols
 
 
 def _td3_eval_result(cols, rows):
@@ -923,21 +930,15 @@ def td3_evaluate_of(trainers, inputs, rows):
     lib = _lib.load()
     chunks = {i: [] for i in served}
     for r0, ids, counts in windows(served, n_rows):
-        parts, outs = [], []
-        for i, k in zip(ids, counts):
-            parts.append([np.ascontiguousarray(a[r0:r0 + k]) for a in inputs[i]])
-            o = dict(rows=np.empty((len(_lib.TD3_EVAL_ROWS), k), np.float32))
-            o.update((name, np.empty((k, trainers[i].act_dim), np.float32)) for name in _lib.TD3_EVAL_ARRAYS)
-            outs.append(o)
-        ios = (_lib.Td3EvalIO * len(ids))(*[
-            _lib.Td3EvalIO(*[a.ctypes.data for a in p], o["rows"].ctypes.data,
-                           *[o[name].ctypes.data for name in _lib.TD3_EVAL_ARRAYS]) for p, o in zip(parts, outs)])
+        made = [_eval_io(_lib.Td3EvalIO, _lib.TD3_EVAL_ROWS, _lib.TD3_EVAL_ARRAYS, inputs[i], r0, r0 + k, trainers[i].act_dim)
+                for i, k in zip(ids, counts)]
+        ios = (_lib.Td3EvalIO * len(ids))(*[m[0] for m in made])
         _lib.check(lib.td3_evaluate_many(_handles(trainers, ids), len(ids), _ints(counts), ios), "td3_evaluate_many")
-        for i, o in zip(ids, outs):
-            chunks[i].append(o)
+        for i, m in zip(ids, made):
+            chunks[i].append(m[1])
     for i in served:
         trainers[i]._settled()
-        out[i] = _td3_eval_result(_td3_eval_columns(chunks[i]), rows)
+        out[i] = _td3_eval_result(_eval_columns(chunks[i], _lib.TD3_EVAL_ROWS, _lib.TD3_EVAL_ARRAYS), rows)
     return out
 
 
@@ -949,19 +950,12 @@ def td3_evaluate_many(trainers, batches, eps=None, rngs=None, rows=False):
     host path inside the same call.  A member's columns never depend on its neighbours: they are bit for bit those of
     its own evaluate_td3.  Results come back in member order; rows=True as for evaluate_td3.  A SAC member raises
     (evaluate_many is the call for the SAC objective)."""
-    trainers = list(trainers)
-    R = len(trainers)
-    eps = [None] * R if eps is None else list(eps)
-    rngs = [None] * R if rngs is None else list(rngs)
-    if not (len(batches) == len(eps) == len(rngs) == R):
-        raise RuntimeError("td3_evaluate_many takes one batch (and eps, and rng) per trainer")
-    if len({id(t) for t in trainers}) != R:
-        raise RuntimeError("a trainer appears twice in td3_evaluate_many")
+    trainers, batches, eps, rngs = _member_args("td3_evaluate_many", "batch (and eps, and rng)", trainers, batches, eps, rngs)
     for i, t in enumerate(trainers):
         if not _is_td3(t):
             raise RuntimeError(f"td3_evaluate_many member {i} is a SAC trainer: this call evaluates the TD3 objective (a "
                                "deterministic policy with target smoothing); evaluate_many evaluates the SAC objective")
-    inputs = [None] * R
+    inputs = [None] * len(trainers)
     for i, (t, b) in enumerate(zip(trainers, batches)):
         if b is None or np.atleast_2d(b["observations"]).shape[0] == 0:
             continue

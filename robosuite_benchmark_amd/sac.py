@@ -32,10 +32,6 @@ def _q_forward(layers, x):
     return (h @ layers[-1][0].T + layers[-1][1])[:, 0]
 
 
-def _lib_pointers(parts):
-    return [None if p is None else p.ctypes.data for p in parts]
-
-
 class SACTrainer:
     def __init__(self, env=None, policy=None, qf1=None, qf2=None, target_qf1=None, target_qf2=None,
                  discount=0.99, reward_scale=1.0, policy_lr=1e-3, qf_lr=1e-3, optimizer_class=None,
@@ -536,17 +532,24 @@ class SACTrainer:
             rng = self._eval_rng
         return rng
 
-    def _eval_inputs(self, batch, eps, rng):
-        """evaluate's arguments, checked before any library call: float32 obs, act, rew, term, next_obs, eps, eps_next."""
+    def _eval_batch(self, caller, batch):
+        """The batch of `caller` (evaluate, evaluate_td3), checked before any library call: float32 obs, act, rew, term,
+        next_obs."""
         obs = _lib.f32(np.atleast_2d(batch["observations"]))
         n = obs.shape[0]
         act, nobs = _lib.f32(np.atleast_2d(batch["actions"])), _lib.f32(np.atleast_2d(batch["next_observations"]))
         if n < 1 or obs.shape != (n, self.obs_dim) or nobs.shape != obs.shape or act.shape != (n, self.act_dim):
-            raise ValueError(f"evaluate: observations {obs.shape} / actions {act.shape} / next_observations {nobs.shape} "
+            raise ValueError(f"{caller}: observations {obs.shape} / actions {act.shape} / next_observations {nobs.shape} "
                              f"do not fit dims ({self.obs_dim}, {self.act_dim}) (at least one row)")
         rew, term = (_lib.f32(np.asarray(batch[k]).reshape(-1)) for k in ("rewards", "terminals"))
         if rew.shape != (n,) or term.shape != (n,):
-            raise ValueError(f"evaluate: {rew.size} rewards and {term.size} terminals for {n} rows")
+            raise ValueError(f"{caller}: {rew.size} rewards and {term.size} terminals for {n} rows")
+        return obs, act, rew, term, nobs
+
+    def _eval_inputs(self, batch, eps, rng):
+        """evaluate's arguments, checked before any library call: float32 obs, act, rew, term, next_obs, eps, eps_next."""
+        obs, act, rew, term, nobs = self._eval_batch("evaluate", batch)
+        n = obs.shape[0]
         if eps is None:
             rng = self._eval_stream(rng)
             eps = (rng.standard_normal((n, self.act_dim)), rng.standard_normal((n, self.act_dim)))
@@ -558,27 +561,22 @@ class SACTrainer:
     def _eval_io(self, arrs, i, j, outputs=True):
         """sac_eval_io_t over rows i..j of evaluate's inputs, and the output arrays it points to.  outputs=False (the
         *_stats_many entries alone take it): no output array is made, `rows` and the optional arrays are NULL."""
-        k, A = j - i, self.act_dim
-        # (an input that is None -- evaluate_replay: the five arrays the device takes from the replay storage -- stays NULL)
-        parts = [None if a is None else np.ascontiguousarray(a[i:j]) for a in arrs]
-        if not outputs:
-            return _lib.SacEvalIO(*_lib_pointers(parts), *([None] * (1 + len(_lib.EVAL_ARRAYS))), 0.0), None, parts
-        out = dict(rows=np.empty((len(_lib.EVAL_ROWS), k), np.float32))
-        out.update((name, np.empty((k, A), np.float32)) for name in _lib.EVAL_ARRAYS)
-        io = _lib.SacEvalIO(*_lib_pointers(parts), out["rows"].ctypes.data,
-                            *[out[name].ctypes.data for name in _lib.EVAL_ARRAYS], 0.0)
-        return io, out, parts
+        return infer._eval_io(_lib.SacEvalIO, _lib.EVAL_ROWS, _lib.EVAL_ARRAYS, arrs, i, j, self.act_dim, outputs)
+
+    _POLICY_HEADS = 2                # heads of act_dim units behind the policy's hidden layers: mean and log_std
 
     def _host_net(self, name):
-        """[(W, b)] of one net from the current weights: sac_get_params, or the holder's arrays without a handle."""
+        """[(W, b)] of one net from the current weights: sac_get_params, or the holder's arrays without a handle.  A
+        policy's heads all read the last hidden layer; a Q net ends in one unit over cat(obs, act)."""
         flat = self._get_params(name) if self._h is not None else _lib.f32(getattr(self, name).flat())
-        sizes = self._hidden(name) + ([self.act_dim, self.act_dim] if name == "policy" else [1])
-        k = self.obs_dim if name == "policy" else self.obs_dim + self.act_dim
+        is_policy, hidden = name.endswith("policy"), self._hidden(name)
+        heads = [self.act_dim] * self._POLICY_HEADS if is_policy else [1]
+        k = self.obs_dim if is_policy else self.obs_dim + self.act_dim
         layers, off = [], 0
-        for l, n_out in enumerate(sizes):
+        for l, n_out in enumerate(hidden + heads):
             layers.append((flat[off:off + n_out * k].reshape(n_out, k), flat[off + n_out * k:off + n_out * k + n_out]))
             off += n_out * k + n_out
-            if l < len(self._hidden(name)):
+            if l < len(hidden):
                 k = n_out
         assert off == flat.size
         return layers
@@ -624,7 +622,7 @@ class SACTrainer:
                         y=eval_target(rew, term, tq1, tq2, log_pi_next, alpha, self.reward_scale, self.discount))
         out = dict(rows=np.stack([_lib.f32(cols[k]) for k in _lib.EVAL_ROWS]), mu=_lib.f32(mu), log_std=_lib.f32(log_std),
                    a_new=_lib.f32(a_new), a_next=_lib.f32(a_next))
-        return infer._eval_columns([out], alpha)
+        return infer._sac_eval_columns([out], alpha)
 
     def _scalars(self):
         sc = np.zeros(6, np.float64)

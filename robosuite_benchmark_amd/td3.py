@@ -78,33 +78,15 @@ class TD3Trainer(SACTrainer):
     # ---- the TD3 objectives on held-out transitions ------------------------------------------
     def _td3_eval_inputs(self, batch, eps, rng):
         """evaluate_td3's arguments, checked before any library call: float32 obs, act, rew, term, next_obs, eps."""
-        obs = _lib.f32(np.atleast_2d(batch["observations"]))
-        n = obs.shape[0]
-        act, nobs = _lib.f32(np.atleast_2d(batch["actions"])), _lib.f32(np.atleast_2d(batch["next_observations"]))
-        if n < 1 or obs.shape != (n, self.obs_dim) or nobs.shape != obs.shape or act.shape != (n, self.act_dim):
-            raise ValueError(f"evaluate_td3: observations {obs.shape} / actions {act.shape} / next_observations "
-                             f"{nobs.shape} do not fit dims ({self.obs_dim}, {self.act_dim}) (at least one row)")
-        rew, term = (_lib.f32(np.asarray(batch[k]).reshape(-1)) for k in ("rewards", "terminals"))
-        if rew.shape != (n,) or term.shape != (n,):
-            raise ValueError(f"evaluate_td3: {rew.size} rewards and {term.size} terminals for {n} rows")
+        obs, act, rew, term, nobs = self._eval_batch("evaluate_td3", batch)
         if eps is None:
-            eps = self._eval_stream(rng).standard_normal((n, self.act_dim))
+            eps = self._eval_stream(rng).standard_normal(act.shape)
         eps = _lib.f32(np.atleast_2d(eps))
         if eps.shape != act.shape:
             raise ValueError(f"evaluate_td3: eps {eps.shape} for actions {act.shape}")
         return obs, act, rew, term, nobs, eps
 
-    def _host_net(self, name):
-        """[(W, b)] of one net from the current weights; the two policies are TanhMlpPolicy: one head of act_dim units."""
-        if name not in ("policy", "target_policy"):
-            return super()._host_net(name)
-        flat = self._get_params(name) if self._h is not None else _lib.f32(getattr(self, name).flat())
-        layers, off, k = [], 0, self.obs_dim
-        for n_out in self._hidden(name) + [self.act_dim]:
-            layers.append((flat[off:off + n_out * k].reshape(n_out, k), flat[off + n_out * k:off + n_out * k + n_out]))
-            off, k = off + n_out * k + n_out, n_out
-        assert off == flat.size
-        return layers
+    _POLICY_HEADS = 1                # (_host_net) the two policies are TanhMlpPolicy: one head of act_dim units
 
     def _evaluate_td3_host(self, arrs):
         """The host path of evaluate_td3: the nets' current weights (sac_sync, sac_get_params; the holders' own arrays
@@ -130,7 +112,7 @@ class TD3Trainer(SACTrainer):
                         y=infer.td3_eval_target(rew, term, tq1, tq2, self.reward_scale, self.discount))
         out = dict(rows=np.stack([_lib.f32(cols[k]) for k in _lib.TD3_EVAL_ROWS]), a_pi=_lib.f32(a_pi),
                    a_target=_lib.f32(a_target), a_smooth=_lib.f32(a_smooth))
-        return infer._td3_eval_columns([out])
+        return infer._eval_columns([out], _lib.TD3_EVAL_ROWS, _lib.TD3_EVAL_ARRAYS)
 
     def evaluate_td3(self, batch, eps=None, rng=None, rows=False):
         """The TD3 objectives of this run on `batch` WITHOUT a gradient step: `batch` is the dict train() takes
