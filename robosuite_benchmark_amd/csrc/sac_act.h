@@ -63,19 +63,6 @@ __global__ __launch_bounds__(256) void k_act(const ActMember *__restrict__ tab, 
 
 namespace {
 
-// the staging of acting calls (sac_trainer::act_stage), owned by the trainer that launches: the first of a call
-int act_stage_reserve(sac_trainer *t, size_t bytes) {
-    sac_trainer::ActStage &S = t->act_stage;
-    if (S.bytes >= bytes) return 0;
-    if (S.h) SAC_HIP(hipHostFree(S.h));
-    S = sac_trainer::ActStage{};
-    bytes = (bytes + 65535) & ~(size_t)65535;
-    SAC_HIP(hipHostMalloc(reinterpret_cast<void **>(&S.h), bytes, hipHostMallocMapped));
-    SAC_HIP(hipHostGetDevicePointer(reinterpret_cast<void **>(&S.d), S.h, 0));
-    S.bytes = bytes;
-    return 0;
-}
-
 size_t act_lds_bytes(int KP) { return sizeof(float) * (size_t)RB * (((KP + 63) & ~63) + 2 * H + ACT_HEAD_LD); }
 
 std::atomic<bool> g_act_lds_raised[64];

@@ -4,11 +4,13 @@
 // A session (sac_gactor) is made once for a fixed list of general-step trainers.  What never changes between two ticks
 // is written once, at creation:
 //
-//   device memory   the job table GActJob[GMAXL][SAC_GROUP_MAX]: slot [l][i] is member i's layer l -- W and b inside
-//                   GenNet::P, the input and output pointers, eps, N, K, tiles_n, A, vec and the static part of the kind
-//                   (hidden, SAC head, TD3 head).  A member shallower than l has no job there (live == 0).
+//   device memory   the job table GActJob[GMAXL][SAC_GROUP_MAX]: slot [l][i] is member i's layer l -- the LayerJob that
+//                   LayerSchedule::chain (sac_infer.h) writes for sac_policy_act_general_many, on the slab and the
+//                   session's scratch; a SAC head's kind is its static part.  GActJob stays a struct of its own around
+//                   it: the table is indexed by member and never rewritten, the per-call part (rows, stochastic, wg0)
+//                   is GActCtl.  A member shallower than l has no job there (live == 0).
 //   scratch         two ping-pong activation buffers per member, max_rows x its widest hidden layer each, owned by the
-//                   SESSION: the trainer's act_gen buffers (sac_act_general.h) may be freed and reallocated by
+//                   SESSION: the trainer's act_gen buffers (sac_infer.h) may be freed and reallocated by
 //                   act_general_reserve, and two sessions over the same trainers must not meet in one buffer.
 //   the slab        ONE mapped pinned allocation: the control block GActCtl, then per member obs (max_rows, O) FLOAT64,
 //                   eps (max_rows, A) fp32, act (max_rows, A) fp32, each 256-byte aligned and fixed for the session's
@@ -19,13 +21,12 @@
 // layer depth on member 0's stream and waits for one event of its own.  As with sac_actor_act the launches go on member
 // 0's stream even when member 0 sits out.
 //
-// Behind its prologue k_act_layer_session runs k_act_layer's tile and epilogues (sac_act_general.h; infer_layer_tile,
-// infer_layer_store, infer_layer_head of sac_infer.h): a session's actions are bit for bit sac_policy_act_general's.
-// The prologue reads the launch's wg0 row,
-// n and stochastic with three 16-dword scalar loads issued together, picks the member with scalar compares and reads
-// that member's static job from device memory.  In launch 0 (template parameter F64) the input rows are float64 in the
-// slab (infer_layer_tile<double, false>) and are rounded to fp32 on the way into LDS: a plain cast, round to nearest
-// even, the value of numpy's astype(float32).  The fp32 instance is k_act_layer's.
+// Behind its prologue k_act_layer_session runs k_act_layer's frame (infer_layer_frame<T, false, LayerHead<false>> of
+// sac_infer.h) on a job the same builder wrote: a session's actions are bit for bit sac_policy_act_general's.  The
+// prologue reads the launch's wg0 row, n and stochastic with three 16-dword scalar loads issued together, picks the
+// member with scalar compares and reads that member's static job from device memory.  In launch 0 (template parameter
+// F64) the input rows are float64 in the slab (infer_layer_tile<double, false>) and are rounded to fp32 on the way into
+// LDS: a plain cast, round to nearest even, the value of numpy's astype(float32).  The fp32 instance is k_act_layer's.
 //
 // GenNet::P and the layer offsets.  A general-step trainer's networks live in sac_general::arena, which
 // gen_build_sac / gen_build_td3 (sac_general_host.h) allocate once and carve with a bump allocator; gen_shape_net, the
@@ -40,12 +41,8 @@
 namespace sac {
 
 struct GActJob {                   // static, device memory: member i's layer l
-    const float *W, *b;            // [N][K], [N] inside GenNet::P
-    const void *X;                 // input rows [max_rows][K]: l == 0 the slab's float64 obs, else session scratch (fp32)
-    const float *eps;              // the slab's eps [max_rows][A]
-    float *Y;                      // session scratch [max_rows][N]; the member's last layer: the slab's act [max_rows][A]
-    int N, K, tiles_n, A;
-    int vec, kind;                 // kind: AG_HIDDEN, AG_SAC_MEAN (a SAC head: the call's flag makes it AG_SAC_SAMPLE), AG_TD3
+    LayerJob J;                    // X: the slab's FLOAT64 obs for l == 0; a SAC head says LAYER_SAC_MEAN (the call's flag makes
+                                   // it LAYER_SAC_SAMPLE); n and wg0 are unused (the control block has the call's)
     int live, pad;                 // 0: the member has no layer l
 };
 
@@ -58,8 +55,6 @@ struct GActCtl {                   // per call, at the head of the slab
 
 template <bool F64>
 __global__ __launch_bounds__(256) void k_act_layer_session(const GActJob *__restrict__ tab, const GActCtl *__restrict__ ctl, int l) {
-    __shared__ __attribute__((aligned(16))) float Xs[RB * AG_LD];
-    __shared__ float HL[RB * ACT_HEAD_LD];
     typedef typename std::conditional<F64, double, float>::type xin_t;
     // this workgroup's member: the last one whose first workgroup is not behind this one (wave-uniform; the three arrays
     // come over the link in one go: three 16-dword scalar loads); a member without a job here is passed over
@@ -70,19 +65,9 @@ __global__ __launch_bounds__(256) void k_act_layer_session(const GActJob *__rest
 #pragma unroll
     for (int i = 1; i < SAC_GROUP_MAX; ++i)
         if ((int)blockIdx.x >= w0s[i]) { mi = i; wg0 = w0s[i]; n = ns[i]; stochastic = sts[i]; }
-    const GActJob *J = tab + mi;
-    const float *W = sload(&J->W), *bp = sload(&J->b);
-    const xin_t *X = reinterpret_cast<const xin_t *>(sload(&J->X));
-    const int N = sload(&J->N), K = sload(&J->K), kind_s = sload(&J->kind);
-    const int kind = (kind_s == AG_SAC_MEAN && stochastic) ? AG_SAC_SAMPLE : kind_s;
-    const int tiles_n = sload(&J->tiles_n);
-    const bool vec = sload(&J->vec) != 0;
-    const int tile = (int)blockIdx.x - wg0;
-    const int row0 = RB * (tile / tiles_n), n0 = AG_CT * (tile % tiles_n);
-    const int ncol = n0 + 16 * (threadIdx.x >> 6) + (threadIdx.x & 15);
-    const LayerTile t = infer_layer_tile<xin_t, false>(Xs, W, bp, X, X, N, K, K, n, vec, row0, ncol);
-    if (kind == AG_HIDDEN) infer_layer_store(t, sload(&J->Y), N, n, row0, ncol, true);
-    else infer_layer_head(t, HL, J, kind, n, row0);
+    const LayerJob *J = &tab[mi].J;
+    const int kind_s = sload(&J->kind);
+    infer_layer_frame<xin_t, false, LayerHead<false>>(J, wg0, n, (kind_s == LAYER_SAC_MEAN && stochastic) ? LAYER_SAC_SAMPLE : kind_s);
 }
 
 }  // namespace sac
@@ -114,6 +99,10 @@ int gactor_build(sac_gactor *a, size_t slab_bytes) {
         floats += 2 * buf[i];
     }
     SAC_HIP(hipMalloc(reinterpret_cast<void **>(&a->scratch), sizeof(float) * floats));
+    // the static table through the schedule builder: its own table is thrown away, each job goes to its member's slot
+    std::vector<LayerJob> jobs((size_t)SAC_GROUP_MAX * gen::GMAXL);
+    LayerSchedule LS(SAC_GROUP_MAX);
+    LS.bind(jobs.data(), nullptr);
     float *next = a->scratch;
     for (int i = 0; i < a->n; ++i) {
         const sac_trainer *t = a->member[i];
@@ -121,22 +110,18 @@ int gactor_build(sac_gactor *a, size_t slab_bytes) {
         float *pp[2] = {next, next + buf[i]};
         next += 2 * buf[i];
         a->P[i] = P.P;
-        a->launches = std::max(a->launches, P.nl);
-        const void *x = a->slab_d + a->off[i][0];
-        for (int l = 0; l < P.nl; ++l) {
-            const GenLayer &L = P.L[l];
-            const bool head = l + 1 == P.nl;
-            GActJob &J = a->tab[l][i];
-            infer_layer_job(J, P, L);
-            J.X = x;
-            J.eps = reinterpret_cast<const float *>(a->slab_d + a->off[i][1]);
-            J.Y = head ? reinterpret_cast<float *>(a->slab_d + a->off[i][2]) : pp[l & 1];
-            J.A = t->A;
-            J.kind = !head ? AG_HIDDEN : (t->algo == 1 ? AG_TD3 : AG_SAC_MEAN);
-            J.live = 1;
-            x = J.Y;
-        }
+        const float *x = reinterpret_cast<const float *>(a->slab_d + a->off[i][0]);        // (float64 rows: GActJob)
+        LS.chain({P, x, x, P.L[0].K, a->max_rows[i], pp, 0, reinterpret_cast<float *>(a->slab_d + a->off[i][2])},
+                 [&](LayerJob &J, int l) {
+            if (l + 1 == P.nl) {
+                J.kind = t->algo == 1 ? LAYER_TD3 : LAYER_SAC_MEAN;
+                J.eps = reinterpret_cast<const float *>(a->slab_d + a->off[i][1]); J.A = t->A;
+            }
+            a->tab[l][i].J = J;
+            a->tab[l][i].live = 1;
+        });
     }
+    a->launches = LS.launches;
     SAC_HIP(hipMalloc(reinterpret_cast<void **>(&a->d_tab), sizeof(a->tab)));
     SAC_HIP(hipMemcpy(a->d_tab, a->tab, sizeof(a->tab), hipMemcpyHostToDevice));
     SAC_HIP(hipEventCreateWithFlags(&a->ev, hipEventDisableTiming));
@@ -216,7 +201,7 @@ int sac_gactor_act(sac_gactor_t *a, const int32_t *n_rows, const int32_t *determ
         ctl->stochastic[i] = (rows && a->member[i]->algo == 0 && !deterministic[i]) ? 1 : 0;
         for (int l = 0; l < gen::GMAXL; ++l) {
             ctl->wg0[l][i] = blocks[l];
-            if (rows && a->tab[l][i].live) blocks[l] += ((n_rows[i] + RB - 1) / RB) * a->tab[l][i].tiles_n;
+            if (rows && a->tab[l][i].live) blocks[l] += ((n_rows[i] + RB - 1) / RB) * a->tab[l][i].J.tiles_n;
         }
     }
     const GActCtl *d_ctl = reinterpret_cast<const GActCtl *>(a->slab_d);

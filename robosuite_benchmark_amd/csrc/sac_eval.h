@@ -1,6 +1,6 @@
 // Evaluating an objective on the device: the forward half of the step on rows the run has not trained on (included by
-// sac_trainer.hip).  Here: the row-block frame and the host staging of every such evaluation, once, and the SAC
-// objective; td3_eval.h holds the TD3 objective.
+// sac_trainer.hip).  Here: the row-block frame of every such evaluation, once, and the SAC objective; td3_eval.h holds
+// the TD3 objective.  The host staging is InferStage (sac_infer.h), which the general-shape entries share.
 //
 // eval_frame<Objective> computes, for 1..1024 transitions (s, a, r, d, s') of each of 1..SAC_GROUP_MAX trainers in ONE
 // launch and from the live weights, three chains per 16-row block:
@@ -24,7 +24,7 @@
 // So the Q columns are bit for bit k_qval's values on the same rows and the actions bit for bit k_act's.  Row
 // independence as there: a row's columns are a function of that row's inputs and the member's weights only.  Rows beyond
 // a member's n are zero padding and are never written.  A kernel writes the caller's outputs in the staging
-// (act_stage_reserve, sac_act.h) and nothing else: nothing the step kernels read, no noise counter, no parameter.
+// (act_stage_reserve, sac_infer.h) and nothing else: nothing the step kernels read, no noise counter, no parameter.
 //
 // k_eval = eval_frame<SacObjective>, with the N(0,1) draws eps / eps_next:
 //   chain P   the policy with eps: a_new = tanh(mean + exp(clamp(log_std)) eps), log_pi, mu, clamped log_std; qf1, qf2
@@ -43,8 +43,6 @@
 // General-step trainers are refused (SACTrainer.evaluate's host path serves them, or sac_evaluate_general:
 // sac_eval_general.h), TD3 trainers too: this is the SAC objective.
 #pragma once
-
-#include <initializer_list>
 
 namespace sac {
 
@@ -197,34 +195,6 @@ size_t eval_lds_bytes(int KQ) { return sizeof(float) * (size_t)RB * (((KQ + 63) 
 
 template <class Member> std::atomic<bool> g_eval_lds_raised[64];     // (infer_raise_lds: per kernel, that is per member table)
 
-// ---- the host staging of a grouped evaluation call (evaluate_many, td3_evaluate_many, evaluate_general_many) ----
-
-// The call's place in the first member's staging (act_stage_reserve): the kernels' tables in front (head_bytes), then
-// per member its parts -- float arrays, each on a 256-byte boundary -- in the order of the caller's size table.
-struct EvalStage {
-    size_t off[SAC_GROUP_MAX][12], floats[SAC_GROUP_MAX][12], bytes;
-    const sac_trainer::ActStage *S = nullptr;                            // behind reserve()
-    explicit EvalStage(size_t head_bytes) : bytes(infer_align(head_bytes)) {}
-    void carve(int i, const size_t *part, int count) {
-        infer_carve(bytes, off[i], part, count);
-        std::copy(part, part + count, floats[i]);
-    }
-    int reserve(sac_trainer *t0) { S = &t0->act_stage; return act_stage_reserve(t0, bytes); }
-    // part k of member i on the device (`asked` false: null); as an input, filled from `from` first (null: a kernel in
-    // front fills the part)
-    float *dev(int i, int k, bool asked = true) const { return asked ? reinterpret_cast<float *>(S->d + off[i][k]) : nullptr; }
-    const float *in(int i, int k, const float *from) const {
-        if (from) memcpy(S->h + off[i][k], from, sizeof(float) * floats[i][k]);
-        return dev(i, k);
-    }
-    // behind the wait: the parts the caller asked for (dst not null) into its arrays
-    struct Back { float *dst; int part; };
-    void back(int i, std::initializer_list<Back> table) const {
-        for (const Back &b : table)
-            if (b.dst) memcpy(b.dst, S->h + off[i][b.part], sizeof(float) * floats[i][b.part]);
-    }
-};
-
 void eval_layers(long long *W, long long *B, const Net &N) {
     for (int l = 0; l < 3; ++l) { W[l] = N.L[l].offW; B[l] = N.L[l].offB; }
 }
@@ -252,12 +222,6 @@ int eval_launch(void (*kernel)(const Member *, int), sac_trainer *t0, int wgs, i
     hipLaunchKernelGGL(kernel, dim3(wgs), dim3(256), lds, t0->stream, reinterpret_cast<const Member *>(t0->act_stage.d), m);
     SAC_HIP(hipGetLastError());
     return behind() || wait_trainer_stream(t0) ? -1 : 0;
-}
-
-// the row count of a one-trainer entry
-int eval_admit_solo(const char *fn, int64_t n) {
-    SAC_REQUIRE(n >= 1 && n <= ACT_MAX_ROWS, "%s: %lld rows (1..%d per call)", fn, (long long)n, ACT_MAX_ROWS);
-    return 0;
 }
 
 // the entropy coefficient of this moment for every member with rows (sac_get_scalars' scalars[5]; 1 with automatic
@@ -311,7 +275,7 @@ static int evaluate_many(const InferEntry &IE, sac_trainer_t *const *trainers, i
     if (eval_read_alpha(trainers, n_trainers, n_rows, alpha, stats ? log_alpha : nullptr)) return -1;
 
     enum { P_OBS, P_ACT, P_REW, P_TERM, P_NOBS, P_EPS, P_EPS_NEXT, P_ROWS, P_MU, P_LOG_STD, P_A_NEW, P_A_NEXT, NPART };
-    EvalStage ST(sizeof(EvalMember) * SAC_GROUP_MAX);
+    InferStage ST(sizeof(EvalMember) * SAC_GROUP_MAX);
     for (int i = 0; i < n_trainers; ++i) {
         const sac_trainer *t = trainers[i];
         const size_t n = (size_t)n_rows[i], nO = n * t->O, nA = n * t->A;
@@ -385,7 +349,7 @@ int sac_evaluate_replay_many(sac_trainer_t *const *trainers, int n_trainers, con
 
 int sac_evaluate(sac_trainer_t *t, int64_t n, sac_eval_io_t *io) {
     SAC_REQUIRE(t && io, "bad arguments to sac_evaluate");
-    if (int rc = eval_admit_solo("sac_evaluate", n)) return rc;
+    if (int rc = infer_admit_solo("sac_evaluate", n)) return rc;
     const int32_t rows = (int32_t)n;
     return sac_evaluate_many(&t, 1, &rows, io);
 }

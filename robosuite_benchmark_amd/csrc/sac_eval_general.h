@@ -17,10 +17,13 @@
 //                                         target_qf1 and target_qf2.  Chain Q needs no policy, but it waits for the
 //                                         critic phase: one rule for all six jobs, and no launch more.
 //               launch LP+LQ              k_eval_y: y, elementwise, from the columns the launches in front of it wrote
-//   table     a launch carries up to EG_JOBS = 6 SAC_GROUP_MAX jobs (EvalLayerJob, device-visible memory, read with scalar
-//             loads).  A workgroup finds its job by a bisection over wg0 (ascending), as in k_qval_layer.
+//   table     a launch carries up to EG_JOBS = 6 SAC_GROUP_MAX jobs (LayerJob, device-visible memory, read with scalar
+//             loads).  LayerSchedule (sac_infer.h) writes the tables: per member two policy chains from launch 0 and six
+//             critic chains from launch LP, k_act_layer's and k_qval_layer's chains.
+//   kernel    infer_layer_find, then infer_layer_frame<float, SPLIT, Head>: LayerHead<true> for the policy launches,
+//             LayerStore (no head, no HL) for the critics'
 //   grid      one workgroup (4 waves) per 16-row x 64-column output tile of one job
-//   policy    infer_layer_tile<float, false> and infer_layer_store (sac_infer.h): k_act_layer's hidden layers
+//   policy    infer_layer_tile<float, false> and infer_layer_store: k_act_layer's hidden layers
 //   head      N = 2A <= 32, one column tile, through HL: infer_layer_head_eval (sac_infer.h) -- the action is
 //             infer_action's with the draws (k_act_layer's stochastic action, bit for bit), log_pi is k_eval's expression
 //             summed by group16_sum, and for the rows s the mean and the clamped log_std (a NaN stays a NaN).  a_new and
@@ -35,7 +38,7 @@
 // the launches on one stream.  Row independence as in k_act_layer / k_qval_layer: an output element is one MFMA chain
 // over k in an order fixed by K alone, rows beyond a job's n repeat row n - 1 on the way in and are never written.
 //
-// The kernels write the caller's outputs in the staging (act_stage_reserve) and the members' activation scratch: nothing
+// The kernels write the caller's outputs in the staging (InferStage) and the members' activation scratch: nothing
 // the step reads.  The scratch is the trainer's act_gen pair (act_general_reserve), shared with sac_policy_act_general
 // and sac_q_values_general -- each of those calls, and this one, ends with a wait on the stream, so they never overlap.
 // Each buffer holds max(2 n x the widest policy layer, 6 n x the widest critic layer) floats; the worst case is
@@ -47,19 +50,6 @@ namespace sac {
 constexpr int EG_JOBS = 6 * SAC_GROUP_MAX;      // jobs of one launch
 constexpr int EG_LAUNCHES = 2 * gen::GMAXL;     // layer launches of one call, at most
 constexpr int EG_YROWS = 256;                   // rows of one k_eval_y workgroup
-enum { EG_STORE = 0, EG_HEAD = 1 };
-
-struct EvalLayerJob {
-    const float *W, *b;            // [N][K], [N]
-    const float *X, *X2;           // input rows: columns 0 .. K1-1 from X [n][K1], columns K1 .. K-1 from X2 [n][K - K1]
-    float *Y;                      // hidden layer: [n][N]; critic output (N == 1): its row of `rows`; head: the actions [n][A]
-    const float *eps;              // head: the N(0,1) draws [n][A]
-    float *lp, *mu, *ls;           // head: log_pi [n]; mean and clamped log_std [n][A], or null
-    int N, K, K1, n;
-    int wg0, tiles_n, relu, vec;   // wg0: first workgroup of this job in the launch; vec: 16-byte pieces of W's rows
-    int kind, A, pad[2];
-};
-
 struct EvalYMember {
     const float *rew, *term;       // [n]
     float *rows;                   // (SAC_EVAL_ROWS_N, n)
@@ -70,32 +60,10 @@ struct EvalYMember {
 
 // SPLIT false: a policy launch (hidden layers and heads); true: a critic launch
 template <bool SPLIT>
-__global__ __launch_bounds__(256) void k_eval_layer(const EvalLayerJob *__restrict__ tab, int n_jobs) {
-    __shared__ __attribute__((aligned(16))) float Xs[RB * AG_LD];
-    // this workgroup's job: the last one whose first workgroup is not behind this one (wave-uniform, scalar loads)
-    int lo = 0, hi = n_jobs;
-    while (hi - lo > 1) {
-        const int mid = (lo + hi) >> 1;
-        if ((int)blockIdx.x >= sload(&tab[mid].wg0)) lo = mid; else hi = mid;
-    }
-    const EvalLayerJob *J = tab + lo;
-    const float *W = sload(&J->W), *X = sload(&J->X), *bp = sload(&J->b);
-    const int N = sload(&J->N), K = sload(&J->K), n = sload(&J->n);
-    const int tiles_n = sload(&J->tiles_n);
-    const bool vec = sload(&J->vec) != 0;
-    const int tile = (int)blockIdx.x - sload(&J->wg0);
-    const int row0 = RB * (tile / tiles_n), n0 = AG_CT * (tile % tiles_n);
-    const int ncol = n0 + 16 * (threadIdx.x >> 6) + (threadIdx.x & 15);
-    if constexpr (SPLIT) {
-        const LayerTile t = infer_layer_tile<float, true>(Xs, W, bp, X, sload(&J->X2), N, K, sload(&J->K1), n, vec, row0, ncol);
-        // hidden layer: ReLU; output layer (N == 1, relu == 0): column 0 alone passes ncol < N and lands in its row of `rows`
-        infer_layer_store(t, sload(&J->Y), N, n, row0, ncol, sload(&J->relu) != 0);
-    } else {
-        __shared__ float HL[RB * ACT_HEAD_LD];
-        const LayerTile t = infer_layer_tile<float, false>(Xs, W, bp, X, X, N, K, K, n, vec, row0, ncol);
-        if (sload(&J->kind) == EG_STORE) infer_layer_store(t, sload(&J->Y), N, n, row0, ncol, true);
-        else infer_layer_head_eval(t, HL, J, n, row0);
-    }
+__global__ __launch_bounds__(256) void k_eval_layer(const LayerJob *__restrict__ tab, int n_jobs) {
+    const LayerJob *J = infer_layer_find(tab, n_jobs);
+    typedef typename std::conditional<SPLIT, LayerStore, LayerHead<true>>::type Head;
+    infer_layer_frame<float, SPLIT, Head>(J, sload(&J->wg0), sload(&J->n), SPLIT ? (int)LAYER_STORE : sload(&J->kind));
 }
 
 __global__ __launch_bounds__(EG_YROWS) void k_eval_y(const EvalYMember *__restrict__ tab, int n_members) {
@@ -132,8 +100,10 @@ static int evaluate_general_many(const InferEntry &IE, sac_trainer_t *const *tra
     // the staging: the layer tables, k_eval_y's table, then per member
     //   obs act rew term nobs eps eps_next | rows a_new a_next (always: the critic launches read them) mu log_std
     enum { P_OBS, P_ACT, P_REW, P_TERM, P_NOBS, P_EPS, P_EPS_NEXT, P_ROWS, P_A_NEW, P_A_NEXT, P_MU, P_LOG_STD, NPART };
-    const size_t tab_bytes = infer_align(sizeof(EvalLayerJob) * EG_JOBS * EG_LAUNCHES);
-    EvalStage ST(tab_bytes + infer_align(sizeof(EvalYMember) * SAC_GROUP_MAX));
+    LayerSchedule LS(EG_JOBS);
+    static_assert(EG_LAUNCHES <= LayerSchedule::MAX_LAUNCHES, "the schedule counts every launch of an evaluation");
+    const size_t tab_bytes = LS.bytes(EG_LAUNCHES);
+    InferStage ST(tab_bytes + infer_align(sizeof(EvalYMember) * SAC_GROUP_MAX));
     int LP = 0, LQ = 0;
     size_t slice_p[SAC_GROUP_MAX] = {}, slice_q[SAC_GROUP_MAX] = {};
     for (int i = 0; i < n_trainers; ++i) {
@@ -145,6 +115,8 @@ static int evaluate_general_many(const InferEntry &IE, sac_trainer_t *const *tra
         ST.carve(i, part, NPART);
         if (n == 0) continue;
         const GenNet &P = t->gen->net[SAC_NET_POLICY], &Q = t->gen->net[SAC_NET_QF1];      // (the four Q nets share their layout)
+        // (one reservation for the larger of the two phases, not infer_scratch_reserve twice: that would free and
+        // allocate again where the second phase is the larger)
         slice_p[i] = n * infer_widest(P); slice_q[i] = n * infer_widest(Q);
         if (act_general_reserve(t, std::max(2 * slice_p[i], 6 * slice_q[i]))) return -1;
         LP = std::max(LP, P.nl); LQ = std::max(LQ, Q.nl);
@@ -155,14 +127,14 @@ static int evaluate_general_many(const InferEntry &IE, sac_trainer_t *const *tra
     if (src) eval_rows_carve(ST.bytes, RS, n_trainers, n_rows);
     if (ST.reserve(t0)) return -1;
     const sac_trainer::ActStage &S = t0->act_stage;
-    EvalLayerJob *tab = reinterpret_cast<EvalLayerJob *>(S.h);
+    LS.bind(S.h, S.d);
     EvalYMember *ytab = reinterpret_cast<EvalYMember *>(S.h + tab_bytes);
-    int njobs[EG_LAUNCHES] = {}, blocks[EG_LAUNCHES] = {}, yblocks = 0, m = 0, row_wgs = 0;
+    int yblocks = 0, m = 0, row_wgs = 0;
     for (int i = 0; i < n_trainers; ++i) {
         const sac_trainer *t = trainers[i];
         if (n_rows[i] == 0) continue;
         const sac_eval_io_t &E = io[i];
-        const int n = n_rows[i], rbs = (n + RB - 1) / RB;
+        const int n = n_rows[i];
         auto dev = [&](int k) { return ST.dev(i, k); };
         auto in = [&](int k, const float *from) { ST.in(i, k, from); };
         if (src) {
@@ -172,52 +144,27 @@ static int evaluate_general_many(const InferEntry &IE, sac_trainer_t *const *tra
         }
         in(P_EPS, E.eps); in(P_EPS_NEXT, E.eps_next);
         float *rows = dev(P_ROWS);
-        auto job = [&](int launch, const GenNet &N, const GenLayer &L) -> EvalLayerJob & {
-            EvalLayerJob &J = tab[(size_t)launch * EG_JOBS + njobs[launch]++];
-            J = EvalLayerJob{};
-            infer_layer_job(J, N, L);
-            J.K1 = L.K; J.n = n; J.A = t->A; J.relu = 1; J.kind = EG_STORE;
-            J.wg0 = blocks[launch];
-            blocks[launch] += rbs * J.tiles_n;
-            return J;
-        };
-        // the policy on s (with eps) and on s' (with eps_next)
+        // the policy on s (with eps) and on s' (with eps_next), launches 0 .. : its head writes the action and log_pi
         const GenNet &P = t->gen->net[SAC_NET_POLICY];
         for (int s = 0; s < 2; ++s) {
             const float *x = dev(s ? P_NOBS : P_OBS);
-            for (int l = 0; l < P.nl; ++l) {
-                EvalLayerJob &J = job(l, P, P.L[l]);
-                J.X = J.X2 = x;
-                if (l + 1 < P.nl) {
-                    J.Y = t->act_gen[l & 1] + (size_t)s * slice_p[i];
-                } else {
-                    J.kind = EG_HEAD; J.relu = 0;
-                    J.Y = dev(s ? P_A_NEXT : P_A_NEW);
-                    J.eps = dev(s ? P_EPS_NEXT : P_EPS);
-                    J.lp = rows + (size_t)(s ? EVAL_LOG_PI_NEXT : EVAL_LOG_PI) * n;
-                    J.mu = !s && (E.mu || stats) ? dev(P_MU) : nullptr;
-                    J.ls = !s && (E.log_std || stats) ? dev(P_LOG_STD) : nullptr;
-                }
-                x = J.Y;
-            }
+            LS.chain({P, x, x, P.L[0].K, n, t->act_gen, s * slice_p[i], dev(s ? P_A_NEXT : P_A_NEW)},
+                     [&](sac::LayerJob &J, int l) {
+                if (l + 1 < P.nl) return;
+                J.kind = LAYER_EVAL; J.A = t->A;
+                J.eps = dev(s ? P_EPS_NEXT : P_EPS);
+                J.lp = rows + (size_t)(s ? EVAL_LOG_PI_NEXT : EVAL_LOG_PI) * n;
+                J.mu = !s && (E.mu || stats) ? dev(P_MU) : nullptr;
+                J.ls = !s && (E.log_std || stats) ? dev(P_LOG_STD) : nullptr;
+            });
         }
-        // the critics: job s writes row s of `rows` (EVAL_Q1 .. EVAL_TQ2)
+        // the critics, launches LP .. : chain s writes row s of `rows` (EVAL_Q1 .. EVAL_TQ2)
         const int net_of[6] = {SAC_NET_QF1, SAC_NET_QF2, SAC_NET_QF1, SAC_NET_QF2, SAC_NET_TARGET_QF1, SAC_NET_TARGET_QF2};
         const int obs_of[6] = {P_OBS, P_OBS, P_OBS, P_OBS, P_NOBS, P_NOBS};
         const int act_of[6] = {P_ACT, P_ACT, P_A_NEW, P_A_NEW, P_A_NEXT, P_A_NEXT};
-        for (int s = 0; s < 6; ++s) {
-            const GenNet &Q = t->gen->net[net_of[s]];
-            const float *x = dev(obs_of[s]), *x2 = dev(act_of[s]);
-            for (int l = 0; l < Q.nl; ++l) {
-                const bool last = l + 1 == Q.nl;
-                EvalLayerJob &J = job(LP + l, Q, Q.L[l]);
-                J.X = x; J.X2 = x2;
-                J.K1 = l == 0 ? t->O : Q.L[l].K;
-                J.Y = last ? rows + (size_t)s * n : t->act_gen[l & 1] + (size_t)s * slice_q[i];
-                J.relu = last ? 0 : 1;
-                x = x2 = J.Y;
-            }
-        }
+        for (int s = 0; s < 6; ++s)
+            LS.chain({t->gen->net[net_of[s]], dev(obs_of[s]), dev(act_of[s]), t->O, n, t->act_gen, s * slice_q[i],
+                      rows + (size_t)s * n, true, LP});
         if (stats) moments_member(S, MS, m, i, rows, dev(P_MU), dev(P_LOG_STD), n, t->A);
         EvalYMember &M = ytab[m++];
         M.rew = dev(P_REW); M.term = dev(P_TERM); M.rows = rows;
@@ -226,12 +173,8 @@ static int evaluate_general_many(const InferEntry &IE, sac_trainer_t *const *tra
         yblocks += (n + EG_YROWS - 1) / EG_YROWS;
     }
     if (src && eval_rows_launch(t0, RS, m, row_wgs, src, n_trainers, n_rows)) return -1;
-    const EvalLayerJob *d_tab = reinterpret_cast<const EvalLayerJob *>(S.d);
-    for (int l = 0; l < LP + LQ; ++l) {
-        if (l < LP) hipLaunchKernelGGL(k_eval_layer<false>, dim3(blocks[l]), dim3(256), 0, t0->stream, d_tab + (size_t)l * EG_JOBS, njobs[l]);
-        else hipLaunchKernelGGL(k_eval_layer<true>, dim3(blocks[l]), dim3(256), 0, t0->stream, d_tab + (size_t)l * EG_JOBS, njobs[l]);
-        SAC_HIP(hipGetLastError());
-    }
+    for (int l = 0; l < LP + LQ; ++l)
+        if (LS.launch(l < LP ? k_eval_layer<false> : k_eval_layer<true>, t0, l)) return -1;
     hipLaunchKernelGGL(k_eval_y, dim3(yblocks), dim3(EG_YROWS), 0, t0->stream,
                        reinterpret_cast<const EvalYMember *>(S.d + tab_bytes), m);
     SAC_HIP(hipGetLastError());
@@ -273,7 +216,7 @@ int sac_evaluate_replay_general_many(sac_trainer_t *const *trainers, int n_train
 
 int sac_evaluate_general(sac_trainer_t *t, int64_t n, sac_eval_io_t *io) {
     SAC_REQUIRE(t && io, "bad arguments to sac_evaluate_general");
-    if (int rc = eval_admit_solo("sac_evaluate_general", n)) return rc;
+    if (int rc = infer_admit_solo("sac_evaluate_general", n)) return rc;
     const int32_t rows = (int32_t)n;
     return sac_evaluate_general_many(&t, 1, &rows, io);
 }

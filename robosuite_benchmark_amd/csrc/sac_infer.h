@@ -4,18 +4,34 @@
 // (the fused kernels' shapes: one workgroup carries a 16-row block through a whole net in LDS) and k_act_layer,
 // k_act_layer_session<F64>, k_qval_layer, k_eval_layer<SPLIT> (general shapes: one launch per layer, one workgroup per
 // 16 x 64 output tile).
-// Each of them is a prologue that finds its member or job, calls into the pieces below, and an epilogue of its own.
+// Each of the fused-shape kernels is a prologue that finds its member, calls into the pieces below, and an epilogue of
+// its own.  Each general-shape kernel is a prologue that finds its job (LayerJob) and ONE call:
+//
+//   kernel                      job found by                   infer_layer_frame<T, SPLIT, Head>
+//   k_act_layer                 infer_layer_find               <float, false, LayerHead<false>>
+//   k_qval_layer                infer_layer_find               <float, true,  LayerStore>
+//   k_eval_layer<false>         infer_layer_find               <float, false, LayerHead<true>>
+//   k_eval_layer<true>          infer_layer_find               <float, true,  LayerStore>
+//   k_act_layer_session<F64>    the control block, by member   <double | float, false, LayerHead<false>>
+//
 // Every bit-for-bit promise between them -- a session's actions are the device call's, k_eval's Q values are k_qval's
-// and its actions k_act's -- holds because they run THESE functions, not copies of them.  A new inference kernel
-// composes the same pieces; it does not paste a body.
+// and its actions k_act's, the general evaluation's Q columns are sac_q_values_general's and the unit statistics'
+// activations k_qval_layer's -- holds because they run THESE functions, not copies of them, on job tables that ONE
+// builder writes (LayerSchedule: the layer chain, the ping-pong of the activation scratch, wg0).  A new inference kernel
+// composes the same pieces; it does not paste a body, and a new per-layer entry appends chains; it does not spell the
+// schedule.
 //
 //   fused shapes     infer_member, infer_fill, infer_hidden, infer_head, infer_q_out, infer_action
-//   general shapes   infer_layer_tile, infer_layer_store, infer_layer_head / infer_layer_head_eval (infer_action again)
-//   host             infer_admit / infer_admit_session (the refusals), infer_carve / infer_slab (staging and slab layout),
-//                    infer_raise_lds, infer_widest / infer_layer_job (per-layer job tables)
+//   general shapes   LayerJob, infer_layer_find, infer_layer_frame = infer_layer_tile + a Head (LayerStore, LayerHead<EVAL>:
+//                    infer_layer_store, infer_layer_head / infer_layer_head_eval, infer_action again)
+//   host             infer_admit / infer_admit_session / infer_admit_solo (the refusals), InferStage (a grouped call's staging:
+//                    carve, reserve, in, dev, back) over infer_carve and act_stage_reserve, infer_slab (a session's slab),
+//                    infer_raise_lds, LayerSchedule over infer_widest / infer_layer_job (per-layer job tables, their launches),
+//                    infer_scratch_reserve over act_general_reserve (the activation scratch)
 #pragma once
 
 #include <atomic>
+#include <initializer_list>
 #include <type_traits>
 
 namespace sac {
@@ -163,7 +179,26 @@ constexpr int AG_LD = AG_KC + 4;          // LDS row stride of the staged input 
 constexpr int AG_NQ = AG_KC / 16;         // groups of four MFMAs per chunk
 constexpr int AG_XE = RB * AG_KC / 256;   // input values of a chunk per thread
 constexpr int AG_CT = 64;                 // columns of an output tile
-enum { AG_HIDDEN = 0, AG_SAC_MEAN = 1, AG_SAC_SAMPLE = 2, AG_TD3 = 3 };
+
+// One layer of one net for one member's rows: a job of a per-layer launch (device-visible memory, read with scalar
+// loads; LayerSchedule, below, is the tables' one writer)
+enum { LAYER_STORE = 0,           // a hidden layer or a critic's output unit: infer_layer_store
+       LAYER_SAC_MEAN = 1,        // a SAC policy's head, tanh(mean)
+       LAYER_SAC_SAMPLE = 2,      // the same head with the draws: tanh(mean + exp(clamp(log_std)) * eps)
+       LAYER_TD3 = 3,             // a TD3 policy's head, tanh(last_fc)
+       LAYER_EVAL = 4 };          // the stochastic SAC head with what the objectives need: infer_layer_head_eval
+
+struct LayerJob {
+    const float *W, *b;            // [N][K], [N]
+    const float *X, *X2;           // input rows: columns 0 .. K1-1 from X [n][K1], columns K1 .. K-1 from X2 [n][K - K1].
+                                   // The frame reads them as its T: a session's layer 0 keeps FLOAT64 rows behind X
+    float *Y;                      // LAYER_STORE: [n][N] (N == 1: the net's row of values, [n]); a head: the actions [n][A]
+    const float *eps;              // head: the N(0,1) draws [n][A]
+    float *lp, *mu, *ls;           // LAYER_EVAL: log_pi [n]; mean and clamped log_std [n][A], or null
+    int N, K, K1, n;
+    int wg0, tiles_n, relu, vec;   // wg0: first workgroup of this job in the launch; vec: 16-byte pieces of W's rows
+    int kind, A, pad[2];
+};
 
 __device__ __forceinline__ double ld1gd(const double *p) { return *(const __attribute__((address_space(1))) double *)(uintptr_t)p; }
 
@@ -308,8 +343,7 @@ __device__ __forceinline__ void infer_layer_head_lds(const LayerTile &t, float *
     __syncthreads();
 }
 
-template <class Job>
-__device__ __forceinline__ void infer_layer_head(const LayerTile &t, float *HL, const Job *J, int kind, int n, int row0) {
+__device__ __forceinline__ void infer_layer_head(const LayerTile &t, float *HL, const LayerJob *J, int kind, int n, int row0) {
     typedef __attribute__((address_space(1))) float *gout;
     infer_layer_head_lds(t, HL);
     const int tid = threadIdx.x;
@@ -318,17 +352,16 @@ __device__ __forceinline__ void infer_layer_head(const LayerTile &t, float *HL, 
     if (a < A && row0 + r < n) {
         const unsigned o = (unsigned)(row0 + r) * (unsigned)A + (unsigned)a;
         *(gout)(uintptr_t)(sload(&J->Y) + o) =
-            infer_action(HL, r, a, A, kind == AG_SAC_SAMPLE, [&] { return ld1g(sload(&J->eps) + o); });
+            infer_action(HL, r, a, A, kind == LAYER_SAC_SAMPLE, [&] { return ld1g(sload(&J->eps) + o); });
     }
 }
 
 // infer_layer_head's sibling for loss evaluation: the stochastic SAC head of job J with everything the objectives need
-// from it.  The action is infer_action's (bit for bit k_act_layer's AG_SAC_SAMPLE action) and goes to J->Y always; log_pi is
+// from it.  The action is infer_action's (bit for bit k_act_layer's LAYER_SAC_SAMPLE action) and goes to J->Y always; log_pi is
 // k_eval's expression on the same head values -- Normal.log_prob of the value under the tanh, minus
 // log(1 - a^2 + TANH_EPS), summed over the actions by group16_sum -- and goes to J->lp [n]; J->mu / J->ls [n][A], where
 // not null, get the mean and the clamped log_std (a NaN stays a NaN: fmaxf would drop it).
-template <class Job>
-__device__ __forceinline__ void infer_layer_head_eval(const LayerTile &t, float *HL, const Job *J, int n, int row0) {
+__device__ __forceinline__ void infer_layer_head_eval(const LayerTile &t, float *HL, const LayerJob *J, int n, int row0) {
     typedef __attribute__((address_space(1))) float *gout;
     infer_layer_head_lds(t, HL);
     const int tid = threadIdx.x;
@@ -355,6 +388,54 @@ __device__ __forceinline__ void infer_layer_head_eval(const LayerTile &t, float 
     }
     const float lsum = group16_sum(lp);
     if (a == 0 && live) *(gout)(uintptr_t)(sload(&J->lp) + (unsigned)(row0 + r)) = lsum;
+}
+
+// What follows the tile (the frame's Head).  A kernel gets the epilogues of its Head and no other: LayerStore has no HL
+// and no head branch; the two with a head store a hidden layer with its ReLU and send every other kind through HL.
+struct LayerStore {                // the critics' launches: every job is a store, ReLU as the job says (off: the output unit)
+    static __device__ __forceinline__ void finish(const LayerTile &t, const LayerJob *J, int, int N, int n, int row0, int ncol) {
+        infer_layer_store(t, sload(&J->Y), N, n, row0, ncol, sload(&J->relu) != 0);
+    }
+};
+template <bool EVAL>               // a policy's launches: hidden layers, and the acting heads or (EVAL) the evaluation head
+struct LayerHead {
+    static __device__ __forceinline__ void finish(const LayerTile &t, const LayerJob *J, int kind, int N, int n, int row0, int ncol) {
+        __shared__ float HL[RB * ACT_HEAD_LD];
+        if (kind == LAYER_STORE) infer_layer_store(t, sload(&J->Y), N, n, row0, ncol, true);
+        else if constexpr (EVAL) infer_layer_head_eval(t, HL, J, n, row0);
+        else infer_layer_head(t, HL, J, kind, n, row0);
+    }
+};
+
+// this workgroup's job of a launch's table: the last one whose first workgroup is not behind this one (wave-uniform,
+// scalar loads).  A bisection over wg0, which LayerSchedule writes in ascending order: at most 7 dependent loads where a
+// scan over the 96 jobs of an evaluation launch would chain 96.
+__device__ __forceinline__ const LayerJob *infer_layer_find(const LayerJob *tab, int n_jobs) {
+    int lo = 0, hi = n_jobs;
+    while (hi - lo > 1) {
+        const int mid = (lo + hi) >> 1;
+        if ((int)blockIdx.x >= sload(&tab[mid].wg0)) lo = mid; else hi = mid;
+    }
+    return tab + lo;
+}
+
+// The layer frame: the body of every per-layer kernel behind its prologue, which resolves the job J and, with it, the
+// job's first workgroup, its rows and its kind (a session reads those three from its control block).  T and SPLIT are
+// infer_layer_tile's: without SPLIT neither X2 nor K1 is loaded.
+template <class T, bool SPLIT, class Head>
+__device__ __forceinline__ void infer_layer_frame(const LayerJob *J, int wg0, int n, int kind) {
+    __shared__ __attribute__((aligned(16))) float Xs[RB * AG_LD];
+    const float *W = sload(&J->W), *bp = sload(&J->b);
+    const T *X = reinterpret_cast<const T *>(sload(&J->X));
+    const int N = sload(&J->N), K = sload(&J->K);
+    const int tiles_n = sload(&J->tiles_n);
+    const bool vec = sload(&J->vec) != 0;
+    const int tile = (int)blockIdx.x - wg0;
+    const int row0 = RB * (tile / tiles_n), n0 = AG_CT * (tile % tiles_n);
+    const int ncol = n0 + 16 * (threadIdx.x >> 6) + (threadIdx.x & 15);
+    const T *X2 = SPLIT ? reinterpret_cast<const T *>(sload(&J->X2)) : X;
+    const LayerTile t = infer_layer_tile<T, SPLIT>(Xs, W, bp, X, X2, N, K, SPLIT ? sload(&J->K1) : K, n, vec, row0, ncol);
+    Head::finish(t, J, kind, N, n, row0, ncol);
 }
 
 }  // namespace sac
@@ -433,12 +514,61 @@ int infer_admit_session(const InferEntry &E, sac_trainer_t *const *trainers, int
     return 0;
 }
 
+// the row count of a one-trainer entry
+int infer_admit_solo(const char *fn, int64_t n) {
+    SAC_REQUIRE(n >= 1 && n <= ACT_MAX_ROWS, "%s: %lld rows (1..%d per call)", fn, (long long)n, ACT_MAX_ROWS);
+    return 0;
+}
+
 inline size_t infer_align(size_t bytes) { return (bytes + 255) & ~(size_t)255; }
 
 // carves `count` arrays of part[k] elements out of a buffer that is `bytes` long so far: each on a 256-byte boundary
 inline void infer_carve(size_t &bytes, size_t *off, const size_t *part, int count, size_t elem = sizeof(float)) {
     for (int k = 0; k < count; ++k) { off[k] = bytes; bytes += infer_align(elem * part[k]); }
 }
+
+// the staging of inference calls (sac_trainer::act_stage, mapped pinned), owned by the trainer that launches: the first
+int act_stage_reserve(sac_trainer *t, size_t bytes) {
+    sac_trainer::ActStage &S = t->act_stage;
+    if (S.bytes >= bytes) return 0;
+    if (S.h) SAC_HIP(hipHostFree(S.h));
+    S = sac_trainer::ActStage{};
+    bytes = (bytes + 65535) & ~(size_t)65535;
+    SAC_HIP(hipHostMalloc(reinterpret_cast<void **>(&S.h), bytes, hipHostMallocMapped));
+    SAC_HIP(hipHostGetDevicePointer(reinterpret_cast<void **>(&S.d), S.h, 0));
+    S.bytes = bytes;
+    return 0;
+}
+
+// A grouped call's place in the first member's staging: the kernels' tables in front (head_bytes), then per member its
+// parts -- arrays of float, or of elem[k] bytes per element, each on a 256-byte boundary -- in the order of the caller's
+// size table.
+struct InferStage {
+    size_t off[SAC_GROUP_MAX][12], size[SAC_GROUP_MAX][12], bytes;       // size: bytes of a part
+    const sac_trainer::ActStage *S = nullptr;                            // behind reserve()
+    explicit InferStage(size_t head_bytes) : bytes(infer_align(head_bytes)) {}
+    void carve(int i, const size_t *part, int count, const size_t *elem = nullptr) {
+        for (int k = 0; k < count; ++k) {
+            size[i][k] = (elem ? elem[k] : sizeof(float)) * part[k];
+            infer_carve(bytes, off[i] + k, size[i] + k, 1, 1);
+        }
+    }
+    int reserve(sac_trainer *t0) { S = &t0->act_stage; return act_stage_reserve(t0, bytes); }
+    // part k of member i on the device (`asked` false: null); as an input, filled from `from` first (null: a kernel in
+    // front fills the part)
+    template <class T = float>
+    T *dev(int i, int k, bool asked = true) const { return asked ? reinterpret_cast<T *>(S->d + off[i][k]) : nullptr; }
+    const float *in(int i, int k, const float *from) const {
+        if (from) memcpy(S->h + off[i][k], from, size[i][k]);
+        return dev(i, k);
+    }
+    // behind the wait: the parts the caller asked for (dst not null) into its arrays
+    struct Back { void *dst; int part; };
+    void back(int i, std::initializer_list<Back> table) const {
+        for (const Back &b : table)
+            if (b.dst) memcpy(b.dst, S->h + off[i][b.part], size[i][b.part]);
+    }
+};
 
 // the slab of an acting session: the control block, then per member obs (max_rows, O) FLOAT64, eps (max_rows, A) fp32,
 // act (max_rows, A) fp32, each 256-byte aligned.  Returns the slab's size.
@@ -476,13 +606,98 @@ int infer_widest(const GenNet &N) {
     return widest;
 }
 
+// the two activation buffers of a general-step trainer's inference calls (sac_trainer::act_gen), `floats` each.  The
+// per-layer entries share them: each call ends with a wait on the stream, so they never overlap
+int act_general_reserve(sac_trainer *t, size_t floats) {
+    if (t->act_gen_floats >= floats) return 0;
+    for (float *&p : t->act_gen) { if (p) SAC_HIP(hipFree(p)); p = nullptr; }
+    t->act_gen_floats = 0;
+    floats = (floats + 16383) & ~(size_t)16383;
+    for (float *&p : t->act_gen) SAC_HIP(hipMalloc(reinterpret_cast<void **>(&p), sizeof(float) * floats));
+    t->act_gen_floats = floats;
+    return 0;
+}
+
+// a member's scratch for `slices` chains side by side: a slice is n rows x the widest hidden layer; *slice (or null)
+// gets its floats
+int infer_scratch_reserve(sac_trainer *t, int n, int widest, int slices, size_t *slice = nullptr) {
+    const size_t floats = (size_t)n * widest;
+    if (slice) *slice = floats;
+    return act_general_reserve(t, floats * slices);
+}
+
 // what every per-layer job says about layer L of net N (vec: W's rows may be fetched in 16-byte pieces)
-template <class Job>
-void infer_layer_job(Job &J, const GenNet &N, const GenLayer &L) {
+void infer_layer_job(sac::LayerJob &J, const GenNet &N, const GenLayer &L) {
     J.W = N.P + L.offW; J.b = N.P + L.offB;
     J.N = L.N; J.K = L.K;
     J.tiles_n = (L.N + AG_CT - 1) / AG_CT;
     J.vec = (L.K % 4 == 0 && L.offW % 4 == 0) ? 1 : 0;
 }
+
+// The job tables of a call's per-layer launches and the one place that writes them: table [launch][stride] of LayerJob
+// in the staging, per launch the jobs so far and their workgroups.  A chain is one net on one member's rows; a launch
+// holds layer l of every chain that has one, in the order of the chain() calls, wg0 ascending (infer_layer_find).
+struct LayerSchedule {
+    static constexpr int MAX_LAUNCHES = 2 * gen::GMAXL;               // evaluation: the policy's launches, then the critics'
+    sac::LayerJob *h = nullptr; const sac::LayerJob *d = nullptr;     // the table: host view, device view
+    int stride;                                                       // jobs of one launch, at most
+    int launches = 0, njobs[MAX_LAUNCHES] = {}, blocks[MAX_LAUNCHES] = {};
+    explicit LayerSchedule(int jobs_per_launch) : stride(jobs_per_launch) {}
+    size_t bytes(int max_launches = gen::GMAXL) const { return infer_align(sizeof(sac::LayerJob) * stride * max_launches); }
+    void bind(void *host, const void *device) {
+        h = static_cast<sac::LayerJob *>(host);
+        d = static_cast<const sac::LayerJob *>(device);
+    }
+    // One chain: net G on n rows, layer l into launch `at` + l.  The first layer reads x | x2 split at K1 (one source:
+    // x2 = x, K1 = its K); every later layer reads the layer in front of it, which went to pp[l & 1] + slice -- the
+    // ping-pong pair and this chain's slice of it; the last layer (left out without `with_last`: unit statistics stop
+    // in front of it) writes `out` with no ReLU.
+    struct Chain {
+        const GenNet &G;
+        const float *x, *x2;
+        int K1, n;
+        float *const *pp;
+        size_t slice;
+        float *out;
+        bool with_last = true;
+        int at = 0;
+    };
+    // own(J, l) sets what is the caller's: a head's kind, eps, lp, mu and ls, another Y (the chain follows it), the job's
+    // companion in a table of the caller's
+    template <class Own>
+    void chain(const Chain &c, Own own) {
+        const GenNet &G = c.G;
+        const float *x = c.x, *x2 = c.x2;
+        const int n = c.n;
+        for (int l = 0; l < (c.with_last ? G.nl : G.nl - 1); ++l) {
+            const GenLayer &L = G.L[l];
+            const bool last = l + 1 == G.nl;
+            const int launch = c.at + l;
+            sac::LayerJob &J = h[(size_t)launch * stride + njobs[launch]++];
+            J = sac::LayerJob{};
+            infer_layer_job(J, G, L);
+            J.X = x; J.X2 = x2; J.K1 = l == 0 ? c.K1 : L.K;
+            J.Y = last ? c.out : c.pp[l & 1] + c.slice;
+            J.n = n; J.relu = last ? 0 : 1; J.kind = sac::LAYER_STORE;
+            J.wg0 = blocks[launch];
+            blocks[launch] += ((n + RB - 1) / RB) * J.tiles_n;
+            launches = std::max(launches, launch + 1);
+            own(J, l);
+            x = x2 = J.Y;
+        }
+    }
+    void chain(const Chain &c) { chain(c, [](sac::LayerJob &, int) {}); }
+    // launch l of the table on t0's stream
+    int launch(void (*kernel)(const sac::LayerJob *, int), sac_trainer *t0, int l) const {
+        hipLaunchKernelGGL(kernel, dim3(blocks[l]), dim3(256), 0, t0->stream, d + (size_t)l * stride, njobs[l]);
+        SAC_HIP(hipGetLastError());
+        return 0;
+    }
+    int launch_all(void (*kernel)(const sac::LayerJob *, int), sac_trainer *t0) const {
+        for (int l = 0; l < launches; ++l)
+            if (launch(kernel, t0, l)) return -1;
+        return 0;
+    }
+};
 
 }  // namespace

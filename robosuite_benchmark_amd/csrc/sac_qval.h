@@ -21,7 +21,7 @@
 // evaluation, and row r of any call the one-row call of that row (tests/test_gpu_q_values.py).
 //
 // The kernel writes the caller's Q values and nothing else: nothing the step kernels read.  Inputs, outputs and the
-// member table live in the trainer's mapped pinned staging (act_stage_reserve, sac_act.h): a call is one launch and one
+// member table live in the trainer's mapped pinned staging (act_stage_reserve, sac_infer.h): a call is one launch and one
 // wait, without a copy call of its own.
 //
 // General-step trainers (hidden sizes beyond the fused kernels') are out of scope here: these entries refuse them.  Their

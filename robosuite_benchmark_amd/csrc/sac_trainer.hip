@@ -2011,8 +2011,8 @@ struct sac_trainer {
     bool mirror_valid = false;
     // device acting (sac_act.h): observations, eps, actions and the member table of a call, in mapped pinned host memory
     struct ActStage { char *h = nullptr, *d = nullptr; size_t bytes = 0; } act_stage;
-    // general-step device acting (sac_act_general.h) and Q evaluation (sac_qval_general.h): the activations between two
-    // layer launches ping-pong between these
+    // general-step device inference, one launch per layer (act_general_reserve, sac_infer.h): the activations between
+    // two layer launches ping-pong between these
     float *act_gen[2] = {nullptr, nullptr}; size_t act_gen_floats = 0;
     // fused step (k_abc, sac_fused.h; k_chain8<.., BWD>, sac_chain.h): launches A + B + C as one launch with in-launch
     // hand-offs.  Starts as plan.fused; a give-up or sac_trainer_set_xcd_mask clears it for good (trainer_drop_fused).

@@ -1,15 +1,17 @@
 // Per-unit statistics of the hidden layers for general-step trainers: sac_unit_moments_general[_many] (included by
 // sac_trainer.hip behind sac_units.h).
 //
-// No forward kernel of its own: a hidden layer of any net -- the policy's too, with K1 = K -- is a QvalLayerJob, "one
-// layer Y = relu(X W^T + b) with a split input".  Per depth l the entry builds the jobs of every (member, selected net)
-// that has a HIDDEN layer l -- no output layer, no head --, launches k_qval_layer unchanged, then k_unit_moments on that
-// depth's outputs, then depth l + 1: two launches per depth on the first member's stream and one wait at the end.
+// No forward kernel of its own: a hidden layer of any net -- the policy's too, with K1 = K -- is a LAYER_STORE job, "one
+// layer Y = relu(X W^T + b) with a split input".  Per (member, selected net) the entry appends one chain WITHOUT its last
+// layer to a LayerSchedule (sac_infer.h) -- no output layer, no head -- and gives every job its UnitJob in the same slot
+// of the reducer's table; per depth l it launches k_qval_layer unchanged, then k_unit_moments on that depth's outputs,
+// then depth l + 1: two launches per depth on the first member's stream and one wait at the end.
 //
-//   Y       without io->activations the trainer's act_gen ping-pong pair (act_general_reserve), one slice per selected
+//   Y       without io->activations the trainer's act_gen ping-pong pair (infer_scratch_reserve), one slice per selected
 //           net of n x the widest hidden layer selected: stream order keeps reducer l in front of layer l + 2's writes.
 //           With io->activations the staging's output block itself, (n, N_l) row-major per net and layer: no copy kernel.
-//   records the mapped staging, per selected net in ascending id, per hidden layer: SAC_UNIT_FIELDS_N arrays of N_l
+//   records the mapped staging (InferStage, a part of doubles), per selected net in ascending id, per hidden layer:
+//           SAC_UNIT_FIELDS_N arrays of N_l
 //
 // The activations are k_qval_layer's (the policy's: the same tile, so k_act_layer's values): row independence, grouped ==
 // solo and n rows == n one-row calls carry over, and the reducer's order depends on n alone.  The entry writes the
@@ -24,93 +26,70 @@ int sac_unit_moments_general_many(sac_trainer_t *const *trainers, int n_trainers
                           "reduce"};
     if (int rc = units_admit(E, trainers, n_trainers, n_rows, io)) return rc;
     sac_trainer *t0 = trainers[0];
-    // staging: the two job tables, then per member obs (n, O), act (n, A), the records, the activations asked for
-    const size_t tab_q = 0, tab_u = infer_align(sizeof(QvalLayerJob) * UNIT_JOBS * gen::GMAXL);
-    size_t bytes = tab_u + infer_align(sizeof(UnitJob) * UNIT_JOBS * gen::GMAXL);
-    size_t off[SAC_GROUP_MAX][4] = {}, slice[SAC_GROUP_MAX] = {}, units[SAC_GROUP_MAX] = {};
-    int launches = 0;
+    // the staging: the layer jobs' tables and the reducer's (slot for slot the same jobs), then per member obs (n, O),
+    // act (n, A), the records (double), the activations asked for
+    enum { P_OBS, P_ACT, P_REC, P_TAPS, NPART };
+    LayerSchedule LS(UNIT_JOBS);
+    const size_t tab_u = LS.bytes();
+    InferStage ST(tab_u + infer_align(sizeof(UnitJob) * UNIT_JOBS * gen::GMAXL));
+    size_t slice[SAC_GROUP_MAX] = {};
     for (int i = 0; i < n_trainers; ++i) {
         const sac_trainer *t = trainers[i];
-        if (n_rows[i] == 0) continue;
         const size_t n = (size_t)n_rows[i];
+        size_t units = 0;
         int widest = 1;
-        for (int k = 0; k < UNIT_NETS; ++k) {
+        for (int k = 0; n && k < UNIT_NETS; ++k) {
             if (!(io[i].nets >> k & 1u)) continue;
             const GenNet &G = t->gen->net[k];
-            for (int l = 0; l + 1 < G.nl; ++l) units[i] += (size_t)G.L[l].N;
+            for (int l = 0; l + 1 < G.nl; ++l) units += (size_t)G.L[l].N;
             widest = std::max(widest, infer_widest(G));
-            launches = std::max(launches, G.nl - 1);
         }
-        slice[i] = n * widest;
-        bytes = infer_align(bytes);
-        off[i][0] = bytes; bytes += infer_align(sizeof(float) * n * t->O);
-        off[i][1] = bytes; bytes += infer_align(sizeof(float) * n * t->A);
-        off[i][2] = bytes; bytes += infer_align(sizeof(double) * SAC_UNIT_FIELDS_N * units[i]);
-        off[i][3] = bytes; bytes += io[i].activations ? infer_align(sizeof(float) * n * units[i]) : 0;
-        if (!io[i].activations && act_general_reserve(trainers[i], slice[i] * __builtin_popcount(io[i].nets))) return -1;
+        const size_t part[NPART] = {n * t->O, n * t->A, SAC_UNIT_FIELDS_N * units, n && io[i].activations ? n * units : 0};
+        const size_t elem[NPART] = {sizeof(float), sizeof(float), sizeof(double), sizeof(float)};
+        ST.carve(i, part, NPART, elem);
+        if (n && !io[i].activations &&
+            infer_scratch_reserve(trainers[i], n_rows[i], widest, __builtin_popcount(io[i].nets), &slice[i])) return -1;
     }
-    if (act_stage_reserve(t0, bytes)) return -1;
-    const sac_trainer::ActStage &S = t0->act_stage;
-    QvalLayerJob *qtab = reinterpret_cast<QvalLayerJob *>(S.h + tab_q);
-    UnitJob *utab = reinterpret_cast<UnitJob *>(S.h + tab_u);
-    int njobs[gen::GMAXL] = {}, qblocks[gen::GMAXL] = {}, ublocks[gen::GMAXL] = {};
+    if (ST.reserve(t0)) return -1;
+    LS.bind(ST.S->h, ST.S->d);
+    UnitJob *utab = reinterpret_cast<UnitJob *>(ST.S->h + tab_u);
+    int ublocks[gen::GMAXL] = {};
     for (int i = 0; i < n_trainers; ++i) {
         const sac_trainer *t = trainers[i];
         if (n_rows[i] == 0) continue;
         const size_t n = (size_t)n_rows[i];
-        const float *o = reinterpret_cast<const float *>(S.d + off[i][0]);
-        const float *a = reinterpret_cast<const float *>(S.d + off[i][1]);
-        double *rec = reinterpret_cast<double *>(S.d + off[i][2]);
-        float *taps = io[i].activations ? reinterpret_cast<float *>(S.d + off[i][3]) : nullptr;
+        const float *o = ST.in(i, P_OBS, io[i].obs), *a = ST.in(i, P_ACT, (io[i].nets & UNIT_Q_NETS) ? io[i].act : nullptr);
+        double *rec = ST.dev<double>(i, P_REC);
+        float *taps = ST.dev(i, P_TAPS, io[i].activations != nullptr);
         int s = 0;
         for (int k = 0; k < UNIT_NETS; ++k) {
             if (!(io[i].nets >> k & 1u)) continue;
-            const GenNet &G = t->gen->net[k];
             const bool q = (UNIT_Q_NETS >> k & 1u) != 0;
-            const float *x = o, *x2 = q ? a : o;
-            for (int l = 0; l + 1 < G.nl; ++l) {
-                const GenLayer &L = G.L[l];
-                const size_t slot = (size_t)l * UNIT_JOBS + njobs[l];
-                QvalLayerJob &J = qtab[slot];
-                infer_layer_job(J, G, L);
-                J.X = x; J.X2 = x2;
-                J.Y = taps ? taps : t->act_gen[l & 1] + (size_t)s * slice[i];
-                J.K1 = (l == 0 && q) ? t->O : L.K; J.n = n_rows[i];
-                J.wg0 = qblocks[l];
-                J.relu = 1;
-                qblocks[l] += ((n_rows[i] + RB - 1) / RB) * J.tiles_n;
-                UnitJob &U = utab[slot];
-                U.X = J.Y; U.out = rec; U.ld = L.N; U.N = L.N; U.n = n_rows[i];
+            // the hidden layers only; with activations a layer writes its (n, N_l) block of the staging instead of the scratch
+            LS.chain({t->gen->net[k], o, q ? a : o, t->O, n_rows[i], t->act_gen, taps ? 0 : s * slice[i], nullptr, false},
+                     [&](sac::LayerJob &J, int l) {
+                if (taps) { J.Y = taps; taps += n * J.N; }
+                UnitJob &U = utab[(size_t)l * UNIT_JOBS + LS.njobs[l] - 1];       // the job's own slot
+                U.X = J.Y; U.out = rec; U.ld = J.N; U.N = J.N; U.n = n_rows[i];
                 U.wg0 = ublocks[l];
-                ublocks[l] += (L.N + UM_COLS - 1) / UM_COLS;
-                njobs[l] += 1;
-                x = x2 = J.Y;
-                rec += (size_t)SAC_UNIT_FIELDS_N * L.N;
-                if (taps) taps += n * L.N;
-            }
+                ublocks[l] += (J.N + UM_COLS - 1) / UM_COLS;
+                rec += (size_t)SAC_UNIT_FIELDS_N * J.N;
+            });
             s += 1;
         }
-        memcpy(S.h + off[i][0], io[i].obs, sizeof(float) * n * t->O);
-        if (io[i].nets & UNIT_Q_NETS) memcpy(S.h + off[i][1], io[i].act, sizeof(float) * n * t->A);
     }
-    for (int l = 0; l < launches; ++l) {
-        hipLaunchKernelGGL(k_qval_layer, dim3(qblocks[l]), dim3(256), 0, t0->stream,
-                           reinterpret_cast<const QvalLayerJob *>(S.d + tab_q) + (size_t)l * UNIT_JOBS, njobs[l]);
-        SAC_HIP(hipGetLastError());
-        if (units_launch(t0, reinterpret_cast<const UnitJob *>(S.d + tab_u) + (size_t)l * UNIT_JOBS, njobs[l], ublocks[l])) return -1;
-    }
+    const UnitJob *d_utab = reinterpret_cast<const UnitJob *>(ST.S->d + tab_u);
+    for (int l = 0; l < LS.launches; ++l)
+        if (LS.launch(k_qval_layer, t0, l) || units_launch(t0, d_utab + (size_t)l * UNIT_JOBS, LS.njobs[l], ublocks[l])) return -1;
     if (wait_trainer_stream(t0)) return -1;
-    for (int i = 0; i < n_trainers; ++i) {
-        if (n_rows[i] == 0) continue;
-        memcpy(io[i].moments, S.h + off[i][2], sizeof(double) * SAC_UNIT_FIELDS_N * units[i]);
-        if (io[i].activations) memcpy(io[i].activations, S.h + off[i][3], sizeof(float) * (size_t)n_rows[i] * units[i]);
-    }
+    for (int i = 0; i < n_trainers; ++i)
+        if (n_rows[i] > 0) ST.back(i, {{io[i].moments, P_REC}, {io[i].activations, P_TAPS}});
     return 0;
 }
 
 int sac_unit_moments_general(sac_trainer_t *t, int64_t n, sac_units_io_t *io) {
     SAC_REQUIRE(t && io, "bad arguments to sac_unit_moments_general");
-    SAC_REQUIRE(n >= 1 && n <= ACT_MAX_ROWS, "sac_unit_moments_general: %lld rows (1..%d per call)", (long long)n, ACT_MAX_ROWS);
+    if (int rc = infer_admit_solo("sac_unit_moments_general", n)) return rc;
     const int32_t rows = (int32_t)n;
     return sac_unit_moments_general_many(&t, 1, &rows, io);
 }

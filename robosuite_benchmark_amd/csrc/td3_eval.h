@@ -111,7 +111,7 @@ int td3_evaluate_many(sac_trainer_t *const *trainers, int n_trainers, const int3
     sac_trainer *t0 = trainers[0];
 
     enum { P_OBS, P_ACT, P_REW, P_TERM, P_NOBS, P_EPS, P_ROWS, P_A_PI, P_A_TARGET, P_A_SMOOTH, NPART };
-    EvalStage ST(sizeof(Td3EvalMember) * SAC_GROUP_MAX);
+    InferStage ST(sizeof(Td3EvalMember) * SAC_GROUP_MAX);
     for (int i = 0; i < n_trainers; ++i) {
         const sac_trainer *t = trainers[i];
         const size_t n = (size_t)n_rows[i], nO = n * t->O, nA = n * t->A;
@@ -147,7 +147,7 @@ int td3_evaluate_many(sac_trainer_t *const *trainers, int n_trainers, const int3
 
 int td3_evaluate(sac_trainer_t *t, int64_t n, td3_eval_io_t *io) {
     SAC_REQUIRE(t && io, "bad arguments to td3_evaluate");
-    if (int rc = eval_admit_solo("td3_evaluate", n)) return rc;
+    if (int rc = infer_admit_solo("td3_evaluate", n)) return rc;
     const int32_t rows = (int32_t)n;
     return td3_evaluate_many(&t, 1, &rows, io);
 }

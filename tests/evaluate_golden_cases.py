@@ -89,3 +89,13 @@ def run_case(members, case):
         if stats:
             got[f"m{m}.stats"] = np.frombuffer(bytes(sts[m]), np.float64).copy()
     return got
+
+
+def make_all_members():
+    """make_members of both objectives, as run() takes them."""
+    return {False: make_members(False), True: make_members(True)}
+
+
+def run(all_members, case):
+    """run_case on the members of the case's objective."""
+    return run_case(all_members[case[0] == "td3_evaluate_many"], case)
