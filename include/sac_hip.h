@@ -342,6 +342,15 @@ int sac_measure_peaks(int device, float out[4]);
  * trained net 0..2 the counts of P, PT, MT, VT (general step: P, M, V), then of P for each target net (all 0 by
  * invariant).  Returns the element count, <0 on error. */
 int64_t sac_debug_fetch(sac_trainer_t *t, const char *name, float *out, int64_t cap);
+/* Test hook: put a trainer that runs a fused step (kinds 1 and 4) at launch number `seq`.  A fused launch carries the
+ * number of fused launches of its trainer so far (a 32-bit count that wraps), and the workgroups of a launch wait for
+ * hand-off counters to reach fixed multiples of it modulo 2^32 ("The hand-off protocol").  The call settles
+ * the trainer like the state getters and then leaves it exactly as `seq` completed launches would: the launch number,
+ * every counter at its units x seq modulo 2^32, every tagged word tagged seq, the give-up word clear.  Parameters,
+ * optimizer state and step counts are untouched -- results do not depend on the launch number, which is what
+ * tests/test_gpu_launch_numbers.py checks around every power of two the multiples cross.  SAC_FUSED_TEST_STALL=n counts
+ * from the number set here: it stalls launch seq + n.  A trainer on any other step is refused (-1, sac_last_error). */
+int sac_debug_set_launch_number(sac_trainer_t *t, uint32_t seq);
 
 /* policy.get_action(obs) on the HOST with weights mirrored from the device (acting path,
  * /root/reference/util/rlkit_custom.py:437; MakeDeterministic => tanh(mean)).

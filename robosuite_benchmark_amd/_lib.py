@@ -193,6 +193,7 @@ SYMBOLS = {
     "sac_buffer_set_xcd_mask": (C.c_int, [_P, C.c_uint]),
     "sac_trainer_set_xcd_mask": (C.c_int, [_P, C.c_uint]),
     "sac_debug_fetch": (C.c_int64, [_P, C.c_char_p, _P, C.c_int64]),
+    "sac_debug_set_launch_number": (C.c_int, [_P, C.c_uint32]),
     "sac_policy_mirror": (C.c_int, [_P]),
     "sac_policy_act": (C.c_int, [_P, _P, C.c_int, _P, _P]),
     "sac_policy_act_device": (C.c_int, [_P, C.c_int64, _P, C.c_int, _P, _P]),

@@ -569,7 +569,7 @@ __global__ __launch_bounds__(512) void k_chain8(Dev d, const float *__restrict__
         if constexpr (BWD) {
             handoff_publish(cnt_qa + (size_t)rb * CNT_STRIDE);
             // the target values of this row-block and the log-pi sums of all: then Q1's critic backward block
-            handoff_wait_multi<16>(2, cnt_tq + (size_t)rb * CNT_STRIDE, sa.seq, cnt_lp, (unsigned)d.NB * sa.seq, cnt_lp, (unsigned)d.NB * sa.seq,
+            handoff_wait_multi<16>(2, cnt_tq + (size_t)rb * CNT_STRIDE, CHAIN_UNITS_RB * sa.seq, cnt_lp, chain_units_lp(d.NB) * sa.seq, cnt_lp, chain_units_lp(d.NB) * sa.seq,
                                d.abort_flag, &s_ok);
             lds_barrier();
             if (!s_ok) return;
@@ -694,7 +694,7 @@ __global__ __launch_bounds__(512) void k_chain8(Dev d, const float *__restrict__
         if constexpr (BWD) {
             handoff_publish(cnt_tq + (size_t)rb * CNT_STRIDE);
             // item C's Q2(s, a) pass of this row-block (long out) and the log-pi sums of all: then Q2's critic backward block
-            handoff_wait_multi<16>(2, cnt_qa + (size_t)rb * CNT_STRIDE, sa.seq, cnt_lp, (unsigned)d.NB * sa.seq, cnt_lp, (unsigned)d.NB * sa.seq,
+            handoff_wait_multi<16>(2, cnt_qa + (size_t)rb * CNT_STRIDE, CHAIN_UNITS_RB * sa.seq, cnt_lp, chain_units_lp(d.NB) * sa.seq, cnt_lp, chain_units_lp(d.NB) * sa.seq,
                                d.abort_flag, &s_ok);
             lds_barrier();
             if (!s_ok) return;
@@ -747,7 +747,7 @@ __global__ __launch_bounds__(512) void k_chain8(Dev d, const float *__restrict__
     if constexpr (BWD) {
         if (qi == 1) { handoff_publish(cnt_ac + (size_t)rb * CNT_STRIDE); return; }
         // P0: the other twin's q_new and action gradient, the log-pi sums of all row-blocks: then the policy backward block
-        handoff_wait_multi<16>(2, cnt_ac + (size_t)rb * CNT_STRIDE, sa.seq, cnt_lp, (unsigned)d.NB * sa.seq, cnt_lp, (unsigned)d.NB * sa.seq,
+        handoff_wait_multi<16>(2, cnt_ac + (size_t)rb * CNT_STRIDE, CHAIN_UNITS_RB * sa.seq, cnt_lp, chain_units_lp(d.NB) * sa.seq, cnt_lp, chain_units_lp(d.NB) * sa.seq,
                            d.abort_flag, &s_ok);
         asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
         lds_barrier();

@@ -26,7 +26,12 @@
 // producer: payload with agent-scope write-through stores (sc1) -> every storing wave s_waitcnt vmcnt(0) -> workgroup
 // barrier -> ONE lane: agent-scope atomic add on a counter; consumer: one lane polls the counter with sc1 loads (plus
 // s_sleep), workgroup barrier, then loads.  Counters are monotonic (targets are multiples of the launch number:
-// no reset, no ABA).  Every handed-off datum lives in 128-B lines that ONE producer block writes and nobody reads
+// no reset, no ABA) -- modulo 2^32: after launch n a counter holds units * n mod 2^32 (the units per launch: sac_step_plan.h),
+// the launch number itself wraps through 0xffffffff to 0, and a wait compares (int)(counter - target) >= 0, which is right
+// while a consumer is less than 2^31 / units launches away from its producer -- it is in the SAME launch.  So no value of a
+// counter, of a target or of a tag may stand for "nothing": an early look that was not taken is said with a flag, never
+// with a 0 (tests/test_gpu_launch_numbers.py runs the launches across every power of two the targets cross).
+// Every handed-off datum lives in 128-B lines that ONE producer block writes and nobody reads
 // before the counter says so, so neither a CU's L1 nor an XCD's L2 can hold a stale copy of them (both are
 // invalidated at dispatch); 4-byte consumer loads are sc1 (L1-bypassing) on top of that.  The one single-word hand-off -- a
 // row-block's sum of log pi, 16 words for the entropy coefficient of every phase C -- travels as {launch number, value} in ONE
@@ -40,7 +45,7 @@
 // at least 16*NB CUs.  Fused launches of different trainers in one process are serialised by the host.
 #pragma once
 
-constexpr int CNT_STRIDE = 32;                                  // unsigned per counter: one 128-B line each
+constexpr int CNT_STRIDE = SYNC_STRIDE;                         // unsigned per counter: one 128-B line each (sac_step_plan.h)
 constexpr unsigned long long HANDOFF_TIMEOUT_TICKS = 5000000ull;   // s_memrealtime ticks (100 MHz): 50 ms
 // (FUSED_RED, the floats of split-K scratch: sac_step_plan.h)
 
@@ -104,19 +109,20 @@ __device__ __forceinline__ int tagged_wait(const unsigned long long *p, unsigned
 // s_lp[0 .. NB-1] in LDS): still one memory round trip per poll iteration for all of them
 // (peek: what multi_lp_peek loaded for this lane some time ago -- an early look that usually finds everything there, so that the
 //  wait costs no memory round trip: 0.6-0.8 us at the start of the critic chain's phase C, whose conditions have been true for a
-//  microsecond by then; 0 = no early look)
+//  microsecond by then; have_peek = false: no early look was taken and `peek` means nothing -- every value of it, 0 included, is
+//  a counter value or a tagged word some launch number matches)
 __device__ __forceinline__ void handoff_wait_multi_lp(int n, const unsigned *c0, unsigned t0, const unsigned *c1, unsigned t1,
                                                       const unsigned long long *lp_tag, int NB, unsigned seq, unsigned *abort_flag,
-                                                      int *s_ok, float *s_lp, unsigned long long peek = 0ull) {
+                                                      int *s_ok, float *s_lp, bool have_peek = false, unsigned long long peek = 0ull) {
     if (threadIdx.x < 64) {
         const int l = threadIdx.x;
         int ok = 1;
         if (l < n) {
             const unsigned t = l == 0 ? t0 : t1;
-            if ((int)((unsigned)peek - t) < 0) ok = handoff_wait(l == 0 ? c0 : c1, t, abort_flag);
+            if (!have_peek || (int)((unsigned)peek - t) < 0) ok = handoff_wait(l == 0 ? c0 : c1, t, abort_flag);
         } else if (l >= 16 && l < 16 + NB) {
             float v = __builtin_bit_cast(float, (unsigned)peek);
-            if ((unsigned)(peek >> 32) != seq) ok = tagged_wait(lp_tag + (l - 16), seq, abort_flag, &v);
+            if (!have_peek || (unsigned)(peek >> 32) != seq) ok = tagged_wait(lp_tag + (l - 16), seq, abort_flag, &v);
             s_lp[l - 16] = v;
         }
         const unsigned long long all = __ballot(ok != 0);
@@ -263,6 +269,7 @@ __global__ __launch_bounds__(256) void k_abc(Dev d, const float *__restrict__ S,
     const int n0 = SW * part + 16 * wave;                     // this wave's tile of the split layers
     // counters (one per 128-B line): head[side][rb] (policy chain, phase A), qa[rb] (critic chain, phase A), tq[rb] (policy
     // chains, phase B), ac[rb] (critic chain, phase B incl. the actor tail); the NB row-block sums of log pi need none: tagged words
+    // (the lines of the regions: sync_region_line, sac_step_plan.h -- head 0, qa 2 NB, tq 3 NB, ac 4 NB, zx 5 NB + 2, lp_tag 11 NB + 2)
     unsigned *cnt_head = d.cnt, *cnt_qa = d.cnt + (size_t)2 * NB * CNT_STRIDE, *cnt_tq = d.cnt + (size_t)3 * NB * CNT_STRIDE,
              *cnt_ac = d.cnt + (size_t)4 * NB * CNT_STRIDE;
     unsigned *cnt_zx = d.cnt + (size_t)(5 * NB + 2) * CNT_STRIDE;   // [6 chains][NB]: the exchange of the split first layers (WIDE)
@@ -279,7 +286,10 @@ __global__ __launch_bounds__(256) void k_abc(Dev d, const float *__restrict__ S,
     float eps = 0.f;                     // the N(0,1) draw of phase B's rsample (made in phase A, below)
     f32x4 keep1[4], zkeep[4];
     float bv1[1], w3[4];
-    unsigned peek = 0u;                  // (thread 0 of a critic-chain block: early look at head[s][rb])
+    unsigned peek = 0u;                  // (thread 0 of a critic-chain block: early look at head[s][rb]; taken iff have_peek)
+    // (SAC: phase A always runs -- skip_a is a TD3 matter -- so a critic-chain block always gets to the look; the TD3 critic
+    //  pass has no head wait on its critic chain and takes none.  Said as a flag: no value of `peek` means "not taken".)
+    const bool have_peek = (MODE == M_SAC) && isq;
     // TD3 critic pass: the online policy on s runs only when an actor pass follows (it reads this chain's head partials)
     const bool skip_a = (MODE == M_TD3_CRITIC) && !isq && net == 0 && !(sa.pad2 & 4u);
     if (!skip_a) {
@@ -339,7 +349,7 @@ __global__ __launch_bounds__(256) void k_abc(Dev d, const float *__restrict__ S,
         if constexpr (WIDE) {   // first layer: this part's quarter, then the exchange with the other three parts
             const int chain = isq ? net : 2 + net;
             if (!split_first_layer(rq, X0, KLQ, K0 >> 4, bq, d.zx + (size_t)(chain * NB + rb) * (RB * H),
-                                   cnt_zx + (size_t)(chain * NB + rb) * CNT_STRIDE, 4u * seq, d.abort_flag, &s_ok, part, zkeep)) return;
+                                   cnt_zx + (size_t)(chain * NB + rb) * CNT_STRIDE, ABC_UNITS_ZX * seq, d.abort_flag, &s_ok, part, zkeep)) return;
 #pragma unroll
             for (int t = 0; t < 4; ++t)
 #pragma unroll
@@ -381,7 +391,7 @@ __global__ __launch_bounds__(256) void k_abc(Dev d, const float *__restrict__ S,
         } else {        // partial Q_i(s, a) over these 64 columns
             // (early look at the head counter of phase B: the policy chains publish ~1 us before this chain gets here, so the
             //  wait below usually finds this answer waiting and costs no round trip)
-            if (MODE == M_SAC && threadIdx.x == 0) peek = __hip_atomic_load(cnt_head + (size_t)rb * CNT_STRIDE, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+            if (have_peek && threadIdx.x == 0) peek = __hip_atomic_load(cnt_head + (size_t)rb * CNT_STRIDE, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
             float s = 0.f;
 #pragma unroll
             for (int u = 0; u < 4; ++u) s += XS[lds_off(row, a + 16 * u, SW)] * w3[u];
@@ -414,7 +424,7 @@ __global__ __launch_bounds__(256) void k_abc(Dev d, const float *__restrict__ S,
     // phase B: requests that do not depend on the hand-off first, then the wait
     // =========================================================================================================
     WRing<1, 8> rc;                      // critic chain: the transposed W2 slice of the critic backward (phase C)
-    unsigned long long peek_c = 0ull;    // critic chain, wave 0: early look at phase C's counters / tagged words (multi_lp_peek)
+    unsigned long long peek_c = 0ull;    // critic chain, wave 0, SAC: early look at phase C's counters / tagged words (multi_lp_peek)
     if (MODE == M_SAC || !isq) {         // (TD3 critic pass: the critic chain goes straight on to phase C)
     const int p4 = isq ? net : 2 + net;                       // Q1, Q2 on (s, a_new) | T1, T2 on (s', a')
     const int side = isq ? 0 : 1, pass = 2 + p4;
@@ -440,7 +450,8 @@ __global__ __launch_bounds__(256) void k_abc(Dev d, const float *__restrict__ S,
         else rows2.issue(d.KQ, S + SL.off_nobs + (size_t)row0 * O, O, O, nullptr, 0, 0, 0);
     }
     if (threadIdx.x == 0)
-        s_ok = (isq && (int)(peek - 4u * seq) >= 0) ? 1 : handoff_wait(cnt_head + (size_t)(side * NB + rb) * CNT_STRIDE, 4u * seq, d.abort_flag);
+        s_ok = (have_peek && (int)(peek - ABC_UNITS_HEAD * seq) >= 0)
+                   ? 1 : handoff_wait(cnt_head + (size_t)(side * NB + rb) * CNT_STRIDE, ABC_UNITS_HEAD * seq, d.abort_flag);
     if (isq) asm volatile("s_waitcnt vmcnt(0)" ::: "memory");          // phase A's stores (and two small loads): ~1 us old
     lds_barrier();
     if (!s_ok) return;
@@ -546,7 +557,7 @@ __global__ __launch_bounds__(256) void k_abc(Dev d, const float *__restrict__ S,
             hidden_epilogue<4>(acc0, 64 * wave, 16, bv0b, X1, H, keep1);
         } else {
             if (!split_first_layer(rq2, X0, KLQ, KS0, bq2, d.zx + (size_t)((4 + net) * NB + rb) * (RB * H),
-                                   cnt_zx + (size_t)((4 + net) * NB + rb) * CNT_STRIDE, 4u * seq, d.abort_flag, &s_ok, part, acc0)) return;
+                                   cnt_zx + (size_t)((4 + net) * NB + rb) * CNT_STRIDE, ABC_UNITS_ZX * seq, d.abort_flag, &s_ok, part, acc0)) return;
 #pragma unroll
             for (int t = 0; t < 4; ++t)
 #pragma unroll
@@ -657,8 +668,8 @@ __global__ __launch_bounds__(256) void k_abc(Dev d, const float *__restrict__ S,
         const int k = threadIdx.x;
         // the three counters in ONE round trip, with nothing of this block in flight; the target partials have usually been
         // out for a microsecond by now (the policy chains have no actor tail)
-        handoff_wait_multi_lp(2, cnt_tq + (size_t)rb * CNT_STRIDE, 8u * seq, cnt_qa + (size_t)rb * CNT_STRIDE, 8u * seq, lp_tag,
-                              (MODE == M_SAC) ? NB : 0, seq, d.abort_flag, &s_ok, s_lp, peek_c);
+        handoff_wait_multi_lp(2, cnt_tq + (size_t)rb * CNT_STRIDE, ABC_UNITS_TQ * seq, cnt_qa + (size_t)rb * CNT_STRIDE, ABC_UNITS_QA * seq,
+                              lp_tag, (MODE == M_SAC) ? NB : 0, seq, d.abort_flag, &s_ok, s_lp, MODE == M_SAC, peek_c);
         lds_barrier();
         if (!s_ok) return;
         STAMP(0, 8);
@@ -753,7 +764,7 @@ __global__ __launch_bounds__(256) void k_abc(Dev d, const float *__restrict__ S,
         const float b3a = sload(d.P[1] + oB3), b3b = sload(d.P[2] + oB3);
         SB();
         for (int e = threadIdx.x; e < RB * 64; e += 256) XH[e] = 0.f;
-        handoff_wait_multi_lp(1, cnt_tq + (size_t)rb * CNT_STRIDE, 8u * seq, nullptr, 0u, lp_tag, NB, seq,
+        handoff_wait_multi_lp(1, cnt_tq + (size_t)rb * CNT_STRIDE, ABC_UNITS_TQ * seq, nullptr, 0u, lp_tag, NB, seq,
                               d.abort_flag, &s_ok, s_lp);      // the policy chains' phases A + B (pi(s)'s activations), the log-pi sums
         lds_barrier();
         if (!s_ok) return;
@@ -763,7 +774,7 @@ __global__ __launch_bounds__(256) void k_abc(Dev d, const float *__restrict__ S,
         f32x4 h1v[1];
         h1v[0] = ld4(d.PH1T + frag_off(nt + c, row0 + 4 * g, B));
         const float alpha = alpha_step_v(d.ctl, s_lp, NB, d.Bt, d.target_entropy, d.alpha_lr, d.auto_alpha, sa.bc1, sa.bc2s).alpha;
-        if (threadIdx.x == 0) s_ok = handoff_wait(cnt_ac + (size_t)rb * CNT_STRIDE, 8u * seq, d.abort_flag);   // the eight actor tails
+        if (threadIdx.x == 0) s_ok = handoff_wait(cnt_ac + (size_t)rb * CNT_STRIDE, ABC_UNITS_AC * seq, d.abort_flag);   // the eight actor tails
         lds_barrier();
         if (!s_ok) return;
         STAMP(0, 8);

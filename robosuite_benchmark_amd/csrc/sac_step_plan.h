@@ -31,7 +31,8 @@ struct StepEnv {
     EnvInt wide_min_kq;           // SAC_WIDE_MIN_KQ: the narrowest "wide" first layer (tuning experiments only)
     bool dw_form_loop = false;    // SAC_DW_FORM=loop: the weight-gradient launch keeps its loop form (ablations, tests)
     EnvInt fused;                 // SAC_FUSED=0: the four-launch step (co-tenant processes on one GPU; ablations)
-    EnvInt fused_test_stall;      // SAC_FUSED_TEST_STALL=<n>: the n-th fused launch loses a producer (tests)
+    EnvInt fused_test_stall;      // SAC_FUSED_TEST_STALL=<n>: the n-th fused launch loses a producer (tests; counted from the
+                                  // launch number sac_debug_set_launch_number last set, 0 without it: test_stall_hits)
     EnvInt chain;                 // SAC_CHAIN=0 / 1: never / wherever it can run (A/B comparisons)
     EnvInt chain8;                // SAC_CHAIN8=0: the four-wave k_chain (A/B comparisons)
     EnvInt bwd8;                  // SAC_BWD8=0: the four-wave backward launch at column split 1 (A/B comparisons)
@@ -156,5 +157,89 @@ static inline StepPlan step_plan(int obs_dim, int act_dim, int batch, int algo, 
     }
     return P;
 }
+
+// ---- The hand-off words of the fused launches (k_abc: sac_fused.h; k_chain8<.., BWD>: sac_chain.h) ----------------------
+// One allocation per trainer (sac_trainer::d_sync), cut into 128-byte lines of SYNC_STRIDE words; a counter is the first
+// word of its line.  INVARIANT: after launch number n of a trainer every counter holds units * n modulo 2^32, where
+// `units` is how often one launch adds to it, and a consumer of launch n waits for (int)(counter - units * n) >= 0.  Every
+// value of a counter, of a launch number and of a tag is an ordinary value: none is reserved to mean "nothing".  The
+// kernels take their targets from the constants below and the host's test hook (sac_debug_set_launch_number) fills the
+// words from the same table, so the two cannot drift apart; tests/test_sync_words_host.py checks table and fill.
+constexpr int SYNC_STRIDE = 32;                   // unsigned words per line
+enum SyncRegion {
+    SYNC_HEAD = 0,      // [2][NB]  k_abc: a policy chain's head partials of (side, row-block)
+    SYNC_QA,            // [NB]     critic-chain phase A (k_abc) / item C's Q2 pass (k_chain8)
+    SYNC_TQ,            // [NB]     the target partials
+    SYNC_AC,            // [NB]     the actor tails (k_abc, SAC) / item P1 (k_chain8)
+    SYNC_LP,            // [1]      k_chain8: the log-pi sums of every P0 item
+    SYNC_ABORT,         // [1]      the sticky give-up word
+    SYNC_ZX,            // [6][NB]  k_abc, wide first layers: the exchange of the split first layers
+    SYNC_LP_TAG,        // [1]      k_abc: NB (<= 16) 8-byte words {value, launch number} -- the row-block sums of log pi
+    SYNC_REGIONS
+};
+enum FusedKernel { FUSED_ABC_SAC = 0, FUSED_ABC_TD3 = 1, FUSED_CHAIN8 = 2 };
+
+// per-launch units, named once
+constexpr unsigned ABC_UNITS_HEAD = 4;            // the four column parts of a policy chain
+constexpr unsigned ABC_UNITS_QA = 8;              // two twins x four parts
+constexpr unsigned ABC_UNITS_TQ = 8;              // two policy chains x four parts
+constexpr unsigned ABC_UNITS_AC = 8;              // two twins x four parts (SAC; the TD3 critic pass has no actor tail: 0)
+constexpr unsigned ABC_UNITS_ZX = 4;              // the four parts of a chain (wide first layers only)
+constexpr unsigned CHAIN_UNITS_RB = 1;            // k_chain8: one item per row-block counter
+constexpr unsigned chain_units_lp(int NB) { return (unsigned)NB; }          // k_chain8: every P0 item (constexpr: host and kernels)
+
+static inline int sync_region_lines(int region, int NB) {
+    switch (region) {
+    case SYNC_HEAD: return 2 * NB;
+    case SYNC_QA: case SYNC_TQ: case SYNC_AC: return NB;
+    case SYNC_ZX: return 6 * NB;
+    case SYNC_LP: case SYNC_ABORT: case SYNC_LP_TAG: return 1;
+    default: return 0;
+    }
+}
+// first line of a region: the regions lie back to back in the order of the enum
+static inline int sync_region_line(int region, int NB) {
+    int at = 0;
+    for (int r = 0; r < region; ++r) at += sync_region_lines(r, NB);
+    return at;
+}
+static inline size_t sync_words(int NB) { return (size_t)SYNC_STRIDE * (size_t)sync_region_line(SYNC_REGIONS, NB); }
+
+// what ONE launch of `kernel` adds to each counter of `region` (wide: k_abc's split first layers run).
+// The TD3 critic pass adds to the head counters of side 0 only on launches an actor pass follows; nothing waits for
+// them in that mode (the actor pass is a launch of its own), so the table carries the side-1 figure for both.
+static inline unsigned sync_units(int kernel, int region, int NB, bool wide) {
+    if (kernel == FUSED_CHAIN8) {
+        if (region == SYNC_QA || region == SYNC_TQ || region == SYNC_AC) return CHAIN_UNITS_RB;
+        return region == SYNC_LP ? chain_units_lp(NB) : 0u;
+    }
+    switch (region) {
+    case SYNC_HEAD: return ABC_UNITS_HEAD;
+    case SYNC_QA: return ABC_UNITS_QA;
+    case SYNC_TQ: return ABC_UNITS_TQ;
+    case SYNC_AC: return kernel == FUSED_ABC_SAC ? ABC_UNITS_AC : 0u;
+    case SYNC_ZX: return wide ? ABC_UNITS_ZX : 0u;
+    default: return 0u;
+    }
+}
+
+// The sync_words(NB) words as `seq` completed launches of `kernel` leave them: every counter at units * seq modulo 2^32,
+// every tagged word {0.0f, seq} (k_abc, SAC), the give-up word clear, everything else 0.
+static inline void sync_fill(unsigned *w, int NB, int kernel, bool wide, unsigned seq) {
+    memset(w, 0, sizeof(unsigned) * sync_words(NB));
+    for (int r = 0; r < SYNC_REGIONS; ++r) {
+        if (r == SYNC_ABORT || r == SYNC_LP_TAG) continue;
+        const unsigned v = sync_units(kernel, r, NB, wide) * seq;
+        unsigned *p = w + (size_t)SYNC_STRIDE * sync_region_line(r, NB);
+        for (int i = 0; i < sync_region_lines(r, NB); ++i) p[(size_t)SYNC_STRIDE * i] = v;
+    }
+    if (kernel == FUSED_ABC_SAC) {
+        unsigned *p = w + (size_t)SYNC_STRIDE * sync_region_line(SYNC_LP_TAG, NB);
+        for (int i = 0; i < NB && i < SYNC_STRIDE / 2; ++i) p[2 * i + 1] = seq;       // (little-endian: the tag is the high word)
+    }
+}
+
+// SAC_FUSED_TEST_STALL=<n> counts from the launch number the test hook last set (0 without it): is launch `seq` the one?
+static inline bool test_stall_hits(unsigned stall_at, unsigned base, unsigned seq) { return stall_at != 0u && seq - base == stall_at; }
 
 }  // namespace sac

@@ -2017,7 +2017,8 @@ struct sac_trainer {
     // fused step (k_abc, sac_fused.h; k_chain8<.., BWD>, sac_chain.h): launches A + B + C as one launch with in-launch
     // hand-offs.  Starts as plan.fused; a give-up or sac_trainer_set_xcd_mask clears it for good (trainer_drop_fused).
     bool fused = false;
-    unsigned fused_seq = 0;                           // launches so far: the hand-off counters count in units of it
+    unsigned fused_seq = 0;                           // launches so far, modulo 2^32: the hand-off counters count in units of it
+    unsigned stall_base = 0;                          // SAC_FUSED_TEST_STALL counts from here (sac_debug_set_launch_number; tests)
     unsigned fused_unchecked = 0;                     // fused launches since the host last looked at the abort marker
     bool publish_diag = true;                         // the next step's diagnostics go to the pinned host buffer (its caller reads them)
     // Fused steps launched by sac_step_device that the host has not yet seen applied: should one of them give up, these
@@ -2176,7 +2177,7 @@ int launch_fused_abc(sac_trainer *t, const float *S, const SlotLayout &SL, StepA
     hipStream_t s = t->stream;
     SAC_REQUIRE(!t->plan.row_images || (SL.has_images() && SL.KLQ == round_up(t->plan.KQ, 64)), "the fused step reads row images, this slot has none");
     sa.seq = ++t->fused_seq;
-    sa.pad2 |= extra_flags | ((t->plan.test_stall_at && sa.seq == t->plan.test_stall_at) ? 1u : 0u);
+    sa.pad2 |= extra_flags | (test_stall_hits(t->plan.test_stall_at, t->stall_base, sa.seq) ? 1u : 0u);
     t->fused_unchecked += 1;
     FusedGate &G = g_gate[t->device & 63];
     std::lock_guard<std::mutex> lk(G.mu);
@@ -2554,7 +2555,7 @@ static int trainer_alloc(sac_trainer *t, const sac_config_t *cfg, const td3_conf
     if (alloc_zero(&t->d_diag, (long long)SAC_DIAG_N * (2 + DIAG_TRACE_CAP), s)) return -1;
     arena.reserve(reinterpret_cast<void **>(&t->d_ctl), sizeof(Ctl));
     // head[2][NB], qa / tq / ac [NB], log-pi, abort; then zx[6][NB] (the exchange of the split first layers)
-    t->sync_bytes = sizeof(unsigned) * (size_t)CNT_STRIDE * (5 * t->NB + 2 + 6 * t->NB + 1);   // (+1: k_abc's tagged sums of log pi)
+    t->sync_bytes = sizeof(unsigned) * sync_words(t->NB);      // (the regions: sac_step_plan.h)
     arena.reserve(reinterpret_cast<void **>(&t->d_sync), t->sync_bytes);
     arena.reserve(reinterpret_cast<void **>(&t->d_dwl), sizeof(DwLayer) * NDW * 3);
     g_arena = nullptr;
@@ -2578,7 +2579,7 @@ static int trainer_alloc(sac_trainer *t, const sac_config_t *cfg, const td3_conf
     d.diag_dev = t->d_diag;
     d.eps1 = d.eps2 = nullptr;
     d.cnt = t->d_sync;
-    d.abort_flag = t->d_sync + (size_t)CNT_STRIDE * (5 * t->NB + 1);
+    d.abort_flag = t->d_sync + (size_t)SYNC_STRIDE * sync_region_line(SYNC_ABORT, t->NB);
 
     return 0;
 }
@@ -3387,6 +3388,25 @@ int sac_last_loop_ms(sac_trainer_t *t, float *total_ms, float *sample_ms, float 
     if (sample_ms) *sample_ms = t->last_ms[1];
     if (gather_ms) *gather_ms = t->last_ms[2];
     if (steps_ms) *steps_ms = t->last_ms[3];
+    return 0;
+}
+
+// Test hook: the trainer as `seq` completed fused launches leave it -- the launch number, every hand-off counter at
+// units * seq modulo 2^32, every tagged word tagged seq, the give-up word clear (sync_fill, sac_step_plan.h).  Trained
+// state, optimizer state and step counts are not touched: the launch number never enters the arithmetic.
+int sac_debug_set_launch_number(sac_trainer_t *t, uint32_t seq) {
+    SAC_REQUIRE(t != nullptr, "null trainer");
+    SAC_HIP(hipSetDevice(t->device));
+    if (settle_trainer(t)) return -1;
+    SAC_REQUIRE(t->fused, "sac_debug_set_launch_number: this trainer does not run the fused step");
+    SAC_HIP(hipStreamSynchronize(t->stream));
+    const int kernel = t->plan.chain_bwd ? FUSED_CHAIN8 : (t->algo == 1 ? FUSED_ABC_TD3 : FUSED_ABC_SAC);
+    std::vector<unsigned> w(sync_words(t->NB));
+    sync_fill(w.data(), t->NB, kernel, t->plan.wide, seq);
+    SAC_HIP(hipMemcpyAsync(t->d_sync, w.data(), t->sync_bytes, hipMemcpyHostToDevice, t->stream));
+    SAC_HIP(hipStreamSynchronize(t->stream));
+    t->fused_seq = seq;
+    t->stall_base = seq;
     return 0;
 }
 

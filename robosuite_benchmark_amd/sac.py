@@ -751,3 +751,11 @@ class SACTrainer:
         got = self._lib.sac_debug_fetch(self._h, name.encode(), _lib.ptr(out), out.size)
         _lib.check(int(got), "sac_debug_fetch")
         return out[:got]
+
+    def set_launch_number(self, seq):
+        """Test hook (sac_debug_set_launch_number): this trainer as `seq` (modulo 2^32) completed fused launches leave it
+        -- launch number, hand-off counters, tagged words.  Trained state is untouched; a trainer that does not run a
+        fused step is refused."""
+        if self._h is None:
+            raise RuntimeError("set_launch_number: no device trainer")
+        _lib.check(self._lib.sac_debug_set_launch_number(self._h, int(seq) & 0xFFFFFFFF), "sac_debug_set_launch_number")
