@@ -553,22 +553,24 @@ int gen_run_list(sac_trainer *t, const std::vector<GenStage> &list, const float 
     return 0;
 }
 
-// one step on minibatch slot S.  SAC: the launch list built by gen_build.  TD3 (rlkit TD3Trainer.train_from_torch, as
-// launch_step_td3): the critic pass every step -- its Adam launch also soft-updates the critics' targets on policy steps --
+// one step on minibatch slot c.S.  SAC: the launch list built by gen_build.  TD3 (rlkit TD3Trainer.train_from_torch, as
+// launch_step's): the critic pass every step -- its Adam launch also soft-updates the critics' targets on policy steps --
 // and the actor pass on policy steps (n_train_steps_total % policy_and_target_update_period == 0: Q1(s, policy(s)) through the
 // ALREADY UPDATED qf1, policy backward, policy Adam + soft update of the target policy); want_stats on another step: the
 // actor pass's forward half only, for Policy Loss / Policy Action (rlkit recomputes them for the epoch statistics).
-int gen_launch_step(sac_trainer *t, const float *S, const SlotLayout &SL, int j, bool want_stats) {
+int gen_launch_step(sac_trainer *t, const StepCall &c) {
     sac_general *g = t->gen;
+    const float *S = c.S;
+    const SlotLayout &SL = *c.SL;
     SAC_REQUIRE(SL.off_obs == t->ext_layout.off_obs && SL.off_nobs == t->ext_layout.off_nobs && SL.Bt == g->n,
                 "internal: minibatch slot layout differs from the one the general step was built for");
-    g->dev.eps1 = t->dev.eps1; g->dev.eps2 = t->dev.eps2;
-    StepArg sa = step_arg(t->n_train_steps_total, t->adam_t + 1, j, 0, t->publish_diag);
+    g->dev.eps1 = c.eps1; g->dev.eps2 = c.eps2;
+    StepArg sa = step_arg(t->n_train_steps_total, t->adam_t + 1, c.loop_pos, 0, c.publish);
     if (t->algo == 0) {
         if (gen_run_list(t, g->stages, S, SL, sa, (t->n_train_steps_total % g->dev.period) == 0)) return -1;
     } else {
-        const Td3Plan P = td3_plan(t, 0, 0, want_stats);
-        const StepArg sp = step_arg(P.step, P.t_pi, j, 2, t->publish_diag);
+        const Td3Plan P = td3_plan(t, 0, 0, c.want_stats);
+        const StepArg sp = step_arg(P.step, P.t_pi, c.loop_pos, 2, c.publish);
         sa.pad = 1;
         if (gen_run_list(t, g->td3_critic, S, SL, sa, P.pstep)) return -1;
         if (P.actor && gen_run_list(t, P.pstep ? g->td3_actor : g->td3_stats, S, SL, sp, true)) return -1;

@@ -6,8 +6,8 @@
 //
 // Every kind of group is a STAGE LIST built at creation (GroupStage) and one loop that walks it:
 //   * same-shape and mixed groups of the fused kernels' shapes (sac_group_create[_mixed], td3_group_create[_mixed]): the
-//     members' four-launch step -- SAC: A, B, C, dW; TD3: A, B, C, dW of the critic pass, then B, C, dW of the actor
-//     pass.  A, B, C go once per variant class (GroupClass: members of different dims and batches run different kernel
+//     members' four-launch step, read from the list the solo step walks (step_schedule, sac_step_plan.h) -- SAC: A, B, C,
+//     dW; TD3: A, B, C, dW of the critic pass, then B, C, dW of the actor pass.  A, B, C go once per variant class (GroupClass: members of different dims and batches run different kernel
 //     instances), the weight-gradient launch once for all members;
 //   * MLP and arch groups (sac_group_create_mlp / _arch, td3_...): the merged schedule of the members' general-step
 //     launch lists, one grouped launch per GEMM stage and one per class (or one for all) per elementwise stage.
@@ -379,62 +379,58 @@ static int group_build_fused(sac_group *g) {
             key[g->ncls++] = k;
         }
     }
-    // per class: its kernels (step_kernels), the largest member extents and the largest member LDS of launches A, B, C
-    const void *ker[4][5] = {};
-    StepLaunch mx[4][5];                              // [class][launch a, b, c, b2, c2]
+    // the classes' ranges of the device tables and their grouped kernel instances (step_kernels: a, b, c, b2, c2)
+    StepKernels sk[4];
     int pos = 0;
     for (int c = 0; c < g->ncls; ++c) {
         GroupClass &K = g->cls[c];
         K.lo = pos;
-        for (int i = 0; i < R; ++i) {
-            const sac_trainer *t = g->m[i];
-            if (!same_variant(t, key[c])) continue;
-            g->ord[pos++] = i;
-            const StepLaunch *const l[5] = {&t->plan.a, &t->plan.b, &t->plan.c, &t->plan.b2, &t->plan.c2};
-            for (int q = 0; q < 5; ++q) {
-                mx[c][q].grid = std::max(mx[c][q].grid, l[q]->grid);
-                mx[c][q].lds = std::max(mx[c][q].lds, l[q]->lds);
-            }
-        }
+        for (int i = 0; i < R; ++i)
+            if (same_variant(g->m[i], key[c])) g->ord[pos++] = i;
         K.n = pos - K.lo;
         const StepPlan &P0 = key[c]->plan;
-        const StepKernels sk = step_kernels(P0.nth, P0.wide, 4, algo, P0.chain8, P0.wide4);
-        for (int q = 0; q < 5; ++q) ker[c][q] = sk.group[q];
-        if (!ker[c][0]) {
+        sk[c] = step_kernels(P0.nth, P0.wide, 4, algo, P0.chain8, P0.wide4);
+        if (!sk[c].group[0]) {
             sac::set_error("internal: no grouped instance of the members' step kernels");
             return -1;
         }
     }
-    // k_dw_adam_group: the largest njobs + 1 (SAC; TD3 critic / policy)
-    int grid_d = 0, grid_dq = 0, grid_dpi = 0;
-    for (int i = 0; i < R; ++i) {
-        const sac_trainer *t = g->m[i];
-        grid_d = std::max(grid_d, t->dw.njobs + 1);
-        grid_dq = std::max(grid_dq, std::max(t->dw_q.njobs, t->dw_q_tp.njobs) + 1);
-        grid_dpi = std::max(grid_dpi, t->dw_pi.njobs + 1);
-    }
-    auto per_class = [&](int which, int need, int arg) {
-        GroupStage st;
-        st.per_class = true; st.need = need; st.arg = arg;
-        for (int c = 0; c < g->ncls; ++c) { st.fn[c] = ker[c][which]; st.gx[c] = mx[c][which].grid; st.lds[c] = mx[c][which].lds; }
-        g->stages.push_back(st);
-    };
     // the one-group form of the weight-gradient body where every member runs it solo (batch <= 256, not SAC_DW_FORM=loop)
     bool one = true;
     for (int i = 0; i < R; ++i) one = one && g->m[i]->plan.dw_one;
-    auto for_all = [&](auto kernel, int gx, int need, bool idle_one) {
-        GroupStage st;
-        st.fn[0] = reinterpret_cast<const void *>(kernel); st.gx[0] = gx; st.need = need; st.idle_one = idle_one;
-        g->stages.push_back(st);
+    auto dw_group = [one](int kernel) {
+        auto fn = [](auto f) { return reinterpret_cast<const void *>(f); };
+        if (kernel == SK_DW) return one ? fn(&k_dw_adam_group<M_SAC, true>) : fn(&k_dw_adam_group<M_SAC, false>);
+        if (kernel == SK_DW_Q) return one ? fn(&k_dw_adam_group<M_TD3_CRITIC, true>) : fn(&k_dw_adam_group<M_TD3_CRITIC, false>);
+        return one ? fn(&k_dw_adam_group<M_TD3_ACTOR, true>) : fn(&k_dw_adam_group<M_TD3_ACTOR, false>);
     };
-    if (algo == 0) {                                  // launch_step: A, B, C (compact: 3 * 4 * NB <= 192 for every member), dW
-        per_class(0, 0, 0); per_class(1, 0, 0); per_class(2, 0, 1);
-        for_all(one ? &k_dw_adam_group<M_SAC, true> : &k_dw_adam_group<M_SAC, false>, grid_d, 0, false);
-    } else {                                          // launch_step_td3: the critic pass, then the actor pass
-        per_class(0, 0, 0); per_class(1, 0, 0); per_class(2, 0, 0);
-        for_all(one ? &k_dw_adam_group<M_TD3_CRITIC, true> : &k_dw_adam_group<M_TD3_CRITIC, false>, grid_dq, 0, false);
-        per_class(3, 1, 0); per_class(4, 2, 0);
-        for_all(one ? &k_dw_adam_group<M_TD3_ACTOR, true> : &k_dw_adam_group<M_TD3_ACTOR, false>, grid_dpi, 1, true);
+    // The stage list is the members' four-launch schedule (sac_trainer::sched[0]: step_schedule(plan, false) as the solo
+    // step walks it), the same for every member: A, B, C, B2, C2 once per class over the largest member extent and LDS,
+    // a weight-gradient stage once for all members over the largest njobs + 1 of the tables it chooses between.
+    const sac_trainer *t0 = g->m[0];
+    for (int k = 0; k < t0->n_sched[0]; ++k) {
+        const StepStage &s0 = t0->sched[0][k].st;
+        GroupStage st;
+        st.need = s0.need; st.block = s0.launch.threads;
+        st.arg = std::max(s0.tail, 0);                // (launch C's `compact`; TD3's launch A reads "an actor pass follows" from its step row)
+        st.per_class = s0.kernel <= SK_C2;
+        st.idle_one = s0.kernel == SK_DW_PI;          // (off a policy step every member's table is dw_none: one block each)
+        if (!st.per_class) st.fn[0] = dw_group(s0.kernel);
+        for (int d = 0; d < R; ++d) {
+            const sac_trainer *t = g->m[g->ord[d]];
+            SAC_REQUIRE(t->n_sched[0] == t0->n_sched[0], "internal: trainer group member %d has another step schedule than member 0", g->ord[d]);
+            const sac_trainer::Stage &ms = t->sched[0][k];
+            SAC_REQUIRE(ms.st.kernel == s0.kernel && ms.st.need == s0.need && ms.st.arg == s0.arg && ms.st.tail == s0.tail,
+                        "internal: trainer group member %d has another step schedule than member 0", g->ord[d]);
+            int c = 0;
+            while (st.per_class && !(d >= g->cls[c].lo && d < g->cls[c].lo + g->cls[c].n)) ++c;
+            if (st.per_class) {
+                st.fn[c] = sk[c].group[s0.kernel];
+                st.gx[c] = std::max(st.gx[c], ms.st.launch.grid);
+                st.lds[c] = std::max(st.lds[c], ms.st.launch.lds);
+            } else st.gx[0] = std::max(st.gx[0], std::max(ms.tab[0]->njobs, ms.tab[1]->njobs) + 1);
+        }
+        g->stages.push_back(st);
     }
     for (const GroupStage &st : g->stages)
         for (int c = 0; c < 4; ++c)
@@ -558,10 +554,7 @@ int sac_group_train_loop(sac_group_t *g, sac_buffer_t *const *bufs, int64_t n_st
     // what sac_train_loop does first, for every member and every buffer (each with its member's own batch)
     for (int r = 0; r < R; ++r) {
         sac_trainer *t = g->m[r];
-        if (t->fused && t->pend_n > 0) {          // device-batch steps nobody has verified yet: settle them first
-            if (wait_trainer_stream(t)) return -1;
-            if (recover_device_steps(t) < 0) return -1;
-        }
+        if (settle_trainer(t)) return -1;         // (device-batch steps nobody has verified yet come first)
         sac_buffer *b = bufs[r];
         if (host_rng_sync_in(b)) return -1;
         if (b->ra_ahead > 0) { if (readahead_rollback(b)) return -1; }
@@ -570,7 +563,6 @@ int sac_group_train_loop(sac_group_t *g, sac_buffer_t *const *bufs, int64_t n_st
         b->loop_streak = 0;
         if (ensure_slots(b, t->Bt, LOOP_RING)) return -1;
         if (ensure_idx(b, LOOP_RING * t->B)) return -1;
-        t->dev.eps1 = t->dev.eps2 = nullptr;
     }
     // Buffers bound to the SAME host generator (sac_rng_bind_host: by default every EnvReplayBuffer samples np.random)
     // continue it one after another, as R sac_train_loop calls in member order would: buffer r starts where the previous
@@ -617,6 +609,7 @@ int sac_group_train_loop(sac_group_t *g, sac_buffer_t *const *bufs, int64_t n_st
         sac_buffer *b = bufs[r];
         GroupMember &M = h_mem[k];
         M.d = t->dev;
+        M.d.eps1 = M.d.eps2 = nullptr;                // (loop steps draw their noise on the device)
         M.T = t->dw;
         M.T.abort = nullptr;                          // (the four-launch step: no fused launch can give up in front of it)
         M.SL = b->slot;

@@ -1,7 +1,8 @@
 // The step plan: which kernels, grids, block sizes and LDS a trainer of the fused kernels' shapes runs, decided once at
 // creation as a pure function of (obs_dim, act_dim, batch, algo, CU count, environment).  Plain C++17: no HIP header,
-// no HIP call, no kernel named -- sac_trainer.hip binds the plan to template instances (step_kernels), the launch sites
-// and the trainer groups read it, tests/test_step_plan_host.py checks it with the host compiler alone.
+// no HIP call, no kernel named -- sac_trainer.hip binds the plan to template instances (step_kernels); the order of a
+// step's launches is step_schedule below, which the solo step and the trainer groups both walk;
+// tests/test_step_plan_host.py checks plan and schedule with the host compiler alone.
 #pragma once
 #include <cstddef>
 #include <cstdlib>
@@ -156,6 +157,46 @@ static inline StepPlan step_plan(int obs_dim, int act_dim, int batch, int algo, 
         P.c2 = StepLaunch{SP * NB, 256, lds_bw};
     }
     return P;
+}
+
+// ---- The step schedule: the plan's launches of ONE step, in launch order -------------------------------------------------
+// The solo step (launch_step walks it, sac_profile_loop with events between its stages) and the trainer groups of these
+// shapes (group_build_fused) read this one list.  fused_now: the trainer still runs the plan's fused launch (a give-up or
+// a confinement drops it for good: the four-launch list, with `chained` in place of A + B where the plan chains).
+enum StepKernelId { SK_A, SK_B, SK_C, SK_B2, SK_C2, SK_FUSED, SK_CHAINED, SK_DW, SK_DW_Q, SK_DW_PI };
+constexpr int STEP_NEED_ACTOR = 1, STEP_NEED_PSTEP = 2;       // (the bits of GroupStage::need)
+constexpr int TAIL_ACTOR_FOLLOWS = -1;
+struct StepStage {
+    int kernel = 0;               // StepKernelId
+    StepLaunch launch;            // the plan's; a weight-gradient stage: threads 256, lds 0, the grid left to whoever binds its tables
+    int need = 0;                 // runs on: 0 every step, STEP_NEED_ACTOR steps with an actor pass, STEP_NEED_PSTEP policy steps (TD3)
+    int arg = 0;                  // its StepArg: 0 the step's first (SAC, TD3's critic pass), 1 the actor pass's
+    int tail = 0;                 // the launch's trailing int where it has one: >= 0 as it stands (launch C: `compact`);
+                                  // TAIL_ACTOR_FOLLOWS: 1 on the steps an actor pass follows (TD3's launch A and fused launch)
+    int last_event = 0;           // sac_profile_loop: the events up to this one (of 1..6) are recorded behind the stage; 0: none
+};
+constexpr int STEP_STAGES_MAX = 8;
+static inline int step_schedule(const StepPlan &P, bool fused_now, StepStage out[STEP_STAGES_MAX]) {
+    const bool td3 = P.algo == 1;
+    const int follows = td3 ? TAIL_ACTOR_FOLLOWS : 0, ev = td3 ? 0 : 1;       // (the profiling pass is the SAC step's)
+    const StepLaunch dw{0, 256, 0};
+    int n = 0;
+    if (P.fused && fused_now) out[n++] = StepStage{SK_FUSED, P.fused_launch, 0, 0, follows, 4 * ev};
+    else {
+        if (P.chain) out[n++] = StepStage{SK_CHAINED, P.chained, 0, 0, 0, 2 * ev};
+        else {
+            out[n++] = StepStage{SK_A, P.a, 0, 0, follows, 1 * ev};
+            out[n++] = StepStage{SK_B, P.b, 0, 0, 0, 2 * ev};
+        }
+        out[n++] = StepStage{SK_C, P.c, 0, 0, P.compact, 4 * ev};
+    }
+    out[n++] = StepStage{td3 ? SK_DW_Q : SK_DW, dw, 0, 0, 0, 6 * ev};
+    if (td3) {                    // the actor pass: Q1(s, pi(s)) on every step that wants it, the policy's backward and update on policy steps
+        out[n++] = StepStage{SK_B2, P.b2, STEP_NEED_ACTOR, 1, 0, 0};
+        out[n++] = StepStage{SK_C2, P.c2, STEP_NEED_PSTEP, 1, 0, 0};
+        out[n++] = StepStage{SK_DW_PI, dw, STEP_NEED_ACTOR, 1, 0, 0};
+    }
+    return n;
 }
 
 // ---- The hand-off words of the fused launches (k_abc: sac_fused.h; k_chain8<.., BWD>: sac_chain.h) ----------------------

@@ -4,7 +4,7 @@
 // sites /root/reference/util/rlkit_utils.py:64-106, /root/reference/util/rlkit_custom.py:238.
 // Normative step order: SURVEY.md Appendix A (lines 1-18), ordering O1, logging quirk Q1.
 // TD3 (rlkit TD3Trainer, /root/reference/util/rlkit_utils.py:107-135) runs on the same kernels as compile-time
-// variants (MODE = M_TD3_CRITIC / M_TD3_ACTOR, see launch_step_td3).
+// variants (MODE = M_TD3_CRITIC / M_TD3_ACTOR; their order in a step: step_schedule, sac_step_plan.h).
 //
 // Decomposition (DESIGN.md "Kernels"): batch rows are independent through forward and backward-dX,
 // so a workgroup owns a 16-row block (one MFMA 16x16x4 M-tile) and chains whole layers through LDS;
@@ -1829,10 +1829,10 @@ struct GroupMember {
     DwTable T;                     // the member's weight-gradient table (abort = null: the four-launch step); TD3: dw_q
     SlotLayout SL;
     const float *slots;            // the member's loop slot 0: slot j at slots + j * SL.slot_floats
-    DwTable T_tp, T_pi, T_none;    // TD3 only: dw_q_tp, dw_pi, dw_none (launch_step_td3's other tables)
+    DwTable T_tp, T_pi, T_none;    // TD3 only: dw_q_tp, dw_pi, dw_none (the other tables of the TD3 step's weight-gradient stages)
     int xa, xb, xc, xpi;           // the member's solo x-extents: launch A, B, C; TD3 actor pass B / C
 };
-// A TD3 member's step (the [step][R] table of a TD3 group): launch_step_td3's two StepArgs and its plan.  Members may be
+// A TD3 member's step (the [step][R] table of a TD3 group): the solo TD3 step's two StepArgs and its plan.  Members may be
 // in different phases of the delayed update, so the actor launches of a step run for every member that needs them and
 // the others leave at block entry (a uniform branch on these flags).
 struct Td3GroupStep {
@@ -2020,7 +2020,13 @@ struct sac_trainer {
     unsigned fused_seq = 0;                           // launches so far, modulo 2^32: the hand-off counters count in units of it
     unsigned stall_base = 0;                          // SAC_FUSED_TEST_STALL counts from here (sac_debug_set_launch_number; tests)
     unsigned fused_unchecked = 0;                     // fused launches since the host last looked at the abort marker
-    bool publish_diag = true;                         // the next step's diagnostics go to the pinned host buffer (its caller reads them)
+    // The step as launchable stages: step_schedule(plan, fused) bound once (trainer_bind) to its kernel instances and, for
+    // a weight-gradient stage, to the two tables it chooses between -- off / on a policy step (SAC: dw / dw; TD3's critics:
+    // dw_q / dw_q_tp; TD3's policy: dw_none / dw_pi), pointers into this trainer (set_abort_ptrs reaches them).  `fused`
+    // picks the list.
+    struct Stage { StepStage st; const void *fn = nullptr; const DwTable *tab[2] = {nullptr, nullptr}; };
+    Stage sched[2][STEP_STAGES_MAX];                  // [0] the four-launch step (what a fused trainer falls back to), [1] the fused step
+    int n_sched[2] = {0, 0};
     // Fused steps launched by sac_step_device that the host has not yet seen applied: should one of them give up, these
     // are re-run on the four-launch step from their slots (still intact: the host never runs more than two groups of
     // sixteen steps ahead of the device on this path -- thr_ev, one event per sixteen steps).
@@ -2052,6 +2058,17 @@ inline Td3Plan td3_plan(const sac_trainer *t, long long i, long long pi_steps, b
     const bool pstep = (step % t->td3_period) == 0;
     return Td3Plan{step, t->adam_t + i + 1, t->adam_t_pi + pi_steps + 1, pstep, pstep || want_stats};
 }
+
+// One step, as its caller asks for it (launch_step; gen_launch_step): everything a step takes besides the trainer's state.
+struct StepCall {
+    const float *S;                // the minibatch slot
+    const SlotLayout *SL;
+    int loop_pos;                  // StepArg::loop_pos
+    bool publish;                  // the step's diagnostics go to the pinned host buffer (its caller reads them)
+    bool want_stats;               // TD3: run the actor pass's statistics half also off a policy step
+    const float *eps1, *eps2;      // caller-supplied noise on the device, or null (the counter-based device stream)
+    hipEvent_t *ev;                // sac_profile_loop: seven events around the stages, or null
+};
 
 #include "sac_general_host.h"
 
@@ -2143,11 +2160,6 @@ int ensure_stage_t(sac_trainer *t, size_t bytes) {
     return 0;
 }
 
-// TD3 step (rlkit TD3Trainer.train_from_torch): critic pass = 4 launches every step; on policy steps
-// (n_train_steps_total % policy_and_target_update_period == 0) the critics' Adam launch also soft-updates their
-// targets and the actor pass follows -- Q1(s, policy(s)) through the ALREADY UPDATED qf1, policy backward, policy
-// Adam + soft update of the target policy.  want_stats: also produce Policy Loss / Policy Action on a non-policy
-// step (rlkit recomputes them for the epoch statistics), without any update.
 // Fused launches of different trainers (streams) of one process must not overlap on a device: two half-resident grids
 // would wait for each other's CUs until the hand-off timeout.  While more than one fused trainer lives on a device,
 // each fused launch waits for the previous one there and records an event behind itself (host section under a lock).
@@ -2189,77 +2201,62 @@ int launch_fused_abc(sac_trainer *t, const float *S, const SlotLayout &SL, StepA
     return 0;
 }
 
-int launch_step_td3(sac_trainer *t, const float *S, const SlotLayout &SL, int j, bool want_stats) {
-    const Dev &d = t->dev;
+// One step on minibatch slot c.S: a walk over the trainer's current schedule (sac_trainer::sched; step_schedule,
+// sac_step_plan.h), SAC and TD3 alike.  A stage runs where the step has what it needs -- TD3 (rlkit
+// TD3Trainer.train_from_torch): the critic pass every step; on policy steps (n_train_steps_total %
+// policy_and_target_update_period == 0) the critics' Adam launch also soft-updates their targets and the actor pass
+// follows: Q1(s, policy(s)) through the ALREADY UPDATED qf1, policy backward, policy Adam + soft update of the target
+// policy; c.want_stats: Policy Loss / Policy Action on another step too (rlkit recomputes them for the epoch statistics),
+// without any update.  The diagnostics -- and the flat gradient copies of sac_debug_fetch -- go out only on the steps
+// whose caller reads them (c.publish; td3_diagnostics keeps "last" the most recent value of each entry across launches).
+// c.ev: e0 in front of the first stage, behind each stage the events up to its last_event (profiling pass only).
+int launch_step(sac_trainer *t, const StepCall &c) {
+    if (t->gen) return gen_launch_step(t, c);
     hipStream_t s = t->stream;
-    const StepPlan &L = t->plan;
-    const Td3Plan P = td3_plan(t, 0, 0, want_stats);
-    const bool pstep = P.pstep, actor = P.actor;
-    // (the diagnostics -- and the flat gradient copies of sac_debug_fetch -- go out only on the steps whose caller reads
-    //  them, like the SAC step's; td3_diagnostics keeps "last" the most recent value of each entry across launches)
-    StepArg sq = step_arg(P.step, P.t_q, j, 1, t->publish_diag);
-    const StepArg sp = step_arg(P.step, P.t_pi, j, 2, t->publish_diag);
-    if (t->fused) {
-        // the critic pass as ONE launch (k_abc<.., M_TD3_CRITIC>, sac_fused.h) + its weight-gradient launch
-        if (launch_fused_abc(t, S, SL, sq, actor ? 4u : 0u)) return -1;
-    } else {
-        hipLaunchKernelGGL(t->k.a, dim3(L.a.grid), dim3(L.a.threads), L.a.lds, s, d, S, SL, actor ? 1 : 0);
-        hipLaunchKernelGGL(t->k.b, dim3(L.b.grid), dim3(L.b.threads), L.b.lds, s, d, S, SL, sq);
-        hipLaunchKernelGGL(t->k.c, dim3(L.c.grid), dim3(L.c.threads), L.c.lds, s, d, S, SL, sq, 0);
-    }
-    const DwTable &Tq = pstep ? t->dw_q_tp : t->dw_q;
-    hipLaunchKernelGGL(t->plan.dw_one ? k_dw_adam_one : k_dw_adam, dim3(Tq.njobs + 1), dim3(256), 0, s, d, Tq, S, sq);
-    if (actor) {
-        hipLaunchKernelGGL(t->k.b2, dim3(L.b2.grid), dim3(L.b2.threads), L.b2.lds, s, d, S, SL, sp);
-        if (pstep) {
-            hipLaunchKernelGGL(t->k.c2, dim3(L.c2.grid), dim3(L.c2.threads), L.c2.lds, s, d, S, SL, sp, 0);
-            hipLaunchKernelGGL(t->plan.dw_one ? k_dw_adam_one : k_dw_adam, dim3(t->dw_pi.njobs + 1), dim3(256), 0, s, d, t->dw_pi, S, sp);
-            t->adam_t_pi += 1;
-        } else {
-            hipLaunchKernelGGL(t->plan.dw_one ? k_dw_adam_one : k_dw_adam, dim3(1), dim3(256), 0, s, d, t->dw_none, S, sp);      // statistics only
+    t->dev.eps1 = c.eps1; t->dev.eps2 = c.eps2;
+    const Td3Plan P = td3_plan(t, 0, 0, c.want_stats);
+    const bool td3 = t->algo == 1, actor = td3 && P.actor, pstep = td3 && P.pstep;
+    const int have = (actor ? STEP_NEED_ACTOR : 0) | (pstep ? STEP_NEED_PSTEP : 0);
+    StepArg sa[2];                                    // [0] SAC / the critic pass (kind = algo), [1] the actor pass
+    sa[0] = step_arg(P.step, P.t_q, c.loop_pos, t->algo, c.publish);
+    if (td3) sa[1] = step_arg(P.step, P.t_pi, c.loop_pos, 2, c.publish);
+    const float *S = c.S;
+    int ev_at = 0;
+    if (c.ev) SAC_HIP(hipEventRecord(c.ev[0], s));
+    const int which = t->fused ? 1 : 0;
+    for (int i = 0; i < t->n_sched[which]; ++i) {
+        const sac_trainer::Stage &g = t->sched[which][i];
+        const StepStage &st = g.st;
+        if ((have & st.need) != st.need) continue;
+        int tail = st.tail == TAIL_ACTOR_FOLLOWS ? (actor ? 1 : 0) : st.tail;
+        if (st.kernel == SK_FUSED) {
+            // A + B + C as one launch with in-launch hand-offs (k_abc, k_chain8<.., BWD>); TD3: the critic pass
+            if (launch_fused_abc(t, S, *c.SL, sa[st.arg], tail ? 4u : 0u)) return -1;
+        } else if (g.tab[0]) {                        // weight gradients, Adam, Polyak, diagnostics: (Dev, DwTable, S, StepArg)
+            const DwTable *T = g.tab[pstep ? 1 : 0];
+            void *args[] = {&t->dev, const_cast<DwTable *>(T), &S, &sa[st.arg]};
+            (void)hipLaunchKernel(g.fn, dim3(T->njobs + 1), dim3(st.launch.threads), args, st.launch.lds, s);
+        } else {                                      // (Dev, S, SlotLayout, int) launch A; (.., StepArg [, int]) the others
+            void *args[] = {&t->dev, &S, const_cast<SlotLayout *>(c.SL), &sa[st.arg], &tail};
+            if (st.kernel == SK_A) args[3] = &tail;
+            (void)hipLaunchKernel(g.fn, dim3(st.launch.grid), dim3(st.launch.threads), args, st.launch.lds, s);
         }
+        for (; c.ev && ev_at < st.last_event; ++ev_at) SAC_HIP(hipEventRecord(c.ev[ev_at + 1], s));
     }
     SAC_HIP(hipGetLastError());
     t->n_train_steps_total += 1;
     t->adam_t += 1;
+    if (pstep) t->adam_t_pi += 1;
     return 0;
 }
 
-// the four launches of step j of the current chunk, on minibatch slot S; ev != null => HIP events
-// between the launches (profiling pass only)
-
-int launch_step(sac_trainer *t, const float *S, const SlotLayout &SL, int j, hipEvent_t *ev = nullptr, bool want_stats = false) {
-    if (t->gen) return gen_launch_step(t, S, SL, j, want_stats);
-    if (t->algo == 1) return launch_step_td3(t, S, SL, j, want_stats);
-    const Dev &d = t->dev;
-    hipStream_t s = t->stream;
-    const StepPlan &L = t->plan;
-    StepArg sa = step_arg(t->n_train_steps_total, t->adam_t + 1, j, 0, t->publish_diag);
-    if (ev) SAC_HIP(hipEventRecord(ev[0], s));
-    if (t->fused) {
-        // two launches: A + B + C as k_abc (in-launch hand-offs), then the weight-gradient / Adam launch
-        if (launch_fused_abc(t, S, SL, sa, 0u)) return -1;
-        if (ev) { SAC_HIP(hipEventRecord(ev[1], s)); SAC_HIP(hipEventRecord(ev[2], s)); SAC_HIP(hipEventRecord(ev[3], s)); }
-    } else {
-        if (L.chain) {
-            hipLaunchKernelGGL(t->k.chain, dim3(L.chained.grid), dim3(L.chained.threads), L.chained.lds, s, d, S, SL, sa);
-            if (ev) { SAC_HIP(hipEventRecord(ev[1], s)); SAC_HIP(hipEventRecord(ev[2], s)); }
-        } else {
-            hipLaunchKernelGGL(t->k.a, dim3(L.a.grid), dim3(L.a.threads), L.a.lds, s, d, S, SL, 0);
-            if (ev) SAC_HIP(hipEventRecord(ev[1], s));
-            hipLaunchKernelGGL(t->k.b, dim3(L.b.grid), dim3(L.b.threads), L.b.lds, s, d, S, SL, sa);
-            if (ev) SAC_HIP(hipEventRecord(ev[2], s));
-        }
-        hipLaunchKernelGGL(t->k.c, dim3(L.c.grid), dim3(L.c.threads), L.c.lds, s, d, S, SL, sa, L.compact);
-        if (ev) SAC_HIP(hipEventRecord(ev[3], s));
-    }
-    if (ev) SAC_HIP(hipEventRecord(ev[4], s));
-    hipLaunchKernelGGL(t->plan.dw_one ? k_dw_adam_one : k_dw_adam, dim3(t->dw.njobs + 1), dim3(256), 0, s, d, t->dw, S, sa);
-    if (ev) { SAC_HIP(hipEventRecord(ev[5], s)); SAC_HIP(hipEventRecord(ev[6], s)); }
-    SAC_HIP(hipGetLastError());
-    t->n_train_steps_total += 1;
-    t->adam_t += 1;
-    return 0;
+// The one user-space poll of an event: until it has completed (hipSuccess), failed, or `budget_us` have passed
+// (hipErrorNotReady) -- the caller chooses the budget and what it falls back to.
+static hipError_t poll_event(hipEvent_t e, int budget_us) {
+    const auto spin_until = std::chrono::steady_clock::now() + std::chrono::microseconds(budget_us);
+    hipError_t st;
+    while ((st = hipEventQuery(e)) == hipErrorNotReady && std::chrono::steady_clock::now() < spin_until) { }
+    return st;
 }
 
 // Wait until everything launched on the trainer's stream so far has finished: a user-space poll (up to 2 ms) of an event
@@ -2268,10 +2265,7 @@ int launch_step(sac_trainer *t, const float *S, const SlotLayout &SL, int j, hip
 static int wait_trainer_stream(sac_trainer *t, hipEvent_t recorded = nullptr) {
     hipEvent_t e = recorded;
     if (!e) { e = t->ev[3]; SAC_HIP(hipEventRecord(e, t->stream)); }
-    const auto spin_until = std::chrono::steady_clock::now() + std::chrono::milliseconds(2);
-    hipError_t st;
-    while ((st = hipEventQuery(e)) == hipErrorNotReady && std::chrono::steady_clock::now() < spin_until) { }
-    if (st == hipSuccess) return 0;
+    if (poll_event(e, 2000) == hipSuccess) return 0;
     SAC_HIP(hipStreamSynchronize(t->stream));
     return 0;
 }
@@ -2291,9 +2285,7 @@ static void trainer_drop_fused(sac_trainer *t) {
 
 // wait for ONE event (not for the stream behind it): a short user-space poll, then the blocking wait
 static int wait_event(hipEvent_t e) {
-    const auto spin_until = std::chrono::steady_clock::now() + std::chrono::milliseconds(2);
-    hipError_t st;
-    while ((st = hipEventQuery(e)) == hipErrorNotReady && std::chrono::steady_clock::now() < spin_until) { }
+    const hipError_t st = poll_event(e, 2000);
     if (st == hipSuccess) return 0;
     if (st == hipErrorNotReady) (void)hipGetLastError();
     SAC_HIP(hipEventSynchronize(e));
@@ -2344,12 +2336,9 @@ int replay_pending(sac_trainer *t, unsigned n) {
         const sac_trainer::Pending &P = t->pend[(t->pend_head + i) % sac_trainer::NPEND];
         const int slot = sac_ring_slot_of(P.buf, P.token);
         if (slot < 0) return -1;
-        t->dev.eps1 = t->dev.eps2 = nullptr;
-        t->publish_diag = (i == t->pend_n - 1);
-        const int rc = launch_step(t, P.buf->d_ring + (size_t)slot * P.buf->ring_layout.slot_floats, P.buf->ring_layout, 0,
-                                   nullptr, i == t->pend_n - 1);
-        t->publish_diag = true;
-        if (rc) return -1;
+        const bool last = i == t->pend_n - 1;
+        if (launch_step(t, StepCall{P.buf->d_ring + (size_t)slot * P.buf->ring_layout.slot_floats, &P.buf->ring_layout, 0, last,
+                                    last, nullptr, nullptr, nullptr})) return -1;
         for (auto &sb : seen) { if (sb == P.buf) break; if (!sb) { sb = P.buf; break; } }
     }
     // the slot-release events of those steps were recorded behind the launches that gave up: the buffers' streams now
@@ -2369,14 +2358,22 @@ int recover_device_steps(sac_trainer *t) {
     return wait_trainer_stream(t);
 }
 
-// Settle a trainer in front of an entry that reads or overwrites its state outside any step path (sac_get_* / sac_set_*,
-// the acting mirror, sac_trainer_set_xcd_mask): fused steps that nobody has verified yet are waited for, and if one of
-// them gave up the lost steps are re-run, so that the caller sees the state as of the last completed step -- the one the
-// counters already name.  A trainer with nothing unverified (and every general-step trainer) returns at once.
-int settle_trainer(sac_trainer *t) {
-    if (!t->fused || (t->pend_n == 0 && t->fused_unchecked == 0)) return 0;
+// wait for the trainer's stream, then recover what a fused step that gave up has lost
+int drain_and_recover(sac_trainer *t) {
     if (wait_trainer_stream(t)) return -1;
     return recover_device_steps(t) < 0 ? -1 : 0;
+}
+
+// Settle a trainer in front of an entry that reads or overwrites its state outside any step path (sac_get_* / sac_set_*,
+// the acting mirror, sac_trainer_set_xcd_mask) or that steps it on another stream or path (sac_train_loop, the group
+// loop): fused steps that nobody has verified yet are waited for, and if one of them gave up the lost steps are re-run,
+// so that the caller sees the state as of the last completed step -- the one the counters already name.  A trainer with
+// nothing unverified (and every general-step trainer) returns at once.  (pend_n and fused_unchecked are nonzero together
+// at every entry of the library: sac_step_device adds to both, and every path that zeroes one -- check_fused_abort and
+// the re-runs behind it -- zeroes the other.)
+int settle_trainer(sac_trainer *t) {
+    if (!t->fused || (t->pend_n == 0 && t->fused_unchecked == 0)) return 0;
+    return drain_and_recover(t);
 }
 
 // sample + gather all slots of a loop on the buffer's stream, make the trainer's stream wait
@@ -2679,6 +2676,25 @@ static int trainer_bind(sac_trainer *t) {
     if (P.chain && raise_lds(fn(t->k.chain), P.chained)) return -1;
     if (raise_lds(fn(t->k.a), P.a) || raise_lds(fn(t->k.b), P.b)) return -1;
     if (t->k.b2 && raise_lds(fn(t->k.b2), P.b2)) return -1;
+    // both schedules as launchable stages: the kernel instance, and a weight-gradient stage's two tables (off / on a
+    // policy step; its grid is the chosen table's njobs + 1 -- 1 for dw_none)
+    const void *const by_id[] = {fn(t->k.a), fn(t->k.b), fn(t->k.c), fn(t->k.b2), fn(t->k.c2), fn(t->k.fused), fn(t->k.chain)};
+    const void *const dw_fn = P.dw_one ? fn(&k_dw_adam_one) : fn(&k_dw_adam);
+    for (int f = 0; f < 2; ++f) {
+        StepStage st[STEP_STAGES_MAX];
+        t->n_sched[f] = step_schedule(P, f == 1, st);
+        for (int i = 0; i < t->n_sched[f]; ++i) {
+            sac_trainer::Stage &g = t->sched[f][i];
+            g.st = st[i];
+            switch (st[i].kernel) {
+            case SK_DW: g.fn = dw_fn; g.tab[0] = g.tab[1] = &t->dw; break;
+            case SK_DW_Q: g.fn = dw_fn; g.tab[0] = &t->dw_q; g.tab[1] = &t->dw_q_tp; break;
+            case SK_DW_PI: g.fn = dw_fn; g.tab[0] = &t->dw_none; g.tab[1] = &t->dw_pi; break;
+            default: g.fn = by_id[st[i].kernel];
+            }
+            SAC_REQUIRE(g.fn, "internal: no kernel instance for stage %d of the step schedule", i);
+        }
+    }
     return 0;
 }
 
@@ -2932,11 +2948,10 @@ int sac_step(sac_trainer_t *t, const float *obs, const float *act, const float *
     if (eps1) {
         memcpy(se, eps1, sizeof(float) * Bt * A); memcpy(se + (size_t)B * A, eps2, sizeof(float) * Bt * A);
         SAC_HIP(hipMemcpyAsync(t->d_eps, se, sizeof(float) * 2 * B * A, hipMemcpyHostToDevice, s));
-        t->dev.eps1 = t->d_eps; t->dev.eps2 = t->d_eps + (size_t)B * A;
-    } else {
-        t->dev.eps1 = t->dev.eps2 = nullptr;
     }
-    if (launch_step(t, t->ext_slot, L, 0, nullptr, diag != nullptr)) return -1;
+    const StepCall call{t->ext_slot, &L, 0, true, diag != nullptr, eps1 ? t->d_eps : nullptr,
+                        eps1 ? t->d_eps + (size_t)B * A : nullptr, nullptr};
+    if (launch_step(t, call)) return -1;
     if (wait_trainer_stream(t)) return -1;
     {   // a fused step that gave up: earlier device-batch steps still on record first, then this one again
         unsigned lost = 0;
@@ -2945,8 +2960,7 @@ int sac_step(sac_trainer_t *t, const float *obs, const float *act, const float *
         if (fa == 1) {
             if (lost > 1 && replay_pending(t, lost - 1)) return -1;
             t->pend_n = 0;
-            t->dev.eps1 = eps1 ? t->d_eps : nullptr; t->dev.eps2 = eps1 ? t->d_eps + (size_t)B * A : nullptr;
-            if (launch_step(t, t->ext_slot, L, 0, nullptr, diag != nullptr)) return -1;
+            if (launch_step(t, call)) return -1;
             if (wait_trainer_stream(t)) return -1;
         }
     }
@@ -2973,12 +2987,9 @@ int sac_step_device(sac_trainer_t *t, sac_buffer_t *b, int64_t token, float diag
         b->waited_stream = s;
         b->waited_chunk_token = b->ring_chunk_token[slot];
     }
-    t->dev.eps1 = t->dev.eps2 = nullptr;
-    t->publish_diag = diag != nullptr;
     const bool was_fused = t->fused;
-    const int rc_step = launch_step(t, b->d_ring + (size_t)slot * b->ring_layout.slot_floats, b->ring_layout, 0, nullptr, diag != nullptr);
-    t->publish_diag = true;
-    if (rc_step) return -1;
+    if (launch_step(t, StepCall{b->d_ring + (size_t)slot * b->ring_layout.slot_floats, &b->ring_layout, 0, diag != nullptr,
+                                diag != nullptr, nullptr, nullptr, nullptr})) return -1;
     if (was_fused) {
         // on record until the host has seen it applied (a fused step that gives up is re-run from its slot)
         if (t->pend_n == sac_trainer::NPEND) { t->pend_head = (t->pend_head + 1) % sac_trainer::NPEND; t->pend_n -= 1; }
@@ -3004,8 +3015,7 @@ int sac_step_device(sac_trainer_t *t, sac_buffer_t *b, int64_t token, float diag
     }
     t->mirror_valid = false;
     if (diag) {
-        if (wait_trainer_stream(t)) return -1;
-        if (recover_device_steps(t) < 0) return -1;
+        if (drain_and_recover(t)) return -1;
         memcpy(diag, t->h_diag + SAC_DIAG_N, sizeof(float) * SAC_DIAG_N);
     } else if (was_fused) {
         // Nobody waits for these steps.  The host looks at the give-up word (mapped pinned memory: a plain read) on every
@@ -3018,10 +3028,7 @@ int sac_step_device(sac_trainer_t *t, sac_buffer_t *b, int64_t token, float diag
             gave_up = t->h_diag[SAC_DIAG_N + 31] != 0.f;
             if (!gave_up && t->pend_n > 17) { t->pend_head = (t->pend_head + t->pend_n - 17) % sac_trainer::NPEND; t->pend_n = 17; }
         }
-        if (gave_up) {
-            if (wait_trainer_stream(t)) return -1;
-            if (recover_device_steps(t) < 0) return -1;
-        }
+        if (gave_up && drain_and_recover(t)) return -1;
     }
     return 0;
 }
@@ -3074,7 +3081,6 @@ static int train_loop_run(sac_trainer_t *t, sac_buffer_t *b, int64_t n_steps, in
                                  std::chrono::duration<double, std::micro>(std::chrono::steady_clock::now() - ht0).count());
     };
     hipStream_t s = t->stream;
-    t->dev.eps1 = t->dev.eps2 = nullptr;
     b->in_loop = true;                   // (this call's own draws and set-up are not outside touches of the buffer)
     struct InLoop { sac_buffer *b; ~InLoop() { b->in_loop = false; } } in_loop_guard{b};
     if (ensure_slots(b, t->Bt, LOOP_RING)) return -1;
@@ -3196,19 +3202,14 @@ static int train_loop_run(sac_trainer_t *t, sac_buffer_t *b, int64_t n_steps, in
             // SEEN the gather's event complete, the steps need no dependency at all.  (Bounded: a gather that is itself
             // waiting for slots takes the in-stream wait.)
             SAC_HIP(hipEventRecord(t->ev_ready[e], b->stream));
-            const auto spin_until = std::chrono::steady_clock::now() + std::chrono::microseconds(400);
-            hipError_t st;
-            while ((st = hipEventQuery(t->ev_ready[e])) == hipErrorNotReady && std::chrono::steady_clock::now() < spin_until) { }
-            if (st != hipSuccess) { (void)hipGetLastError(); SAC_HIP(hipStreamWaitEvent(s, t->ev_ready[e], 0)); }
+            if (poll_event(t->ev_ready[e], 400) != hipSuccess) { (void)hipGetLastError(); SAC_HIP(hipStreamWaitEvent(s, t->ev_ready[e], 0)); }
         }
-        for (int64_t i = 0; i < m; ++i) {
-            t->publish_diag = (first + i == n_steps - 1);
-            if (launch_step(t, b->d_slots + (size_t)(pos + i) * b->slot.slot_floats, b->slot, (int)(step0 + first + i), nullptr, step0 + first + i == 0)) return -1;
-        }
+        for (int64_t i = 0; i < m; ++i)             // (the diagnostics: published on the call's last step, TD3's statistics on its first)
+            if (launch_step(t, StepCall{b->d_slots + (size_t)(pos + i) * b->slot.slot_floats, &b->slot, (int)(step0 + first + i),
+                                        first + i == n_steps - 1, step0 + first + i == 0, nullptr, nullptr, nullptr})) return -1;
         // the generator's state is one in-order sequence: everything later on the buffer's stream follows chunk 0's draw
         // (told to that stream only now, behind chunk 0's step launches: nothing of it is in front of the first step)
         if (c == 0 && !use_spec && (more_chunks || will_speculate)) SAC_HIP(hipStreamWaitEvent(b->stream, b->ev[3], 0));
-        t->publish_diag = true;
         // "the trainer is done with this chunk's slots": only a call that wraps the slot ring ever asks (the next call
         // starts behind a drained stream) -- a short call keeps these records out of its stream (~2-5 us each)
         if (n_steps > LOOP_RING) {
@@ -3247,10 +3248,7 @@ int sac_train_loop(sac_trainer_t *t, sac_buffer_t *b, int64_t n_steps, float *di
     SAC_REQUIRE(b->O == t->O && b->A == t->A, "buffer dims (%d,%d) do not match trainer dims (%d,%d)", b->O, b->A,
                 t->O, t->A);
     SAC_HIP(hipSetDevice(t->device));
-    if (t->fused && t->pend_n > 0) {          // device-batch steps nobody has verified yet: settle them first
-        if (wait_trainer_stream(t)) return -1;
-        if (recover_device_steps(t) < 0) return -1;
-    }
+    if (settle_trainer(t)) return -1;              // (device-batch steps nobody has verified yet come first)
     if (host_rng_sync_in(b)) return -1;            // (a bound generator: somebody else may have moved np.random)
     // (batches the stepwise interface drew ahead: the generator goes back first -- a speculative first chunk of THIS call,
     //  left by the previous loop call, is not an outside touch and stays: train_loop_run decides about it)
@@ -3284,16 +3282,13 @@ int sac_profile_loop(sac_trainer_t *t, sac_buffer_t *b, int64_t n_steps, float o
     SAC_REQUIRE(b->device == t->device && b->O == t->O && b->A == t->A, "buffer does not match trainer");
     SAC_HIP(hipSetDevice(t->device));
     hipStream_t s = t->stream;
-    t->dev.eps1 = t->dev.eps2 = nullptr;
     if (stage_batches(t, b, n_steps)) return -1;
-    constexpr int NE = 7;            // e0 A e1 B e2 C e3 (nothing) e4 D e5 (nothing) e6
+    constexpr int NE = 7;            // e0 A e1 B e2 C e3 (nothing) e4 D e5 (nothing) e6: StepStage::last_event says which stage they follow
     std::vector<hipEvent_t> ev((size_t)n_steps * NE);
     for (auto &e : ev) SAC_HIP(hipEventCreate(&e));
-    for (int64_t i = 0; i < n_steps; ++i) {
-        t->publish_diag = (i == n_steps - 1);
-        if (launch_step(t, b->d_slots + (size_t)i * b->slot.slot_floats, b->slot, (int)i, &ev[(size_t)i * NE])) return -1;
-    }
-    t->publish_diag = true;
+    for (int64_t i = 0; i < n_steps; ++i)
+        if (launch_step(t, StepCall{b->d_slots + (size_t)i * b->slot.slot_floats, &b->slot, (int)i, i == n_steps - 1, false,
+                                    nullptr, nullptr, &ev[(size_t)i * NE]})) return -1;
     SAC_HIP(hipStreamSynchronize(s));
     if (check_fused_abort(t)) {
         sac::set_error("the fused step gave up during the profiling pass (is another process using this GPU?); the trainer "
@@ -3329,8 +3324,7 @@ int sac_profile_loop(sac_trainer_t *t, sac_buffer_t *b, int64_t n_steps, float o
 int sac_sync(sac_trainer_t *t) {
     SAC_REQUIRE(t, "null trainer");
     SAC_HIP(hipSetDevice(t->device));
-    if (wait_trainer_stream(t)) return -1;
-    return recover_device_steps(t) < 0 ? -1 : 0;
+    return drain_and_recover(t);
 }
 
 // Experiment (bench.py --replicas-per-gpu): confine this trainer's launches to the CUs of the XCDs in `xcd_mask` (bit k =

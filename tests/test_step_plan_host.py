@@ -198,3 +198,114 @@ def test_the_environment_is_read_in_one_place(lib, monkeypatch):
             assert not pat.search(open(os.path.join(CSRC, name)).read()), name
     header = open(os.path.join(CSRC, "sac_step_plan.h")).read()
     assert all('"%s"' % name in header for name in ENV_NAMES)
+
+
+# ---- the step schedule: the plan's launches of one step in launch order (step_schedule) ----------------------------------
+WRAPPER += r"""
+// out: per stage {kernel, grid, threads, lds, need, arg, tail, last_event}; returns the number of stages
+extern "C" int schedule_of(int O, int A, int batch, int algo, int cus, const int *set, const int *val, int fused_now, int *out) {
+    StepEnv E;
+    EnvInt *f[] = {&E.force_sp, &E.wide_min_kq, nullptr, &E.fused, &E.fused_test_stall, &E.chain, &E.chain8, &E.bwd8, &E.chain_bwd};
+    for (int i = 0; i < 9; ++i) {
+        if (!set[i]) continue;
+        if (f[i]) { f[i]->set = true; f[i]->v = val[i]; }
+        else E.dw_form_loop = val[i] == 1;
+    }
+    StepStage st[STEP_STAGES_MAX];
+    const int n = step_schedule(step_plan(O, A, batch, algo, cus, E), fused_now != 0, st);
+    for (int i = 0; i < n; ++i) {
+        const int v[] = {st[i].kernel, st[i].launch.grid, st[i].launch.threads, (int)st[i].launch.lds, st[i].need, st[i].arg,
+                         st[i].tail, st[i].last_event};
+        for (int x : v) *out++ = x;
+    }
+    return n;
+}
+"""
+
+KERNEL_IDS = ["A", "B", "C", "B2", "C2", "FUSED", "CHAINED", "DW", "DW_Q", "DW_PI"]        # enum StepKernelId, in order
+PLAN_LAUNCH = {"A": "a", "B": "b", "C": "c", "B2": "b2", "C2": "c2", "FUSED": "fused_launch", "CHAINED": "chained"}
+ACTOR_FOLLOWS = -1                                                                           # TAIL_ACTOR_FOLLOWS
+
+
+def schedule(lib, O, A, batch, fused_now, algo=0, cus=256, **env):
+    """[(kernel name, launch (grid, threads, lds), need, arg, tail, last_event)] of one step"""
+    sets, vals = [0] * 9, [0] * 9
+    for k, v in env.items():
+        i = ENV_NAMES.index(k)
+        sets[i], vals[i] = 1, (1 if v == "loop" else 0) if k == "SAC_DW_FORM" else int(v)
+    out = (ctypes.c_int * 64)()
+    n = lib.schedule_of(O, A, batch, algo, cus, (ctypes.c_int * 9)(*sets), (ctypes.c_int * 9)(*vals), int(fused_now), out)
+    assert 0 < n <= 8
+    return [(KERNEL_IDS[out[8 * i]], tuple(out[8 * i + 1: 8 * i + 4])) + tuple(out[8 * i + 4: 8 * i + 8]) for i in range(n)]
+
+
+def _check_launches(lib, sched, shape, algo, env):
+    """every stage's launch is the plan's corresponding StepLaunch; a weight-gradient stage: 256 threads, no LDS, no grid"""
+    p = plan(lib, *shape, algo=algo, **env)
+    for name, launch, *_ in sched:
+        assert launch == (p[PLAN_LAUNCH[name]] if name in PLAN_LAUNCH else (0, 256, 0)), (name, launch)
+    return p
+
+
+SAC_FOUR = [("A", 1), ("B", 2), ("C", 4), ("DW", 6)]
+SAC_CHAINED = [("CHAINED", 2), ("C", 4), ("DW", 6)]
+SAC_FUSED = [("FUSED", 4), ("DW", 6)]
+
+
+@pytest.mark.parametrize("shape, env, kind, fused_now, want", [
+    ((42, 7, 256), {"SAC_FUSED": 0}, 0, True, SAC_FOUR),
+    ((42, 7, 256), {"SAC_FUSED": 0}, 0, False, SAC_FOUR),
+    ((379, 6, 1024), {}, 0, True, SAC_FOUR),
+    ((379, 6, 1024), {}, 0, False, SAC_FOUR),
+    ((46, 7, 544), {}, 2, True, SAC_CHAINED),
+    ((46, 7, 544), {}, 2, False, SAC_CHAINED),
+    ((86, 14, 1024), {}, 2, True, SAC_CHAINED),
+    ((86, 14, 1024), {}, 2, False, SAC_CHAINED),
+    ((42, 7, 256), {}, 1, True, SAC_FUSED),
+    ((46, 7, 1024), {}, 4, True, SAC_FUSED),
+    ((42, 7, 256), {}, 1, False, SAC_FOUR),
+    ((46, 7, 1024), {}, 4, False, SAC_CHAINED),
+])
+def test_sac_schedules(lib, shape, env, kind, fused_now, want):
+    s = schedule(lib, *shape, fused_now, **env)
+    p = _check_launches(lib, s, shape, 0, env)
+    assert p["kind"] == kind
+    assert [(name, last_event) for name, _, _, _, _, last_event in s] == want
+    for name, _, need, arg, tail, _ in s:
+        assert (need, arg) == (0, 0)
+        assert tail == (p["compact"] if name == "C" else 0), (name, tail)
+
+
+TD3_ACTOR_PASS = [("B2", 1, 1, 0), ("C2", 2, 1, 0), ("DW_PI", 1, 1, 0)]                       # (kernel, need, arg, tail)
+TD3_FOUR = [("A", 0, 0, ACTOR_FOLLOWS), ("B", 0, 0, 0), ("C", 0, 0, 0), ("DW_Q", 0, 0, 0)] + TD3_ACTOR_PASS
+TD3_FUSED = [("FUSED", 0, 0, ACTOR_FOLLOWS), ("DW_Q", 0, 0, 0)] + TD3_ACTOR_PASS
+
+
+@pytest.mark.parametrize("shape, env, kind, fused_now, want", [
+    ((46, 7, 1024), {}, 0, True, TD3_FOUR),
+    ((46, 7, 1024), {}, 0, False, TD3_FOUR),
+    ((42, 7, 256), {"SAC_FUSED": 0}, 0, True, TD3_FOUR),
+    ((42, 7, 256), {"SAC_FUSED": 0}, 0, False, TD3_FOUR),
+    ((42, 7, 256), {}, 1, True, TD3_FUSED),
+    ((42, 7, 256), {}, 1, False, TD3_FOUR),
+])
+def test_td3_schedules(lib, shape, env, kind, fused_now, want):
+    s = schedule(lib, *shape, fused_now, algo=1, **env)
+    p = _check_launches(lib, s, shape, 1, env)
+    assert p["kind"] == kind and p["compact"] == 0
+    assert [(name, need, arg, tail) for name, _, need, arg, tail, _ in s] == want
+    assert all(last_event == 0 for *_, last_event in s)            # (the profiling pass instruments the SAC step only)
+
+
+def test_profile_event_stream_of_a_schedule(lib):
+    """e0 in front of the first stage; behind each stage the events after the previous stage's last_event up to its own"""
+    def stream(s):
+        out, at = ["e0"], 0
+        for name, *_, last_event in s:
+            out.append(name)
+            out += ["e%d" % k for k in range(at + 1, last_event + 1)]
+            at = max(at, last_event)
+        return out
+    assert stream(schedule(lib, 42, 7, 256, True)) == ["e0", "FUSED", "e1", "e2", "e3", "e4", "DW", "e5", "e6"]
+    assert stream(schedule(lib, 46, 7, 544, True)) == ["e0", "CHAINED", "e1", "e2", "C", "e3", "e4", "DW", "e5", "e6"]
+    assert stream(schedule(lib, 42, 7, 256, False)) == ["e0", "A", "e1", "B", "e2", "C", "e3", "e4", "DW", "e5", "e6"]
