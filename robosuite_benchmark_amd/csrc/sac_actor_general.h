@@ -29,8 +29,8 @@
 // LDS: a plain cast, round to nearest even, the value of numpy's astype(float32).  The fp32 instance is k_act_layer's.
 //
 // GenNet::P and the layer offsets.  A general-step trainer's networks live in sac_general::arena, which
-// gen_build_sac / gen_build_td3 (sac_general_host.h) allocate once and carve with a bump allocator; gen_shape_net, the
-// only writer of offW / offB, runs there and nowhere else.  No general step path, no group loop (MLP and arch groups
+// gen_build / gen_build_td3 (sac_general_host.h) allocate once and carve with the trainer's Arena; param_shape
+// (sac_param_map.h), the only writer of offW / offB, runs in their opening (gen_open) and nowhere else.  No general step path, no group loop (MLP and arch groups
 // launch on the members' own tables), no sac_set_params / sac_set_opt_state / sac_set_scalars and no checkpoint load
 // allocates, frees or re-lays the arena: all of them write INTO GenNet::P.  The table is therefore valid for the trainer
 // handle's life and sac_gactor_act only asserts that (one pointer compare per member).  What does end a table entry is

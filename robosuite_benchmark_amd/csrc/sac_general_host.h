@@ -1,14 +1,13 @@
 // Host side of the general-shape SAC step (sac_general.h): network tables, the job lists of the matrix-product
-// launches, parameter transfer, the step's launch sequence.  Included by sac_trainer.hip behind struct sac_trainer.
+// launches, the step's launch sequence.  Included by sac_trainer.hip behind struct sac_trainer and Arena.
 #pragma once
 
-struct GenLayer { int N = 0, K = 0; long long offW = 0, offB = 0; };
-struct GenNet {
+static_assert(gen::GMAXL == PARAM_LAYERS_MAX, "the parameter map holds the general step's layers");
+struct GenNet {                             // (its layers and their offsets: param_shape, sac_param_map.h)
     int nl = 0;
-    GenLayer L[gen::GMAXL];
-    long long n = 0, nflat = 0;             // floats of the device vector (every W starts on a 16-byte boundary) / of the flat vector
+    Layer L[gen::GMAXL] = {};
+    long long n = 0;                        // floats of the device vector (every W starts on a 16-byte boundary)
     float *P = nullptr, *M = nullptr, *V = nullptr, *G = nullptr;
-    std::vector<long long> perm;            // flat (sac_get_params) index -> index in the device vector
 };
 constexpr int GEN_MAX_JOBS = 16 * gen::GMAXJ;
 struct GenStage { int kind = 0, mode = 0; size_t base = 0; gen::GemmStage gs{}; };   // mode: 0 forward, 1 backward, 2 weight gradients   // kind 0: a k_g_gemm launch; else see launch
@@ -28,48 +27,6 @@ struct sac_general {
 };
 
 namespace {
-
-struct GenBump {
-    std::vector<std::pair<void **, size_t>> req;
-    size_t total = 0;
-    template <typename T> void want(T **p, long long count) {
-        req.emplace_back(reinterpret_cast<void **>(p), total);
-        total += ((size_t)count * sizeof(T) + 255) & ~(size_t)255;
-    }
-};
-
-void gen_shape_net(GenNet &N, const int *hidden, int nh, int in_dim, int out_dim, bool merged_heads, int A) {
-    long long off = 0, flat = 0;
-    int d = in_dim;
-    N.nl = nh + 1;
-    for (int l = 0; l <= nh; ++l) {
-        GenLayer &L = N.L[l];
-        L.N = (l < nh) ? hidden[l] : out_dim; L.K = d;
-        off = (off + 3) & ~3LL;                              // (16-byte loads of the matrix-product kernel)
-        L.offW = off; off += (long long)L.N * L.K;
-        L.offB = off; off += L.N;
-        flat += (long long)L.N * L.K + L.N;
-        d = L.N;
-    }
-    N.n = (off + 3) & ~3LL; N.nflat = flat;
-    // flat layout: per layer W then b, packed; the policy's two heads are two layers there (last_fc, last_fc_log_std) and
-    // ONE layer of 2A outputs here ([W_mean ; W_log_std] then [b_mean ; b_log_std])
-    N.perm.resize((size_t)flat);
-    long long fi = 0;
-    for (int l = 0; l <= nh; ++l) {
-        const GenLayer &L = N.L[l];
-        if (l == nh && merged_heads) {
-            const long long AK = (long long)A * L.K;
-            for (long long i = 0; i < AK; ++i) N.perm[(size_t)fi++] = L.offW + i;               // last_fc.weight
-            for (int a = 0; a < A; ++a) N.perm[(size_t)fi++] = L.offB + a;                      // last_fc.bias
-            for (long long i = 0; i < AK; ++i) N.perm[(size_t)fi++] = L.offW + AK + i;          // last_fc_log_std.weight
-            for (int a = 0; a < A; ++a) N.perm[(size_t)fi++] = L.offB + A + a;                  // last_fc_log_std.bias
-        } else {
-            for (long long i = 0; i < (long long)L.N * L.K; ++i) N.perm[(size_t)fi++] = L.offW + i;
-            for (int i = 0; i < L.N; ++i) N.perm[(size_t)fi++] = L.offB + i;
-        }
-    }
-}
 
 gen::GemmJob gen_job_zero() { gen::GemmJob J; memset(&J, 0, sizeof(J)); return J; }
 
@@ -94,7 +51,7 @@ gen::GemmJob gen_bwd(const float *dY, int M, int Nl, const float *W, int K, int 
 }
 // dW = dY^T X over `rows` rows, db = column sums of dY (dY [rows][Nl], X [rows][K]) for layer L of net N, whose owner tiles
 // apply Adam at learning rate lr and the Polyak average into `target` (null: none) in their epilogue
-gen::GemmJob gen_dw(const float *dY, const float *X, int rows, const GenNet &N, const GenLayer &L, float lr, const GenNet *target) {
+gen::GemmJob gen_dw(const float *dY, const float *X, int rows, const GenNet &N, const Layer &L, float lr, const GenNet *target) {
     gen::GemmJob J = gen_job_zero();
     J.A = dY; J.sa_m = 1; J.sa_r = L.N;
     J.Bm = X; J.sb_n = 1; J.sb_r = L.K;
@@ -170,29 +127,62 @@ int gen_commit_plan(sac_trainer *t, GenPlanner &pl, std::initializer_list<std::v
     return 0;
 }
 
-int gen_build(sac_trainer *t, const int *hp, int np_, const int *hq, int nq_) {
+// What gen_build and gen_build_td3 open with: the shapes into sac_general and the parameter map (SAC: nets 0..4, the
+// policy's two heads one layer of 2A outputs; TD3: nets 0..5, one head), the operand-offset check, and the arena's first
+// reservations -- the nets' arrays.
+int gen_open(sac_trainer *t, const int *hp, int np_, const int *hq, int nq_, Arena &bump) {
     sac_general *g = new sac_general();
     t->gen = g;
     const int n = t->Bt, O = t->O, A = t->A;
     g->n = n; g->O = O; g->A = A; g->Lp = np_; g->Lq = nq_;
     for (int i = 0; i < np_; ++i) g->hp[i] = hp[i];
     for (int i = 0; i < nq_; ++i) g->hq[i] = hq[i];
-    gen_shape_net(g->net[0], hp, np_, O, 2 * A, true, A);
-    for (int i = 1; i < 5; ++i) gen_shape_net(g->net[i], hq, nq_, O + A, 1, false, A);
-    const int Lp = np_, Lq = nq_, ldq = O + A;
     {   // the matrix-product kernel indexes its operands with 32-bit offsets
-        long long widest = ldq;
+        long long widest = O + A;
         for (int i = 0; i < np_; ++i) widest = hp[i] > widest ? hp[i] : widest;
         for (int i = 0; i < nq_; ++i) widest = hq[i] > widest ? hq[i] : widest;
         SAC_REQUIRE(3LL * n * widest < (1LL << 31) && widest * widest < (1LL << 31),
                     "batch %d x layer width %lld is beyond the general step's 32-bit operand offsets", n, widest);
     }
-
-    GenBump bump;
-    for (int i = 0; i < 5; ++i) {
-        bump.want(&g->net[i].P, g->net[i].n);
-        if (i < 3) { bump.want(&g->net[i].M, g->net[i].n); bump.want(&g->net[i].V, g->net[i].n); bump.want(&g->net[i].G, g->net[i].n); }
+    t->shape = param_shape(PF_GENERAL, t->algo, O, A, hp, np_, hq, nq_);
+    for (int i = 0; i < (t->algo == 1 ? 6 : 5); ++i) {
+        GenNet &N = g->net[i];
+        const int q = param_kind(i);
+        N.nl = t->shape.nh[q] + 1; N.n = t->shape.n[q];
+        for (int l = 0; l < N.nl; ++l) N.L[l] = t->shape.L[q][l];
+        bump.want(&N.P, N.n);
+        if (i < 3) { bump.want(&N.M, N.n); bump.want(&N.V, N.n); bump.want(&N.G, N.n); }
     }
+    return 0;
+}
+
+// ... and what they reserve last -- what the entry points of sac_trainer.hip share with the fused kernels' trainers
+// (host-batch slot, caller-supplied noise, diagnostics, entropy state) and the job table -- and the commit
+int gen_commit_arena(sac_trainer *t, Arena &bump) {
+    t->ext_layout = make_slot_layout(t->Bt, t->O, t->A);
+    bump.want(&t->ext_slot, t->ext_layout.slot_floats);
+    bump.want(&t->d_eps, 2LL * t->B * t->A);
+    bump.want(&t->d_diag, (long long)SAC_DIAG_N * (2 + DIAG_TRACE_CAP));
+    bump.want(&t->d_ctl, 1);
+    bump.want(&t->gen->d_jobs, GEN_MAX_JOBS);
+    return bump.commit(&t->gen->arena, t->stream);
+}
+
+// the fields of GDev that both algorithms fill alike
+void gen_wire_dev(sac_trainer *t) {
+    gen::GDev &d = t->gen->dev;
+    d.n = t->Bt; d.O = t->O; d.A = t->A; d.NI = 16; d.ldq = t->O + t->A;
+    d.ctl = t->d_ctl;
+    d.diag_first = t->d_diag_host; d.diag_last = t->d_diag_host + SAC_DIAG_N; d.diag_trace = t->d_diag + 2 * SAC_DIAG_N;
+    d.diag_dev = t->d_diag;
+    d.eps1 = d.eps2 = nullptr;
+}
+
+int gen_build(sac_trainer *t, const int *hp, int np_, const int *hq, int nq_) {
+    Arena bump;
+    if (int rc = gen_open(t, hp, np_, hq, nq_, bump)) return rc;
+    sac_general *g = t->gen;
+    const int n = t->Bt, O = t->O, A = t->A, Lp = np_, Lq = nq_, ldq = O + A;
     gen::GDev &d = g->dev;
     float *PH[gen::GMAXL] = {}, *dPZ[gen::GMAXL] = {}, *HD = nullptr;
     float *QH[2][gen::GMAXL] = {}, *TH[2][gen::GMAXL] = {}, *dQZ[2][gen::GMAXL] = {}, *QO[4] = {}, *DA[2] = {};
@@ -209,30 +199,15 @@ int gen_build(sac_trainer *t, const int *hp, int np_, const int *hq, int nq_) {
         bump.want(&QO[k], 2LL * n); bump.want(&QO[2 + k], n); bump.want(&d.DQ[k], 2LL * n); bump.want(&DA[k], (long long)n * A);
     }
     bump.want(&d.DHD, (long long)n * 2 * A);
-    // shared with the entry points of sac_trainer.hip: host-batch slot, caller-supplied noise, diagnostics, entropy state
-    t->ext_layout = make_slot_layout(t->Bt, O, A);
-    bump.want(&t->ext_slot, t->ext_layout.slot_floats);
-    bump.want(&t->d_eps, 2LL * t->B * A);
-    bump.want(&t->d_diag, (long long)SAC_DIAG_N * (2 + DIAG_TRACE_CAP));
-    bump.want(&t->d_ctl, 1);
-    bump.want(&g->d_jobs, GEN_MAX_JOBS);
-    {
-        const size_t bytes = (bump.total + ((size_t)2 << 20) - 1) & ~(((size_t)2 << 20) - 1);
-        SAC_HIP(hipMalloc(reinterpret_cast<void **>(&g->arena), bytes));
-        SAC_HIP(hipMemsetAsync(g->arena, 0, bytes, t->stream));
-        for (auto &r : bump.req) *r.first = g->arena + r.second;
-    }
+    if (gen_commit_arena(t, bump)) return -1;
+    gen_wire_dev(t);
     const sac_config_t &cfg = t->cfg;
-    d.n = n; d.O = O; d.A = A; d.NI = 16; d.ldq = ldq;
     d.discount = cfg.discount; d.reward_scale = cfg.reward_scale; d.tau = cfg.soft_target_tau;
     d.target_entropy = std::isnan(cfg.target_entropy) ? -(float)A : cfg.target_entropy;
     d.alpha_lr = cfg.policy_lr; d.period = cfg.target_update_period; d.auto_alpha = cfg.use_automatic_entropy_tuning;
-    d.noise_seed = cfg.noise_seed; d.ctl = t->d_ctl; d.HD = HD;
+    d.noise_seed = cfg.noise_seed; d.HD = HD;
     for (int k = 0; k < 4; ++k) d.QO[k] = QO[k];
     for (int k = 0; k < 2; ++k) d.DA[k] = DA[k];
-    d.diag_first = t->d_diag_host; d.diag_last = t->d_diag_host + SAC_DIAG_N; d.diag_trace = t->d_diag + 2 * SAC_DIAG_N;
-    d.diag_dev = t->d_diag;
-    d.eps1 = d.eps2 = nullptr;
     const float lrs[3] = {cfg.policy_lr, cfg.qf_lr, cfg.qf_lr};
 
     // ---- the launch sequence ----
@@ -247,7 +222,7 @@ int gen_build(sac_trainer *t, const int *hp, int np_, const int *hq, int nq_) {
 
     const SlotLayout &XL = t->ext_layout;               // (the buffer's slots have the same layout: make_slot_layout(batch, O, A))
     for (int l = 0; l < Lp; ++l) {                       // policy trunk on [s ; s']: the first layer reads the slot's rows
-        const GenLayer &L = g->net[0].L[l];
+        const Layer &L = g->net[0].L[l];
         begin(0);
         if (l == 0) {
             gen::GemmJob Js = gen_fwd(nullptr, n, Wp(0, 0), Bp(0, 0), L.N, L.K, PH[0], 1), Jn = Js;
@@ -273,12 +248,12 @@ int gen_build(sac_trainer *t, const int *hp, int np_, const int *hq, int nq_) {
     for (int l = 0; l < Lq; ++l) {                       // Q1, Q2 on [(s,a) ; (s,a_new)], targets on (s',a'): the hidden layers
         begin(0);
         for (int k = 0; k < 2; ++k) {
-            const GenLayer &L = g->net[1 + k].L[l];
+            const Layer &L = g->net[1 + k].L[l];
             float *out = l < Lq ? QH[k][l] : QO[k];
             add(gen_fwd(l == 0 ? d.XQ : QH[k][l - 1], 2 * n, Wp(1 + k, l), Bp(1 + k, l), L.N, L.K, out, l < Lq));
         }
         for (int k = 0; k < 2; ++k) {
-            const GenLayer &L = g->net[3 + k].L[l];
+            const Layer &L = g->net[3 + k].L[l];
             float *out = l < Lq ? TH[k][l] : QO[2 + k];
             add(gen_fwd(l == 0 ? d.XQ + 2LL * n * ldq : TH[k][l - 1], n, Wp(3 + k, l), Bp(3 + k, l), L.N, L.K, out, l < Lq));
         }
@@ -288,26 +263,26 @@ int gen_build(sac_trainer *t, const int *hp, int np_, const int *hq, int nq_) {
     for (int j = Lq - 1; j >= 1; --j) {                  // backward through hidden layer j of Q1, Q2 (critic and actor rows)
         begin(1);
         for (int k = 0; k < 2; ++k) {
-            const GenLayer &L = g->net[1 + k].L[j];
+            const Layer &L = g->net[1 + k].L[j];
             add(gen_bwd(dQZ[k][j], 2 * n, L.N, Wp(1 + k, j), L.K, 0, L.K, dQZ[k][j - 1], L.K, QH[k][j - 1], L.K));
         }
         end();
     }
     plain(GS_POLGRAD);
     for (int j = Lp - 1; j >= 1; --j) {                  // backward through the policy's hidden layers (rows of s only)
-        const GenLayer &L = g->net[0].L[j];
+        const Layer &L = g->net[0].L[j];
         begin(1); add(gen_bwd(dPZ[j], n, L.N, Wp(0, j), L.K, 0, L.K, dPZ[j - 1], L.K, PH[j - 1], L.K)); end();
     }
     begin(2);                                             // every weight gradient of the step
     for (int l = Lp; l >= 0; --l) {
-        const GenLayer &L = g->net[0].L[l];
+        const Layer &L = g->net[0].L[l];
         gen::GemmJob Jw = gen_dw(l == Lp ? d.DHD : dPZ[l], l == 0 ? nullptr : PH[l - 1], n, g->net[0], L, lrs[0], nullptr);
         if (l == 0) { Jw.b_slot = 1; Jw.b_off = XL.off_obs; }
         add(Jw);
     }
     for (int k = 0; k < 2; ++k)
         for (int l = Lq; l >= 0; --l) {
-            const GenLayer &L = g->net[1 + k].L[l];
+            const Layer &L = g->net[1 + k].L[l];
             add(gen_dw(l == Lq ? d.DQ[k] : dQZ[k][l], l == 0 ? d.XQ : QH[k][l - 1], n, g->net[1 + k], L, lrs[1 + k], &g->net[3 + k]));
         }
     end();
@@ -317,28 +292,10 @@ int gen_build(sac_trainer *t, const int *hp, int np_, const int *hq, int nq_) {
 
 // TD3 (td3_trainer_create_mlp): nets 0 policy (one head of A outputs, tanh), 1, 2 critics, 3, 4 their targets, 5 target policy
 int gen_build_td3(sac_trainer *t, const td3_config_t *c, const int *hp, int np_, const int *hq, int nq_) {
-    sac_general *g = new sac_general();
-    t->gen = g;
-    const int n = t->Bt, O = t->O, A = t->A;
-    g->n = n; g->O = O; g->A = A; g->Lp = np_; g->Lq = nq_;
-    for (int i = 0; i < np_; ++i) g->hp[i] = hp[i];
-    for (int i = 0; i < nq_; ++i) g->hq[i] = hq[i];
-    gen_shape_net(g->net[0], hp, np_, O, A, false, A);
-    gen_shape_net(g->net[5], hp, np_, O, A, false, A);
-    for (int i = 1; i < 5; ++i) gen_shape_net(g->net[i], hq, nq_, O + A, 1, false, A);
-    const int Lp = np_, Lq = nq_, ldq = O + A;
-    {
-        long long widest = ldq;
-        for (int i = 0; i < np_; ++i) widest = hp[i] > widest ? hp[i] : widest;
-        for (int i = 0; i < nq_; ++i) widest = hq[i] > widest ? hq[i] : widest;
-        SAC_REQUIRE(3LL * n * widest < (1LL << 31) && widest * widest < (1LL << 31),
-                    "batch %d x layer width %lld is beyond the general step's 32-bit operand offsets", n, widest);
-    }
-    GenBump bump;
-    for (int i = 0; i < 6; ++i) {
-        bump.want(&g->net[i].P, g->net[i].n);
-        if (i < 3) { bump.want(&g->net[i].M, g->net[i].n); bump.want(&g->net[i].V, g->net[i].n); bump.want(&g->net[i].G, g->net[i].n); }
-    }
+    Arena bump;
+    if (int rc = gen_open(t, hp, np_, hq, nq_, bump)) return rc;
+    sac_general *g = t->gen;
+    const int n = t->Bt, O = t->O, A = t->A, Lp = np_, Lq = nq_, ldq = O + A;
     gen::GDev &d = g->dev;
     float *PHT[gen::GMAXL] = {}, *PHP[gen::GMAXL] = {}, *dPZ[gen::GMAXL] = {}, *HDT = nullptr, *HDP = nullptr;
     float *QH[2][gen::GMAXL] = {}, *TH[2][gen::GMAXL] = {}, *dQZ[2][gen::GMAXL] = {}, *QO[4] = {};
@@ -353,27 +310,14 @@ int gen_build_td3(sac_trainer *t, const td3_config_t *c, const int *hp, int np_,
         bump.want(&QO[k], n); bump.want(&QO[2 + k], n); bump.want(&d.DQ[k], n);
     }
     for (int l = 0; l < Lq; ++l) { bump.want(&AH[l], (long long)n * hq[l]); bump.want(&dAZ[l], (long long)n * hq[l]); }
-    t->ext_layout = make_slot_layout(t->Bt, O, A);
-    bump.want(&t->ext_slot, t->ext_layout.slot_floats);
-    bump.want(&t->d_eps, 2LL * t->B * A);
-    bump.want(&t->d_diag, (long long)SAC_DIAG_N * (2 + DIAG_TRACE_CAP));
-    bump.want(&t->d_ctl, 1);
-    bump.want(&g->d_jobs, GEN_MAX_JOBS);
-    {
-        const size_t bytes = (bump.total + ((size_t)2 << 20) - 1) & ~(((size_t)2 << 20) - 1);
-        SAC_HIP(hipMalloc(reinterpret_cast<void **>(&g->arena), bytes));
-        SAC_HIP(hipMemsetAsync(g->arena, 0, bytes, t->stream));
-        for (auto &r : bump.req) *r.first = g->arena + r.second;
-    }
-    d.n = n; d.O = O; d.A = A; d.NI = 16; d.ldq = ldq; d.algo = 1;
+    if (gen_commit_arena(t, bump)) return -1;
+    gen_wire_dev(t);
+    d.algo = 1;
     d.discount = c->discount; d.reward_scale = c->reward_scale; d.tau = c->tau; d.period = 1; d.auto_alpha = 0;
-    d.noise_seed = c->noise_seed; d.ctl = t->d_ctl;
+    d.noise_seed = c->noise_seed;
     d.td3_sigma = c->target_policy_noise; d.td3_clip = c->target_policy_noise_clip;
     d.HDT = HDT; d.HDP = HDP; d.QA = QA; d.DAa = DAa;
     for (int k = 0; k < 4; ++k) d.QO[k] = QO[k];
-    d.diag_first = t->d_diag_host; d.diag_last = t->d_diag_host + SAC_DIAG_N; d.diag_trace = t->d_diag + 2 * SAC_DIAG_N;
-    d.diag_dev = t->d_diag;
-    d.eps1 = d.eps2 = nullptr;
     GenPlanner pl;
     const SlotLayout &XL = t->ext_layout;
     auto Wp = [&](int net, int l) { return g->net[net].P + g->net[net].L[l].offW; };
@@ -382,7 +326,7 @@ int gen_build_td3(sac_trainer *t, const td3_config_t *c, const int *hp, int np_,
     // behind it, like every layer of a handful of outputs: see gen_build)
     auto policy_fwd = [&](int net, long long off, float **PHx) {
         for (int l = 0; l < Lp; ++l) {
-            const GenLayer &L = g->net[net].L[l];
+            const Layer &L = g->net[net].L[l];
             gen::GemmJob J = gen_fwd(l == 0 ? nullptr : PHx[l - 1], n, Wp(net, l), Bp(net, l), L.N, L.K, PHx[l], 1);
             if (l == 0) { J.a_slot = 1; J.a_off = off; }
             pl.one(0, J);
@@ -401,11 +345,11 @@ int gen_build_td3(sac_trainer *t, const td3_config_t *c, const int *hp, int np_,
     for (int l = 0; l < Lq; ++l) {                       // Q1, Q2 on (s, a), their targets on (s', a~): the hidden layers
         pl.begin(0);
         for (int k = 0; k < 2; ++k) {
-            const GenLayer &L = g->net[1 + k].L[l];
+            const Layer &L = g->net[1 + k].L[l];
             pl.add(gen_fwd(l == 0 ? d.XQ : QH[k][l - 1], n, Wp(1 + k, l), Bp(1 + k, l), L.N, L.K, l < Lq ? QH[k][l] : QO[k], l < Lq));
         }
         for (int k = 0; k < 2; ++k) {
-            const GenLayer &L = g->net[3 + k].L[l];
+            const Layer &L = g->net[3 + k].L[l];
             pl.add(gen_fwd(l == 0 ? d.XQ + (long long)n * ldq : TH[k][l - 1], n, Wp(3 + k, l), Bp(3 + k, l), L.N, L.K, l < Lq ? TH[k][l] : QO[2 + k], l < Lq));
         }
         pl.end();
@@ -414,7 +358,7 @@ int gen_build_td3(sac_trainer *t, const td3_config_t *c, const int *hp, int np_,
     for (int j = Lq - 1; j >= 1; --j) {
         pl.begin(1);
         for (int k = 0; k < 2; ++k) {
-            const GenLayer &L = g->net[1 + k].L[j];
+            const Layer &L = g->net[1 + k].L[j];
             pl.add(gen_bwd(dQZ[k][j], n, L.N, Wp(1 + k, j), L.K, 0, L.K, dQZ[k][j - 1], L.K, QH[k][j - 1], L.K));
         }
         pl.end();
@@ -422,7 +366,7 @@ int gen_build_td3(sac_trainer *t, const td3_config_t *c, const int *hp, int np_,
     pl.begin(2);
     for (int k = 0; k < 2; ++k)
         for (int l = Lq; l >= 0; --l) {
-            const GenLayer &L = g->net[1 + k].L[l];
+            const Layer &L = g->net[1 + k].L[l];
             pl.add(gen_dw(l == Lq ? d.DQ[k] : dQZ[k][l], l == 0 ? d.XQ : QH[k][l - 1], n, g->net[1 + k], L, c->qf_learning_rate, &g->net[3 + k]));
         }
     pl.end();
@@ -433,24 +377,24 @@ int gen_build_td3(sac_trainer *t, const td3_config_t *c, const int *hp, int np_,
         policy_fwd(0, XL.off_obs, PHP);
         pl.plain(GS_TD3_AHEAD);
         for (int l = 0; l < Lq; ++l) {                   // Q1(s, policy(s)) through the updated qf1: the hidden layers
-            const GenLayer &L = g->net[1].L[l];
+            const Layer &L = g->net[1].L[l];
             pl.one(0, gen_fwd(l == 0 ? d.XA : AH[l - 1], n, Wp(1, l), Bp(1, l), L.N, L.K, AH[l], 1));
         }
         pl.plain(GS_TD3_QA);                             // its last layer (and, on policy steps, the backward pass through it)
         pl.list->back().mode = full;
         if (full) {
             for (int j = Lq - 1; j >= 1; --j) {
-                const GenLayer &L = g->net[1].L[j];
+                const Layer &L = g->net[1].L[j];
                 pl.one(1, gen_bwd(dAZ[j], n, L.N, Wp(1, j), L.K, 0, L.K, dAZ[j - 1], L.K, AH[j - 1], L.K));
             }
             pl.plain(GS_TD3_POLGRAD);
             for (int j = Lp - 1; j >= 1; --j) {
-                const GenLayer &L = g->net[0].L[j];
+                const Layer &L = g->net[0].L[j];
                 pl.one(1, gen_bwd(dPZ[j], n, L.N, Wp(0, j), L.K, 0, L.K, dPZ[j - 1], L.K, PHP[j - 1], L.K));
             }
             pl.begin(2);
             for (int l = Lp; l >= 0; --l) {
-                const GenLayer &L = g->net[0].L[l];
+                const Layer &L = g->net[0].L[l];
                 gen::GemmJob Jw = gen_dw(l == Lp ? d.DHP : dPZ[l], l == 0 ? nullptr : PHP[l - 1], n, g->net[0], L, c->policy_learning_rate, &g->net[5]);
                 if (l == 0) { Jw.b_slot = 1; Jw.b_off = XL.off_obs; }
                 pl.add(Jw);
@@ -468,32 +412,6 @@ void gen_destroy(sac_general *g) {
     if (g->d_scratch) (void)hipFree(g->d_scratch);
     if (g->d_tile_cnt) (void)hipFree(g->d_tile_cnt);
     delete g;
-}
-
-int gen_upload(sac_trainer *t, int net, const float *flat, float *dst) {
-    const GenNet &N = t->gen->net[net];
-    std::vector<float> h((size_t)N.n, 0.f);
-    for (long long i = 0; i < N.nflat; ++i) h[(size_t)N.perm[(size_t)i]] = flat[i];
-    SAC_HIP(hipMemcpyAsync(dst, h.data(), sizeof(float) * h.size(), hipMemcpyHostToDevice, t->stream));
-    SAC_HIP(hipStreamSynchronize(t->stream));
-    return 0;
-}
-
-int gen_download(sac_trainer *t, int net, const float *src, float *flat) {
-    const GenNet &N = t->gen->net[net];
-    std::vector<float> h((size_t)N.n);
-    SAC_HIP(hipMemcpyAsync(h.data(), src, sizeof(float) * h.size(), hipMemcpyDeviceToHost, t->stream));
-    SAC_HIP(hipStreamSynchronize(t->stream));
-    for (long long i = 0; i < N.nflat; ++i) flat[i] = h[(size_t)N.perm[(size_t)i]];
-    return 0;
-}
-
-// elements x with !(x == 0) (non-finite ones count) of a padded device array, read back as h, at the positions that no
-// flat index maps to (reach[i] == 0)
-int64_t count_unreached_nonzero(const std::vector<float> &h, const std::vector<char> &reach) {
-    int64_t c = 0;
-    for (size_t i = 0; i < h.size(); ++i) c += (!reach[i] && !(h[i] == 0.f)) ? 1 : 0;
-    return c;
 }
 
 // one launch list on minibatch slot S
@@ -579,70 +497,6 @@ int gen_launch_step(sac_trainer *t, const StepCall &c) {
     t->n_train_steps_total += 1;
     t->adam_t += 1;
     return 0;
-}
-
-// sac_debug_fetch on a general trainer: the same names, rows of the true batch
-int64_t gen_debug_fetch(sac_trainer *t, const std::string &nm, float *out, int64_t cap) {
-    sac_general *g = t->gen;
-    const gen::GDev &d = g->dev;
-    const int64_t n = g->n, nA = (int64_t)g->n * g->A;
-    struct V { const char *name; const float *p; int64_t cnt; };
-    if (t->algo == 1) {
-        const V tv[] = {{"a_next", d.a2, nA}, {"a_new", d.pa, nA}, {"q1", d.QO[0], n}, {"q2", d.QO[1], n}, {"tq1", d.QO[2], n},
-                        {"tq2", d.QO[3], n}, {"q_target", d.y, n}, {"q1_new", d.QA, n},
-                        {"diag_trace", d.diag_trace, (int64_t)DIAG_TRACE_CAP * SAC_DIAG_N}};
-        for (const V &v : tv)
-            if (nm == v.name) {
-                const int64_t cnt = nm == "diag_trace" && cap < v.cnt ? cap : v.cnt;
-                if (cap < cnt) { sac::set_error("buffer too small"); return -2; }
-                if (hipMemcpyAsync(out, v.p, sizeof(float) * cnt, hipMemcpyDeviceToHost, t->stream) != hipSuccess ||
-                    hipStreamSynchronize(t->stream) != hipSuccess) { sac::set_error("copy failed in sac_debug_fetch"); return -1; }
-                return cnt;
-            }
-    }
-    const V vs[] = {{"a_new", d.anew, nA}, {"mu", d.mu, nA}, {"log_std", d.ls, nA}, {"a_next", d.a2, nA},
-                    {"log_pi", d.logpi, n}, {"log_pi_next", d.logpi2, n}, {"q1", d.QO[0], n}, {"q2", d.QO[1], n},
-                    {"q1_new", d.QO[0] + n, n}, {"q2_new", d.QO[1] + n, n}, {"tq1", d.QO[2], n}, {"tq2", d.QO[3], n},
-                    {"q_target", d.y, n}, {"diag_trace", d.diag_trace, (int64_t)DIAG_TRACE_CAP * SAC_DIAG_N}};
-    for (const V &v : vs)
-        if (t->algo == 0 && nm == v.name) {
-            const int64_t cnt = nm == "diag_trace" && cap < v.cnt ? cap : v.cnt;
-            if (cap < cnt) { sac::set_error("buffer too small"); return -2; }
-            if (hipMemcpyAsync(out, v.p, sizeof(float) * cnt, hipMemcpyDeviceToHost, t->stream) != hipSuccess ||
-                hipStreamSynchronize(t->stream) != hipSuccess) { sac::set_error("copy failed in sac_debug_fetch"); return -1; }
-            return cnt;
-        }
-    const char *gn[3] = {"g_policy", "g_qf1", "g_qf2"};
-    for (int i = 0; i < 3; ++i)
-        if (nm == gn[i]) {
-            if (cap < g->net[i].nflat) { sac::set_error("buffer too small"); return -2; }
-            if (gen_download(t, i, g->net[i].G, out)) return -1;
-            return g->net[i].nflat;
-        }
-    // Elements x with !(x == 0) of the device vectors outside GenNet::perm (the alignment gaps in front of each W and at
-    // the end).  Order: for each trained net 0..2 (policy, qf1, qf2) the counts of P, M, V; then the count of P for each
-    // target net 3, 4 (TD3: and 5).  11 floats (TD3: 12).  (The general step keeps no transposed copy: no "pt_<net>".)
-    if (nm == "pad_nonzero") {
-        const int nnets = t->algo == 1 ? 6 : 5;
-        const int64_t cnt = 3 * 3 + (nnets - 3);
-        if (cap < cnt) { sac::set_error("buffer too small"); return -2; }
-        int64_t o = 0;
-        for (int i = 0; i < nnets; ++i) {
-            const GenNet &N = g->net[i];
-            std::vector<char> reach((size_t)N.n, 0);
-            for (long long fi = 0; fi < N.nflat; ++fi) reach[(size_t)N.perm[(size_t)fi]] = 1;
-            std::vector<float> h((size_t)N.n);
-            const float *arrs[3] = {N.P, N.M, N.V};
-            for (int a = 0; a < (i < 3 ? 3 : 1); ++a) {
-                if (hipMemcpyAsync(h.data(), arrs[a], sizeof(float) * h.size(), hipMemcpyDeviceToHost, t->stream) != hipSuccess ||
-                    hipStreamSynchronize(t->stream) != hipSuccess) { sac::set_error("copy failed in sac_debug_fetch"); return -1; }
-                out[o++] = (float)count_unreached_nonzero(h, reach);
-            }
-        }
-        return cnt;
-    }
-    sac::set_error("unknown debug tensor '%s'", nm.c_str());
-    return -2;
 }
 
 }  // namespace

@@ -627,7 +627,7 @@ int infer_scratch_reserve(sac_trainer *t, int n, int widest, int slices, size_t 
 }
 
 // what every per-layer job says about layer L of net N (vec: W's rows may be fetched in 16-byte pieces)
-void infer_layer_job(sac::LayerJob &J, const GenNet &N, const GenLayer &L) {
+void infer_layer_job(sac::LayerJob &J, const GenNet &N, const Layer &L) {
     J.W = N.P + L.offW; J.b = N.P + L.offB;
     J.N = L.N; J.K = L.K;
     J.tiles_n = (L.N + AG_CT - 1) / AG_CT;
@@ -670,7 +670,7 @@ struct LayerSchedule {
         const float *x = c.x, *x2 = c.x2;
         const int n = c.n;
         for (int l = 0; l < (c.with_last ? G.nl : G.nl - 1); ++l) {
-            const GenLayer &L = G.L[l];
+            const Layer &L = G.L[l];
             const bool last = l + 1 == G.nl;
             const int launch = c.at + l;
             sac::LayerJob &J = h[(size_t)launch * stride + njobs[launch]++];

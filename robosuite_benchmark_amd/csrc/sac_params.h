@@ -6,15 +6,7 @@
 // A job is one TENSOR of the flat nn.Linear layout of sac_get_params: fc<i>.weight, fc<i>.bias, ..., last_fc.weight,
 // last_fc.bias and, on a SAC policy, last_fc_log_std.weight, last_fc_log_std.bias (two tensors of their own, although the
 // device keeps both heads in one layer).  Its E elements are taken in flat order e = 0 .. E - 1; where element e lives
-// is param_addr's business -- the ONE statement of the two layouts:
-//
-//   PA_FLAT   off + e: every bias, and every weight of the general step (W row-major at GenNet::P + offW; the log-std
-//             head's rows behind the mean head's, as GenNet::perm splits them)
-//   PA_FRAG   a weight of the fused kernels' shapes, element (n, k) = (e / K, e % K): k' = k below O, KP + (k - O) from
-//             O on (the action columns of a Q net's first layer), row n + nshift (nshift = A for the log-std head);
-//             the forward copy at off + frag_off(n + nshift, k', ld), the transposed copy -- where the weights' Adam
-//             moments live (MT / VT) -- at offT + frag_off(k', n + nshift, ldT): what for_each_param with download_padded
-//             reads
+// is param_addr's business (sac_param_map.h: the tensor list and the address rule the getters use, PA_FLAT or PA_FRAG).
 //
 // Pads are never an element, so they cannot enter a sum.  The record is SAC_PARAM_FIELDS_N float64 per tensor, every
 // value formed in float64 from the float32 words with add, multiply, compare and fabs only (the product of two float32
@@ -48,22 +40,6 @@ namespace sac {
 
 constexpr int PM_CH = 16384;              // elements of one chunk (one workgroup)
 constexpr int PM_LANES = 256;
-
-enum { PA_FLAT = 0, PA_FRAG = 1 };
-
-struct ParamAddr {
-    long long off, offT;           // PA_FLAT: first element.  PA_FRAG: the layer's offW / offWt
-    int kind, K, O, KP, nshift, ld, ldT, pad_;
-};
-
-// where flat element e of a tensor lives (transposed: in the transposed copy, PA_FRAG only)
-static inline __host__ __device__ long long param_addr(const ParamAddr &a, long long e, bool transposed) {
-    if (a.kind == PA_FLAT) return a.off + e;
-    const int n = (int)(e / a.K), k = (int)(e - (long long)n * a.K);
-    const int kk = k >= a.O ? a.KP + (k - a.O) : k;
-    return transposed ? a.offT + (long long)frag_off(kk, n + a.nshift, a.ldT)
-                      : a.off + (long long)frag_off(n + a.nshift, kk, a.ld);
-}
 
 struct ParamJob {
     const float *X, *T;            // the net's parameters; its target's (same layout) or null
@@ -159,49 +135,6 @@ __global__ __launch_bounds__(PM_LANES) void k_param_finish(const ParamJob *__res
 namespace {
 
 constexpr int PARAM_NETS = 6;
-constexpr int PARAM_MAX_TENSORS = 2 * gen::GMAXL + 2;       // W and b per layer; a SAC policy's second head
-
-struct ParamTensor { ParamAddr a; long long E; };
-
-// the tensors of net `net` of trainer t in flat order: where each lives (both families).  Returns their number.
-int param_tensor_list(const sac_trainer *t, int net, ParamTensor *out) {
-    int n = 0;
-    auto flat = [&](long long off, long long E) {
-        ParamTensor &P = out[n++];
-        P = ParamTensor{};
-        P.a.kind = PA_FLAT; P.a.off = off; P.a.K = 1; P.E = E;
-    };
-    if (t->gen) {
-        const GenNet &G = t->gen->net[net];
-        const bool merged = t->algo == 0 && net == SAC_NET_POLICY;
-        for (int l = 0; l < G.nl; ++l) {
-            const GenLayer &L = G.L[l];
-            if (l == G.nl - 1 && merged) {
-                const long long AK = (long long)t->A * L.K;
-                flat(L.offW, AK); flat(L.offB, t->A);
-                flat(L.offW + AK, AK); flat(L.offB + t->A, t->A);
-            } else {
-                flat(L.offW, (long long)L.N * L.K); flat(L.offB, L.N);
-            }
-        }
-        return n;
-    }
-    const FlatMap f = flat_map(t, net);
-    for (int l = 0; l < f.nl; ++l) {
-        const int dl = l < 2 ? l : 2;
-        const int nshift = (net == SAC_NET_POLICY && l == 3) ? t->A : 0;
-        const bool qin = net >= 1 && net <= 4 && l == 0;
-        const Layer &L = t->net[net].L[dl];
-        ParamTensor &P = out[n++];
-        P = ParamTensor{};
-        P.a.kind = PA_FRAG; P.a.off = L.offW; P.a.offT = L.offWt;
-        P.a.K = f.K[l]; P.a.O = qin ? t->O : f.K[l]; P.a.KP = t->KP;
-        P.a.nshift = nshift; P.a.ld = L.Kp; P.a.ldT = L.Np;
-        P.E = (long long)f.N[l] * f.K[l];
-        flat(L.offB + nshift, f.N[l]);
-    }
-    return n;
-}
 
 // the target a trained net is paired with, or -1
 int param_target_of(const sac_trainer *t, int net) {
@@ -216,7 +149,7 @@ int param_target_of(const sac_trainer *t, int net) {
 int sac_param_tensors(const sac_trainer_t *t, int net, int64_t *sizes) {
     SAC_REQUIRE(t && net >= 0 && net <= (t->algo == 1 ? 5 : 4), "bad arguments to sac_param_tensors");
     ParamTensor T[PARAM_MAX_TENSORS];
-    const int n = param_tensor_list(t, net, T);
+    const int n = param_tensor_list(t->shape, net, T);
     if (sizes) for (int i = 0; i < n; ++i) sizes[i] = T[i].E;
     return n;
 }
@@ -247,7 +180,7 @@ int sac_param_moments_many(sac_trainer_t *const *trainers, int n_trainers, sac_p
     for (int i = 0; i < n_trainers; ++i)
         for (int k = 0; k < PARAM_NETS; ++k) {
             if (!(io[i].nets >> k & 1u)) continue;
-            const int n = param_tensor_list(trainers[i], k, T);
+            const int n = param_tensor_list(trainers[i]->shape, k, T);
             for (int j = 0; j < n; ++j) chunks += (size_t)((T[j].E + PM_CH - 1) / PM_CH);
             recs[i] += (size_t)n;
             jobs += (size_t)n;
@@ -265,25 +198,18 @@ int sac_param_moments_many(sac_trainer_t *const *trainers, int n_trainers, sac_p
         const sac_trainer *t = trainers[i];
         for (int k = 0; k < PARAM_NETS; ++k) {
             if (!(io[i].nets >> k & 1u)) continue;
-            const int n = param_tensor_list(t, k, T);
+            const int n = param_tensor_list(t->shape, k, T);
             const bool opt = (io[i].flags & SAC_PARAMS_OPT) && k <= 2;
             const int tk = (io[i].flags & SAC_PARAMS_GAP) ? param_target_of(t, k) : -1;
+            const NetArrays N = net_arrays(t, k);
             for (int j = 0; j < n; ++j) {
                 ParamJob &J = tab[nj];
                 J = ParamJob{};
                 J.a = T[j].a; J.E = T[j].E;
-                if (t->gen) {
-                    const GenNet &G = t->gen->net[k];
-                    J.X = G.P;
-                    if (opt) { J.M = G.M; J.V = G.V; }
-                    if (tk >= 0) J.T = t->gen->net[tk].P;
-                } else {
-                    const Net &N = t->net[k];
-                    J.X = N.P;
-                    J.mt = T[j].a.kind == PA_FRAG ? 1 : 0;
-                    if (opt) { J.M = J.mt ? N.MT : N.M; J.V = J.mt ? N.VT : N.V; }
-                    if (tk >= 0) J.T = t->net[tk].P;
-                }
+                J.X = N.P;
+                J.mt = T[j].a.kind == PA_FRAG ? 1 : 0;
+                if (opt) { J.M = J.mt ? N.MT : N.M; J.V = J.mt ? N.VT : N.V; }
+                if (tk >= 0) J.T = net_arrays(t, tk).P;
                 J.nch = (int)((J.E + PM_CH - 1) / PM_CH);
                 J.wg0 = wgs;
                 J.part = part + (size_t)wgs * SAC_PARAM_FIELDS_N;

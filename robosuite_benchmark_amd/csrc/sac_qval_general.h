@@ -5,7 +5,7 @@
 // times up to 4 selected nets in one launch; a call is one launch per layer depth, max(layers) launches on the first
 // member's stream and one wait at the end: k_act_layer's scheme (sac_act_general.h).  It reads the general step's live
 // critic weights where they are (sac_general::net[SAC_NET_QF1 .. SAC_NET_TARGET_QF2].P: nn.Linear layout W [N][K] then
-// b, at GenLayer::offW / offB): nothing is repacked, mirrored or copied.
+// b, at Layer::offW / offB): nothing is repacked, mirrored or copied.
 //
 //   table   a launch carries up to QG_JOBS = 4 SAC_GROUP_MAX jobs (LayerJob, device-visible memory, read with scalar
 //           loads): a job is (member, selected net, layer l).  Launch l holds layer l of every (member, net) that has

@@ -92,13 +92,7 @@ struct Ctl {                       // device-resident state of the entropy coeff
 
 struct AlphaStep { float alpha, alpha_loss, log_alpha, m, v; };
 
-struct Layer {                     // one nn.Linear in the padded device layout
-    int N, K, Np, Kp;
-    long long offW, offB;          // in P / M / V / G : W [Np][Kp] fragment-major (frag_off), b [Np]
-    long long offWt;               // in PT / MT / VT : W^T [Kp + 16][Np] fragment-major (frag_off)
-};
-
-struct Net {
+struct Net {                       // (Layer: sac_param_map.h)
     float *P = nullptr, *M = nullptr, *V = nullptr, *PT = nullptr, *MT = nullptr, *VT = nullptr, *G = nullptr;
     long long nP = 0, nPT = 0;
     Layer L[3];
@@ -1983,6 +1977,7 @@ struct sac_trainer {
     StepKernels k{};                                  // ... and the kernel instances behind it (c: k_bwd8 where the plan says so)
     Net net[6];                                       // 5: TD3 target policy
     int HP[2] = {256, 256}, HQ[2] = {256, 256};       // logical hidden sizes (<= 256: zero-padded to the kernels' 256)
+    ParamShape shape{};                               // where the nets' parameters live (sac_param_map.h; both families)
     int algo = 0;                                     // 0 SAC, 1 TD3
     int td3_period = 2;                               // policy_and_target_update_period
     long long adam_t_pi = 0;                          // TD3: optimizer steps of the policy (delayed)
@@ -2070,85 +2065,40 @@ struct StepCall {
     hipEvent_t *ev;                // sac_profile_loop: seven events around the stages, or null
 };
 
+namespace {
+
+// One arena for every device buffer of a trainer (weights, Adam state, activations, control words):
+// a single 2-MiB-aligned allocation keeps the whole working set (a few MB) on a handful of large
+// pages, so a kernel's first touches do not each pay an address-translation miss.  Buffers lie in the
+// order they are asked for, each on a 256-byte boundary.
+struct Arena {
+    std::vector<std::pair<void **, size_t>> req;
+    size_t total = 0;
+    template <typename T> void want(T **p, long long count) {
+        req.emplace_back(reinterpret_cast<void **>(p), total);
+        total += ((size_t)count * sizeof(T) + 255) & ~(size_t)255;
+    }
+    int commit(char **base, hipStream_t s) {
+        const size_t bytes = (total + ((size_t)2 << 20) - 1) & ~(((size_t)2 << 20) - 1);
+        SAC_HIP(hipMalloc(reinterpret_cast<void **>(base), bytes));
+        SAC_HIP(hipMemsetAsync(*base, 0, bytes, s));
+        for (auto &r : req) *r.first = *base + r.second;
+        return 0;
+    }
+};
+
+}  // namespace
+
 #include "sac_general_host.h"
 
 namespace {
 
-void build_layers(Net &n, const int (*shape)[2], int nl) {
-    long long off = 0, offt = 0;
-    for (int l = 0; l < nl; ++l) {
-        Layer &L = n.L[l];
-        L.N = shape[l][0]; L.K = shape[l][1];
-        L.Np = round_up(L.N, 16); L.Kp = round_up(L.K, 16);
-        L.offW = off; off += (long long)L.Np * L.Kp;
-        L.offB = off; off += L.Np;
-        off = round_up64(off, 4);
-        L.offWt = offt; offt += (long long)(L.Kp + 16) * L.Np;
-    }
-    n.nP = off; n.nPT = offt;
-}
-
-// One arena for every device buffer of a trainer (weights, Adam state, activations, control words):
-// a single 2-MiB-aligned allocation keeps the whole working set (a few MB) on a handful of large
-// pages, so a kernel's first touches do not each pay an address-translation miss.
-struct Arena {
-    std::vector<std::pair<void **, size_t>> req;
-    size_t total = 0;
-    void reserve(void **p, size_t bytes) {
-        req.emplace_back(p, total);
-        total += (bytes + 255) & ~(size_t)255;
-    }
-};
-thread_local Arena *g_arena = nullptr;      // only during sac_trainer_create
-
-int alloc_zero(float **p, long long n, hipStream_t) {
-    g_arena->reserve(reinterpret_cast<void **>(p), sizeof(float) * (size_t)n);
-    return 0;
-}
-
-int arena_commit(Arena &a, char **base, hipStream_t s) {
-    const size_t bytes = (a.total + ((size_t)2 << 20) - 1) & ~(((size_t)2 << 20) - 1);
-    SAC_HIP(hipMalloc(reinterpret_cast<void **>(base), bytes));
-    SAC_HIP(hipMemsetAsync(*base, 0, bytes, s));
-    for (auto &r : a.req) *r.first = *base + r.second;
-    return 0;
-}
-
-// flat nn.Linear layout <-> padded device layout (host vectors)
-struct FlatMap { int nl; int N[4], K[4]; };   // logical layers in the flat vector
-
-FlatMap flat_map(const sac_trainer *t, int netid) {
-    FlatMap f{};
-    if (netid == SAC_NET_POLICY || netid == 5) {
-        f.nl = t->algo == 1 ? 3 : 4;                        // TD3: TanhMlpPolicy (one head); SAC: mean + log-std heads
-        f.N[0] = t->HP[0]; f.K[0] = t->O; f.N[1] = t->HP[1]; f.K[1] = t->HP[0];
-        f.N[2] = t->A; f.K[2] = t->HP[1]; f.N[3] = t->A; f.K[3] = t->HP[1];
-    } else {
-        f.nl = 3;
-        f.N[0] = t->HQ[0]; f.K[0] = t->O + t->A; f.N[1] = t->HQ[1]; f.K[1] = t->HQ[0]; f.N[2] = 1; f.K[2] = t->HQ[1];
-    }
-    return f;
-}
-
-int64_t flat_count(const FlatMap &f) {
-    int64_t n = 0;
-    for (int l = 0; l < f.nl; ++l) n += (int64_t)f.N[l] * f.K[l] + f.N[l];
-    return n;
-}
-
-// iterate (flat index) -> (device layer, n, k | bias)
-template <typename F>
-void for_each_param(const sac_trainer *t, int netid, F &&fn) {
-    const FlatMap f = flat_map(t, netid);
-    int64_t fi = 0;
-    for (int l = 0; l < f.nl; ++l) {
-        const int dl = (l < 2) ? l : 2;                       // policy heads share device layer 2
-        const int nshift = (netid == SAC_NET_POLICY && l == 3) ? t->A : 0;
-        const bool qin = (netid >= 1 && netid <= 4) && l == 0;   // Q first layer: action columns start at KP
-        for (int n = 0; n < f.N[l]; ++n)
-            for (int k = 0; k < f.K[l]; ++k) fn(fi++, dl, n + nshift, (qin && k >= t->O) ? t->KP + (k - t->O) : k, false);
-        for (int n = 0; n < f.N[l]; ++n) fn(fi++, dl, n + nshift, 0, true);
-    }
+// the device arrays of a net in the trainer's family (a general net has no transposed copies; a target net only P)
+struct NetArrays { float *P, *M, *V, *PT, *MT, *VT, *G; };
+NetArrays net_arrays(const sac_trainer *t, int net) {
+    if (t->gen) { const GenNet &N = t->gen->net[net]; return {N.P, N.M, N.V, nullptr, nullptr, nullptr, N.G}; }
+    const Net &N = t->net[net];
+    return {N.P, N.M, N.V, N.PT, N.MT, N.VT, N.G};
 }
 
 int ensure_stage_t(sac_trainer *t, size_t bytes) {
@@ -2518,17 +2468,17 @@ static int trainer_alloc(sac_trainer *t, const sac_config_t *cfg, const td3_conf
     hipStream_t s = t->stream;
     const int B = t->B;
     Arena arena;
-    g_arena = &arena;
-    const int shp[3][2] = {{H, t->O}, {H, H}, {(td3 ? 1 : 2) * t->A, H}};
-    const int shq[3][2] = {{H, t->KQ}, {H, H}, {1, H}};     // device K of the Q first layer: padded [obs | act] layout
+    t->shape = param_shape(PF_FUSED, t->algo, t->O, t->A, t->HP, 2, t->HQ, 2);
     const int nnets = td3 ? 6 : 5;
     for (int i = 0; i < nnets; ++i) {
         Net &n = t->net[i];
-        build_layers(n, (i == 0 || i == 5) ? shp : shq, 3);
-        if (alloc_zero(&n.P, n.nP, s)) return -1;
+        const int q = param_kind(i);
+        for (int l = 0; l < 3; ++l) n.L[l] = t->shape.L[q][l];
+        n.nP = t->shape.n[q]; n.nPT = t->shape.nT[q];
+        arena.want(&n.P, n.nP);
         if (i < 3) {
-            if (alloc_zero(&n.M, n.nP, s) || alloc_zero(&n.V, n.nP, s) || alloc_zero(&n.PT, n.nPT, s) ||
-                alloc_zero(&n.MT, n.nPT, s) || alloc_zero(&n.VT, n.nPT, s) || alloc_zero(&n.G, n.nP, s)) return -1;
+            arena.want(&n.M, n.nP); arena.want(&n.V, n.nP); arena.want(&n.PT, n.nPT);
+            arena.want(&n.MT, n.nPT); arena.want(&n.VT, n.nPT); arena.want(&n.G, n.nP);
         }
     }
     // workspace carve
@@ -2544,19 +2494,18 @@ static int trainer_alloc(sac_trainer *t, const sac_config_t *cfg, const td3_conf
         {&d.dheadT, (long long)t->NH * B}, {&d.dPH2T, (long long)H * B}, {&d.dPH1T, (long long)H * B}};
     long long tot = 0;
     for (auto &p : parts) tot += round_up64(p.second, 64);
-    if (alloc_zero(&t->ws, tot, s)) return -1;
+    arena.want(&t->ws, tot);
     t->ws_floats = tot;
     t->ext_layout = make_slot_layout(t->Bt, t->O, t->A);
-    if (alloc_zero(&t->ext_slot, t->ext_layout.slot_floats, s)) return -1;
-    if (alloc_zero(&t->d_eps, 2LL * B * t->A, s)) return -1;
-    if (alloc_zero(&t->d_diag, (long long)SAC_DIAG_N * (2 + DIAG_TRACE_CAP), s)) return -1;
-    arena.reserve(reinterpret_cast<void **>(&t->d_ctl), sizeof(Ctl));
+    arena.want(&t->ext_slot, t->ext_layout.slot_floats);
+    arena.want(&t->d_eps, 2LL * B * t->A);
+    arena.want(&t->d_diag, (long long)SAC_DIAG_N * (2 + DIAG_TRACE_CAP));
+    arena.want(&t->d_ctl, 1);
     // head[2][NB], qa / tq / ac [NB], log-pi, abort; then zx[6][NB] (the exchange of the split first layers)
     t->sync_bytes = sizeof(unsigned) * sync_words(t->NB);      // (the regions: sac_step_plan.h)
-    arena.reserve(reinterpret_cast<void **>(&t->d_sync), t->sync_bytes);
-    arena.reserve(reinterpret_cast<void **>(&t->d_dwl), sizeof(DwLayer) * NDW * 3);
-    g_arena = nullptr;
-    if (arena_commit(arena, &t->arena, s)) return -1;
+    arena.want(&t->d_sync, (long long)sync_words(t->NB));
+    arena.want(&t->d_dwl, NDW * 3);
+    if (arena.commit(&t->arena, s)) return -1;
     tot = 0;
     for (auto &p : parts) { *p.first = t->ws + tot; tot += round_up64(p.second, 64); }
 
@@ -2794,45 +2743,36 @@ int sac_trainer_destroy(sac_trainer_t *t) {
 
 int64_t sac_param_count(const sac_trainer_t *t, int net) {
     if (!t || net < 0 || net > (t->algo == 1 ? 5 : 4)) return -1;
-    if (t->gen) return t->gen->net[net].nflat;
-    return flat_count(flat_map(t, net));
+    ParamTensor T[PARAM_MAX_TENSORS];
+    return param_count(T, param_tensor_list(t->shape, net, T));
 }
 
-static int upload_padded(sac_trainer *t, int net, const float *flat, float *devbuf, float *devT) {
-    Net &n = t->net[net];
-    const bool also_transposed = devT != nullptr;
-    std::vector<float> P((size_t)n.nP, 0.f), PT;
-    if (also_transposed) PT.assign((size_t)n.nPT, 0.f);
-    for_each_param(t, net, [&](int64_t fi, int l, int nn, int k, bool is_b) {
-        const Layer &L = n.L[l];
-        if (is_b) P[L.offB + nn] = flat[fi];
-        else {
-            P[L.offW + frag_off(nn, k, L.Kp)] = flat[fi];
-            if (also_transposed) PT[L.offWt + frag_off(k, nn, L.Np)] = flat[fi];
-        }
-    });
-    SAC_HIP(hipMemcpyAsync(devbuf, P.data(), sizeof(float) * P.size(), hipMemcpyHostToDevice, t->stream));
-    if (also_transposed)
-        SAC_HIP(hipMemcpyAsync(devT, PT.data(), sizeof(float) * PT.size(), hipMemcpyHostToDevice, t->stream));
+// a flat vector into a device array of net `net` (pads +0.0) and, where dstT is given (a fused trained net), its weights
+// into the transposed array as well
+static int params_upload(sac_trainer *t, int net, const float *flat, float *dst, float *dstT) {
+    ParamTensor T[PARAM_MAX_TENSORS];
+    const int nt = param_tensor_list(t->shape, net, T), q = param_kind(net);
+    std::vector<float> P((size_t)t->shape.n[q], 0.f), PT((size_t)(dstT ? t->shape.nT[q] : 0), 0.f);
+    param_scatter(T, nt, flat, P.data(), false);
+    SAC_HIP(hipMemcpyAsync(dst, P.data(), sizeof(float) * P.size(), hipMemcpyHostToDevice, t->stream));
+    if (dstT) {
+        param_scatter(T, nt, flat, PT.data(), true);
+        SAC_HIP(hipMemcpyAsync(dstT, PT.data(), sizeof(float) * PT.size(), hipMemcpyHostToDevice, t->stream));
+    }
     SAC_HIP(hipStreamSynchronize(t->stream));
     return 0;
 }
 
-// weights come from the transposed buffer when devT is given (Adam moments), else from devbuf
-static int download_padded(sac_trainer *t, int net, const float *devbuf, float *flat, const float *devT = nullptr) {
-    Net &n = t->net[net];
-    std::vector<float> P((size_t)n.nP), PT;
-    SAC_HIP(hipMemcpyAsync(P.data(), devbuf, sizeof(float) * P.size(), hipMemcpyDeviceToHost, t->stream));
-    if (devT) {
-        PT.resize((size_t)n.nPT);
-        SAC_HIP(hipMemcpyAsync(PT.data(), devT, sizeof(float) * PT.size(), hipMemcpyDeviceToHost, t->stream));
-    }
+// the flat vector of a device array; weights come from the transposed array where srcT is given (Adam moments, "pt_<net>")
+static int params_download(sac_trainer *t, int net, const float *src, const float *srcT, float *flat) {
+    ParamTensor T[PARAM_MAX_TENSORS];
+    const int nt = param_tensor_list(t->shape, net, T), q = param_kind(net);
+    std::vector<float> P((size_t)t->shape.n[q]), PT((size_t)(srcT ? t->shape.nT[q] : 0));
+    SAC_HIP(hipMemcpyAsync(P.data(), src, sizeof(float) * P.size(), hipMemcpyDeviceToHost, t->stream));
+    if (srcT) SAC_HIP(hipMemcpyAsync(PT.data(), srcT, sizeof(float) * PT.size(), hipMemcpyDeviceToHost, t->stream));
     SAC_HIP(hipStreamSynchronize(t->stream));
-    for_each_param(t, net, [&](int64_t fi, int l, int nn, int k, bool is_b) {
-        const Layer &L = n.L[l];
-        if (is_b) flat[fi] = P[L.offB + nn];
-        else flat[fi] = devT ? PT[L.offWt + frag_off(k, nn, L.Np)] : P[L.offW + frag_off(nn, k, L.Kp)];
-    });
+    param_gather(T, nt, P.data(), flat, false);
+    if (srcT) param_gather(T, nt, PT.data(), flat, true);
     return 0;
 }
 
@@ -2843,8 +2783,8 @@ int sac_set_params(sac_trainer_t *t, int net, const float *flat, int64_t n) {
     SAC_HIP(hipSetDevice(t->device));
     if (settle_trainer(t)) return -1;
     t->mirror_valid = false;
-    if (t->gen) return gen_upload(t, net, flat, t->gen->net[net].P);
-    return upload_padded(t, net, flat, t->net[net].P, net < 3 ? t->net[net].PT : nullptr);
+    const NetArrays N = net_arrays(t, net);
+    return params_upload(t, net, flat, N.P, N.PT);
 }
 
 int sac_get_params(sac_trainer_t *t, int net, float *flat, int64_t n) {
@@ -2853,8 +2793,7 @@ int sac_get_params(sac_trainer_t *t, int net, float *flat, int64_t n) {
                 (long long)sac_param_count(t, net), (long long)n);
     SAC_HIP(hipSetDevice(t->device));
     if (settle_trainer(t)) return -1;
-    if (t->gen) return gen_download(t, net, t->gen->net[net].P, flat);
-    return download_padded(t, net, t->net[net].P, flat);
+    return params_download(t, net, net_arrays(t, net).P, nullptr, flat);
 }
 
 int sac_set_opt_state(sac_trainer_t *t, int net, const float *m, const float *v, int64_t n) {
@@ -2862,9 +2801,8 @@ int sac_set_opt_state(sac_trainer_t *t, int net, const float *m, const float *v,
     SAC_REQUIRE(n == sac_param_count(t, net), "size mismatch in sac_set_opt_state");
     SAC_HIP(hipSetDevice(t->device));
     if (settle_trainer(t)) return -1;
-    if (t->gen) return gen_upload(t, net, m, t->gen->net[net].M) || gen_upload(t, net, v, t->gen->net[net].V) ? -1 : 0;
-    if (upload_padded(t, net, m, t->net[net].M, t->net[net].MT)) return -1;
-    return upload_padded(t, net, v, t->net[net].V, t->net[net].VT);
+    const NetArrays N = net_arrays(t, net);
+    return params_upload(t, net, m, N.M, N.MT) || params_upload(t, net, v, N.V, N.VT) ? -1 : 0;
 }
 
 int sac_get_opt_state(sac_trainer_t *t, int net, float *m, float *v, int64_t n) {
@@ -2872,9 +2810,8 @@ int sac_get_opt_state(sac_trainer_t *t, int net, float *m, float *v, int64_t n) 
     SAC_REQUIRE(n == sac_param_count(t, net), "size mismatch in sac_get_opt_state");
     SAC_HIP(hipSetDevice(t->device));
     if (settle_trainer(t)) return -1;
-    if (t->gen) return gen_download(t, net, t->gen->net[net].M, m) || gen_download(t, net, t->gen->net[net].V, v) ? -1 : 0;
-    if (download_padded(t, net, t->net[net].M, m, t->net[net].MT)) return -1;
-    return download_padded(t, net, t->net[net].V, v, t->net[net].VT);
+    const NetArrays N = net_arrays(t, net);
+    return params_download(t, net, N.M, N.MT, m) || params_download(t, net, N.V, N.VT, v) ? -1 : 0;
 }
 
 int sac_set_scalars(sac_trainer_t *t, const double sc[6]) {
@@ -3404,106 +3341,124 @@ int sac_debug_set_launch_number(sac_trainer_t *t, uint32_t seq) {
     return 0;
 }
 
+// One tensor sac_debug_fetch answers by name: rows x cols floats, `stride` floats from one row to the next on the device.
+struct FetchEntry { const char *name; const float *src; int64_t rows, cols, stride; };
+constexpr int FETCH_MAX = 16;
+
+// The names a trainer answers from the table, per (family, algo); rows of the true batch.  Returns their number.
+static int fetch_table(const sac_trainer *t, FetchEntry *E) {
+    int n = 0;
+    const int64_t Bt = t->Bt, A = t->A;
+    auto rows = [&](const char *name, const float *p, int64_t stride) { E[n++] = FetchEntry{name, p, Bt, A, stride}; };
+    auto vec = [&](const char *name, const float *p) { E[n++] = FetchEntry{name, p, Bt, 1, 1}; };
+    if (!t->gen) {                                         // the fused kernels' shapes, SAC and TD3: head values [B][16]
+        const Dev &d = t->dev;
+        const size_t B = (size_t)t->B;
+        rows("a_new", d.anew, 16); rows("mu", d.mu, 16); rows("log_std", d.ls, 16); rows("a_next", d.a2, 16); rows("z", d.z, 16);
+        vec("log_pi", d.logpi); vec("log_pi_next", d.logpi2); vec("q1", d.q); vec("q2", d.q + B);
+        vec("q1_new", d.q + 2 * B); vec("q2_new", d.q + 3 * B); vec("tq1", d.q + 4 * B); vec("tq2", d.q + 5 * B);
+        vec("q_target", d.y);
+    } else if (t->algo == 0) {                             // the general step, SAC
+        const gen::GDev &d = t->gen->dev;
+        rows("a_new", d.anew, A); rows("mu", d.mu, A); rows("log_std", d.ls, A); rows("a_next", d.a2, A);
+        vec("log_pi", d.logpi); vec("log_pi_next", d.logpi2); vec("q1", d.QO[0]); vec("q2", d.QO[1]);
+        vec("q1_new", d.QO[0] + Bt); vec("q2_new", d.QO[1] + Bt); vec("tq1", d.QO[2]); vec("tq2", d.QO[3]);
+        vec("q_target", d.y);
+    } else {                                               // the general step, TD3
+        const gen::GDev &d = t->gen->dev;
+        rows("a_next", d.a2, A); rows("a_new", d.pa, A);
+        vec("q1", d.QO[0]); vec("q2", d.QO[1]); vec("tq1", d.QO[2]); vec("tq2", d.QO[3]); vec("q_target", d.y);
+        vec("q1_new", d.QA);
+    }
+    E[n++] = FetchEntry{"diag_trace", t->d_diag + 2 * SAC_DIAG_N, (int64_t)DIAG_TRACE_CAP * SAC_DIAG_N, 1, 1};
+    return n;
+}
+
+static int fetch_floats(sac_trainer *t, const float *src, int64_t n, float *dst) {
+    if (hipMemcpyAsync(dst, src, sizeof(float) * n, hipMemcpyDeviceToHost, t->stream) != hipSuccess ||
+        hipStreamSynchronize(t->stream) != hipSuccess) { sac::set_error("copy failed in sac_debug_fetch"); return -1; }
+    return 0;
+}
+
+// the copy behind every entry: the cap check ("diag_trace" alone is cut to what fits instead), the copy on the trainer's
+// stream, padded rows compacted
+static int64_t fetch_copy(sac_trainer *t, const FetchEntry &e, float *out, int64_t cap) {
+    const bool cut = !strcmp(e.name, "diag_trace") && cap < e.rows * e.cols;
+    const int64_t rows = cut ? cap / e.cols : e.rows, n = rows * e.cols;
+    if (cap < n) { sac::set_error("buffer too small"); return -2; }
+    if (e.stride == e.cols) return fetch_floats(t, e.src, n, out) ? -1 : n;
+    std::vector<float> h((size_t)(rows * e.stride));
+    if (fetch_floats(t, e.src, rows * e.stride, h.data())) return -1;
+    for (int64_t r = 0; r < rows; ++r) memcpy(out + r * e.cols, h.data() + r * e.stride, sizeof(float) * e.cols);
+    return n;
+}
+
+// elements x with !(x == 0) (non-finite ones count) of a padded device array, read back as h, at the positions that no
+// flat index maps to (reach[i] == 0)
+static int64_t count_unreached_nonzero(const std::vector<float> &h, const std::vector<char> &reach) {
+    int64_t c = 0;
+    for (size_t i = 0; i < h.size(); ++i) c += (!reach[i] && !(h[i] == 0.f)) ? 1 : 0;
+    return c;
+}
+
 int64_t sac_debug_fetch(sac_trainer_t *t, const char *name, float *out, int64_t cap) {
     if (!t || !name || !out) { sac::set_error("bad arguments to sac_debug_fetch"); return -2; }
     if (hipSetDevice(t->device) != hipSuccess) { sac::set_error("hipSetDevice failed"); return -1; }
     const std::string nm(name);
     // the readers of trained state ("pt_<net>", "pad_nonzero") see it as of the last completed step, as sac_get_params does
     if ((nm == "pad_nonzero" || nm.rfind("pt_", 0) == 0) && settle_trainer(t)) return -1;
-    if (t->gen) return gen_debug_fetch(t, nm, out, cap);
-    const int B = t->B, A = t->A;
-    const Dev &d = t->dev;
-    auto fetch = [&](const float *src, int64_t n, std::vector<float> &h) -> int {
-        h.resize((size_t)n);
-        SAC_HIP(hipMemcpyAsync(h.data(), src, sizeof(float) * n, hipMemcpyDeviceToHost, t->stream));
-        SAC_HIP(hipStreamSynchronize(t->stream));
-        return 0;
-    };
-    std::vector<float> h;
-    // the flat nn.Linear vector of a trained net as the backward passes (and Adam) see it: weights from the transposed
-    // copy PT, biases from P.  Bit-equal to sac_get_params while the two copies agree.
-    const char *ptn[3] = {"pt_policy", "pt_qf1", "pt_qf2"};
-    for (int i = 0; i < 3; ++i)
-        if (nm == ptn[i]) {
-            const int64_t n = sac_param_count(t, i);
-            if (cap < n) { sac::set_error("buffer too small"); return -2; }
-            if (download_padded(t, i, t->net[i].P, out, t->net[i].PT)) return -1;
-            return n;
-        }
-    // Elements x with !(x == 0) (non-finite ones count) at the positions of the padded arrays that the flat map
-    // (for_each_param) does not reach: row and column padding, the action-column gap of a Q first layer, alignment gaps,
-    // the +16 rows of the transposed arrays.  Order: for each trained net 0..2 (policy, qf1, qf2) the counts of P, PT, MT,
-    // VT; then the count of P for each target net 3, 4 (TD3: and 5).  14 floats (TD3: 15).
+    // "pt_<net>": the flat nn.Linear vector of a trained net as the backward passes (and Adam) see it -- weights from the
+    // transposed copy PT, biases from P; bit-equal to sac_get_params while the two copies agree (the general step keeps no
+    // transposed copy: no such name there).  "g_<net>": its gradient.
+    const char *trained[3] = {"policy", "qf1", "qf2"};
+    for (int i = 0; i < 3; ++i) {
+        const NetArrays N = net_arrays(t, i);
+        const bool pt = N.PT && nm == std::string("pt_") + trained[i], g = nm == std::string("g_") + trained[i];
+        if (!pt && !g) continue;
+        const int64_t n = sac_param_count(t, i);
+        if (cap < n) { sac::set_error("buffer too small"); return -2; }
+        if (params_download(t, i, pt ? N.P : N.G, pt ? N.PT : nullptr, out)) return -1;
+        return n;
+    }
+    // Elements x with !(x == 0) (non-finite ones count) at the positions of the device arrays that the parameter map does
+    // not reach: row and column padding, the action-column gap of a Q first layer, alignment gaps, the +16 rows of the
+    // transposed arrays.  Order: for each trained net 0..2 (policy, qf1, qf2) the counts of P, PT, MT, VT (general step:
+    // of P, M, V); then the count of P for each target net 3, 4 (TD3: and 5).  14 floats (TD3: 15; general step: 11 / 12).
     if (nm == "pad_nonzero") {
-        const int nnets = t->algo == 1 ? 6 : 5;
-        const int64_t n = 4 * 3 + (nnets - 3);
+        const int nnets = t->algo == 1 ? 6 : 5, per = t->gen ? 3 : 4;
+        const int64_t n = per * 3 + (nnets - 3);
         if (cap < n) { sac::set_error("buffer too small"); return -2; }
         int64_t o = 0;
+        ParamTensor T[PARAM_MAX_TENSORS];
+        std::vector<float> h;
         for (int i = 0; i < nnets; ++i) {
-            const Net &N = t->net[i];
-            std::vector<char> fwd((size_t)N.nP, 0), tr((size_t)(i < 3 ? N.nPT : 0), 0);
-            for_each_param(t, i, [&](int64_t, int l, int nn, int k, bool is_b) {
-                const Layer &L = N.L[l];
-                if (is_b) fwd[(size_t)L.offB + nn] = 1;
-                else {
-                    fwd[(size_t)L.offW + frag_off(nn, k, L.Kp)] = 1;
-                    if (i < 3) tr[(size_t)L.offWt + frag_off(k, nn, L.Np)] = 1;
-                }
-            });
+            const int nt = param_tensor_list(t->shape, i, T), q = param_kind(i);
+            const NetArrays N = net_arrays(t, i);
+            std::vector<char> fwd((size_t)t->shape.n[q], 0), tr((size_t)(N.PT ? t->shape.nT[q] : 0), 0);
+            param_reach(T, nt, fwd.data(), false);
+            if (N.PT) param_reach(T, nt, tr.data(), true);
             struct Arr { const float *p; const std::vector<char> *reach; };
-            const Arr arrs[4] = {{N.P, &fwd}, {N.PT, &tr}, {N.MT, &tr}, {N.VT, &tr}};
-            for (int a = 0; a < (i < 3 ? 4 : 1); ++a) {
-                if (fetch(arrs[a].p, (int64_t)arrs[a].reach->size(), h)) return -1;
+            const Arr fused[4] = {{N.P, &fwd}, {N.PT, &tr}, {N.MT, &tr}, {N.VT, &tr}};
+            const Arr general[3] = {{N.P, &fwd}, {N.M, &fwd}, {N.V, &fwd}};
+            const Arr *arrs = t->gen ? general : fused;
+            for (int a = 0; a < (i < 3 ? per : 1); ++a) {
+                h.resize(arrs[a].reach->size());
+                if (fetch_floats(t, arrs[a].p, (int64_t)h.size(), h.data())) return -1;
                 out[o++] = (float)count_unreached_nonzero(h, *arrs[a].reach);
             }
         }
         return n;
     }
-    if (nm == "ext_img_sa" || nm == "ext_img_n") {          // a row image of the external-batch slot (sac_step's staging)
+    if (!t->gen && (nm == "ext_img_sa" || nm == "ext_img_n")) {   // a row image of the external-batch slot (sac_step's staging)
         const SlotLayout &L = t->ext_layout;
-        const int64_t n = (int64_t)L.B * L.KLQ;
         if (!L.has_images()) { sac::set_error("the external-batch slot carries no row images"); return -2; }
-        if (cap < n) { sac::set_error("buffer too small"); return -2; }
-        if (fetch(t->ext_slot + (nm == "ext_img_sa" ? L.off_img_sa : L.off_img_n), n, h)) return -1;
-        memcpy(out, h.data(), sizeof(float) * n);
-        return n;
+        return fetch_copy(t, FetchEntry{name, t->ext_slot + (nm == "ext_img_sa" ? L.off_img_sa : L.off_img_n), L.B, L.KLQ, L.KLQ},
+                          out, cap);
     }
-    if (nm == "diag_trace") {
-        const int64_t n = (int64_t)DIAG_TRACE_CAP * SAC_DIAG_N < cap ? (int64_t)DIAG_TRACE_CAP * SAC_DIAG_N : cap;
-        if (fetch(d.diag_trace, n, h)) return -1;
-        memcpy(out, h.data(), sizeof(float) * n);
-        return n;
-    }
-    struct Row16 { const char *n; const float *p; };
-    const Row16 r16[] = {{"a_new", d.anew}, {"mu", d.mu}, {"log_std", d.ls}, {"a_next", d.a2}, {"z", d.z}};
-    for (auto &e : r16)
-        if (nm == e.n) {
-            const int Bt = t->Bt;           // (the rows of the true batch)
-            if (cap < (int64_t)Bt * A) { sac::set_error("buffer too small"); return -2; }
-            if (fetch(e.p, 16LL * Bt, h)) return -1;
-            for (int b = 0; b < Bt; ++b) for (int a = 0; a < A; ++a) out[(size_t)b * A + a] = h[(size_t)b * 16 + a];
-            return (int64_t)Bt * A;
-        }
-    struct Vec { const char *n; const float *p; };
-    const Vec vecs[] = {{"log_pi", d.logpi}, {"log_pi_next", d.logpi2}, {"q1", d.q}, {"q2", d.q + B},
-                        {"q1_new", d.q + 2 * (size_t)B}, {"q2_new", d.q + 3 * (size_t)B},
-                        {"tq1", d.q + 4 * (size_t)B}, {"tq2", d.q + 5 * (size_t)B}, {"q_target", d.y}};
-    for (auto &e : vecs)
-        if (nm == e.n) {
-            const int Bt = t->Bt;
-            if (cap < Bt) { sac::set_error("buffer too small"); return -2; }
-            if (fetch(e.p, Bt, h)) return -1;
-            memcpy(out, h.data(), sizeof(float) * Bt);
-            return Bt;
-        }
-    const char *gn[3] = {"g_policy", "g_qf1", "g_qf2"};
-    for (int i = 0; i < 3; ++i)
-        if (nm == gn[i]) {
-            const int64_t n = sac_param_count(t, i);
-            if (cap < n) { sac::set_error("buffer too small"); return -2; }
-            if (download_padded(t, i, t->net[i].G, out)) return -1;
-            return n;
-        }
+    FetchEntry E[FETCH_MAX];
+    const int ne = fetch_table(t, E);
+    for (int i = 0; i < ne; ++i)
+        if (nm == E[i].name) return fetch_copy(t, E[i], out, cap);
     sac::set_error("unknown debug tensor '%s'", name);
     return -2;
 }
