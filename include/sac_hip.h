@@ -555,6 +555,22 @@ int td3_evaluate(sac_trainer_t *t, int64_t n, td3_eval_io_t *io);               
  * sac_trainer_set_xcd[_mask], n_rows outside 0..1024 or all zero, and for a member with rows a null input array or null
  * rows. */
 int td3_evaluate_many(sac_trainer_t *const *trainers, int n_trainers, const int32_t *n_rows, td3_eval_io_t *io);
+/* The same two entries for GENERAL-STEP TD3 trainers (a policy or critics beyond two hidden layers of at most 256 units:
+ * depth 1..7, widths 1..4096): k_eval_layer_td3 (csrc/td3_eval_general.h) and k_eval_layer, one launch per layer depth on
+ * the live weights of the general step -- the policy's layers on s and the TARGET policy's on s', then the critics'
+ * layers on [s | a], [s | a_pi] and [s' | a_smooth], then y -- on the first trainer's stream with one wait at the end; no
+ * mirror, no repacking, no parameter copy.  The contract is that of td3_evaluate / td3_evaluate_many: the same
+ * td3_eval_io_t, the same six rows, the same optional arrays, n 1..1024 for the solo call, 1..16 trainers of one device
+ * with dims, depths, widths and row counts mixed, n_rows[i] == 0 = sits out (at least one with rows), every member with
+ * rows drained as by sac_sync first.  The five Q columns are bit for bit sac_q_values_general's on the same rows, a_pi bit
+ * for bit sac_policy_act_general's, a_smooth and y their float32 restatements; each member's columns are bit for bit its
+ * own td3_evaluate_general's and row r of any call bit for bit the one-row call.  The kernels write the trainers' own
+ * activation scratch (shared with sac_policy_act_general and sac_q_values_general: the calls never overlap) and the
+ * outputs, nothing the step reads.  Refused (<0, sac_last_error, nothing changed, no output written): what
+ * td3_evaluate_many refuses (general-step trainers apart), and trainers with the fused kernels' shapes (td3_evaluate is
+ * their entry).  td3_evaluate / td3_evaluate_many keep refusing general-step trainers. */
+int td3_evaluate_general(sac_trainer_t *t, int64_t n, td3_eval_io_t *io);         /* n in 1..1024 */
+int td3_evaluate_general_many(sac_trainer_t *const *trainers, int n_trainers, const int32_t *n_rows, td3_eval_io_t *io);
 
 /* PER-UNIT statistics of the hidden layers, on the device from the live weights: how much of each network is alive
  * (dormant units, Sokar et al. 2023; dead units; the feature norm).  For n (obs, act) rows, each selected net and each of

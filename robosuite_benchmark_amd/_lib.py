@@ -214,6 +214,8 @@ SYMBOLS = {
     "sac_evaluate_replay_general_many": (C.c_int, [_P, C.c_int, _P, _P, _P, _P]),
     "td3_evaluate": (C.c_int, [_P, C.c_int64, _P]),
     "td3_evaluate_many": (C.c_int, [_P, C.c_int, _P, _P]),
+    "td3_evaluate_general": (C.c_int, [_P, C.c_int64, _P]),
+    "td3_evaluate_general_many": (C.c_int, [_P, C.c_int, _P, _P]),
     "sac_unit_moments": (C.c_int, [_P, C.c_int64, _P]),
     "sac_unit_moments_many": (C.c_int, [_P, C.c_int, _P, _P]),
     "sac_unit_moments_general": (C.c_int, [_P, C.c_int64, _P]),

@@ -462,8 +462,8 @@ class EvalOptions(NamedTuple):
     validation/<key> for every key of evaluate and validation/Num Transitions.  A TD3 variant is refused.
     eval_general ("host" or "device") is evaluate's `general`: where a run of the general step evaluates its objectives
     -- sac_get_params and a NumPy forward, or sac_evaluate_general (one k_eval_layer launch per layer on the live
-    weights; in a group one sac_evaluate_general_many call per 16 such runs).  Without validation and replay_eval, and
-    for a run with the fused kernels' shapes, it has no effect.
+    weights; in a group one sac_evaluate_general_many call per 16 such runs).  Without validation, td3_validation and
+    replay_eval, and for a run with the fused kernels' shapes, it has no effect.
     eval_stats ("host" or "device") is evaluate's `stats`: where the statistics of a run that is evaluated on the device
     are reduced -- eval_statistics on the columns copied out, or k_eval_moments on the device (the same columns of
     progress.csv, equal up to the rounding of a float64 sum in another order).  Without validation and replay_eval it
@@ -496,7 +496,10 @@ class EvalOptions(NamedTuple):
     RandomState([seed, epoch, 0x56414C]).standard_normal((n, A)): nothing to checkpoint, and a resumed run logs the same
     rows.  The row gains validation/<key> for every key of td3_eval_statistics and validation/Num Transitions where the
     SAC validation block sits; the group entries make ONE td3_evaluate_many call per epoch.  Every run must be a TD3
-    variant: a SAC variant is refused (validation=True is its option)."""
+    variant: a SAC variant is refused (validation=True is its option).  eval_general applies to it as to validation:
+    under "device" a TD3 run of the general step evaluates on the device as well (td3_evaluate_general: k_eval_layer_td3
+    and k_eval_layer, one launch per layer on the live weights; in a group one td3_evaluate_general_many call per 16
+    such runs)."""
     q_diagnostics: bool = False
     q_general: str = "host"
     validation: bool = False
@@ -584,8 +587,8 @@ def _epoch_evaluations(runs, epoch, opts, take=ALL_BLOCKS, many=True):
     if opts.td3_validation and "validation" in take:
         batches = [_validation_batch(p, t.obs_dim, t.act_dim) for p, t in zip(paths, trainers)]
         eps = [_td3_validation_eps(r["seed"], epoch, b, t.act_dim) for r, b, t in zip(runs, batches, trainers)]
-        got = (td3_evaluate_many(trainers, batches, eps=eps) if many else
-               [None if b is None else t.evaluate_td3(b, eps=e) for t, b, e in zip(trainers, batches, eps)])
+        got = (td3_evaluate_many(trainers, batches, eps=eps, **gen) if many else
+               [None if b is None else t.evaluate_td3(b, eps=e, **gen) for t, b, e in zip(trainers, batches, eps)])
         for c, s, b in zip(cols, got, batches):
             c["validation"] = _td3_validation_columns(s, b)
     if opts.replay_eval and "replay" in take:

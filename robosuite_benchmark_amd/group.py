@@ -91,10 +91,10 @@ class _Members:
         return evaluate_replay_many(self.trainers, replay_buffers, n=n, indices=indices, eps=eps, rngs=rngs, rows=rows,
                                     general=general, stats=stats)
 
-    def td3_evaluate_many(self, batches, eps=None, rngs=None, rows=False):
+    def td3_evaluate_many(self, batches, eps=None, rngs=None, rows=False, general="host"):
         """td3_evaluate_many over the group's members: the TD3 objectives (a SAC group raises through the member check
-        there)."""
-        return td3_evaluate_many(self.trainers, batches, eps=eps, rngs=rngs, rows=rows)
+        there; general as there)."""
+        return td3_evaluate_many(self.trainers, batches, eps=eps, rngs=rngs, rows=rows, general=general)
 
 
 class _SACMembers:

@@ -79,6 +79,7 @@ EVAL_ENTRIES = {FUSED: ("sac_evaluate_many", "sac_evaluate_stats_many"),        
                 GENERAL_STEP: ("sac_evaluate_general_many", "sac_evaluate_general_stats_many")}
 EVAL_REPLAY_ENTRIES = {FUSED: "sac_evaluate_replay_many",                            # (stats: an argument, NULL for "host")
                        GENERAL_STEP: "sac_evaluate_replay_general_many"}
+TD3_EVAL_ENTRIES = {FUSED: "td3_evaluate_many", GENERAL_STEP: "td3_evaluate_general_many"}
 
 
 def route(t, general, on_host=False):
@@ -86,7 +87,7 @@ def route(t, general, on_host=False):
     *_ENTRIES).  No handle: the host.  The fused kernels' shapes: the fused entry under either `general`.  The general
     step: the host, or the general entry under general="device".  on_host (evaluation: _evaluate_on_host) sends a member
     with a handle to the host too; a TD3 member's evaluate never gets here (its own evaluate refuses), its evaluate_td3
-    does, under general="host": td3_evaluate_many is the fused entry and there is no general one."""
+    does, with TD3_EVAL_ENTRIES: td3_evaluate_many is the fused entry and td3_evaluate_general_many the general one."""
     if t._h is None or on_host:
         return HOST
     if not runs_general_step(t):
@@ -910,46 +911,54 @@ def _td3_eval_result(cols, rows):
     return (result, cols) if rows else result
 
 
-def td3_evaluate_of(trainers, inputs, rows):
+def td3_evaluate_of(trainers, inputs, rows, general="host"):
     """evaluate_td3 / td3_evaluate_many behind their argument checks: inputs[i] = the member's arrays as
     TD3Trainer._td3_eval_inputs checked them, or None for a member that sits out (its result: None).  The host members
-    first, in member order; then the members with the fused kernels' shapes in windows (td3_evaluate_many: 16 members
-    and 1024 rows per call)."""
+    first, in member order; then the fused family, then the general one (general="device"), each in windows of its
+    entry of TD3_EVAL_ENTRIES: 16 members and 1024 rows per call."""
     R = len(trainers)
-    out, n_rows, served = [None] * R, [0] * R, []
+    out, n_rows, served = [None] * R, [0] * R, {FUSED: [], GENERAL_STEP: []}
     for i, (t, arrs) in enumerate(zip(trainers, inputs)):
         if arrs is None:
             continue
-        if route(t, "host", t._evaluate_on_host) == HOST:
+        where = route(t, general, t._evaluate_on_host)
+        if where == HOST:
             out[i] = _td3_eval_result(t._evaluate_td3_host(arrs), rows)
         else:
             n_rows[i] = arrs[0].shape[0]
-            served.append(i)
-    if not served:
+            served[where].append(i)
+    members = served[FUSED] + served[GENERAL_STEP]
+    if not members:
         return out
     lib = _lib.load()
-    chunks = {i: [] for i in served}
-    for r0, ids, counts in windows(served, n_rows):
-        made = [_eval_io(_lib.Td3EvalIO, _lib.TD3_EVAL_ROWS, _lib.TD3_EVAL_ARRAYS, inputs[i], r0, r0 + k, trainers[i].act_dim)
-                for i, k in zip(ids, counts)]
-        ios = (_lib.Td3EvalIO * len(ids))(*[m[0] for m in made])
-        _lib.check(lib.td3_evaluate_many(_handles(trainers, ids), len(ids), _ints(counts), ios), "td3_evaluate_many")
-        for i, m in zip(ids, made):
-            chunks[i].append(m[1])
-    for i in served:
+    chunks = {i: [] for i in members}
+    for family in (FUSED, GENERAL_STEP):
+        entry = TD3_EVAL_ENTRIES[family]
+        for r0, ids, counts in windows(served[family], n_rows):
+            made = [_eval_io(_lib.Td3EvalIO, _lib.TD3_EVAL_ROWS, _lib.TD3_EVAL_ARRAYS, inputs[i], r0, r0 + k,
+                             trainers[i].act_dim) for i, k in zip(ids, counts)]
+            ios = (_lib.Td3EvalIO * len(ids))(*[m[0] for m in made])
+            _lib.check(getattr(lib, entry)(_handles(trainers, ids), len(ids), _ints(counts), ios), entry)
+            for i, m in zip(ids, made):
+                chunks[i].append(m[1])
+    for i in members:
         trainers[i]._settled()
         out[i] = _td3_eval_result(_eval_columns(chunks[i], _lib.TD3_EVAL_ROWS, _lib.TD3_EVAL_ARRAYS), rows)
     return out
 
 
-def td3_evaluate_many(trainers, batches, eps=None, rngs=None, rows=False):
+def td3_evaluate_many(trainers, batches, eps=None, rngs=None, rows=False, general="host"):
     """TD3Trainer.evaluate_td3 for many runs at once: result[i] = trainers[i].evaluate_td3(batches[i], eps[i], rngs[i])
     (eps / rngs: one entry per trainer or None; batches[i] None or without rows: the member sits out and gets None).  The
     TD3 members with the fused kernels' shapes are served by ONE launch per 16 of them and 1024 rows (td3_evaluate_many:
     dims, hidden sizes and row counts mixed); the others -- the general step, trainers without a handle -- take their
     host path inside the same call.  A member's columns never depend on its neighbours: they are bit for bit those of
     its own evaluate_td3.  Results come back in member order; rows=True as for evaluate_td3.  A SAC member raises
-    (evaluate_many is the call for the SAC objective)."""
+    (evaluate_many is the call for the SAC objective).
+    general="device": the TD3 members of the general step are evaluated on the device as well, by ONE
+    td3_evaluate_general_many call per 16 of them and 1024 rows; their results are bit for bit those of their own
+    evaluate_td3(general="device")."""
+    check_general(general)
     trainers, batches, eps, rngs = _member_args("td3_evaluate_many", "batch (and eps, and rng)", trainers, batches, eps, rngs)
     for i, t in enumerate(trainers):
         if not _is_td3(t):
@@ -960,7 +969,7 @@ def td3_evaluate_many(trainers, batches, eps=None, rngs=None, rows=False):
         if b is None or np.atleast_2d(b["observations"]).shape[0] == 0:
             continue
         inputs[i] = t._td3_eval_inputs(b, eps[i], rngs[i])
-    return td3_evaluate_of(trainers, inputs, rows)
+    return td3_evaluate_of(trainers, inputs, rows, general)
 
 
 # ---- acting sessions ----------------------------------------------------------------------------------------------------

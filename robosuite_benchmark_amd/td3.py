@@ -114,14 +114,18 @@ class TD3Trainer(SACTrainer):
                    a_target=_lib.f32(a_target), a_smooth=_lib.f32(a_smooth))
         return infer._eval_columns([out], _lib.TD3_EVAL_ROWS, _lib.TD3_EVAL_ARRAYS)
 
-    def evaluate_td3(self, batch, eps=None, rng=None, rows=False):
+    def evaluate_td3(self, batch, eps=None, rng=None, rows=False, general="host"):
         """The TD3 objectives of this run on `batch` WITHOUT a gradient step: `batch` is the dict train() takes
         (observations, actions, rewards, terminals, next_observations; any n >= 1), typically transitions the run has not
         trained on -- an epoch's evaluation paths.  From the LIVE weights: on the device (td3_evaluate: k_eval_td3, one
-        launch per 1024 rows, no parameter copy); a trainer of the general step, which the library's entry refuses, and a
+        launch per 1024 rows, no parameter copy); a trainer of the general step, which that entry refuses, and a
         trainer without a handle take the host path -- sac_sync, sac_get_params, a float32 NumPy forward.  Nothing the
         step reads is written either way, and the trainer's own statistics (get_diagnostics, the step counters) are left
         alone.
+        general="device": a trainer of the general step is evaluated on the device as well (td3_evaluate_general:
+        k_eval_layer_td3 and k_eval_layer, one launch per layer depth and 1024 rows, on the general step's own weights);
+        its Q columns are bit for bit q_values(general="device")'s and a_pi policy_act_general's.  For the fused kernels'
+        shapes and for a trainer without a handle the keyword changes nothing.
         eps: the (n, A) N(0,1) draw of the target smoothing; None: drawn as standard_normal((n, A)) from `rng`, or from a
         RandomState private to the trainer (seeded from noise_seed) when that is None too -- np.random is never touched.
         Returns an OrderedDict with get_diagnostics()' keys plus TD Error 1 / TD Error 2 Mean / Std / Max / Min (q - y,
@@ -130,7 +134,8 @@ class TD3Trainer(SACTrainer):
         q_pi = Q1(s, a_pi), a_pi the policy's action on s; a_target the TARGET policy's action on s',
         a_smooth = a_target + clip(eps * target_policy_noise, +-target_policy_noise_clip), the targets tq1 / tq2 on
         (s', a_smooth), y = reward_scale r + (1 - d) discount min(tq1, tq2)."""
-        return infer.td3_evaluate_of([self], [self._td3_eval_inputs(batch, eps, rng)], rows)[0]
+        infer.check_general(general)
+        return infer.td3_evaluate_of([self], [self._td3_eval_inputs(batch, eps, rng)], rows, general)[0]
 
     def get_snapshot(self):
         snap = super().get_snapshot()

@@ -17,7 +17,8 @@
  --q_general device: with --q_diagnostics, runs of any hidden sizes evaluate their critics on the device too.
  --validation: every epoch, the SAC losses, TD errors and targets on the evaluation paths' transitions -- held-out data
  -- from the live weights: validation/ columns in progress.csv; SAC only.
- --eval_general device: with --validation, runs of any hidden sizes evaluate these objectives on the device too.
+ --eval_general device: with --validation (or --td3_validation), runs of any hidden sizes evaluate these objectives on
+ the device too.
  --eval_stats device: with --validation, the statistics of the runs evaluated on the device are reduced there as well.
  --replay_eval [N]: every epoch, the same objectives on N (bare: 1024) rows of the replay buffer, read in place on the
  device: replay/ columns in progress.csv, the training-data figures next to the validation/ ones; SAC only.
@@ -85,9 +86,10 @@ def build_parser():
                          "the transitions of the evaluation paths, which never enter the replay buffer (a HIP kernel on "
                          "the live weights), and log them as validation/<key>; SAC only; off: progress.csv is unchanged")
     ap.add_argument("--eval_general", type=str, default="host", choices=["host", "device"],
-                    help="with --validation: where runs whose hidden sizes are beyond two layers of at most 256 units "
-                         "evaluate the SAC objectives -- host (a parameter copy and a NumPy forward) or device (one HIP "
-                         "launch per layer on the live weights); without --validation it has no effect")
+                    help="with --validation or --td3_validation: where runs whose hidden sizes are beyond two layers of at "
+                         "most 256 units evaluate their objectives (SAC's, or TD3's under --td3_validation) -- host (a "
+                         "parameter copy and a NumPy forward) or device (one HIP launch per layer on the live weights); "
+                         "without either option it has no effect")
     ap.add_argument("--eval_stats", type=str, default="host", choices=["host", "device"],
                     help="with --validation: where the statistics (means, deviations, extremes, losses) of the runs that are "
                          "evaluated on the device are reduced -- host (the columns are copied out and reduced in NumPy) or "
