@@ -571,6 +571,41 @@ int td3_evaluate_many(sac_trainer_t *const *trainers, int n_trainers, const int3
  * their entry).  td3_evaluate / td3_evaluate_many keep refusing general-step trainers. */
 int td3_evaluate_general(sac_trainer_t *t, int64_t n, td3_eval_io_t *io);         /* n in 1..1024 */
 int td3_evaluate_general_many(sac_trainer_t *const *trainers, int n_trainers, const int32_t *n_rows, td3_eval_io_t *io);
+/* The STATISTICS of a TD3 evaluation reduced on the device as well (k_eval_moments_td3, csrc/td3_eval_moments.h): one more
+ * launch behind k_eval_td3 (fused shapes) or k_eval_y_td3 (general step) and in front of the call's single wait reads the
+ * float32 columns where they lie and leaves nine moment records (sac_eval_moment_t, above) per member, every element
+ * formed in float64:
+ *   TD3_EVAL_M_Q1 / Q2 / Y / Q_PI       the rows q1, q2, y, q_pi                                    (n elements)
+ *   TD3_EVAL_M_A_PI                     the policy's action                                         (n A elements)
+ *   TD3_EVAL_M_TD1 / TD2                (double)q1 - (double)y, (double)q2 - (double)y              (n)
+ *   TD3_EVAL_M_BELLMAN1 / BELLMAN2      d * d with d as above, the product rounded on its own       (n)
+ * The reduction is k_eval_moments': the order of every sum is a function of the record's own element count only, so a
+ * member's records are byte for byte those of its solo call, whatever its neighbours, its place among them or the
+ * optional arrays asked for.  The contract is that of td3_evaluate_many / td3_evaluate_general_many (admission,
+ * refusals, the drain, 0..1024 rows, 1..16 trainers, SAC trainers refused, each family refusing the other's trainers)
+ * with two differences: io[i].rows may be NULL -- then no column is copied back -- and stats[i] is filled for every
+ * member with rows.  Null stats: refused.  The columns are bit for bit those of the entries above. */
+enum { TD3_EVAL_M_Q1, TD3_EVAL_M_Q2, TD3_EVAL_M_Y, TD3_EVAL_M_Q_PI, TD3_EVAL_M_A_PI,
+       TD3_EVAL_M_TD1, TD3_EVAL_M_TD2, TD3_EVAL_M_BELLMAN1, TD3_EVAL_M_BELLMAN2, TD3_EVAL_MOMENTS_N };
+typedef struct { sac_eval_moment_t m[TD3_EVAL_MOMENTS_N]; } td3_eval_stats_t;
+int td3_evaluate_stats_many(sac_trainer_t *const *trainers, int n_trainers, const int32_t *n_rows, td3_eval_io_t *io,
+                            td3_eval_stats_t *stats);
+int td3_evaluate_general_stats_many(sac_trainer_t *const *trainers, int n_trainers, const int32_t *n_rows, td3_eval_io_t *io,
+                                    td3_eval_stats_t *stats);
+/* The same TD3 evaluations on REPLAY rows IN PLACE, as sac_evaluate_replay_many / sac_evaluate_replay_general_many above:
+ * the five input arrays of member i are storage rows src[i].idx[0 .. n_rows[i]) of the replay buffer src[i].buf, copied
+ * on the device (k_eval_rows, unchanged, one launch in front of k_eval_td3 or the first k_eval_layer_td3) into the staging
+ * the evaluation reads.  io[i].obs / act / rew / term / next_obs are ignored and may be NULL; eps still comes from the
+ * host.  stats NULL: the contract of td3_evaluate_many / td3_evaluate_general_many (io[i].rows needed); with stats that of
+ * the *_stats_many entries (rows may be NULL).  The columns and the moment records are bit for bit those of the same entry
+ * on the rows sac_gather returns for the same indices.  Two members may name one buffer.  The rows are read behind every
+ * insert pending on the buffer's stream (an event, no host wait), and the buffer is only read.  Refused in addition (<0,
+ * sac_last_error, nothing launched, no output written), each naming the member: a null buf or idx, a buffer on another
+ * device, buffer dims other than the trainer's, an empty buffer, an index outside [0, sac_buffer_size). */
+int td3_evaluate_replay_many(sac_trainer_t *const *trainers, int n_trainers, const int32_t *n_rows,
+                             const sac_eval_src_t *src, td3_eval_io_t *io, td3_eval_stats_t *stats /* may be NULL */);
+int td3_evaluate_replay_general_many(sac_trainer_t *const *trainers, int n_trainers, const int32_t *n_rows,
+                                     const sac_eval_src_t *src, td3_eval_io_t *io, td3_eval_stats_t *stats /* may be NULL */);
 
 /* PER-UNIT statistics of the hidden layers, on the device from the live weights: how much of each network is alive
  * (dormant units, Sokar et al. 2023; dead units; the feature norm).  For n (obs, act) rows, each selected net and each of

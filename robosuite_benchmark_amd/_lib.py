@@ -110,6 +110,15 @@ class SacEvalStats(C.Structure):
     _fields_ = [("m", SacEvalMoment * len(EVAL_MOMENTS)), ("alpha", C.c_double), ("log_alpha", C.c_double)]
 
 
+# the moment records of td3_evaluate_stats_many (TD3_EVAL_M_*: td3_eval_stats_t.m, in this order)
+TD3_EVAL_MOMENTS = ["q1", "q2", "y", "q_pi", "a_pi", "td1", "td2", "bellman1", "bellman2"]
+
+
+class Td3EvalStats(C.Structure):
+    """td3_eval_stats_t"""
+    _fields_ = [("m", SacEvalMoment * len(TD3_EVAL_MOMENTS))]
+
+
 # the per-unit records of sac_unit_moments_* (SAC_UNIT_*: the arrays of one hidden layer's record, in this order)
 UNIT_FIELDS = ("sum", "sumsq", "active", "max")
 UNIT_NET_BITS = {name: 1 << k for name, k in TD3_NET_IDS.items()}      # name -> bit SAC_NET_* of sac_units_io_t.nets
@@ -216,6 +225,10 @@ SYMBOLS = {
     "td3_evaluate_many": (C.c_int, [_P, C.c_int, _P, _P]),
     "td3_evaluate_general": (C.c_int, [_P, C.c_int64, _P]),
     "td3_evaluate_general_many": (C.c_int, [_P, C.c_int, _P, _P]),
+    "td3_evaluate_stats_many": (C.c_int, [_P, C.c_int, _P, _P, _P]),
+    "td3_evaluate_general_stats_many": (C.c_int, [_P, C.c_int, _P, _P, _P]),
+    "td3_evaluate_replay_many": (C.c_int, [_P, C.c_int, _P, _P, _P, _P]),
+    "td3_evaluate_replay_general_many": (C.c_int, [_P, C.c_int, _P, _P, _P, _P]),
     "sac_unit_moments": (C.c_int, [_P, C.c_int64, _P]),
     "sac_unit_moments_many": (C.c_int, [_P, C.c_int, _P, _P]),
     "sac_unit_moments_general": (C.c_int, [_P, C.c_int64, _P]),

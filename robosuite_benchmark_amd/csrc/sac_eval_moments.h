@@ -40,15 +40,21 @@ struct MomentsMember {
 __device__ __forceinline__ double em_max(double m, double x) { return (x > m || x != x) ? x : m; }
 __device__ __forceinline__ double em_min(double m, double x) { return (x < m || x != x) ? x : m; }
 
-enum { EM_COLUMN, EM_DIFF, EM_POLICY };
+enum { EM_COLUMN, EM_DIFF, EM_POLICY, EM_SQDIFF };
 
-// element i of a quantity: a[i], a[i] - b[i], or a[i] - min(b[i], c[i])
+// element i of a quantity: a[i], a[i] - b[i], a[i] - min(b[i], c[i]), or (a[i] - b[i])^2 (td3_eval_moments.h: the
+// product rounded on its own, never fused into the sum behind it, as (q - y) ** 2 is in float64 NumPy)
 template <int KIND>
 __device__ __forceinline__ double em_elem(const float *a, const float *b, const float *c, int i) {
     const double x = (double)a[i];
     if constexpr (KIND == EM_COLUMN) return x;
     else if constexpr (KIND == EM_DIFF) return x - (double)b[i];
-    else return x - em_min((double)b[i], (double)c[i]);
+    else if constexpr (KIND == EM_POLICY) return x - em_min((double)b[i], (double)c[i]);
+    else {
+#pragma clang fp contract(off)
+        const double d = x - (double)b[i];
+        return d * d;
+    }
 }
 
 // L[k][t] <- the tree over lanes of L[k], for k < NK: sums for k < NSUM, then one max, then one min.  The result is in L[k][0].

@@ -78,12 +78,9 @@ namespace {
 struct EvalRowsStage { size_t tab = 0, idx[SAC_GROUP_MAX] = {}; };
 
 // the replay entries' own refusals for member i with n rows: eps and eps_next (and `rows` unless the entry returns
-// statistics) -- the five input arrays of io are not looked at -- then the source: a buffer and indices, the buffer on
-// the trainer's device, of its dims and not empty, every index inside [0, size)
-int eval_rows_admit(const sac_eval_io_t &E, const sac_eval_src_t &R, const sac_trainer *t, int i, int n, bool need_rows) {
-    const bool inputs = E.eps && E.eps_next;
-    if (need_rows) SAC_REQUIRE(inputs && E.rows, "trainer %d: null eps, eps_next or rows", i);
-    SAC_REQUIRE(inputs, "trainer %d: null eps or eps_next", i);
+// statistics) -- the five input arrays of io are not looked at -- then the source (eval_rows_admit_src): a buffer and
+// indices, the buffer on the trainer's device, of its dims and not empty, every index inside [0, size)
+int eval_rows_admit_src(const sac_eval_src_t &R, const sac_trainer *t, int i, int n) {
     SAC_REQUIRE(R.buf && R.idx, "trainer %d: a null replay buffer or null indices", i);
     const sac_buffer *b = R.buf;
     SAC_REQUIRE(b->device == t->device, "trainer %d lives on device %d, its replay buffer on device %d", i, t->device, b->device);
@@ -94,6 +91,20 @@ int eval_rows_admit(const sac_eval_io_t &E, const sac_eval_src_t &R, const sac_t
         SAC_REQUIRE(R.idx[j] >= 0 && R.idx[j] < b->size, "trainer %d: index %lld (row %d) out of range [0, %lld)", i,
                     (long long)R.idx[j], j, (long long)b->size);
     return 0;
+}
+
+int eval_rows_admit(const sac_eval_io_t &E, const sac_eval_src_t &R, const sac_trainer *t, int i, int n, bool need_rows) {
+    const bool inputs = E.eps && E.eps_next;
+    if (need_rows) SAC_REQUIRE(inputs && E.rows, "trainer %d: null eps, eps_next or rows", i);
+    SAC_REQUIRE(inputs, "trainer %d: null eps or eps_next", i);
+    return eval_rows_admit_src(R, t, i, n);
+}
+
+// the same for the TD3 objective's single draw (td3_eval.h, td3_eval_general.h)
+int eval_rows_admit(const td3_eval_io_t &E, const sac_eval_src_t &R, const sac_trainer *t, int i, int n, bool need_rows) {
+    if (need_rows) SAC_REQUIRE(E.eps && E.rows, "trainer %d: null eps or rows", i);
+    SAC_REQUIRE(E.eps, "trainer %d: null eps", i);
+    return eval_rows_admit_src(R, t, i, n);
 }
 
 void eval_rows_carve(size_t &bytes, EvalRowsStage &RS, int n_trainers, const int32_t *n_rows) {

@@ -2347,6 +2347,7 @@ int stage_batches(sac_trainer *t, sac_buffer *b, int64_t n_steps) {
 #include "sac_eval_moments.h"
 #include "sac_eval_rows.h"
 #include "sac_eval.h"
+#include "td3_eval_moments.h"
 #include "td3_eval.h"
 #include "sac_act_general.h"
 #include "sac_qval_general.h"

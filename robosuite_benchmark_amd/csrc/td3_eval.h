@@ -19,8 +19,12 @@
 // So q1, q2, q_pi, tq1, tq2 are bit for bit k_qval's values on the same rows and a_pi bit for bit k_act's; a NaN row stays
 // in its row.
 //
-// SAC trainers are refused (sac_evaluate is their entry) and so are general-step TD3 trainers (TD3Trainer.evaluate_td3's
-// host path serves them).
+// SAC trainers are refused (sac_evaluate is their entry) and so are general-step TD3 trainers (td3_eval_general.h serves
+// them, or TD3Trainer.evaluate_td3's host path).
+//
+// td3_evaluate_stats_many reduces the statistics on the device as well (k_eval_moments_td3, td3_eval_moments.h, behind
+// k_eval_td3) and td3_evaluate_replay_many takes the input rows from the replay storage (k_eval_rows, sac_eval_rows.h, in
+// front of it): one body serves all three entries.
 #pragma once
 
 namespace sac {
@@ -96,17 +100,16 @@ __global__ __launch_bounds__(256) void k_eval_td3(const Td3EvalMember *__restric
 static_assert((int)T3E_ROWS_N == (int)TD3_EVAL_ROWS_N && (int)T3E_Y == (int)TD3_EVAL_Y && (int)T3E_Q_PI == (int)TD3_EVAL_Q_PI &&
               T3E_Q1 == 0 && T3E_Q2 == 1, "k_eval_td3's rows are sac_hip.h's, chain Q's the first two");
 
-// (declared extern "C" in include/sac_hip.h)
-int td3_evaluate_many(sac_trainer_t *const *trainers, int n_trainers, const int32_t *n_rows, td3_eval_io_t *io) {
-    SAC_REQUIRE(trainers && n_rows && io, "bad arguments to td3_evaluate_many");
-    InferEntry IE = {"td3_evaluate_many", false, false, "device evaluation",
-                     "sac_get_params and a forward on the host is the path", "evaluate"};
-    IE.td3_only = true;
+// td3_evaluate_many (stats and src null), td3_evaluate_stats_many and td3_evaluate_replay_many, as evaluate_many
+// (sac_eval.h) serves the SAC entries of the same names: with stats, a_pi always has its place in the staging
+// (k_eval_moments_td3 reads it there; only the copy to the caller depends on what was asked for), k_eval_moments_td3
+// (td3_eval_moments.h) runs behind k_eval_td3 in front of the wait, and a null io[i].rows is taken.  With src the five
+// input parts of the staging are filled on the device, by k_eval_rows (sac_eval_rows.h) in front of k_eval_td3, from
+// src[i]'s replay storage instead of io[i]'s arrays; everything else is the same body
+static int td3_evaluate_body(const InferEntry &IE, sac_trainer_t *const *trainers, int n_trainers, const int32_t *n_rows,
+                             td3_eval_io_t *io, td3_eval_stats_t *stats, const sac_eval_src_t *src = nullptr) {
     if (int rc = infer_admit(IE, trainers, n_trainers, n_rows, [&](int i) {
-            const td3_eval_io_t &E = io[i];
-            SAC_REQUIRE(E.obs && E.act && E.rew && E.term && E.next_obs && E.eps && E.rows,
-                        "trainer %d: a null input array or null rows", i);
-            return 0;
+            return src ? eval_rows_admit(io[i], src[i], trainers[i], i, n_rows[i], !stats) : td3_eval_admit_io(io[i], i, !stats);
         })) return rc;
     sac_trainer *t0 = trainers[0];
 
@@ -117,12 +120,17 @@ int td3_evaluate_many(sac_trainer_t *const *trainers, int n_trainers, const int3
         const size_t n = (size_t)n_rows[i], nO = n * t->O, nA = n * t->A;
         const td3_eval_io_t &E = io[i];
         const size_t part[NPART] = {nO, nA, n, n, nO, nA, n * TD3_EVAL_ROWS_N,
-                                    n && E.a_pi ? nA : 0, n && E.a_target ? nA : 0, n && E.a_smooth ? nA : 0};
+                                    n && (E.a_pi || stats) ? nA : 0, n && E.a_target ? nA : 0, n && E.a_smooth ? nA : 0};
         ST.carve(i, part, NPART);
     }
+    MomentsStage MS;
+    if (stats) moments_carve(ST.bytes, MS, n_trainers);
+    EvalRowsStage RS;
+    if (src) eval_rows_carve(ST.bytes, RS, n_trainers, n_rows);
     if (ST.reserve(t0)) return -1;
-    Td3EvalMember *tab = reinterpret_cast<Td3EvalMember *>(ST.S->h);
-    int wgs = 0, m = 0, kq_max = 0;
+    const sac_trainer::ActStage &S = t0->act_stage;
+    Td3EvalMember *tab = reinterpret_cast<Td3EvalMember *>(S.h);
+    int wgs = 0, m = 0, kq_max = 0, row_wgs = 0;
     for (int i = 0; i < n_trainers; ++i) {
         const sac_trainer *t = trainers[i];
         if (n_rows[i] == 0) continue;
@@ -130,19 +138,53 @@ int td3_evaluate_many(sac_trainer_t *const *trainers, int n_trainers, const int3
         Td3EvalMember &M = tab[m++];
         eval_member(M, t, 6, n_rows[i], wgs, kq_max);
         eval_layers(M.tW, M.tB, t->net[SAC_NET_TARGET_POLICY]);
-        M.obs = ST.in(i, P_OBS, E.obs); M.act = ST.in(i, P_ACT, E.act); M.rew = ST.in(i, P_REW, E.rew);
-        M.term = ST.in(i, P_TERM, E.term); M.nobs = ST.in(i, P_NOBS, E.next_obs); M.eps = ST.in(i, P_EPS, E.eps);
-        M.rows = ST.dev(i, P_ROWS); M.a_pi = ST.dev(i, P_A_PI, E.a_pi); M.a_target = ST.dev(i, P_A_TARGET, E.a_target);
+        // (src: k_eval_rows fills the five parts)
+        M.obs = ST.in(i, P_OBS, src ? nullptr : E.obs); M.act = ST.in(i, P_ACT, src ? nullptr : E.act);
+        M.rew = ST.in(i, P_REW, src ? nullptr : E.rew); M.term = ST.in(i, P_TERM, src ? nullptr : E.term);
+        M.nobs = ST.in(i, P_NOBS, src ? nullptr : E.next_obs); M.eps = ST.in(i, P_EPS, E.eps);
+        if (src) row_wgs += eval_rows_member(S, RS, m - 1, i, row_wgs, src[i], n_rows[i], ST.dev(i, P_OBS), ST.dev(i, P_ACT),
+                                             ST.dev(i, P_REW), ST.dev(i, P_TERM), ST.dev(i, P_NOBS));
+        M.rows = ST.dev(i, P_ROWS); M.a_pi = ST.dev(i, P_A_PI, E.a_pi || stats); M.a_target = ST.dev(i, P_A_TARGET, E.a_target);
         M.a_smooth = ST.dev(i, P_A_SMOOTH, E.a_smooth);
         M.sigma = t->dev.td3_sigma; M.clip = t->dev.td3_clip;
+        if (stats) td3_moments_member(S, MS, m - 1, i, M.rows, M.a_pi, n_rows[i], t->A);
     }
-    if (eval_launch(k_eval_td3, t0, wgs, m, kq_max, [] { return 0; })) return -1;
+    if (src && eval_rows_launch(t0, RS, m, row_wgs, src, n_trainers, n_rows)) return -1;
+    if (eval_launch(k_eval_td3, t0, wgs, m, kq_max, [&] { return stats ? td3_moments_launch(t0, MS, m) : 0; })) return -1;
     for (int i = 0; i < n_trainers; ++i) {
         if (n_rows[i] == 0) continue;
         const td3_eval_io_t &E = io[i];
         ST.back(i, {{E.rows, P_ROWS}, {E.a_pi, P_A_PI}, {E.a_target, P_A_TARGET}, {E.a_smooth, P_A_SMOOTH}});
+        if (stats) td3_moments_read(S, MS, i, &stats[i]);
     }
     return 0;
+}
+
+static InferEntry td3_eval_entry(const char *fn, const char *instead) {
+    InferEntry IE = {fn, false, false, "device evaluation", instead, "evaluate"};
+    IE.td3_only = true;
+    return IE;
+}
+
+// (declared extern "C" in include/sac_hip.h)
+int td3_evaluate_many(sac_trainer_t *const *trainers, int n_trainers, const int32_t *n_rows, td3_eval_io_t *io) {
+    SAC_REQUIRE(trainers && n_rows && io, "bad arguments to td3_evaluate_many");
+    return td3_evaluate_body(td3_eval_entry("td3_evaluate_many", "sac_get_params and a forward on the host is the path"),
+                             trainers, n_trainers, n_rows, io, nullptr);
+}
+
+int td3_evaluate_stats_many(sac_trainer_t *const *trainers, int n_trainers, const int32_t *n_rows, td3_eval_io_t *io,
+                            td3_eval_stats_t *stats) {
+    SAC_REQUIRE(trainers && n_rows && io && stats, "bad arguments to td3_evaluate_stats_many");
+    return td3_evaluate_body(td3_eval_entry("td3_evaluate_stats_many", "td3_evaluate_general_stats_many is the entry"),
+                             trainers, n_trainers, n_rows, io, stats);
+}
+
+int td3_evaluate_replay_many(sac_trainer_t *const *trainers, int n_trainers, const int32_t *n_rows, const sac_eval_src_t *src,
+                             td3_eval_io_t *io, td3_eval_stats_t *stats) {
+    SAC_REQUIRE(trainers && n_rows && src && io, "bad arguments to td3_evaluate_replay_many");
+    return td3_evaluate_body(td3_eval_entry("td3_evaluate_replay_many", "td3_evaluate_replay_general_many is the entry"),
+                             trainers, n_trainers, n_rows, io, stats, src);
 }
 
 int td3_evaluate(sac_trainer_t *t, int64_t n, td3_eval_io_t *io) {

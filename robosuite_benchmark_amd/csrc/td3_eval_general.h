@@ -106,17 +106,15 @@ __global__ __launch_bounds__(EG_YROWS) void k_eval_y_td3(const EvalYTd3Member *_
 static_assert(T3E_Q_PI == 2 && T3E_TQ1 == 3 && T3E_TQ2 == 4, "the five critic chains write rows TD3_EVAL_Q1 .. TQ2 in order");
 static_assert(5 * SAC_GROUP_MAX <= EG_JOBS, "a critic launch of a TD3 evaluation fits the evaluation's job table");
 
-// (declared extern "C" in include/sac_hip.h)
-int td3_evaluate_general_many(sac_trainer_t *const *trainers, int n_trainers, const int32_t *n_rows, td3_eval_io_t *io) {
-    SAC_REQUIRE(trainers && n_rows && io, "bad arguments to td3_evaluate_general_many");
-    InferEntry IE = {"td3_evaluate_general_many", true, false, "device evaluation",
-                     "td3_evaluate is its device evaluation entry, td3_evaluate_general serves the general step", "evaluate"};
-    IE.td3_only = true;
+// td3_evaluate_general_many (stats and src null), td3_evaluate_general_stats_many and td3_evaluate_replay_general_many,
+// as evaluate_general_many (sac_eval_general.h) serves the SAC entries of the same names: with stats,
+// k_eval_moments_td3 (td3_eval_moments.h) runs behind k_eval_y_td3 in front of the wait and a null io[i].rows is taken
+// (a_pi has its place in the staging either way); with src, k_eval_rows (sac_eval_rows.h) fills the five input parts
+// from src[i]'s replay storage in front of the first layer launch
+static int td3_evaluate_general_body(const InferEntry &IE, sac_trainer_t *const *trainers, int n_trainers, const int32_t *n_rows,
+                                     td3_eval_io_t *io, td3_eval_stats_t *stats, const sac_eval_src_t *src = nullptr) {
     if (int rc = infer_admit(IE, trainers, n_trainers, n_rows, [&](int i) {
-            const td3_eval_io_t &E = io[i];
-            SAC_REQUIRE(E.obs && E.act && E.rew && E.term && E.next_obs && E.eps && E.rows,
-                        "trainer %d: a null input array or null rows", i);
-            return 0;
+            return src ? eval_rows_admit(io[i], src[i], trainers[i], i, n_rows[i], !stats) : td3_eval_admit_io(io[i], i, !stats);
         })) return rc;
     sac_trainer *t0 = trainers[0];
 
@@ -141,19 +139,28 @@ int td3_evaluate_general_many(sac_trainer_t *const *trainers, int n_trainers, co
         if (act_general_reserve(t, std::max(2 * slice_p[i], 5 * slice_q[i]))) return -1;
         LP = std::max(LP, P.nl); LQ = std::max(LQ, Q.nl);
     }
+    MomentsStage MS;
+    if (stats) moments_carve(ST.bytes, MS, n_trainers);
+    EvalRowsStage RS;
+    if (src) eval_rows_carve(ST.bytes, RS, n_trainers, n_rows);
     if (ST.reserve(t0)) return -1;
     const sac_trainer::ActStage &S = t0->act_stage;
     LS.bind(S.h, S.d);
     EvalYTd3Member *ytab = reinterpret_cast<EvalYTd3Member *>(S.h + tab_bytes);
-    int yblocks = 0, m = 0;
+    int yblocks = 0, m = 0, row_wgs = 0;
     for (int i = 0; i < n_trainers; ++i) {
         const sac_trainer *t = trainers[i];
         if (n_rows[i] == 0) continue;
         const td3_eval_io_t &E = io[i];
         const int n = n_rows[i];
         auto dev = [&](int k) { return ST.dev(i, k); };
-        ST.in(i, P_OBS, E.obs); ST.in(i, P_ACT, E.act); ST.in(i, P_REW, E.rew); ST.in(i, P_TERM, E.term);
-        ST.in(i, P_NOBS, E.next_obs); ST.in(i, P_EPS, E.eps);
+        if (src) {
+            row_wgs += eval_rows_member(S, RS, m, i, row_wgs, src[i], n, dev(P_OBS), dev(P_ACT), dev(P_REW), dev(P_TERM), dev(P_NOBS));
+        } else {
+            ST.in(i, P_OBS, E.obs); ST.in(i, P_ACT, E.act); ST.in(i, P_REW, E.rew); ST.in(i, P_TERM, E.term);
+            ST.in(i, P_NOBS, E.next_obs);
+        }
+        ST.in(i, P_EPS, E.eps);
         float *rows = dev(P_ROWS);
         // the policy on s and the target policy on s', launches 0 .. : their heads write a_pi and a_smooth (a_target)
         for (int s = 0; s < 2; ++s) {
@@ -178,24 +185,59 @@ int td3_evaluate_general_many(sac_trainer_t *const *trainers, int n_trainers, co
         for (int s = 0; s < 5; ++s)
             LS.chain({t->gen->net[net_of[s]], dev(obs_of[s]), dev(act_of[s]), t->O, n, t->act_gen, s * slice_q[i],
                       rows + (size_t)s * n, true, LP});
+        if (stats) td3_moments_member(S, MS, m, i, rows, dev(P_A_PI), n, t->A);
         EvalYTd3Member &M = ytab[m++];
         M.rew = dev(P_REW); M.term = dev(P_TERM); M.rows = rows;
         M.n = n; M.wg0 = yblocks;
         M.rs = t->cfg.reward_scale; M.discount = t->cfg.discount;
         yblocks += (n + EG_YROWS - 1) / EG_YROWS;
     }
+    if (src && eval_rows_launch(t0, RS, m, row_wgs, src, n_trainers, n_rows)) return -1;
     for (int l = 0; l < LP + LQ; ++l)
         if (LS.launch(l < LP ? k_eval_layer_td3 : k_eval_layer<true>, t0, l)) return -1;
     hipLaunchKernelGGL(k_eval_y_td3, dim3(yblocks), dim3(EG_YROWS), 0, t0->stream,
                        reinterpret_cast<const EvalYTd3Member *>(S.d + tab_bytes), m);
     SAC_HIP(hipGetLastError());
+    if (stats && td3_moments_launch(t0, MS, m)) return -1;
     if (wait_trainer_stream(t0)) return -1;
     for (int i = 0; i < n_trainers; ++i) {
         if (n_rows[i] == 0) continue;
         const td3_eval_io_t &E = io[i];
         ST.back(i, {{E.rows, P_ROWS}, {E.a_pi, P_A_PI}, {E.a_target, P_A_TARGET}, {E.a_smooth, P_A_SMOOTH}});
+        if (stats) td3_moments_read(S, MS, i, &stats[i]);
     }
     return 0;
+}
+
+static InferEntry td3_eval_general_entry(const char *fn, const char *instead) {
+    InferEntry IE = {fn, true, false, "device evaluation", instead, "evaluate"};
+    IE.td3_only = true;
+    return IE;
+}
+
+// (declared extern "C" in include/sac_hip.h)
+int td3_evaluate_general_many(sac_trainer_t *const *trainers, int n_trainers, const int32_t *n_rows, td3_eval_io_t *io) {
+    SAC_REQUIRE(trainers && n_rows && io, "bad arguments to td3_evaluate_general_many");
+    const InferEntry IE = td3_eval_general_entry(
+        "td3_evaluate_general_many", "td3_evaluate is its device evaluation entry, td3_evaluate_general serves the general step");
+    return td3_evaluate_general_body(IE, trainers, n_trainers, n_rows, io, nullptr);
+}
+
+int td3_evaluate_general_stats_many(sac_trainer_t *const *trainers, int n_trainers, const int32_t *n_rows, td3_eval_io_t *io,
+                                    td3_eval_stats_t *stats) {
+    SAC_REQUIRE(trainers && n_rows && io && stats, "bad arguments to td3_evaluate_general_stats_many");
+    const InferEntry IE = td3_eval_general_entry(
+        "td3_evaluate_general_stats_many", "td3_evaluate_stats_many is its entry, td3_evaluate_general_stats_many serves the general step");
+    return td3_evaluate_general_body(IE, trainers, n_trainers, n_rows, io, stats);
+}
+
+int td3_evaluate_replay_general_many(sac_trainer_t *const *trainers, int n_trainers, const int32_t *n_rows,
+                                     const sac_eval_src_t *src, td3_eval_io_t *io, td3_eval_stats_t *stats) {
+    SAC_REQUIRE(trainers && n_rows && src && io, "bad arguments to td3_evaluate_replay_general_many");
+    const InferEntry IE = td3_eval_general_entry(
+        "td3_evaluate_replay_general_many",
+        "td3_evaluate_replay_many is its entry, td3_evaluate_replay_general_many serves the general step");
+    return td3_evaluate_general_body(IE, trainers, n_trainers, n_rows, io, stats, src);
 }
 
 int td3_evaluate_general(sac_trainer_t *t, int64_t n, td3_eval_io_t *io) {

@@ -26,7 +26,7 @@ from .replay_buffer import EnvReplayBuffer
 from .group import (ArchSACTrainerGroup, ArchTD3TrainerGroup, GroupActor, MixedSACTrainerGroup, MixedTD3TrainerGroup,
                     MlpSACTrainerGroup, MlpTD3TrainerGroup, SACTrainerGroup, TD3TrainerGroup, act_many,
                     evaluate_many, evaluate_replay_many, q_values_many, runs_general_step, param_moments_many, param_statistics,
-                    td3_evaluate_many,
+                    td3_evaluate_many, td3_evaluate_replay_many,
                     unit_moments_many, unit_statistics)
 from .infer import check_general, check_stats, param_target
 from .infer import td3_eval_statistics
@@ -369,14 +369,25 @@ def _td3_validation_eps(seed, epoch, batch, A):
     return rs.standard_normal((batch["observations"].shape[0], A))
 
 
+def _td3_objective_columns(prefix, stats, n):
+    """<prefix><key> for every key of td3_eval_statistics, and <prefix>Num Transitions = n.  stats None (nothing to
+    evaluate this epoch: no evaluation path, an empty buffer): the columns stay, empty."""
+    if stats is None:
+        stats = OrderedDict((k, float("nan")) for k in td3_eval_statistics(np.zeros((6, 1)), np.zeros((1, 1))))
+    d = OrderedDict((prefix + k, v) for k, v in stats.items())
+    d[prefix + "Num Transitions"] = int(n)
+    return d
+
+
 def _td3_validation_columns(stats, batch):
     """The validation block of a TD3 run's row: validation/<key> for every key of td3_eval_statistics and
     validation/Num Transitions.  stats None (no evaluation path this epoch): the columns stay, empty."""
-    if stats is None:
-        stats = OrderedDict((k, float("nan")) for k in td3_eval_statistics(np.zeros((6, 1)), np.zeros((1, 1))))
-    d = OrderedDict(("validation/" + k, v) for k, v in stats.items())
-    d["validation/Num Transitions"] = 0 if batch is None else int(batch["observations"].shape[0])
-    return d
+    return _td3_objective_columns("validation/", stats, 0 if batch is None else batch["observations"].shape[0])
+
+
+def _td3_replay_columns(stats, n):
+    """The replay block of a TD3 run's row: the statistics of n replay rows (0: an empty buffer this epoch)."""
+    return _td3_objective_columns("replay/", stats, n)
 
 
 def _objective_columns(prefix, stats, n):
@@ -398,9 +409,9 @@ def _validation_columns(stats, batch):
 REPLAY_STREAM = 0x52504C          # "RPL": the third seed word of an epoch's replay-evaluation draws
 
 
-def check_replay_eval(replay_eval):
+def check_replay_eval(replay_eval, name="replay_eval"):
     if isinstance(replay_eval, bool) or not isinstance(replay_eval, (int, np.integer)) or replay_eval < 0:
-        raise RuntimeError(f"replay_eval is a row count (0: off), got {replay_eval!r}")
+        raise RuntimeError(f"{name} is a row count (0: off), got {replay_eval!r}")
     return int(replay_eval)
 
 
@@ -466,8 +477,9 @@ class EvalOptions(NamedTuple):
     replay_eval, and for a run with the fused kernels' shapes, it has no effect.
     eval_stats ("host" or "device") is evaluate's `stats`: where the statistics of a run that is evaluated on the device
     are reduced -- eval_statistics on the columns copied out, or k_eval_moments on the device (the same columns of
-    progress.csv, equal up to the rounding of a float64 sum in another order).  Without validation and replay_eval it
-    has no effect.
+    progress.csv, equal up to the rounding of a float64 sum in another order).  It applies to td3_validation and
+    td3_replay_eval in the same way (evaluate_td3's `stats`: k_eval_moments_td3).  Without validation, replay_eval,
+    td3_validation and td3_replay_eval it has no effect.
 
     replay_eval=N > 0: the same objectives on min(N, buffer size) rows of the REPLAY buffer in place (evaluate_replay: a
     kernel copies the rows into the evaluation's staging, no gather to the host), in front of the epoch's exploration
@@ -499,7 +511,17 @@ class EvalOptions(NamedTuple):
     variant: a SAC variant is refused (validation=True is its option).  eval_general applies to it as to validation:
     under "device" a TD3 run of the general step evaluates on the device as well (td3_evaluate_general: k_eval_layer_td3
     and k_eval_layer, one launch per layer on the live weights; in a group one td3_evaluate_general_many call per 16
-    such runs)."""
+    such runs).  eval_stats applies too: under "device" the statistics of a run that is evaluated on the device are
+    reduced there (td3_evaluate_stats_many / td3_evaluate_general_stats_many).
+
+    td3_replay_eval=N > 0: the TD3 objectives on min(N, buffer size) rows of the REPLAY buffer in place
+    (evaluate_td3_replay: k_eval_rows copies the rows into the evaluation's staging, no gather to the host), taken where
+    validation is taken -- the figure validation/QF1 Loss stands next to, at the same parameters.  Indices and the
+    smoothing draw come from RandomState([seed, epoch, 0x52504C]), the indices first: nothing to checkpoint.  The row
+    gains replay/<key> for every key of td3_eval_statistics and replay/Num Transitions where the SAC replay block sits;
+    the group entries make ONE td3_evaluate_replay_many call per epoch, and only when some run has rows.  eval_general
+    and eval_stats apply to it as to td3_validation.  Every run must be a TD3 variant: a SAC variant is refused
+    (replay_eval=N is its option)."""
     q_diagnostics: bool = False
     q_general: str = "host"
     validation: bool = False
@@ -509,6 +531,7 @@ class EvalOptions(NamedTuple):
     unit_diagnostics: bool = False
     unit_general: str = "host"
     param_diagnostics: bool = False
+    td3_replay_eval: int = 0
     td3_validation: bool = False
 
 
@@ -518,7 +541,8 @@ def _refuse_td3(variant, what, call, reason):
 
 
 def _options(what, specs, acting, q_diagnostics, q_general, validation, eval_general, eval_stats, replay_eval,
-             unit_diagnostics=False, unit_general="host", param_diagnostics=False, td3_validation=False):
+             unit_diagnostics=False, unit_general="host", param_diagnostics=False, td3_replay_eval=0,
+             td3_validation=False):
     """The EvalOptions of entry `what`, after the value checks of its keywords (acting's too) and, for the variant at
     the head of every run spec in `specs`, the TD3 refusals: all of it in front of anything that builds a run."""
     check_stats(eval_stats)
@@ -527,7 +551,8 @@ def _options(what, specs, acting, q_diagnostics, q_general, validation, eval_gen
     check_general(eval_general)
     check_general(unit_general)
     opts = EvalOptions(q_diagnostics, q_general, validation, eval_general, eval_stats, check_replay_eval(replay_eval),
-                       bool(unit_diagnostics), unit_general, bool(param_diagnostics), bool(td3_validation))
+                       bool(unit_diagnostics), unit_general, bool(param_diagnostics),
+                       check_replay_eval(td3_replay_eval, "td3_replay_eval"), bool(td3_validation))
     for spec in specs if opts.validation else ():
         _refuse_td3(tuple(spec)[0], what, "validation=True", "validation evaluates the SAC objective (SACTrainer.evaluate)")
     for spec in specs if opts.replay_eval else ():
@@ -537,6 +562,10 @@ def _options(what, specs, acting, q_diagnostics, q_general, validation, eval_gen
         if tuple(spec)[0].get("algorithm", "SAC") != "TD3":
             raise RuntimeError(f"{what}(td3_validation=True): td3_validation evaluates the TD3 objective "
                                "(TD3Trainer.evaluate_td3); a SAC variant takes validation=True")
+    for spec in specs if opts.td3_replay_eval else ():
+        if tuple(spec)[0].get("algorithm", "SAC") != "TD3":
+            raise RuntimeError(f"{what}(td3_replay_eval=N): td3_replay_eval evaluates the TD3 objective "
+                               "(TD3Trainer.evaluate_td3_replay); a SAC variant takes replay_eval=N")
     return opts
 
 
@@ -565,7 +594,9 @@ def _epoch_evaluations(runs, epoch, opts, take=ALL_BLOCKS, many=True):
     """The blocks of `take` that `opts` switches on, for every run at this moment of `epoch`: ([{block: columns} per
     run], seconds spent).  many: ONE q_values_many / evaluate_many / evaluate_replay_many / unit_moments_many
     / param_moments_many call over all runs (evaluate_replay_many only when some run has rows); otherwise each trainer's
-    own q_values / evaluate / evaluate_replay / unit_moments / param_moments."""
+    own q_values / evaluate / evaluate_replay / unit_moments / param_moments.  For TD3 runs (td3_validation,
+    td3_replay_eval) td3_evaluate_many and td3_evaluate_replay_many stand in the same two places, or the trainer's own
+    evaluate_td3 / evaluate_td3_replay."""
     s0 = time.time()
     cols, trainers = [{} for _ in runs], [r["trainer"] for r in runs]
     paths = [r["evalc"].epoch_paths for r in runs]
@@ -587,10 +618,20 @@ def _epoch_evaluations(runs, epoch, opts, take=ALL_BLOCKS, many=True):
     if opts.td3_validation and "validation" in take:
         batches = [_validation_batch(p, t.obs_dim, t.act_dim) for p, t in zip(paths, trainers)]
         eps = [_td3_validation_eps(r["seed"], epoch, b, t.act_dim) for r, b, t in zip(runs, batches, trainers)]
-        got = (td3_evaluate_many(trainers, batches, eps=eps, **gen) if many else
-               [None if b is None else t.evaluate_td3(b, eps=e, **gen) for t, b, e in zip(trainers, batches, eps)])
+        got = (td3_evaluate_many(trainers, batches, eps=eps, **gen, **stats_kw) if many else
+               [None if b is None else t.evaluate_td3(b, eps=e, **gen, **stats_kw) for t, b, e in zip(trainers, batches, eps)])
         for c, s, b in zip(cols, got, batches):
             c["validation"] = _td3_validation_columns(s, b)
+    if opts.td3_replay_eval and "replay" in take:               # (the row's replay block, taken where SAC's is)
+        bufs, ns = [r["buf"] for r in runs], [_replay_rows(opts.td3_replay_eval, r["buf"]) for r in runs]
+        got = [None] * len(runs)
+        if any(ns):
+            rngs = [_replay_rng(r["seed"], epoch) for r in runs]
+            got = (td3_evaluate_replay_many(trainers, bufs, n=ns, rngs=rngs, **gen, **stats_kw) if many else
+                   [t.evaluate_td3_replay(b, n=n, rng=g, **gen, **stats_kw) if n else None
+                    for t, b, n, g in zip(trainers, bufs, ns, rngs)])
+        for c, s, n in zip(cols, got, ns):
+            c["replay"] = _td3_replay_columns(s, n)
     if opts.replay_eval and "replay" in take:
         bufs, ns = [r["buf"] for r in runs], [_replay_rows(opts.replay_eval, r["buf"]) for r in runs]
         got = [None] * len(runs)
@@ -732,7 +773,7 @@ def _prefill(r):
 def experiment(variant, log_dir=None, seed=1, obs_dim=None, action_dim=None, num_epochs=None, device=0,
                fused_loop=True, quiet=False, checkpoint_dir=None, resume=False, acting="host", q_diagnostics=False,
                q_general="host", validation=False, eval_general="host", eval_stats="host", replay_eval=0,
-               unit_diagnostics=False, unit_general="host", param_diagnostics=False, td3_validation=False):
+               unit_diagnostics=False, unit_general="host", param_diagnostics=False, td3_replay_eval=0, td3_validation=False):
     """variant.json -> training run.  Returns the list of progress rows (also written to
     <log_dir>/progress.csv when log_dir is given).
 
@@ -749,10 +790,11 @@ def experiment(variant, log_dir=None, seed=1, obs_dim=None, action_dim=None, num
     same amounts, whichever value is given.
 
     q_diagnostics, q_general, validation, eval_general, eval_stats, replay_eval, unit_diagnostics, unit_general,
-    param_diagnostics, td3_validation: the
+    param_diagnostics, td3_replay_eval, td3_validation: the
     per-epoch evaluations, EvalOptions; here from the trainer's own q_values, evaluate, evaluate_replay and unit_moments."""
     opts = _options("experiment", [(variant,)], acting, q_diagnostics, q_general, validation, eval_general, eval_stats,
-                    replay_eval, unit_diagnostics, unit_general, param_diagnostics, td3_validation)
+                    replay_eval, unit_diagnostics, unit_general, param_diagnostics, td3_replay_eval,
+                    td3_validation)
     validate(variant)
     # This driver's runs are a function of `seed` alone: initial weights come from np.random (seeded here), every noise
     # stream from `seed` -- whether or not torch happens to be loaded in the process (the reference's own scripts seed
@@ -918,7 +960,7 @@ def experiment_group(variant, seeds, log_dir=None, num_epochs=None, obs_dim=None
                      quiet=False, checkpoint_dir=None, resume=False, chunk_rows=DEFAULT_CHUNK_ROWS, acting="host", sessions=True,
                      general_sessions=None, q_diagnostics=False, q_general="host", validation=False,
                      eval_general="host", eval_stats="host", replay_eval=0, unit_diagnostics=False, unit_general="host",
-                     param_diagnostics=False, td3_validation=False):
+                     param_diagnostics=False, td3_replay_eval=0, td3_validation=False):
     """One configuration, several seeds, one process: each seed is the run ``experiment(variant, seed=s)`` would make --
     its own synthetic environments, collectors, weights and replay buffer -- and every epoch's training block is ONE
     SACTrainerGroup.train_loop (TD3 variants: TD3TrainerGroup; hidden sizes other than two layers of at most 256 units:
@@ -940,10 +982,11 @@ def experiment_group(variant, seeds, log_dir=None, num_epochs=None, obs_dim=None
     device too (one sac_policy_act_general_many call per tick and 16 of them; with sessions and general_sessions=True one
     sac_gactor_act call, None: GroupActor's default); rows as experiment(..., acting="device_all").
     q_diagnostics, q_general, validation, eval_general, eval_stats, replay_eval, unit_diagnostics, unit_general,
-    param_diagnostics, td3_validation: the
+    param_diagnostics, td3_replay_eval, td3_validation: the
     per-epoch evaluations, EvalOptions; each seed's rows are those of experiment(variant, seed=s) with the same options."""
     opts = _options("experiment_group", [(variant,)], acting, q_diagnostics, q_general, validation, eval_general,
-                    eval_stats, replay_eval, unit_diagnostics, unit_general, param_diagnostics, td3_validation)
+                    eval_stats, replay_eval, unit_diagnostics, unit_general, param_diagnostics, td3_replay_eval,
+                    td3_validation)
     if resume and not checkpoint_dir:
         raise RuntimeError("experiment_group(resume=True) needs the checkpoint_dir to resume from")
     validate(variant)
@@ -998,7 +1041,7 @@ def experiment_sweep(runs, log_dir=None, num_epochs=None, device=0, quiet=False,
                      chunk_rows=DEFAULT_CHUNK_ROWS, hidden_sweep=False, acting="host", sessions=True, general_sessions=None,
                      q_diagnostics=False, q_general="host", validation=False,
                      eval_general="host", eval_stats="host", replay_eval=0, unit_diagnostics=False, unit_general="host",
-                     param_diagnostics=False, td3_validation=False):
+                     param_diagnostics=False, td3_replay_eval=0, td3_validation=False):
     """Several tasks x seeds, one process, one device: every entry of ``runs`` -- (variant, seed), or (variant, seed,
     obs_dim, action_dim) for a task without pinned dims -- is the run ``experiment(variant, seed=seed)`` would make, and
     every epoch's training block is ONE MixedSACTrainerGroup.train_loop (TD3 variants: MixedTD3TrainerGroup; hidden sizes
@@ -1017,12 +1060,13 @@ def experiment_sweep(runs, log_dir=None, num_epochs=None, device=0, quiet=False,
     "device_all" those runs act on the device inside the same ticks, and each run's rows are those of its solo
     experiment(..., acting="device_all").
     q_diagnostics, q_general, validation, eval_general, eval_stats, replay_eval, unit_diagnostics, unit_general,
-    param_diagnostics, td3_validation: the
+    param_diagnostics, td3_replay_eval, td3_validation: the
     per-epoch evaluations, EvalOptions, as for experiment_group; in a hidden sweep the runs of the general step take the
     host path inside the same call, or
     the device's under q_general / eval_general "device".  A sweep with a TD3 run refuses validation and replay_eval."""
     opts = _options("experiment_sweep", runs, acting, q_diagnostics, q_general, validation, eval_general, eval_stats,
-                    replay_eval, unit_diagnostics, unit_general, param_diagnostics, td3_validation)
+                    replay_eval, unit_diagnostics, unit_general, param_diagnostics, td3_replay_eval,
+                    td3_validation)
     if resume and not checkpoint_dir:
         raise RuntimeError("experiment_sweep(resume=True) needs the checkpoint_dir to resume from")
     specs = []

@@ -20,7 +20,8 @@ from . import _lib
 # (the inference names live in infer.py; they stay importable from here)
 from .infer import (GENERAL, GENERAL_SESSIONS, MAX_MEMBERS, GroupActor, act_many, check_general,  # noqa: F401
                     evaluate_many, evaluate_replay_many, general_shape, merge_unit_moments, param_moments_many,
-                    param_moments_reference, param_statistics, q_values_many, runs_general_step, td3_evaluate_many, unit_moments_many, unit_moments_reference, unit_statistics)
+                    param_moments_reference, param_statistics, q_values_many, runs_general_step, td3_eval_moments, td3_evaluate_many,
+                    td3_evaluate_replay_many, td3_moments_statistics, unit_moments_many, unit_moments_reference, unit_statistics)
 from .sac import SACTrainer
 from .td3 import TD3Trainer
 
@@ -91,10 +92,17 @@ class _Members:
         return evaluate_replay_many(self.trainers, replay_buffers, n=n, indices=indices, eps=eps, rngs=rngs, rows=rows,
                                     general=general, stats=stats)
 
-    def td3_evaluate_many(self, batches, eps=None, rngs=None, rows=False, general="host"):
+    def td3_evaluate_many(self, batches, eps=None, rngs=None, rows=False, general="host", stats="host"):
         """td3_evaluate_many over the group's members: the TD3 objectives (a SAC group raises through the member check
-        there; general as there)."""
-        return td3_evaluate_many(self.trainers, batches, eps=eps, rngs=rngs, rows=rows, general=general)
+        there; general and stats as there)."""
+        return td3_evaluate_many(self.trainers, batches, eps=eps, rngs=rngs, rows=rows, general=general, stats=stats)
+
+    def td3_evaluate_replay_many(self, replay_buffers, n=None, indices=None, eps=None, rngs=None, rows=False, general="host",
+                                 stats="host"):
+        """td3_evaluate_replay_many over the group's members on their replay buffers -- the ones train_loop takes, one per
+        member (n, indices, general and stats as there; a SAC group raises through the member check there)."""
+        return td3_evaluate_replay_many(self.trainers, replay_buffers, n=n, indices=indices, eps=eps, rngs=rngs, rows=rows,
+                                        general=general, stats=stats)
 
 
 class _SACMembers:

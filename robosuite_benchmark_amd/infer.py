@@ -80,6 +80,10 @@ EVAL_ENTRIES = {FUSED: ("sac_evaluate_many", "sac_evaluate_stats_many"),        
 EVAL_REPLAY_ENTRIES = {FUSED: "sac_evaluate_replay_many",                            # (stats: an argument, NULL for "host")
                        GENERAL_STEP: "sac_evaluate_replay_general_many"}
 TD3_EVAL_ENTRIES = {FUSED: "td3_evaluate_many", GENERAL_STEP: "td3_evaluate_general_many"}
+TD3_EVAL_STATS_ENTRIES = {FUSED: "td3_evaluate_stats_many",                          # (stats "device")
+                          GENERAL_STEP: "td3_evaluate_general_stats_many"}
+TD3_EVAL_REPLAY_ENTRIES = {FUSED: "td3_evaluate_replay_many",                        # (stats: an argument, NULL for "host")
+                           GENERAL_STEP: "td3_evaluate_replay_general_many"}
 
 
 def route(t, general, on_host=False):
@@ -697,12 +701,13 @@ def _merge_all(a, b):
     return b if a is None else OrderedDict((k, merge_moments(a[k], b[k])) for k in a)
 
 
-def _stats_moments(st):
-    """The records of one sac_eval_stats_t as eval_moments returns them."""
-    vals = np.frombuffer(st, np.float64, len(_lib.EVAL_MOMENTS) * len(_lib.EVAL_MOMENT_FIELDS)).tolist()
+def _stats_moments(st, names=_lib.EVAL_MOMENTS):
+    """The records of one sac_eval_stats_t as eval_moments returns them (names=_lib.TD3_EVAL_MOMENTS: of one
+    td3_eval_stats_t, as td3_eval_moments does)."""
+    vals = np.frombuffer(st, np.float64, len(names) * len(_lib.EVAL_MOMENT_FIELDS)).tolist()
     k = len(_lib.EVAL_MOMENT_FIELDS)
     return OrderedDict((name, dict(zip(_lib.EVAL_MOMENT_FIELDS, vals[i * k:(i + 1) * k])))
-                       for i, name in enumerate(_lib.EVAL_MOMENTS))
+                       for i, name in enumerate(names))
 
 
 def moments_statistics(moments, alpha, log_alpha, target_entropy, auto):
@@ -911,43 +916,159 @@ def _td3_eval_result(cols, rows):
     return (result, cols) if rows else result
 
 
-def td3_evaluate_of(trainers, inputs, rows, general="host"):
+def td3_eval_moments(rows, a_pi):
+    """k_eval_moments_td3 (csrc/td3_eval_moments.h) restated in NumPy float64 -- the reference of its tests and nothing
+    else: an OrderedDict with one record {count, sum, m2, sumsq, max, min} per name of _lib.TD3_EVAL_MOMENTS, over q1, q2,
+    y, q_pi (n elements), a_pi (n A), td1 = q1 - y, td2 = q2 - y and bellman1 / bellman2 = (q - y)^2 (n), every element
+    formed in float64 from the columns given.  m2 = sum((x - sum / count)^2), a second pass as np.std's; max and min keep
+    a NaN."""
+    q1, q2, q_pi, _, _, y = [np.asarray(x, np.float64).ravel() for x in rows]
+    out = OrderedDict()
+    with np.errstate(all="ignore"):
+        xs = [q1, q2, y, q_pi, np.asarray(a_pi, np.float64).ravel(), q1 - y, q2 - y, (q1 - y) ** 2, (q2 - y) ** 2]
+        for name, x in zip(_lib.TD3_EVAL_MOMENTS, xs):
+            s = float(np.sum(x))
+            out[name] = dict(count=float(x.size), sum=s, m2=float(np.sum((x - s / x.size) ** 2)), sumsq=float(np.sum(x * x)),
+                             max=float(np.max(x)), min=float(np.min(x)))
+    return out
+
+
+def td3_moments_statistics(moments):
+    """td3_eval_statistics' OrderedDict -- the same keys in the same order -- from the moment records of td3_eval_moments
+    or of the device (td3_evaluate_stats_many): Mean = sum / count, Std = sqrt(m2 / count), Max and Min as stored,
+    QF Loss = bellman.sum / count, Policy Loss = -(q_pi.sum / count)."""
+    def stats(d, name, m):
+        d[name + " Mean"], d[name + " Std"] = m["sum"] / m["count"], float(np.sqrt(m["m2"] / m["count"]))
+        d[name + " Max"], d[name + " Min"] = m["max"], m["min"]
+
+    M = moments
+    d = OrderedDict()
+    with np.errstate(all="ignore"):
+        d["QF1 Loss"] = M["bellman1"]["sum"] / M["bellman1"]["count"]
+        d["QF2 Loss"] = M["bellman2"]["sum"] / M["bellman2"]["count"]
+        d["Policy Loss"] = -(M["q_pi"]["sum"] / M["q_pi"]["count"])
+        for name, key in (("Q1 Predictions", "q1"), ("Q2 Predictions", "q2"), ("Q Targets", "y"),
+                          ("Bellman Errors 1", "bellman1"), ("Bellman Errors 2", "bellman2"), ("Policy Action", "a_pi"),
+                          ("TD Error 1", "td1"), ("TD Error 2", "td2")):
+            stats(d, name, M[key])
+    return d
+
+
+def td3_evaluate_of(trainers, inputs, rows, general="host", stats="host", replay=None):
     """evaluate_td3 / td3_evaluate_many behind their argument checks: inputs[i] = the member's arrays as
     TD3Trainer._td3_eval_inputs checked them, or None for a member that sits out (its result: None).  The host members
     first, in member order; then the fused family, then the general one (general="device"), each in windows of its
-    entry of TD3_EVAL_ENTRIES: 16 members and 1024 rows per call."""
+    entry of TD3_EVAL_ENTRIES (stats="device": of TD3_EVAL_STATS_ENTRIES): 16 members and 1024 rows per call.
+    stats="device": a member on the device gets its statistics from the moment records of the same call
+    (td3_moments_statistics; the windows of a member joined by merge_moments) -- no td3_eval_statistics, and with
+    rows=False no column is copied back.  The host members get td3_eval_statistics under either value.
+    replay (td3_evaluate_replay_of): replay[i] = (buffer, indices) of a member with rows, whose inputs[i] then holds None
+    for the five arrays the device takes from the replay storage (TD3_EVAL_REPLAY_ENTRIES); a host member evaluates the
+    gathered batch."""
+    on_device = stats == "device"
     R = len(trainers)
     out, n_rows, served = [None] * R, [0] * R, {FUSED: [], GENERAL_STEP: []}
     for i, (t, arrs) in enumerate(zip(trainers, inputs)):
         if arrs is None:
             continue
-        where = route(t, general, t._evaluate_on_host)
+        where = route(t, general, t._evaluate_on_host) if replay is None else replay_route(t, replay[i][0], general)
         if where == HOST:
+            if replay is not None:
+                arrs = t._td3_eval_inputs(replay[i][0].gather(replay[i][1]), arrs[5], None)
             out[i] = _td3_eval_result(t._evaluate_td3_host(arrs), rows)
         else:
-            n_rows[i] = arrs[0].shape[0]
+            n_rows[i] = arrs[5].shape[0]
             served[where].append(i)
     members = served[FUSED] + served[GENERAL_STEP]
     if not members:
         return out
     lib = _lib.load()
-    chunks = {i: [] for i in members}
+    chunks, moments = {i: [] for i in members}, [None] * R
     for family in (FUSED, GENERAL_STEP):
-        entry = TD3_EVAL_ENTRIES[family]
+        if replay is not None:
+            entry = TD3_EVAL_REPLAY_ENTRIES[family]
+        else:
+            entry = (TD3_EVAL_STATS_ENTRIES if on_device else TD3_EVAL_ENTRIES)[family]
         for r0, ids, counts in windows(served[family], n_rows):
             made = [_eval_io(_lib.Td3EvalIO, _lib.TD3_EVAL_ROWS, _lib.TD3_EVAL_ARRAYS, inputs[i], r0, r0 + k,
-                             trainers[i].act_dim) for i, k in zip(ids, counts)]
+                             trainers[i].act_dim, outputs=rows or not on_device) for i, k in zip(ids, counts)]
             ios = (_lib.Td3EvalIO * len(ids))(*[m[0] for m in made])
-            _lib.check(getattr(lib, entry)(_handles(trainers, ids), len(ids), _ints(counts), ios), entry)
-            for i, m in zip(ids, made):
-                chunks[i].append(m[1])
+            sts = (_lib.Td3EvalStats * len(ids))() if on_device else None
+            if replay is None:
+                args = [ios] + ([sts] if on_device else [])
+            else:
+                idx = [np.ascontiguousarray(replay[i][1][r0:r0 + k]) for i, k in zip(ids, counts)]
+                srcs = (_lib.SacEvalSrc * len(ids))(*[_lib.SacEvalSrc(replay[i][0]._h.value, x.ctypes.data)
+                                                      for i, x in zip(ids, idx)])
+                args = [srcs, ios, sts]
+            _lib.check(getattr(lib, entry)(_handles(trainers, ids), len(ids), _ints(counts), *args), entry)
+            for k, i in enumerate(ids):
+                chunks[i].append(made[k][1])
+                if on_device:
+                    moments[i] = _merge_all(moments[i], _stats_moments(sts[k], _lib.TD3_EVAL_MOMENTS))
     for i in members:
         trainers[i]._settled()
-        out[i] = _td3_eval_result(_eval_columns(chunks[i], _lib.TD3_EVAL_ROWS, _lib.TD3_EVAL_ARRAYS), rows)
+        cols = _eval_columns(chunks[i], _lib.TD3_EVAL_ROWS, _lib.TD3_EVAL_ARRAYS) if rows or not on_device else None
+        if on_device:
+            result = td3_moments_statistics(moments[i])
+            out[i] = (result, cols) if rows else result
+        else:
+            out[i] = _td3_eval_result(cols, rows)
     return out
 
 
-def td3_evaluate_many(trainers, batches, eps=None, rngs=None, rows=False, general="host"):
+def td3_evaluate_replay_of(trainers, buffers, requests, rows, general, stats):
+    """evaluate_td3_replay / td3_evaluate_replay_many behind their argument checks: requests[i] = (indices, eps) as
+    TD3Trainer._td3_replay_request checked them, or None for a member that sits out.  With rows the column dict of a
+    member additionally holds "indices"."""
+    inputs = [None if q is None else (None,) * 5 + (q[1],) for q in requests]
+    replay = [None if q is None else (b, q[0]) for b, q in zip(buffers, requests)]
+    out = td3_evaluate_of(trainers, inputs, rows, general, stats, replay=replay)
+    if rows:
+        for q, res in zip(requests, out):
+            if q is not None:
+                res[1]["indices"] = q[0]
+    return out
+
+
+def _refuse_sac_members(caller, trainers, instead):
+    for i, t in enumerate(trainers):
+        if not _is_td3(t):
+            raise RuntimeError(f"{caller} member {i} is a SAC trainer: this call evaluates the TD3 objective (a "
+                               f"deterministic policy with target smoothing); {instead} evaluates the SAC objective")
+
+
+def td3_evaluate_replay_many(trainers, buffers, n=None, indices=None, eps=None, rngs=None, rows=False, general="host",
+                             stats="host"):
+    """TD3Trainer.evaluate_td3_replay for many runs at once: result[i] = trainers[i].evaluate_td3_replay(buffers[i], n or
+    indices[i], eps[i], rngs[i]).  Exactly one of n and indices: n one row count for every member or one per member,
+    indices one array of storage rows per member; an entry of None / 0 / no rows: the member sits out and gets None.
+    eps / rngs: one entry per trainer or None.  Two members may share a buffer (rows are only read).  The members on
+    the device are served by ONE call per 16 of them and 1024 rows per family (td3_evaluate_replay_many /
+    td3_evaluate_replay_general_many; general and stats as for td3_evaluate_many); the others run evaluate_td3 on their
+    gathered batch inside the same call.  A member's result is bit for bit that of its own evaluate_td3_replay; a SAC
+    member raises (evaluate_replay_many is the call for the SAC objective)."""
+    check_stats(stats)
+    check_general(general)
+    trainers = list(trainers)
+    R = len(trainers)
+    if (n is None) == (indices is None):
+        raise ValueError("td3_evaluate_replay_many takes exactly one of n and indices")
+    trainers, buffers, counts, indices, eps, rngs = _member_args(
+        "td3_evaluate_replay_many", "buffer (and row count or indices, eps, rng)", trainers, buffers,
+        [n] * R if np.isscalar(n) else n, indices, eps, rngs)
+    _refuse_sac_members("td3_evaluate_replay_many", trainers, "evaluate_replay_many")
+    requests = [None] * R
+    for i, (t, b) in enumerate(zip(trainers, buffers)):
+        if n is not None and not counts[i]:
+            continue
+        if n is None and (indices[i] is None or np.asarray(indices[i]).size == 0):
+            continue
+        requests[i] = t._td3_replay_request(b, counts[i], indices[i], eps[i], rngs[i])
+    return td3_evaluate_replay_of(trainers, buffers, requests, rows, general, stats)
+
+
+def td3_evaluate_many(trainers, batches, eps=None, rngs=None, rows=False, general="host", stats="host"):
     """TD3Trainer.evaluate_td3 for many runs at once: result[i] = trainers[i].evaluate_td3(batches[i], eps[i], rngs[i])
     (eps / rngs: one entry per trainer or None; batches[i] None or without rows: the member sits out and gets None).  The
     TD3 members with the fused kernels' shapes are served by ONE launch per 16 of them and 1024 rows (td3_evaluate_many:
@@ -957,19 +1078,22 @@ def td3_evaluate_many(trainers, batches, eps=None, rngs=None, rows=False, genera
     (evaluate_many is the call for the SAC objective).
     general="device": the TD3 members of the general step are evaluated on the device as well, by ONE
     td3_evaluate_general_many call per 16 of them and 1024 rows; their results are bit for bit those of their own
-    evaluate_td3(general="device")."""
+    evaluate_td3(general="device").
+    stats="device" (evaluate_td3's `stats`): the members served by those two entries get their statistics reduced on the
+    device in the same call (td3_evaluate_stats_many / td3_evaluate_general_stats_many: one k_eval_moments_td3 launch in
+    front of the call's wait) -- no td3_eval_statistics for them, and with rows=False no column is copied back.  A
+    member's records are byte for byte those of its own evaluate_td3(stats="device").  The members on the host path get
+    td3_eval_statistics under either value."""
+    check_stats(stats)
     check_general(general)
     trainers, batches, eps, rngs = _member_args("td3_evaluate_many", "batch (and eps, and rng)", trainers, batches, eps, rngs)
-    for i, t in enumerate(trainers):
-        if not _is_td3(t):
-            raise RuntimeError(f"td3_evaluate_many member {i} is a SAC trainer: this call evaluates the TD3 objective (a "
-                               "deterministic policy with target smoothing); evaluate_many evaluates the SAC objective")
+    _refuse_sac_members("td3_evaluate_many", trainers, "evaluate_many")
     inputs = [None] * len(trainers)
     for i, (t, b) in enumerate(zip(trainers, batches)):
         if b is None or np.atleast_2d(b["observations"]).shape[0] == 0:
             continue
         inputs[i] = t._td3_eval_inputs(b, eps[i], rngs[i])
-    return td3_evaluate_of(trainers, inputs, rows, general)
+    return td3_evaluate_of(trainers, inputs, rows, general, stats)
 
 
 # ---- acting sessions ----------------------------------------------------------------------------------------------------

@@ -114,7 +114,7 @@ class TD3Trainer(SACTrainer):
                    a_target=_lib.f32(a_target), a_smooth=_lib.f32(a_smooth))
         return infer._eval_columns([out], _lib.TD3_EVAL_ROWS, _lib.TD3_EVAL_ARRAYS)
 
-    def evaluate_td3(self, batch, eps=None, rng=None, rows=False, general="host"):
+    def evaluate_td3(self, batch, eps=None, rng=None, rows=False, general="host", stats="host"):
         """The TD3 objectives of this run on `batch` WITHOUT a gradient step: `batch` is the dict train() takes
         (observations, actions, rewards, terminals, next_observations; any n >= 1), typically transitions the run has not
         trained on -- an epoch's evaluation paths.  From the LIVE weights: on the device (td3_evaluate: k_eval_td3, one
@@ -133,9 +133,67 @@ class TD3Trainer(SACTrainer):
         float32 per-row arrays q1, q2, q_pi, tq1, tq2, y (n,) and a_pi, a_target, a_smooth (n, A):
         q_pi = Q1(s, a_pi), a_pi the policy's action on s; a_target the TARGET policy's action on s',
         a_smooth = a_target + clip(eps * target_policy_noise, +-target_policy_noise_clip), the targets tq1 / tq2 on
-        (s', a_smooth), y = reward_scale r + (1 - d) discount min(tq1, tq2)."""
+        (s', a_smooth), y = reward_scale r + (1 - d) discount min(tq1, tq2).
+        stats (one of infer.STATS) decides where the statistics of a trainer that is evaluated on the device are reduced:
+        "host", the default, copies the columns out and runs td3_eval_statistics; "device" reduces them on the device as
+        well (td3_evaluate_stats_many / td3_evaluate_general_stats_many: k_eval_moments_td3 behind the evaluation's
+        kernels, in front of the same wait) and builds the same keys from the moment records (td3_moments_statistics) --
+        no td3_eval_statistics, and with rows=False no column leaves the staging.  The values agree with "host" up to the
+        rounding of a float64 sum in another order; Max and Min are equal.  A trainer on the host path gets
+        td3_eval_statistics under either value."""
+        infer.check_stats(stats)
         infer.check_general(general)
-        return infer.td3_evaluate_of([self], [self._td3_eval_inputs(batch, eps, rng)], rows, general)[0]
+        return infer.td3_evaluate_of([self], [self._td3_eval_inputs(batch, eps, rng)], rows, general, stats)[0]
+
+    def _td3_replay_request(self, buffer, n, indices, eps, rng):
+        """evaluate_td3_replay's arguments, checked before any library call: (indices int64 (k,), eps float32 (k, A)).
+        Exactly one of n and indices; with n the indices are rng.randint(0, size, n), drawn IN FRONT of the single
+        standard_normal((k, A)) from the same stream (rng None: evaluate_td3's private one)."""
+        if (n is None) == (indices is None):
+            raise ValueError("evaluate_td3_replay takes exactly one of n and indices")
+        size = int(buffer.num_steps_can_sample())
+        if size < 1:
+            raise RuntimeError("evaluate_td3_replay: the replay buffer is empty")
+        if indices is None:
+            if int(n) < 1:
+                raise ValueError(f"evaluate_td3_replay: n = {n} (at least one row)")
+            rng = self._eval_stream(rng)
+            idx = np.ascontiguousarray(rng.randint(0, size, int(n)), dtype=np.int64)
+        else:
+            idx = np.ascontiguousarray(np.asarray(indices).reshape(-1), dtype=np.int64)
+            if idx.size < 1:
+                raise ValueError("evaluate_td3_replay: no indices (at least one row)")
+            if int(idx.min()) < 0 or int(idx.max()) >= size:
+                bad = idx[(idx < 0) | (idx >= size)][0]
+                raise RuntimeError(f"evaluate_td3_replay: index {int(bad)} out of range [0, {size})")
+        k, A = idx.size, self.act_dim
+        if eps is None:
+            eps = self._eval_stream(rng).standard_normal((k, A))
+        eps = _lib.f32(np.atleast_2d(eps))
+        if eps.shape != (k, A):
+            raise ValueError(f"evaluate_td3_replay: eps {eps.shape} for {k} rows of {A} actions")
+        return idx, eps
+
+    def evaluate_td3_replay(self, buffer, n=None, indices=None, eps=None, rng=None, rows=False, general="host",
+                            stats="host"):
+        """evaluate_td3 on rows of `buffer` (an EnvReplayBuffer of this run's dims) IN PLACE: the TD3 objectives at the
+        current parameters on the data the run trains on -- the figure validation/QF1 Loss stands next to.  Exactly one
+        of n and indices: `indices` are STORAGE rows (0 <= index < buffer size, any count, repeats allowed), `n` draws
+        them as rng.randint(0, size, n) in front of the single standard_normal((k, A)) from the same `rng` (None:
+        evaluate_td3's private stream; np.random is never touched).  eps, rng, rows, general and stats are evaluate_td3's;
+        the result is what evaluate_td3(buffer.gather(indices), eps=the same draw, ...) returns, bit for bit, and with
+        rows=True the column dict additionally holds "indices".
+        On the device td3_evaluate_replay_many / td3_evaluate_replay_general_many copy the rows with a kernel from the
+        replay storage into the evaluation's staging (k_eval_rows, one launch per 1024 rows in front of the evaluation's
+        kernels), ordered behind pending add_* copies by an event: no synchronised D2H copy, no NumPy dict, no conversion
+        and no memcpy into the staging.  The buffer is only read: its generator, np.random, its read-ahead and loop
+        speculation stay as they are, and training continues bit for bit as if the call had not happened.  A trainer
+        that evaluate_td3 sends to the host path (no handle; the general step under general="host"), and a buffer
+        without device storage, run evaluate_td3(buffer.gather(indices) as a batch, ...)."""
+        infer.check_stats(stats)
+        infer.check_general(general)
+        request = self._td3_replay_request(buffer, n, indices, eps, rng)
+        return infer.td3_evaluate_replay_of([self], [buffer], [request], rows, general, stats)[0]
 
     def get_snapshot(self):
         snap = super().get_snapshot()

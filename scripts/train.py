@@ -26,7 +26,9 @@
  the evaluation paths, from per-unit reductions of the hidden layers: twelve units/ columns; SAC and TD3.
  --unit_general device: with --unit_diagnostics, runs of any hidden sizes reduce them on the device.
  --td3_validation: --validation for TD3 runs: every epoch, the TD3 losses, TD errors and targets on the evaluation
- paths' transitions from the live weights: validation/ columns in progress.csv; TD3 only.)
+ paths' transitions from the live weights: validation/ columns in progress.csv; TD3 only.
+ --td3_replay_eval [N]: --replay_eval for TD3 runs: every epoch, the TD3 objectives on N (bare: 1024) rows of the replay
+ buffer, read in place on the device: replay/ columns in progress.csv; TD3 only.  --eval_stats device applies to both.)
 Runs the variant unchanged (batch size, lrs, tau, period, buffer size ... from the JSON) on the
 HIP library with a synthetic environment of the task's dimensions (robosuite is not installed)."""
 import argparse
@@ -94,7 +96,8 @@ def build_parser():
                     help="with --validation: where the statistics (means, deviations, extremes, losses) of the runs that are "
                          "evaluated on the device are reduced -- host (the columns are copied out and reduced in NumPy) or "
                          "device (one more HIP launch in front of the call's wait); the same validation/ columns either "
-                         "way; without --validation it has no effect")
+                         "way; it applies to --td3_validation and --td3_replay_eval (the TD3 objectives) in the same way; "
+                         "without --validation, --replay_eval and those two it has no effect")
     ap.add_argument("--replay_eval", type=int, nargs="?", const=1024, default=0, metavar="N",
                     help="every epoch, evaluate the same objectives on min(N, buffer size) rows of the replay buffer in "
                          "place (a HIP kernel copies the rows from the replay storage into the evaluation's mapped staging: no "
@@ -120,6 +123,12 @@ def build_parser():
                          "policy loss) on the transitions of the evaluation paths, which never enter the replay buffer (a "
                          "HIP kernel on the live weights), and log them as validation/<key>; TD3 only (SAC runs take "
                          "--validation); off: progress.csv is unchanged")
+    ap.add_argument("--td3_replay_eval", type=int, nargs="?", const=1024, default=0, metavar="N",
+                    help="--replay_eval for TD3 runs: every epoch, evaluate the TD3 objectives on min(N, buffer size) rows of "
+                         "the replay buffer in place (a HIP kernel copies the rows from the replay storage into the "
+                         "evaluation's staging: no gather to the host), at the point where --td3_validation is taken, and "
+                         "log them as replay/<key>; the bare flag: 1024 rows; TD3 only (SAC runs take --replay_eval); "
+                         "--eval_general and --eval_stats apply to it too; 0 (the default): progress.csv is unchanged")
     return ap
 
 
@@ -141,6 +150,8 @@ if __name__ == "__main__":
         option_kw["param_diagnostics"] = True
     if args.td3_validation:
         option_kw["td3_validation"] = True
+    if args.td3_replay_eval:
+        option_kw["td3_replay_eval"] = args.td3_replay_eval
     if (args.hidden_sweep or args.hidden_sizes) and not args.variants:
         raise SystemExit("--hidden_sweep / --hidden_sizes need --variants")
     if args.variants or args.seeds:
