@@ -69,7 +69,8 @@ def layers_from_flat(flat, shapes):
 
 def make_pair_from_flat(flats, O, A, B, device=0, with_f64=False, **kw):
     """Oracle + HIP trainer from flat parameter vectors {policy, qf1, qf2[, target_qf1, target_qf2]} (with_f64: and the
-    oracle's float64 twin, third)."""
+    oracle's float64 twin, third).  Without targets in `flats` the target nets ALIAS the critics; tests/trained_states.py
+    is the variant with distinct (lagged) ones."""
     from collections import OrderedDict
     from robosuite_benchmark_amd import FlattenMlp, SACTrainer, TanhGaussianPolicy
     kw.setdefault("policy_lr", 1e-3)
