@@ -685,6 +685,39 @@ int sac_param_tensors(const sac_trainer_t *t, int net, int64_t *sizes /* may be 
 int sac_param_moments(sac_trainer_t *t, sac_params_io_t *io);
 int sac_param_moments_many(sac_trainer_t *const *trainers, int n_trainers, sac_params_io_t *io);   /* up to SAC_GROUP_MAX */
 
+/* RECYCLING hidden units on the device (ReDo, Sokar et al. 2023: the remedy that goes with the dormant / dead fractions of
+ * sac_unit_moments): k_unit_recycle, csrc/sac_recycle.h.  For a listed unit u of hidden layer l (0-based) of a TRAINED net
+ * (policy, qf1, qf2; on TD3 handles the online policy), in terms of the flat nn.Linear tensors of sac_get_params:
+ *   incoming   fc<l>.weight[u, :] becomes the caller's fresh row and fc<l>.bias[u] the fresh bias
+ *   outgoing   column u of the tensor(s) that read layer l becomes +0.0: fc<l+1>.weight[:, u]; for the last hidden layer
+ *              last_fc.weight[:, u] and, on a SAC policy, last_fc_log_std.weight[:, u] too
+ *   moments    with SAC_RECYCLE_OPT, Adam's m and v of every element written above become +0.0; step counts and bias
+ *              corrections are untouched
+ *   crossing   where an element is both incoming and outgoing -- (v, u) of fc<l+1>.weight with v listed in layer l + 1
+ *              and u listed in layer l -- zero wins
+ * Nothing else changes: target nets are left alone (the paper resets the online net; the Polyak average carries the
+ * change over, and sac_param_moments' gap jumps for a while), pads stay +0.0, scalars, counters, generators and buffers
+ * stay bit for bit.  Both weight copies of the fused kernels' shapes and the moments where they live are written through
+ * the parameter map (csrc/sac_param_map.h, sac_recycle_map.h): what sac_get_params / sac_get_opt_state return afterwards
+ * is infer.recycle_reference of what they returned before, byte for byte.
+ * Both families and both algorithms are served, mixed in one call: two k_unit_recycle launches (incoming, then outgoing)
+ * on the first member's stream, one wait before return.  Admission is sac_param_moments_many's (1..16 trainers of one
+ * device, none confined by sac_trainer_set_xcd[_mask], none twice); every member is settled first (unverified fused steps,
+ * as by the setters) and its acting mirror invalidated.  A call in which every list is empty returns 0 and launches
+ * nothing.  Refused (<0, sac_last_error, nothing written): a mask that selects no net, bits 3..5 (target nets are not
+ * recycled) or an unknown bit, unknown flags, null counts, null units or fresh with units listed, a unit outside the
+ * layer's true width (the pads of a narrow fused layer are not units), a list that is not strictly ascending. */
+enum { SAC_RECYCLE_OPT = 1 };
+typedef struct sac_recycle_io {
+    uint32_t nets;          /* bit k selects SAC_NET_* == k; only 0..2 */
+    uint32_t flags;         /* SAC_RECYCLE_OPT */
+    const int32_t *counts;  /* per selected net ascending, per hidden layer: units listed (0 allowed) */
+    const int32_t *units;   /* the lists, concatenated in that order; strictly ascending, each in [0, true width N_l) */
+    const float *fresh;     /* per listed unit in that order: K_l incoming weights (flat row order), then its bias */
+} sac_recycle_io_t;
+int sac_recycle_units(sac_trainer_t *t, const sac_recycle_io_t *io);
+int sac_recycle_units_many(sac_trainer_t *const *trainers, int n_trainers, const sac_recycle_io_t *io);   /* up to SAC_GROUP_MAX */
+
 /* ------------------------------------------------------------------------------------------
  * Trainer groups: several runs of one configuration (the reference's seed sweeps, /root/reference/launch_jobs.sh)
  * stepped together.  A group holds 1..SAC_GROUP_MAX existing SAC trainers that share obs_dim, act_dim, batch (at most

@@ -142,6 +142,16 @@ class SacParamsIO(C.Structure):
     _fields_ = [("nets", C.c_uint32), ("flags", C.c_uint32), ("moments", C.c_void_p)]
 
 
+RECYCLE_OPT = 1                                                        # sac_recycle_io_t.flags
+RECYCLE_NETS = ("policy", "qf1", "qf2")                                # the nets sac_recycle_units writes: the trained ones
+
+
+class SacRecycleIO(C.Structure):
+    """sac_recycle_io_t"""
+    _fields_ = [("nets", C.c_uint32), ("flags", C.c_uint32), ("counts", C.c_void_p), ("units", C.c_void_p),
+                ("fresh", C.c_void_p)]
+
+
 TD3_DIAG_NAMES = DIAG_NAMES[:16] + [f"Bellman Errors {i} {s}" for i in (1, 2) for s in ("Mean", "Std", "Max", "Min")] + [
     f"Policy Action {s}" for s in ("Mean", "Std", "Max", "Min")]
 
@@ -236,6 +246,8 @@ SYMBOLS = {
     "sac_param_tensors": (C.c_int, [_P, C.c_int, _P]),
     "sac_param_moments": (C.c_int, [_P, _P]),
     "sac_param_moments_many": (C.c_int, [_P, C.c_int, _P]),
+    "sac_recycle_units": (C.c_int, [_P, _P]),
+    "sac_recycle_units_many": (C.c_int, [_P, C.c_int, _P]),
     "sac_group_create": (C.c_int, [C.POINTER(_P), _P, C.c_int]),
     "td3_group_create": (C.c_int, [C.POINTER(_P), _P, C.c_int]),
     "sac_group_create_mixed": (C.c_int, [C.POINTER(_P), _P, C.c_int]),

@@ -25,10 +25,10 @@ from .networks import (FlattenMlp, GaussianStrategy, MakeDeterministic, PolicyWr
 from .replay_buffer import EnvReplayBuffer
 from .group import (ArchSACTrainerGroup, ArchTD3TrainerGroup, GroupActor, MixedSACTrainerGroup, MixedTD3TrainerGroup,
                     MlpSACTrainerGroup, MlpTD3TrainerGroup, SACTrainerGroup, TD3TrainerGroup, act_many,
-                    evaluate_many, evaluate_replay_many, q_values_many, runs_general_step, param_moments_many, param_statistics,
-                    td3_evaluate_many, td3_evaluate_replay_many,
+                    evaluate_many, evaluate_replay_many, q_values_many, recycle_units_many, runs_general_step,
+                    param_moments_many, param_statistics, td3_evaluate_many, td3_evaluate_replay_many,
                     unit_moments_many, unit_statistics)
-from .infer import check_general, check_stats, param_target
+from .infer import UNIT_NET_TITLES, check_general, check_stats, dormant_units, param_target
 from .infer import td3_eval_statistics
 from .sac import SACTrainer, eval_statistics
 from .td3 import TD3Trainer
@@ -415,6 +415,17 @@ def check_replay_eval(replay_eval, name="replay_eval"):
     return int(replay_eval)
 
 
+def check_recycle_period(recycle_period):
+    if isinstance(recycle_period, bool) or not isinstance(recycle_period, (int, np.integer)) or recycle_period < 0:
+        raise RuntimeError(f"recycle_period is a number of epochs (0: off), got {recycle_period!r}")
+    return int(recycle_period)
+
+
+def _recycle_rng(seed, epoch):
+    """The generator of an epoch's fresh rows: a function of (seed, epoch), so there is nothing to checkpoint."""
+    return np.random.RandomState([seed, epoch, 0x524344])
+
+
 def _replay_rows(replay_eval, buf):
     """The replay rows of an epoch's evaluation: min(replay_eval, buffer size)."""
     return min(int(replay_eval), int(buf.num_steps_can_sample()))
@@ -521,7 +532,13 @@ class EvalOptions(NamedTuple):
     gains replay/<key> for every key of td3_eval_statistics and replay/Num Transitions where the SAC replay block sits;
     the group entries make ONE td3_evaluate_replay_many call per epoch, and only when some run has rows.  eval_general
     and eval_stats apply to it as to td3_validation.  Every run must be a TD3 variant: a SAC variant is refused
-    (replay_eval=N is its option)."""
+    (replay_eval=N is its option).
+
+    recycle_period=E > 0 (no evaluation: the one option here that CHANGES the run): on the epochs with epoch > 0 and
+    epoch % E == 0 the recycle_tau-dormant hidden units of policy, qf1 and qf2 are recycled (ReDo;
+    SACTrainer.recycle_dormant: fresh incoming weights, zero outgoing weights, Adam's moments of both reset, on the
+    device) directly in front of the training block -- _epoch_recycle.  The row gains a last block recycle/Policy Units /
+    QF1 Units / QF2 Units.  Target nets are left alone, so params/* Target Gap jumps on such an epoch.  SAC and TD3."""
     q_diagnostics: bool = False
     q_general: str = "host"
     validation: bool = False
@@ -532,6 +549,8 @@ class EvalOptions(NamedTuple):
     unit_general: str = "host"
     param_diagnostics: bool = False
     td3_replay_eval: int = 0
+    recycle_period: int = 0
+    recycle_tau: float = 0.025
     td3_validation: bool = False
 
 
@@ -542,7 +561,7 @@ def _refuse_td3(variant, what, call, reason):
 
 def _options(what, specs, acting, q_diagnostics, q_general, validation, eval_general, eval_stats, replay_eval,
              unit_diagnostics=False, unit_general="host", param_diagnostics=False, td3_replay_eval=0,
-             td3_validation=False):
+             recycle_period=0, recycle_tau=0.025, td3_validation=False):
     """The EvalOptions of entry `what`, after the value checks of its keywords (acting's too) and, for the variant at
     the head of every run spec in `specs`, the TD3 refusals: all of it in front of anything that builds a run."""
     check_stats(eval_stats)
@@ -552,7 +571,10 @@ def _options(what, specs, acting, q_diagnostics, q_general, validation, eval_gen
     check_general(unit_general)
     opts = EvalOptions(q_diagnostics, q_general, validation, eval_general, eval_stats, check_replay_eval(replay_eval),
                        bool(unit_diagnostics), unit_general, bool(param_diagnostics),
-                       check_replay_eval(td3_replay_eval, "td3_replay_eval"), bool(td3_validation))
+                       check_replay_eval(td3_replay_eval, "td3_replay_eval"), check_recycle_period(recycle_period),
+                       float(recycle_tau), bool(td3_validation))
+    if not opts.recycle_tau >= 0.0:
+        raise RuntimeError(f"recycle_tau is a threshold >= 0, got {recycle_tau!r}")
     for spec in specs if opts.validation else ():
         _refuse_td3(tuple(spec)[0], what, "validation=True", "validation evaluates the SAC objective (SACTrainer.evaluate)")
     for spec in specs if opts.replay_eval else ():
@@ -656,9 +678,39 @@ def _epoch_evaluations(runs, epoch, opts, take=ALL_BLOCKS, many=True):
     return cols, time.time() - s0
 
 
+ROW_BLOCKS = ALL_BLOCKS + ("recycle",)                        # ... and the recycle/ block, the row's last in front of time/*
+
+
+def _epoch_recycle(runs, blocks, epoch, opts, many=True):
+    """recycle_period=E > 0: on the epochs with epoch > 0 and epoch % E == 0 the recycle_tau-dormant units of policy, qf1
+    and qf2 of every run are recycled (SACTrainer.recycle_dormant) -- directly in front of the training block, behind
+    every evaluation block and both collections, so the row's blocks and paths show the state before.  The records come
+    from the steps of the epoch's evaluation paths (_path_steps) under unit_general, the fresh rows from
+    RandomState([seed, epoch, 0x524344]): nothing to checkpoint.  many: ONE unit_moments_many and ONE recycle_units_many
+    call over all runs.  Every row gains blocks["recycle"]: recycle/Policy Units, QF1 Units, QF2 Units -- the counts, 0
+    on the other epochs.  With the option at 0 nothing is called and nothing is added."""
+    if not opts.recycle_period:
+        return
+    counts = [None] * len(runs)
+    if epoch > 0 and epoch % opts.recycle_period == 0:
+        trainers = [r["trainer"] for r in runs]
+        steps = [_path_steps(r["evalc"].epoch_paths, t.obs_dim, t.act_dim) for r, t in zip(runs, trainers)]
+        rngs = [_recycle_rng(r["seed"], epoch) for r in runs]
+        kw = _q_general_kw(opts.unit_general)
+        if many:
+            moments = unit_moments_many(trainers, [s[0] for s in steps], [s[1] for s in steps], [UNIT_NETS] * len(runs), **kw)
+            units = [None if m is None else dormant_units(m, opts.recycle_tau) for m in moments]
+            counts = recycle_units_many(trainers, units, rngs=rngs)
+        else:
+            counts = [t.recycle_dormant(*s, nets=UNIT_NETS, tau=opts.recycle_tau, rng=g, **kw) if s[0].shape[0] else None
+                      for t, s, g in zip(trainers, steps, rngs)]
+    for b, c in zip(blocks, counts):
+        b["recycle"] = OrderedDict((f"recycle/{UNIT_NET_TITLES[n]} Units", 0 if c is None else int(c[n])) for n in UNIT_NETS)
+
+
 def _end_epoch_row(r, blocks, epoch):
     """Run r's progress.csv columns of `epoch` in the reference's order up to the time/* block, the blocks of
-    _epoch_evaluations behind them in ALL_BLOCKS' order; then the run's parts end their epoch."""
+    _epoch_evaluations and _epoch_recycle behind them in ROW_BLOCKS' order; then the run's parts end their epoch."""
     buf, trainer, expl, evalc = r["buf"], r["trainer"], r["expl"], r["evalc"]
     row = OrderedDict()
     row.update(("replay_buffer/" + k, v) for k, v in buf.get_diagnostics().items())
@@ -667,7 +719,7 @@ def _end_epoch_row(r, blocks, epoch):
     row.update(path_information(expl.epoch_paths, "exploration/"))
     row.update(("evaluation/" + k, v) for k, v in evalc.get_diagnostics().items())
     row.update(path_information(evalc.epoch_paths, "evaluation/", r["ak"]["expl_max_path_length"]))
-    for name in ALL_BLOCKS:
+    for name in ROW_BLOCKS:
         row.update(blocks.get(name, ()))
     for x in (trainer, buf, expl, evalc):
         x.end_epoch(epoch)
@@ -773,7 +825,8 @@ def _prefill(r):
 def experiment(variant, log_dir=None, seed=1, obs_dim=None, action_dim=None, num_epochs=None, device=0,
                fused_loop=True, quiet=False, checkpoint_dir=None, resume=False, acting="host", q_diagnostics=False,
                q_general="host", validation=False, eval_general="host", eval_stats="host", replay_eval=0,
-               unit_diagnostics=False, unit_general="host", param_diagnostics=False, td3_replay_eval=0, td3_validation=False):
+               unit_diagnostics=False, unit_general="host", param_diagnostics=False, td3_replay_eval=0,
+               recycle_period=0, recycle_tau=0.025, td3_validation=False):
     """variant.json -> training run.  Returns the list of progress rows (also written to
     <log_dir>/progress.csv when log_dir is given).
 
@@ -794,7 +847,7 @@ def experiment(variant, log_dir=None, seed=1, obs_dim=None, action_dim=None, num
     per-epoch evaluations, EvalOptions; here from the trainer's own q_values, evaluate, evaluate_replay and unit_moments."""
     opts = _options("experiment", [(variant,)], acting, q_diagnostics, q_general, validation, eval_general, eval_stats,
                     replay_eval, unit_diagnostics, unit_general, param_diagnostics, td3_replay_eval,
-                    td3_validation)
+                    recycle_period, recycle_tau, td3_validation)
     validate(variant)
     # This driver's runs are a function of `seed` alone: initial weights come from np.random (seeded here), every noise
     # stream from `seed` -- whether or not torch happens to be loaded in the process (the reference's own scripts seed
@@ -821,6 +874,8 @@ def experiment(variant, log_dir=None, seed=1, obs_dim=None, action_dim=None, num
         t2 = time.time()
         buf.add_paths(new_paths)
         t3 = time.time()
+        _epoch_recycle([r], blocks, epoch, opts, many=False)
+        recycle_s = time.time() - t3                              # (counted as evaluation: it reads the evaluation paths)
         if fused_loop:
             trainer.train_loop(buf, n_train, batch_size=ak["batch_size"])
         else:
@@ -832,8 +887,8 @@ def experiment(variant, log_dir=None, seed=1, obs_dim=None, action_dim=None, num
         if checkpoint_dir:
             save_checkpoint(checkpoint_dir, trainer, buf, dict(_pack_extra(r, epoch), np_random=_rs_pack(np.random)))
         t6 = time.time()
-        _stamp_times(row, epoch, storing=t3 - t2, evaluation=t1 - t0, exploration=t2 - t1, logging=t5 - t4,
-                     saving=t6 - t5, training=t4 - t3, epoch_s=t6 - t0, total=t6 - t_start)
+        _stamp_times(row, epoch, storing=t3 - t2, evaluation=t1 - t0 + recycle_s, exploration=t2 - t1, logging=t5 - t4,
+                     saving=t6 - t5, training=t4 - t3 - recycle_s, epoch_s=t6 - t0, total=t6 - t_start)
         _log_row(r, row, log_dir, first_epoch)
         if not quiet:
             print(f"epoch {epoch}: buffer {row['replay_buffer/size']}  QF1 {row['trainer/QF1 Loss']:.4f}  "
@@ -929,6 +984,10 @@ def _group_epochs(*, runs, train_block, n_epochs, n_train, log_dir, quiet, what,
                 for b, more in zip(blocks, behind):
                     b.update(more)
                 times = [(a0, eval_s + b_s, expl_s, store_s) for a0, eval_s, expl_s, store_s in times]
+            t2r = time.time()
+            _epoch_recycle(runs, blocks, epoch, opts)         # (in front of the training block: ONE call pair for all runs)
+            if opts.recycle_period:
+                times = [(a0, eval_s + time.time() - t2r, expl_s, store_s) for a0, eval_s, expl_s, store_s in times]
             t3 = time.time()
             train_block()
             t4 = time.time()
@@ -960,7 +1019,7 @@ def experiment_group(variant, seeds, log_dir=None, num_epochs=None, obs_dim=None
                      quiet=False, checkpoint_dir=None, resume=False, chunk_rows=DEFAULT_CHUNK_ROWS, acting="host", sessions=True,
                      general_sessions=None, q_diagnostics=False, q_general="host", validation=False,
                      eval_general="host", eval_stats="host", replay_eval=0, unit_diagnostics=False, unit_general="host",
-                     param_diagnostics=False, td3_replay_eval=0, td3_validation=False):
+                     param_diagnostics=False, td3_replay_eval=0, recycle_period=0, recycle_tau=0.025, td3_validation=False):
     """One configuration, several seeds, one process: each seed is the run ``experiment(variant, seed=s)`` would make --
     its own synthetic environments, collectors, weights and replay buffer -- and every epoch's training block is ONE
     SACTrainerGroup.train_loop (TD3 variants: TD3TrainerGroup; hidden sizes other than two layers of at most 256 units:
@@ -986,7 +1045,7 @@ def experiment_group(variant, seeds, log_dir=None, num_epochs=None, obs_dim=None
     per-epoch evaluations, EvalOptions; each seed's rows are those of experiment(variant, seed=s) with the same options."""
     opts = _options("experiment_group", [(variant,)], acting, q_diagnostics, q_general, validation, eval_general,
                     eval_stats, replay_eval, unit_diagnostics, unit_general, param_diagnostics, td3_replay_eval,
-                    td3_validation)
+                    recycle_period, recycle_tau, td3_validation)
     if resume and not checkpoint_dir:
         raise RuntimeError("experiment_group(resume=True) needs the checkpoint_dir to resume from")
     validate(variant)
@@ -1041,7 +1100,7 @@ def experiment_sweep(runs, log_dir=None, num_epochs=None, device=0, quiet=False,
                      chunk_rows=DEFAULT_CHUNK_ROWS, hidden_sweep=False, acting="host", sessions=True, general_sessions=None,
                      q_diagnostics=False, q_general="host", validation=False,
                      eval_general="host", eval_stats="host", replay_eval=0, unit_diagnostics=False, unit_general="host",
-                     param_diagnostics=False, td3_replay_eval=0, td3_validation=False):
+                     param_diagnostics=False, td3_replay_eval=0, recycle_period=0, recycle_tau=0.025, td3_validation=False):
     """Several tasks x seeds, one process, one device: every entry of ``runs`` -- (variant, seed), or (variant, seed,
     obs_dim, action_dim) for a task without pinned dims -- is the run ``experiment(variant, seed=seed)`` would make, and
     every epoch's training block is ONE MixedSACTrainerGroup.train_loop (TD3 variants: MixedTD3TrainerGroup; hidden sizes
@@ -1066,7 +1125,7 @@ def experiment_sweep(runs, log_dir=None, num_epochs=None, device=0, quiet=False,
     the device's under q_general / eval_general "device".  A sweep with a TD3 run refuses validation and replay_eval."""
     opts = _options("experiment_sweep", runs, acting, q_diagnostics, q_general, validation, eval_general, eval_stats,
                     replay_eval, unit_diagnostics, unit_general, param_diagnostics, td3_replay_eval,
-                    td3_validation)
+                    recycle_period, recycle_tau, td3_validation)
     if resume and not checkpoint_dir:
         raise RuntimeError("experiment_sweep(resume=True) needs the checkpoint_dir to resume from")
     specs = []

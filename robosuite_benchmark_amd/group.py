@@ -20,7 +20,8 @@ from . import _lib
 # (the inference names live in infer.py; they stay importable from here)
 from .infer import (GENERAL, GENERAL_SESSIONS, MAX_MEMBERS, GroupActor, act_many, check_general,  # noqa: F401
                     evaluate_many, evaluate_replay_many, general_shape, merge_unit_moments, param_moments_many,
-                    param_moments_reference, param_statistics, q_values_many, runs_general_step, td3_eval_moments, td3_evaluate_many,
+                    param_moments_reference, param_statistics, q_values_many, recycle_units_many, runs_general_step,
+                    td3_eval_moments, td3_evaluate_many,
                     td3_evaluate_replay_many, td3_moments_statistics, unit_moments_many, unit_moments_reference, unit_statistics)
 from .sac import SACTrainer
 from .td3 import TD3Trainer
@@ -80,6 +81,11 @@ class _Members:
         """param_moments_many over the group's members (nets_list None: every net of every member; opt, gap and route as
         there): one sac_param_moments_many call per 16 members."""
         return param_moments_many(self.trainers, nets_list, opt=opt, gap=gap, route=route)
+
+    def recycle_units_many(self, units_list, fresh_list=None, rngs=None, opt=True, route="device"):
+        """recycle_units_many over the group's members (units_list[i] None: member i sits out; fresh_list, rngs, opt and
+        route as there): one sac_recycle_units_many call per 16 members."""
+        return recycle_units_many(self.trainers, units_list, fresh_list=fresh_list, rngs=rngs, opt=opt, route=route)
 
     def evaluate_many(self, batches, eps=None, rngs=None, rows=False, general="host", stats="host"):
         """evaluate_many over the group's members (general and stats as there)."""

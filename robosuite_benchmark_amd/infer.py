@@ -576,6 +576,218 @@ def param_moments_many(trainers, nets_list=None, opt=True, gap=True, route="devi
     return param_moments_of(trainers, names, bool(opt), bool(gap), route)
 
 
+# ---- recycling dormant hidden units (ReDo, Sokar et al. 2023) ------------------------------------------------------------
+RECYCLE_ROUTES = ("device", "host")
+B_INIT_VALUE = 0.1                          # networks._Mlp.__init__'s constant hidden bias
+
+
+def dormant_units(moments, tau=0.025):
+    """The tau-dormant units of a unit_moments result (OrderedDict net -> [record per hidden layer]): an OrderedDict
+    net -> [int32 array per hidden layer], ascending -- exactly unit_statistics' predicate, sum[u] <= tau * mean(sum) of
+    the layer, with its NaN behaviour (a NaN unit is not listed and, through the mean, nothing of its layer is; an
+    all-zero layer is listed whole).  The listed count over the unit count is unit_statistics' Dormant Fraction."""
+    out = OrderedDict()
+    with np.errstate(all="ignore"):
+        for net, records in moments.items():
+            out[net] = [np.flatnonzero(r["sum"] <= tau * np.mean(r["sum"])).astype(np.int32) for r in records]
+    return out
+
+
+def _recycle_layers(t, net):
+    """[(N_l, K_l, first element of fc<l>.weight, of fc<l>.bias)] per hidden layer of `net` in the flat vector, then
+    [(rows, first element)] of every weight that reads the LAST hidden layer (last_fc, and a SAC policy's
+    last_fc_log_std), and the vector's size."""
+    hidden, heads, off = [], [], 0
+    nh = len(t._hidden(net))
+    for j, (_, (w, b)) in enumerate(getattr(t, net).layers.items()):
+        n, k = w.shape
+        if j < nh:
+            hidden.append((n, k, off, off + n * k))
+        else:
+            heads.append((n, off))
+        off += n * k + b.size
+    return hidden, heads, off
+
+
+def check_recycle_units(t, units, caller="recycle_units"):
+    """recycle_units' unit selection, checked before any library call: a mapping net -> [unit list per hidden layer] over
+    trained nets of trainer t (policy, qf1, qf2), each once, one list per hidden layer, every list strictly ascending
+    and inside the layer's true width.  Returns it as an OrderedDict net -> [int32 array per hidden layer]."""
+    if not hasattr(units, "items"):
+        raise ValueError(f"{caller}: units is a mapping net -> [unit list per hidden layer], got {type(units).__name__}")
+    out = OrderedDict()
+    for net, lists in units.items():
+        if net not in _lib.RECYCLE_NETS or net not in t.NETS:
+            raise ValueError(f"{caller}: {net!r} is not recycled: one of {_lib.RECYCLE_NETS} (target nets are left alone: "
+                             "the Polyak average carries the change over)")
+        widths = t._hidden(net)
+        lists = list(lists)
+        if len(lists) != len(widths):
+            raise ValueError(f"{caller}: {net} has {len(widths)} hidden layers, got {len(lists)} unit lists")
+        out[net] = []
+        for l, (us, N) in enumerate(zip(lists, widths)):
+            raw = np.asarray(us if us is not None else [])
+            if raw.ndim != 1 or (raw.size and not np.issubdtype(raw.dtype, np.integer)):
+                raise ValueError(f"{caller}: {net}, hidden layer {l}: a unit list is a 1-d array of integers")
+            a = raw.astype(np.int64)
+            if a.size and (a.min() < 0 or a.max() >= N):
+                raise ValueError(f"{caller}: {net}, hidden layer {l}: units {a.min()}..{a.max()} outside the layer's "
+                                 f"width 0..{N - 1}")
+            if a.size > 1 and not (np.diff(a) > 0).all():
+                raise ValueError(f"{caller}: {net}, hidden layer {l}: the unit list is not strictly ascending")
+            out[net].append(np.ascontiguousarray(a, np.int32))
+    if not out:
+        raise ValueError(f"{caller} needs at least one network")
+    return out
+
+
+def fresh_unit_rows(trainer, units, rng, b_init_value=B_INIT_VALUE):
+    """Fresh incoming rows for the listed units, as networks._Mlp.__init__ draws a hidden layer: per (net, layer) WITH
+    units -- nets in the order given, layers ascending -- ONE rng.uniform(-1/sqrt(N_l), 1/sqrt(N_l), (n, K_l)) as
+    float32, and the constant bias b_init_value.  An OrderedDict net -> [float32 array (n, K_l + 1) per hidden layer]:
+    a unit's K_l weights in flat row order, then its bias (sac_recycle_io_t.fresh).  A layer without units draws nothing."""
+    units = check_recycle_units(trainer, units, "fresh_unit_rows")
+    out = OrderedDict()
+    for net, lists in units.items():
+        hidden, _, _ = _recycle_layers(trainer, net)
+        out[net] = []
+        for us, (N, K, _, _) in zip(lists, hidden):
+            rows = np.empty((us.size, K + 1), np.float32)
+            if us.size:
+                bound = 1.0 / np.sqrt(N)
+                rows[:, :K] = rng.uniform(-bound, bound, (us.size, K)).astype(np.float32)
+                rows[:, K] = np.float32(b_init_value)
+            out[net].append(rows)
+    return out
+
+
+def check_recycle_fresh(t, units, fresh, caller="recycle_units"):
+    """The fresh rows that go with checked `units`: net -> [float32 (n, K_l + 1) per hidden layer], shapes checked."""
+    out = OrderedDict()
+    for net, lists in units.items():
+        hidden, _, _ = _recycle_layers(t, net)
+        if net not in fresh or len(fresh[net]) != len(lists):
+            raise ValueError(f"{caller}: fresh holds no rows for {net}, or not one array per hidden layer")
+        out[net] = []
+        for l, (us, (N, K, _, _)) in enumerate(zip(lists, hidden)):
+            rows = _lib.f32(np.empty((0, K + 1)) if fresh[net][l] is None else fresh[net][l])
+            if rows.size != us.size * (K + 1):
+                raise ValueError(f"{caller}: {net}, hidden layer {l}: fresh rows must be ({us.size}, {K + 1}): K_l weights, "
+                                 "then the bias, per listed unit")
+            out[net].append(rows.reshape(us.size, K + 1))
+    return out
+
+
+def recycle_reference(state, trainer, units, fresh, opt=True):
+    """sac_recycle_units restated on the flat vectors of SACTrainer._export_state(): a new state (the given one is left
+    alone) in which, for a listed unit u of hidden layer l of a trained net,
+      incoming   fc<l>.weight[u, :] and fc<l>.bias[u] are the fresh row (K_l weights, then the bias),
+      outgoing   column u of fc<l+1>.weight -- for the last hidden layer of last_fc.weight and, on a SAC policy, of
+                 last_fc_log_std.weight -- is +0.0,
+      moments    with opt, Adam's m and v of every element written are +0.0,
+    all incoming rows first, then all outgoing columns: at a crossing zero wins.  Everything else -- target nets, scalars,
+    counters -- is the same bytes."""
+    units = check_recycle_units(trainer, units, "recycle_reference")
+    fresh = check_recycle_fresh(trainer, units, fresh, "recycle_reference")
+    new = dict(params={k: np.array(v, np.float32) for k, v in state["params"].items()},
+               opt={k: (np.array(m, np.float32), np.array(v, np.float32)) for k, (m, v) in state["opt"].items()},
+               scalars=np.array(state["scalars"], np.float64))
+    for net, lists in units.items():
+        hidden, heads, size = _recycle_layers(trainer, net)
+        x = new["params"][net]
+        if x.size != size:
+            raise ValueError(f"recycle_reference: {net} holds {x.size} parameters, the trainer's has {size}")
+        written = np.zeros(size, bool)
+        for us, rows, (N, K, off_w, off_b) in zip(lists, fresh[net], hidden):
+            for u, row in zip(us, rows):
+                x[off_w + u * K:off_w + (u + 1) * K] = row[:K]
+                x[off_b + u] = row[K]
+                written[off_w + u * K:off_w + (u + 1) * K] = True
+                written[off_b + u] = True
+        for l, us in enumerate(lists):
+            N = hidden[l][0]
+            readers = [(hidden[l + 1][0], hidden[l + 1][2])] if l + 1 < len(hidden) else heads
+            for rows_out, off in readers:
+                for u in us:
+                    idx = off + np.arange(rows_out) * N + u
+                    x[idx] = np.float32(0.0)
+                    written[idx] = True
+        if opt:
+            m, v = new["opt"][net]
+            m[written] = np.float32(0.0)
+            v[written] = np.float32(0.0)
+    return new
+
+
+def _recycle_counts(units):
+    return OrderedDict((net, int(sum(us.size for us in lists))) for net, lists in units.items())
+
+
+def recycle_units_of(trainers, units, fresh, opt, route_):
+    """recycle_units / recycle_units_many behind their argument checks: units[i] / fresh[i] as check_recycle_units /
+    check_recycle_fresh left them (units None: the member sits out and gets None).  The members without a handle, and all
+    of them under route "host", take their own host route (export, recycle_reference, import); the others ONE
+    sac_recycle_units_many call per 16 of them, both families and both algorithms mixed.  Returns the per-net counts."""
+    R = len(trainers)
+    out, served = [None] * R, []
+    for i, t in enumerate(trainers):
+        if units[i] is None:
+            continue
+        out[i] = _recycle_counts(units[i])
+        if t._h is None or route_ == "host":
+            t._recycle_host(units[i], fresh[i], opt)
+        else:
+            served.append(i)
+    if not served:
+        return out
+    lib = _lib.load()
+    for c in range(0, len(served), MAX_MEMBERS):
+        ids = served[c:c + MAX_MEMBERS]
+        keep, ios = [], []
+        for i in ids:
+            order = sorted(units[i], key=_lib.UNIT_NET_BITS.get)
+            counts = np.array([us.size for net in order for us in units[i][net]], np.int32)
+            us = np.concatenate([us for net in order for us in units[i][net]] + [np.empty(0, np.int32)]).astype(np.int32)
+            rows = np.concatenate([r.ravel() for net in order for r in fresh[i][net]] + [np.empty(0, np.float32)])
+            rows = _lib.f32(rows)
+            keep.append((counts, us, rows))
+            ios.append(_lib.SacRecycleIO(sum(_lib.UNIT_NET_BITS[net] for net in order), _lib.RECYCLE_OPT if opt else 0,
+                                         counts.ctypes.data, us.ctypes.data if us.size else None,
+                                         rows.ctypes.data if rows.size else None))
+        arr = (_lib.SacRecycleIO * len(ids))(*ios)
+        _lib.check(lib.sac_recycle_units_many(_handles(trainers, ids), len(ids), arr), "sac_recycle_units_many")
+        for i in ids:
+            trainers[i]._settled()
+            if out[i].get("policy"):
+                trainers[i]._host_policy_stale = True        # (as _set_params: the holder's arrays are refreshed at their next use)
+    return out
+
+
+def recycle_units_many(trainers, units_list, fresh_list=None, rngs=None, opt=True, route="device"):
+    """SACTrainer.recycle_units for many runs at once: trainers[i]'s units units_list[i] (net -> [unit list per hidden
+    layer]; None: the member sits out and gets None) take the rows fresh_list[i], or where those are None rows drawn by
+    fresh_unit_rows from rngs[i].  The members with a handle are served by ONE sac_recycle_units_many call per 16 of them
+    (two k_unit_recycle launches: SAC and TD3, the fused kernels' shapes and the general step mixed); the others -- and
+    all of them under route="host" -- by their own host route.  A member's state never depends on its neighbours: it is
+    byte for byte that of its own recycle_units.  Returns per member the per-net counts."""
+    if route not in RECYCLE_ROUTES:
+        raise RuntimeError(f"route must be one of {RECYCLE_ROUTES}, got {route!r}")
+    trainers = list(trainers)
+    R = len(trainers)
+    fresh_list = [None] * R if fresh_list is None else list(fresh_list)
+    rngs = [None] * R if rngs is None else list(rngs)
+    if not (len(units_list) == len(fresh_list) == len(rngs) == R):
+        raise RuntimeError("recycle_units_many takes one unit selection, one set of fresh rows and one generator per trainer")
+    if len({id(t) for t in trainers}) != R:
+        raise RuntimeError("a trainer appears twice in recycle_units_many")
+    units, fresh = [None] * R, [None] * R
+    for i, t in enumerate(trainers):
+        if units_list[i] is None:
+            continue
+        units[i], fresh[i] = t._recycle_inputs(units_list[i], fresh_list[i], rngs[i])
+    return recycle_units_of(trainers, units, fresh, bool(opt), route)
+
+
 # ---- evaluation: its statistics -----------------------------------------------------------------------------------------
 def eval_target(rew, term, tq1, tq2, log_pi_next, alpha, reward_scale, discount):
     """k_eval's y in float32 NumPy, operation for operation:

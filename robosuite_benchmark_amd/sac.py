@@ -518,8 +518,61 @@ class SACTrainer:
         names = self._param_names(nets)
         return infer.param_moments_of([self], [names], bool(opt), bool(gap), route)[0]
 
+    # ---- recycling dormant hidden units ---------------------------------------------------------
+    def _recycle_inputs(self, units, fresh, rng):
+        """recycle_units' arguments, checked before any library call: (units, fresh) as infer.check_recycle_units and
+        infer.check_recycle_fresh leave them; fresh None: rows drawn by infer.fresh_unit_rows from rng, which must then be
+        given (np.random is never touched)."""
+        units = infer.check_recycle_units(self, units)
+        if fresh is None:
+            if rng is None:
+                raise ValueError("recycle_units needs fresh rows or a generator to draw them from")
+            fresh = infer.fresh_unit_rows(self, units, rng)
+        return units, infer.check_recycle_fresh(self, units, fresh)
+
+    def _recycle_host(self, units, fresh, opt=True):
+        """The host route of recycle_units: export, infer.recycle_reference, import -- ten full-state transfers.  Without
+        a handle the state is the saved one, if any, and the holders' own arrays."""
+        if self._h is not None:
+            self._import_state(infer.recycle_reference(self._export_state(), self, units, fresh, opt))
+            return
+        st = self._saved_state
+        if st is None:
+            zeros = {k: np.zeros(getattr(self, k).flat().size, np.float32) for k in infer.PARAM_TRAINED}
+            st = dict(params={k: _lib.f32(getattr(self, k).flat()) for k in self.NETS},
+                      opt={k: (z, z.copy()) for k, z in zeros.items()}, scalars=np.zeros(6, np.float64))
+        new = infer.recycle_reference(st, self, units, fresh, opt)
+        if self._saved_state is not None:
+            self._saved_state = new
+        for k in units:
+            getattr(self, k).load_flat(new["params"][k])
+
+    def recycle_units(self, units, fresh=None, rng=None, opt=True, route="device"):
+        """ReDo (Sokar et al. 2023) on the live state: every listed unit of a hidden layer of a trained net gets a fresh
+        incoming row and bias, +0.0 on its outgoing column(s) and, with opt, +0.0 in Adam's m and v of every element
+        written; where a fresh row crosses a zeroed column, zero wins.  units: a mapping net -> [unit list per hidden
+        layer] over "policy", "qf1", "qf2" (strictly ascending lists, e.g. infer.dormant_units of a unit_moments result);
+        fresh: net -> [(n, K_l + 1) float32 per hidden layer], or None: drawn by infer.fresh_unit_rows from rng.  Target
+        nets are left alone -- the Polyak average carries the change over, and params/* Target Gap jumps for a while --
+        as are scalars, counters, generators and buffers.
+        route="device": sac_recycle_units -- two k_unit_recycle launches write the selected rows and columns in place, both
+        weight copies and the moments where they live, no parameter copy; both step families.  route="host", and a trainer
+        without a handle: export, infer.recycle_reference, import -- the same bytes.  Returns the per-net counts."""
+        if route not in infer.RECYCLE_ROUTES:
+            raise RuntimeError(f"route must be one of {infer.RECYCLE_ROUTES}, got {route!r}")
+        units, fresh = self._recycle_inputs(units, fresh, rng)
+        return infer.recycle_units_of([self], [units], [fresh], bool(opt), route)[0]
+
+    def recycle_dormant(self, obs, act=None, nets=("policy", "qf1", "qf2"), tau=0.025, rng=None, general="host", opt=True):
+        """unit_moments on the rows obs / act -> infer.dormant_units(tau) -> recycle_units with rows drawn from rng: the
+        tau-dormant units of `nets` on those rows are recycled.  Returns the per-net counts."""
+        if rng is None:
+            raise ValueError("recycle_dormant needs a generator to draw the fresh rows from")
+        units = infer.dormant_units(self.unit_moments(obs, act, nets=nets, general=general), tau)
+        return self.recycle_units(units, rng=rng, opt=opt)
+
     # ---- evaluation on held-out transitions --------------------------------------------------
-    _evaluate_on_host = False       # private switch: the host path for a fused-shape trainer too (scripts/bench_evaluate.py
+    _evaluate_on_host = False      # private switch: the host path for a fused-shape trainer too (scripts/bench_evaluate.py
                                      # measures the two paths of ONE trainer against each other)
     _eval_rng = None                 # evaluate's private noise stream, made on first use
 

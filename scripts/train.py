@@ -28,7 +28,9 @@
  --td3_validation: --validation for TD3 runs: every epoch, the TD3 losses, TD errors and targets on the evaluation
  paths' transitions from the live weights: validation/ columns in progress.csv; TD3 only.
  --td3_replay_eval [N]: --replay_eval for TD3 runs: every epoch, the TD3 objectives on N (bare: 1024) rows of the replay
- buffer, read in place on the device: replay/ columns in progress.csv; TD3 only.  --eval_stats device applies to both.)
+ buffer, read in place on the device: replay/ columns in progress.csv; TD3 only.  --eval_stats device applies to both.
+ --recycle [E] --recycle_tau T: every E-th epoch the T-dormant hidden units of policy, qf1 and qf2 are recycled on the
+ device in front of the training block (ReDo): recycle/ columns in progress.csv; SAC and TD3.)
 Runs the variant unchanged (batch size, lrs, tau, period, buffer size ... from the JSON) on the
 HIP library with a synthetic environment of the task's dimensions (robosuite is not installed)."""
 import argparse
@@ -129,6 +131,15 @@ def build_parser():
                          "evaluation's staging: no gather to the host), at the point where --td3_validation is taken, and "
                          "log them as replay/<key>; the bare flag: 1024 rows; TD3 only (SAC runs take --replay_eval); "
                          "--eval_general and --eval_stats apply to it too; 0 (the default): progress.csv is unchanged")
+    ap.add_argument("--recycle", type=int, nargs="?", const=1, default=0, metavar="E",
+                    help="every E-th epoch (the bare flag: every epoch; never epoch 0), in front of the training block, "
+                         "recycle the dormant hidden units of policy, qf1 and qf2 found on the evaluation paths (ReDo: "
+                         "fresh incoming weights, zero outgoing weights, Adam's moments of both reset -- HIP kernels on "
+                         "the live state, no parameter copy) and log recycle/<Net> Units; target nets are left alone; "
+                         "SAC and TD3; --unit_general applies to it; 0 (the default): the run and progress.csv are unchanged")
+    ap.add_argument("--recycle_tau", type=float, default=0.025,
+                    help="with --recycle: a unit is dormant when its mean activation is at most this share of its "
+                         "layer's (the Dormant Fraction of --unit_diagnostics at the same value)")
     return ap
 
 
@@ -152,6 +163,8 @@ if __name__ == "__main__":
         option_kw["td3_validation"] = True
     if args.td3_replay_eval:
         option_kw["td3_replay_eval"] = args.td3_replay_eval
+    if args.recycle:
+        option_kw.update(recycle_period=args.recycle, recycle_tau=args.recycle_tau)
     if (args.hidden_sweep or args.hidden_sizes) and not args.variants:
         raise SystemExit("--hidden_sweep / --hidden_sizes need --variants")
     if args.variants or args.seeds:
