@@ -246,13 +246,124 @@ int eval_read_alpha(sac_trainer_t *const *trainers, int n_trainers, const int32_
     return 0;
 }
 
+// ---- the host half of every evaluation entry: one description per objective, one body per family ----
+//
+// An objective's host description (SacEval below, Td3Eval in td3_eval.h) is a struct of static members that names
+//   IO, Stats                    the caller's structs
+//   Member, kernel               the fixed-shape member table and its kernel; NETS of the trainer's nets go into it
+//   Moments, moments_kernel      the statistics' member table and kernel; moments(M, dev) names its columns
+//   draws[DRAWS]                 the N(0,1) inputs, as pointers to IO's fields
+//   arrays[ARRAYS]               the (n, A) outputs, as pointers to IO's fields, with what makes one staged unasked
+//   Call                         what is read once per call in front of the staging (prepare) and handed back per member
+//                                behind the wait (finish): SAC's alpha and log_alpha, nothing for TD3
+//   member(M, t, C, i, dev)      the member's fields beyond EvalCommon
+//   General                      the general step's half (sac_eval_general.h, td3_eval_general.h)
+// A member's staging, for both families: obs act rew term nobs | the draws | rows | the arrays, in the order of `arrays`.
+
+// an (n, A) output of an objective: staged where the caller asked for it, and besides
+template <class IO> struct EvalArray {
+    float *IO::*field;
+    bool critics;        // the general step's critic launches read it there: always staged by the general body
+    bool moments;        // the moments kernel reads it there: staged under stats
+};
+
+enum { EVAL_P_OBS, EVAL_P_ACT, EVAL_P_REW, EVAL_P_TERM, EVAL_P_NOBS, EVAL_P_DRAW };      // the parts every objective starts with
+
+struct SacEval {
+    typedef sac_eval_io_t IO;
+    typedef sac_eval_stats_t Stats;
+    typedef sac::EvalMember Member;
+    typedef sac::MomentsMember Moments;
+    static constexpr auto kernel = sac::k_eval;
+    static constexpr auto moments_kernel = sac::k_eval_moments;
+    static constexpr bool TD3 = false;
+    static constexpr int NETS = 5, DRAWS = 2, ARRAYS = 4, ROWS_N = SAC_EVAL_ROWS_N, MOMENTS_N = SAC_EVAL_MOMENTS_N;
+    enum { P_EPS = EVAL_P_DRAW, P_EPS_NEXT, P_ROWS, P_MU, P_LOG_STD, P_A_NEW, P_A_NEXT, NPART };
+    static constexpr const float *IO::*draws[DRAWS] = {&IO::eps, &IO::eps_next};
+    static constexpr EvalArray<IO> arrays[ARRAYS] = {{&IO::mu, false, true}, {&IO::log_std, false, true},
+                                                     {&IO::a_new, true, false}, {&IO::a_next, true, false}};
+    struct Call {
+        float alpha[SAC_GROUP_MAX], log_alpha[SAC_GROUP_MAX];
+        int prepare(sac_trainer_t *const *trainers, int n_trainers, const int32_t *n_rows, bool stats) {
+            return eval_read_alpha(trainers, n_trainers, n_rows, alpha, stats ? log_alpha : nullptr);
+        }
+        // the alpha the entry evaluated y with, and under stats the log_alpha of the same Ctl copy
+        void finish(int i, IO &E, Stats *st) const {
+            E.alpha = alpha[i];
+            if (st) { st->alpha = (double)alpha[i]; st->log_alpha = (double)log_alpha[i]; }
+        }
+    };
+    template <class Dev> static void member(Member &M, const sac_trainer *, const Call &C, int i, Dev dev) {
+        M.eps = dev(P_EPS); M.eps_next = dev(P_EPS_NEXT);
+        M.mu = dev(P_MU); M.log_std = dev(P_LOG_STD); M.a_new = dev(P_A_NEW); M.a_next = dev(P_A_NEXT);
+        M.alpha = C.alpha[i]; M.pad = 0;
+    }
+    template <class Dev> static void moments(Moments &M, Dev dev) {
+        M.rows = dev(P_ROWS); M.mu = dev(P_MU); M.log_std = dev(P_LOG_STD);
+    }
+    struct General;
+};
+
+template <class Obj> InferEntry eval_entry(const char *fn, bool general, const char *instead) {
+    InferEntry IE = {fn, general, !Obj::TD3, "device evaluation", instead, "evaluate"};
+    IE.td3_only = Obj::TD3;
+    return IE;
+}
+
 // an entry's own refusal for a member with rows: every input array is there, and `rows` unless the entry returns
-// statistics (there a null `rows` means that no column is copied back)
-int eval_admit_io(const sac_eval_io_t &E, int i, bool need_rows) {
-    const bool inputs = E.obs && E.act && E.rew && E.term && E.next_obs && E.eps && E.eps_next;
+// statistics (there a null `rows` means that no column is copied back); with src (the replay entries) the draws, `rows`
+// and the source (eval_rows_admit, sac_eval_rows.h)
+template <class Obj>
+int eval_admit_io(const typename Obj::IO &E, const sac_eval_src_t *src, const sac_trainer *t, int i, int n, bool need_rows) {
+    if (src) return eval_rows_admit(E, src[i], t, i, n, need_rows);
+    bool inputs = E.obs && E.act && E.rew && E.term && E.next_obs;
+    for (auto draw : Obj::draws) inputs = inputs && E.*draw;
     if (need_rows) SAC_REQUIRE(inputs && E.rows, "trainer %d: a null input array or null rows", i);
     SAC_REQUIRE(inputs, "trainer %d: a null input array", i);
     return 0;
+}
+
+// member i's parts into the call's staging: an array has its place where the caller asked for it, where the moments
+// kernel reads it (stats) and where the general step's critic launches do (general)
+template <class Obj>
+void eval_carve(InferStage &ST, int i, const sac_trainer *t, int n_rows, const typename Obj::IO &E, bool stats, bool general) {
+    const size_t n = (size_t)n_rows, nO = n * t->O, nA = n * t->A;
+    size_t part[Obj::NPART] = {nO, nA, n, n, nO};
+    for (int d = 0; d < Obj::DRAWS; ++d) part[EVAL_P_DRAW + d] = nA;
+    part[Obj::P_ROWS] = n * Obj::ROWS_N;
+    for (int k = 0; k < Obj::ARRAYS; ++k) {
+        const EvalArray<typename Obj::IO> &a = Obj::arrays[k];
+        part[Obj::P_ROWS + 1 + k] = n && (E.*a.field || (stats && a.moments) || (general && a.critics)) ? nA : 0;
+    }
+    ST.carve(i, part, Obj::NPART);
+}
+
+// the inputs of member i with n rows (entry m of the launch) into its staging: the five arrays of a transition from the
+// caller's, or with src by k_eval_rows from src[i]'s replay storage (its table entry is written here), and the draws.
+// Returns the member's k_eval_rows workgroups.
+template <class Obj>
+int eval_inputs(const InferStage &ST, const EvalRowsStage &RS, int m, int i, int n, const typename Obj::IO &E,
+                const sac_eval_src_t *src, int row_wg0) {
+    int row_wgs = 0;
+    if (src) {
+        row_wgs = eval_rows_member(*ST.S, RS, m, i, row_wg0, src[i], n, ST.dev(i, EVAL_P_OBS), ST.dev(i, EVAL_P_ACT),
+                                   ST.dev(i, EVAL_P_REW), ST.dev(i, EVAL_P_TERM), ST.dev(i, EVAL_P_NOBS));
+    } else {
+        ST.in(i, EVAL_P_OBS, E.obs); ST.in(i, EVAL_P_ACT, E.act); ST.in(i, EVAL_P_REW, E.rew); ST.in(i, EVAL_P_TERM, E.term);
+        ST.in(i, EVAL_P_NOBS, E.next_obs);
+    }
+    for (int d = 0; d < Obj::DRAWS; ++d) ST.in(i, EVAL_P_DRAW + d, E.*Obj::draws[d]);
+    return row_wgs;
+}
+
+// behind the wait: what member i's caller asked for into its arrays, the call's own values, the moment records
+template <class Obj>
+void eval_finish(const InferStage &ST, const MomentsStage &MS, const typename Obj::Call &C, int i, typename Obj::IO &E,
+                 typename Obj::Stats *st) {
+    ST.back(i, {{E.rows, Obj::P_ROWS}});
+    for (int k = 0; k < Obj::ARRAYS; ++k) ST.back(i, {{E.*Obj::arrays[k].field, Obj::P_ROWS + 1 + k}});
+    if (st) moments_read(*ST.S, MS, i, st);
+    C.finish(i, E, st);
 }
 
 }  // namespace
@@ -260,91 +371,73 @@ int eval_admit_io(const sac_eval_io_t &E, int i, bool need_rows) {
 static_assert((int)EVAL_ROWS_N == (int)SAC_EVAL_ROWS_N && (int)EVAL_Y == (int)SAC_EVAL_Y && EVAL_Q1 == 0 && EVAL_Q2 == 1,
               "k_eval's rows are sac_hip.h's, chain Q's the first two");
 
-// sac_evaluate_many (stats null) and sac_evaluate_stats_many: with stats, mu and log_std always have their place in the
-// staging (k_eval_moments reads them there; only the copy to the caller depends on what was asked for), k_eval_moments
-// runs behind k_eval in front of the wait, and a null io[i].rows is taken.  sac_evaluate_replay_many (src not null): the
-// five input parts of the staging are filled on the device, by k_eval_rows (sac_eval_rows.h) in front of k_eval, from
-// src[i]'s replay storage instead of io[i]'s arrays; everything else is the same body
-static int evaluate_many(const InferEntry &IE, sac_trainer_t *const *trainers, int n_trainers, const int32_t *n_rows,
-                         sac_eval_io_t *io, sac_eval_stats_t *stats, const sac_eval_src_t *src = nullptr) {
+// The fixed-shape body of an objective: *_evaluate_many (stats and src null), *_evaluate_stats_many and
+// *_evaluate_replay_many.  With stats, the arrays the moments kernel reads always have their place in the staging (only
+// the copy to the caller depends on what was asked for), the moments kernel runs behind the frame's kernel in front of the
+// wait, and a null io[i].rows is taken.  With src the five input parts of the staging are filled on the device, by
+// k_eval_rows (sac_eval_rows.h) in front of the frame's kernel, from src[i]'s replay storage instead of io[i]'s arrays.
+template <class Obj>
+static int eval_fused_many(const InferEntry &IE, sac_trainer_t *const *trainers, int n_trainers, const int32_t *n_rows,
+                           typename Obj::IO *io, typename Obj::Stats *stats, const sac_eval_src_t *src = nullptr) {
     if (int rc = infer_admit(IE, trainers, n_trainers, n_rows, [&](int i) {
-            return src ? eval_rows_admit(io[i], src[i], trainers[i], i, n_rows[i], !stats) : eval_admit_io(io[i], i, !stats);
+            return eval_admit_io<Obj>(io[i], src, trainers[i], i, n_rows[i], !stats);
         })) return rc;
     sac_trainer *t0 = trainers[0];
-    float alpha[SAC_GROUP_MAX], log_alpha[SAC_GROUP_MAX];
-    if (eval_read_alpha(trainers, n_trainers, n_rows, alpha, stats ? log_alpha : nullptr)) return -1;
+    typename Obj::Call C;
+    if (C.prepare(trainers, n_trainers, n_rows, stats != nullptr)) return -1;
 
-    enum { P_OBS, P_ACT, P_REW, P_TERM, P_NOBS, P_EPS, P_EPS_NEXT, P_ROWS, P_MU, P_LOG_STD, P_A_NEW, P_A_NEXT, NPART };
-    InferStage ST(sizeof(EvalMember) * SAC_GROUP_MAX);
-    for (int i = 0; i < n_trainers; ++i) {
-        const sac_trainer *t = trainers[i];
-        const size_t n = (size_t)n_rows[i], nO = n * t->O, nA = n * t->A;
-        const sac_eval_io_t &E = io[i];
-        const size_t part[NPART] = {nO, nA, n, n, nO, nA, nA, n * SAC_EVAL_ROWS_N,
-                                    n && (E.mu || stats) ? nA : 0, n && (E.log_std || stats) ? nA : 0,
-                                    n && E.a_new ? nA : 0, n && E.a_next ? nA : 0};
-        ST.carve(i, part, NPART);
-    }
+    InferStage ST(sizeof(typename Obj::Member) * SAC_GROUP_MAX);
+    for (int i = 0; i < n_trainers; ++i) eval_carve<Obj>(ST, i, trainers[i], n_rows[i], io[i], stats != nullptr, false);
     MomentsStage MS;
     if (stats) moments_carve(ST.bytes, MS, n_trainers);
     EvalRowsStage RS;
     if (src) eval_rows_carve(ST.bytes, RS, n_trainers, n_rows);
     if (ST.reserve(t0)) return -1;
     const sac_trainer::ActStage &S = t0->act_stage;
-    EvalMember *tab = reinterpret_cast<EvalMember *>(S.h);
+    typename Obj::Member *tab = reinterpret_cast<typename Obj::Member *>(S.h);
     int wgs = 0, m = 0, kq_max = 0, row_wgs = 0;
     for (int i = 0; i < n_trainers; ++i) {
         const sac_trainer *t = trainers[i];
         if (n_rows[i] == 0) continue;
-        const sac_eval_io_t &E = io[i];
-        EvalMember &M = tab[m++];
-        eval_member(M, t, 5, n_rows[i], wgs, kq_max);
-        // (src: k_eval_rows fills the five parts)
-        M.obs = ST.in(i, P_OBS, src ? nullptr : E.obs); M.act = ST.in(i, P_ACT, src ? nullptr : E.act);
-        M.rew = ST.in(i, P_REW, src ? nullptr : E.rew); M.term = ST.in(i, P_TERM, src ? nullptr : E.term);
-        M.nobs = ST.in(i, P_NOBS, src ? nullptr : E.next_obs);
-        M.eps = ST.in(i, P_EPS, E.eps); M.eps_next = ST.in(i, P_EPS_NEXT, E.eps_next);
-        if (src) row_wgs += eval_rows_member(S, RS, m - 1, i, row_wgs, src[i], n_rows[i], ST.dev(i, P_OBS), ST.dev(i, P_ACT),
-                                             ST.dev(i, P_REW), ST.dev(i, P_TERM), ST.dev(i, P_NOBS));
-        M.rows = ST.dev(i, P_ROWS); M.mu = ST.dev(i, P_MU, E.mu || stats); M.log_std = ST.dev(i, P_LOG_STD, E.log_std || stats);
-        M.a_new = ST.dev(i, P_A_NEW, E.a_new); M.a_next = ST.dev(i, P_A_NEXT, E.a_next);
-        if (stats) moments_member(S, MS, m - 1, i, M.rows, M.mu, M.log_std, n_rows[i], t->A);
-        M.alpha = alpha[i]; M.pad = 0;
+        auto dev = [&](int k) { return ST.dev(i, k, ST.size[i][k] != 0); };        // (null: a part nobody asked for)
+        typename Obj::Member &M = tab[m];
+        eval_member(M, t, Obj::NETS, n_rows[i], wgs, kq_max);
+        row_wgs += eval_inputs<Obj>(ST, RS, m, i, n_rows[i], io[i], src, row_wgs);
+        M.obs = dev(EVAL_P_OBS); M.act = dev(EVAL_P_ACT); M.rew = dev(EVAL_P_REW); M.term = dev(EVAL_P_TERM);
+        M.nobs = dev(EVAL_P_NOBS); M.rows = dev(Obj::P_ROWS);
+        Obj::member(M, t, C, i, dev);
+        if (stats) moments_member<Obj>(S, MS, m, i, dev, n_rows[i], t->A);
+        ++m;
     }
     if (src && eval_rows_launch(t0, RS, m, row_wgs, src, n_trainers, n_rows)) return -1;
-    if (eval_launch(k_eval, t0, wgs, m, kq_max, [&] { return stats ? moments_launch(t0, MS, m) : 0; })) return -1;
-    for (int i = 0; i < n_trainers; ++i) {
-        if (n_rows[i] == 0) continue;
-        sac_eval_io_t &E = io[i];
-        ST.back(i, {{E.rows, P_ROWS}, {E.mu, P_MU}, {E.log_std, P_LOG_STD}, {E.a_new, P_A_NEW}, {E.a_next, P_A_NEXT}});
-        E.alpha = alpha[i];
-        if (stats) moments_read(S, MS, i, alpha[i], log_alpha[i], &stats[i]);
-    }
+    if (eval_launch(Obj::kernel, t0, wgs, m, kq_max, [&] { return stats ? moments_launch<Obj>(t0, MS, m) : 0; })) return -1;
+    for (int i = 0; i < n_trainers; ++i)
+        if (n_rows[i]) eval_finish<Obj>(ST, MS, C, i, io[i], stats ? &stats[i] : nullptr);
     return 0;
 }
 
 // (declared extern "C" in include/sac_hip.h)
 int sac_evaluate_many(sac_trainer_t *const *trainers, int n_trainers, const int32_t *n_rows, sac_eval_io_t *io) {
     SAC_REQUIRE(trainers && n_rows && io, "bad arguments to sac_evaluate_many");
-    const InferEntry IE = {"sac_evaluate_many", false, true, "device evaluation",
-                           "sac_get_params and a forward on the host is the path", "evaluate"};
-    return evaluate_many(IE, trainers, n_trainers, n_rows, io, nullptr);
+    const InferEntry IE = eval_entry<SacEval>("sac_evaluate_many", false,
+                                             "sac_get_params and a forward on the host is the path");
+    return eval_fused_many<SacEval>(IE, trainers, n_trainers, n_rows, io, nullptr);
 }
 
 int sac_evaluate_stats_many(sac_trainer_t *const *trainers, int n_trainers, const int32_t *n_rows, sac_eval_io_t *io,
                             sac_eval_stats_t *stats) {
     SAC_REQUIRE(trainers && n_rows && io && stats, "bad arguments to sac_evaluate_stats_many");
-    const InferEntry IE = {"sac_evaluate_stats_many", false, true, "device evaluation",
-                           "sac_evaluate_general_stats_many is the entry", "evaluate"};
-    return evaluate_many(IE, trainers, n_trainers, n_rows, io, stats);
+    const InferEntry IE = eval_entry<SacEval>("sac_evaluate_stats_many", false,
+                                             "sac_evaluate_general_stats_many is the entry");
+    return eval_fused_many<SacEval>(IE, trainers, n_trainers, n_rows, io, stats);
 }
 
 int sac_evaluate_replay_many(sac_trainer_t *const *trainers, int n_trainers, const int32_t *n_rows, const sac_eval_src_t *src,
                              sac_eval_io_t *io, sac_eval_stats_t *stats) {
     SAC_REQUIRE(trainers && n_rows && src && io, "bad arguments to sac_evaluate_replay_many");
-    const InferEntry IE = {"sac_evaluate_replay_many", false, true, "device evaluation",
-                           "sac_evaluate_replay_general_many is the entry", "evaluate"};
-    return evaluate_many(IE, trainers, n_trainers, n_rows, io, stats, src);
+    const InferEntry IE = eval_entry<SacEval>("sac_evaluate_replay_many", false,
+                                             "sac_evaluate_replay_general_many is the entry");
+    return eval_fused_many<SacEval>(IE, trainers, n_trainers, n_rows, io, stats, src);
 }
 
 int sac_evaluate(sac_trainer_t *t, int64_t n, sac_eval_io_t *io) {

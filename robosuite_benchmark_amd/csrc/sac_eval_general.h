@@ -1,5 +1,7 @@
 // Evaluating the SAC objectives on the device for general-step trainers: nets of any depth and width (included by
 // sac_trainer.hip behind sac_eval.h, sac_act_general.h and sac_qval_general.h).
+// Here: the general-step body of both objectives (eval_general_many), described with the SAC objective's kernels, which
+// live here; td3_eval_general.h says what differs for TD3.
 //
 // What k_eval (sac_eval.h) computes in one launch for the fused kernels' shapes -- the thirteen arrays of sac_eval_io_t
 // for 1..1024 transitions (s, a, r, d, s') with their draws eps / eps_next, of each of 1..SAC_GROUP_MAX SAC trainers, from
@@ -83,42 +85,74 @@ __global__ __launch_bounds__(EG_YROWS) void k_eval_y(const EvalYMember *__restri
 
 }  // namespace sac
 
-// sac_evaluate_general_many (stats null) and sac_evaluate_general_stats_many: with stats, mu and log_std always have
-// their place in the staging, k_eval_moments (sac_eval_moments.h) runs behind k_eval_y in front of the wait, and a null
-// io[i].rows is taken -- as evaluate_many (sac_eval.h) does for the fused shapes.  sac_evaluate_replay_general_many (src
-// not null): k_eval_rows (sac_eval_rows.h) fills the five input parts from src[i]'s replay storage in front of the first
-// layer launch, as there
-static int evaluate_general_many(const InferEntry &IE, sac_trainer_t *const *trainers, int n_trainers, const int32_t *n_rows,
-                                 sac_eval_io_t *io, sac_eval_stats_t *stats, const sac_eval_src_t *src = nullptr) {
+namespace {
+
+// a critic chain of the general body: net `net` on [part obs | part act] of the member's staging; chain s writes row s of `rows`
+struct EvalCritic { int net, obs, act; };
+
+// The general step's half of the SAC description.  An objective's General names
+//   YMember, y_kernel            the y kernel and its member table
+//   policy_kernel                the kernel of the policy launches
+//   policy_net, action           the two policy chains (0: on s, 1: on s'): their nets, and the parts their heads write
+//   head(J, t, s, n, dev)        the head job of policy chain s
+//   critics[CRITICS]             the critic chains, in the order of their rows
+struct SacEval::General {
+    typedef sac::EvalYMember YMember;
+    static constexpr auto y_kernel = sac::k_eval_y;
+    static constexpr auto policy_kernel = sac::k_eval_layer<false>;
+    static constexpr int policy_net[2] = {SAC_NET_POLICY, SAC_NET_POLICY}, action[2] = {P_A_NEW, P_A_NEXT};
+    static constexpr int CRITICS = 6;
+    static constexpr EvalCritic critics[CRITICS] = {
+        {SAC_NET_QF1, EVAL_P_OBS, EVAL_P_ACT}, {SAC_NET_QF2, EVAL_P_OBS, EVAL_P_ACT},
+        {SAC_NET_QF1, EVAL_P_OBS, P_A_NEW}, {SAC_NET_QF2, EVAL_P_OBS, P_A_NEW},
+        {SAC_NET_TARGET_QF1, EVAL_P_NOBS, P_A_NEXT}, {SAC_NET_TARGET_QF2, EVAL_P_NOBS, P_A_NEXT}};
+    // the head writes the action and log_pi, and for the rows s the mean and the clamped log_std where they have a place
+    template <class Dev> static void head(sac::LayerJob &J, const sac_trainer *t, int s, int n, Dev dev) {
+        J.kind = LAYER_EVAL; J.A = t->A;
+        J.eps = dev(s ? P_EPS_NEXT : P_EPS);
+        J.lp = dev(P_ROWS) + (size_t)(s ? EVAL_LOG_PI_NEXT : EVAL_LOG_PI) * n;
+        J.mu = s ? nullptr : dev(P_MU);
+        J.ls = s ? nullptr : dev(P_LOG_STD);
+    }
+};
+
+}  // namespace
+
+// The general-step body of an objective: *_evaluate_general_many (stats and src null), *_evaluate_general_stats_many and
+// *_evaluate_replay_general_many, as eval_fused_many (sac_eval.h) serves the fixed-shape entries of the same names: with
+// stats, the moments kernel runs behind the y kernel in front of the wait and a null io[i].rows is taken; with src,
+// k_eval_rows (sac_eval_rows.h) fills the five input parts from src[i]'s replay storage in front of the first layer launch.
+// The staging: the layer tables, the y kernel's table, then per member the parts as there -- the actions that the critic
+// launches read always have their place.
+template <class Obj>
+static int eval_general_many(const InferEntry &IE, sac_trainer_t *const *trainers, int n_trainers, const int32_t *n_rows,
+                             typename Obj::IO *io, typename Obj::Stats *stats, const sac_eval_src_t *src = nullptr) {
+    typedef typename Obj::General G;
+    static_assert(G::CRITICS * SAC_GROUP_MAX <= EG_JOBS, "a critic launch fits the evaluation's job table");
     if (int rc = infer_admit(IE, trainers, n_trainers, n_rows, [&](int i) {
-            return src ? eval_rows_admit(io[i], src[i], trainers[i], i, n_rows[i], !stats) : eval_admit_io(io[i], i, !stats);
+            return eval_admit_io<Obj>(io[i], src, trainers[i], i, n_rows[i], !stats);
         })) return rc;
     sac_trainer *t0 = trainers[0];
-    float alpha[SAC_GROUP_MAX], log_alpha[SAC_GROUP_MAX];
-    if (eval_read_alpha(trainers, n_trainers, n_rows, alpha, stats ? log_alpha : nullptr)) return -1;
+    typename Obj::Call C;
+    if (C.prepare(trainers, n_trainers, n_rows, stats != nullptr)) return -1;
 
-    // the staging: the layer tables, k_eval_y's table, then per member
-    //   obs act rew term nobs eps eps_next | rows a_new a_next (always: the critic launches read them) mu log_std
-    enum { P_OBS, P_ACT, P_REW, P_TERM, P_NOBS, P_EPS, P_EPS_NEXT, P_ROWS, P_A_NEW, P_A_NEXT, P_MU, P_LOG_STD, NPART };
     LayerSchedule LS(EG_JOBS);
     static_assert(EG_LAUNCHES <= LayerSchedule::MAX_LAUNCHES, "the schedule counts every launch of an evaluation");
     const size_t tab_bytes = LS.bytes(EG_LAUNCHES);
-    InferStage ST(tab_bytes + infer_align(sizeof(EvalYMember) * SAC_GROUP_MAX));
+    InferStage ST(tab_bytes + infer_align(sizeof(typename G::YMember) * SAC_GROUP_MAX));
     int LP = 0, LQ = 0;
     size_t slice_p[SAC_GROUP_MAX] = {}, slice_q[SAC_GROUP_MAX] = {};
     for (int i = 0; i < n_trainers; ++i) {
         sac_trainer *t = trainers[i];
-        const size_t n = (size_t)n_rows[i], nO = n * t->O, nA = n * t->A;
-        const sac_eval_io_t &E = io[i];
-        const size_t part[NPART] = {nO, nA, n, n, nO, nA, nA, n * SAC_EVAL_ROWS_N, nA, nA,
-                                    n && (E.mu || stats) ? nA : 0, n && (E.log_std || stats) ? nA : 0};
-        ST.carve(i, part, NPART);
+        const size_t n = (size_t)n_rows[i];
+        eval_carve<Obj>(ST, i, t, n_rows[i], io[i], stats != nullptr, true);
         if (n == 0) continue;
-        const GenNet &P = t->gen->net[SAC_NET_POLICY], &Q = t->gen->net[SAC_NET_QF1];      // (the four Q nets share their layout)
+        // (a policy and its target share their layout, and so do the four Q nets)
+        const GenNet &P = t->gen->net[SAC_NET_POLICY], &Q = t->gen->net[SAC_NET_QF1];
         // (one reservation for the larger of the two phases, not infer_scratch_reserve twice: that would free and
         // allocate again where the second phase is the larger)
         slice_p[i] = n * infer_widest(P); slice_q[i] = n * infer_widest(Q);
-        if (act_general_reserve(t, std::max(2 * slice_p[i], 6 * slice_q[i]))) return -1;
+        if (act_general_reserve(t, std::max(2 * slice_p[i], G::CRITICS * slice_q[i]))) return -1;
         LP = std::max(LP, P.nl); LQ = std::max(LQ, Q.nl);
     }
     MomentsStage MS;
@@ -128,90 +162,75 @@ static int evaluate_general_many(const InferEntry &IE, sac_trainer_t *const *tra
     if (ST.reserve(t0)) return -1;
     const sac_trainer::ActStage &S = t0->act_stage;
     LS.bind(S.h, S.d);
-    EvalYMember *ytab = reinterpret_cast<EvalYMember *>(S.h + tab_bytes);
+    typename G::YMember *ytab = reinterpret_cast<typename G::YMember *>(S.h + tab_bytes);
     int yblocks = 0, m = 0, row_wgs = 0;
     for (int i = 0; i < n_trainers; ++i) {
         const sac_trainer *t = trainers[i];
         if (n_rows[i] == 0) continue;
-        const sac_eval_io_t &E = io[i];
         const int n = n_rows[i];
-        auto dev = [&](int k) { return ST.dev(i, k); };
-        auto in = [&](int k, const float *from) { ST.in(i, k, from); };
-        if (src) {
-            row_wgs += eval_rows_member(S, RS, m, i, row_wgs, src[i], n, dev(P_OBS), dev(P_ACT), dev(P_REW), dev(P_TERM), dev(P_NOBS));
-        } else {
-            in(P_OBS, E.obs); in(P_ACT, E.act); in(P_REW, E.rew); in(P_TERM, E.term); in(P_NOBS, E.next_obs);
-        }
-        in(P_EPS, E.eps); in(P_EPS_NEXT, E.eps_next);
-        float *rows = dev(P_ROWS);
-        // the policy on s (with eps) and on s' (with eps_next), launches 0 .. : its head writes the action and log_pi
-        const GenNet &P = t->gen->net[SAC_NET_POLICY];
+        auto dev = [&](int k) { return ST.dev(i, k, ST.size[i][k] != 0); };        // (null: a part nobody asked for)
+        row_wgs += eval_inputs<Obj>(ST, RS, m, i, n, io[i], src, row_wgs);
+        float *rows = dev(Obj::P_ROWS);
+        // the policy chains, launches 0 .. : on s and on s'
         for (int s = 0; s < 2; ++s) {
-            const float *x = dev(s ? P_NOBS : P_OBS);
-            LS.chain({P, x, x, P.L[0].K, n, t->act_gen, s * slice_p[i], dev(s ? P_A_NEXT : P_A_NEW)},
-                     [&](sac::LayerJob &J, int l) {
-                if (l + 1 < P.nl) return;
-                J.kind = LAYER_EVAL; J.A = t->A;
-                J.eps = dev(s ? P_EPS_NEXT : P_EPS);
-                J.lp = rows + (size_t)(s ? EVAL_LOG_PI_NEXT : EVAL_LOG_PI) * n;
-                J.mu = !s && (E.mu || stats) ? dev(P_MU) : nullptr;
-                J.ls = !s && (E.log_std || stats) ? dev(P_LOG_STD) : nullptr;
+            const GenNet &P = t->gen->net[G::policy_net[s]];
+            const float *x = dev(s ? EVAL_P_NOBS : EVAL_P_OBS);
+            LS.chain({P, x, x, P.L[0].K, n, t->act_gen, s * slice_p[i], dev(G::action[s])}, [&](sac::LayerJob &J, int l) {
+                if (l + 1 == P.nl) G::head(J, t, s, n, dev);
             });
         }
-        // the critics, launches LP .. : chain s writes row s of `rows` (EVAL_Q1 .. EVAL_TQ2)
-        const int net_of[6] = {SAC_NET_QF1, SAC_NET_QF2, SAC_NET_QF1, SAC_NET_QF2, SAC_NET_TARGET_QF1, SAC_NET_TARGET_QF2};
-        const int obs_of[6] = {P_OBS, P_OBS, P_OBS, P_OBS, P_NOBS, P_NOBS};
-        const int act_of[6] = {P_ACT, P_ACT, P_A_NEW, P_A_NEW, P_A_NEXT, P_A_NEXT};
-        for (int s = 0; s < 6; ++s)
-            LS.chain({t->gen->net[net_of[s]], dev(obs_of[s]), dev(act_of[s]), t->O, n, t->act_gen, s * slice_q[i],
-                      rows + (size_t)s * n, true, LP});
-        if (stats) moments_member(S, MS, m, i, rows, dev(P_MU), dev(P_LOG_STD), n, t->A);
-        EvalYMember &M = ytab[m++];
-        M.rew = dev(P_REW); M.term = dev(P_TERM); M.rows = rows;
+        // the critics, launches LP .. : chain s writes row s of `rows`
+        for (int s = 0; s < G::CRITICS; ++s) {
+            const EvalCritic &c = G::critics[s];
+            LS.chain({t->gen->net[c.net], dev(c.obs), dev(c.act), t->O, n, t->act_gen, s * slice_q[i], rows + (size_t)s * n,
+                      true, LP});
+        }
+        if (stats) moments_member<Obj>(S, MS, m, i, dev, n, t->A);
+        typename G::YMember &M = ytab[m++];
+        M.rew = dev(EVAL_P_REW); M.term = dev(EVAL_P_TERM); M.rows = rows;
         M.n = n; M.wg0 = yblocks;
-        M.alpha = alpha[i]; M.rs = t->cfg.reward_scale; M.discount = t->cfg.discount; M.pad = 0;
+        M.rs = t->cfg.reward_scale; M.discount = t->cfg.discount;
+        if constexpr (!Obj::TD3) { M.alpha = C.alpha[i]; M.pad = 0; }       // (y's entropy term)
         yblocks += (n + EG_YROWS - 1) / EG_YROWS;
     }
     if (src && eval_rows_launch(t0, RS, m, row_wgs, src, n_trainers, n_rows)) return -1;
     for (int l = 0; l < LP + LQ; ++l)
-        if (LS.launch(l < LP ? k_eval_layer<false> : k_eval_layer<true>, t0, l)) return -1;
-    hipLaunchKernelGGL(k_eval_y, dim3(yblocks), dim3(EG_YROWS), 0, t0->stream,
-                       reinterpret_cast<const EvalYMember *>(S.d + tab_bytes), m);
+        if (LS.launch(l < LP ? G::policy_kernel : k_eval_layer<true>, t0, l)) return -1;
+    hipLaunchKernelGGL(G::y_kernel, dim3(yblocks), dim3(EG_YROWS), 0, t0->stream,
+                       reinterpret_cast<const typename G::YMember *>(S.d + tab_bytes), m);
     SAC_HIP(hipGetLastError());
-    if (stats && moments_launch(t0, MS, m)) return -1;
+    if (stats && moments_launch<Obj>(t0, MS, m)) return -1;
     if (wait_trainer_stream(t0)) return -1;
-    for (int i = 0; i < n_trainers; ++i) {
-        if (n_rows[i] == 0) continue;
-        sac_eval_io_t &E = io[i];
-        ST.back(i, {{E.rows, P_ROWS}, {E.a_new, P_A_NEW}, {E.a_next, P_A_NEXT}, {E.mu, P_MU}, {E.log_std, P_LOG_STD}});
-        E.alpha = alpha[i];
-        if (stats) moments_read(S, MS, i, alpha[i], log_alpha[i], &stats[i]);
-    }
+    for (int i = 0; i < n_trainers; ++i)
+        if (n_rows[i]) eval_finish<Obj>(ST, MS, C, i, io[i], stats ? &stats[i] : nullptr);
     return 0;
 }
 
 // (declared extern "C" in include/sac_hip.h)
 int sac_evaluate_general_many(sac_trainer_t *const *trainers, int n_trainers, const int32_t *n_rows, sac_eval_io_t *io) {
     SAC_REQUIRE(trainers && n_rows && io, "bad arguments to sac_evaluate_general_many");
-    const InferEntry IE = {"sac_evaluate_general_many", true, true, "device evaluation",
-                           "sac_evaluate is its device evaluation entry, sac_evaluate_general serves the general step", "evaluate"};
-    return evaluate_general_many(IE, trainers, n_trainers, n_rows, io, nullptr);
+    const InferEntry IE = eval_entry<SacEval>(
+        "sac_evaluate_general_many", true,
+        "sac_evaluate is its device evaluation entry, sac_evaluate_general serves the general step");
+    return eval_general_many<SacEval>(IE, trainers, n_trainers, n_rows, io, nullptr);
 }
 
 int sac_evaluate_general_stats_many(sac_trainer_t *const *trainers, int n_trainers, const int32_t *n_rows, sac_eval_io_t *io,
                                     sac_eval_stats_t *stats) {
     SAC_REQUIRE(trainers && n_rows && io && stats, "bad arguments to sac_evaluate_general_stats_many");
-    const InferEntry IE = {"sac_evaluate_general_stats_many", true, true, "device evaluation",
-                           "sac_evaluate_stats_many is its entry, sac_evaluate_general_stats_many serves the general step", "evaluate"};
-    return evaluate_general_many(IE, trainers, n_trainers, n_rows, io, stats);
+    const InferEntry IE = eval_entry<SacEval>(
+        "sac_evaluate_general_stats_many", true,
+        "sac_evaluate_stats_many is its entry, sac_evaluate_general_stats_many serves the general step");
+    return eval_general_many<SacEval>(IE, trainers, n_trainers, n_rows, io, stats);
 }
 
 int sac_evaluate_replay_general_many(sac_trainer_t *const *trainers, int n_trainers, const int32_t *n_rows,
                                      const sac_eval_src_t *src, sac_eval_io_t *io, sac_eval_stats_t *stats) {
     SAC_REQUIRE(trainers && n_rows && src && io, "bad arguments to sac_evaluate_replay_general_many");
-    const InferEntry IE = {"sac_evaluate_replay_general_many", true, true, "device evaluation",
-                           "sac_evaluate_replay_many is its entry, sac_evaluate_replay_general_many serves the general step", "evaluate"};
-    return evaluate_general_many(IE, trainers, n_trainers, n_rows, io, stats, src);
+    const InferEntry IE = eval_entry<SacEval>(
+        "sac_evaluate_replay_general_many", true,
+        "sac_evaluate_replay_many is its entry, sac_evaluate_replay_general_many serves the general step");
+    return eval_general_many<SacEval>(IE, trainers, n_trainers, n_rows, io, stats, src);
 }
 
 int sac_evaluate_general(sac_trainer_t *t, int64_t n, sac_eval_io_t *io) {

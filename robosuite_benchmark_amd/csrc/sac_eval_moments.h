@@ -144,29 +144,29 @@ void moments_carve(size_t &bytes, MomentsStage &MS, int n_trainers) {
     }
 }
 
-// member m of the launch (trainer i of the call): its columns in the staging
-void moments_member(const sac_trainer::ActStage &S, const MomentsStage &MS, int m, int i, const float *rows, const float *mu,
-                    const float *log_std, int n, int A) {
-    MomentsMember &M = reinterpret_cast<MomentsMember *>(S.h + MS.tab)[m];
-    M.rows = rows; M.mu = mu; M.log_std = log_std;
+// member m of the launch (trainer i of the call): its columns in the staging (dev(k): part k of the member on the device),
+// named by the objective (Obj::moments)
+template <class Obj, class Dev>
+void moments_member(const sac_trainer::ActStage &S, const MomentsStage &MS, int m, int i, Dev dev, int n, int A) {
+    typename Obj::Moments &M = reinterpret_cast<typename Obj::Moments *>(S.h + MS.tab)[m];
+    Obj::moments(M, dev);
     M.out = reinterpret_cast<sac_eval_moment_t *>(S.d + MS.rec[i]);
     M.n = n; M.A = A;
 }
 
+template <class Obj>
 int moments_launch(sac_trainer *t0, const MomentsStage &MS, int m) {
     const sac_trainer::ActStage &S = t0->act_stage;
-    hipLaunchKernelGGL(k_eval_moments, dim3(m * SAC_EVAL_MOMENTS_N), dim3(EM_LANES), 0, t0->stream,
-                       reinterpret_cast<const MomentsMember *>(S.d + MS.tab));
+    hipLaunchKernelGGL(Obj::moments_kernel, dim3(m * Obj::MOMENTS_N), dim3(sac::EM_LANES), 0, t0->stream,
+                       reinterpret_cast<const typename Obj::Moments *>(S.d + MS.tab));
     SAC_HIP(hipGetLastError());
     return 0;
 }
 
-// behind the wait: trainer i's records, with the alpha the entry evaluated y with and the log_alpha of the same Ctl copy
-void moments_read(const sac_trainer::ActStage &S, const MomentsStage &MS, int i, float alpha, float log_alpha,
-                  sac_eval_stats_t *st) {
+// behind the wait: trainer i's records
+template <class Stats>
+void moments_read(const sac_trainer::ActStage &S, const MomentsStage &MS, int i, Stats *st) {
     memcpy(st->m, S.h + MS.rec[i], sizeof(st->m));
-    st->alpha = (double)alpha;
-    st->log_alpha = (double)log_alpha;
 }
 
 }  // namespace

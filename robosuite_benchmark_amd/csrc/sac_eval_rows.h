@@ -4,7 +4,7 @@
 // k_eval_rows copies, for 1..1024 storage rows idx[j] of each of 1..SAC_GROUP_MAX members' replay buffers in ONE launch,
 // the five arrays of a transition out of the strided storage (ReplayView: row strides Ost / Ast, multiples of 4 floats)
 // into the DENSE input parts of the evaluation staging -- obs (n, O), act (n, A), rew (n), term (n), nobs (n, O) -- the
-// parts evaluate_many (sac_eval.h) and evaluate_general_many (sac_eval_general.h) otherwise fill with the caller's
+// parts eval_fused_many (sac_eval.h) and eval_general_many (sac_eval_general.h) otherwise fill with the caller's
 // arrays.  The layout infer_fill and k_eval_layer read is unchanged, so k_eval, k_eval_layer, k_eval_y and
 // k_eval_moments run behind it as they are, and the columns are bit for bit those of an evaluation of the gathered batch.
 //

@@ -1,5 +1,5 @@
 // Evaluating the TD3 objectives on the device: the forward half of the TD3 step on rows the run has not trained on
-// (included by sac_trainer.hip behind sac_eval.h, whose row-block frame, host staging and y expression it uses).
+// (included by sac_trainer.hip behind sac_eval.h, whose row-block frame, host body and y expression it uses).
 //
 // k_eval_td3 = eval_frame<Td3Objective> (sac_eval.h: the grid, the LDS layout, chain Q and the critics behind the heads)
 // computes, for 1..1024 transitions (s, a, r, d, s') with their N(0,1) smoothing draw eps, of each of 1..SAC_GROUP_MAX
@@ -22,9 +22,7 @@
 // SAC trainers are refused (sac_evaluate is their entry) and so are general-step TD3 trainers (td3_eval_general.h serves
 // them, or TD3Trainer.evaluate_td3's host path).
 //
-// td3_evaluate_stats_many reduces the statistics on the device as well (k_eval_moments_td3, td3_eval_moments.h, behind
-// k_eval_td3) and td3_evaluate_replay_many takes the input rows from the replay storage (k_eval_rows, sac_eval_rows.h, in
-// front of it): one body serves all three entries.
+// The entries are eval_fused_many (sac_eval.h) with Td3Eval, the objective's host description below.
 #pragma once
 
 namespace sac {
@@ -100,91 +98,60 @@ __global__ __launch_bounds__(256) void k_eval_td3(const Td3EvalMember *__restric
 static_assert((int)T3E_ROWS_N == (int)TD3_EVAL_ROWS_N && (int)T3E_Y == (int)TD3_EVAL_Y && (int)T3E_Q_PI == (int)TD3_EVAL_Q_PI &&
               T3E_Q1 == 0 && T3E_Q2 == 1, "k_eval_td3's rows are sac_hip.h's, chain Q's the first two");
 
-// td3_evaluate_many (stats and src null), td3_evaluate_stats_many and td3_evaluate_replay_many, as evaluate_many
-// (sac_eval.h) serves the SAC entries of the same names: with stats, a_pi always has its place in the staging
-// (k_eval_moments_td3 reads it there; only the copy to the caller depends on what was asked for), k_eval_moments_td3
-// (td3_eval_moments.h) runs behind k_eval_td3 in front of the wait, and a null io[i].rows is taken.  With src the five
-// input parts of the staging are filled on the device, by k_eval_rows (sac_eval_rows.h) in front of k_eval_td3, from
-// src[i]'s replay storage instead of io[i]'s arrays; everything else is the same body
-static int td3_evaluate_body(const InferEntry &IE, sac_trainer_t *const *trainers, int n_trainers, const int32_t *n_rows,
-                             td3_eval_io_t *io, td3_eval_stats_t *stats, const sac_eval_src_t *src = nullptr) {
-    if (int rc = infer_admit(IE, trainers, n_trainers, n_rows, [&](int i) {
-            return src ? eval_rows_admit(io[i], src[i], trainers[i], i, n_rows[i], !stats) : td3_eval_admit_io(io[i], i, !stats);
-        })) return rc;
-    sac_trainer *t0 = trainers[0];
+namespace {
 
-    enum { P_OBS, P_ACT, P_REW, P_TERM, P_NOBS, P_EPS, P_ROWS, P_A_PI, P_A_TARGET, P_A_SMOOTH, NPART };
-    InferStage ST(sizeof(Td3EvalMember) * SAC_GROUP_MAX);
-    for (int i = 0; i < n_trainers; ++i) {
-        const sac_trainer *t = trainers[i];
-        const size_t n = (size_t)n_rows[i], nO = n * t->O, nA = n * t->A;
-        const td3_eval_io_t &E = io[i];
-        const size_t part[NPART] = {nO, nA, n, n, nO, nA, n * TD3_EVAL_ROWS_N,
-                                    n && (E.a_pi || stats) ? nA : 0, n && E.a_target ? nA : 0, n && E.a_smooth ? nA : 0};
-        ST.carve(i, part, NPART);
-    }
-    MomentsStage MS;
-    if (stats) moments_carve(ST.bytes, MS, n_trainers);
-    EvalRowsStage RS;
-    if (src) eval_rows_carve(ST.bytes, RS, n_trainers, n_rows);
-    if (ST.reserve(t0)) return -1;
-    const sac_trainer::ActStage &S = t0->act_stage;
-    Td3EvalMember *tab = reinterpret_cast<Td3EvalMember *>(S.h);
-    int wgs = 0, m = 0, kq_max = 0, row_wgs = 0;
-    for (int i = 0; i < n_trainers; ++i) {
-        const sac_trainer *t = trainers[i];
-        if (n_rows[i] == 0) continue;
-        const td3_eval_io_t &E = io[i];
-        Td3EvalMember &M = tab[m++];
-        eval_member(M, t, 6, n_rows[i], wgs, kq_max);
+// the TD3 objective's host description (sac_eval.h says what one names)
+struct Td3Eval {
+    typedef td3_eval_io_t IO;
+    typedef td3_eval_stats_t Stats;
+    typedef sac::Td3EvalMember Member;
+    typedef sac::Td3MomentsMember Moments;
+    static constexpr auto kernel = sac::k_eval_td3;
+    static constexpr auto moments_kernel = sac::k_eval_moments_td3;
+    static constexpr bool TD3 = true;
+    static constexpr int NETS = 6, DRAWS = 1, ARRAYS = 3, ROWS_N = TD3_EVAL_ROWS_N, MOMENTS_N = TD3_EVAL_MOMENTS_N;
+    enum { P_EPS = EVAL_P_DRAW, P_ROWS, P_A_PI, P_A_TARGET, P_A_SMOOTH, NPART };
+    static constexpr const float *IO::*draws[DRAWS] = {&IO::eps};
+    static constexpr EvalArray<IO> arrays[ARRAYS] = {{&IO::a_pi, true, true}, {&IO::a_target, false, false},
+                                                     {&IO::a_smooth, true, false}};
+    struct Call {                            // (nothing is read per call, nothing handed back)
+        int prepare(sac_trainer_t *const *, int, const int32_t *, bool) { return 0; }
+        void finish(int, IO &, Stats *) const {}
+    };
+    template <class Dev> static void member(Member &M, const sac_trainer *t, const Call &, int, Dev dev) {
+        M.eps = dev(P_EPS);
+        M.a_pi = dev(P_A_PI); M.a_target = dev(P_A_TARGET); M.a_smooth = dev(P_A_SMOOTH);
         eval_layers(M.tW, M.tB, t->net[SAC_NET_TARGET_POLICY]);
-        // (src: k_eval_rows fills the five parts)
-        M.obs = ST.in(i, P_OBS, src ? nullptr : E.obs); M.act = ST.in(i, P_ACT, src ? nullptr : E.act);
-        M.rew = ST.in(i, P_REW, src ? nullptr : E.rew); M.term = ST.in(i, P_TERM, src ? nullptr : E.term);
-        M.nobs = ST.in(i, P_NOBS, src ? nullptr : E.next_obs); M.eps = ST.in(i, P_EPS, E.eps);
-        if (src) row_wgs += eval_rows_member(S, RS, m - 1, i, row_wgs, src[i], n_rows[i], ST.dev(i, P_OBS), ST.dev(i, P_ACT),
-                                             ST.dev(i, P_REW), ST.dev(i, P_TERM), ST.dev(i, P_NOBS));
-        M.rows = ST.dev(i, P_ROWS); M.a_pi = ST.dev(i, P_A_PI, E.a_pi || stats); M.a_target = ST.dev(i, P_A_TARGET, E.a_target);
-        M.a_smooth = ST.dev(i, P_A_SMOOTH, E.a_smooth);
         M.sigma = t->dev.td3_sigma; M.clip = t->dev.td3_clip;
-        if (stats) td3_moments_member(S, MS, m - 1, i, M.rows, M.a_pi, n_rows[i], t->A);
     }
-    if (src && eval_rows_launch(t0, RS, m, row_wgs, src, n_trainers, n_rows)) return -1;
-    if (eval_launch(k_eval_td3, t0, wgs, m, kq_max, [&] { return stats ? td3_moments_launch(t0, MS, m) : 0; })) return -1;
-    for (int i = 0; i < n_trainers; ++i) {
-        if (n_rows[i] == 0) continue;
-        const td3_eval_io_t &E = io[i];
-        ST.back(i, {{E.rows, P_ROWS}, {E.a_pi, P_A_PI}, {E.a_target, P_A_TARGET}, {E.a_smooth, P_A_SMOOTH}});
-        if (stats) td3_moments_read(S, MS, i, &stats[i]);
-    }
-    return 0;
-}
+    template <class Dev> static void moments(Moments &M, Dev dev) { M.rows = dev(P_ROWS); M.a_pi = dev(P_A_PI); }
+    struct General;
+};
 
-static InferEntry td3_eval_entry(const char *fn, const char *instead) {
-    InferEntry IE = {fn, false, false, "device evaluation", instead, "evaluate"};
-    IE.td3_only = true;
-    return IE;
-}
+}  // namespace
 
 // (declared extern "C" in include/sac_hip.h)
 int td3_evaluate_many(sac_trainer_t *const *trainers, int n_trainers, const int32_t *n_rows, td3_eval_io_t *io) {
     SAC_REQUIRE(trainers && n_rows && io, "bad arguments to td3_evaluate_many");
-    return td3_evaluate_body(td3_eval_entry("td3_evaluate_many", "sac_get_params and a forward on the host is the path"),
-                             trainers, n_trainers, n_rows, io, nullptr);
+    const InferEntry IE = eval_entry<Td3Eval>("td3_evaluate_many", false,
+                                             "sac_get_params and a forward on the host is the path");
+    return eval_fused_many<Td3Eval>(IE, trainers, n_trainers, n_rows, io, nullptr);
 }
 
 int td3_evaluate_stats_many(sac_trainer_t *const *trainers, int n_trainers, const int32_t *n_rows, td3_eval_io_t *io,
                             td3_eval_stats_t *stats) {
     SAC_REQUIRE(trainers && n_rows && io && stats, "bad arguments to td3_evaluate_stats_many");
-    return td3_evaluate_body(td3_eval_entry("td3_evaluate_stats_many", "td3_evaluate_general_stats_many is the entry"),
-                             trainers, n_trainers, n_rows, io, stats);
+    const InferEntry IE = eval_entry<Td3Eval>("td3_evaluate_stats_many", false,
+                                             "td3_evaluate_general_stats_many is the entry");
+    return eval_fused_many<Td3Eval>(IE, trainers, n_trainers, n_rows, io, stats);
 }
 
 int td3_evaluate_replay_many(sac_trainer_t *const *trainers, int n_trainers, const int32_t *n_rows, const sac_eval_src_t *src,
                              td3_eval_io_t *io, td3_eval_stats_t *stats) {
     SAC_REQUIRE(trainers && n_rows && src && io, "bad arguments to td3_evaluate_replay_many");
-    return td3_evaluate_body(td3_eval_entry("td3_evaluate_replay_many", "td3_evaluate_replay_general_many is the entry"),
-                             trainers, n_trainers, n_rows, io, stats, src);
+    const InferEntry IE = eval_entry<Td3Eval>("td3_evaluate_replay_many", false,
+                                             "td3_evaluate_replay_general_many is the entry");
+    return eval_fused_many<Td3Eval>(IE, trainers, n_trainers, n_rows, io, stats, src);
 }
 
 int td3_evaluate(sac_trainer_t *t, int64_t n, td3_eval_io_t *io) {

@@ -1,6 +1,5 @@
 // The statistics of a TD3 evaluation reduced on the device: k_eval_moments_td3 (included by sac_trainer.hip behind
-// sac_eval_moments.h, whose reduction it runs, and in front of td3_eval.h and td3_eval_general.h, whose *_stats_many and
-// *_replay_* entries launch it).
+// sac_eval_moments.h, whose reduction it runs and whose host helpers launch it, and in front of td3_eval.h).
 //
 // One launch on the first member's stream behind k_eval_td3 (fused shapes) or k_eval_y_td3 (general step) and in front of
 // the entry's single wait.  It reads the float32 columns where those kernels left them in the staging -- `rows`
@@ -58,36 +57,5 @@ namespace {
 // the staging is MomentsStage as moments_carve lays it out (sac_eval_moments.h): a table at least as large, as many records
 static_assert(sizeof(sac::Td3MomentsMember) <= sizeof(sac::MomentsMember) && (int)TD3_EVAL_MOMENTS_N == (int)SAC_EVAL_MOMENTS_N,
               "k_eval_moments_td3's table and records fit the places moments_carve makes");
-
-// member m of the launch (trainer i of the call): its columns in the staging
-void td3_moments_member(const sac_trainer::ActStage &S, const MomentsStage &MS, int m, int i, const float *rows,
-                        const float *a_pi, int n, int A) {
-    sac::Td3MomentsMember &M = reinterpret_cast<sac::Td3MomentsMember *>(S.h + MS.tab)[m];
-    M.rows = rows; M.a_pi = a_pi;
-    M.out = reinterpret_cast<sac_eval_moment_t *>(S.d + MS.rec[i]);
-    M.n = n; M.A = A;
-}
-
-int td3_moments_launch(sac_trainer *t0, const MomentsStage &MS, int m) {
-    const sac_trainer::ActStage &S = t0->act_stage;
-    hipLaunchKernelGGL(sac::k_eval_moments_td3, dim3(m * TD3_EVAL_MOMENTS_N), dim3(sac::EM_LANES), 0, t0->stream,
-                       reinterpret_cast<const sac::Td3MomentsMember *>(S.d + MS.tab));
-    SAC_HIP(hipGetLastError());
-    return 0;
-}
-
-// behind the wait: trainer i's records
-void td3_moments_read(const sac_trainer::ActStage &S, const MomentsStage &MS, int i, td3_eval_stats_t *st) {
-    memcpy(st->m, S.h + MS.rec[i], sizeof(st->m));
-}
-
-// an entry's own refusal for a member with rows: every input array is there, and `rows` unless the entry returns
-// statistics (there a null `rows` means that no column is copied back)
-int td3_eval_admit_io(const td3_eval_io_t &E, int i, bool need_rows) {
-    const bool inputs = E.obs && E.act && E.rew && E.term && E.next_obs && E.eps;
-    if (need_rows) SAC_REQUIRE(inputs && E.rows, "trainer %d: a null input array or null rows", i);
-    SAC_REQUIRE(inputs, "trainer %d: a null input array", i);
-    return 0;
-}
 
 }  // namespace

@@ -14,7 +14,7 @@ them: the statistics of an evaluation (eval_statistics on the host, the moment r
 from __future__ import annotations
 
 import ctypes as C
-from collections import OrderedDict
+from collections import OrderedDict, namedtuple
 
 import numpy as np
 
@@ -877,6 +877,18 @@ def eval_statistics(rows, mu, log_std, alpha, log_alpha, target_entropy, auto):
     return d
 
 
+def _moment_records(names, xs):
+    """One record {count, sum, m2, sumsq, max, min} per name over its elements x, in float64: m2 = sum((x - sum / count)^2),
+    a second pass as np.std's; max and min keep a NaN."""
+    out = OrderedDict()
+    with np.errstate(all="ignore"):
+        for name, x in zip(names, xs):
+            s = float(np.sum(x))
+            out[name] = dict(count=float(x.size), sum=s, m2=float(np.sum((x - s / x.size) ** 2)), sumsq=float(np.sum(x * x)),
+                             max=float(np.max(x)), min=float(np.min(x)))
+    return out
+
+
 def eval_moments(rows, mu, log_std):
     """k_eval_moments (csrc/sac_eval_moments.h) restated in NumPy float64 -- the reference of its tests and nothing else:
     an OrderedDict with one record {count, sum, m2, sumsq, max, min} per name of _lib.EVAL_MOMENTS, over q1, q2, y, log_pi
@@ -886,14 +898,7 @@ def eval_moments(rows, mu, log_std):
     r = [np.asarray(x, np.float64).ravel() for x in rows]
     q1, q2, q1n, q2n, _, _, lp, _, y = r
     flat = lambda x: np.asarray(x, np.float64).ravel()               # noqa: E731
-    xs = [q1, q2, y, lp, flat(mu), flat(log_std), q1 - y, q2 - y, lp - np.minimum(q1n, q2n)]
-    out = OrderedDict()
-    with np.errstate(all="ignore"):
-        for name, x in zip(_lib.EVAL_MOMENTS, xs):
-            s = float(np.sum(x))
-            out[name] = dict(count=float(x.size), sum=s, m2=float(np.sum((x - s / x.size) ** 2)), sumsq=float(np.sum(x * x)),
-                             max=float(np.max(x)), min=float(np.min(x)))
-    return out
+    return _moment_records(_lib.EVAL_MOMENTS, [q1, q2, y, lp, flat(mu), flat(log_std), q1 - y, q2 - y, lp - np.minimum(q1n, q2n)])
 
 
 def merge_moments(a, b):
@@ -922,16 +927,18 @@ def _stats_moments(st, names=_lib.EVAL_MOMENTS):
                        for i, name in enumerate(names))
 
 
+def _moment_figures(d, name, m):
+    """_four_figures from a moment record: Mean = sum / count, Std = sqrt(m2 / count), Max and Min as stored."""
+    d[name + " Mean"], d[name + " Std"] = m["sum"] / m["count"], float(np.sqrt(m["m2"] / m["count"]))
+    d[name + " Max"], d[name + " Min"] = m["max"], m["min"]
+
+
 def moments_statistics(moments, alpha, log_alpha, target_entropy, auto):
     """eval_statistics' OrderedDict -- the same keys in the same order -- from the moment records of eval_moments or of
     the device (sac_evaluate_stats_many): Mean = sum / count, Std = sqrt(m2 / count), Max and Min as stored, QF Loss =
     td.sumsq / count, Policy Loss = policy.sum / count, Alpha Loss = -(log_alpha (log_pi.sum / count + target_entropy)),
     0 with tuning off."""
-    def stats(d, name, m):
-        d[name + " Mean"], d[name + " Std"] = m["sum"] / m["count"], float(np.sqrt(m["m2"] / m["count"]))
-        d[name + " Max"], d[name + " Min"] = m["max"], m["min"]
-
-    M = moments
+    M, stats = moments, _moment_figures
     d = OrderedDict()
     with np.errstate(all="ignore"):
         d["QF1 Loss"] = M["td1"]["sumsq"] / M["td1"]["count"]
@@ -947,141 +954,7 @@ def moments_statistics(moments, alpha, log_alpha, target_entropy, auto):
     return d
 
 
-# ---- evaluation ---------------------------------------------------------------------------------------------------------
-def replay_route(t, buffer, general):
-    """route for a member of evaluate_replay: a buffer without device storage (no handle) sends it to the host too."""
-    return route(t, general, t._evaluate_on_host or getattr(buffer, "_h", None) is None)
-
-
-def evaluate_of(trainers, inputs, rows, general, stats, replay=None):
-    """evaluate / evaluate_many behind their argument checks: inputs[i] = the member's arrays as SACTrainer._eval_inputs
-    checked them, or None for a member that sits out (its result: None).  The host members first, in member order; then
-    the fused family, then the general one, each in windows.
-    replay (evaluate_replay_of): replay[i] = (buffer, indices) of a member with rows, whose inputs[i] then holds None for
-    the five arrays the device takes from the replay storage (EVAL_REPLAY_ENTRIES); a host member evaluates the gathered
-    batch."""
-    on_device = stats == "device"
-    R = len(trainers)
-    out, n_rows, served = [None] * R, [0] * R, {FUSED: [], GENERAL_STEP: []}
-    for i, (t, arrs) in enumerate(zip(trainers, inputs)):
-        if arrs is None:
-            continue
-        where = route(t, general, t._evaluate_on_host) if replay is None else replay_route(t, replay[i][0], general)
-        if where == HOST:
-            if replay is not None:
-                arrs = t._eval_inputs(replay[i][0].gather(replay[i][1]), arrs[5:], None)
-            cols = t._evaluate_host(arrs)
-            result = t._eval_stats(cols)
-            out[i] = (result, cols) if rows else result
-        else:
-            n_rows[i] = arrs[5].shape[0]
-            served[where].append(i)
-    members = served[FUSED] + served[GENERAL_STEP]
-    lib = _lib.load() if members else None
-    chunks, alphas, moments, log_alphas = {i: [] for i in members}, [1.0] * R, [None] * R, [0.0] * R
-    for family in (FUSED, GENERAL_STEP):
-        entry = EVAL_ENTRIES[family][on_device] if replay is None else EVAL_REPLAY_ENTRIES[family]
-        for r0, ids, counts in windows(served[family], n_rows):
-            made = [trainers[i]._eval_io(inputs[i], r0, r0 + k, outputs=rows or not on_device) for i, k in zip(ids, counts)]
-            ios = (_lib.SacEvalIO * len(ids))(*[m[0] for m in made])
-            sts = (_lib.SacEvalStats * len(ids))() if on_device else None
-            if replay is None:
-                args = [ios] + ([sts] if on_device else [])
-            else:
-                idx = [np.ascontiguousarray(replay[i][1][r0:r0 + k]) for i, k in zip(ids, counts)]
-                srcs = (_lib.SacEvalSrc * len(ids))(*[_lib.SacEvalSrc(replay[i][0]._h.value, x.ctypes.data)
-                                                      for i, x in zip(ids, idx)])
-                args = [srcs, ios, sts]
-            _lib.check(getattr(lib, entry)(_handles(trainers, ids), len(ids), _ints(counts), *args), entry)
-            for k, i in enumerate(ids):
-                chunks[i].append(made[k][1])
-                alphas[i] = float(ios[k].alpha)
-                if on_device:
-                    moments[i], log_alphas[i] = _merge_all(moments[i], _stats_moments(sts[k])), sts[k].log_alpha
-    for i in members:
-        t = trainers[i]
-        cols = _sac_eval_columns(chunks[i], alphas[i]) if rows or not on_device else None
-        if on_device:
-            result = moments_statistics(moments[i], alphas[i], log_alphas[i], t.target_entropy, t.use_automatic_entropy_tuning)
-        else:
-            result = t._eval_stats(cols)
-        out[i] = (result, cols) if rows else result
-    return out
-
-
-def evaluate_many(trainers, batches, eps=None, rngs=None, rows=False, general="host", stats="host"):
-    """SACTrainer.evaluate for many runs at once: result[i] = trainers[i].evaluate(batches[i], eps[i], rngs[i]) (eps / rngs:
-    one entry per trainer or None; batches[i] None or without rows: the member sits out and gets None).  The SAC members
-    with the fused kernels' shapes are served by ONE launch per 16 of them and 1024 rows (sac_evaluate_many: dims, hidden
-    sizes and row counts mixed); the others -- the general step, trainers without a handle -- go through their own
-    evaluate inside the same call (a TD3 member raises there).  A member's columns never depend on its neighbours: they
-    are bit for bit those of its own evaluate.  Results come back in member order; rows=True as for evaluate.
-    general="device": the SAC members of the general step are evaluated on the device as well, by ONE
-    sac_evaluate_general_many call per 16 of them and 1024 rows; their results are bit for bit those of their own
-    evaluate(general="device").
-    stats="device" (evaluate's `stats`): the members served by those two entries get their statistics reduced on the device
-    in the same call (sac_evaluate_stats_many / sac_evaluate_general_stats_many: one k_eval_moments launch in front of the
-    call's wait) -- no eval_statistics and no sac_get_scalars for them, and with rows=False no column is copied back.  A
-    member's records are byte for byte those of its own evaluate(stats="device").  The members on the host path get
-    eval_statistics under either value."""
-    check_stats(stats)
-    check_general(general)
-    trainers, batches, eps, rngs = _member_args("evaluate_many", "batch (and eps pair, and rng)", trainers, batches, eps, rngs)
-    inputs = [None] * len(trainers)
-    for i, (t, b) in enumerate(zip(trainers, batches)):
-        if b is None or np.atleast_2d(b["observations"]).shape[0] == 0:
-            continue
-        if _is_td3(t):
-            t.evaluate(b, eps=eps[i], rng=rngs[i], rows=rows)        # (TD3Trainer.evaluate refuses: the SAC objective)
-        inputs[i] = t._eval_inputs(b, eps[i], rngs[i])
-    return evaluate_of(trainers, inputs, rows, general, stats)
-
-
-def evaluate_replay_of(trainers, buffers, requests, rows, general, stats):
-    """evaluate_replay / evaluate_replay_many behind their argument checks: requests[i] = (indices, eps, eps_next) as
-    SACTrainer._replay_request checked them, or None for a member that sits out.  With rows the column dict of a member
-    additionally holds "indices"."""
-    inputs = [None if q is None else (None,) * 5 + (q[1], q[2]) for q in requests]
-    replay = [None if q is None else (b, q[0]) for b, q in zip(buffers, requests)]
-    out = evaluate_of(trainers, inputs, rows, general, stats, replay=replay)
-    if rows:
-        for q, res in zip(requests, out):
-            if q is not None:
-                res[1]["indices"] = q[0]
-    return out
-
-
-def evaluate_replay_many(trainers, buffers, n=None, indices=None, eps=None, rngs=None, rows=False, general="host",
-                         stats="host"):
-    """SACTrainer.evaluate_replay for many runs at once: result[i] = trainers[i].evaluate_replay(buffers[i], n or
-    indices[i], eps[i], rngs[i]).  Exactly one of n and indices: n one row count for every member or one per member,
-    indices one array of storage rows per member; an entry of None / 0 / no rows: the member sits out and gets None.
-    eps / rngs: one entry per trainer or None.  Two members may share a buffer (rows are only read).  The members on
-    the device are served by ONE call per 16 of them and 1024 rows per family (sac_evaluate_replay_many /
-    sac_evaluate_replay_general_many; general and stats as for evaluate_many); the others run evaluate on their gathered
-    batch inside the same call.  A member's result is bit for bit that of its own evaluate_replay; a TD3 member raises."""
-    check_stats(stats)
-    check_general(general)
-    trainers = list(trainers)
-    R = len(trainers)
-    if (n is None) == (indices is None):
-        raise ValueError("evaluate_replay_many takes exactly one of n and indices")
-    trainers, buffers, counts, indices, eps, rngs = _member_args(
-        "evaluate_replay_many", "buffer (and row count or indices, eps pair, rng)", trainers, buffers,
-        [n] * R if np.isscalar(n) else n, indices, eps, rngs)
-    requests = [None] * R
-    for i, (t, b) in enumerate(zip(trainers, buffers)):
-        if n is not None and not counts[i]:
-            continue
-        if n is None and (indices[i] is None or np.asarray(indices[i]).size == 0):
-            continue
-        if _is_td3(t):
-            t.evaluate_replay(b, n=counts[i], indices=indices[i])     # (TD3Trainer.evaluate_replay refuses: the SAC objective)
-        requests[i] = t._replay_request(b, counts[i], indices[i], eps[i], rngs[i])
-    return evaluate_replay_of(trainers, buffers, requests, rows, general, stats)
-
-
-# ---- evaluation of the TD3 objectives -----------------------------------------------------------------------------------
+# ---- evaluation of the TD3 objectives: its statistics -------------------------------------------------------------------
 def td3_eval_target(rew, term, tq1, tq2, reward_scale, discount):
     """k_eval_td3's y in float32 NumPy, operation for operation:
     y = rs * r + ((1 - d) * discount) * min(tq1, tq2), each result rounded to float32 (np.fmin, as fminf)."""
@@ -1123,11 +996,6 @@ def td3_eval_statistics(rows, a_pi):
     return d
 
 
-def _td3_eval_result(cols, rows):
-    result = td3_eval_statistics(np.stack([cols[k] for k in _lib.TD3_EVAL_ROWS]), cols["a_pi"])
-    return (result, cols) if rows else result
-
-
 def td3_eval_moments(rows, a_pi):
     """k_eval_moments_td3 (csrc/td3_eval_moments.h) restated in NumPy float64 -- the reference of its tests and nothing
     else: an OrderedDict with one record {count, sum, m2, sumsq, max, min} per name of _lib.TD3_EVAL_MOMENTS, over q1, q2,
@@ -1135,24 +1003,15 @@ def td3_eval_moments(rows, a_pi):
     formed in float64 from the columns given.  m2 = sum((x - sum / count)^2), a second pass as np.std's; max and min keep
     a NaN."""
     q1, q2, q_pi, _, _, y = [np.asarray(x, np.float64).ravel() for x in rows]
-    out = OrderedDict()
     with np.errstate(all="ignore"):
         xs = [q1, q2, y, q_pi, np.asarray(a_pi, np.float64).ravel(), q1 - y, q2 - y, (q1 - y) ** 2, (q2 - y) ** 2]
-        for name, x in zip(_lib.TD3_EVAL_MOMENTS, xs):
-            s = float(np.sum(x))
-            out[name] = dict(count=float(x.size), sum=s, m2=float(np.sum((x - s / x.size) ** 2)), sumsq=float(np.sum(x * x)),
-                             max=float(np.max(x)), min=float(np.min(x)))
-    return out
+    return _moment_records(_lib.TD3_EVAL_MOMENTS, xs)
 
 
 def td3_moments_statistics(moments):
     """td3_eval_statistics' OrderedDict -- the same keys in the same order -- from the moment records of td3_eval_moments
     or of the device (td3_evaluate_stats_many): Mean = sum / count, Std = sqrt(m2 / count), Max and Min as stored,
     QF Loss = bellman.sum / count, Policy Loss = -(q_pi.sum / count)."""
-    def stats(d, name, m):
-        d[name + " Mean"], d[name + " Std"] = m["sum"] / m["count"], float(np.sqrt(m["m2"] / m["count"]))
-        d[name + " Max"], d[name + " Min"] = m["max"], m["min"]
-
     M = moments
     d = OrderedDict()
     with np.errstate(all="ignore"):
@@ -1162,8 +1021,212 @@ def td3_moments_statistics(moments):
         for name, key in (("Q1 Predictions", "q1"), ("Q2 Predictions", "q2"), ("Q Targets", "y"),
                           ("Bellman Errors 1", "bellman1"), ("Bellman Errors 2", "bellman2"), ("Policy Action", "a_pi"),
                           ("TD Error 1", "td1"), ("TD Error 2", "td2")):
-            stats(d, name, M[key])
+            _moment_figures(d, name, M[key])
     return d
+
+
+# ---- evaluation: one call path for both objectives ----------------------------------------------------------------------
+def replay_route(t, buffer, general):
+    """route for a member of evaluate_replay: a buffer without device storage (no handle) sends it to the host too."""
+    return route(t, general, t._evaluate_on_host or getattr(buffer, "_h", None) is None)
+
+
+def _refuse_sac_members(caller, trainers, instead):
+    for i, t in enumerate(trainers):
+        if not _is_td3(t):
+            raise RuntimeError(f"{caller} member {i} is a SAC trainer: this call evaluates the TD3 objective (a "
+                               f"deterministic policy with target smoothing); {instead} evaluates the SAC objective")
+
+
+# What the call path below needs to know about an objective:
+#   td3                               the TD3 objective: it refuses SAC members in front of everything (_refuse_sac_members);
+#                                     the SAC objective refuses a TD3 member through TD3Trainer.evaluate[_replay] raising
+#   io, stats                         the ctypes structs of the entries
+#   rows, arrays, moments             the names of the per-row columns, of the (n, A) arrays and of the moment records
+#   entries, stats_entries, replay_entries   family -> entry: plain, with statistics, on replay rows
+#   draws                             the N(0,1) arrays of a request: the inputs behind the five arrays of a transition
+#   inputs, host, request             the trainer's methods: a batch's checked arrays, the host forward (arrays ->
+#                                     columns), a replay request's checked (indices, draws)
+#   host_stats(t, cols)               the statistics of the columns on the host
+#   device_stats(t, moments, alpha, log_alpha)   the same keys from the device's moment records
+#   columns(chunks, alpha)            what becomes of a member's chunks (SAC adds `alpha`)
+Objective = namedtuple("Objective", "td3 io stats rows arrays moments entries stats_entries replay_entries draws inputs host "
+                                    "request host_stats device_stats columns")
+SAC_OBJECTIVE = Objective(
+    False, _lib.SacEvalIO, _lib.SacEvalStats, _lib.EVAL_ROWS, _lib.EVAL_ARRAYS, _lib.EVAL_MOMENTS,
+    {f: e[0] for f, e in EVAL_ENTRIES.items()}, {f: e[1] for f, e in EVAL_ENTRIES.items()}, EVAL_REPLAY_ENTRIES, 2,
+    "_eval_inputs", "_evaluate_host", "_replay_request", lambda t, cols: t._eval_stats(cols),
+    lambda t, m, alpha, log_alpha: moments_statistics(m, alpha, log_alpha, t.target_entropy, t.use_automatic_entropy_tuning),
+    _sac_eval_columns)
+TD3_OBJECTIVE = Objective(
+    True, _lib.Td3EvalIO, _lib.Td3EvalStats, _lib.TD3_EVAL_ROWS, _lib.TD3_EVAL_ARRAYS, _lib.TD3_EVAL_MOMENTS,
+    TD3_EVAL_ENTRIES, TD3_EVAL_STATS_ENTRIES, TD3_EVAL_REPLAY_ENTRIES, 1,
+    "_td3_eval_inputs", "_evaluate_td3_host", "_td3_replay_request",
+    lambda t, cols: td3_eval_statistics(np.stack([cols[k] for k in _lib.TD3_EVAL_ROWS]), cols["a_pi"]),
+    lambda t, m, alpha, log_alpha: td3_moments_statistics(m),
+    lambda chunks, alpha: _eval_columns(chunks, _lib.TD3_EVAL_ROWS, _lib.TD3_EVAL_ARRAYS))
+
+
+def _evaluate_of(ob, trainers, inputs, rows, general, stats, replay=None):
+    """evaluate_of / td3_evaluate_of for objective ob.  The host members first, in member order; then the fused family, then
+    the general one, each in windows of its entry: 16 members and 1024 rows per call.  Every member served on the device
+    is settled behind its calls (the library ran sac_sync on it)."""
+    on_device = stats == "device"
+    R = len(trainers)
+    out, n_rows, served = [None] * R, [0] * R, {FUSED: [], GENERAL_STEP: []}
+    for i, (t, arrs) in enumerate(zip(trainers, inputs)):
+        if arrs is None:
+            continue
+        where = route(t, general, t._evaluate_on_host) if replay is None else replay_route(t, replay[i][0], general)
+        if where == HOST:
+            if replay is not None:
+                arrs = getattr(t, ob.inputs)(replay[i][0].gather(replay[i][1]), arrs[5:] if ob.draws > 1 else arrs[5], None)
+            cols = getattr(t, ob.host)(arrs)
+            result = ob.host_stats(t, cols)
+            out[i] = (result, cols) if rows else result
+        else:
+            n_rows[i] = arrs[5].shape[0]
+            served[where].append(i)
+    members = served[FUSED] + served[GENERAL_STEP]
+    if not members:
+        return out
+    lib = _lib.load()
+    chunks, alphas, moments, log_alphas = {i: [] for i in members}, [1.0] * R, [None] * R, [0.0] * R
+    for family in (FUSED, GENERAL_STEP):
+        if replay is not None:
+            entry = ob.replay_entries[family]
+        else:
+            entry = (ob.stats_entries if on_device else ob.entries)[family]
+        for r0, ids, counts in windows(served[family], n_rows):
+            made = [_eval_io(ob.io, ob.rows, ob.arrays, inputs[i], r0, r0 + k, trainers[i].act_dim,
+                             outputs=rows or not on_device) for i, k in zip(ids, counts)]
+            ios = (ob.io * len(ids))(*[m[0] for m in made])
+            sts = (ob.stats * len(ids))() if on_device else None
+            if replay is None:
+                args = [ios] + ([sts] if on_device else [])
+            else:
+                idx = [np.ascontiguousarray(replay[i][1][r0:r0 + k]) for i, k in zip(ids, counts)]
+                srcs = (_lib.SacEvalSrc * len(ids))(*[_lib.SacEvalSrc(replay[i][0]._h.value, x.ctypes.data)
+                                                      for i, x in zip(ids, idx)])
+                args = [srcs, ios, sts]
+            _lib.check(getattr(lib, entry)(_handles(trainers, ids), len(ids), _ints(counts), *args), entry)
+            for k, i in enumerate(ids):
+                chunks[i].append(made[k][1])
+                if not ob.td3:                                        # (the entropy coefficient of the call, and its log)
+                    alphas[i] = float(ios[k].alpha)
+                if on_device:
+                    moments[i] = _merge_all(moments[i], _stats_moments(sts[k], ob.moments))
+                    if not ob.td3:
+                        log_alphas[i] = sts[k].log_alpha
+    for i in members:
+        t = trainers[i]
+        t._settled()
+        cols = ob.columns(chunks[i], alphas[i]) if rows or not on_device else None
+        result = ob.device_stats(t, moments[i], alphas[i], log_alphas[i]) if on_device else ob.host_stats(t, cols)
+        out[i] = (result, cols) if rows else result
+    return out
+
+
+def _evaluate_replay_of(ob, trainers, buffers, requests, rows, general, stats):
+    """evaluate_replay_of / td3_evaluate_replay_of for objective ob: requests[i] = (indices, the draws)."""
+    inputs = [None if q is None else (None,) * 5 + tuple(q[1:]) for q in requests]
+    replay = [None if q is None else (b, q[0]) for b, q in zip(buffers, requests)]
+    out = _evaluate_of(ob, trainers, inputs, rows, general, stats, replay=replay)
+    if rows:
+        for q, res in zip(requests, out):
+            if q is not None:
+                res[1]["indices"] = q[0]
+    return out
+
+
+def _evaluate_many(ob, caller, takes, trainers, batches, eps, rngs, rows, general, stats):
+    """evaluate_many / td3_evaluate_many (`caller`) for objective ob."""
+    check_stats(stats)
+    check_general(general)
+    trainers, batches, eps, rngs = _member_args(caller, takes, trainers, batches, eps, rngs)
+    if ob.td3:
+        _refuse_sac_members(caller, trainers, "evaluate_many")
+    inputs = [None] * len(trainers)
+    for i, (t, b) in enumerate(zip(trainers, batches)):
+        if b is None or np.atleast_2d(b["observations"]).shape[0] == 0:
+            continue
+        if not ob.td3 and _is_td3(t):
+            t.evaluate(b, eps=eps[i], rng=rngs[i], rows=rows)        # (TD3Trainer.evaluate refuses: the SAC objective)
+        inputs[i] = getattr(t, ob.inputs)(b, eps[i], rngs[i])
+    return _evaluate_of(ob, trainers, inputs, rows, general, stats)
+
+
+def _evaluate_replay_many(ob, caller, takes, trainers, buffers, n, indices, eps, rngs, rows, general, stats):
+    """evaluate_replay_many / td3_evaluate_replay_many (`caller`) for objective ob."""
+    check_stats(stats)
+    check_general(general)
+    trainers = list(trainers)
+    R = len(trainers)
+    if (n is None) == (indices is None):
+        raise ValueError(f"{caller} takes exactly one of n and indices")
+    trainers, buffers, counts, indices, eps, rngs = _member_args(
+        caller, takes, trainers, buffers, [n] * R if np.isscalar(n) else n, indices, eps, rngs)
+    if ob.td3:
+        _refuse_sac_members(caller, trainers, "evaluate_replay_many")
+    requests = [None] * R
+    for i, (t, b) in enumerate(zip(trainers, buffers)):
+        if n is not None and not counts[i]:
+            continue
+        if n is None and (indices[i] is None or np.asarray(indices[i]).size == 0):
+            continue
+        if not ob.td3 and _is_td3(t):
+            t.evaluate_replay(b, n=counts[i], indices=indices[i])     # (TD3Trainer.evaluate_replay refuses: the SAC objective)
+        requests[i] = getattr(t, ob.request)(b, counts[i], indices[i], eps[i], rngs[i])
+    return _evaluate_replay_of(ob, trainers, buffers, requests, rows, general, stats)
+
+
+def evaluate_of(trainers, inputs, rows, general, stats, replay=None):
+    """evaluate / evaluate_many behind their argument checks: inputs[i] = the member's arrays as SACTrainer._eval_inputs
+    checked them, or None for a member that sits out (its result: None).  The host members first, in member order; then
+    the fused family, then the general one, each in windows.
+    replay (evaluate_replay_of): replay[i] = (buffer, indices) of a member with rows, whose inputs[i] then holds None for
+    the five arrays the device takes from the replay storage (EVAL_REPLAY_ENTRIES); a host member evaluates the gathered
+    batch."""
+    return _evaluate_of(SAC_OBJECTIVE, trainers, inputs, rows, general, stats, replay)
+
+
+def evaluate_many(trainers, batches, eps=None, rngs=None, rows=False, general="host", stats="host"):
+    """SACTrainer.evaluate for many runs at once: result[i] = trainers[i].evaluate(batches[i], eps[i], rngs[i]) (eps / rngs:
+    one entry per trainer or None; batches[i] None or without rows: the member sits out and gets None).  The SAC members
+    with the fused kernels' shapes are served by ONE launch per 16 of them and 1024 rows (sac_evaluate_many: dims, hidden
+    sizes and row counts mixed); the others -- the general step, trainers without a handle -- go through their own
+    evaluate inside the same call (a TD3 member raises there).  A member's columns never depend on its neighbours: they
+    are bit for bit those of its own evaluate.  Results come back in member order; rows=True as for evaluate.
+    general="device": the SAC members of the general step are evaluated on the device as well, by ONE
+    sac_evaluate_general_many call per 16 of them and 1024 rows; their results are bit for bit those of their own
+    evaluate(general="device").
+    stats="device" (evaluate's `stats`): the members served by those two entries get their statistics reduced on the device
+    in the same call (sac_evaluate_stats_many / sac_evaluate_general_stats_many: one k_eval_moments launch in front of the
+    call's wait) -- no eval_statistics and no sac_get_scalars for them, and with rows=False no column is copied back.  A
+    member's records are byte for byte those of its own evaluate(stats="device").  The members on the host path get
+    eval_statistics under either value."""
+    return _evaluate_many(SAC_OBJECTIVE, "evaluate_many", "batch (and eps pair, and rng)", trainers, batches, eps, rngs, rows,
+                          general, stats)
+
+
+def evaluate_replay_of(trainers, buffers, requests, rows, general, stats):
+    """evaluate_replay / evaluate_replay_many behind their argument checks: requests[i] = (indices, eps, eps_next) as
+    SACTrainer._replay_request checked them, or None for a member that sits out.  With rows the column dict of a member
+    additionally holds "indices"."""
+    return _evaluate_replay_of(SAC_OBJECTIVE, trainers, buffers, requests, rows, general, stats)
+
+
+def evaluate_replay_many(trainers, buffers, n=None, indices=None, eps=None, rngs=None, rows=False, general="host",
+                         stats="host"):
+    """SACTrainer.evaluate_replay for many runs at once: result[i] = trainers[i].evaluate_replay(buffers[i], n or
+    indices[i], eps[i], rngs[i]).  Exactly one of n and indices: n one row count for every member or one per member,
+    indices one array of storage rows per member; an entry of None / 0 / no rows: the member sits out and gets None.
+    eps / rngs: one entry per trainer or None.  Two members may share a buffer (rows are only read).  The members on
+    the device are served by ONE call per 16 of them and 1024 rows per family (sac_evaluate_replay_many /
+    sac_evaluate_replay_general_many; general and stats as for evaluate_many); the others run evaluate on their gathered
+    batch inside the same call.  A member's result is bit for bit that of its own evaluate_replay; a TD3 member raises."""
+    return _evaluate_replay_many(SAC_OBJECTIVE, "evaluate_replay_many", "buffer (and row count or indices, eps pair, rng)",
+                                 trainers, buffers, n, indices, eps, rngs, rows, general, stats)
 
 
 def td3_evaluate_of(trainers, inputs, rows, general="host", stats="host", replay=None):
@@ -1177,77 +1240,14 @@ def td3_evaluate_of(trainers, inputs, rows, general="host", stats="host", replay
     replay (td3_evaluate_replay_of): replay[i] = (buffer, indices) of a member with rows, whose inputs[i] then holds None
     for the five arrays the device takes from the replay storage (TD3_EVAL_REPLAY_ENTRIES); a host member evaluates the
     gathered batch."""
-    on_device = stats == "device"
-    R = len(trainers)
-    out, n_rows, served = [None] * R, [0] * R, {FUSED: [], GENERAL_STEP: []}
-    for i, (t, arrs) in enumerate(zip(trainers, inputs)):
-        if arrs is None:
-            continue
-        where = route(t, general, t._evaluate_on_host) if replay is None else replay_route(t, replay[i][0], general)
-        if where == HOST:
-            if replay is not None:
-                arrs = t._td3_eval_inputs(replay[i][0].gather(replay[i][1]), arrs[5], None)
-            out[i] = _td3_eval_result(t._evaluate_td3_host(arrs), rows)
-        else:
-            n_rows[i] = arrs[5].shape[0]
-            served[where].append(i)
-    members = served[FUSED] + served[GENERAL_STEP]
-    if not members:
-        return out
-    lib = _lib.load()
-    chunks, moments = {i: [] for i in members}, [None] * R
-    for family in (FUSED, GENERAL_STEP):
-        if replay is not None:
-            entry = TD3_EVAL_REPLAY_ENTRIES[family]
-        else:
-            entry = (TD3_EVAL_STATS_ENTRIES if on_device else TD3_EVAL_ENTRIES)[family]
-        for r0, ids, counts in windows(served[family], n_rows):
-            made = [_eval_io(_lib.Td3EvalIO, _lib.TD3_EVAL_ROWS, _lib.TD3_EVAL_ARRAYS, inputs[i], r0, r0 + k,
-                             trainers[i].act_dim, outputs=rows or not on_device) for i, k in zip(ids, counts)]
-            ios = (_lib.Td3EvalIO * len(ids))(*[m[0] for m in made])
-            sts = (_lib.Td3EvalStats * len(ids))() if on_device else None
-            if replay is None:
-                args = [ios] + ([sts] if on_device else [])
-            else:
-                idx = [np.ascontiguousarray(replay[i][1][r0:r0 + k]) for i, k in zip(ids, counts)]
-                srcs = (_lib.SacEvalSrc * len(ids))(*[_lib.SacEvalSrc(replay[i][0]._h.value, x.ctypes.data)
-                                                      for i, x in zip(ids, idx)])
-                args = [srcs, ios, sts]
-            _lib.check(getattr(lib, entry)(_handles(trainers, ids), len(ids), _ints(counts), *args), entry)
-            for k, i in enumerate(ids):
-                chunks[i].append(made[k][1])
-                if on_device:
-                    moments[i] = _merge_all(moments[i], _stats_moments(sts[k], _lib.TD3_EVAL_MOMENTS))
-    for i in members:
-        trainers[i]._settled()
-        cols = _eval_columns(chunks[i], _lib.TD3_EVAL_ROWS, _lib.TD3_EVAL_ARRAYS) if rows or not on_device else None
-        if on_device:
-            result = td3_moments_statistics(moments[i])
-            out[i] = (result, cols) if rows else result
-        else:
-            out[i] = _td3_eval_result(cols, rows)
-    return out
+    return _evaluate_of(TD3_OBJECTIVE, trainers, inputs, rows, general, stats, replay)
 
 
 def td3_evaluate_replay_of(trainers, buffers, requests, rows, general, stats):
     """evaluate_td3_replay / td3_evaluate_replay_many behind their argument checks: requests[i] = (indices, eps) as
     TD3Trainer._td3_replay_request checked them, or None for a member that sits out.  With rows the column dict of a
     member additionally holds "indices"."""
-    inputs = [None if q is None else (None,) * 5 + (q[1],) for q in requests]
-    replay = [None if q is None else (b, q[0]) for b, q in zip(buffers, requests)]
-    out = td3_evaluate_of(trainers, inputs, rows, general, stats, replay=replay)
-    if rows:
-        for q, res in zip(requests, out):
-            if q is not None:
-                res[1]["indices"] = q[0]
-    return out
-
-
-def _refuse_sac_members(caller, trainers, instead):
-    for i, t in enumerate(trainers):
-        if not _is_td3(t):
-            raise RuntimeError(f"{caller} member {i} is a SAC trainer: this call evaluates the TD3 objective (a "
-                               f"deterministic policy with target smoothing); {instead} evaluates the SAC objective")
+    return _evaluate_replay_of(TD3_OBJECTIVE, trainers, buffers, requests, rows, general, stats)
 
 
 def td3_evaluate_replay_many(trainers, buffers, n=None, indices=None, eps=None, rngs=None, rows=False, general="host",
@@ -1260,24 +1260,8 @@ def td3_evaluate_replay_many(trainers, buffers, n=None, indices=None, eps=None, 
     td3_evaluate_replay_general_many; general and stats as for td3_evaluate_many); the others run evaluate_td3 on their
     gathered batch inside the same call.  A member's result is bit for bit that of its own evaluate_td3_replay; a SAC
     member raises (evaluate_replay_many is the call for the SAC objective)."""
-    check_stats(stats)
-    check_general(general)
-    trainers = list(trainers)
-    R = len(trainers)
-    if (n is None) == (indices is None):
-        raise ValueError("td3_evaluate_replay_many takes exactly one of n and indices")
-    trainers, buffers, counts, indices, eps, rngs = _member_args(
-        "td3_evaluate_replay_many", "buffer (and row count or indices, eps, rng)", trainers, buffers,
-        [n] * R if np.isscalar(n) else n, indices, eps, rngs)
-    _refuse_sac_members("td3_evaluate_replay_many", trainers, "evaluate_replay_many")
-    requests = [None] * R
-    for i, (t, b) in enumerate(zip(trainers, buffers)):
-        if n is not None and not counts[i]:
-            continue
-        if n is None and (indices[i] is None or np.asarray(indices[i]).size == 0):
-            continue
-        requests[i] = t._td3_replay_request(b, counts[i], indices[i], eps[i], rngs[i])
-    return td3_evaluate_replay_of(trainers, buffers, requests, rows, general, stats)
+    return _evaluate_replay_many(TD3_OBJECTIVE, "td3_evaluate_replay_many", "buffer (and row count or indices, eps, rng)",
+                                 trainers, buffers, n, indices, eps, rngs, rows, general, stats)
 
 
 def td3_evaluate_many(trainers, batches, eps=None, rngs=None, rows=False, general="host", stats="host"):
@@ -1296,16 +1280,8 @@ def td3_evaluate_many(trainers, batches, eps=None, rngs=None, rows=False, genera
     front of the call's wait) -- no td3_eval_statistics for them, and with rows=False no column is copied back.  A
     member's records are byte for byte those of its own evaluate_td3(stats="device").  The members on the host path get
     td3_eval_statistics under either value."""
-    check_stats(stats)
-    check_general(general)
-    trainers, batches, eps, rngs = _member_args("td3_evaluate_many", "batch (and eps, and rng)", trainers, batches, eps, rngs)
-    _refuse_sac_members("td3_evaluate_many", trainers, "evaluate_many")
-    inputs = [None] * len(trainers)
-    for i, (t, b) in enumerate(zip(trainers, batches)):
-        if b is None or np.atleast_2d(b["observations"]).shape[0] == 0:
-            continue
-        inputs[i] = t._td3_eval_inputs(b, eps[i], rngs[i])
-    return td3_evaluate_of(trainers, inputs, rows, general, stats)
+    return _evaluate_many(TD3_OBJECTIVE, "td3_evaluate_many", "batch (and eps, and rng)", trainers, batches, eps, rngs, rows,
+                          general, stats)
 
 
 # ---- acting sessions ----------------------------------------------------------------------------------------------------

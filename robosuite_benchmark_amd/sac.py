@@ -611,11 +611,6 @@ class SACTrainer:
             raise ValueError(f"evaluate: eps {e1.shape} / eps_next {e2.shape} for actions {act.shape}")
         return obs, act, rew, term, nobs, e1, e2
 
-    def _eval_io(self, arrs, i, j, outputs=True):
-        """sac_eval_io_t over rows i..j of evaluate's inputs, and the output arrays it points to.  outputs=False (the
-        *_stats_many entries alone take it): no output array is made, `rows` and the optional arrays are NULL."""
-        return infer._eval_io(_lib.SacEvalIO, _lib.EVAL_ROWS, _lib.EVAL_ARRAYS, arrs, i, j, self.act_dim, outputs)
-
     _POLICY_HEADS = 2                # heads of act_dim units behind the policy's hidden layers: mean and log_std
 
     def _host_net(self, name):
@@ -722,35 +717,39 @@ class SACTrainer:
         infer.check_general(general)
         return infer.evaluate_of([self], [self._eval_inputs(batch, eps, rng)], rows, general, stats)[0]
 
-    def _replay_request(self, buffer, n, indices, eps, rng):
-        """evaluate_replay's arguments, checked before any library call: (indices int64 (k,), eps, eps_next float32 (k, A)).
-        Exactly one of n and indices; with n the indices are rng.randint(0, size, n), drawn IN FRONT of the eps pair from
+    def _replay_request(self, buffer, n, indices, eps, rng, caller="evaluate_replay", draws=2):
+        """`caller`'s arguments, checked before any library call: (indices int64 (k,), then the `draws` float32 (k, A)
+        arrays: eps and eps_next for evaluate_replay, the single eps of evaluate_td3_replay).  Exactly one of n and
+        indices; with n the indices are rng.randint(0, size, n), drawn IN FRONT of the standard_normal((k, A)) draws from
         the same stream (rng None: evaluate's private one)."""
         if (n is None) == (indices is None):
-            raise ValueError("evaluate_replay takes exactly one of n and indices")
+            raise ValueError(f"{caller} takes exactly one of n and indices")
         size = int(buffer.num_steps_can_sample())
         if size < 1:
-            raise RuntimeError("evaluate_replay: the replay buffer is empty")
+            raise RuntimeError(f"{caller}: the replay buffer is empty")
         if indices is None:
             if int(n) < 1:
-                raise ValueError(f"evaluate_replay: n = {n} (at least one row)")
+                raise ValueError(f"{caller}: n = {n} (at least one row)")
             rng = self._eval_stream(rng)
             idx = np.ascontiguousarray(rng.randint(0, size, int(n)), dtype=np.int64)
         else:
             idx = np.ascontiguousarray(np.asarray(indices).reshape(-1), dtype=np.int64)
             if idx.size < 1:
-                raise ValueError("evaluate_replay: no indices (at least one row)")
+                raise ValueError(f"{caller}: no indices (at least one row)")
             if int(idx.min()) < 0 or int(idx.max()) >= size:
                 bad = idx[(idx < 0) | (idx >= size)][0]
-                raise RuntimeError(f"evaluate_replay: index {int(bad)} out of range [0, {size})")
+                raise RuntimeError(f"{caller}: index {int(bad)} out of range [0, {size})")
         k, A = idx.size, self.act_dim
         if eps is None:
             rng = self._eval_stream(rng)
-            eps = (rng.standard_normal((k, A)), rng.standard_normal((k, A)))
-        e1, e2 = (_lib.f32(np.atleast_2d(e)) for e in eps)
-        if e1.shape != (k, A) or e2.shape != (k, A):
-            raise ValueError(f"evaluate_replay: eps {e1.shape} / eps_next {e2.shape} for {k} rows of {A} actions")
-        return idx, e1, e2
+            eps = [rng.standard_normal((k, A)) for _ in range(draws)]
+        elif draws == 1:
+            eps = [eps]
+        es = [_lib.f32(np.atleast_2d(e)) for e in eps]
+        if len(es) != draws or any(e.shape != (k, A) for e in es):
+            shapes = " / ".join(f"{name} {e.shape}" for name, e in zip(("eps", "eps_next"), es))
+            raise ValueError(f"{caller}: {shapes} for {k} rows of {A} actions")
+        return (idx, *es)
 
     def evaluate_replay(self, buffer, n=None, indices=None, eps=None, rng=None, rows=False, general="host", stats="host"):
         """evaluate on rows of `buffer` (an EnvReplayBuffer of this run's dims) IN PLACE: the SAC objectives at the

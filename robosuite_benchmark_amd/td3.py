@@ -149,30 +149,7 @@ class TD3Trainer(SACTrainer):
         """evaluate_td3_replay's arguments, checked before any library call: (indices int64 (k,), eps float32 (k, A)).
         Exactly one of n and indices; with n the indices are rng.randint(0, size, n), drawn IN FRONT of the single
         standard_normal((k, A)) from the same stream (rng None: evaluate_td3's private one)."""
-        if (n is None) == (indices is None):
-            raise ValueError("evaluate_td3_replay takes exactly one of n and indices")
-        size = int(buffer.num_steps_can_sample())
-        if size < 1:
-            raise RuntimeError("evaluate_td3_replay: the replay buffer is empty")
-        if indices is None:
-            if int(n) < 1:
-                raise ValueError(f"evaluate_td3_replay: n = {n} (at least one row)")
-            rng = self._eval_stream(rng)
-            idx = np.ascontiguousarray(rng.randint(0, size, int(n)), dtype=np.int64)
-        else:
-            idx = np.ascontiguousarray(np.asarray(indices).reshape(-1), dtype=np.int64)
-            if idx.size < 1:
-                raise ValueError("evaluate_td3_replay: no indices (at least one row)")
-            if int(idx.min()) < 0 or int(idx.max()) >= size:
-                bad = idx[(idx < 0) | (idx >= size)][0]
-                raise RuntimeError(f"evaluate_td3_replay: index {int(bad)} out of range [0, {size})")
-        k, A = idx.size, self.act_dim
-        if eps is None:
-            eps = self._eval_stream(rng).standard_normal((k, A))
-        eps = _lib.f32(np.atleast_2d(eps))
-        if eps.shape != (k, A):
-            raise ValueError(f"evaluate_td3_replay: eps {eps.shape} for {k} rows of {A} actions")
-        return idx, eps
+        return self._replay_request(buffer, n, indices, eps, rng, caller="evaluate_td3_replay", draws=1)
 
     def evaluate_td3_replay(self, buffer, n=None, indices=None, eps=None, rng=None, rows=False, general="host",
                             stats="host"):

@@ -12,8 +12,13 @@ A case module has GOLDEN (the file's name), CASES, case_id(case), make_all_membe
       entries compute (k_act_layer, k_qval_layer, k_eval_layer, k_act_layer_session, k_eval_y, k_unit_moments behind the
       layer launches); tests/test_gpu_general_golden.py compares.  It was written by the commit in front of the one that
       introduced infer_layer_frame and LayerSchedule (csrc/sac_infer.h).
+  tests.evaluate_entries_cases                tests/golden/evaluate_entries.npz pins the evaluation entries the other two
+      files do not reach (sac_evaluate_replay_many, td3_evaluate_stats_many, td3_evaluate_replay_many and the three
+      td3_evaluate_general*_many entries); tests/test_gpu_evaluate_entries_golden.py compares.  It was written by the
+      commit in front of the one that gave the SAC and TD3 entries one host body per family (eval_fused_many,
+      eval_general_many).
 
-A difference means that a later kernel changed behaviour: regenerate a file only for a change that is meant to change the
+A difference means that a later kernel or host body changed behaviour: regenerate a file only for a change that is meant to change the
 bits, from the commit in front of it.  --commit names the commit where no git checkout is at hand (default: git rev-parse
 HEAD)."""
 from __future__ import annotations

@@ -47,7 +47,9 @@ def test_bindings_and_header_name_the_general_entry_points():
     assert "sac_evaluate_general" in fused and "k_eval_layer" in header
     assert "forward on the host" in fused and "general step" in infer and "SAC objective" in infer
     general = open(os.path.join(csrc, "sac_eval_general.h")).read()
-    assert "eval_read_alpha" in general and "eval_read_alpha" in fused      # one alpha read for both entries
+    # one alpha read for both entries: the SAC description's per-call preparation, which the body of either family runs
+    assert fused.count("eval_read_alpha(") == 2 and "return eval_read_alpha(" in fused.split("int prepare(")[1].split("}")[0]
+    assert "eval_read_alpha" not in general and "C.prepare(" in general and "C.prepare(" in fused
 
 
 def test_general_is_checked_before_any_library_call(monkeypatch):

@@ -99,6 +99,24 @@ class Lib:
                 sts[k].alpha, sts[k].log_alpha = 0.5, 0.0
         return 0
 
+    def _replay_many(self, entry, handles, n, n_rows, srcs, ios, sts):
+        """A replay entry of either objective: zeros for every column, and with sts the records of r zeros."""
+        sac = isinstance(ios[0], _lib.SacEvalIO)
+        row_names, array_names = (_lib.EVAL_ROWS, _lib.EVAL_ARRAYS) if sac else (_lib.TD3_EVAL_ROWS, _lib.TD3_EVAL_ARRAYS)
+        for k, (h, r) in enumerate(zip(*self._note(entry, handles, n, n_rows))):
+            assert addr(srcs[k].buf) and not ios[k].obs
+            if ios[k].rows:
+                f32_view(ios[k].rows, len(row_names), r)[...] = 0.0
+                for name in array_names:
+                    f32_view(getattr(ios[k], name), r, A)[...] = 0.0
+            if sts is not None:
+                for m in sts[k].m:
+                    m.count = r
+        return 0
+
+    def sac_evaluate_replay_many(self, *a):
+        return self._replay_many("sac_evaluate_replay_many", *a)
+
     def sac_evaluate_stats_many(self, *a):
         return self._evaluate_many("sac_evaluate_stats_many", *a)
 
@@ -337,3 +355,25 @@ def test_fused_shapes_that_the_library_built_on_the_general_step_are_routed_as_g
     assert entries(lib) == act_entry
     # one predicate: what the library built, not what the hidden sizes say
     assert runs_general_step(t) and t.runs_general_step() and not runs_general_step(make(lib, hidden=(256, 256), handle=False))
+
+
+# ---- 4. a member served on the device is settled ----------------------------------------------------------------------------
+class DeviceBuffer:
+    """A replay buffer with device storage's face: a handle and a size."""
+    _h = Handle(77)
+
+    def num_steps_can_sample(self):
+        return 10
+
+
+def test_a_member_served_on_the_device_is_settled(lib):
+    """The library runs sac_sync on every member with rows (infer_admit), so the call path drops the references that keep
+    the stepped-on buffers alive -- under stats="device" too, where no sac_get_scalars follows that would."""
+    t = make(lib)
+    _, _, batch, eps = request(3)
+    for call, entry in ((lambda: t.evaluate(batch, eps=eps, stats="device"), "sac_evaluate_stats_many"),
+                        (lambda: t.evaluate_replay(DeviceBuffer(), indices=[0, 9, 9], eps=eps, stats="device"),
+                         "sac_evaluate_replay_many")):
+        t._stepped_buffers = (object(),)
+        call()
+        assert entries(lib) == [entry] and t._stepped_buffers == ()

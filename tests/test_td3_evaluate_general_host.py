@@ -15,7 +15,7 @@ from robosuite_benchmark_amd.infer import FUSED, GENERAL_STEP, HOST, TD3_EVAL_EN
 from tests import td3_eval_reference as two_layer
 from tests.td3_eval_reference import make_td3_trainer
 from tests.td3_eval_reference_general import SHAPES, column_scales, conditioned_inputs, net_layers, rows_of, shape_id
-from tests.test_infer_routing_host import A, O, Lib, entries, f32_view, make, request, value
+from tests.test_infer_routing_host import A, O, DeviceBuffer, Lib, entries, f32_view, make, request, value
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 
@@ -37,6 +37,9 @@ class Td3Lib(Lib):
 
     def td3_evaluate_general_many(self, *a):
         return self._td3_many("td3_evaluate_general_many", *a)
+
+    def td3_evaluate_replay_many(self, *a):
+        return self._replay_many("td3_evaluate_replay_many", *a)
 
 
 @pytest.fixture
@@ -80,6 +83,17 @@ def test_route_table(lib, kind, general):
     # the default is "host": the call without the keyword is the call with it
     t.evaluate_td3(batch, eps=eps[0])
     assert entries(lib) == ([] if ROUTES[(kind, "host")] == HOST else ["td3_evaluate_many"])
+
+
+def test_a_member_served_on_the_device_is_settled(lib):
+    """As for the SAC objective (tests/test_infer_routing_host.py): one call path settles the members of both."""
+    t = td3(lib)
+    _, _, batch, eps = request(3)
+    for call, entry in ((lambda: t.evaluate_td3(batch, eps=eps[0]), "td3_evaluate_many"),
+                        (lambda: t.evaluate_td3_replay(DeviceBuffer(), indices=[0, 9, 9], eps=eps[0]), "td3_evaluate_replay_many")):
+        t._stepped_buffers = (object(),)
+        call()
+        assert entries(lib) == [entry] and t._stepped_buffers == ()
 
 
 def test_a_mixed_call_serves_each_family_in_its_own_windows(lib):
