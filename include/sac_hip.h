@@ -718,6 +718,45 @@ typedef struct sac_recycle_io {
 int sac_recycle_units(sac_trainer_t *t, const sac_recycle_io_t *io);
 int sac_recycle_units_many(sac_trainer_t *const *trainers, int n_trainers, const sac_recycle_io_t *io);   /* up to SAC_GROUP_MAX */
 
+/* RESET and SHRINK-AND-PERTURB of whole networks on the device (Nikishin et al. 2022, D'Oro et al. 2023; Ash & Adams 2020):
+ * k_param_perturb, csrc/sac_perturb.h -- the whole-network remedies next to sac_recycle_units, the per-unit one.  For every
+ * element x of every flat nn.Linear tensor (sac_get_params) of a selected TRAINED net (policy, qf1, qf2; on TD3 handles the
+ * online policy):
+ *   fresh      f(e) of element e of tensor j (its place in the net's flat tensor list) of net k:
+ *                hidden weight fc<l>.weight   bound * s, bound = float32(1 / sqrt((double)N_l)) (networks._Mlp's rule)
+ *                hidden bias   fc<l>.bias     the constant b_init[k]: no draw
+ *                head weight and head bias    init_w[k] * s (last_fc and, on a SAC policy, last_fc_log_std)
+ *              s = 2u - 1 (exact in float32), u = (float(word >> 8) + 0.5f) * 2^-24, word = output word e & 3 of
+ *              Philox4x32-10 with counter (e >> 2, j | k << 8, draw lo, draw hi) and key (seed lo, seed hi); the product
+ *              with the bound is rounded once
+ *   new value  a = shrink * x, formed only if shrink != 0; b = perturb * f, formed only if perturb != 0; x' = a + b where
+ *              both are present, else the one that is: every operation rounded once, no FMA.  With shrink == 0 the old
+ *              value is not read into the result -- a reset clears a NaN or Inf weight; with shrink != 0 a NaN stays NaN
+ *   moments    with SAC_PERTURB_OPT, Adam's m and v of every element written become +0.0; step counts and bias
+ *              corrections are untouched (as with sac_recycle_units)
+ *   targets    with SAC_PERTURB_TARGETS the target paired with a selected net (target_qf1, target_qf2; on TD3 the target
+ *              policy; a SAC policy has none) receives the same new bits in every copy it has.  Without it targets are
+ *              left alone, and sac_param_moments' gap jumps
+ * Nothing else changes: pads stay +0.0, scalars, counters, generators and buffers stay bit for bit.  Both weight copies of
+ * the fused kernels' shapes and the moments where they live are written through the parameter map (csrc/sac_param_map.h);
+ * the fresh values are drawn on the device (csrc/sac_perturb_map.h): no parameter crosses the link.  What sac_get_params /
+ * sac_get_opt_state return afterwards is infer.shrink_perturb_reference of what they returned before, byte for byte.
+ * Both families and both algorithms are served, mixed in one call: ONE k_param_perturb launch on the first member's
+ * stream, one wait before return; a member's result does not depend on its neighbours.  Admission is
+ * sac_recycle_units_many's (1..16 trainers of one device, none confined by sac_trainer_set_xcd[_mask], none twice); every
+ * member is settled first and its acting mirror invalidated.  Refused (<0, sac_last_error, nothing written): a mask that
+ * selects no net, bits 3..5 or an unknown bit, unknown flags, shrink or perturb not finite, negative or both zero, a
+ * non-finite or negative init_w or a non-finite b_init of a selected net. */
+enum { SAC_PERTURB_OPT = 1, SAC_PERTURB_TARGETS = 2 };
+typedef struct sac_perturb_io {
+    uint32_t nets, flags;        /* nets: bit k selects SAC_NET_* == k, bits 0..2 only; flags: SAC_PERTURB_* */
+    float shrink, perturb;
+    uint64_t seed, draw;
+    float init_w[3], b_init[3];  /* per net id 0..2; read for the selected nets */
+} sac_perturb_io_t;
+int sac_shrink_perturb(sac_trainer_t *t, const sac_perturb_io_t *io);
+int sac_shrink_perturb_many(sac_trainer_t *const *trainers, int n_trainers, const sac_perturb_io_t *io);   /* up to SAC_GROUP_MAX */
+
 /* ------------------------------------------------------------------------------------------
  * Trainer groups: several runs of one configuration (the reference's seed sweeps, /root/reference/launch_jobs.sh)
  * stepped together.  A group holds 1..SAC_GROUP_MAX existing SAC trainers that share obs_dim, act_dim, batch (at most

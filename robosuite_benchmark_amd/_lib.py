@@ -152,6 +152,15 @@ class SacRecycleIO(C.Structure):
                 ("fresh", C.c_void_p)]
 
 
+PERTURB_OPT, PERTURB_TARGETS = 1, 2                                    # sac_perturb_io_t.flags
+
+
+class SacPerturbIO(C.Structure):
+    """sac_perturb_io_t"""
+    _fields_ = [("nets", C.c_uint32), ("flags", C.c_uint32), ("shrink", C.c_float), ("perturb", C.c_float),
+                ("seed", C.c_uint64), ("draw", C.c_uint64), ("init_w", C.c_float * 3), ("b_init", C.c_float * 3)]
+
+
 TD3_DIAG_NAMES = DIAG_NAMES[:16] + [f"Bellman Errors {i} {s}" for i in (1, 2) for s in ("Mean", "Std", "Max", "Min")] + [
     f"Policy Action {s}" for s in ("Mean", "Std", "Max", "Min")]
 
@@ -248,6 +257,8 @@ SYMBOLS = {
     "sac_param_moments_many": (C.c_int, [_P, C.c_int, _P]),
     "sac_recycle_units": (C.c_int, [_P, _P]),
     "sac_recycle_units_many": (C.c_int, [_P, C.c_int, _P]),
+    "sac_shrink_perturb": (C.c_int, [_P, _P]),
+    "sac_shrink_perturb_many": (C.c_int, [_P, C.c_int, _P]),
     "sac_group_create": (C.c_int, [C.POINTER(_P), _P, C.c_int]),
     "td3_group_create": (C.c_int, [C.POINTER(_P), _P, C.c_int]),
     "sac_group_create_mixed": (C.c_int, [C.POINTER(_P), _P, C.c_int]),

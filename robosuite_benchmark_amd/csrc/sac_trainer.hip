@@ -2355,6 +2355,7 @@ int stage_batches(sac_trainer *t, sac_buffer *b, int64_t n_steps) {
 #include "sac_units_general.h"
 #include "sac_params.h"
 #include "sac_recycle.h"
+#include "sac_perturb.h"
 #include "sac_eval_general.h"
 #include "td3_eval_general.h"
 #include "sac_actor.h"

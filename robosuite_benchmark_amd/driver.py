@@ -25,7 +25,7 @@ from .networks import (FlattenMlp, GaussianStrategy, MakeDeterministic, PolicyWr
 from .replay_buffer import EnvReplayBuffer
 from .group import (ArchSACTrainerGroup, ArchTD3TrainerGroup, GroupActor, MixedSACTrainerGroup, MixedTD3TrainerGroup,
                     MlpSACTrainerGroup, MlpTD3TrainerGroup, SACTrainerGroup, TD3TrainerGroup, act_many,
-                    evaluate_many, evaluate_replay_many, q_values_many, recycle_units_many, runs_general_step,
+                    evaluate_many, evaluate_replay_many, q_values_many, recycle_units_many, runs_general_step, shrink_perturb_many,
                     param_moments_many, param_statistics, td3_evaluate_many, td3_evaluate_replay_many,
                     unit_moments_many, unit_statistics)
 from .infer import UNIT_NET_TITLES, check_general, check_stats, dormant_units, param_target
@@ -426,6 +426,22 @@ def _recycle_rng(seed, epoch):
     return np.random.RandomState([seed, epoch, 0x524344])
 
 
+def check_reset(reset_period, reset_shrink, reset_perturb):
+    if isinstance(reset_period, bool) or not isinstance(reset_period, (int, np.integer)) or reset_period < 0:
+        raise RuntimeError(f"reset_period is a number of epochs (0: off), got {reset_period!r}")
+    sh, pe = float(reset_shrink), float(reset_perturb)
+    if not (np.isfinite(sh) and np.isfinite(pe) and sh >= 0.0 and pe >= 0.0 and (sh > 0.0 or pe > 0.0)):
+        raise RuntimeError(f"reset_shrink and reset_perturb are finite factors >= 0, not both 0, got {reset_shrink!r} and "
+                           f"{reset_perturb!r}")
+    return int(reset_period), sh, pe
+
+
+def _reset_words(seed, epoch):
+    """(seed, draw) of an epoch's reset, two 64-bit words: a function of (seed, epoch), so there is nothing to checkpoint."""
+    w = [int(x) for x in np.random.RandomState([seed, epoch, 0x525354]).randint(0, 2**32, 4)]
+    return w[0] | w[1] << 32, w[2] | w[3] << 32
+
+
 def _replay_rows(replay_eval, buf):
     """The replay rows of an epoch's evaluation: min(replay_eval, buffer size)."""
     return min(int(replay_eval), int(buf.num_steps_can_sample()))
@@ -538,7 +554,14 @@ class EvalOptions(NamedTuple):
     epoch % E == 0 the recycle_tau-dormant hidden units of policy, qf1 and qf2 are recycled (ReDo;
     SACTrainer.recycle_dormant: fresh incoming weights, zero outgoing weights, Adam's moments of both reset, on the
     device) directly in front of the training block -- _epoch_recycle.  The row gains a last block recycle/Policy Units /
-    QF1 Units / QF2 Units.  Target nets are left alone, so params/* Target Gap jumps on such an epoch.  SAC and TD3."""
+    QF1 Units / QF2 Units.  Target nets are left alone, so params/* Target Gap jumps on such an epoch.  SAC and TD3.
+
+    reset_period=E > 0 (it CHANGES the run too): on the epochs with epoch > 0 and epoch % E == 0 policy, qf1 and qf2 become
+    reset_shrink * theta + reset_perturb * theta_fresh (the defaults 0 and 1: a full reset, Nikishin et al. 2022; 0.8 and
+    0.2: shrink and perturb, Ash & Adams 2020), Adam's moments +0.0 and the targets the same bits, on the device
+    (SACTrainer.shrink_perturb) directly in front of the training block, behind _epoch_recycle -- _epoch_reset.  The
+    replay buffer, the step counts and the entropy coefficient stay.  The row gains a last block reset/Networks, the
+    number of nets written that epoch.  SAC and TD3."""
     q_diagnostics: bool = False
     q_general: str = "host"
     validation: bool = False
@@ -551,6 +574,9 @@ class EvalOptions(NamedTuple):
     td3_replay_eval: int = 0
     recycle_period: int = 0
     recycle_tau: float = 0.025
+    reset_period: int = 0
+    reset_shrink: float = 0.0
+    reset_perturb: float = 1.0
     td3_validation: bool = False
 
 
@@ -561,7 +587,7 @@ def _refuse_td3(variant, what, call, reason):
 
 def _options(what, specs, acting, q_diagnostics, q_general, validation, eval_general, eval_stats, replay_eval,
              unit_diagnostics=False, unit_general="host", param_diagnostics=False, td3_replay_eval=0,
-             recycle_period=0, recycle_tau=0.025, td3_validation=False):
+             recycle_period=0, recycle_tau=0.025, reset_period=0, reset_shrink=0.0, reset_perturb=1.0, td3_validation=False):
     """The EvalOptions of entry `what`, after the value checks of its keywords (acting's too) and, for the variant at
     the head of every run spec in `specs`, the TD3 refusals: all of it in front of anything that builds a run."""
     check_stats(eval_stats)
@@ -572,7 +598,7 @@ def _options(what, specs, acting, q_diagnostics, q_general, validation, eval_gen
     opts = EvalOptions(q_diagnostics, q_general, validation, eval_general, eval_stats, check_replay_eval(replay_eval),
                        bool(unit_diagnostics), unit_general, bool(param_diagnostics),
                        check_replay_eval(td3_replay_eval, "td3_replay_eval"), check_recycle_period(recycle_period),
-                       float(recycle_tau), bool(td3_validation))
+                       float(recycle_tau), *check_reset(reset_period, reset_shrink, reset_perturb), bool(td3_validation))
     if not opts.recycle_tau >= 0.0:
         raise RuntimeError(f"recycle_tau is a threshold >= 0, got {recycle_tau!r}")
     for spec in specs if opts.validation else ():
@@ -708,9 +734,35 @@ def _epoch_recycle(runs, blocks, epoch, opts, many=True):
         b["recycle"] = OrderedDict((f"recycle/{UNIT_NET_TITLES[n]} Units", 0 if c is None else int(c[n])) for n in UNIT_NETS)
 
 
+RESET_BLOCKS = ROW_BLOCKS + ("reset",)                        # ... and the reset/ block behind it
+
+
+def _epoch_reset(runs, blocks, epoch, opts, many=True):
+    """reset_period=E > 0: on the epochs with epoch > 0 and epoch % E == 0 policy, qf1 and qf2 of every run become
+    reset_shrink * theta + reset_perturb * theta_fresh with opt=True, targets=True (SACTrainer.shrink_perturb) -- directly
+    in front of the training block, behind _epoch_recycle.  (seed, draw) are _reset_words(run seed, epoch): nothing to
+    checkpoint.  many: ONE shrink_perturb_many call over all runs.  Every row gains blocks["reset"]: reset/Networks, the
+    number of nets written, 0 on the other epochs.  With the option at 0 nothing is called and nothing is added."""
+    if not opts.reset_period:
+        return
+    done = [None] * len(runs)
+    if epoch > 0 and epoch % opts.reset_period == 0:
+        trainers = [r["trainer"] for r in runs]
+        words = [_reset_words(r["seed"], epoch) for r in runs]
+        kw = dict(shrink=opts.reset_shrink, perturb=opts.reset_perturb, opt=True, targets=True)
+        if many:
+            done = shrink_perturb_many(trainers, [UNIT_NETS] * len(runs), seeds=[w[0] for w in words],
+                                       draws=[w[1] for w in words], **kw)
+        else:
+            done = [t.shrink_perturb(UNIT_NETS, seed=w[0], draw=w[1], **kw) for t, w in zip(trainers, words)]
+    for b, d in zip(blocks, done):
+        b["reset"] = OrderedDict([("reset/Networks", 0 if d is None else len(d))])
+
+
 def _end_epoch_row(r, blocks, epoch):
     """Run r's progress.csv columns of `epoch` in the reference's order up to the time/* block, the blocks of
-    _epoch_evaluations and _epoch_recycle behind them in ROW_BLOCKS' order; then the run's parts end their epoch."""
+    _epoch_evaluations, _epoch_recycle and _epoch_reset behind them in RESET_BLOCKS' order; then the run's parts end
+    their epoch."""
     buf, trainer, expl, evalc = r["buf"], r["trainer"], r["expl"], r["evalc"]
     row = OrderedDict()
     row.update(("replay_buffer/" + k, v) for k, v in buf.get_diagnostics().items())
@@ -719,7 +771,7 @@ def _end_epoch_row(r, blocks, epoch):
     row.update(path_information(expl.epoch_paths, "exploration/"))
     row.update(("evaluation/" + k, v) for k, v in evalc.get_diagnostics().items())
     row.update(path_information(evalc.epoch_paths, "evaluation/", r["ak"]["expl_max_path_length"]))
-    for name in ROW_BLOCKS:
+    for name in RESET_BLOCKS:
         row.update(blocks.get(name, ()))
     for x in (trainer, buf, expl, evalc):
         x.end_epoch(epoch)
@@ -826,7 +878,8 @@ def experiment(variant, log_dir=None, seed=1, obs_dim=None, action_dim=None, num
                fused_loop=True, quiet=False, checkpoint_dir=None, resume=False, acting="host", q_diagnostics=False,
                q_general="host", validation=False, eval_general="host", eval_stats="host", replay_eval=0,
                unit_diagnostics=False, unit_general="host", param_diagnostics=False, td3_replay_eval=0,
-               recycle_period=0, recycle_tau=0.025, td3_validation=False):
+               recycle_period=0, recycle_tau=0.025, reset_period=0, reset_shrink=0.0, reset_perturb=1.0,
+               td3_validation=False):
     """variant.json -> training run.  Returns the list of progress rows (also written to
     <log_dir>/progress.csv when log_dir is given).
 
@@ -847,7 +900,7 @@ def experiment(variant, log_dir=None, seed=1, obs_dim=None, action_dim=None, num
     per-epoch evaluations, EvalOptions; here from the trainer's own q_values, evaluate, evaluate_replay and unit_moments."""
     opts = _options("experiment", [(variant,)], acting, q_diagnostics, q_general, validation, eval_general, eval_stats,
                     replay_eval, unit_diagnostics, unit_general, param_diagnostics, td3_replay_eval,
-                    recycle_period, recycle_tau, td3_validation)
+                    recycle_period, recycle_tau, reset_period, reset_shrink, reset_perturb, td3_validation)
     validate(variant)
     # This driver's runs are a function of `seed` alone: initial weights come from np.random (seeded here), every noise
     # stream from `seed` -- whether or not torch happens to be loaded in the process (the reference's own scripts seed
@@ -875,6 +928,7 @@ def experiment(variant, log_dir=None, seed=1, obs_dim=None, action_dim=None, num
         buf.add_paths(new_paths)
         t3 = time.time()
         _epoch_recycle([r], blocks, epoch, opts, many=False)
+        _epoch_reset([r], blocks, epoch, opts, many=False)
         recycle_s = time.time() - t3                              # (counted as evaluation: it reads the evaluation paths)
         if fused_loop:
             trainer.train_loop(buf, n_train, batch_size=ak["batch_size"])
@@ -986,7 +1040,8 @@ def _group_epochs(*, runs, train_block, n_epochs, n_train, log_dir, quiet, what,
                 times = [(a0, eval_s + b_s, expl_s, store_s) for a0, eval_s, expl_s, store_s in times]
             t2r = time.time()
             _epoch_recycle(runs, blocks, epoch, opts)         # (in front of the training block: ONE call pair for all runs)
-            if opts.recycle_period:
+            _epoch_reset(runs, blocks, epoch, opts)           # (behind it: ONE shrink_perturb_many call for all runs)
+            if opts.recycle_period or opts.reset_period:
                 times = [(a0, eval_s + time.time() - t2r, expl_s, store_s) for a0, eval_s, expl_s, store_s in times]
             t3 = time.time()
             train_block()
@@ -1019,7 +1074,8 @@ def experiment_group(variant, seeds, log_dir=None, num_epochs=None, obs_dim=None
                      quiet=False, checkpoint_dir=None, resume=False, chunk_rows=DEFAULT_CHUNK_ROWS, acting="host", sessions=True,
                      general_sessions=None, q_diagnostics=False, q_general="host", validation=False,
                      eval_general="host", eval_stats="host", replay_eval=0, unit_diagnostics=False, unit_general="host",
-                     param_diagnostics=False, td3_replay_eval=0, recycle_period=0, recycle_tau=0.025, td3_validation=False):
+                     param_diagnostics=False, td3_replay_eval=0, recycle_period=0, recycle_tau=0.025, reset_period=0,
+                     reset_shrink=0.0, reset_perturb=1.0, td3_validation=False):
     """One configuration, several seeds, one process: each seed is the run ``experiment(variant, seed=s)`` would make --
     its own synthetic environments, collectors, weights and replay buffer -- and every epoch's training block is ONE
     SACTrainerGroup.train_loop (TD3 variants: TD3TrainerGroup; hidden sizes other than two layers of at most 256 units:
@@ -1045,7 +1101,7 @@ def experiment_group(variant, seeds, log_dir=None, num_epochs=None, obs_dim=None
     per-epoch evaluations, EvalOptions; each seed's rows are those of experiment(variant, seed=s) with the same options."""
     opts = _options("experiment_group", [(variant,)], acting, q_diagnostics, q_general, validation, eval_general,
                     eval_stats, replay_eval, unit_diagnostics, unit_general, param_diagnostics, td3_replay_eval,
-                    recycle_period, recycle_tau, td3_validation)
+                    recycle_period, recycle_tau, reset_period, reset_shrink, reset_perturb, td3_validation)
     if resume and not checkpoint_dir:
         raise RuntimeError("experiment_group(resume=True) needs the checkpoint_dir to resume from")
     validate(variant)
@@ -1100,7 +1156,8 @@ def experiment_sweep(runs, log_dir=None, num_epochs=None, device=0, quiet=False,
                      chunk_rows=DEFAULT_CHUNK_ROWS, hidden_sweep=False, acting="host", sessions=True, general_sessions=None,
                      q_diagnostics=False, q_general="host", validation=False,
                      eval_general="host", eval_stats="host", replay_eval=0, unit_diagnostics=False, unit_general="host",
-                     param_diagnostics=False, td3_replay_eval=0, recycle_period=0, recycle_tau=0.025, td3_validation=False):
+                     param_diagnostics=False, td3_replay_eval=0, recycle_period=0, recycle_tau=0.025, reset_period=0,
+                     reset_shrink=0.0, reset_perturb=1.0, td3_validation=False):
     """Several tasks x seeds, one process, one device: every entry of ``runs`` -- (variant, seed), or (variant, seed,
     obs_dim, action_dim) for a task without pinned dims -- is the run ``experiment(variant, seed=seed)`` would make, and
     every epoch's training block is ONE MixedSACTrainerGroup.train_loop (TD3 variants: MixedTD3TrainerGroup; hidden sizes
@@ -1125,7 +1182,7 @@ def experiment_sweep(runs, log_dir=None, num_epochs=None, device=0, quiet=False,
     the device's under q_general / eval_general "device".  A sweep with a TD3 run refuses validation and replay_eval."""
     opts = _options("experiment_sweep", runs, acting, q_diagnostics, q_general, validation, eval_general, eval_stats,
                     replay_eval, unit_diagnostics, unit_general, param_diagnostics, td3_replay_eval,
-                    recycle_period, recycle_tau, td3_validation)
+                    recycle_period, recycle_tau, reset_period, reset_shrink, reset_perturb, td3_validation)
     if resume and not checkpoint_dir:
         raise RuntimeError("experiment_sweep(resume=True) needs the checkpoint_dir to resume from")
     specs = []

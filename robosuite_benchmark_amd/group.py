@@ -20,7 +20,7 @@ from . import _lib
 # (the inference names live in infer.py; they stay importable from here)
 from .infer import (GENERAL, GENERAL_SESSIONS, MAX_MEMBERS, GroupActor, act_many, check_general,  # noqa: F401
                     evaluate_many, evaluate_replay_many, general_shape, merge_unit_moments, param_moments_many,
-                    param_moments_reference, param_statistics, q_values_many, recycle_units_many, runs_general_step,
+                    param_moments_reference, param_statistics, q_values_many, recycle_units_many, runs_general_step, shrink_perturb_many,
                     td3_eval_moments, td3_evaluate_many,
                     td3_evaluate_replay_many, td3_moments_statistics, unit_moments_many, unit_moments_reference, unit_statistics)
 from .sac import SACTrainer
@@ -86,6 +86,13 @@ class _Members:
         """recycle_units_many over the group's members (units_list[i] None: member i sits out; fresh_list, rngs, opt and
         route as there): one sac_recycle_units_many call per 16 members."""
         return recycle_units_many(self.trainers, units_list, fresh_list=fresh_list, rngs=rngs, opt=opt, route=route)
+
+    def shrink_perturb_many(self, nets_list=None, shrink=0.8, perturb=0.2, seeds=None, draws=0, opt=True, targets=False,
+                            init_w=None, b_init=None, route="device"):
+        """shrink_perturb_many over the group's members (nets_list[i] None: member i sits out; the other arguments shared
+        or one per member, as there): one sac_shrink_perturb_many call per 16 members."""
+        return shrink_perturb_many(self.trainers, nets_list, shrink=shrink, perturb=perturb, seeds=seeds, draws=draws,
+                                   opt=opt, targets=targets, init_w=init_w, b_init=b_init, route=route)
 
     def evaluate_many(self, batches, eps=None, rngs=None, rows=False, general="host", stats="host"):
         """evaluate_many over the group's members (general and stats as there)."""

@@ -788,6 +788,215 @@ def recycle_units_many(trainers, units_list, fresh_list=None, rngs=None, opt=Tru
     return recycle_units_of(trainers, units, fresh, bool(opt), route)
 
 
+# ---- whole-network reset and shrink-and-perturb (Nikishin et al. 2022; Ash & Adams 2020) -----------------------------------
+PERTURB_INIT_W = OrderedDict([("policy", 1e-3), ("qf1", 3e-3), ("qf2", 3e-3)])      # the Python constructors' init_w
+_U64 = 0xFFFFFFFFFFFFFFFF
+
+
+def _philox4x32_10(c0, c1, c2, c3, k0, k1):
+    """Philox4x32-10 (csrc/sac_perturb_map.h's philox4x32_10) on uint32-valued uint64 arrays: the four output words."""
+    mask, s32 = np.uint64(0xFFFFFFFF), np.uint64(32)
+    c0, c1, c2, c3, k0, k1 = (np.array(x, np.uint64) & mask for x in np.broadcast_arrays(c0, c1, c2, c3, k0, k1))
+    for _ in range(10):
+        p0, p1 = np.uint64(0xD2511F53) * c0, np.uint64(0xCD9E8D57) * c2
+        c0, c1, c2, c3 = (p1 >> s32) ^ c1 ^ k0, p1 & mask, (p0 >> s32) ^ c3 ^ k1, p0 & mask
+        k0, k1 = (k0 + np.uint64(0x9E3779B9)) & mask, (k1 + np.uint64(0xBB67AE85)) & mask
+    return c0, c1, c2, c3
+
+
+def _sign_uniform(net_id, j, E, seed, draw):
+    """s = 2u - 1 of the E elements of tensor j of net net_id: u = (float32(word >> 8) + 0.5f) * 2^-24, word = output
+    word e & 3 of Philox4x32-10 with counter (e >> 2, j | net_id << 8, draw lo, draw hi), key (seed lo, seed hi)."""
+    q = np.arange((E + 3) // 4, dtype=np.uint64)
+    words = _philox4x32_10(q, j | net_id << 8, draw & 0xFFFFFFFF, draw >> 32, seed & 0xFFFFFFFF, seed >> 32)
+    word = np.stack(words, axis=1).reshape(-1)[:E]
+    u = ((word >> np.uint64(8)).astype(np.float32) + np.float32(0.5)) * np.float32(1.0 / 16777216.0)
+    return (u + u) - np.float32(1.0)
+
+
+def _per_net(value, names, default, what):
+    """A per-net float argument: None (the defaults), one number for every net, or a mapping net -> number."""
+    out = OrderedDict()
+    for net in names:
+        v = default[net] if value is None else value.get(net, default[net]) if hasattr(value, "get") else value
+        if isinstance(v, bool) or not isinstance(v, (int, float, np.integer, np.floating)):
+            raise ValueError(f"{what} is a number or a mapping net -> number, got {v!r} for {net}")
+        out[net] = float(np.float32(v))
+    return out
+
+
+PerturbArgs = namedtuple("PerturbArgs", "nets shrink perturb seed draw opt targets init_w b_init")
+
+
+def check_shrink_perturb(t, nets=None, shrink=0.8, perturb=0.2, seed=None, draw=0, opt=True, targets=False, init_w=None,
+                         b_init=None, caller="shrink_perturb"):
+    """shrink_perturb's arguments, checked before any library call (sac_shrink_perturb's refusals): a PerturbArgs with the
+    selected trained nets in id order, shrink and perturb as float32 values, seed (None: the trainer's noise seed) and
+    draw as 64-bit words, init_w / b_init per selected net as float32 values."""
+    if nets is None:
+        nets = PARAM_TRAINED
+    if isinstance(nets, str):
+        nets = (nets,)
+    nets = tuple(nets)
+    for net in nets:
+        if net not in PARAM_TRAINED or net not in t.NETS:
+            raise ValueError(f"{caller}: {net!r} is not a trained net: one of {PARAM_TRAINED} (a target is written through "
+                             "its trained net with targets=True)")
+    if not nets or len(set(nets)) != len(nets):
+        raise ValueError(f"{caller} needs at least one network, each once")
+    names = tuple(n for n in PARAM_TRAINED if n in nets)
+    with np.errstate(all="ignore"):
+        sh, pe = np.float32(shrink), np.float32(perturb)
+    if not (np.isfinite(sh) and np.isfinite(pe) and sh >= 0 and pe >= 0):
+        raise ValueError(f"{caller}: shrink {shrink!r} and perturb {perturb!r} must be finite float32 values, not negative")
+    if sh == 0 and pe == 0:
+        raise ValueError(f"{caller}: shrink and perturb are both zero")
+    for what, v in (("seed", t.noise_seed if seed is None else seed), ("draw", draw)):
+        if isinstance(v, bool) or not isinstance(v, (int, np.integer)) or not 0 <= int(v) <= _U64:
+            raise ValueError(f"{caller}: {what} is a 64-bit unsigned integer, got {v!r}")
+    with np.errstate(all="ignore"):
+        iw = _per_net(init_w, names, PERTURB_INIT_W, f"{caller}: init_w")
+        bi = _per_net(b_init, names, dict.fromkeys(PARAM_TRAINED, B_INIT_VALUE), f"{caller}: b_init")
+    for net in names:
+        if not (np.isfinite(iw[net]) and iw[net] >= 0):
+            raise ValueError(f"{caller}: init_w of {net} must be finite and not negative, got {iw[net]!r}")
+        if not np.isfinite(bi[net]):
+            raise ValueError(f"{caller}: b_init of {net} must be finite, got {bi[net]!r}")
+    return PerturbArgs(names, float(sh), float(pe), int(t.noise_seed if seed is None else seed), int(draw), bool(opt),
+                       bool(targets), iw, bi)
+
+
+def fresh_params(trainer, net, seed, draw, init_w=None, b_init=None):
+    """The flat float32 vector of FRESH values of a trained net, as k_param_perturb draws them (csrc/sac_perturb_map.h):
+    element e of tensor j of net k (its C id) is
+      hidden weight fc<l>.weight   bound * s, bound = float32(1 / sqrt(N_l))    (networks._Mlp's out-size rule)
+      hidden bias   fc<l>.bias     the constant b_init
+      head weight and head bias    init_w * s
+    with s = 2u - 1 from Philox4x32-10 at counter (e >> 2, j | k << 8, draw), key seed, output word e & 3.  init_w and
+    b_init default to the Python constructors' (1e-3 for a policy, 3e-3 for a Q net; B_INIT_VALUE)."""
+    a = check_shrink_perturb(trainer, (net,), 0.0, 1.0, seed, draw, init_w=init_w, b_init=b_init, caller="fresh_params")
+    k, nh = _lib.NET_IDS[net], len(trainer._hidden(net))
+    out = []
+    for j, (_, shape) in enumerate(trainer.param_tensors(net)):
+        E = int(np.prod(shape))
+        if j < 2 * nh and j & 1:
+            out.append(np.full(E, a.b_init[net], np.float32))
+            continue
+        scale = np.float32(1.0 / np.sqrt(np.float64(shape[0]))) if j < 2 * nh else np.float32(a.init_w[net])
+        out.append(scale * _sign_uniform(k, j, E, a.seed, a.draw))
+    return np.concatenate(out).astype(np.float32)
+
+
+def _shrink_perturb_state(state, trainer, a):
+    """shrink_perturb_reference behind the argument checks (a: PerturbArgs)."""
+    new = dict(params={k: np.array(v, np.float32) for k, v in state["params"].items()},
+               opt={k: (np.array(m, np.float32), np.array(v, np.float32)) for k, (m, v) in state["opt"].items()},
+               scalars=np.array(state["scalars"], np.float64))
+    sh, pe = np.float32(a.shrink), np.float32(a.perturb)
+    for net in a.nets:
+        x = new["params"][net]
+        with np.errstate(all="ignore"):
+            if pe != 0:
+                y = pe * fresh_params(trainer, net, a.seed, a.draw, a.init_w[net], a.b_init[net])
+                if y.size != x.size:
+                    raise ValueError(f"shrink_perturb_reference: {net} holds {x.size} parameters, the trainer's has {y.size}")
+                if sh != 0:
+                    y = sh * x + y
+            else:
+                y = sh * x
+        new["params"][net] = y.astype(np.float32)
+        if a.opt:
+            new["opt"][net] = (np.zeros(x.size, np.float32), np.zeros(x.size, np.float32))
+        tname = param_target(trainer, net) if a.targets else None
+        if tname is not None and tname in new["params"]:
+            new["params"][tname] = new["params"][net].copy()
+    return new
+
+
+def shrink_perturb_reference(state, trainer, nets=None, shrink=0.8, perturb=0.2, seed=None, draw=0, opt=True, targets=False,
+                             init_w=None, b_init=None):
+    """sac_shrink_perturb restated on the flat vectors of SACTrainer._export_state(): a new state (the given one is left
+    alone) in which every element x of a selected trained net is
+      x' = float32(shrink) * x + float32(perturb) * f       each product and the sum rounded to float32 on its own;
+    f = fresh_params' value of the element; a term whose factor is 0 is not formed (shrink == 0: the old value, a NaN too,
+    does not reach the result; shrink != 0: a NaN stays).  With opt, Adam's m and v of the selected nets are +0.0; with
+    targets, the paired target (param_target) is the same bits.  Everything else -- scalars, counters -- is the same bytes."""
+    a = check_shrink_perturb(trainer, nets, shrink, perturb, seed, draw, opt, targets, init_w, b_init, "shrink_perturb_reference")
+    return _shrink_perturb_state(state, trainer, a)
+
+
+def shrink_perturb_of(trainers, args, route_):
+    """shrink_perturb / shrink_perturb_many behind their argument checks: args[i] a PerturbArgs, or None: the member sits
+    out and gets None.  The members without a handle, and all of them under route "host", take their own host route
+    (export, shrink_perturb_reference, import); the others ONE sac_shrink_perturb_many call -- one k_param_perturb launch --
+    per 16 of them, both families and both algorithms mixed.  Returns per member the names of the nets written."""
+    out, served = [None] * len(trainers), []
+    for i, (t, a) in enumerate(zip(trainers, args)):
+        if a is None:
+            continue
+        out[i] = a.nets
+        if t._h is None or route_ == "host":
+            t._shrink_perturb_host(a)
+        else:
+            served.append(i)
+    if not served:
+        return out
+    lib = _lib.load()
+    for c in range(0, len(served), MAX_MEMBERS):
+        ids = served[c:c + MAX_MEMBERS]
+        ios = []
+        for i in ids:
+            a = args[i]
+            iw = [a.init_w.get(n, 0.0) for n in PARAM_TRAINED]
+            bi = [a.b_init.get(n, 0.0) for n in PARAM_TRAINED]
+            flags = (_lib.PERTURB_OPT if a.opt else 0) | (_lib.PERTURB_TARGETS if a.targets else 0)
+            ios.append(_lib.SacPerturbIO(sum(_lib.UNIT_NET_BITS[n] for n in a.nets), flags, a.shrink, a.perturb, a.seed, a.draw,
+                                         (C.c_float * 3)(*iw), (C.c_float * 3)(*bi)))
+        arr = (_lib.SacPerturbIO * len(ids))(*ios)
+        _lib.check(lib.sac_shrink_perturb_many(_handles(trainers, ids), len(ids), arr), "sac_shrink_perturb_many")
+        for i in ids:
+            trainers[i]._settled()
+            if "policy" in args[i].nets:
+                trainers[i]._host_policy_stale = True        # (as _set_params: the holder's arrays are refreshed at their next use)
+    return out
+
+
+def _member_values(value, R, what):
+    """A shared argument, or one per member (a list or tuple of R)."""
+    if isinstance(value, (list, tuple)):
+        if len(value) != R:
+            raise RuntimeError(f"shrink_perturb_many takes one {what} per trainer, or one for all")
+        return list(value)
+    return [value] * R
+
+
+def shrink_perturb_many(trainers, nets_list=None, shrink=0.8, perturb=0.2, seeds=None, draws=0, opt=True, targets=False,
+                        init_w=None, b_init=None, route="device"):
+    """SACTrainer.shrink_perturb for many runs at once.  nets_list: None for the list: every trained net of every trainer;
+    else one selection per trainer, None for a member: it sits out and gets None.  shrink, perturb, seeds, draws, opt,
+    targets, init_w and b_init are shared values or lists with one value per trainer (seeds None: each trainer's noise
+    seed).  The members with a handle are served by ONE sac_shrink_perturb_many call per 16 of them (one k_param_perturb
+    launch: SAC and TD3, the fused kernels' shapes and the general step mixed); the others -- and all of them under
+    route="host" -- by their own host route.  A member's state never depends on its neighbours: it is byte for byte that
+    of its own shrink_perturb.  Returns per member the names of the nets written."""
+    if route not in RECYCLE_ROUTES:
+        raise RuntimeError(f"route must be one of {RECYCLE_ROUTES}, got {route!r}")
+    trainers = list(trainers)
+    R = len(trainers)
+    if nets_list is None:
+        nets_list = [PARAM_TRAINED] * R
+    if len(nets_list) != R:
+        raise RuntimeError("shrink_perturb_many takes one net selection per trainer")
+    if len({id(t) for t in trainers}) != R:
+        raise RuntimeError("a trainer appears twice in shrink_perturb_many")
+    per = [_member_values(v, R, w) for v, w in ((shrink, "shrink"), (perturb, "perturb"), (seeds, "seed"), (draws, "draw"),
+                                                (opt, "opt"), (targets, "targets"), (init_w, "init_w"), (b_init, "b_init"))]
+    args = [None if nets_list[i] is None else
+            check_shrink_perturb(t, nets_list[i], *(v[i] for v in per), caller="shrink_perturb_many")
+            for i, t in enumerate(trainers)]
+    return shrink_perturb_of(trainers, args, route)
+
+
 # ---- evaluation: its statistics -----------------------------------------------------------------------------------------
 def eval_target(rew, term, tq1, tq2, log_pi_next, alpha, reward_scale, discount):
     """k_eval's y in float32 NumPy, operation for operation:

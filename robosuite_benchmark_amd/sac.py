@@ -571,6 +571,61 @@ class SACTrainer:
         units = infer.dormant_units(self.unit_moments(obs, act, nets=nets, general=general), tau)
         return self.recycle_units(units, rng=rng, opt=opt)
 
+    # ---- whole-network reset and shrink-and-perturb --------------------------------------------
+    def _shrink_perturb_host(self, a):
+        """The host route of shrink_perturb (a: infer.PerturbArgs): export, the reference, import -- full-state transfers.
+        Without a handle the state is the saved one, if any, and the holders' own arrays."""
+        if self._h is not None:
+            self._import_state(infer._shrink_perturb_state(self._export_state(), self, a))
+            return
+        st = self._saved_state
+        if st is None:
+            zeros = {k: np.zeros(getattr(self, k).flat().size, np.float32) for k in infer.PARAM_TRAINED}
+            st = dict(params={k: _lib.f32(getattr(self, k).flat()) for k in self.NETS},
+                      opt={k: (z, z.copy()) for k, z in zeros.items()}, scalars=np.zeros(6, np.float64))
+        new = infer._shrink_perturb_state(st, self, a)
+        if self._saved_state is not None:
+            self._saved_state = new
+        for k in self.NETS:
+            getattr(self, k).load_flat(new["params"][k])
+
+    def shrink_perturb(self, nets=None, shrink=0.8, perturb=0.2, seed=None, draw=0, opt=True, targets=False, init_w=None,
+                       b_init=None, route="device"):
+        """Shrink and perturb (Ash & Adams 2020) on the live state: every element x of the trained nets `nets` (None: all of
+        policy, qf1, qf2) becomes shrink * x + perturb * f, each operation rounded to float32 once, f the element's fresh
+        value -- what the constructors would have drawn (hidden weights uniform in +-1/sqrt(N_l), hidden biases b_init,
+        heads uniform in +-init_w), from a Philox stream keyed by (seed, draw): seed None takes the trainer's noise seed,
+        and a caller that wants new values passes a new draw.  A term whose factor is 0 is not formed: shrink=0 clears a
+        NaN or Inf weight, shrink != 0 keeps it.  opt: Adam's m and v of every element written become +0.0; the step
+        counts and bias corrections are NOT reset.  targets: the paired target (target_qf1 / target_qf2, a TD3 trainer's
+        target_policy) receives the same bits; without it targets are left alone and params/* Target Gap jumps.  Scalars,
+        counters, generators and buffers are untouched.
+        route="device": sac_shrink_perturb -- ONE k_param_perturb launch draws and writes in place, both weight copies and
+        the moments where they live, no parameter crosses the link; both step families.  route="host", and a trainer
+        without a handle: export, infer.shrink_perturb_reference, import -- the same bytes.  Returns the nets written."""
+        if route not in infer.RECYCLE_ROUTES:
+            raise RuntimeError(f"route must be one of {infer.RECYCLE_ROUTES}, got {route!r}")
+        a = infer.check_shrink_perturb(self, nets, shrink, perturb, seed, draw, opt, targets, init_w, b_init)
+        return infer.shrink_perturb_of([self], [a], route)[0]
+
+    def reset_networks(self, nets=None, seed=None, draw=0, alpha=False, route="device"):
+        """Periodic reset (Nikishin et al. 2022): shrink_perturb(shrink=0, perturb=1, opt=True, targets=True) -- the trained
+        nets `nets` and their targets take fresh values, Adam's moments +0.0; the replay buffer, the step counts and every
+        counter stay.  alpha=True also puts log_alpha and its two Adam moments back to their initial values (0; alpha 1);
+        a TD3 trainer has no entropy coefficient, and nothing is done for it there."""
+        done = self.shrink_perturb(nets, 0.0, 1.0, seed, draw, True, True, route=route)
+        if alpha and not infer._is_td3(self):
+            if self._h is not None:
+                sc = np.zeros(6, np.float64)
+                _lib.check(self._lib.sac_get_scalars(self._h, _lib.ptr(sc)), "sac_get_scalars")
+                sc[[0, 1, 2]], sc[5] = 0.0, 1.0
+                _lib.check(self._lib.sac_set_scalars(self._h, _lib.ptr(sc)), "sac_set_scalars")
+                self._settled()
+            elif self._saved_state is not None:
+                self._saved_state["scalars"][[0, 1, 2]] = 0.0
+                self._saved_state["scalars"][5] = 1.0
+        return done
+
     # ---- evaluation on held-out transitions --------------------------------------------------
     _evaluate_on_host = False      # private switch: the host path for a fused-shape trainer too (scripts/bench_evaluate.py
                                      # measures the two paths of ONE trainer against each other)

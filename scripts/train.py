@@ -30,7 +30,10 @@
  --td3_replay_eval [N]: --replay_eval for TD3 runs: every epoch, the TD3 objectives on N (bare: 1024) rows of the replay
  buffer, read in place on the device: replay/ columns in progress.csv; TD3 only.  --eval_stats device applies to both.
  --recycle [E] --recycle_tau T: every E-th epoch the T-dormant hidden units of policy, qf1 and qf2 are recycled on the
- device in front of the training block (ReDo): recycle/ columns in progress.csv; SAC and TD3.)
+ device in front of the training block (ReDo): recycle/ columns in progress.csv; SAC and TD3.
+ --reset [E] --reset_shrink S --reset_perturb P: every E-th epoch policy, qf1 and qf2 become S theta + P theta_fresh on
+ the device in front of the training block (the defaults 0 and 1: a periodic reset; 0.8 and 0.2: shrink and perturb),
+ Adam's moments zero, targets alike: the reset/Networks column in progress.csv; SAC and TD3.)
 Runs the variant unchanged (batch size, lrs, tau, period, buffer size ... from the JSON) on the
 HIP library with a synthetic environment of the task's dimensions (robosuite is not installed)."""
 import argparse
@@ -140,6 +143,16 @@ def build_parser():
     ap.add_argument("--recycle_tau", type=float, default=0.025,
                     help="with --recycle: a unit is dormant when its mean activation is at most this share of its "
                          "layer's (the Dormant Fraction of --unit_diagnostics at the same value)")
+    ap.add_argument("--reset", type=int, nargs="?", const=1, default=0, metavar="E",
+                    help="every E-th epoch (the bare flag: every epoch; never epoch 0), in front of the training block, set "
+                         "policy, qf1 and qf2 to reset_shrink * theta + reset_perturb * theta_fresh (a HIP kernel draws the "
+                         "fresh parameters and writes the live state, no parameter copy), zero Adam's moments and give the "
+                         "targets the same values; the replay buffer stays; logs reset/Networks; SAC and TD3; 0 (the "
+                         "default): the run and progress.csv are unchanged")
+    ap.add_argument("--reset_shrink", type=float, default=0.0,
+                    help="with --reset: the factor on the trained parameters (0, the default: a full reset)")
+    ap.add_argument("--reset_perturb", type=float, default=1.0,
+                    help="with --reset: the factor on the fresh parameters (shrink and perturb: 0.8 and 0.2)")
     return ap
 
 
@@ -165,6 +178,8 @@ if __name__ == "__main__":
         option_kw["td3_replay_eval"] = args.td3_replay_eval
     if args.recycle:
         option_kw.update(recycle_period=args.recycle, recycle_tau=args.recycle_tau)
+    if args.reset:
+        option_kw.update(reset_period=args.reset, reset_shrink=args.reset_shrink, reset_perturb=args.reset_perturb)
     if (args.hidden_sweep or args.hidden_sizes) and not args.variants:
         raise SystemExit("--hidden_sweep / --hidden_sizes need --variants")
     if args.variants or args.seeds:
