@@ -138,10 +138,19 @@ def check_f64(name, got, p32, r64, path=None, scale=None, factor=F64_FACTOR, flo
     K, P, R = _np64(got), _np64(p32), _np64(r64)
     assert K.shape == R.shape == P.shape, (name, K.shape, P.shape, R.shape)
     s = float(np.max(np.abs(R))) if scale is None else float(scale)
+    return check_f64_e32(name, K, R, s, float(np.max(np.abs(P - R))) / s if s else 0.0, path, factor, floor)
+
+
+def check_f64_e32(name, got, r64, s, e32, path=None, factor=F64_FACTOR, floor=F64_FLOOR):
+    """The per-tensor rule with the fp32 oracle's error given as a number: s = max|R| (or the tensor's stated scale) and
+    e32 = max|P - R| / s, computed when R was (check_f64: now; a frozen fixture: when it was written, over the whole
+    tensor, of which `got` and `r64` may be the same sample).  Returns the kernel's error."""
+    K, R = _np64(got), _np64(r64)
+    assert K.shape == R.shape, (name, K.shape, R.shape)
     if s == 0.0:
         assert np.all(K == 0.0), f"{name}: the float64 reference is exactly 0, the kernel has max|K| = {np.max(np.abs(K)):.3g}"
         return 0.0
-    eK, eP = float(np.max(np.abs(K - R))) / s, float(np.max(np.abs(P - R))) / s
+    eK, eP = float(np.max(np.abs(K - R))) / s, float(e32)
     if path is not None and eK >= F64_ERRORS.get(path, (0.0,))[0]:
         F64_ERRORS[path] = (eK, name, eP)
     bound = max(factor * eP, floor)
@@ -229,13 +238,21 @@ def _row_quantities(o, td3):
 
 def check_diag_f64(diag, names, want32, want64, o64, path):
     """Every diagnostic of one step: a statistic at the scale of its rows, Alpha / Alpha Loss at their own."""
-    scales = _row_quantities(o64, hasattr(o64, "target_policy"))
+    scales = diag_scales(want64, o64)
     for i, name in enumerate(names):
         if name not in want64:
             continue
+        check_f64(name, [diag[i]], [want32[name]], [want64[name]], path, scale=scales[name])
+
+
+def diag_scales(want64, o64):
+    """{diagnostic: its scale}: a statistic's is the largest |.| of the rows it summarises, Alpha's / Alpha Loss's their own."""
+    scales = _row_quantities(o64, hasattr(o64, "target_policy"))
+    out = {}
+    for name in want64:
         quantity = name.rsplit(" ", 1)[0] if name.rsplit(" ", 1)[-1] in ("Mean", "Std", "Max", "Min") else name
-        s = scales.get(quantity, abs(want64[name]))
-        check_f64(name, [diag[i]], [want32[name]], [want64[name]], path, scale=s)
+        out[name] = scales.get(quantity, abs(want64[name]))
+    return out
 
 
 def check_step_f64(hip, o32, o64, diag, want32, want64, path=None, skip_rows=()):
